@@ -21,9 +21,9 @@
 
 thread_local Profiler* g_prof = nullptr;
 
-// A handle of several stream groups drives two HIP streams per group (front end + LaserMapping); the runtime's default of 4 hardware
-// queues makes pairs of them share a queue and serialise.  The host process exports GPU_MAX_HW_QUEUES=16 before its first HIP call
-// (bench.py, tests/conftest.py, binding.py do; include/alego_mi355x.h documents it) — the library does not touch the environment.
+// A handle of several stream groups drives two HIP streams per group (front end + LaserMapping); the HIP runtime maps them onto the
+// process's hardware queues, so streams may share a queue and serialise.  How many queues a process opens is the host's setting
+// (include/alego_mi355x.h) — the library does not touch the environment.
 
 void launch_ip(const DevCtx& d, int ring_pos, bool want_labels, hipStream_t st);
 void launch_fe(const DevCtx& d, hipStream_t st);

@@ -13,8 +13,13 @@ same place.  A "step" advances every resident stream by one scan (ImageProjectio
 LaserMapping on every 2nd scan); inputs are in HBM before the timed region.  One process per GPU; streams are independent
 (no data-path collective), so N GPUs run N x `--streams` streams: weak scaling.  Rank 0 prints one JSON line.
 
-The CPU legs (rank 0, N = 1) run the oracle on exactly the scan sequence of stream 0 (cpu_seq, cpu_pipe3) and of
-streams 0..C-1 (cpu_replicas), BASELINE.md §2.
+The default run is the timed region and a short HIP-event pass for the kernel table, so its length follows --steps.  `--full`
+adds the reports that take minutes: the CPU legs (rank 0, N = 1) run the oracle on exactly the scan sequence of stream 0
+(cpu_seq, cpu_pipe3) and of streams 0..C-1 (cpu_replicas); timed_handle_check; the isolated-kernel pass; the
+`configs` block.
+
+`--dump-outputs DIR` writes what the last timed step computed (dump_outputs) as DIR/<name>.npy: the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 """
 import argparse
 import contextlib
@@ -28,8 +33,6 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-# two HIP streams per stream group (front end + LaserMapping) + RCCL's own: the runtime's default of 4 hardware queues would alias them
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 from alego_loader import load_package  # noqa: E402
 
 load_package()
@@ -39,6 +42,7 @@ from alego_amd import dist as D  # noqa: E402
 HBM_PEAK = 8.0e12  # B/s, MI355X spec (MI355X_MICROARCH.md)
 LAP = 560          # scans per T0 lap
 PMC_ROUNDS = ("r06", "r05", "r04")   # the newest committed --pmc passes of a workload are used
+PROFILE_STEPS = 20   # steps of the HIP-event passes after the timed region: two events per launch, so they do not grow with --steps
 
 
 def _pmc_path(stem):
@@ -252,6 +256,47 @@ def timed_handle_check(h, p, bags, B, total_steps, device, oracle_map_t=None, pe
         h1.close()
     return dict(slots=len(slots), slot_ids=slots, stream_groups=groups, slots_per_group=per, steps_replayed=total_steps, arrays=list(CHECK_ARRAYS) + ["odom pose", "LM params_ / pose", "flags"],
                 bit_equal=not bad and not truncated, differing_slots=bad, capacity_errors=truncated, stream0_vs_oracle=vs_oracle)
+
+
+DUMP_BUDGET = 64 << 20   # bytes --dump-outputs may write
+DUMP_SLOTS = 8           # slots whose clouds are written (a seeded sample)
+DUMP_ROWS = 65536        # rows per cloud at most (a seeded sample of a larger cloud, in its order)
+
+
+def dump_outputs(h, n_slots, out_dir, seed=0):
+    """--dump-outputs: what the last timed step left for a caller of the batch path, as float32 / float64 arrays in `out_dir`/<name>.npy.
+    Every slot: the value alego_batch_get_pose returns (`flags`; -1 where it reports an error, the poses are then NaN) and both poses
+    (`odom_*`, `map_*`: t, q = w x y z, params_).  A seeded sample of DUMP_SLOTS slots (`cloud_slots`): the clouds timed_handle_check
+    compares, `slot<s>_<name>`.  Inputs are seeded, so two builds run with the same arguments can be compared file by file."""
+    out = {"flags": np.full(n_slots, -1.0)}
+    for w in ("odom", "map"):
+        for k, n in (("t", 3), ("q", 4), ("params", 6)):
+            out[f"{w}_{k}"] = np.full((n_slots, n), np.nan)
+    for s in range(n_slots):
+        try:
+            f, odom, mp = h.batch_get_pose(s)
+        except binding.AlegoError:
+            continue
+        out["flags"][s] = f
+        for w, pose in (("odom", odom), ("map", mp)):
+            for k in ("t", "q", "params"):
+                out[f"{w}_{k}"][s] = pose[k]
+    slots = np.sort(np.random.default_rng(seed).choice(n_slots, min(DUMP_SLOTS, n_slots), replace=False))
+    out["cloud_slots"] = slots.astype(np.float64)
+    for s in slots.tolist():
+        for name in CHECK_ARRAYS:
+            a = h.debug_get(name, slot=s)
+            a = a if a.dtype == np.float32 else a.astype(np.float64)
+            if a.shape[0] > DUMP_ROWS:
+                a = a[np.sort(np.random.default_rng((seed, s)).choice(a.shape[0], DUMP_ROWS, replace=False))]
+            out[f"slot{s}_{name}"] = a
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_BUDGET:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_BUDGET}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    print(f"bench.py: {len(out)} arrays, {total} bytes -> {out_dir}", file=sys.stderr)
 
 
 class env_override:
@@ -621,6 +666,8 @@ def main():
                     help="BASELINE config 5: every rank replays the SAME streams and each scan-to-map registration is split over the ranks "
                          "(alego_dist_init: query slices + one ncclAllReduce of the normal equations per solver evaluation); strong scaling")
     ap.add_argument("--scan-flags", type=int, default=0, help="synthetic scan generator flags (synth.cpp): 1 azimuth jitter +-0.45 column, 2 NaN returns, 4 azimuth uniform over the column")
+    ap.add_argument("--full", action="store_true", help="also run the reports that take minutes whatever --steps is: the CPU legs (cpu_baseline, parity, single "
+                                                        "stream), timed_handle_check, the isolated-kernel pass and the `configs` block; --no-* below skips one of them")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("--no-check", action="store_true", help="skip timed_handle_check (slots of the timed handle against one-slot replicas)")
@@ -629,15 +676,14 @@ def main():
                                                               "bit for bit; always on at N > 1 (--no-self-check turns it off)")
     ap.add_argument("--no-self-check", action="store_true")
     ap.add_argument("--no-configs", action="store_true", help="skip the `configs` block (BASELINE.json's other single-GPU configurations, each timed as a line of its own)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps write what the last one computed (rank 0's streams: every pose, "
+                                                          "the clouds of a seeded sample of slots) as DIR/<name>.npy, float32 / float64")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank, local, world = D.env()
     use_dist = world > 1 or bool(os.environ.get("ALEGO_BENCH_FORCE_DIST") and "RANK" in os.environ)   # (second form: the launcher path at N = 1, for testing)
-    if use_dist:
-        # An RCCL communicator brings HIP streams of its own.  With the runtime's default of 4 hardware queues they alias with the
-        # handle's 4 stream groups, two of which then share a queue and serialise: 293 k instead of 329 k scans/s with the communicator
-        # merely alive (measured at N = 1 under the launcher; 8 queues: 329.7 k).  Must be set before the HIP runtime initialises.
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X: there is no CPU fallback for the product path")
@@ -685,6 +731,8 @@ def main():
     step += args.steps
     dt_local = dt
     dt = D.max_over_ranks(dt, dist, device="cuda")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(h, B, args.dump_outputs)   # before the profile pass below advances the streams further
     sample = range(0, B, max(1, B // 64))
     cs = [h.batch_get_counts(s) for s in sample]
     counts = {k: int(round(float(np.mean([c[k] for c in cs])))) for k in cs[0]}      # mean over a sample of streams (they are at different places)
@@ -718,12 +766,13 @@ def main():
     rebuilds0 = sum(h.batch_get_counts(s)["n_rebuild"] for s in range(B))
 
     roof, kern, rebuilds, per, groups = None, None, 0, B, 1
+    prof_steps = min(args.steps, PROFILE_STEPS)
     if rank == 0 and not args.no_profile:
-        # per-kernel durations with HIP events on the handle's streams, over another K steps.  One launch covers one
+        # per-kernel durations with HIP events on the handle's streams, over another min(K, PROFILE_STEPS) steps.  One launch covers one
         # stream group (`per` streams); the groups run concurrently, exactly as in the timed region.
         groups, per = h.stream_groups()
         h.profile_enable(True)
-        h.batch_run(step, args.steps, stages); step += args.steps
+        h.batch_run(step, prof_steps, stages); step += prof_steps
         rep = h.profile_report()
         h.profile_enable(False)
         kern = kernel_table(rep)
@@ -783,25 +832,25 @@ def main():
         if kern is not None:
             out["kernels"] = kern
         omt = None
-        if world == 1 and not args.no_cpu:
+        if world == 1 and args.full and not args.no_cpu:
             out.update(single_stream(p, bags[0], local, args.prime, max(args.steps, 200)))
             out["cpu_baseline"], out["parity"], omt = cpu_legs(p, bags, args.prime, device=local, n_streams=B)
-        if not args.no_check and not shard:
+        if args.full and not args.no_check and not shard:
             out["timed_handle_check"] = timed_handle_check(h, p, bags, B, step, local, omt)
     h.close()
-    if rank == 0 and world == 1 and not shard and not args.no_configs and not args.no_cpu and args.geometry.lower() == "16x1800" and args.keyframes == 0:
+    if rank == 0 and world == 1 and not shard and args.full and not args.no_configs and not args.no_cpu and args.geometry.lower() == "16x1800" and args.keyframes == 0:
         single = {k: out[k] for k in ("single_stream_scans_per_s", "single_stream_serial_scans_per_s", "single_stream_note") if k in out}
         out["configs"] = all_configs(args, p, bags, local, kern, per, single if len(single) == 3 else None, out.get("cpu_baseline"))
     if rank == 0 and kern is not None:
         # the same launch shape (`per` streams per launch) ALONE on the chip: one stream group, nothing else resident
         iso = None
-        if not args.no_isolated and groups > 1:
+        if args.full and not args.no_isolated and groups > 1:
             with env_override("ALEGO_STREAM_GROUPS", "1"):
                 hi = binding.Handle(p, device=local, n_slots=per, ring_len=1)
             setup_replay(hi, bags, per)
             hi.batch_run(0, args.prime + args.warmup, stages)
             hi.profile_enable(True)
-            hi.batch_run(args.prime + args.warmup, args.steps, stages)
+            hi.batch_run(args.prime + args.warmup, prof_steps, stages)
             iso = kernel_table(hi.profile_report())
             hi.close()
             out["kernels_isolated"] = {k: v["avg_us"] for k, v in iso.items()}   # one stream group alone on the chip: every launch by itself

@@ -133,8 +133,8 @@ int alego_batch_load(alego_handle* h, int slot, int ring_pos, const alego_point*
  * last scans may still be in flight on the stream groups' second ("back") HIP streams when the call returns: every entry point that
  * touches LaserOdometry / LaserMapping state waits for it first (per-slot calls for their own group, alego_lo_process /
  * alego_lm_process / alego_stream_run / alego_dist_init / alego_dist_shutdown for all groups); alego_batch_load, which only writes the
- * input ring, does not.  A handle of G stream groups drives 2 G HIP streams: export GPU_MAX_HW_QUEUES=16 in the host process before
- * its first HIP call (the runtime's default of 4 hardware queues makes pairs of streams serialise); the library never sets it. */
+ * input ring, does not.  A handle of G stream groups drives 2 G HIP streams; the HIP runtime maps them onto the process's hardware
+ * queues, and streams that share a queue serialise.  The number of queues is the host's setting; the library never sets it. */
 int alego_batch_run(alego_handle* h, int first_pos, int n_scans, int stages, int sync);
 int alego_synchronize(alego_handle* h);
 /* OR into `stages` of alego_batch_run: replay the resident ring back and forth (0..R-1,R-2..0,1..)

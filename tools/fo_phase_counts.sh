@@ -1,7 +1,8 @@
 # VALU / SALU / LDS instructions of fe_ring_out by phase: libraries built with -DFO_STOP_AFTER=<tick> stop every ring after that phase; the differences
 # between consecutive stops are the phases.  usage (GPU box): bash tools/fo_phase_counts.sh   (after: for k in 1 2 3 12 4 5 13 7; do
 #   ALEGO_EXTRA_FLAGS=-DFO_STOP_AFTER=$k ALEGO_BUILD_DIR=build_s$k ALEGO_SO=libalego_s$k.so bash a-lego-loam_amd/build.sh; done)
-cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
+ROOT=$(cd "$(dirname "$0")/.." && pwd)   # the repository this script belongs to
+cd /tmp && export TMPDIR=/tmp; cd "$ROOT"
 for k in 1 2 3 12 4 5 13 7 full; do
   lib=$PWD/a-lego-loam_amd/libalego_s$k.so; [ $k = full ] && lib=$PWD/a-lego-loam_amd/libalego_mi355x.so
   rm -rf /tmp/fo_pc

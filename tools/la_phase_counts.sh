@@ -3,7 +3,8 @@
 # Build first:  for k in 1 4 5 6 7; do ALEGO_EXTRA_FLAGS=-DLA_STOP_AFTER=$k ALEGO_BUILD_DIR=build_la$k ALEGO_SO=libalego_la$k.so bash a-lego-loam_amd/build.sh; done
 # usage (GPU box): bash tools/la_phase_counts.sh [streams] [geometry] [keyframes]      IP + FE + LO only (stages 3)
 B=${1:-512}; GEO=${2:-16x1800}; KF=${3:-0}
-cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
+ROOT=$(cd "$(dirname "$0")/.." && pwd)   # the repository this script belongs to
+cd /tmp && export TMPDIR=/tmp; cd "$ROOT"
 for k in 1 4 5 6 7 full; do
   lib=$PWD/a-lego-loam_amd/libalego_la$k.so; [ $k = full ] && lib=$PWD/a-lego-loam_amd/libalego_mi355x.so
   rm -rf /tmp/la_pc
