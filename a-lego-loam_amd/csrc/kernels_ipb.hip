@@ -166,7 +166,10 @@ __global__ void __launch_bounds__(IPB_TW) ipb_band(DevCtx d, int ring_pos, int k
   }
   IPB_TICK(1);
   const u64 act = filled & ~ground;
-  s_a[tid] = have ? act : 0ull;
+  // s_a[0 .. TW - 1]: one slot per column, written by its own thread; s_a[TW]: the halo column, written ONLY by lane 0 of wave 0 below.  In a
+  // partial last band thread TW owns no column and must not touch slot TW: it may sit in another wavefront, so without a barrier between the two
+  // stores either could land last (a 0 there drops every right-edge across the seam).  Readers: s_a[min(tid + 1, TW)], never above TW
+  if (have) s_a[tid] = act;
   if (lane == 0) {
 #pragma unroll
     for (int row = 0; row < 64; ++row) s_first[wave][row] = rng[row];
@@ -216,7 +219,7 @@ __global__ void __launch_bounds__(IPB_TW) ipb_band(DevCtx d, int ring_pos, int k
   if (H <= 1) ex = 0;
   IPB_TICK(3);
   const u64 rs = act & ~(ey << 1);   // run starts: active cells the cell below has no down-edge to
-  s_y[tid] = ey; s_rs[tid] = rs;
+  s_y[tid] = ey; s_rs[tid] = rs;   // (one writer per slot; read as [tid + 1] only when tid + 1 < TW)
   for (u64 m = rs; m; m &= m - 1) { const int r = __ffsll((long long)m) - 1; par[r * IPB_TW + tid] = (uint16_t)(r * IPB_TW + tid); }
   __syncthreads();
   IPB_TICK(4);

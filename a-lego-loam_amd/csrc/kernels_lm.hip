@@ -1037,14 +1037,15 @@ DEV_INLINE void lm_shard_next_outer_dev(const LmCtx& L, int slot);
 // pre (round 6: what used to be separate one-thread-per-slot launches between two evaluations runs at the head of the next evaluation's own workgroup, so an
 // evaluation is ONE launch around its all-reduce instead of two or three):  LM_PRE_PACK = lm_shard_pack (the first evaluation of a frame), LM_PRE_STEP_FIRST /
 // LM_PRE_STEP = lm_shard_step on the sums the all-reduce has just delivered, LM_PRE_STEP_NEXT = that step followed by lm_shard_next_outer (the first evaluation of
-// a further outer iteration).  A workgroup is one slot: its thread 0 does exactly what the slot's thread of the separate launch did.
-enum { LM_PRE_NONE = 0, LM_PRE_PACK, LM_PRE_STEP_FIRST, LM_PRE_STEP, LM_PRE_STEP_NEXT };
+// a further outer iteration); LM_PRE_STEP_FIRST_NEXT = the same when the sums are those of the evaluation at params_ (lm_max_iters = 0: the inner loop was empty, so
+// the step that closes the outer iteration is its first one, lm_begin included, as in lm_solve).  A workgroup is one slot: its thread 0 does exactly what the slot's thread of the separate launch did.
+enum { LM_PRE_NONE = 0, LM_PRE_PACK, LM_PRE_STEP_FIRST, LM_PRE_STEP, LM_PRE_STEP_NEXT, LM_PRE_STEP_FIRST_NEXT };
 __global__ void __launch_bounds__(LM_SOLVE_T) lm_shard_eval(DevCtx d, LmCtx L, int which, int pre) {
   const int slot = blockIdx.x + d.slot0;
   if (pre == LM_PRE_PACK) lm_shard_pack_dev(d, L, slot);
   else if (pre != LM_PRE_NONE && threadIdx.x == 0) {
-    lm_shard_step_dev(d, L, slot, pre == LM_PRE_STEP_FIRST ? 1 : 0);
-    if (pre == LM_PRE_STEP_NEXT) lm_shard_next_outer_dev(L, slot);
+    lm_shard_step_dev(d, L, slot, (pre == LM_PRE_STEP_FIRST || pre == LM_PRE_STEP_FIRST_NEXT) ? 1 : 0);
+    if (pre == LM_PRE_STEP_NEXT || pre == LM_PRE_STEP_FIRST_NEXT) lm_shard_next_outer_dev(L, slot);
   }
   if (pre != LM_PRE_NONE) { __threadfence_block(); __syncthreads(); }   // (the control words, the candidate and the packed rows are read back by the whole workgroup)
   const int* ctl = L.shard_ctl + (size_t)slot * 8;
@@ -1158,15 +1159,16 @@ int launch_lm_register(const DevCtx& d, const LmCtx& L, hipStream_t st, int (*al
     const dim3 g1((d.n_launch + 63) / 64), b1(64);
     // per evaluation ONE launch + the all-reduce (round 6; before: pack | eval, all-reduce, step | next_outer as separate launches — 86 launches per mapping frame,
     // now 43): the step on the sums of evaluation k runs at the head of evaluation k + 1's workgroups, a last stand-alone step closes the frame
+    const int pre_next = d.P.lm_max_iters <= 0 ? (int)LM_PRE_STEP_FIRST_NEXT : (int)LM_PRE_STEP_NEXT;   // (the evaluation before it: at params_ when the inner loop is empty)
     for (int outer = 0; outer < d.P.lm_outer_iters; ++outer) {
-      ALEGO_LAUNCH(lm_shard_eval, dim3(d.n_launch), dim3(LM_SOLVE_T), LM_SOLVE_RED_BYTES, st, d, L, 0, outer == 0 ? (int)LM_PRE_PACK : (int)LM_PRE_STEP_NEXT);
+      ALEGO_LAUNCH(lm_shard_eval, dim3(d.n_launch), dim3(LM_SOLVE_T), LM_SOLVE_RED_BYTES, st, d, L, 0, outer == 0 ? (int)LM_PRE_PACK : pre_next);
       if (int rc = allreduce(ar_ctx, part, cnt, st)) return rc;
       for (int it = 0; it < d.P.lm_max_iters; ++it) {
         ALEGO_LAUNCH(lm_shard_eval, dim3(d.n_launch), dim3(LM_SOLVE_T), LM_SOLVE_RED_BYTES, st, d, L, 1, it == 0 ? (int)LM_PRE_STEP_FIRST : (int)LM_PRE_STEP);
         if (int rc = allreduce(ar_ctx, part, cnt, st)) return rc;
       }
     }
-    ALEGO_LAUNCH(lm_shard_step, g1, b1, 0, st, d, L, d.P.lm_max_iters == 0 ? 1 : 0);
+    ALEGO_LAUNCH(lm_shard_step, g1, b1, 0, st, d, L, d.P.lm_max_iters <= 0 ? 1 : 0);
   } else {
   ALEGO_LAUNCH(lm_solve, dim3(d.n_launch), dim3(LM_SOLVE_T), LM_SOLVE_RED_BYTES + L.solve_row_bytes, st, d, L);
   }

@@ -430,7 +430,7 @@ def test_batch_slots_independent(params_a):
     hb.close()
 
 
-@pytest.mark.parametrize("geom", [(64, 2048), (40, 1800)])
+@pytest.mark.parametrize("geom", [(64, 2048), (40, 1800), (64, 4000), (48, 1000)])
 def test_band_path_in_a_batch_equals_the_seven_kernel_path(geom, monkeypatch):
     """The banded ImageProjection (kernels_ipb.hip) in a batch launch — several slots per launch, no images kept, statistics entries re-zeroed scan after
     scan — against one-slot handles on the seven-kernel path (ALEGO_IP_BAND=0) over 6 scans: segmented cloud, cloud_info arrays, outliers, ring indices and the
@@ -480,6 +480,105 @@ def test_band_path_on_edge_case_scans(geom):
     for name, pts in seq:
         _ip_compare(h, o, np.ascontiguousarray(pts, np.float32), f"{geom} {name}")
     h.close()
+
+
+def _seam_wall(p, rows, rng_m, w=10):
+    """Points at the cell centres of `rows` x the w columns either side of the wrap-around seam (columns H-w .. H-1, 0 .. w-1), all at
+    range rng_m: one component that exists only across the seam.  Two rows of 2w columns are feasible (>= seg_big_num = 30 cells); either
+    half alone (2 rows, w cells each) is not, so an image that loses the right-edges from column H-1 to column 0 drops the wall."""
+    H = p.horizon_scan
+    cols = np.r_[H - w:H, 0:w].astype(np.float64)
+    out = []
+    for r in rows:
+        va = np.radians(r * p.ang_res_y - p.ang_bottom)                        # row = round((va + ang_bottom) / ang_res_y)
+        az = np.radians(360.0 - (cols + 0.5) * p.ang_res_x)                    # column = floor((360 - azimuth) / ang_res_x)
+        out.append(np.stack([rng_m * np.cos(va) * np.cos(az), rng_m * np.cos(va) * np.sin(az), np.full_like(az, rng_m * np.sin(va)), np.zeros_like(az)], 1))
+    return np.concatenate(out).astype(np.float32)
+
+
+def _crosses_wrap_seam(p, label_img):
+    """a segment (feasible label) that holds cells in both column H-1 and column 0 of one row"""
+    lab = label_img.reshape(p.n_scan, p.horizon_scan)
+    a, b = lab[:, -1], lab[:, 0]
+    return bool(np.any((a == b) & (a > 0) & (a < 999999)))
+
+
+def _slots_that_fit(p, want):
+    """`want` slots, or the largest multiple of 4 whose handle takes at most 3/4 of the free device memory (measured on a 4-slot handle,
+    which also carries the small-handle map buffers: an over-estimate per slot)"""
+    import ctypes
+    import ctypes.util
+    hip = ctypes.CDLL(ctypes.util.find_library("amdhip64") or "libamdhip64.so")
+
+    def free_bytes():
+        free, total = ctypes.c_size_t(), ctypes.c_size_t()
+        assert hip.hipMemGetInfo(ctypes.byref(free), ctypes.byref(total)) == 0
+        return free.value
+    h = binding.Handle(p, n_slots=4, ring_len=1)   # (the device is current from here on)
+    free1 = free_bytes()
+    h.close()
+    free0 = free_bytes()
+    per4 = max(free0 - free1, 1)
+    return max(4, min(want, 4 * int(0.75 * free0 // per4)))
+
+
+@pytest.mark.parametrize("geom", [(64, 4000), (48, 1000), (24, 320), (17, 70), (64, 2048)])
+def test_band_path_under_load_at_partial_band_widths(geom):
+    """The banded ImageProjection in the handle shape bench.py times — up to 1024 slots in the default four stream groups replaying HBM-resident
+    bags from staggered start scans, every CU busy — at widths whose last band is partial (64x4000: 160 columns, 48x1000: 232, 24x320: 64,
+    17x70: one band of 70) and at 64x2048 (full bands).  In a partial band the halo column (the wrap-around column 0) lands in LDS slot TW
+    of ipb_band, next to threads that own no column: a race on that slot loses the right-edges across the seam only when the waves of a
+    workgroup run far apart, i.e. under load (the ip_front halo race).  Every scan carries a wall that is one segment only
+    across the wrap-around seam (_seam_wall; one bag with ranges quantised to 0.5 m on top), so a lost seam edge changes the segmented cloud.
+    ImageProjection keeps no state from scan to scan: EVERY slot's outputs are compared bit for bit with the oracle's for the scan it
+    processed last.  Two passes on fresh handles."""
+    p = synth.default_params(*geom)
+    p.recent_keyframe_num, p.kf_cap_surf, p.kf_cap_outlier = 1, 1024, 1024   # (IP only: the mapping buffers are not used)
+    n_bags, bag_len, steps = 4, 6, 5
+    n_slots = _slots_that_fit(p, 1024)
+    print(f"{geom}: {n_slots} slots")
+    rows = (p.n_scan - 4, p.n_scan - 3)
+    bags = []
+    for b in range(n_bags):
+        scans = []
+        for k in range(bag_len):
+            pts = synth.scan(p, 3 * k + 1, stream=b)
+            if b == n_bags - 1:   # ranges quantised to 0.5 m: huge components across every band seam
+                r = np.linalg.norm(pts[:, :3], axis=1)
+                pts[:, :3] *= (np.maximum(np.round(r * 2) / 2, 0.5) / np.maximum(r, 1e-6))[:, None]
+            wall = _seam_wall(p, rows, 1.5 + 0.25 * b + 0.1 * k)   # (last: the last writer of a cell wins; a scan holds at most n_scan x horizon_scan points)
+            scans.append(np.ascontiguousarray(np.concatenate([pts[:p.n_scan * p.horizon_scan - len(wall)], wall]), np.float32))
+        bags.append(scans)
+    names = ("seg_cloud", "seg_col", "seg_range", "seg_ground", "outlier", "ring_start", "ring_end")
+    ref = {}
+    for b in range(n_bags):
+        o = O.Oracle(p)
+        for k in range(bag_len):
+            o.ip(bags[b][k])
+            ref[b, k] = {n: o.get(n).copy() for n in names}
+            ref[b, k]["crosses"] = _crosses_wrap_seam(p, o.get("label_img"))
+    src = lambda s: (s % n_bags, ((s // n_bags) * 5) % bag_len)
+    last = lambda s: (src(s)[0], (src(s)[1] + steps - 1) % bag_len)
+    assert any(ref[last(s)]["crosses"] for s in range(n_slots)), "no slot's last scan has a segment across the wrap-around column"
+    N = p.n_scan * p.horizon_scan
+    cap = dict(seg_cloud=N * 16, outlier=N * 16, ring_start=p.n_scan * 4, ring_end=p.n_scan * 4)
+    for rep in range(2):
+        hb = binding.Handle(p, n_slots=n_slots, ring_len=1)
+        groups, per = hb.stream_groups()
+        assert groups == 4, (groups, per)
+        hb.replay_create(n_bags, bag_len)
+        for b in range(n_bags):
+            for k in range(bag_len):
+                hb.replay_load(b, k, bags[b][k])
+        for s in range(n_slots):
+            hb.replay_assign(s, *src(s))
+        hb.batch_run(0, steps, 1 | binding.REPLAY_BAG, sync=False)
+        hb.synchronize()
+        for s in range(n_slots):
+            want = ref[last(s)]
+            for n in names:
+                assert_bit_equal(hb.debug_get(n, slot=s, cap_bytes=cap.get(n, N * 4) + 64), want[n], f"{geom} pass {rep} slot {s} (bag, scan) {last(s)} {n}")
+        hb.close()
 
 
 @pytest.mark.parametrize("geom", [(32, 1024), (40, 1800), (24, 320), (64, 1024)])
@@ -600,8 +699,8 @@ def _random_params(seed):
     p.recent_keyframe_num = int(rng.integers(1, 7))
     p.min_keyframe_dist = float(rng.choice([0.01, 0.04, 0.09, 0.25]))
     p.lm_every = int(rng.integers(1, 4))
-    p.lm_outer_iters = int(rng.integers(1, 3))
-    p.lm_max_iters = int(rng.integers(4, 21))
+    p.lm_outer_iters = int(rng.integers(1, 4))
+    p.lm_max_iters = int(rng.integers(0, 3)) if rng.random() < 0.4 else int(rng.integers(0, 21))   # weight on the budgets 0 - 2
     p.lm_leaf_corner = float(rng.choice([0.2, 0.4, 0.6]))
     p.lm_leaf_surf = float(rng.choice([0.4, 0.8, 1.2]))
     p.lm_leaf_outlier = float(rng.choice([0.5, 1.0]))
@@ -1787,6 +1886,92 @@ def test_sharded_registration_single_rank_equals_fused_solver(params_a):
     _, _, ma = ha.scan_process(synth.scan(p, 24), stages=7)
     assert_bit_equal(mb["params"], ma["params"], "after alego_dist_shutdown")
     ha.close(); hb.close()
+
+
+@pytest.mark.parametrize("mods", [{}, dict(lm_outer_iters=3, lm_max_iters=0)])
+def test_sharded_registration_in_a_3_slot_batch_equals_fused_solver(params_a, mods):
+    """The sharded kernel sequence (world = 1) over a launch of three slots — lm_shard_eval / lm_shard_step index their state by
+    d.slot0 + block / thread and all-reduce the partials of all slots of the launch in one collective — against a 3-slot handle on the
+    fused solver, step by step: every slot's LM params_, map pose, solver summaries and per-outer-iteration params_ / costs bit for bit."""
+    p = params_a.copy()
+    for k, v in mods.items():
+        setattr(p, k, v)
+    nslot, nscan = 3, 20
+    ha, hb = binding.Handle(p, n_slots=nslot, ring_len=nscan), binding.Handle(p, n_slots=nslot, ring_len=nscan)
+    hb.dist_init(0, 1, binding.dist_unique_id())
+    for s in range(nslot):
+        for k in range(nscan):
+            pts = synth.scan(p, k, stream=s)
+            ha.batch_load(s, k, pts)
+            hb.batch_load(s, k, pts)
+    optimised = 0
+    for k in range(nscan):
+        ha.batch_run(k, 1, stages=7)
+        hb.batch_run(k, 1, stages=7)
+        for s in range(nslot):
+            _, _, ma = ha.batch_get_pose(s)
+            _, _, mb = hb.batch_get_pose(s)
+            tag = f"{mods} scan {k} slot {s}"
+            assert_bit_equal(mb["params"], ma["params"], f"{tag} LM params_")
+            assert_bit_equal(mb["t"], ma["t"], f"{tag} map translation")
+            ia, ib = ha.debug_get("lm_info", slot=s), hb.debug_get("lm_info", slot=s)
+            assert_bit_equal(ib[6:12], ia[6:12], f"{tag} correspondences / solver summaries")
+            assert_bit_equal(hb.debug_get("lm_state", slot=s)[27:43], ha.debug_get("lm_state", slot=s)[27:43], f"{tag} params_ per outer iteration and costs")
+            optimised += int(ia[11])
+    assert optimised >= 3 * nslot, f"only {optimised} optimised mapping frames"
+    hb.dist_shutdown()
+    ha.close(); hb.close()
+
+
+@pytest.mark.parametrize("outer,inner,lo_surf,lo_corner", [(1, 0, 0, 1), (2, 0, 1, 0), (3, 0, 0, 0), (2, 1, 1, 1), (3, 2, 1, 0), (1, 1, 0, 1), (3, 20, 5, 5)])
+def test_solver_iteration_budget_edges(outer, inner, lo_surf, lo_corner, monkeypatch):
+    """LaserMapping's solver budgets at their edges — lm_max_iters = 0 (ceres::Solve evaluates the cost and returns), 1, 2, and
+    lm_outer_iters = 1 - 3 — on every solver path: the fused lm_solve, the sharded kernel sequence (alego_dist_init, world = 1: one launch
+    per evaluation, the trust-region step at the head of the next evaluation) and lm_solve with every row read from HBM (ALEGO_LM_ROW_LDS=0).
+    Teacher-forced against the oracle (_lm_compare: accepted queries, summaries, params_ per outer iteration, pose), and the three handles
+    against each other bit for bit.  LaserOdometry's budgets ride along: lo_iters_surf / lo_iters_corner of 0 and 1 (params_ at 1e-7,
+    equal solver summaries)."""
+    p = synth.default_params(16, 1800)
+    p.lm_outer_iters, p.lm_max_iters = outer, inner
+    p.lo_iters_surf, p.lo_iters_corner = lo_surf, lo_corner
+    hf = binding.Handle(p)
+    hs = binding.Handle(p)
+    hs.dist_init(0, 1, binding.dist_unique_id())
+    monkeypatch.setenv("ALEGO_LM_ROW_LDS", "0")
+    hh = binding.Handle(p)
+    handles = (("fused", hf), ("sharded", hs), ("rows in HBM", hh))
+    o = O.Oracle(p)
+    optimised = 0
+    for k in range(14):
+        pts = synth.scan(p, k)
+        for _, h in handles:
+            h.set_lo_params(o.get("lo_params"))
+            h.set_lm_params(o.get("lm_params"))
+        o.process_scan(pts)
+        outs = {name: h.scan_process(pts, stages=7) for name, h in handles}
+        if k == 0:
+            continue
+        info = o.get("lo_solve_info")
+        for name, h in handles:
+            tag = f"budgets LM ({outer}, {inner}) LO ({lo_surf}, {lo_corner}) {name} scan {k}"
+            _, odom, mp = outs[name]
+            np.testing.assert_allclose(odom["params"], o.get("lo_params"), rtol=0, atol=1e-7, err_msg=f"{tag} LO params_")
+            sc = h.debug_get("scal")
+            assert (sc[10] & 0xFF, (sc[10] >> 8) & 0xFF, sc[10] >> 16) == tuple(info[0:3]), f"{tag} LO surf solve summary"
+            assert (sc[11] & 0xFF, (sc[11] >> 8) & 0xFF, sc[11] >> 16) == tuple(info[3:6]), f"{tag} LO corner solve summary"
+            _lm_compare(h, o, k, tag)
+            want = o.get("map_pose")
+            assert np.abs(mp["t"] - want[:3]).max() < POSE_TOL and quat_angle(mp["q"], want[3:]) < POSE_TOL, tag
+        for name, h in handles[1:]:
+            tag = f"budgets LM ({outer}, {inner}) scan {k} {name} vs fused"
+            assert_bit_equal(outs[name][2]["params"], outs["fused"][2]["params"], f"{tag} LM params_")
+            assert_bit_equal(h.debug_get("lm_info")[6:12], hf.debug_get("lm_info")[6:12], f"{tag} correspondences / solver summaries")
+            assert_bit_equal(h.debug_get("lm_state")[27:43], hf.debug_get("lm_state")[27:43], f"{tag} params_ per outer iteration and costs")
+        optimised += int(o.get("lm_info")[1])
+    assert optimised >= 3, f"only {optimised} optimised mapping frames"
+    hs.dist_shutdown()
+    for _, h in handles:
+        h.close()
 
 
 def test_lm_solve_rows_in_lds_or_hbm_are_bit_identical(params_a, monkeypatch):
