@@ -180,9 +180,13 @@ DEV_INLINE float vxl_dec(unsigned e) {
   return __int_as_float((int)b);
 }
 
-// grid (2, slots): grid geometry from the raw map bounding box, zero the cell counters
+// The cell of a point is floorf(x * inv) - ox in integers: inv is a power of two, so x * inv and its floor are exact and every point lies in its true
+// cell of a global lattice.  (floorf((x - ox) * inv) with a float origin rounds in the subtraction: across a binade boundary of x - ox a point at
+// f32 d^2 < cell^2 from a query could sit two cells away from it, outside the 27 cells lm_knn searches.)  The float is clamped before the
+// conversion so that any finite input gives a defined int.
+DEV_INLINE int cell_coord(float x, float inv) { return (int)fminf(fmaxf(floorf(x * inv), -1073741824.0f), 1073741824.0f); }
 DEV_INLINE int grid_cell(const GridGeom& g, float x, float y, float z, int* cx, int* cy, int* cz) {
-  int ix = (int)floorf((x - g.ox) * g.inv), iy = (int)floorf((y - g.oy) * g.inv), iz = (int)floorf((z - g.oz) * g.inv);
+  int ix = cell_coord(x, g.inv) - g.ox, iy = cell_coord(y, g.inv) - g.oy, iz = cell_coord(z, g.inv) - g.oz;
   *cx = ix; *cy = iy; *cz = iz;
   ix = min(max(ix, 0), g.gx - 1); iy = min(max(iy, 0), g.gy - 1); iz = min(max(iz, 0), g.gz - 1);
   return ix + g.gx * (iy + g.gy * iz);
@@ -204,15 +208,20 @@ __global__ void __launch_bounds__(LM_BLOCK) lm_grid_build(DevCtx d, LmCtx L) {
     float mn[3], mx[3];
     for (int a = 0; a < 3; ++a) { mn[a] = vxl_dec(bb[a]); mx[a] = vxl_dec(~bb[4 + a]); }
     if (li[LI_KRAW_C + m] <= 0) { for (int a = 0; a < 3; ++a) { mn[a] = 0.f; mx[a] = 0.f; } }
-    float cell = 1.0f;  // >= sqrt(knn_max_dist)
-    const float need = sqrtf((float)d.P.knn_max_dist);
-    while (cell < need) cell *= 2.0f;
+    // cell^2 >= knn_max_dist: lm_knn keeps only candidates with f32 d^2 < flim <= cell^2, so |dx| < cell along every axis in real arithmetic
+    // (rounding is monotonic and cell is a power of two) and the candidate is at most one cell away from the query
+    float cell = 1.0f;
+    while ((double)cell * cell < d.P.knn_max_dist) cell *= 2.0f;
+    // the box is the RAW window's: an f32 voxel centroid can lie an ulp outside it, so one cell of margin on either side keeps every map point
+    // unclamped in its true cell
+    int lo[3], hi[3];
     for (;;) {
-      g.gx = (int)floorf((mx[0] - mn[0]) / cell) + 2; g.gy = (int)floorf((mx[1] - mn[1]) / cell) + 2; g.gz = (int)floorf((mx[2] - mn[2]) / cell) + 2;
-      if ((long long)g.gx * g.gy * g.gz <= (long long)L.gcap) break;
+      for (int a = 0; a < 3; ++a) { lo[a] = cell_coord(mn[a], 1.0f / cell) - 1; hi[a] = cell_coord(mx[a], 1.0f / cell) + 1; }
+      const long long ex = (long long)hi[0] - lo[0] + 1, ey = (long long)hi[1] - lo[1] + 1, ez = (long long)hi[2] - lo[2] + 1;
+      if (ex <= L.gcap && ey <= L.gcap && ez <= L.gcap && ex * ey * ez <= (long long)L.gcap) { g.gx = (int)ex; g.gy = (int)ey; g.gz = (int)ez; break; }
       cell *= 2.0f;
     }
-    g.ox = mn[0]; g.oy = mn[1]; g.oz = mn[2]; g.inv = 1.0f / cell; g.ncell = g.gx * g.gy * g.gz;
+    g.ox = lo[0]; g.oy = lo[1]; g.oz = lo[2]; g.inv = 1.0f / cell; g.ncell = g.gx * g.gy * g.gz;
     s_g = g;
     L.grid[(size_t)slot * 2 + m] = g;
     s_run = 0;
@@ -514,7 +523,7 @@ __global__ void __launch_bounds__(128) lm_knn(DevCtx d, LmCtx L) {
   double r[3];
   dq_rotate(qm, vin, r);
   const float sx = (float)(r[0] + ld[LD_T_M2L + 0]), sy = (float)(r[1] + ld[LD_T_M2L + 1]), sz = (float)(r[2] + ld[LD_T_M2L + 2]);
-  // exact 5-NN among all points with d^2 < knn_max_dist: they all lie in the 27 surrounding cells.
+  // exact 5-NN among all points with d^2 < knn_max_dist: they all lie in the 27 surrounding cells (lm_grid_build: cell^2 >= knn_max_dist, exact cell coordinates).
   // A lane's five best candidates are an UNSORTED set of 64-bit keys (f32 distance bits << 32 | map index: the lexicographic
   // (distance, index) order is the integer order) with the set's maximum tracked next to it: a candidate that beats the maximum
   // replaces it (five compare-selects) and the maximum is recomputed (four), instead of a five-step insertion sort — the kernel is

@@ -43,7 +43,7 @@ enum {
   LD_COUNT = 48
 };
 
-struct GridGeom { float ox, oy, oz, inv; int gx, gy, gz, ncell; };
+struct GridGeom { int ox, oy, oz; float inv; int gx, gy, gz, ncell; };   // cell of x: floorf(x * inv) - ox (lm_grid_build)
 
 // Packed voxel key of a point: PCL's VoxelGrid orders the output by idx = i + j dx + k dx dy with (i, j, k) the integer voxel
 // coordinates relative to the cloud's bounding box, i.e. lexicographically by (floor(z inv), floor(y inv), floor(x inv)) — an order that

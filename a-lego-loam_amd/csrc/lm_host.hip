@@ -570,6 +570,7 @@ int lm_host_debug_get(LmHost* lm, int slot, const char* name, void* out, int cap
   else if (s == "lm_outlier_ds") set(L.cur_outl_ds + b * L.kf_cap_o, (size_t)li[LI_NCUR_O] * 4, 0);
   else if (s == "lm_surf_total_ds") set(L.cur_total_ds + b * L.total_cap, (size_t)li[LI_NTOTAL_DS] * 4, 0);
   else if (s == "lm_blocks") set(L.blocks + b * L.qcap * 8, (size_t)L.qcap * 8, 1);
+  else if (s == "lm_knn") set(L.knn + b * L.qcap * 5, (size_t)L.qcap * 5, 2);   // lm_knn's rows: corner queries from 0, surf queries from kf_cap_c; -1 x 5 = rejected
   else if (s == "lm_keyposes") set(L.kf_pose + b * L.KR * 8, (size_t)L.KR * 8, 0);
   else if (s == "lm_window") set(L.rec + b * L.K, (size_t)li[LI_REC_CNT], 2);   // frame ids of recent_*_keyframes_
   else if (s == "lm_kf_corner_map" || s == "lm_kf_surf_map") {   // newest key frame in the map frame, sorted by voxel key (surf = surf + outlier)

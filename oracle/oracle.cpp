@@ -1349,6 +1349,8 @@ struct LaserMapping {
   bool ran_body = false, optimized = false, keyframe_added = false;
   int n_corner_corr = 0, n_surf_corr = 0;
   std::vector<int> corner_corr_q, surf_corr_q;  // accepted query indices (first outer iteration)
+  std::vector<Pt> query_c, query_s;             // first outer iteration: every query in the map frame (the `sel` of pointAssociateToMap)
+  std::vector<int> knn_c, knn_s;                // ... and its five neighbours in ascending (distance, index) order; -1 x 5 = not gated in (:376,:426)
   std::vector<double> blocks14;                 // the residual blocks of the first outer iteration: type, cp, a, b, c, d
   std::vector<int> plane_rank_hist = std::vector<int>(4, 0);   // first outer iteration: plane fits by nonzeroPivots() (tests: were rank-deficient neighbourhoods reached?)
   SolveSummary sums[2];
@@ -1452,6 +1454,7 @@ struct LaserMapping {
   void scan2map_optimization() {  // :348-479
     optimized = false; n_corner_corr = n_surf_corr = 0;
     corner_corr_q.clear(); surf_corr_q.clear();
+    query_c.clear(); query_s.clear(); knn_c.clear(); knn_s.clear();
     if ((int)laser_corner_ds.size() < P.lm_min_corner || (int)laser_surf_total.size() < P.lm_min_surf ||
         (int)corner_from_map_ds.size() < P.lm_min_map_corner) return;
     auto t0 = std::chrono::steady_clock::now();
@@ -1466,7 +1469,12 @@ struct LaserMapping {
       int nidx[5]; float ndist[5];
       for (int i = 0; i < (int)laser_corner_ds.size(); ++i) {  // :371-417
         Pt sel; point_associate_to_map(laser_corner_ds[i], sel);
-        if (kd_corner_map.knn(sel, 5, nidx, ndist) < 5) continue;
+        const int nf = kd_corner_map.knn(sel, 5, nidx, ndist);
+        if (iter_cnt == 0) {
+          query_c.push_back(sel);
+          for (int j = 0; j < 5; ++j) knn_c.push_back(nf == 5 && (double)ndist[4] < P.knn_max_dist ? nidx[j] : -1);
+        }
+        if (nf < 5) continue;
         if ((double)ndist[4] < P.knn_max_dist) {
           double near[5][3], center[3] = {0, 0, 0};
           for (int j = 0; j < 5; ++j) {
@@ -1501,7 +1509,12 @@ struct LaserMapping {
       if (iter_cnt == 0) plane_rank_hist.assign(4, 0);
       for (int i = 0; i < (int)laser_surf_total_ds.size(); ++i) {  // :419-462
         Pt sel; point_associate_to_map(laser_surf_total_ds[i], sel);
-        if (kd_surf_map.knn(sel, 5, nidx, ndist) < 5) continue;
+        const int nf = kd_surf_map.knn(sel, 5, nidx, ndist);
+        if (iter_cnt == 0) {
+          query_s.push_back(sel);
+          for (int j = 0; j < 5; ++j) knn_s.push_back(nf == 5 && (double)ndist[4] < P.knn_max_dist ? nidx[j] : -1);
+        }
+        if (nf < 5) continue;
         if ((double)ndist[4] < P.knn_max_dist) {
           double A[15], b[5] = {-1.0, -1.0, -1.0, -1.0, -1.0};   // Matrix<double, 5, 3> / Matrix<double, 5, 1>: fixed size, no heap
           for (int j = 0; j < 5; ++j) {
@@ -1914,6 +1927,10 @@ int oracle_get(void* h, const char* name, const void** ptr, int* count, int* dty
   if (s == "lm_corner_corr_q") { *dtype = ORACLE_I32; return ret(lm.corner_corr_q, ptr, count); }
   if (s == "lm_surf_corr_q") { *dtype = ORACLE_I32; return ret(lm.surf_corr_q, ptr, count); }
   if (s == "lm_plane_rank_hist") { *dtype = ORACLE_I32; return ret(lm.plane_rank_hist, ptr, count); }
+  if (s == "lm_query_c") return cloud(lm.query_c);
+  if (s == "lm_query_s") return cloud(lm.query_s);
+  if (s == "lm_knn_c") { *dtype = ORACLE_I32; return ret(lm.knn_c, ptr, count); }
+  if (s == "lm_knn_s") { *dtype = ORACLE_I32; return ret(lm.knn_s, ptr, count); }
   if (s == "lm_blocks14") { *dtype = ORACLE_F64; return ret(lm.blocks14, ptr, count); }
   if (s == "lm_keyposes") { *dtype = ORACLE_F32; *ptr = lm.keyposes.data(); *count = (int)lm.keyposes.size() * 6; return 0; }
   if (s == "lm_map2odom") {

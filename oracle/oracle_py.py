@@ -190,7 +190,7 @@ class Oracle:
 
 _CLOUDS = {"seg_cloud", "undistorted", "outlier", "sharp", "less_sharp", "flat", "less_flat", "surf_last", "corner_last",
            "lm_corner_map_ds", "lm_surf_map_ds", "lm_corner_map", "lm_surf_map", "lm_corner_ds", "lm_surf_ds",
-           "lm_outlier_ds", "lm_surf_total_ds"}
+           "lm_outlier_ds", "lm_surf_total_ds", "lm_query_c", "lm_query_s"}
 
 
 def std_sort_order(keys, depth_limit=-1):

@@ -8,7 +8,7 @@ import pytest
 
 from alego_amd import binding, synth
 from oracle import oracle_py as O
-from util import assert_bit_equal, imu_stream, quat_angle
+from util import KNN_SCENES, assert_bit_equal, assert_knn_scene_premise, imu_stream, knn_scene, knn_sparse_box_scene, lm_unit_cells_needed, quat_angle, run_knn_scene
 
 pytestmark = pytest.mark.gpu
 POSE_TOL = 1e-4
@@ -626,11 +626,37 @@ def _lm_compare(h, o, k, tag):
         kf_cap_c = h.params.n_less_sharp * h.params.n_sectors * h.params.n_scan   # capacity of laser_corner_ds_ = of corner_last (lm_host.hip)
         qs = np.nonzero(blocks[kf_cap_c:kf_cap_c + gi[23], 7] != 0)[0]
         assert_bit_equal(qs.astype(np.int32), o.get("lm_surf_corr_q"), f"{tag} accepted surf queries")
+        _lm_knn_blocks_compare(h, o, blocks, ncur, kf_cap_c, gi[23], tag)
         st = h.debug_get("lm_state")
         np.testing.assert_allclose(st[27:39], o.get("lm_params_iter"), rtol=0, atol=1e-6, err_msg=f"{tag} params_ after each outer iteration")
         assert ((gi[8] & 0xFF, (gi[8] >> 8) & 0xFF, gi[8] >> 16), (gi[9] & 0xFF, (gi[9] >> 8) & 0xFF, gi[9] >> 16)) == \
             (tuple(oi[5:8]), tuple(oi[8:11])), f"{tag} solver summaries {gi[8]:x} {gi[9]:x} vs {oi[5:11]}"
     np.testing.assert_allclose(h.debug_get("lm_state")[0:6], o.get("lm_params"), rtol=0, atol=1e-6, err_msg=f"{tag} params_")
+
+
+LM_BLOCK_STATS = dict(edges=0, edges_bit=0, planes=0, planes_bit=0)
+
+
+def _lm_knn_blocks_compare(h, o, blocks, ncur, kf_cap_c, ntot, tag):
+    """lm_knn's five neighbours of every query against the oracle's kd-tree (bit for bit: a wrong fifth neighbour of an accepted query moves
+    its line / plane but hardly params_), and every accepted block against lm_blocks14: edges a, b; planes normal, d (atol 1e-12: the same
+    fp64 operations in the same order; bit-equality is counted in LM_BLOCK_STATS)."""
+    kn = h.debug_get("lm_knn").reshape(-1, 5)
+    for what, got, want in (("corner", kn[:ncur], o.get("lm_knn_c").reshape(-1, 5)), ("surf", kn[kf_cap_c:kf_cap_c + ntot], o.get("lm_knn_s").reshape(-1, 5))):
+        assert got.shape == want.shape, f"{tag} {what} k-NN rows: {got.shape} vs {want.shape}"
+        bad = np.nonzero((got != want).any(axis=1))[0]
+        assert bad.size == 0, f"{tag} {what} k-NN rows: {bad.size} of {len(want)} differ, first queries {bad[:4]}: got {got[bad[:4]].tolist()} want {want[bad[:4]].tolist()}"
+    b14 = o.get("lm_blocks14").reshape(-1, 14)
+    ge = blocks[:ncur][blocks[:ncur, 7] == 2.0]
+    gp = blocks[kf_cap_c:kf_cap_c + ntot][blocks[kf_cap_c:kf_cap_c + ntot, 7] == 3.0]
+    we, wp = b14[b14[:, 0] == 2], b14[b14[:, 0] == 3]
+    assert (ge.shape[0], gp.shape[0]) == (we.shape[0], wp.shape[0]), f"{tag}: blocks {ge.shape[0]} edges, {gp.shape[0]} planes vs {we.shape[0]}, {wp.shape[0]}"
+    np.testing.assert_allclose(ge[:, 0:6], we[:, 4:10], rtol=0, atol=1e-12, err_msg=f"{tag} edge blocks (a, b)")
+    np.testing.assert_allclose(gp[:, [0, 1, 2, 6]], wp[:, [4, 5, 6, 13]], rtol=0, atol=1e-12, err_msg=f"{tag} plane blocks (normal, d)")
+    LM_BLOCK_STATS["edges"] += ge.shape[0]
+    LM_BLOCK_STATS["edges_bit"] += int((ge[:, 0:6] == we[:, 4:10]).all(axis=1).sum())
+    LM_BLOCK_STATS["planes"] += gp.shape[0]
+    LM_BLOCK_STATS["planes_bit"] += int((gp[:, [0, 1, 2, 6]] == wp[:, [4, 5, 6, 13]]).all(axis=1).sum())
 
 
 @pytest.mark.parametrize("geom,nscan,mods", [
@@ -2289,4 +2315,34 @@ def test_sharded_registration_world1_config5_geometry_vs_oracle():
         assert np.abs(mp["t"] - want[:3]).max() < POSE_TOL and quat_angle(mp["q"], want[3:]) < POSE_TOL, k
     assert optimised >= 15 and o.get("lm_info")[11] >= 18
     h.dist_shutdown()
+    h.close()
+
+
+@pytest.mark.parametrize("outer", [1, 2])
+@pytest.mark.parametrize("name", KNN_SCENES + ["sparse_80x80x45", "sparse_110x110x90"])
+def test_lm_knn_edge_scenes(name, outer):
+    """lm_knn at the edges of its uniform grid and of f32 rounding (tests/util.py; each scene asserts its own premise on the oracle): a fifth neighbour
+    across a binade boundary of x - ox two cells from the query, voxel centroids that fall below the raw window box, the d5^2 gate at flim and one
+    ulp either side for knn_max_dist 1.0 / 0.7 / 1.1 / 2/3, exact distance ties near the origin and 4 km away, maps of 4 - 6 points with queries
+    outside the box, and boxes that need more than gcap unit cells (2^18 in a 65-slot handle, 2^20 in a 1-slot one).  Every neighbour row and
+    every accepted block must equal the oracle's (_lm_compare)."""
+    if name.startswith("sparse"):
+        ext = tuple(float(v) for v in name.split("_")[1].split("x"))
+        scene, n_slots, gcap = knn_sparse_box_scene(ext), (65 if ext[0] < 100 else 1), (1 << 18 if ext[0] < 100 else 1 << 20)
+    else:
+        scene, n_slots, gcap = knn_scene(name), 1, 1 << 20
+    p = synth.default_params(16, 1800)
+    for k, v in scene["mods"].items():
+        setattr(p, k, v)
+    p.lm_outer_iters = outer
+    h, o = binding.Handle(p, n_slots=n_slots), O.Oracle(p)
+    run_knn_scene(o, scene)
+    if name.startswith("sparse"):
+        assert lm_unit_cells_needed(scene["keyframe"][1]) > gcap
+    else:
+        assert_knn_scene_premise(name, scene, o)
+    flags, mp = run_knn_scene(h, scene, device=True)
+    _lm_compare(h, o, 0, f"{name} outer {outer}")
+    assert h.debug_get("lm_info")[11], name
+    print(f"{name}: blocks so far {LM_BLOCK_STATS}")
     h.close()

@@ -9,7 +9,8 @@ import pytest
 
 from alego_amd import synth
 from oracle import oracle_py as O
-from util import assert_bit_equal
+from util import (KNN_SCENES, assert_bit_equal, assert_knn_scene_premise, knn_brute_rows, knn_scene, knn_sparse_box_scene, lm_unit_cells_needed,
+                  run_knn_scene)
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "oracle_cfgA.npz")
 
@@ -584,3 +585,45 @@ def test_solver_agrees_with_scipy_least_squares_on_noisy_data_with_outliers():
     assert np.abs(x - ref.x).max() < 3e-4, (x, ref.x)
     assert abs(info["final_cost"] - ref.cost) < 5e-6 * ref.cost, (info["final_cost"], ref.cost)
     assert np.abs(x - true)[[0, 1, 2, 5]].max() < 0.02   # and both are near the truth despite the outliers
+
+
+def _knn_rows_against_brute_force(o, kmd, tag):
+    for kind, mp, q, rows in (("corner", "lm_corner_map_ds", "lm_query_c", "lm_knn_c"), ("surf", "lm_surf_map_ds", "lm_query_s", "lm_knn_s")):
+        got = o.get(rows).reshape(-1, 5)
+        qs = o.get(q)
+        assert got.shape[0] == qs.shape[0], f"{tag} {kind}: {got.shape[0]} rows for {qs.shape[0]} queries"
+        assert_bit_equal(got, knn_brute_rows(o.get(mp), qs, kmd), f"{tag} {kind} k-NN rows")
+    return int((o.get("lm_knn_c").reshape(-1, 5)[:, 0] >= 0).sum()), int((o.get("lm_knn_s").reshape(-1, 5)[:, 0] >= 0).sum())
+
+
+def test_lm_knn_rows_equal_brute_force_on_a_synthetic_run(params_a):
+    """The oracle's LaserMapping k-NN rows (kd-tree, first outer iteration) against a numpy brute force over the filtered maps and the exported
+    map-frame queries: f32 distances in the kernels' order, ties to the lower index, the f64 gate d5^2 < knn_max_dist."""
+    p = params_a.copy()
+    p.lm_every = 1
+    o = O.Oracle(p)
+    nopt = nacc = 0
+    for k in range(6):
+        o.process_scan(synth.scan(p, k))
+        if not o.get("lm_info")[1]:
+            continue
+        nopt += 1
+        nacc += sum(_knn_rows_against_brute_force(o, p.knn_max_dist, f"scan {k}"))
+    assert nopt >= 4 and nacc > 4000, (nopt, nacc)
+
+
+@pytest.mark.parametrize("name", KNN_SCENES + ["sparse_80x80x45", "sparse_110x110x90"])
+def test_lm_knn_edge_scenes_on_the_oracle(params_a, name):
+    """The constructed k-NN scenes (tests/util.py) on the oracle: its rows equal the brute force, and every scene reaches what it is built for."""
+    scene = knn_sparse_box_scene(tuple(float(v) for v in name.split("_")[1].split("x"))) if name.startswith("sparse") else knn_scene(name)
+    p = params_a.copy()
+    for k, v in scene["mods"].items():
+        setattr(p, k, v)
+    o = O.Oracle(p)
+    run_knn_scene(o, scene)
+    _knn_rows_against_brute_force(o, p.knn_max_dist, name)
+    if name.startswith("sparse"):
+        assert lm_unit_cells_needed(scene["keyframe"][1]) > (1 << 18 if name == "sparse_80x80x45" else 1 << 20)
+        assert (o.get("lm_knn_c").reshape(-1, 5)[:, 0] >= 0).sum() >= 16
+    else:
+        assert_knn_scene_premise(name, scene, o)
