@@ -29,10 +29,14 @@ EXPORTS = [
     "alego_loop_detect", "alego_loop_closure_icp",
     "alego_bag_open", "alego_bag_close", "alego_bag_last_error", "alego_bag_topic_count", "alego_bag_topic_info", "alego_bag_message_count",
     "alego_bag_read_raw", "alego_bag_read_pc2", "alego_handle_lock", "alego_handle_unlock",
+    "alego_map_enable", "alego_map_status", "alego_map_set_keyposes", "alego_map_get_keyframe", "alego_map_assemble", "alego_map_keyposes",
+    "alego_lm_get_local_map", "alego_voxel_grid", "alego_write_pcd",
 ]
 
 REPLAY_PINGPONG = 0x100
 REPLAY_BAG = 0x200
+MAP_SURF, MAP_CORNER, MAP_OUTLIER, MAP_FRAME_ID = 1, 2, 4, 8
+ERR_CAPACITY, ERR_ARG = -3, -4
 FLAG_LO_INIT, FLAG_FEW_SURF, FLAG_FEW_CORNER, FLAG_LM_SKIPPED, FLAG_LM_FEW_FEATURES, FLAG_LM_KEYFRAME = 1, 2, 4, 8, 16, 32
 
 
@@ -231,6 +235,15 @@ def lib():
         L.alego_bag_read_raw.restype = C.c_int
         L.alego_bag_read_raw.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
         L.alego_bag_read_pc2.restype = C.c_int
+        L.alego_map_enable.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+        L.alego_map_status.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.alego_map_set_keyposes.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.c_void_p]
+        L.alego_map_get_keyframe.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.POINTER(KeyFrame)]
+        L.alego_map_assemble.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int32]
+        L.alego_map_keyposes.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int32]
+        L.alego_lm_get_local_map.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+        L.alego_voxel_grid.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_int32]
+        L.alego_write_pcd.argtypes = [C.c_char_p, C.c_void_p, C.c_int32]
         L.alego_bag_read_pc2.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
         if L.alego_params_sizeof() != C.sizeof(AlegoParams):
             raise RuntimeError("alego_params layout mismatch between params.py and include/alego_params.h")
@@ -258,6 +271,14 @@ def check_guards():
     """(count, report) of damaged allocation guards; count = -1 unless ALEGO_DEBUG_CANARY is set"""
     buf = C.create_string_buffer(4096)
     return lib().alego_debug_check_guards(buf, 4096), buf.value.decode(errors="replace")
+
+
+def write_pcd(path, pts):
+    """alego_write_pcd: PCD v0.7, DATA binary, FIELDS x y z intensity"""
+    a = np.ascontiguousarray(pts, np.float32).reshape(-1, 4)
+    rc = lib().alego_write_pcd(os.fsencode(path), a.ctypes.data, a.shape[0])
+    if rc != 0:
+        raise AlegoError(f"alego_write_pcd({path}) failed ({rc})")
 
 
 def loop_detect(params, keyposes6, stamps, cur_xyz):
@@ -553,6 +574,62 @@ class Handle:
         out = np.empty((max(a.shape[0], 1), 4), np.float32)
         n = self._check(lib().alego_debug_voxel(self._h, a.ctypes.data, a.shape[0], leaf, out.ctypes.data, out.shape[0]), "alego_debug_voxel")
         return out[:n].copy()
+
+    def voxel_grid_large(self, pts, leaf):
+        """alego_voxel_grid: pcl::VoxelGrid of a host cloud of any size (the product entry point; large clouds on the whole device)"""
+        a = np.ascontiguousarray(pts, np.float32).reshape(-1, 4)
+        n = self._check(lib().alego_voxel_grid(self._h, a.ctypes.data, a.shape[0], leaf, None, 0), "alego_voxel_grid")
+        out = np.empty((max(n, 1), 4), np.float32)
+        m = self._check(lib().alego_voxel_grid(self._h, a.ctypes.data, a.shape[0], leaf, out.ctypes.data, out.shape[0]), "alego_voxel_grid")
+        return out[:m].copy()
+
+    # ---- the global map (key-frame archive) ----
+    def map_enable(self, max_keyframes, max_points):
+        self._check(lib().alego_map_enable(self._h, max_keyframes, max_points), "alego_map_enable")
+
+    def map_status(self, slot=0):
+        """(frames stored, frames dropped, points stored, point capacity)"""
+        out = np.zeros(4, np.int32)
+        self._check(lib().alego_map_status(self._h, slot, out.ctypes.data), "alego_map_status")
+        return tuple(int(v) for v in out)
+
+    def map_set_keyposes(self, first, poses6, slot=0):
+        a = np.ascontiguousarray(poses6, np.float32).reshape(-1, 6)
+        self._check(lib().alego_map_set_keyposes(self._h, slot, first, a.shape[0], a.ctypes.data), "alego_map_set_keyposes")
+
+    def map_get_keyframe(self, kf_id, slot=0):
+        """dict(id, pose[6], corner, surf, outlier): any archived key frame"""
+        k = KeyFrame()
+        self._check(lib().alego_map_get_keyframe(self._h, slot, kf_id, C.byref(k)), "alego_map_get_keyframe")   # (counts only)
+        bufs = [np.empty((max(n, 1), 4), np.float32) for n in (k.n_corner, k.n_surf, k.n_outlier)]
+        k.corner, k.corner_cap = bufs[0].ctypes.data, bufs[0].shape[0]
+        k.surf, k.surf_cap = bufs[1].ctypes.data, bufs[1].shape[0]
+        k.outlier, k.outlier_cap = bufs[2].ctypes.data, bufs[2].shape[0]
+        self._check(lib().alego_map_get_keyframe(self._h, slot, kf_id, C.byref(k)), "alego_map_get_keyframe")
+        return dict(id=int(k.id), pose=np.array(k.pose[:], np.float32), corner=bufs[0][:k.n_corner].copy(), surf=bufs[1][:k.n_surf].copy(),
+                    outlier=bufs[2][:k.n_outlier].copy())
+
+    def map_assemble(self, kinds, leaf=0.0, slot=0, cap=None):
+        """the global map of `slot` (ALEGO_MAP_* kinds, optionally VoxelGrid(leaf)); cap: output capacity (default: the count)"""
+        if cap is None:
+            cap = self._check(lib().alego_map_assemble(self._h, slot, kinds, leaf, None, 0), "alego_map_assemble")
+        out = np.empty((max(cap, 1), 4), np.float32)
+        n = self._check(lib().alego_map_assemble(self._h, slot, kinds, leaf, out.ctypes.data, cap), "alego_map_assemble")
+        return out[:n].copy()
+
+    def map_keyposes(self, slot=0):
+        n = self._check(lib().alego_map_keyposes(self._h, slot, None, 0), "alego_map_keyposes")
+        out = np.empty((max(n, 1), 4), np.float32)
+        n = self._check(lib().alego_map_keyposes(self._h, slot, out.ctypes.data, out.shape[0]), "alego_map_keyposes")
+        return out[:n].copy()
+
+    def lm_local_map(self, slot=0):
+        """(corner_from_map_ds_, surf_from_map_ds_) of the last mapping frame"""
+        n = np.zeros(2, np.int32)
+        self._check(lib().alego_lm_get_local_map(self._h, slot, None, 0, None, 0, n.ctypes.data), "alego_lm_get_local_map")
+        c, s = np.empty((max(int(n[0]), 1), 4), np.float32), np.empty((max(int(n[1]), 1), 4), np.float32)
+        self._check(lib().alego_lm_get_local_map(self._h, slot, c.ctypes.data, c.shape[0], s.ctypes.data, s.shape[0], n.ctypes.data), "alego_lm_get_local_map")
+        return c[:n[0]].copy(), s[:n[1]].copy()
 
     def math(self, mode, a, b=None):
         """device single-precision functions: mode 0 atan2f(a, b), 1 hypotf(a, b), 2 sinf(a), 3 cosf(a)"""

@@ -77,6 +77,7 @@ struct alego_handle {
   hipStream_t s_lo = nullptr, s_lm = nullptr;
   std::vector<hipEvent_t> ev_pool;
   size_t ev_next = 0;
+  bool map_on = false;         // alego_map_enable: the key-frame archive exists
 };
 
 namespace {
@@ -431,6 +432,7 @@ int alego_stream_setup(alego_handle* h, int bag, int start_scan) {
   if (!h->d.bag_pts || bag < 0 || bag >= h->d.n_bags || start_scan < 0) { h->err = "alego_stream_setup: needs alego_replay_create and a valid bag"; return ALEGO_ERR_ARG; }
   if (h->d.n_slots < 3 || h->streams.size() != 1) { h->err = "alego_stream_setup: the handle needs n_slots = 1 + 2 W >= 3 (one stream group)"; return ALEGO_ERR_ARG; }
   if (h->d.traj) { h->err = "alego_stream_setup: the per-scan pose log belongs to the batch path"; return ALEGO_ERR_ARG; }
+  if (h->map_on) { h->err = "alego_stream_setup: the key-frame archive belongs to the batch / single-scan paths"; return ALEGO_ERR_ARG; }
   if (h->P.deskew_mode) { h->err = "alego_stream_setup: bags carry no stamps / IMU data; the motion de-skew runs through alego_scan_process / alego_lo_process"; return ALEGO_ERR_ARG; }
   hipSetDevice(h->device);
   const int W = (h->d.n_slots - 1) / 2;
@@ -1030,6 +1032,7 @@ int alego_debug_set_option(alego_handle* h, const char* name, int value) {
   else if (s == "ALEGO_MAP_MERGE") { if (int r = lm_host_set_map_merge(h->lm, value != 0, &h->err)) return r; d.opt_map_merge = value != 0; }
   else if (s == "ALEGO_IP_FAST") d.ip_fast = h->ip_fast_capable & value;
   else if (s == "ALEGO_POKE_GUARD") { HIP_TRY(h, hipMemset(d.scal + (size_t)d.n_slots * SC_COUNT + value, 0xFF, 4)); }   // tests of the guard pages: a write `value` ints past the end of an array
+  else if (s == "ALEGO_GV_SMALL_MAX") { HIP_TRY(h, sync_all(h)); return lm_host_set_gv_small_max(h->lm, value); }   // tools/gmap_timing.py: largest cloud alego_voxel_grid gives to one workgroup
   else if (s == "ALEGO_SHARD_SLICE") return lm_host_debug_slice(h->lm, value & 0xff, value >> 8, &h->err);   // tests: rank | world << 8 without a communicator
   else { h->err = "unknown option " + s; return ALEGO_ERR_ARG; }
   return 0;
@@ -1119,6 +1122,58 @@ int alego_lm_add_keyframe(alego_handle* h, int slot, const float pose6[6], const
   hipSetDevice(h->device);
   g_prof = &h->prof;
   return lm_host_add_keyframe(h->lm, h->d, slot, pose6, corner, n_corner, surf, n_surf, outlier, n_outlier, &h->err);
+}
+
+// ---- the global map -------------------------------------------------------------------------------------------------
+int alego_map_enable(alego_handle* h, int32_t max_keyframes, int32_t max_points) {
+  if (!h || max_keyframes <= 0 || max_points <= 0) return ALEGO_ERR_ARG;
+  if (h->stream_mode) { h->err = "alego_map_enable: not available with alego_stream_setup"; return ALEGO_ERR_ARG; }
+  if (h->map_on) { h->err = "alego_map_enable: already enabled"; return ALEGO_ERR_ARG; }
+  hipSetDevice(h->device);
+  HIP_TRY(h, sync_all(h));
+  if (int r = lm_host_map_enable(h->lm, max_keyframes, max_points, &h->err)) return r;
+  h->map_on = true;
+  return 0;
+}
+int alego_map_status(alego_handle* h, int slot, int32_t out[4]) {
+  if (int r = check_slot(h, slot)) return r;
+  if (!out) return ALEGO_ERR_ARG;
+  hipSetDevice(h->device);
+  return lm_host_map_status(h->lm, slot, out, &h->err);
+}
+int alego_map_set_keyposes(alego_handle* h, int slot, int32_t first, int32_t n, const float* poses6) {
+  if (int r = check_slot(h, slot)) return r;
+  hipSetDevice(h->device);
+  return lm_host_map_set_keyposes(h->lm, slot, first, n, poses6, &h->err);
+}
+int alego_map_get_keyframe(alego_handle* h, int slot, int32_t id, alego_keyframe* out) {
+  if (int r = check_slot(h, slot)) return r;
+  if (!out) return ALEGO_ERR_ARG;
+  hipSetDevice(h->device);
+  return lm_host_map_get_keyframe(h->lm, slot, id, out, &h->err);
+}
+int alego_map_assemble(alego_handle* h, int slot, int kinds, float leaf, alego_point* out, int32_t cap) {
+  if (int r = check_slot(h, slot)) return r;
+  hipSetDevice(h->device);
+  g_prof = &h->prof;
+  return lm_host_map_assemble(h->lm, slot, kinds, leaf, out, cap, &h->err);
+}
+int alego_map_keyposes(alego_handle* h, int slot, alego_point* out, int32_t cap) {
+  if (int r = check_slot(h, slot)) return r;
+  hipSetDevice(h->device);
+  return lm_host_map_keyposes(h->lm, slot, out, cap, &h->err);
+}
+int alego_lm_get_local_map(alego_handle* h, int slot, alego_point* corner, int32_t corner_cap, alego_point* surf, int32_t surf_cap, int32_t n_out[2]) {
+  if (int r = check_slot(h, slot)) return r;
+  if (!n_out || corner_cap < 0 || surf_cap < 0) return ALEGO_ERR_ARG;
+  hipSetDevice(h->device);
+  return lm_host_get_local_map(h->lm, slot, corner, corner_cap, surf, surf_cap, n_out, &h->err);
+}
+int alego_voxel_grid(alego_handle* h, const alego_point* pts, int32_t n, float leaf, alego_point* out, int32_t cap) {
+  if (!h || n < 0 || cap < 0 || (n > 0 && !pts) || !(leaf > 0.f)) return ALEGO_ERR_ARG;
+  hipSetDevice(h->device);
+  g_prof = &h->prof;
+  return lm_host_voxel_grid(h->lm, h->stream, pts, n, leaf, out, cap, &h->err);
 }
 
 int alego_debug_get(alego_handle* h, int slot, const char* name, void* out, int cap_bytes, int* count, int* dtype) {

@@ -13,6 +13,7 @@
 #include "dev_cost.h"
 #include "prof.h"
 #include "lm_ctx.h"
+#include "gmap.h"
 
 #define LM_BLOCK 256
 
@@ -1183,6 +1184,7 @@ int launch_lm_register(const DevCtx& d, const LmCtx& L, hipStream_t st, int (*al
   }
   ALEGO_LAUNCH(lm_finish, dim3((d.n_launch + 63) / 64), dim3(64), 0, st, d, L);
   ALEGO_LAUNCH(lm_store_kf, dim3(8, 3, d.n_launch), dim3(LM_BLOCK), 0, st, d, L, -1);
+  if (L.arc_frames_cap > 0) launch_map_archive(d, L, 0, st);   // (alego_map_enable; nothing is launched without it)
   return 0;
 }
 void launch_lm_retransform(const DevCtx& d, const LmCtx& L, int ring, hipStream_t st) {

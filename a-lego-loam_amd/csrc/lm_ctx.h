@@ -149,6 +149,13 @@ struct LmCtx {
   // residual blocks
   double* blocks;                                 // [slot][qcap][8]: a/normal (3), b (3), d, type (0 = none)
   double* crows;                                  // [slot][qcap][10]: accepted rows that do not fit lm_solve's LDS (all rows on the sharded path): the 8 doubles above + the query point (float4)
+  // key-frame archive (alego_map_enable; arc_frames_cap == 0: off, nothing is launched): EVERY key frame of a slot as the ring stores it
+  // (sensor frame, kf_raw_* / kf_cnt) + its f32 key pose, appended by map_archive behind lm_store_kf; the stored frames are always a prefix
+  int arc_frames_cap, arc_points_cap;             // per slot
+  float4* arc_pts;                                // [slot][arc_points_cap] corner | surf | outlier of each frame, frames back to back
+  int* arc_tab;                                   // [slot][arc_frames_cap][4] point offset, n corner, n surf, n outlier
+  float* arc_pose;                                // [slot][arc_frames_cap][8] x y z roll pitch yaw
+  int* arc_stat;                                  // [slot][4] frames stored, frames dropped, points stored, -
 };
 
 #endif

@@ -40,4 +40,14 @@ int lm_host_dist_probe(LmHost* lm, int iters, double* usec, std::string* err);
 int lm_host_debug_slice(LmHost* lm, int rank, int world, std::string* err);
 int lm_host_set_map_merge(LmHost* lm, int on, std::string* err);
 int lm_host_debug_get(LmHost* lm, int slot, const char* name, void* out, int cap_bytes, int* count, int* dtype, std::string* err);
+// the global map (include/alego_mi355x.h: alego_map_*, alego_lm_get_local_map, alego_voxel_grid)
+int lm_host_map_enable(LmHost* lm, int max_frames, int max_points, std::string* err);
+int lm_host_map_status(LmHost* lm, int slot, int* out4, std::string* err);
+int lm_host_map_set_keyposes(LmHost* lm, int slot, int first, int n, const float* poses6, std::string* err);
+int lm_host_map_get_keyframe(LmHost* lm, int slot, int id, alego_keyframe* out, std::string* err);
+int lm_host_map_assemble(LmHost* lm, int slot, int kinds, float leaf, alego_point* out, int cap, std::string* err);
+int lm_host_map_keyposes(LmHost* lm, int slot, alego_point* out, int cap, std::string* err);
+int lm_host_get_local_map(LmHost* lm, int slot, alego_point* corner, int corner_cap, alego_point* surf, int surf_cap, int* n_out, std::string* err);
+int lm_host_voxel_grid(LmHost* lm, hipStream_t st, const alego_point* pts, int n, float leaf, alego_point* out, int cap, std::string* err);
+int lm_host_set_gv_small_max(LmHost* lm, int v);
 #endif

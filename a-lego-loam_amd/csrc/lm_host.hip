@@ -12,6 +12,7 @@
 
 #include "lm_ctx.h"
 #include "voxel.h"
+#include "gmap.h"
 
 void launch_lm_prepare(const DevCtx& d, const LmCtx& L, int stage, int run_hint, int par, hipStream_t st);
 void launch_lm_stage(const DevCtx& d, const LmCtx& L, int run_hint, int par, hipStream_t st);
@@ -44,6 +45,9 @@ struct LmHost {
   std::string dist_err;
   std::vector<void*> allocs;
   std::vector<long> frames;  // host mirror of frame_cnt per slot: only used to skip launches
+  // the global map (alego_map_* / alego_voxel_grid): device-wide VoxelGrid scratch + the assembly's frame offsets
+  GvCtx gv;
+  int* arc_off = nullptr;      // [arc_frames_cap + 1]
 };
 
 namespace {
@@ -64,6 +68,7 @@ bool A(LmHost* lm, T** p, size_t count, std::string* err) {
 LmHost* lm_host_create(const alego_params& P, const DevCtx& d, int n_slots, int gsize, const std::vector<hipStream_t>& st, std::string* err) {
   LmHost* lm = new LmHost();
   lm->P = P; lm->n_slots = n_slots; lm->gsize = gsize; lm->st = st; lm->frames.assign(n_slots, 0);
+  lm->gv.small_max = gv_small_max_env();
   VoxCtx vz; std::memset(&vz, 0, sizeof(VoxCtx));
   lm->vm.assign(st.size(), vz); lm->v2.assign(st.size(), vz); lm->vk.assign(st.size(), vz);
   lm->work.assign(st.size(), MapWork{nullptr, nullptr, 0});
@@ -177,6 +182,7 @@ void lm_host_destroy(LmHost* lm) {
   for (auto& v : lm->vm) vox_destroy(&v);
   for (auto& v : lm->v2) vox_destroy(&v);
   for (auto& v : lm->vk) vox_destroy(&v);
+  gv_destroy(&lm->gv);
   for (void* p : lm->allocs) (void)guard_free(p);
   delete lm;
 }
@@ -417,6 +423,11 @@ int lm_host_set_keypose(LmHost* lm, const DevCtx& dfull, int slot, int kf_id, co
   if (kf_id < 0 || kf_id >= nkf || kf_id < nkf - L.K) { *err = "set_keypose: key frame not resident"; return ALEGO_ERR_ARG; }
   const int ring = kf_id % L.KR;
   if (hipMemcpy(L.kf_pose + ((size_t)slot * L.KR + ring) * 8, pose6, 6 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { *err = "set_keypose: copy failed"; return ALEGO_ERR_HIP; }
+  if (L.arc_frames_cap > 0) {   // the archived copy of the frame (alego_map_enable) follows
+    int stat[4];
+    if (hipMemcpy(stat, L.arc_stat + (size_t)slot * 4, sizeof(stat), hipMemcpyDeviceToHost) != hipSuccess) { *err = "set_keypose: copy failed"; return ALEGO_ERR_HIP; }
+    if (kf_id < stat[0] && hipMemcpy(L.arc_pose + ((size_t)slot * L.arc_frames_cap + kf_id) * 8, pose6, 6 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { *err = "set_keypose: copy failed"; return ALEGO_ERR_HIP; }
+  }
   return retransform(lm, dfull, slot, ring, err);
 }
 int lm_host_reset_window(LmHost* lm, int slot, std::string* err) {
@@ -476,7 +487,14 @@ int lm_host_add_keyframe(LmHost* lm, const DevCtx& dfull, int slot, const float*
   if (e == hipSuccess) e = hipMemcpy(li + LI_NKF, &nkf1, sizeof(int), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(li + LI_DIRTY, &one, sizeof(int), hipMemcpyHostToDevice);
   if (e != hipSuccess) { *err = std::string("add_keyframe: ") + hipGetErrorString(e); return ALEGO_ERR_HIP; }
-  return retransform(lm, dfull, slot, ring, err);
+  if (int r = retransform(lm, dfull, slot, ring, err)) return r;
+  if (L.arc_frames_cap > 0) {   // the archive (alego_map_enable) takes the inserted frame like a saved one
+    DevCtx d = dfull;
+    d.slot0 = slot; d.n_launch = 1;
+    launch_map_archive(d, L, 1, stream_of_slot(lm, slot));
+    if (hipStreamSynchronize(stream_of_slot(lm, slot)) != hipSuccess) { *err = "add_keyframe: archive append failed"; return ALEGO_ERR_HIP; }
+  }
+  return 0;
 }
 
 // ---- one registration sharded over the ranks of a communicator (alego_dist_*) ----
@@ -590,5 +608,132 @@ int lm_host_debug_get(LmHost* lm, int slot, const char* name, void* out, int cap
   if ((size_t)cap_bytes < n * esz) { *err = "debug_get: buffer too small"; return ALEGO_ERR_CAPACITY; }
   if (n && hipMemcpy(out, src, n * esz, hipMemcpyDeviceToHost) != hipSuccess) { *err = "debug_get: copy failed"; return ALEGO_ERR_HIP; }
   *count = (int)n; *dtype = dt;
+  return 0;
+}
+
+// ---- the global map (alego_map_* / alego_lm_get_local_map / alego_voxel_grid) ----
+int lm_host_map_enable(LmHost* lm, int max_frames, int max_points, std::string* err) {
+  LmCtx& L = lm->L;
+  if (L.arc_frames_cap > 0) { *err = "map_enable: already enabled"; return ALEGO_ERR_ARG; }
+  if (max_frames <= 0 || max_points <= 0) { *err = "map_enable: capacities must be positive"; return ALEGO_ERR_ARG; }
+  // the archive holds frame ids 0, 1, ...: it has to exist before the first key frame
+  std::vector<int> li((size_t)lm->n_slots * LI_COUNT);
+  if (hipMemcpy(li.data(), L.li, li.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { *err = "map_enable: device read failed"; return ALEGO_ERR_HIP; }
+  for (int s = 0; s < lm->n_slots; ++s) if (li[(size_t)s * LI_COUNT + LI_NKF] != 0) { *err = "map_enable: call it before the first key frame is saved"; return ALEGO_ERR_ARG; }
+  const size_t B = lm->n_slots;
+  LmCtx T = L;
+  bool ok = A(lm, &T.arc_pts, B * max_points, err) && A(lm, &T.arc_tab, B * max_frames * 4, err) && A(lm, &T.arc_pose, B * max_frames * 8, err) &&
+            A(lm, &T.arc_stat, B * 4, err) && A(lm, &lm->arc_off, (size_t)max_frames + 1, err);
+  if (!ok) return ALEGO_ERR_HIP;
+  if (int r = gv_reserve(&lm->gv, max_points, err)) return r == -3 ? ALEGO_ERR_CAPACITY : ALEGO_ERR_HIP;
+  T.arc_frames_cap = max_frames; T.arc_points_cap = max_points;
+  L = T;
+  return 0;
+}
+static int map_stat(LmHost* lm, int slot, int* st4, std::string* err) {
+  if (lm->L.arc_frames_cap <= 0) { *err = "the key-frame archive is off (alego_map_enable)"; return ALEGO_ERR_ARG; }
+  if (hipStreamSynchronize(stream_of_slot(lm, slot)) != hipSuccess || hipMemcpy(st4, lm->L.arc_stat + (size_t)slot * 4, 4 * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) {
+    *err = "map: device read failed"; return ALEGO_ERR_HIP;
+  }
+  return 0;
+}
+int lm_host_map_status(LmHost* lm, int slot, int* out4, std::string* err) {
+  int st[4];
+  if (int r = map_stat(lm, slot, st, err)) return r;
+  out4[0] = st[0]; out4[1] = st[1]; out4[2] = st[2]; out4[3] = lm->L.arc_points_cap;
+  return 0;
+}
+int lm_host_map_set_keyposes(LmHost* lm, int slot, int first, int n, const float* poses6, std::string* err) {
+  int st[4];
+  if (int r = map_stat(lm, slot, st, err)) return r;
+  if (first < 0 || n < 0 || first > st[0] || n > st[0] - first || (n > 0 && !poses6)) { *err = "map_set_keyposes: range beyond the archived frames"; return ALEGO_ERR_ARG; }
+  if (n == 0) return 0;
+  // poses6 is [n][6]; the archive keeps 8 floats per frame
+  if (hipMemcpy2D(lm->L.arc_pose + ((size_t)slot * lm->L.arc_frames_cap + first) * 8, 8 * sizeof(float), poses6, 6 * sizeof(float), 6 * sizeof(float), n,
+                  hipMemcpyHostToDevice) != hipSuccess) { *err = "map_set_keyposes: copy failed"; return ALEGO_ERR_HIP; }
+  return 0;
+}
+int lm_host_map_get_keyframe(LmHost* lm, int slot, int id, alego_keyframe* out, std::string* err) {
+  int st[4];
+  if (int r = map_stat(lm, slot, st, err)) return r;
+  if (id < 0 || id >= st[0]) { *err = "map_get_keyframe: frame not archived"; return ALEGO_ERR_ARG; }
+  const LmCtx& L = lm->L;
+  const size_t fs = (size_t)slot * L.arc_frames_cap + id;
+  int tab[4];
+  float kp[8];
+  if (hipMemcpy(tab, L.arc_tab + fs * 4, sizeof(tab), hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(kp, L.arc_pose + fs * 8, sizeof(kp), hipMemcpyDeviceToHost) != hipSuccess) { *err = "map_get_keyframe: copy failed"; return ALEGO_ERR_HIP; }
+  out->id = id;
+  for (int k = 0; k < 6; ++k) out->pose[k] = kp[k];
+  out->n_corner = tab[1]; out->n_surf = tab[2]; out->n_outlier = tab[3];
+  if ((out->corner && tab[1] > out->corner_cap) || (out->surf && tab[2] > out->surf_cap) || (out->outlier && tab[3] > out->outlier_cap)) { *err = "map_get_keyframe: buffer too small"; return ALEGO_ERR_CAPACITY; }
+  const float4* src = L.arc_pts + (size_t)slot * L.arc_points_cap + tab[0];
+  hipError_t e = hipSuccess;
+  if (out->corner && tab[1]) e = hipMemcpy(out->corner, src, (size_t)tab[1] * 16, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && out->surf && tab[2]) e = hipMemcpy(out->surf, src + tab[1], (size_t)tab[2] * 16, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && out->outlier && tab[3]) e = hipMemcpy(out->outlier, src + tab[1] + tab[2], (size_t)tab[3] * 16, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) { *err = std::string("map_get_keyframe: ") + hipGetErrorString(e); return ALEGO_ERR_HIP; }
+  return 0;
+}
+// the filtered (gv.out) or raw (gv.in) cloud of `n` points to the caller: count only, capacity error, or copy
+static int copy_out(const float4* src, int n, alego_point* out, int cap, const char* what, std::string* err) {
+  if (!out && cap == 0) return n;
+  if (cap < n || (n > 0 && !out)) { *err = std::string(what) + ": output capacity"; return ALEGO_ERR_CAPACITY; }
+  if (n > 0 && hipMemcpy(out, src, (size_t)n * 16, hipMemcpyDeviceToHost) != hipSuccess) { *err = std::string(what) + ": copy failed"; return ALEGO_ERR_HIP; }
+  return n;
+}
+int lm_host_map_assemble(LmHost* lm, int slot, int kinds, float leaf, alego_point* out, int cap, std::string* err) {
+  int st[4];
+  if (int r = map_stat(lm, slot, st, err)) return r;
+  if ((kinds & ~15) || !(kinds & 7) || cap < 0) { *err = "map_assemble: kinds must select surf / corner / outlier (optionally | FRAME_ID)"; return ALEGO_ERR_ARG; }
+  hipStream_t s = stream_of_slot(lm, slot);
+  GvCtx& G = lm->gv;
+  if (int r = gv_reserve(&G, lm->L.arc_points_cap, err)) return r == -3 ? ALEGO_ERR_CAPACITY : ALEGO_ERR_HIP;
+  launch_map_assemble(lm->L, slot, st[0], kinds, G.in, lm->arc_off, G.cnt, s);
+  int n = 0;
+  if (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(&n, G.cnt, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { *err = "map_assemble: assembly failed"; return ALEGO_ERR_HIP; }
+  if (leaf <= 0.f) return copy_out(G.in, n, out, cap, "map_assemble", err);
+  if (int r = gv_filter(&G, n, leaf, s, err)) return r == -3 ? ALEGO_ERR_CAPACITY : ALEGO_ERR_HIP;
+  int m = 0;
+  if (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(&m, G.cnt + 1, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { *err = "map_assemble: VoxelGrid failed"; return ALEGO_ERR_HIP; }
+  return copy_out(G.out, m, out, cap, "map_assemble", err);
+}
+int lm_host_map_keyposes(LmHost* lm, int slot, alego_point* out, int cap, std::string* err) {
+  int st[4];
+  if (int r = map_stat(lm, slot, st, err)) return r;
+  const int nf = st[0];
+  if (!out && cap == 0) return nf;
+  if (cap < nf || (nf > 0 && !out)) { *err = "map_keyposes: output capacity"; return ALEGO_ERR_CAPACITY; }
+  std::vector<float> kp((size_t)nf * 8);
+  if (nf > 0 && hipMemcpy(kp.data(), lm->L.arc_pose + (size_t)slot * lm->L.arc_frames_cap * 8, kp.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) { *err = "map_keyposes: copy failed"; return ALEGO_ERR_HIP; }
+  for (int i = 0; i < nf; ++i) out[i] = alego_point{kp[(size_t)i * 8 + 0], kp[(size_t)i * 8 + 1], kp[(size_t)i * 8 + 2], (float)i};   // saveMapCB :833-838
+  return nf;
+}
+int lm_host_get_local_map(LmHost* lm, int slot, alego_point* corner, int corner_cap, alego_point* surf, int surf_cap, int* n_out, std::string* err) {
+  const LmCtx& L = lm->L;
+  int li[LI_COUNT];
+  if (hipStreamSynchronize(stream_of_slot(lm, slot)) != hipSuccess || hipMemcpy(li, L.li + (size_t)slot * LI_COUNT, sizeof(li), hipMemcpyDeviceToHost) != hipSuccess) { *err = "get_local_map: device read failed"; return ALEGO_ERR_HIP; }
+  const int nc = li[LI_KDS_C], ns = li[LI_KDS_S];
+  n_out[0] = nc; n_out[1] = ns;
+  if ((corner && nc > corner_cap) || (surf && ns > surf_cap)) { *err = "get_local_map: buffer too small"; return ALEGO_ERR_CAPACITY; }
+  hipError_t e = hipSuccess;
+  if (corner && nc) e = hipMemcpy(corner, L.map_corner_ds + (size_t)slot * L.map_cap_c, (size_t)nc * 16, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && surf && ns) e = hipMemcpy(surf, L.map_surf_ds + (size_t)slot * L.map_cap_s, (size_t)ns * 16, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) { *err = std::string("get_local_map: ") + hipGetErrorString(e); return ALEGO_ERR_HIP; }
+  return 0;
+}
+int lm_host_voxel_grid(LmHost* lm, hipStream_t s, const alego_point* pts, int n, float leaf, alego_point* out, int cap, std::string* err) {
+  GvCtx& G = lm->gv;
+  if (n == 0) return copy_out(G.out, 0, out, cap, "voxel_grid", err);
+  if (int r = gv_reserve(&G, n, err)) return r == -3 ? ALEGO_ERR_CAPACITY : ALEGO_ERR_HIP;
+  if (hipMemcpyAsync(G.in, pts, (size_t)n * 16, hipMemcpyHostToDevice, s) != hipSuccess || hipMemcpyAsync(G.cnt, &n, sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess) { *err = "voxel_grid: upload failed"; return ALEGO_ERR_HIP; }
+  if (int r = gv_filter(&G, n, leaf, s, err)) return r == -3 ? ALEGO_ERR_CAPACITY : ALEGO_ERR_HIP;
+  int m = 0;
+  if (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(&m, G.cnt + 1, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { *err = "voxel_grid: filter failed"; return ALEGO_ERR_HIP; }
+  return copy_out(G.out, m, out, cap, "voxel_grid", err);
+}
+int lm_host_set_gv_small_max(LmHost* lm, int v) {
+  gv_destroy(&lm->gv);   // (the one-workgroup job is re-created with the new capacity by the next call)
+  lm->gv.small_max = std::max(0, v);
   return 0;
 }

@@ -9,6 +9,10 @@
 //       --standalone selects the IP.cpp twin of ImageProjection: RFANS-16M ring table + removeClosedPointCloud(1.0 m)
 //       (IP.cpp:77-104,117,142-172; utility.h:81); the default is the nodelet (imageProjection.cpp) on the reference geometry
 //       16 x 4000 (utility.h:50-55).  --list prints the bag's topics and needs no GPU.
+//   either source + --save-map DIR [--map-leaf L] [--map-frames N] [--map-points N]
+//       keeps every key frame on the device (alego_map_enable, capacities per stream) and, at the end, writes saveMapCB's files
+//       (laserMapping.cpp:826-874: keypose.pcd, corner.pcd, surf.pcd, outlier.pcd) and global.pcd, the cloud
+//       visualizeGlobalMapThread publishes (:598-616), VoxelGrid(L)-filtered when --map-leaf is given.
 // Every scan goes through ImageProjection -> LaserOdometry -> LaserMapping with one alego_scan_process call, as a single nodelet
 // manager would run them (launch/test.launch:6-10); every new key frame is pulled across the boundary the way the reference's
 // pose-graph thread reads cloud_keyposes_6d_ (laserMapping.cpp:586-596); one JSON line with the final poses is printed.
@@ -26,7 +30,9 @@
 extern "C" int alego_synth_scan(const alego_params* P, int stream, long scan_index, int flags, alego_point* out, int cap);
 
 int main(int argc, char** argv) {
-  std::string bag_path, topic = "/lslidar_point_cloud";
+  std::string bag_path, topic = "/lslidar_point_cloud", map_dir;
+  float map_leaf = 0.f;
+  int map_frames = 4096, map_points = 1 << 24;
   bool list_only = false, standalone = false;
   long max_scans = -1;
   int n_scan = 16, horizon = -1;
@@ -41,6 +47,10 @@ int main(int argc, char** argv) {
     else if (a == "--scans") max_scans = std::atol(val());
     else if (a == "--n-scan") n_scan = std::atoi(val());
     else if (a == "--horizon") horizon = std::atoi(val());
+    else if (a == "--save-map") map_dir = val();
+    else if (a == "--map-leaf") map_leaf = std::atof(val());
+    else if (a == "--map-frames") map_frames = std::atoi(val());
+    else if (a == "--map-points") map_points = std::atoi(val());
     else pos.push_back(argv[i]);
   }
   alego_bag* bag = nullptr;
@@ -82,6 +92,9 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "alego_create failed (%d): there is no CPU fallback, an MI355X is required\n", rc);
     return 1;
   }
+  if (!map_dir.empty() && alego_map_enable(h, map_frames, map_points) != ALEGO_OK) {
+    std::fprintf(stderr, "map_enable: %s\n", alego_last_error(h)); alego_destroy(h); return 1;
+  }
   alego_pose odom{}, mapped{};
   int key_frames = 0, last_flags = 0, dropped = 0;
   float last_key_pose[6] = {0, 0, 0, 0, 0, 0};
@@ -113,7 +126,26 @@ int main(int argc, char** argv) {
               n_scans, dropped, last_flags, key_frames, alego_lm_keyframe_count(h, 0), odom.t[0], odom.t[1], odom.t[2], mapped.t[0], mapped.t[1], mapped.t[2],
               mapped.params[0], mapped.params[1], mapped.params[2], mapped.params[3], mapped.params[4], mapped.params[5],
               last_key_pose[0], last_key_pose[1], last_key_pose[2], last_key_pose[3], last_key_pose[4], last_key_pose[5]);
+  int rc = 0;
+  if (!map_dir.empty()) {   // saveMapCB + the /laser_cloud_surround cloud, from the archive at the key poses that hold now
+    struct { const char* name; int kinds; float leaf; } files[] = {
+        {"corner.pcd", ALEGO_MAP_CORNER | ALEGO_MAP_FRAME_ID, 0.f}, {"surf.pcd", ALEGO_MAP_SURF | ALEGO_MAP_FRAME_ID, 0.f},
+        {"outlier.pcd", ALEGO_MAP_OUTLIER | ALEGO_MAP_FRAME_ID, 0.f}, {"global.pcd", ALEGO_MAP_SURF | ALEGO_MAP_CORNER | ALEGO_MAP_OUTLIER, map_leaf}};
+    std::vector<alego_point> cloud;
+    int n = alego_map_keyposes(h, 0, nullptr, 0);
+    if (n >= 0) { cloud.resize(n > 0 ? n : 1); n = alego_map_keyposes(h, 0, cloud.data(), n); }
+    if (n < 0 || alego_write_pcd((map_dir + "/keypose.pcd").c_str(), cloud.data(), n) != ALEGO_OK) rc = 1;
+    for (const auto& f : files) {
+      if (rc) break;
+      n = alego_map_assemble(h, 0, f.kinds, f.leaf, nullptr, 0);
+      if (n >= 0) { cloud.resize(n > 0 ? n : 1); n = alego_map_assemble(h, 0, f.kinds, f.leaf, cloud.data(), n); }
+      if (n < 0 || alego_write_pcd((map_dir + "/" + f.name).c_str(), cloud.data(), n) != ALEGO_OK) rc = 1;
+    }
+    int32_t st[4];
+    if (!rc && alego_map_status(h, 0, st) == ALEGO_OK && st[1] > 0) std::fprintf(stderr, "map: %d key frames did not fit the archive (--map-frames / --map-points)\n", st[1]);
+    if (rc) std::fprintf(stderr, "save map to %s: %s\n", map_dir.c_str(), alego_last_error(h));
+  }
   alego_destroy(h);
   if (bag) alego_bag_close(bag);
-  return 0;
+  return rc;
 }

@@ -274,6 +274,56 @@ int alego_lm_apply_correction(alego_handle* h, int slot, const double rc[12]);
 int alego_lm_add_keyframe(alego_handle* h, int slot, const float pose6[6], const alego_point* corner, int32_t n_corner,
                           const alego_point* surf, int32_t n_surf, const alego_point* outlier, int32_t n_outlier);
 
+/* ---- the global map (saveMapCB, laserMapping.cpp:826-874; visualizeGlobalMapThread, :598-631) -----------------------------
+ * The device keeps only the recent_keyframe_num + 1 newest key frames.  The opt-in ARCHIVE keeps every key frame of every slot on the
+ * device — its sensor-frame clouds exactly as the ring stores them (after any kf_cap_* truncation) and its f32 key pose — appended by a
+ * kernel behind the key-frame store on the slot's own stream, so the batch path needs no host synchronisation per scan (the key-frame
+ * counterpart of alego_trajectory_enable).  The map is re-assembled from the archive at the poses that hold NOW, as the reference does
+ * after correctPoses (:561-584) rewrote them.
+ *
+ * alego_map_enable: capacities per slot (device memory: max_points * 16 B + max_keyframes * 48 B per slot).  Call it once, before the
+ * first key frame is saved; a second call, a call after key frames exist and a call on a handle set up with alego_stream_setup return
+ * ALEGO_ERR_ARG.  A frame that does not fit is dropped whole and counted, and so is every later frame: the archived frames are always
+ * the prefix 0 .. frames stored - 1 of the key-frame ids.  alego_lm_add_keyframe appends too; alego_lm_set_keypose also updates the
+ * archived pose of the frame.  Every other alego_map_* call returns ALEGO_ERR_ARG while the archive is off.
+ * alego_map_status: out = {frames stored, frames dropped, points stored, point capacity}.
+ * alego_map_set_keyposes: correctPoses (:569-578) over the whole graph: poses6[n][6] (x y z roll pitch yaw) of archived frames
+ *   first .. first + n - 1.  It does not touch the resident ring (resident frames still go through alego_lm_set_keypose).
+ * alego_map_get_keyframe: any archived frame, as alego_lm_get_keyframe returns a resident one. */
+int alego_map_enable(alego_handle* h, int32_t max_keyframes, int32_t max_points);
+int alego_map_status(alego_handle* h, int slot, int32_t out[4]);
+int alego_map_set_keyposes(alego_handle* h, int slot, int32_t first, int32_t n, const float* poses6);
+int alego_map_get_keyframe(alego_handle* h, int slot, int32_t id, alego_keyframe* out);
+/* kinds of alego_map_assemble */
+enum {
+  ALEGO_MAP_SURF = 1,
+  ALEGO_MAP_CORNER = 2,
+  ALEGO_MAP_OUTLIER = 4,
+  ALEGO_MAP_FRAME_ID = 8   /* intensity = frame index (transformPointCloud(cloud, pose, idx), laserMapping.h:178-186; saveMapCB :844-852) */
+};
+/* The global map of `slot`: archived frames in id order, each transformed by its archived key pose (transformPointCloud,
+ * laserMapping.h:164-177), within a frame surf, corner, outlier restricted to `kinds` (:607-612).  saveMapCB's corner.pcd is
+ * kinds = CORNER | FRAME_ID (surf.pcd, outlier.pcd likewise); the /laser_cloud_surround cloud is SURF | CORNER | OUTLIER.
+ * leaf > 0: the concatenation goes through pcl::VoxelGrid(leaf) (as alego_voxel_grid) before the copy-out; leaf <= 0: the raw
+ * concatenation, which is what saveMapCB writes.  Returns the number of points; out == NULL with cap == 0 only counts; a cap smaller
+ * than the count returns ALEGO_ERR_CAPACITY and writes nothing. */
+int alego_map_assemble(alego_handle* h, int slot, int kinds, float leaf, alego_point* out, int32_t cap);
+/* saveMapCB's keypose.pcd (:833-838): xyz of every archived frame's key pose, intensity = index.  Returns the count (out == NULL with
+ * cap == 0 only counts). */
+int alego_map_keyposes(alego_handle* h, int slot, alego_point* out, int32_t cap);
+/* corner_from_map_ds_ / surf_from_map_ds_ of the last mapping frame of `slot` (the local map visualizeGlobalMapThread publishes on
+ * /recent_keyframes, :618-628); n_out = {corner points, surf points}; either buffer may be NULL (count only). */
+int alego_lm_get_local_map(alego_handle* h, int slot, alego_point* corner, int32_t corner_cap, alego_point* surf, int32_t surf_cap, int32_t n_out[2]);
+/* pcl::VoxelGrid<PointXYZI>::filter(leaf) of a host cloud of any size (f32 getMinMax3D, the dx dy dz > INT_MAX "leaf size too small"
+ * rule that returns the input unchanged, PCL's 32-bit voxel index, stable order inside a voxel, f32 sums in input order divided by the
+ * count), bit-exact.  Small clouds go to the one-workgroup kernels of the local maps, large ones to a multi-kernel radix sort spread
+ * over the whole device.  leaf must be > 0.  Returns the number of voxels (out == NULL with cap == 0 only counts);
+ * ALEGO_ERR_CAPACITY when cap is too small (nothing written).  Scratch grows with the largest n seen and stays with the handle. */
+int alego_voxel_grid(alego_handle* h, const alego_point* pts, int32_t n, float leaf, alego_point* out, int32_t cap);
+/* pcl::io::savePCDFile's product as PCD v0.7, DATA binary, FIELDS x y z intensity (F 4 each), WIDTH n, HEIGHT 1, VIEWPOINT 0 0 0 1 0 0 0
+ * (saveMapCB :869-872).  Host only.  0 or ALEGO_ERR_ARG (bad arguments, the file cannot be written). */
+int alego_write_pcd(const char* path, const alego_point* pts, int32_t n);
+
 /* ---- loop closure (laserMapping.cpp:633-824): the host keeps the pose graph (GTSAM in the reference) and every key frame; the
  * library does the per-point work of one closure attempt.
  *   alego_loop_detect        detectLoopClosure's choice (:771-790), plain host code: the key pose nearest to `cur_xyz` within
