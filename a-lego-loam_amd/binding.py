@@ -31,6 +31,7 @@ EXPORTS = [
     "alego_bag_read_raw", "alego_bag_read_pc2", "alego_handle_lock", "alego_handle_unlock",
     "alego_map_enable", "alego_map_status", "alego_map_set_keyposes", "alego_map_get_keyframe", "alego_map_assemble", "alego_map_keyposes",
     "alego_lm_get_local_map", "alego_voxel_grid", "alego_write_pcd",
+    "alego_map_get_stamps", "alego_map_set_stamps", "alego_loop_search", "alego_loop_constraint", "alego_debug_nn1",
 ]
 
 REPLAY_PINGPONG = 0x100
@@ -93,6 +94,19 @@ class KfIn(C.Structure):
 class IcpResult(C.Structure):
     _fields_ = [("converged", C.c_int32), ("iterations", C.c_int32), ("n_source", C.c_int32), ("n_target", C.c_int32),
                 ("fitness", C.c_double), ("correction", C.c_float * 16)]
+
+
+class LoopResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("latest_id", C.c_int32), ("closest_id", C.c_int32), ("converged", C.c_int32), ("iterations", C.c_int32),
+                ("n_source", C.c_int32), ("n_target", C.c_int32), ("fitness", C.c_double), ("correction", C.c_float * 16),
+                ("t_correct", C.c_float * 16), ("between", C.c_double * 12), ("noise_variance", C.c_double)]
+
+
+def _loop_result(r):
+    return dict(status=int(r.status), latest_id=int(r.latest_id), closest_id=int(r.closest_id), converged=int(r.converged),
+                iterations=int(r.iterations), n_source=int(r.n_source), n_target=int(r.n_target), fitness=float(r.fitness),
+                T=np.array(r.correction[:], np.float32).reshape(4, 4), t_correct=np.array(r.t_correct[:], np.float32).reshape(4, 4),
+                between=np.array(r.between[:], np.float64).reshape(3, 4), noise_variance=float(r.noise_variance))
 
 
 class Pc2Field(C.Structure):
@@ -243,6 +257,11 @@ def lib():
         L.alego_map_keyposes.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int32]
         L.alego_lm_get_local_map.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
         L.alego_voxel_grid.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_int32]
+        L.alego_map_get_stamps.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.c_void_p]
+        L.alego_map_set_stamps.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.c_void_p]
+        L.alego_loop_search.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(LoopResult)]
+        L.alego_loop_constraint.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.alego_debug_nn1.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
         L.alego_write_pcd.argtypes = [C.c_char_p, C.c_void_p, C.c_int32]
         L.alego_bag_read_pc2.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
         if L.alego_params_sizeof() != C.sizeof(AlegoParams):
@@ -287,6 +306,19 @@ def loop_detect(params, keyposes6, stamps, cur_xyz):
     t = np.ascontiguousarray(stamps, np.float64)
     c = np.ascontiguousarray(cur_xyz, np.float64)
     return int(lib().alego_loop_detect(C.byref(params), kp.ctypes.data, t.ctypes.data, kp.shape[0], c.ctypes.data))
+
+
+def loop_constraint(correction, latest_pose6, closest_pose6):
+    """:714-730 on the host: (t_correct 4x4 f32, between 3x4 f64 [R | t]) from an ICP correction and the newest / closest key poses"""
+    c = np.ascontiguousarray(correction, np.float32).reshape(16)
+    a = np.ascontiguousarray(latest_pose6, np.float32).reshape(6)
+    b = np.ascontiguousarray(closest_pose6, np.float32).reshape(6)
+    t = np.zeros(16, np.float32)
+    bt = np.zeros(12, np.float64)
+    rc = lib().alego_loop_constraint(c.ctypes.data, a.ctypes.data, b.ctypes.data, t.ctypes.data, bt.ctypes.data)
+    if rc != 0:
+        raise AlegoError(f"alego_loop_constraint failed ({rc})")
+    return t.reshape(4, 4), bt.reshape(3, 4)
 
 
 def pc2_to_points(data: bytes, width, height, point_step, row_step, fields, is_bigendian=False, cap=None):
@@ -617,6 +649,17 @@ class Handle:
         n = self._check(lib().alego_map_assemble(self._h, slot, kinds, leaf, out.ctypes.data, cap), "alego_map_assemble")
         return out[:n].copy()
 
+    def map_get_stamps(self, first=0, n=None, slot=0):
+        if n is None:
+            n = self.map_status(slot)[0] - first
+        out = np.zeros(max(n, 1), np.float64)
+        self._check(lib().alego_map_get_stamps(self._h, slot, first, n, out.ctypes.data), "alego_map_get_stamps")
+        return out[:n].copy()
+
+    def map_set_stamps(self, first, stamps, slot=0):
+        a = np.ascontiguousarray(stamps, np.float64).reshape(-1)
+        self._check(lib().alego_map_set_stamps(self._h, slot, first, a.shape[0], a.ctypes.data), "alego_map_set_stamps")
+
     def map_keyposes(self, slot=0):
         n = self._check(lib().alego_map_keyposes(self._h, slot, None, 0), "alego_map_keyposes")
         out = np.empty((max(n, 1), 4), np.float32)
@@ -707,6 +750,23 @@ class Handle:
                     "alego_loop_closure_icp")
         return dict(converged=int(out.converged), iterations=int(out.iterations), n_source=int(out.n_source), n_target=int(out.n_target),
                     fitness=float(out.fitness), T=np.array(out.correction[:], np.float32).reshape(4, 4)), tgt[:out.n_target].copy()
+
+    def loop_search(self, slots):
+        """alego_loop_search: one dict per listed slot (status, ids, converged, iterations, n_source, n_target, fitness, T, t_correct,
+        between, noise_variance)"""
+        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        out = (LoopResult * max(sl.shape[0], 1))()
+        self._check(lib().alego_loop_search(self._h, sl.ctypes.data, sl.shape[0], out), "alego_loop_search")
+        return [_loop_result(out[i]) for i in range(sl.shape[0])]
+
+    def debug_nn1(self, tgt, queries):
+        """the grid 1-NN of alego_loop_search alone: (index, f32 squared distance) per query"""
+        t = np.ascontiguousarray(tgt, np.float32).reshape(-1, 4)
+        q = np.ascontiguousarray(queries, np.float32).reshape(-1, 4)
+        idx = np.zeros(max(q.shape[0], 1), np.int32)
+        d2 = np.zeros(max(q.shape[0], 1), np.float32)
+        self._check(lib().alego_debug_nn1(self._h, t.ctypes.data, t.shape[0], q.ctypes.data, q.shape[0], idx.ctypes.data, d2.ctypes.data), "alego_debug_nn1")
+        return idx[:q.shape[0]].copy(), d2[:q.shape[0]].copy()
 
     # ---- one registration sharded over the ranks of an RCCL communicator (BASELINE config 5) ----
     def dist_init(self, rank, world, unique_id: bytes):

@@ -38,6 +38,11 @@ const double* lm_host_stage_odom(LmHost* lm);
 void launch_dbg_eval_blocks(int type, int n, const double* geom13, const double* params6, double* res, double* jac6, hipStream_t st);
 int icp_run(const alego_params& P, const alego_kf_in* latest, const alego_kf_in* history, int n_history, alego_icp_result* out,
             alego_point* target_out, int target_cap, hipStream_t st, std::string* err);
+struct LcCtx;   // kernels_loop.hip: the batched loop-closure search
+int loop_search(LcCtx** pc, const LmCtx& L, const alego_params& P, int n_slots, const int* slots, int n, alego_loop_result* res, hipStream_t st, std::string* err);
+void loop_ctx_destroy(LcCtx* C);
+void loop_ctx_set_budget(LcCtx** pc, long long points);
+int loop_debug_nn1(const alego_point* tgt, int n_tgt, const alego_point* q, int nq, int32_t* idx, float* d2, hipStream_t st, std::string* err);
 void launch_dbg_transform_to_start(const double* params6, const float4* pts, int n, float4* out, hipStream_t st);
 int ip_configure(const DevCtx& d);
 int lo_configure();
@@ -78,6 +83,7 @@ struct alego_handle {
   std::vector<hipEvent_t> ev_pool;
   size_t ev_next = 0;
   bool map_on = false;         // alego_map_enable: the key-frame archive exists
+  LcCtx* lc = nullptr;         // alego_loop_search: detection / chunk scratch, allocated by the first call and kept
 };
 
 namespace {
@@ -370,6 +376,7 @@ void alego_destroy(alego_handle* h) {
   (void)sync_all(h);
   if (g_prof == &h->prof) g_prof = nullptr;
   if (h->lm) lm_host_destroy(h->lm);
+  loop_ctx_destroy(h->lc);
   for (void* p : h->allocs) (void)guard_free(p);
   for (hipStream_t s : h->streams) hipStreamDestroy(s);
   for (hipStream_t s : h->back) hipStreamDestroy(s);
@@ -717,6 +724,7 @@ int alego_lo_process(alego_handle* h, const alego_seg_out* in, alego_feat_out* f
   HIP_TRY(h, hipMemcpyAsync(d.scal + SC_M, &in->m, 4, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipMemcpyAsync(d.ori, in->orientation, 12, hipMemcpyHostToDevice, h->stream));       // seg_info's start / end orientation: adjustDistortion reads them
   HIP_TRY(h, hipMemcpyAsync(d.scan_stamp, &in->stamp, 8, hipMemcpyHostToDevice, h->stream));
+  if (h->map_on && lm_host_map_mark_stamped(h->lm, 0, h->stream)) { h->err = "alego_lo_process: upload failed"; return ALEGO_ERR_HIP; }
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   if (int r = enqueue_scan(h, 0, 1, 0, 2, false)) return r;
   if (feat) { if (int r = download_feat(h, 0, feat)) return r; }
@@ -740,6 +748,7 @@ int alego_scan_process(alego_handle* h, int slot, const alego_scan_in* in, int s
   hipSetDevice(h->device);
   if (int r = alego_batch_load(h, slot, 0, in->pts, in->n)) return r;
   HIP_TRY(h, hipMemcpyAsync(h->d.scan_stamp + slot, &in->stamp, 8, hipMemcpyHostToDevice, stream_of(h, slot)));
+  if (h->map_on && lm_host_map_mark_stamped(h->lm, slot, stream_of(h, slot))) { h->err = "alego_scan_process: upload failed"; return ALEGO_ERR_HIP; }
   HIP_TRY(h, hipStreamSynchronize(stream_of(h, slot)));   // (`in` is the caller's)
   if (int r = enqueue_scan(h, slot, 1, 0, stages, seg && seg->label_image)) return r;
   if (seg) { if (int r = download_seg(h, slot, seg)) return r; seg->stamp = in->stamp; }
@@ -1033,6 +1042,7 @@ int alego_debug_set_option(alego_handle* h, const char* name, int value) {
   else if (s == "ALEGO_IP_FAST") d.ip_fast = h->ip_fast_capable & value;
   else if (s == "ALEGO_POKE_GUARD") { HIP_TRY(h, hipMemset(d.scal + (size_t)d.n_slots * SC_COUNT + value, 0xFF, 4)); }   // tests of the guard pages: a write `value` ints past the end of an array
   else if (s == "ALEGO_GV_SMALL_MAX") { HIP_TRY(h, sync_all(h)); return lm_host_set_gv_small_max(h->lm, value); }   // tools/gmap_timing.py: largest cloud alego_voxel_grid gives to one workgroup
+  else if (s == "ALEGO_LC_BUDGET") loop_ctx_set_budget(&h->lc, value);   // tests / tools: raw sub-map points per chunk of alego_loop_search
   else if (s == "ALEGO_SHARD_SLICE") return lm_host_debug_slice(h->lm, value & 0xff, value >> 8, &h->err);   // tests: rank | world << 8 without a communicator
   else { h->err = "unknown option " + s; return ALEGO_ERR_ARG; }
   return 0;
@@ -1061,6 +1071,86 @@ int alego_loop_closure_icp(alego_handle* h, const alego_kf_in* latest, const ale
   hipSetDevice(h->device);
   g_prof = &h->prof;
   return icp_run(h->P, latest, history, n_history, out, target_out, target_out ? target_cap : 0, h->stream, &h->err);
+}
+
+int alego_loop_search(alego_handle* h, const int32_t* slots, int32_t n, alego_loop_result* out) {
+  if (!h || n < 0 || (n > 0 && (!slots || !out))) return ALEGO_ERR_ARG;
+  if (!h->map_on) { h->err = "alego_loop_search: the key-frame archive is off (alego_map_enable)"; return ALEGO_ERR_ARG; }
+  for (int i = 0; i < n; ++i) if (slots[i] < 0 || slots[i] >= h->d.n_slots) { h->err = "alego_loop_search: slot out of range"; return ALEGO_ERR_ARG; }
+  hipSetDevice(h->device);
+  g_prof = &h->prof;
+  HIP_TRY(h, sync_all(h));   // behind everything already queued on every stream group
+  return loop_search(&h->lc, *lm_host_ctx(h->lm), h->P, h->d.n_slots, slots, n, out, h->stream, &h->err);
+}
+// :714-730 on the host: t_correct = correction * initial_guess (Matrix4f), r_correct = Quaternionf(t_correct rotation), pose_from =
+// Pose3(Rot3::Quaternion(r_correct), t_correct translation), pose_to = Pose3(Rot3::RzRyRx(closest roll, pitch, yaw), closest xyz),
+// between = pose_from^-1 * pose_to.  initial_guess's rotation is AngleAxisf(yaw, Z) * AngleAxisf(pitch, Y) * AngleAxisf(roll, X) (:680-687).
+int alego_loop_constraint(const float correction[16], const float latest_pose6[6], const float closest_pose6[6], float t_correct[16], double between12[12]) {
+  if (!correction || !latest_pose6 || !closest_pose6 || !t_correct || !between12) return ALEGO_ERR_ARG;
+  const float* kp = latest_pose6;
+  const float hz = 0.5f * kp[5], hy = 0.5f * kp[4], hx = 0.5f * kp[3];
+  const float qz[4] = {std::cos(hz), 0.f, 0.f, std::sin(hz)}, qy[4] = {std::cos(hy), 0.f, std::sin(hy), 0.f}, qx[4] = {std::cos(hx), std::sin(hx), 0.f, 0.f};
+  float t[4], q[4];
+  t[0] = qz[0] * qy[0] - qz[1] * qy[1] - qz[2] * qy[2] - qz[3] * qy[3];
+  t[1] = qz[0] * qy[1] + qz[1] * qy[0] + qz[2] * qy[3] - qz[3] * qy[2];
+  t[2] = qz[0] * qy[2] + qz[2] * qy[0] + qz[3] * qy[1] - qz[1] * qy[3];
+  t[3] = qz[0] * qy[3] + qz[3] * qy[0] + qz[1] * qy[2] - qz[2] * qy[1];
+  q[0] = t[0] * qx[0] - t[1] * qx[1] - t[2] * qx[2] - t[3] * qx[3];
+  q[1] = t[0] * qx[1] + t[1] * qx[0] + t[2] * qx[3] - t[3] * qx[2];
+  q[2] = t[0] * qx[2] + t[2] * qx[0] + t[3] * qx[1] - t[1] * qx[3];
+  q[3] = t[0] * qx[3] + t[3] * qx[0] + t[1] * qx[2] - t[2] * qx[1];
+  const float w = q[0], x = q[1], y = q[2], z = q[3];
+  const float tx = 2 * x, ty = 2 * y, tz = 2 * z;
+  const float twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y, tyz = tz * y, tzz = tz * z;
+  const float G[16] = {1 - (tyy + tzz), txy - twz, txz + twy, kp[0], txy + twz, 1 - (txx + tzz), tyz - twx, kp[1],
+                       txz - twy, tyz + twx, 1 - (txx + tyy), kp[2], 0.f, 0.f, 0.f, 1.f};
+  for (int r = 0; r < 4; ++r)
+    for (int c = 0; c < 4; ++c) {
+      float acc = 0.f;
+      for (int k = 0; k < 4; ++k) acc += correction[r * 4 + k] * G[k * 4 + c];
+      t_correct[r * 4 + c] = acc;
+    }
+  // Eigen's Quaternionf(Matrix3f): trace branch or largest-diagonal branch, f32
+  const float* M = t_correct;
+  float qf[4];   // w, x, y, z
+  float tr = M[0] + M[5] + M[10];
+  if (tr > 0.f) {
+    tr = std::sqrt(tr + 1.f); qf[0] = 0.5f * tr; tr = 0.5f / tr;
+    qf[1] = (M[9] - M[6]) * tr; qf[2] = (M[2] - M[8]) * tr; qf[3] = (M[4] - M[1]) * tr;
+  } else {
+    int i = 0;
+    if (M[5] > M[0]) i = 1;
+    if (M[10] > M[i * 5]) i = 2;
+    const int j = (i + 1) % 3, k = (j + 1) % 3;
+    tr = std::sqrt(M[i * 5] - M[j * 5] - M[k * 5] + 1.f);
+    qf[1 + i] = 0.5f * tr; tr = 0.5f / tr;
+    qf[0] = (M[k * 4 + j] - M[j * 4 + k]) * tr; qf[1 + j] = (M[j * 4 + i] + M[i * 4 + j]) * tr; qf[1 + k] = (M[k * 4 + i] + M[i * 4 + k]) * tr;
+  }
+  // Rot3::Quaternion(w, x, y, z) = Eigen::Quaterniond(...).toRotationMatrix() (f64)
+  const double qw = qf[0], qxd = qf[1], qyd = qf[2], qzd = qf[3];
+  const double dx = 2 * qxd, dy = 2 * qyd, dz = 2 * qzd;
+  const double dwx = dx * qw, dwy = dy * qw, dwz = dz * qw, dxx = dx * qxd, dxy = dy * qxd, dxz = dz * qxd, dyy = dy * qyd, dyz = dz * qyd, dzz = dz * qzd;
+  const double Rf[9] = {1 - (dyy + dzz), dxy - dwz, dxz + dwy, dxy + dwz, 1 - (dxx + dzz), dyz - dwx, dxz - dwy, dyz + dwx, 1 - (dxx + dyy)};
+  const double tf[3] = {M[3], M[7], M[11]};
+  // Rot3::RzRyRx(roll, pitch, yaw) (f64)
+  const double cx = std::cos((double)closest_pose6[3]), sx = std::sin((double)closest_pose6[3]);
+  const double cy = std::cos((double)closest_pose6[4]), sy = std::sin((double)closest_pose6[4]);
+  const double cz = std::cos((double)closest_pose6[5]), sz = std::sin((double)closest_pose6[5]);
+  const double ss_ = sx * sy, cs_ = cx * sy, sc_ = sx * cy, cc_ = cx * cy, c_s = cx * sz, s_s = sx * sz, _cs = cy * sz, _cc = cy * cz, s_c = sx * cz, c_c = cx * cz;
+  const double ssc = ss_ * cz, csc = cs_ * cz, sss = ss_ * sz, css = cs_ * sz;
+  const double Rt[9] = {_cc, -c_s + ssc, s_s + csc, _cs, c_c + sss, -s_c + css, -sy, sc_, cc_};
+  const double tt[3] = {closest_pose6[0], closest_pose6[1], closest_pose6[2]};
+  // Pose3::between: R = Rf^T Rt, t = Rf^T (tt - tf)
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) between12[r * 4 + c] = Rf[0 * 3 + r] * Rt[0 * 3 + c] + Rf[1 * 3 + r] * Rt[1 * 3 + c] + Rf[2 * 3 + r] * Rt[2 * 3 + c];
+    between12[r * 4 + 3] = Rf[0 * 3 + r] * (tt[0] - tf[0]) + Rf[1 * 3 + r] * (tt[1] - tf[1]) + Rf[2 * 3 + r] * (tt[2] - tf[2]);
+  }
+  return ALEGO_OK;
+}
+int alego_debug_nn1(alego_handle* h, const alego_point* tgt, int32_t n_tgt, const alego_point* queries, int32_t n_q, int32_t* idx, float* d2) {
+  if (!h || n_tgt < 0 || n_q < 0 || (n_tgt > 0 && !tgt) || (n_q > 0 && (!queries || !idx || !d2))) return ALEGO_ERR_ARG;
+  hipSetDevice(h->device);
+  return loop_debug_nn1(tgt, n_tgt, queries, n_q, idx, d2, h->stream, &h->err);
 }
 
 // ---- one registration sharded over the GPUs of a node ---------------------------------------------------------------
@@ -1157,6 +1247,16 @@ int alego_map_assemble(alego_handle* h, int slot, int kinds, float leaf, alego_p
   hipSetDevice(h->device);
   g_prof = &h->prof;
   return lm_host_map_assemble(h->lm, slot, kinds, leaf, out, cap, &h->err);
+}
+int alego_map_get_stamps(alego_handle* h, int slot, int32_t first, int32_t n, double* out) {
+  if (int r = check_slot(h, slot)) return r;
+  hipSetDevice(h->device);
+  return lm_host_map_stamps(h->lm, slot, first, n, out, 0, &h->err);
+}
+int alego_map_set_stamps(alego_handle* h, int slot, int32_t first, int32_t n, const double* stamps) {
+  if (int r = check_slot(h, slot)) return r;
+  hipSetDevice(h->device);
+  return lm_host_map_stamps(h->lm, slot, first, n, const_cast<double*>(stamps), 1, &h->err);
 }
 int alego_map_keyposes(alego_handle* h, int slot, alego_point* out, int32_t cap) {
   if (int r = check_slot(h, slot)) return r;

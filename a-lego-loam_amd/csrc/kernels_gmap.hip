@@ -1,6 +1,6 @@
 // kernels_gmap.hip — the global map (saveMapCB, laserMapping.cpp:826-874; visualizeGlobalMapThread, :598-631) on gfx950.
 //
-//   map_archive        appends the key frame lm_store_kf just wrote (sensor-frame clouds + f32 key pose) to the slot's archive
+//   map_archive        appends the key frame lm_store_kf just wrote (sensor-frame clouds + f32 key pose + stamp) to the slot's archive
 //   map_offsets        exclusive prefix sum of the selected cloud sizes of the archived frames (one workgroup per slot)
 //   map_gather         every selected point transformed by its frame's archived key pose (transformPointCloud,
 //                      laserMapping.h:164-186), written once at its offset
@@ -65,6 +65,8 @@ __global__ void __launch_bounds__(GM_T) map_archive(DevCtx d, LmCtx L, int force
   if (threadIdx.x == 0) {
     int* tab = L.arc_tab + ((size_t)slot * L.arc_frames_cap + nf) * 4;
     tab[0] = np; tab[1] = nc; tab[2] = ns; tab[3] = no;
+    // the stamp of the scan that saved the frame; paths without stamps (batch, replay) number the slot's mapping frames
+    L.arc_stamp[(size_t)slot * L.arc_frames_cap + nf] = L.arc_stamped[slot] ? d.scan_stamp[slot] : (double)(li[LI_FRAME] - 1) * d.P.scan_period;
     st[0] = nf + 1; st[2] = np + nc + ns + no;
   }
 }

@@ -7,7 +7,7 @@
 //   icp_corr      one thread per source point: apply the last iteration's transformation (f32, as pcl::transformPointCloud), exact
 //                 1-NN in the target (f32 squared distance, ties -> lowest index; target tiled through LDS), correspondences within the
 //                 maximum distance feed the sums of the closed-form alignment (f64): per-workgroup partials in fixed order
-//   icp_step      one workgroup: partials -> sums, Horn's closed-form rigid transform (largest eigenvector of the 4x4 quaternion
+//   icp_step      one workgroup: partials -> sums, then (icp_math.h) Horn's closed-form rigid transform (largest eigenvector of the 4x4 quaternion
 //                 matrix; PCL's TransformationEstimationSVD solves the same least-squares problem by SVD in f32), accumulation of
 //                 final_transformation_ (Matrix4f), DefaultConvergenceCriteria (iterations, transformation epsilon, absolute and
 //                 relative MSE)
@@ -19,16 +19,11 @@
 #include "lm_ctx.h"
 #include "prof.h"
 #include "voxel.h"
+#include "icp_math.h"
 
 #define ICP_T 256
 #define ICP_TILE 2048
 
-struct IcpState {
-  float M[16];        // transformation_ of the last iteration (applied to the source by the next icp_corr)
-  float Tf[16];       // final_transformation_
-  double prev_mse, fitness;
-  int iter, done, converged, apply, n_src, n_tgt;
-};
 
 struct IcpFrame { float pose[6]; int off[4]; int dst[3]; };   // raw cloud offsets (corner, surf, outlier, end) and destination offsets of the three clouds
 
@@ -43,28 +38,6 @@ __global__ void __launch_bounds__(ICP_T) icp_build(const IcpFrame* frames, int n
     const int n = F.off[kind + 1] - F.off[kind];
     for (int i = blockIdx.x * ICP_T + threadIdx.x; i < n; i += gridDim.x * ICP_T) dst[F.dst[kind] + i] = kf_transform(m, raw[F.off[kind] + i]);
   }
-}
-
-// symmetric 4x4 eigen-decomposition, cyclic Jacobi (same algorithm as oracle_icp.h)
-DEV_INLINE void jacobi4(double A[4][4], double V[4][4], double lam[4]) {
-  for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) V[i][j] = i == j ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 60; ++sweep) {
-    double off = 0;
-    for (int p = 0; p < 4; ++p) for (int q = p + 1; q < 4; ++q) off += A[p][q] * A[p][q];
-    if (off < 1e-300) break;
-    for (int p = 0; p < 3; ++p)
-      for (int q = p + 1; q < 4; ++q) {
-        const double apq = A[p][q];
-        if (apq == 0.0) continue;
-        const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
-        const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-        for (int k = 0; k < 4; ++k) { const double akp = A[k][p], akq = A[k][q]; A[k][p] = c * akp - s * akq; A[k][q] = s * akp + c * akq; }
-        for (int k = 0; k < 4; ++k) { const double apk = A[p][k], aqk = A[q][k]; A[p][k] = c * apk - s * aqk; A[q][k] = s * apk + c * aqk; }
-        for (int k = 0; k < 4; ++k) { const double vkp = V[k][p], vkq = V[k][q]; V[k][p] = c * vkp - s * vkq; V[k][q] = s * vkp + c * vkq; }
-      }
-  }
-  for (int i = 0; i < 4; ++i) lam[i] = A[i][i];
 }
 
 // exact 1-NN of p in tgt[0..n): f32 squared distance as flann::L2_Simple, ties -> lowest index; the target goes through LDS in tiles
@@ -132,50 +105,7 @@ __global__ void icp_step(IcpState* S, const double* partial, int nwg, alego_para
   if (threadIdx.x != 0 || S->done) return;
   double T[17];
   for (int k = 0; k < 17; ++k) { double t = 0; for (int w = 0; w < nwg; ++w) t += partial[(size_t)w * 18 + k]; T[k] = t; }
-  const double n = T[16];
-  if (n < 3.0) { S->done = 1; S->converged = 0; return; }   // "Not enough correspondences found"
-  const double mse = T[15] / n;
-  const double ms[3] = {T[0] / n, T[1] / n, T[2] / n}, mt[3] = {T[3] / n, T[4] / n, T[5] / n};
-  double Mc[3][3];
-  for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) Mc[a][b] = T[6 + a * 3 + b] - n * ms[a] * mt[b];
-  double Nq[4][4] = {{Mc[0][0] + Mc[1][1] + Mc[2][2], Mc[1][2] - Mc[2][1], Mc[2][0] - Mc[0][2], Mc[0][1] - Mc[1][0]},
-                     {Mc[1][2] - Mc[2][1], Mc[0][0] - Mc[1][1] - Mc[2][2], Mc[0][1] + Mc[1][0], Mc[2][0] + Mc[0][2]},
-                     {Mc[2][0] - Mc[0][2], Mc[0][1] + Mc[1][0], -Mc[0][0] + Mc[1][1] - Mc[2][2], Mc[1][2] + Mc[2][1]},
-                     {Mc[0][1] - Mc[1][0], Mc[2][0] + Mc[0][2], Mc[1][2] + Mc[2][1], -Mc[0][0] - Mc[1][1] + Mc[2][2]}};
-  double V[4][4], lam[4];
-  jacobi4(Nq, V, lam);
-  int best = 0;
-  for (int i = 1; i < 4; ++i) if (lam[i] > lam[best]) best = i;
-  double q[4] = {V[0][best], V[1][best], V[2][best], V[3][best]};
-  if (q[0] < 0) for (int i = 0; i < 4; ++i) q[i] = -q[i];
-  const double nn = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-  const double w = q[0] / nn, x = q[1] / nn, y = q[2] / nn, z = q[3] / nn;
-  const double R[9] = {1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y), 2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
-                       2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)};
-  float M[16];
-  for (int a = 0; a < 3; ++a) {
-    for (int b = 0; b < 3; ++b) M[a * 4 + b] = (float)R[a * 3 + b];
-    M[a * 4 + 3] = (float)(mt[a] - (R[a * 3 + 0] * ms[0] + R[a * 3 + 1] * ms[1] + R[a * 3 + 2] * ms[2]));
-  }
-  M[12] = 0.f; M[13] = 0.f; M[14] = 0.f; M[15] = 1.f;
-  float Nf[16];   // final_transformation_ = transformation_ * final_transformation_ (Matrix4f)
-  for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) Nf[r * 4 + c] = M[r * 4 + 0] * S->Tf[0 * 4 + c] + M[r * 4 + 1] * S->Tf[1 * 4 + c] + M[r * 4 + 2] * S->Tf[2 * 4 + c] + M[r * 4 + 3] * S->Tf[3 * 4 + c];
-  for (int k = 0; k < 16; ++k) { S->M[k] = M[k]; S->Tf[k] = Nf[k]; }
-  S->apply = 1;
-  const int it = ++S->iter;
-  // DefaultConvergenceCriteria::hasConverged (absolute MSE 1e-12 is PCL's default; IterativeClosestPoint::computeTransformation sets the
-  // rotation threshold to 1 - transformation_epsilon_ (PCL 1.8: setRotationThreshold(1.0 - transformation_epsilon_)), i.e. 0.999999 with laserMapping.cpp:673)
-  bool conv = false;
-  if (it >= P.icp_max_iters) conv = true;
-  else {
-    const double cos_angle = 0.5 * ((double)M[0] + (double)M[5] + (double)M[10] - 1.0);
-    const double tr2 = (double)M[3] * M[3] + (double)M[7] * M[7] + (double)M[11] * M[11];
-    if (cos_angle >= 1.0 - P.icp_trans_eps && tr2 <= P.icp_trans_eps) conv = true;
-    else if (fabs(mse - S->prev_mse) < 1e-12) conv = true;
-    else if (fabs(mse - S->prev_mse) / S->prev_mse < P.icp_fitness_eps) conv = true;
-    else S->prev_mse = mse;
-  }
-  if (conv) { S->done = 1; S->converged = 1; }
+  icp_update(S, T, P);
 }
 
 __global__ void __launch_bounds__(ICP_T) icp_fitness(const IcpState* S, const float4* src, const float4* tgt, double* partial) {

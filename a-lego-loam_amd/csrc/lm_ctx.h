@@ -156,6 +156,9 @@ struct LmCtx {
   int* arc_tab;                                   // [slot][arc_frames_cap][4] point offset, n corner, n surf, n outlier
   float* arc_pose;                                // [slot][arc_frames_cap][8] x y z roll pitch yaw
   int* arc_stat;                                  // [slot][4] frames stored, frames dropped, points stored, -
+  double* arc_stamp;                              // [slot][arc_frames_cap] stamp of each frame (detectLoopClosure's key-pose time, :782)
+  int* arc_stamped;                               // [slot] 1: DevCtx::scan_stamp holds the slot's scan stamps (alego_scan_process / alego_lo_process);
+                                                  // 0: the stamp is (LI_FRAME - 1) * scan_period
 };
 
 #endif

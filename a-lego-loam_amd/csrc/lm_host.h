@@ -45,6 +45,12 @@ int lm_host_map_enable(LmHost* lm, int max_frames, int max_points, std::string* 
 int lm_host_map_status(LmHost* lm, int slot, int* out4, std::string* err);
 int lm_host_map_set_keyposes(LmHost* lm, int slot, int first, int n, const float* poses6, std::string* err);
 int lm_host_map_get_keyframe(LmHost* lm, int slot, int id, alego_keyframe* out, std::string* err);
+// stamps of archived frames first .. first + n - 1: read (write = 0) or overwrite (write = 1)
+int lm_host_map_stamps(LmHost* lm, int slot, int first, int n, double* stamps, int write, std::string* err);
+// the stamped entry points (alego_scan_process / alego_lo_process): the slot's archived frames take DevCtx::scan_stamp from now on
+int lm_host_map_mark_stamped(LmHost* lm, int slot, hipStream_t st);
+struct LmCtx;
+const LmCtx* lm_host_ctx(LmHost* lm);   // the device view (the batched loop-closure search reads the archive through it)
 int lm_host_map_assemble(LmHost* lm, int slot, int kinds, float leaf, alego_point* out, int cap, std::string* err);
 int lm_host_map_keyposes(LmHost* lm, int slot, alego_point* out, int cap, std::string* err);
 int lm_host_get_local_map(LmHost* lm, int slot, alego_point* corner, int corner_cap, alego_point* surf, int surf_cap, int* n_out, std::string* err);

@@ -623,7 +623,8 @@ int lm_host_map_enable(LmHost* lm, int max_frames, int max_points, std::string* 
   const size_t B = lm->n_slots;
   LmCtx T = L;
   bool ok = A(lm, &T.arc_pts, B * max_points, err) && A(lm, &T.arc_tab, B * max_frames * 4, err) && A(lm, &T.arc_pose, B * max_frames * 8, err) &&
-            A(lm, &T.arc_stat, B * 4, err) && A(lm, &lm->arc_off, (size_t)max_frames + 1, err);
+            A(lm, &T.arc_stat, B * 4, err) && A(lm, &T.arc_stamp, B * max_frames, err) && A(lm, &T.arc_stamped, B, err) &&
+            A(lm, &lm->arc_off, (size_t)max_frames + 1, err);
   if (!ok) return ALEGO_ERR_HIP;
   if (int r = gv_reserve(&lm->gv, max_points, err)) return r == -3 ? ALEGO_ERR_CAPACITY : ALEGO_ERR_HIP;
   T.arc_frames_cap = max_frames; T.arc_points_cap = max_points;
@@ -653,6 +654,21 @@ int lm_host_map_set_keyposes(LmHost* lm, int slot, int first, int n, const float
                   hipMemcpyHostToDevice) != hipSuccess) { *err = "map_set_keyposes: copy failed"; return ALEGO_ERR_HIP; }
   return 0;
 }
+int lm_host_map_stamps(LmHost* lm, int slot, int first, int n, double* stamps, int write, std::string* err) {
+  int st[4];
+  if (int r = map_stat(lm, slot, st, err)) return r;
+  if (first < 0 || n < 0 || first > st[0] || n > st[0] - first || (n > 0 && !stamps)) { *err = "map_stamps: range beyond the archived frames"; return ALEGO_ERR_ARG; }
+  if (n == 0) return 0;
+  double* dev = lm->L.arc_stamp + (size_t)slot * lm->L.arc_frames_cap + first;
+  if (hipMemcpy(write ? (void*)dev : (void*)stamps, write ? (const void*)stamps : (const void*)dev, (size_t)n * sizeof(double),
+                write ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost) != hipSuccess) { *err = "map_stamps: copy failed"; return ALEGO_ERR_HIP; }
+  return 0;
+}
+int lm_host_map_mark_stamped(LmHost* lm, int slot, hipStream_t st) {
+  static const int one = 1;
+  return lm->L.arc_frames_cap > 0 && hipMemcpyAsync(lm->L.arc_stamped + slot, &one, sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess ? ALEGO_ERR_HIP : 0;
+}
+const LmCtx* lm_host_ctx(LmHost* lm) { return &lm->L; }
 int lm_host_map_get_keyframe(LmHost* lm, int slot, int id, alego_keyframe* out, std::string* err) {
   int st[4];
   if (int r = map_stat(lm, slot, st, err)) return r;

@@ -13,6 +13,10 @@
 //       keeps every key frame on the device (alego_map_enable, capacities per stream) and, at the end, writes saveMapCB's files
 //       (laserMapping.cpp:826-874: keypose.pcd, corner.pcd, surf.pcd, outlier.pcd) and global.pcd, the cloud
 //       visualizeGlobalMapThread publishes (:598-616), VoxelGrid(L)-filtered when --map-leaf is given.
+//   either source + --loop-search EVERY
+//       keeps the archive on too and calls alego_loop_search every EVERY scans (performLoopClosure, laserMapping.cpp:652-733, on the
+//       device); every accepted constraint prints one line "loop: scan K slot S latest L closest C fitness F".  A host with a pose
+//       graph would add the Between factor here and write the corrected poses back.
 // Every scan goes through ImageProjection -> LaserOdometry -> LaserMapping with one alego_scan_process call, as a single nodelet
 // manager would run them (launch/test.launch:6-10); every new key frame is pulled across the boundary the way the reference's
 // pose-graph thread reads cloud_keyposes_6d_ (laserMapping.cpp:586-596); one JSON line with the final poses is printed.
@@ -32,7 +36,7 @@ extern "C" int alego_synth_scan(const alego_params* P, int stream, long scan_ind
 int main(int argc, char** argv) {
   std::string bag_path, topic = "/lslidar_point_cloud", map_dir;
   float map_leaf = 0.f;
-  int map_frames = 4096, map_points = 1 << 24;
+  int map_frames = 4096, map_points = 1 << 24, loop_every = 0;
   bool list_only = false, standalone = false;
   long max_scans = -1;
   int n_scan = 16, horizon = -1;
@@ -51,6 +55,7 @@ int main(int argc, char** argv) {
     else if (a == "--map-leaf") map_leaf = std::atof(val());
     else if (a == "--map-frames") map_frames = std::atoi(val());
     else if (a == "--map-points") map_points = std::atoi(val());
+    else if (a == "--loop-search") loop_every = std::atoi(val());
     else pos.push_back(argv[i]);
   }
   alego_bag* bag = nullptr;
@@ -92,7 +97,7 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "alego_create failed (%d): there is no CPU fallback, an MI355X is required\n", rc);
     return 1;
   }
-  if (!map_dir.empty() && alego_map_enable(h, map_frames, map_points) != ALEGO_OK) {
+  if ((!map_dir.empty() || loop_every > 0) && alego_map_enable(h, map_frames, map_points) != ALEGO_OK) {
     std::fprintf(stderr, "map_enable: %s\n", alego_last_error(h)); alego_destroy(h); return 1;
   }
   alego_pose odom{}, mapped{};
@@ -118,6 +123,12 @@ int main(int argc, char** argv) {
       if (alego_lm_get_keyframe(h, 0, -1, &kf) < 0) { std::fprintf(stderr, "get_keyframe: %s\n", alego_last_error(h)); alego_destroy(h); return 1; }
       ++key_frames;
       for (int i = 0; i < 6; ++i) last_key_pose[i] = kf.pose[i];
+    }
+    if (loop_every > 0 && (k + 1) % loop_every == 0) {
+      const int32_t slot = 0;
+      alego_loop_result lr{};
+      if (alego_loop_search(h, &slot, 1, &lr) != ALEGO_OK) { std::fprintf(stderr, "loop_search: %s\n", alego_last_error(h)); alego_destroy(h); return 1; }
+      if (lr.status == 2) std::printf("loop: scan %ld slot %d latest %d closest %d fitness %.9g\n", k, slot, lr.latest_id, lr.closest_id, lr.fitness);
     }
   }
   std::printf("{\"scans\": %ld, \"dropped\": %d, \"flags\": %d, \"key_frames\": %d, \"resident_key_frames\": %d, "

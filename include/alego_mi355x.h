@@ -281,7 +281,7 @@ int alego_lm_add_keyframe(alego_handle* h, int slot, const float pose6[6], const
  * counterpart of alego_trajectory_enable).  The map is re-assembled from the archive at the poses that hold NOW, as the reference does
  * after correctPoses (:561-584) rewrote them.
  *
- * alego_map_enable: capacities per slot (device memory: max_points * 16 B + max_keyframes * 48 B per slot).  Call it once, before the
+ * alego_map_enable: capacities per slot (device memory: max_points * 16 B + max_keyframes * 56 B + 4 B per slot).  Call it once, before the
  * first key frame is saved; a second call, a call after key frames exist and a call on a handle set up with alego_stream_setup return
  * ALEGO_ERR_ARG.  A frame that does not fit is dropped whole and counted, and so is every later frame: the archived frames are always
  * the prefix 0 .. frames stored - 1 of the key-frame ids.  alego_lm_add_keyframe appends too; alego_lm_set_keypose also updates the
@@ -289,8 +289,15 @@ int alego_lm_add_keyframe(alego_handle* h, int slot, const float pose6[6], const
  * alego_map_status: out = {frames stored, frames dropped, points stored, point capacity}.
  * alego_map_set_keyposes: correctPoses (:569-578) over the whole graph: poses6[n][6] (x y z roll pitch yaw) of archived frames
  *   first .. first + n - 1.  It does not touch the resident ring (resident frames still go through alego_lm_set_keypose).
- * alego_map_get_keyframe: any archived frame, as alego_lm_get_keyframe returns a resident one. */
+ * alego_map_get_keyframe: any archived frame, as alego_lm_get_keyframe returns a resident one.
+ * alego_map_get_stamps / alego_map_set_stamps: the stamps of archived frames first .. first + n - 1 (detectLoopClosure's key-pose time,
+ *   :782).  A frame saved by a scan of alego_scan_process, or of alego_lo_process + alego_lm_process (alego_seg_out.stamp), carries
+ *   that scan's stamp.  The batch and replay paths carry no stamps: there a frame's stamp is (m - 1) * scan_period, with m the slot's
+ *   mapping frames so far (scans with odometry) when it was saved.  alego_lm_add_keyframe stamps by the same rule.  Hosts that know
+ *   the true stamps, or that restore a session, overwrite them with alego_map_set_stamps. */
 int alego_map_enable(alego_handle* h, int32_t max_keyframes, int32_t max_points);
+int alego_map_get_stamps(alego_handle* h, int slot, int32_t first, int32_t n, double* out);
+int alego_map_set_stamps(alego_handle* h, int slot, int32_t first, int32_t n, const double* stamps);
 int alego_map_status(alego_handle* h, int slot, int32_t out[4]);
 int alego_map_set_keyposes(alego_handle* h, int slot, int32_t first, int32_t n, const float* poses6);
 int alego_map_get_keyframe(alego_handle* h, int slot, int32_t id, alego_keyframe* out);
@@ -349,6 +356,37 @@ typedef struct alego_icp_result {
 int alego_loop_detect(const alego_params* params, const float* keyposes6, const double* stamps, int32_t n, const double cur_xyz[3]);
 int alego_loop_closure_icp(alego_handle* h, const alego_kf_in* latest, const alego_kf_in* history, int32_t n_history,
                            alego_icp_result* out, alego_point* target_out, int32_t target_cap);
+
+/* ---- batched loop-closure search over the key-frame archive (needs alego_map_enable)
+ *   alego_loop_search        performLoopClosure + detectLoopClosure (:652-824) for every listed slot at once, from the archive: the
+ *                            current position is the slot's t_map2laser_ (alego_batch_get_pose's map pose) as f32; detection as
+ *                            alego_loop_detect on the archived key poses and stamps; source = the newest archived frame (surf,
+ *                            corner, outlier); target = frames closest ± lc_search_num below the newest, transformed by their archived
+ *                            poses and VoxelGrid(lc_leaf)-filtered; ICP as alego_loop_closure_icp.  out[i] belongs to slots[i].
+ *                            Synchronous; it runs behind the work already queued on every stream group and changes no device state
+ *                            (archive, poses, window): the host adds the Between factor to its graph and writes corrected poses back
+ *                            (alego_map_set_keyposes, alego_lm_set_keypose, alego_lm_reset_window, alego_lm_apply_correction).
+ *                            A slot's result does not depend on the other slots of the call.  ALEGO_ERR_ARG with the archive off or
+ *                            a slot out of range.
+ *   alego_loop_constraint    host only: t_correct and between from an ICP correction and the two key poses (:714-730), as
+ *                            alego_loop_search fills them in. */
+typedef struct alego_loop_result {
+  int32_t status;          /* 0 no candidate (or no key frame), 1 attempted and rejected (:697), 2 accepted, < 0 slot not searchable
+                              (-1: its archive dropped frames) */
+  int32_t latest_id, closest_id;
+  int32_t converged, iterations, n_source, n_target;
+  double fitness;          /* getFitnessScore() */
+  float correction[16];    /* getFinalTransformation(), row-major */
+  float t_correct[16];     /* correction * initial_guess (:714-715; initial_guess = the newest key pose, :680-687) */
+  double between[12];      /* pose_from.between(pose_to), row-major [R | t]: the BetweenFactor measurement (:716-730) */
+  double noise_variance;   /* (float)fitness: the diagonal Variances of constraint_noise_ (:724-728) */
+} alego_loop_result;
+int alego_loop_search(alego_handle* h, const int32_t* slots, int32_t n, alego_loop_result* out);
+int alego_loop_constraint(const float correction[16], const float latest_pose6[6], const float closest_pose6[6],
+                          float t_correct[16], double between12[12]);
+/* the exact 1-NN of alego_loop_search on its own (tests): for every query the target index with the smallest f32 squared distance
+ * ((dx dx + dy dy) + dz dz), the lowest index on ties; idx = -1, d2 = FLT_MAX for an empty target or a non-finite query */
+int alego_debug_nn1(alego_handle* h, const alego_point* tgt, int32_t n_tgt, const alego_point* queries, int32_t n_q, int32_t* idx, float* d2);
 
 /* ---- one scan-to-map registration sharded over the GPUs of a node (BASELINE.json config 5) ----------------
  * One process per GPU; every rank feeds its handle the SAME scans and so keeps a bit-identical replica of the stream's state
