@@ -166,186 +166,6 @@ __global__ void __launch_bounds__(MU_T) map_update(DevCtx d, LmCtx L, MapWork W)
     int* cnt = map_Ucnt(L, slot, m);
     const int* rec = L.rec + (size_t)slot * L.K;
     const int ncur = li[LI_REC_CNT];
-    {
-      // the two windows into LDS (s_add / s_rem double as staging), then their multiset difference by one thread:
-      // both are non-decreasing lists of frame ids
-      const int* prev = L.rec_prev + (size_t)slot * L.K;
-      const int np = li[LI_PREV_CNT], nkf = li[LI_NKF];
-      int* s_cur = reinterpret_cast<int*>(mu_smem);
-      int* s_prev = s_cur + MAP_KMAX;
-      for (int j = tid; j < ncur; j += MU_T) s_cur[j] = rec[j];
-      for (int j = tid; j < np; j += MU_T) s_prev[j] = prev[j];
-      __syncthreads();
-      if (tid == 0) {
-        int nr = 0, na = 0;
-        bool valid = li[LI_UVALID] != 0;
-        if (valid) {
-          int a = 0, b = 0;
-          while (a < np || b < ncur) {
-            if (b >= ncur || (a < np && s_prev[a] < s_cur[b])) { if (s_prev[a] < nkf - L.KR) valid = false; s_rem[nr++] = s_prev[a++] % L.KR; }   // its ring entry must still hold it
-            else if (a >= np || s_cur[b] < s_prev[a]) s_add[na++] = s_cur[b++] % L.KR;
-            else { ++a; ++b; }
-          }
-        }
-        if (!valid) {   // rebuild from nothing: every run of the window is inserted
-          nr = 0; na = 0;
-          for (int b = 0; b < ncur; ++b) s_add[na++] = s_cur[b] % L.KR;
-        }
-        s_nrem = nr; s_nadd = na; s_nU = valid ? li[LI_NU_C + m] : 0; s_err = 0;
-      }
-    }
-    __syncthreads();
-    int nU = s_nU;
-    u64* S_key = reinterpret_cast<u64*>(map_out(L, slot, m));   // scratch of the merges: the map's output buffer (rewritten by map_accum afterwards)
-    int* S_cnt = reinterpret_cast<int*>(S_key + cap);
-    const int nR = s_nrem == 1 ? run_n(L, slot, m, s_rem[0]) : 0, nA = s_nadd == 1 ? run_n(L, slot, m, s_add[0]) : 0;
-    const bool fast = nU > 0 && s_nrem <= 1 && s_nadd <= 1 && nR <= MU_FCAP && nA <= MU_FCAP;
-    if (fast) {
-      // ---- steady state: one run out, one run in.  The voxel keys of both runs are staged in LDS (sorted, as the runs are);
-      // every thread owns MU_E consecutive entries of the list, finds the pieces of both runs that fall into its key interval by
-      // binary search and merges the three sorted sequences: counts go down / up, new voxels are inserted in order, empty ones
-      // disappear.  No atomics; two passes (count, write) around one scan.
-      u64* s_kr = reinterpret_cast<u64*>(mu_smem);
-      u64* s_ka = s_kr + MU_FCAP;
-      __syncthreads();   // (the window lists staged in the same LDS are dead)
-      if (nR) { const float4* pts = run_pts(L, slot, m, s_rem[0]); for (int i = tid; i < nR; i += MU_T) s_kr[i] = vkey_of(pts[i], inv); }
-      if (nA) { const float4* pts = run_pts(L, slot, m, s_add[0]); for (int i = tid; i < nA; i += MU_T) s_ka[i] = vkey_of(pts[i], inv); }
-      __syncthreads();
-      auto lb = [](const u64* k, int n, u64 key) { int lo = 0, hi = n; while (lo < hi) { const int mid = (lo + hi) >> 1; if (k[mid] < key) lo = mid + 1; else hi = mid; } return lo; };
-      int out_off = 0;
-      for (int t0 = 0; t0 < nU; t0 += MU_T * MU_E) {
-        const int i0 = t0 + tid * MU_E, ne = max(0, min(MU_E, nU - i0));
-        u64 uk[MU_E];
-        int uc[MU_E];
-#pragma unroll
-        for (int e = 0; e < MU_E; ++e) { const int i = min(i0 + e, nU - 1); uk[e] = U[i]; uc[e] = cnt[i]; }
-        const u64 klo = i0 == 0 ? 0ull : uk[0];
-        const u64 khi = (ne > 0 && i0 + ne < nU) ? U[i0 + ne] : ~0ull;
-        const int pr0 = ne > 0 ? lb(s_kr, nR, klo) : 0, pa0 = ne > 0 ? lb(s_ka, nA, klo) : 0, pa1 = ne > 0 ? (khi == ~0ull ? nA : lb(s_ka, nA, khi)) : 0;
-        // the merge of this thread's interval; emit(key, count) is called for every voxel of the new list, in order
-        auto merge = [&](auto&& emit) {
-          int r = pr0, a = pa0;
-#pragma unroll
-          for (int e = 0; e < MU_E; ++e) {
-            if (e < ne) {
-              const u64 key = uk[e];
-              while (a < pa1 && s_ka[a] < key) { const u64 k2 = s_ka[a]; int c = 0; while (a < pa1 && s_ka[a] == k2) { ++c; ++a; } emit(k2, c); }
-              while (r < nR && s_kr[r] < key) { ++r; s_err = 1; }   // a point that left was never counted: list out of sync
-              int c = uc[e];
-              while (r < nR && s_kr[r] == key) { --c; ++r; }
-              while (a < pa1 && s_ka[a] == key) { ++c; ++a; }
-              if (c > 0) emit(key, c);
-            }
-          }
-          while (a < pa1) { const u64 k2 = s_ka[a]; int c = 0; while (a < pa1 && s_ka[a] == k2) { ++c; ++a; } emit(k2, c); }
-        };
-        int nout = 0;
-        merge([&](u64, int) { ++nout; });
-        int tot;
-        int pos = out_off + block_excl_scan(nout, s_w, &tot);
-        merge([&](u64 k, int c) { if (pos < cap) { S_key[pos] = k; S_cnt[pos] = c; } ++pos; });
-        out_off += tot;
-      }
-      __threadfence_block();
-      __syncthreads();
-      int nU2 = out_off;
-      if (nU2 > cap) { nU2 = cap; if (tid == 0) s_err = 2; }
-      for (int i = tid; i < nU2; i += MU_T) { U[i] = S_key[i]; cnt[i] = S_cnt[i]; }
-      __threadfence_block();
-      __syncthreads();
-      nU = nU2;
-    } else {
-    // ---- the runs that left: one decrement per point
-    for (int r = 0; r < s_nrem; ++r) {
-      const float4* pts = run_pts(L, slot, m, s_rem[r]);
-      const int n = run_n(L, slot, m, s_rem[r]);
-      for (int i = tid; i < n; i += MU_T) {
-        const u64 key = vkey_of(pts[i], inv);
-        const int pos = lower_bound_U(U, nU, key);
-        if (pos < nU && U[pos] == key) atomicSub(&cnt[pos], 1); else s_err = 1;
-      }
-    }
-    __threadfence_block();
-    __syncthreads();
-    // ---- the runs that entered, one after the other
-    float4* nk = L.newkeys + ((size_t)slot * 2 + m) * L.total_cap;   // (key lo, key hi, lower bound, count) of the voxels this run adds
-    int* S_E = S_cnt + cap;   // third part of the scratch: exclusive keep-scan
-    const int nadd = s_nadd;
-    for (int a = 0; a <= nadd; ++a) {
-      // (iteration nadd is the purge-only pass when nothing was added but something left)
-      if (a == nadd && !(nadd == 0 && s_nrem > 0)) break;
-      const bool purge_only = a == nadd;
-      const float4* pts = purge_only ? nullptr : run_pts(L, slot, m, s_add[a]);
-      const int n = purge_only ? 0 : run_n(L, slot, m, s_add[a]);
-      if (tid == 0) s_nnew = 0;
-      __syncthreads();
-      // B1: known voxels count the point; the first point of every unknown voxel is collected in run order
-      for (int i0 = 0; i0 < n; i0 += MU_T) {
-        const int i = i0 + tid;
-        bool newhead = false;
-        u64 key = 0;
-        int pos = 0, c = 0;
-        if (i < n) {
-          key = vkey_of(pts[i], inv);
-          pos = lower_bound_U(U, nU, key);
-          const bool found = pos < nU && U[pos] == key;
-          if (found) atomicAdd(&cnt[pos], 1);
-          else if (i == 0 || vkey_of(pts[i - 1], inv) != key) {
-            newhead = true;
-            int i2 = i + 1;
-            while (i2 < n && vkey_of(pts[i2], inv) == key) ++i2;
-            c = i2 - i;
-          }
-        }
-        int tot;
-        const int ex = block_excl_scan(newhead ? 1 : 0, s_w, &tot);
-        const int base = s_nnew;
-        if (newhead) nk[base + ex] = make_float4(__uint_as_float((unsigned)key), __uint_as_float((unsigned)(key >> 32)), __int_as_float(pos), __int_as_float(c));
-        __syncthreads();
-        if (tid == 0) s_nnew = base + tot;
-        __syncthreads();
-      }
-      __threadfence_block();
-      __syncthreads();
-      const int nnew = s_nnew;
-      // B2: merge.  Old entry i (kept iff its count is > 0) goes to E(i) + #{new keys with lower bound <= i}; new key j to E(lb_j) + j,
-      // E = exclusive scan of the keep flags.
-      int kept_total = 0;
-      for (int i0 = 0; i0 < nU; i0 += MU_T) {
-        const int i = i0 + tid;
-        const int c = i < nU ? __hip_atomic_load(&cnt[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
-        const int keep = c > 0 ? 1 : 0;
-        int tot;
-        const int ex = kept_total + block_excl_scan(keep, s_w, &tot);
-        if (i < nU) {
-          S_E[i] = ex;
-          if (keep) {
-            int lo = 0, hi = nnew;   // new keys with lower bound <= i
-            while (lo < hi) { const int mid = (lo + hi) >> 1; if (__float_as_int(nk[mid].z) <= i) lo = mid + 1; else hi = mid; }
-            const int p = ex + lo;
-            if (p < cap) { S_key[p] = U[i]; S_cnt[p] = c; }
-          }
-        }
-        kept_total += tot;
-      }
-      __threadfence_block();
-      __syncthreads();
-      for (int j = tid; j < nnew; j += MU_T) {
-        const float4 e = nk[j];
-        const int lb = __float_as_int(e.z);
-        const int p = (lb < nU ? S_E[lb] : kept_total) + j;
-        if (p < cap) { S_key[p] = ((u64)__float_as_uint(e.y) << 32) | (u64)__float_as_uint(e.x); S_cnt[p] = __float_as_int(e.w); }
-      }
-      __threadfence_block();
-      __syncthreads();
-      int nU2 = kept_total + nnew;
-      if (nU2 > cap) { nU2 = cap; if (tid == 0) s_err = 2; }
-      for (int i = tid; i < nU2; i += MU_T) { U[i] = S_key[i]; cnt[i] = S_cnt[i]; }
-      __threadfence_block();
-      __syncthreads();
-      nU = nU2;
-    }
-    }   // general path
     // ---- window totals, bounding box (for PCL's leaf-size check and for the k-NN grid), outputs
     float mn[3] = {3.402823466e+38f, 3.402823466e+38f, 3.402823466e+38f}, mx[3] = {-3.402823466e+38f, -3.402823466e+38f, -3.402823466e+38f};
     int kraw = 0;
@@ -375,6 +195,192 @@ __global__ void __launch_bounds__(MU_T) map_update(DevCtx d, LmCtx L, MapWork W)
     }
     const long long dx = (long long)((mx[0] - mn[0]) * inv) + 1, dy = (long long)((mx[1] - mn[1]) * inv) + 1, dz = (long long)((mx[2] - mn[2]) * inv) + 1;
     const bool pass = kraw > 0 && dx * dy * dz > 2147483647LL;   // PCL: "leaf size too small" -> output = input (in the reference's order)
+    // A window that passes through keeps no voxel list: its map is the raw concatenation, and one of its runs may be a key frame that was
+    // itself too large for a voxel id (stored unsorted by the VoxelGrid sort, voxel.h) — the merges below would read it as sorted.  U is
+    // rebuilt from the window's runs by the next window that is filtered (LI_UVALID is cleared below when a map passed).
+    int nU = 0;
+    if (!pass) {
+      {
+        // the two windows into LDS (s_add / s_rem double as staging), then their multiset difference by one thread:
+        // both are non-decreasing lists of frame ids
+        const int* prev = L.rec_prev + (size_t)slot * L.K;
+        const int np = li[LI_PREV_CNT], nkf = li[LI_NKF];
+        int* s_cur = reinterpret_cast<int*>(mu_smem);
+        int* s_prev = s_cur + MAP_KMAX;
+        for (int j = tid; j < ncur; j += MU_T) s_cur[j] = rec[j];
+        for (int j = tid; j < np; j += MU_T) s_prev[j] = prev[j];
+        __syncthreads();
+        if (tid == 0) {
+          int nr = 0, na = 0;
+          bool valid = li[LI_UVALID] != 0;
+          if (valid) {
+            int a = 0, b = 0;
+            while (a < np || b < ncur) {
+              if (b >= ncur || (a < np && s_prev[a] < s_cur[b])) { if (s_prev[a] < nkf - L.KR) valid = false; s_rem[nr++] = s_prev[a++] % L.KR; }   // its ring entry must still hold it
+              else if (a >= np || s_cur[b] < s_prev[a]) s_add[na++] = s_cur[b++] % L.KR;
+              else { ++a; ++b; }
+            }
+          }
+          if (!valid) {   // rebuild from nothing: every run of the window is inserted
+            nr = 0; na = 0;
+            for (int b = 0; b < ncur; ++b) s_add[na++] = s_cur[b] % L.KR;
+          }
+          s_nrem = nr; s_nadd = na; s_nU = valid ? li[LI_NU_C + m] : 0; s_err = 0;
+        }
+      }
+      __syncthreads();
+      nU = s_nU;
+      u64* S_key = reinterpret_cast<u64*>(map_out(L, slot, m));   // scratch of the merges: the map's output buffer (rewritten by map_accum afterwards)
+      int* S_cnt = reinterpret_cast<int*>(S_key + cap);
+      const int nR = s_nrem == 1 ? run_n(L, slot, m, s_rem[0]) : 0, nA = s_nadd == 1 ? run_n(L, slot, m, s_add[0]) : 0;
+      const bool fast = nU > 0 && s_nrem <= 1 && s_nadd <= 1 && nR <= MU_FCAP && nA <= MU_FCAP;
+      if (fast) {
+        // ---- steady state: one run out, one run in.  The voxel keys of both runs are staged in LDS (sorted, as the runs are);
+        // every thread owns MU_E consecutive entries of the list, finds the pieces of both runs that fall into its key interval by
+        // binary search and merges the three sorted sequences: counts go down / up, new voxels are inserted in order, empty ones
+        // disappear.  No atomics; two passes (count, write) around one scan.
+        u64* s_kr = reinterpret_cast<u64*>(mu_smem);
+        u64* s_ka = s_kr + MU_FCAP;
+        __syncthreads();   // (the window lists staged in the same LDS are dead)
+        if (nR) { const float4* pts = run_pts(L, slot, m, s_rem[0]); for (int i = tid; i < nR; i += MU_T) s_kr[i] = vkey_of(pts[i], inv); }
+        if (nA) { const float4* pts = run_pts(L, slot, m, s_add[0]); for (int i = tid; i < nA; i += MU_T) s_ka[i] = vkey_of(pts[i], inv); }
+        __syncthreads();
+        auto lb = [](const u64* k, int n, u64 key) { int lo = 0, hi = n; while (lo < hi) { const int mid = (lo + hi) >> 1; if (k[mid] < key) lo = mid + 1; else hi = mid; } return lo; };
+        int out_off = 0;
+        for (int t0 = 0; t0 < nU; t0 += MU_T * MU_E) {
+          const int i0 = t0 + tid * MU_E, ne = max(0, min(MU_E, nU - i0));
+          u64 uk[MU_E];
+          int uc[MU_E];
+  #pragma unroll
+          for (int e = 0; e < MU_E; ++e) { const int i = min(i0 + e, nU - 1); uk[e] = U[i]; uc[e] = cnt[i]; }
+          const u64 klo = i0 == 0 ? 0ull : uk[0];
+          const u64 khi = (ne > 0 && i0 + ne < nU) ? U[i0 + ne] : ~0ull;
+          const int pr0 = ne > 0 ? lb(s_kr, nR, klo) : 0, pa0 = ne > 0 ? lb(s_ka, nA, klo) : 0, pa1 = ne > 0 ? (khi == ~0ull ? nA : lb(s_ka, nA, khi)) : 0;
+          // the merge of this thread's interval; emit(key, count) is called for every voxel of the new list, in order
+          auto merge = [&](auto&& emit) {
+            int r = pr0, a = pa0;
+  #pragma unroll
+            for (int e = 0; e < MU_E; ++e) {
+              if (e < ne) {
+                const u64 key = uk[e];
+                while (a < pa1 && s_ka[a] < key) { const u64 k2 = s_ka[a]; int c = 0; while (a < pa1 && s_ka[a] == k2) { ++c; ++a; } emit(k2, c); }
+                while (r < nR && s_kr[r] < key) { ++r; s_err = 1; }   // a point that left was never counted: list out of sync
+                int c = uc[e];
+                while (r < nR && s_kr[r] == key) { --c; ++r; }
+                while (a < pa1 && s_ka[a] == key) { ++c; ++a; }
+                if (c > 0) emit(key, c);
+              }
+            }
+            while (a < pa1) { const u64 k2 = s_ka[a]; int c = 0; while (a < pa1 && s_ka[a] == k2) { ++c; ++a; } emit(k2, c); }
+          };
+          int nout = 0;
+          merge([&](u64, int) { ++nout; });
+          int tot;
+          int pos = out_off + block_excl_scan(nout, s_w, &tot);
+          merge([&](u64 k, int c) { if (pos < cap) { S_key[pos] = k; S_cnt[pos] = c; } ++pos; });
+          out_off += tot;
+        }
+        __threadfence_block();
+        __syncthreads();
+        int nU2 = out_off;
+        if (nU2 > cap) { nU2 = cap; if (tid == 0) s_err = 2; }
+        for (int i = tid; i < nU2; i += MU_T) { U[i] = S_key[i]; cnt[i] = S_cnt[i]; }
+        __threadfence_block();
+        __syncthreads();
+        nU = nU2;
+      } else {
+      // ---- the runs that left: one decrement per point
+      for (int r = 0; r < s_nrem; ++r) {
+        const float4* pts = run_pts(L, slot, m, s_rem[r]);
+        const int n = run_n(L, slot, m, s_rem[r]);
+        for (int i = tid; i < n; i += MU_T) {
+          const u64 key = vkey_of(pts[i], inv);
+          const int pos = lower_bound_U(U, nU, key);
+          if (pos < nU && U[pos] == key) atomicSub(&cnt[pos], 1); else s_err = 1;
+        }
+      }
+      __threadfence_block();
+      __syncthreads();
+      // ---- the runs that entered, one after the other
+      float4* nk = L.newkeys + ((size_t)slot * 2 + m) * L.total_cap;   // (key lo, key hi, lower bound, count) of the voxels this run adds
+      int* S_E = S_cnt + cap;   // third part of the scratch: exclusive keep-scan
+      const int nadd = s_nadd;
+      for (int a = 0; a <= nadd; ++a) {
+        // (iteration nadd is the purge-only pass when nothing was added but something left)
+        if (a == nadd && !(nadd == 0 && s_nrem > 0)) break;
+        const bool purge_only = a == nadd;
+        const float4* pts = purge_only ? nullptr : run_pts(L, slot, m, s_add[a]);
+        const int n = purge_only ? 0 : run_n(L, slot, m, s_add[a]);
+        if (tid == 0) s_nnew = 0;
+        __syncthreads();
+        // B1: known voxels count the point; the first point of every unknown voxel is collected in run order
+        for (int i0 = 0; i0 < n; i0 += MU_T) {
+          const int i = i0 + tid;
+          bool newhead = false;
+          u64 key = 0;
+          int pos = 0, c = 0;
+          if (i < n) {
+            key = vkey_of(pts[i], inv);
+            pos = lower_bound_U(U, nU, key);
+            const bool found = pos < nU && U[pos] == key;
+            if (found) atomicAdd(&cnt[pos], 1);
+            else if (i == 0 || vkey_of(pts[i - 1], inv) != key) {
+              newhead = true;
+              int i2 = i + 1;
+              while (i2 < n && vkey_of(pts[i2], inv) == key) ++i2;
+              c = i2 - i;
+            }
+          }
+          int tot;
+          const int ex = block_excl_scan(newhead ? 1 : 0, s_w, &tot);
+          const int base = s_nnew;
+          if (newhead) nk[base + ex] = make_float4(__uint_as_float((unsigned)key), __uint_as_float((unsigned)(key >> 32)), __int_as_float(pos), __int_as_float(c));
+          __syncthreads();
+          if (tid == 0) s_nnew = base + tot;
+          __syncthreads();
+        }
+        __threadfence_block();
+        __syncthreads();
+        const int nnew = s_nnew;
+        // B2: merge.  Old entry i (kept iff its count is > 0) goes to E(i) + #{new keys with lower bound <= i}; new key j to E(lb_j) + j,
+        // E = exclusive scan of the keep flags.
+        int kept_total = 0;
+        for (int i0 = 0; i0 < nU; i0 += MU_T) {
+          const int i = i0 + tid;
+          const int c = i < nU ? __hip_atomic_load(&cnt[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+          const int keep = c > 0 ? 1 : 0;
+          int tot;
+          const int ex = kept_total + block_excl_scan(keep, s_w, &tot);
+          if (i < nU) {
+            S_E[i] = ex;
+            if (keep) {
+              int lo = 0, hi = nnew;   // new keys with lower bound <= i
+              while (lo < hi) { const int mid = (lo + hi) >> 1; if (__float_as_int(nk[mid].z) <= i) lo = mid + 1; else hi = mid; }
+              const int p = ex + lo;
+              if (p < cap) { S_key[p] = U[i]; S_cnt[p] = c; }
+            }
+          }
+          kept_total += tot;
+        }
+        __threadfence_block();
+        __syncthreads();
+        for (int j = tid; j < nnew; j += MU_T) {
+          const float4 e = nk[j];
+          const int lb = __float_as_int(e.z);
+          const int p = (lb < nU ? S_E[lb] : kept_total) + j;
+          if (p < cap) { S_key[p] = ((u64)__float_as_uint(e.y) << 32) | (u64)__float_as_uint(e.x); S_cnt[p] = __float_as_int(e.w); }
+        }
+        __threadfence_block();
+        __syncthreads();
+        int nU2 = kept_total + nnew;
+        if (nU2 > cap) { nU2 = cap; if (tid == 0) s_err = 2; }
+        for (int i = tid; i < nU2; i += MU_T) { U[i] = S_key[i]; cnt[i] = S_cnt[i]; }
+        __threadfence_block();
+        __syncthreads();
+        nU = nU2;
+      }
+      }   // general path
+    }
     if (pass) {
       float4* out = map_out(L, slot, m);
       const int* kc = L.kf_cnt + (size_t)slot * L.KR * 4;
@@ -399,7 +405,7 @@ __global__ void __launch_bounds__(MU_T) map_update(DevCtx d, LmCtx L, MapWork W)
       li[LI_KRAW_C + m] = kraw;
       li[LI_KDS_C + m] = pass ? min(kraw, cap) : nU;
       if (pass) atomicOr(&li[LI_MAP_PASS], 1 << m); else atomicAnd(&li[LI_MAP_PASS], ~(1 << m));
-      if (s_err) li[LI_OVERFLOW] = s_err == 2 ? 1 : 4;   // 4: voxel list out of sync with the window (internal error)
+      if (!pass && s_err) li[LI_OVERFLOW] = s_err == 2 ? 1 : 4;   // 4: voxel list out of sync with the window (internal error)
       unsigned* bb = L.map_bbox + ((size_t)slot * 2 + m) * 8;
       for (int a = 0; a < 3; ++a) { bb[a] = vbox_enc(mn[a]); bb[4 + a] = ~vbox_enc(mx[a]); }
     }
@@ -431,7 +437,7 @@ __global__ void __launch_bounds__(MU_T) map_update(DevCtx d, LmCtx L, MapWork W)
         int* prev = L.rec_prev + (size_t)(s + d.slot0) * L.K;
         const int nc = l2[LI_REC_CNT];
         for (int j = 0; j < nc; ++j) prev[j] = rec[j];
-        l2[LI_PREV_CNT] = nc; l2[LI_UVALID] = 1;
+        l2[LI_PREV_CNT] = nc; l2[LI_UVALID] = l2[LI_MAP_PASS] == 0;   // (a map that passed through left its U stale)
       }
     }
     int tot;

@@ -120,9 +120,10 @@ __device__ void vox_big_job(const VoxCtx& V, int job, unsigned char* smem) {
   float4* const outp = J.out + (size_t)sel * (J.mode == 1 ? J.out_stride : 0);
   if (J.mode == 1 && tid < 6 && J.box_out) J.box_out[(size_t)sel * 8 + (tid < 3 ? tid : tid + 1)] = tid == 0 ? mn[0] : tid == 1 ? mn[1] : tid == 2 ? mn[2] : tid == 3 ? mx[0] : tid == 4 ? mx[1] : mx[2];
   if (dx * dy * dz > 2147483647LL) {  // PCL: "leaf size too small" -> output = input
-    // (mode 1: a cloud that cannot be ordered by a 31-bit voxel id is reported as a capacity error)
+    // (mode 1: the cloud is stored unsorted.  Its box lies inside the box of every window that holds it, so every such window passes
+    // through too, and map_update reads no sorted run of a window that passes through.)
     for (int i = tid; i < min(n, J.out_cap); i += VG_T) outp[i] = J.in[i];
-    if (tid == 0) { *J.n_out = min(n, J.out_cap); if ((n > J.out_cap || J.mode == 1) && J.overflow) *J.overflow = J.mode == 1 ? 3 : 1;
+    if (tid == 0) { *J.n_out = min(n, J.out_cap); if (n > J.out_cap && J.overflow) *J.overflow = 1;
                     if (J.mode == 1 && J.n_sel_out) J.n_sel_out[(size_t)sel * J.n_sel_stride] = min(n, J.out_cap); }
     return;
   }
@@ -367,7 +368,7 @@ __device__ void vox_small_job(const VoxCtx& V, int job) {
   if (J.mode == 1 && tid < 6 && J.box_out) J.box_out[(size_t)sel * 8 + (tid < 3 ? tid : tid + 1)] = tid == 0 ? mn[0] : tid == 1 ? mn[1] : tid == 2 ? mn[2] : tid == 3 ? mx[0] : tid == 4 ? mx[1] : mx[2];
   if (dx * dy * dz > 2147483647LL) {  // PCL: "leaf size too small" -> output = input
     for (int i = tid; i < min(n, J.out_cap); i += VX_SB) outp[i] = J.in[i];
-    if (tid == 0) { *J.n_out = min(n, J.out_cap); if ((n > J.out_cap || J.mode == 1) && J.overflow) *J.overflow = J.mode == 1 ? 3 : 1;
+    if (tid == 0) { *J.n_out = min(n, J.out_cap); if (n > J.out_cap && J.overflow) *J.overflow = 1;   // (mode 1: stored unsorted, see vox_big_job)
                     if (J.mode == 1 && J.n_sel_out) J.n_sel_out[(size_t)sel * J.n_sel_stride] = min(n, J.out_cap); }
     return;
   }

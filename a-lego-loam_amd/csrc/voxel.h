@@ -24,6 +24,7 @@ struct VoxJob {
   // mode 1 ("sort only"): out = the input points in ascending voxel id (stable: the order inside a voxel is the input order),
   // n_out = n.  Used when a key frame enters LaserMapping's ring: PCL's voxel id orders points by (floor(z/leaf), floor(y/leaf),
   // floor(x/leaf)) whatever the bounding box, so key frames sorted once can be merged into every local map they belong to.
+  // A cloud beyond PCL's INT_MAX rule is stored unsorted: every window that holds it passes through as well (kernels_map.hip).
   int mode;
   const int* out_sel;   // mode 1 (may be nullptr): the output goes to out + *out_sel * out_stride (ring entry chosen on the device)
   int out_stride;

@@ -627,3 +627,62 @@ def test_lm_knn_edge_scenes_on_the_oracle(params_a, name):
         assert (o.get("lm_knn_c").reshape(-1, 5)[:, 0] >= 0).sum() >= 16
     else:
         assert_knn_scene_premise(name, scene, o)
+
+
+def _int_max_cloud(dims, leaf, rng):
+    """a cloud whose pcl::VoxelGrid grid is exactly `dims` at `leaf` (leaf 1/16: (max - min) * inv is exact): the two box corners, half a cell
+    inside the last one, and clusters of points that share voxels"""
+    inv = 1.0 / leaf
+    hi = np.array([(d - 1 + 0.5) / inv for d in dims])
+    c = np.floor(rng.uniform(0, hi, (40, 3)) * inv) / inv
+    pts = np.concatenate([[np.zeros(3), hi]] + [c + rng.uniform(0, 1 / inv, (40, 3)) * 0.9 for _ in range(3)])
+    return np.c_[pts, rng.uniform(0, 100, len(pts))].astype(np.float32)
+
+
+@pytest.mark.parametrize("dims,passes", [((49981, 651, 66), False), ((65535, 32767, 1), False), ((32768, 1024, 64), True),
+                                         ((2, 1073741824 // 16384, 16384), True)])
+def test_oracle_voxel_grid_at_the_int_max_rule(dims, passes):
+    """The oracle's pcl::VoxelGrid against a numpy restatement (tests/util.py voxel_grid_np) on both sides of dx * dy * dz > INT_MAX.  INT_MAX
+    = 2^31 - 1 is prime and f32 extents times inv cannot land on it, so the two sides are the largest reachable products below the rule
+    (2^31 - 2 = 49981 * 651 * 66; 65535 * 32767 on two axes) and INT_MAX + 1 = 2^31 (on three axes and with dx = 2)."""
+    from util import INT_MAX, pcl_dims, voxel_grid_np
+    rng = np.random.default_rng(sum(dims))
+    pts = _int_max_cloud(dims, 1 / 16, rng)
+    got = pcl_dims(pts, 1 / 16)
+    assert got == dims and (np.prod(got, dtype=np.int64) > INT_MAX) == passes, (got, np.prod(got, dtype=np.int64))
+    want = voxel_grid_np(pts, 1 / 16)
+    out = O.voxel_grid(pts, 1 / 16, 0)
+    assert_bit_equal(out, want, f"VoxelGrid at {dims}")
+    assert (len(out) == len(pts) and (out == pts).all()) == passes
+
+
+def test_oracle_voxel_grid_when_the_f32_extent_rounds_onto_an_integer():
+    """leaf 0.05 (inv = 20.0f): (max - min) * inv is below 32767 in exact arithmetic but rounds onto 32767 in f32, so PCL's dx is 32768 and the
+    product 32768 * 512 * 128 = 2^31 crosses the rule (exact arithmetic would give 2^31 - 65536 and filter)"""
+    from util import INT_MAX, _round_extent, pcl_dims, voxel_grid_np
+    x0, x1 = _round_extent(np.float32(1) / np.float32(0.05), 32767)
+    pts = np.array([[x0, 0, 0, 1], [x1, 25.575, 6.375, 2], [x0 + 1, 3, 3, 3], [x0 + 1.01, 3.01, 3.01, 4]], np.float32)
+    assert pcl_dims(pts, 0.05) == (32768, 512, 128)
+    assert (np.float64(x1) - np.float64(x0)) * 20.0 < 32767
+    assert_bit_equal(O.voxel_grid(pts, 0.05, 0), voxel_grid_np(pts, 0.05), "VoxelGrid, rounded extent")
+    assert_bit_equal(O.voxel_grid(pts, 0.05, 0), pts, "pass-through keeps the input")
+    q = pts.copy()
+    q[1, 0] = np.nextafter(np.float32(x1), np.float32(-np.inf))
+    while pcl_dims(q, 0.05)[0] == 32768:
+        q[1, 0] = np.nextafter(q[1, 0], np.float32(-np.inf))
+    assert np.prod(pcl_dims(q, 0.05), dtype=np.int64) <= INT_MAX
+    assert_bit_equal(O.voxel_grid(q, 0.05, 0), voxel_grid_np(q, 0.05), "VoxelGrid one cell below")
+    assert len(O.voxel_grid(q, 0.05, 0)) == 3
+
+
+@pytest.mark.parametrize("name", ["boundary_below_both", "boundary_above_both", "boundary_round_surf", "window_plain", "window_quirk",
+                                  "window_correction", "scan_big", "keyframe_big"])
+def test_lm_pass_through_scenes_on_the_oracle(name):
+    """The pass-through scenes of tests/test_lm_pass_through.py on the oracle alone: every premise holds (tests/util.py)."""
+    from util import pass_scene, run_pass_scene_oracle
+    scene = pass_scene(name)
+    p = synth.default_params(16, 1800)
+    for k, v in scene["mods"].items():
+        setattr(p, k, v)
+    o = O.Oracle(p)
+    assert run_pass_scene_oracle(o, scene, name) == sum(any(v) for v in scene["expect"].values())

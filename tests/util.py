@@ -411,3 +411,312 @@ def assert_knn_scene_premise(name, scene, o):
         assert len(mc) == n
         acc = int((kc[:, 0] >= 0).sum())
         assert (acc == 0) if n < 5 else (0 < acc < len(qc)), f"{name}: {acc} of {len(qc)} queries accepted"
+
+
+# ---- PCL's "leaf size too small" rule in LaserMapping's VoxelGrids -----------------------------------------------------------------------------
+
+INT_MAX = 2 ** 31 - 1
+
+
+def pcl_dims(xyz, leaf):
+    """pcl::VoxelGrid's grid size (dx, dy, dz) of a cloud, in its own f32 arithmetic: d = int64((max - min) * inv) + 1 with inv = 1.0f / leaf"""
+    p = np.asarray(xyz, F32).reshape(-1, np.shape(xyz)[-1])[:, :3]
+    inv = F32(1.0) / F32(leaf)
+    ext = (p.max(axis=0) - p.min(axis=0)) * inv   # f32 throughout
+    return tuple(int(e) + 1 for e in ext)
+
+
+def pcl_passes(xyz, leaf):
+    """True when pcl::VoxelGrid returns the cloud unchanged: dx * dy * dz > INT_MAX (never for an empty cloud)"""
+    if len(xyz) == 0:
+        return False
+    dx, dy, dz = pcl_dims(xyz, leaf)
+    return dx * dy * dz > INT_MAX
+
+
+def voxel_grid_np(pts, leaf):
+    """numpy restatement of pcl::VoxelGrid<PointXYZI>::applyFilter: the pass-through rule, then one centroid per voxel in ascending
+    idx = i + j dx + k dx dy (stable), each the f32 sum of the voxel's points in input order divided by the count"""
+    a = np.asarray(pts, F32)
+    if len(a) == 0 or pcl_passes(a, leaf):
+        return a.copy()
+    inv = F32(1.0) / F32(leaf)
+    xyz = a[:, :3]
+    minb = np.floor(xyz.min(axis=0) * inv).astype(np.int64)
+    maxb = np.floor(xyz.max(axis=0) * inv).astype(np.int64)
+    div = maxb - minb + 1
+    ijk = (np.floor(xyz * inv) - minb.astype(F32)).astype(np.int64)
+    idx = ijk[:, 0] + ijk[:, 1] * div[0] + ijk[:, 2] * div[0] * div[1]
+    order = np.argsort(idx, kind="stable")
+    out = []
+    for key in np.unique(idx):
+        members = order[idx[order] == key]
+        s = np.zeros(4, F32)
+        for i in members:
+            s = s + a[i]
+        out.append(s / F32(len(members)))
+    return np.array(out, F32).reshape(-1, 4)
+
+
+def _pass_world(rng):
+    """a small static scene in map coordinates: ground, two walls, eight poles (corner), a few loose points (outlier)"""
+    g = np.mgrid[-12:12.01:0.5, -12:12.01:0.5].reshape(2, -1).T
+    ground = np.c_[g, np.full(len(g), -1.7)] + rng.normal(0, 0.01, (len(g), 3))
+    w = np.mgrid[-6:6.01:0.4, -1.5:2.01:0.4].reshape(2, -1).T
+    wall_a = np.c_[np.full(len(w), 8.0), w] + rng.normal(0, 0.01, (len(w), 3))
+    wall_b = np.c_[w[:, 0], np.full(len(w), -7.0), w[:, 1]] + rng.normal(0, 0.01, (len(w), 3))
+    poles = []
+    for px, py in ((5, 5), (-5, 4), (4, -5), (-6, -3), (2, 9), (-9, 1), (9, -2), (0, -10)):
+        z = np.arange(-1.5, 2.01, 0.25)
+        poles.append(np.c_[np.full(len(z), px), np.full(len(z), py), z] + rng.normal(0, 0.005, (len(z), 3)))
+    outl = np.c_[rng.uniform(-10, 10, (40, 2)), rng.uniform(-1, 1, 40)]
+    return np.concatenate(poles), np.concatenate([ground, wall_a, wall_b]), outl
+
+
+def _to_lidar(xyz, t, yaw):
+    c, s = np.cos(yaw), np.sin(yaw)
+    R = np.array([[c, -s, 0], [s, c, 0], [0, 0, 1]])
+    return (np.asarray(xyz, float).reshape(-1, 3) - t) @ R   # R^T (p - t)
+
+
+def _odom7(t, yaw):
+    return np.r_[t, np.cos(yaw / 2), 0.0, 0.0, np.sin(yaw / 2)]
+
+
+def _pass_mods(leaf_c, leaf_s, leaf_o, **extra):
+    mods = dict(lm_leaf_corner=float(leaf_c), lm_leaf_surf=float(leaf_s), lm_leaf_outlier=float(leaf_o), lm_every=1, min_keyframe_dist=0.0)
+    mods.update(extra)
+    return mods
+
+
+# scene 1: the window's box right at the rule.  INT_MAX = 2^31 - 1 is prime, so no box of three dimensions (and no f32 extent times inv, whose
+# f32 values next to 2^31 are 128 apart) has it as its product: the largest reachable product below the rule is 2^31 - 2 = 49981 * 651 * 66.
+# leaf 1/16 makes (max - min) * inv exact; "round" uses leaf 0.05 (inv = 20.0f) and an x extent whose exact product with inv lies below 32767
+# while the f32 product rounds onto 32767, so that PCL's dx is 32768 and the product 2^31 (exact arithmetic: 2^31 - 65536, filtered).
+PASS_BOUNDARY = {"below": (1 / 16, (49981, 651, 66), False), "above": (1 / 16, (32768, 1024, 64), True), "round": (0.05, (32768, 512, 128), True)}
+
+
+def _round_extent(inv, k):
+    """(x0, x1): f32 values with fl(fl(x1 - x0) * inv) == k although the exact (x1 - x0) * inv is below k"""
+    inv = F32(inv)
+    x0 = F32(-16.0)
+    x1 = F32((k / float(inv)) + float(x0))
+    for _ in range(64):   # (downwards from the nearest f32 of x0 + k / inv)
+        e = F32(x1 - x0)
+        if F32(e * inv) == F32(k) and float(e) * float(inv) < k and float(e) == float(x1) - float(x0):
+            return float(x0), float(x1)
+        if F32(e * inv) < F32(k):
+            break
+        x1 = np.nextafter(x1, F32(-np.inf))
+    raise AssertionError(f"no extent rounds onto {k}")
+
+
+def pass_boundary_scene(kind, maps):
+    """Two key frames at the identity pose (lm_add_keyframe) that hold the scene plus one point at each corner of a box whose PCL grid is
+    PASS_BOUNDARY[kind]; maps = "corner" (corner clouds), "surf" (min corner in a surf cloud, max corner in an outlier cloud: the surf map is
+    surf + outlier) or "both".  Two mapping frames at the identity odometry follow; their key frames lie inside the box."""
+    leaf, dims, passes = PASS_BOUNDARY[kind]
+    rng = np.random.default_rng(21)
+    inv = F32(1.0) / F32(leaf)
+    lo, hi = [], []
+    for a, d in enumerate(dims):
+        if kind == "round" and a == 0:
+            x0, x1 = _round_extent(inv, d - 1)
+        else:
+            e = F32((d - 1 + 0.5) / float(inv))   # half a cell past d - 1: the truncation is unambiguous
+            x0 = float(F32(np.floor((0.15 if a == 2 else 0.0) * 32 - float(e) / 2 * 32) / 32))   # (centred on the scene)
+            x1 = float(F32(x0 + e))
+            assert float(F32(x1) - F32(x0)) == float(e)
+        lo.append(x0); hi.append(x1)
+    corner, surf, outl = _pass_world(rng)
+    allp = np.concatenate([corner, surf, outl])
+    assert (allp.min(0) > np.add(lo, 0.05)).all() and (allp.max(0) < np.subtract(hi, 0.05)).all(), "the scene must lie inside the box"
+    leaf_c = leaf if maps in ("corner", "both") else 0.4
+    leaf_s = leaf if maps in ("surf", "both") else 0.4
+    kfs = []
+    for k, anchor in enumerate((lo, hi)):
+        c, s, o = corner.copy(), surf.copy(), outl.copy()
+        if maps in ("corner", "both"):
+            c = np.concatenate([c, [anchor]])
+        if maps in ("surf", "both"):
+            if k == 0:
+                s = np.concatenate([s, [anchor]])
+            else:
+                o = np.concatenate([o, [anchor]])
+        kfs.append((np.zeros(6, F32), _cloud(c), _cloud(s), _cloud(o)))
+    frames = []
+    for i in range(2):
+        frames.append((_cloud(corner + rng.normal(0, 0.005, corner.shape)), _cloud(surf + rng.normal(0, 0.005, surf.shape)), _cloud(outl),
+                       _odom7(np.zeros(3), 0.0)))
+    expect = {i: (passes if maps != "surf" else False, passes if maps != "corner" else False) for i in range(2)}
+    return dict(mods=_pass_mods(leaf_c, leaf_s, 0.4, recent_keyframe_num=4), keyframes=kfs, frames=frames, expect=expect, dims=dims,
+                leaf=leaf, maps=maps)
+
+
+def _moving_frames(n, rng, extra, pause=()):
+    """n frames of the static scene seen from a platform that drives 0.41 m per frame (standing still at the frames in `pause`);
+    extra[i] = (corner, surf, outlier) map points added to frame i"""
+    corner, surf, outl = _pass_world(rng)
+    frames, t, yaw = [], np.zeros(3), 0.0
+    for i in range(n):
+        if i and i not in pause:
+            t = t + (0.4, 0.1, 0.0)
+            yaw += 0.01
+        ex = extra.get(i, (np.zeros((0, 3)),) * 3)
+        c = np.concatenate([corner + rng.normal(0, 0.005, corner.shape), ex[0]])
+        s = np.concatenate([surf + rng.normal(0, 0.005, surf.shape), ex[1]])
+        o = np.concatenate([outl, ex[2]])
+        frames.append((_cloud(_to_lidar(c, t, yaw)), _cloud(_to_lidar(s, t, yaw)), _cloud(_to_lidar(o, t, yaw)), _odom7(t, yaw)))
+    return frames
+
+
+def pass_window_scene(variant):
+    """Enter, stay, leave: a 3-key-frame window, every mapping frame saves a key frame.  One frame holds a point 500 m along x, a later one a
+    point 500 m along y (in all three clouds).  Neither frame alone crosses the rule at leaf 0.05 (~10^4 * 480 * 80 cells); a window holding
+    both does (~10^4 * 10^4 * 80), so the maps pass through while both are in the window and are filtered again once the first has left.
+      plain       X at frame 3, Y at frame 4: frames 5 and 6 pass, 7 - 9 filter
+      quirk       the platform stands still at frame 3 (min_keyframe_dist 0.01: no key frame), X at 1, Y at 2: frame 3 passes with the window
+                  {0, 1, 2}, frame 4 with the deque quirk's duplicate {1, 2, 2}, frames 5 - 8 filter
+      correction  as plain, and after frame 5 every key pose is moved (lm_set_keypose), the window cleared and map -> odom corrected"""
+    rng = np.random.default_rng(22)
+    X = (np.array([[500.0, 0.0, 0.0]]),) * 3
+    Y = (np.array([[0.0, 500.0, 0.0]]),) * 3
+    if variant == "quirk":
+        frames = _moving_frames(9, rng, {1: X, 2: Y}, pause=(3,))
+        expect = {i: (i in (3, 4),) * 2 for i in range(2, 9)}   # (a window of one key frame is its own filtered map)
+        mods = _pass_mods(0.05, 0.05, 0.05, recent_keyframe_num=3, min_keyframe_dist=0.01)
+    else:
+        frames = _moving_frames(10, rng, {3: X, 4: Y})
+        expect = {i: (i in (5, 6),) * 2 for i in range(2, 10)}
+        mods = _pass_mods(0.05, 0.05, 0.05, recent_keyframe_num=3)
+    return dict(mods=mods, keyframes=[], frames=frames, expect=expect, correct_after=5 if variant == "correction" else None, variant=variant)
+
+
+def _spread(rng, n, half=(100.0, 100.0, 15.0)):
+    """n points spread over a 200 m x 200 m x 30 m box around the origin: its own grid at leaf 0.05 has 4000 * 4000 * 600 cells"""
+    h = np.asarray(half)
+    pts = rng.uniform(-h, h, (n, 3))
+    pts[:2] = [-h, h]
+    return pts
+
+
+def pass_scan_scene(size):
+    """The current scan's own clouds beyond the rule (downsampleCurrentScan: corner, surf and outlier, then laser_surf_total_): a key frame of
+    the plain scene at the identity pose, then three mapping frames at the identity odometry (min_keyframe_dist 1: none saves a key frame) whose
+    clouds also hold points spread over 200 m x 200 m x 30 m.  size "small": every cloud of at most 8192 points (vox_small); "big": the surf
+    cloud and laser_surf_total_ above 8192 (vox_big)."""
+    rng = np.random.default_rng(23 if size == "small" else 24)
+    corner, surf, outl = _pass_world(rng)
+    kf = (np.zeros(6, F32), _cloud(corner), _cloud(surf), _cloud(outl))
+    ns = 2000 if size == "small" else 9000
+    frames = []
+    for i in range(3):
+        c = np.concatenate([corner + rng.normal(0, 0.005, corner.shape), _spread(rng, 300)])
+        s = np.concatenate([surf + rng.normal(0, 0.005, surf.shape), _spread(rng, ns)])
+        o = np.concatenate([outl, _spread(rng, 1500)])
+        frames.append((_cloud(c), _cloud(s), _cloud(o), _odom7(np.zeros(3), 0.0)))
+    expect = {i: (False, False) for i in range(3)}
+    return dict(mods=_pass_mods(0.05, 0.05, 0.05, recent_keyframe_num=3, min_keyframe_dist=1.0), keyframes=[kf], frames=frames, expect=expect,
+                scan_pass=True, size=size)
+
+
+def pass_keyframe_scene(size):
+    """A single key frame beyond the rule: frame 3 of a moving run also holds points spread over 200 m x 200 m x 30 m in all three clouds, so
+    its downsampled clouds are the raw ones and the key frame it saves crosses the rule on its own (the key-frame sort cannot order it).  With a
+    3-key-frame window it is in the window at frames 4 - 6 (the maps pass through) and has left it at frame 7; frames 7 - 9 filter.
+    size "small" / "big": the saved surf + outlier cloud of at most / more than 8192 points."""
+    rng = np.random.default_rng(25 if size == "small" else 26)
+    ns = 2000 if size == "small" else 9000
+    frames = _moving_frames(10, rng, {3: (_spread(rng, 300), _spread(rng, ns), _spread(rng, 1500))})
+    expect = {i: (i in (4, 5, 6),) * 2 for i in range(2, 10)}
+    return dict(mods=_pass_mods(0.05, 0.05, 0.05, recent_keyframe_num=3), keyframes=[], frames=frames, expect=expect, kf_frame=3, size=size)
+
+
+PASS_SCENES = [f"boundary_{k}_{m}" for k in PASS_BOUNDARY for m in ("corner", "surf", "both")] + \
+    ["window_plain", "window_quirk", "window_correction", "scan_small", "scan_big", "keyframe_small", "keyframe_big"]
+
+
+def pass_scene(name):
+    kind, _, arg = name.partition("_")
+    if kind == "boundary":
+        k, m = arg.split("_")
+        return pass_boundary_scene(k, m)
+    if kind == "window":
+        return pass_window_scene(arg)
+    if kind == "scan":
+        return pass_scan_scene(arg)
+    if kind == "keyframe":
+        return pass_keyframe_scene(arg)
+    raise KeyError(name)
+
+
+def assert_pass_scene_premise(name, scene, o, i):
+    """What mapping frame i of the scene is built to reach, from the oracle's own outputs after that frame: each local map passes through
+    (the filtered map is the raw concatenation, row for row) exactly where scene["expect"] says so; the boundary scenes' window has exactly the planned grid; the
+    scan scenes' downsampled clouds are their inputs; the key-frame scene's saved frame crosses the rule on its own."""
+    P = scene["mods"]
+    if i not in scene["expect"]:
+        return
+    for m, (raw_name, ds_name, leaf) in enumerate((("lm_corner_map", "lm_corner_map_ds", P["lm_leaf_corner"]),
+                                                   ("lm_surf_map", "lm_surf_map_ds", P["lm_leaf_surf"]))):
+        raw, ds = o.get(raw_name), o.get(ds_name)
+        want = scene["expect"][i][m]
+        same = len(ds) == len(raw) and (bits(ds) == bits(raw)).all()   # (a sparse filtered map can keep every row, but not in the raw order)
+        assert len(raw) > 0 and pcl_passes(raw, leaf) == want and same == want, \
+            f"{name} frame {i}: {raw_name} of {len(raw)} points -> {len(ds)}, grid {pcl_dims(raw, leaf)}, expected pass-through {want}"
+        if name.startswith("boundary") and scene["maps"] in (("corner", "both") if m == 0 else ("surf", "both")):
+            assert pcl_dims(raw, leaf) == scene["dims"], f"{name} frame {i}: {raw_name} grid {pcl_dims(raw, leaf)} vs {scene['dims']}"
+    if scene.get("scan_pass"):
+        c, s, ol, _ = scene["frames"][i]
+        for what, inp, leaf in (("lm_corner_ds", c, P["lm_leaf_corner"]), ("lm_surf_ds", s, P["lm_leaf_surf"]), ("lm_outlier_ds", ol, P["lm_leaf_outlier"])):
+            assert pcl_passes(inp, leaf) and len(o.get(what)) == len(inp), f"{name} frame {i}: {what}"
+        tot = o.get("lm_surf_total_ds")
+        assert len(tot) == len(s) + len(ol), f"{name} frame {i}: laser_surf_total_ passes through"
+        big = scene["size"] == "big"
+        assert len(c) <= 8192 and len(ol) <= 8192 and (len(s) > 8192) == big and (len(tot) > 8192) == big, f"{name}: cloud sizes"
+    if scene.get("variant") == "quirk" and i in (3, 4):   # frame 3 saves no key frame; frame 4's window is {1, 2, 2}
+        nk = [len(o.lm_keyframe(k)[0]) for k in range(3)]
+        assert o.get("lm_info")[11] == (3 if i == 3 else 4) and (i == 3 or len(o.get("lm_corner_map")) == nk[1] + 2 * nk[2]), f"{name} frame {i}: no duplicate"
+    if name.startswith("keyframe") and i == scene["kf_frame"] + 1:
+        kp = o.get("lm_keyposes").reshape(-1, 6)[scene["kf_frame"]]
+        kc, ks, ko = o.lm_keyframe(scene["kf_frame"])
+        assert pcl_passes(O_transform(kp, kc), P["lm_leaf_corner"]), f"{name}: the key frame's corner cloud does not cross the rule"
+        kso = O_transform(kp, np.concatenate([ks, ko]))
+        assert pcl_passes(kso, P["lm_leaf_surf"]) and (len(kso) > 8192) == (scene["size"] == "big"), f"{name}: the key frame's surf + outlier cloud"
+
+
+def O_transform(pose6, pts):
+    from oracle import oracle_py as O
+    return O.transform_cloud(pose6, pts)
+
+
+def pass_correction(keyposes):
+    """the key-pose correction of the "correction" window scene (a rigid 'loop closure': 0.02 rad about z and a shift): the new f32 key poses
+    and the 3 x 4 map -> odom correction"""
+    c, s = np.cos(0.02), np.sin(0.02)
+    rc = np.array([[c, -s, 0, 0.15], [s, c, 0, -0.1], [0, 0, 1, 0.02]])
+    out = []
+    for kp in np.asarray(keyposes).reshape(-1, 6):
+        q = kp.astype(np.float64)
+        q[:3] = rc[:, :3] @ q[:3] + rc[:, 3]
+        q[5] += 0.02
+        out.append(q.astype(F32))
+    return out, rc
+
+
+def run_pass_scene_oracle(o, scene, name):
+    """the whole scene on an oracle, asserting its premise after every mapping frame; returns the number of frames whose maps passed through"""
+    for kp, c, s, ol in scene["keyframes"]:
+        o.lm_add_keyframe(kp, c, s, ol)
+    npass = 0
+    for i, (c, s, ol, od) in enumerate(scene["frames"]):
+        o.lm_process(c, s, ol, od)
+        assert_pass_scene_premise(name, scene, o, i)
+        npass += int(any(scene["expect"].get(i, (False, False))))
+        if i == scene.get("correct_after"):
+            poses, rc = pass_correction(o.get("lm_keyposes"))
+            for k, q in enumerate(poses):
+                o.lm_set_keypose(k, q)
+            o.lm_reset_window()
+            o.lm_apply_correction(rc)
+    return npass
