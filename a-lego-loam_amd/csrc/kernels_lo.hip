@@ -237,8 +237,8 @@ void launch_lo_grid(const DevCtx& d, hipStream_t st) {
 }
 
 // kind (compile-time): the corner association has one class of second points, the surf one two.  BLKA threads per workgroup, BLKA / 16
-// queries at a time; workgroup qb0 of qbn of the stream takes the query blocks qb0, qb0 + qbn, ...  (A device function: the batch path
-// launches it as lo_assoc, one stream's chain kernel lo_chain calls it between its grid barriers.)
+// queries at a time; workgroup qb0 of qbn of the stream takes the query blocks qb0, qb0 + qbn, ...  (A device function: the kernel
+// lo_assoc below is its only caller.)
 template <int kind, int BLKA, int BOXCAP = LO_BOX_LDS>
 DEV_INLINE void lo_assoc_body(const DevCtx& d, int box_lds_max, int slot, int qb0, int qbn) {
   static_assert(LO_CH % 16 == 0, "a box is evaluated as LO_CH / 16 targets per lane of a 16-lane row");

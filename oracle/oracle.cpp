@@ -1667,6 +1667,29 @@ int oracle_ip(void* h, const alego_point* pts, int n) {
   return (int)c->ip.seg_cloud.size();
 }
 
+// A segmented cloud given by the caller in place of oracle_ip()'s (the /segmented_cloud + /seg_info pair LaserOdometry subscribes to):
+// m points with their ground flags, columns and ranges, the n_scan start / end ring indices and the three orientations.  The next
+// oracle_lo() / oracle_fe() runs on it.  Returns m, or -1 when the cloud does not fit the sensor's n_scan x horizon_scan cells.
+int oracle_set_seg(void* h, const alego_point* seg, int m, const uint8_t* ground, const int* col, const float* range,
+                   const int* ring_start, const int* ring_end, const float* ori3) {
+  Ctx* c = (Ctx*)h;
+  ImageProjection& ip = c->ip;
+  if (m < 0 || m > ip.N) return -1;
+  ip.seg_cloud.assign(seg, seg + m);
+  ip.outlier_cloud.clear();
+  // (the per-point arrays keep their length N, as after pcCB: feature extraction reads them only below m)
+  std::fill(ip.seg_ground.begin(), ip.seg_ground.end(), 0);
+  std::fill(ip.seg_col.begin(), ip.seg_col.end(), 0);
+  std::fill(ip.seg_range.begin(), ip.seg_range.end(), 0.f);
+  std::copy(ground, ground + m, ip.seg_ground.begin());
+  std::copy(col, col + m, ip.seg_col.begin());
+  std::copy(range, range + m, ip.seg_range.begin());
+  ip.start_ring.assign(ring_start, ring_start + c->P.n_scan);
+  ip.end_ring.assign(ring_end, ring_end + c->P.n_scan);
+  for (int k = 0; k < 3; ++k) ip.ori[k] = ori3 ? ori3[k] : 0.f;
+  return m;
+}
+
 // a7-a17: one LaserOdometry::mainLoop body on the last oracle_ip() result.
 // Returns 1 when odometry was produced, 0 on the initialising scan.
 int oracle_lo(void* h) {

@@ -27,6 +27,8 @@ def lib():
             getattr(L, f).argtypes = [C.c_void_p]
         L.oracle_ip.restype = C.c_int
         L.oracle_ip.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.oracle_set_seg.restype = C.c_int
+        L.oracle_set_seg.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.oracle_process_scan.restype = C.c_int
         L.oracle_process_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.oracle_set_lo_params.argtypes = [C.c_void_p, C.c_void_p]
@@ -96,6 +98,20 @@ class Oracle:
     def ip(self, pts):
         a = self._pts(pts)
         return lib().oracle_ip(self._h, a.ctypes.data, a.shape[0])
+
+    def set_seg(self, seg):
+        """A segmented cloud in place of ip()'s: the dict Handle.lo_process takes (seg, ground, col, range, ring_start, ring_end,
+        orientation).  The next lo() / fe() runs on it."""
+        a = [self._pts(seg["seg"]), np.ascontiguousarray(seg["ground"], np.uint8), np.ascontiguousarray(seg["col"], np.int32),
+             np.ascontiguousarray(seg["range"], np.float32), np.ascontiguousarray(seg["ring_start"], np.int32),
+             np.ascontiguousarray(seg["ring_end"], np.int32), np.ascontiguousarray(seg.get("orientation", np.zeros(3)), np.float32)]
+        m = a[0].shape[0]
+        assert a[1].size == m and a[2].size == m and a[3].size == m, "per-point arrays of the segmented cloud differ in length"
+        assert a[4].size == self._p.n_scan and a[5].size == self._p.n_scan and a[6].size == 3
+        r = lib().oracle_set_seg(self._h, *[x.ctypes.data for x in a[:1]], m, *[x.ctypes.data for x in a[1:]])
+        if r < 0:
+            raise ValueError(f"segmented cloud of {m} points does not fit {self._p.n_scan} x {self._p.horizon_scan}")
+        return r
 
     def fe(self):
         return lib().oracle_fe(self._h)

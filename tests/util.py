@@ -720,3 +720,548 @@ def run_pass_scene_oracle(o, scene, name):
             o.lm_reset_window()
             o.lm_apply_correction(rc)
     return npass
+
+
+# ---- LaserOdometry's correspondence search (lo_assoc) at its edges --------------------------------------------------------------------------------
+
+LO_R, LO_SPIKE = 20.0, 20.25   # ranges of the constructed segmented clouds: flat ground everywhere, a non-ground spike where a corner feature goes
+
+
+def lo_assoc_brute(prev_less_flat, prev_less_sharp, flat, sharp, params6, P):
+    """numpy restatement of laserOdometry.cpp:337-481 for every query: (surf rows (j, closest, idx2, idx3), corner rows (j, closest, idx2, -1)).
+    closest is -1 on a rejected row, whose partial walk results stay: idx2 / idx3 of a surf row whose 1-NN passed the gate but whose walk found only
+    one of them, idx2 = -1 and idx3 = -1 when the 1-NN did not pass.  1-NN: brute force over the f32 distance (dx^2 + dy^2) + dz^2, ties to the
+    lowest index, accepted when (double)d < nearest_feature_dist.  Walk: up from closest + 1, then down from closest - 1, each direction ending at
+    the first point whose int(intensity) lies beyond ring_window; pow(f32 difference, 2) summed in double, strict < against a running minimum
+    that starts at nearest_feature_dist."""
+    from oracle import oracle_py as O
+    nfd, W = float(P.nearest_feature_dist), int(P.ring_window)
+
+    def search(tg, qs, kind):
+        tg = np.asarray(tg, F32).reshape(-1, 4)
+        qs = np.asarray(qs, F32).reshape(-1, 4)
+        rows = np.full((len(qs), 4), -1, np.int32)
+        rows[:, 0] = np.arange(len(qs))
+        if len(qs) == 0 or len(tg) == 0:
+            return rows
+        sel = O.transform_to_start(params6, qs)
+        ring = tg[:, 3].astype(np.int64)   # (int)intensity: C truncation of a non-negative float
+        for j, s in enumerate(sel):
+            d = f32_dist2(tg, s)
+            c = int(np.argmin(d))   # (first minimum: the lowest index)
+            if not float(d[c]) < nfd:
+                continue
+            cs = ring[c]
+            up = np.arange(c + 1, len(tg))
+            stop = np.nonzero(ring[up] > cs + W)[0]
+            up = up[:stop[0]] if stop.size else up
+            dn = np.arange(c - 1, -1, -1)
+            stop = np.nonzero(ring[dn] < cs - W)[0]
+            dn = dn[:stop[0]] if stop.size else dn
+            order = np.concatenate([up, dn]).astype(np.int64)   # the visiting order
+            df = tg[order, :3] - s[:3]                           # f32 differences
+            e = df.astype(np.float64) ** 2
+            pd = (e[:, 0] + e[:, 1]) + e[:, 2]
+            same = ring[order] == cs
+            if kind == 0:
+                cls2, cls3 = same, ~same
+            else:
+                cls2, cls3 = np.concatenate([ring[up] > cs, ring[dn] < cs]), np.zeros(len(order), bool)
+            out = []
+            for cls in (cls2, cls3):
+                m = cls & (pd < nfd)
+                if not m.any():
+                    out.append(-1)
+                    continue
+                v = np.where(m, pd, np.inf)
+                out.append(int(order[int(np.argmin(v))]))   # first minimum in visiting order: strict < keeps the first one seen
+            i2, i3 = out
+            ok = (i2 >= 0 and i3 >= 0) if kind == 0 else i2 >= 0
+            rows[j] = (j, c if ok else -1, i2, i3 if kind == 0 else -1)
+        return rows
+
+    return search(prev_less_flat, flat, 0), search(prev_less_sharp, sharp, 1)
+
+
+def lo_brute_detail(tg, sel, P, kind):
+    """per query (already at transform_to_start): the f32 1-NN distances, the number of targets at the minimum, and the double walk distances of
+    every candidate in the window by class — what the scene premises count"""
+    tg = np.asarray(tg, F32).reshape(-1, 4)
+    ring = tg[:, 3].astype(np.int64)
+    out = []
+    if len(tg) == 0:
+        return out
+    for s in np.asarray(sel, F32).reshape(-1, 4):
+        d = f32_dist2(tg, s)
+        c = int(np.argmin(d))
+        e = (tg[:, :3] - s[:3]).astype(np.float64) ** 2
+        pd = (e[:, 0] + e[:, 1]) + e[:, 2]
+        out.append(dict(d=d, c=c, dmin=d[c], n_min=int((d == d[c]).sum()), ring=ring, pd=pd, cs=int(ring[c])))
+    return out
+
+
+def lo_grid_geometry(tg):
+    """lo_grid_build's grid over a target cloud's (x, y) extent, restated: (gx, gy, csz) or None when there is no grid"""
+    tg = np.asarray(tg, F32).reshape(-1, 4)
+    n = len(tg)
+    if n <= 0 or n > 65535:
+        return None
+    mn, mx = tg[:, :2].min(axis=0), tg[:, :2].max(axis=0)
+    ext = mx - mn
+    if not (ext[0] < F32(1e6) and ext[1] < F32(1e6)):
+        return None
+    csz = F32(1.0)
+    for _ in range(24):
+        gx, gy = int(np.floor(ext[0] / csz)) + 2, int(np.floor(ext[1] / csz)) + 2
+        if gx * gy <= 4096:
+            return gx, gy, float(csz)
+        csz = F32(csz * 2)
+    return None
+
+
+def _sector_cover(L, nsec):
+    """positions 0..L-1 of a ring's [startRingIndex, endRingIndex] that some sector of laserOdometry.cpp:177-178 visits (sp < ep)"""
+    cov = np.zeros(max(L, 0), bool)
+    S, E = 0, L - 1
+    for j in range(nsec):
+        sp = (S * (nsec - j) + E * j) // nsec
+        ep = (S * (nsec - 1 - j) + E * (j + 1)) // nsec - 1
+        if sp < ep:
+            cov[sp:ep + 1] = True
+    return cov
+
+
+def _seg_from_rings(P, rings):
+    """a segmented cloud from per-ring slot lists [(xyz, spike), ...] placed on the positions the sector split visits; 5 padding points on either
+    side of every ring (ring_start = first + 5, ring_end = last - 5, as ImageProjection publishes them).  Non-spike points are ground with range
+    LO_R (curvature 0: flat candidates, never corners); a spike is non-ground at LO_SPIKE with a column jump of 11 on both sides (no suppression,
+    no occlusion marking reaches it), so it becomes a sharp / less_sharp feature.  Intensity = ring + col / 10000."""
+    pts, gnd, col, rng_, rs, re_ = [], [], [], [], [], []
+    far = np.array([4096.0, 4096.0, 4096.0], F32)
+    for r in range(P.n_scan):
+        slots = list(rings[r]) if r < len(rings) else []
+        L = 0
+        if slots:   # the shortest ring whose visited positions take the slots exactly, else the shortest that takes them all
+            fit = [L for L in range(len(slots), len(slots) + 40) if _sector_cover(L, P.n_sectors).sum() == len(slots)]
+            L = fit[0] if fit else next(L for L in range(len(slots), 10 * len(slots) + 40) if _sector_cover(L, P.n_sectors).sum() >= len(slots))
+        cov = _sector_cover(L, P.n_sectors)
+        seq = [(far, False)] * 5
+        it = iter(slots)
+        n_extra = int(cov.sum()) - len(slots)
+        flat_slots = [s for s in slots if not s[1]]
+        assert n_extra == 0 or flat_slots, f"ring {r}: {n_extra} visited positions left over and no flat target to repeat"
+        for k in range(L):
+            if cov[k]:
+                s = next(it, None)
+                if s is None:   # (a visited position beyond the slots: a second copy of a flat target, merged into its voxel)
+                    s = flat_slots[n_extra % len(flat_slots)]
+                    n_extra -= 1
+                seq.append(s)
+            else:
+                seq.append((far, False))
+        seq += [(far, False)] * 5
+        rs.append(len(pts) + 5)
+        re_.append(len(pts) + len(seq) - 6)
+        c = 0
+        for k, (xyz, spike) in enumerate(seq):
+            if k > 0 and (spike or seq[k - 1][1]):
+                c += 11
+            elif k > 0:
+                c += 1
+            pts.append([xyz[0], xyz[1], xyz[2], F32(r) + F32(c) / F32(10000)])
+            gnd.append(0 if spike else 1)
+            col.append(c)
+            rng_.append(LO_SPIKE if spike else LO_R)
+        assert c < 65536
+    n = len(pts)
+    assert n <= P.n_scan * P.horizon_scan, (n, P.n_scan * P.horizon_scan)
+    return dict(seg=np.asarray(pts, F32).reshape(-1, 4), ground=np.asarray(gnd, np.uint8), col=np.asarray(col, np.int32),
+                range=np.asarray(rng_, F32), ring_start=np.asarray(rs, np.int32), ring_end=np.asarray(re_, np.int32), orientation=np.zeros(3, F32))
+
+
+def lo_scene_params(name, geom):
+    p = synth.default_params(*geom)
+    p.lo_iters_surf = 0   # the corner search runs at exactly the forced parameters
+    p.lo_iters_corner = 0
+    for k, v in LO_SCENES_MODS.get(name.split(":")[0], {}).items():
+        setattr(p, k, v)
+    if ":" in name:
+        k, v = name.split(":")[1].split("=")
+        setattr(p, k, type(getattr(p, k))(float(v)))
+    return p
+
+
+def _target_rings(P, surf, corner):
+    """surf / corner: {ring: [xyz, ...]} -> per-ring slot lists, each ring's corner spikes spread evenly among its flat targets"""
+    rings = []
+    for r in range(P.n_scan):
+        s = [(np.asarray(x, F32), False) for x in surf.get(r, [])]
+        c = [(np.asarray(x, F32), True) for x in corner.get(r, [])]
+        out = list(s)
+        for j, t in enumerate(c):
+            out.insert((j + 1) * len(s) // (len(c) + 1) + j, t)
+        rings.append(out)
+    return rings
+
+
+def _query_rings(P, ring_len=60, short_ring=None):
+    """scan 1's profile: every ring ring_len positions of flat ground with a spike in every twelve (the sharp queries); xyz follow"""
+    rings = []
+    for r in range(P.n_scan):
+        L = short_ring if (short_ring is not None and r == 0) else ring_len
+        rings.append([(np.zeros(3, F32), k % 12 == 6) for k in range(L)])
+    return rings
+
+
+def build_lo_scene(name, geom):
+    """the two segmented clouds of LO scene `name` on an n_scan x horizon sensor: scan 0 holds the targets, scan 1 the queries.  Feature selection
+    reads only range / col / ground, so the picks of scan 1 are read from the oracle first and the queries' xyz placed on them afterwards
+    (the scene's query lists, repeated until every pick has one)."""
+    from oracle import oracle_py as O
+    P = lo_scene_params(name, geom)
+    spec = LO_SCENE_FNS[name.split(":")[0]](P)
+    seg0 = _seg_from_rings(P, _target_rings(P, spec["surf"], spec.get("corner", {})))
+    seg1 = _seg_from_rings(P, _query_rings(P, spec.get("ring_len", 60), spec.get("short_ring")))
+    o = O.Oracle(P)
+    o.set_seg(seg1)
+    o.fe()
+    fi, si = o.get("flat_idx"), o.get("sharp_idx")
+    o.close()
+    fq = np.asarray(spec["flat_q"], F32).reshape(-1, 3)
+    sq = np.asarray(spec.get("sharp_q", spec["flat_q"]), F32).reshape(-1, 3)
+    assert len(fi) >= len(fq) and len(si) >= len(sq), f"{name}: {len(fi)} flat / {len(si)} sharp picks for {len(fq)} / {len(sq)} queries"
+    seg1["seg"][fi, :3] = fq[np.arange(len(fi)) % len(fq)]
+    seg1["seg"][si, :3] = sq[np.arange(len(si)) % len(sq)]
+    return dict(P=P, seg0=seg0, seg1=seg1, params6=np.asarray(spec.get("params6", np.zeros(6)), np.float64), spec=spec)
+
+
+def run_lo_scene_oracle(sc):
+    """scan 0, then scan 1 at the forced params6; returns the oracle (its clouds of scan 0 are in sc['less_flat'] / sc['less_sharp'])"""
+    from oracle import oracle_py as O
+    o = O.Oracle(sc["P"])
+    o.set_seg(sc["seg0"])
+    o.lo()
+    sc["less_flat"], sc["less_sharp"] = o.get("less_flat"), o.get("less_sharp")
+    o.set_lo_params(sc["params6"])
+    o.set_seg(sc["seg1"])
+    assert o.lo() == 1
+    return o
+
+
+def _put(d, P, r, *xyz):
+    if 0 <= r < P.n_scan:
+        d.setdefault(r, []).extend(np.asarray(x, F32) for x in xyz)
+
+
+def lo_nn_ties(P):
+    """queries at exactly equal f32 distance (0.25 or 9) from 2 - 4 targets: in one ring, in different rings (ascending and descending with the
+    offset), and — in a band of its own — in one ring 40 fillers apart (different boxes); corner targets repeat the pattern without fillers"""
+    NS, surf, corner, q = P.n_scan, {}, {}, []
+    for k in range(24):
+        c = np.array([8 * (k % 8) - 28, 10 * (k // 8) - 10, 0.25])
+        a = 0.5 if k % 2 == 0 else 3.0
+        offs = [(a, 0, 0), (-a, 0, 0), (0, a, 0), (0, -a, 0)][:2 + k % 3]
+        for j, o in enumerate(offs):
+            r = [k, k + 4 * j, k + NS - 1 - j, k + (j % 2)][k % 4] % NS
+            _put(surf, P, r, c + o)
+            _put(corner, P, r, c + o)
+        q.append(c)
+    for j in range(6):
+        c = np.array([-80 + 32 * j, 30, 0.25])
+        a = 3.0 if j % 2 else 0.5
+        r = (5 * j + 2) % NS
+        _put(surf, P, r, c + (0, -a, 0), c + (0, a, 0), *[c + (3.0 + 0.5 * i, 1.5 if a == 3.0 else 0.0, 0) for i in range(40)])
+        q.append(c)
+    return dict(surf=surf, corner=corner, flat_q=q)
+
+
+def lo_nn_gate(P):
+    """1-NN at f32 distance exactly nearest_feature_dist (rejected), one ulp below (accepted), one ulp above; each with two more targets at the same
+    f32 distance (mirror images) in the same ring and the next, so that the walk can complete an accepted row"""
+    nfd = P.nearest_feature_dist
+    g = F32(nfd)
+    lim = g if float(g) >= nfd else np.nextafter(g, F32(np.inf))   # the smallest f32 that is not < nfd
+    surf, corner, q = {}, {}, []
+    for i, t in enumerate([lim, np.nextafter(lim, F32(0)), np.nextafter(lim, F32(np.inf)), np.nextafter(np.nextafter(lim, F32(0)), F32(0))]):
+        for rep in range(3):
+            k = 4 * rep + i
+            c = np.array([24.0 * (k % 4), 24.0 * (k // 4), 0.25])
+            seed = 31 + k
+            dx, dy, dz = _gate_offset(t, seed)
+            while i == 0 and not dx * dx + dy * dy + dz * dz < nfd:   # at the gate: an exact (double) distance below it, so `<=` would accept
+                seed += 1000
+                dx, dy, dz = _gate_offset(t, seed)
+            r = (3 * k + 1) % (P.n_scan - 1)
+            _put(surf, P, r, c + (dx, dy, dz), c + (-dx, dy, dz))
+            _put(surf, P, r + 1, c + (dx, -dy, dz))
+            _put(corner, P, r, c + (dx, dy, dz))
+            _put(corner, P, r + 1, c + (dx, -dy, dz))
+            q.append(c)
+    if float(lim) == nfd:   # 3-4-0 against an integer gate
+        c = np.array([-24.0, 0.0, 0.25])
+        _put(surf, P, 2, c + (3, 4, 0), c + (-3, 4, 0))
+        _put(surf, P, 3, c + (3, -4, 0))
+        q.append(c)
+    return dict(surf=surf, corner=corner, flat_q=q)
+
+
+def _walk_star(P, surf, corner, c, cs, kind):
+    """closest at c + (0.25, 0, 0) in ring cs; kind 0: equal-distance candidates above and below it (ring cs: (+-1, +-1, 0); rings cs +- 1: (1, 1, 0));
+    kind 1: only below (ring cs: (+-1, -1, 0); ring cs - 1: (+-1, 1, 0))"""
+    _put(surf, P, cs, c + (0.25, 0, 0))
+    _put(corner, P, cs, c + (0.25, 0, 0))
+    if kind == 0:
+        _put(surf, P, cs, c + (1, 1, 0), c + (-1, 1, 0), c + (1, -1, 0), c + (-1, -1, 0))
+        _put(surf, P, cs + 1, c + (1, 1, 0), c + (-1, 1, 0))
+        _put(surf, P, cs - 1, c + (1, 1, 0))
+        _put(corner, P, cs + 1, c + (1, 1, 0), c + (-1, 1, 0))
+        _put(corner, P, cs - 1, c + (1, 1, 0))
+    else:
+        _put(surf, P, cs, c + (1, -1, 0), c + (-1, -1, 0))
+        _put(surf, P, cs - 1, c + (1, 1, 0), c + (-1, 1, 0))
+        _put(corner, P, cs - 1, c + (1, 1, 0), c + (-1, 1, 0))
+
+
+def lo_walk_ties(P):
+    """equal double distances of second / third candidates: above against below (up wins), two on the way up (lower index wins), two on the way
+    down (higher index wins), across two rings (class 3) and for corner one ring above against one below"""
+    surf, corner, q = {}, {}, []
+    for k in range(16):
+        c = np.array([8.0 * (k % 8), 8.0 * (k // 8), 0.25])
+        _walk_star(P, surf, corner, c, 1 + (3 * k) % (P.n_scan - 2), k % 2)
+        q.append(c)
+    return dict(surf=surf, corner=corner, flat_q=q)
+
+
+def lo_walk_gate(P):
+    """1-NN 0.0625 away; second / third candidates at double distance exactly nearest_feature_dist (3-4-0: rejected) and just below it
+    (4 - 2^-20 for the 4: accepted)"""
+    surf, corner, q = {}, {}, []
+    for k in range(12):
+        c = np.array([16.0 * (k % 6), 16.0 * (k // 6), 0.25])
+        cs = 1 + (5 * k) % (P.n_scan - 2)
+        y = 4.0 if k % 2 == 0 else 4.0 - 2.0 ** -20
+        _put(surf, P, cs, c + (0.25, 0, 0), c + (3, y, 0))
+        _put(surf, P, cs + 1, c + (-3, y, 0))
+        _put(surf, P, cs - 1, c + (3, -y, 0))
+        _put(corner, P, cs, c + (0.25, 0, 0))
+        _put(corner, P, cs + 1, c + (-3, y, 0))
+        _put(corner, P, cs - 1, c + (3, -y, 0))
+        q.append(c)
+    return dict(surf=surf, corner=corner, flat_q=q)
+
+
+def lo_ring_window(P):
+    """closest in ring cs (0, 1, mid, NS-2, NS-1); candidates at distance^2 4 in rings cs +- W (inside) and closer ones (1) in cs +- (W + 1)
+    (outside); ring mid + 1 holds no target at all; ring NS - 3 holds one target (a surf closest without any idx2); a corner query with
+    candidates only in its own ring"""
+    NS, W = P.n_scan, P.ring_window
+    mid = NS // 2
+    surf, corner, q = {}, {}, []
+    for k, cs in enumerate([0, 1, mid, NS - 2, NS - 1, mid - 1]):
+        c = np.array([12.0 * k, 0.0, 0.25])
+        _put(surf, P, cs, c + (0.25, 0, 0), c + (0, 0, 2.5))
+        _put(corner, P, cs, c + (0.25, 0, 0))
+        for sgn in (1, -1):
+            for r, o in ((cs + sgn * W, (0, 2.0 * sgn, 0)), (cs + sgn * (W + 1), (sgn * 1.0, 0, 0))):
+                if r != mid + 1 and r != NS - 3:
+                    _put(surf, P, r, c + o)
+                    _put(corner, P, r, c + o)
+        q.append(c)
+    c = np.array([0.0, 20.0, 0.25])   # the lone target of ring NS - 3
+    _put(surf, P, NS - 3, c + (0.25, 0, 0))
+    _put(surf, P, NS - 4, c + (0, 1, 0))
+    q.append(c)
+    c = np.array([12.0, 20.0, 0.25])  # corner: second candidates only in the closest's own ring
+    _put(corner, P, 2, c + (0.25, 0, 0), c + (-1.0, 0, 0), c + (0, -2.0, 0))
+    _put(surf, P, 2, c + (0, 0, 9.0))
+    q.append(c)
+    return dict(surf=surf, corner=corner, flat_q=q)
+
+
+def lo_box_edges(P):
+    """rings of 1, 31, 32, 33, 64 and 65 targets on lines along x (1 m apart, ring r at y = 0.5 r): queries at the first and last target, on
+    either side of the 32-target box seams, and beyond the ends of the lines (the nearest point of the box is its corner: bound == distance)"""
+    surf, q = {}, []
+    sizes = [1, 31, 32, 33, 64, 65]
+    for r, n in enumerate(sizes):
+        y = 0.5 * r
+        _put(surf, P, r, *[(float(i), y, 0.0) for i in range(n)])
+        for i in sorted({0, n - 1, 30, 31, 32, 33, 63, 64}):
+            if i < n:
+                q.append((float(i), y, 0.25))
+        q += [(-0.5, y, 0.25), (n - 0.5, y, 0.25), (-1.0, y, 0.0), (float(n), y, 0.0)]
+    return dict(surf=surf, corner={}, flat_q=q)
+
+
+LO_GRID_EXTENT = {"gc": 62.5, "double": 70.0, "csz8": 300.0, "none": 300.0}
+
+
+def lo_grid_scene(P, kind):
+    """a lattice of targets over [0, E] x [0, E] (E = 62.5: exactly 64 x 64 cells of 1 m, the full-grid sentinel; 70: one doubling; 300: cells of
+    8 m; 'none': the same plus one target 1e6 m away, no grid).  Queries on cell boundaries, 0.5 / 1 / 1.5 cells outside every side, exactly one
+    cell size from their nearest target in (x, y) (not settled by the grid), just inside that, and close in (x, y) but far in z"""
+    E = LO_GRID_EXTENT[kind]
+    g = lo_grid_geometry_of(E)
+    s = E / 5
+    surf, corner, q = {}, {}, []
+    for i in range(6):
+        for j in range(6):
+            t, r = np.array([i * s, j * s, 0.0]), (i + 2 * j) % (P.n_scan - 1)
+            _put(surf, P, r, t, t + (0, 0, 1.5))    # (the companions above and in the next ring let the walk accept the row)
+            _put(surf, P, r + 1, t + (0, 0, -1.5))
+            _put(corner, P, r, t)
+            _put(corner, P, r + 1, t + (0, 0, -1.5))
+    if kind == "none":
+        _put(surf, P, 0, (1e6, 0.0, 0.0))
+    csz = g[2] if g else 8.0
+    for f in (0.5, 1.0, 1.5):
+        for y in (0.0, 2 * s, E):
+            q += [(-f * csz, y, 0.0), (E + f * csz, y, 0.0), (y, -f * csz, 0.0), (y, E + f * csz, 0.0)]
+    for k in range(6):
+        t = np.array([k * s, (5 - k) * s, 0.0])
+        q += [t + (csz, 0, 0), t + (0, -csz, 0), t + (csz - 0.25, 0, 0), t + (0.5, 0, 30.0), t + (k * csz if k < 5 else 0.0, 0.0, 0.25)]
+    return dict(surf=surf, corner=corner, flat_q=q)
+
+
+def lo_grid_geometry_of(E):
+    return lo_grid_geometry(np.array([[0.0, 0.0, 0.0, 0.0], [E, E, 0.0, 0.0]], F32))
+
+
+def lo_grid_count(P, n):
+    """at 64 x 2048: a less_flat cloud of exactly n targets (a 256 x 256 lattice of 1 m, cut to n) — 65535 has a grid (cells of 8 m),
+    65536 has none and reads its boxes from HBM"""
+    xs = np.arange(n)
+    surf, q = {}, []
+    per = -(-n // P.n_scan)
+    for i in xs:
+        _put(surf, P, int(i // per), (float(i % 256), float(i // 256), 0.0))
+    rng = np.random.default_rng(n)
+    q = np.round(rng.uniform(-2, 258, (300, 3)) * 16) / 16
+    q[:, 2] = rng.uniform(-1, 1, 300)
+    return dict(surf=surf, corner={}, flat_q=q, sharp_q=q[:150])
+
+
+def lo_dense_random(P):
+    """jittered 1 m lattice targets, queries near them under a generic rotation + translation; more queries than one sweep takes and not a multiple of 16"""
+    rng = np.random.default_rng(5)
+    surf, corner = {}, {}
+    pts = []
+    for i in range(24):
+        for j in range(24):
+            pts.append((i + rng.uniform(-0.25, 0.25), j + rng.uniform(-0.25, 0.25), rng.uniform(-0.5, 0.5)))
+    pts = np.asarray(pts)
+    rr = rng.integers(0, P.n_scan, len(pts))
+    for p, r in zip(pts, rr):
+        _put(surf, P, int(r), p)
+    for p, r in zip(pts[::7], rr[::7]):
+        _put(corner, P, int(r), p)
+    p6 = np.array([0.31, -0.22, 0.05, 0.013, -0.021, 0.047])
+    from oracle import oracle_py as O
+    sel = rng.uniform(-1, 24, (200, 3))
+    R = O.transform_to_start(p6, np.array([[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 1, 0], [0, 0, 0, 0]], F32))[:, :3].astype(np.float64)
+    t = R[3]
+    Rm = (R[:3] - t).T
+    q = (np.linalg.solve(Rm, (sel - t).T)).T
+    return dict(surf=surf, corner=corner, flat_q=q[:150], sharp_q=q[:100], params6=p6, ring_len=84, short_ring=23)
+
+
+LO_SCENE_FNS = {"nn_ties": lo_nn_ties, "nn_gate": lo_nn_gate, "walk_ties": lo_walk_ties, "walk_gate": lo_walk_gate, "ring_window": lo_ring_window,
+                "box_edges": lo_box_edges, "dense_random": lo_dense_random,
+                **{f"grid_{k}": (lambda P, k=k: lo_grid_scene(P, k)) for k in LO_GRID_EXTENT},
+                "grid_count_65535": lambda P: lo_grid_count(P, 65535), "grid_count_65536": lambda P: lo_grid_count(P, 65536)}
+LO_SCENES_MODS = {"grid_gc": dict(nearest_feature_dist=100.0), "grid_double": dict(nearest_feature_dist=100.0),
+                  "grid_csz8": dict(nearest_feature_dist=100.0), "grid_none": dict(nearest_feature_dist=100.0)}
+LO_SCENES = ["nn_ties", "nn_gate", "nn_gate:nearest_feature_dist=0.49", "walk_ties", "walk_gate", "ring_window:ring_window=0", "ring_window:ring_window=1",
+             "ring_window", "ring_window:ring_window=3", "ring_window:ring_window=100", "box_edges", "grid_gc", "grid_double", "grid_csz8", "grid_none",
+             "dense_random"]
+LO_SCENES_BIG = ["grid_count_65535", "grid_count_65536"]   # 64 x 2048 only: a 16 x 1800 scan cannot hold 65535 targets
+
+
+def assert_lo_scene_premise(name, sc, o, rows):
+    """What each LO scene is built to reach, recomputed from the oracle's own outputs (a later change must not make a scene vacuous).
+    rows = lo_assoc_brute's (surf, corner) rows of the scene."""
+    from oracle import oracle_py as O
+    P, kind = sc["P"], name.split(":")[0]
+    lf, ls = sc["less_flat"], sc["less_sharp"]
+    nfd, W = P.nearest_feature_dist, P.ring_window
+    sel_f = O.transform_to_start(sc["params6"], o.get("flat"))
+    sel_s = O.transform_to_start(sc["params6"], o.get("sharp"))
+    det_f, det_s = lo_brute_detail(lf, sel_f, P, 0), lo_brute_detail(ls, sel_s, P, 1)
+    geo = lo_grid_geometry(lf)
+    surf, corner = rows
+    assert_bit_equal(o.get("lo_params_after_surf"), sc["params6"], f"{name}: params after the surf solve (lo_iters_surf = 0)")
+
+    def n_where(det, rr, pred):
+        return sum(1 for d, r in zip(det, rr) if pred(d, r))
+
+    def walk_ties(det, rr, col):
+        # accepted rows whose chosen walk candidate shares its double distance with another candidate of its class in the window
+        out = 0
+        for d, r in zip(det, rr):
+            if r[1] < 0 or r[col] < 0:
+                continue
+            pd, ring, cs = d["pd"], d["ring"], d["cs"]
+            win = (ring >= cs - W) & (ring <= cs + W)
+            cls = (ring == cs) if (col == 2 and rr is surf) else ((ring != cs) if rr is surf else (ring != cs))
+            m = win & cls & (pd == pd[r[col]])
+            m[r[1]] = False
+            out += int(m.sum() >= 2)
+        return out
+
+    if kind == "nn_ties":
+        tied = [(d, r) for d, r in zip(det_f, surf) if d["n_min"] >= 2 and float(d["dmin"]) < nfd]
+        assert len(tied) >= 8, f"{name}: {len(tied)} surf queries with an exact 1-NN tie"
+        assert all(r[1] < 0 or r[1] == d["c"] for d, r in tied)
+        g = 0.999 * geo[2] ** 2
+        assert any(float(d["dmin"]) < g for d, _ in tied) and any(float(d["dmin"]) > g for d, _ in tied), f"{name}: ties on one search path only"
+        assert n_where(det_s, corner, lambda d, r: d["n_min"] >= 2 and r[1] >= 0) >= 4, f"{name}: corner ties"
+        assert n_where(det_f, surf, lambda d, r: d["n_min"] >= 2 and float(d["dmin"]) < nfd and np.ptp(d["ring"][np.nonzero(d["d"] == d["dmin"])[0]]) == 0
+                       and np.ptp(np.nonzero(d["d"] == d["dmin"])[0]) > 32) >= 1, f"{name}: no accepted tie in one ring across boxes"
+    elif kind == "nn_gate":
+        g = F32(nfd)
+        lim = g if float(g) >= nfd else np.nextafter(g, F32(np.inf))
+        at = [r for d, r in zip(det_f, surf) if d["dmin"] == lim]
+        below = [r for d, r in zip(det_f, surf) if d["dmin"] == np.nextafter(lim, F32(0))]
+        assert at and all(r[1] < 0 and r[2] < 0 and r[3] < 0 for r in at), f"{name}: 1-NN at the gate not rejected"
+        assert any(bool(((d["pd"] < nfd) & (d["d"] == lim)).sum() >= 3) for d in det_f if d["dmin"] == lim), f"{name}: the walk would accept a row at the gate"
+        assert below and any(r[1] >= 0 for r in below), f"{name}: 1-NN one ulp below the gate never accepted"
+        if float(g) != nfd:
+            assert float(g) > nfd and any(d["dmin"] == g for d in det_f), f"{name}: f32(nearest_feature_dist) not reached"
+    elif kind == "walk_ties":
+        for what, det, rr, col in (("surf idx2", det_f, surf, 2), ("surf idx3", det_f, surf, 3), ("corner idx2", det_s, corner, 2)):
+            assert walk_ties(det, rr, col) >= 4, f"{name}: {what}: too few ties among walk candidates"
+        assert n_where(det_f, surf, lambda d, r: r[1] >= 0 and r[2] > r[1]) >= 4 and n_where(det_f, surf, lambda d, r: r[1] >= 0 and r[2] < r[1]) >= 4
+    elif kind == "walk_gate":
+        eq = n_where(det_f, surf, lambda d, r: float(d["dmin"]) < nfd and bool(((d["pd"] == nfd) & (np.abs(d["ring"] - d["cs"]) <= W)).any()))
+        assert eq >= 4, f"{name}: {eq} queries with a walk candidate at exactly nearest_feature_dist"
+        assert n_where(det_f, surf, lambda d, r: r[1] >= 0 and nfd - 1e-5 < d["pd"][r[3]] < nfd) >= 2, f"{name}: no third point just below the gate"
+        assert n_where(det_s, corner, lambda d, r: r[1] >= 0 and nfd - 1e-5 < d["pd"][r[2]] < nfd) >= 2, f"{name}: no corner point just below the gate"
+    elif kind == "ring_window":
+        if W < P.n_scan:
+            edge = n_where(det_f, surf, lambda d, r: r[3] >= 0 and abs(d["ring"][r[3]] - d["cs"]) == W and
+                           bool(((np.abs(d["ring"] - d["cs"]) == W + 1) & (d["pd"] < d["pd"][r[3]])).any()))
+            assert W == 0 or edge >= 2, f"{name}: no third point at cs +- W with a closer one at cs +- (W + 1)"
+        assert n_where(det_f, surf, lambda d, r: d["cs"] in (0, P.n_scan - 1) and float(d["dmin"]) < nfd) >= 2
+        assert n_where(det_f, surf, lambda d, r: float(d["dmin"]) < nfd and r[2] < 0 and (d["ring"] == d["cs"]).sum() == 1) >= 1, f"{name}: lone closest"
+        assert n_where(det_s, corner, lambda d, r: float(d["dmin"]) < nfd and r[2] < 0) >= 1
+    elif kind == "box_edges":
+        cnt = np.bincount(lf[:, 3].astype(np.int64), minlength=6)[:6]
+        assert cnt.tolist() == [1, 31, 32, 33, 64, 65], cnt
+        base = np.concatenate([[0], np.cumsum(cnt)])
+        pos = {int(r[1] - base[int(lf[r[1], 3])]) for r in surf if r[1] >= 0}
+        assert {0, 30, 31, 32, 33, 63, 64} <= pos, f"{name}: closest positions in their rings {sorted(pos)}"
+    elif kind.startswith("grid_count"):
+        n = int(kind.split("_")[-1])
+        assert len(lf) == n and (geo is None) == (n > 65535), (len(lf), geo)
+        assert geo is None or geo[2] == 8.0
+    elif kind.startswith("grid_"):
+        want = {"gc": (64, 64, 1.0), "double": (37, 37, 2.0), "csz8": (39, 39, 8.0), "none": None}[kind[5:]]
+        assert geo == want, f"{name}: grid {geo}"
+        csz = 8.0 if geo is None else geo[2]
+        assert n_where(det_f, surf, lambda d, r: r[1] >= 0 and float(d["dmin"]) == csz * csz) >= 2, f"{name}: no accepted 1-NN exactly one cell away"
+        assert n_where(det_f, surf, lambda d, r: r[1] >= 0 and float(d["dmin"]) < 0.999 * csz * csz) >= 2
+    elif kind == "dense_random":
+        nq = len(surf)
+        assert nq > 128 and nq % 16, f"{name}: {nq} surf queries"
+        assert (surf[:, 1] >= 0).sum() >= 20 and (corner[:, 1] >= 0).sum() >= 5, ((surf[:, 1] >= 0).sum(), (corner[:, 1] >= 0).sum())
