@@ -17,6 +17,7 @@
 #include "fe_common.h"
 #include "prof.h"
 #include "stdsort_emu.h"
+#include "vgrid.h"
 
 #define FE_BLOCK 256
 #define FE_CW 1024   // points per fe_curv workgroup
@@ -536,14 +537,12 @@ __global__ void __launch_bounds__(FV_BLOCK) fe_voxel(DevCtx d) {
 #pragma unroll
     for (int u = 0; u < FV_U; ++u) {   // (a clamped duplicate of the last point does not change min / max)
       if (i0 + u * FV_BLOCK < min(n, cap)) s_pt[i0 + u * FV_BLOCK] = pt[u];   // every later pass reads the point from LDS: one global round trip instead of three
-      mn[0] = fminf(mn[0], pt[u].x); mn[1] = fminf(mn[1], pt[u].y); mn[2] = fminf(mn[2], pt[u].z);
-      mx[0] = fmaxf(mx[0], pt[u].x); mx[1] = fmaxf(mx[1], pt[u].y); mx[2] = fmaxf(mx[2], pt[u].z);
+      vgr_box_add(mn, mx, pt[u]);
     }
   }
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { mn[a] = fminf(mn[a], __shfl_xor(mn[a], o, 64)); mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], o, 64)); }
+    vgr_wave_minmax(mn[a], mx[a]);
     if ((tid & 63) == 0) { s_red[a][tid >> 6] = mn[a]; s_red[3 + a][tid >> 6] = mx[a]; }
   }
   __syncthreads();
@@ -553,28 +552,15 @@ __global__ void __launch_bounds__(FV_BLOCK) fe_voxel(DevCtx d) {
 #pragma unroll
     for (int w = 1; w < FV_BLOCK / 64; ++w) { mn[a] = fminf(mn[a], s_red[a][w]); mx[a] = fmaxf(mx[a], s_red[3 + a][w]); }
   }
-  const long long dx = (long long)((mx[0] - mn[0]) * inv) + 1, dy = (long long)((mx[1] - mn[1]) * inv) + 1, dz = (long long)((mx[2] - mn[2]) * inv) + 1;
-  if (dx * dy * dz > 2147483647LL) {  // "leaf size too small": the input is returned unchanged
+  if (vgr_leaf_too_small(mn, mx, inv)) {  // "leaf size too small": the input is returned unchanged
     for (int i = tid; i < n; i += FV_BLOCK) out[i] = point(i);
     if (tid == 0) cnts[4] = n;
     return;
   }
   FV_TICK(1);
-  int minb[3], divb[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    minb[a] = (int)floorf(mn[a] * inv);
-    divb[a] = (int)floorf(mx[a] * inv) - minb[a] + 1;
-  }
-  const int mul1 = divb[0], mul2 = divb[0] * divb[1];
+  const VgrGeom g = vgr_geom(mn, mx, inv);
 #pragma unroll 4
-  for (int i = tid; i < n; i += FV_BLOCK) {
-    const float4 q = point(i);
-    const int i0 = (int)(floorf(q.x * inv) - (float)minb[0]);
-    const int i1 = (int)(floorf(q.y * inv) - (float)minb[1]);
-    const int i2 = (int)(floorf(q.z * inv) - (float)minb[2]);
-    s_key[i] = (uint32_t)(i0 + i1 * mul1 + i2 * mul2);
-  }
+  for (int i = tid; i < n; i += FV_BLOCK) s_key[i] = vgr_id(g, point(i), inv);
   __syncthreads();
   FV_TICK(2);
   // runs of consecutive equal voxel ids
@@ -602,8 +588,7 @@ __global__ void __launch_bounds__(FV_BLOCK) fe_voxel(DevCtx d) {
   // into <= FV_NB buckets that are monotone in the voxel id (LDS atomics; arbitrary order inside a bucket), then
   // every run ranks itself among the one or two runs of its bucket — instead of against all runs of the ring.
   {
-    unsigned T = (unsigned)divb[0] * (unsigned)divb[1] * (unsigned)divb[2];
-    if (T == 0) T = 1;
+    const unsigned long long T = max(g.T, 1ull);
     int shift = 0;
     while (((T - 1) >> shift) >= (unsigned)FV_NB) ++shift;
     const int nb = (int)((T - 1) >> shift) + 1;

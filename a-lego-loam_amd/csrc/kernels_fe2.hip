@@ -20,6 +20,7 @@
 #include <cstdlib>
 #include "dev_common.h"
 #include "prof.h"
+#include "vgrid.h"
 
 #define FE_MAXH 4096   // largest horizon_scan (as kernels_fe.hip)
 
@@ -681,9 +682,7 @@ __global__ void __launch_bounds__(FO_BLOCK) fe_ring_out(DevCtx d) {
 #pragma nounroll
     for (int i = tid; i < n_all; i += FO_BLOCK) {
       if (hole(i)) continue;
-      const float4 q = point(i);
-      mn[0] = fminf(mn[0], q.x); mn[1] = fminf(mn[1], q.y); mn[2] = fminf(mn[2], q.z);
-      mx[0] = fmaxf(mx[0], q.x); mx[1] = fmaxf(mx[1], q.y); mx[2] = fmaxf(mx[2], q.z);
+      vgr_box_add(mn, mx, point(i));
     }
     (void)wg_box(0);
   };
@@ -701,37 +700,24 @@ __global__ void __launch_bounds__(FO_BLOCK) fe_ring_out(DevCtx d) {
         const int i = i0 + u * FO_BLOCK;
         if (i < min(n_all, cap)) s_pt[i] = pt[u];
 #endif
-        mn[0] = fminf(mn[0], pt[u].x); mn[1] = fminf(mn[1], pt[u].y); mn[2] = fminf(mn[2], pt[u].z);
-        mx[0] = fmaxf(mx[0], pt[u].x); mx[1] = fmaxf(mx[1], pt[u].y); mx[2] = fmaxf(mx[2], pt[u].z);
+        vgr_box_add(mn, mx, pt[u]);
       }
     }
     nval = n_all - wg_box(nh);
   }
   FO_TICK(2);
   bool passthrough = false;
-  if (nval > 0) {
-    auto too_many = [&]() -> bool {
-      const long long dx = (long long)((mx[0] - mn[0]) * inv) + 1, dy = (long long)((mx[1] - mn[1]) * inv) + 1, dz = (long long)((mx[2] - mn[2]) * inv) + 1;
-      return dx * dy * dz > 2147483647LL;
-    };
-    if (too_many()) { bbox_exact(); passthrough = too_many(); }   // "leaf size too small": the input is returned unchanged
-  }
+  if (nval > 0 && vgr_leaf_too_small(mn, mx, inv)) { bbox_exact(); passthrough = vgr_leaf_too_small(mn, mx, inv); }   // "leaf size too small": the input is returned unchanged
   int nout = 0, nrv = 0, nruns = 0, vex = 0;   // vex: voxels before every (chunk, wavefront) of the order, one per lane
   if (passthrough) {
     if (tid == 0) { int acc = 0; for (int w = 0; w <= BW; ++w) { s_wpre[w] = acc; acc += __popc(s_bm[w]); } }
     nout = nval;
   } else if (nval > 0) {
-    int minb[3], divb[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      minb[a] = (int)floorf(mn[a] * inv);
-      divb[a] = (int)floorf(mx[a] * inv) - minb[a] + 1;
-    }
-    const int mul1 = divb[0], mul2 = divb[0] * divb[1];
+    const VgrGeom g = vgr_geom(mn, mx, inv);
     // a hole takes the id of the nearest non-hole before it (none: invalid, a leading run that is never ordered), so that the few
     // labelled points do not cut the runs
     // (24-bit multiplies run at full rate, 32-bit ones at a quarter)
-    const bool u24 = (unsigned)divb[0] < (1u << 24) && (unsigned)divb[1] < (1u << 24) && (unsigned)divb[2] < (1u << 24) && (unsigned)mul2 < (1u << 24);
+    const bool u24 = (unsigned)g.divb[0] < (1u << 24) && (unsigned)g.divb[1] < (1u << 24) && (unsigned)g.divb[2] < (1u << 24) && g.mul2 < (1u << 24);
     // runs of consecutive equal voxel ids: the heads inside a wavefront are counted per (chunk, wavefront) while the keys are written (the key of the
     // lane before: DPP wave_shr); the first position of a wavefront is compared after the barrier, when every wavefront scans the counts
     auto key_chunk = [&](int c, float4 own) {
@@ -741,10 +727,9 @@ __global__ void __launch_bounds__(FO_BLOCK) fe_ring_out(DevCtx d) {
         const int src = prev_kept(i);
         float4 q = own;
         if (src != i) q = point(max(src, 0));   // (a hole: the point it inherits from)
-        const int i0 = (int)(floorf(q.x * inv) - (float)minb[0]);
-        const int i1 = (int)(floorf(q.y * inv) - (float)minb[1]);
-        const int i2 = (int)(floorf(q.z * inv) - (float)minb[2]);
-        const uint32_t id = u24 ? mad_u24((uint32_t)i2, (uint32_t)mul2, mad_u24((uint32_t)i1, (uint32_t)mul1, (uint32_t)i0)) : (uint32_t)(i0 + i1 * mul1 + i2 * mul2);
+        int i0, i1, i2;
+        vgr_coords(g, q, inv, &i0, &i1, &i2);
+        const uint32_t id = u24 ? mad_u24((uint32_t)i2, g.mul2, mad_u24((uint32_t)i1, g.mul1, (uint32_t)i0)) : (uint32_t)i0 + (uint32_t)i1 * g.mul1 + (uint32_t)i2 * g.mul2;
         key = src < 0 ? FO_INVALID : id;
         s_key[i] = key;
       }
@@ -783,8 +768,7 @@ __global__ void __launch_bounds__(FO_BLOCK) fe_ring_out(DevCtx d) {
     FO_TICK(3);
     // order the valid runs by (voxel id, run index): dealt into <= FO_NB buckets monotone in the voxel id, ranked inside the bucket
     {
-      unsigned T = (unsigned)divb[0] * (unsigned)divb[1] * (unsigned)divb[2];
-      if (T == 0) T = 1;
+      const unsigned long long T = max(g.T, 1ull);
       int shift = 0;
       while (((T - 1) >> shift) >= (unsigned)FO_NB) ++shift;
       const int nb = (int)((T - 1) >> shift) + 1;

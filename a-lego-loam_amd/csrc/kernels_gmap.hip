@@ -25,6 +25,7 @@
 #include "guard_alloc.h"
 #include "lm_ctx.h"
 #include "prof.h"
+#include "vgrid.h"
 
 #define GM_T 256
 #define GS_T 1024                    // scan workgroup
@@ -184,23 +185,15 @@ static void scan_excl(int* a, int n, int* bs, hipStream_t st) {
 }
 
 // ---- device-wide VoxelGrid ----------------------------------------------------------------------------------------
-DEV_INLINE float vbox_dec(unsigned u) { return __int_as_float((int)((u >> 31) ? (u ^ 0x80000000u) : ~u)); }
-
-// getMinMax3D: per-lane fminf / fmaxf (NaN-ignoring, as std::min / std::max against a finite running value), wavefront shuffles,
-// one atomicMin per workgroup and axis on the order-preserving codes (bbox[4..6] hold ~code of the max)
+// getMinMax3D: per-lane fminf / fmaxf, wavefront shuffles, one atomicMin per workgroup and axis on the order-preserving codes (vgrid.h)
 __global__ void __launch_bounds__(GV_T) gv_bbox(const float4* in, int n, unsigned* bbox) {
   __shared__ float s_r[6][GV_T / 64];
   float mn[3] = {3.402823466e+38f, 3.402823466e+38f, 3.402823466e+38f}, mx[3] = {-3.402823466e+38f, -3.402823466e+38f, -3.402823466e+38f};
-  for (size_t i = (size_t)blockIdx.x * GV_T + threadIdx.x; i < (size_t)n; i += (size_t)gridDim.x * GV_T) {
-    const float4 p = in[i];
-    mn[0] = fminf(mn[0], p.x); mn[1] = fminf(mn[1], p.y); mn[2] = fminf(mn[2], p.z);
-    mx[0] = fmaxf(mx[0], p.x); mx[1] = fmaxf(mx[1], p.y); mx[2] = fmaxf(mx[2], p.z);
-  }
+  for (size_t i = (size_t)blockIdx.x * GV_T + threadIdx.x; i < (size_t)n; i += (size_t)gridDim.x * GV_T) vgr_box_add(mn, mx, in[i]);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { mn[a] = fminf(mn[a], __shfl_xor(mn[a], o, 64)); mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], o, 64)); }
+    vgr_wave_minmax(mn[a], mx[a]);
     if (lane == 0) { s_r[a][wave] = mn[a]; s_r[3 + a][wave] = mx[a]; }
   }
   __syncthreads();
@@ -208,8 +201,8 @@ __global__ void __launch_bounds__(GV_T) gv_bbox(const float4* in, int n, unsigne
     const int a = threadIdx.x;
     float v = s_r[a][0];
     for (int w = 1; w < GV_T / 64; ++w) v = a < 3 ? fminf(v, s_r[a][w]) : fmaxf(v, s_r[a][w]);
-    if (a < 3) atomicMin(bbox + a, vbox_enc(v));
-    else atomicMin(bbox + 1 + a, ~vbox_enc(v));
+    if (a < 3) atomicMin(bbox + a, vgr_enc(v));
+    else atomicMin(bbox + 1 + a, ~vgr_enc(v));
   }
 }
 
@@ -218,32 +211,25 @@ __global__ void gv_geom(const unsigned* bbox, float leaf, int* geom) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   const float inv = 1.0f / leaf;
   float mn[3], mx[3];
-  for (int a = 0; a < 3; ++a) { mn[a] = vbox_dec(bbox[a]); mx[a] = vbox_dec(~bbox[4 + a]); }
-  const long long dx = (long long)((mx[0] - mn[0]) * inv) + 1, dy = (long long)((mx[1] - mn[1]) * inv) + 1, dz = (long long)((mx[2] - mn[2]) * inv) + 1;
-  if (dx * dy * dz > 2147483647LL) { geom[GG_PASS] = 1; geom[GG_P] = 0; return; }   // PCL: "leaf size too small" -> output = input
-  int minb[3], divb[3];
-  for (int a = 0; a < 3; ++a) { minb[a] = (int)floorf(mn[a] * inv); divb[a] = (int)floorf(mx[a] * inv) - minb[a] + 1; geom[GG_MINB + a] = minb[a]; }
-  geom[GG_MUL1] = divb[0];
-  geom[GG_MUL2] = (int)((unsigned)divb[0] * (unsigned)divb[1]);   // (int arithmetic wraps as the reference's does)
-  const unsigned long long T = (unsigned long long)(unsigned)divb[0] * (unsigned)divb[1] * (unsigned)divb[2];
-  int bits = 0;
-  if (T > 0xFFFFFFFFull || T == 0) bits = 32;
-  else if (T > 1) bits = 32 - __clz((int)(unsigned)(T - 1));
+  vgr_box_load(bbox, mn, mx);
+  if (vgr_leaf_too_small(mn, mx, inv)) { geom[GG_PASS] = 1; geom[GG_P] = 0; return; }   // PCL: "leaf size too small" -> output = input
+  const VgrGeom g = vgr_geom(mn, mx, inv);
+  for (int a = 0; a < 3; ++a) geom[GG_MINB + a] = g.minb[a];
+  geom[GG_MUL1] = (int)g.mul1;
+  geom[GG_MUL2] = (int)g.mul2;
   geom[GG_PASS] = 0;
-  geom[GG_P] = (bits + GV_D - 1) / GV_D;
+  geom[GG_P] = (vgr_bits(g.T) + GV_D - 1) / GV_D;
 }
 
 __global__ void __launch_bounds__(GV_T) gv_keys(const float4* in, int n, float leaf, const int* geom, unsigned* keys, int* vals) {
   if (geom[GG_PASS]) return;
   const float inv = 1.0f / leaf;
-  const float fb0 = (float)geom[GG_MINB], fb1 = (float)geom[GG_MINB + 1], fb2 = (float)geom[GG_MINB + 2];
-  const unsigned mul1 = (unsigned)geom[GG_MUL1], mul2 = (unsigned)geom[GG_MUL2];
+  VgrGeom g;
+  for (int a = 0; a < 3; ++a) g.minb[a] = geom[GG_MINB + a];
+  g.mul1 = (unsigned)geom[GG_MUL1];
+  g.mul2 = (unsigned)geom[GG_MUL2];
   for (size_t i = (size_t)blockIdx.x * GV_T + threadIdx.x; i < (size_t)n; i += (size_t)gridDim.x * GV_T) {
-    const float4 p = in[i];
-    const int i0 = (int)(floorf(p.x * inv) - fb0);
-    const int i1 = (int)(floorf(p.y * inv) - fb1);
-    const int i2 = (int)(floorf(p.z * inv) - fb2);
-    keys[i] = (unsigned)i0 + (unsigned)i1 * mul1 + (unsigned)i2 * mul2;
+    keys[i] = vgr_id(g, in[i], inv);
     vals[i] = (int)i;
   }
 }

@@ -14,6 +14,7 @@
 #include "prof.h"
 #include "lm_ctx.h"
 #include "gmap.h"
+#include "vgrid.h"
 
 #define LM_BLOCK 256
 
@@ -176,11 +177,6 @@ __global__ void __launch_bounds__(LM_BLOCK) lm_total(DevCtx d, LmCtx L) {
   if (blockIdx.x == 0 && threadIdx.x == 0) li[LI_NTOTAL] = ns + no;
 }
 
-DEV_INLINE float vxl_dec(unsigned e) {
-  const unsigned b = (e >> 31) ? (e ^ 0x80000000u) : ~e;
-  return __int_as_float((int)b);
-}
-
 // The cell of a point is floorf(x * inv) - ox in integers: inv is a power of two, so x * inv and its floor are exact and every point lies in its true
 // cell of a global lattice.  (floorf((x - ox) * inv) with a float origin rounds in the subtraction: across a binade boundary of x - ox a point at
 // f32 d^2 < cell^2 from a query could sit two cells away from it, outside the 27 cells lm_knn searches.)  The float is clamped before the
@@ -207,7 +203,7 @@ __global__ void __launch_bounds__(LM_BLOCK) lm_grid_build(DevCtx d, LmCtx L) {
     const unsigned* bb = d.opt_map_merge ? L.map_bbox + ((size_t)slot * 2 + m) * 8 : L.vox_bbox + ((size_t)(slot - L.vox_slot0) * 2 + m) * 8;
     GridGeom g;
     float mn[3], mx[3];
-    for (int a = 0; a < 3; ++a) { mn[a] = vxl_dec(bb[a]); mx[a] = vxl_dec(~bb[4 + a]); }
+    vgr_box_load(bb, mn, mx);
     if (li[LI_KRAW_C + m] <= 0) { for (int a = 0; a < 3; ++a) { mn[a] = 0.f; mx[a] = 0.f; } }
     // cell^2 >= knn_max_dist: lm_knn keeps only candidates with f32 d^2 < flim <= cell^2, so |dx| < cell along every axis in real arithmetic
     // (rounding is monotonic and cell is a power of two) and the candidate is at most one cell away from the query

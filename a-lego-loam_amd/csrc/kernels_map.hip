@@ -24,6 +24,7 @@
 #include "dev_common.h"
 #include "lm_ctx.h"
 #include "prof.h"
+#include "vgrid.h"
 
 typedef unsigned long long u64;
 
@@ -193,8 +194,7 @@ __global__ void __launch_bounds__(MU_T) map_update(DevCtx d, LmCtx L, MapWork W)
       kraw += s_kr_tot[w];
       for (int a = 0; a < 3; ++a) { mn[a] = fminf(w ? mn[a] : s_box[a][0], s_box[a][w]); mx[a] = fmaxf(w ? mx[a] : s_box[3 + a][0], s_box[3 + a][w]); }
     }
-    const long long dx = (long long)((mx[0] - mn[0]) * inv) + 1, dy = (long long)((mx[1] - mn[1]) * inv) + 1, dz = (long long)((mx[2] - mn[2]) * inv) + 1;
-    const bool pass = kraw > 0 && dx * dy * dz > 2147483647LL;   // PCL: "leaf size too small" -> output = input (in the reference's order)
+    const bool pass = kraw > 0 && vgr_leaf_too_small(mn, mx, inv);   // PCL: "leaf size too small" -> output = input (in the reference's order)
     // A window that passes through keeps no voxel list: its map is the raw concatenation, and one of its runs may be a key frame that was
     // itself too large for a voxel id (stored unsorted by the VoxelGrid sort, voxel.h) — the merges below would read it as sorted.  U is
     // rebuilt from the window's runs by the next window that is filtered (LI_UVALID is cleared below when a map passed).
@@ -407,7 +407,7 @@ __global__ void __launch_bounds__(MU_T) map_update(DevCtx d, LmCtx L, MapWork W)
       if (pass) atomicOr(&li[LI_MAP_PASS], 1 << m); else atomicAnd(&li[LI_MAP_PASS], ~(1 << m));
       if (!pass && s_err) li[LI_OVERFLOW] = s_err == 2 ? 1 : 4;   // 4: voxel list out of sync with the window (internal error)
       unsigned* bb = L.map_bbox + ((size_t)slot * 2 + m) * 8;
-      for (int a = 0; a < 3; ++a) { bb[a] = vbox_enc(mn[a]); bb[4 + a] = ~vbox_enc(mx[a]); }
+      for (int a = 0; a < 3; ++a) { bb[a] = vgr_enc(mn[a]); bb[4 + a] = ~vgr_enc(mx[a]); }
     }
   }
   }   // items of this workgroup

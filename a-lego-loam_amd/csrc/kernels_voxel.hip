@@ -19,15 +19,12 @@
 #include <vector>
 
 #include "voxel.h"
+#include "vgrid.h"
 #include "guard_alloc.h"
 #include "prof.h"
 
 typedef unsigned long long u64;
 
-__device__ __forceinline__ unsigned vx_enc(float f) {
-  const unsigned b = (unsigned)__float_as_int(f);
-  return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
 __device__ __forceinline__ bool vx_enabled(const VoxJob& J) { return J.enable == nullptr || *J.enable != 0; }
 
 #ifndef VX_SMALL_MAX
@@ -92,15 +89,11 @@ __device__ void vox_big_job(const VoxCtx& V, int job, unsigned char* smem) {
 #pragma unroll
     for (int k = 0; k < VG_U; ++k) p[k] = J.in[min(i0 + k * VG_T, n - 1)];
 #pragma unroll
-    for (int k = 0; k < VG_U; ++k) {
-      mn[0] = fminf(mn[0], p[k].x); mn[1] = fminf(mn[1], p[k].y); mn[2] = fminf(mn[2], p[k].z);
-      mx[0] = fmaxf(mx[0], p[k].x); mx[1] = fmaxf(mx[1], p[k].y); mx[2] = fmaxf(mx[2], p[k].z);
-    }
+    for (int k = 0; k < VG_U; ++k) vgr_box_add(mn, mx, p[k]);
   }
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { mn[a] = fminf(mn[a], __shfl_xor(mn[a], o, 64)); mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], o, 64)); }
+    vgr_wave_minmax(mn[a], mx[a]);
     if (lane == 0) { s_red[a][wave] = mn[a]; s_red[3 + a][wave] = mx[a]; }
   }
   __syncthreads();
@@ -112,14 +105,13 @@ __device__ void vox_big_job(const VoxCtx& V, int job, unsigned char* smem) {
   }
   if (tid < 3) {   // (selects, not mn[tid]: a dynamically indexed local array lives in scratch memory)
     unsigned* bb = V.bbox + job * 8;
-    bb[tid] = vx_enc(tid == 0 ? mn[0] : tid == 1 ? mn[1] : mn[2]);
-    bb[4 + tid] = ~vx_enc(tid == 0 ? mx[0] : tid == 1 ? mx[1] : mx[2]);
+    bb[tid] = vgr_enc(tid == 0 ? mn[0] : tid == 1 ? mn[1] : mn[2]);
+    bb[4 + tid] = ~vgr_enc(tid == 0 ? mx[0] : tid == 1 ? mx[1] : mx[2]);
   }
-  const long long dx = (long long)((mx[0] - mn[0]) * inv) + 1, dy = (long long)((mx[1] - mn[1]) * inv) + 1, dz = (long long)((mx[2] - mn[2]) * inv) + 1;
   const int sel = (J.mode == 1 && J.out_sel) ? *J.out_sel : 0;
   float4* const outp = J.out + (size_t)sel * (J.mode == 1 ? J.out_stride : 0);
   if (J.mode == 1 && tid < 6 && J.box_out) J.box_out[(size_t)sel * 8 + (tid < 3 ? tid : tid + 1)] = tid == 0 ? mn[0] : tid == 1 ? mn[1] : tid == 2 ? mn[2] : tid == 3 ? mx[0] : tid == 4 ? mx[1] : mx[2];
-  if (dx * dy * dz > 2147483647LL) {  // PCL: "leaf size too small" -> output = input
+  if (vgr_leaf_too_small(mn, mx, inv)) {  // PCL: "leaf size too small" -> output = input
     // (mode 1: the cloud is stored unsorted.  Its box lies inside the box of every window that holds it, so every such window passes
     // through too, and map_update reads no sorted run of a window that passes through.)
     for (int i = tid; i < min(n, J.out_cap); i += VG_T) outp[i] = J.in[i];
@@ -127,13 +119,8 @@ __device__ void vox_big_job(const VoxCtx& V, int job, unsigned char* smem) {
                     if (J.mode == 1 && J.n_sel_out) J.n_sel_out[(size_t)sel * J.n_sel_stride] = min(n, J.out_cap); }
     return;
   }
-  int minb[3], divb[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) { minb[a] = (int)floorf(mn[a] * inv); divb[a] = (int)floorf(mx[a] * inv) - minb[a] + 1; }
-  const int mul1 = divb[0], mul2 = divb[0] * divb[1];
-  unsigned T = (unsigned)divb[0] * (unsigned)divb[1] * (unsigned)divb[2];
-  if (T < 2) T = 2;
-  const int bits = 32 - __clz((int)(T - 1));
+  const VgrGeom g = vgr_geom(mn, mx, inv);
+  const int bits = max(vgr_bits(g.T), 1);
   const int P = (bits + VG_DMAX - 1) / VG_DMAX, D = (bits + P - 1) / P, nd = 1 << D;
   const unsigned dmask = (unsigned)(nd - 1);
   // every wavefront owns [seg0, seg1): whole rounds of 64 so that lanes are in index order
@@ -154,10 +141,7 @@ __device__ void vox_big_job(const VoxCtx& V, int job, unsigned char* smem) {
     for (int k = 0; k < VG_U; ++k) {
       const int i = r0 + 64 * k;
       if (i < seg1) {
-        const int i0 = (int)(floorf(pt[k].x * inv) - (float)minb[0]);
-        const int i1 = (int)(floorf(pt[k].y * inv) - (float)minb[1]);
-        const int i2 = (int)(floorf(pt[k].z * inv) - (float)minb[2]);
-        const unsigned key = (unsigned)(i0 + i1 * mul1 + i2 * mul2);
+        const unsigned key = vgr_id(g, pt[k], inv);
         keys[i] = key;
         atomicAdd(&s_cnt[0][wave][key & dmask], 1);
       }
@@ -341,15 +325,10 @@ __device__ void vox_small_job(const VoxCtx& V, int job) {
   VG_TICK(0);
   // getMinMax3D
   float mn[3] = {3.402823466e+38f, 3.402823466e+38f, 3.402823466e+38f}, mx[3] = {-3.402823466e+38f, -3.402823466e+38f, -3.402823466e+38f};
-  for (int i = tid; i < n; i += VX_SB) {
-    const float4 p = J.in[i];
-    mn[0] = fminf(mn[0], p.x); mn[1] = fminf(mn[1], p.y); mn[2] = fminf(mn[2], p.z);
-    mx[0] = fmaxf(mx[0], p.x); mx[1] = fmaxf(mx[1], p.y); mx[2] = fmaxf(mx[2], p.z);
-  }
+  for (int i = tid; i < n; i += VX_SB) vgr_box_add(mn, mx, J.in[i]);
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { mn[a] = fminf(mn[a], __shfl_xor(mn[a], o, 64)); mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], o, 64)); }
+    vgr_wave_minmax(mn[a], mx[a]);
     if (lane == 0) { s_red[a][wave] = mn[a]; s_red[3 + a][wave] = mx[a]; }
   }
   __syncthreads();
@@ -361,38 +340,25 @@ __device__ void vox_small_job(const VoxCtx& V, int job) {
   }
   if (tid < 3) {   // (selects, not mn[tid]: a dynamically indexed local array lives in scratch memory)
     unsigned* bb = V.bbox + job * 8;
-    bb[tid] = vx_enc(tid == 0 ? mn[0] : tid == 1 ? mn[1] : mn[2]);
-    bb[4 + tid] = ~vx_enc(tid == 0 ? mx[0] : tid == 1 ? mx[1] : mx[2]);
+    bb[tid] = vgr_enc(tid == 0 ? mn[0] : tid == 1 ? mn[1] : mn[2]);
+    bb[4 + tid] = ~vgr_enc(tid == 0 ? mx[0] : tid == 1 ? mx[1] : mx[2]);
   }
-  const long long dx = (long long)((mx[0] - mn[0]) * inv) + 1, dy = (long long)((mx[1] - mn[1]) * inv) + 1, dz = (long long)((mx[2] - mn[2]) * inv) + 1;
   if (J.mode == 1 && tid < 6 && J.box_out) J.box_out[(size_t)sel * 8 + (tid < 3 ? tid : tid + 1)] = tid == 0 ? mn[0] : tid == 1 ? mn[1] : tid == 2 ? mn[2] : tid == 3 ? mx[0] : tid == 4 ? mx[1] : mx[2];
-  if (dx * dy * dz > 2147483647LL) {  // PCL: "leaf size too small" -> output = input
+  if (vgr_leaf_too_small(mn, mx, inv)) {  // PCL: "leaf size too small" -> output = input
     for (int i = tid; i < min(n, J.out_cap); i += VX_SB) outp[i] = J.in[i];
     if (tid == 0) { *J.n_out = min(n, J.out_cap); if (n > J.out_cap && J.overflow) *J.overflow = 1;   // (mode 1: stored unsorted, see vox_big_job)
                     if (J.mode == 1 && J.n_sel_out) J.n_sel_out[(size_t)sel * J.n_sel_stride] = min(n, J.out_cap); }
     return;
   }
   VG_TICK(1);
-  int minb[3], divb[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) { minb[a] = (int)floorf(mn[a] * inv); divb[a] = (int)floorf(mx[a] * inv) - minb[a] + 1; }
-  const int mul1 = divb[0], mul2 = divb[0] * divb[1];
-  unsigned T = (unsigned)divb[0] * (unsigned)divb[1] * (unsigned)divb[2];
-  if (T == 0) T = 1;
+  const VgrGeom g = vgr_geom(mn, mx, inv);
   // ---- voxel ids
-  for (int i = tid; i < n; i += VX_SB) {
-    const float4 p = J.in[i];
-    const int i0 = (int)(floorf(p.x * inv) - (float)minb[0]);
-    const int i1 = (int)(floorf(p.y * inv) - (float)minb[1]);
-    const int i2 = (int)(floorf(p.z * inv) - (float)minb[2]);
-    s_key[i] = (unsigned)(i0 + i1 * mul1 + i2 * mul2);
-  }
+  for (int i = tid; i < n; i += VX_SB) s_key[i] = vgr_id(g, J.in[i], inv);
   VG_TICK(2);
   // ---- stable LSD radix sort of the point order by voxel id (as vox_big, but every array in LDS): every wavefront owns a
   // contiguous segment, counts its digits, and after the digit-major / wave-minor prefix scatters its segment in order; the
   // rank among equal digits inside a round of 64 comes from D ballots.  The order inside a voxel stays the original one.
-  if (T < 2) T = 2;
-  const int bits = 32 - __clz((int)(T - 1));
+  const int bits = max(vgr_bits(g.T), 1);
   const int P = (bits + VS_DMAX - 1) / VS_DMAX, D = (bits + P - 1) / P, nd = 1 << D;
   const unsigned dmask = (unsigned)(nd - 1);
   const int seglen = ((n + VX_SB - 1) / VX_SB) * 64;

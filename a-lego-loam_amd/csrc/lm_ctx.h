@@ -45,22 +45,6 @@ enum {
 
 struct GridGeom { int ox, oy, oz; float inv; int gx, gy, gz, ncell; };   // cell of x: floorf(x * inv) - ox (lm_grid_build)
 
-// Packed voxel key of a point: PCL's VoxelGrid orders the output by idx = i + j dx + k dx dy with (i, j, k) the integer voxel
-// coordinates relative to the cloud's bounding box, i.e. lexicographically by (floor(z inv), floor(y inv), floor(x inv)) — an order that
-// does not depend on the bounding box.  21 bits per axis (|coordinate| < 2^20 voxels: 419 km at a 0.4 m leaf).
-DEV_INLINE unsigned long long vkey_pack(int ix, int iy, int iz) {
-  const int B = 1 << 20;
-  const unsigned long long x = (unsigned long long)(unsigned)min(max(ix + B, 0), 2 * B - 1), y = (unsigned long long)(unsigned)min(max(iy + B, 0), 2 * B - 1),
-                           z = (unsigned long long)(unsigned)min(max(iz + B, 0), 2 * B - 1);
-  return (z << 42) | (y << 21) | x;
-}
-DEV_INLINE unsigned long long vkey_of(const float4& p, float inv) {   // floor(p * inverse_leaf_size) as pcl::VoxelGrid computes it (f32)
-  return vkey_pack((int)floorf(p.x * inv), (int)floorf(p.y * inv), (int)floorf(p.z * inv));
-}
-DEV_INLINE unsigned vbox_enc(float f) {   // order-preserving u32 code of a float (the VoxelGrid kernels' bounding-box format)
-  const unsigned b = (unsigned)__float_as_int(f);
-  return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
 
 // f32 4x4 of transformPointCloud (laserMapping.h:166-173): AngleAxisf(yaw,Z)*AngleAxisf(pitch,Y)*AngleAxisf(roll,X).
 // sin/cos of the half angles are glibc's sinf / cosf (dev_common.h), as Eigen's Quaternionf(AngleAxisf) calls them.
@@ -128,7 +112,7 @@ struct LmCtx {
   double* shard_part;                             // [slot][32] this rank's partial sums of an evaluation: 21 J^T J, 6 J^T r, cost, corner / surf rows; all-reduced in place
   void* shard_state;                              // [slot] LmState of the solve in flight (dev_cost.h)
   int* shard_ctl;                                 // [slot][8]: 0 local rows, 1 action of the last step, 2 solve finished, 3 outer iteration, 4 guard failed
-  unsigned* map_bbox;                             // [slot][2][8] bounding box of the window's points in the VoxelGrid kernels' encoding (merge path)
+  unsigned* map_bbox;                             // [slot][2][8] bounding box of the window's points in the VoxelGrid kernels' encoding (vgrid.h; merge path)
   // the same key frames as saveKeyFramesAndFactor stores them (sensor frame, :553-555): host read-back + pose correction
   float4 *kf_raw_c, *kf_raw_s, *kf_raw_o;         // [slot][KR][kf_cap_*]
   int* rec;                                       // [slot][K] frame ids held by recent_*_keyframes_, front first

@@ -36,7 +36,7 @@ struct VoxJob {
 struct VoxCtx {
   VoxJob* jobs;         // device array [njobs]
   int njobs;
-  unsigned* bbox;       // [job][8] ordered-int encoded min xyz (0..2) and ~max xyz (4..6) of the input cloud
+  unsigned* bbox;       // [job][8] bounding box of the input cloud (vgrid.h format)
   unsigned* keys;       // voxel id per input point; later the list of voxel run starts
   unsigned long long *pairs_a, *pairs_b;  // (voxel id << 32 | position) ping-pong buffers of the radix passes
   int *list_small, *list_big, *cnt;       // work lists of a round (vox_plan): enabled jobs of <= 8192 / more points; cnt[2]

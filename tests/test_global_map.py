@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from alego_amd import binding, synth
-from util import assert_bit_equal
+from util import assert_bit_equal, tall_cloud
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ALL = binding.MAP_SURF | binding.MAP_CORNER | binding.MAP_OUTLIER
@@ -245,7 +245,8 @@ def test_batch_replay_global_maps_match_single_slot_replicas():
 
 
 VG_CASES = ["uniform_1M", "clustered_1M", "uniform_4M", "clustered_4M", "lattice_negative", "one_voxel_1e5",
-            f"threshold_{GV_SMALL_MAX - 1}", f"threshold_{GV_SMALL_MAX}", f"threshold_{GV_SMALL_MAX + 1}", "n1"]
+            f"threshold_{GV_SMALL_MAX - 1}", f"threshold_{GV_SMALL_MAX}", f"threshold_{GV_SMALL_MAX + 1}", "n1",
+            f"tall_{GV_SMALL_MAX // 2}", f"tall_{GV_SMALL_MAX * 2}"]   # more than 2^32 grid cells
 
 
 def _vg_case(name):
@@ -270,6 +271,8 @@ def _vg_case(name):
         return cloud(one[rng.permutation(one.shape[0])]), 0.4
     if name.startswith("threshold_"):
         return cloud(rng.uniform(-30, 30, (int(name.split("_")[1]), 3))), 0.4
+    if name.startswith("tall_"):
+        return tall_cloud(int(name.split("_")[1]), rng), 1.0
     assert name == "n1"
     return cloud(np.array([[1.0, -2.0, 3.0]])), 0.4
 

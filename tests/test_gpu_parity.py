@@ -8,7 +8,7 @@ import pytest
 
 from alego_amd import binding, synth
 from oracle import oracle_py as O
-from util import KNN_SCENES, assert_bit_equal, assert_knn_scene_premise, imu_stream, knn_scene, knn_sparse_box_scene, lm_unit_cells_needed, quat_angle, run_knn_scene
+from util import KNN_SCENES, assert_bit_equal, assert_knn_scene_premise, imu_stream, knn_scene, knn_sparse_box_scene, lm_unit_cells_needed, quat_angle, run_knn_scene, tall_cloud
 
 pytestmark = pytest.mark.gpu
 POSE_TOL = 1e-4
@@ -874,11 +874,11 @@ def test_plane_fit_on_rank_deficient_neighbourhoods():
 
 @pytest.mark.parametrize("n,leaf,kind", [(0, 0.4, "gauss"), (1, 0.4, "gauss"), (37, 0.4, "gauss"), (3000, 0.4, "gauss"), (8192, 0.8, "gauss"),
                                          (8193, 0.8, "gauss"), (60000, 0.4, "gauss"), (60000, 0.8, "dense"), (120000, 0.8, "wall"),
-                                         (5000, 0.001, "gauss"), (20000, 50.0, "gauss")])
+                                         (5000, 0.001, "gauss"), (20000, 50.0, "gauss"), (4096, 1.0, "tall")])
 def test_device_voxel_grid_bit_exact(params_a, n, leaf, kind):
     """Both device VoxelGrid paths (LDS-resident radix sort up to 8192 points, the HBM-scratch radix sort above) against the
     oracle's restatement of pcl::VoxelGrid: small, large, skewed (thousands of points in one voxel), leaf too small
-    (PCL returns the input) and leaf larger than the cloud (a single voxel)."""
+    (PCL returns the input), leaf larger than the cloud (a single voxel) and a grid of more than 2^32 cells (tall)."""
     h = binding.Handle(params_a)
     rng = np.random.default_rng(n + int(leaf * 1000))
     if kind == "gauss":
@@ -886,6 +886,8 @@ def test_device_voxel_grid_bit_exact(params_a, n, leaf, kind):
     elif kind == "dense":  # most points in a handful of voxels
         pts = (rng.standard_normal((n, 4)) * [0.5, 0.5, 0.2, 1]).astype(np.float32)
         pts[: n // 10] *= np.float32(20)
+    elif kind == "tall":
+        pts = tall_cloud(n, rng)
     else:  # a planar wall revisited many times (map-like duplicates)
         base = (rng.random((n // 40, 4)) * [30, 0.05, 5, 1]).astype(np.float32)
         pts = (np.repeat(base, 40, axis=0) + rng.standard_normal((n // 40 * 40, 4)).astype(np.float32) * np.float32(0.01))

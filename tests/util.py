@@ -434,6 +434,19 @@ def pcl_passes(xyz, leaf):
     return dx * dy * dz > INT_MAX
 
 
+def tall_cloud(n, rng):
+    """n points (leaf 1) that pass PCL's INT_MAX rule on a grid of more than 2^32 cells: x and y are 0.9 or 1.1 (d = 1, but two cells), z
+    spans [0, 2^30] on multiples of 128 (d = 2^30 + 1), so divb = (2, 2, 2^30 + 1) and PCL's wrapped u32 voxel ids need all 32 bits"""
+    p = np.empty((n, 4), F32)
+    p[:, 0] = rng.choice(F32([0.9, 1.1]), n)
+    p[:, 1] = rng.choice(F32([0.9, 1.1]), n)
+    p[:, 2] = rng.integers(0, 1 << 23, n).astype(F32) * F32(128)
+    p[:2, 2] = [0, 1 << 30]
+    p[:, 3] = rng.uniform(0, 1, n)
+    assert not pcl_passes(p, 1.0) and np.prod(np.floor(p[:, :3].max(axis=0)).astype(np.int64) - np.floor(p[:, :3].min(axis=0)) + 1) > 2 ** 32
+    return p
+
+
 def voxel_grid_np(pts, leaf):
     """numpy restatement of pcl::VoxelGrid<PointXYZI>::applyFilter: the pass-through rule, then one centroid per voxel in ascending
     idx = i + j dx + k dx dy (stable), each the f32 sum of the voxel's points in input order divided by the count"""
