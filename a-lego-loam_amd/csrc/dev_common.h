@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "../../include/alego_params.h"
+#include "wave.h"
 
 // per-slot integer scalars (DevCtx::scal, stride SC_COUNT)
 enum {
@@ -314,58 +315,5 @@ DEV_INLINE float d_sincosf(float y, int is_cos) {
 }
 DEV_INLINE float d_sinf(float y) { return d_sincosf(y, 0); }
 DEV_INLINE float d_cosf(float y) { return d_sincosf(y, 1); }
-
-// ---------------------------------------------------------------------------
-// wavefront (64 lanes) helpers
-// ---------------------------------------------------------------------------
-DEV_INLINE double wave_sum_f64(double v) {  // fixed butterfly order -> deterministic
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-DEV_INLINE int lane_id() { return threadIdx.x & 63; }
-
-// Wave-wide max / min of a u32 returned as a uniform value: four DPP steps inside each 16-lane row
-// (quad_perm xor1, xor2, row_half_mirror, row_mirror — valid because max/min are idempotent), then the four
-// row results through v_readlane.  ~12 instructions instead of 6 dependent ds_bpermute round trips.
-DEV_INLINE uint32_t wave_max_u32(uint32_t v) {
-  int x = (int)v, t;
-  t = __builtin_amdgcn_update_dpp(x, x, 0xB1, 0xF, 0xF, false); x = (uint32_t)t > (uint32_t)x ? t : x;   // quad_perm [1,0,3,2]
-  t = __builtin_amdgcn_update_dpp(x, x, 0x4E, 0xF, 0xF, false); x = (uint32_t)t > (uint32_t)x ? t : x;   // quad_perm [2,3,0,1]
-  t = __builtin_amdgcn_update_dpp(x, x, 0x141, 0xF, 0xF, false); x = (uint32_t)t > (uint32_t)x ? t : x;  // row_half_mirror
-  t = __builtin_amdgcn_update_dpp(x, x, 0x140, 0xF, 0xF, false); x = (uint32_t)t > (uint32_t)x ? t : x;  // row_mirror
-  const uint32_t a = (uint32_t)__builtin_amdgcn_readlane(x, 0), b = (uint32_t)__builtin_amdgcn_readlane(x, 16);
-  const uint32_t c = (uint32_t)__builtin_amdgcn_readlane(x, 32), e = (uint32_t)__builtin_amdgcn_readlane(x, 48);
-  const uint32_t ab = a > b ? a : b, ce = c > e ? c : e;
-  return ab > ce ? ab : ce;
-}
-DEV_INLINE uint32_t wave_min_u32(uint32_t v) { return ~wave_max_u32(~v); }
-// u64 versions: high word first, then the low word among the lanes that hold the winning high word
-DEV_INLINE unsigned long long wave_max_u64(unsigned long long v) {
-  const uint32_t hi = wave_max_u32((uint32_t)(v >> 32));
-  const uint32_t lo = wave_max_u32((uint32_t)(v >> 32) == hi ? (uint32_t)v : 0u);
-  return ((unsigned long long)hi << 32) | lo;
-}
-DEV_INLINE unsigned long long wave_min_u64(unsigned long long v) {
-  const uint32_t hi = wave_min_u32((uint32_t)(v >> 32));
-  const uint32_t lo = wave_min_u32((uint32_t)(v >> 32) == hi ? (uint32_t)v : 0xFFFFFFFFu);
-  return ((unsigned long long)hi << 32) | lo;
-}
-
-// 16-lane (one DPP row) versions: every lane of the row gets the result; no cross-row traffic at all
-DEV_INLINE uint32_t row16_max_u32(uint32_t v) {
-  int x = (int)v, t;
-  t = __builtin_amdgcn_update_dpp(x, x, 0xB1, 0xF, 0xF, false); x = (uint32_t)t > (uint32_t)x ? t : x;
-  t = __builtin_amdgcn_update_dpp(x, x, 0x4E, 0xF, 0xF, false); x = (uint32_t)t > (uint32_t)x ? t : x;
-  t = __builtin_amdgcn_update_dpp(x, x, 0x141, 0xF, 0xF, false); x = (uint32_t)t > (uint32_t)x ? t : x;
-  t = __builtin_amdgcn_update_dpp(x, x, 0x140, 0xF, 0xF, false); x = (uint32_t)t > (uint32_t)x ? t : x;
-  return (uint32_t)x;
-}
-DEV_INLINE uint32_t row16_min_u32(uint32_t v) { return ~row16_max_u32(~v); }
-DEV_INLINE unsigned long long row16_min_u64(unsigned long long v) {
-  const uint32_t hi = row16_min_u32((uint32_t)(v >> 32));
-  const uint32_t lo = row16_min_u32((uint32_t)(v >> 32) == hi ? (uint32_t)v : 0xFFFFFFFFu);
-  return ((unsigned long long)hi << 32) | lo;
-}
 
 #endif

@@ -353,23 +353,23 @@ __global__ void __launch_bounds__(64) fe_pick4(DevCtx d) {
 #pragma unroll
       for (int t = 0; t < FE_T; ++t) if (((sharp_m >> t) & 1) && key[t] >= bk) { bk = key[t]; bt = t; }
       if (!act) bk = 0;
-      const uint32_t kmax = row16_max_u32(bk);
+      const uint32_t kmax = group_max_u32<16>(bk);
       act = act && kmax != 0;
       if (!__any(act)) break;
-      int c = (int)row16_max_u32(bk == kmax ? (uint32_t)(lsp + gl + 16 * bt) : 0u);   // ties -> larger index
+      int c = (int)group_max_u32<16>(bk == kmax ? (uint32_t)(lsp + gl + 16 * bt) : 0u);   // ties -> larger index
       if constexpr (STDSORT) {
         int cnt = 0;
 #pragma unroll
         for (int t = 0; t < FE_T; ++t) cnt += (((sharp_m >> t) & 1) && key[t] == kmax) ? 1 : 0;
         if (!act) cnt = 0;
-        const bool tied = row16_max_u32((uint32_t)cnt) > 1u || __popc((unsigned)(__ballot(cnt > 0) >> (16 * g)) & 0xffffu) > 1;
+        const bool tied = group_max_u32<16>((uint32_t)cnt) > 1u || __popc((unsigned)(__ballot(cnt > 0) >> (16 * g)) & 0xffffu) > 1;
         if (__any(tied)) {
           ring_arrangements(tied);
           uint32_t best = 0;   // k = ep .. sp: of the tied candidates the one std::sort placed last comes first
 #pragma unroll
           for (int t = 0; t < FE_T; ++t)
             if (((sharp_m >> t) & 1) && key[t] == kmax) best = max(best, (((uint32_t)s_pos[g][gl + 16 * t] + 1u) << 16) | (uint32_t)(gl + 16 * t));
-          const int ca = lsp + (int)(row16_max_u32(tied ? best : 0u) & 0xFFFFu);
+          const int ca = lsp + (int)(group_max_u32<16>(tied ? best : 0u) & 0xFFFFu);
           c = tied ? ca : c;
         }
       }
@@ -396,23 +396,23 @@ __global__ void __launch_bounds__(64) fe_pick4(DevCtx d) {
 #pragma unroll
       for (int t = 0; t < FE_T; ++t) if (((flat_m >> t) & 1) && key[t] < bk) { bk = key[t]; bt = t; }
       if (!act) bk = 0xFFFFFFFFu;
-      const uint32_t kmin = row16_min_u32(bk);
+      const uint32_t kmin = group_min_u32<16>(bk);
       act = act && kmin != 0xFFFFFFFFu;
       if (!__any(act)) break;
-      int c = (int)row16_min_u32(bk == kmin ? (uint32_t)(lsp + gl + 16 * bt) : 0xFFFFFFFFu);   // ties -> smaller index
+      int c = (int)group_min_u32<16>(bk == kmin ? (uint32_t)(lsp + gl + 16 * bt) : 0xFFFFFFFFu);   // ties -> smaller index
       if constexpr (STDSORT) {
         int cnt = 0;
 #pragma unroll
         for (int t = 0; t < FE_T; ++t) cnt += (((flat_m >> t) & 1) && key[t] == kmin) ? 1 : 0;
         if (!act) cnt = 0;
-        const bool tied = row16_max_u32((uint32_t)cnt) > 1u || __popc((unsigned)(__ballot(cnt > 0) >> (16 * g)) & 0xffffu) > 1;
+        const bool tied = group_max_u32<16>((uint32_t)cnt) > 1u || __popc((unsigned)(__ballot(cnt > 0) >> (16 * g)) & 0xffffu) > 1;
         if (__any(tied)) {
           ring_arrangements(tied);
           uint32_t best = 0xFFFFFFFFu;   // k = sp .. ep: the tied candidate std::sort placed first
 #pragma unroll
           for (int t = 0; t < FE_T; ++t)
             if (((flat_m >> t) & 1) && key[t] == kmin) best = min(best, ((uint32_t)s_pos[g][gl + 16 * t] << 16) | (uint32_t)(gl + 16 * t));
-          const int ca = lsp + (int)(row16_min_u32(tied ? best : 0xFFFFFFFFu) & 0xFFFFu);
+          const int ca = lsp + (int)(group_min_u32<16>(tied ? best : 0xFFFFFFFFu) & 0xFFFFu);
           c = tied ? ca : c;
         }
       }
@@ -542,7 +542,7 @@ __global__ void __launch_bounds__(FV_BLOCK) fe_voxel(DevCtx d) {
   }
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    vgr_wave_minmax(mn[a], mx[a]);
+    bfly_minmax_f32(mn[a], mx[a]);
     if ((tid & 63) == 0) { s_red[a][tid >> 6] = mn[a]; s_red[3 + a][tid >> 6] = mx[a]; }
   }
   __syncthreads();
@@ -602,9 +602,7 @@ __global__ void __launch_bounds__(FV_BLOCK) fe_voxel(DevCtx d) {
       int v[PER], sum = 0;
 #pragma unroll
       for (int k = 0; k < PER; ++k) { const int b = tid * PER + k; v[k] = b < nb ? s_boff[b + 1] : 0; sum += v[k]; }
-      int incl = sum;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o, 64); if ((tid & 63) >= o) incl += t; }
+      const int incl = wave_incl_scan(sum);
       if ((tid & 63) == 63) s_scan[tid >> 6] = incl;
       __syncthreads();
       int run = incl - sum;
@@ -669,7 +667,7 @@ __global__ void __launch_bounds__(FV_BLOCK) fe_voxel(DevCtx d) {
 // 32 consecutive threads hold the 32 points of a box.
 #define FC_T 512
 __global__ void __launch_bounds__(FC_T) fe_collect(DevCtx d) {
-  const int slot = blockIdx.x + d.slot0, tid = threadIdx.x, lane = tid & 63;
+  const int slot = blockIdx.x + d.slot0, tid = threadIdx.x;
   const int cur = cur_in_flight(d, slot);
   const size_t base = (size_t)slot * d.N;
   const int NS = d.NS;
@@ -682,16 +680,12 @@ __global__ void __launch_bounds__(FC_T) fe_collect(DevCtx d) {
     c[2] = r < NS ? allc[r * 8 + 2] : 0; c[3] = r < NS ? allc[r * 8 + 4] : 0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      int incl = c[k];
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
+      const int incl = wave_incl_scan(c[k]);
       s_off[k][r] = incl - c[k];
       if (r == 63) s_off[k][64] = incl;
       if (k == 1 || k == 3) {
         const int nb = (c[k] + LO_CH - 1) / LO_CH;
-        int bi = nb;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(bi, o, 64); if (lane >= o) bi += t; }
+        const int bi = wave_incl_scan(nb);
         s_boff[k == 1 ? 0 : 1][r] = bi - nb;
         if (r == 63) s_boff[k == 1 ? 0 : 1][64] = bi;
       }
@@ -755,8 +749,7 @@ __global__ void __launch_bounds__(FC_T) fe_collect(DevCtx d) {
         if (v) { mn[0] = mx[0] = p.x; mn[1] = mx[1] = p.y; mn[2] = mx[2] = p.z; }
 #pragma unroll
         for (int a = 0; a < 3; ++a)
-#pragma unroll
-          for (int o = LO_CH / 2; o > 0; o >>= 1) { mn[a] = fminf(mn[a], __shfl_xor(mn[a], o, 64)); mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], o, 64)); }
+          bfly_minmax_f32<LO_CH>(mn[a], mx[a]);
         if ((tid % LO_CH) == 0 && v) {   // (thread 0 of a box holds its first point: every box has one)
           const int len = min(LO_CH, s_off[k][r + 1] - i);
           bx[2 * bxi] = make_float4(mn[0], mn[1], mn[2], __int_as_float(i));

@@ -49,17 +49,6 @@ __host__ __device__ inline FfLayout ff_layout(int sector_cap) {
   return L;
 }
 
-// max over the 64 / FF_G lanes of a ring group (quad_perm xor 1, xor 2, row_half_mirror; row_mirror for 16 lanes), result in every lane of the group
-DEV_INLINE uint32_t grp8_max_u32(uint32_t v) {
-  int x = (int)v, t;
-  t = __builtin_amdgcn_update_dpp(x, x, 0xB1, 0xF, 0xF, false); x = (uint32_t)t > (uint32_t)x ? t : x;
-  t = __builtin_amdgcn_update_dpp(x, x, 0x4E, 0xF, 0xF, false); x = (uint32_t)t > (uint32_t)x ? t : x;
-  t = __builtin_amdgcn_update_dpp(x, x, 0x141, 0xF, 0xF, false); x = (uint32_t)t > (uint32_t)x ? t : x;
-#if FF_G == 4   // 16 lanes per ring: one more step (row_mirror) = row16_max_u32
-  t = __builtin_amdgcn_update_dpp(x, x, 0x140, 0xF, 0xF, false); x = (uint32_t)t > (uint32_t)x ? t : x;
-#endif
-  return (uint32_t)x;
-}
 // bits [pos, pos + 64) of the 128-bit value hi:lo
 DEV_INLINE unsigned long long ext128(unsigned long long lo, unsigned long long hi, int pos) { return (lo >> pos) | (pos ? hi << (64 - pos) : 0ull); }
 
@@ -258,10 +247,10 @@ DEV_INLINE void ff_pick_regs(const alego_params& P, FfPick& R, int ncand, const 
       bk = take ? key[t] : bk; bp = take ? pay[t] : bp;
     }
     if (!act) bk = 0u;
-    const uint32_t kmax = grp8_max_u32(bk);
+    const uint32_t kmax = group_max_u32<64 / FF_G>(bk);
     act = act && kmax != 0u;
     if (!__any(act)) break;
-    uint32_t pm = grp8_max_u32(bk == kmax ? bp : 0u);
+    uint32_t pm = group_max_u32<64 / FF_G>(bk == kmax ? bp : 0u);
     if (FLAT) pm = ~pm;
     const int c = (int)(pm >> 6), rf = (int)((pm >> 3) & 7u), rb = (int)(pm & 7u);
     picked += act ? 1 : 0;
@@ -302,10 +291,10 @@ DEV_INLINE void ff_pick_mem(const alego_params& P, FfPick& R, int ncand, int nwa
         bk = take ? e.x : bk; bp = take ? e.y : bp;
       }
     }
-    const uint32_t kmax = grp8_max_u32(bk);
+    const uint32_t kmax = group_max_u32<64 / FF_G>(bk);
     act = act && kmax != 0u;
     if (!__any(act)) break;
-    uint32_t pm = grp8_max_u32(bk == kmax ? bp : 0u);
+    uint32_t pm = group_max_u32<64 / FF_G>(bk == kmax ? bp : 0u);
     if (FLAT) pm = ~pm;
     const int c = (int)(pm >> 6), rf = (int)((pm >> 3) & 7u), rb = (int)(pm & 7u);
     picked += act ? 1 : 0;
@@ -414,25 +403,6 @@ __host__ __device__ inline FoLayout fo_layout(int H) {
 }
 static size_t fo_lds_bytes(int H) { const FoLayout L = fo_layout(H); return std::max((size_t)(L.keyed ? 14 : 12) * H + (size_t)16 * L.cap, (size_t)6 * 65 * 4); }
 
-// reductions over the 64 lanes by DPP (quad, half row, row, then the row results passed on: row_bcast15 / row_bcast31): the result is in lane 63
-#define FO_DPP_F(x, ctrl, rmask) __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(x), __float_as_int(x), ctrl, rmask, 0xF, false))
-DEV_INLINE float wave_min_f32(float x) {
-  x = fminf(x, FO_DPP_F(x, 0xB1, 0xF)); x = fminf(x, FO_DPP_F(x, 0x4E, 0xF)); x = fminf(x, FO_DPP_F(x, 0x141, 0xF)); x = fminf(x, FO_DPP_F(x, 0x140, 0xF));
-  x = fminf(x, FO_DPP_F(x, 0x142, 0xA)); x = fminf(x, FO_DPP_F(x, 0x143, 0xC));
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 63));
-}
-DEV_INLINE float wave_max_f32(float x) {
-  x = fmaxf(x, FO_DPP_F(x, 0xB1, 0xF)); x = fmaxf(x, FO_DPP_F(x, 0x4E, 0xF)); x = fmaxf(x, FO_DPP_F(x, 0x141, 0xF)); x = fmaxf(x, FO_DPP_F(x, 0x140, 0xF));
-  x = fmaxf(x, FO_DPP_F(x, 0x142, 0xA)); x = fmaxf(x, FO_DPP_F(x, 0x143, 0xC));
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 63));
-}
-DEV_INLINE int wave_sum_i32(int x) {   // (a disabled row keeps `old` = 0: nothing added)
-  x += __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, false); x += __builtin_amdgcn_update_dpp(0, x, 0x4E, 0xF, 0xF, false);
-  x += __builtin_amdgcn_update_dpp(0, x, 0x141, 0xF, 0xF, false); x += __builtin_amdgcn_update_dpp(0, x, 0x140, 0xF, 0xF, false);
-  x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xA, 0xF, false); x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xC, 0xF, false);
-  return __builtin_amdgcn_readlane(x, 63);
-}
-
 // a * b + c on the low 24 bits of a and b, at full rate (a 32-bit multiply takes four times as long; written out because the compiler turns __umul24 of
 // values it cannot bound back into mask + 32-bit multiply)
 DEV_INLINE uint32_t mad_u24(uint32_t a, uint32_t b, uint32_t c) { uint32_t r; asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
@@ -458,7 +428,7 @@ extern "C" void alego_fo_times(long long* out) { (void)hipMemcpyFromSymbol(out, 
 // the workgroup of row NS: the stream's sharp / less_sharp / flat clouds (ring-ascending concatenation of the picks, :199-205,:245), their
 // index lists, the less_sharp ring offsets and bounding boxes (everything fe_pickc counted; no ring has to wait for this)
 DEV_INLINE void fo_picks_out(const DevCtx& d, int slot, unsigned char* smem) {
-  const int tid = threadIdx.x, lane = tid & 63, NS = d.NS;
+  const int tid = threadIdx.x, NS = d.NS;
   const size_t base = (size_t)slot * d.N;
   const size_t fb = (size_t)slot * 2 + cur_in_flight(d, slot);
   const int* allc = d.st_cnt + (size_t)slot * NS * 8;
@@ -471,9 +441,7 @@ DEV_INLINE void fo_picks_out(const DevCtx& d, int slot, unsigned char* smem) {
     c[3] = (c[1] + LO_CH - 1) / LO_CH;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      int incl = c[k];
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
+      const int incl = wave_incl_scan(c[k]);
       s_off[k][r] = incl - c[k];
       if (r == 63) s_off[k][64] = incl;
     }
@@ -518,8 +486,7 @@ DEV_INLINE void fo_picks_out(const DevCtx& d, int slot, unsigned char* smem) {
         if (v) { mn[0] = mx[0] = p.x; mn[1] = mx[1] = p.y; mn[2] = mx[2] = p.z; }
 #pragma unroll
         for (int a = 0; a < 3; ++a)
-#pragma unroll
-          for (int o = LO_CH / 2; o > 0; o >>= 1) { mn[a] = fminf(mn[a], __shfl_xor(mn[a], o, 64)); mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], o, 64)); }
+          bfly_minmax_f32<LO_CH>(mn[a], mx[a]);
         if ((tid % LO_CH) == 0 && v) {   // (thread 0 of a box holds its first pick: every box has one)
           bx[2 * bxi] = make_float4(mn[0], mn[1], mn[2], __int_as_float(i));
           bx[2 * bxi + 1] = make_float4(mx[0], mx[1], mx[2], __int_as_float(min(LO_CH, s_off[k][r + 1] - i)));
@@ -595,13 +562,6 @@ __global__ void __launch_bounds__(FO_BLOCK) fe_ring_out(DevCtx d) {
   constexpr int NW = FO_BLOCK / 64;
   const int wv = tid >> 6;
   const unsigned long long lt = (1ull << lane) - 1ull;
-  auto scan64 = [&](int cnt, int* total) -> int {   // exclusive prefix of one value per lane over the wavefront
-    int incl = cnt;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
-    *total = __builtin_amdgcn_readlane(incl, 63);
-    return incl - cnt;
-  };
   if (tid < 64) s_rc[tid] = 0;
   FO_TICK(0);
   // the ring's first FO_U x FO_BLOCK points are fetched now, in front of the bitmap's own round trip (the pick list), and stay in registers for the
@@ -744,7 +704,7 @@ __global__ void __launch_bounds__(FO_BLOCK) fe_ring_out(DevCtx d) {
     __syncthreads();
     {
       const int p0 = lane * 64;   // (count `lane` belongs to the 64 positions from p0)
-      const int ex = scan64(s_rc[lane] + ((p0 < n_all && (p0 == 0 || s_key[p0] != s_key[p0 - 1])) ? 1 : 0), &nruns);
+      const int ex = wave_excl_scan(s_rc[lane] + ((p0 < n_all && (p0 == 0 || s_key[p0] != s_key[p0 - 1])) ? 1 : 0), &nruns);
 #pragma nounroll
       for (int c = 0; c * FO_BLOCK < n_all; ++c) {
         const int i = c * FO_BLOCK + tid;
@@ -783,9 +743,7 @@ __global__ void __launch_bounds__(FO_BLOCK) fe_ring_out(DevCtx d) {
         int v[PER], sum = 0;
 #pragma unroll
         for (int k = 0; k < PER; ++k) { const int b = tid * PER + k; v[k] = b < nb ? s_boff[b + 1] : 0; sum += v[k]; }
-        int incl = sum;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
+        const int incl = wave_incl_scan(sum);
         if (lane == 63) s_scan[tid >> 6] = incl;
         __syncthreads();
         int run = incl - sum;
@@ -858,7 +816,7 @@ __global__ void __launch_bounds__(FO_BLOCK) fe_ring_out(DevCtx d) {
       if (lane == 0) s_rc[c * NW + wv] = (int)__popcll(m);
     }
     __syncthreads();
-    vex = scan64(s_rc[lane], &nout);
+    vex = wave_excl_scan(s_rc[lane], &nout);
   }
   FO_TICK(5);
   // ---- the ring's less_flat offset: its count for the rings above, the counts of the rings below
@@ -878,8 +836,7 @@ __global__ void __launch_bounds__(FO_BLOCK) fe_ring_out(DevCtx d) {
       c = bad ? 0 : (int)(v & 0xFFFFu);   // (a count that never came counts as 0: every offset below only shrinks, so whatever this ring still writes stays inside the slot's arrays)
       nbx = (c + LO_CH - 1) / LO_CH;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { c += __shfl_xor(c, o, 64); nbx += __shfl_xor(nbx, o, 64); bad += __shfl_xor(bad, o, 64); }
+    c = bfly_sum_i32(c); nbx = bfly_sum_i32(nbx); bad = bfly_sum_i32(bad);
     if (lane == 0) { s_look[0] = c; s_look[1] = nbx; s_look[2] = bad; }
   }
   const int nbox = (nout + LO_CH - 1) / LO_CH;

@@ -77,30 +77,6 @@ void launch_map_archive(const DevCtx& d, const LmCtx& L, int force, hipStream_t 
 }
 
 // ---- assembly -----------------------------------------------------------------------------------------------------
-DEV_INLINE int wave_incl(int v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(v, o, 64); if (lane >= o) v += t; }
-  return v;
-}
-// exclusive prefix of v over the workgroup (blockDim.x multiple of 64, <= 1024); *total = the workgroup's sum
-DEV_INLINE int block_excl(int v, int* s_w, int* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  const int incl = wave_incl(v, lane);
-  if (lane == 63) s_w[wave] = incl;
-  __syncthreads();
-  if (wave == 0) {
-    const int w = lane < nw ? s_w[lane] : 0;
-    const int wi = wave_incl(w, lane);
-    if (lane < nw) s_w[lane] = wi - w;
-    if (lane == 63) s_w[16] = wi;
-  }
-  __syncthreads();
-  const int r = incl - v + s_w[wave];
-  *total = s_w[16];
-  __syncthreads();   // s_w is reused by the next call
-  return r;
-}
-
 DEV_INLINE int sel_count(const int* tab, int kinds) {
   return ((kinds & 2) ? tab[1] : 0) + ((kinds & 1) ? tab[2] : 0) + ((kinds & 4) ? tab[3] : 0);
 }
@@ -114,7 +90,7 @@ __global__ void __launch_bounds__(GS_T) map_offsets(LmCtx L, int slot, int nf, i
     const int f = f0 + threadIdx.x;
     const int v = f < nf ? sel_count(tab + (size_t)f * 4, kinds) : 0;
     int tot;
-    const int ex = block_excl(v, s_w, &tot);
+    const int ex = block_excl_scan<GS_T / 64>(v, s_w, &tot);
     if (f < nf) off[f] = carry + ex;
     carry += tot;
   }
@@ -154,7 +130,7 @@ __global__ void __launch_bounds__(GS_T) gs_block(int* a, int n, int* bs) {
 #pragma unroll
   for (int k = 0; k < GS_PER; ++k) { v[k] = base + k < (size_t)n ? a[base + k] : 0; s += v[k]; }
   int tot;
-  int run = block_excl(s, s_w, &tot);
+  int run = block_excl_scan<GS_T / 64>(s, s_w, &tot);
 #pragma unroll
   for (int k = 0; k < GS_PER; ++k) { if (base + k < (size_t)n) a[base + k] = run; run += v[k]; }
   if (threadIdx.x == 0) bs[blockIdx.x] = tot;
@@ -167,7 +143,7 @@ __global__ void __launch_bounds__(GS_T) gs_top(int* bs, int nb) {
     const int b = b0 + threadIdx.x;
     const int v = b < nb ? bs[b] : 0;
     int tot;
-    const int ex = block_excl(v, s_w, &tot);
+    const int ex = block_excl_scan<GS_T / 64>(v, s_w, &tot);
     if (b < nb) bs[b] = carry + ex;
     carry += tot;
   }
@@ -193,7 +169,7 @@ __global__ void __launch_bounds__(GV_T) gv_bbox(const float4* in, int n, unsigne
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    vgr_wave_minmax(mn[a], mx[a]);
+    bfly_minmax_f32(mn[a], mx[a]);
     if (lane == 0) { s_r[a][wave] = mn[a]; s_r[3 + a][wave] = mx[a]; }
   }
   __syncthreads();

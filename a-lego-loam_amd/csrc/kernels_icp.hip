@@ -91,7 +91,7 @@ __global__ void __launch_bounds__(ICP_T) icp_corr(IcpState* S, float4* cur, cons
     v[15] = (double)d2; v[16] = 1.0;
   }
 #pragma unroll
-  for (int k = 0; k < 17; ++k) v[k] = wave_sum_f64(v[k]);
+  for (int k = 0; k < 17; ++k) v[k] = bfly_sum_f64(v[k]);
   if (lane_id() == 0) for (int k = 0; k < 17; ++k) s_red[threadIdx.x >> 6][k] = v[k];
   __syncthreads();
   if (threadIdx.x < 17) {
@@ -121,7 +121,7 @@ __global__ void __launch_bounds__(ICP_T) icp_fitness(const IcpState* S, const fl
   int idx;
   icp_nn(p, tgt, n_tgt, s_tile, &d2, &idx);
   double s = (i < n_src && idx >= 0) ? (double)d2 : 0.0, c = (i < n_src && idx >= 0) ? 1.0 : 0.0;
-  s = wave_sum_f64(s); c = wave_sum_f64(c);
+  s = bfly_sum_f64(s); c = bfly_sum_f64(c);
   if (lane_id() == 0) { s_red[threadIdx.x >> 6][0] = s; s_red[threadIdx.x >> 6][1] = c; }
   __syncthreads();
   if (threadIdx.x < 2) { double t = 0; for (int w = 0; w < ICP_T / 64; ++w) t += s_red[w][threadIdx.x]; partial[(size_t)blockIdx.x * 18 + threadIdx.x] = t; }

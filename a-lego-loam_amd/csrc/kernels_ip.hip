@@ -81,12 +81,7 @@ __global__ void __launch_bounds__(IP_BLOCK) ip_project(DevCtx d, int ring_pos) {
     if (cell >= 0) atomicMax(&d.owner[(size_t)slot * d.N + cell], IP_OWNER_TAG | i);
   }
   // first / last valid point for the orientation block (:62-63): one atomic per wavefront
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    vmin = min(vmin, __shfl_xor(vmin, o, 64));
-    vmax = max(vmax, __shfl_xor(vmax, o, 64));
-    nvalid += __shfl_xor(nvalid, o, 64);
-  }
+  vmin = bfly_min_i32(vmin); vmax = bfly_max_i32(vmax); nvalid = bfly_sum_i32(nvalid);
   if (lane_id() == 0 && nvalid) {
     int* sc = d.scal + slot * SC_COUNT;
     atomicMin(&sc[SC_FIRST], vmin);
@@ -425,11 +420,8 @@ __global__ void __launch_bounds__(CC_LDS_THREADS) cc_lds(DevCtx d, int ring_pos,
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
       v3[a] = e < PER * NW ? s_cnt[a][e] : 0;
-      int incl = v3[a];
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
-      in3[a] = incl;
-      if (lane == 63) s_wtot[a][wave] = incl;
+      in3[a] = wave_incl_scan(v3[a]);
+      if (lane == 63) s_wtot[a][wave] = in3[a];
     }
     __syncthreads();
 #pragma unroll
@@ -730,11 +722,8 @@ __global__ void __attribute__((amdgpu_waves_per_eu(8, 8))) __launch_bounds__(CC_
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
       v3[a] = e < per * NW ? s_cnt[a][e] : 0;
-      int incl = v3[a];
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
-      in3[a] = incl;
-      if (lane == 63) s_wtot[a][wave] = incl;
+      in3[a] = wave_incl_scan(v3[a]);
+      if (lane == 63) s_wtot[a][wave] = in3[a];
     }
     __syncthreads();
 #pragma unroll
@@ -876,8 +865,7 @@ __global__ void __launch_bounds__(IP_BLOCK) ip_rowcount(DevCtx d) {
     d.flag_img[base + v] = (uint8_t)((d.flag_img[base + v] & 0x0F) | (c << 4) | (fr ? 0x40 : 0));
   }
   __shared__ int s[3][IP_BLOCK / 64];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { nk += __shfl_xor(nk, o, 64); no += __shfl_xor(no, o, 64); nf += __shfl_xor(nf, o, 64); }
+  nk = bfly_sum_i32(nk); no = bfly_sum_i32(no); nf = bfly_sum_i32(nf);
   if (lane_id() == 0) { s[0][threadIdx.x >> 6] = nk; s[1][threadIdx.x >> 6] = no; s[2][threadIdx.x >> 6] = nf; }
   __syncthreads();
   if (threadIdx.x < 3) {
@@ -901,11 +889,8 @@ __global__ void __launch_bounds__(IP_BLOCK) ip_compact(DevCtx d, int ring_pos) {
     int k = r < d.NS ? rc[r * 4 + 0] : 0, o = r < d.NS ? rc[r * 4 + 1] : 0, f = r < d.NS ? rc[r * 4 + 2] : 0;
     int pk = (r < row) ? k : 0, po = (r < row) ? o : 0, pf = (r < row) ? f : 0;
     int tk = k, to = o, tf = f;
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) {
-      pk += __shfl_xor(pk, s, 64); po += __shfl_xor(po, s, 64); pf += __shfl_xor(pf, s, 64);
-      tk += __shfl_xor(tk, s, 64); to += __shfl_xor(to, s, 64); tf += __shfl_xor(tf, s, 64);
-    }
+    pk = bfly_sum_i32(pk); po = bfly_sum_i32(po); pf = bfly_sum_i32(pf);
+    tk = bfly_sum_i32(tk); to = bfly_sum_i32(to); tf = bfly_sum_i32(tf);
     if (threadIdx.x == 0) {
       s_off[0] = pk; s_off[1] = po; s_off[2] = pf;
       const int mykeep = rc[row * 4 + 0];

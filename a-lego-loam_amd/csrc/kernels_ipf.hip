@@ -134,12 +134,7 @@ __global__ void __launch_bounds__(IPF2_T) ip_fused(DevCtx d, int ring_pos, int k
     }
   }
   IPF_TICK(1);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    vmin = min(vmin, __shfl_xor(vmin, o, 64));
-    vmax = max(vmax, __shfl_xor(vmax, o, 64));
-    nvalid += __shfl_xor(nvalid, o, 64);
-  }
+  vmin = bfly_min_i32(vmin); vmax = bfly_max_i32(vmax); nvalid = bfly_sum_i32(nvalid);
   if (lane == 0) { S.red[0][wave] = vmin; S.red[1][wave] = vmax; S.red[2][wave] = nvalid; }
   __syncthreads();
   if (tid == IPF2_T - 1) {   // orientation block (:62-72): two dependent loads + two atan2f by ONE thread — the last one, whose wavefront has no columns
@@ -367,11 +362,8 @@ __global__ void __launch_bounds__(IPF2_T) ip_fused(DevCtx d, int ring_pos, int k
 #pragma unroll
       for (int a = 0; a < 3; ++a) {
         v3[a] = S.cnt[a][tid];
-        int incl = v3[a];
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
-        in3[a] = incl;
-        if (lane == 63) S.wtot[a][wave] = incl;
+        in3[a] = wave_incl_scan(v3[a]);
+        if (lane == 63) S.wtot[a][wave] = in3[a];
       }
     }
     __syncthreads();
@@ -676,12 +668,7 @@ __global__ void __launch_bounds__(T, IPH_MINW) ip_fused_t(DevCtx d, int ring_pos
         if (c2 >= 0) iph_max16(own16w, c2, (unsigned)(i + 1));
       }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      vmin = min(vmin, __shfl_xor(vmin, o, 64));
-      vmax = max(vmax, __shfl_xor(vmax, o, 64));
-      nvalid += __shfl_xor(nvalid, o, 64);
-    }
+    vmin = bfly_min_i32(vmin); vmax = bfly_max_i32(vmax); nvalid = bfly_sum_i32(nvalid);
     if (lane == 0) { S.red[0][wave] = vmin; S.red[1][wave] = vmax; S.red[2][wave] = nvalid; }
   }
   __syncthreads();
@@ -1005,11 +992,8 @@ __global__ void __launch_bounds__(T, IPH_MINW) ip_fused_t(DevCtx d, int ring_pos
 #pragma unroll
       for (int a = 0; a < 3; ++a) {
         v3[a] = S.u.cnt[a][tid];
-        int incl = v3[a];
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
-        in3[a] = incl;
-        if (lane == 63) S.wtot[a][wave] = incl;
+        in3[a] = wave_incl_scan(v3[a]);
+        if (lane == 63) S.wtot[a][wave] = in3[a];
       }
     }
     __syncthreads();

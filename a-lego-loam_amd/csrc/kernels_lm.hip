@@ -246,19 +246,12 @@ __global__ void __launch_bounds__(LM_BLOCK) lm_grid_build(DevCtx d, LmCtx L) {
     const int c = c0 + threadIdx.x;
     // (the counts were accumulated by L2 atomics: read them past the CU's vector cache)
     const int v = __hip_atomic_load(&cs[min(c, ncell)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) * (c < ncell ? 1 : 0);
-    int incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o, 64); if ((threadIdx.x & 63) >= o) incl += t; }
-    if ((threadIdx.x & 63) == 63) s[threadIdx.x >> 6] = incl;
-    __syncthreads();
-    int woff = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < LM_BLOCK / 64; ++w) { if (w < (int)(threadIdx.x >> 6)) woff += s[w]; tot += s[w]; }
+    int tot;
+    const int ex = block_excl_scan<LM_BLOCK / 64>(v, s, &tot);
     const int run = s_run;
-    if (c <= ncell) { const int e2 = run + woff + incl - v; cs[c] = e2; cc[c] = e2; }
+    if (c <= ncell) { const int e2 = run + ex; cs[c] = e2; cc[c] = e2; }
     __syncthreads();
-    if (threadIdx.x == 0) s_run = run + tot;
-    __syncthreads();
+    if (threadIdx.x == 0) s_run = run + tot;   // (read after the next call's barriers)
   }
   __threadfence_block();
   __syncthreads();
@@ -432,24 +425,10 @@ DEV_INLINE void d_colpiv_qr53(double A[3][5], const double b[5], double x[3]) {
   }
 }
 
-// minimum of a u64 over a group of LM_KNN_LANES consecutive lanes (high word, then low word among the winners): every
-// lane of the group gets it.  DPP quad_perm xor 1, xor 2, row_half_mirror cover 8 lanes; row_mirror extends to 16.
+// lanes per query of lm_knn: its private sets are merged by group_min_u64<LM_KNN_LANES> (wave.h)
 #ifndef LM_KNN_LANES
 #define LM_KNN_LANES 4   // measured at 1024 streams: 16 lanes 1008 us, 8: 689, 4: 581, 2: 662, 1: 1176
 #endif
-DEV_INLINE uint32_t row_max_u32(uint32_t v) {
-  int x = (int)v, t;
-  if (LM_KNN_LANES >= 2) { t = __builtin_amdgcn_update_dpp(x, x, 0xB1, 0xF, 0xF, false); x = (uint32_t)t > (uint32_t)x ? t : x; }
-  if (LM_KNN_LANES >= 4) { t = __builtin_amdgcn_update_dpp(x, x, 0x4E, 0xF, 0xF, false); x = (uint32_t)t > (uint32_t)x ? t : x; }
-  if (LM_KNN_LANES >= 8) { t = __builtin_amdgcn_update_dpp(x, x, 0x141, 0xF, 0xF, false); x = (uint32_t)t > (uint32_t)x ? t : x; }
-  if (LM_KNN_LANES == 16) { t = __builtin_amdgcn_update_dpp(x, x, 0x140, 0xF, 0xF, false); x = (uint32_t)t > (uint32_t)x ? t : x; }
-  return (uint32_t)x;
-}
-DEV_INLINE unsigned long long row_min_u64(unsigned long long v) {
-  const uint32_t hi = ~row_max_u32(~(uint32_t)(v >> 32));
-  const uint32_t lo = ~row_max_u32(~((uint32_t)(v >> 32) == hi ? (uint32_t)v : 0xFFFFFFFFu));
-  return ((unsigned long long)hi << 32) | lo;
-}
 
 // The queries [qlo, qhi) of `kind` that this rank registers: all of them, or — one registration sharded over the ranks of a communicator
 // (alego_dist_init) — this rank's contiguous slice of laser_corner_ds_ ++ laser_surf_total_ds_.
@@ -600,7 +579,7 @@ __global__ void __launch_bounds__(128) lm_knn(DevCtx d, LmCtx L) {
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
       const u64k m01 = k0 < k1 ? k0 : k1, m23 = k2 < k3 ? k2 : k3, m03 = m01 < m23 ? m01 : m23, mine = m03 < k4 ? m03 : k4;
-      const u64k m = row_min_u64(mine);
+      const u64k m = group_min_u64<LM_KNN_LANES>(mine);
       bd[k] = d_i2f((int32_t)(m >> 32)); bi[k] = (int)(uint32_t)m;   // (KNONE: distance bits 0xFFFFFFFF = NaN, index 0xFFFFFFFF — see `ok` below)
       if (mine == m && m != KNONE) {   // keys are unique (one per map point): exactly one lane of the group, exactly one of its entries
         k0 = k0 == m ? KNONE : k0; k1 = k1 == m ? KNONE : k1; k2 = k2 == m ? KNONE : k2; k3 = k3 == m ? KNONE : k3; k4 = k4 == m ? KNONE : k4;
@@ -743,9 +722,7 @@ DEV_INLINE void lm_pack_rows(const LmCtx& L, int slot, int nqc, int nqs, unsigne
 #pragma unroll
     for (int u = 0; u < U; ++u) if (i0 + u < hi && ty[u] != 0.0) { if (i0 + u < nqc) ++cc; else ++cs; }
   }
-  int ic = cc, is = cs;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const int tc = __shfl_up(ic, o, 64), ts = __shfl_up(is, o, 64); if (lane >= o) { ic += tc; is += ts; } }
+  const int ic = wave_incl_scan(cc), is = wave_incl_scan(cs);
   if (lane == 63) { s_cnt[0][wave] = ic; s_cnt[1][wave] = is; }
   __syncthreads();
   int epos = ic - cc, ppos = is - cs, Rc = 0, Rs = 0;

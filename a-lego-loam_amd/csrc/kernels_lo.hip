@@ -85,9 +85,9 @@ DEV_INLINE WalkBest walk_reduce(WalkBest b) {
 #endif
 DEV_INLINE WalkBest walk_reduce_row(WalkBest b) {
   const unsigned long long bits = (unsigned long long)__double_as_longlong(b.dist);
-  const unsigned long long mn = row16_min_u64(bits);
-  const uint32_t rk = row16_min_u32(bits == mn ? (uint32_t)b.rank : 0xFFFFFFFFu);
-  const uint32_t ix = row16_min_u32((bits == mn && (uint32_t)b.rank == rk) ? (uint32_t)b.idx : 0xFFFFFFFFu);
+  const unsigned long long mn = group_min_u64<16>(bits);
+  const uint32_t rk = group_min_u32<16>(bits == mn ? (uint32_t)b.rank : 0xFFFFFFFFu);
+  const uint32_t ix = group_min_u32<16>((bits == mn && (uint32_t)b.rank == rk) ? (uint32_t)b.idx : 0xFFFFFFFFu);
   WalkBest r;
   r.dist = __longlong_as_double((long long)mn); r.rank = (int)rk; r.idx = (int)ix;  // idx -1 (0xFFFFFFFF) = none
   return r;
@@ -149,8 +149,7 @@ __global__ void __launch_bounds__(LG_T) lo_grid_build(DevCtx d) {
   }
 #pragma unroll
   for (int a = 0; a < 2; ++a) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { mn[a] = fminf(mn[a], __shfl_xor(mn[a], o, 64)); mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], o, 64)); }
+    bfly_minmax_f32(mn[a], mx[a]);
     if (lane == 0) { s_red[a][wave] = mn[a]; s_red[2 + a][wave] = mx[a]; }
   }
   for (int w = tid; w < LO_GC / 2; w += LG_T) s_cnt[w] = 0u;
@@ -192,9 +191,7 @@ __global__ void __launch_bounds__(LG_T) lo_grid_build(DevCtx d) {
   int tsum = 0;
 #pragma unroll 4
   for (int k = 0; k < WPT; ++k) { const unsigned w = s_cnt[tid * WPT + k]; tsum += (int)(w & 0xFFFFu) + (int)(w >> 16); }
-  int incl = tsum;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
+  const int incl = wave_incl_scan(tsum);
   if (lane == 63) s_tot[wave] = incl;
   __syncthreads();
   int run = incl - tsum;
@@ -381,7 +378,7 @@ DEV_INLINE void lo_assoc_body(const DevCtx& d, int box_lds_max, int slot, int qb
             if (v) gbest = k < gbest ? k : gbest;
           }
         }
-        gbest = row16_min_u64(gbest);
+        gbest = group_min_u64<16>(gbest);
         settled = gbest != ~0ull && d_i2f((int32_t)(gbest >> 32)) < s_geom[3];
       }
     }
@@ -392,11 +389,11 @@ DEV_INLINE void lo_assoc_body(const DevCtx& d, int box_lds_max, int slot, int qb
       const unsigned long long k = ((unsigned long long)(uint32_t)d_f2i(lb_f32(c)) << 32) | (uint32_t)c;
       m1 = k < m1 ? k : m1;
     }
-    const int cs = (int)(uint32_t)row16_min_u64(m1);
+    const int cs = (int)(uint32_t)group_min_u64<16>(m1);
     LA_TICK(2);   // box with the smallest bound: nt > 0, so it exists
     unsigned long long best;
     { int cb[LO_NB]; for (int u = 0; u < LO_NB; ++u) cb[u] = -1; cb[0] = cs; cb[1] = (cs ^ 1) < nch ? (cs ^ 1) : -1; best = nn_eval(cb, ~0ull); }
-    const float bound = d_i2f((int32_t)(row16_min_u64(best) >> 32));
+    const float bound = d_i2f((int32_t)(group_min_u64<16>(best) >> 32));
     LA_TICK(3);
     for (int c0 = 0; c0 < nch; c0 += 16) {
       const int c = c0 + l16;
@@ -407,7 +404,7 @@ DEV_INLINE void lo_assoc_body(const DevCtx& d, int box_lds_max, int slot, int qb
         best = nn_eval(cb, best);
       }
     }
-    bj = row16_min_u64(best);
+    bj = group_min_u64<16>(best);
     }
     LA_TICK(4);
     const bool found = (double)d_i2f((int32_t)(bj >> 32)) < nfd;
@@ -477,7 +474,7 @@ DEV_INLINE void lo_assoc_body(const DevCtx& d, int box_lds_max, int slot, int qb
         }
       }
     }
-    mo = row16_min_u64(mo);
+    mo = group_min_u64<16>(mo);
     LA_TICK(5);
     const int cseedS = cw1 >= cw0 ? min(max(same_b0 + (closest - same_lo) / LO_CH, cw0), cw1) : -1, cseedO = mo == ~0ull ? -1 : (int)(uint32_t)mo;
     { int cb[LO_NB]; for (int u = 0; u < LO_NB; ++u) cb[u] = -1; cb[0] = cseedS; cb[1] = cseedO != cseedS ? cseedO : -1; walk_eval(cb); }
@@ -487,9 +484,9 @@ DEV_INLINE void lo_assoc_body(const DevCtx& d, int box_lds_max, int slot, int qb
     const double seenS = b2.dist, seenO3 = b3.dist;
     double inS = nfd, inO = seenS;
     if (kind == 0) { inS = seenS; inO = seenO3; }
-    const double boundS = __longlong_as_double((long long)row16_min_u64((unsigned long long)__double_as_longlong(inS)));
+    const double boundS = __longlong_as_double((long long)group_min_u64<16>((unsigned long long)__double_as_longlong(inS)));
     LA_TICK(6);
-    const double boundO = __longlong_as_double((long long)row16_min_u64((unsigned long long)__double_as_longlong(inO)));
+    const double boundO = __longlong_as_double((long long)group_min_u64<16>((unsigned long long)__double_as_longlong(inO)));
     // (round 6) the survivors of up to FOUR groups of 16 boxes are collected in one 64-bit mask per row before any of them is evaluated: the few boxes that survive
     // (one or two per ring of the window) lie in different groups, and evaluating group by group spent a half-empty walk_eval turn on most of them
     if (lane == 0) LA_COUNT(0, 1);
@@ -638,8 +635,7 @@ DEV_INLINE void lo_solve_body(const DevCtx& d, int phase, int slot) {
     const int* rows = d.lo_corr + ((size_t)slot * (d.lo_qcap_surf + d.lo_qcap_corner) + (phase == 0 ? 0 : d.lo_qcap_surf)) * 4;
     int c = 0;
     for (int i = threadIdx.x; i < n; i += BLK) c += rows[(size_t)i * 4 + 1] >= 0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    c = bfly_sum_i32(c);
     if (lane_id() == 0) s_cnt[threadIdx.x >> 6] = c;
     __syncthreads();
     if (threadIdx.x == 0) {

@@ -75,8 +75,7 @@ __global__ void __launch_bounds__(LC_DT) lc_detect(LmCtx L, const int* list, ale
     // radiusSearch (f32 d² < r², :778) + the first candidate in (d², id) order that is old enough (:781-788); d² >= 0: its bits order it
     if (r < r2 && t_last - L.arc_stamp[fb + i] > P.lc_min_time_gap) best = min(best, ((unsigned long long)__float_as_uint(r) << 32) | (unsigned)i);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) best = min(best, (unsigned long long)__shfl_xor(best, o, 64));
+  best = bfly_min_u64(best);
   if (lane_id() == 0) s_min[threadIdx.x >> 6] = best;
   __syncthreads();
   if (threadIdx.x != 0) return;
@@ -152,8 +151,7 @@ DEV_INLINE void lc_grid_build(const float4* P, int n, int cell_cap, LcGrid* geo,
   }
 #pragma unroll
   for (int a = 0; a < 3; ++a)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { mn[a] = fminf(mn[a], __shfl_xor(mn[a], o, 64)); mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], o, 64)); }
+    bfly_minmax_f32(mn[a], mx[a]);
   if (lane_id() == 0) for (int a = 0; a < 3; ++a) { s_r[a][threadIdx.x >> 6] = mn[a]; s_r[3 + a][threadIdx.x >> 6] = mx[a]; }
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -195,17 +193,10 @@ DEV_INLINE void lc_grid_build(const float4* P, int n, int cell_cap, LcGrid* geo,
   for (int c0 = 0; c0 < G.ncell; c0 += LC_DT) {
     const int c = c0 + threadIdx.x;
     const int v = c < G.ncell ? cstart[c] : 0;
-    const int lane = lane_id(), wave = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
-    if (lane == 63) s_w[wave] = incl;
-    __syncthreads();
-    int wo = 0, tot = 0;
-    for (int w = 0; w < LC_DT / 64; ++w) { if (w < wave) wo += s_w[w]; tot += s_w[w]; }
-    if (c < G.ncell) { cstart[c] = carry + wo + incl - v; ccur[c] = carry + wo + incl - v; }
+    int tot;
+    const int ex = carry + block_excl_scan<LC_DT / 64>(v, s_w, &tot);
+    if (c < G.ncell) { cstart[c] = ex; ccur[c] = ex; }
     carry += tot;
-    __syncthreads();
   }
   if (threadIdx.x == 0) cstart[G.ncell] = n;
   __syncthreads();
@@ -350,7 +341,7 @@ __global__ void __launch_bounds__(LC_IT) lc_icp(const LcJob* jobs, const LcDet* 
       }
     }
 #pragma unroll
-    for (int k = 0; k < 17; ++k) v[k] = wave_sum_f64(v[k]);
+    for (int k = 0; k < 17; ++k) v[k] = bfly_sum_f64(v[k]);
     if (lane_id() == 0) for (int k = 0; k < 17; ++k) s_red[tid >> 6][k] = v[k];
     __syncthreads();
     if (tid < 17) { double t = 0; for (int w = 0; w < LC_IT / 64; ++w) t += s_red[w][tid]; s_T[tid] = t; }
@@ -370,7 +361,7 @@ __global__ void __launch_bounds__(LC_IT) lc_icp(const LcJob* jobs, const LcDet* 
     lc_nn(G, cs, cb, tp, p, &d2, &idx, &pos);
     if (idx >= 0) { s += (double)d2; c += 1.0; }
   }
-  s = wave_sum_f64(s); c = wave_sum_f64(c);
+  s = bfly_sum_f64(s); c = bfly_sum_f64(c);
   if (lane_id() == 0) { s_red[tid >> 6][0] = s; s_red[tid >> 6][1] = c; }
   __syncthreads();
   if (tid == 0) {

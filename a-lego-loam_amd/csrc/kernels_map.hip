@@ -100,22 +100,6 @@ struct MapWork {
   int cap;
 };
 
-// block-wide exclusive scan of one int per thread (MU_T threads); returns the exclusive prefix, *total = sum
-DEV_INLINE int block_excl_scan(int v, int* s_w /*[MU_T/64 + 1]*/, int* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
-  __syncthreads();
-  if (lane == 63) s_w[wave] = incl;
-  __syncthreads();
-  int woff = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < MU_T / 64; ++w) { const int c = s_w[w]; if (w < wave) woff += c; tot += c; }
-  *total = tot;
-  return woff + incl - v;
-}
-
 #define MU_FCAP 4096      // points of a run whose voxel keys the fast path of map_update stages in LDS (2 x 32 KB)
 #define MU_E 16           // consecutive entries of the voxel list per thread in the fast path
 #ifndef MU_WORKLIST
@@ -149,7 +133,7 @@ __global__ void __launch_bounds__(MU_T) map_update(DevCtx d, LmCtx L, MapWork W)
     const int sx = s0 + tid;
     const int flag = (sx < min(c0 + MU_LIST, d.n_launch) && lipm(L, sx + d.slot0)[LI_REBUILD] && d.opt_map_merge) ? 1 : 0;
     int tot;
-    const int ex = block_excl_scan(flag, s_w, &tot);
+    const int ex = block_excl_scan<MU_T / 64>(flag, s_w, &tot);
     if (flag) s_items[n_items + ex] = (unsigned short)(sx - c0);
     n_items += tot;
   }
@@ -180,12 +164,9 @@ __global__ void __launch_bounds__(MU_T) map_update(DevCtx d, LmCtx L, MapWork W)
         mx[0] = fmaxf(mx[0], b[4]); mx[1] = fmaxf(mx[1], b[5]); mx[2] = fmaxf(mx[2], b[6]);
       }
     }
+    kraw = bfly_sum_i32(kraw);
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      kraw += __shfl_xor(kraw, o, 64);
-#pragma unroll
-      for (int a = 0; a < 3; ++a) { mn[a] = fminf(mn[a], __shfl_xor(mn[a], o, 64)); mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], o, 64)); }
-    }
+    for (int a = 0; a < 3; ++a) bfly_minmax_f32(mn[a], mx[a]);
     __syncthreads();
     if ((tid & 63) == 0) { s_kr_tot[tid >> 6] = kraw; for (int a = 0; a < 3; ++a) { s_box[a][tid >> 6] = mn[a]; s_box[3 + a][tid >> 6] = mx[a]; } }
     __syncthreads();
@@ -276,7 +257,7 @@ __global__ void __launch_bounds__(MU_T) map_update(DevCtx d, LmCtx L, MapWork W)
           int nout = 0;
           merge([&](u64, int) { ++nout; });
           int tot;
-          int pos = out_off + block_excl_scan(nout, s_w, &tot);
+          int pos = out_off + block_excl_scan<MU_T / 64>(nout, s_w, &tot);
           merge([&](u64 k, int c) { if (pos < cap) { S_key[pos] = k; S_cnt[pos] = c; } ++pos; });
           out_off += tot;
         }
@@ -332,7 +313,7 @@ __global__ void __launch_bounds__(MU_T) map_update(DevCtx d, LmCtx L, MapWork W)
             }
           }
           int tot;
-          const int ex = block_excl_scan(newhead ? 1 : 0, s_w, &tot);
+          const int ex = block_excl_scan<MU_T / 64>(newhead ? 1 : 0, s_w, &tot);
           const int base = s_nnew;
           if (newhead) nk[base + ex] = make_float4(__uint_as_float((unsigned)key), __uint_as_float((unsigned)(key >> 32)), __int_as_float(pos), __int_as_float(c));
           __syncthreads();
@@ -350,7 +331,7 @@ __global__ void __launch_bounds__(MU_T) map_update(DevCtx d, LmCtx L, MapWork W)
           const int c = i < nU ? __hip_atomic_load(&cnt[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
           const int keep = c > 0 ? 1 : 0;
           int tot;
-          const int ex = kept_total + block_excl_scan(keep, s_w, &tot);
+          const int ex = kept_total + block_excl_scan<MU_T / 64>(keep, s_w, &tot);
           if (i < nU) {
             S_E[i] = ex;
             if (keep) {
@@ -441,7 +422,7 @@ __global__ void __launch_bounds__(MU_T) map_update(DevCtx d, LmCtx L, MapWork W)
       }
     }
     int tot;
-    int n = run_total + block_excl_scan(nmine, s_w, &tot);
+    int n = run_total + block_excl_scan<MU_T / 64>(nmine, s_w, &tot);
     if (rebuilt) {
       for (int mm = 0; mm < 2; ++mm)
         for (int c = 0; c < nch[mm]; ++c) {

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "voxel.h"
+#include "wave.h"
 #include "vgrid.h"
 #include "guard_alloc.h"
 #include "prof.h"
@@ -93,7 +94,7 @@ __device__ void vox_big_job(const VoxCtx& V, int job, unsigned char* smem) {
   }
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    vgr_wave_minmax(mn[a], mx[a]);
+    bfly_minmax_f32(mn[a], mx[a]);
     if (lane == 0) { s_red[a][wave] = mn[a]; s_red[3 + a][wave] = mx[a]; }
   }
   __syncthreads();
@@ -169,9 +170,7 @@ __device__ void vox_big_job(const VoxCtx& V, int job, unsigned char* smem) {
       int v[PER], sum = 0;
 #pragma unroll
       for (int k = 0; k < PER; ++k) { const int dgt = lane * PER + k; v[k] = dgt < nd ? s_tot[dgt] : 0; sum += v[k]; }
-      int incl = sum;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
+      const int incl = wave_incl_scan(sum);
       int run = incl - sum;
 #pragma unroll
       for (int k = 0; k < PER; ++k) { const int dgt = lane * PER + k; if (dgt < nd) s_tot[dgt] = run; run += v[k]; }
@@ -328,7 +327,7 @@ __device__ void vox_small_job(const VoxCtx& V, int job) {
   for (int i = tid; i < n; i += VX_SB) vgr_box_add(mn, mx, J.in[i]);
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    vgr_wave_minmax(mn[a], mx[a]);
+    bfly_minmax_f32(mn[a], mx[a]);
     if (lane == 0) { s_red[a][wave] = mn[a]; s_red[3 + a][wave] = mx[a]; }
   }
   __syncthreads();
@@ -386,9 +385,7 @@ __device__ void vox_small_job(const VoxCtx& V, int job) {
           int v[PER], sum = 0;
 #pragma unroll
           for (int k = 0; k < PER; ++k) { const int dgt = lane * PER + k; v[k] = dgt < nd ? s_tot[dgt] : 0; sum += v[k]; }
-          int incl = sum;
-#pragma unroll
-          for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
+          const int incl = wave_incl_scan(sum);
           int run = incl - sum;
 #pragma unroll
           for (int k = 0; k < PER; ++k) { const int dgt = lane * PER + k; if (dgt < nd) s_tot[dgt] = run; run += v[k]; }

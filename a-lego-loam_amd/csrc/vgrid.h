@@ -23,11 +23,7 @@ __device__ __forceinline__ void vgr_box_add(float mn[3], float mx[3], float4 p) 
   mn[0] = fminf(mn[0], p.x); mn[1] = fminf(mn[1], p.y); mn[2] = fminf(mn[2], p.z);
   mx[0] = fmaxf(mx[0], p.x); mx[1] = fmaxf(mx[1], p.y); mx[2] = fmaxf(mx[2], p.z);
 }
-// across the wavefront, one axis at a time: a butterfly, every lane ends with the wavefront's min / max
-__device__ __forceinline__ void vgr_wave_minmax(float& mn, float& mx) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { mn = fminf(mn, __shfl_xor(mn, o, 64)); mx = fmaxf(mx, __shfl_xor(mx, o, 64)); }
-}
+// across the wavefront: bfly_minmax_f32 (wave.h), one axis at a time
 
 // ---- the grid ----
 // PCL's "leaf size too small" rule: the filter returns its input unchanged
