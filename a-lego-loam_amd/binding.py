@@ -32,6 +32,8 @@ EXPORTS = [
     "alego_map_enable", "alego_map_status", "alego_map_set_keyposes", "alego_map_get_keyframe", "alego_map_assemble", "alego_map_keyposes",
     "alego_lm_get_local_map", "alego_voxel_grid", "alego_write_pcd",
     "alego_map_get_stamps", "alego_map_set_stamps", "alego_loop_search", "alego_loop_constraint", "alego_debug_nn1",
+    "alego_graph_enable", "alego_graph_status", "alego_graph_get_edges", "alego_graph_set_edges", "alego_graph_add_loops", "alego_graph_add_edge",
+    "alego_graph_optimize", "alego_graph_get_estimate", "alego_graph_residuals",
 ]
 
 REPLAY_PINGPONG = 0x100
@@ -107,6 +109,55 @@ def _loop_result(r):
                 iterations=int(r.iterations), n_source=int(r.n_source), n_target=int(r.n_target), fitness=float(r.fitness),
                 T=np.array(r.correction[:], np.float32).reshape(4, 4), t_correct=np.array(r.t_correct[:], np.float32).reshape(4, 4),
                 between=np.array(r.between[:], np.float64).reshape(3, 4), noise_variance=float(r.noise_variance))
+
+
+class GraphEdge(C.Structure):
+    _fields_ = [("frm", C.c_int32), ("to", C.c_int32), ("between", C.c_double * 12), ("variance", C.c_double * 6)]
+
+
+class GraphOpts(C.Structure):
+    _fields_ = [("max_iters", C.c_int32), ("step_tol", C.c_double), ("apply", C.c_int32)]
+
+
+class GraphResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("n_poses", C.c_int32), ("n_loops", C.c_int32), ("applied", C.c_int32),
+                ("cost0", C.c_double), ("cost", C.c_double), ("last_step", C.c_double)]
+
+
+GRAPH_MAX_LOOPS = 64
+GRAPH_MAX_ITERS, GRAPH_STEP_TOL = 20, 1e-9   # ALEGO_GRAPH_MAX_ITERS, ALEGO_GRAPH_STEP_TOL
+
+
+def graph_edges(frm, to, between, variance):
+    """a ctypes array of alego_graph_edge from arrays: from (n,) (-1 = prior), to (n,), between (n, 3, 4), variance (n, 6)"""
+    frm = np.asarray(frm, np.int64).reshape(-1)
+    to = np.asarray(to, np.int64).reshape(-1)
+    b = np.ascontiguousarray(between, np.float64).reshape(-1, 12)
+    v = np.ascontiguousarray(variance, np.float64).reshape(-1, 6)
+    out = (GraphEdge * max(len(frm), 1))()
+    for i in range(len(frm)):
+        out[i].frm, out[i].to = int(frm[i]), int(to[i])
+        out[i].between[:] = b[i].tolist()
+        out[i].variance[:] = v[i].tolist()
+    return out
+
+
+def _graph_edges_out(e, n):
+    return dict(frm=np.array([e[i].frm for i in range(n)], np.int64), to=np.array([e[i].to for i in range(n)], np.int64),
+                between=np.array([e[i].between[:] for i in range(n)], np.float64).reshape(n, 3, 4),
+                variance=np.array([e[i].variance[:] for i in range(n)], np.float64).reshape(n, 6))
+
+
+def graph_residuals(poses12, frm, to, between, variance):
+    """alego_graph_residuals (host only): whitened errors (n, 6), d / d delta_from (n, 6, 6), d / d delta_to (n, 6, 6)"""
+    X = np.ascontiguousarray(poses12, np.float64).reshape(-1, 12)
+    n = len(np.asarray(frm).reshape(-1))
+    e = graph_edges(frm, to, between, variance)
+    r, jf, jt = np.zeros((max(n, 1), 6)), np.zeros((max(n, 1), 36)), np.zeros((max(n, 1), 36))
+    rc = lib().alego_graph_residuals(X.ctypes.data, X.shape[0], e, n, r.ctypes.data, jf.ctypes.data, jt.ctypes.data)
+    if rc != 0:
+        raise AlegoError(f"alego_graph_residuals failed ({rc})")
+    return r[:n], jf[:n].reshape(n, 6, 6), jt[:n].reshape(n, 6, 6)
 
 
 class Pc2Field(C.Structure):
@@ -262,6 +313,15 @@ def lib():
         L.alego_loop_search.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(LoopResult)]
         L.alego_loop_constraint.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.alego_debug_nn1.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        L.alego_graph_enable.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        L.alego_graph_status.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.alego_graph_get_edges.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int32, C.c_int32, C.POINTER(GraphEdge)]
+        L.alego_graph_set_edges.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.POINTER(GraphEdge)]
+        L.alego_graph_add_loops.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(LoopResult)]
+        L.alego_graph_add_edge.argtypes = [C.c_void_p, C.c_int, C.POINTER(GraphEdge), C.c_void_p]
+        L.alego_graph_optimize.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(GraphOpts), C.POINTER(GraphResult)]
+        L.alego_graph_get_estimate.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.c_void_p]
+        L.alego_graph_residuals.argtypes = [C.c_void_p, C.c_int32, C.POINTER(GraphEdge), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.alego_write_pcd.argtypes = [C.c_char_p, C.c_void_p, C.c_int32]
         L.alego_bag_read_pc2.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
         if L.alego_params_sizeof() != C.sizeof(AlegoParams):
@@ -758,6 +818,63 @@ class Handle:
         out = (LoopResult * max(sl.shape[0], 1))()
         self._check(lib().alego_loop_search(self._h, sl.ctypes.data, sl.shape[0], out), "alego_loop_search")
         return [_loop_result(out[i]) for i in range(sl.shape[0])]
+
+    # ---- the key-pose graph (needs map_enable) ----
+    def graph_enable(self, max_loops, odom_variance=None):
+        v = None if odom_variance is None else np.ascontiguousarray(odom_variance, np.float64).reshape(6)
+        self._check(lib().alego_graph_enable(self._h, int(max_loops), None if v is None else v.ctypes.data), "alego_graph_enable")
+
+    def graph_get_edges(self, kind=0, first=0, n=None, slot=0):
+        """dict(frm, to, between (n, 3, 4), variance (n, 6)); kind 0: the chain (edge 0 = the prior), 1: the loop edges; n = None: all"""
+        if n is None:
+            n = self.graph_status(slot)[0 if kind == 0 else 1] - first
+        e = (GraphEdge * max(n, 1))()
+        self._check(lib().alego_graph_get_edges(self._h, slot, kind, first, n, e), "alego_graph_get_edges")
+        return _graph_edges_out(e, n)
+
+    def graph_status(self, slot=0):
+        """(chain edges, loop edges, loop_closed_, poses of the last estimate)"""
+        out = np.zeros(4, np.int32)
+        self._check(lib().alego_graph_status(self._h, slot, out.ctypes.data), "alego_graph_status")
+        return tuple(int(v) for v in out)
+
+    def graph_set_edges(self, first, frm, to, between, variance, slot=0):
+        e = graph_edges(frm, to, between, variance)
+        self._check(lib().alego_graph_set_edges(self._h, slot, first, len(np.asarray(frm).reshape(-1)), e), "alego_graph_set_edges")
+
+    def graph_add_loops(self, slots, results):
+        """results: the dicts loop_search returned for `slots`; entries with status == 2 are appended"""
+        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        r = (LoopResult * max(sl.shape[0], 1))()
+        for i, d in enumerate(results):
+            r[i].status, r[i].latest_id, r[i].closest_id = d["status"], d["latest_id"], d["closest_id"]
+            r[i].fitness, r[i].noise_variance = d["fitness"], d["noise_variance"]
+            r[i].correction[:] = np.asarray(d["T"], np.float32).reshape(16).tolist()
+            r[i].between[:] = np.asarray(d["between"], np.float64).reshape(12).tolist()
+        self._check(lib().alego_graph_add_loops(self._h, sl.ctypes.data, sl.shape[0], r), "alego_graph_add_loops")
+
+    def graph_add_edge(self, frm, to, between, variance, correction=None, slot=0):
+        e = graph_edges([frm], [to], [between], [variance])
+        c = None if correction is None else np.ascontiguousarray(correction, np.float32).reshape(16)
+        self._check(lib().alego_graph_add_edge(self._h, slot, e, None if c is None else c.ctypes.data), "alego_graph_add_edge")
+
+    def graph_optimize(self, slots, max_iters=0, step_tol=0.0, apply=False):
+        """alego_graph_optimize: one dict per listed slot (status, iterations, n_poses, n_loops, applied, cost0, cost, last_step);
+        max_iters / step_tol 0 = the library's defaults"""
+        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        o = GraphOpts(int(max_iters), float(step_tol), int(bool(apply)))
+        out = (GraphResult * max(sl.shape[0], 1))()
+        self._check(lib().alego_graph_optimize(self._h, sl.ctypes.data, sl.shape[0], C.byref(o), out), "alego_graph_optimize")
+        return [dict(status=int(r.status), iterations=int(r.iterations), n_poses=int(r.n_poses), n_loops=int(r.n_loops), applied=int(r.applied),
+                     cost0=float(r.cost0), cost=float(r.cost), last_step=float(r.last_step)) for r in out[:sl.shape[0]]]
+
+    def graph_get_estimate(self, first=0, n=None, slot=0):
+        """(n, 3, 4) f64 poses of the slot's last optimise"""
+        if n is None:
+            n = self.map_status(slot)[0] - first
+        out = np.zeros((max(n, 1), 12), np.float64)
+        self._check(lib().alego_graph_get_estimate(self._h, slot, first, n, out.ctypes.data), "alego_graph_get_estimate")
+        return out[:n].reshape(n, 3, 4)
 
     def debug_nn1(self, tgt, queries):
         """the grid 1-NN of alego_loop_search alone: (index, f32 squared distance) per query"""

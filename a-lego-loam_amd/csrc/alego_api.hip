@@ -16,6 +16,7 @@
 #include "dev_common.h"
 #include "guard_alloc.h"
 #include "lm_host.h"
+#include "pgraph.h"
 #include "prof.h"
 #include "voxel.h"
 
@@ -84,6 +85,8 @@ struct alego_handle {
   size_t ev_next = 0;
   bool map_on = false;         // alego_map_enable: the key-frame archive exists
   LcCtx* lc = nullptr;         // alego_loop_search: detection / chunk scratch, allocated by the first call and kept
+  bool graph_on = false;       // alego_graph_enable: the key-pose graph exists
+  PgCtx* pg = nullptr;         // alego_graph_optimize: chunk scratch, allocated by the first call and kept
 };
 
 namespace {
@@ -377,6 +380,7 @@ void alego_destroy(alego_handle* h) {
   if (g_prof == &h->prof) g_prof = nullptr;
   if (h->lm) lm_host_destroy(h->lm);
   loop_ctx_destroy(h->lc);
+  graph_ctx_destroy(h->pg);
   for (void* p : h->allocs) (void)guard_free(p);
   for (hipStream_t s : h->streams) hipStreamDestroy(s);
   for (hipStream_t s : h->back) hipStreamDestroy(s);
@@ -1042,6 +1046,7 @@ int alego_debug_set_option(alego_handle* h, const char* name, int value) {
   else if (s == "ALEGO_IP_FAST") d.ip_fast = h->ip_fast_capable & value;
   else if (s == "ALEGO_POKE_GUARD") { HIP_TRY(h, hipMemset(d.scal + (size_t)d.n_slots * SC_COUNT + value, 0xFF, 4)); }   // tests of the guard pages: a write `value` ints past the end of an array
   else if (s == "ALEGO_GV_SMALL_MAX") { HIP_TRY(h, sync_all(h)); return lm_host_set_gv_small_max(h->lm, value); }   // tools/gmap_timing.py: largest cloud alego_voxel_grid gives to one workgroup
+  else if (s == "ALEGO_PG_BUDGET") graph_ctx_set_budget(&h->pg, value);   // tests / tools: bytes of scratch per chunk of alego_graph_optimize
   else if (s == "ALEGO_LC_BUDGET") loop_ctx_set_budget(&h->lc, value);   // tests / tools: raw sub-map points per chunk of alego_loop_search
   else if (s == "ALEGO_SHARD_SLICE") return lm_host_debug_slice(h->lm, value & 0xff, value >> 8, &h->err);   // tests: rank | world << 8 without a communicator
   else { h->err = "unknown option " + s; return ALEGO_ERR_ARG; }
@@ -1151,6 +1156,106 @@ int alego_debug_nn1(alego_handle* h, const alego_point* tgt, int32_t n_tgt, cons
   if (!h || n_tgt < 0 || n_q < 0 || (n_tgt > 0 && !tgt) || (n_q > 0 && (!queries || !idx || !d2))) return ALEGO_ERR_ARG;
   hipSetDevice(h->device);
   return loop_debug_nn1(tgt, n_tgt, queries, n_q, idx, d2, h->stream, &h->err);
+}
+
+// ---- the key-pose graph -----------------------------------------------------------------------------------------------
+static int graph_ready(alego_handle* h, const char* what) {
+  if (!h) return ALEGO_ERR_ARG;
+  if (!h->graph_on) { h->err = std::string(what) + ": the key-pose graph is off (alego_map_enable, then alego_graph_enable)"; return ALEGO_ERR_ARG; }
+  hipSetDevice(h->device);
+  g_prof = &h->prof;
+  return 0;
+}
+int alego_graph_enable(alego_handle* h, int32_t max_loops, const double odom_variance[6]) {
+  if (!h) return ALEGO_ERR_ARG;
+  if (!h->map_on) { h->err = "alego_graph_enable: the key-frame archive is off (alego_map_enable first)"; return ALEGO_ERR_ARG; }
+  if (h->graph_on) { h->err = "alego_graph_enable: already enabled"; return ALEGO_ERR_ARG; }
+  hipSetDevice(h->device);
+  HIP_TRY(h, sync_all(h));
+  if (int r = lm_host_graph_enable(h->lm, max_loops, odom_variance, &h->err)) return r;
+  h->graph_on = true;
+  return 0;
+}
+int alego_graph_status(alego_handle* h, int slot, int32_t out[4]) {
+  if (int r = graph_ready(h, "alego_graph_status")) return r;
+  if (int r = check_slot(h, slot)) return r;
+  if (!out) return ALEGO_ERR_ARG;
+  HIP_TRY(h, hipStreamSynchronize(stream_of(h, slot)));
+  return graph_status(*lm_host_ctx(h->lm), slot, out, &h->err);
+}
+int alego_graph_get_edges(alego_handle* h, int slot, int kind, int32_t first, int32_t n, alego_graph_edge* out) {
+  if (int r = graph_ready(h, "alego_graph_get_edges")) return r;
+  if (int r = check_slot(h, slot)) return r;
+  HIP_TRY(h, hipStreamSynchronize(stream_of(h, slot)));
+  return graph_get_edges(*lm_host_ctx(h->lm), slot, kind, first, n, out, &h->err);
+}
+int alego_graph_set_edges(alego_handle* h, int slot, int32_t first, int32_t n, const alego_graph_edge* chain) {
+  if (int r = graph_ready(h, "alego_graph_set_edges")) return r;
+  if (int r = check_slot(h, slot)) return r;
+  HIP_TRY(h, hipStreamSynchronize(stream_of(h, slot)));
+  return graph_set_edges(*lm_host_ctx(h->lm), slot, first, n, chain, &h->err);
+}
+int alego_graph_add_loops(alego_handle* h, const int32_t* slots, int32_t n, const alego_loop_result* r) {
+  if (int rc = graph_ready(h, "alego_graph_add_loops")) return rc;
+  if (n < 0 || (n > 0 && (!slots || !r))) return ALEGO_ERR_ARG;
+  std::vector<PgAppend> a;
+  for (int i = 0; i < n; ++i) {
+    if (slots[i] < 0 || slots[i] >= h->d.n_slots) { h->err = "alego_graph_add_loops: slot out of range"; return ALEGO_ERR_ARG; }
+    if (r[i].status != 2) continue;
+    PgAppend p;
+    std::memset(&p, 0, sizeof(p));
+    p.slot = slots[i];
+    p.e.from = r[i].latest_id; p.e.to = r[i].closest_id;
+    std::memcpy(p.e.between, r[i].between, sizeof(p.e.between));
+    for (int k = 0; k < 6; ++k) p.e.variance[k] = r[i].noise_variance;
+    std::memcpy(p.corr, r[i].correction, sizeof(p.corr));
+    a.push_back(p);
+  }
+  HIP_TRY(h, sync_all(h));
+  return graph_append(&h->pg, *lm_host_ctx(h->lm), h->d.n_slots, a, h->stream, &h->err);
+}
+int alego_graph_add_edge(alego_handle* h, int slot, const alego_graph_edge* e, const float correction[16]) {
+  if (int r = graph_ready(h, "alego_graph_add_edge")) return r;
+  if (int r = check_slot(h, slot)) return r;
+  if (!e) return ALEGO_ERR_ARG;
+  PgAppend p;
+  std::memset(&p, 0, sizeof(p));
+  p.slot = slot; p.e = *e;
+  for (int k = 0; k < 16; ++k) p.corr[k] = correction ? correction[k] : (k % 5 == 0 ? 1.f : 0.f);
+  HIP_TRY(h, sync_all(h));
+  return graph_append(&h->pg, *lm_host_ctx(h->lm), h->d.n_slots, std::vector<PgAppend>(1, p), h->stream, &h->err);
+}
+int alego_graph_optimize(alego_handle* h, const int32_t* slots, int32_t n, const alego_graph_opts* opts, alego_graph_result* out) {
+  if (int r = graph_ready(h, "alego_graph_optimize")) return r;
+  if (n < 0 || (n > 0 && (!slots || !out))) return ALEGO_ERR_ARG;
+  std::vector<char> listed(h->d.n_slots, 0);
+  for (int i = 0; i < n; ++i) {
+    if (slots[i] < 0 || slots[i] >= h->d.n_slots) { h->err = "alego_graph_optimize: slot out of range"; return ALEGO_ERR_ARG; }
+    if (listed[slots[i]]) { h->err = "alego_graph_optimize: a slot is listed twice"; return ALEGO_ERR_ARG; }
+    listed[slots[i]] = 1;
+  }
+  alego_graph_opts o = {ALEGO_GRAPH_MAX_ITERS, ALEGO_GRAPH_STEP_TOL, 0};
+  if (opts) { if (opts->max_iters > 0) o.max_iters = opts->max_iters; if (opts->step_tol > 0.0) o.step_tol = opts->step_tol; o.apply = opts->apply != 0; }
+  if (n == 0) return 0;
+  HIP_TRY(h, sync_all(h));   // behind everything already queued on every stream group
+  std::vector<int> apply;
+  if (int r = graph_optimize(&h->pg, *lm_host_ctx(h->lm), h->d.n_slots, slots, n, o, out, &apply, h->stream, &h->err)) return r;
+  int most = 0;
+  for (int i = 0; i < n; ++i) if (out[i].applied) most = std::max(most, out[i].n_poses);
+  if (most == 0) return 0;
+  const int* apply_dev = nullptr;
+  if (int r = graph_upload_apply(h->pg, apply, &apply_dev, h->stream, &h->err)) return r;
+  return lm_host_graph_apply(h->lm, apply, apply_dev, most, &h->err);
+}
+int alego_graph_get_estimate(alego_handle* h, int slot, int32_t first, int32_t n, double* poses12) {
+  if (int r = graph_ready(h, "alego_graph_get_estimate")) return r;
+  if (int r = check_slot(h, slot)) return r;
+  return graph_get_estimate(*lm_host_ctx(h->lm), slot, first, n, poses12, &h->err);
+}
+int alego_graph_residuals(const double* poses12, int32_t n_poses, const alego_graph_edge* edges, int32_t n_edges, double* whitened6, double* jac_from36, double* jac_to36) {
+  if (!poses12 || n_poses <= 0 || n_edges < 0 || (n_edges > 0 && !edges)) return ALEGO_ERR_ARG;
+  for (long i = 0; i < (long)n_poses * 12; ++i) if (!std::isfinite(poses12[i])) return ALEGO_ERR_ARG;
+  return graph_residuals_host(poses12, n_poses, edges, n_edges, whitened6, jac_from36, jac_to36);
 }
 
 // ---- one registration sharded over the GPUs of a node ---------------------------------------------------------------

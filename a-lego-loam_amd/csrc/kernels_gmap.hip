@@ -21,9 +21,11 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "../../include/alego_mi355x.h"
 #include "gmap.h"
 #include "guard_alloc.h"
 #include "lm_ctx.h"
+#include "pg_math.h"
 #include "prof.h"
 #include "vgrid.h"
 
@@ -69,6 +71,22 @@ __global__ void __launch_bounds__(GM_T) map_archive(DevCtx d, LmCtx L, int force
     // the stamp of the scan that saved the frame; paths without stamps (batch, replay) number the slot's mapping frames
     L.arc_stamp[(size_t)slot * L.arc_frames_cap + nf] = L.arc_stamped[slot] ? d.scan_stamp[slot] : (double)(li[LI_FRAME] - 1) * d.P.scan_period;
     st[0] = nf + 1; st[2] = np + nc + ns + no;
+    // the key-pose graph (alego_graph_enable): PriorFactor on the first frame (:495), else BetweenFactor(pre_pose, this pose) (:510-512),
+    // both poses as Pose3(Rot3::RzRyRx, xyz) of their f32 key poses; pre_pose is the archived pose of frame nf - 1 as it stands now
+    if (L.pg_loops_cap > 0) {
+      alego_graph_edge* e = L.pg_chain + (size_t)slot * L.arc_frames_cap + nf;
+      double xn[12];
+      pg_from_pose6(L.kf_pose + rs * 8, xn);
+      e->from = nf - 1; e->to = nf;
+      if (nf == 0) {
+        for (int k = 0; k < 12; ++k) e->between[k] = xn[k];
+      } else {
+        double xp[12];
+        pg_from_pose6(L.arc_pose + ((size_t)slot * L.arc_frames_cap + nf - 1) * 8, xp);
+        pg_between(xp, xn, e->between);
+      }
+      for (int k = 0; k < 6; ++k) e->variance[k] = L.pg_odom_var[k];
+    }
   }
 }
 

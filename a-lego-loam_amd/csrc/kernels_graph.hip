@@ -1,0 +1,749 @@
+// kernels_graph.hip — the key-pose graph of every slot, optimised on gfx950 (laserMapping.cpp:491-584).
+//
+// The graph of a slot: its archived key frames as Pose3 nodes, a prior on node 0, the odometry chain map_archive recorded
+// (kernels_gmap.hip) and up to pg_loops_cap loop edges.  alego_graph_optimize runs plain Gauss-Newton in f64 for a chunk of slots
+// at once; every phase is a kernel, a slot's work inside a phase never leaves its workgroup (or its lane):
+//   pg_init        X <- Pose3(Rot3::RzRyRx, xyz) of the archived f32 key poses
+//   pg_linearize   one lane per edge: whitened error and the two 6x6 Jacobian blocks (pg_math.h)
+//   pg_assemble    one lane per node: the block-tridiagonal part T of J^T J (prior + chain) and the gradient g (chain + loops)
+//   pg_factor      one lane per slot: block Cholesky of T along the chain, T = L L^T with L block-bidiagonal
+//   pg_solve       one workgroup per slot, one lane per right-hand side: forward and backward sweeps of L for -g and for the 6 columns
+//                  of every loop edge's Jacobian side by side; the loop terms enter exactly through the capacitance system
+//                  C = I + J_loop T^-1 J_loop^T (Woodbury), factorised by the same workgroup; delta = z0 - Z C^-1 J_loop z0
+//   pg_update      one workgroup per slot: |delta|_inf, the finiteness check, X <- X Expmap(delta), the stopping rule
+//   pg_cost        one workgroup per slot: sum of squared whitened errors in a fixed order
+//   pg_store       the estimate of a finished slot goes to LmCtx::pg_est
+// All sums of a slot run in an order that depends on the slot's own graph only.
+// correctPoses (:561-584) for the slots that converged: pg_apply (poses, window reset words, map -> odom), then pg_retransform +
+// the key-frame sort jobs once per resident frame (lm_host.hip).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <type_traits>
+#include <vector>
+
+#include "../../include/alego_mi355x.h"
+#include "dev_cost.h"
+#include "guard_alloc.h"
+#include "lm_ctx.h"
+#include "pg_math.h"
+#include "pgraph.h"
+#include "prof.h"
+
+#define PG_T 256                       // workgroup of the per-edge / per-node / per-slot-reduction kernels
+#define PG_SOLVE_MAX 448               // lanes of pg_solve: 1 + 6 * ALEGO_GRAPH_MAX_LOOPS right-hand sides, rounded up to wavefronts
+#define PG_BUDGET_DEFAULT (1LL << 30)  // bytes of chunk scratch
+static_assert(1 + 6 * ALEGO_GRAPH_MAX_LOOPS <= PG_SOLVE_MAX, "pg_solve sweeps one right-hand side per lane");
+
+enum { PC_STATUS = 0, PC_ITERS, PC_DONE, PC_N, PC_NL, PC_SLOT, PC_COUNT = 8 };   // int control words of a chunk entry
+enum { PD_COST0 = 0, PD_COST, PD_STEP, PD_COUNT = 4 };                            // double control words
+
+// the scratch of one chunk entry q lives at fixed strides (Nmax poses, Lmax loop edges, R = 1 + 6 Lmax right-hand sides)
+struct PgWork {
+  int S, Nmax, Lmax, R;
+  int* ctl;        // [S][PC_COUNT]
+  double* dctl;    // [S][PD_COUNT]
+  double* X;       // [S][Nmax][12]
+  double* res;     // [S][Nmax + Lmax][6]     edge e < Nmax: chain edge e (the prior is edge 0); Nmax + l: loop edge l
+  double* Jf;      // [S][Nmax + Lmax][36]
+  double* Jt;      // [S][Nmax + Lmax][36]
+  double* Td;      // [S][Nmax][36]  diagonal blocks of T, then L_kk
+  double* To;      // [S][Nmax][36]  T_{k+1,k}, then L_{k+1,k}
+  double* g;       // [S][Nmax][6]   gradient, then delta
+  double* Z;       // [S][Nmax][6][R]
+  double* C;       // [S][6 Lmax][6 Lmax]
+};
+
+DEV_INLINE DQuat ldq(const double* p) { return DQuat{p[0], p[1], p[2], p[3]}; }
+DEV_INLINE void stq(double* p, const DQuat& q) { p[0] = q.w; p[1] = q.x; p[2] = q.y; p[3] = q.z; }
+DEV_INLINE const alego_graph_edge* pg_edge_of(const LmCtx& L, int slot, int Nmax, int e) {
+  return e < Nmax ? L.pg_chain + (size_t)slot * L.arc_frames_cap + e : L.pg_loops + (size_t)slot * L.pg_loops_cap + (e - Nmax);
+}
+
+__global__ void __launch_bounds__(PG_T) pg_init(LmCtx L, PgWork W) {
+  const int q = blockIdx.y, k = blockIdx.x * PG_T + threadIdx.x;
+  const int* ctl = W.ctl + q * PC_COUNT;
+  if (k >= ctl[PC_N]) return;
+  pg_from_pose6(L.arc_pose + ((size_t)ctl[PC_SLOT] * L.arc_frames_cap + k) * 8, W.X + ((size_t)q * W.Nmax + k) * 12);
+}
+
+// grid (edge tiles, chunk entries); force: also the slots that have finished (the final cost)
+__global__ void __launch_bounds__(PG_T) pg_linearize(LmCtx L, PgWork W, int force) {
+  const int q = blockIdx.y, e = blockIdx.x * PG_T + threadIdx.x;
+  const int* ctl = W.ctl + q * PC_COUNT;
+  if (ctl[PC_DONE] && !force) return;
+  const int N = ctl[PC_N];
+  if (!(e < N || (e >= W.Nmax && e < W.Nmax + ctl[PC_NL]))) return;
+  const alego_graph_edge* ed = pg_edge_of(L, ctl[PC_SLOT], W.Nmax, e);
+  const double* X = W.X + (size_t)q * W.Nmax * 12;
+  const size_t o = (size_t)q * (W.Nmax + W.Lmax) + e;
+  double r[6], Jf[36], Jt[36];
+  pg_factor(ed->from < 0 ? nullptr : X + (size_t)ed->from * 12, X + (size_t)ed->to * 12, ed->between, ed->variance, r, Jf, Jt);
+  for (int i = 0; i < 6; ++i) W.res[o * 6 + i] = r[i];
+  for (int i = 0; i < 36; ++i) { W.Jf[o * 36 + i] = Jf[i]; W.Jt[o * 36 + i] = Jt[i]; }
+}
+
+// out (6x6) (+)= A^T B; v (6) (+)= A^T r
+DEV_INLINE void pg_atb(const double* A, const double* B, double* out, bool add) {
+  for (int i = 0; i < 6; ++i)
+    for (int j = 0; j < 6; ++j) {
+      double a = add ? out[i * 6 + j] : 0.0;
+      for (int k = 0; k < 6; ++k) a += A[k * 6 + i] * B[k * 6 + j];
+      out[i * 6 + j] = a;
+    }
+}
+DEV_INLINE void pg_atr(const double* A, const double* r, double* v) {
+  for (int i = 0; i < 6; ++i) {
+    double a = v[i];
+    for (int k = 0; k < 6; ++k) a += A[k * 6 + i] * r[k];
+    v[i] = a;
+  }
+}
+
+// grid (node tiles, chunk entries): node k takes edge k (its `to` side), edge k + 1 (its `from` side) and, for the gradient, the loop
+// edges in index order
+__global__ void __launch_bounds__(PG_T) pg_assemble(LmCtx L, PgWork W) {
+  const int q = blockIdx.y, k = blockIdx.x * PG_T + threadIdx.x;
+  const int* ctl = W.ctl + q * PC_COUNT;
+  if (ctl[PC_DONE]) return;
+  const int N = ctl[PC_N], NL = ctl[PC_NL];
+  if (k >= N) return;
+  const size_t eb = (size_t)q * (W.Nmax + W.Lmax), nb = (size_t)q * W.Nmax + k;
+  double D[36], gk[6] = {0, 0, 0, 0, 0, 0};
+  pg_atb(W.Jt + (eb + k) * 36, W.Jt + (eb + k) * 36, D, false);
+  pg_atr(W.Jt + (eb + k) * 36, W.res + (eb + k) * 6, gk);
+  if (k + 1 < N) {
+    double O[36];
+    pg_atb(W.Jf + (eb + k + 1) * 36, W.Jf + (eb + k + 1) * 36, D, true);
+    pg_atr(W.Jf + (eb + k + 1) * 36, W.res + (eb + k + 1) * 6, gk);
+    pg_atb(W.Jt + (eb + k + 1) * 36, W.Jf + (eb + k + 1) * 36, O, false);   // H_{k+1,k}
+    for (int i = 0; i < 36; ++i) W.To[nb * 36 + i] = O[i];
+  }
+  const alego_graph_edge* lp = L.pg_loops + (size_t)ctl[PC_SLOT] * L.pg_loops_cap;
+  for (int l = 0; l < NL; ++l) {
+    if (lp[l].from == k) pg_atr(W.Jf + (eb + W.Nmax + l) * 36, W.res + (eb + W.Nmax + l) * 6, gk);
+    if (lp[l].to == k) pg_atr(W.Jt + (eb + W.Nmax + l) * 36, W.res + (eb + W.Nmax + l) * 6, gk);
+  }
+  for (int i = 0; i < 36; ++i) W.Td[nb * 36 + i] = D[i];
+  for (int i = 0; i < 6; ++i) W.g[nb * 6 + i] = gk[i];
+}
+
+// one lane per chunk entry: D_0 = T_00; L_kk = chol(D_k); L_{k+1,k} = T_{k+1,k} L_kk^-T; D_{k+1} = T_{k+1,k+1} - L_{k+1,k} L_{k+1,k}^T.
+// A pivot that is not positive gives NaN, which pg_update reports as a non-finite step.
+__global__ void __launch_bounds__(64) pg_factor_chain(PgWork W) {
+  const int q = blockIdx.x * 64 + threadIdx.x;
+  if (q >= W.S) return;
+  const int* ctl = W.ctl + q * PC_COUNT;
+  if (ctl[PC_DONE]) return;
+  const int N = ctl[PC_N];
+  double* Td = W.Td + (size_t)q * W.Nmax * 36;
+  double* To = W.To + (size_t)q * W.Nmax * 36;
+  double D[36], Lk[36], Lo[36];
+#pragma unroll
+  for (int i = 0; i < 36; ++i) D[i] = Td[i];
+  for (int k = 0; k < N; ++k) {
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+      double d = D[j * 6 + j];
+#pragma unroll
+      for (int p = 0; p < j; ++p) d -= Lk[j * 6 + p] * Lk[j * 6 + p];
+      d = sqrt(d);
+      Lk[j * 6 + j] = d;
+#pragma unroll
+      for (int i = 0; i < 6; ++i) {
+        if (i < j) Lk[i * 6 + j] = 0.0;
+        if (i > j) {
+          double a = D[i * 6 + j];
+#pragma unroll
+          for (int p = 0; p < j; ++p) a -= Lk[i * 6 + p] * Lk[j * 6 + p];
+          Lk[i * 6 + j] = a / d;
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 36; ++i) Td[(size_t)k * 36 + i] = Lk[i];
+    if (k + 1 == N) break;
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+      for (int c = 0; c < 6; ++c) {
+        double a = To[(size_t)k * 36 + r * 6 + c];
+#pragma unroll
+        for (int j = 0; j < c; ++j) a -= Lo[r * 6 + j] * Lk[c * 6 + j];
+        Lo[r * 6 + c] = a / Lk[c * 6 + c];
+      }
+#pragma unroll
+    for (int i = 0; i < 36; ++i) To[(size_t)k * 36 + i] = Lo[i];
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+      for (int c = 0; c < 6; ++c) {
+        double a = Td[(size_t)(k + 1) * 36 + r * 6 + c];
+#pragma unroll
+        for (int j = 0; j < 6; ++j) a -= Lo[r * 6 + j] * Lo[c * 6 + j];
+        D[r * 6 + c] = a;
+      }
+  }
+}
+
+// y <- L_kk^-1 y (forward) / L_kk^-T y (backward) for one 6-vector
+DEV_INLINE void pg_lsolve(const double* Lk, double* y) {
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    double a = y[i];
+#pragma unroll
+    for (int j = 0; j < i; ++j) a -= Lk[i * 6 + j] * y[j];
+    y[i] = a / Lk[i * 6 + i];
+  }
+}
+DEV_INLINE void pg_ltsolve(const double* Lk, double* y) {
+#pragma unroll
+  for (int i = 5; i >= 0; --i) {
+    double a = y[i];
+#pragma unroll
+    for (int j = i + 1; j < 6; ++j) a -= Lk[j * 6 + i] * y[j];
+    y[i] = a / Lk[i * 6 + i];
+  }
+}
+
+// grid (chunk entries), R lanes rounded up to wavefronts.  Lane 0 sweeps -g, lane 1 + 6 l + i row i of loop edge l's Jacobian
+// (Jf at node `from`, Jt at node `to`, zero elsewhere).  Every lane reads the same factor blocks; its column of Z is its own.
+__global__ void __launch_bounds__(PG_SOLVE_MAX) pg_solve(LmCtx L, PgWork W) {
+  __shared__ double s_y[6 * ALEGO_GRAPH_MAX_LOOPS];
+  const int q = blockIdx.x, c = threadIdx.x;
+  const int* ctl = W.ctl + q * PC_COUNT;
+  if (ctl[PC_DONE]) return;
+  const int N = ctl[PC_N], NL = ctl[PC_NL], n = 6 * NL, R = W.R;
+  const double* Td = W.Td + (size_t)q * W.Nmax * 36;
+  const double* To = W.To + (size_t)q * W.Nmax * 36;
+  double* g = W.g + (size_t)q * W.Nmax * 6;
+  double* Z = W.Z + (size_t)q * W.Nmax * 6 * R;
+  double* Cm = W.C + (size_t)q * 36 * W.Lmax * W.Lmax;
+  const size_t eb = (size_t)q * (W.Nmax + W.Lmax) + W.Nmax;
+  const alego_graph_edge* lp = L.pg_loops + (size_t)ctl[PC_SLOT] * L.pg_loops_cap;
+  if (c < 1 + n) {
+    const int l = c > 0 ? (c - 1) / 6 : 0, row = c > 0 ? (c - 1) % 6 : 0;
+    const int from = c > 0 ? lp[l].from : -1, to = c > 0 ? lp[l].to : -1;
+    const double* jf = W.Jf + (eb + l) * 36 + row * 6;
+    const double* jt = W.Jt + (eb + l) * 36 + row * 6;
+    double y[6] = {0, 0, 0, 0, 0, 0};
+    for (int k = 0; k < N; ++k) {   // forward: y_k = L_kk^-1 (b_k - L_{k,k-1} y_{k-1})
+      double b[6];
+#pragma unroll
+      for (int i = 0; i < 6; ++i) b[i] = c == 0 ? -g[k * 6 + i] : (k == from ? jf[i] : (k == to ? jt[i] : 0.0));
+      if (k > 0) {
+        const double* Lo = To + (size_t)(k - 1) * 36;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+          double a = b[i];
+#pragma unroll
+          for (int j = 0; j < 6; ++j) a -= Lo[i * 6 + j] * y[j];
+          b[i] = a;
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < 6; ++i) y[i] = b[i];
+      pg_lsolve(Td + (size_t)k * 36, y);
+#pragma unroll
+      for (int i = 0; i < 6; ++i) Z[((size_t)k * 6 + i) * R + c] = y[i];
+    }
+    for (int k = N - 1; k >= 0; --k) {   // backward: x_k = L_kk^-T (y_k - L_{k+1,k}^T x_{k+1})
+      double b[6];
+#pragma unroll
+      for (int i = 0; i < 6; ++i) b[i] = Z[((size_t)k * 6 + i) * R + c];
+      if (k + 1 < N) {
+        const double* Lo = To + (size_t)k * 36;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+          double a = b[i];
+#pragma unroll
+          for (int j = 0; j < 6; ++j) a -= Lo[j * 6 + i] * y[j];
+          b[i] = a;
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < 6; ++i) y[i] = b[i];
+      pg_ltsolve(Td + (size_t)k * 36, y);
+#pragma unroll
+      for (int i = 0; i < 6; ++i) Z[((size_t)k * 6 + i) * R + c] = y[i];
+    }
+  }
+  __syncthreads();
+  if (NL > 0) {
+    // capacitance C = I + J Z[:, 1:], right-hand side J z0: entry (a, b), a = (l, row), b = column 1 + b of Z (b = n: column 0)
+    for (int t = c; t < n * (n + 1); t += blockDim.x) {
+      const int a = t / (n + 1), b = t % (n + 1);
+      const int l = a / 6, row = a % 6, col = b < n ? 1 + b : 0;
+      const double* jf = W.Jf + (eb + l) * 36 + row * 6;
+      const double* jt = W.Jt + (eb + l) * 36 + row * 6;
+      const double* zf = Z + (size_t)lp[l].from * 6 * R + col;
+      const double* zt = Z + (size_t)lp[l].to * 6 * R + col;
+      double s = b == a ? 1.0 : 0.0;
+      for (int j = 0; j < 6; ++j) s += jf[j] * zf[(size_t)j * R];
+      for (int j = 0; j < 6; ++j) s += jt[j] * zt[(size_t)j * R];
+      if (b < n) Cm[(size_t)a * n + b] = s; else s_y[a] = s;
+    }
+    __syncthreads();
+    // dense Cholesky of C in place (lower triangle), right-looking, then the two triangular solves for y
+    for (int j = 0; j < n; ++j) {
+      if (c == 0) Cm[(size_t)j * n + j] = sqrt(Cm[(size_t)j * n + j]);
+      __syncthreads();
+      const double d = Cm[(size_t)j * n + j];
+      for (int i = j + 1 + c; i < n; i += blockDim.x) Cm[(size_t)i * n + j] /= d;
+      __syncthreads();
+      const int m = n - j - 1;
+      for (int t = c; t < m * m; t += blockDim.x) {
+        const int i = j + 1 + t / m, k2 = j + 1 + t % m;
+        if (k2 <= i) Cm[(size_t)i * n + k2] -= Cm[(size_t)i * n + j] * Cm[(size_t)k2 * n + j];
+      }
+      __syncthreads();
+    }
+    for (int j = 0; j < n; ++j) {
+      if (c == 0) s_y[j] /= Cm[(size_t)j * n + j];
+      __syncthreads();
+      const double yj = s_y[j];
+      for (int i = j + 1 + c; i < n; i += blockDim.x) s_y[i] -= Cm[(size_t)i * n + j] * yj;
+      __syncthreads();
+    }
+    for (int j = n - 1; j >= 0; --j) {
+      if (c == 0) s_y[j] /= Cm[(size_t)j * n + j];
+      __syncthreads();
+      const double yj = s_y[j];
+      for (int i = c; i < j; i += blockDim.x) s_y[i] -= Cm[(size_t)j * n + i] * yj;
+      __syncthreads();
+    }
+  }
+  // delta = z0 - Z[:, 1:] y, summed in column order
+  for (int t = c; t < N * 6; t += blockDim.x) {
+    const double* z = Z + (size_t)t * R;
+    double s = z[0];
+    for (int b = 0; b < n; ++b) s -= z[1 + b] * s_y[b];
+    g[t] = s;
+  }
+}
+
+// fixed-order workgroup sum / max over PG_T lanes
+DEV_INLINE double pg_block_sum(double v, double* s) {
+  s[threadIdx.x] = v;
+  __syncthreads();
+  for (int h = PG_T / 2; h > 0; h >>= 1) {
+    if ((int)threadIdx.x < h) s[threadIdx.x] += s[threadIdx.x + h];
+    __syncthreads();
+  }
+  const double r = s[0];
+  __syncthreads();
+  return r;
+}
+
+// grid (chunk entries): the step is taken only when every component of delta is finite (the state is left untouched otherwise)
+__global__ void __launch_bounds__(PG_T) pg_update(PgWork W, int max_iters, double step_tol) {
+  __shared__ double s_m[PG_T];
+  __shared__ int s_bad;
+  const int q = blockIdx.x;
+  int* ctl = W.ctl + q * PC_COUNT;
+  if (ctl[PC_DONE]) return;
+  const int N = ctl[PC_N];
+  const double* dl = W.g + (size_t)q * W.Nmax * 6;
+  double* X = W.X + (size_t)q * W.Nmax * 12;
+  if (threadIdx.x == 0) s_bad = 0;
+  __syncthreads();
+  double mx = 0.0;
+  int bad = 0;
+  for (int t = threadIdx.x; t < N * 6; t += PG_T) {
+    const double a = fabs(dl[t]);
+    if (!(a <= 1.79769313486231570815e+308)) bad = 1;
+    mx = fmax(mx, a);
+  }
+  if (bad) s_bad = 1;
+  s_m[threadIdx.x] = mx;
+  __syncthreads();
+  for (int h = PG_T / 2; h > 0; h >>= 1) {
+    if ((int)threadIdx.x < h) s_m[threadIdx.x] = fmax(s_m[threadIdx.x], s_m[threadIdx.x + h]);
+    __syncthreads();
+  }
+  const double step = s_m[0];
+  if (s_bad) {
+    if (threadIdx.x == 0) { ctl[PC_STATUS] = -2; ctl[PC_DONE] = 1; }
+    return;
+  }
+  for (int k = threadIdx.x; k < N; k += PG_T) {
+    double E[12], O[12];
+    pg_exp(dl + (size_t)k * 6, E);
+    pg_compose(X + (size_t)k * 12, E, O);
+    for (int i = 0; i < 12; ++i) X[(size_t)k * 12 + i] = O[i];
+  }
+  if (threadIdx.x == 0) {
+    const int it = ctl[PC_ITERS] + 1;
+    ctl[PC_ITERS] = it;
+    W.dctl[q * PD_COUNT + PD_STEP] = step;
+    if (step < step_tol) { ctl[PC_STATUS] = 2; ctl[PC_DONE] = 1; }
+    else if (it >= max_iters) { ctl[PC_STATUS] = 1; ctl[PC_DONE] = 1; }
+  }
+}
+
+// grid (chunk entries): which = PD_COST0 / PD_COST; lane t sums edges t, t + PG_T, ... (chain first, then loops), then a fixed tree
+__global__ void __launch_bounds__(PG_T) pg_cost(PgWork W, int which) {
+  __shared__ double s_m[PG_T];
+  const int q = blockIdx.x;
+  const int* ctl = W.ctl + q * PC_COUNT;
+  const int N = ctl[PC_N], NL = ctl[PC_NL];
+  const double* res = W.res + (size_t)q * (W.Nmax + W.Lmax) * 6;
+  double s = 0.0;
+  for (int e = threadIdx.x; e < N + NL; e += PG_T) {
+    const double* r = res + (size_t)(e < N ? e : W.Nmax + (e - N)) * 6;
+    for (int i = 0; i < 6; ++i) s += r[i] * r[i];
+  }
+  const double tot = pg_block_sum(s, s_m);
+  if (threadIdx.x == 0) W.dctl[q * PD_COUNT + which] = tot;
+}
+
+__global__ void __launch_bounds__(PG_T) pg_store(LmCtx L, PgWork W) {
+  const int q = blockIdx.y, t = blockIdx.x * PG_T + threadIdx.x;
+  const int* ctl = W.ctl + q * PC_COUNT;
+  if (ctl[PC_STATUS] < 1 || t >= ctl[PC_N] * 12) return;
+  L.pg_est[(size_t)ctl[PC_SLOT] * L.arc_frames_cap * 12 + t] = W.X[(size_t)q * W.Nmax * 12 + t];
+  if (t == 0) L.pg_stat[ctl[PC_SLOT] * 4 + 2] = ctl[PC_N];
+}
+
+// ---- correctPoses (:561-584) for the slots with apply[slot] != 0 ------------------------------------------------------------
+// grid (slots): archived poses and the resident ring's poses <- f32 pose of the estimate; recent_*.clear() as lm_host_reset_window sets it;
+// map -> odom corrected by the last loop edge's ICP correction as lm_apply_correction does; loop_closed_ cleared
+__global__ void __launch_bounds__(PG_T) pg_apply(LmCtx L, const int* apply) {
+  const int slot = blockIdx.x;
+  if (!apply[slot]) return;
+  int* li = L.li + (size_t)slot * LI_COUNT;
+  const int N = L.pg_stat[slot * 4 + 2], nkf = li[LI_NKF];
+  for (int k = threadIdx.x; k < N; k += PG_T) {
+    float kp[6];
+    pg_to_pose6(L.pg_est + ((size_t)slot * L.arc_frames_cap + k) * 12, kp);
+    float* ap = L.arc_pose + ((size_t)slot * L.arc_frames_cap + k) * 8;
+    for (int i = 0; i < 6; ++i) ap[i] = kp[i];
+    if (k < nkf && k >= nkf - L.K) {
+      float* rp = L.kf_pose + ((size_t)slot * L.KR + k % L.KR) * 8;
+      for (int i = 0; i < 6; ++i) rp[i] = kp[i];
+    }
+  }
+  if (threadIdx.x == 0) {
+    li[LI_REC_CNT] = 0; li[LI_DIRTY] = 1; li[LI_UVALID] = 0;
+    double* ld = L.ld + (size_t)slot * LD_COUNT;
+    const float* cf = L.pg_corr + (size_t)slot * 16;
+    double rc[12], R[9], M[9], t[3];
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) rc[r * 4 + c] = (double)cf[r * 4 + c];
+    dq_to_mat(ldq(ld + LD_Q_M2O), R);
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) M[i * 3 + j] = rc[i * 4 + 0] * R[0 * 3 + j] + rc[i * 4 + 1] * R[1 * 3 + j] + rc[i * 4 + 2] * R[2 * 3 + j];
+    for (int i = 0; i < 3; ++i) t[i] = rc[i * 4 + 0] * ld[LD_T_M2O + 0] + rc[i * 4 + 1] * ld[LD_T_M2O + 1] + rc[i * 4 + 2] * ld[LD_T_M2O + 2] + rc[i * 4 + 3];
+    stq(ld + LD_Q_M2O, dq_from_mat(M));
+    for (int i = 0; i < 3; ++i) ld[LD_T_M2O + i] = t[i];
+    L.pg_stat[slot * 4 + 1] = 0;
+  }
+}
+
+// grid (8, 3, slots of the group): lm_store_kf's re-transform of ONE resident frame of every applied slot — the j-th oldest of its
+// min(K, key frames) resident frames — from its raw clouds into kf_tmp_* for the key-frame sort jobs
+__global__ void __launch_bounds__(PG_T) pg_retransform(LmCtx L, const int* apply, int slot0, int j) {
+  const int slot = blockIdx.z + slot0, kind = blockIdx.y;
+  if (!apply[slot]) return;
+  int* li = L.li + (size_t)slot * LI_COUNT;
+  const int nkf = li[LI_NKF], f = nkf - min(L.K, nkf) + j;
+  if (f >= nkf) return;
+  const int ring = f % L.KR;
+  const size_t rs = (size_t)slot * L.KR + ring;
+  float m[3][4];
+  keypose_matrix(L.kf_pose + rs * 8, m);
+  const float4* raw = kind == 0 ? L.kf_raw_c + rs * L.kf_cap_c : (kind == 1 ? L.kf_raw_s + rs * L.kf_cap_s : L.kf_raw_o + rs * L.kf_cap_o);
+  const int cap = kind == 0 ? L.kf_cap_c : (kind == 1 ? L.kf_cap_s : L.kf_cap_o);
+  const int* kc = L.kf_cnt + rs * 4;
+  const int n_c = kc[0], n_s = kc[1], n_o = kc[2];
+  const int n = min(kind == 0 ? n_c : (kind == 1 ? n_s : n_o), cap);
+  float4* dst = kind == 0 ? L.kf_tmp_c + (size_t)slot * L.kf_cap_c : L.kf_tmp_s + (size_t)slot * L.total_cap + (kind == 1 ? 0 : n_s);
+  for (int i = blockIdx.x * PG_T + threadIdx.x; i < n; i += gridDim.x * PG_T) dst[i] = kf_transform(m, raw[i]);
+  if (blockIdx.x == 0 && threadIdx.x == 0 && kind == 0) { li[LI_TMPN_C] = n_c; li[LI_TMPN_S] = n_s + n_o; li[LI_KF_PEND_RING] = ring; li[LI_KF_PENDING] = 1; }
+}
+// the sort jobs ran: the frame is in its ring entry, the voxel lists of an applied slot no longer describe its window.  all: after the
+// flush of the frames the last mapping frame left pending, every slot of the group is done with its sort (as map_update notes it), so the
+// rounds that follow only sort the applied slots' frames
+__global__ void pg_sorted(LmCtx L, const int* apply, int slot0, int n, int all) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= n) return;
+  int* li = L.li + (size_t)(slot0 + s) * LI_COUNT;
+  if (all || apply[slot0 + s]) li[LI_KF_PENDING] = 0;
+  if (apply[slot0 + s]) li[LI_UVALID] = 0;
+}
+
+void launch_pg_apply(const LmCtx& L, const int* apply_dev, int n_slots, hipStream_t st) {
+  ALEGO_LAUNCH(pg_apply, dim3(n_slots), dim3(PG_T), 0, st, L, apply_dev);
+}
+void launch_pg_retransform(const LmCtx& L, const int* apply_dev, int slot0, int n, int j, hipStream_t st) {
+  ALEGO_LAUNCH(pg_retransform, dim3(8, 3, n), dim3(PG_T), 0, st, L, apply_dev, slot0, j);
+}
+void launch_pg_sorted(const LmCtx& L, const int* apply_dev, int slot0, int n, int all, hipStream_t st) {
+  ALEGO_LAUNCH(pg_sorted, dim3((n + 63) / 64), dim3(64), 0, st, L, apply_dev, slot0, n, all);
+}
+
+// one loop edge per lane, at the index the host chose; the last entry of a slot leaves its correction and the loop count
+__global__ void pg_append(LmCtx L, const PgAppend* a, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  L.pg_loops[(size_t)a[i].slot * L.pg_loops_cap + a[i].index] = a[i].e;
+  if (a[i].last) {
+    for (int k = 0; k < 16; ++k) L.pg_corr[(size_t)a[i].slot * 16 + k] = a[i].corr[k];
+    L.pg_stat[a[i].slot * 4 + 0] = a[i].index + 1;
+    L.pg_stat[a[i].slot * 4 + 1] = 1;
+  }
+}
+
+// ---- host -------------------------------------------------------------------------------------------------------------------
+struct PgCtx {
+  long long budget = PG_BUDGET_DEFAULT;
+  char* buf = nullptr;
+  size_t cap = 0;
+  int* apply = nullptr;      // [n_slots]
+  int apply_cap = 0;
+  PgAppend* stage = nullptr; // loop edges on their way to pg_append
+  size_t stage_cap = 0;
+};
+void graph_ctx_destroy(PgCtx* C) {
+  if (!C) return;
+  if (C->buf) (void)guard_free(C->buf);
+  if (C->apply) (void)guard_free(C->apply);
+  if (C->stage) (void)guard_free(C->stage);
+  delete C;
+}
+void graph_ctx_set_budget(PgCtx** pc, long long bytes) {
+  if (!*pc) *pc = new PgCtx();
+  (*pc)->budget = std::max(1LL, bytes);
+}
+
+namespace {
+size_t pg_align(size_t b) { return (b + 255) & ~(size_t)255; }
+// bytes of a chunk of S entries; with base != nullptr the pointers are laid out too
+size_t pg_layout(PgWork* W, char* base, int S, int Nmax, int Lmax) {
+  size_t o = 0;
+  const size_t s = (size_t)S, N = (size_t)Nmax, E = (size_t)Nmax + Lmax, R = 1 + 6 * (size_t)Lmax;
+  auto take = [&](auto** p, size_t count) {
+    using T = std::remove_pointer_t<std::remove_pointer_t<decltype(p)>>;
+    if (base) *p = (T*)(base + o);
+    o += pg_align(count * sizeof(T));
+  };
+  W->S = S; W->Nmax = Nmax; W->Lmax = Lmax; W->R = (int)R;
+  take(&W->ctl, s * PC_COUNT); take(&W->dctl, s * PD_COUNT); take(&W->X, s * N * 12);
+  take(&W->res, s * E * 6); take(&W->Jf, s * E * 36); take(&W->Jt, s * E * 36);
+  take(&W->Td, s * N * 36); take(&W->To, s * N * 36); take(&W->g, s * N * 6);
+  take(&W->Z, s * N * 6 * R); take(&W->C, s * 36 * (size_t)Lmax * Lmax);
+  return o;
+}
+bool pg_finite_edge(const alego_graph_edge& e) {
+  for (int k = 0; k < 12; ++k) if (!std::isfinite(e.between[k])) return false;
+  for (int k = 0; k < 6; ++k) if (!(e.variance[k] > 0.0) || !std::isfinite(e.variance[k])) return false;
+  return true;
+}
+int pg_fail(std::string* err, const char* msg, int rc) { *err = msg; return rc; }
+// the counters of one slot: arc4 = LmCtx::arc_stat, pg4 = LmCtx::pg_stat
+int pg_read_slot(const LmCtx& L, int slot, int* arc4, int* pg4, std::string* err) {
+  if (hipMemcpy(arc4, L.arc_stat + (size_t)slot * 4, 4 * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(pg4, L.pg_stat + (size_t)slot * 4, 4 * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return pg_fail(err, "graph: device read failed", ALEGO_ERR_HIP);
+  return 0;
+}
+int pg_read_stats(const LmCtx& L, int n_slots, std::vector<int>* arc, std::vector<int>* pg, std::string* err) {
+  arc->resize((size_t)n_slots * 4); pg->resize((size_t)n_slots * 4);
+  if (hipMemcpy(arc->data(), L.arc_stat, arc->size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(pg->data(), L.pg_stat, pg->size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return pg_fail(err, "graph: device read failed", ALEGO_ERR_HIP);
+  return 0;
+}
+}  // namespace
+
+int graph_status(const LmCtx& L, int slot, int* out4, std::string* err) {
+  int arc[4], pg[4];
+  if (int r = pg_read_slot(L, slot, arc, pg, err)) return r;
+  out4[0] = arc[0]; out4[1] = pg[0]; out4[2] = pg[1]; out4[3] = pg[2];
+  return 0;
+}
+
+int graph_get_edges(const LmCtx& L, int slot, int kind, int first, int n, alego_graph_edge* out, std::string* err) {
+  int arc[4], pg[4];
+  if (int r = pg_read_slot(L, slot, arc, pg, err)) return r;
+  const int have = kind == 0 ? arc[0] : pg[0];
+  if ((kind != 0 && kind != 1) || first < 0 || n < 0 || first > have || n > have - first || (n > 0 && !out)) return pg_fail(err, "graph_get_edges: range beyond the stored edges", ALEGO_ERR_ARG);
+  if (n == 0) return 0;
+  const alego_graph_edge* src = kind == 0 ? L.pg_chain + (size_t)slot * L.arc_frames_cap + first : L.pg_loops + (size_t)slot * L.pg_loops_cap + first;
+  if (hipMemcpy(out, src, (size_t)n * sizeof(alego_graph_edge), hipMemcpyDeviceToHost) != hipSuccess) return pg_fail(err, "graph_get_edges: copy failed", ALEGO_ERR_HIP);
+  return 0;
+}
+
+int graph_set_edges(const LmCtx& L, int slot, int first, int n, const alego_graph_edge* chain, std::string* err) {
+  int arc[4], pg[4];
+  if (int r = pg_read_slot(L, slot, arc, pg, err)) return r;
+  const int have = arc[0];
+  if (first < 0 || n < 0 || first > have || n > have - first || (n > 0 && !chain)) return pg_fail(err, "graph_set_edges: range beyond the archived frames", ALEGO_ERR_ARG);
+  for (int i = 0; i < n; ++i) {
+    if (chain[i].to != first + i || chain[i].from != first + i - 1) return pg_fail(err, "graph_set_edges: chain edge i is the prior (from = -1, to = 0) or i - 1 -> i", ALEGO_ERR_ARG);
+    if (!pg_finite_edge(chain[i])) return pg_fail(err, "graph_set_edges: measurement not finite or variance not positive and finite", ALEGO_ERR_ARG);
+  }
+  if (n == 0) return 0;
+  if (hipMemcpy(L.pg_chain + (size_t)slot * L.arc_frames_cap + first, chain, (size_t)n * sizeof(alego_graph_edge), hipMemcpyHostToDevice) != hipSuccess)
+    return pg_fail(err, "graph_set_edges: copy failed", ALEGO_ERR_HIP);
+  return 0;
+}
+
+// appends every entry (validated as a whole first: nothing is written on an error)
+int graph_append(PgCtx** pc, const LmCtx& L, int n_slots, const std::vector<PgAppend>& in, hipStream_t st, std::string* err) {
+  if (in.empty()) return 0;
+  if (!*pc) *pc = new PgCtx();
+  PgCtx* C = *pc;
+  std::vector<int> arc, pg;
+  if (int r = pg_read_stats(L, n_slots, &arc, &pg, err)) return r;
+  std::vector<PgAppend> a = in;
+  std::vector<int> cnt(n_slots), last(n_slots, -1);
+  for (int s = 0; s < n_slots; ++s) cnt[s] = pg[s * 4];
+  for (size_t i = 0; i < a.size(); ++i) {
+    const alego_graph_edge& e = a[i].e;
+    const int nf = arc[a[i].slot * 4];
+    if (e.from < 0 || e.to < 0 || e.from >= nf || e.to >= nf || e.from == e.to) return pg_fail(err, "graph: loop edge ids outside the archived frames, or from == to", ALEGO_ERR_ARG);
+    if (!pg_finite_edge(e)) return pg_fail(err, "graph: measurement not finite or variance not positive and finite", ALEGO_ERR_ARG);
+    if (cnt[a[i].slot] >= L.pg_loops_cap) return pg_fail(err, "graph: max_loops loop edges are stored already", ALEGO_ERR_CAPACITY);
+    a[i].index = cnt[a[i].slot]++;
+    a[i].last = 0;
+    last[a[i].slot] = (int)i;
+  }
+  for (int s = 0; s < n_slots; ++s) if (last[s] >= 0) a[last[s]].last = 1;
+  if (a.size() > C->stage_cap) {
+    if (C->stage) (void)guard_free(C->stage);
+    C->stage = nullptr; C->stage_cap = 0;
+    void* p = nullptr;
+    if (guard_malloc(&p, a.size() * sizeof(PgAppend)) != hipSuccess) return pg_fail(err, "graph: staging allocation failed", ALEGO_ERR_HIP);
+    C->stage = (PgAppend*)p; C->stage_cap = a.size();
+  }
+  hipError_t e = hipMemcpy(C->stage, a.data(), a.size() * sizeof(PgAppend), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    ALEGO_LAUNCH(pg_append, dim3(((int)a.size() + 63) / 64), dim3(64), 0, st, L, (const PgAppend*)C->stage, (int)a.size());
+    e = hipStreamSynchronize(st);
+  }
+  if (e != hipSuccess) return pg_fail(err, "graph: append failed", ALEGO_ERR_HIP);
+  return 0;
+}
+
+int graph_get_estimate(const LmCtx& L, int slot, int first, int n, double* poses12, std::string* err) {
+  int arc[4], pg[4];
+  if (int r = pg_read_slot(L, slot, arc, pg, err)) return r;
+  const int have = pg[2];
+  if (first < 0 || n < 0 || first > have || n > have - first || (n > 0 && !poses12)) return pg_fail(err, "graph_get_estimate: range beyond the poses of the last optimise", ALEGO_ERR_ARG);
+  if (n && hipMemcpy(poses12, L.pg_est + ((size_t)slot * L.arc_frames_cap + first) * 12, (size_t)n * 12 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+    return pg_fail(err, "graph_get_estimate: copy failed", ALEGO_ERR_HIP);
+  return 0;
+}
+
+// Gauss-Newton for the listed slots, chunk by chunk under the budget; out[i] belongs to slots[i].  apply_out[slot] = 1 for the slots whose
+// correction is to be applied (converged, loop_closed_ set, opts.apply): the caller runs correctPoses for them.
+int graph_optimize(PgCtx** pc, const LmCtx& L, int n_slots, const int* slots, int n, const alego_graph_opts& opt, alego_graph_result* out,
+                   std::vector<int>* apply_out, hipStream_t st, std::string* err) {
+  if (!*pc) *pc = new PgCtx();
+  PgCtx* C = *pc;
+  std::vector<int> arc, pg;
+  if (int r = pg_read_stats(L, n_slots, &arc, &pg, err)) return r;
+  apply_out->assign(n_slots, 0);
+  std::vector<int> todo;
+  int Nmax = 1, Lmax = 0;
+  for (int i = 0; i < n; ++i) {
+    const int s = slots[i];
+    alego_graph_result& r = out[i];
+    std::memset(&r, 0, sizeof(r));
+    r.n_poses = arc[s * 4]; r.n_loops = pg[s * 4];
+    if (arc[s * 4 + 1] > 0) { r.status = -1; continue; }
+    if (r.n_poses == 0) { r.status = 0; continue; }
+    todo.push_back(i);
+    Nmax = std::max(Nmax, r.n_poses); Lmax = std::max(Lmax, r.n_loops);
+  }
+  if (todo.empty()) return 0;
+  PgWork W;
+  const size_t per = pg_layout(&W, nullptr, 1, Nmax, Lmax) + 16 * 256;
+  const int chunk = (int)std::max<long long>(1, std::min<long long>((long long)todo.size(), C->budget / (long long)per));
+  const size_t need = pg_layout(&W, nullptr, chunk, Nmax, Lmax);
+  if (need > C->cap) {
+    if (C->buf) (void)guard_free(C->buf);
+    C->buf = nullptr; C->cap = 0;
+    void* p = nullptr;
+    if (guard_malloc(&p, need) != hipSuccess) return pg_fail(err, "graph_optimize: scratch allocation failed (lower the budget or max_loops)", ALEGO_ERR_HIP);
+    C->buf = (char*)p; C->cap = need;
+  }
+  const int R = 1 + 6 * Lmax, lanes = std::max(64, (R + 63) / 64 * 64);
+  std::vector<int> ctl;
+  std::vector<double> dctl;
+  for (size_t c0 = 0; c0 < todo.size(); c0 += chunk) {
+    const int S = (int)std::min<size_t>(chunk, todo.size() - c0);
+    pg_layout(&W, C->buf, S, Nmax, Lmax);
+    ctl.assign((size_t)S * PC_COUNT, 0);
+    for (int q = 0; q < S; ++q) {
+      const alego_graph_result& r = out[todo[c0 + q]];
+      ctl[q * PC_COUNT + PC_N] = r.n_poses; ctl[q * PC_COUNT + PC_NL] = r.n_loops; ctl[q * PC_COUNT + PC_SLOT] = slots[todo[c0 + q]];
+    }
+    if (hipMemcpyAsync(W.ctl, ctl.data(), ctl.size() * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemsetAsync(W.dctl, 0, (size_t)S * PD_COUNT * sizeof(double), st) != hipSuccess) return pg_fail(err, "graph_optimize: upload failed", ALEGO_ERR_HIP);
+    const dim3 gn((Nmax + PG_T - 1) / PG_T, S), ge((Nmax + Lmax + PG_T - 1) / PG_T, S);
+    ALEGO_LAUNCH(pg_init, gn, dim3(PG_T), 0, st, L, W);
+    for (int it = 0; it < opt.max_iters; ++it) {
+      ALEGO_LAUNCH(pg_linearize, ge, dim3(PG_T), 0, st, L, W, 0);
+      if (it == 0) ALEGO_LAUNCH(pg_cost, dim3(S), dim3(PG_T), 0, st, W, (int)PD_COST0);
+      ALEGO_LAUNCH(pg_assemble, gn, dim3(PG_T), 0, st, L, W);
+      ALEGO_LAUNCH(pg_factor_chain, dim3((S + 63) / 64), dim3(64), 0, st, W);
+      ALEGO_LAUNCH(pg_solve, dim3(S), dim3(lanes), 0, st, L, W);
+      ALEGO_LAUNCH(pg_update, dim3(S), dim3(PG_T), 0, st, W, opt.max_iters, opt.step_tol);
+      // one read per iteration for the whole chunk: stop launching once every slot of it has finished
+      if (hipMemcpyAsync(ctl.data(), W.ctl, ctl.size() * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+        return pg_fail(err, "graph_optimize: a kernel failed", ALEGO_ERR_HIP);
+      bool all = true;
+      for (int q = 0; q < S; ++q) all = all && ctl[q * PC_COUNT + PC_DONE];
+      if (all) break;
+    }
+    ALEGO_LAUNCH(pg_linearize, ge, dim3(PG_T), 0, st, L, W, 1);
+    ALEGO_LAUNCH(pg_cost, dim3(S), dim3(PG_T), 0, st, W, (int)PD_COST);
+    ALEGO_LAUNCH(pg_store, dim3((Nmax * 12 + PG_T - 1) / PG_T, S), dim3(PG_T), 0, st, L, W);
+    dctl.assign((size_t)S * PD_COUNT, 0.0);
+    if (hipMemcpyAsync(ctl.data(), W.ctl, ctl.size() * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(dctl.data(), W.dctl, dctl.size() * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+      return pg_fail(err, "graph_optimize: a kernel failed", ALEGO_ERR_HIP);
+    for (int q = 0; q < S; ++q) {
+      alego_graph_result& r = out[todo[c0 + q]];
+      const int s = slots[todo[c0 + q]];
+      r.status = ctl[q * PC_COUNT + PC_STATUS]; r.iterations = ctl[q * PC_COUNT + PC_ITERS];
+      r.cost0 = dctl[q * PD_COUNT + PD_COST0]; r.cost = dctl[q * PD_COUNT + PD_COST]; r.last_step = dctl[q * PD_COUNT + PD_STEP];
+      if (r.status == 2 && opt.apply && pg[s * 4 + 1]) { r.applied = 1; (*apply_out)[s] = 1; }
+    }
+  }
+  return 0;
+}
+
+// the applied slots' flags on the device (kept with the context)
+int graph_upload_apply(PgCtx* C, const std::vector<int>& apply, const int** dev, hipStream_t st, std::string* err) {
+  if ((int)apply.size() > C->apply_cap) {
+    if (C->apply) (void)guard_free(C->apply);
+    C->apply = nullptr; C->apply_cap = 0;
+    void* p = nullptr;
+    if (guard_malloc(&p, apply.size() * sizeof(int)) != hipSuccess) return pg_fail(err, "graph_optimize: allocation failed", ALEGO_ERR_HIP);
+    C->apply = (int*)p; C->apply_cap = (int)apply.size();
+  }
+  if (hipMemcpyAsync(C->apply, apply.data(), apply.size() * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+    return pg_fail(err, "graph_optimize: upload failed", ALEGO_ERR_HIP);
+  *dev = C->apply;
+  return 0;
+}
+
+// host only: the whitened errors and Jacobian blocks of pg_math.h for a list of edges over n_poses poses
+int graph_residuals_host(const double* poses12, int n_poses, const alego_graph_edge* edges, int n_edges, double* whitened6, double* jac_from36, double* jac_to36) {
+  for (int i = 0; i < n_edges; ++i) {
+    const alego_graph_edge& e = edges[i];
+    if (e.to < 0 || e.to >= n_poses || e.from < -1 || e.from >= n_poses || e.from == e.to || !pg_finite_edge(e)) return ALEGO_ERR_ARG;
+  }
+  for (int i = 0; i < n_edges; ++i) {
+    const alego_graph_edge& e = edges[i];
+    double r[6], Jf[36], Jt[36];
+    pg_factor(e.from < 0 ? nullptr : poses12 + (size_t)e.from * 12, poses12 + (size_t)e.to * 12, e.between, e.variance, r, Jf, Jt);
+    if (whitened6) std::memcpy(whitened6 + (size_t)i * 6, r, sizeof(r));
+    if (jac_from36) std::memcpy(jac_from36 + (size_t)i * 36, Jf, sizeof(Jf));
+    if (jac_to36) std::memcpy(jac_to36 + (size_t)i * 36, Jt, sizeof(Jt));
+  }
+  return 0;
+}

@@ -43,6 +43,8 @@ enum {
   LD_COUNT = 48
 };
 
+struct alego_graph_edge;   // include/alego_mi355x.h
+
 struct GridGeom { int ox, oy, oz; float inv; int gx, gy, gz, ncell; };   // cell of x: floorf(x * inv) - ox (lm_grid_build)
 
 
@@ -143,6 +145,15 @@ struct LmCtx {
   double* arc_stamp;                              // [slot][arc_frames_cap] stamp of each frame (detectLoopClosure's key-pose time, :782)
   int* arc_stamped;                               // [slot] 1: DevCtx::scan_stamp holds the slot's scan stamps (alego_scan_process / alego_lo_process);
                                                   // 0: the stamp is (LI_FRAME - 1) * scan_period
+  // key-pose graph next to the archive (alego_graph_enable; pg_loops_cap == 0: off, nothing is launched or allocated): the prior and
+  // the odometry chain recorded by map_archive as frames are appended, the loop edges the host added, the last optimise's estimate
+  int pg_loops_cap;                               // loop edges per slot
+  double pg_odom_var[6];                          // variances of the prior and of every odometry edge (laserMapping.cpp:68-70)
+  alego_graph_edge* pg_chain;                     // [slot][arc_frames_cap] edge i: the prior (i = 0, from = -1) or i - 1 -> i
+  alego_graph_edge* pg_loops;                     // [slot][pg_loops_cap]
+  float* pg_corr;                                 // [slot][16] ICP correction of the last loop edge added (correctPoses :579-580)
+  int* pg_stat;                                   // [slot][4] loop edges stored, loop_closed_ (a loop edge was added since the last apply), poses of the estimate, -
+  double* pg_est;                                 // [slot][arc_frames_cap][12] Pose3 estimate of the slot's last optimise, row-major [R | t]
 };
 
 #endif

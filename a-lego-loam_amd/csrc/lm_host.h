@@ -56,4 +56,8 @@ int lm_host_map_keyposes(LmHost* lm, int slot, alego_point* out, int cap, std::s
 int lm_host_get_local_map(LmHost* lm, int slot, alego_point* corner, int corner_cap, alego_point* surf, int surf_cap, int* n_out, std::string* err);
 int lm_host_voxel_grid(LmHost* lm, hipStream_t st, const alego_point* pts, int n, float leaf, alego_point* out, int cap, std::string* err);
 int lm_host_set_gv_small_max(LmHost* lm, int v);
+// the key-pose graph (alego_graph_*; kernels_graph.hip)
+int lm_host_graph_enable(LmHost* lm, int max_loops, const double* odom_var6, std::string* err);
+// correctPoses for the slots with apply[slot] != 0 (apply_dev: the same flags on the device); n_poses_max: most key frames of an applied slot
+int lm_host_graph_apply(LmHost* lm, const std::vector<int>& apply, const int* apply_dev, int n_poses_max, std::string* err);
 #endif

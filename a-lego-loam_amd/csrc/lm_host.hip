@@ -27,6 +27,9 @@ struct MapWork { int* items; int* count; int cap; };   // kernels_map.hip
 void launch_map_update(const DevCtx& d, const LmCtx& L, const MapWork& W, hipStream_t st);
 void launch_map_accum(const DevCtx& d, const LmCtx& L, const MapWork& W, hipStream_t st);
 void launch_lm_apply_correction(const DevCtx& d, const LmCtx& L, int slot, const double* rc_dev, hipStream_t st);
+void launch_pg_apply(const LmCtx& L, const int* apply_dev, int n_slots, hipStream_t st);   // kernels_graph.hip
+void launch_pg_retransform(const LmCtx& L, const int* apply_dev, int slot0, int n, int j, hipStream_t st);
+void launch_pg_sorted(const LmCtx& L, const int* apply_dev, int slot0, int n, int all, hipStream_t st);
 
 struct LmHost {
   alego_params P;
@@ -669,6 +672,57 @@ int lm_host_map_mark_stamped(LmHost* lm, int slot, hipStream_t st) {
   return lm->L.arc_frames_cap > 0 && hipMemcpyAsync(lm->L.arc_stamped + slot, &one, sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess ? ALEGO_ERR_HIP : 0;
 }
 const LmCtx* lm_host_ctx(LmHost* lm) { return &lm->L; }
+
+// ---- the key-pose graph (alego_graph_*) ----
+int lm_host_graph_enable(LmHost* lm, int max_loops, const double* odom_var6, std::string* err) {
+  LmCtx& L = lm->L;
+  if (L.arc_frames_cap <= 0) { *err = "graph_enable: the key-frame archive is off (alego_map_enable first)"; return ALEGO_ERR_ARG; }
+  if (L.pg_loops_cap > 0) { *err = "graph_enable: already enabled"; return ALEGO_ERR_ARG; }
+  if (max_loops < 1 || max_loops > ALEGO_GRAPH_MAX_LOOPS) { *err = "graph_enable: max_loops out of range"; return ALEGO_ERR_ARG; }
+  static const double dflt[6] = {1e-6, 1e-6, 1e-6, 1e-8, 1e-8, 1e-6};   // laserMapping.cpp:68-70
+  const double* v = odom_var6 ? odom_var6 : dflt;
+  for (int k = 0; k < 6; ++k) if (!(v[k] > 0.0) || !(v[k] < 1e300)) { *err = "graph_enable: variances must be positive and finite"; return ALEGO_ERR_ARG; }
+  // the chain starts with the prior on frame 0: the graph has to exist before the first key frame
+  std::vector<int> li((size_t)lm->n_slots * LI_COUNT);
+  if (hipMemcpy(li.data(), L.li, li.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { *err = "graph_enable: device read failed"; return ALEGO_ERR_HIP; }
+  for (int s = 0; s < lm->n_slots; ++s) if (li[(size_t)s * LI_COUNT + LI_NKF] != 0) { *err = "graph_enable: call it before the first key frame is saved"; return ALEGO_ERR_ARG; }
+  const size_t B = lm->n_slots, F = L.arc_frames_cap;
+  LmCtx T = L;
+  bool ok = A(lm, &T.pg_chain, B * F, err) && A(lm, &T.pg_loops, B * max_loops, err) && A(lm, &T.pg_corr, B * 16, err) && A(lm, &T.pg_stat, B * 4, err) &&
+            A(lm, &T.pg_est, B * F * 12, err);
+  if (!ok) return ALEGO_ERR_HIP;
+  for (int k = 0; k < 6; ++k) T.pg_odom_var[k] = v[k];
+  T.pg_loops_cap = max_loops;
+  L = T;
+  return 0;
+}
+
+int lm_host_graph_apply(LmHost* lm, const std::vector<int>& apply, const int* apply_dev, int n_poses_max, std::string* err) {
+  const LmCtx& L = lm->L;
+  for (hipStream_t s : lm->st) if (hipStreamSynchronize(s) != hipSuccess) { *err = "graph apply: a stream failed"; return ALEGO_ERR_HIP; }
+  launch_pg_apply(L, apply_dev, lm->n_slots, lm->st[0]);
+  if (hipStreamSynchronize(lm->st[0]) != hipSuccess) { *err = "graph apply: pose write failed"; return ALEGO_ERR_HIP; }
+  // every resident frame of every applied slot goes through kf_tmp_* and the key-frame sort jobs, oldest first, one frame of every slot of
+  // a stream group per round (what alego_lm_set_keypose does for one frame of one slot)
+  const int rounds = std::min(L.K, n_poses_max);
+  for (size_t g = 0; g < lm->st.size(); ++g) {
+    const int s0 = (int)g * lm->gsize, n = std::min(lm->gsize, lm->n_slots - s0);
+    bool any = false;
+    for (int s = s0; s < s0 + n; ++s) any = any || apply[s];
+    if (!any) continue;
+    hipStream_t st = lm->st[g];
+    // a key frame saved by the last mapping frame may still wait in kf_tmp_* for its sort: flush it before the buffer is reused
+    if (int r = vox_run(lm->vk[g], st, err)) return r;
+    launch_pg_sorted(L, apply_dev, s0, n, 1, st);
+    for (int j = 0; j < rounds; ++j) {
+      launch_pg_retransform(L, apply_dev, s0, n, j, st);
+      if (int r = vox_run(lm->vk[g], st, err)) return r;
+      launch_pg_sorted(L, apply_dev, s0, n, 0, st);
+    }
+  }
+  for (hipStream_t s : lm->st) if (hipStreamSynchronize(s) != hipSuccess) { *err = "graph apply: key-frame transform failed"; return ALEGO_ERR_HIP; }
+  return 0;
+}
 int lm_host_map_get_keyframe(LmHost* lm, int slot, int id, alego_keyframe* out, std::string* err) {
   int st[4];
   if (int r = map_stat(lm, slot, st, err)) return r;

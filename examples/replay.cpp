@@ -17,6 +17,11 @@
 //       keeps the archive on too and calls alego_loop_search every EVERY scans (performLoopClosure, laserMapping.cpp:652-733, on the
 //       device); every accepted constraint prints one line "loop: scan K slot S latest L closest C fitness F".  A host with a pose
 //       graph would add the Between factor here and write the corrected poses back.
+//   either source + --close-loops EVERY [--max-loops N]
+//       the whole loop closure on the device: the key-pose graph next to the archive (alego_graph_enable), and every EVERY scans
+//       alego_loop_search -> alego_graph_add_loops -> alego_graph_optimize with apply = 1 (correctPoses, :561-584).  Every applied
+//       correction prints one line "closed: scan K slot S poses N loops L iterations I cost C0 -> C"; with --save-map the map comes
+//       out at the corrected poses.
 // Every scan goes through ImageProjection -> LaserOdometry -> LaserMapping with one alego_scan_process call, as a single nodelet
 // manager would run them (launch/test.launch:6-10); every new key frame is pulled across the boundary the way the reference's
 // pose-graph thread reads cloud_keyposes_6d_ (laserMapping.cpp:586-596); one JSON line with the final poses is printed.
@@ -36,7 +41,7 @@ extern "C" int alego_synth_scan(const alego_params* P, int stream, long scan_ind
 int main(int argc, char** argv) {
   std::string bag_path, topic = "/lslidar_point_cloud", map_dir;
   float map_leaf = 0.f;
-  int map_frames = 4096, map_points = 1 << 24, loop_every = 0;
+  int map_frames = 4096, map_points = 1 << 24, loop_every = 0, close_every = 0, max_loops = 16;
   bool list_only = false, standalone = false;
   long max_scans = -1;
   int n_scan = 16, horizon = -1;
@@ -56,6 +61,8 @@ int main(int argc, char** argv) {
     else if (a == "--map-frames") map_frames = std::atoi(val());
     else if (a == "--map-points") map_points = std::atoi(val());
     else if (a == "--loop-search") loop_every = std::atoi(val());
+    else if (a == "--close-loops") close_every = std::atoi(val());
+    else if (a == "--max-loops") max_loops = std::atoi(val());
     else pos.push_back(argv[i]);
   }
   alego_bag* bag = nullptr;
@@ -97,8 +104,11 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "alego_create failed (%d): there is no CPU fallback, an MI355X is required\n", rc);
     return 1;
   }
-  if ((!map_dir.empty() || loop_every > 0) && alego_map_enable(h, map_frames, map_points) != ALEGO_OK) {
+  if ((!map_dir.empty() || loop_every > 0 || close_every > 0) && alego_map_enable(h, map_frames, map_points) != ALEGO_OK) {
     std::fprintf(stderr, "map_enable: %s\n", alego_last_error(h)); alego_destroy(h); return 1;
+  }
+  if (close_every > 0 && alego_graph_enable(h, max_loops, nullptr) != ALEGO_OK) {
+    std::fprintf(stderr, "graph_enable: %s\n", alego_last_error(h)); alego_destroy(h); return 1;
   }
   alego_pose odom{}, mapped{};
   int key_frames = 0, last_flags = 0, dropped = 0;
@@ -129,6 +139,17 @@ int main(int argc, char** argv) {
       alego_loop_result lr{};
       if (alego_loop_search(h, &slot, 1, &lr) != ALEGO_OK) { std::fprintf(stderr, "loop_search: %s\n", alego_last_error(h)); alego_destroy(h); return 1; }
       if (lr.status == 2) std::printf("loop: scan %ld slot %d latest %d closest %d fitness %.9g\n", k, slot, lr.latest_id, lr.closest_id, lr.fitness);
+    }
+    if (close_every > 0 && (k + 1) % close_every == 0) {   // search -> add the Between factor -> optimise and correct, all on the device
+      const int32_t slot = 0;
+      alego_loop_result lr{};
+      alego_graph_result gr{};
+      const alego_graph_opts go{0, 0.0, 1};
+      if (alego_loop_search(h, &slot, 1, &lr) != ALEGO_OK || alego_graph_add_loops(h, &slot, 1, &lr) != ALEGO_OK ||
+          (lr.status == 2 && alego_graph_optimize(h, &slot, 1, &go, &gr) != ALEGO_OK)) {
+        std::fprintf(stderr, "close loops: %s\n", alego_last_error(h)); alego_destroy(h); return 1;
+      }
+      if (gr.applied) std::printf("closed: scan %ld slot %d poses %d loops %d iterations %d cost %.9g -> %.9g\n", k, slot, gr.n_poses, gr.n_loops, gr.iterations, gr.cost0, gr.cost);
     }
   }
   std::printf("{\"scans\": %ld, \"dropped\": %d, \"flags\": %d, \"key_frames\": %d, \"resident_key_frames\": %d, "

@@ -388,6 +388,87 @@ int alego_loop_constraint(const float correction[16], const float latest_pose6[6
  * ((dx dx + dy dy) + dz dz), the lowest index on ties; idx = -1, d2 = FLT_MAX for an empty target or a non-finite query */
 int alego_debug_nn1(alego_handle* h, const alego_point* tgt, int32_t n_tgt, const alego_point* queries, int32_t n_q, int32_t* idx, float* d2);
 
+/* ---- the key-pose graph (saveKeyFramesAndFactor :491-559, correctPoses :561-584, the Between factor of :716-733), kept per slot next to
+ * the key-frame archive and optimised on the device (needs alego_map_enable)
+ *   nodes     the archived key frames 0 .. N-1 of a slot as Pose3
+ *   prior     on node 0 (:495): key pose 0 as it was archived
+ *   odometry  edge i-1 -> i for every later frame (:510-512): between(pose[i-1], pose[i]) in f64, both poses Pose3(Rot3::RzRyRx(roll, pitch,
+ *             yaw), xyz) of the ARCHIVED f32 key poses — pose[i-1] as it stands when frame i is appended (the reference's pre_pose, :500)
+ *             and pose[i] the new frame's f32 pose (the reference uses the f64 q/t_map2laser_ there; the f32 image is what it stores and
+ *             what alego_lm_add_keyframe knows, and the difference is below f32 rounding of the pose).  Recorded by the archive's kernel.
+ *   loops     edge from -> to with a measured Pose3 and six variances, added by the host from alego_loop_search / alego_loop_closure_icp
+ *   noise     diagonal variances per edge in GTSAM's tangent order: rotation x y z, then translation x y z.  The default of the prior and
+ *             the odometry is {1e-6, 1e-6, 1e-6, 1e-8, 1e-8, 1e-6} (:68-70) — in that order the two 1e-8 entries weigh translation x and
+ *             y; the quirk is kept.
+ *   error     Logmap(measured^-1 (x_from^-1 x_to)), prior: Logmap(prior^-1 x_0), with the full SE(3) Logmap (GTSAM_POSE3_EXPMAP /
+ *             GTSAM_ROT3_EXPMAP, GTSAM's default since 4.0.3); update x <- x Expmap(delta)
+ * alego_graph_optimize computes the MINIMISER of the sum of squared whitened errors by plain Gauss-Newton in f64 (no damping), started
+ * from the archived poses as they are now.  iSAM2 as the reference drives it (relinearizeSkip 1, two update() calls per factor) takes
+ * Gauss-Newton steps towards the same point without iterating to it: the contract here is the optimum, not iSAM2's iterate. */
+#define ALEGO_GRAPH_MAX_LOOPS 64   /* largest max_loops of alego_graph_enable */
+typedef struct alego_graph_edge {
+  int32_t from, to;        /* from = -1: the prior on node `to` (between = the prior pose) */
+  double between[12];      /* the measurement, row-major 3x4 [R | t] */
+  double variance[6];      /* rotation x y z, translation x y z */
+} alego_graph_edge;
+/* Once, after alego_map_enable and before the first key frame (else ALEGO_ERR_ARG).  max_loops in [1, ALEGO_GRAPH_MAX_LOOPS]: loop edges a slot
+ * can hold.  odom_variance: of the prior and of every recorded odometry edge; NULL = the default above.  Device memory per slot:
+ * max_keyframes * (152 + 96) B + max_loops * 152 B + 80 B.  Without this call nothing of the graph is allocated or launched. */
+int alego_graph_enable(alego_handle* h, int32_t max_loops, const double odom_variance[6]);
+/* out = {chain edges (one per archived frame), loop edges stored, loop_closed_ (a loop edge was added since the last apply), poses of
+ * the estimate of the last optimise} */
+int alego_graph_status(alego_handle* h, int slot, int32_t out[4]);
+/* edges first .. first + n - 1 of `slot`: kind 0 the chain (edge 0 is the prior, edge i the odometry edge i-1 -> i; one per archived frame),
+ * kind 1 the loop edges in the order they were added */
+int alego_graph_get_edges(alego_handle* h, int slot, int kind, int32_t first, int32_t n, alego_graph_edge* out);
+/* overwrite chain edges first .. first + n - 1 (restored sessions, as alego_map_set_stamps): chain[j] must be the prior (from -1, to 0) or
+ * first + j - 1 -> first + j.  alego_lm_set_keypose / alego_map_set_keyposes never touch edges: a measurement stays what was measured. */
+int alego_graph_set_edges(alego_handle* h, int slot, int32_t first, int32_t n, const alego_graph_edge* chain);
+/* append, for every r[i] with status == 2, the edge latest_id -> closest_id with r[i].between and r[i].noise_variance on all six components
+ * (:716-733) to slots[i]; r[i].correction is kept as the slot's map -> odom correction (:734).  Sets the slot's loop_closed_.
+ * alego_graph_add_edge: one edge from any source (e.g. alego_loop_closure_icp); correction = row-major 4x4, NULL = identity.
+ * ALEGO_ERR_ARG: graph off, slot out of range, ids outside [0, frames stored), from == to, a variance not positive and finite, a
+ * measurement not finite.  ALEGO_ERR_CAPACITY: max_loops edges are stored already.  On any error nothing is written. */
+int alego_graph_add_loops(alego_handle* h, const int32_t* slots, int32_t n, const alego_loop_result* r);
+int alego_graph_add_edge(alego_handle* h, int slot, const alego_graph_edge* e, const float correction[16]);
+/* Defaults (opts == NULL, or a field <= 0): max_iters = ALEGO_GRAPH_MAX_ITERS, step_tol = ALEGO_GRAPH_STEP_TOL, apply = 0.
+ * Observed on the MI355X over the constructed graphs of tests/test_pose_graph.py (drifted circles of 2 .. 2000 poses, up to 19 m / 0.34 rad
+ * of end drift, 1 .. 64 loop edges of variance 1e-4 .. 0.4; table in DESIGN.md section 13): the step shrinks 10 - 100 x per iteration
+ * (linearly: the loop residual does not vanish at the optimum).  Steps until the largest component is below 1e-9: 2 (2 and 3 poses), 6 - 7
+ * (150 poses, 1 - 8 loop edges; 2000 poses), 10 in the worst case (400 poses, 18.7 m / 0.27 rad), hence max_iters = 2 x 10.  Left to run,
+ * the steps stagnate between 6e-17 and 2.0e-13 (largest on 2000 poses), so step_tol = 1e-9 is 5000 x above the stagnation level; with it
+ * the estimate ends within 2.7e-11 m / 8.8e-13 rad of the optimum.  The test asserts both margins on the device. */
+#define ALEGO_GRAPH_MAX_ITERS 20
+#define ALEGO_GRAPH_STEP_TOL 1e-9
+typedef struct alego_graph_opts {
+  int32_t max_iters;       /* Gauss-Newton steps at most */
+  double step_tol;         /* stop when the largest component of delta (rad, m) is below it */
+  int32_t apply;           /* 1: correctPoses (:561-584) on the device for every slot that converged and has had a loop edge added since its last apply */
+} alego_graph_opts;
+typedef struct alego_graph_result {
+  int32_t status;          /* 2 converged, 1 max_iters reached (not applied), 0 no key frame, -1 the archive dropped frames, -2 a step was not finite
+                              (the slot's poses and estimate are left untouched) */
+  int32_t iterations, n_poses, n_loops, applied;
+  double cost0, cost;      /* sum of squared whitened errors at the archived poses / at the estimate (the first Gauss-Newton step of a drifted
+                              loop RAISES the cost before it falls: only cost <= cost0 at the end holds) */
+  double last_step;        /* largest |component| of the last delta */
+} alego_graph_result;
+/* Optimise the graphs of the listed slots at once; out[i] belongs to slots[i].  Synchronous; runs behind the work already queued on every stream
+ * group.  A slot's result does not depend on the other slots of the call, their order or the chunking (sums run in a fixed order).
+ * ALEGO_ERR_ARG: graph off, a slot out of range or listed twice.
+ * apply = 1: archived poses <- f32 (x y z, roll = atan2(R21, R22), pitch = atan2(-R20, sqrt(R21^2 + R22^2)), yaw = atan2(R10, R00)) of the
+ * estimate; the resident key frames get the same poses and are re-transformed; the local-map window is reset as by alego_lm_reset_window;
+ * map -> odom is corrected by the LAST loop edge's correction as by alego_lm_apply_correction; loop_closed_ is cleared — the same state the
+ * per-slot calls alego_map_set_keyposes + alego_lm_set_keypose (every resident frame) + alego_lm_reset_window + alego_lm_apply_correction
+ * leave, without a host call or a synchronisation per slot. */
+int alego_graph_optimize(alego_handle* h, const int32_t* slots, int32_t n, const alego_graph_opts* opts, alego_graph_result* out);
+/* poses first .. first + n - 1 of the f64 estimate of the slot's last optimise with status > 0, row-major 3x4 each */
+int alego_graph_get_estimate(alego_handle* h, int slot, int32_t first, int32_t n, double* poses12);
+/* host only (csrc/pg_math.h, the arithmetic the kernels run): whitened errors [n_edges][6] and the Jacobian blocks d error / d delta_from,
+ * d error / d delta_to [n_edges][36] (row-major; zero for the `from` side of a prior) of `edges` over poses12[n_poses][12]; any output may be NULL */
+int alego_graph_residuals(const double* poses12, int32_t n_poses, const alego_graph_edge* edges, int32_t n_edges,
+                          double* whitened6, double* jac_from36, double* jac_to36);
+
 /* ---- one scan-to-map registration sharded over the GPUs of a node (BASELINE.json config 5) ----------------
  * One process per GPU; every rank feeds its handle the SAME scans and so keeps a bit-identical replica of the stream's state
  * (ImageProjection, feature extraction, LaserOdometry and the local map are cheap and are computed redundantly).  What is split
