@@ -34,6 +34,7 @@ EXPORTS = [
     "alego_map_get_stamps", "alego_map_set_stamps", "alego_loop_search", "alego_loop_constraint", "alego_debug_nn1",
     "alego_graph_enable", "alego_graph_status", "alego_graph_get_edges", "alego_graph_set_edges", "alego_graph_add_loops", "alego_graph_add_edge",
     "alego_graph_optimize", "alego_graph_get_estimate", "alego_graph_residuals",
+    "alego_loc_select", "alego_loc_enable", "alego_loc_status",
 ]
 
 REPLAY_PINGPONG = 0x100
@@ -322,6 +323,10 @@ def lib():
         L.alego_graph_optimize.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(GraphOpts), C.POINTER(GraphResult)]
         L.alego_graph_get_estimate.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.c_void_p]
         L.alego_graph_residuals.argtypes = [C.c_void_p, C.c_int32, C.POINTER(GraphEdge), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.alego_loc_select.restype = C.c_int
+        L.alego_loc_select.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_int32, C.c_void_p]
+        L.alego_loc_enable.argtypes = [C.c_void_p, C.POINTER(KfIn), C.c_int32, C.c_double]
+        L.alego_loc_status.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.alego_write_pcd.argtypes = [C.c_char_p, C.c_void_p, C.c_int32]
         L.alego_bag_read_pc2.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
         if L.alego_params_sizeof() != C.sizeof(AlegoParams):
@@ -366,6 +371,17 @@ def loop_detect(params, keyposes6, stamps, cur_xyz):
     t = np.ascontiguousarray(stamps, np.float64)
     c = np.ascontiguousarray(cur_xyz, np.float64)
     return int(lib().alego_loop_detect(C.byref(params), kp.ctypes.data, t.ctypes.data, kp.shape[0], c.ctypes.data))
+
+
+def loc_select(keyposes6, xyz, radius, k):
+    """alego_loc_select: the window a localising slot at f32 position xyz selects from the map's key poses (ids ascending; host code of the library)"""
+    kp = np.ascontiguousarray(keyposes6, np.float32).reshape(-1, 6)
+    p = np.ascontiguousarray(xyz, np.float32).reshape(3)
+    ids = np.empty(max(int(k), 1), np.int32)
+    n = int(lib().alego_loc_select(kp.ctypes.data, kp.shape[0], p.ctypes.data, float(radius), int(k), ids.ctypes.data))
+    if n < 0:
+        raise AlegoError(f"alego_loc_select failed ({n})")
+    return ids[:n].copy()
 
 
 def loop_constraint(correction, latest_pose6, closest_pose6):
@@ -818,6 +834,25 @@ class Handle:
         out = (LoopResult * max(sl.shape[0], 1))()
         self._check(lib().alego_loop_search(self._h, sl.ctypes.data, sl.shape[0], out), "alego_loop_search")
         return [_loop_result(out[i]) for i in range(sl.shape[0])]
+
+    # ---- localisation against a frozen key-frame map ----
+    def loc_enable(self, frames, radius=0.0):
+        """frames = [(pose6, corner, surf, outlier), ...] (what map_get_keyframe returns, as tuples): every slot localises in them from now on"""
+        keep, kfs = [], (KfIn * max(len(frames), 1))()
+        for i, f in enumerate(frames):
+            kfs[i].pose[:] = [float(v) for v in f[0]]
+            arrs = [np.ascontiguousarray(c, np.float32).reshape(-1, 4) for c in f[1:4]]
+            keep.append(arrs)
+            kfs[i].corner, kfs[i].n_corner = arrs[0].ctypes.data, arrs[0].shape[0]
+            kfs[i].surf, kfs[i].n_surf = arrs[1].ctypes.data, arrs[1].shape[0]
+            kfs[i].outlier, kfs[i].n_outlier = arrs[2].ctypes.data, arrs[2].shape[0]
+        self._check(lib().alego_loc_enable(self._h, kfs, len(frames), float(radius)), "alego_loc_enable")
+
+    def loc_status(self, slot=0):
+        """dict(frames, window, rebuilds, optimized) of the slot's last mapping frame"""
+        out = np.zeros(4, np.int32)
+        self._check(lib().alego_loc_status(self._h, slot, out.ctypes.data), "alego_loc_status")
+        return dict(frames=int(out[0]), window=int(out[1]), rebuilds=int(out[2]), optimized=int(out[3]))
 
     # ---- the key-pose graph (needs map_enable) ----
     def graph_enable(self, max_loops, odom_variance=None):

@@ -153,6 +153,12 @@ int check_slot(alego_handle* h, int slot, bool drain = true) {
   return 0;
 }
 
+// a localising handle (alego_loc_enable) owns no key frames of its own: the calls that read, write or archive them refuse
+int not_localising(alego_handle* h, const char* what) {
+  if (h->lm && lm_host_localising(h->lm)) { h->err = std::string(what) + ": not available on a localising handle (alego_loc_enable)"; return ALEGO_ERR_ARG; }
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -440,6 +446,7 @@ int alego_replay_assign(alego_handle* h, int slot, int bag, int start_scan) {
 
 int alego_stream_setup(alego_handle* h, int bag, int start_scan) {
   if (!h) return ALEGO_ERR_ARG;
+  if (int r = not_localising(h, "alego_stream_setup")) return r;
   if (!h->d.bag_pts || bag < 0 || bag >= h->d.n_bags || start_scan < 0) { h->err = "alego_stream_setup: needs alego_replay_create and a valid bag"; return ALEGO_ERR_ARG; }
   if (h->d.n_slots < 3 || h->streams.size() != 1) { h->err = "alego_stream_setup: the handle needs n_slots = 1 + 2 W >= 3 (one stream group)"; return ALEGO_ERR_ARG; }
   if (h->d.traj) { h->err = "alego_stream_setup: the per-scan pose log belongs to the batch path"; return ALEGO_ERR_ARG; }
@@ -1262,6 +1269,7 @@ int alego_graph_residuals(const double* poses12, int32_t n_poses, const alego_gr
 int alego_dist_unique_id(char id[ALEGO_DIST_ID_BYTES]) { return id ? lm_host_dist_unique_id(id) : ALEGO_ERR_ARG; }
 int alego_dist_init(alego_handle* h, int rank, int world, const char id[ALEGO_DIST_ID_BYTES]) {
   if (!h || !id) return ALEGO_ERR_ARG;
+  if (int r = not_localising(h, "alego_dist_init")) return r;
   hipSetDevice(h->device);
   drain_back(h);
   return lm_host_dist_init(h->lm, rank, world, id, &h->err);
@@ -1279,6 +1287,27 @@ int alego_dist_shutdown(alego_handle* h) {
   return lm_host_dist_shutdown(h->lm);
 }
 
+// ---- localisation against a frozen key-frame map (kernels_loc.hip) ---------------------------
+int alego_loc_enable(alego_handle* h, const alego_kf_in* frames, int32_t n, double radius) {
+  if (!h) return ALEGO_ERR_ARG;
+  if (h->stream_mode) { h->err = "alego_loc_enable: not available with alego_stream_setup"; return ALEGO_ERR_ARG; }
+  if (h->map_on || h->graph_on) { h->err = "alego_loc_enable: the key-frame archive / key-pose graph belong to a mapping handle"; return ALEGO_ERR_ARG; }
+  bool used = false;
+  for (long v : h->lo_scans) used = used || v != 0;
+  for (long v : h->grp_scans) used = used || v != 0;
+  if (used) { h->err = "alego_loc_enable: call it before the first scan of any slot"; return ALEGO_ERR_ARG; }
+  hipSetDevice(h->device);
+  g_prof = &h->prof;
+  HIP_TRY(h, sync_all(h));
+  return lm_host_loc_enable(h->lm, h->d, frames, n, radius, &h->err);
+}
+int alego_loc_status(alego_handle* h, int slot, int32_t out[4]) {
+  if (int r = check_slot(h, slot)) return r;
+  if (!out) return ALEGO_ERR_ARG;
+  hipSetDevice(h->device);
+  return lm_host_loc_status(h->lm, slot, out, &h->err);
+}
+
 // ---- key-frame pass-through ---------------------------------------------------------------------------------------
 int alego_lm_keyframe_count(alego_handle* h, int slot) {
   if (int r = check_slot(h, slot)) return r;
@@ -1288,18 +1317,21 @@ int alego_lm_keyframe_count(alego_handle* h, int slot) {
 int alego_lm_get_keyframe(alego_handle* h, int slot, int kf_id, alego_keyframe* out) {
   if (int r = check_slot(h, slot)) return r;
   if (!out) return ALEGO_ERR_ARG;
+  if (int r = not_localising(h, "alego_lm_get_keyframe")) return r;
   hipSetDevice(h->device);
   return lm_host_get_keyframe(h->lm, slot, kf_id, out, &h->err);
 }
 int alego_lm_set_keypose(alego_handle* h, int slot, int kf_id, const float pose6[6]) {
   if (int r = check_slot(h, slot)) return r;
   if (!pose6) return ALEGO_ERR_ARG;
+  if (int r = not_localising(h, "alego_lm_set_keypose")) return r;
   hipSetDevice(h->device);
   g_prof = &h->prof;
   return lm_host_set_keypose(h->lm, h->d, slot, kf_id, pose6, &h->err);
 }
 int alego_lm_reset_window(alego_handle* h, int slot) {
   if (int r = check_slot(h, slot)) return r;
+  if (int r = not_localising(h, "alego_lm_reset_window")) return r;
   hipSetDevice(h->device);
   return lm_host_reset_window(h->lm, slot, &h->err);
 }
@@ -1314,6 +1346,7 @@ int alego_lm_add_keyframe(alego_handle* h, int slot, const float pose6[6], const
                           const alego_point* surf, int32_t n_surf, const alego_point* outlier, int32_t n_outlier) {
   if (int r = check_slot(h, slot)) return r;
   if (!pose6) return ALEGO_ERR_ARG;
+  if (int r = not_localising(h, "alego_lm_add_keyframe")) return r;
   hipSetDevice(h->device);
   g_prof = &h->prof;
   return lm_host_add_keyframe(h->lm, h->d, slot, pose6, corner, n_corner, surf, n_surf, outlier, n_outlier, &h->err);
@@ -1323,6 +1356,7 @@ int alego_lm_add_keyframe(alego_handle* h, int slot, const float pose6[6], const
 int alego_map_enable(alego_handle* h, int32_t max_keyframes, int32_t max_points) {
   if (!h || max_keyframes <= 0 || max_points <= 0) return ALEGO_ERR_ARG;
   if (h->stream_mode) { h->err = "alego_map_enable: not available with alego_stream_setup"; return ALEGO_ERR_ARG; }
+  if (int r = not_localising(h, "alego_map_enable")) return r;
   if (h->map_on) { h->err = "alego_map_enable: already enabled"; return ALEGO_ERR_ARG; }
   hipSetDevice(h->device);
   HIP_TRY(h, sync_all(h));

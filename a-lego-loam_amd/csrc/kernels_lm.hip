@@ -10,6 +10,8 @@
 //   lm_assoc       a21/a22: 5-NN, 3x3 scatter eigen-decomposition (line) / 5x3 Householder LS (plane)
 //   lm_solve       a23/a24: both ceres::Solve calls of :360-478 in one workgroup per stream
 //   lm_finish / lm_store_kf  saveKeyFramesAndFactor (no-loop-closure pass-through) + transformUpdate
+// The registration guards read "no map yet" as (LI_NKF | LI_REC_CNT) == 0: no key frame in SLAM mode (a window entry implies one), an empty
+// window in localisation mode, where LI_NKF stays 0 (kernels_loc.hip).
 #include "dev_cost.h"
 #include "prof.h"
 #include "lm_ctx.h"
@@ -101,6 +103,7 @@ __global__ void __launch_bounds__(LM_BLOCK) lm_prepare(DevCtx d, LmCtx L, int st
   li[LI_RUN] = run;
   if (run_hint >= 0 && run != run_hint) li[LI_OVERFLOW] = 2;  // host launch-skipping logic out of sync
   if (!run) { li[LI_FLAGS] = 8; return; }
+  if (L.loc_on) return;   // localisation: the window is loc_select's (kernels_loc.hip), from the pose just associated
   lm_map_update(L, slot, li, d.opt_map_merge);
   li[LI_REBUILD_FB] = li[LI_REBUILD] && !d.opt_map_merge;
 }
@@ -471,7 +474,7 @@ __global__ void __launch_bounds__(128) lm_knn(DevCtx d, LmCtx L) {
   if (!li[LI_RUN]) return;
   const alego_params& P = d.P;
   // registration guard :350
-  if (li[LI_NCUR_C] < P.lm_min_corner || li[LI_NTOTAL] < P.lm_min_surf || li[LI_KDS_C] < P.lm_min_map_corner || li[LI_NKF] == 0) return;
+  if (li[LI_NCUR_C] < P.lm_min_corner || li[LI_NTOTAL] < P.lm_min_surf || li[LI_KDS_C] < P.lm_min_map_corner || (li[LI_NKF] | li[LI_REC_CNT]) == 0) return;
   const int nq = kind == 0 ? li[LI_NCUR_C] : li[LI_NTOTAL_DS];
   int qlo, qhi;
   lm_shard_slice(L, li[LI_NCUR_C], li[LI_NTOTAL_DS], kind, &qlo, &qhi);
@@ -606,7 +609,7 @@ __global__ void __launch_bounds__(128) lm_fit(DevCtx d, LmCtx L) {
   const int* li = lip(L, slot);
   if (!li[LI_RUN]) return;
   const alego_params& P = d.P;
-  if (li[LI_NCUR_C] < P.lm_min_corner || li[LI_NTOTAL] < P.lm_min_surf || li[LI_KDS_C] < P.lm_min_map_corner || li[LI_NKF] == 0) return;
+  if (li[LI_NCUR_C] < P.lm_min_corner || li[LI_NTOTAL] < P.lm_min_surf || li[LI_KDS_C] < P.lm_min_map_corner || (li[LI_NKF] | li[LI_REC_CNT]) == 0) return;
   const int nq = kind == 0 ? li[LI_NCUR_C] : li[LI_NTOTAL_DS];
   const float4* mp = kind == 0 ? L.map_corner_ds + (size_t)slot * L.map_cap_c : L.map_surf_ds + (size_t)slot * L.map_cap_s;
   for (int q = bx * 128 + threadIdx.x; q < nq; q += gx * 128) {
@@ -814,7 +817,7 @@ __global__ void __launch_bounds__(LM_SOLVE_T) lm_solve(DevCtx d, LmCtx L) {
   if (!li[LI_RUN]) return;
   const alego_params& P = d.P;
   double* ld = ldp(L, slot);
-  if (li[LI_NCUR_C] < P.lm_min_corner || li[LI_NTOTAL] < P.lm_min_surf || li[LI_KDS_C] < P.lm_min_map_corner || li[LI_NKF] == 0) {
+  if (li[LI_NCUR_C] < P.lm_min_corner || li[LI_NTOTAL] < P.lm_min_surf || li[LI_KDS_C] < P.lm_min_map_corner || (li[LI_NKF] | li[LI_REC_CNT]) == 0) {
     if (threadIdx.x == 0) { li[LI_FLAGS] |= 16; li[LI_NCC] = 0; li[LI_NSC] = 0; li[LI_SUM0] = 0; li[LI_SUM1] = 0; }
     return;
   }
@@ -900,7 +903,8 @@ __global__ void lm_finish(DevCtx d, LmCtx L) {
   li[LI_REBUILD] = 0;   // the map sequence of this frame is done: no stale flag for a later round over the group's jobs
   double* ld = ldp(L, slot);
   const int nkf = li[LI_NKF];
-  bool add = true;
+  bool add = !L.loc_on;   // localisation never saves a key frame: the optimised params_ reach transformUpdate as they are
+  if (L.loc_on && li[LI_REC_CNT] == 0) return;   // ... and off the map (empty window) map -> odom stays what it was: dead reckoning
   if (nkf > 0) {
     const float* pre = L.kf_pose + ((size_t)slot * L.KR + (nkf - 1) % L.KR) * 8;
     const double ex = ld[LD_T_M2L + 0] - (double)pre[0], ey = ld[LD_T_M2L + 1] - (double)pre[1], ez = ld[LD_T_M2L + 2] - (double)pre[2];
@@ -1000,7 +1004,7 @@ DEV_INLINE void lm_shard_pack_dev(const DevCtx& d, const LmCtx& L, int slot) {
   if (threadIdx.x == 0) { ctl[0] = 0; ctl[1] = LM_STOP; ctl[2] = 1; ctl[3] = 0; ctl[4] = 1; ctl[5] = 0; }
   if (!li[LI_RUN]) return;
   const alego_params& P = d.P;
-  if (li[LI_NCUR_C] < P.lm_min_corner || li[LI_NTOTAL] < P.lm_min_surf || li[LI_KDS_C] < P.lm_min_map_corner || li[LI_NKF] == 0) {
+  if (li[LI_NCUR_C] < P.lm_min_corner || li[LI_NTOTAL] < P.lm_min_surf || li[LI_KDS_C] < P.lm_min_map_corner || (li[LI_NKF] | li[LI_REC_CNT]) == 0) {
     if (threadIdx.x == 0) { li[LI_FLAGS] |= 16; li[LI_NCC] = 0; li[LI_NSC] = 0; li[LI_SUM0] = 0; li[LI_SUM1] = 0; }
     return;
   }
@@ -1156,6 +1160,7 @@ int launch_lm_register(const DevCtx& d, const LmCtx& L, hipStream_t st, int (*al
   ALEGO_LAUNCH(lm_solve, dim3(d.n_launch), dim3(LM_SOLVE_T), LM_SOLVE_RED_BYTES + L.solve_row_bytes, st, d, L);
   }
   ALEGO_LAUNCH(lm_finish, dim3((d.n_launch + 63) / 64), dim3(64), 0, st, d, L);
+  if (L.loc_on) return 0;   // no key frame is ever stored, sorted or archived
   ALEGO_LAUNCH(lm_store_kf, dim3(8, 3, d.n_launch), dim3(LM_BLOCK), 0, st, d, L, -1);
   if (L.arc_frames_cap > 0) launch_map_archive(d, L, 0, st);   // (alego_map_enable; nothing is launched without it)
   return 0;

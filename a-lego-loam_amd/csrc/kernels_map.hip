@@ -39,10 +39,10 @@ typedef unsigned long long u64;
 
 DEV_INLINE int* lipm(const LmCtx& L, int slot) { return L.li + (size_t)slot * LI_COUNT; }
 DEV_INLINE const float4* run_pts(const LmCtx& L, int slot, int m, int entry) {
-  return m == 0 ? L.kfs_c + ((size_t)slot * L.KR + entry) * L.kf_cap_c : L.kfs_s + ((size_t)slot * L.KR + entry) * L.total_cap;
+  return m == 0 ? L.kfs_c + ((size_t)slot * L.fr_stride + entry) * L.kf_cap_c : L.kfs_s + ((size_t)slot * L.fr_stride + entry) * L.total_cap;
 }
-DEV_INLINE int run_n(const LmCtx& L, int slot, int m, int entry) { return L.kfs_n[((size_t)slot * 2 + m) * L.KR + entry]; }
-DEV_INLINE const float* run_box(const LmCtx& L, int slot, int m, int entry) { return L.kfs_box + (((size_t)slot * 2 + m) * L.KR + entry) * 8; }
+DEV_INLINE int run_n(const LmCtx& L, int slot, int m, int entry) { return L.kfs_n[(size_t)slot * 2 * L.fr_stride + (size_t)m * L.fr_mod + entry]; }
+DEV_INLINE const float* run_box(const LmCtx& L, int slot, int m, int entry) { return L.kfs_box + ((size_t)slot * 2 * L.fr_stride + (size_t)m * L.fr_mod + entry) * 8; }
 DEV_INLINE u64* map_U(const LmCtx& L, int slot, int m) { return m == 0 ? L.U_c + (size_t)slot * L.map_cap_c : L.U_s + (size_t)slot * L.map_cap_s; }
 DEV_INLINE int* map_Ucnt(const LmCtx& L, int slot, int m) { return m == 0 ? L.Ucnt_c + (size_t)slot * L.map_cap_c : L.Ucnt_s + (size_t)slot * L.map_cap_s; }
 DEV_INLINE float4* map_out(const LmCtx& L, int slot, int m) { return m == 0 ? L.map_corner_ds + (size_t)slot * L.map_cap_c : L.map_surf_ds + (size_t)slot * L.map_cap_s; }
@@ -155,7 +155,7 @@ __global__ void __launch_bounds__(MU_T) map_update(DevCtx d, LmCtx L, MapWork W)
     float mn[3] = {3.402823466e+38f, 3.402823466e+38f, 3.402823466e+38f}, mx[3] = {-3.402823466e+38f, -3.402823466e+38f, -3.402823466e+38f};
     int kraw = 0;
     for (int j = tid; j < ncur; j += MU_T) {
-      const int e = rec[j] % L.KR;
+      const int e = rec[j] % L.fr_mod;
       const int n = run_n(L, slot, m, e);
       kraw += n;
       if (n > 0) {
@@ -197,14 +197,14 @@ __global__ void __launch_bounds__(MU_T) map_update(DevCtx d, LmCtx L, MapWork W)
           if (valid) {
             int a = 0, b = 0;
             while (a < np || b < ncur) {
-              if (b >= ncur || (a < np && s_prev[a] < s_cur[b])) { if (s_prev[a] < nkf - L.KR) valid = false; s_rem[nr++] = s_prev[a++] % L.KR; }   // its ring entry must still hold it
-              else if (a >= np || s_cur[b] < s_prev[a]) s_add[na++] = s_cur[b++] % L.KR;
+              if (b >= ncur || (a < np && s_prev[a] < s_cur[b])) { if (s_prev[a] < nkf - L.fr_mod) valid = false; s_rem[nr++] = s_prev[a++] % L.fr_mod; }   // its ring entry must still hold it
+              else if (a >= np || s_cur[b] < s_prev[a]) s_add[na++] = s_cur[b++] % L.fr_mod;
               else { ++a; ++b; }
             }
           }
           if (!valid) {   // rebuild from nothing: every run of the window is inserted
             nr = 0; na = 0;
-            for (int b = 0; b < ncur; ++b) s_add[na++] = s_cur[b] % L.KR;
+            for (int b = 0; b < ncur; ++b) s_add[na++] = s_cur[b] % L.fr_mod;
           }
           s_nrem = nr; s_nadd = na; s_nU = valid ? li[LI_NU_C + m] : 0; s_err = 0;
         }
@@ -364,11 +364,11 @@ __global__ void __launch_bounds__(MU_T) map_update(DevCtx d, LmCtx L, MapWork W)
     }
     if (pass) {
       float4* out = map_out(L, slot, m);
-      const int* kc = L.kf_cnt + (size_t)slot * L.KR * 4;
+      const int* kc = L.kf_cnt + (size_t)slot * L.fr_stride * 4;
       int off = 0;
       for (int j = 0; j < ncur; ++j) {
-        const int e = rec[j] % L.KR;
-        const size_t rs = (size_t)slot * L.KR + e;
+        const int e = rec[j] % L.fr_mod;
+        const size_t rs = (size_t)slot * L.fr_stride + e;
         // (the sorted runs lost the input order: the raw clouds are transformed again, in the reference's order)
         float mm[3][4];
         keypose_matrix(L.kf_pose + rs * 8, mm);
@@ -474,7 +474,7 @@ __global__ void __launch_bounds__(MA_T, 8) map_accum(DevCtx d, LmCtx L, MapWork 
   __shared__ unsigned short s_start[MA_JB * MAP_R];   // [sub-piece][voxel]: position + 1 of the pair's first point in the batch (valid where s_mask has the bit)
   __shared__ unsigned s_mask[MAP_R];                  // per voxel: the sub-pieces of the batch that hold points of it
   __shared__ int s_lo[MAP_KMAX], s_hi[MAP_KMAX];
-  __shared__ unsigned short s_ent[MAP_KMAX];   // (ring entries < KR <= MAP_KMAX + 1; 16 bits keep the kernel under 40 KB: four workgroups per CU)
+  __shared__ unsigned short s_ent[MAP_KMAX];   // (entries < fr_mod: KR <= MAP_KMAX + 1, or the frames of a localisation map store, at most 8192; 16 bits keep the kernel under 40 KB: four workgroups per CU)
   __shared__ int s_sub_ent[MA_JB], s_sub_lo[MA_JB], s_sub_off[MA_JB + 1];
   __shared__ int s_nsub, s_next_j, s_next_pos;
   // the chunk's voxels by key: open addressing, MA_HT slots for <= MAP_R keys (entry = voxel + 1, 0 = empty; the key itself is compared in s_key).  A staged
@@ -516,7 +516,7 @@ __global__ void __launch_bounds__(MA_T, 8) map_accum(DevCtx d, LmCtx L, MapWork 
     __syncthreads();
     const u64 key_lo = s_key[0], key_hi = s_key[nr - 1];
     for (int j = tid; j < nwin; j += MA_T) {   // the piece of every run that falls into this chunk's key range
-      const int e = rec[j] % L.KR;
+      const int e = rec[j] % L.fr_mod;
       const float4* pts = run_pts(L, slot, m, e);
       const int n = run_n(L, slot, m, e);
       s_ent[j] = (unsigned short)e;

@@ -40,6 +40,7 @@ enum {
   LD_T_M2L = 20, LD_Q_M2L = 23,  // map -> laser
   LD_PARAMS_IT = 27,             // params_ after each outer iteration [2][6]
   LD_COSTS = 39,                 // initial/final cost of both solves
+  LD_LOC_P = 44,                 // localisation (kernels_loc.hip): the f32 position the last mapping frame selected its window with, x y z (44..46)
   LD_COUNT = 48
 };
 
@@ -83,6 +84,12 @@ DEV_INLINE float4 kf_transform(const float m[3][4], const float4& p) {   // lase
 
 struct LmCtx {
   int K;                         // recent_keyframe_num
+  // Where the key frames of a slot live.  Frame f of slot s is row  s * fr_stride + f % fr_mod  of kfs_c / kfs_s / kf_raw_* / kf_cnt / kf_pose, and
+  // entry  s * 2 * fr_stride + m * fr_mod + f % fr_mod  of kfs_n / kfs_box.  SLAM: the slot's own ring, fr_stride = fr_mod = KR.  Localisation
+  // (alego_loc_enable): those pointers name ONE frozen map store shared by every slot, fr_stride = 0 and fr_mod = its frame capacity.
+  int fr_stride, fr_mod;
+  int loc_on, loc_n;             // localisation mode; frames of the map store
+  float loc_r2;                  // (float)(radius * radius) of loc_select
   int KR;                        // ring entries per slot = K + 1: frame f lives in entry f % KR, so the frame a full window pops
                                  // (f - K) is still intact when the frame that pushes it out (f) has been stored
   int kf_cap_c, kf_cap_s, kf_cap_o;

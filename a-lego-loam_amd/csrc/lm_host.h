@@ -60,4 +60,8 @@ int lm_host_set_gv_small_max(LmHost* lm, int v);
 int lm_host_graph_enable(LmHost* lm, int max_loops, const double* odom_var6, std::string* err);
 // correctPoses for the slots with apply[slot] != 0 (apply_dev: the same flags on the device); n_poses_max: most key frames of an applied slot
 int lm_host_graph_apply(LmHost* lm, const std::vector<int>& apply, const int* apply_dev, int n_poses_max, std::string* err);
+// localisation mode (alego_loc_*; kernels_loc.hip): the frozen map store shared by every slot
+int lm_host_loc_enable(LmHost* lm, const DevCtx& d, const alego_kf_in* frames, int n, double radius, std::string* err);
+int lm_host_loc_status(LmHost* lm, int slot, int* out4, std::string* err);
+bool lm_host_localising(LmHost* lm);
 #endif

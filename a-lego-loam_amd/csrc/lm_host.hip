@@ -13,6 +13,7 @@
 #include "lm_ctx.h"
 #include "voxel.h"
 #include "gmap.h"
+#include "loc_math.h"
 
 void launch_lm_prepare(const DevCtx& d, const LmCtx& L, int stage, int run_hint, int par, hipStream_t st);
 void launch_lm_stage(const DevCtx& d, const LmCtx& L, int run_hint, int par, hipStream_t st);
@@ -30,6 +31,7 @@ void launch_lm_apply_correction(const DevCtx& d, const LmCtx& L, int slot, const
 void launch_pg_apply(const LmCtx& L, const int* apply_dev, int n_slots, hipStream_t st);   // kernels_graph.hip
 void launch_pg_retransform(const LmCtx& L, const int* apply_dev, int slot0, int n, int j, hipStream_t st);
 void launch_pg_sorted(const LmCtx& L, const int* apply_dev, int slot0, int n, int all, hipStream_t st);
+void launch_loc_select(const DevCtx& d, const LmCtx& L, hipStream_t st);   // kernels_loc.hip
 
 struct LmHost {
   alego_params P;
@@ -51,6 +53,9 @@ struct LmHost {
   // the global map (alego_map_* / alego_voxel_grid): device-wide VoxelGrid scratch + the assembly's frame offsets
   GvCtx gv;
   int* arc_off = nullptr;      // [arc_frames_cap + 1]
+  // localisation mode (alego_loc_enable): the two sort jobs that fill the map store, frame after frame
+  VoxCtx vloc;
+  bool vloc_made = false;
 };
 
 namespace {
@@ -79,6 +84,7 @@ LmHost* lm_host_create(const alego_params& P, const DevCtx& d, int n_slots, int 
   std::memset(&L, 0, sizeof(L));
   L.K = P.recent_keyframe_num > 0 ? P.recent_keyframe_num : 1;
   L.KR = L.K + 1;
+  L.fr_stride = L.KR; L.fr_mod = L.KR;   // every slot's frames live in its own ring
   // the concat + radix-sort path needs the raw maps and 20 B of sort scratch per map point (~42 MB per stream at 16x1800 / K = 50): large
   // batches only carry it when they are configured to use it
   lm->fallback_ok = n_slots <= 64 || !d.opt_map_merge;
@@ -185,6 +191,7 @@ void lm_host_destroy(LmHost* lm) {
   for (auto& v : lm->vm) vox_destroy(&v);
   for (auto& v : lm->v2) vox_destroy(&v);
   for (auto& v : lm->vk) vox_destroy(&v);
+  if (lm->vloc_made) vox_destroy(&lm->vloc);
   gv_destroy(&lm->gv);
   for (void* p : lm->allocs) (void)guard_free(p);
   delete lm;
@@ -271,6 +278,10 @@ static int lm_sequence(LmHost* lm, const DevCtx& d, int stage, const std::vector
   launch_lm_prepare(d, L, stage, hint, par, st);
   if (!dbg_sync(st, "lm_prepare", err)) return ALEGO_ERR_HIP;
   if (n_run == 0) return 0;
+  if (L.loc_on) {   // the window of every slot that maps this scan, from the pose lm_prepare has just associated
+    launch_loc_select(d, L, st);
+    if (!dbg_sync(st, "loc_select", err)) return ALEGO_ERR_HIP;
+  }
   if (int r = map_sequence(lm, d, L, g, st, err)) return r;   // (includes the VoxelGrid filters of the scan's three clouds)
   launch_lm_total(d, L, st);
   if (int r = vox_run(lm->v2[g], st, err)) return r;
@@ -563,6 +574,7 @@ int lm_host_debug_slice(LmHost* lm, int rank, int world, std::string* err) {
 // ALEGO_MAP_MERGE switched at run time (tests): the voxel lists no longer describe what the other path did in between
 int lm_host_set_map_merge(LmHost* lm, int on, std::string* err) {
   if (!on && !lm->fallback_ok) { *err = "ALEGO_MAP_MERGE=0 needs the handle to be created with it (more than 64 slots)"; return ALEGO_ERR_ARG; }
+  if (!on && lm->L.loc_on) { *err = "ALEGO_MAP_MERGE=0: a localising handle builds its local maps from the map store's sorted runs only"; return ALEGO_ERR_ARG; }
   for (hipStream_t s : lm->st) (void)hipStreamSynchronize(s);
   const int zero = 0;
   for (int b = 0; b < lm->n_slots; ++b)
@@ -592,7 +604,7 @@ int lm_host_debug_get(LmHost* lm, int slot, const char* name, void* out, int cap
   else if (s == "lm_surf_total_ds") set(L.cur_total_ds + b * L.total_cap, (size_t)li[LI_NTOTAL_DS] * 4, 0);
   else if (s == "lm_blocks") set(L.blocks + b * L.qcap * 8, (size_t)L.qcap * 8, 1);
   else if (s == "lm_knn") set(L.knn + b * L.qcap * 5, (size_t)L.qcap * 5, 2);   // lm_knn's rows: corner queries from 0, surf queries from kf_cap_c; -1 x 5 = rejected
-  else if (s == "lm_keyposes") set(L.kf_pose + b * L.KR * 8, (size_t)L.KR * 8, 0);
+  else if (s == "lm_keyposes") set(L.kf_pose + b * L.fr_stride * 8, (size_t)(L.loc_on ? L.loc_n : L.KR) * 8, 0);   // (localisation: the map store's)
   else if (s == "lm_window") set(L.rec + b * L.K, (size_t)li[LI_REC_CNT], 2);   // frame ids of recent_*_keyframes_
   else if (s == "lm_kf_corner_map" || s == "lm_kf_surf_map") {   // newest key frame in the map frame, sorted by voxel key (surf = surf + outlier)
     const int nkf = li[LI_NKF];
@@ -672,6 +684,118 @@ int lm_host_map_mark_stamped(LmHost* lm, int slot, hipStream_t st) {
   return lm->L.arc_frames_cap > 0 && hipMemcpyAsync(lm->L.arc_stamped + slot, &one, sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess ? ALEGO_ERR_HIP : 0;
 }
 const LmCtx* lm_host_ctx(LmHost* lm) { return &lm->L; }
+
+// ---- localisation mode (alego_loc_*; kernels_loc.hip) ----
+// The map store: every frame transformed by its key pose and sorted by voxel key exactly as a ring entry is (lm_store_kf's re-transform path
+// into kf_tmp_*, then the key-frame sort, VoxelGrid mode 1), once for the whole handle.  The rings of the slots are released: kfs_* / kf_raw_* /
+// kf_cnt / kf_pose name the store from now on, and fr_stride = 0 sends every slot's frame f to row f of it.
+static void release(LmHost* lm, void* p) {
+  auto it = std::find(lm->allocs.begin(), lm->allocs.end(), p);
+  if (it == lm->allocs.end()) return;
+  (void)guard_free(p);
+  lm->allocs.erase(it);
+}
+int lm_host_loc_enable(LmHost* lm, const DevCtx& dfull, const alego_kf_in* frames, int n, double radius, std::string* err) {
+  LmCtx& L = lm->L;
+  if (L.loc_on) { *err = "alego_loc_enable: already enabled"; return ALEGO_ERR_ARG; }
+  if (n < 0 || (n > 0 && !frames)) { *err = "alego_loc_enable: null frames / negative count"; return ALEGO_ERR_ARG; }
+  if (L.arc_frames_cap > 0 || L.pg_loops_cap > 0) { *err = "alego_loc_enable: the key-frame archive / key-pose graph belong to a mapping handle"; return ALEGO_ERR_ARG; }
+  if (lm->comm) { *err = "alego_loc_enable: not available on a handle with a sharded registration (alego_dist_init)"; return ALEGO_ERR_ARG; }
+  if (!dfull.opt_map_merge) { *err = "alego_loc_enable: ALEGO_MAP_MERGE=0 (concat + radix VoxelGrid) is a mapping-only path"; return ALEGO_ERR_ARG; }
+  for (long f : lm->frames) if (f != 0) { *err = "alego_loc_enable: call it before the first scan of any slot"; return ALEGO_ERR_ARG; }
+  for (hipStream_t s : lm->st) if (hipStreamSynchronize(s) != hipSuccess) { *err = "alego_loc_enable: a stream failed"; return ALEGO_ERR_HIP; }
+  {
+    std::vector<int> li((size_t)lm->n_slots * LI_COUNT);
+    if (hipMemcpy(li.data(), L.li, li.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { *err = "alego_loc_enable: device read failed"; return ALEGO_ERR_HIP; }
+    for (int s = 0; s < lm->n_slots; ++s)
+      if (li[(size_t)s * LI_COUNT + LI_NKF] != 0 || li[(size_t)s * LI_COUNT + LI_FRAME] != 0) { *err = "alego_loc_enable: call it before the first scan / key frame of any slot"; return ALEGO_ERR_ARG; }
+  }
+  if (n > LOC_MAX_FRAMES) { *err = "alego_loc_enable: more than " + std::to_string(LOC_MAX_FRAMES) + " frames"; return ALEGO_ERR_CAPACITY; }
+  for (int i = 0; i < n; ++i) {
+    const alego_kf_in& f = frames[i];
+    if (f.n_corner < 0 || f.n_surf < 0 || f.n_outlier < 0 || (f.n_corner && !f.corner) || (f.n_surf && !f.surf) || (f.n_outlier && !f.outlier)) { *err = "alego_loc_enable: frame " + std::to_string(i) + ": null cloud / negative count"; return ALEGO_ERR_ARG; }
+    if (f.n_corner > L.kf_cap_c || f.n_surf > L.kf_cap_s || f.n_outlier > L.kf_cap_o) {
+      *err = "alego_loc_enable: frame " + std::to_string(i) + " (" + std::to_string(f.n_corner) + " corner, " + std::to_string(f.n_surf) + " surf, " + std::to_string(f.n_outlier) +
+             " outlier points) exceeds the handle's key-frame capacities (" + std::to_string(L.kf_cap_c) + ", " + std::to_string(L.kf_cap_s) + ", " + std::to_string(L.kf_cap_o) + ")";
+      return ALEGO_ERR_CAPACITY;
+    }
+  }
+  LmCtx T = L;
+  const size_t F = (size_t)std::max(n, 1);
+  T.kfs_c = nullptr; T.kfs_s = nullptr; T.kfs_n = nullptr; T.kfs_box = nullptr; T.kf_raw_c = nullptr; T.kf_raw_s = nullptr; T.kf_raw_o = nullptr; T.kf_cnt = nullptr; T.kf_pose = nullptr;
+  std::string aerr;
+  const bool ok = A(lm, &T.kfs_c, F * L.kf_cap_c, &aerr) && A(lm, &T.kfs_s, F * L.total_cap, &aerr) && A(lm, &T.kfs_n, 2 * F, &aerr) && A(lm, &T.kfs_box, 2 * F * 8, &aerr) &&
+                  A(lm, &T.kf_raw_c, F * L.kf_cap_c, &aerr) && A(lm, &T.kf_raw_s, F * L.kf_cap_s, &aerr) && A(lm, &T.kf_raw_o, F * L.kf_cap_o, &aerr) &&
+                  A(lm, &T.kf_cnt, F * 4, &aerr) && A(lm, &T.kf_pose, F * 8, &aerr);
+  if (!ok) {   // the handle stays what it was
+    for (void* p : {(void*)T.kfs_c, (void*)T.kfs_s, (void*)T.kfs_n, (void*)T.kfs_box, (void*)T.kf_raw_c, (void*)T.kf_raw_s, (void*)T.kf_raw_o, (void*)T.kf_cnt, (void*)T.kf_pose}) if (p) release(lm, p);
+    *err = "alego_loc_enable: the map store of " + std::to_string(n) + " frames does not fit (" + aerr + ")";
+    return ALEGO_ERR_CAPACITY;
+  }
+  // The store is built through a view T of its own; the handle becomes a localising one — and its rings go — only once every frame is in.
+  // Until then any failure undoes the store and leaves the handle the SLAM handle it was.
+  T.fr_stride = 0; T.fr_mod = (int)F; T.loc_on = 1; T.loc_n = n; T.loc_r2 = loc_r2(radius);
+  int* li0 = T.li;
+  auto undo = [&](int rc) {
+    (void)hipStreamSynchronize(lm->st[0]);
+    (void)hipMemset(li0 + LI_KF_PENDING, 0, 8 * sizeof(int));
+    (void)hipMemset(li0 + LI_OVERFLOW, 0, sizeof(int));
+    if (lm->vloc_made) { vox_destroy(&lm->vloc); lm->vloc_made = false; }
+    for (void* p : {(void*)T.kfs_c, (void*)T.kfs_s, (void*)T.kfs_n, (void*)T.kfs_box, (void*)T.kf_raw_c, (void*)T.kf_raw_s, (void*)T.kf_raw_o, (void*)T.kf_cnt, (void*)T.kf_pose}) release(lm, p);
+    return rc;
+  };
+  // the sort jobs of slot 0's kf_tmp_*, with the store as their ring
+  VoxJob kc{T.kf_tmp_c, li0 + LI_TMPN_C, T.kfs_c, li0 + LI_SORT_N, li0 + LI_KF_PENDING, lm->P.lm_leaf_corner, T.kf_cap_c, T.kf_cap_c, li0 + LI_OVERFLOW, 0};
+  kc.mode = 1; kc.out_sel = li0 + LI_KF_PEND_RING; kc.out_stride = T.kf_cap_c; kc.box_out = T.kfs_box; kc.n_sel_out = T.kfs_n; kc.n_sel_stride = 1;
+  VoxJob ks{T.kf_tmp_s, li0 + LI_TMPN_S, T.kfs_s, li0 + LI_SORT_N + 1, li0 + LI_KF_PENDING, lm->P.lm_leaf_surf, T.total_cap, T.total_cap, li0 + LI_OVERFLOW, 0};
+  ks.mode = 1; ks.out_sel = li0 + LI_KF_PEND_RING; ks.out_stride = T.total_cap; ks.box_out = T.kfs_box + F * 8; ks.n_sel_out = T.kfs_n + F; ks.n_sel_stride = 1;
+  const VoxJob jobs[2] = {kc, ks};
+  std::memset(&lm->vloc, 0, sizeof(VoxCtx));
+  if (vox_create(&lm->vloc, jobs, 2, err)) return undo(ALEGO_ERR_HIP);
+  lm->vloc_made = true;
+  lm->vloc.grid_small = 2; lm->vloc.grid_big = 2;
+  hipStream_t st = lm->st[0];
+  DevCtx d = dfull;
+  d.slot0 = 0; d.n_launch = 1;
+  hipError_t e = hipSuccess;
+  for (int i = 0; i < n && e == hipSuccess; ++i) {
+    const alego_kf_in& f = frames[i];
+    const float kp[8] = {f.pose[0], f.pose[1], f.pose[2], f.pose[3], f.pose[4], f.pose[5], 0.f, 0.f};
+    const int cnt[4] = {f.n_corner, f.n_surf, f.n_outlier, 0};
+    e = hipMemcpy(T.kf_pose + (size_t)i * 8, kp, sizeof(kp), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(T.kf_cnt + (size_t)i * 4, cnt, sizeof(cnt), hipMemcpyHostToDevice);
+    if (e == hipSuccess && f.n_corner) e = hipMemcpy(T.kf_raw_c + (size_t)i * T.kf_cap_c, f.corner, (size_t)f.n_corner * 16, hipMemcpyHostToDevice);
+    if (e == hipSuccess && f.n_surf) e = hipMemcpy(T.kf_raw_s + (size_t)i * T.kf_cap_s, f.surf, (size_t)f.n_surf * 16, hipMemcpyHostToDevice);
+    if (e == hipSuccess && f.n_outlier) e = hipMemcpy(T.kf_raw_o + (size_t)i * T.kf_cap_o, f.outlier, (size_t)f.n_outlier * 16, hipMemcpyHostToDevice);
+    if (e != hipSuccess) break;
+    launch_lm_retransform(d, T, i, st);   // row i of the store -> kf_tmp_* of slot 0 (slot 0's rows start at 0 whatever fr_stride is)
+    if (int r = vox_run(lm->vloc, st, err)) return undo(r);
+  }
+  // slot 0 lent its key-frame staging words (LI_KF_PENDING .. LI_SORT_N1) to the build: it leaves as fresh as every other slot
+  static_assert(LI_SORT_N1 - LI_KF_PENDING == 7 && LI_REBUILD_FB > LI_KF_PENDING && LI_MAP_PASS < LI_SORT_N1, "the words in between are zero on a fresh slot too");
+  if (e == hipSuccess) e = hipMemsetAsync(li0 + LI_KF_PENDING, 0, 8 * sizeof(int), st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) { *err = std::string("alego_loc_enable: building the map store failed: ") + hipGetErrorString(e); return undo(ALEGO_ERR_HIP); }
+  int ovf = 0;
+  if (hipMemcpy(&ovf, li0 + LI_OVERFLOW, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { *err = "alego_loc_enable: device read failed"; return undo(ALEGO_ERR_HIP); }
+  if (ovf) { *err = "alego_loc_enable: a frame was truncated while it was sorted"; return undo(ALEGO_ERR_CAPACITY); }
+  // The slots' rings give their memory back (no scan has used them).  The per-slot key-frame sort jobs in the job tables of vm[g] / vk[g]
+  // (lm_host_create) still name those rings: they run only for a slot whose LI_KF_PENDING is set, which lm_store_kf alone sets, and neither
+  // lm_store_kf nor a vk round is ever launched on a localising handle (launch_lm_register returns before it; lm_kf_changed, retransform and
+  // lm_host_graph_apply sit behind API calls that refuse such a handle).
+  for (void* p : {(void*)L.kfs_c, (void*)L.kfs_s, (void*)L.kfs_n, (void*)L.kfs_box, (void*)L.kf_raw_c, (void*)L.kf_raw_s, (void*)L.kf_raw_o, (void*)L.kf_cnt, (void*)L.kf_pose}) release(lm, p);
+  L = T;
+  return 0;
+}
+int lm_host_loc_status(LmHost* lm, int slot, int* out4, std::string* err) {
+  const LmCtx& L = lm->L;
+  if (!L.loc_on) { *err = "alego_loc_status: the handle does not localise (alego_loc_enable)"; return ALEGO_ERR_ARG; }
+  int li[LI_COUNT];
+  if (hipStreamSynchronize(stream_of_slot(lm, slot)) != hipSuccess || hipMemcpy(li, L.li + (size_t)slot * LI_COUNT, sizeof(li), hipMemcpyDeviceToHost) != hipSuccess) { *err = "alego_loc_status: device read failed"; return ALEGO_ERR_HIP; }
+  out4[0] = L.loc_n; out4[1] = li[LI_REC_CNT]; out4[2] = li[LI_NREBUILD]; out4[3] = li[LI_OPTIMIZED];
+  return 0;
+}
+bool lm_host_localising(LmHost* lm) { return lm->L.loc_on != 0; }
 
 // ---- the key-pose graph (alego_graph_*) ----
 int lm_host_graph_enable(LmHost* lm, int max_loops, const double* odom_var6, std::string* err) {

@@ -22,12 +22,18 @@
 //       alego_loop_search -> alego_graph_add_loops -> alego_graph_optimize with apply = 1 (correctPoses, :561-584).  Every applied
 //       correction prints one line "closed: scan K slot S poses N loops L iterations I cost C0 -> C"; with --save-map the map comes
 //       out at the corrected poses.
+//   either source + --localize [--loc-radius R]
+//       map once, then localise in that map: the run above keeps the archive on; afterwards every archived key frame is pulled with
+//       alego_map_get_keyframe, a SECOND handle is opened, alego_loc_enable hands it those frames, and the same scans are replayed through
+//       it.  It never saves a key frame; every mapping frame registers against the map frames nearest to its pose.  The JSON line gains
+//       "loc_map_t" (its final map pose) and "loc_max_dev" (the largest per-axis distance between the two runs' map poses).
 // Every scan goes through ImageProjection -> LaserOdometry -> LaserMapping with one alego_scan_process call, as a single nodelet
 // manager would run them (launch/test.launch:6-10); every new key frame is pulled across the boundary the way the reference's
 // pose-graph thread reads cloud_keyposes_6d_ (laserMapping.cpp:586-596); one JSON line with the final poses is printed.
 //
 //   g++ -O2 -std=c++17 -Iinclude examples/replay.cpp -o examples/replay -La-lego-loam_amd -lalego_mi355x -lalego_synth
 //       -Wl,-rpath,'$ORIGIN/../a-lego-loam_amd'                                  (__graft_entry__.build() does this)
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -42,7 +48,8 @@ int main(int argc, char** argv) {
   std::string bag_path, topic = "/lslidar_point_cloud", map_dir;
   float map_leaf = 0.f;
   int map_frames = 4096, map_points = 1 << 24, loop_every = 0, close_every = 0, max_loops = 16;
-  bool list_only = false, standalone = false;
+  bool list_only = false, standalone = false, localize = false;
+  double loc_radius = 0.0;
   long max_scans = -1;
   int n_scan = 16, horizon = -1;
   std::vector<const char*> pos;
@@ -63,6 +70,8 @@ int main(int argc, char** argv) {
     else if (a == "--loop-search") loop_every = std::atoi(val());
     else if (a == "--close-loops") close_every = std::atoi(val());
     else if (a == "--max-loops") max_loops = std::atoi(val());
+    else if (a == "--localize") localize = true;
+    else if (a == "--loc-radius") loc_radius = std::atof(val());
     else pos.push_back(argv[i]);
   }
   alego_bag* bag = nullptr;
@@ -104,7 +113,7 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "alego_create failed (%d): there is no CPU fallback, an MI355X is required\n", rc);
     return 1;
   }
-  if ((!map_dir.empty() || loop_every > 0 || close_every > 0) && alego_map_enable(h, map_frames, map_points) != ALEGO_OK) {
+  if ((!map_dir.empty() || loop_every > 0 || close_every > 0 || localize) && alego_map_enable(h, map_frames, map_points) != ALEGO_OK) {
     std::fprintf(stderr, "map_enable: %s\n", alego_last_error(h)); alego_destroy(h); return 1;
   }
   if (close_every > 0 && alego_graph_enable(h, max_loops, nullptr) != ALEGO_OK) {
@@ -113,11 +122,13 @@ int main(int argc, char** argv) {
   alego_pose odom{}, mapped{};
   int key_frames = 0, last_flags = 0, dropped = 0;
   float last_key_pose[6] = {0, 0, 0, 0, 0, 0};
+  std::vector<double> map_track;   // --localize: the mapping run's map pose of every scan (NaN for a dropped message)
   for (long k = 0; k < n_scans; ++k) {
     int n;
     double stamp = 0.1 * k;
     if (bag) {
       n = alego_bag_read_pc2(bag, topic.c_str(), k, pts.data(), cap_in, &stamp, nullptr);
+      if (n < 0 || n > N) map_track.insert(map_track.end(), 3, 0.0 / 0.0);
       if (n < 0) { std::fprintf(stderr, "message %ld: %s\n", k, alego_bag_last_error(bag)); ++dropped; continue; }   // pcCB would warn and return
       if (n > N) { std::fprintf(stderr, "message %ld: %d points > n_scan * horizon_scan = %d (use --n-scan / --horizon)\n", k, n, N); ++dropped; continue; }
     } else {
@@ -127,6 +138,7 @@ int main(int argc, char** argv) {
     const int flags = alego_scan_process(h, 0, &in, /*IP | LO | LM*/ 7, nullptr, nullptr, &odom, &mapped);
     if (flags < 0) { std::fprintf(stderr, "scan %ld: %s\n", k, alego_last_error(h)); alego_destroy(h); return 1; }
     last_flags = flags;
+    map_track.insert(map_track.end(), mapped.t, mapped.t + 3);
     if (flags & ALEGO_FLAG_LM_KEYFRAME) {   // saveKeyFramesAndFactor stored a frame: fetch it as the pose-graph thread would
       alego_keyframe kf{};
       kf.corner = kc.data(); kf.corner_cap = N; kf.surf = ks.data(); kf.surf_cap = N; kf.outlier = ko.data(); kf.outlier_cap = N;
@@ -152,12 +164,58 @@ int main(int argc, char** argv) {
       if (gr.applied) std::printf("closed: scan %ld slot %d poses %d loops %d iterations %d cost %.9g -> %.9g\n", k, slot, gr.n_poses, gr.n_loops, gr.iterations, gr.cost0, gr.cost);
     }
   }
+  std::string loc_json;
+  if (localize) {   // the second half: a fresh handle localises the same scans in the map the first one built
+    int32_t st[4] = {0, 0, 0, 0};
+    if (alego_map_status(h, 0, st) != ALEGO_OK) { std::fprintf(stderr, "map_status: %s\n", alego_last_error(h)); alego_destroy(h); return 1; }
+    const int nf = st[0];
+    std::vector<std::vector<alego_point>> clouds((size_t)nf * 3);
+    std::vector<alego_kf_in> frames(nf);
+    for (int i = 0; i < nf; ++i) {
+      alego_keyframe kf{};
+      kf.corner = kc.data(); kf.corner_cap = N; kf.surf = ks.data(); kf.surf_cap = N; kf.outlier = ko.data(); kf.outlier_cap = N;
+      if (alego_map_get_keyframe(h, 0, i, &kf) < 0) { std::fprintf(stderr, "map_get_keyframe: %s\n", alego_last_error(h)); alego_destroy(h); return 1; }
+      clouds[i * 3 + 0].assign(kc.begin(), kc.begin() + kf.n_corner);
+      clouds[i * 3 + 1].assign(ks.begin(), ks.begin() + kf.n_surf);
+      clouds[i * 3 + 2].assign(ko.begin(), ko.begin() + kf.n_outlier);
+      for (int a = 0; a < 6; ++a) frames[i].pose[a] = kf.pose[a];
+      frames[i].corner = clouds[i * 3 + 0].data(); frames[i].n_corner = kf.n_corner;
+      frames[i].surf = clouds[i * 3 + 1].data(); frames[i].n_surf = kf.n_surf;
+      frames[i].outlier = clouds[i * 3 + 2].data(); frames[i].n_outlier = kf.n_outlier;
+    }
+    alego_handle* hl = nullptr;
+    if (alego_create(&P, 0, 1, 1, &hl)) { std::fprintf(stderr, "alego_create (localising handle) failed\n"); alego_destroy(h); return 1; }
+    if (alego_loc_enable(hl, frames.data(), nf, loc_radius) != ALEGO_OK) { std::fprintf(stderr, "loc_enable: %s\n", alego_last_error(hl)); alego_destroy(hl); alego_destroy(h); return 1; }
+    alego_pose lo{}, lm{};
+    double max_dev = 0.0;
+    for (long k = 0; k < n_scans; ++k) {
+      int n;
+      double stamp = 0.1 * k;
+      if (bag) {
+        n = alego_bag_read_pc2(bag, topic.c_str(), k, pts.data(), cap_in, &stamp, nullptr);
+        if (n < 0 || n > N) continue;
+      } else {
+        n = alego_synth_scan(&P, 0, k, 0, pts.data(), N);
+      }
+      alego_scan_in in{pts.data(), n, stamp};
+      const int flags = alego_scan_process(hl, 0, &in, 7, nullptr, nullptr, &lo, &lm);
+      if (flags < 0) { std::fprintf(stderr, "localise scan %ld: %s\n", k, alego_last_error(hl)); alego_destroy(hl); alego_destroy(h); return 1; }
+      for (int a = 0; a < 3; ++a) {
+        const double dev = lm.t[a] - map_track[(size_t)k * 3 + a];
+        if (!(std::fabs(dev) <= max_dev)) max_dev = std::fabs(dev);   // (a NaN sticks)
+      }
+    }
+    char buf[256];
+    std::snprintf(buf, sizeof(buf), ", \"loc_frames\": %d, \"loc_map_t\": [%.17g, %.17g, %.17g], \"loc_max_dev\": %.9g", nf, lm.t[0], lm.t[1], lm.t[2], max_dev);
+    loc_json = buf;
+    alego_destroy(hl);
+  }
   std::printf("{\"scans\": %ld, \"dropped\": %d, \"flags\": %d, \"key_frames\": %d, \"resident_key_frames\": %d, "
               "\"odom_t\": [%.17g, %.17g, %.17g], \"map_t\": [%.17g, %.17g, %.17g], \"map_params\": [%.17g, %.17g, %.17g, %.17g, %.17g, %.17g], "
-              "\"last_key_pose\": [%.9g, %.9g, %.9g, %.9g, %.9g, %.9g]}\n",
+              "\"last_key_pose\": [%.9g, %.9g, %.9g, %.9g, %.9g, %.9g]%s}\n",
               n_scans, dropped, last_flags, key_frames, alego_lm_keyframe_count(h, 0), odom.t[0], odom.t[1], odom.t[2], mapped.t[0], mapped.t[1], mapped.t[2],
               mapped.params[0], mapped.params[1], mapped.params[2], mapped.params[3], mapped.params[4], mapped.params[5],
-              last_key_pose[0], last_key_pose[1], last_key_pose[2], last_key_pose[3], last_key_pose[4], last_key_pose[5]);
+              last_key_pose[0], last_key_pose[1], last_key_pose[2], last_key_pose[3], last_key_pose[4], last_key_pose[5], loc_json.c_str());
   int rc = 0;
   if (!map_dir.empty()) {   // saveMapCB + the /laser_cloud_surround cloud, from the archive at the key poses that hold now
     struct { const char* name; int kinds; float leaf; } files[] = {

@@ -469,6 +469,37 @@ int alego_graph_get_estimate(alego_handle* h, int slot, int32_t first, int32_t n
 int alego_graph_residuals(const double* poses12, int32_t n_poses, const alego_graph_edge* edges, int32_t n_edges,
                           double* whitened6, double* jac_from36, double* jac_to36);
 
+/* ---- localisation: many streams against ONE frozen key-frame map -------------------------------------
+ * A handle-wide mode, off by default (nothing of it is allocated or launched then).  alego_loc_enable hands the handle N key frames — pose
+ * and sensor-frame clouds, exactly what alego_map_get_keyframe returns from a mapping run; from then on EVERY slot localises in that map.
+ * ImageProjection, feature extraction, LaserOdometry, LaserMapping's gate and laserOdomHandler are unchanged.  A mapping frame of a slot
+ *   1  selects its window: p = (float)t_map2laser_ after transformAssociateToMap; frame i is a candidate when its f32 squared distance
+ *      ((dx dx) + dy dy) + dz dz to p is < (float)(radius * radius); of the candidates the K = recent_keyframe_num smallest in the order
+ *      (d2 bits, id) are kept; the window is their ids in ascending order; a non-finite p selects nothing.  (The project's own rule, not
+ *      the reference's surround-key-frame bookkeeping of laserMapping.cpp:245-313.)
+ *   2  builds the local map of the window as :238-243 / :315-319 do, in window order — only when the window differs from the last one;
+ *   3  runs downsampleCurrentScan, scan2MapOptimization and transformUpdate as they are, with the same guards;
+ *   4  never saves a key frame: ALEGO_FLAG_LM_KEYFRAME is never returned, alego_lm_keyframe_count stays 0, the optimised params_ reach
+ *      transformUpdate as they are;
+ *   5  with an empty window (off the map) down-samples the scan, does not optimise and leaves map -> odom exactly as it was.
+ * The initial pose of a slot is set with alego_lm_apply_correction on the fresh slot (map -> odom = [R | c]); params_, from which the
+ * first registration starts, with alego_set_lm_params.
+ *   alego_loc_select   host only, plain C++: the selection rule above over keyposes6[n][6]; ids ascending, returns their count
+ *                      (ALEGO_ERR_ARG for null / negative arguments).  radius <= 0: 50.0.
+ *   alego_loc_enable   once, before the first scan of any slot.  radius <= 0: 50.0 (surround_keyframe_search_radius_, LM.cpp:183).
+ *                      ALEGO_ERR_ARG: a second call, a call after a scan, with the archive / graph enabled or after alego_stream_setup.
+ *                      ALEGO_ERR_CAPACITY (+ alego_last_error): a frame exceeds the handle's key-frame capacities, more than 8192 frames,
+ *                      or the store does not fit.  Device memory: 32 * (corner capacity + surf capacity + outlier capacity) + 112 B per
+ *                      frame, once per handle; the slots' own key-frame rings are released.
+ *   alego_loc_status   out = {map frames, frames in the window of the last mapping frame, local-map rebuilds so far, 1 if that frame optimised}
+ * On a localising handle alego_map_enable / alego_graph_enable, every alego_map_* / alego_graph_* call that takes a handle,
+ * alego_loop_search, alego_lm_add_keyframe / _set_keypose / _reset_window / _get_keyframe, alego_stream_setup, alego_dist_init and
+ * alego_debug_set_option("ALEGO_MAP_MERGE", 0) return ALEGO_ERR_ARG.  alego_debug_get(.., "lm_window") returns the window's map-frame ids;
+ * doubles 44..46 of "lm_state" hold p of the last mapping frame. */
+int alego_loc_select(const float* keyposes6, int32_t n, const float xyz[3], double radius, int32_t k, int32_t* ids);
+int alego_loc_enable(alego_handle* h, const alego_kf_in* frames, int32_t n, double radius);
+int alego_loc_status(alego_handle* h, int slot, int32_t out[4]);
+
 /* ---- one scan-to-map registration sharded over the GPUs of a node (BASELINE.json config 5) ----------------
  * One process per GPU; every rank feeds its handle the SAME scans and so keeps a bit-identical replica of the stream's state
  * (ImageProjection, feature extraction, LaserOdometry and the local map are cheap and are computed redundantly).  What is split
