@@ -62,6 +62,18 @@ DEV_INLINE DQuat dq_inverse(const DQuat& q) {
   const double n2 = q.w * q.w + q.x * q.x + q.y * q.y + q.z * q.z;
   return DQuat{q.w / n2, -q.x / n2, -q.y / n2, -q.z / n2};
 }
+DEV_INLINE DQuat ldq(const double* p) { return DQuat{p[0], p[1], p[2], p[3]}; }
+DEV_INLINE void stq(double* p, const DQuat& q) { p[0] = q.w; p[1] = q.x; p[2] = q.y; p[3] = q.z; }
+// correctPoses (laserMapping.cpp:579-580): the pose (q[4], t[3]) <- [R | c] * pose, rc_ the 3x4 [R | c] of a loop-closure correction (f32 or f64)
+template <class T> DEV_INLINE void dq_apply_correction(double* q, double* t3, const T* rc_) {
+  double rc[12], R[9], M[9], t[3];
+  for (int k = 0; k < 12; ++k) rc[k] = (double)rc_[k];
+  dq_to_mat(ldq(q), R);
+  for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) M[i * 3 + j] = rc[i * 4 + 0] * R[0 * 3 + j] + rc[i * 4 + 1] * R[1 * 3 + j] + rc[i * 4 + 2] * R[2 * 3 + j];
+  for (int i = 0; i < 3; ++i) t[i] = rc[i * 4 + 0] * t3[0] + rc[i * 4 + 1] * t3[1] + rc[i * 4 + 2] * t3[2] + rc[i * 4 + 3];
+  stq(q, dq_from_mat(M));
+  for (int i = 0; i < 3; ++i) t3[i] = t[i];
+}
 
 // Pose-dependent terms shared by every residual of one evaluation.
 struct PoseTerms {

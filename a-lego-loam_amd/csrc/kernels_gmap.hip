@@ -24,7 +24,7 @@
 #include "../../include/alego_mi355x.h"
 #include "gmap.h"
 #include "guard_alloc.h"
-#include "lm_ctx.h"
+#include "kf_store.h"
 #include "pg_math.h"
 #include "prof.h"
 #include "vgrid.h"
@@ -48,41 +48,38 @@ __global__ void __launch_bounds__(GM_T) map_archive(DevCtx d, LmCtx L, int force
   const int slot = blockIdx.x + d.slot0;
   const int* li = L.li + (size_t)slot * LI_COUNT;
   if (!force && !li[LI_KF_ADDED]) return;
-  const size_t rs = (size_t)slot * L.KR + (li[LI_NKF] - 1) % L.KR;
-  const int* kc = L.kf_cnt + rs * 4;
-  const int nc = kc[0], ns = kc[1], no = kc[2];
-  int* st = L.arc_stat + (size_t)slot * 4;
-  const int nf = st[0], dropped = st[1], np = st[2];
+  const KfRingRow R = kf_ring_row_at(L, slot, kf_entry(L, li[LI_NKF] - 1), KF_CORNER);
+  const int nc = R.cnt[KF_CORNER], ns = R.cnt[KF_SURF], no = R.cnt[KF_OUTL];
+  int* st = arc_stat_of(L, slot);
+  const int nf = st[AS_FRAMES], dropped = st[AS_DROPPED], np = st[AS_POINTS];
   const bool fits = dropped == 0 && nf < L.arc_frames_cap && (long long)np + nc + ns + no <= (long long)L.arc_points_cap;
   __syncthreads();   // every thread has read the counters before thread 0 moves them
   if (!fits) {
-    if (threadIdx.x == 0) st[1] = dropped + 1;
+    if (threadIdx.x == 0) st[AS_DROPPED] = dropped + 1;
     return;
   }
   float4* dst = L.arc_pts + (size_t)slot * L.arc_points_cap + np;
-  const float4* rc = L.kf_raw_c + rs * L.kf_cap_c;
-  const float4* rsf = L.kf_raw_s + rs * L.kf_cap_s;
-  const float4* ro = L.kf_raw_o + rs * L.kf_cap_o;
+  const float4 *rc = R.raw, *rsf = kf_raw_of(L, R.row, KF_SURF), *ro = kf_raw_of(L, R.row, KF_OUTL);
   for (int i = threadIdx.x; i < nc + ns + no; i += GM_T) dst[i] = i < nc ? rc[i] : (i < nc + ns ? rsf[i - nc] : ro[i - nc - ns]);
-  if (threadIdx.x < 8) L.arc_pose[((size_t)slot * L.arc_frames_cap + nf) * 8 + threadIdx.x] = L.kf_pose[rs * 8 + threadIdx.x];
+  if (threadIdx.x < KF_POSE_W) arc_pose_of(L, slot, nf)[threadIdx.x] = R.pose[threadIdx.x];
   if (threadIdx.x == 0) {
-    int* tab = L.arc_tab + ((size_t)slot * L.arc_frames_cap + nf) * 4;
-    tab[0] = np; tab[1] = nc; tab[2] = ns; tab[3] = no;
+    int* tab = arc_tab_of(L, slot, nf);
+    tab[AT_OFF] = np; tab[AT_N + KF_CORNER] = nc; tab[AT_N + KF_SURF] = ns; tab[AT_N + KF_OUTL] = no;
     // the stamp of the scan that saved the frame; paths without stamps (batch, replay) number the slot's mapping frames
-    L.arc_stamp[(size_t)slot * L.arc_frames_cap + nf] = L.arc_stamped[slot] ? d.scan_stamp[slot] : (double)(li[LI_FRAME] - 1) * d.P.scan_period;
-    st[0] = nf + 1; st[2] = np + nc + ns + no;
+    L.arc_stamp[arc_row(L, slot, nf)] = L.arc_stamped[slot] ? d.scan_stamp[slot] : (double)(li[LI_FRAME] - 1) * d.P.scan_period;
+    st[AS_FRAMES] = nf + 1; st[AS_POINTS] = np + nc + ns + no;
     // the key-pose graph (alego_graph_enable): PriorFactor on the first frame (:495), else BetweenFactor(pre_pose, this pose) (:510-512),
     // both poses as Pose3(Rot3::RzRyRx, xyz) of their f32 key poses; pre_pose is the archived pose of frame nf - 1 as it stands now
     if (L.pg_loops_cap > 0) {
-      alego_graph_edge* e = L.pg_chain + (size_t)slot * L.arc_frames_cap + nf;
+      alego_graph_edge* e = L.pg_chain + arc_row(L, slot, nf);
       double xn[12];
-      pg_from_pose6(L.kf_pose + rs * 8, xn);
+      pg_from_pose6(R.pose, xn);
       e->from = nf - 1; e->to = nf;
       if (nf == 0) {
         for (int k = 0; k < 12; ++k) e->between[k] = xn[k];
       } else {
         double xp[12];
-        pg_from_pose6(L.arc_pose + ((size_t)slot * L.arc_frames_cap + nf - 1) * 8, xp);
+        pg_from_pose6(arc_pose_of(L, slot, nf - 1), xp);
         pg_between(xp, xn, e->between);
       }
       for (int k = 0; k < 6; ++k) e->variance[k] = L.pg_odom_var[k];
@@ -95,18 +92,13 @@ void launch_map_archive(const DevCtx& d, const LmCtx& L, int force, hipStream_t 
 }
 
 // ---- assembly -----------------------------------------------------------------------------------------------------
-DEV_INLINE int sel_count(const int* tab, int kinds) {
-  return ((kinds & 2) ? tab[1] : 0) + ((kinds & 1) ? tab[2] : 0) + ((kinds & 4) ? tab[3] : 0);
-}
-
 // one workgroup: off[f] = selected points of frames [0, f), off[nf] = *n = the total
 __global__ void __launch_bounds__(GS_T) map_offsets(LmCtx L, int slot, int nf, int kinds, int* off, int* n) {
   __shared__ int s_w[17];
-  const int* tab = L.arc_tab + (size_t)slot * L.arc_frames_cap * 4;
   int carry = 0;
   for (int f0 = 0; f0 < nf; f0 += GS_T) {
     const int f = f0 + threadIdx.x;
-    const int v = f < nf ? sel_count(tab + (size_t)f * 4, kinds) : 0;
+    const int v = f < nf ? kf_sel_count(kf_arc_frame(L, slot, f), kinds) : 0;
     int tot;
     const int ex = block_excl_scan<GS_T / 64>(v, s_w, &tot);
     if (f < nf) off[f] = carry + ex;
@@ -119,17 +111,14 @@ __global__ void __launch_bounds__(GS_T) map_offsets(LmCtx L, int slot, int nf, i
 // frame index (transformPointCloud(cloud, pose, idx), laserMapping.h:178-186)
 __global__ void __launch_bounds__(GM_T) map_gather(LmCtx L, int slot, int kinds, const int* off, float4* out) {
   const int f = blockIdx.x;
-  const int* tab = L.arc_tab + ((size_t)slot * L.arc_frames_cap + f) * 4;
-  const float4* src = L.arc_pts + (size_t)slot * L.arc_points_cap + tab[0];
-  const int nc = tab[1], ns = tab[2], no = tab[3];
-  const int ks = (kinds & 1) ? ns : 0, kc = (kinds & 2) ? nc : 0, ko = (kinds & 4) ? no : 0;
+  const KfArcFrame A = kf_arc_frame(L, slot, f);
+  const int n = kf_sel_count(A, kinds);
   float m[3][4];
-  keypose_matrix(L.arc_pose + ((size_t)slot * L.arc_frames_cap + f) * 8, m);
+  keypose_matrix(A.pose, m);
   float4* dst = out + off[f];
   const float fid = (float)f;
-  for (int i = threadIdx.x; i < ks + kc + ko; i += GM_T) {
-    const int j = i < ks ? nc + i : (i < ks + kc ? i - ks : nc + ns + (i - ks - kc));   // (archive layout: corner | surf | outlier)
-    float4 p = kf_transform(m, src[j]);
+  for (int i = threadIdx.x; i < n; i += GM_T) {
+    float4 p = kf_transform(m, A.pts[kf_arc_index(A.nc, A.ns, kinds, i)]);
     if (kinds & 8) p.w = fid;
     dst[i] = p;
   }

@@ -28,7 +28,7 @@
 #include "../../include/alego_mi355x.h"
 #include "dev_cost.h"
 #include "guard_alloc.h"
-#include "lm_ctx.h"
+#include "kf_store.h"
 #include "pg_math.h"
 #include "pgraph.h"
 #include "prof.h"
@@ -57,17 +57,15 @@ struct PgWork {
   double* C;       // [S][6 Lmax][6 Lmax]
 };
 
-DEV_INLINE DQuat ldq(const double* p) { return DQuat{p[0], p[1], p[2], p[3]}; }
-DEV_INLINE void stq(double* p, const DQuat& q) { p[0] = q.w; p[1] = q.x; p[2] = q.y; p[3] = q.z; }
 DEV_INLINE const alego_graph_edge* pg_edge_of(const LmCtx& L, int slot, int Nmax, int e) {
-  return e < Nmax ? L.pg_chain + (size_t)slot * L.arc_frames_cap + e : L.pg_loops + (size_t)slot * L.pg_loops_cap + (e - Nmax);
+  return e < Nmax ? L.pg_chain + arc_row(L, slot, e) : L.pg_loops + (size_t)slot * L.pg_loops_cap + (e - Nmax);
 }
 
 __global__ void __launch_bounds__(PG_T) pg_init(LmCtx L, PgWork W) {
   const int q = blockIdx.y, k = blockIdx.x * PG_T + threadIdx.x;
   const int* ctl = W.ctl + q * PC_COUNT;
   if (k >= ctl[PC_N]) return;
-  pg_from_pose6(L.arc_pose + ((size_t)ctl[PC_SLOT] * L.arc_frames_cap + k) * 8, W.X + ((size_t)q * W.Nmax + k) * 12);
+  pg_from_pose6(arc_pose_of(L, ctl[PC_SLOT], k), W.X + ((size_t)q * W.Nmax + k) * 12);
 }
 
 // grid (edge tiles, chunk entries); force: also the slots that have finished (the final cost)
@@ -404,8 +402,8 @@ __global__ void __launch_bounds__(PG_T) pg_store(LmCtx L, PgWork W) {
   const int q = blockIdx.y, t = blockIdx.x * PG_T + threadIdx.x;
   const int* ctl = W.ctl + q * PC_COUNT;
   if (ctl[PC_STATUS] < 1 || t >= ctl[PC_N] * 12) return;
-  L.pg_est[(size_t)ctl[PC_SLOT] * L.arc_frames_cap * 12 + t] = W.X[(size_t)q * W.Nmax * 12 + t];
-  if (t == 0) L.pg_stat[ctl[PC_SLOT] * 4 + 2] = ctl[PC_N];
+  L.pg_est[arc_row(L, ctl[PC_SLOT], 0) * 12 + t] = W.X[(size_t)q * W.Nmax * 12 + t];
+  if (t == 0) pg_stat_of(L, ctl[PC_SLOT])[PS_EST] = ctl[PC_N];
 }
 
 // ---- correctPoses (:561-584) for the slots with apply[slot] != 0 ------------------------------------------------------------
@@ -415,30 +413,22 @@ __global__ void __launch_bounds__(PG_T) pg_apply(LmCtx L, const int* apply) {
   const int slot = blockIdx.x;
   if (!apply[slot]) return;
   int* li = L.li + (size_t)slot * LI_COUNT;
-  const int N = L.pg_stat[slot * 4 + 2], nkf = li[LI_NKF];
+  const int N = pg_stat_of(L, slot)[PS_EST], nkf = li[LI_NKF];
   for (int k = threadIdx.x; k < N; k += PG_T) {
     float kp[6];
-    pg_to_pose6(L.pg_est + ((size_t)slot * L.arc_frames_cap + k) * 12, kp);
-    float* ap = L.arc_pose + ((size_t)slot * L.arc_frames_cap + k) * 8;
+    pg_to_pose6(L.pg_est + arc_row(L, slot, k) * 12, kp);
+    float* ap = arc_pose_of(L, slot, k);
     for (int i = 0; i < 6; ++i) ap[i] = kp[i];
     if (k < nkf && k >= nkf - L.K) {
-      float* rp = L.kf_pose + ((size_t)slot * L.KR + k % L.KR) * 8;
+      float* rp = kf_pose_of(L, kf_row(L, slot, k));
       for (int i = 0; i < 6; ++i) rp[i] = kp[i];
     }
   }
   if (threadIdx.x == 0) {
-    li[LI_REC_CNT] = 0; li[LI_DIRTY] = 1; li[LI_UVALID] = 0;
+    kf_reset_window([&](int w, int v) { li[w] = v; });
     double* ld = L.ld + (size_t)slot * LD_COUNT;
-    const float* cf = L.pg_corr + (size_t)slot * 16;
-    double rc[12], R[9], M[9], t[3];
-    for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) rc[r * 4 + c] = (double)cf[r * 4 + c];
-    dq_to_mat(ldq(ld + LD_Q_M2O), R);
-    for (int i = 0; i < 3; ++i)
-      for (int j = 0; j < 3; ++j) M[i * 3 + j] = rc[i * 4 + 0] * R[0 * 3 + j] + rc[i * 4 + 1] * R[1 * 3 + j] + rc[i * 4 + 2] * R[2 * 3 + j];
-    for (int i = 0; i < 3; ++i) t[i] = rc[i * 4 + 0] * ld[LD_T_M2O + 0] + rc[i * 4 + 1] * ld[LD_T_M2O + 1] + rc[i * 4 + 2] * ld[LD_T_M2O + 2] + rc[i * 4 + 3];
-    stq(ld + LD_Q_M2O, dq_from_mat(M));
-    for (int i = 0; i < 3; ++i) ld[LD_T_M2O + i] = t[i];
-    L.pg_stat[slot * 4 + 1] = 0;
+    dq_apply_correction(ld + LD_Q_M2O, ld + LD_T_M2O, L.pg_corr + (size_t)slot * 16);
+    pg_stat_of(L, slot)[PS_CLOSED] = 0;
   }
 }
 
@@ -450,18 +440,7 @@ __global__ void __launch_bounds__(PG_T) pg_retransform(LmCtx L, const int* apply
   int* li = L.li + (size_t)slot * LI_COUNT;
   const int nkf = li[LI_NKF], f = nkf - min(L.K, nkf) + j;
   if (f >= nkf) return;
-  const int ring = f % L.KR;
-  const size_t rs = (size_t)slot * L.KR + ring;
-  float m[3][4];
-  keypose_matrix(L.kf_pose + rs * 8, m);
-  const float4* raw = kind == 0 ? L.kf_raw_c + rs * L.kf_cap_c : (kind == 1 ? L.kf_raw_s + rs * L.kf_cap_s : L.kf_raw_o + rs * L.kf_cap_o);
-  const int cap = kind == 0 ? L.kf_cap_c : (kind == 1 ? L.kf_cap_s : L.kf_cap_o);
-  const int* kc = L.kf_cnt + rs * 4;
-  const int n_c = kc[0], n_s = kc[1], n_o = kc[2];
-  const int n = min(kind == 0 ? n_c : (kind == 1 ? n_s : n_o), cap);
-  float4* dst = kind == 0 ? L.kf_tmp_c + (size_t)slot * L.kf_cap_c : L.kf_tmp_s + (size_t)slot * L.total_cap + (kind == 1 ? 0 : n_s);
-  for (int i = blockIdx.x * PG_T + threadIdx.x; i < n; i += gridDim.x * PG_T) dst[i] = kf_transform(m, raw[i]);
-  if (blockIdx.x == 0 && threadIdx.x == 0 && kind == 0) { li[LI_TMPN_C] = n_c; li[LI_TMPN_S] = n_s + n_o; li[LI_KF_PEND_RING] = ring; li[LI_KF_PENDING] = 1; }
+  kf_row_to_tmp<PG_T>(L, slot, kf_entry(L, f), kind, false);
 }
 // the sort jobs ran: the frame is in its ring entry, the voxel lists of an applied slot no longer describe its window.  all: after the
 // flush of the frames the last mapping frame left pending, every slot of the group is done with its sort (as map_update notes it), so the
@@ -491,8 +470,8 @@ __global__ void pg_append(LmCtx L, const PgAppend* a, int n) {
   L.pg_loops[(size_t)a[i].slot * L.pg_loops_cap + a[i].index] = a[i].e;
   if (a[i].last) {
     for (int k = 0; k < 16; ++k) L.pg_corr[(size_t)a[i].slot * 16 + k] = a[i].corr[k];
-    L.pg_stat[a[i].slot * 4 + 0] = a[i].index + 1;
-    L.pg_stat[a[i].slot * 4 + 1] = 1;
+    pg_stat_of(L, a[i].slot)[PS_LOOPS] = a[i].index + 1;
+    pg_stat_of(L, a[i].slot)[PS_CLOSED] = 1;
   }
 }
 
@@ -544,12 +523,12 @@ bool pg_finite_edge(const alego_graph_edge& e) {
 int pg_fail(std::string* err, const char* msg, int rc) { *err = msg; return rc; }
 // the counters of one slot: arc4 = LmCtx::arc_stat, pg4 = LmCtx::pg_stat
 int pg_read_slot(const LmCtx& L, int slot, int* arc4, int* pg4, std::string* err) {
-  if (hipMemcpy(arc4, L.arc_stat + (size_t)slot * 4, 4 * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
-      hipMemcpy(pg4, L.pg_stat + (size_t)slot * 4, 4 * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return pg_fail(err, "graph: device read failed", ALEGO_ERR_HIP);
+  if (hipMemcpy(arc4, arc_stat_of(L, slot), AS_W * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(pg4, pg_stat_of(L, slot), PS_W * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return pg_fail(err, "graph: device read failed", ALEGO_ERR_HIP);
   return 0;
 }
 int pg_read_stats(const LmCtx& L, int n_slots, std::vector<int>* arc, std::vector<int>* pg, std::string* err) {
-  arc->resize((size_t)n_slots * 4); pg->resize((size_t)n_slots * 4);
+  arc->resize((size_t)n_slots * AS_W); pg->resize((size_t)n_slots * PS_W);
   if (hipMemcpy(arc->data(), L.arc_stat, arc->size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
       hipMemcpy(pg->data(), L.pg_stat, pg->size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return pg_fail(err, "graph: device read failed", ALEGO_ERR_HIP);
   return 0;
@@ -557,34 +536,34 @@ int pg_read_stats(const LmCtx& L, int n_slots, std::vector<int>* arc, std::vecto
 }  // namespace
 
 int graph_status(const LmCtx& L, int slot, int* out4, std::string* err) {
-  int arc[4], pg[4];
+  int arc[AS_W], pg[PS_W];
   if (int r = pg_read_slot(L, slot, arc, pg, err)) return r;
-  out4[0] = arc[0]; out4[1] = pg[0]; out4[2] = pg[1]; out4[3] = pg[2];
+  out4[0] = arc[AS_FRAMES]; out4[1] = pg[PS_LOOPS]; out4[2] = pg[PS_CLOSED]; out4[3] = pg[PS_EST];
   return 0;
 }
 
 int graph_get_edges(const LmCtx& L, int slot, int kind, int first, int n, alego_graph_edge* out, std::string* err) {
-  int arc[4], pg[4];
+  int arc[AS_W], pg[PS_W];
   if (int r = pg_read_slot(L, slot, arc, pg, err)) return r;
-  const int have = kind == 0 ? arc[0] : pg[0];
+  const int have = kind == 0 ? arc[AS_FRAMES] : pg[PS_LOOPS];
   if ((kind != 0 && kind != 1) || first < 0 || n < 0 || first > have || n > have - first || (n > 0 && !out)) return pg_fail(err, "graph_get_edges: range beyond the stored edges", ALEGO_ERR_ARG);
   if (n == 0) return 0;
-  const alego_graph_edge* src = kind == 0 ? L.pg_chain + (size_t)slot * L.arc_frames_cap + first : L.pg_loops + (size_t)slot * L.pg_loops_cap + first;
+  const alego_graph_edge* src = kind == 0 ? L.pg_chain + arc_row(L, slot, first) : L.pg_loops + (size_t)slot * L.pg_loops_cap + first;
   if (hipMemcpy(out, src, (size_t)n * sizeof(alego_graph_edge), hipMemcpyDeviceToHost) != hipSuccess) return pg_fail(err, "graph_get_edges: copy failed", ALEGO_ERR_HIP);
   return 0;
 }
 
 int graph_set_edges(const LmCtx& L, int slot, int first, int n, const alego_graph_edge* chain, std::string* err) {
-  int arc[4], pg[4];
+  int arc[AS_W], pg[PS_W];
   if (int r = pg_read_slot(L, slot, arc, pg, err)) return r;
-  const int have = arc[0];
+  const int have = arc[AS_FRAMES];
   if (first < 0 || n < 0 || first > have || n > have - first || (n > 0 && !chain)) return pg_fail(err, "graph_set_edges: range beyond the archived frames", ALEGO_ERR_ARG);
   for (int i = 0; i < n; ++i) {
     if (chain[i].to != first + i || chain[i].from != first + i - 1) return pg_fail(err, "graph_set_edges: chain edge i is the prior (from = -1, to = 0) or i - 1 -> i", ALEGO_ERR_ARG);
     if (!pg_finite_edge(chain[i])) return pg_fail(err, "graph_set_edges: measurement not finite or variance not positive and finite", ALEGO_ERR_ARG);
   }
   if (n == 0) return 0;
-  if (hipMemcpy(L.pg_chain + (size_t)slot * L.arc_frames_cap + first, chain, (size_t)n * sizeof(alego_graph_edge), hipMemcpyHostToDevice) != hipSuccess)
+  if (hipMemcpy(L.pg_chain + arc_row(L, slot, first), chain, (size_t)n * sizeof(alego_graph_edge), hipMemcpyHostToDevice) != hipSuccess)
     return pg_fail(err, "graph_set_edges: copy failed", ALEGO_ERR_HIP);
   return 0;
 }
@@ -598,10 +577,10 @@ int graph_append(PgCtx** pc, const LmCtx& L, int n_slots, const std::vector<PgAp
   if (int r = pg_read_stats(L, n_slots, &arc, &pg, err)) return r;
   std::vector<PgAppend> a = in;
   std::vector<int> cnt(n_slots), last(n_slots, -1);
-  for (int s = 0; s < n_slots; ++s) cnt[s] = pg[s * 4];
+  for (int s = 0; s < n_slots; ++s) cnt[s] = pg[s * PS_W + PS_LOOPS];
   for (size_t i = 0; i < a.size(); ++i) {
     const alego_graph_edge& e = a[i].e;
-    const int nf = arc[a[i].slot * 4];
+    const int nf = arc[a[i].slot * AS_W + AS_FRAMES];
     if (e.from < 0 || e.to < 0 || e.from >= nf || e.to >= nf || e.from == e.to) return pg_fail(err, "graph: loop edge ids outside the archived frames, or from == to", ALEGO_ERR_ARG);
     if (!pg_finite_edge(e)) return pg_fail(err, "graph: measurement not finite or variance not positive and finite", ALEGO_ERR_ARG);
     if (cnt[a[i].slot] >= L.pg_loops_cap) return pg_fail(err, "graph: max_loops loop edges are stored already", ALEGO_ERR_CAPACITY);
@@ -627,11 +606,11 @@ int graph_append(PgCtx** pc, const LmCtx& L, int n_slots, const std::vector<PgAp
 }
 
 int graph_get_estimate(const LmCtx& L, int slot, int first, int n, double* poses12, std::string* err) {
-  int arc[4], pg[4];
+  int arc[AS_W], pg[PS_W];
   if (int r = pg_read_slot(L, slot, arc, pg, err)) return r;
-  const int have = pg[2];
+  const int have = pg[PS_EST];
   if (first < 0 || n < 0 || first > have || n > have - first || (n > 0 && !poses12)) return pg_fail(err, "graph_get_estimate: range beyond the poses of the last optimise", ALEGO_ERR_ARG);
-  if (n && hipMemcpy(poses12, L.pg_est + ((size_t)slot * L.arc_frames_cap + first) * 12, (size_t)n * 12 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+  if (n && hipMemcpy(poses12, L.pg_est + arc_row(L, slot, first) * 12, (size_t)n * 12 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
     return pg_fail(err, "graph_get_estimate: copy failed", ALEGO_ERR_HIP);
   return 0;
 }
@@ -651,8 +630,8 @@ int graph_optimize(PgCtx** pc, const LmCtx& L, int n_slots, const int* slots, in
     const int s = slots[i];
     alego_graph_result& r = out[i];
     std::memset(&r, 0, sizeof(r));
-    r.n_poses = arc[s * 4]; r.n_loops = pg[s * 4];
-    if (arc[s * 4 + 1] > 0) { r.status = -1; continue; }
+    r.n_poses = arc[s * AS_W + AS_FRAMES]; r.n_loops = pg[s * PS_W + PS_LOOPS];
+    if (arc[s * AS_W + AS_DROPPED] > 0) { r.status = -1; continue; }
     if (r.n_poses == 0) { r.status = 0; continue; }
     todo.push_back(i);
     Nmax = std::max(Nmax, r.n_poses); Lmax = std::max(Lmax, r.n_loops);
@@ -710,7 +689,7 @@ int graph_optimize(PgCtx** pc, const LmCtx& L, int n_slots, const int* slots, in
       const int s = slots[todo[c0 + q]];
       r.status = ctl[q * PC_COUNT + PC_STATUS]; r.iterations = ctl[q * PC_COUNT + PC_ITERS];
       r.cost0 = dctl[q * PD_COUNT + PD_COST0]; r.cost = dctl[q * PD_COUNT + PD_COST]; r.last_step = dctl[q * PD_COUNT + PD_STEP];
-      if (r.status == 2 && opt.apply && pg[s * 4 + 1]) { r.applied = 1; (*apply_out)[s] = 1; }
+      if (r.status == 2 && opt.apply && pg[s * PS_W + PS_CLOSED]) { r.applied = 1; (*apply_out)[s] = 1; }
     }
   }
   return 0;

@@ -16,7 +16,7 @@
 #include <vector>
 
 #include "dev_common.h"
-#include "lm_ctx.h"
+#include "kf_store.h"
 #include "prof.h"
 #include "voxel.h"
 #include "icp_math.h"
@@ -158,16 +158,15 @@ int icp_run(const alego_params& P, const alego_kf_in* latest, const alego_kf_in*
   int n_src = 0, n_traw = 0;
   for (int f = 0; f < nf; ++f) {
     const alego_kf_in& k = f == 0 ? *latest : history[f - 1];
-    if (k.n_corner < 0 || k.n_surf < 0 || k.n_outlier < 0 || (k.n_corner && !k.corner) || (k.n_surf && !k.surf) || (k.n_outlier && !k.outlier)) { *err = "loop closure: null cloud / negative count"; return ALEGO_ERR_ARG; }
+    if (!kf_in_valid(k)) { *err = "loop closure: null cloud / negative count"; return ALEGO_ERR_ARG; }
     for (int a = 0; a < 6; ++a) F[f].pose[a] = k.pose[a];
     F[f].off[0] = (int)raw.size(); raw.insert(raw.end(), k.corner, k.corner + k.n_corner);
     F[f].off[1] = (int)raw.size(); raw.insert(raw.end(), k.surf, k.surf + k.n_surf);
     F[f].off[2] = (int)raw.size(); raw.insert(raw.end(), k.outlier, k.outlier + k.n_outlier);
     F[f].off[3] = (int)raw.size();
     int& base = f == 0 ? n_src : n_traw;   // destination order: surf, corner, outlier (laserMapping.cpp:794-796,:805-807)
-    F[f].dst[1] = base; base += k.n_surf;
-    F[f].dst[0] = base; base += k.n_corner;
-    F[f].dst[2] = base; base += k.n_outlier;
+    for (int kind = 0; kind < KF_KINDS; ++kind) F[f].dst[kind] = base + kf_out_start(k.n_corner, k.n_surf, KF_SEL_ALL, kind);
+    base += k.n_surf + k.n_corner + k.n_outlier;
   }
   Temps T;
   IcpFrame* dF; float4 *draw, *dsrc, *dcur, *dtraw, *dtgt; int* dcnt; IcpState* dS; double* dpart;

@@ -14,7 +14,7 @@
 // window in localisation mode, where LI_NKF stays 0 (kernels_loc.hip).
 #include "dev_cost.h"
 #include "prof.h"
-#include "lm_ctx.h"
+#include "kf_store.h"
 #include "gmap.h"
 #include "vgrid.h"
 
@@ -22,8 +22,6 @@
 
 DEV_INLINE double* ldp(const LmCtx& L, int slot) { return L.ld + (size_t)slot * LD_COUNT; }
 DEV_INLINE int* lip(const LmCtx& L, int slot) { return L.li + (size_t)slot * LI_COUNT; }
-DEV_INLINE DQuat ldq(const double* p) { return DQuat{p[0], p[1], p[2], p[3]}; }
-DEV_INLINE void stq(double* p, const DQuat& q) { p[0] = q.w; p[1] = q.x; p[2] = q.y; p[3] = q.z; }
 
 // Map sequence = lm_concat, VoxelGrid of the two maps, lm_grid_*, at the start of every mapping frame.  lm_map_update
 // (called by lm_prepare's bookkeeping thread) replays the deque bookkeeping of extractSurroundingKeyFrames
@@ -145,18 +143,14 @@ __global__ void __launch_bounds__(LM_BLOCK) lm_concat(DevCtx d, LmCtx L) {
   if (!li[LI_REBUILD_FB]) return;
   const int nk = li[LI_REC_CNT];
   if (j >= nk) return;
-  const int* kc = L.kf_cnt + (size_t)slot * L.KR * 4;
-  const int* rec = L.rec + (size_t)slot * L.K;   // frame f lives in ring entry f % KR
+  const int* rec = L.rec + (size_t)slot * L.K;
   int offc = 0, offs = 0;
-  for (int i = 0; i < j; ++i) { const int r = rec[i] % L.KR; offc += kc[r * 4 + 0]; offs += kc[r * 4 + 1] + kc[r * 4 + 2]; }
-  const int ring = rec[j] % L.KR;
-  const int nc = kc[ring * 4 + 0], ns = kc[ring * 4 + 1], no = kc[ring * 4 + 2];
-  const size_t rs = (size_t)slot * L.KR + ring;
+  for (int i = 0; i < j; ++i) { const int* kc = kf_cnt_of(L, kf_row(L, slot, rec[i])); offc += kc[KF_CORNER]; offs += kc[KF_SURF] + kc[KF_OUTL]; }
+  const KfRingRow R = kf_ring_row_at(L, slot, kf_entry(L, rec[j]), KF_CORNER);
+  const int nc = R.cnt[KF_CORNER], ns = R.cnt[KF_SURF], no = R.cnt[KF_OUTL];
   float m[3][4];
-  keypose_matrix(L.kf_pose + rs * 8, m);
-  const float4* sc_ = L.kf_raw_c + rs * L.kf_cap_c;
-  const float4* ss_ = L.kf_raw_s + rs * L.kf_cap_s;
-  const float4* so_ = L.kf_raw_o + rs * L.kf_cap_o;
+  keypose_matrix(R.pose, m);
+  const float4 *sc_ = R.raw, *ss_ = kf_raw_of(L, R.row, KF_SURF), *so_ = kf_raw_of(L, R.row, KF_OUTL);
   float4* dc = L.map_corner_raw + (size_t)slot * L.map_cap_c + offc;
   float4* ds = L.map_surf_raw + (size_t)slot * L.map_cap_s + offs;  // surf then outlier per key frame (:241-242)
   for (int i = blockIdx.x * LM_BLOCK + threadIdx.x; i < nc; i += gridDim.x * LM_BLOCK) dc[i] = kf_transform(m, sc_[i]);
@@ -906,7 +900,7 @@ __global__ void lm_finish(DevCtx d, LmCtx L) {
   bool add = !L.loc_on;   // localisation never saves a key frame: the optimised params_ reach transformUpdate as they are
   if (L.loc_on && li[LI_REC_CNT] == 0) return;   // ... and off the map (empty window) map -> odom stays what it was: dead reckoning
   if (nkf > 0) {
-    const float* pre = L.kf_pose + ((size_t)slot * L.KR + (nkf - 1) % L.KR) * 8;
+    const float* pre = kf_pose_of(L, kf_row(L, slot, nkf - 1));
     const double ex = ld[LD_T_M2L + 0] - (double)pre[0], ey = ld[LD_T_M2L + 1] - (double)pre[1], ez = ld[LD_T_M2L + 2] - (double)pre[2];
     if (ex * ex + ey * ey + ez * ez < d.P.min_keyframe_dist) add = false;  // :501-508
   }
@@ -916,7 +910,7 @@ __global__ void lm_finish(DevCtx d, LmCtx L) {
     const double roll = atan2(R[7], R[8]);
     const double pitch = atan2(-R[6], sqrt(R[7] * R[7] + R[8] * R[8]));
     const double yaw = atan2(R[3], R[0]);
-    float* kp = L.kf_pose + ((size_t)slot * L.KR + nkf % L.KR) * 8;
+    float* kp = kf_pose_of(L, kf_row(L, slot, nkf));
     kp[0] = (float)ld[LD_T_M2L + 0]; kp[1] = (float)ld[LD_T_M2L + 1]; kp[2] = (float)ld[LD_T_M2L + 2];
     kp[3] = (float)roll; kp[4] = (float)pitch; kp[5] = (float)yaw;
     for (int k = 0; k < 6; ++k) ld[LD_PARAMS + k] = (double)kp[k];  // :539-544
@@ -944,42 +938,14 @@ __global__ void __launch_bounds__(LM_BLOCK) lm_store_kf(DevCtx d, LmCtx L, int o
   const int slot = blockIdx.z + d.slot0, kind = blockIdx.y;
   int* li = lip(L, slot);
   if (only_ring < 0 && !li[LI_KF_ADDED]) return;
-  const int ring = only_ring < 0 ? (li[LI_NKF] - 1) % L.KR : only_ring;
-  const size_t rs = (size_t)slot * L.KR + ring;
-  float m[3][4];
-  keypose_matrix(L.kf_pose + rs * 8, m);
-  float4* raw = kind == 0 ? L.kf_raw_c + rs * L.kf_cap_c : (kind == 1 ? L.kf_raw_s + rs * L.kf_cap_s : L.kf_raw_o + rs * L.kf_cap_o);
-  const float4* cur = kind == 0 ? L.cur_corner_ds + (size_t)slot * L.kf_cap_c : (kind == 1 ? L.cur_surf_ds + (size_t)slot * L.kf_cap_s : L.cur_outl_ds + (size_t)slot * L.kf_cap_o);
-  const int cap = kind == 0 ? L.kf_cap_c : (kind == 1 ? L.kf_cap_s : L.kf_cap_o);
-  const int* kc = L.kf_cnt + rs * 4;
-  // counts of the three clouds of this key frame (new frame: the current scan's; re-transform: the stored ones)
-  const int n_c = only_ring < 0 ? min(li[LI_NCUR_C], L.kf_cap_c) : kc[0];
-  const int n_s = only_ring < 0 ? min(li[LI_NCUR_S], L.kf_cap_s) : kc[1];
-  const int n_o = only_ring < 0 ? min(li[LI_NCUR_O], L.kf_cap_o) : kc[2];
-  const int n = min(kind == 0 ? n_c : (kind == 1 ? n_s : n_o), cap);
-  float4* dst = kind == 0 ? L.kf_tmp_c + (size_t)slot * L.kf_cap_c : L.kf_tmp_s + (size_t)slot * L.total_cap + (kind == 1 ? 0 : n_s);
-  for (int i = blockIdx.x * LM_BLOCK + threadIdx.x; i < n; i += gridDim.x * LM_BLOCK) {
-    float4 p;
-    if (only_ring < 0) { p = cur[i]; raw[i] = p; } else { p = raw[i]; }
-    dst[i] = kf_transform(m, p);
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    if (only_ring < 0) L.kf_cnt[rs * 4 + kind] = n;
-    if (kind == 0) { li[LI_TMPN_C] = n_c; li[LI_TMPN_S] = n_s + n_o; li[LI_KF_PEND_RING] = ring; li[LI_KF_PENDING] = 1; }
-  }
+  kf_row_to_tmp<LM_BLOCK>(L, slot, only_ring < 0 ? kf_entry(L, li[LI_NKF] - 1) : only_ring, kind, only_ring < 0);
 }
 
 // one thread: correctPoses :579-580 on map -> odom with the 3x4 [R | c] of the loop-closure correction
 __global__ void lm_apply_correction(DevCtx d, LmCtx L, int slot, const double* rc) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   double* ld = ldp(L, slot);
-  double R[9], M[9], t[3];
-  dq_to_mat(ldq(ld + LD_Q_M2O), R);
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) M[i * 3 + j] = rc[i * 4 + 0] * R[0 * 3 + j] + rc[i * 4 + 1] * R[1 * 3 + j] + rc[i * 4 + 2] * R[2 * 3 + j];
-  for (int i = 0; i < 3; ++i) t[i] = rc[i * 4 + 0] * ld[LD_T_M2O + 0] + rc[i * 4 + 1] * ld[LD_T_M2O + 1] + rc[i * 4 + 2] * ld[LD_T_M2O + 2] + rc[i * 4 + 3];
-  stq(ld + LD_Q_M2O, dq_from_mat(M));
-  for (int i = 0; i < 3; ++i) ld[LD_T_M2O + i] = t[i];
+  dq_apply_correction(ld + LD_Q_M2O, ld + LD_T_M2O, rc);
 }
 
 

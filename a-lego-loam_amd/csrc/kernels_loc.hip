@@ -13,7 +13,7 @@
 
 #include "../../include/alego_mi355x.h"
 #include "dev_common.h"
-#include "lm_ctx.h"
+#include "kf_store.h"
 #include "loc_math.h"
 #include "prof.h"
 #include "wave.h"
@@ -32,10 +32,10 @@ __global__ void __launch_bounds__(LS_T) loc_select(DevCtx d, LmCtx L) {
   const float px = (float)ld[LD_T_M2L + 0], py = (float)ld[LD_T_M2L + 1], pz = (float)ld[LD_T_M2L + 2];   // :250-252, as lc_detect reads it
   const int n = (loc_finite(px) && loc_finite(py) && loc_finite(pz)) ? L.loc_n : 0;
   const float r2 = L.loc_r2;
-  const float* kp = L.kf_pose;   // [frame][8] of the map store
+  const float* kp = kf_pose_of(L, kf_row_at(L, slot, 0));   // the rows of the map store (frame i < loc_n <= fr_mod is entry i)
   const int K = min(L.K, LS_KMAX);
   int c = 0;
-  for (int i = tid; i < n; i += LS_T) c += loc_key(kp + (size_t)i * 8, i, px, py, pz, r2) != ~0ull ? 1 : 0;
+  for (int i = tid; i < n; i += LS_T) c += loc_key(kp + (size_t)i * KF_POSE_W, i, px, py, pz, r2) != ~0ull ? 1 : 0;
   int ncand;
   block_excl_scan<LS_T / 64>(c, s_w, &ncand);
   // more candidates than the window holds: the K-th smallest key, by K rounds of "smallest key above the last one" (keys are unique)
@@ -45,7 +45,7 @@ __global__ void __launch_bounds__(LS_T) loc_select(DevCtx d, LmCtx L) {
     for (int r = 0; r < K; ++r) {
       unsigned long long best = ~0ull;
       for (int i = tid; i < n; i += LS_T) {
-        const unsigned long long key = loc_key(kp + (size_t)i * 8, i, px, py, pz, r2);
+        const unsigned long long key = loc_key(kp + (size_t)i * KF_POSE_W, i, px, py, pz, r2);
         if (r == 0 || key > last) best = min(best, key);
       }
       best = bfly_min_u64(best);
@@ -63,7 +63,7 @@ __global__ void __launch_bounds__(LS_T) loc_select(DevCtx d, LmCtx L) {
   int nsel = 0;
   for (int i0 = 0; i0 < n; i0 += LS_T) {
     const int i = i0 + tid;
-    const unsigned long long key = i < n ? loc_key(kp + (size_t)i * 8, i, px, py, pz, r2) : ~0ull;
+    const unsigned long long key = i < n ? loc_key(kp + (size_t)i * KF_POSE_W, i, px, py, pz, r2) : ~0ull;
     const int sel = (key != ~0ull && key <= thr) ? 1 : 0;
     int tot;
     const int ex = block_excl_scan<LS_T / 64>(sel, s_w, &tot);

@@ -30,7 +30,7 @@
 #include "../../include/alego_mi355x.h"
 #include "guard_alloc.h"
 #include "icp_math.h"
-#include "lm_ctx.h"
+#include "kf_store.h"
 #include "prof.h"
 #include "voxel.h"
 
@@ -52,8 +52,8 @@ struct LcOut { int converged, iterations, n_source, n_target; double fitness; fl
 __global__ void __launch_bounds__(LC_DT) lc_detect(LmCtx L, const int* list, alego_params P, LcDet* det) {
   __shared__ unsigned long long s_min[LC_DT / 64];
   const int b = blockIdx.x, slot = list[b];
-  const int* st = L.arc_stat + (size_t)slot * 4;
-  const int nf = st[0], dropped = st[1];
+  const int* st = arc_stat_of(L, slot);
+  const int nf = st[AS_FRAMES], dropped = st[AS_DROPPED];
   LcDet D;
   memset(&D, 0, sizeof(D));
   D.latest = nf - 1; D.closest = -1; D.jlo = 0; D.jhi = -1;
@@ -65,11 +65,11 @@ __global__ void __launch_bounds__(LC_DT) lc_detect(LmCtx L, const int* list, ale
   const double* ld = L.ld + (size_t)slot * LD_COUNT;
   const float cx = (float)ld[LD_T_M2L + 0], cy = (float)ld[LD_T_M2L + 1], cz = (float)ld[LD_T_M2L + 2];
   const float r2 = (float)(P.lc_search_radius * P.lc_search_radius);
-  const size_t fb = (size_t)slot * L.arc_frames_cap;
+  const size_t fb = arc_row(L, slot, 0);
   const double t_last = L.arc_stamp[fb + nf - 1];
   unsigned long long best = ~0ull;
   for (int i = threadIdx.x; i < nf; i += LC_DT) {
-    const float* kp = L.arc_pose + (fb + i) * 8;
+    const float* kp = arc_pose_of(L, slot, i);
     float r = 0.f, df;
     df = kp[0] - cx; r += df * df; df = kp[1] - cy; r += df * df; df = kp[2] - cz; r += df * df;
     // radiusSearch (f32 d² < r², :778) + the first candidate in (d², id) order that is old enough (:781-788); d² >= 0: its bits order it
@@ -80,17 +80,16 @@ __global__ void __launch_bounds__(LC_DT) lc_detect(LmCtx L, const int* list, ale
   __syncthreads();
   if (threadIdx.x != 0) return;
   for (int w = 1; w < LC_DT / 64; ++w) best = min(best, s_min[w]);
-  const int* tab = L.arc_tab + fb * 4;
-  for (int k = 0; k < 6; ++k) D.pose_latest[k] = L.arc_pose[(fb + nf - 1) * 8 + k];
-  D.n_src = tab[(nf - 1) * 4 + 1] + tab[(nf - 1) * 4 + 2] + tab[(nf - 1) * 4 + 3];
+  for (int k = 0; k < 6; ++k) D.pose_latest[k] = arc_pose_of(L, slot, nf - 1)[k];
+  D.n_src = arc_tab_points(arc_tab_of(L, slot, nf - 1));
   if (best == ~0ull) { D.status = 0; det[b] = D; return; }
   D.status = 1;
   D.closest = (int)(best & 0xffffffffu);
-  for (int k = 0; k < 6; ++k) D.pose_closest[k] = L.arc_pose[(fb + D.closest) * 8 + k];
+  for (int k = 0; k < 6; ++k) D.pose_closest[k] = arc_pose_of(L, slot, D.closest)[k];
   D.jlo = max(0, D.closest - P.lc_search_num);                 // :798-803: j < 0 || j >= latest_history_frame_id_ are skipped
   D.jhi = min(D.latest - 1, D.closest + P.lc_search_num);
   long long n = 0;
-  for (int j = D.jlo; j <= D.jhi; ++j) n += tab[j * 4 + 1] + tab[j * 4 + 2] + tab[j * 4 + 3];
+  for (int j = D.jlo; j <= D.jhi; ++j) n += arc_tab_points(arc_tab_of(L, slot, j));
   D.n_raw = (int)n;
   det[b] = D;
 }
@@ -100,7 +99,6 @@ __global__ void __launch_bounds__(LC_DT) lc_detect(LmCtx L, const int* list, ale
 __global__ void __launch_bounds__(LC_DT) lc_gather(LmCtx L, const LcJob* jobs, const LcDet* det, float4* src, float4* raw) {
   const LcJob J = jobs[blockIdx.y];
   const LcDet& D = det[J.li];
-  const size_t fb = (size_t)J.slot * L.arc_frames_cap;
   int f;
   float4* out;
   if (blockIdx.x == 0) {
@@ -110,18 +108,14 @@ __global__ void __launch_bounds__(LC_DT) lc_gather(LmCtx L, const LcJob* jobs, c
     f = D.jlo + (int)blockIdx.x - 1;
     if (f > D.jhi) return;
     int off = 0;
-    for (int j = D.jlo; j < f; ++j) { const int* t = L.arc_tab + (fb + j) * 4; off += t[1] + t[2] + t[3]; }
+    for (int j = D.jlo; j < f; ++j) off += arc_tab_points(arc_tab_of(L, J.slot, j));
     out = raw + J.raw_off + off;
   }
-  const int* tab = L.arc_tab + (fb + f) * 4;
-  const float4* in = L.arc_pts + (size_t)J.slot * L.arc_points_cap + tab[0];
-  const int nc = tab[1], ns = tab[2], no = tab[3];
+  const KfArcFrame A = kf_arc_frame(L, J.slot, f);
+  const int n = kf_sel_count(A, KF_SEL_ALL);
   float m[3][4];
-  keypose_matrix(L.arc_pose + (fb + f) * 8, m);
-  for (int i = threadIdx.x; i < ns + nc + no; i += LC_DT) {
-    const int j = i < ns ? nc + i : (i < ns + nc ? i - ns : i);   // archive layout corner | surf | outlier -> surf, corner, outlier
-    out[i] = kf_transform(m, in[j]);
-  }
+  keypose_matrix(A.pose, m);
+  for (int i = threadIdx.x; i < n; i += LC_DT) out[i] = kf_transform(m, A.pts[kf_arc_index(A.nc, A.ns, KF_SEL_ALL, i)]);   // surf, corner, outlier
 }
 
 // ---- uniform grid ---------------------------------------------------------------------------------------------------------------

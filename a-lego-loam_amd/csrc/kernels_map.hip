@@ -22,7 +22,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include "dev_common.h"
-#include "lm_ctx.h"
+#include "kf_store.h"
 #include "prof.h"
 #include "vgrid.h"
 
@@ -39,10 +39,10 @@ typedef unsigned long long u64;
 
 DEV_INLINE int* lipm(const LmCtx& L, int slot) { return L.li + (size_t)slot * LI_COUNT; }
 DEV_INLINE const float4* run_pts(const LmCtx& L, int slot, int m, int entry) {
-  return m == 0 ? L.kfs_c + ((size_t)slot * L.fr_stride + entry) * L.kf_cap_c : L.kfs_s + ((size_t)slot * L.fr_stride + entry) * L.total_cap;
+  return m == 0 ? L.kfs_c + kf_row_at(L, slot, entry) * L.kf_cap_c : L.kfs_s + kf_row_at(L, slot, entry) * L.total_cap;
 }
-DEV_INLINE int run_n(const LmCtx& L, int slot, int m, int entry) { return L.kfs_n[(size_t)slot * 2 * L.fr_stride + (size_t)m * L.fr_mod + entry]; }
-DEV_INLINE const float* run_box(const LmCtx& L, int slot, int m, int entry) { return L.kfs_box + ((size_t)slot * 2 * L.fr_stride + (size_t)m * L.fr_mod + entry) * 8; }
+DEV_INLINE int run_n(const LmCtx& L, int slot, int m, int entry) { return L.kfs_n[kf_run_at(L, slot, m, entry)]; }
+DEV_INLINE const float* run_box(const LmCtx& L, int slot, int m, int entry) { return L.kfs_box + kf_run_at(L, slot, m, entry) * 8; }
 DEV_INLINE u64* map_U(const LmCtx& L, int slot, int m) { return m == 0 ? L.U_c + (size_t)slot * L.map_cap_c : L.U_s + (size_t)slot * L.map_cap_s; }
 DEV_INLINE int* map_Ucnt(const LmCtx& L, int slot, int m) { return m == 0 ? L.Ucnt_c + (size_t)slot * L.map_cap_c : L.Ucnt_s + (size_t)slot * L.map_cap_s; }
 DEV_INLINE float4* map_out(const LmCtx& L, int slot, int m) { return m == 0 ? L.map_corner_ds + (size_t)slot * L.map_cap_c : L.map_surf_ds + (size_t)slot * L.map_cap_s; }
@@ -93,12 +93,6 @@ DEV_INLINE void bound_run_pair(const float4* pts, int n, float inv, u64 key_lo, 
   }
   *out_lo = lo0; *out_hi = lo1;
 }
-
-struct MapWork {
-  int* items;      // [cap] packed (slot - slot0) << 12 | m << 11 | chunk   (chunk < 2048)
-  int* count;      // [2]: items, ticket
-  int cap;
-};
 
 #define MU_FCAP 4096      // points of a run whose voxel keys the fast path of map_update stages in LDS (2 x 32 KB)
 #define MU_E 16           // consecutive entries of the voxel list per thread in the fast path
@@ -155,7 +149,7 @@ __global__ void __launch_bounds__(MU_T) map_update(DevCtx d, LmCtx L, MapWork W)
     float mn[3] = {3.402823466e+38f, 3.402823466e+38f, 3.402823466e+38f}, mx[3] = {-3.402823466e+38f, -3.402823466e+38f, -3.402823466e+38f};
     int kraw = 0;
     for (int j = tid; j < ncur; j += MU_T) {
-      const int e = rec[j] % L.fr_mod;
+      const int e = kf_entry(L, rec[j]);
       const int n = run_n(L, slot, m, e);
       kraw += n;
       if (n > 0) {
@@ -197,14 +191,14 @@ __global__ void __launch_bounds__(MU_T) map_update(DevCtx d, LmCtx L, MapWork W)
           if (valid) {
             int a = 0, b = 0;
             while (a < np || b < ncur) {
-              if (b >= ncur || (a < np && s_prev[a] < s_cur[b])) { if (s_prev[a] < nkf - L.fr_mod) valid = false; s_rem[nr++] = s_prev[a++] % L.fr_mod; }   // its ring entry must still hold it
-              else if (a >= np || s_cur[b] < s_prev[a]) s_add[na++] = s_cur[b++] % L.fr_mod;
+              if (b >= ncur || (a < np && s_prev[a] < s_cur[b])) { if (s_prev[a] < nkf - L.fr_mod) valid = false; s_rem[nr++] = kf_entry(L, s_prev[a++]); }   // its ring entry must still hold it
+              else if (a >= np || s_cur[b] < s_prev[a]) s_add[na++] = kf_entry(L, s_cur[b++]);
               else { ++a; ++b; }
             }
           }
           if (!valid) {   // rebuild from nothing: every run of the window is inserted
             nr = 0; na = 0;
-            for (int b = 0; b < ncur; ++b) s_add[na++] = s_cur[b] % L.fr_mod;
+            for (int b = 0; b < ncur; ++b) s_add[na++] = kf_entry(L, s_cur[b]);
           }
           s_nrem = nr; s_nadd = na; s_nU = valid ? li[LI_NU_C + m] : 0; s_err = 0;
         }
@@ -364,17 +358,15 @@ __global__ void __launch_bounds__(MU_T) map_update(DevCtx d, LmCtx L, MapWork W)
     }
     if (pass) {
       float4* out = map_out(L, slot, m);
-      const int* kc = L.kf_cnt + (size_t)slot * L.fr_stride * 4;
       int off = 0;
       for (int j = 0; j < ncur; ++j) {
-        const int e = rec[j] % L.fr_mod;
-        const size_t rs = (size_t)slot * L.fr_stride + e;
+        const KfRingRow R = kf_ring_row_at(L, slot, kf_entry(L, rec[j]), m == 0 ? KF_CORNER : KF_SURF);
         // (the sorted runs lost the input order: the raw clouds are transformed again, in the reference's order)
         float mm[3][4];
-        keypose_matrix(L.kf_pose + rs * 8, mm);
-        const int n0 = m == 0 ? kc[e * 4 + 0] : kc[e * 4 + 1], n1 = m == 0 ? 0 : kc[e * 4 + 2];
-        const float4* a0 = m == 0 ? L.kf_raw_c + rs * L.kf_cap_c : L.kf_raw_s + rs * L.kf_cap_s;
-        const float4* a1 = L.kf_raw_o + rs * L.kf_cap_o;
+        keypose_matrix(R.pose, mm);
+        const int n0 = m == 0 ? R.cnt[KF_CORNER] : R.cnt[KF_SURF], n1 = m == 0 ? 0 : R.cnt[KF_OUTL];
+        const float4* a0 = R.raw;
+        const float4* a1 = kf_raw_of(L, R.row, KF_OUTL);
         for (int i = tid; i < n0 && off + i < cap; i += MU_T) out[off + i] = kf_transform(mm, a0[i]);
         for (int i = tid; i < n1 && off + n0 + i < cap; i += MU_T) out[off + n0 + i] = kf_transform(mm, a1[i]);
         const int n = n0 + n1;
@@ -516,7 +508,7 @@ __global__ void __launch_bounds__(MA_T, 8) map_accum(DevCtx d, LmCtx L, MapWork 
     __syncthreads();
     const u64 key_lo = s_key[0], key_hi = s_key[nr - 1];
     for (int j = tid; j < nwin; j += MA_T) {   // the piece of every run that falls into this chunk's key range
-      const int e = rec[j] % L.fr_mod;
+      const int e = kf_entry(L, rec[j]);
       const float4* pts = run_pts(L, slot, m, e);
       const int n = run_n(L, slot, m, e);
       s_ent[j] = (unsigned short)e;

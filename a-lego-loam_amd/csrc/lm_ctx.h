@@ -46,6 +46,11 @@ enum {
 
 struct alego_graph_edge;   // include/alego_mi355x.h
 
+struct MapWork {     // work list of map_accum, written by map_update (kernels_map.hip)
+  int* items;      // [cap] packed (slot - slot0) << 12 | m << 11 | chunk   (chunk < 2048)
+  int* count;      // [2]: items, ticket
+  int cap;
+};
 struct GridGeom { int ox, oy, oz; float inv; int gx, gy, gz, ncell; };   // cell of x: floorf(x * inv) - ox (lm_grid_build)
 
 
@@ -84,9 +89,8 @@ DEV_INLINE float4 kf_transform(const float m[3][4], const float4& p) {   // lase
 
 struct LmCtx {
   int K;                         // recent_keyframe_num
-  // Where the key frames of a slot live.  Frame f of slot s is row  s * fr_stride + f % fr_mod  of kfs_c / kfs_s / kf_raw_* / kf_cnt / kf_pose, and
-  // entry  s * 2 * fr_stride + m * fr_mod + f % fr_mod  of kfs_n / kfs_box.  SLAM: the slot's own ring, fr_stride = fr_mod = KR.  Localisation
-  // (alego_loc_enable): those pointers name ONE frozen map store shared by every slot, fr_stride = 0 and fr_mod = its frame capacity.
+  // Where the key frames of a slot live: kf_row / kf_run_at (kf_store.h) find frame f of slot s in kfs_* / kf_raw_* / kf_cnt / kf_pose from these two.  SLAM: the slot's own
+  // ring, fr_stride = fr_mod = KR.  Localisation (alego_loc_enable): those pointers name ONE frozen map store shared by every slot, fr_stride = 0 and fr_mod = its frame capacity.
   int fr_stride, fr_mod;
   int loc_on, loc_n;             // localisation mode; frames of the map store
   float loc_r2;                  // (float)(radius * radius) of loc_select
@@ -108,8 +112,8 @@ struct LmCtx {
   // key-frame ring (clouds already transformed into the map frame, laserMapping.cpp:216-218) and SORTED by voxel key of the
   // map's leaf size (stable: input order inside a voxel): corner, and surf followed by outlier (:240-242) as one run
   float4 *kfs_c, *kfs_s;                          // [slot][KR][kf_cap_c] / [slot][KR][total_cap]
-  int* kfs_n;                                     // [slot][KR][2] points per run
-  float* kfs_box;                                 // [slot][KR][2][8] min xyz (0..2) / max xyz (4..6) of the run
+  int* kfs_n;                                     // [slot][2][KR] points per run (kf_run_at)
+  float* kfs_box;                                 // [slot][2][KR][8] min xyz (0..2) / max xyz (4..6) of the run
   float4 *kf_tmp_c, *kf_tmp_s;                    // [slot][kf_cap_c] / [slot][total_cap] transformed clouds of the key frame waiting to be sorted
   // sorted list of the occupied voxels of each local map (persistent, updated incrementally when the window changes)
   unsigned long long *U_c, *U_s;                  // [slot][map_cap_*]

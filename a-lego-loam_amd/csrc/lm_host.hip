@@ -10,7 +10,7 @@
 
 #include <rccl/rccl.h>
 
-#include "lm_ctx.h"
+#include "kf_store.h"
 #include "voxel.h"
 #include "gmap.h"
 #include "loc_math.h"
@@ -24,9 +24,8 @@ int launch_lm_register(const DevCtx& d, const LmCtx& L, hipStream_t st, int (*al
 size_t lm_solve_row_bytes_max();
 size_t lm_solve_row_bytes_default();
 void launch_lm_retransform(const DevCtx& d, const LmCtx& L, int ring, hipStream_t st);
-struct MapWork { int* items; int* count; int cap; };   // kernels_map.hip
 void launch_map_update(const DevCtx& d, const LmCtx& L, const MapWork& W, hipStream_t st);
-void launch_map_accum(const DevCtx& d, const LmCtx& L, const MapWork& W, hipStream_t st);
+void launch_map_accum(const DevCtx& d, const LmCtx& L, const MapWork& W, hipStream_t st);   // kernels_map.hip
 void launch_lm_apply_correction(const DevCtx& d, const LmCtx& L, int slot, const double* rc_dev, hipStream_t st);
 void launch_pg_apply(const LmCtx& L, const int* apply_dev, int n_slots, hipStream_t st);   // kernels_graph.hip
 void launch_pg_retransform(const LmCtx& L, const int* apply_dev, int slot0, int n, int j, hipStream_t st);
@@ -71,6 +70,36 @@ bool A(LmHost* lm, T** p, size_t count, std::string* err) {
   *p = (T*)q;
   return true;
 }
+void release(LmHost* lm, void* p) {
+  auto it = std::find(lm->allocs.begin(), lm->allocs.end(), p);
+  if (it == lm->allocs.end()) return;
+  (void)guard_free(p);
+  lm->allocs.erase(it);
+}
+
+// the nine arrays of the key-frame ring (or of the map store that takes its place, alego_loc_enable): f(array, elements per row)
+template <class F> void ring_each(LmCtx& L, F f) {
+  f(L.kfs_c, L.kf_cap_c); f(L.kfs_s, L.total_cap); f(L.kfs_n, 2); f(L.kfs_box, 2 * 8); f(L.kf_raw_c, L.kf_cap_c); f(L.kf_raw_s, L.kf_cap_s); f(L.kf_raw_o, L.kf_cap_o);
+  f(L.kf_cnt, KF_CNT_W); f(L.kf_pose, KF_POSE_W);
+}
+bool ring_alloc(LmHost* lm, LmCtx& L, size_t rows, std::string* err) {   // (a pointer that was not allocated is left null)
+  bool ok = true;
+  ring_each(L, [&](auto*& p, size_t per_row) { p = nullptr; ok = ok && A(lm, &p, rows * per_row, err); });
+  return ok;
+}
+void ring_release(LmHost* lm, LmCtx& L) { ring_each(L, [&](auto*& p, size_t) { if (p) release(lm, p); p = nullptr; }); }
+// the two sort jobs of a slot's kf_tmp_* (corner, surf + outlier): sorted by voxel key of the map's leaf into the row of the slot that LI_KF_PEND_RING names (VoxelGrid mode 1)
+void kf_sort_jobs(const LmCtx& L, const alego_params& P, int slot, std::vector<VoxJob>* out) {
+  int* li = L.li + (size_t)slot * LI_COUNT;
+  for (int m = 0; m < 2; ++m) {   // (LI_TMPN_S = LI_TMPN_C + 1, LI_SORT_N1 = LI_SORT_N + 1)
+    const int cap = m ? L.total_cap : L.kf_cap_c;
+    VoxJob j{(m ? L.kf_tmp_s : L.kf_tmp_c) + (size_t)slot * cap, li + LI_TMPN_C + m, (m ? L.kfs_s : L.kfs_c) + kf_row_at(L, slot, 0) * cap, li + LI_SORT_N + m, li + LI_KF_PENDING,
+             m ? P.lm_leaf_surf : P.lm_leaf_corner, cap, cap, li + LI_OVERFLOW, 0};
+    j.mode = 1; j.out_sel = li + LI_KF_PEND_RING; j.out_stride = cap;
+    j.box_out = L.kfs_box + kf_run_at(L, slot, m, 0) * 8; j.n_sel_out = L.kfs_n + kf_run_at(L, slot, m, 0); j.n_sel_stride = 1;
+    out->push_back(j);
+  }
+}
 }  // namespace
 
 LmHost* lm_host_create(const alego_params& P, const DevCtx& d, int n_slots, int gsize, const std::vector<hipStream_t>& st, std::string* err) {
@@ -112,12 +141,9 @@ LmHost* lm_host_create(const alego_params& P, const DevCtx& d, int n_slots, int 
   ok = ok && A(lm, &L.li, B * LI_COUNT, err) && A(lm, &L.ld, B * LD_COUNT, err);
   ok = ok && A(lm, &L.stage_odom, B * 2 * 8, err);
   ok = ok && A(lm, &L.in_corner, B * L.in_cap_c, err) && A(lm, &L.in_surf, B * L.in_cap_s, err) && A(lm, &L.in_outl, B * L.in_cap_o, err);
-  ok = ok && A(lm, &L.kfs_c, B * L.KR * L.kf_cap_c, err) && A(lm, &L.kfs_s, B * L.KR * L.total_cap, err);
-  ok = ok && A(lm, &L.kfs_n, B * 2 * L.KR, err) && A(lm, &L.kfs_box, B * 2 * L.KR * 8, err);
+  ok = ok && ring_alloc(lm, L, B * L.KR, err);
   ok = ok && A(lm, &L.kf_tmp_c, B * L.kf_cap_c, err) && A(lm, &L.kf_tmp_s, B * L.total_cap, err);
-  ok = ok && A(lm, &L.kf_raw_c, B * L.KR * L.kf_cap_c, err) && A(lm, &L.kf_raw_s, B * L.KR * L.kf_cap_s, err) && A(lm, &L.kf_raw_o, B * L.KR * L.kf_cap_o, err);
   ok = ok && A(lm, &L.rec, B * L.K, err) && A(lm, &L.rec_prev, B * L.K, err);
-  ok = ok && A(lm, &L.kf_cnt, B * L.KR * 4, err) && A(lm, &L.kf_pose, B * L.KR * 8, err);
   ok = ok && A(lm, &L.U_c, B * L.map_cap_c, err) && A(lm, &L.U_s, B * L.map_cap_s, err) && A(lm, &L.Ucnt_c, B * L.map_cap_c, err) && A(lm, &L.Ucnt_s, B * L.map_cap_s, err);
   ok = ok && A(lm, &L.newkeys, B * 2 * L.total_cap, err) && A(lm, &L.map_bbox, B * 2 * 8, err);
   {
@@ -153,14 +179,7 @@ LmHost* lm_host_create(const alego_params& P, const DevCtx& d, int n_slots, int 
     j1.push_back(VoxJob{L.in_surf + b * L.in_cap_s, li + LI_NIN_S, L.cur_surf_ds + b * L.kf_cap_s, li + LI_NCUR_S, li + LI_RUN, P.lm_leaf_surf, L.in_cap_s, L.kf_cap_s, li + LI_OVERFLOW, 0});
     j1.push_back(VoxJob{L.in_outl + b * L.in_cap_o, li + LI_NIN_O, L.cur_outl_ds + b * L.kf_cap_o, li + LI_NCUR_O, li + LI_RUN, P.lm_leaf_outlier, L.in_cap_o, L.kf_cap_o, li + LI_OVERFLOW, 0});
     j2.push_back(VoxJob{L.cur_total + b * L.total_cap, li + LI_NTOTAL, L.cur_total_ds + b * L.total_cap, li + LI_NTOTAL_DS, li + LI_RUN, P.lm_leaf_surf, L.total_cap, L.total_cap, li + LI_OVERFLOW, 0});
-    // the key frame waiting in kf_tmp_*: sorted by voxel key of the map's leaf into its ring entry (mode 1)
-    VoxJob kc{L.kf_tmp_c + b * L.kf_cap_c, li + LI_TMPN_C, L.kfs_c + b * L.KR * L.kf_cap_c, li + LI_SORT_N, li + LI_KF_PENDING, P.lm_leaf_corner, L.kf_cap_c, L.kf_cap_c, li + LI_OVERFLOW, 0};
-    kc.mode = 1; kc.out_sel = li + LI_KF_PEND_RING; kc.out_stride = L.kf_cap_c;
-    kc.box_out = L.kfs_box + (b * 2 + 0) * L.KR * 8; kc.n_sel_out = L.kfs_n + (b * 2 + 0) * L.KR; kc.n_sel_stride = 1;
-    VoxJob ks{L.kf_tmp_s + b * L.total_cap, li + LI_TMPN_S, L.kfs_s + b * L.KR * L.total_cap, li + LI_SORT_N + 1, li + LI_KF_PENDING, P.lm_leaf_surf, L.total_cap, L.total_cap, li + LI_OVERFLOW, 0};
-    ks.mode = 1; ks.out_sel = li + LI_KF_PEND_RING; ks.out_stride = L.total_cap;
-    ks.box_out = L.kfs_box + (b * 2 + 1) * L.KR * 8; ks.n_sel_out = L.kfs_n + (b * 2 + 1) * L.KR; ks.n_sel_stride = 1;
-    jk.push_back(kc); jk.push_back(ks);
+    kf_sort_jobs(L, P, (int)b, &jk);
   }
   const int ns = (int)j1.size() / 3;
   jm.insert(jm.end(), j1.begin(), j1.end());
@@ -205,18 +224,6 @@ static bool dbg_sync(hipStream_t st, const char* what, std::string* err) {
   fprintf(stderr, "[alego dbg] %s: %s\n", what, hipGetErrorString(e));
   if (e != hipSuccess) { *err = std::string(what) + ": " + hipGetErrorString(e); return false; }
   return true;
-}
-
-// A key frame's clouds were (re)written outside the regular sequence (set_keypose / add_keyframe): sort it into the ring now and
-// make the next map update rebuild its voxel lists from scratch.
-static void lm_kf_changed(LmHost* lm, const DevCtx& d, int /*ring*/, hipStream_t st) {
-  const int g = d.slot0 / lm->gsize;
-  std::string e;
-  (void)vox_run(lm->vk[g], st, &e);
-  const int zero = 0;
-  int* li = lm->L.li + (size_t)d.slot0 * LI_COUNT;
-  (void)hipMemcpyAsync(li + LI_KF_PENDING, &zero, sizeof(int), hipMemcpyHostToDevice, st);
-  (void)hipMemcpyAsync(li + LI_UVALID, &zero, sizeof(int), hipMemcpyHostToDevice, st);
 }
 
 // the local maps of the slots whose window changed (LI_REBUILD, set by lm_prepare) + the VoxelGrid filters of the scan's three
@@ -394,26 +401,42 @@ int lm_host_keyframe_count(LmHost* lm, int slot) {
   if (hipMemcpy(&n, lm->L.li + (size_t)slot * LI_COUNT + LI_NKF, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return ALEGO_ERR_HIP;
   return n;
 }
+// One frame to the host: id, pose and counts always, each cloud the caller gave a buffer for (ALEGO_ERR_CAPACITY when one is too small); n / src: points and device cloud per kind
+static int frame_to_host(const char* what, int id, const float* pose_dev, const int* n, const float4* const* src, alego_keyframe* out, std::string* err) {
+  float kp[KF_POSE_W];
+  if (hipMemcpy(kp, pose_dev, sizeof(kp), hipMemcpyDeviceToHost) != hipSuccess) { *err = std::string(what) + ": copy failed"; return ALEGO_ERR_HIP; }
+  out->id = id;
+  for (int k = 0; k < 6; ++k) out->pose[k] = kp[k];
+  out->n_corner = n[KF_CORNER]; out->n_surf = n[KF_SURF]; out->n_outlier = n[KF_OUTL];
+  alego_point* const dst[KF_KINDS] = {out->corner, out->surf, out->outlier};   // (KF_CORNER, KF_SURF, KF_OUTL)
+  const int cap[KF_KINDS] = {out->corner_cap, out->surf_cap, out->outlier_cap};
+  for (int k = 0; k < KF_KINDS; ++k) if (dst[k] && n[k] > cap[k]) { *err = std::string(what) + ": buffer too small"; return ALEGO_ERR_CAPACITY; }
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < KF_KINDS; ++k) if (e == hipSuccess && dst[k] && n[k]) e = hipMemcpy(dst[k], src[k], (size_t)n[k] * 16, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) { *err = std::string(what) + ": " + hipGetErrorString(e); return ALEGO_ERR_HIP; }
+  return 0;
+}
 int lm_host_get_keyframe(LmHost* lm, int slot, int kf_id, alego_keyframe* out, std::string* err) {
   const LmCtx& L = lm->L;
   const int nkf = lm_host_keyframe_count(lm, slot);
   if (nkf < 0) { *err = "get_keyframe: device error"; return nkf; }
   if (kf_id < 0) kf_id = nkf - 1;
   if (kf_id < 0 || kf_id >= nkf || kf_id < nkf - L.K) { *err = "get_keyframe: key frame not resident (only the recent_keyframe_num newest are)"; return ALEGO_ERR_ARG; }
-  const size_t rs = (size_t)slot * L.KR + kf_id % L.KR;
-  int cnt[4];
-  float kp[8];
-  if (hipMemcpy(cnt, L.kf_cnt + rs * 4, sizeof(cnt), hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(kp, L.kf_pose + rs * 8, sizeof(kp), hipMemcpyDeviceToHost) != hipSuccess) { *err = "get_keyframe: copy failed"; return ALEGO_ERR_HIP; }
-  out->id = kf_id;
-  for (int k = 0; k < 6; ++k) out->pose[k] = kp[k];
-  out->n_corner = cnt[0]; out->n_surf = cnt[1]; out->n_outlier = cnt[2];
-  if ((out->corner && cnt[0] > out->corner_cap) || (out->surf && cnt[1] > out->surf_cap) || (out->outlier && cnt[2] > out->outlier_cap)) { *err = "get_keyframe: buffer too small"; return ALEGO_ERR_CAPACITY; }
-  hipError_t e = hipSuccess;
-  if (out->corner && cnt[0]) e = hipMemcpy(out->corner, L.kf_raw_c + rs * L.kf_cap_c, (size_t)cnt[0] * 16, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && out->surf && cnt[1]) e = hipMemcpy(out->surf, L.kf_raw_s + rs * L.kf_cap_s, (size_t)cnt[1] * 16, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && out->outlier && cnt[2]) e = hipMemcpy(out->outlier, L.kf_raw_o + rs * L.kf_cap_o, (size_t)cnt[2] * 16, hipMemcpyDeviceToHost);
-  if (e != hipSuccess) { *err = std::string("get_keyframe: ") + hipGetErrorString(e); return ALEGO_ERR_HIP; }
-  return 0;
+  const KfRingRow R = kf_ring_row_at(L, slot, kf_entry(L, kf_id), KF_CORNER);
+  int cnt[KF_CNT_W];
+  if (hipMemcpy(cnt, R.cnt, sizeof(cnt), hipMemcpyDeviceToHost) != hipSuccess) { *err = "get_keyframe: copy failed"; return ALEGO_ERR_HIP; }
+  const float4* const src[KF_KINDS] = {R.raw, kf_raw_of(L, R.row, KF_SURF), kf_raw_of(L, R.row, KF_OUTL)};
+  return frame_to_host("get_keyframe", kf_id, R.pose, cnt, src, out, err);
+}
+// a frame of the host into ring row R: key pose, counts, the three clouds
+static hipError_t frame_to_row(const LmCtx& L, const KfRingRow& R, const alego_kf_in& f) {
+  const float kp[KF_POSE_W] = {f.pose[0], f.pose[1], f.pose[2], f.pose[3], f.pose[4], f.pose[5], 0.f, 0.f};
+  const int cnt[KF_CNT_W] = {f.n_corner, f.n_surf, f.n_outlier, 0};   // (KF_CORNER, KF_SURF, KF_OUTL)
+  const alego_point* const src[KF_KINDS] = {f.corner, f.surf, f.outlier};
+  hipError_t e = hipMemcpy(R.pose, kp, sizeof(kp), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(R.cnt, cnt, sizeof(cnt), hipMemcpyHostToDevice);
+  for (int k = 0; k < KF_KINDS; ++k) if (e == hipSuccess && cnt[k]) e = hipMemcpy(kf_raw_of(L, R.row, k), src[k], (size_t)cnt[k] * 16, hipMemcpyHostToDevice);
+  return e;
 }
 static int retransform(LmHost* lm, const DevCtx& dfull, int slot, int ring, std::string* err) {
   DevCtx d = dfull;
@@ -426,7 +449,11 @@ static int retransform(LmHost* lm, const DevCtx& dfull, int slot, int ring, std:
   if (int r = vox_run(lm->vk[g], st, err)) return r;
   (void)hipMemcpyAsync(li + LI_KF_PENDING, &zero, sizeof(int), hipMemcpyHostToDevice, st);
   launch_lm_retransform(d, lm->L, ring, st);
-  lm_kf_changed(lm, d, ring, st);
+  // the row's clouds were (re)written outside the regular sequence: sort it into the ring now, and the next map update rebuilds its voxel lists
+  std::string e;
+  (void)vox_run(lm->vk[g], st, &e);
+  (void)hipMemcpyAsync(li + LI_KF_PENDING, &zero, sizeof(int), hipMemcpyHostToDevice, st);
+  (void)hipMemcpyAsync(li + LI_UVALID, &zero, sizeof(int), hipMemcpyHostToDevice, st);
   if (hipStreamSynchronize(st) != hipSuccess) { *err = "key-frame transform failed"; return ALEGO_ERR_HIP; }
   return 0;
 }
@@ -435,22 +462,19 @@ int lm_host_set_keypose(LmHost* lm, const DevCtx& dfull, int slot, int kf_id, co
   const int nkf = lm_host_keyframe_count(lm, slot);
   if (nkf < 0) return nkf;
   if (kf_id < 0 || kf_id >= nkf || kf_id < nkf - L.K) { *err = "set_keypose: key frame not resident"; return ALEGO_ERR_ARG; }
-  const int ring = kf_id % L.KR;
-  if (hipMemcpy(L.kf_pose + ((size_t)slot * L.KR + ring) * 8, pose6, 6 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { *err = "set_keypose: copy failed"; return ALEGO_ERR_HIP; }
+  if (hipMemcpy(kf_pose_of(L, kf_row(L, slot, kf_id)), pose6, 6 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { *err = "set_keypose: copy failed"; return ALEGO_ERR_HIP; }
   if (L.arc_frames_cap > 0) {   // the archived copy of the frame (alego_map_enable) follows
-    int stat[4];
-    if (hipMemcpy(stat, L.arc_stat + (size_t)slot * 4, sizeof(stat), hipMemcpyDeviceToHost) != hipSuccess) { *err = "set_keypose: copy failed"; return ALEGO_ERR_HIP; }
-    if (kf_id < stat[0] && hipMemcpy(L.arc_pose + ((size_t)slot * L.arc_frames_cap + kf_id) * 8, pose6, 6 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { *err = "set_keypose: copy failed"; return ALEGO_ERR_HIP; }
+    int stat[AS_W];
+    if (hipMemcpy(stat, arc_stat_of(L, slot), sizeof(stat), hipMemcpyDeviceToHost) != hipSuccess) { *err = "set_keypose: copy failed"; return ALEGO_ERR_HIP; }
+    if (kf_id < stat[AS_FRAMES] && hipMemcpy(arc_pose_of(L, slot, kf_id), pose6, 6 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { *err = "set_keypose: copy failed"; return ALEGO_ERR_HIP; }
   }
-  return retransform(lm, dfull, slot, ring, err);
+  return retransform(lm, dfull, slot, kf_entry(L, kf_id), err);
 }
 int lm_host_reset_window(LmHost* lm, int slot, std::string* err) {
-  // recent_*_keyframes_.clear() (:563-565): the next mapping frame refills the window from the newest key frames (:208-223)
-  const int v[2] = {0, 1};
   int* li = lm->L.li + (size_t)slot * LI_COUNT;
-  if (hipStreamSynchronize(stream_of_slot(lm, slot)) != hipSuccess || hipMemcpy(li + LI_REC_CNT, &v[0], sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(li + LI_DIRTY, &v[1], sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(li + LI_UVALID, &v[0], sizeof(int), hipMemcpyHostToDevice) != hipSuccess) { *err = "reset_window failed"; return ALEGO_ERR_HIP; }
+  bool ok = hipStreamSynchronize(stream_of_slot(lm, slot)) == hipSuccess;
+  kf_reset_window([&](int w, int v) { ok = ok && hipMemcpy(li + w, &v, sizeof(int), hipMemcpyHostToDevice) == hipSuccess; });
+  if (!ok) { *err = "reset_window failed"; return ALEGO_ERR_HIP; }
   return 0;
 }
 int lm_host_apply_correction(LmHost* lm, const DevCtx& dfull, int slot, const double* rc12, std::string* err) {
@@ -466,14 +490,11 @@ int lm_host_apply_correction(LmHost* lm, const DevCtx& dfull, int slot, const do
 int lm_host_add_keyframe(LmHost* lm, const DevCtx& dfull, int slot, const float* pose6, const alego_point* corner, int nc, const alego_point* surf, int ns,
                          const alego_point* outlier, int no, std::string* err) {
   const LmCtx& L = lm->L;
-  if (nc < 0 || ns < 0 || no < 0 || (nc && !corner) || (ns && !surf) || (no && !outlier)) { *err = "add_keyframe: null cloud / negative count"; return ALEGO_ERR_ARG; }
+  const alego_kf_in f{{pose6[0], pose6[1], pose6[2], pose6[3], pose6[4], pose6[5]}, corner, nc, surf, ns, outlier, no};
+  if (!kf_in_valid(f)) { *err = "add_keyframe: null cloud / negative count"; return ALEGO_ERR_ARG; }
   if (nc > L.kf_cap_c || ns > L.kf_cap_s || no > L.kf_cap_o) { *err = "add_keyframe: cloud exceeds the key-frame capacity"; return ALEGO_ERR_CAPACITY; }
   const int nkf = lm_host_keyframe_count(lm, slot);
   if (nkf < 0) return nkf;
-  const int ring = nkf % L.KR;
-  const size_t rs = (size_t)slot * L.KR + ring;
-  float kp[8] = {pose6[0], pose6[1], pose6[2], pose6[3], pose6[4], pose6[5], 0.f, 0.f};
-  const int cnt[4] = {nc, ns, no, 0};
   int* li = L.li + (size_t)slot * LI_COUNT;
   {
     // A full window advances by ONE frame per mapping frame (pop the oldest, push the newest, laserMapping.cpp:224-237): it keeps its
@@ -493,15 +514,11 @@ int lm_host_add_keyframe(LmHost* lm, const DevCtx& dfull, int slot, const float*
     }
   }
   const int nkf1 = nkf + 1, one = 1;
-  hipError_t e = hipMemcpy(L.kf_pose + rs * 8, kp, sizeof(kp), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(L.kf_cnt + rs * 4, cnt, sizeof(cnt), hipMemcpyHostToDevice);
-  if (e == hipSuccess && nc) e = hipMemcpy(L.kf_raw_c + rs * L.kf_cap_c, corner, (size_t)nc * 16, hipMemcpyHostToDevice);
-  if (e == hipSuccess && ns) e = hipMemcpy(L.kf_raw_s + rs * L.kf_cap_s, surf, (size_t)ns * 16, hipMemcpyHostToDevice);
-  if (e == hipSuccess && no) e = hipMemcpy(L.kf_raw_o + rs * L.kf_cap_o, outlier, (size_t)no * 16, hipMemcpyHostToDevice);
+  hipError_t e = frame_to_row(L, kf_ring_row_at(L, slot, kf_entry(L, nkf), KF_CORNER), f);
   if (e == hipSuccess) e = hipMemcpy(li + LI_NKF, &nkf1, sizeof(int), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(li + LI_DIRTY, &one, sizeof(int), hipMemcpyHostToDevice);
   if (e != hipSuccess) { *err = std::string("add_keyframe: ") + hipGetErrorString(e); return ALEGO_ERR_HIP; }
-  if (int r = retransform(lm, dfull, slot, ring, err)) return r;
+  if (int r = retransform(lm, dfull, slot, kf_entry(L, nkf), err)) return r;
   if (L.arc_frames_cap > 0) {   // the archive (alego_map_enable) takes the inserted frame like a saved one
     DevCtx d = dfull;
     d.slot0 = slot; d.n_launch = 1;
@@ -604,16 +621,16 @@ int lm_host_debug_get(LmHost* lm, int slot, const char* name, void* out, int cap
   else if (s == "lm_surf_total_ds") set(L.cur_total_ds + b * L.total_cap, (size_t)li[LI_NTOTAL_DS] * 4, 0);
   else if (s == "lm_blocks") set(L.blocks + b * L.qcap * 8, (size_t)L.qcap * 8, 1);
   else if (s == "lm_knn") set(L.knn + b * L.qcap * 5, (size_t)L.qcap * 5, 2);   // lm_knn's rows: corner queries from 0, surf queries from kf_cap_c; -1 x 5 = rejected
-  else if (s == "lm_keyposes") set(L.kf_pose + b * L.fr_stride * 8, (size_t)(L.loc_on ? L.loc_n : L.KR) * 8, 0);   // (localisation: the map store's)
+  else if (s == "lm_keyposes") set(kf_pose_of(L, kf_row_at(L, slot, 0)), (size_t)(L.loc_on ? L.loc_n : L.fr_mod) * KF_POSE_W, 0);   // (localisation: the map store's)
   else if (s == "lm_window") set(L.rec + b * L.K, (size_t)li[LI_REC_CNT], 2);   // frame ids of recent_*_keyframes_
   else if (s == "lm_kf_corner_map" || s == "lm_kf_surf_map") {   // newest key frame in the map frame, sorted by voxel key (surf = surf + outlier)
     const int nkf = li[LI_NKF];
     if (nkf <= 0) { *count = 0; *dtype = 0; return 0; }
-    const int e = (nkf - 1) % L.KR, m = s == "lm_kf_corner_map" ? 0 : 1;
+    const int m = s == "lm_kf_corner_map" ? 0 : 1;
     int n = 0;
-    (void)hipMemcpy(&n, L.kfs_n + (b * 2 + m) * L.KR + e, sizeof(int), hipMemcpyDeviceToHost);
-    if (m == 0) set(L.kfs_c + (b * L.KR + e) * L.kf_cap_c, (size_t)n * 4, 0);
-    else set(L.kfs_s + (b * L.KR + e) * L.total_cap, (size_t)n * 4, 0);
+    (void)hipMemcpy(&n, L.kfs_n + kf_run_at(L, slot, m, kf_entry(L, nkf - 1)), sizeof(int), hipMemcpyDeviceToHost);
+    if (m == 0) set(L.kfs_c + kf_row(L, slot, nkf - 1) * L.kf_cap_c, (size_t)n * 4, 0);
+    else set(L.kfs_s + kf_row(L, slot, nkf - 1) * L.total_cap, (size_t)n * 4, 0);
   }
   else if (s == "lm_voxel_keys_c" || s == "lm_voxel_keys_s") {   // the sorted voxel-key list of a map as pairs of i32 (lo, hi)
     const int m = s == "lm_voxel_keys_c" ? 0 : 1;
@@ -626,19 +643,28 @@ int lm_host_debug_get(LmHost* lm, int slot, const char* name, void* out, int cap
   return 0;
 }
 
+// 0 while no slot has saved a key frame (scans too: or run a mapping frame), else ALEGO_ERR_ARG: what is enabled on a handle has to exist before the first one
+static int rings_empty(LmHost* lm, const char* what, bool scans_too, std::string* err) {
+  std::vector<int> li((size_t)lm->n_slots * LI_COUNT);
+  if (hipMemcpy(li.data(), lm->L.li, li.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { *err = std::string(what) + ": device read failed"; return ALEGO_ERR_HIP; }
+  for (int s = 0; s < lm->n_slots; ++s)
+    if (li[(size_t)s * LI_COUNT + LI_NKF] != 0 || (scans_too && li[(size_t)s * LI_COUNT + LI_FRAME] != 0)) {
+      *err = std::string(what) + (scans_too ? ": call it before the first scan / key frame of any slot" : ": call it before the first key frame is saved");
+      return ALEGO_ERR_ARG;
+    }
+  return 0;
+}
+
 // ---- the global map (alego_map_* / alego_lm_get_local_map / alego_voxel_grid) ----
 int lm_host_map_enable(LmHost* lm, int max_frames, int max_points, std::string* err) {
   LmCtx& L = lm->L;
   if (L.arc_frames_cap > 0) { *err = "map_enable: already enabled"; return ALEGO_ERR_ARG; }
   if (max_frames <= 0 || max_points <= 0) { *err = "map_enable: capacities must be positive"; return ALEGO_ERR_ARG; }
-  // the archive holds frame ids 0, 1, ...: it has to exist before the first key frame
-  std::vector<int> li((size_t)lm->n_slots * LI_COUNT);
-  if (hipMemcpy(li.data(), L.li, li.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { *err = "map_enable: device read failed"; return ALEGO_ERR_HIP; }
-  for (int s = 0; s < lm->n_slots; ++s) if (li[(size_t)s * LI_COUNT + LI_NKF] != 0) { *err = "map_enable: call it before the first key frame is saved"; return ALEGO_ERR_ARG; }
+  if (int r = rings_empty(lm, "map_enable", false, err)) return r;   // the archive holds frame ids 0, 1, ...: it has to exist before the first key frame
   const size_t B = lm->n_slots;
   LmCtx T = L;
-  bool ok = A(lm, &T.arc_pts, B * max_points, err) && A(lm, &T.arc_tab, B * max_frames * 4, err) && A(lm, &T.arc_pose, B * max_frames * 8, err) &&
-            A(lm, &T.arc_stat, B * 4, err) && A(lm, &T.arc_stamp, B * max_frames, err) && A(lm, &T.arc_stamped, B, err) &&
+  bool ok = A(lm, &T.arc_pts, B * max_points, err) && A(lm, &T.arc_tab, B * max_frames * AT_W, err) && A(lm, &T.arc_pose, B * max_frames * KF_POSE_W, err) &&
+            A(lm, &T.arc_stat, B * AS_W, err) && A(lm, &T.arc_stamp, B * max_frames, err) && A(lm, &T.arc_stamped, B, err) &&
             A(lm, &lm->arc_off, (size_t)max_frames + 1, err);
   if (!ok) return ALEGO_ERR_HIP;
   if (int r = gv_reserve(&lm->gv, max_points, err)) return r == -3 ? ALEGO_ERR_CAPACITY : ALEGO_ERR_HIP;
@@ -646,35 +672,35 @@ int lm_host_map_enable(LmHost* lm, int max_frames, int max_points, std::string* 
   L = T;
   return 0;
 }
-static int map_stat(LmHost* lm, int slot, int* st4, std::string* err) {
+static int map_stat(LmHost* lm, int slot, int* st4 /* [AS_W] */, std::string* err) {
   if (lm->L.arc_frames_cap <= 0) { *err = "the key-frame archive is off (alego_map_enable)"; return ALEGO_ERR_ARG; }
-  if (hipStreamSynchronize(stream_of_slot(lm, slot)) != hipSuccess || hipMemcpy(st4, lm->L.arc_stat + (size_t)slot * 4, 4 * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) {
+  if (hipStreamSynchronize(stream_of_slot(lm, slot)) != hipSuccess || hipMemcpy(st4, arc_stat_of(lm->L, slot), AS_W * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) {
     *err = "map: device read failed"; return ALEGO_ERR_HIP;
   }
   return 0;
 }
 int lm_host_map_status(LmHost* lm, int slot, int* out4, std::string* err) {
-  int st[4];
+  int st[AS_W];
   if (int r = map_stat(lm, slot, st, err)) return r;
-  out4[0] = st[0]; out4[1] = st[1]; out4[2] = st[2]; out4[3] = lm->L.arc_points_cap;
+  out4[0] = st[AS_FRAMES]; out4[1] = st[AS_DROPPED]; out4[2] = st[AS_POINTS]; out4[3] = lm->L.arc_points_cap;
   return 0;
 }
 int lm_host_map_set_keyposes(LmHost* lm, int slot, int first, int n, const float* poses6, std::string* err) {
-  int st[4];
+  int st[AS_W];
   if (int r = map_stat(lm, slot, st, err)) return r;
-  if (first < 0 || n < 0 || first > st[0] || n > st[0] - first || (n > 0 && !poses6)) { *err = "map_set_keyposes: range beyond the archived frames"; return ALEGO_ERR_ARG; }
+  if (first < 0 || n < 0 || first > st[AS_FRAMES] || n > st[AS_FRAMES] - first || (n > 0 && !poses6)) { *err = "map_set_keyposes: range beyond the archived frames"; return ALEGO_ERR_ARG; }
   if (n == 0) return 0;
-  // poses6 is [n][6]; the archive keeps 8 floats per frame
-  if (hipMemcpy2D(lm->L.arc_pose + ((size_t)slot * lm->L.arc_frames_cap + first) * 8, 8 * sizeof(float), poses6, 6 * sizeof(float), 6 * sizeof(float), n,
+  // poses6 is [n][6]; the archive keeps KF_POSE_W floats per frame
+  if (hipMemcpy2D(arc_pose_of(lm->L, slot, first), KF_POSE_W * sizeof(float), poses6, 6 * sizeof(float), 6 * sizeof(float), n,
                   hipMemcpyHostToDevice) != hipSuccess) { *err = "map_set_keyposes: copy failed"; return ALEGO_ERR_HIP; }
   return 0;
 }
 int lm_host_map_stamps(LmHost* lm, int slot, int first, int n, double* stamps, int write, std::string* err) {
-  int st[4];
+  int st[AS_W];
   if (int r = map_stat(lm, slot, st, err)) return r;
-  if (first < 0 || n < 0 || first > st[0] || n > st[0] - first || (n > 0 && !stamps)) { *err = "map_stamps: range beyond the archived frames"; return ALEGO_ERR_ARG; }
+  if (first < 0 || n < 0 || first > st[AS_FRAMES] || n > st[AS_FRAMES] - first || (n > 0 && !stamps)) { *err = "map_stamps: range beyond the archived frames"; return ALEGO_ERR_ARG; }
   if (n == 0) return 0;
-  double* dev = lm->L.arc_stamp + (size_t)slot * lm->L.arc_frames_cap + first;
+  double* dev = lm->L.arc_stamp + arc_row(lm->L, slot, first);
   if (hipMemcpy(write ? (void*)dev : (void*)stamps, write ? (const void*)stamps : (const void*)dev, (size_t)n * sizeof(double),
                 write ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost) != hipSuccess) { *err = "map_stamps: copy failed"; return ALEGO_ERR_HIP; }
   return 0;
@@ -689,12 +715,6 @@ const LmCtx* lm_host_ctx(LmHost* lm) { return &lm->L; }
 // The map store: every frame transformed by its key pose and sorted by voxel key exactly as a ring entry is (lm_store_kf's re-transform path
 // into kf_tmp_*, then the key-frame sort, VoxelGrid mode 1), once for the whole handle.  The rings of the slots are released: kfs_* / kf_raw_* /
 // kf_cnt / kf_pose name the store from now on, and fr_stride = 0 sends every slot's frame f to row f of it.
-static void release(LmHost* lm, void* p) {
-  auto it = std::find(lm->allocs.begin(), lm->allocs.end(), p);
-  if (it == lm->allocs.end()) return;
-  (void)guard_free(p);
-  lm->allocs.erase(it);
-}
 int lm_host_loc_enable(LmHost* lm, const DevCtx& dfull, const alego_kf_in* frames, int n, double radius, std::string* err) {
   LmCtx& L = lm->L;
   if (L.loc_on) { *err = "alego_loc_enable: already enabled"; return ALEGO_ERR_ARG; }
@@ -704,16 +724,11 @@ int lm_host_loc_enable(LmHost* lm, const DevCtx& dfull, const alego_kf_in* frame
   if (!dfull.opt_map_merge) { *err = "alego_loc_enable: ALEGO_MAP_MERGE=0 (concat + radix VoxelGrid) is a mapping-only path"; return ALEGO_ERR_ARG; }
   for (long f : lm->frames) if (f != 0) { *err = "alego_loc_enable: call it before the first scan of any slot"; return ALEGO_ERR_ARG; }
   for (hipStream_t s : lm->st) if (hipStreamSynchronize(s) != hipSuccess) { *err = "alego_loc_enable: a stream failed"; return ALEGO_ERR_HIP; }
-  {
-    std::vector<int> li((size_t)lm->n_slots * LI_COUNT);
-    if (hipMemcpy(li.data(), L.li, li.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { *err = "alego_loc_enable: device read failed"; return ALEGO_ERR_HIP; }
-    for (int s = 0; s < lm->n_slots; ++s)
-      if (li[(size_t)s * LI_COUNT + LI_NKF] != 0 || li[(size_t)s * LI_COUNT + LI_FRAME] != 0) { *err = "alego_loc_enable: call it before the first scan / key frame of any slot"; return ALEGO_ERR_ARG; }
-  }
+  if (int r = rings_empty(lm, "alego_loc_enable", true, err)) return r;
   if (n > LOC_MAX_FRAMES) { *err = "alego_loc_enable: more than " + std::to_string(LOC_MAX_FRAMES) + " frames"; return ALEGO_ERR_CAPACITY; }
   for (int i = 0; i < n; ++i) {
     const alego_kf_in& f = frames[i];
-    if (f.n_corner < 0 || f.n_surf < 0 || f.n_outlier < 0 || (f.n_corner && !f.corner) || (f.n_surf && !f.surf) || (f.n_outlier && !f.outlier)) { *err = "alego_loc_enable: frame " + std::to_string(i) + ": null cloud / negative count"; return ALEGO_ERR_ARG; }
+    if (!kf_in_valid(f)) { *err = "alego_loc_enable: frame " + std::to_string(i) + ": null cloud / negative count"; return ALEGO_ERR_ARG; }
     if (f.n_corner > L.kf_cap_c || f.n_surf > L.kf_cap_s || f.n_outlier > L.kf_cap_o) {
       *err = "alego_loc_enable: frame " + std::to_string(i) + " (" + std::to_string(f.n_corner) + " corner, " + std::to_string(f.n_surf) + " surf, " + std::to_string(f.n_outlier) +
              " outlier points) exceeds the handle's key-frame capacities (" + std::to_string(L.kf_cap_c) + ", " + std::to_string(L.kf_cap_s) + ", " + std::to_string(L.kf_cap_o) + ")";
@@ -722,13 +737,9 @@ int lm_host_loc_enable(LmHost* lm, const DevCtx& dfull, const alego_kf_in* frame
   }
   LmCtx T = L;
   const size_t F = (size_t)std::max(n, 1);
-  T.kfs_c = nullptr; T.kfs_s = nullptr; T.kfs_n = nullptr; T.kfs_box = nullptr; T.kf_raw_c = nullptr; T.kf_raw_s = nullptr; T.kf_raw_o = nullptr; T.kf_cnt = nullptr; T.kf_pose = nullptr;
   std::string aerr;
-  const bool ok = A(lm, &T.kfs_c, F * L.kf_cap_c, &aerr) && A(lm, &T.kfs_s, F * L.total_cap, &aerr) && A(lm, &T.kfs_n, 2 * F, &aerr) && A(lm, &T.kfs_box, 2 * F * 8, &aerr) &&
-                  A(lm, &T.kf_raw_c, F * L.kf_cap_c, &aerr) && A(lm, &T.kf_raw_s, F * L.kf_cap_s, &aerr) && A(lm, &T.kf_raw_o, F * L.kf_cap_o, &aerr) &&
-                  A(lm, &T.kf_cnt, F * 4, &aerr) && A(lm, &T.kf_pose, F * 8, &aerr);
-  if (!ok) {   // the handle stays what it was
-    for (void* p : {(void*)T.kfs_c, (void*)T.kfs_s, (void*)T.kfs_n, (void*)T.kfs_box, (void*)T.kf_raw_c, (void*)T.kf_raw_s, (void*)T.kf_raw_o, (void*)T.kf_cnt, (void*)T.kf_pose}) if (p) release(lm, p);
+  if (!ring_alloc(lm, T, F, &aerr)) {   // the handle stays what it was
+    ring_release(lm, T);
     *err = "alego_loc_enable: the map store of " + std::to_string(n) + " frames does not fit (" + aerr + ")";
     return ALEGO_ERR_CAPACITY;
   }
@@ -741,17 +752,14 @@ int lm_host_loc_enable(LmHost* lm, const DevCtx& dfull, const alego_kf_in* frame
     (void)hipMemset(li0 + LI_KF_PENDING, 0, 8 * sizeof(int));
     (void)hipMemset(li0 + LI_OVERFLOW, 0, sizeof(int));
     if (lm->vloc_made) { vox_destroy(&lm->vloc); lm->vloc_made = false; }
-    for (void* p : {(void*)T.kfs_c, (void*)T.kfs_s, (void*)T.kfs_n, (void*)T.kfs_box, (void*)T.kf_raw_c, (void*)T.kf_raw_s, (void*)T.kf_raw_o, (void*)T.kf_cnt, (void*)T.kf_pose}) release(lm, p);
+    ring_release(lm, T);
     return rc;
   };
   // the sort jobs of slot 0's kf_tmp_*, with the store as their ring
-  VoxJob kc{T.kf_tmp_c, li0 + LI_TMPN_C, T.kfs_c, li0 + LI_SORT_N, li0 + LI_KF_PENDING, lm->P.lm_leaf_corner, T.kf_cap_c, T.kf_cap_c, li0 + LI_OVERFLOW, 0};
-  kc.mode = 1; kc.out_sel = li0 + LI_KF_PEND_RING; kc.out_stride = T.kf_cap_c; kc.box_out = T.kfs_box; kc.n_sel_out = T.kfs_n; kc.n_sel_stride = 1;
-  VoxJob ks{T.kf_tmp_s, li0 + LI_TMPN_S, T.kfs_s, li0 + LI_SORT_N + 1, li0 + LI_KF_PENDING, lm->P.lm_leaf_surf, T.total_cap, T.total_cap, li0 + LI_OVERFLOW, 0};
-  ks.mode = 1; ks.out_sel = li0 + LI_KF_PEND_RING; ks.out_stride = T.total_cap; ks.box_out = T.kfs_box + F * 8; ks.n_sel_out = T.kfs_n + F; ks.n_sel_stride = 1;
-  const VoxJob jobs[2] = {kc, ks};
+  std::vector<VoxJob> jobs;
+  kf_sort_jobs(T, lm->P, 0, &jobs);
   std::memset(&lm->vloc, 0, sizeof(VoxCtx));
-  if (vox_create(&lm->vloc, jobs, 2, err)) return undo(ALEGO_ERR_HIP);
+  if (vox_create(&lm->vloc, jobs.data(), 2, err)) return undo(ALEGO_ERR_HIP);
   lm->vloc_made = true;
   lm->vloc.grid_small = 2; lm->vloc.grid_big = 2;
   hipStream_t st = lm->st[0];
@@ -759,16 +767,9 @@ int lm_host_loc_enable(LmHost* lm, const DevCtx& dfull, const alego_kf_in* frame
   d.slot0 = 0; d.n_launch = 1;
   hipError_t e = hipSuccess;
   for (int i = 0; i < n && e == hipSuccess; ++i) {
-    const alego_kf_in& f = frames[i];
-    const float kp[8] = {f.pose[0], f.pose[1], f.pose[2], f.pose[3], f.pose[4], f.pose[5], 0.f, 0.f};
-    const int cnt[4] = {f.n_corner, f.n_surf, f.n_outlier, 0};
-    e = hipMemcpy(T.kf_pose + (size_t)i * 8, kp, sizeof(kp), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(T.kf_cnt + (size_t)i * 4, cnt, sizeof(cnt), hipMemcpyHostToDevice);
-    if (e == hipSuccess && f.n_corner) e = hipMemcpy(T.kf_raw_c + (size_t)i * T.kf_cap_c, f.corner, (size_t)f.n_corner * 16, hipMemcpyHostToDevice);
-    if (e == hipSuccess && f.n_surf) e = hipMemcpy(T.kf_raw_s + (size_t)i * T.kf_cap_s, f.surf, (size_t)f.n_surf * 16, hipMemcpyHostToDevice);
-    if (e == hipSuccess && f.n_outlier) e = hipMemcpy(T.kf_raw_o + (size_t)i * T.kf_cap_o, f.outlier, (size_t)f.n_outlier * 16, hipMemcpyHostToDevice);
+    e = frame_to_row(T, kf_ring_row_at(T, 0, kf_entry(T, i), KF_CORNER), frames[i]);
     if (e != hipSuccess) break;
-    launch_lm_retransform(d, T, i, st);   // row i of the store -> kf_tmp_* of slot 0 (slot 0's rows start at 0 whatever fr_stride is)
+    launch_lm_retransform(d, T, kf_entry(T, i), st);   // row i of the store -> kf_tmp_* of slot 0
     if (int r = vox_run(lm->vloc, st, err)) return undo(r);
   }
   // slot 0 lent its key-frame staging words (LI_KF_PENDING .. LI_SORT_N1) to the build: it leaves as fresh as every other slot
@@ -781,9 +782,9 @@ int lm_host_loc_enable(LmHost* lm, const DevCtx& dfull, const alego_kf_in* frame
   if (ovf) { *err = "alego_loc_enable: a frame was truncated while it was sorted"; return undo(ALEGO_ERR_CAPACITY); }
   // The slots' rings give their memory back (no scan has used them).  The per-slot key-frame sort jobs in the job tables of vm[g] / vk[g]
   // (lm_host_create) still name those rings: they run only for a slot whose LI_KF_PENDING is set, which lm_store_kf alone sets, and neither
-  // lm_store_kf nor a vk round is ever launched on a localising handle (launch_lm_register returns before it; lm_kf_changed, retransform and
+  // lm_store_kf nor a vk round is ever launched on a localising handle (launch_lm_register returns before it; retransform and
   // lm_host_graph_apply sit behind API calls that refuse such a handle).
-  for (void* p : {(void*)L.kfs_c, (void*)L.kfs_s, (void*)L.kfs_n, (void*)L.kfs_box, (void*)L.kf_raw_c, (void*)L.kf_raw_s, (void*)L.kf_raw_o, (void*)L.kf_cnt, (void*)L.kf_pose}) release(lm, p);
+  ring_release(lm, L);
   L = T;
   return 0;
 }
@@ -806,13 +807,10 @@ int lm_host_graph_enable(LmHost* lm, int max_loops, const double* odom_var6, std
   static const double dflt[6] = {1e-6, 1e-6, 1e-6, 1e-8, 1e-8, 1e-6};   // laserMapping.cpp:68-70
   const double* v = odom_var6 ? odom_var6 : dflt;
   for (int k = 0; k < 6; ++k) if (!(v[k] > 0.0) || !(v[k] < 1e300)) { *err = "graph_enable: variances must be positive and finite"; return ALEGO_ERR_ARG; }
-  // the chain starts with the prior on frame 0: the graph has to exist before the first key frame
-  std::vector<int> li((size_t)lm->n_slots * LI_COUNT);
-  if (hipMemcpy(li.data(), L.li, li.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { *err = "graph_enable: device read failed"; return ALEGO_ERR_HIP; }
-  for (int s = 0; s < lm->n_slots; ++s) if (li[(size_t)s * LI_COUNT + LI_NKF] != 0) { *err = "graph_enable: call it before the first key frame is saved"; return ALEGO_ERR_ARG; }
+  if (int r = rings_empty(lm, "graph_enable", false, err)) return r;   // the chain starts with the prior on frame 0: the graph has to exist before the first key frame
   const size_t B = lm->n_slots, F = L.arc_frames_cap;
   LmCtx T = L;
-  bool ok = A(lm, &T.pg_chain, B * F, err) && A(lm, &T.pg_loops, B * max_loops, err) && A(lm, &T.pg_corr, B * 16, err) && A(lm, &T.pg_stat, B * 4, err) &&
+  bool ok = A(lm, &T.pg_chain, B * F, err) && A(lm, &T.pg_loops, B * max_loops, err) && A(lm, &T.pg_corr, B * 16, err) && A(lm, &T.pg_stat, B * PS_W, err) &&
             A(lm, &T.pg_est, B * F * 12, err);
   if (!ok) return ALEGO_ERR_HIP;
   for (int k = 0; k < 6; ++k) T.pg_odom_var[k] = v[k];
@@ -848,25 +846,14 @@ int lm_host_graph_apply(LmHost* lm, const std::vector<int>& apply, const int* ap
   return 0;
 }
 int lm_host_map_get_keyframe(LmHost* lm, int slot, int id, alego_keyframe* out, std::string* err) {
-  int st[4];
+  int st[AS_W];
   if (int r = map_stat(lm, slot, st, err)) return r;
-  if (id < 0 || id >= st[0]) { *err = "map_get_keyframe: frame not archived"; return ALEGO_ERR_ARG; }
-  const LmCtx& L = lm->L;
-  const size_t fs = (size_t)slot * L.arc_frames_cap + id;
-  int tab[4];
-  float kp[8];
-  if (hipMemcpy(tab, L.arc_tab + fs * 4, sizeof(tab), hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(kp, L.arc_pose + fs * 8, sizeof(kp), hipMemcpyDeviceToHost) != hipSuccess) { *err = "map_get_keyframe: copy failed"; return ALEGO_ERR_HIP; }
-  out->id = id;
-  for (int k = 0; k < 6; ++k) out->pose[k] = kp[k];
-  out->n_corner = tab[1]; out->n_surf = tab[2]; out->n_outlier = tab[3];
-  if ((out->corner && tab[1] > out->corner_cap) || (out->surf && tab[2] > out->surf_cap) || (out->outlier && tab[3] > out->outlier_cap)) { *err = "map_get_keyframe: buffer too small"; return ALEGO_ERR_CAPACITY; }
-  const float4* src = L.arc_pts + (size_t)slot * L.arc_points_cap + tab[0];
-  hipError_t e = hipSuccess;
-  if (out->corner && tab[1]) e = hipMemcpy(out->corner, src, (size_t)tab[1] * 16, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && out->surf && tab[2]) e = hipMemcpy(out->surf, src + tab[1], (size_t)tab[2] * 16, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && out->outlier && tab[3]) e = hipMemcpy(out->outlier, src + tab[1] + tab[2], (size_t)tab[3] * 16, hipMemcpyDeviceToHost);
-  if (e != hipSuccess) { *err = std::string("map_get_keyframe: ") + hipGetErrorString(e); return ALEGO_ERR_HIP; }
-  return 0;
+  if (id < 0 || id >= st[AS_FRAMES]) { *err = "map_get_keyframe: frame not archived"; return ALEGO_ERR_ARG; }
+  int tab[AT_W];
+  if (hipMemcpy(tab, arc_tab_of(lm->L, slot, id), sizeof(tab), hipMemcpyDeviceToHost) != hipSuccess) { *err = "map_get_keyframe: copy failed"; return ALEGO_ERR_HIP; }
+  const KfArcFrame A = kf_arc_frame(lm->L, slot, id, tab);
+  const float4* const src[KF_KINDS] = {A.pts, A.pts + A.nc, A.pts + A.nc + A.ns};
+  return frame_to_host("map_get_keyframe", id, A.pose, tab + AT_N, src, out, err);
 }
 // the filtered (gv.out) or raw (gv.in) cloud of `n` points to the caller: count only, capacity error, or copy
 static int copy_out(const float4* src, int n, alego_point* out, int cap, const char* what, std::string* err) {
@@ -876,13 +863,13 @@ static int copy_out(const float4* src, int n, alego_point* out, int cap, const c
   return n;
 }
 int lm_host_map_assemble(LmHost* lm, int slot, int kinds, float leaf, alego_point* out, int cap, std::string* err) {
-  int st[4];
+  int st[AS_W];
   if (int r = map_stat(lm, slot, st, err)) return r;
   if ((kinds & ~15) || !(kinds & 7) || cap < 0) { *err = "map_assemble: kinds must select surf / corner / outlier (optionally | FRAME_ID)"; return ALEGO_ERR_ARG; }
   hipStream_t s = stream_of_slot(lm, slot);
   GvCtx& G = lm->gv;
   if (int r = gv_reserve(&G, lm->L.arc_points_cap, err)) return r == -3 ? ALEGO_ERR_CAPACITY : ALEGO_ERR_HIP;
-  launch_map_assemble(lm->L, slot, st[0], kinds, G.in, lm->arc_off, G.cnt, s);
+  launch_map_assemble(lm->L, slot, st[AS_FRAMES], kinds, G.in, lm->arc_off, G.cnt, s);
   int n = 0;
   if (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(&n, G.cnt, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { *err = "map_assemble: assembly failed"; return ALEGO_ERR_HIP; }
   if (leaf <= 0.f) return copy_out(G.in, n, out, cap, "map_assemble", err);
@@ -892,14 +879,14 @@ int lm_host_map_assemble(LmHost* lm, int slot, int kinds, float leaf, alego_poin
   return copy_out(G.out, m, out, cap, "map_assemble", err);
 }
 int lm_host_map_keyposes(LmHost* lm, int slot, alego_point* out, int cap, std::string* err) {
-  int st[4];
+  int st[AS_W];
   if (int r = map_stat(lm, slot, st, err)) return r;
-  const int nf = st[0];
+  const int nf = st[AS_FRAMES];
   if (!out && cap == 0) return nf;
   if (cap < nf || (nf > 0 && !out)) { *err = "map_keyposes: output capacity"; return ALEGO_ERR_CAPACITY; }
-  std::vector<float> kp((size_t)nf * 8);
-  if (nf > 0 && hipMemcpy(kp.data(), lm->L.arc_pose + (size_t)slot * lm->L.arc_frames_cap * 8, kp.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) { *err = "map_keyposes: copy failed"; return ALEGO_ERR_HIP; }
-  for (int i = 0; i < nf; ++i) out[i] = alego_point{kp[(size_t)i * 8 + 0], kp[(size_t)i * 8 + 1], kp[(size_t)i * 8 + 2], (float)i};   // saveMapCB :833-838
+  std::vector<float> kp((size_t)nf * KF_POSE_W);
+  if (nf > 0 && hipMemcpy(kp.data(), arc_pose_of(lm->L, slot, 0), kp.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) { *err = "map_keyposes: copy failed"; return ALEGO_ERR_HIP; }
+  for (int i = 0; i < nf; ++i) out[i] = alego_point{kp[(size_t)i * KF_POSE_W + 0], kp[(size_t)i * KF_POSE_W + 1], kp[(size_t)i * KF_POSE_W + 2], (float)i};   // saveMapCB :833-838
   return nf;
 }
 int lm_host_get_local_map(LmHost* lm, int slot, alego_point* corner, int corner_cap, alego_point* surf, int surf_cap, int* n_out, std::string* err) {
