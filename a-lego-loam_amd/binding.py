@@ -35,12 +35,15 @@ EXPORTS = [
     "alego_graph_enable", "alego_graph_status", "alego_graph_get_edges", "alego_graph_set_edges", "alego_graph_add_loops", "alego_graph_add_edge",
     "alego_graph_optimize", "alego_graph_get_estimate", "alego_graph_residuals",
     "alego_loc_select", "alego_loc_enable", "alego_loc_status",
+    "alego_reloc_enable", "alego_loc_relocalize", "alego_reloc_descriptor", "alego_reloc_match", "alego_debug_reloc_search",
 ]
 
 REPLAY_PINGPONG = 0x100
 REPLAY_BAG = 0x200
 MAP_SURF, MAP_CORNER, MAP_OUTLIER, MAP_FRAME_ID = 1, 2, 4, 8
 ERR_CAPACITY, ERR_ARG = -3, -4
+RELOC_MAX_CAND = 8
+RELOC_SECTORS, RELOC_RINGS = 60, 20
 FLAG_LO_INIT, FLAG_FEW_SURF, FLAG_FEW_CORNER, FLAG_LM_SKIPPED, FLAG_LM_FEW_FEATURES, FLAG_LM_KEYFRAME = 1, 2, 4, 8, 16, 32
 
 
@@ -110,6 +113,17 @@ def _loop_result(r):
                 iterations=int(r.iterations), n_source=int(r.n_source), n_target=int(r.n_target), fitness=float(r.fitness),
                 T=np.array(r.correction[:], np.float32).reshape(4, 4), t_correct=np.array(r.t_correct[:], np.float32).reshape(4, 4),
                 between=np.array(r.between[:], np.float64).reshape(3, 4), noise_variance=float(r.noise_variance))
+
+
+class RelocOpts(C.Structure):
+    _fields_ = [("n_cand", C.c_int32), ("verify", C.c_int32), ("apply", C.c_int32)]
+
+
+class RelocResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_cand", C.c_int32), ("cand_id", C.c_int32 * 8), ("cand_dist", C.c_int32 * 8), ("cand_shift", C.c_int32 * 8),
+                ("verified", C.c_int32), ("converged", C.c_int32), ("iterations", C.c_int32), ("n_source", C.c_int32), ("n_target", C.c_int32),
+                ("applied", C.c_int32), ("fitness", C.c_double), ("correction", C.c_float * 16), ("guess6", C.c_float * 6), ("t_map", C.c_float * 16),
+                ("rc", C.c_double * 12), ("params6", C.c_double * 6)]
 
 
 class GraphEdge(C.Structure):
@@ -327,6 +341,11 @@ def lib():
         L.alego_loc_select.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_int32, C.c_void_p]
         L.alego_loc_enable.argtypes = [C.c_void_p, C.POINTER(KfIn), C.c_int32, C.c_double]
         L.alego_loc_status.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.alego_reloc_enable.argtypes = [C.c_void_p, C.c_double, C.c_double]
+        L.alego_loc_relocalize.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(RelocOpts), C.POINTER(RelocResult)]
+        L.alego_reloc_descriptor.argtypes = [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
+        L.alego_reloc_match.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.alego_debug_reloc_search.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.alego_write_pcd.argtypes = [C.c_char_p, C.c_void_p, C.c_int32]
         L.alego_bag_read_pc2.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
         if L.alego_params_sizeof() != C.sizeof(AlegoParams):
@@ -382,6 +401,37 @@ def loc_select(keyposes6, xyz, radius, k):
     if n < 0:
         raise AlegoError(f"alego_loc_select failed ({n})")
     return ids[:n].copy()
+
+
+def reloc_descriptor(pts, max_range=0.0, z_offset=float("nan")):
+    """alego_reloc_descriptor: (descriptor (60, 20) u8 [sector][ring], ring key (20,) u16) of a sensor-frame cloud (host code of the library)"""
+    a = np.ascontiguousarray(pts, np.float32).reshape(-1, 4)
+    d = np.zeros((RELOC_SECTORS, RELOC_RINGS), np.uint8)
+    k = np.zeros(RELOC_RINGS, np.uint16)
+    rc = lib().alego_reloc_descriptor(a.ctypes.data, a.shape[0], float(max_range), float(z_offset), d.ctypes.data, k.ctypes.data)
+    if rc != 0:
+        raise AlegoError(f"alego_reloc_descriptor failed ({rc})")
+    return d, k
+
+
+def reloc_match(q, m):
+    """alego_reloc_match: (D, shift) of two descriptors — the brute force over all 60 shifts (host code of the library)"""
+    a = np.ascontiguousarray(q, np.uint8).reshape(RELOC_SECTORS * RELOC_RINGS)
+    b = np.ascontiguousarray(m, np.uint8).reshape(RELOC_SECTORS * RELOC_RINGS)
+    d, sh = C.c_int32(), C.c_int32()
+    rc = lib().alego_reloc_match(a.ctypes.data, b.ctypes.data, C.byref(d), C.byref(sh))
+    if rc != 0:
+        raise AlegoError(f"alego_reloc_match failed ({rc})")
+    return int(d.value), int(sh.value)
+
+
+def _reloc_result(r):
+    n = int(r.n_cand)
+    return dict(status=int(r.status), n_cand=n, cand_id=np.array(r.cand_id[:n], np.int32), cand_dist=np.array(r.cand_dist[:n], np.int32),
+                cand_shift=np.array(r.cand_shift[:n], np.int32), verified=int(r.verified), converged=int(r.converged), iterations=int(r.iterations),
+                n_source=int(r.n_source), n_target=int(r.n_target), applied=int(r.applied), fitness=float(r.fitness),
+                T=np.array(r.correction[:], np.float32).reshape(4, 4), guess6=np.array(r.guess6[:], np.float32),
+                t_map=np.array(r.t_map[:], np.float32).reshape(4, 4), rc=np.array(r.rc[:], np.float64), params6=np.array(r.params6[:], np.float64))
 
 
 def loop_constraint(correction, latest_pose6, closest_pose6):
@@ -853,6 +903,27 @@ class Handle:
         out = np.zeros(4, np.int32)
         self._check(lib().alego_loc_status(self._h, slot, out.ctypes.data), "alego_loc_status")
         return dict(frames=int(out[0]), window=int(out[1]), rebuilds=int(out[2]), optimized=int(out[3]))
+
+    # ---- relocalisation in the frozen map (needs loc_enable) ----
+    def reloc_enable(self, max_range=0.0, z_offset=float("nan")):
+        self._check(lib().alego_reloc_enable(self._h, float(max_range), float(z_offset)), "alego_reloc_enable")
+
+    def loc_relocalize(self, slots, n_cand=0, verify=-1, apply=False):
+        """alego_loc_relocalize: one dict per listed slot (status, candidates, the verified candidate's ICP, t_map, rc, params6)"""
+        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        out = (RelocResult * max(sl.shape[0], 1))()
+        opts = RelocOpts(int(n_cand), int(verify), int(bool(apply)))
+        self._check(lib().alego_loc_relocalize(self._h, sl.ctypes.data, sl.shape[0], C.byref(opts), out), "alego_loc_relocalize")
+        return [_reloc_result(out[i]) for i in range(sl.shape[0])]
+
+    def debug_reloc_search(self, map_desc, q_desc, n_cand):
+        """the search kernels of alego_loc_relocalize alone: (ids, dists, shifts), each (n_q, n_cand) int32, -1 where the map has fewer frames"""
+        m = np.ascontiguousarray(map_desc, np.uint8).reshape(-1, RELOC_SECTORS * RELOC_RINGS)
+        q = np.ascontiguousarray(q_desc, np.uint8).reshape(-1, RELOC_SECTORS * RELOC_RINGS)
+        ids, dists, shifts = (np.zeros((q.shape[0], n_cand), np.int32) for _ in range(3))
+        self._check(lib().alego_debug_reloc_search(self._h, m.ctypes.data, m.shape[0], q.ctypes.data, q.shape[0], int(n_cand), ids.ctypes.data,
+                                                   dists.ctypes.data, shifts.ctypes.data), "alego_debug_reloc_search")
+        return ids, dists, shifts
 
     # ---- the key-pose graph (needs map_enable) ----
     def graph_enable(self, max_loops, odom_variance=None):

@@ -44,6 +44,17 @@ int loop_search(LcCtx** pc, const LmCtx& L, const alego_params& P, int n_slots, 
 void loop_ctx_destroy(LcCtx* C);
 void loop_ctx_set_budget(LcCtx** pc, long long points);
 int loop_debug_nn1(const alego_point* tgt, int n_tgt, const alego_point* q, int nq, int32_t* idx, float* d2, hipStream_t st, std::string* err);
+struct RlCtx;   // kernels_reloc.hip: relocalisation in the frozen map
+int reloc_enable(RlCtx** pr, const LmCtx& L, int n_slots, double max_range, double z_offset, hipStream_t st, std::string* err);
+bool reloc_enabled(const RlCtx* R);
+int reloc_run(RlCtx* R, LcCtx** lc, const LmCtx& L, const alego_params& P, const int* slots, int n, int n_cand, int verify, int apply, alego_reloc_result* out,
+              hipStream_t st, std::string* err);
+int reloc_debug_search(RlCtx** pr, const uint8_t* map_desc, int n_map, const uint8_t* q_desc, int n_q, int n_cand, int32_t* ids, int32_t* dists, int32_t* shifts,
+                       hipStream_t st, std::string* err);
+int reloc_debug_get(RlCtx* R, int slot, const char* name, const void** src, size_t* bytes);
+void reloc_debug_stats(const RlCtx* R, int out[2]);
+void reloc_ctx_set(RlCtx** pr, int what, long long v);
+void reloc_ctx_destroy(RlCtx* R);
 void launch_dbg_transform_to_start(const double* params6, const float4* pts, int n, float4* out, hipStream_t st);
 int ip_configure(const DevCtx& d);
 int lo_configure();
@@ -87,6 +98,7 @@ struct alego_handle {
   LcCtx* lc = nullptr;         // alego_loop_search: detection / chunk scratch, allocated by the first call and kept
   bool graph_on = false;       // alego_graph_enable: the key-pose graph exists
   PgCtx* pg = nullptr;         // alego_graph_optimize: chunk scratch, allocated by the first call and kept
+  RlCtx* rl = nullptr;         // alego_reloc_enable: map / query descriptors; search scratch allocated by the first call and kept
 };
 
 namespace {
@@ -386,6 +398,7 @@ void alego_destroy(alego_handle* h) {
   if (g_prof == &h->prof) g_prof = nullptr;
   if (h->lm) lm_host_destroy(h->lm);
   loop_ctx_destroy(h->lc);
+  reloc_ctx_destroy(h->rl);
   graph_ctx_destroy(h->pg);
   for (void* p : h->allocs) (void)guard_free(p);
   for (hipStream_t s : h->streams) hipStreamDestroy(s);
@@ -1055,6 +1068,8 @@ int alego_debug_set_option(alego_handle* h, const char* name, int value) {
   else if (s == "ALEGO_GV_SMALL_MAX") { HIP_TRY(h, sync_all(h)); return lm_host_set_gv_small_max(h->lm, value); }   // tools/gmap_timing.py: largest cloud alego_voxel_grid gives to one workgroup
   else if (s == "ALEGO_PG_BUDGET") graph_ctx_set_budget(&h->pg, value);   // tests / tools: bytes of scratch per chunk of alego_graph_optimize
   else if (s == "ALEGO_LC_BUDGET") loop_ctx_set_budget(&h->lc, value);   // tests / tools: raw sub-map points per chunk of alego_loop_search
+  else if (s == "ALEGO_RL_BUDGET") reloc_ctx_set(&h->rl, 0, value);   // tests / tools: (query, frame) pairs per chunk of the relocalisation search
+  else if (s == "ALEGO_RL_BRUTE") reloc_ctx_set(&h->rl, 1, value);    // tests / tools: evaluate every pair instead of pruning with the ring-key bound
   else if (s == "ALEGO_SHARD_SLICE") return lm_host_debug_slice(h->lm, value & 0xff, value >> 8, &h->err);   // tests: rank | world << 8 without a communicator
   else { h->err = "unknown option " + s; return ALEGO_ERR_ARG; }
   return 0;
@@ -1301,6 +1316,42 @@ int alego_loc_enable(alego_handle* h, const alego_kf_in* frames, int32_t n, doub
   HIP_TRY(h, sync_all(h));
   return lm_host_loc_enable(h->lm, h->d, frames, n, radius, &h->err);
 }
+// ---- relocalisation (kernels_reloc.hip) ----
+int alego_reloc_enable(alego_handle* h, double max_range, double z_offset) {
+  if (!h) return ALEGO_ERR_ARG;
+  if (!h->lm || !lm_host_localising(h->lm)) { h->err = "alego_reloc_enable: the handle does not localise (alego_loc_enable)"; return ALEGO_ERR_ARG; }
+  if (reloc_enabled(h->rl)) { h->err = "alego_reloc_enable: already enabled"; return ALEGO_ERR_ARG; }
+  hipSetDevice(h->device);
+  g_prof = &h->prof;
+  HIP_TRY(h, sync_all(h));
+  return reloc_enable(&h->rl, *lm_host_ctx(h->lm), h->d.n_slots, max_range, z_offset, h->stream, &h->err);
+}
+int alego_loc_relocalize(alego_handle* h, const int32_t* slots, int32_t n, const alego_reloc_opts* opts, alego_reloc_result* out) {
+  if (!h || n < 0 || (n > 0 && (!slots || !out))) return ALEGO_ERR_ARG;
+  if (!reloc_enabled(h->rl)) { h->err = "alego_loc_relocalize: relocalisation is off (alego_loc_enable, then alego_reloc_enable)"; return ALEGO_ERR_ARG; }
+  int n_cand = 4, verify = 1, apply = 0;
+  if (opts) { if (opts->n_cand > 0) n_cand = opts->n_cand; if (opts->verify >= 0) verify = opts->verify; apply = opts->apply != 0; }
+  if (n_cand > ALEGO_RELOC_MAX_CAND || verify > n_cand) { h->err = "alego_loc_relocalize: n_cand is 1 .. ALEGO_RELOC_MAX_CAND, verify 0 .. n_cand"; return ALEGO_ERR_ARG; }
+  std::vector<char> seen((size_t)h->d.n_slots, 0);
+  for (int i = 0; i < n; ++i) {
+    if (slots[i] < 0 || slots[i] >= h->d.n_slots) { h->err = "alego_loc_relocalize: slot out of range"; return ALEGO_ERR_ARG; }
+    if (seen[slots[i]]) { h->err = "alego_loc_relocalize: slot " + std::to_string(slots[i]) + " is listed twice"; return ALEGO_ERR_ARG; }
+    seen[slots[i]] = 1;
+  }
+  hipSetDevice(h->device);
+  g_prof = &h->prof;
+  HIP_TRY(h, sync_all(h));   // behind everything already queued on every stream group
+  return reloc_run(h->rl, &h->lc, *lm_host_ctx(h->lm), h->P, slots, n, n_cand, verify, apply, out, h->stream, &h->err);
+}
+int alego_debug_reloc_search(alego_handle* h, const uint8_t* map_desc, int32_t n_map, const uint8_t* q_desc, int32_t n_q, int32_t n_cand,
+                             int32_t* ids, int32_t* dists, int32_t* shifts) {
+  if (!h || n_map < 0 || n_map > (1 << 24) - 1 || n_q < 0 || n_cand < 1 || n_cand > ALEGO_RELOC_MAX_CAND || (n_map > 0 && !map_desc) || (n_q > 0 && (!q_desc || !ids || !dists || !shifts)))
+    return ALEGO_ERR_ARG;
+  hipSetDevice(h->device);
+  g_prof = &h->prof;
+  return reloc_debug_search(&h->rl, map_desc, n_map, q_desc, n_q, n_cand, ids, dists, shifts, h->stream, &h->err);
+}
+
 int alego_loc_status(alego_handle* h, int slot, int32_t out[4]) {
   if (int r = check_slot(h, slot)) return r;
   if (!out) return ALEGO_ERR_ARG;
@@ -1423,6 +1474,21 @@ int alego_debug_get(alego_handle* h, int slot, const char* name, void* out, int 
   HIP_TRY(h, hipMemcpyAsync(sc, d.scal + (size_t)slot * SC_COUNT, sizeof(sc), hipMemcpyDeviceToHost, stream_of(h, slot)));
   HIP_TRY(h, hipStreamSynchronize(stream_of(h, slot)));
   const std::string s(name);
+  if (s.rfind("rl_", 0) == 0) {   // relocalisation: descriptors as bytes; "rl_stats": pairs evaluated by the second round / pairs in all of the last search
+    if (s == "rl_stats") {
+      if (cap_bytes < 8) { h->err = "debug_get: buffer too small"; return ALEGO_ERR_CAPACITY; }
+      reloc_debug_stats(h->rl, (int*)out);
+      *count = 2; *dtype = 2;
+      return 0;
+    }
+    const void* rsrc = nullptr;
+    size_t bytes = 0;
+    if (reloc_debug_get(h->rl, slot, name, &rsrc, &bytes)) { h->err = std::string("debug_get: ") + name + " needs alego_reloc_enable"; return ALEGO_ERR_ARG; }
+    if ((size_t)cap_bytes < bytes) { h->err = "debug_get: buffer too small"; return ALEGO_ERR_CAPACITY; }
+    if (bytes) HIP_TRY(h, hipMemcpy(out, rsrc, bytes, hipMemcpyDeviceToHost));
+    *count = (int)bytes; *dtype = 3;
+    return 0;
+  }
   const size_t base = (size_t)slot * d.N;
   const int M = sc[SC_M];
   const int cur = sc[SC_CUR];  // buffer written by the last processed scan

@@ -58,6 +58,31 @@ DEV_INLINE DQuat dq_from_mat(const double m[9]) {
   }
   return q;
 }
+// dq_from_mat with the largest-diagonal branch spelt out per axis: the same operations in the same order, without the dynamically indexed
+// locals that put a small kernel's frame in scratch (rl_apply, kernels_reloc.hip); test_relocalize.py pins the two to each other bit for bit
+template <int I> DEV_INLINE DQuat dq_from_mat_diag(const double* m) {
+  constexpr int J = (I + 1) % 3, K = (J + 1) % 3;
+  double t = sqrt(m[I * 3 + I] - m[J * 3 + J] - m[K * 3 + K] + 1.0);
+  double v[3];
+  v[I] = 0.5 * t; t = 0.5 / t;
+  DQuat q;
+  q.w = (m[K * 3 + J] - m[J * 3 + K]) * t;
+  v[J] = (m[J * 3 + I] + m[I * 3 + J]) * t;
+  v[K] = (m[K * 3 + I] + m[I * 3 + K]) * t;
+  q.x = v[0]; q.y = v[1]; q.z = v[2];
+  return q;
+}
+DEV_INLINE DQuat dq_from_mat_flat(const double* m) {
+  double t = m[0] + m[4] + m[8];
+  if (t > 0) {
+    DQuat q;
+    t = sqrt(t + 1.0); q.w = 0.5 * t; t = 0.5 / t;
+    q.x = (m[7] - m[5]) * t; q.y = (m[2] - m[6]) * t; q.z = (m[3] - m[1]) * t;
+    return q;
+  }
+  if (m[4] > m[0]) return m[8] > m[4] ? dq_from_mat_diag<2>(m) : dq_from_mat_diag<1>(m);
+  return m[8] > m[0] ? dq_from_mat_diag<2>(m) : dq_from_mat_diag<0>(m);
+}
 DEV_INLINE DQuat dq_inverse(const DQuat& q) {
   const double n2 = q.w * q.w + q.x * q.x + q.y * q.y + q.z * q.z;
   return DQuat{q.w / n2, -q.x / n2, -q.y / n2, -q.z / n2};
@@ -65,13 +90,14 @@ DEV_INLINE DQuat dq_inverse(const DQuat& q) {
 DEV_INLINE DQuat ldq(const double* p) { return DQuat{p[0], p[1], p[2], p[3]}; }
 DEV_INLINE void stq(double* p, const DQuat& q) { p[0] = q.w; p[1] = q.x; p[2] = q.y; p[3] = q.z; }
 // correctPoses (laserMapping.cpp:579-580): the pose (q[4], t[3]) <- [R | c] * pose, rc_ the 3x4 [R | c] of a loop-closure correction (f32 or f64)
-template <class T> DEV_INLINE void dq_apply_correction(double* q, double* t3, const T* rc_) {
+// (FLAT: dq_from_mat_flat instead of dq_from_mat, for kernels that must stay out of scratch)
+template <class T, bool FLAT = false> DEV_INLINE void dq_apply_correction(double* q, double* t3, const T* rc_) {
   double rc[12], R[9], M[9], t[3];
   for (int k = 0; k < 12; ++k) rc[k] = (double)rc_[k];
   dq_to_mat(ldq(q), R);
   for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) M[i * 3 + j] = rc[i * 4 + 0] * R[0 * 3 + j] + rc[i * 4 + 1] * R[1 * 3 + j] + rc[i * 4 + 2] * R[2 * 3 + j];
   for (int i = 0; i < 3; ++i) t[i] = rc[i * 4 + 0] * t3[0] + rc[i * 4 + 1] * t3[1] + rc[i * 4 + 2] * t3[2] + rc[i * 4 + 3];
-  stq(q, dq_from_mat(M));
+  if constexpr (FLAT) stq(q, dq_from_mat_flat(M)); else stq(q, dq_from_mat(M));
   for (int i = 0; i < 3; ++i) t3[i] = t[i];
 }
 

@@ -31,6 +31,7 @@
 #include "guard_alloc.h"
 #include "icp_math.h"
 #include "kf_store.h"
+#include "loop_ctx.h"
 #include "prof.h"
 #include "voxel.h"
 
@@ -38,15 +39,7 @@
 #define LC_IT 512     // lc_icp
 #define LC_PRUNE 0.999999
 
-struct LcDet {        // lc_detect's verdict on one listed slot
-  int status;         // 0 no candidate, 1 attempt, -1 the archive dropped frames
-  int latest, closest, jlo, jhi;   // history frames jlo .. jhi (jhi < jlo: none)
-  int n_src, n_raw, pad;
-  float pose_latest[6], pose_closest[6];
-};
-struct LcJob { int li, slot, src_off, raw_off, cell_off, cell_cap; };   // one attempted slot of a chunk and its scratch regions
 struct LcGrid { double mn[3], slack[3], h, inv_h; int g[3], ncell; };
-struct LcOut { int converged, iterations, n_source, n_target; double fitness; float correction[16]; };
 
 // ---- detection ------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(LC_DT) lc_detect(LmCtx L, const int* list, alego_params P, LcDet* det) {
@@ -460,14 +453,9 @@ static int lc_reserve(LcCtx* C, int list_cap, long long need, std::string* err) 
   return 0;
 }
 
-// one piece of the list (at most list_cap entries): detection, then the attempted slots in chunks
-static int lc_piece(LcCtx* C, const LmCtx& L, const alego_params& P, const int* slots, int n, alego_loop_result* res, hipStream_t st, std::string* err) {
-  if (hipMemcpyAsync(C->list, slots, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess) { *err = "loop search: upload failed"; return ALEGO_ERR_HIP; }
-  ALEGO_LAUNCH(lc_detect, dim3(n), dim3(LC_DT), 0, st, L, C->list, P, C->det);
-  std::vector<LcDet> det((size_t)n);
-  if (hipMemcpyAsync(det.data(), C->det, (size_t)n * sizeof(LcDet), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-    *err = "loop search: detection failed"; return ALEGO_ERR_HIP;
-  }
+// The attempts of one piece (det[i].status == 1; C->det holds det already): chunks of consecutive attempts, each gathered by `gather`, then
+// VoxelGrid(lc_leaf), lc_grid and lc_icp; o[i] = the verdict on attempt i
+static int lc_attempts(LcCtx* C, const alego_params& P, const int* slots, const LcDet* det, int n, const LcGather& gather, LcOut* o, hipStream_t st, std::string* err) {
   // chunks of consecutive attempts whose raw sub-maps, sources and cells fit the budget (a larger single slot grows the scratch)
   const int nfr = 1 + 2 * std::max(0, P.lc_search_num) + 1;
   std::vector<std::vector<LcJob>> chunks;
@@ -492,7 +480,7 @@ static int lc_piece(LcCtx* C, const LmCtx& L, const alego_params& P, const int* 
     for (const auto& ch : chunks) {
       const int J = (int)ch.size();
       if (hipMemcpyAsync(C->jobs, ch.data(), (size_t)J * sizeof(LcJob), hipMemcpyHostToDevice, st) != hipSuccess) { *err = "loop search: upload failed"; return ALEGO_ERR_HIP; }
-      ALEGO_LAUNCH(lc_gather, dim3(nfr, J), dim3(LC_DT), 0, st, L, C->jobs, C->det, C->src, C->raw);
+      gather(C->jobs, C->det, J, nfr, C->src, C->raw, st);
       vjobs.emplace_back((size_t)J);
       std::vector<VoxJob>& vj = vjobs.back();
       std::memset(vj.data(), 0, vj.size() * sizeof(VoxJob));
@@ -511,10 +499,24 @@ static int lc_piece(LcCtx* C, const LmCtx& L, const alego_params& P, const int* 
       // the next chunk reuses jobs / scratch: the copies and kernels above are ordered on `st`
     }
   }
-  std::vector<LcOut> o((size_t)n);
-  if (hipMemcpyAsync(o.data(), C->out, (size_t)n * sizeof(LcOut), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+  if (hipMemcpyAsync(o, C->out, (size_t)n * sizeof(LcOut), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
     *err = "loop search: kernels failed"; return ALEGO_ERR_HIP;
   }
+  return 0;
+}
+
+// one piece of the list (at most list_cap entries): detection, then the attempted slots in chunks
+static int lc_piece(LcCtx* C, const LmCtx& L, const alego_params& P, const int* slots, int n, alego_loop_result* res, hipStream_t st, std::string* err) {
+  if (hipMemcpyAsync(C->list, slots, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess) { *err = "loop search: upload failed"; return ALEGO_ERR_HIP; }
+  ALEGO_LAUNCH(lc_detect, dim3(n), dim3(LC_DT), 0, st, L, C->list, P, C->det);
+  std::vector<LcDet> det((size_t)n);
+  if (hipMemcpyAsync(det.data(), C->det, (size_t)n * sizeof(LcDet), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+    *err = "loop search: detection failed"; return ALEGO_ERR_HIP;
+  }
+  std::vector<LcOut> o((size_t)n);
+  if (int rc = lc_attempts(C, P, slots, det.data(), n, [&](const LcJob* jobs, const LcDet* dd, int J, int nfr, float4* src, float4* raw, hipStream_t s2) {
+        ALEGO_LAUNCH(lc_gather, dim3(nfr, J), dim3(LC_DT), 0, s2, L, jobs, dd, src, raw);
+      }, o.data(), st, err)) return rc;
   for (int i = 0; i < n; ++i) {
     alego_loop_result& r = res[i];
     std::memset(&r, 0, sizeof(r));
@@ -539,6 +541,15 @@ int loop_search(LcCtx** pc, const LmCtx& L, const alego_params& P, int n_slots, 
   for (int i0 = 0; i0 < n; i0 += C->list_cap)
     if (int rc = lc_piece(C, L, P, slots + i0, std::min(C->list_cap, n - i0), res + i0, st, err)) return rc;
   return 0;
+}
+
+int loop_attempts(LcCtx** pc, const alego_params& P, int n_slots, const int* slots, const LcDet* det, int n, const LcGather& gather, LcOut* out, hipStream_t st, std::string* err) {
+  if (!*pc) *pc = new LcCtx();
+  LcCtx* C = *pc;
+  if (n > n_slots) { *err = "loop attempts: more entries than slots"; return ALEGO_ERR_ARG; }
+  if (int rc = lc_reserve(C, n_slots, 0, err)) return rc;
+  if (n > 0 && hipMemcpyAsync(C->det, det, (size_t)n * sizeof(LcDet), hipMemcpyHostToDevice, st) != hipSuccess) { *err = "loop attempts: upload failed"; return ALEGO_ERR_HIP; }
+  return lc_attempts(C, P, slots, det, n, gather, out, st, err);
 }
 
 int loop_debug_nn1(const alego_point* tgt, int n_tgt, const alego_point* q, int nq, int32_t* idx, float* d2, hipStream_t st, std::string* err) {

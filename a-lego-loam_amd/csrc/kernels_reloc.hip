@@ -1,0 +1,561 @@
+// kernels_reloc.hip — alego_loc_relocalize: slots of a localising handle are placed in the frozen key-frame map
+// without an initial pose.  The rule is reloc_math.h's; everything here returns exactly what its brute force returns.
+//
+//   rl_desc      one workgroup per map frame (at alego_reloc_enable) or per listed slot: every point is read once, binned, and its code
+//                raised into an LDS word per bin with atomicMax (a maximum of integers does not depend on the order); the tile is then
+//                packed to bytes and the ring key summed from it
+//   rl_bound     one thread per (query, frame): B = sum over rings of |keyQ - keyM| (<= dist(Q, M, s) for every s)
+//   rl_pick      one workgroup per query: the n_cand frames smallest in (B, id)
+//   rl_search    the hot path.  One wavefront per (query, frame) pair of a list, ONE LANE PER SHIFT: Q sits twice over in LDS (120 columns of
+//                5 words), so lane s reads column c + s — 5 words apart from its neighbour, and 5 is coprime to the 64 banks: no conflicts —
+//                while M's 300 words are wave-uniform (scalar loads).  v_sad_u8 sums four absolute byte differences per instruction; the
+//                wave arg-min of (dist << 8 | s) gives D and the smallest s attaining it.
+//   rl_list2     one workgroup per query: tau = the largest D among the n_cand frames rl_pick chose; the list of ALL frames with B <= tau, in id
+//                order.  A frame with B > tau has D >= B > tau: it can neither enter the n_cand smallest (D, id) nor tie with them.
+//   rl_topk      one workgroup per query: the n_cand smallest (D, id) of the second list
+//   rl_gather    verification: the slot's current scan under the guess (source) and the map frames around the candidate under their key poses
+//                (raw sub-map), from the map store through kf_store.h's views; VoxelGrid, lc_grid and lc_icp are kernels_loop.hip's (loop_ctx.h)
+//   rl_apply     one lane per accepted slot: map -> odom corrected as lm_apply_correction does, params_ replaced
+// Phase boundaries are kernel boundaries; no workgroup waits for another.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "../../include/alego_mi355x.h"
+#include "dev_common.h"
+#include "dev_cost.h"
+#include "guard_alloc.h"
+#include "kf_store.h"
+#include "loop_ctx.h"
+#include "prof.h"
+#include "reloc_math.h"
+#include "wave.h"
+
+#define RL_T 256
+#define RL_WAVES (RL_T / 64)
+#define RL_SEARCH_BLOCKS 64        // workgroups per query of rl_search at most
+#ifndef RL_BUDGET_DEFAULT
+#define RL_BUDGET_DEFAULT (1 << 22)   // (query, frame) pairs per chunk of the search: 12 B of scratch each
+#endif
+static_assert(RL_NR % 4 == 0 && RL_SW == 5, "a sector is five words: the lanes of rl_search stride 5 words");
+
+// one record per listed slot, written by rl_desc (mode 1): what the host needs of the slot's state
+struct RlSlot {
+  int frame, n[KF_KINDS];   // LI_FRAME; points of laser_corner_ds_, laser_surf_ds_, laser_outlier_ds_ (clamped to their capacities)
+  double t_m2l[3], q_m2l[4];
+};
+
+// ---- descriptors ----------------------------------------------------------------------------------------------------------------------
+// mode 0: frame blockIdx.x of the map store -> desc / key row blockIdx.x; mode 1: the current scan of slot list[blockIdx.x] -> row `slot`,
+// and for the host the slot's record state[blockIdx.x] and a copy of its ring key klist[blockIdx.x]
+__global__ void __launch_bounds__(RL_T) rl_desc(LmCtx L, int mode, const int* list, float w, float zoff, uint32_t* desc, uint16_t* key, RlSlot* state, uint16_t* klist) {
+  __shared__ int s_bin[RL_BYTES];
+  const int tid = threadIdx.x;
+  const int e = mode == 0 ? (int)blockIdx.x : list[blockIdx.x];   // map frame / slot
+  for (int i = tid; i < RL_BYTES; i += RL_T) s_bin[i] = 0;
+  __syncthreads();
+  const int* li = L.li + (size_t)(mode == 0 ? 0 : e) * LI_COUNT;
+#pragma unroll
+  for (int kind = 0; kind < KF_KINDS; ++kind) {
+    const float4* pts;
+    int n;
+    if (mode == 0) {
+      const KfRingRow R = kf_ring_row_at(L, 0, e, kind);
+      pts = R.raw; n = min(R.cnt[kind], R.cap);
+    } else {
+      const int cap = kf_cap_of(L, kind);
+      pts = kf_pick(kind, L.cur_corner_ds, L.cur_surf_ds, L.cur_outl_ds) + (size_t)e * cap;
+      n = min(li[LI_NCUR_C + kind], cap);
+    }
+    for (int i = tid; i < n; i += RL_T) {
+      const float4 p = pts[i];
+      int bin, code;
+      if (rl_bin(p.x, p.y, p.z, w, zoff, &bin, &code)) atomicMax(&s_bin[bin], code);
+    }
+  }
+  __syncthreads();
+  uint32_t* d = desc + (size_t)e * RL_WORDS;
+  for (int i = tid; i < RL_WORDS; i += RL_T)
+    d[i] = (uint32_t)s_bin[4 * i] | ((uint32_t)s_bin[4 * i + 1] << 8) | ((uint32_t)s_bin[4 * i + 2] << 16) | ((uint32_t)s_bin[4 * i + 3] << 24);
+  if (tid < RL_NR) {
+    int s = 0;
+    for (int c = 0; c < RL_NS; ++c) s += s_bin[c * RL_NR + tid];
+    key[(size_t)e * RL_NR + tid] = (uint16_t)s;
+    if (mode == 1) klist[(size_t)blockIdx.x * RL_NR + tid] = (uint16_t)s;
+  }
+  if (mode == 1 && tid == 0) {
+    const double* ld = L.ld + (size_t)e * LD_COUNT;
+    RlSlot S;
+    S.frame = li[LI_FRAME];
+    S.n[KF_CORNER] = min(li[LI_NCUR_C], L.kf_cap_c); S.n[KF_SURF] = min(li[LI_NCUR_S], L.kf_cap_s); S.n[KF_OUTL] = min(li[LI_NCUR_O], L.kf_cap_o);
+    for (int k = 0; k < 3; ++k) S.t_m2l[k] = ld[LD_T_M2L + k];
+    for (int k = 0; k < 4; ++k) S.q_m2l[k] = ld[LD_Q_M2L + k];
+    state[blockIdx.x] = S;
+  }
+}
+static_assert(LI_NCUR_S == LI_NCUR_C + KF_SURF && LI_NCUR_O == LI_NCUR_C + KF_OUTL, "rl_desc / rl_gather index the current scan's counts by kind");
+
+// ring keys of descriptors handed in by the host (alego_debug_reloc_search): one workgroup of 64 per descriptor
+__global__ void __launch_bounds__(64) rl_keys(const uint32_t* desc, uint16_t* key) {
+  const uint8_t* d = (const uint8_t*)(desc + (size_t)blockIdx.x * RL_WORDS);
+  if (threadIdx.x < RL_NR) {
+    int s = 0;
+    for (int c = 0; c < RL_NS; ++c) s += d[c * RL_NR + threadIdx.x];
+    key[(size_t)blockIdx.x * RL_NR + threadIdx.x] = (uint16_t)s;
+  }
+}
+
+// ---- the search -------------------------------------------------------------------------------------------------------------------------
+// Queries of a chunk are numbered q = 0 .. nq - 1; qsel[q] = the row of qdesc / qkey (the slot).  Per query the scratch rows are N wide.
+// grid (ceil(N / RL_T), nq)
+__global__ void __launch_bounds__(RL_T) rl_bound(const int* qsel, const uint16_t* qkey, const uint16_t* mkey, int N, uint32_t* bound) {
+  const int q = blockIdx.y, i = blockIdx.x * RL_T + threadIdx.x;
+  if (i >= N) return;
+  bound[(size_t)q * N + i] = rl_key_bound(qkey + (size_t)qsel[q] * RL_NR, mkey + (size_t)i * RL_NR);
+}
+
+// the smallest key of the workgroup in every thread (s_min: RL_WAVES words of LDS; a barrier on entry protects the previous call's readers)
+DEV_INLINE unsigned long long rl_block_min(unsigned long long v, unsigned long long* s_min) {
+  v = bfly_min_u64(v);
+  __syncthreads();
+  if (lane_id() == 0) s_min[threadIdx.x >> 6] = v;
+  __syncthreads();
+  v = s_min[0];
+#pragma unroll
+  for (int w = 1; w < RL_WAVES; ++w) v = min(v, s_min[w]);
+  return v;
+}
+
+// grid (nq): listA[q][0 .. cntA[q]) = the n_cand frames smallest in (B, id), by n_cand rounds of "smallest key above the last one"
+__global__ void __launch_bounds__(RL_T) rl_pick(const uint32_t* bound, int N, int n_cand, int* listA, int* cntA) {
+  __shared__ unsigned long long s_min[RL_WAVES];
+  const int q = blockIdx.x, tid = threadIdx.x;
+  const uint32_t* b = bound + (size_t)q * N;
+  const int k = min(n_cand, N);
+  unsigned long long last = 0ull;
+  for (int r = 0; r < k; ++r) {
+    unsigned long long best = ~0ull;
+    for (int i = tid; i < N; i += RL_T) {
+      const unsigned long long key = ((unsigned long long)b[i] << 32) | (uint32_t)i;
+      if (r == 0 || key > last) best = min(best, key);
+    }
+    last = rl_block_min(best, s_min);
+    if (tid == 0) listA[q * ALEGO_RELOC_MAX_CAND + r] = (int)(last & 0xffffffffu);
+  }
+  if (tid == 0) cntA[q] = k;
+}
+
+// grid (workgroups per query, nq): res[q * stride + j] = D << 8 | s of frame list[q * stride + j], j < cnt[q]
+__global__ void __launch_bounds__(RL_T) rl_search(const int* qsel, const uint32_t* qdesc, const uint32_t* __restrict__ mdesc, const int* list, const int* cnt, int stride,
+                                                  uint32_t* res) {
+  __shared__ uint32_t s_q[2 * RL_WORDS];
+  const int q = blockIdx.y, tid = threadIdx.x;
+  const uint32_t* qd = qdesc + (size_t)qsel[q] * RL_WORDS;
+  for (int i = tid; i < 2 * RL_WORDS; i += RL_T) s_q[i] = qd[i < RL_WORDS ? i : i - RL_WORDS];
+  __syncthreads();
+  const int n = cnt[q];
+  const int lane = lane_id();
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const uint32_t* col = s_q + (lane < RL_NS ? lane : 0) * RL_SW;   // (lanes 60 .. 63 repeat shift 0 and are left out of the arg-min)
+  for (int j = blockIdx.x * RL_WAVES + wave; j < n; j += gridDim.x * RL_WAVES) {
+    const int f = __builtin_amdgcn_readfirstlane(list[(size_t)q * stride + j]);
+    const uint32_t* m = mdesc + (size_t)f * RL_WORDS;
+    uint32_t acc = 0;
+#pragma unroll 4
+    for (int c = 0; c < RL_NS; ++c) {
+#pragma unroll
+      for (int k = 0; k < RL_SW; ++k) acc = __builtin_amdgcn_sad_u8(col[c * RL_SW + k], m[c * RL_SW + k], acc);
+    }
+    const uint32_t best = wave_min_u32(lane < RL_NS ? (acc << 8) | (uint32_t)lane : 0xFFFFFFFFu);
+    if (lane == 0) res[(size_t)q * stride + j] = best;
+  }
+}
+
+// grid (nq): list2[q][0 .. cnt2[q]) = every frame with B <= tau in id order; tau = the largest D of the first round (brute: every frame)
+__global__ void __launch_bounds__(RL_T) rl_list2(const uint32_t* bound, int N, const uint32_t* resA, const int* cntA, int brute, int* list2, int* cnt2) {
+  __shared__ int s_w[RL_WAVES];
+  const int q = blockIdx.x, tid = threadIdx.x;
+  uint32_t tau = 0;
+  for (int j = 0; j < cntA[q]; ++j) tau = max(tau, resA[q * ALEGO_RELOC_MAX_CAND + j] >> 8);
+  if (brute) tau = 0xFFFFFFFFu;
+  const uint32_t* b = bound + (size_t)q * N;
+  int carry = 0;
+  for (int i0 = 0; i0 < N; i0 += RL_T) {
+    const int i = i0 + tid;
+    const int sel = (i < N && b[i] <= tau) ? 1 : 0;
+    int tot;
+    const int ex = carry + block_excl_scan<RL_WAVES>(sel, s_w, &tot);
+    if (sel) list2[(size_t)q * N + ex] = i;
+    carry += tot;
+  }
+  if (tid == 0) cnt2[q] = carry;
+}
+
+// grid (nq): the n_cand smallest (D, id) of the second list -> cand[q][r] = D << 32 | id << 8 | s (~0: none)
+__global__ void __launch_bounds__(RL_T) rl_topk(const int* list2, const int* cnt2, const uint32_t* res2, int N, int n_cand, unsigned long long* cand) {
+  __shared__ unsigned long long s_min[RL_WAVES];
+  const int q = blockIdx.x, tid = threadIdx.x;
+  const int n = cnt2[q];
+  unsigned long long last = 0ull;
+  for (int r = 0; r < n_cand; ++r) {
+    unsigned long long best = ~0ull;
+    if (r < n)
+      for (int j = tid; j < n; j += RL_T) {
+        const uint32_t v = res2[(size_t)q * N + j];
+        const unsigned long long key = ((unsigned long long)(v >> 8) << 32) | ((unsigned long long)(uint32_t)list2[(size_t)q * N + j] << 8) | (v & 0xffu);
+        if (r == 0 || key > last) best = min(best, key);
+      }
+    last = rl_block_min(best, s_min);
+    if (tid == 0) cand[q * ALEGO_RELOC_MAX_CAND + r] = r < n ? last : ~0ull;
+  }
+}
+
+// points of map frame f as every reader of the store counts them (rl_desc, rl_gather, the host's plan): each cloud clamped to its capacity
+KF_FN int rl_frame_points(const int* cnt, int cap_c, int cap_s, int cap_o) {
+  const int c = cnt[KF_CORNER] < cap_c ? cnt[KF_CORNER] : cap_c, s = cnt[KF_SURF] < cap_s ? cnt[KF_SURF] : cap_s, o = cnt[KF_OUTL] < cap_o ? cnt[KF_OUTL] : cap_o;
+  return c + s + o;
+}
+DEV_INLINE int rl_frame_points(const LmCtx& L, int f) { return rl_frame_points(kf_cnt_of(L, kf_row_at(L, 0, f)), L.kf_cap_c, L.kf_cap_s, L.kf_cap_o); }
+
+// ---- verification ---------------------------------------------------------------------------------------------------------------------
+// grid (1 + frames, jobs): x = 0 the source — the slot's current scan read out surf, corner, outlier under the guess (det.pose_latest);
+// x = 1 + k the map frame jlo + k under its key pose, surf, corner, outlier (as lc_gather reads an archived frame)
+__global__ void __launch_bounds__(RL_T) rl_gather(LmCtx L, const LcJob* jobs, const LcDet* det, float4* src, float4* raw) {
+  const LcJob J = jobs[blockIdx.y];
+  const LcDet& D = det[J.li];
+  const int order[KF_KINDS] = {KF_SURF, KF_CORNER, KF_OUTL};
+  float m[3][4];
+  if (blockIdx.x == 0) {
+    const int* li = L.li + (size_t)J.slot * LI_COUNT;
+    keypose_matrix(D.pose_latest, m);
+    float4* out = src + J.src_off;
+#pragma unroll
+    for (int o = 0; o < KF_KINDS; ++o) {
+      const int kind = order[o], cap = kf_cap_of(L, kind);
+      const float4* pts = kf_pick(kind, L.cur_corner_ds, L.cur_surf_ds, L.cur_outl_ds) + (size_t)J.slot * cap;
+      const int n = min(li[LI_NCUR_C + kind], cap);
+      for (int i = threadIdx.x; i < n; i += RL_T) out[i] = kf_transform(m, pts[i]);
+      out += n;
+    }
+    return;
+  }
+  const int f = D.jlo + (int)blockIdx.x - 1;
+  if (f > D.jhi) return;
+  int off = 0;
+  for (int j = D.jlo; j < f; ++j) off += rl_frame_points(L, j);
+  float4* out = raw + J.raw_off + off;
+  keypose_matrix(kf_pose_of(L, kf_row_at(L, J.slot, f)), m);
+#pragma unroll
+  for (int o = 0; o < KF_KINDS; ++o) {
+    const KfRingRow R = kf_ring_row_at(L, J.slot, f, order[o]);
+    const int n = min(R.cnt[order[o]], R.cap);
+    for (int i = threadIdx.x; i < n; i += RL_T) out[i] = kf_transform(m, R.raw[i]);
+    out += n;
+  }
+}
+
+struct RlApply { int slot, pad; double rc[12], params6[6]; };
+// one lane per accepted slot: correctPoses :579-580 on map -> odom exactly as lm_apply_correction computes it, then params_
+__global__ void __launch_bounds__(64) rl_apply(LmCtx L, const RlApply* a, int n) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  double* ld = L.ld + (size_t)a[i].slot * LD_COUNT;
+  dq_apply_correction<double, true>(ld + LD_Q_M2O, ld + LD_T_M2O, a[i].rc);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) ld[LD_PARAMS + k] = a[i].params6[k];
+}
+
+// ---- host -----------------------------------------------------------------------------------------------------------------------------
+struct RlCtx {
+  int N = 0, n_slots = 0;
+  float w = 0.f, zoff = 0.f;
+  uint32_t *mdesc = nullptr, *qdesc = nullptr;
+  uint16_t *mkey = nullptr, *qkey = nullptr;
+  int* list = nullptr;                  // [n_slots] the listed slots of a call
+  RlSlot* state = nullptr;              // [n_slots] their records (rl_desc)
+  uint16_t* klist = nullptr;            // [n_slots][RL_NR] their ring keys, in list order
+  RlApply* apply = nullptr;             // [n_slots]
+  std::vector<int> cnt;                 // host copy of the store: points per frame
+  std::vector<float> pose;              // [N][6]
+  // search scratch, grown on first use
+  long long budget = RL_BUDGET_DEFAULT;
+  int brute = 0;
+  size_t pairs_cap = 0, q_cap = 0;
+  uint32_t *bound = nullptr, *res2 = nullptr, *resA = nullptr;
+  int *list2 = nullptr, *cnt2 = nullptr, *listA = nullptr, *cntA = nullptr, *qsel = nullptr;
+  unsigned long long* cand = nullptr;
+  int stats[2] = {0, 0};                // of the last search: (query, frame) pairs the second round evaluated, pairs in all
+};
+
+template <class T>
+static bool rl_alloc(T** p, size_t count, std::string* err) {
+  void* q = nullptr;
+  hipError_t e = guard_malloc(&q, std::max<size_t>(16, count * sizeof(T)));
+  if (e != hipSuccess) { *err = std::string("relocalisation: ") + hipGetErrorString(e); return false; }
+  *p = (T*)q;
+  return true;
+}
+template <class T> static void rl_free(T** p) { if (*p) (void)guard_free(*p); *p = nullptr; }
+static void rl_free_scratch(RlCtx* R) {
+  rl_free(&R->bound); rl_free(&R->res2); rl_free(&R->resA); rl_free(&R->list2); rl_free(&R->cnt2); rl_free(&R->listA); rl_free(&R->cntA); rl_free(&R->qsel); rl_free(&R->cand);
+  R->pairs_cap = R->q_cap = 0;
+}
+void reloc_ctx_destroy(RlCtx* R) {
+  if (!R) return;
+  rl_free_scratch(R);
+  rl_free(&R->mdesc); rl_free(&R->qdesc); rl_free(&R->mkey); rl_free(&R->qkey); rl_free(&R->list); rl_free(&R->apply); rl_free(&R->state); rl_free(&R->klist);
+  delete R;
+}
+void reloc_ctx_set(RlCtx** pr, int what, long long v) {   // what 0: pairs per chunk of the search, 1: brute force
+  if (!*pr) *pr = new RlCtx();
+  if (what == 0) (*pr)->budget = std::max(1LL, v); else (*pr)->brute = v != 0;
+}
+bool reloc_enabled(const RlCtx* R) { return R && R->n_slots > 0; }
+
+int reloc_enable(RlCtx** pr, const LmCtx& L, int n_slots, double max_range, double z_offset, hipStream_t st, std::string* err) {
+  if (!*pr) *pr = new RlCtx();
+  RlCtx* R = *pr;
+  const int N = L.loc_n;
+  R->w = rl_ring_width(max_range); R->zoff = rl_z_offset(z_offset);
+  auto undo = [&](int rc) { rl_free(&R->mdesc); rl_free(&R->qdesc); rl_free(&R->mkey); rl_free(&R->qkey); rl_free(&R->list); rl_free(&R->apply); rl_free(&R->state); rl_free(&R->klist); return rc; };   // (the handle stays what it was)
+  if (!rl_alloc(&R->mdesc, (size_t)N * RL_WORDS, err) || !rl_alloc(&R->mkey, (size_t)N * RL_NR, err) || !rl_alloc(&R->qdesc, (size_t)n_slots * RL_WORDS, err) ||
+      !rl_alloc(&R->qkey, (size_t)n_slots * RL_NR, err) || !rl_alloc(&R->list, (size_t)n_slots, err) || !rl_alloc(&R->apply, (size_t)n_slots, err) ||
+      !rl_alloc(&R->state, (size_t)n_slots, err) || !rl_alloc(&R->klist, (size_t)n_slots * RL_NR, err)) return undo(ALEGO_ERR_HIP);
+  hipError_t e = hipMemsetAsync(R->qdesc, 0, std::max<size_t>(16, (size_t)n_slots * RL_BYTES), st);
+  if (e == hipSuccess) e = hipMemsetAsync(R->qkey, 0, std::max<size_t>(16, (size_t)n_slots * RL_NR * 2), st);
+  if (e == hipSuccess && N > 0) ALEGO_LAUNCH(rl_desc, dim3(N), dim3(RL_T), 0, st, L, 0, (const int*)nullptr, R->w, R->zoff, R->mdesc, R->mkey, (RlSlot*)nullptr, (uint16_t*)nullptr);
+  std::vector<int> cnt((size_t)N * KF_CNT_W);
+  std::vector<float> pose((size_t)N * KF_POSE_W);
+  if (e == hipSuccess && N > 0) e = hipMemcpyAsync(cnt.data(), kf_cnt_of(L, kf_row_at(L, 0, 0)), cnt.size() * sizeof(int), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && N > 0) e = hipMemcpyAsync(pose.data(), kf_pose_of(L, kf_row_at(L, 0, 0)), pose.size() * sizeof(float), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) { *err = std::string("alego_reloc_enable: ") + hipGetErrorString(e); return undo(ALEGO_ERR_HIP); }
+  R->cnt.resize(N); R->pose.resize((size_t)N * 6);
+  for (int i = 0; i < N; ++i) {
+    R->cnt[i] = rl_frame_points(cnt.data() + (size_t)i * KF_CNT_W, L.kf_cap_c, L.kf_cap_s, L.kf_cap_o);
+    for (int k = 0; k < 6; ++k) R->pose[(size_t)i * 6 + k] = pose[(size_t)i * KF_POSE_W + k];
+  }
+  R->N = N; R->n_slots = n_slots;
+  return 0;
+}
+
+// The exact search of nq queries (rows sel[q] of qdesc / qkey) over N frames: cand[q][r] = D << 32 | id << 8 | s, ~0 where N < n_cand.
+// Queries are taken in chunks of at most budget / N; a query's result does not depend on its chunk.
+static int rl_search_run(RlCtx* R, const uint32_t* qdesc, const uint16_t* qkey, const int* sel, int nq, const uint32_t* mdesc, const uint16_t* mkey, int N, int n_cand,
+                         unsigned long long* cand, hipStream_t st, std::string* err) {
+  for (size_t i = 0; i < (size_t)nq * ALEGO_RELOC_MAX_CAND; ++i) cand[i] = ~0ull;
+  R->stats[0] = 0; R->stats[1] = (int)std::min<long long>((long long)nq * N, 0x7fffffff);
+  if (nq == 0 || N == 0) return 0;
+  std::vector<int> cnt2;
+  const int QC = (int)std::max<long long>(1, std::min<long long>(nq, R->budget / N));
+  if (R->pairs_cap < (size_t)QC * N || R->q_cap < (size_t)QC) {
+    const size_t pc = std::max(R->pairs_cap, (size_t)QC * N), qc = std::max(R->q_cap, (size_t)QC);
+    if (hipStreamSynchronize(st) != hipSuccess) { *err = "relocalisation: a stream failed"; return ALEGO_ERR_HIP; }
+    rl_free_scratch(R);
+    if (!rl_alloc(&R->bound, pc, err) || !rl_alloc(&R->res2, pc, err) || !rl_alloc(&R->list2, pc, err) || !rl_alloc(&R->resA, qc * ALEGO_RELOC_MAX_CAND, err) ||
+        !rl_alloc(&R->listA, qc * ALEGO_RELOC_MAX_CAND, err) || !rl_alloc(&R->cntA, qc, err) || !rl_alloc(&R->cnt2, qc, err) || !rl_alloc(&R->qsel, qc, err) ||
+        !rl_alloc(&R->cand, qc * ALEGO_RELOC_MAX_CAND, err)) { rl_free_scratch(R); return ALEGO_ERR_HIP; }
+    R->pairs_cap = pc; R->q_cap = qc;
+  }
+  const int nblk = std::max(1, std::min(RL_SEARCH_BLOCKS, (N + RL_WAVES - 1) / RL_WAVES));
+  for (int q0 = 0; q0 < nq; q0 += QC) {
+    const int c = std::min(QC, nq - q0);
+    if (hipMemcpyAsync(R->qsel, sel + q0, (size_t)c * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess) { *err = "relocalisation: upload failed"; return ALEGO_ERR_HIP; }
+    ALEGO_LAUNCH(rl_bound, dim3((N + RL_T - 1) / RL_T, c), dim3(RL_T), 0, st, R->qsel, qkey, mkey, N, R->bound);
+    ALEGO_LAUNCH(rl_pick, dim3(c), dim3(RL_T), 0, st, R->bound, N, n_cand, R->listA, R->cntA);
+    ALEGO_LAUNCH(rl_search, dim3(1, c), dim3(RL_T), 0, st, R->qsel, qdesc, mdesc, R->listA, R->cntA, ALEGO_RELOC_MAX_CAND, R->resA);
+    ALEGO_LAUNCH(rl_list2, dim3(c), dim3(RL_T), 0, st, R->bound, N, R->resA, R->cntA, R->brute, R->list2, R->cnt2);
+    ALEGO_LAUNCH(rl_search, dim3(nblk, c), dim3(RL_T), 0, st, R->qsel, qdesc, mdesc, R->list2, R->cnt2, N, R->res2);
+    ALEGO_LAUNCH(rl_topk, dim3(c), dim3(RL_T), 0, st, R->list2, R->cnt2, R->res2, N, n_cand, R->cand);
+    // (the next chunk reuses the scratch: copies and kernels are ordered on `st`; cand is pageable, so the copy below has left the device when it returns)
+    cnt2.resize((size_t)c);
+    if (hipMemcpyAsync(cand + (size_t)q0 * ALEGO_RELOC_MAX_CAND, R->cand, (size_t)c * ALEGO_RELOC_MAX_CAND * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(cnt2.data(), R->cnt2, (size_t)c * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess) { *err = "relocalisation: the search failed"; return ALEGO_ERR_HIP; }
+    for (int v : cnt2) R->stats[0] = (int)std::min<long long>((long long)R->stats[0] + v, 0x7fffffff);
+  }
+  return 0;
+}
+
+void reloc_debug_stats(const RlCtx* R, int out[2]) { out[0] = R ? R->stats[0] : 0; out[1] = R ? R->stats[1] : 0; }
+
+int reloc_debug_search(RlCtx** pr, const uint8_t* map_desc, int n_map, const uint8_t* q_desc, int n_q, int n_cand, int32_t* ids, int32_t* dists, int32_t* shifts,
+                       hipStream_t st, std::string* err) {
+  if (!*pr) *pr = new RlCtx();
+  RlCtx* R = *pr;
+  uint32_t *md = nullptr, *qd = nullptr;
+  uint16_t *mk = nullptr, *qk = nullptr;
+  struct Free { uint32_t **a, **b; uint16_t **c, **d; ~Free() { rl_free(a); rl_free(b); rl_free(c); rl_free(d); } } fr{&md, &qd, &mk, &qk};
+  if (!rl_alloc(&md, (size_t)n_map * RL_WORDS, err) || !rl_alloc(&qd, (size_t)n_q * RL_WORDS, err) || !rl_alloc(&mk, (size_t)n_map * RL_NR, err) || !rl_alloc(&qk, (size_t)n_q * RL_NR, err))
+    return ALEGO_ERR_HIP;
+  hipError_t e = n_map ? hipMemcpyAsync(md, map_desc, (size_t)n_map * RL_BYTES, hipMemcpyHostToDevice, st) : hipSuccess;
+  if (e == hipSuccess && n_q) e = hipMemcpyAsync(qd, q_desc, (size_t)n_q * RL_BYTES, hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) { *err = "debug_reloc_search: upload failed"; return ALEGO_ERR_HIP; }
+  if (n_map) ALEGO_LAUNCH(rl_keys, dim3(n_map), dim3(64), 0, st, md, mk);
+  if (n_q) ALEGO_LAUNCH(rl_keys, dim3(n_q), dim3(64), 0, st, qd, qk);
+  std::vector<int> sel((size_t)n_q);
+  for (int q = 0; q < n_q; ++q) sel[q] = q;
+  std::vector<unsigned long long> cand((size_t)n_q * ALEGO_RELOC_MAX_CAND);
+  int rc = rl_search_run(R, qd, qk, sel.data(), n_q, md, mk, n_map, n_cand, cand.data(), st, err);
+  if (hipStreamSynchronize(st) != hipSuccess && !rc) { *err = "debug_reloc_search: kernels failed"; rc = ALEGO_ERR_HIP; }
+  if (rc) return rc;
+  for (int q = 0; q < n_q; ++q)
+    for (int r = 0; r < n_cand; ++r) {
+      const unsigned long long c = cand[(size_t)q * ALEGO_RELOC_MAX_CAND + r];
+      const size_t o = (size_t)q * n_cand + r;
+      if (c == ~0ull) { ids[o] = -1; dists[o] = -1; shifts[o] = -1; }
+      else { ids[o] = (int32_t)((c >> 8) & 0xffffffu); dists[o] = (int32_t)(c >> 32); shifts[o] = (int32_t)(c & 0xffu); }
+    }
+  return 0;
+}
+
+int reloc_debug_get(RlCtx* R, int slot, const char* name, const void** src, size_t* bytes) {
+  if (!reloc_enabled(R)) return ALEGO_ERR_ARG;
+  const std::string s(name);
+  if (s == "rl_query_desc") { *src = R->qdesc + (size_t)slot * RL_WORDS; *bytes = RL_BYTES; }
+  else if (s == "rl_query_key") { *src = R->qkey + (size_t)slot * RL_NR; *bytes = RL_NR * 2; }
+  else if (s == "rl_map_desc") { *src = R->mdesc; *bytes = (size_t)R->N * RL_BYTES; }
+  else if (s == "rl_map_key") { *src = R->mkey; *bytes = (size_t)R->N * RL_NR * 2; }
+  else return ALEGO_ERR_ARG;
+  return 0;
+}
+
+// f64 arithmetic of `apply` (include/alego_mi355x.h): rc = t_map * T_cur^-1, params6 = translation and Euler angles of t_map
+static void rl_placement(const float* t_map, const double* t_cur, const double* q_cur /* w x y z */, double* rc, double* params6) {
+  const double w = q_cur[0], x = q_cur[1], y = q_cur[2], z = q_cur[3];
+  const double tx = 2 * x, ty = 2 * y, tz = 2 * z, twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y, tyz = tz * y, tzz = tz * z;
+  const double Rc[9] = {1 - (tyy + tzz), txy - twz, txz + twy, txy + twz, 1 - (txx + tzz), tyz - twx, txz - twy, tyz + twx, 1 - (txx + tyy)};   // dq_to_mat
+  double Rm[9], tm[3];
+  for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) Rm[r * 3 + c] = (double)t_map[r * 4 + c]; tm[r] = (double)t_map[r * 4 + 3]; }
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) rc[r * 4 + c] = Rm[r * 3 + 0] * Rc[c * 3 + 0] + Rm[r * 3 + 1] * Rc[c * 3 + 1] + Rm[r * 3 + 2] * Rc[c * 3 + 2];   // R_map R_cur^T
+  }
+  for (int r = 0; r < 3; ++r) rc[r * 4 + 3] = tm[r] - (rc[r * 4 + 0] * t_cur[0] + rc[r * 4 + 1] * t_cur[1] + rc[r * 4 + 2] * t_cur[2]);
+  params6[0] = tm[0]; params6[1] = tm[1]; params6[2] = tm[2];
+  params6[3] = std::atan2(Rm[7], Rm[8]);
+  params6[4] = std::atan2(-Rm[6], std::sqrt(Rm[7] * Rm[7] + Rm[8] * Rm[8]));
+  params6[5] = std::atan2(Rm[3], Rm[0]);
+}
+
+int reloc_run(RlCtx* R, LcCtx** lc, const LmCtx& L, const alego_params& P, const int* slots, int n, int n_cand, int verify, int apply, alego_reloc_result* out,
+              hipStream_t st, std::string* err) {
+  const int N = R->N;
+  for (int i = 0; i < n; ++i) { std::memset(&out[i], 0, sizeof(out[i])); out[i].verified = -1; }
+  if (n == 0) return 0;
+  // the listed slots' descriptors, and of their state what the host needs (the caller has drained every stream): O(n), whatever the handle's size
+  std::vector<RlSlot> state((size_t)n);
+  std::vector<uint16_t> qkey((size_t)n * RL_NR);
+  if (hipMemcpyAsync(R->list, slots, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess) { *err = "alego_loc_relocalize: upload failed"; return ALEGO_ERR_HIP; }
+  ALEGO_LAUNCH(rl_desc, dim3(n), dim3(RL_T), 0, st, L, 1, (const int*)R->list, R->w, R->zoff, R->qdesc, R->qkey, R->state, R->klist);
+  hipError_t e = hipMemcpyAsync(state.data(), R->state, state.size() * sizeof(RlSlot), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(qkey.data(), R->klist, qkey.size() * sizeof(uint16_t), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) { *err = std::string("alego_loc_relocalize: descriptors failed: ") + hipGetErrorString(e); return ALEGO_ERR_HIP; }
+  // searchable: a mapping frame has run and a point lies in range (every code is >= 1, so an all-zero key is an empty descriptor)
+  std::vector<int> qi, sel;
+  for (int i = 0; i < n; ++i) {
+    int any = 0;
+    for (int r = 0; r < RL_NR; ++r) any |= qkey[(size_t)i * RL_NR + r];
+    if (state[i].frame > 0 && any && N > 0) { qi.push_back(i); sel.push_back(slots[i]); }
+  }
+  std::vector<unsigned long long> cand(qi.size() * ALEGO_RELOC_MAX_CAND + 1);
+  if (int rc = rl_search_run(R, R->qdesc, R->qkey, sel.data(), (int)qi.size(), R->mdesc, R->mkey, N, n_cand, cand.data(), st, err)) return rc;
+  for (size_t a = 0; a < qi.size(); ++a) {
+    alego_reloc_result& r = out[qi[a]];
+    for (int k = 0; k < n_cand; ++k) {
+      const unsigned long long c = cand[a * ALEGO_RELOC_MAX_CAND + k];
+      if (c == ~0ull) break;
+      r.cand_id[k] = (int32_t)((c >> 8) & 0xffffffu); r.cand_dist[k] = (int32_t)(c >> 32); r.cand_shift[k] = (int32_t)(c & 0xffu);
+      r.n_cand = k + 1;
+    }
+    r.status = r.n_cand > 0 ? 1 : 0;
+  }
+  // verification: round v tries candidate v of every slot that has one and is not accepted yet
+  std::vector<LcDet> det((size_t)n);
+  std::vector<LcOut> res((size_t)n);
+  for (int v = 0; v < verify; ++v) {
+    bool any = false;
+    for (int i = 0; i < n; ++i) {
+      LcDet& D = det[i];
+      std::memset(&D, 0, sizeof(D));
+      alego_reloc_result& r = out[i];
+      if (r.status != 1 || r.n_cand <= v) continue;
+      any = true;
+      const int f = r.cand_id[v];
+      D.status = 1; D.latest = -1; D.closest = f;
+      D.jlo = std::max(0, f - P.lc_search_num); D.jhi = std::min(N - 1, f + P.lc_search_num);
+      for (int k = 0; k < 6; ++k) D.pose_latest[k] = D.pose_closest[k] = R->pose[(size_t)f * 6 + k];
+      D.pose_latest[5] = rl_guess_yaw(D.pose_latest[5], r.cand_shift[v]);
+      D.n_src = state[i].n[KF_CORNER] + state[i].n[KF_SURF] + state[i].n[KF_OUTL];
+      for (int j = D.jlo; j <= D.jhi; ++j) D.n_raw += R->cnt[j];
+    }
+    if (!any) break;
+    if (int rc = loop_attempts(lc, P, R->n_slots, slots, det.data(), n, [&](const LcJob* jobs, const LcDet* dd, int J, int nfr, float4* src, float4* raw, hipStream_t s2) {
+          ALEGO_LAUNCH(rl_gather, dim3(nfr, J), dim3(RL_T), 0, s2, L, jobs, dd, src, raw);
+        }, res.data(), st, err)) return rc;
+    for (int i = 0; i < n; ++i) {
+      if (det[i].status != 1) continue;
+      alego_reloc_result& r = out[i];
+      const LcOut& O = res[i];
+      r.converged = O.converged; r.iterations = O.iterations; r.n_source = O.n_source; r.n_target = O.n_target; r.fitness = O.fitness;
+      for (int k = 0; k < 16; ++k) r.correction[k] = O.correction[k];
+      for (int k = 0; k < 6; ++k) r.guess6[k] = det[i].pose_latest[k];
+      double between[12];
+      alego_loop_constraint(r.correction, r.guess6, r.guess6, r.t_map, between);   // t_map = correction * matrix(guess6), as t_correct (:714-715)
+      if (O.converged && O.fitness <= P.lc_fitness_max) {   // :697
+        r.status = 2; r.verified = v;
+        rl_placement(r.t_map, state[i].t_m2l, state[i].q_m2l, r.rc, r.params6);
+      }
+    }
+  }
+  if (apply) {
+    std::vector<RlApply> ap;
+    for (int i = 0; i < n; ++i)
+      if (out[i].status == 2) {
+        RlApply a;
+        a.slot = slots[i]; a.pad = 0;
+        std::memcpy(a.rc, out[i].rc, sizeof(a.rc)); std::memcpy(a.params6, out[i].params6, sizeof(a.params6));
+        ap.push_back(a);
+        out[i].applied = 1;
+      }
+    if (!ap.empty()) {
+      if (hipMemcpyAsync(R->apply, ap.data(), ap.size() * sizeof(RlApply), hipMemcpyHostToDevice, st) != hipSuccess) { *err = "alego_loc_relocalize: upload failed"; return ALEGO_ERR_HIP; }
+      ALEGO_LAUNCH(rl_apply, dim3(((int)ap.size() + 63) / 64), dim3(64), 0, st, L, (const RlApply*)R->apply, (int)ap.size());
+      if (hipStreamSynchronize(st) != hipSuccess) { *err = "alego_loc_relocalize: apply failed"; return ALEGO_ERR_HIP; }
+    }
+  }
+  return 0;
+}
+
+// ---- host twins (plain C++) -----------------------------------------------------------------------------------------------------------
+extern "C" int alego_reloc_descriptor(const alego_point* pts, int32_t n, double max_range, double z_offset, uint8_t* desc1200, uint16_t* key20) {
+  if (n < 0 || (n > 0 && !pts) || !desc1200 || !key20) return ALEGO_ERR_ARG;
+  const float w = rl_ring_width(max_range), zoff = rl_z_offset(z_offset);
+  std::memset(desc1200, 0, RL_BYTES);
+  for (int i = 0; i < n; ++i) {
+    int bin, code;
+    if (rl_bin(pts[i].x, pts[i].y, pts[i].z, w, zoff, &bin, &code) && code > desc1200[bin]) desc1200[bin] = (uint8_t)code;
+  }
+  for (int r = 0; r < RL_NR; ++r) {
+    int s = 0;
+    for (int c = 0; c < RL_NS; ++c) s += desc1200[c * RL_NR + r];
+    key20[r] = (uint16_t)s;
+  }
+  return ALEGO_OK;
+}
+extern "C" int alego_reloc_match(const uint8_t* q1200, const uint8_t* m1200, int32_t* dist, int32_t* shift) {
+  if (!q1200 || !m1200 || !dist || !shift) return ALEGO_ERR_ARG;
+  int best = 0x7fffffff, bs = 0;
+  for (int s = 0; s < RL_NS; ++s) {
+    int d = 0;
+    for (int c = 0; c < RL_NS; ++c) {
+      const uint8_t* a = q1200 + ((c + s) % RL_NS) * RL_NR;
+      const uint8_t* b = m1200 + c * RL_NR;
+      for (int r = 0; r < RL_NR; ++r) d += rl_abs_diff(a[r], b[r]);
+    }
+    if (d < best) { best = d; bs = s; }
+  }
+  *dist = best; *shift = bs;
+  return ALEGO_OK;
+}

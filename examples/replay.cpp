@@ -27,6 +27,11 @@
 //       alego_map_get_keyframe, a SECOND handle is opened, alego_loc_enable hands it those frames, and the same scans are replayed through
 //       it.  It never saves a key frame; every mapping frame registers against the map frames nearest to its pose.  The JSON line gains
 //       "loc_map_t" (its final map pose) and "loc_max_dev" (the largest per-axis distance between the two runs' map poses).
+//   --localize + --relocalize [--reloc-start K] [--reloc-range R]
+//       the localising handle's stream starts UNPLACED at scan K of the source (default: half way) — nothing tells the handle where it is.
+//       alego_reloc_enable builds the map's descriptors (R = max_range, default the library's); after the stream's first mapping frame
+//       alego_loc_relocalize with apply = 1 finds the place, verifies it by ICP and places the slot on the device.  The result is printed
+//       as one line "reloc: {...}"; loc_max_dev then covers the scans after the placement, and the JSON line gains "reloc_status".
 // Every scan goes through ImageProjection -> LaserOdometry -> LaserMapping with one alego_scan_process call, as a single nodelet
 // manager would run them (launch/test.launch:6-10); every new key frame is pulled across the boundary the way the reference's
 // pose-graph thread reads cloud_keyposes_6d_ (laserMapping.cpp:586-596); one JSON line with the final poses is printed.
@@ -48,8 +53,9 @@ int main(int argc, char** argv) {
   std::string bag_path, topic = "/lslidar_point_cloud", map_dir;
   float map_leaf = 0.f;
   int map_frames = 4096, map_points = 1 << 24, loop_every = 0, close_every = 0, max_loops = 16;
-  bool list_only = false, standalone = false, localize = false;
-  double loc_radius = 0.0;
+  bool list_only = false, standalone = false, localize = false, relocalize = false;
+  double loc_radius = 0.0, reloc_range = 0.0;
+  long reloc_start = -1;
   long max_scans = -1;
   int n_scan = 16, horizon = -1;
   std::vector<const char*> pos;
@@ -72,6 +78,9 @@ int main(int argc, char** argv) {
     else if (a == "--max-loops") max_loops = std::atoi(val());
     else if (a == "--localize") localize = true;
     else if (a == "--loc-radius") loc_radius = std::atof(val());
+    else if (a == "--relocalize") relocalize = true;
+    else if (a == "--reloc-start") reloc_start = std::atol(val());
+    else if (a == "--reloc-range") reloc_range = std::atof(val());
     else pos.push_back(argv[i]);
   }
   alego_bag* bag = nullptr;
@@ -186,9 +195,12 @@ int main(int argc, char** argv) {
     alego_handle* hl = nullptr;
     if (alego_create(&P, 0, 1, 1, &hl)) { std::fprintf(stderr, "alego_create (localising handle) failed\n"); alego_destroy(h); return 1; }
     if (alego_loc_enable(hl, frames.data(), nf, loc_radius) != ALEGO_OK) { std::fprintf(stderr, "loc_enable: %s\n", alego_last_error(hl)); alego_destroy(hl); alego_destroy(h); return 1; }
+    if (relocalize && alego_reloc_enable(hl, reloc_range, 0.0 / 0.0) != ALEGO_OK) { std::fprintf(stderr, "reloc_enable: %s\n", alego_last_error(hl)); alego_destroy(hl); alego_destroy(h); return 1; }
+    if (reloc_start < 0) reloc_start = n_scans / 2;
+    int reloc_status = -1;   // -1: not asked for; 0: no verdict yet
     alego_pose lo{}, lm{};
     double max_dev = 0.0;
-    for (long k = 0; k < n_scans; ++k) {
+    for (long k = relocalize ? reloc_start : 0; k < n_scans; ++k) {
       int n;
       double stamp = 0.1 * k;
       if (bag) {
@@ -200,13 +212,35 @@ int main(int argc, char** argv) {
       alego_scan_in in{pts.data(), n, stamp};
       const int flags = alego_scan_process(hl, 0, &in, 7, nullptr, nullptr, &lo, &lm);
       if (flags < 0) { std::fprintf(stderr, "localise scan %ld: %s\n", k, alego_last_error(hl)); alego_destroy(hl); alego_destroy(h); return 1; }
+      if (relocalize && reloc_status <= 0) {   // unplaced: ask after every scan until the slot has had a mapping frame (status 0 before)
+        const int32_t slot = 0;
+        const alego_reloc_opts ro{0, -1, 1};   // the defaults (4 candidates, 1 verified) and apply
+        alego_reloc_result rr{};
+        if (alego_loc_relocalize(hl, &slot, 1, &ro, &rr) != ALEGO_OK) { std::fprintf(stderr, "relocalize: %s\n", alego_last_error(hl)); alego_destroy(hl); alego_destroy(h); return 1; }
+        reloc_status = rr.status;
+        if (rr.status > 0) {
+          std::printf("reloc: {\"scan\": %ld, \"status\": %d, \"applied\": %d, \"verified\": %d, \"cand_id\": [", k, rr.status, rr.applied, rr.verified);
+          for (int c = 0; c < rr.n_cand; ++c) std::printf("%s%d", c ? ", " : "", rr.cand_id[c]);
+          std::printf("], \"cand_dist\": [");
+          for (int c = 0; c < rr.n_cand; ++c) std::printf("%s%d", c ? ", " : "", rr.cand_dist[c]);
+          std::printf("], \"cand_shift\": [");
+          for (int c = 0; c < rr.n_cand; ++c) std::printf("%s%d", c ? ", " : "", rr.cand_shift[c]);
+          std::printf("], \"converged\": %d, \"iterations\": %d, \"fitness\": %.17g, \"t_map\": [", rr.converged, rr.iterations, rr.fitness);
+          for (int c = 0; c < 16; ++c) std::printf("%s%.9g", c ? ", " : "", rr.t_map[c]);
+          std::printf("], \"params6\": [");
+          for (int c = 0; c < 6; ++c) std::printf("%s%.17g", c ? ", " : "", rr.params6[c]);
+          std::printf("]}\n");
+        }
+        continue;   // (the deviation is measured from the first scan after the placement)
+      }
       for (int a = 0; a < 3; ++a) {
         const double dev = lm.t[a] - map_track[(size_t)k * 3 + a];
         if (!(std::fabs(dev) <= max_dev)) max_dev = std::fabs(dev);   // (a NaN sticks)
       }
     }
-    char buf[256];
-    std::snprintf(buf, sizeof(buf), ", \"loc_frames\": %d, \"loc_map_t\": [%.17g, %.17g, %.17g], \"loc_max_dev\": %.9g", nf, lm.t[0], lm.t[1], lm.t[2], max_dev);
+    char buf[320];
+    int len = std::snprintf(buf, sizeof(buf), ", \"loc_frames\": %d, \"loc_map_t\": [%.17g, %.17g, %.17g], \"loc_max_dev\": %.9g", nf, lm.t[0], lm.t[1], lm.t[2], max_dev);
+    if (relocalize) std::snprintf(buf + len, sizeof(buf) - len, ", \"reloc_status\": %d", reloc_status);
     loc_json = buf;
     alego_destroy(hl);
   }

@@ -500,6 +500,70 @@ int alego_loc_select(const float* keyposes6, int32_t n, const float xyz[3], doub
 int alego_loc_enable(alego_handle* h, const alego_kf_in* frames, int32_t n, double radius);
 int alego_loc_status(alego_handle* h, int slot, int32_t out[4]);
 
+/* ---- relocalisation: placing slots of a localising handle without an initial pose ------------------------
+ * Place recognition for many slots at once: a rotation-invariant descriptor of every map frame and of a slot's current scan, an EXACT
+ * search of the scan's descriptor over all N map frames, verification by the ICP of alego_loop_search.  The rule (csrc/reloc_math.h; the
+ * project's own, in the family of Scan Context), all f32 without contraction:
+ *   descriptor  60 sectors x 20 rings of one byte, D[sector][ring] (1200 B).  A point with a non-finite coordinate is skipped;
+ *               r = sqrtf((x x) + (y y)), w = (float)max_range / 20.0f, ring = floorf(r / w), skipped unless ring < 20;
+ *               sector = min(59, floorf((atan2f(y, x) + (float)pi) * (float)(60 / 2 pi))); code = min(255, max(1, floorf((z + z_offset) * 16.0f) + 1));
+ *               D[sector][ring] = the largest code of its points, 0 for an empty bin.  ring key: key[ring] = sum over sectors of D[sector][ring] (u16).
+ *               A map frame's descriptor is that of its corner, surf and outlier clouds; a slot's that of laser_corner_ds_, laser_surf_ds_ and
+ *               laser_outlier_ds_ of its last mapping frame (the clouds a key frame would have been saved from).
+ *   match       dist(Q, M, s) = sum over c, r of |Q[(c + s) mod 60][r] - M[c][r]|; D_i = min over s, s_i the smallest s attaining it; the
+ *               candidates are the n_cand frames smallest in the order (D_i, i) — exactly the brute force over all frames and shifts.
+ *   guess       guess6 = key pose of frame i with yaw - (float)s_i * (float)(2 pi / 60), f32.
+ *   verify      candidates in order, at most `verify` of them: source = the slot's three clouds as the frame (guess6, corner, surf, outlier);
+ *               target = map frames [i - lc_search_num, i + lc_search_num] within [0, N), each transformed by its pose (surf, corner, outlier)
+ *               and VoxelGrid(lc_leaf)-filtered; ICP and fitness exactly as alego_loop_search runs them.  Accepted when converged &&
+ *               fitness <= lc_fitness_max; the first accepted candidate ends the slot.  t_map = correction * matrix(guess6), as t_correct of
+ *               alego_loop_constraint.
+ *   apply       accepted slots with apply = 1: rc = t_map * T_cur^-1 in f64 (T_cur = the slot's t_map2laser_ of its last mapping frame,
+ *               R_rc = R_map R_cur^T, c = t_map - R_rc t_cur), params6 = (translation of t_map, roll = atan2(R21, R22), pitch = atan2(-R20,
+ *               sqrt(R21^2 + R22^2)), yaw = atan2(R10, R00) of its rotation); map -> odom and params_ are set as alego_lm_apply_correction(rc)
+ *               and alego_set_lm_params(params6) set them.  The window is left alone: the next mapping frame selects at the new pose.
+ * alego_reloc_enable     once, after alego_loc_enable (else ALEGO_ERR_ARG; a second call too): builds the N map descriptors and ring keys on the
+ *                        device.  max_range <= 0: 80.0; z_offset not finite: 4.0.  Device memory: 1240 B per map frame and per slot; search and
+ *                        ICP scratch grows on first use and stays with the handle.  Without the call nothing is allocated or launched.
+ * alego_loc_relocalize   synchronous; runs behind the work queued on every stream group.  out[i] belongs to slots[i]; a slot's result does not
+ *                        depend on the other slots, their order or the chunking.  ALEGO_ERR_ARG: not enabled, a slot out of range or listed
+ *                        twice, n_cand > ALEGO_RELOC_MAX_CAND, verify > n_cand.  opts == NULL: n_cand 4, verify 1, apply 0; n_cand <= 0: 4;
+ *                        verify < 0: 1; verify == 0: search only.
+ * alego_reloc_descriptor / alego_reloc_match   host only, plain C++: the rule on one cloud / one pair of descriptors.
+ * alego_debug_reloc_search   the search kernels alone on descriptors the caller supplies (tests): ids / dists / shifts [n_q][n_cand], -1 where
+ *                        n_map < n_cand.  alego_debug_set_option("ALEGO_RL_BRUTE", 1) evaluates every (query, frame) pair instead of pruning
+ *                        with the ring-key bound; "ALEGO_RL_BUDGET" sets the (query, frame) pairs per chunk of the search.  These three debug
+ *                        entries work on any handle and are the one exception to "nothing is allocated without alego_reloc_enable": the
+ *                        first of them creates the search context (and, for the search, its scratch), which the handle then keeps;
+ *                        alego_debug_get("rl_stats") (pairs the second round evaluated, pairs in all, of the last search) answers there too.
+ * alego_debug_get names: "rl_query_desc" (the slot's 1200 bytes), "rl_query_key" (40 bytes: 20 u16), "rl_map_desc", "rl_map_key" (all N frames). */
+#define ALEGO_RELOC_MAX_CAND 8
+typedef struct alego_reloc_opts {
+  int32_t n_cand;          /* 1 .. ALEGO_RELOC_MAX_CAND */
+  int32_t verify;          /* candidates verified at most, 0 .. n_cand */
+  int32_t apply;           /* 1: place every accepted slot on the device */
+} alego_reloc_opts;
+typedef struct alego_reloc_result {
+  int32_t status;          /* 2 accepted; 1 candidates but none accepted (or verify == 0); 0 no mapping frame yet, no point in range or an empty map */
+  int32_t n_cand;
+  int32_t cand_id[ALEGO_RELOC_MAX_CAND], cand_dist[ALEGO_RELOC_MAX_CAND], cand_shift[ALEGO_RELOC_MAX_CAND];
+  int32_t verified;        /* index into the candidates of the accepted one, or -1 */
+  int32_t converged, iterations, n_source, n_target;   /* of the last candidate verified */
+  int32_t applied;
+  double fitness;
+  float correction[16];    /* getFinalTransformation(), row-major */
+  float guess6[6];         /* the ICP's initial guess (the last candidate verified) */
+  float t_map[16];         /* correction * matrix(guess6): the sensor pose in the map */
+  double rc[12];           /* row-major 3x4 for alego_lm_apply_correction (accepted slots) */
+  double params6[6];       /* for alego_set_lm_params (accepted slots) */
+} alego_reloc_result;
+int alego_reloc_enable(alego_handle* h, double max_range, double z_offset);
+int alego_loc_relocalize(alego_handle* h, const int32_t* slots, int32_t n, const alego_reloc_opts* opts, alego_reloc_result* out);
+int alego_reloc_descriptor(const alego_point* pts, int32_t n, double max_range, double z_offset, uint8_t* desc1200, uint16_t* key20);
+int alego_reloc_match(const uint8_t* q1200, const uint8_t* m1200, int32_t* dist, int32_t* shift);
+int alego_debug_reloc_search(alego_handle* h, const uint8_t* map_desc, int32_t n_map, const uint8_t* q_desc, int32_t n_q, int32_t n_cand,
+                             int32_t* ids, int32_t* dists, int32_t* shifts);
+
 /* ---- one scan-to-map registration sharded over the GPUs of a node (BASELINE.json config 5) ----------------
  * One process per GPU; every rank feeds its handle the SAME scans and so keeps a bit-identical replica of the stream's state
  * (ImageProjection, feature extraction, LaserOdometry and the local map are cheap and are computed redundantly).  What is split
