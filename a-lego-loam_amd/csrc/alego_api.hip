@@ -14,10 +14,14 @@
 
 #include "../../include/alego_mi355x.h"
 #include "dev_common.h"
-#include "guard_alloc.h"
+#include "dev_mem.h"
+#include "front_end.h"
+#include "lm_ctx.h"
 #include "lm_host.h"
+#include "loop_ctx.h"
 #include "pgraph.h"
 #include "prof.h"
+#include "reloc.h"
 #include "voxel.h"
 
 thread_local Profiler* g_prof = nullptr;
@@ -25,40 +29,6 @@ thread_local Profiler* g_prof = nullptr;
 // A handle of several stream groups drives two HIP streams per group (front end + LaserMapping); the HIP runtime maps them onto the
 // process's hardware queues, so streams may share a queue and serialise.  How many queues a process opens is the host's setting
 // (include/alego_mi355x.h) — the library does not touch the environment.
-
-void launch_ip(const DevCtx& d, int ring_pos, bool want_labels, hipStream_t st);
-void launch_fe(const DevCtx& d, hipStream_t st);
-void launch_lo(const DevCtx& d, hipStream_t st);
-void launch_lo_grid(const DevCtx& d, hipStream_t st);
-void launch_atan2f_probe(const float* y, const float* x, float* out, int n, int mode, hipStream_t st);
-int launch_stdsort_probe(const uint32_t* keys, int n, int depth_limit, int* pos_out, hipStream_t st);
-void launch_lo_imu_push(const DevCtx& d, int slot, const double* smp_dev, int n, hipStream_t st);
-void launch_lo_deskew(const DevCtx& d, hipStream_t st);
-void launch_traj_log(const DevCtx& d, hipStream_t st, const double* staged_odom = nullptr, int par = 0);
-const double* lm_host_stage_odom(LmHost* lm);
-void launch_dbg_eval_blocks(int type, int n, const double* geom13, const double* params6, double* res, double* jac6, hipStream_t st);
-int icp_run(const alego_params& P, const alego_kf_in* latest, const alego_kf_in* history, int n_history, alego_icp_result* out,
-            alego_point* target_out, int target_cap, hipStream_t st, std::string* err);
-struct LcCtx;   // kernels_loop.hip: the batched loop-closure search
-int loop_search(LcCtx** pc, const LmCtx& L, const alego_params& P, int n_slots, const int* slots, int n, alego_loop_result* res, hipStream_t st, std::string* err);
-void loop_ctx_destroy(LcCtx* C);
-void loop_ctx_set_budget(LcCtx** pc, long long points);
-int loop_debug_nn1(const alego_point* tgt, int n_tgt, const alego_point* q, int nq, int32_t* idx, float* d2, hipStream_t st, std::string* err);
-struct RlCtx;   // kernels_reloc.hip: relocalisation in the frozen map
-int reloc_enable(RlCtx** pr, const LmCtx& L, int n_slots, double max_range, double z_offset, hipStream_t st, std::string* err);
-bool reloc_enabled(const RlCtx* R);
-int reloc_run(RlCtx* R, LcCtx** lc, const LmCtx& L, const alego_params& P, const int* slots, int n, int n_cand, int verify, int apply, alego_reloc_result* out,
-              hipStream_t st, std::string* err);
-int reloc_debug_search(RlCtx** pr, const uint8_t* map_desc, int n_map, const uint8_t* q_desc, int n_q, int n_cand, int32_t* ids, int32_t* dists, int32_t* shifts,
-                       hipStream_t st, std::string* err);
-int reloc_debug_get(RlCtx* R, int slot, const char* name, const void** src, size_t* bytes);
-void reloc_debug_stats(const RlCtx* R, int out[2]);
-void reloc_ctx_set(RlCtx** pr, int what, long long v);
-void reloc_ctx_destroy(RlCtx* R);
-void launch_dbg_transform_to_start(const double* params6, const float4* pts, int n, float4* out, hipStream_t st);
-int ip_configure(const DevCtx& d);
-int lo_configure();
-int lm_configure();
 
 struct alego_handle {
   std::recursive_mutex host_lock;   // alego_handle_lock / alego_handle_unlock: for hosts that drive ONE handle from several threads (the three nodelets)
@@ -77,7 +47,7 @@ struct alego_handle {
   std::vector<hipEvent_t> ev_stage, ev_back;   // [group][2]
   std::vector<long> grp_scans;                  // scans handed over per group
   DevCtx d;
-  std::vector<void*> allocs;
+  DevPool mem;                 // every device block the handle itself owns
   std::string err;
   std::vector<long> lo_scans;  // LO steps enqueued per slot (the first one only initialises, laserOdometry.cpp:316-324)
   LmHost* lm = nullptr;
@@ -114,14 +84,8 @@ namespace {
 
 template <class T>
 int dalloc(alego_handle* h, T** p, size_t count, bool zero = true) {
-  void* q = nullptr;
-  size_t bytes = count * sizeof(T);
-  if (bytes == 0) bytes = sizeof(T);
-  hipError_t e = guard_malloc(&q, bytes);
-  if (e != hipSuccess) { h->err = std::string("hipMalloc: ") + hipGetErrorString(e); return ALEGO_ERR_HIP; }
-  h->allocs.push_back(q);
-  if (zero) { e = hipMemset(q, 0, bytes); if (e != hipSuccess) { h->err = "hipMemset failed"; return ALEGO_ERR_HIP; } }
-  *p = (T*)q;
+  const hipError_t e = h->mem.get(p, count, zero);
+  if (e != hipSuccess) { h->err = std::string("device allocation: ") + hipGetErrorString(e); return ALEGO_ERR_HIP; }
   return 0;
 }
 
@@ -140,13 +104,6 @@ hipError_t sync_all(const alego_handle* h) {
   for (hipStream_t s : {h->s_lo, h->s_lm}) if (s) { hipError_t e = hipStreamSynchronize(s); if (e != hipSuccess) r = e; }
   return r;
 }
-
-// frees temporary device buffers on every exit path of the debug entries
-struct DevTemps {
-  std::vector<void*> p;
-  template <class T> hipError_t get(T** q, size_t bytes) { void* v = nullptr; hipError_t e = hipMalloc(&v, bytes ? bytes : 16); if (e == hipSuccess) p.push_back(v); *q = (T*)v; return e; }
-  ~DevTemps() { for (void* v : p) (void)hipFree(v); }
-};
 
 int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 
@@ -400,7 +357,7 @@ void alego_destroy(alego_handle* h) {
   loop_ctx_destroy(h->lc);
   reloc_ctx_destroy(h->rl);
   graph_ctx_destroy(h->pg);
-  for (void* p : h->allocs) (void)guard_free(p);
+  h->mem.clear();
   for (hipStream_t s : h->streams) hipStreamDestroy(s);
   for (hipStream_t s : h->back) hipStreamDestroy(s);
   for (hipEvent_t e : h->ev_stage) (void)hipEventDestroy(e);
@@ -893,9 +850,9 @@ int alego_lo_push_imu(alego_handle* h, int slot, const alego_imu* smp, int32_t n
     o[0] = m.stamp; o[1] = roll; o[2] = pitch; o[3] = yaw;
     for (int k = 0; k < 3; ++k) o[4 + k] = (double)(R[k][0] * a[0] + (R[k][1] * a[1] + R[k][2] * a[2]));
   }
-  DevTemps T;
+  DevPool T;   // temporaries of this call
   double* dp;
-  HIP_TRY(h, T.get(&dp, pre.size() * 8));
+  HIP_TRY(h, T.get(&dp, pre.size(), false));
   hipStream_t S = stream_of(h, slot);
   HIP_TRY(h, hipMemcpyAsync(dp, pre.data(), pre.size() * 8, hipMemcpyHostToDevice, S));
   launch_lo_imu_push(h->d, slot, dp, n, S);
@@ -937,11 +894,11 @@ int alego_debug_voxel(alego_handle* h, const alego_point* pts, int n, float leaf
   if (!h || n < 0 || (n > 0 && !pts)) return ALEGO_ERR_ARG;
   hipSetDevice(h->device);
   g_prof = &h->prof;
-  DevTemps T;
+  DevPool T;   // temporaries of this call
   float4 *din = nullptr, *dout = nullptr;
   int* cnt = nullptr;
   const int c = n > 0 ? n : 1;
-  HIP_TRY(h, T.get(&din, (size_t)c * 16)); HIP_TRY(h, T.get(&dout, (size_t)c * 16)); HIP_TRY(h, T.get(&cnt, 8));
+  HIP_TRY(h, T.get(&din, (size_t)c, false)); HIP_TRY(h, T.get(&dout, (size_t)c, false)); HIP_TRY(h, T.get(&cnt, 2, false));
   const int hc[2] = {n, 0};
   HIP_TRY(h, hipMemcpy(cnt, hc, 8, hipMemcpyHostToDevice));
   if (n) HIP_TRY(h, hipMemcpy(din, pts, (size_t)n * 16, hipMemcpyHostToDevice));
@@ -963,9 +920,9 @@ int alego_debug_math(alego_handle* h, int mode, const float* a, const float* b, 
   if (!h || n < 0 || mode < 0 || mode > 3 || (n > 0 && (!a || !out || (mode < 2 && !b)))) return ALEGO_ERR_ARG;
   if (n == 0) return 0;
   hipSetDevice(h->device);
-  DevTemps T;
+  DevPool T;   // temporaries of this call
   float *da, *db, *dout;
-  HIP_TRY(h, T.get(&da, (size_t)n * 4)); HIP_TRY(h, T.get(&db, (size_t)n * 4)); HIP_TRY(h, T.get(&dout, (size_t)n * 4));
+  HIP_TRY(h, T.get(&da, (size_t)n, false)); HIP_TRY(h, T.get(&db, (size_t)n, false)); HIP_TRY(h, T.get(&dout, (size_t)n, false));
   HIP_TRY(h, hipMemcpy(da, a, (size_t)n * 4, hipMemcpyHostToDevice));
   if (b) HIP_TRY(h, hipMemcpy(db, b, (size_t)n * 4, hipMemcpyHostToDevice));
   // the probe kernel takes (y, x): atan2f(y, x), hypotf(x, y), sinf(y), cosf(y)
@@ -980,10 +937,10 @@ int alego_debug_std_sort(alego_handle* h, const uint32_t* keys, int n, int depth
   if (!h || n < 0 || n > 4096 || (n > 0 && (!keys || !order))) return ALEGO_ERR_ARG;
   if (n == 0) return 0;
   hipSetDevice(h->device);
-  DevTemps T;
+  DevPool T;   // temporaries of this call
   uint32_t* dk;
   int* dp;
-  HIP_TRY(h, T.get(&dk, (size_t)n * 4)); HIP_TRY(h, T.get(&dp, (size_t)n * 4));
+  HIP_TRY(h, T.get(&dk, (size_t)n, false)); HIP_TRY(h, T.get(&dp, (size_t)n, false));
   HIP_TRY(h, hipMemcpy(dk, keys, (size_t)n * 4, hipMemcpyHostToDevice));
   if (launch_stdsort_probe(dk, n, depth_limit, dp, h->stream)) return ALEGO_ERR_ARG;
   HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -1000,9 +957,9 @@ int alego_debug_eval_blocks(alego_handle* h, int type, int n, const double* geom
   if (!h || n < 0 || type < 0 || type > 3 || !params6 || (n > 0 && (!geom13 || !res || !jac6))) return ALEGO_ERR_ARG;
   if (n == 0) return 0;
   hipSetDevice(h->device);
-  DevTemps T;
+  DevPool T;   // temporaries of this call
   double *dg, *dp, *dr, *dj;
-  HIP_TRY(h, T.get(&dg, (size_t)n * 13 * 8)); HIP_TRY(h, T.get(&dp, 48)); HIP_TRY(h, T.get(&dr, (size_t)n * 8)); HIP_TRY(h, T.get(&dj, (size_t)n * 48));
+  HIP_TRY(h, T.get(&dg, (size_t)n * 13, false)); HIP_TRY(h, T.get(&dp, 6, false)); HIP_TRY(h, T.get(&dr, (size_t)n, false)); HIP_TRY(h, T.get(&dj, (size_t)n * 6, false));
   HIP_TRY(h, hipMemcpy(dg, geom13, (size_t)n * 13 * 8, hipMemcpyHostToDevice));
   HIP_TRY(h, hipMemcpy(dp, params6, 48, hipMemcpyHostToDevice));
   launch_dbg_eval_blocks(type, n, dg, dp, dr, dj, h->stream);
@@ -1016,10 +973,10 @@ int alego_debug_transform_to_start(alego_handle* h, const double* params6, const
   if (!h || n < 0 || !params6 || (n > 0 && (!pts || !out))) return ALEGO_ERR_ARG;
   if (n == 0) return 0;
   hipSetDevice(h->device);
-  DevTemps T;
+  DevPool T;   // temporaries of this call
   double* dp;
   float4 *di, *dout;
-  HIP_TRY(h, T.get(&dp, 48)); HIP_TRY(h, T.get(&di, (size_t)n * 16)); HIP_TRY(h, T.get(&dout, (size_t)n * 16));
+  HIP_TRY(h, T.get(&dp, 6, false)); HIP_TRY(h, T.get(&di, (size_t)n, false)); HIP_TRY(h, T.get(&dout, (size_t)n, false));
   HIP_TRY(h, hipMemcpy(dp, params6, 48, hipMemcpyHostToDevice));
   HIP_TRY(h, hipMemcpy(di, pts, (size_t)n * 16, hipMemcpyHostToDevice));
   launch_dbg_transform_to_start(dp, di, n, dout, h->stream);

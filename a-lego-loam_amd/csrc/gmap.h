@@ -5,8 +5,8 @@
 #include <hip/hip_runtime.h>
 
 #include <string>
-#include <vector>
 
+#include "dev_mem.h"
 #include "voxel.h"
 
 struct DevCtx;
@@ -34,7 +34,7 @@ struct GvCtx {
   int* cnt = nullptr;            // [2] points in, voxels out
   VoxCtx small;                  // one job over in -> out with capacity small_max (vox_small / vox_big)
   int small_cap = 0;
-  std::vector<void*> allocs;
+  DevPool mem;                   // owns every array above
 };
 int gv_small_max_env();   // GV_SMALL_MAX_DEFAULT, or ALEGO_GV_SMALL_MAX
 int gv_reserve(GvCtx* G, int n, std::string* err);

@@ -39,6 +39,8 @@ hipError_t guard_free(void* p) {
   return hipFree((char*)p - G);
 }
 
+hipError_t guard_zero(void* p, size_t bytes) { return hipMemset(p, 0, bytes); }
+
 int guard_check(std::string* report) {
   if (!enabled()) return -1;
   if (hipDeviceSynchronize() != hipSuccess) { if (report) *report += "device error before the check; "; }

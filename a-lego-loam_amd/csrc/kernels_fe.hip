@@ -15,6 +15,7 @@
 #include <type_traits>
 #include "dev_common.h"
 #include "fe_common.h"
+#include "front_end.h"
 #include "prof.h"
 #include "stdsort_emu.h"
 #include "vgrid.h"
@@ -775,9 +776,6 @@ int launch_stdsort_probe(const uint32_t* keys, int n, int depth_limit, int* pos_
   return 0;
 }
 
-void launch_lo_grid(const DevCtx& d, hipStream_t st);        // kernels_lo.hip: the target grid of the clouds just written, for the next scan's LaserOdometry
-bool fe_fused_eligible(const DevCtx& d);                    // kernels_fe2.hip
-void launch_fe_fused(const DevCtx& d, hipStream_t st);
 void launch_fe_curv_debug(const DevCtx& d, hipStream_t st) { ALEGO_LAUNCH(fe_curv, dim3((d.N + FE_CW - 1) / FE_CW, d.n_launch), dim3(FE_BLOCK), 0, st, d); }
 
 void launch_fe(const DevCtx& d, hipStream_t st) {

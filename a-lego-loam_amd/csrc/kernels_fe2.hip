@@ -19,6 +19,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include "dev_common.h"
+#include "front_end.h"
 #include "prof.h"
 #include "vgrid.h"
 
@@ -922,8 +923,6 @@ __global__ void __launch_bounds__(FO_BLOCK) fe_ring_out(DevCtx d) {
   }
   FO_TICK(8);
 }
-
-void launch_fe_curv_debug(const DevCtx& d, hipStream_t st);   // kernels_fe.hip: fe_curv alone (curvature sums / occlusion marks of the points outside every sector, tests only)
 
 // fused path: everything but alego_params.sort_mode = 2 (the libstdc++ tie order needs the whole sector's keys: four-kernel path)
 // (and only sector counts whose candidate lists fit where they are kept: n_sectors * sector_cap 8-byte entries in a ring's 16 H-byte staging row (ff_list),

@@ -23,7 +23,6 @@
 
 #include "../../include/alego_mi355x.h"
 #include "gmap.h"
-#include "guard_alloc.h"
 #include "kf_store.h"
 #include "pg_math.h"
 #include "prof.h"
@@ -316,21 +315,9 @@ __global__ void __launch_bounds__(GV_T) gv_copy(const float4* in, int n, const i
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------
-namespace {
-template <class T>
-hipError_t galloc(GvCtx* G, T** p, size_t count) {
-  void* q = nullptr;
-  hipError_t e = guard_malloc(&q, count ? count * sizeof(T) : 16);
-  if (e == hipSuccess) { G->allocs.push_back(q); *p = (T*)q; }
-  return e;
-}
-}  // namespace
-
-
 void gv_destroy(GvCtx* G) {
   vox_destroy(&G->small);
-  for (void* p : G->allocs) (void)guard_free(p);
-  G->allocs.clear();
+  G->mem.clear();
   G->cap = 0; G->small_cap = 0;
 }
 
@@ -345,7 +332,7 @@ int gv_reserve(GvCtx* G, int n, std::string* err) {
   const size_t hist_n = tiles * GV_ND;
   const size_t bs_n = std::max(hist_n, (size_t)cap) / GS_BLK + 1;
   hipError_t e = hipSuccess;
-  auto A = [&](auto** p, size_t count) { if (e == hipSuccess) e = galloc(G, p, count); };
+  auto A = [&](auto** p, size_t count) { if (e == hipSuccess) e = G->mem.get(p, count, false); };
   A(&G->in, cap); A(&G->out, cap); A(&G->kA, cap); A(&G->kB, cap); A(&G->vA, cap); A(&G->vB, cap);
   A(&G->run, cap); A(&G->starts, (size_t)cap + 1); A(&G->hist, hist_n); A(&G->bsum, bs_n);
   A(&G->bbox, 8); A(&G->geom, 16); A(&G->cnt, 2);

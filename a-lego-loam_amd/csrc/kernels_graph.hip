@@ -27,7 +27,7 @@
 
 #include "../../include/alego_mi355x.h"
 #include "dev_cost.h"
-#include "guard_alloc.h"
+#include "dev_mem.h"
 #include "kf_store.h"
 #include "pg_math.h"
 #include "pgraph.h"
@@ -478,18 +478,13 @@ __global__ void pg_append(LmCtx L, const PgAppend* a, int n) {
 // ---- host -------------------------------------------------------------------------------------------------------------------
 struct PgCtx {
   long long budget = PG_BUDGET_DEFAULT;
-  char* buf = nullptr;
-  size_t cap = 0;
-  int* apply = nullptr;      // [n_slots]
-  int apply_cap = 0;
-  PgAppend* stage = nullptr; // loop edges on their way to pg_append
-  size_t stage_cap = 0;
+  DevBuf<char> buf;          // chunk scratch (pg_layout)
+  DevBuf<int> apply;         // [n_slots]
+  DevBuf<PgAppend> stage;    // loop edges on their way to pg_append
 };
 void graph_ctx_destroy(PgCtx* C) {
   if (!C) return;
-  if (C->buf) (void)guard_free(C->buf);
-  if (C->apply) (void)guard_free(C->apply);
-  if (C->stage) (void)guard_free(C->stage);
+  C->buf.clear(); C->apply.clear(); C->stage.clear();
   delete C;
 }
 void graph_ctx_set_budget(PgCtx** pc, long long bytes) {
@@ -589,16 +584,10 @@ int graph_append(PgCtx** pc, const LmCtx& L, int n_slots, const std::vector<PgAp
     last[a[i].slot] = (int)i;
   }
   for (int s = 0; s < n_slots; ++s) if (last[s] >= 0) a[last[s]].last = 1;
-  if (a.size() > C->stage_cap) {
-    if (C->stage) (void)guard_free(C->stage);
-    C->stage = nullptr; C->stage_cap = 0;
-    void* p = nullptr;
-    if (guard_malloc(&p, a.size() * sizeof(PgAppend)) != hipSuccess) return pg_fail(err, "graph: staging allocation failed", ALEGO_ERR_HIP);
-    C->stage = (PgAppend*)p; C->stage_cap = a.size();
-  }
-  hipError_t e = hipMemcpy(C->stage, a.data(), a.size() * sizeof(PgAppend), hipMemcpyHostToDevice);
+  if (C->stage.reserve(a.size()) != hipSuccess) return pg_fail(err, "graph: staging allocation failed", ALEGO_ERR_HIP);
+  hipError_t e = hipMemcpy(C->stage.p, a.data(), a.size() * sizeof(PgAppend), hipMemcpyHostToDevice);
   if (e == hipSuccess) {
-    ALEGO_LAUNCH(pg_append, dim3(((int)a.size() + 63) / 64), dim3(64), 0, st, L, (const PgAppend*)C->stage, (int)a.size());
+    ALEGO_LAUNCH(pg_append, dim3(((int)a.size() + 63) / 64), dim3(64), 0, st, L, (const PgAppend*)C->stage.p, (int)a.size());
     e = hipStreamSynchronize(st);
   }
   if (e != hipSuccess) return pg_fail(err, "graph: append failed", ALEGO_ERR_HIP);
@@ -641,19 +630,13 @@ int graph_optimize(PgCtx** pc, const LmCtx& L, int n_slots, const int* slots, in
   const size_t per = pg_layout(&W, nullptr, 1, Nmax, Lmax) + 16 * 256;
   const int chunk = (int)std::max<long long>(1, std::min<long long>((long long)todo.size(), C->budget / (long long)per));
   const size_t need = pg_layout(&W, nullptr, chunk, Nmax, Lmax);
-  if (need > C->cap) {
-    if (C->buf) (void)guard_free(C->buf);
-    C->buf = nullptr; C->cap = 0;
-    void* p = nullptr;
-    if (guard_malloc(&p, need) != hipSuccess) return pg_fail(err, "graph_optimize: scratch allocation failed (lower the budget or max_loops)", ALEGO_ERR_HIP);
-    C->buf = (char*)p; C->cap = need;
-  }
+  if (C->buf.reserve(need) != hipSuccess) return pg_fail(err, "graph_optimize: scratch allocation failed (lower the budget or max_loops)", ALEGO_ERR_HIP);
   const int R = 1 + 6 * Lmax, lanes = std::max(64, (R + 63) / 64 * 64);
   std::vector<int> ctl;
   std::vector<double> dctl;
   for (size_t c0 = 0; c0 < todo.size(); c0 += chunk) {
     const int S = (int)std::min<size_t>(chunk, todo.size() - c0);
-    pg_layout(&W, C->buf, S, Nmax, Lmax);
+    pg_layout(&W, C->buf.p, S, Nmax, Lmax);
     ctl.assign((size_t)S * PC_COUNT, 0);
     for (int q = 0; q < S; ++q) {
       const alego_graph_result& r = out[todo[c0 + q]];
@@ -697,16 +680,10 @@ int graph_optimize(PgCtx** pc, const LmCtx& L, int n_slots, const int* slots, in
 
 // the applied slots' flags on the device (kept with the context)
 int graph_upload_apply(PgCtx* C, const std::vector<int>& apply, const int** dev, hipStream_t st, std::string* err) {
-  if ((int)apply.size() > C->apply_cap) {
-    if (C->apply) (void)guard_free(C->apply);
-    C->apply = nullptr; C->apply_cap = 0;
-    void* p = nullptr;
-    if (guard_malloc(&p, apply.size() * sizeof(int)) != hipSuccess) return pg_fail(err, "graph_optimize: allocation failed", ALEGO_ERR_HIP);
-    C->apply = (int*)p; C->apply_cap = (int)apply.size();
-  }
-  if (hipMemcpyAsync(C->apply, apply.data(), apply.size() * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+  if (C->apply.reserve(apply.size()) != hipSuccess) return pg_fail(err, "graph_optimize: allocation failed", ALEGO_ERR_HIP);
+  if (hipMemcpyAsync(C->apply.p, apply.data(), apply.size() * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
     return pg_fail(err, "graph_optimize: upload failed", ALEGO_ERR_HIP);
-  *dev = C->apply;
+  *dev = C->apply.p;
   return 0;
 }
 

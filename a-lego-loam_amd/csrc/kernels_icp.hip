@@ -140,15 +140,8 @@ __global__ void icp_init(IcpState* S, int n_src, const int* n_tgt) {
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------
-#include "../../include/alego_mi355x.h"
-
-namespace {
-struct Temps {
-  std::vector<void*> p;
-  template <class T> hipError_t get(T** q, size_t bytes) { void* v = nullptr; hipError_t e = hipMalloc(&v, bytes ? bytes : 16); if (e == hipSuccess) p.push_back(v); *q = (T*)v; return e; }
-  ~Temps() { for (void* v : p) (void)hipFree(v); }
-};
-}  // namespace
+#include "dev_mem.h"
+#include "loop_ctx.h"
 
 int icp_run(const alego_params& P, const alego_kf_in* latest, const alego_kf_in* history, int n_history, alego_icp_result* out,
             alego_point* target_out, int target_cap, hipStream_t st, std::string* err) {
@@ -168,18 +161,13 @@ int icp_run(const alego_params& P, const alego_kf_in* latest, const alego_kf_in*
     for (int kind = 0; kind < KF_KINDS; ++kind) F[f].dst[kind] = base + kf_out_start(k.n_corner, k.n_surf, KF_SEL_ALL, kind);
     base += k.n_surf + k.n_corner + k.n_outlier;
   }
-  Temps T;
+  DevPool T;   // temporaries of this call
   IcpFrame* dF; float4 *draw, *dsrc, *dcur, *dtraw, *dtgt; int* dcnt; IcpState* dS; double* dpart;
   const int nwg = std::max(1, (n_src + ICP_T - 1) / ICP_T);
-  hipError_t e = T.get(&dF, sizeof(IcpFrame) * nf);
-  if (e == hipSuccess) e = T.get(&draw, raw.size() * 16);
-  if (e == hipSuccess) e = T.get(&dsrc, (size_t)std::max(n_src, 1) * 16);
-  if (e == hipSuccess) e = T.get(&dcur, (size_t)std::max(n_src, 1) * 16);
-  if (e == hipSuccess) e = T.get(&dtraw, (size_t)std::max(n_traw, 1) * 16);
-  if (e == hipSuccess) e = T.get(&dtgt, (size_t)std::max(n_traw, 1) * 16);
-  if (e == hipSuccess) e = T.get(&dcnt, 8);
-  if (e == hipSuccess) e = T.get(&dS, sizeof(IcpState));
-  if (e == hipSuccess) e = T.get(&dpart, (size_t)nwg * 18 * 8);
+  hipError_t e = hipSuccess;
+  auto get = [&](auto** p, size_t count) { if (e == hipSuccess) e = T.get(p, count, false); };
+  get(&dF, (size_t)nf); get(&draw, raw.size()); get(&dsrc, (size_t)std::max(n_src, 1)); get(&dcur, (size_t)std::max(n_src, 1));
+  get(&dtraw, (size_t)std::max(n_traw, 1)); get(&dtgt, (size_t)std::max(n_traw, 1)); get(&dcnt, 2); get(&dS, 1); get(&dpart, (size_t)nwg * 18);
   if (e == hipSuccess) e = hipMemcpyAsync(dF, F.data(), sizeof(IcpFrame) * nf, hipMemcpyHostToDevice, st);
   if (e == hipSuccess && !raw.empty()) e = hipMemcpyAsync(draw, raw.data(), raw.size() * 16, hipMemcpyHostToDevice, st);
   const int hc[2] = {n_traw, 0};
@@ -197,8 +185,8 @@ int icp_run(const alego_params& P, const alego_kf_in* latest, const alego_kf_in*
     hipLaunchKernelGGL(icp_corr, dim3(nwg), dim3(ICP_T), 0, st, dS, dcur, dtgt, max_d2, dpart);
     hipLaunchKernelGGL(icp_step, dim3(1), dim3(64), 0, st, dS, dpart, nwg, P);
   }
-  hipLaunchKernelGGL(icp_fitness, dim3(nwg), dim3(ICP_T), 0, st, dS, dsrc, dtgt, dpart);
-  hipLaunchKernelGGL(icp_fitness_final, dim3(1), dim3(64), 0, st, dS, dpart, nwg);
+  if (n_src > 0) hipLaunchKernelGGL(icp_fitness, dim3(nwg), dim3(ICP_T), 0, st, dS, dsrc, dtgt, dpart);   // (its idle lanes read src[n_src - 1]; without a source the fitness stays icp_init's)
+  if (n_src > 0) hipLaunchKernelGGL(icp_fitness_final, dim3(1), dim3(64), 0, st, dS, dpart, nwg);
   IcpState S;
   e = hipMemcpyAsync(&S, dS, sizeof(S), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);

@@ -21,6 +21,7 @@
 // same ordered compaction.  tests/test_gpu_parity.py::test_ip_bit_exact[(64,2048) / (32,2048) / (40,1800) x band / tile].
 #include <cstdlib>
 #include "dev_common.h"
+#include "front_end.h"
 #include "ip_common.h"
 #include "prof.h"
 

@@ -22,6 +22,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include "dev_common.h"
+#include "front_end.h"
 #include "ip_common.h"
 #include "prof.h"
 

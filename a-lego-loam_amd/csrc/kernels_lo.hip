@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <type_traits>
 #include "dev_cost.h"
+#include "front_end.h"
 #include "lm_ctx.h"
 #include "prof.h"
 

@@ -28,7 +28,7 @@
 #include <vector>
 
 #include "../../include/alego_mi355x.h"
-#include "guard_alloc.h"
+#include "dev_mem.h"
 #include "icp_math.h"
 #include "kf_store.h"
 #include "loop_ctx.h"
@@ -392,22 +392,17 @@ struct LcCtx {
   int *cstart = nullptr, *ccur = nullptr;
   VoxCtx V;
   bool vox = false;
-  std::vector<void*> allocs;
+  DevPool lists, chunk;                    // own the list arrays (valid while list_cap > 0) and the per-chunk regions (valid while cap > 0)
 };
 
 static void lc_free_chunk(LcCtx* C) {
-  for (void* p : {(void*)C->src, (void*)C->cur, (void*)C->raw, (void*)C->tgt, (void*)C->spts, (void*)C->cbox, (void*)C->cstart, (void*)C->ccur})
-    if (p) (void)guard_free(p);
-  C->src = C->cur = C->raw = C->tgt = C->spts = C->cbox = nullptr;
-  C->cstart = C->ccur = nullptr;
+  C->chunk.clear();
   if (C->vox) vox_destroy(&C->V);
-  C->vox = false;
-  C->cap = 0;
+  C->vox = false; C->cap = 0;
 }
 void loop_ctx_destroy(LcCtx* C) {
   if (!C) return;
-  lc_free_chunk(C);
-  for (void* p : C->allocs) (void)guard_free(p);
+  lc_free_chunk(C); C->lists.clear();
   delete C;
 }
 void loop_ctx_set_budget(LcCtx** pc, long long points) {
@@ -416,23 +411,19 @@ void loop_ctx_set_budget(LcCtx** pc, long long points) {
 }
 
 template <class T>
-static bool lc_alloc(T** p, size_t count, std::string* err) {
-  void* q = nullptr;
-  hipError_t e = guard_malloc(&q, std::max<size_t>(16, count * sizeof(T)));
+static bool lc_alloc(DevPool& mem, T** p, size_t count, std::string* err) {
+  const hipError_t e = mem.get(p, count, false);
   if (e != hipSuccess) { *err = std::string("loop search: ") + hipGetErrorString(e); return false; }
-  *p = (T*)q;
   return true;
 }
 
 // list arrays for list_cap entries; need > 0: per-chunk regions of at least `need` points (+ the VoxelGrid context)
 static int lc_reserve(LcCtx* C, int list_cap, long long need, std::string* err) {
   if (C->list_cap < list_cap) {
-    for (void* p : C->allocs) (void)guard_free(p);
-    C->allocs.clear();
+    C->lists.clear();
     C->list_cap = 0;
-    if (!lc_alloc(&C->list, list_cap, err) || !lc_alloc(&C->det, list_cap, err) || !lc_alloc(&C->out, list_cap, err) || !lc_alloc(&C->jobs, list_cap, err) ||
-        !lc_alloc(&C->geo, list_cap, err) || !lc_alloc(&C->ntgt, list_cap, err)) return ALEGO_ERR_HIP;
-    for (void* p : {(void*)C->list, (void*)C->det, (void*)C->out, (void*)C->jobs, (void*)C->geo, (void*)C->ntgt}) C->allocs.push_back(p);
+    if (!lc_alloc(C->lists, &C->list, list_cap, err) || !lc_alloc(C->lists, &C->det, list_cap, err) || !lc_alloc(C->lists, &C->out, list_cap, err) || !lc_alloc(C->lists, &C->jobs, list_cap, err) ||
+        !lc_alloc(C->lists, &C->geo, list_cap, err) || !lc_alloc(C->lists, &C->ntgt, list_cap, err)) return ALEGO_ERR_HIP;
     C->list_cap = list_cap;
     if (C->vox) { vox_destroy(&C->V); C->vox = false; }
   }
@@ -440,8 +431,8 @@ static int lc_reserve(LcCtx* C, int list_cap, long long need, std::string* err) 
     const long long cap = std::max(C->cap, need);
     lc_free_chunk(C);
     const size_t n = (size_t)cap;
-    if (!lc_alloc(&C->src, n, err) || !lc_alloc(&C->cur, n, err) || !lc_alloc(&C->raw, n, err) || !lc_alloc(&C->tgt, n, err) || !lc_alloc(&C->spts, n, err) ||
-        !lc_alloc(&C->cbox, 2 * n, err) || !lc_alloc(&C->cstart, n + 1, err) || !lc_alloc(&C->ccur, n + 1, err)) { lc_free_chunk(C); return ALEGO_ERR_HIP; }
+    if (!lc_alloc(C->chunk, &C->src, n, err) || !lc_alloc(C->chunk, &C->cur, n, err) || !lc_alloc(C->chunk, &C->raw, n, err) || !lc_alloc(C->chunk, &C->tgt, n, err) || !lc_alloc(C->chunk, &C->spts, n, err) ||
+        !lc_alloc(C->chunk, &C->cbox, 2 * n, err) || !lc_alloc(C->chunk, &C->cstart, n + 1, err) || !lc_alloc(C->chunk, &C->ccur, n + 1, err)) { lc_free_chunk(C); return ALEGO_ERR_HIP; }
     // one VoxelGrid job per attempted slot of a chunk; its sort scratch is the slot's region of the raw sub-map (job.off = raw_off)
     std::vector<VoxJob> jz((size_t)C->list_cap);
     std::memset(jz.data(), 0, jz.size() * sizeof(VoxJob));
@@ -553,14 +544,13 @@ int loop_attempts(LcCtx** pc, const alego_params& P, int n_slots, const int* slo
 }
 
 int loop_debug_nn1(const alego_point* tgt, int n_tgt, const alego_point* q, int nq, int32_t* idx, float* d2, hipStream_t st, std::string* err) {
-  std::vector<void*> tmp;
-  auto get = [&](void** p, size_t bytes) { hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 16)); if (e == hipSuccess) tmp.push_back(*p); return e == hipSuccess; };
-  struct Free { std::vector<void*>& t; ~Free() { for (void* p : t) (void)hipFree(p); } } fr{tmp};
+  DevPool tmp;   // temporaries of this call
+  auto get = [&](auto** p, size_t count) { return tmp.get(p, count, false) == hipSuccess; };
   const int cell_cap = n_tgt / 4 + 2;
   float4 *dt, *dq, *sp, *cb; int *cs, *cc, *di; float* dd; LcGrid* g;
-  if (!get((void**)&dt, (size_t)n_tgt * 16) || !get((void**)&dq, (size_t)nq * 16) || !get((void**)&sp, (size_t)n_tgt * 16) || !get((void**)&cb, (size_t)cell_cap * 32) ||
-      !get((void**)&cs, ((size_t)cell_cap + 1) * 4) || !get((void**)&cc, ((size_t)cell_cap + 1) * 4) || !get((void**)&di, (size_t)nq * 4) || !get((void**)&dd, (size_t)nq * 4) ||
-      !get((void**)&g, sizeof(LcGrid))) { *err = "debug_nn1: hipMalloc failed"; return ALEGO_ERR_HIP; }
+  if (!get(&dt, (size_t)n_tgt) || !get(&dq, (size_t)nq) || !get(&sp, (size_t)n_tgt) || !get(&cb, (size_t)cell_cap * 2) ||
+      !get(&cs, (size_t)cell_cap + 1) || !get(&cc, (size_t)cell_cap + 1) || !get(&di, (size_t)nq) || !get(&dd, (size_t)nq) ||
+      !get(&g, 1)) { *err = "debug_nn1: allocation failed"; return ALEGO_ERR_HIP; }
   hipError_t e = n_tgt ? hipMemcpyAsync(dt, tgt, (size_t)n_tgt * 16, hipMemcpyHostToDevice, st) : hipSuccess;
   if (e == hipSuccess && nq) e = hipMemcpyAsync(dq, q, (size_t)nq * 16, hipMemcpyHostToDevice, st);
   if (e != hipSuccess) { *err = "debug_nn1: upload failed"; return ALEGO_ERR_HIP; }

@@ -25,10 +25,11 @@
 #include "../../include/alego_mi355x.h"
 #include "dev_common.h"
 #include "dev_cost.h"
-#include "guard_alloc.h"
+#include "dev_mem.h"
 #include "kf_store.h"
 #include "loop_ctx.h"
 #include "prof.h"
+#include "reloc.h"
 #include "reloc_math.h"
 #include "wave.h"
 
@@ -286,25 +287,18 @@ struct RlCtx {
   int *list2 = nullptr, *cnt2 = nullptr, *listA = nullptr, *cntA = nullptr, *qsel = nullptr;
   unsigned long long* cand = nullptr;
   int stats[2] = {0, 0};                // of the last search: (query, frame) pairs the second round evaluated, pairs in all
+  DevPool store, scratch;               // own what reloc_enable allocates (valid while n_slots > 0) and the search scratch (valid while pairs_cap > 0)
 };
 
 template <class T>
-static bool rl_alloc(T** p, size_t count, std::string* err) {
-  void* q = nullptr;
-  hipError_t e = guard_malloc(&q, std::max<size_t>(16, count * sizeof(T)));
+static bool rl_alloc(DevPool& mem, T** p, size_t count, std::string* err) {
+  const hipError_t e = mem.get(p, count, false);
   if (e != hipSuccess) { *err = std::string("relocalisation: ") + hipGetErrorString(e); return false; }
-  *p = (T*)q;
   return true;
-}
-template <class T> static void rl_free(T** p) { if (*p) (void)guard_free(*p); *p = nullptr; }
-static void rl_free_scratch(RlCtx* R) {
-  rl_free(&R->bound); rl_free(&R->res2); rl_free(&R->resA); rl_free(&R->list2); rl_free(&R->cnt2); rl_free(&R->listA); rl_free(&R->cntA); rl_free(&R->qsel); rl_free(&R->cand);
-  R->pairs_cap = R->q_cap = 0;
 }
 void reloc_ctx_destroy(RlCtx* R) {
   if (!R) return;
-  rl_free_scratch(R);
-  rl_free(&R->mdesc); rl_free(&R->qdesc); rl_free(&R->mkey); rl_free(&R->qkey); rl_free(&R->list); rl_free(&R->apply); rl_free(&R->state); rl_free(&R->klist);
+  R->scratch.clear(); R->store.clear();
   delete R;
 }
 void reloc_ctx_set(RlCtx** pr, int what, long long v) {   // what 0: pairs per chunk of the search, 1: brute force
@@ -318,10 +312,10 @@ int reloc_enable(RlCtx** pr, const LmCtx& L, int n_slots, double max_range, doub
   RlCtx* R = *pr;
   const int N = L.loc_n;
   R->w = rl_ring_width(max_range); R->zoff = rl_z_offset(z_offset);
-  auto undo = [&](int rc) { rl_free(&R->mdesc); rl_free(&R->qdesc); rl_free(&R->mkey); rl_free(&R->qkey); rl_free(&R->list); rl_free(&R->apply); rl_free(&R->state); rl_free(&R->klist); return rc; };   // (the handle stays what it was)
-  if (!rl_alloc(&R->mdesc, (size_t)N * RL_WORDS, err) || !rl_alloc(&R->mkey, (size_t)N * RL_NR, err) || !rl_alloc(&R->qdesc, (size_t)n_slots * RL_WORDS, err) ||
-      !rl_alloc(&R->qkey, (size_t)n_slots * RL_NR, err) || !rl_alloc(&R->list, (size_t)n_slots, err) || !rl_alloc(&R->apply, (size_t)n_slots, err) ||
-      !rl_alloc(&R->state, (size_t)n_slots, err) || !rl_alloc(&R->klist, (size_t)n_slots * RL_NR, err)) return undo(ALEGO_ERR_HIP);
+  auto undo = [&](int rc) { R->store.clear(); return rc; };   // (the handle stays what it was)
+  if (!rl_alloc(R->store, &R->mdesc, (size_t)N * RL_WORDS, err) || !rl_alloc(R->store, &R->mkey, (size_t)N * RL_NR, err) || !rl_alloc(R->store, &R->qdesc, (size_t)n_slots * RL_WORDS, err) ||
+      !rl_alloc(R->store, &R->qkey, (size_t)n_slots * RL_NR, err) || !rl_alloc(R->store, &R->list, (size_t)n_slots, err) || !rl_alloc(R->store, &R->apply, (size_t)n_slots, err) ||
+      !rl_alloc(R->store, &R->state, (size_t)n_slots, err) || !rl_alloc(R->store, &R->klist, (size_t)n_slots * RL_NR, err)) return undo(ALEGO_ERR_HIP);
   hipError_t e = hipMemsetAsync(R->qdesc, 0, std::max<size_t>(16, (size_t)n_slots * RL_BYTES), st);
   if (e == hipSuccess) e = hipMemsetAsync(R->qkey, 0, std::max<size_t>(16, (size_t)n_slots * RL_NR * 2), st);
   if (e == hipSuccess && N > 0) ALEGO_LAUNCH(rl_desc, dim3(N), dim3(RL_T), 0, st, L, 0, (const int*)nullptr, R->w, R->zoff, R->mdesc, R->mkey, (RlSlot*)nullptr, (uint16_t*)nullptr);
@@ -352,10 +346,10 @@ static int rl_search_run(RlCtx* R, const uint32_t* qdesc, const uint16_t* qkey, 
   if (R->pairs_cap < (size_t)QC * N || R->q_cap < (size_t)QC) {
     const size_t pc = std::max(R->pairs_cap, (size_t)QC * N), qc = std::max(R->q_cap, (size_t)QC);
     if (hipStreamSynchronize(st) != hipSuccess) { *err = "relocalisation: a stream failed"; return ALEGO_ERR_HIP; }
-    rl_free_scratch(R);
-    if (!rl_alloc(&R->bound, pc, err) || !rl_alloc(&R->res2, pc, err) || !rl_alloc(&R->list2, pc, err) || !rl_alloc(&R->resA, qc * ALEGO_RELOC_MAX_CAND, err) ||
-        !rl_alloc(&R->listA, qc * ALEGO_RELOC_MAX_CAND, err) || !rl_alloc(&R->cntA, qc, err) || !rl_alloc(&R->cnt2, qc, err) || !rl_alloc(&R->qsel, qc, err) ||
-        !rl_alloc(&R->cand, qc * ALEGO_RELOC_MAX_CAND, err)) { rl_free_scratch(R); return ALEGO_ERR_HIP; }
+    R->scratch.clear(); R->pairs_cap = R->q_cap = 0;
+    if (!rl_alloc(R->scratch, &R->bound, pc, err) || !rl_alloc(R->scratch, &R->res2, pc, err) || !rl_alloc(R->scratch, &R->list2, pc, err) || !rl_alloc(R->scratch, &R->resA, qc * ALEGO_RELOC_MAX_CAND, err) ||
+        !rl_alloc(R->scratch, &R->listA, qc * ALEGO_RELOC_MAX_CAND, err) || !rl_alloc(R->scratch, &R->cntA, qc, err) || !rl_alloc(R->scratch, &R->cnt2, qc, err) || !rl_alloc(R->scratch, &R->qsel, qc, err) ||
+        !rl_alloc(R->scratch, &R->cand, qc * ALEGO_RELOC_MAX_CAND, err)) { R->scratch.clear(); return ALEGO_ERR_HIP; }
     R->pairs_cap = pc; R->q_cap = qc;
   }
   const int nblk = std::max(1, std::min(RL_SEARCH_BLOCKS, (N + RL_WAVES - 1) / RL_WAVES));
@@ -384,10 +378,10 @@ int reloc_debug_search(RlCtx** pr, const uint8_t* map_desc, int n_map, const uin
                        hipStream_t st, std::string* err) {
   if (!*pr) *pr = new RlCtx();
   RlCtx* R = *pr;
+  DevPool tmp;   // temporaries of this call
   uint32_t *md = nullptr, *qd = nullptr;
   uint16_t *mk = nullptr, *qk = nullptr;
-  struct Free { uint32_t **a, **b; uint16_t **c, **d; ~Free() { rl_free(a); rl_free(b); rl_free(c); rl_free(d); } } fr{&md, &qd, &mk, &qk};
-  if (!rl_alloc(&md, (size_t)n_map * RL_WORDS, err) || !rl_alloc(&qd, (size_t)n_q * RL_WORDS, err) || !rl_alloc(&mk, (size_t)n_map * RL_NR, err) || !rl_alloc(&qk, (size_t)n_q * RL_NR, err))
+  if (!rl_alloc(tmp, &md, (size_t)n_map * RL_WORDS, err) || !rl_alloc(tmp, &qd, (size_t)n_q * RL_WORDS, err) || !rl_alloc(tmp, &mk, (size_t)n_map * RL_NR, err) || !rl_alloc(tmp, &qk, (size_t)n_q * RL_NR, err))
     return ALEGO_ERR_HIP;
   hipError_t e = n_map ? hipMemcpyAsync(md, map_desc, (size_t)n_map * RL_BYTES, hipMemcpyHostToDevice, st) : hipSuccess;
   if (e == hipSuccess && n_q) e = hipMemcpyAsync(qd, q_desc, (size_t)n_q * RL_BYTES, hipMemcpyHostToDevice, st);

@@ -21,7 +21,7 @@
 #include "voxel.h"
 #include "wave.h"
 #include "vgrid.h"
-#include "guard_alloc.h"
+#include "dev_mem.h"
 #include "prof.h"
 
 typedef unsigned long long u64;
@@ -515,20 +515,21 @@ int vox_create(VoxCtx* V, const VoxJob* jobs, int njobs, std::string* err) {
   if (total > 0x7fffffffull) { *err = "vox_create: scratch exceeds 2^31 elements"; return -3; }
   V->njobs = njobs; V->total = (unsigned)total;
   hipError_t e = hipSuccess;
-  auto A = [&](void** p, size_t bytes) { if (e == hipSuccess) { e = guard_malloc(p, bytes ? bytes : 16); if (e == hipSuccess) e = hipMemset(*p, 0, bytes ? bytes : 16); } };
-  A((void**)&V->jobs, sizeof(VoxJob) * njobs);
-  A((void**)&V->bbox, (size_t)njobs * 8 * 4);
-  A((void**)&V->keys, total * 4); A((void**)&V->pairs_a, total * 8); A((void**)&V->pairs_b, total * 8);
-  A((void**)&V->list_small, (size_t)njobs * 4); A((void**)&V->list_big, (size_t)njobs * 4); A((void**)&V->cnt, 8);
+  DevPool mem;   // owns the blocks until everything has succeeded; then V does (a POD: it is a kernel argument), until vox_destroy
+  auto A = [&](auto** p, size_t count) { if (e == hipSuccess) e = mem.get(p, count, true); };
+  A(&V->jobs, (size_t)njobs); A(&V->bbox, (size_t)njobs * 8);
+  A(&V->keys, total); A(&V->pairs_a, total); A(&V->pairs_b, total);
+  A(&V->list_small, (size_t)njobs); A(&V->list_big, (size_t)njobs); A(&V->cnt, 2);
   V->grid_small = V->grid_big = njobs;
   if (e == hipSuccess) e = hipMemcpy(V->jobs, h.data(), sizeof(VoxJob) * njobs, hipMemcpyHostToDevice);
-  if (e != hipSuccess) { *err = std::string("vox_create: ") + hipGetErrorString(e); return -2; }
+  if (e != hipSuccess) { std::memset(V, 0, sizeof(*V)); *err = std::string("vox_create: ") + hipGetErrorString(e); return -2; }
+  mem.detach();
   return 0;
 }
 
 void vox_destroy(VoxCtx* V) {
-  void* ps[] = {V->jobs, V->bbox, V->keys, V->pairs_a, V->pairs_b, V->list_small, V->list_big, V->cnt};
-  for (void* p : ps) if (p) (void)guard_free(p);
+  DevPool mem;
+  for (void* p : {(void*)V->jobs, (void*)V->bbox, (void*)V->keys, (void*)V->pairs_a, (void*)V->pairs_b, (void*)V->list_small, (void*)V->list_big, (void*)V->cnt}) mem.adopt(p);
   std::memset(V, 0, sizeof(*V));
 }
 

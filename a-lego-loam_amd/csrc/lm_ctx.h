@@ -167,4 +167,19 @@ struct LmCtx {
   double* pg_est;                                 // [slot][arc_frames_cap][12] Pose3 estimate of the slot's last optimise, row-major [R | t]
 };
 
+// host entry points of LaserMapping's kernels (kernels_lm.hip, then kernels_map.hip and kernels_loc.hip), called by lm_host.hip; lm_configure: by alego_create
+size_t lm_solve_row_bytes_max(), lm_solve_row_bytes_default();
+int lm_configure();
+void launch_lm_prepare(const DevCtx& d, const LmCtx& L, int stage, int run_hint, int par, hipStream_t st);
+void launch_lm_stage(const DevCtx& d, const LmCtx& L, int run_hint, int par, hipStream_t st);
+void launch_lm_concat(const DevCtx& d, const LmCtx& L, hipStream_t st);
+void launch_lm_total(const DevCtx& d, const LmCtx& L, hipStream_t st);
+void launch_lm_grid(const DevCtx& d, const LmCtx& L, hipStream_t st);
+int launch_lm_register(const DevCtx& d, const LmCtx& L, hipStream_t st, int (*allreduce)(void*, double*, size_t, hipStream_t), void* ar_ctx);
+void launch_lm_retransform(const DevCtx& d, const LmCtx& L, int ring, hipStream_t st);
+void launch_lm_apply_correction(const DevCtx& d, const LmCtx& L, int slot, const double* rc_dev, hipStream_t st);
+void launch_map_update(const DevCtx& d, const LmCtx& L, const MapWork& W, hipStream_t st);
+void launch_map_accum(const DevCtx& d, const LmCtx& L, const MapWork& W, hipStream_t st);
+void launch_loc_select(const DevCtx& d, const LmCtx& L, hipStream_t st);
+
 #endif

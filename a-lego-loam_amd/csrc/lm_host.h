@@ -19,6 +19,7 @@ int lm_host_enqueue(LmHost* lm, const DevCtx& d, const std::vector<char>& odom_v
 // this stream group, back_same / back_other = events recorded on `back` after the LaserMapping of scans k - 2 / k - 1
 int lm_host_enqueue_async(LmHost* lm, const DevCtx& d, const std::vector<char>& odom_valid, std::string* err, hipStream_t front, hipStream_t back,
                           hipEvent_t staged, hipEvent_t back_same, hipEvent_t back_other, long k);
+const double* lm_host_stage_odom(LmHost* lm);   // the odometry lm_stage handed over (device, [slot][2][8])
 int lm_host_get_flags(LmHost* lm, int slot);
 int lm_host_process_host(LmHost* lm, const DevCtx& d, const alego_point* corner_last, int n_corner, const alego_point* surf_last,
                          int n_surf, const alego_point* outlier, int n_outlier, const alego_pose* odom, alego_pose* map_pose,

@@ -1,6 +1,6 @@
 // lm_host.hip — LaserMapping: HBM allocation and kernel sequencing (no numerics here).
 #include "lm_host.h"
-#include "guard_alloc.h"
+#include "dev_mem.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -14,23 +14,7 @@
 #include "voxel.h"
 #include "gmap.h"
 #include "loc_math.h"
-
-void launch_lm_prepare(const DevCtx& d, const LmCtx& L, int stage, int run_hint, int par, hipStream_t st);
-void launch_lm_stage(const DevCtx& d, const LmCtx& L, int run_hint, int par, hipStream_t st);
-void launch_lm_concat(const DevCtx& d, const LmCtx& L, hipStream_t st);
-void launch_lm_total(const DevCtx& d, const LmCtx& L, hipStream_t st);
-void launch_lm_grid(const DevCtx& d, const LmCtx& L, hipStream_t st);
-int launch_lm_register(const DevCtx& d, const LmCtx& L, hipStream_t st, int (*allreduce)(void*, double*, size_t, hipStream_t), void* ar_ctx);
-size_t lm_solve_row_bytes_max();
-size_t lm_solve_row_bytes_default();
-void launch_lm_retransform(const DevCtx& d, const LmCtx& L, int ring, hipStream_t st);
-void launch_map_update(const DevCtx& d, const LmCtx& L, const MapWork& W, hipStream_t st);
-void launch_map_accum(const DevCtx& d, const LmCtx& L, const MapWork& W, hipStream_t st);   // kernels_map.hip
-void launch_lm_apply_correction(const DevCtx& d, const LmCtx& L, int slot, const double* rc_dev, hipStream_t st);
-void launch_pg_apply(const LmCtx& L, const int* apply_dev, int n_slots, hipStream_t st);   // kernels_graph.hip
-void launch_pg_retransform(const LmCtx& L, const int* apply_dev, int slot0, int n, int j, hipStream_t st);
-void launch_pg_sorted(const LmCtx& L, const int* apply_dev, int slot0, int n, int all, hipStream_t st);
-void launch_loc_select(const DevCtx& d, const LmCtx& L, hipStream_t st);   // kernels_loc.hip
+#include "pgraph.h"
 
 struct LmHost {
   alego_params P;
@@ -47,7 +31,7 @@ struct LmHost {
   bool fallback_ok = true;     // buffers of the concat + radix VoxelGrid path (ALEGO_MAP_MERGE=0) are allocated
   ncclComm_t comm = nullptr;   // alego_dist_init: the registration of every slot is sharded over the ranks of this communicator
   std::string dist_err;
-  std::vector<void*> allocs;
+  DevPool mem;               // every device block LaserMapping owns apart from the VoxelGrid contexts and gv
   std::vector<long> frames;  // host mirror of frame_cnt per slot: only used to skip launches
   // the global map (alego_map_* / alego_voxel_grid): device-wide VoxelGrid scratch + the assembly's frame offsets
   GvCtx gv;
@@ -60,21 +44,9 @@ struct LmHost {
 namespace {
 template <class T>
 bool A(LmHost* lm, T** p, size_t count, std::string* err) {
-  void* q = nullptr;
-  size_t bytes = count * sizeof(T);
-  if (bytes == 0) bytes = 16;
-  hipError_t e = guard_malloc(&q, bytes);
-  if (e == hipSuccess) e = hipMemset(q, 0, bytes);
-  if (e != hipSuccess) { *err = std::string("lm hipMalloc: ") + hipGetErrorString(e); return false; }
-  lm->allocs.push_back(q);
-  *p = (T*)q;
+  const hipError_t e = lm->mem.get(p, count, true);
+  if (e != hipSuccess) { *err = std::string("lm allocation: ") + hipGetErrorString(e); return false; }
   return true;
-}
-void release(LmHost* lm, void* p) {
-  auto it = std::find(lm->allocs.begin(), lm->allocs.end(), p);
-  if (it == lm->allocs.end()) return;
-  (void)guard_free(p);
-  lm->allocs.erase(it);
 }
 
 // the nine arrays of the key-frame ring (or of the map store that takes its place, alego_loc_enable): f(array, elements per row)
@@ -87,7 +59,7 @@ bool ring_alloc(LmHost* lm, LmCtx& L, size_t rows, std::string* err) {   // (a p
   ring_each(L, [&](auto*& p, size_t per_row) { p = nullptr; ok = ok && A(lm, &p, rows * per_row, err); });
   return ok;
 }
-void ring_release(LmHost* lm, LmCtx& L) { ring_each(L, [&](auto*& p, size_t) { if (p) release(lm, p); p = nullptr; }); }
+void ring_release(LmHost* lm, LmCtx& L) { ring_each(L, [&](auto*& p, size_t) { lm->mem.release(p); p = nullptr; }); }
 // the two sort jobs of a slot's kf_tmp_* (corner, surf + outlier): sorted by voxel key of the map's leaf into the row of the slot that LI_KF_PEND_RING names (VoxelGrid mode 1)
 void kf_sort_jobs(const LmCtx& L, const alego_params& P, int slot, std::vector<VoxJob>* out) {
   int* li = L.li + (size_t)slot * LI_COUNT;
@@ -212,7 +184,7 @@ void lm_host_destroy(LmHost* lm) {
   for (auto& v : lm->vk) vox_destroy(&v);
   if (lm->vloc_made) vox_destroy(&lm->vloc);
   gv_destroy(&lm->gv);
-  for (void* p : lm->allocs) (void)guard_free(p);
+  lm->mem.clear();
   delete lm;
 }
 
@@ -478,12 +450,12 @@ int lm_host_reset_window(LmHost* lm, int slot, std::string* err) {
   return 0;
 }
 int lm_host_apply_correction(LmHost* lm, const DevCtx& dfull, int slot, const double* rc12, std::string* err) {
+  DevPool tmp;
   double* dev = nullptr;
   hipStream_t st = stream_of_slot(lm, slot);
-  if (hipMalloc((void**)&dev, 12 * sizeof(double)) != hipSuccess) { *err = "apply_correction: hipMalloc"; return ALEGO_ERR_HIP; }
+  if (tmp.get(&dev, 12, false) != hipSuccess) { *err = "apply_correction: allocation failed"; return ALEGO_ERR_HIP; }
   hipError_t e = hipMemcpy(dev, rc12, 12 * sizeof(double), hipMemcpyHostToDevice);
   if (e == hipSuccess) { launch_lm_apply_correction(dfull, lm->L, slot, dev, st); e = hipStreamSynchronize(st); }
-  (void)hipFree(dev);
   if (e != hipSuccess) { *err = std::string("apply_correction: ") + hipGetErrorString(e); return ALEGO_ERR_HIP; }
   return 0;
 }
@@ -554,10 +526,11 @@ int lm_host_dist_probe(LmHost* lm, int iters, double* usec, std::string* err) {
   if (!lm->comm) { *err = "alego_dist_allreduce_probe: no communicator (alego_dist_init first)"; return ALEGO_ERR_ARG; }
   if (iters < 1 || !usec) { *err = "alego_dist_allreduce_probe: iters / output"; return ALEGO_ERR_ARG; }
   hipStream_t st = lm->st[0];
+  DevPool tmp;
   double* buf = nullptr;
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (hipMalloc(&buf, 32 * sizeof(double)) != hipSuccess || hipMemsetAsync(buf, 0, 32 * sizeof(double), st) != hipSuccess ||
-      hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { *err = "alego_dist_allreduce_probe: allocation failed"; if (buf) (void)hipFree(buf); return ALEGO_ERR_HIP; }
+  if (tmp.get(&buf, 32, false) != hipSuccess || hipMemsetAsync(buf, 0, 32 * sizeof(double), st) != hipSuccess ||
+      hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { *err = "alego_dist_allreduce_probe: allocation failed"; return ALEGO_ERR_HIP; }
   int rc = 0;
   for (int i = 0; i < 8 && !rc; ++i) rc = lm_allreduce(lm, buf, 32, st);   // warm the channels
   (void)hipEventRecord(e0, st);
@@ -566,7 +539,7 @@ int lm_host_dist_probe(LmHost* lm, int iters, double* usec, std::string* err) {
   const hipError_t se = hipStreamSynchronize(st);
   float ms = 0.f;
   if (!rc && se == hipSuccess) (void)hipEventElapsedTime(&ms, e0, e1);
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipFree(buf);
+  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); tmp.clear();
   if (rc) { *err = lm->dist_err; return rc; }
   if (se != hipSuccess) { *err = std::string("alego_dist_allreduce_probe: ") + hipGetErrorString(se); return ALEGO_ERR_HIP; }
   *usec = 1e3 * (double)ms / iters;

@@ -25,5 +25,9 @@ int graph_get_estimate(const LmCtx& L, int slot, int first, int n, double* poses
 int graph_optimize(PgCtx** pc, const LmCtx& L, int n_slots, const int* slots, int n, const alego_graph_opts& opt, alego_graph_result* out,
                    std::vector<int>* apply_out, hipStream_t st, std::string* err);
 int graph_upload_apply(PgCtx* C, const std::vector<int>& apply, const int** dev, hipStream_t st, std::string* err);
+// correctPoses on the device for the slots flagged in apply_dev (lm_host_graph_apply)
+void launch_pg_apply(const LmCtx& L, const int* apply_dev, int n_slots, hipStream_t st);
+void launch_pg_retransform(const LmCtx& L, const int* apply_dev, int slot0, int n, int j, hipStream_t st);
+void launch_pg_sorted(const LmCtx& L, const int* apply_dev, int slot0, int n, int all, hipStream_t st);
 int graph_residuals_host(const double* poses12, int n_poses, const alego_graph_edge* edges, int n_edges, double* whitened6, double* jac_from36, double* jac_to36);
 #endif

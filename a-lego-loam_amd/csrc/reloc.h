@@ -1,0 +1,17 @@
+// reloc.h — host interface of relocalisation in the frozen map (kernels_reloc.hip; alego_reloc_* / alego_loc_relocalize)
+#ifndef ALEGO_RELOC_H_
+#define ALEGO_RELOC_H_
+#include "loop_ctx.h"   // LcCtx, LmCtx
+
+struct RlCtx;   // map / query descriptors (reloc_enable); search scratch allocated by the first search and kept
+int reloc_enable(RlCtx** pr, const LmCtx& L, int n_slots, double max_range, double z_offset, hipStream_t st, std::string* err);
+bool reloc_enabled(const RlCtx* R);
+int reloc_run(RlCtx* R, LcCtx** lc, const LmCtx& L, const alego_params& P, const int* slots, int n, int n_cand, int verify, int apply, alego_reloc_result* out,
+              hipStream_t st, std::string* err);
+int reloc_debug_search(RlCtx** pr, const uint8_t* map_desc, int n_map, const uint8_t* q_desc, int n_q, int n_cand, int32_t* ids, int32_t* dists, int32_t* shifts,
+                       hipStream_t st, std::string* err);
+int reloc_debug_get(RlCtx* R, int slot, const char* name, const void** src, size_t* bytes);
+void reloc_debug_stats(const RlCtx* R, int out[2]);
+void reloc_ctx_set(RlCtx** pr, int what, long long v);   // what 0: pairs per chunk of the search, 1: brute force
+void reloc_ctx_destroy(RlCtx* R);
+#endif

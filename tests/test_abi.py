@@ -54,6 +54,20 @@ def test_product_does_not_link_the_oracle():
                     assert "oracle_py" not in txt and "liboracle" not in txt and "from oracle" not in txt, os.path.join(sub, f)
 
 
+def test_device_memory_has_one_owner():
+    """Device memory is taken and returned in one place: csrc/dev_mem.h (DevPool, DevBuf) on top of csrc/guard_alloc.cpp.  No other file under
+    csrc/ names the runtime's allocator or the guard functions; guard_alloc.h, which declares the latter, names them and nothing else of these."""
+    csrc = os.path.join(ROOT, "a-lego-loam_amd", "csrc")
+    allowed = {"hipMalloc": {"guard_alloc.cpp"}, "hipFree": {"guard_alloc.cpp"},
+               "guard_malloc": {"guard_alloc.cpp", "guard_alloc.h", "dev_mem.h"}, "guard_free": {"guard_alloc.cpp", "guard_alloc.h", "dev_mem.h"}}
+    files = sorted(os.listdir(csrc))
+    assert "dev_mem.h" in files and "guard_alloc.cpp" in files
+    for f in files:
+        txt = open(os.path.join(csrc, f), errors="ignore").read()
+        for name, where in allowed.items():
+            assert name not in txt or f in where, f"{f} names {name}"
+
+
 def test_cpp_example_fails_loudly_without_a_gpu():
     """examples/replay.cpp drives the C ABI from plain C++.  In a container without an MI355X it must stop at alego_create with
     ALEGO_ERR_NO_DEVICE — there is no CPU fallback for the product path (on the GPU box tests/test_gpu_parity.py runs it for real)."""

@@ -1741,7 +1741,8 @@ def test_api_misuse_returns_error_codes(params_a):
 
 
 def test_allocation_guards_detect_a_stray_write():
-    """ALEGO_DEBUG_CANARY=1 frames every device allocation with guard pages; a write one int past an array is reported, a clean run
+    """ALEGO_DEBUG_CANARY=1 frames every device allocation with guard pages — what a handle keeps and the temporaries of single calls alike: all of
+    them come from csrc/dev_mem.h (tests/test_abi.py::test_device_memory_has_one_owner); a write one int past an array is reported, a clean run
     is not.  (The whole -m gpu suite was run once under the guards: no kernel writes outside its buffers.)"""
     import os, subprocess, sys
     code = (
@@ -1758,6 +1759,60 @@ def test_allocation_guards_detect_a_stray_write():
     env = dict(os.environ, ALEGO_DEBUG_CANARY="1")
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=300)
     assert "clean 0" in r.stdout and "poked 1" in r.stdout, (r.stdout, r.stderr[-500:])
+
+
+def test_call_temporaries_are_guarded_and_change_no_result():
+    """The entries that take device memory for one call — alego_debug_voxel, debug_nn1, the single-attempt loop-closure ICP, lm_apply_correction,
+    lo_push_imu, debug_reloc_search, alego_debug_eval_blocks, alego_debug_transform_to_start — at the sizes 0 and 1 that meet DevPool's 16-byte minimum
+    (and, for the VoxelGrid, above vox_small's 8192 points): with ALEGO_DEBUG_CANARY=1 their temporaries carry guard pages like every other block, no
+    guard is touched, and every result equals the result without the variable bit for bit."""
+    import os, subprocess, sys
+    code = (
+        "import sys; sys.path.insert(0, %r)\n"
+        "import hashlib\n"
+        "import numpy as np\n"
+        "from alego_loader import load_package; load_package()\n"
+        "from alego_amd import binding, synth\n"
+        "def show(tag, *arrs):\n"
+        "    for a in arrs:\n"
+        "        a = np.ascontiguousarray(a)\n"
+        "        print(tag, a.dtype, a.shape, hashlib.sha256(a.tobytes()).hexdigest())\n"
+        "p = synth.default_params(16, 1800)\n"
+        "h = binding.Handle(p)\n"
+        "rng = np.random.default_rng(7)\n"
+        "pts = rng.uniform(-20, 20, (9000, 4)).astype(np.float32)\n"
+        "one, none, pose = pts[:1], pts[:0], np.zeros(6, np.float32)\n"
+        "for n in (0, 1, 9000): show('voxel %%d' %% n, h.voxel_grid(pts[:n], 0.4))\n"
+        "show('nn1 1x1', *h.debug_nn1(one, pts[1:2]))\n"
+        "show('nn1 1x0', *h.debug_nn1(one, none))\n"
+        "for tag, frames in (('one point, no history', [(pose, one, none, none)]), ('empty newest frame', [(pose, none, none, none)]),\n"
+        "                    ('empty newest frame, one history point', [(pose, none, none, none), (pose, none, one, none)])):\n"
+        "    r, tgt = h.loop_closure_icp(frames)\n"
+        "    show('icp ' + tag, np.array([r['converged'], r['iterations'], r['n_source'], r['n_target']]), np.float64(r['fitness']), r['T'], tgt)\n"
+        "h.lm_apply_correction([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0])\n"
+        "show('lm_state', h.debug_get('lm_state'))\n"
+        "h.push_imu([[0.5, 1, 0, 0, 0, 0.1, -0.2, 9.9, 0, 0, 0]])\n"
+        "show('imu', h.debug_get('imu_ring'), h.debug_get('imu_ptr'))\n"
+        "d = rng.integers(0, 256, (2, binding.RELOC_SECTORS, binding.RELOC_RINGS)).astype(np.uint8)\n"
+        "show('reloc 1x1', *h.debug_reloc_search(d[:1], d[1:], 4))\n"
+        "g, q6 = rng.normal(size=(1, 13)), rng.normal(size=6) * 0.1\n"
+        "for t in range(4): show('eval_blocks %%d' %% t, *h.eval_blocks(t, g, q6))\n"
+        "show('transform_to_start', h.transform_to_start(q6, one))\n"
+        "print('damaged', binding.check_guards()[0])\n"
+        "h.close()\n"
+    ) % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = {}
+    for canary in (False, True):
+        env = dict(os.environ)
+        env.pop("ALEGO_DEBUG_CANARY", None)
+        if canary:
+            env["ALEGO_DEBUG_CANARY"] = "1"
+        r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=300)
+        assert r.returncode == 0, (canary, r.stdout[-2000:], r.stderr[-2000:])
+        lines = r.stdout.strip().splitlines()
+        assert lines[-1] == ("damaged 0" if canary else "damaged -1"), (canary, lines[-1], r.stderr[-800:])
+        out[canary] = lines[:-1]
+    assert len(out[True]) >= 30 and out[True] == out[False], [(a, b) for a, b in zip(out[False], out[True]) if a != b]
 
 
 def test_band_path_leaves_allocation_guards_intact():
