@@ -251,38 +251,25 @@ int alego_create(const alego_params* params, int device, int n_slots, int ring_l
   d.opt_fo_spin = env_int("ALEGO_FE_SPIN", 0);
   d.opt_fo_pad8 = env_int("ALEGO_FE_PAD8", 0) != 0;
   d.opt_map_merge = env_int("ALEGO_MAP_MERGE", 1) != 0;
+  d.fcap[F_SHARP] = d.cap_sharp * d.NS; d.fcap[F_LSHARP] = d.cap_lsharp * d.NS; d.fcap[F_FLAT] = d.cap_flat * d.NS; d.fcap[F_LFLAT] = d.N;
+  d.lo_qcap_surf = d.fcap[F_FLAT]; d.lo_qcap_corner = d.fcap[F_SHARP];
+  d.lo_box_cap = (d.N + LO_CH - 1) / LO_CH + d.NS;   // boxes never straddle rings: up to one partly filled box per ring
   const size_t B = n_slots, N = d.N, NS = d.NS;
   int rc = 0;
   rc |= dalloc(h, &d.in_pts, B * ring_len * d.Pcap, false);
   rc |= dalloc(h, &d.in_n, B * ring_len);
   rc |= dalloc(h, &d.owner, B * N); rc |= dalloc(h, &d.range_img, B * N); rc |= dalloc(h, &d.flag_img, B * N);
   rc |= dalloc(h, &d.parent, B * N); rc |= dalloc(h, &d.cc_size, B * N); rc |= dalloc(h, &d.cc_rows, B * N);
-  rc |= dalloc(h, &d.label_img, B * N); rc |= dalloc(h, &d.cc_label, B * N); rc |= dalloc(h, &d.row_cnt, B * NS * 4);
-  rc |= dalloc(h, &d.scal, B * SC_COUNT);
+  rc |= dalloc(h, &d.label_img, B * N); rc |= dalloc(h, &d.cc_label, B * N);
   d.ipb_col = nullptr; d.ipb_off = nullptr;
-  if (d.NS > 16 && d.NS <= 64) { rc |= dalloc(h, &d.ipb_col, B * IPB_NM * d.H); rc |= dalloc(h, &d.ipb_off, B * 3 * 64 * ((d.H + 63) / 64)); }   // the banded mask path (kernels_ipb.hip)
+  if (d.NS > 16 && d.NS <= 64) { rc |= dalloc(h, &d.ipb_col, B * ipb_col_n(d)); rc |= dalloc(h, &d.ipb_off, B * ipb_off_n(d)); }   // the banded mask path (kernels_ipb.hip)
   d.ipf_own = nullptr;
   if (d.NS <= 16 && d.N <= 65535 && (d.H & 1) == 0) rc |= dalloc(h, &d.ipf_own, B * (N / 2), false);
   rc |= dalloc(h, &d.seg_pts, B * N); rc |= dalloc(h, &d.seg_ground, B * N); rc |= dalloc(h, &d.seg_col, B * N);
-  rc |= dalloc(h, &d.seg_range, B * N); rc |= dalloc(h, &d.ring_start, B * NS); rc |= dalloc(h, &d.ring_end, B * NS);
-  rc |= dalloc(h, &d.ori, B * 4); rc |= dalloc(h, &d.outlier, B * N);
+  rc |= dalloc(h, &d.seg_range, B * N); rc |= dalloc(h, &d.outlier, B * N);
   rc |= dalloc(h, &d.cd, B * N); rc |= dalloc(h, &d.picked0, B * N); rc |= dalloc(h, &d.fe_flag, B * N); rc |= dalloc(h, &d.plabel, B * N);
-  rc |= dalloc(h, &d.st_idx, B * NS * d.st_stride); rc |= dalloc(h, &d.st_cnt, B * NS * 8);
-  rc |= dalloc(h, &d.st_lfds, B * NS * d.H);
-  d.fcap[F_SHARP] = d.cap_sharp * d.NS; d.fcap[F_LSHARP] = d.cap_lsharp * d.NS; d.fcap[F_FLAT] = d.cap_flat * d.NS; d.fcap[F_LFLAT] = d.N;
-  for (int k = 0; k < 4; ++k) rc |= dalloc(h, &d.feat[k], B * 2 * d.fcap[k]);
-  for (int k = 0; k < 3; ++k) rc |= dalloc(h, &d.feat_idx[k], B * 2 * d.fcap[k]);
-  rc |= dalloc(h, &d.feat_cnt, B * 2 * 4); rc |= dalloc(h, &d.ring_off, B * 2 * 2 * (NS + 1)); rc |= dalloc(h, &d.ring_boff, B * 2 * 2 * (NS + 1));
-  rc |= dalloc(h, &d.fe_sync, B * NS);
-  d.lo_qcap_surf = d.fcap[F_FLAT]; d.lo_qcap_corner = d.fcap[F_SHARP];
-  rc |= dalloc(h, &d.lo_corr, B * (d.lo_qcap_surf + d.lo_qcap_corner) * 4);
-  d.lo_box_cap = (d.N + LO_CH - 1) / LO_CH + d.NS;   // boxes never straddle rings: up to one partly filled box per ring
-  rc |= dalloc(h, &d.lo_box, B * 2 * 2 * d.lo_box_cap * 2);
-  rc |= dalloc(h, &d.lo_cpts[0], B * 2 * d.fcap[F_LFLAT], false); rc |= dalloc(h, &d.lo_cpts[1], B * 2 * d.fcap[F_LSHARP], false);
-  rc |= dalloc(h, &d.lo_cell, B * 2 * 2 * (LO_GC + 2)); rc |= dalloc(h, &d.lo_geom, B * 2 * 2 * 8);
-  rc |= dalloc(h, &d.lo_state, B * LO_STATE_N);
-  rc |= dalloc(h, &d.poses, B * 16);
-  rc |= dalloc(h, &d.imu_ring, B * ALEGO_IMU_Q * 10); rc |= dalloc(h, &d.imu_ptr, B * 4); rc |= dalloc(h, &d.scan_stamp, B);
+  rc |= fe_store_alloc(d, B, [&](auto** p, size_t n, bool zero) { return dalloc(h, p, n, zero); });   // the structured arrays (fe_store.h)
+  rc |= dalloc(h, &d.scan_stamp, B);
   rc |= dalloc(h, &d.seg_dsk, h->P.deskew_mode ? B * N : 1);
   {  // boundary tables of ip_project's fast path (kernels_ip.hip)
     const double rx = params->ang_res_x, ry = params->ang_res_y;
@@ -320,20 +307,22 @@ int alego_create(const alego_params* params, int device, int n_slots, int ring_l
   }
   if (rc) { *out = h; int e = ALEGO_ERR_HIP; std::fprintf(stderr, "alego_create: %s\n", h->err.c_str()); alego_destroy(h); *out = nullptr; return e; }
   // r_w_cur_ = identity, pose quaternions = identity (laserOdometry.cpp:46-47)
-  std::vector<double> st(B * LO_STATE_N, 0.0), po(B * 16, 0.0);
-  for (size_t b = 0; b < B; ++b) {
-    st[b * LO_STATE_N + LS_RW + 0] = st[b * LO_STATE_N + LS_RW + 4] = st[b * LO_STATE_N + LS_RW + 8] = 1.0;
-    for (int k = 0; k < 6; ++k) st[b * LO_STATE_N + LS_ROT_P + k] = std::nan("");  // no cached rotation yet
-    po[b * 16 + 3] = 1.0; po[b * 16 + 10] = 1.0;
-  }
-  std::vector<int> sc0(B * SC_COUNT, 0);
-  for (size_t b = 0; b < B; ++b) {
-    sc0[b * SC_COUNT + SC_CUR] = 1;  // the first scan writes feature buffer 0
-    sc0[b * SC_COUNT + SC_FIRST] = 0x7fffffff; sc0[b * SC_COUNT + SC_LAST] = -1;   // accumulators of ip_project, re-armed by ip_front
+  // (host images of the arrays, rows taken by the accessors of a context whose arrays are these vectors)
+  std::vector<double> st(B * lo_state_n(), 0.0), po(B * PO_W, 0.0);
+  std::vector<int> sc0(B * scal_n(), 0), ip0(B * IMP_W, 0);
+  DevCtx hd = d;
+  hd.lo_state = st.data(); hd.poses = po.data(); hd.scal = sc0.data(); hd.imu_ptr = ip0.data();
+  for (int b = 0; b < n_slots; ++b) {
+    double* s = lo_state_of(hd, b);
+    s[LS_RW + 0] = s[LS_RW + 4] = s[LS_RW + 8] = 1.0;
+    for (int k = 0; k < 6; ++k) s[LS_ROT_P + k] = std::nan("");  // no cached rotation yet
+    poses_of(hd, b)[PO_ODOM_Q] = 1.0; poses_of(hd, b)[PO_MAP_Q] = 1.0;
+    int* sc = scal_of(hd, b);
+    sc[SC_CUR] = 1;  // the first scan writes feature buffer 0
+    sc[SC_FIRST] = 0x7fffffff; sc[SC_LAST] = -1;   // accumulators of ip_project, re-armed by ip_front
+    imu_ptr_of(hd, b)[IMP_LAST] = -1;   // imu_ptr_last_ = -1, imu_ptr_front_ = imu_ptr_last_iter_ = 0 (laserOdometry.cpp:17-19)
   }
   d.seg_lo = h->P.deskew_mode ? d.seg_dsk : d.seg_pts;
-  std::vector<int> ip0(B * 4, 0);
-  for (size_t b = 0; b < B; ++b) ip0[b * 4] = -1;   // imu_ptr_last_ = -1, imu_ptr_front_ = imu_ptr_last_iter_ = 0 (laserOdometry.cpp:17-19)
   if (hipMemcpy(d.imu_ptr, ip0.data(), ip0.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) { std::fprintf(stderr, "alego_create: initial state upload failed\n"); alego_destroy(h); return ALEGO_ERR_HIP; }
   h->imu_last_stamp.assign(B, -1e300);
   if (hipMemcpy(d.scal, sc0.data(), sc0.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
@@ -556,23 +545,23 @@ int alego_batch_run(alego_handle* h, int first_pos, int n_scans, int stages, int
 }
 
 static int fetch_pose(alego_handle* h, int slot, alego_pose* odom, alego_pose* map_pose) {
-  double po[16], st[LO_STATE_N];
+  double po[PO_W], st[LO_STATE_N];
   int sc[SC_COUNT];
   const int pslot = (h->stream_mode && slot == 0) ? h->pose_slot : slot;   // alego_stream_run: the last scan's poses live in its lane
   if (h->stream_mode) HIP_TRY(h, sync_all(h));
-  HIP_TRY(h, hipMemcpyAsync(po, h->d.poses + (size_t)pslot * 16, sizeof(po), hipMemcpyDeviceToHost, stream_of(h, slot)));
-  HIP_TRY(h, hipMemcpyAsync(st, h->d.lo_state + (size_t)slot * LO_STATE_N, sizeof(st), hipMemcpyDeviceToHost, stream_of(h, slot)));
-  HIP_TRY(h, hipMemcpyAsync(sc, h->d.scal + (size_t)slot * SC_COUNT, sizeof(sc), hipMemcpyDeviceToHost, stream_of(h, slot)));
+  HIP_TRY(h, hipMemcpyAsync(po, poses_of(h->d, pslot), sizeof(po), hipMemcpyDeviceToHost, stream_of(h, slot)));
+  HIP_TRY(h, hipMemcpyAsync(st, lo_state_of(h->d, slot), sizeof(st), hipMemcpyDeviceToHost, stream_of(h, slot)));
+  HIP_TRY(h, hipMemcpyAsync(sc, scal_of(h->d, slot), sizeof(sc), hipMemcpyDeviceToHost, stream_of(h, slot)));
   HIP_TRY(h, hipStreamSynchronize(stream_of(h, slot)));
   if (odom) {
-    for (int i = 0; i < 3; ++i) odom->t[i] = po[i];
-    for (int i = 0; i < 4; ++i) odom->q[i] = po[3 + i];
+    for (int i = 0; i < 3; ++i) odom->t[i] = po[PO_ODOM_T + i];
+    for (int i = 0; i < 4; ++i) odom->q[i] = po[PO_ODOM_Q + i];
     for (int i = 0; i < 6; ++i) odom->params[i] = st[LS_PARAMS + i];
     odom->valid = sc[SC_ODOM_VALID];
   }
   if (map_pose) {
-    for (int i = 0; i < 3; ++i) map_pose->t[i] = po[7 + i];
-    for (int i = 0; i < 4; ++i) map_pose->q[i] = po[10 + i];
+    for (int i = 0; i < 3; ++i) map_pose->t[i] = po[PO_MAP_T + i];
+    for (int i = 0; i < 4; ++i) map_pose->q[i] = po[PO_MAP_Q + i];
     lm_host_get_params(h->lm, slot, map_pose->params);
     map_pose->valid = sc[SC_ODOM_VALID];
   }
@@ -596,7 +585,7 @@ int alego_trajectory_enable(alego_handle* h, int32_t capacity_scans) {
   HIP_TRY(h, sync_all(h));
   double* t = nullptr;
   int* n = nullptr;
-  if (dalloc(h, &t, (size_t)h->d.n_slots * capacity_scans * 14) || dalloc(h, &n, (size_t)h->d.n_slots)) return ALEGO_ERR_HIP;
+  if (dalloc(h, &t, (size_t)h->d.n_slots * capacity_scans * PO_LOG_W) || dalloc(h, &n, (size_t)h->d.n_slots)) return ALEGO_ERR_HIP;
   h->d.traj = t; h->d.traj_n = n; h->d.traj_cap = capacity_scans;
   return 0;
 }
@@ -606,12 +595,12 @@ int alego_trajectory_get(alego_handle* h, int slot, int32_t first, int32_t n, do
   hipSetDevice(h->device);
   hipStream_t S = stream_of(h, slot);
   int logged = 0;
-  HIP_TRY(h, hipMemcpyAsync(&logged, h->d.traj_n + slot, sizeof(int), hipMemcpyDeviceToHost, S));
+  HIP_TRY(h, hipMemcpyAsync(&logged, traj_n_of(h->d, slot), sizeof(int), hipMemcpyDeviceToHost, S));
   HIP_TRY(h, hipStreamSynchronize(S));
   const int have = std::min(logged, h->d.traj_cap);
   if (first > have || n > have - first) { h->err = "alego_trajectory_get: range beyond the scans logged"; return ALEGO_ERR_ARG; }   // (not first + n: it overflows for large arguments)
   if (n > 0) {
-    HIP_TRY(h, hipMemcpyAsync(out14, h->d.traj + ((size_t)slot * h->d.traj_cap + first) * 14, (size_t)n * 14 * sizeof(double), hipMemcpyDeviceToHost, S));
+    HIP_TRY(h, hipMemcpyAsync(out14, traj_of(h->d, slot, first), (size_t)n * PO_LOG_W * sizeof(double), hipMemcpyDeviceToHost, S));
     HIP_TRY(h, hipStreamSynchronize(S));
   }
   return logged;
@@ -620,17 +609,17 @@ int alego_trajectory_get(alego_handle* h, int slot, int32_t first, int32_t n, do
 int alego_batch_get_counts(alego_handle* h, int slot, int32_t* out, int cap) {
   if (int r = check_slot(h, slot)) return r;
   hipSetDevice(h->device);
-  int sc[SC_COUNT], fc[8], sl[SC_COUNT];
+  int sc[SC_COUNT], fc[F_KINDS], sl[SC_COUNT];
   const bool lane = h->stream_mode && slot == 0;   // alego_stream_run: the per-scan counters of the last scan live in its lane (buffer 0)
   const int cslot = lane ? h->pose_slot : slot;
   if (lane) HIP_TRY(h, sync_all(h));
-  HIP_TRY(h, hipMemcpyAsync(sc, h->d.scal + (size_t)cslot * SC_COUNT, sizeof(sc), hipMemcpyDeviceToHost, stream_of(h, slot)));
-  HIP_TRY(h, hipMemcpyAsync(sl, h->d.scal + (size_t)slot * SC_COUNT, sizeof(sl), hipMemcpyDeviceToHost, stream_of(h, slot)));
-  HIP_TRY(h, hipMemcpyAsync(fc, h->d.feat_cnt + (size_t)cslot * 8, sizeof(fc), hipMemcpyDeviceToHost, stream_of(h, slot)));
+  HIP_TRY(h, hipMemcpyAsync(sc, scal_of(h->d, cslot), sizeof(sc), hipMemcpyDeviceToHost, stream_of(h, slot)));
+  HIP_TRY(h, hipMemcpyAsync(sl, scal_of(h->d, slot), sizeof(sl), hipMemcpyDeviceToHost, stream_of(h, slot)));
   HIP_TRY(h, hipStreamSynchronize(stream_of(h, slot)));
-  sc[SC_LO_NSURF] = sl[SC_LO_NSURF]; sc[SC_LO_NCORNER] = sl[SC_LO_NCORNER];   // LaserOdometry's counters belong to the stream's own slot
   const int cur = lane ? 0 : sc[SC_CUR];  // buffer written by the last processed scan
-  int v[16] = {sc[SC_PVALID_OUT], sc[SC_M], sc[SC_NOUT], fc[cur * 4 + 0], fc[cur * 4 + 1], fc[cur * 4 + 2], fc[cur * 4 + 3],
+  HIP_TRY(h, hipMemcpy(fc, feat_cnt_of(h->d, fbuf(cslot, cur)), sizeof(fc), hipMemcpyDeviceToHost));
+  sc[SC_LO_NSURF] = sl[SC_LO_NSURF]; sc[SC_LO_NCORNER] = sl[SC_LO_NCORNER];   // LaserOdometry's counters belong to the stream's own slot
+  int v[16] = {sc[SC_PVALID_OUT], sc[SC_M], sc[SC_NOUT], fc[F_SHARP], fc[F_LSHARP], fc[F_FLAT], fc[F_LFLAT],
                sc[SC_LO_NSURF], sc[SC_LO_NCORNER], 0, 0, 0, 0, 0, 0, 0};  // v[15] = map rebuilds so far
   lm_host_get_counts(h->lm, slot, v + 9);
   for (int i = 0; i < cap && i < 16; ++i) out[i] = v[i];
@@ -640,7 +629,7 @@ int alego_batch_get_counts(alego_handle* h, int slot, int32_t* out, int cap) {
 static int download_seg(alego_handle* h, int slot, alego_seg_out* out) {
   const DevCtx& d = h->d;
   int sc[SC_COUNT];
-  HIP_TRY(h, hipMemcpyAsync(sc, d.scal + (size_t)slot * SC_COUNT, sizeof(sc), hipMemcpyDeviceToHost, stream_of(h, slot)));
+  HIP_TRY(h, hipMemcpyAsync(sc, scal_of(d, slot), sizeof(sc), hipMemcpyDeviceToHost, stream_of(h, slot)));
   HIP_TRY(h, hipStreamSynchronize(stream_of(h, slot)));
   const int M = sc[SC_M], NO = sc[SC_NOUT];
   out->m = M; out->n_outlier = NO;
@@ -650,9 +639,9 @@ static int download_seg(alego_handle* h, int slot, alego_seg_out* out) {
   if (out->ground) HIP_TRY(h, hipMemcpyAsync(out->ground, d.seg_ground + base, (size_t)M, hipMemcpyDeviceToHost, stream_of(h, slot)));
   if (out->col) HIP_TRY(h, hipMemcpyAsync(out->col, d.seg_col + base, (size_t)M * 4, hipMemcpyDeviceToHost, stream_of(h, slot)));
   if (out->range) HIP_TRY(h, hipMemcpyAsync(out->range, d.seg_range + base, (size_t)M * 4, hipMemcpyDeviceToHost, stream_of(h, slot)));
-  if (out->ring_start) HIP_TRY(h, hipMemcpyAsync(out->ring_start, d.ring_start + (size_t)slot * d.NS, d.NS * 4, hipMemcpyDeviceToHost, stream_of(h, slot)));
-  if (out->ring_end) HIP_TRY(h, hipMemcpyAsync(out->ring_end, d.ring_end + (size_t)slot * d.NS, d.NS * 4, hipMemcpyDeviceToHost, stream_of(h, slot)));
-  HIP_TRY(h, hipMemcpyAsync(out->orientation, d.ori + (size_t)slot * 4, 12, hipMemcpyDeviceToHost, stream_of(h, slot)));
+  if (out->ring_start) HIP_TRY(h, hipMemcpyAsync(out->ring_start, ring_start_of(d, slot, 0), d.NS * 4, hipMemcpyDeviceToHost, stream_of(h, slot)));
+  if (out->ring_end) HIP_TRY(h, hipMemcpyAsync(out->ring_end, ring_end_of(d, slot, 0), d.NS * 4, hipMemcpyDeviceToHost, stream_of(h, slot)));
+  HIP_TRY(h, hipMemcpyAsync(out->orientation, ori_of(d, slot), ORI_N * 4, hipMemcpyDeviceToHost, stream_of(h, slot)));
   if (out->outlier) HIP_TRY(h, hipMemcpyAsync(out->outlier, d.outlier + base, (size_t)NO * 16, hipMemcpyDeviceToHost, stream_of(h, slot)));
   if (out->label_image) HIP_TRY(h, hipMemcpyAsync(out->label_image, d.label_img + base, (size_t)d.N * 4, hipMemcpyDeviceToHost, stream_of(h, slot)));
   HIP_TRY(h, hipStreamSynchronize(stream_of(h, slot)));
@@ -661,16 +650,16 @@ static int download_seg(alego_handle* h, int slot, alego_seg_out* out) {
 
 static int download_feat(alego_handle* h, int slot, alego_feat_out* f) {
   const DevCtx& d = h->d;
-  int fc[4], M, cur;
-  HIP_TRY(h, hipMemcpy(&cur, d.scal + (size_t)slot * SC_COUNT + SC_CUR, 4, hipMemcpyDeviceToHost));
-  HIP_TRY(h, hipMemcpyAsync(fc, d.feat_cnt + ((size_t)slot * 2 + cur) * 4, sizeof(fc), hipMemcpyDeviceToHost, stream_of(h, slot)));
-  HIP_TRY(h, hipMemcpyAsync(&M, d.scal + (size_t)slot * SC_COUNT + SC_M, 4, hipMemcpyDeviceToHost, stream_of(h, slot)));
+  int fc[F_KINDS], M, cur;
+  HIP_TRY(h, hipMemcpy(&cur, scal_of(d, slot) + SC_CUR, 4, hipMemcpyDeviceToHost));
+  HIP_TRY(h, hipMemcpyAsync(fc, feat_cnt_of(d, fbuf(slot, cur)), sizeof(fc), hipMemcpyDeviceToHost, stream_of(h, slot)));
+  HIP_TRY(h, hipMemcpyAsync(&M, scal_of(d, slot) + SC_M, 4, hipMemcpyDeviceToHost, stream_of(h, slot)));
   HIP_TRY(h, hipStreamSynchronize(stream_of(h, slot)));
-  f->n_sharp = fc[0]; f->n_less_sharp = fc[1]; f->n_flat = fc[2]; f->n_less_flat = fc[3];
-  if (fc[0] > f->sharp_cap || fc[1] > f->less_sharp_cap || fc[2] > f->flat_cap || fc[3] > f->less_flat_cap) { h->err = "feature capacity too small"; return ALEGO_ERR_CAPACITY; }
-  alego_point* dst[4] = {f->sharp, f->less_sharp, f->flat, f->less_flat};
-  for (int k = 0; k < 4; ++k)
-    if (dst[k]) HIP_TRY(h, hipMemcpyAsync(dst[k], d.feat[k] + ((size_t)slot * 2 + cur) * d.fcap[k], (size_t)fc[k] * 16, hipMemcpyDeviceToHost, stream_of(h, slot)));
+  f->n_sharp = fc[F_SHARP]; f->n_less_sharp = fc[F_LSHARP]; f->n_flat = fc[F_FLAT]; f->n_less_flat = fc[F_LFLAT];
+  if (fc[F_SHARP] > f->sharp_cap || fc[F_LSHARP] > f->less_sharp_cap || fc[F_FLAT] > f->flat_cap || fc[F_LFLAT] > f->less_flat_cap) { h->err = "feature capacity too small"; return ALEGO_ERR_CAPACITY; }
+  alego_point* dst[F_KINDS] = {f->sharp, f->less_sharp, f->flat, f->less_flat};
+  for (int k = 0; k < F_KINDS; ++k)
+    if (dst[k]) HIP_TRY(h, hipMemcpyAsync(dst[k], feat_of(d, k, fbuf(slot, cur)), (size_t)fc[k] * 16, hipMemcpyDeviceToHost, stream_of(h, slot)));
   if (f->point_label) HIP_TRY(h, hipMemcpyAsync(f->point_label, d.plabel + (size_t)slot * d.N, (size_t)M * 4, hipMemcpyDeviceToHost, stream_of(h, slot)));
   HIP_TRY(h, hipStreamSynchronize(stream_of(h, slot)));
   return 0;
@@ -693,6 +682,7 @@ int alego_lo_process(alego_handle* h, const alego_seg_out* in, alego_feat_out* f
   hipSetDevice(h->device);
   drain_back(h);
   const DevCtx& d = h->d;
+  const int slot = 0;   // the single-scan entry points work on slot 0
   if (in->m < 0 || in->m > d.N) { h->err = "segmented cloud larger than n_scan*horizon_scan"; return ALEGO_ERR_CAPACITY; }
   if (!in->ring_start || !in->ring_end || (in->m > 0 && (!in->seg || !in->ground || !in->col || !in->range))) { h->err = "alego_lo_process: null input array"; return ALEGO_ERR_ARG; }
   const size_t M = in->m;
@@ -700,11 +690,11 @@ int alego_lo_process(alego_handle* h, const alego_seg_out* in, alego_feat_out* f
   HIP_TRY(h, hipMemcpyAsync(d.seg_ground, in->ground, M, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipMemcpyAsync(d.seg_col, in->col, M * 4, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipMemcpyAsync(d.seg_range, in->range, M * 4, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(d.ring_start, in->ring_start, d.NS * 4, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(d.ring_end, in->ring_end, d.NS * 4, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(d.scal + SC_M, &in->m, 4, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(d.ori, in->orientation, 12, hipMemcpyHostToDevice, h->stream));       // seg_info's start / end orientation: adjustDistortion reads them
-  HIP_TRY(h, hipMemcpyAsync(d.scan_stamp, &in->stamp, 8, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(ring_start_of(d, slot, 0), in->ring_start, d.NS * 4, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(ring_end_of(d, slot, 0), in->ring_end, d.NS * 4, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(scal_of(d, slot) + SC_M, &in->m, 4, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(ori_of(d, slot), in->orientation, ORI_N * 4, hipMemcpyHostToDevice, h->stream));       // seg_info's start / end orientation: adjustDistortion reads them
+  HIP_TRY(h, hipMemcpyAsync(d.scan_stamp + slot, &in->stamp, 8, hipMemcpyHostToDevice, h->stream));
   if (h->map_on && lm_host_map_mark_stamped(h->lm, 0, h->stream)) { h->err = "alego_lo_process: upload failed"; return ALEGO_ERR_HIP; }
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   if (int r = enqueue_scan(h, 0, 1, 0, 2, false)) return r;
@@ -740,7 +730,7 @@ int alego_scan_process(alego_handle* h, int slot, const alego_scan_in* in, int s
 int alego_set_lo_params(alego_handle* h, int slot, const double* p6) {
   if (int r = check_slot(h, slot)) return r;
   hipSetDevice(h->device);
-  HIP_TRY(h, hipMemcpyAsync(h->d.lo_state + (size_t)slot * LO_STATE_N + LS_PARAMS, p6, 48, hipMemcpyHostToDevice, stream_of(h, slot)));
+  HIP_TRY(h, hipMemcpyAsync(lo_state_of(h->d, slot) + LS_PARAMS, p6, 48, hipMemcpyHostToDevice, stream_of(h, slot)));
   HIP_TRY(h, hipStreamSynchronize(stream_of(h, slot)));
   return 0;
 }
@@ -757,7 +747,7 @@ int alego_lo_get_undistorted(alego_handle* h, int slot, alego_point* out, int32_
   if (cap < 0 || (cap > 0 && !out)) return ALEGO_ERR_ARG;
   hipSetDevice(h->device);
   int M = 0;
-  HIP_TRY(h, hipMemcpyAsync(&M, h->d.scal + (size_t)slot * SC_COUNT + SC_M_DSK, 4, hipMemcpyDeviceToHost, stream_of(h, slot)));   // lo_deskew's own count, not SC_M
+  HIP_TRY(h, hipMemcpyAsync(&M, scal_of(h->d, slot) + SC_M_DSK, 4, hipMemcpyDeviceToHost, stream_of(h, slot)));   // lo_deskew's own count, not SC_M
   HIP_TRY(h, hipStreamSynchronize(stream_of(h, slot)));
   if (M > cap) return ALEGO_ERR_CAPACITY;
   if (M > 0) HIP_TRY(h, hipMemcpy(out, h->d.seg_dsk + (size_t)slot * h->d.N, (size_t)M * sizeof(alego_point), hipMemcpyDeviceToHost));
@@ -1016,12 +1006,12 @@ int alego_debug_set_option(alego_handle* h, const char* name, int value) {
   else if (s == "ALEGO_FE_ERR_CLEAR") {   // the per-slot reset of the sticky SC_FE_ERR (dev_common.h): value = slot, -1 = every slot; the caller has drained the handle's streams
     if (value < -1 || value >= d.n_slots) return ALEGO_ERR_ARG;
     HIP_TRY(h, hipDeviceSynchronize());
-    if (value >= 0) HIP_TRY(h, hipMemset(d.scal + (size_t)value * SC_COUNT + SC_FE_ERR, 0, 4));
-    else HIP_TRY(h, hipMemset2D(d.scal + SC_FE_ERR, SC_COUNT * sizeof(int), 0, 4, d.n_slots));
+    if (value >= 0) HIP_TRY(h, hipMemset(scal_of(d, value) + SC_FE_ERR, 0, 4));
+    else HIP_TRY(h, hipMemset2D(scal_of(d, 0) + SC_FE_ERR, scal_n() * sizeof(int), 0, 4, d.n_slots));
   }
   else if (s == "ALEGO_MAP_MERGE") { if (int r = lm_host_set_map_merge(h->lm, value != 0, &h->err)) return r; d.opt_map_merge = value != 0; }
   else if (s == "ALEGO_IP_FAST") d.ip_fast = h->ip_fast_capable & value;
-  else if (s == "ALEGO_POKE_GUARD") { HIP_TRY(h, hipMemset(d.scal + (size_t)d.n_slots * SC_COUNT + value, 0xFF, 4)); }   // tests of the guard pages: a write `value` ints past the end of an array
+  else if (s == "ALEGO_POKE_GUARD") { HIP_TRY(h, hipMemset(scal_of(d, d.n_slots) + value, 0xFF, 4)); }   // tests of the guard pages: a write `value` ints past the end of an array
   else if (s == "ALEGO_GV_SMALL_MAX") { HIP_TRY(h, sync_all(h)); return lm_host_set_gv_small_max(h->lm, value); }   // tools/gmap_timing.py: largest cloud alego_voxel_grid gives to one workgroup
   else if (s == "ALEGO_PG_BUDGET") graph_ctx_set_budget(&h->pg, value);   // tests / tools: bytes of scratch per chunk of alego_graph_optimize
   else if (s == "ALEGO_LC_BUDGET") loop_ctx_set_budget(&h->lc, value);   // tests / tools: raw sub-map points per chunk of alego_loop_search
@@ -1428,7 +1418,7 @@ int alego_debug_get(alego_handle* h, int slot, const char* name, void* out, int 
   hipSetDevice(h->device);
   const DevCtx& d = h->d;
   int sc[SC_COUNT];
-  HIP_TRY(h, hipMemcpyAsync(sc, d.scal + (size_t)slot * SC_COUNT, sizeof(sc), hipMemcpyDeviceToHost, stream_of(h, slot)));
+  HIP_TRY(h, hipMemcpyAsync(sc, scal_of(d, slot), sizeof(sc), hipMemcpyDeviceToHost, stream_of(h, slot)));
   HIP_TRY(h, hipStreamSynchronize(stream_of(h, slot)));
   const std::string s(name);
   if (s.rfind("rl_", 0) == 0) {   // relocalisation: descriptors as bytes; "rl_stats": pairs evaluated by the second round / pairs in all of the last search
@@ -1446,47 +1436,34 @@ int alego_debug_get(alego_handle* h, int slot, const char* name, void* out, int 
     *count = (int)bytes; *dtype = 3;
     return 0;
   }
-  const size_t base = (size_t)slot * d.N;
-  const int M = sc[SC_M];
-  const int cur = sc[SC_CUR];  // buffer written by the last processed scan
-  int fc[8];
-  HIP_TRY(h, hipMemcpy(fc, d.feat_cnt + (size_t)slot * 8, sizeof(fc), hipMemcpyDeviceToHost));
-  const void* src = nullptr;
-  size_t n = 0;
-  int dt = 0, esz = 4;
-  auto set = [&](const void* p, size_t cnt, int t) { src = p; n = cnt; dt = t; esz = t == 1 ? 8 : t == 3 ? 1 : 4; };
-  if (s == "range_img") set(d.range_img + base, d.N, 0);
-  else if (s == "label_img") set(d.label_img + base, d.N, 2);
-  else if (s == "flag_img") set(d.flag_img + base, d.N, 3);
-  else if (s == "owner") set(d.owner + base, d.N, 2);
-  else if (s == "parent") set(d.parent + base, d.N, 2);
-  else if (s == "seg_cloud") set(d.seg_pts + base, (size_t)M * 4, 0);
-  else if (s == "outlier") set(d.outlier + base, (size_t)sc[SC_NOUT] * 4, 0);
-  else if (s == "undistorted" && d.P.deskew_mode) set(d.seg_dsk + base, (size_t)sc[SC_M_DSK] * 4, 0);
-  else if (s == "imu_ptr") set(d.imu_ptr + (size_t)slot * 4, 3, 2);
-  else if (s == "imu_ring") set(d.imu_ring + (size_t)slot * ALEGO_IMU_Q * 10, ALEGO_IMU_Q * 10, 1);
-  else if (s == "seg_ground") set(d.seg_ground + base, M, 3);
-  else if (s == "seg_col") set(d.seg_col + base, M, 2);
-  else if (s == "seg_range") set(d.seg_range + base, M, 0);
-  else if (s == "ring_start") set(d.ring_start + (size_t)slot * d.NS, d.NS, 2);
-  else if (s == "ring_end") set(d.ring_end + (size_t)slot * d.NS, d.NS, 2);
-  else if (s == "orientation") set(d.ori + (size_t)slot * 4, 3, 0);
-  else if (s == "scal") set(d.scal + (size_t)slot * SC_COUNT, SC_COUNT, 2);
-  else if (s == "curv_d") set(d.cd + base, M, 0);
-  else if (s == "picked_occl") set(d.picked0 + base, M, 3);
-  else if (s == "point_label") set(d.plabel + base, M, 2);
-  else if (s == "sharp") set(d.feat[0] + ((size_t)slot * 2 + cur) * d.fcap[0], (size_t)fc[cur * 4 + 0] * 4, 0);
-  else if (s == "less_sharp") set(d.feat[1] + ((size_t)slot * 2 + cur) * d.fcap[1], (size_t)fc[cur * 4 + 1] * 4, 0);
-  else if (s == "flat") set(d.feat[2] + ((size_t)slot * 2 + cur) * d.fcap[2], (size_t)fc[cur * 4 + 2] * 4, 0);
-  else if (s == "less_flat") set(d.feat[3] + ((size_t)slot * 2 + cur) * d.fcap[3], (size_t)fc[cur * 4 + 3] * 4, 0);
-  else if (s == "sharp_idx") set(d.feat_idx[0] + ((size_t)slot * 2 + cur) * d.fcap[0], fc[cur * 4 + 0], 2);
-  else if (s == "less_sharp_idx") set(d.feat_idx[1] + ((size_t)slot * 2 + cur) * d.fcap[1], fc[cur * 4 + 1], 2);
-  else if (s == "flat_idx") set(d.feat_idx[2] + ((size_t)slot * 2 + cur) * d.fcap[2], fc[cur * 4 + 2], 2);
-  else if (s == "lo_surf_corr") set(d.lo_corr + (size_t)slot * (d.lo_qcap_surf + d.lo_qcap_corner) * 4, (size_t)fc[cur * 4 + 2] * 4, 2);
-  else if (s == "lo_corner_corr") set(d.lo_corr + ((size_t)slot * (d.lo_qcap_surf + d.lo_qcap_corner) + d.lo_qcap_surf) * 4, (size_t)fc[cur * 4 + 0] * 4, 2);
-  else if (s == "lo_state") set(d.lo_state + (size_t)slot * LO_STATE_N, LO_STATE_N, 1);
-  else if (s == "poses") set(d.poses + (size_t)slot * 16, 16, 1);
-  else return lm_host_debug_get(h->lm, slot, name, out, cap_bytes, count, dtype, &h->err);
+  const size_t base = (size_t)slot * d.N, M = sc[SC_M];
+  const size_t fb = fbuf(slot, sc[SC_CUR]);  // buffer written by the last processed scan
+  int fc[F_KINDS];
+  HIP_TRY(h, hipMemcpy(fc, feat_cnt_of(d, fb), sizeof(fc), hipMemcpyDeviceToHost));
+  static const char* const cloud[F_KINDS] = {"sharp", "less_sharp", "flat", "less_flat"};
+  struct Row { std::string name; const void* row; size_t n; int dtype; };   // dtype 0: f32, 1: f64, 2: i32, 3: u8
+  std::vector<Row> tab = {
+    {"range_img", d.range_img + base, (size_t)d.N, 0}, {"label_img", d.label_img + base, (size_t)d.N, 2}, {"flag_img", d.flag_img + base, (size_t)d.N, 3},
+    {"owner", d.owner + base, (size_t)d.N, 2}, {"parent", d.parent + base, (size_t)d.N, 2},
+    {"seg_cloud", d.seg_pts + base, M * 4, 0}, {"outlier", d.outlier + base, (size_t)sc[SC_NOUT] * 4, 0},
+    {"imu_ptr", imu_ptr_of(d, slot), IMP_N, 2}, {"imu_ring", imu_ring_of(d, slot), imu_ring_n(), 1},
+    {"seg_ground", d.seg_ground + base, M, 3}, {"seg_col", d.seg_col + base, M, 2}, {"seg_range", d.seg_range + base, M, 0},
+    {"ring_start", ring_start_of(d, slot, 0), (size_t)d.NS, 2}, {"ring_end", ring_end_of(d, slot, 0), (size_t)d.NS, 2},
+    {"orientation", ori_of(d, slot), ORI_N, 0}, {"scal", scal_of(d, slot), SC_COUNT, 2},
+    {"curv_d", d.cd + base, M, 0}, {"picked_occl", d.picked0 + base, M, 3}, {"point_label", d.plabel + base, M, 2},
+    {"lo_surf_corr", lo_corr_of(d, slot, 0), (size_t)fc[F_FLAT] * LC_W, 2}, {"lo_corner_corr", lo_corr_of(d, slot, 1), (size_t)fc[F_SHARP] * LC_W, 2},
+    {"lo_state", lo_state_of(d, slot), LO_STATE_N, 1}, {"poses", poses_of(d, slot), PO_W, 1}};
+  if (d.P.deskew_mode) tab.push_back({"undistorted", d.seg_dsk + base, (size_t)sc[SC_M_DSK] * 4, 0});
+  for (int k = 0; k < F_KINDS; ++k) {
+    tab.push_back({cloud[k], feat_of(d, k, fb), (size_t)fc[k] * 4, 0});
+    if (k < F_LFLAT) tab.push_back({std::string(cloud[k]) + "_idx", feat_idx_of(d, k, fb), (size_t)fc[k], 2});
+  }
+  const Row* hit = nullptr;
+  for (const Row& r : tab) if (r.name == s) hit = &r;
+  if (!hit) return lm_host_debug_get(h->lm, slot, name, out, cap_bytes, count, dtype, &h->err);
+  const void* src = hit->row;
+  const size_t n = hit->n, esz = hit->dtype == 1 ? 8 : hit->dtype == 3 ? 1 : 4;
+  const int dt = hit->dtype;
   if ((size_t)cap_bytes < n * esz) { h->err = "debug_get: buffer too small"; return ALEGO_ERR_CAPACITY; }
   if (n) HIP_TRY(h, hipMemcpy(out, src, n * esz, hipMemcpyDeviceToHost));
   *count = (int)n; *dtype = dt;

@@ -1,7 +1,8 @@
 // dev_common.h — device-side view of one handle's HBM-resident state.
 //
 // Every per-scan array is laid out [slot][capacity] (slot = independent stream),
-// so one launch with blockIdx.y = slot advances all streams together.
+// so one launch with blockIdx.y = slot advances all streams together.  The [slot][...] comments of the
+// structured arrays are documentation: fe_store.h defines those layouts, and only it indexes them.
 #ifndef ALEGO_DEV_COMMON_H_
 #define ALEGO_DEV_COMMON_H_
 
@@ -11,41 +12,8 @@
 #include "../../include/alego_params.h"
 #include "wave.h"
 
-// per-slot integer scalars (DevCtx::scal, stride SC_COUNT)
-enum {
-  SC_FIRST = 0,   // smallest index of a valid input point (orientation, imageProjection.cpp:62)
-  SC_LAST,        // largest index of a valid input point
-  SC_PVALID,      // valid input points
-  SC_M,           // segmented cloud size
-  SC_NOUT,        // outlier cloud size
-  SC_NFEAS,       // feasible segments (label_cnt_-1)
-  SC_LO_INIT,     // system_initialized_ (laserOdometry.cpp:36)
-  SC_LO_NSURF,    // surf correspondences of the last scan
-  SC_LO_NCORNER,  // corner correspondences
-  SC_LO_FLAGS,    // ALEGO_FLAG_* of the last LO step
-  SC_LO_ITERS,    // packed solver summaries (surf: it | succ<<8 | term<<16 ; corner <<... in next)
-  SC_LO_ITERS2,
-  SC_CUR,         // feature double-buffer index holding the features of the last COMPLETED LO step;
-                  // FE/LO of the scan in flight write/read buffer SC_CUR^1, lo_solve(phase 1) flips it
-  SC_ODOM_VALID,
-  SC_LM_FRAME,    // LaserMapping frame_cnt (laserMapping.cpp:111)
-  SC_LM_FLAGS,
-  SC_PVALID_OUT,  // valid input points of the last projected scan (SC_PVALID is an accumulator, cleared by ip_front)
-  SC_FE_EPOCH,    // feature-extraction launches of this slot so far (fe_front increments it; tags the ring counts fe_ring_out's workgroups publish to each other)
-  SC_FE_ERR,      // != 0: a workgroup of fe_ring_out gave up waiting for the counts of the rings below it; the slot's less_flat cloud is then treated as EMPTY by
-                  // everything that reads it (lo_grid_build, lo_assoc, lm_stage) and the host gets ALEGO_ERR_HIP (fetch_pose).  Sticky until the host clears it
-                  // with alego_debug_set_option("ALEGO_FE_ERR_CLEAR", slot) (-1: every slot) — a slot that gave up once keeps failing loudly, never silently
-  SC_FE_TICKET,   // fe_ring_out: rings of this launch handed out so far (a workgroup's ring = its ticket, so the rings it waits for belong to workgroups that
-                  // are already running whatever order the dispatchers place them in; fe_pickc resets it)
-  SC_M_DSK,       // points lo_deskew wrote into seg_dsk (/undistorted): its own count, because ImageProjection of the NEXT scan may rewrite SC_M before a host fetches the cloud
-  SC_COUNT = 32
-};
-
 #define IPB_NM 9
 #define IP_OWNER_TAG 0x40000000   // any tagged entry beats every plain one (index or -1) in ip_project's atomicMax
-
-// feature cloud kinds
-enum { F_SHARP = 0, F_LSHARP = 1, F_FLAT = 2, F_LFLAT = 3 };
 
 struct DevCtx {
   alego_params P;
@@ -158,18 +126,6 @@ struct DevCtx {
   int* traj_n;          // [slot] scans logged so far (keeps counting past traj_cap; entries beyond it are dropped)
   int traj_cap;
 };
-#define ALEGO_IMU_Q 200   // imu_queue_length, utility.h:70
-
-enum {
-  LS_PARAMS = 0,        // params_[6]
-  LS_TW = 6,            // t_w_cur_[3]
-  LS_RW = 9,            // r_w_cur_[9] row-major
-  LS_PARAMS_SURF = 18,  // params_ after the surf solve (debug)
-  LS_COSTS = 24,        // initial/final cost of both solves
-  LS_ROT = 32,          // rotation matrix of params_ (row-major), cached for transformToStart ...
-  LS_ROT_P = 41,        // ... and the params_ it was computed from (recomputed by lo_assoc when they differ)
-  LO_STATE_N = 48
-};
 
 #define DEV_INLINE __device__ __forceinline__
 
@@ -183,6 +139,8 @@ enum {
 // were measured: the 1 m cells halve lo_assoc's candidates, but lo_grid_build's scan and table are four times as long: 418 k against 425 k scans/s; 1024 cells: 420 k)
 // LO_CH: targets per bounding box of the LaserOdometry 1-NN / ring-walk pruning
 
+#include "fe_store.h"   // the layout of the structured per-slot arrays above: their widths, columns and accessors, SC_*, LS_*, F_*
+
 // the input scan of `slot` at ring position / replay step `pos`
 DEV_INLINE size_t scan_slot(const DevCtx& d, int slot, int pos) {
   if (d.replay_bag) { const int2 s = d.bag_src[slot]; return (size_t)s.x * d.bag_len + (unsigned)(s.y + pos) % (unsigned)d.bag_len; }
@@ -193,15 +151,6 @@ DEV_INLINE int scan_count(const DevCtx& d, int slot, int pos) { return (d.replay
 
 // row of a cell index without an integer division (exact for v < 2^32 / H, i.e. for every supported image)
 DEV_INLINE int cell_row(const DevCtx& d, int v) { return (int)__umulhi((unsigned)v, d.h_magic); }
-
-// buffer written by the scan in flight (valid from fe_collect until lo_solve phase 1 flips SC_CUR)
-DEV_INLINE int cur_in_flight(const DevCtx& d, int slot) { return d.scal[slot * SC_COUNT + SC_CUR] ^ 1; }
-// index into the [slot][2] feature arrays of the scan in flight / of the previous scan, as LaserOdometry sees them.  A lane never
-// runs lo_solve, so its SC_CUR stays at its initial 1 and feature extraction always fills its buffer 0.
-DEV_INLINE size_t fidx_cur(const DevCtx& d, int slot) { return d.fs_cur >= 0 ? (size_t)d.fs_cur * 2 : (size_t)slot * 2 + cur_in_flight(d, slot); }
-DEV_INLINE size_t fidx_last(const DevCtx& d, int slot) { return d.fs_last >= 0 ? (size_t)d.fs_last * 2 : (size_t)slot * 2 + (cur_in_flight(d, slot) ^ 1); }
-// slot whose per-scan outputs (poses, outlier cloud, outlier count) belong to the scan in flight
-DEV_INLINE int scan_slot_of(const DevCtx& d, int slot) { return d.fs_cur >= 0 ? d.fs_cur : slot; }
 
 DEV_INLINE int32_t d_f2i(float f) { return __float_as_int(f); }
 DEV_INLINE float d_i2f(int32_t i) { return __int_as_float(i); }

@@ -28,7 +28,7 @@
 
 __global__ void __launch_bounds__(FE_BLOCK) fe_curv(DevCtx d) {
   const int slot = blockIdx.y + d.slot0;
-  const int M = d.scal[slot * SC_COUNT + SC_M];
+  const int M = scal_of(d, slot)[SC_M];
   const int t0 = blockIdx.x * FE_CW;   // FE_CW points per workgroup, FE_CW / FE_BLOCK per thread
   if (t0 >= M) return;
   __shared__ float s_r[FE_CW + 2 * FE_HALO];
@@ -50,7 +50,7 @@ __global__ void __launch_bounds__(64) fe_pick(DevCtx d) {
   __shared__ typename std::conditional<STDSORT, SortEmu<64 * FE_T>, char>::type s_emu;
   const size_t base = (size_t)slot * d.N;
   const alego_params& P = d.P;
-  const int S = d.ring_start[slot * d.NS + ring], E = d.ring_end[slot * d.NS + ring];
+  const int S = *ring_start_of(d, slot, ring), E = *ring_end_of(d, slot, ring);
   const int rf = S - 5, rl = E + 5;  // first / last point of this ring in the segmented cloud
   const int cnt = rl - rf + 1;
   extern __shared__ __attribute__((aligned(16))) unsigned char fe_smem[];
@@ -67,8 +67,8 @@ __global__ void __launch_bounds__(64) fe_pick(DevCtx d) {
                           (curv > P.edge_thres ? 4 : 0) | (curv < P.surf_thres ? 8 : 0) | (1 << 4));  // bits 4-5: label + 1
   }
   __syncthreads();
-  int* st = d.st_idx + ((size_t)slot * d.NS + ring) * d.st_stride;
-  int* st_sharp = st, *st_lsharp = st + d.cap_sharp, *st_flat = st_lsharp + d.cap_lsharp, *st_lfs = st_flat + d.cap_flat;
+  int* st = st_idx_of(d, slot, ring);
+  int* st_sharp = st, *st_lsharp = st_idx_of(d, slot, ring, F_LSHARP), *st_flat = st_idx_of(d, slot, ring, F_FLAT), *st_lfs = st_idx_of(d, slot, ring, F_LFLAT);
   int n_sharp = 0, n_ls = 0, n_flat = 0, n_lfs = 0;
   const int NSEC = P.n_sectors, SR = P.suppress_radius;
   for (int j = 0; j < NSEC; ++j) {
@@ -226,8 +226,8 @@ __global__ void __launch_bounds__(64) fe_pick(DevCtx d) {
   __syncthreads();
   for (int k = lane; k < cnt; k += 64) d.plabel[base + rf + k] = (int)((s_flag[k] >> 4) & 3) - 1;
   if (lane == 0) {
-    int* c = d.st_cnt + ((size_t)slot * d.NS + ring) * 8;
-    c[0] = n_sharp; c[1] = n_ls; c[2] = n_flat; c[3] = n_lfs;
+    int* c = st_cnt_of(d, slot, ring);
+    c[F_SHARP] = n_sharp; c[F_LSHARP] = n_ls; c[F_FLAT] = n_flat; c[F_LFLAT] = n_lfs;
   }
 }
 
@@ -256,7 +256,7 @@ __global__ void __launch_bounds__(64) fe_pick4(DevCtx d) {
   // exceeds suppress_col_diff: that is bit 6 of the point's flag byte.
   uint8_t* s_flag = fe_smem;                                  // [FP_G][H]
   for (int r = 0; r < FP_G && ring0 + r < d.NS; ++r) {       // whole wavefront stages one ring after the other
-    const int Sr = d.ring_start[slot * d.NS + ring0 + r], Er = d.ring_end[slot * d.NS + ring0 + r];
+    const int Sr = ring_start_of(d, slot, ring0)[r], Er = ring_end_of(d, slot, ring0)[r];
     const int rfr = Sr - 5, cntr = Er - Sr + 11;
     uint8_t* sf = s_flag + (size_t)r * d.H;
     // the flag byte of every point comes ready from fe_curv_chunk (picked | ground << 1 | curvature > edge_thres << 2 | curvature <
@@ -267,11 +267,11 @@ __global__ void __launch_bounds__(64) fe_pick4(DevCtx d) {
     for (int k = lane; k < cntr; k += 64) sf[k] = k == cntr - 1 ? (uint8_t)(ff[k] & ~64) : ff[k];
   }
   __syncthreads();
-  const int S = rv ? d.ring_start[slot * d.NS + ring] : 0, E = rv ? d.ring_end[slot * d.NS + ring] : 0;
+  const int S = rv ? *ring_start_of(d, slot, ring) : 0, E = rv ? *ring_end_of(d, slot, ring) : 0;
   const int rf = S - 5;
   uint8_t* sf = s_flag + (size_t)g * d.H;
-  int* st = d.st_idx + ((size_t)slot * d.NS + (rv ? ring : 0)) * d.st_stride;
-  int* st_sharp = st, *st_lsharp = st + d.cap_sharp, *st_flat = st_lsharp + d.cap_lsharp;
+  int* st = st_idx_of(d, slot, rv ? ring : 0);
+  int* st_sharp = st, *st_lsharp = st_idx_of(d, slot, rv ? ring : 0, F_LSHARP), *st_flat = st_idx_of(d, slot, rv ? ring : 0, F_FLAT);
   int n_sharp = 0, n_ls = 0, n_flat = 0;
   const int NSEC = P.n_sectors, SR = P.suppress_radius;
   for (int j = 0; j < NSEC; ++j) {
@@ -325,7 +325,7 @@ __global__ void __launch_bounds__(64) fe_pick4(DevCtx d) {
       const int bo = fo + (x ? c : 0);
       atomicXor(&fw[bo >> 2], (x << 4) << ((bo & 3) * 8));
     };
-    int* st_dummy = d.st_cnt + ((size_t)slot * d.NS + (rv ? ring : 0)) * 8 + 7;   // unused field
+    int* st_dummy = st_cnt_of(d, slot, rv ? ring : 0) + ST_DUMMY;   // unused field
     // (STDSORT) the sector arrangement of every ring whose row reports a tie and has none yet, ring by ring with all 64 lanes
     unsigned have_arr = 0;   // wavefront-uniform: bit r = ring r's arrangement of this sector is in s_pos[r]
     auto ring_arrangements = [&](bool tied) {
@@ -429,17 +429,17 @@ __global__ void __launch_bounds__(64) fe_pick4(DevCtx d) {
   }
   __syncthreads();
   if (rv && gl == 0) {
-    int* c = d.st_cnt + ((size_t)slot * d.NS + ring) * 8;
-    c[0] = n_sharp; c[1] = n_ls; c[2] = n_flat;
+    int* c = st_cnt_of(d, slot, ring);
+    c[F_SHARP] = n_sharp; c[F_LSHARP] = n_ls; c[F_FLAT] = n_flat;
   }
   // ---- less-flat candidates in position order (:279-285) and the labels, one ring after the other with all 64 lanes.
   // A sector's labels only change while that sector is picked, so reading them at the end is the same as reading them
   // after the sector.
   for (int r = 0; r < FP_G && ring0 + r < d.NS; ++r) {
-    const int Sr = d.ring_start[slot * d.NS + ring0 + r], Er = d.ring_end[slot * d.NS + ring0 + r];
+    const int Sr = ring_start_of(d, slot, ring0)[r], Er = ring_end_of(d, slot, ring0)[r];
     const int rfr = Sr - 5, cntr = Er - Sr + 11;
     const uint8_t* sfr = s_flag + (size_t)r * d.H;
-    int* st_lfs = d.st_idx + ((size_t)slot * d.NS + ring0 + r) * d.st_stride + d.cap_sharp + d.cap_lsharp + d.cap_flat;
+    int* st_lfs = st_idx_of(d, slot, (size_t)ring0 + r, F_LFLAT);
     int n_lfs = 0;
     for (int j = 0; j < NSEC; ++j) {
       int sp, ep;
@@ -456,7 +456,7 @@ __global__ void __launch_bounds__(64) fe_pick4(DevCtx d) {
       }
     }
     for (int k = lane; k < cntr; k += 64) d.plabel[base + rfr + k] = (int)((sfr[k] >> 4) & 3) - 1;
-    if (lane == 0) d.st_cnt[((size_t)slot * d.NS + ring0 + r) * 8 + 3] = n_lfs;
+    if (lane == 0) st_cnt_of(d, slot, (size_t)ring0 + r)[F_LFLAT] = n_lfs;
   }
 }
 
@@ -504,10 +504,10 @@ static size_t fv_lds_bytes(int H) { return (size_t)10 * H + (size_t)16 * fv_stag
 __global__ void __launch_bounds__(FV_BLOCK) fe_voxel(DevCtx d) {
   const int slot = blockIdx.y + d.slot0, ring = blockIdx.x, tid = threadIdx.x;
   const size_t base = (size_t)slot * d.N;
-  int* cnts = d.st_cnt + ((size_t)slot * d.NS + ring) * 8;
-  const int n = cnts[3];
-  const int* lfs = d.st_idx + ((size_t)slot * d.NS + ring) * d.st_stride + d.cap_sharp + d.cap_lsharp + d.cap_flat;
-  float4* out = d.st_lfds + ((size_t)slot * d.NS + ring) * d.H;
+  int* cnts = st_cnt_of(d, slot, ring);
+  const int n = cnts[F_LFLAT];
+  const int* lfs = st_idx_of(d, slot, ring, F_LFLAT);
+  float4* out = st_lfds_of(d, slot, ring);
   const float4* seg = d.seg_lo + base;
   extern __shared__ __attribute__((aligned(16))) unsigned char fv_smem[];
   float4* s_pt = reinterpret_cast<float4*>(fv_smem);                            // the ring's less_flat_scan points, gathered ONCE [cap] (FV_STAGE)
@@ -522,7 +522,7 @@ __global__ void __launch_bounds__(FV_BLOCK) fe_voxel(DevCtx d) {
   __shared__ float s_red[6][FV_BLOCK / 64];
   __shared__ int s_scan[FV_BLOCK / 64];
   __shared__ int s_boff[FV_NB + 1], s_bcur[FV_NB + 1];
-  if (n == 0) { if (tid == 0) cnts[4] = 0; return; }
+  if (n == 0) { if (tid == 0) cnts[ST_LFDS] = 0; return; }
   const float inv = 1.0f / d.P.less_flat_leaf;
   FV_TICK(0);
   // getMinMax3D
@@ -555,7 +555,7 @@ __global__ void __launch_bounds__(FV_BLOCK) fe_voxel(DevCtx d) {
   }
   if (vgr_leaf_too_small(mn, mx, inv)) {  // "leaf size too small": the input is returned unchanged
     for (int i = tid; i < n; i += FV_BLOCK) out[i] = point(i);
-    if (tid == 0) cnts[4] = n;
+    if (tid == 0) cnts[ST_LFDS] = n;
     return;
   }
   FV_TICK(1);
@@ -657,7 +657,7 @@ __global__ void __launch_bounds__(FV_BLOCK) fe_voxel(DevCtx d) {
     nvox += tot;
     __syncthreads();
   }
-  if (tid == 0) cnts[4] = nvox;
+  if (tid == 0) cnts[ST_LFDS] = nvox;
   FV_TICK(5);
 }
 
@@ -673,12 +673,12 @@ __global__ void __launch_bounds__(FC_T) fe_collect(DevCtx d) {
   const size_t base = (size_t)slot * d.N;
   const int NS = d.NS;
   __shared__ int s_off[4][65], s_boff[2][65];   // s_boff: first box of every ring (less_sharp, less_flat): boxes never straddle rings
-  const int* allc = d.st_cnt + (size_t)slot * NS * 8;
+  const int* allc = st_cnt_of(d, slot, 0);
   if (tid < 64) {
     const int r = tid;
     int c[4];
-    c[0] = r < NS ? allc[r * 8 + 0] : 0; c[1] = r < NS ? allc[r * 8 + 1] : 0;
-    c[2] = r < NS ? allc[r * 8 + 2] : 0; c[3] = r < NS ? allc[r * 8 + 4] : 0;
+    c[0] = r < NS ? allc[r * ST_W + F_SHARP] : 0; c[1] = r < NS ? allc[r * ST_W + F_LSHARP] : 0;
+    c[2] = r < NS ? allc[r * ST_W + F_FLAT] : 0; c[3] = r < NS ? allc[r * ST_W + ST_LFDS] : 0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const int incl = wave_incl_scan(c[k]);
@@ -695,16 +695,15 @@ __global__ void __launch_bounds__(FC_T) fe_collect(DevCtx d) {
   __syncthreads();
   const int tot[4] = {s_off[0][64], s_off[1][64], s_off[2][64], s_off[3][64]};
   if (tid <= NS) {
-    int* ro = d.ring_off + (((size_t)slot * 2 + cur) * 2) * (NS + 1);
-    ro[tid] = tid < NS ? s_off[1][tid] : tot[1];
-    ro[(NS + 1) + tid] = tid < NS ? s_off[3][tid] : tot[3];
-    int* rb = d.ring_boff + (((size_t)slot * 2 + cur) * 2) * (NS + 1);
-    rb[tid] = tid < NS ? s_boff[0][tid] : s_boff[0][64];
-    rb[(NS + 1) + tid] = tid < NS ? s_boff[1][tid] : s_boff[1][64];
+    const size_t fb = fbuf(slot, cur);
+    ring_off_of(d, fb, RO_LSHARP)[tid] = tid < NS ? s_off[1][tid] : tot[1];
+    ring_off_of(d, fb, RO_LFLAT)[tid] = tid < NS ? s_off[3][tid] : tot[3];
+    ring_boff_of(d, fb, RO_LSHARP)[tid] = tid < NS ? s_boff[0][tid] : s_boff[0][64];
+    ring_boff_of(d, fb, RO_LFLAT)[tid] = tid < NS ? s_boff[1][tid] : s_boff[1][64];
   }
   if (tid == 0) {
-    int* fc = d.feat_cnt + ((size_t)slot * 2 + cur) * 4;
-    fc[0] = tot[0]; fc[1] = tot[1]; fc[2] = tot[2]; fc[3] = tot[3];
+    int* fc = feat_cnt_of(d, fbuf(slot, cur));
+    fc[F_SHARP] = tot[0]; fc[F_LSHARP] = tot[1]; fc[F_FLAT] = tot[2]; fc[F_LFLAT] = tot[3];
   }
   const float4* seg = d.seg_lo + base;
   auto ring_of = [&](int k, int i) -> int {   // largest r with s_off[k][r] <= i (rings beyond NS hold the total: never chosen for i < total)
@@ -714,11 +713,11 @@ __global__ void __launch_bounds__(FC_T) fe_collect(DevCtx d) {
   };
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    float4* dst = d.feat[k] + ((size_t)slot * 2 + cur) * d.fcap[k];
-    int* dsti = k < 3 ? d.feat_idx[k] + ((size_t)slot * 2 + cur) * d.fcap[k] : nullptr;
+    float4* dst = feat_of(d, k, fbuf(slot, cur));
+    int* dsti = k < 3 ? feat_idx_of(d, k, fbuf(slot, cur)) : nullptr;
     const bool boxes = k == F_LSHARP || k == F_LFLAT;
-    float4* bx = boxes ? d.lo_box + (((size_t)slot * 2 + cur) * 2 + (k == F_LFLAT ? 0 : 1)) * d.lo_box_cap * 2 : nullptr;
-    const int stoff = k == 0 ? 0 : (k == 1 ? d.cap_sharp : d.cap_sharp + d.cap_lsharp);
+    float4* bx = boxes ? lo_box_of(d, lo_row(fbuf(slot, cur), box_set_of(k))) : nullptr;
+    const int stoff = st_part(d, k);
     // clouds with boxes are walked box by box (LO_CH consecutive threads = the up to LO_CH points of one ring's box), the others point by point
     const int kb = k == F_LSHARP ? 0 : 1;
     const int nwork = boxes ? s_boff[kb][64] * LO_CH : tot[k];
@@ -737,11 +736,11 @@ __global__ void __launch_bounds__(FC_T) fe_collect(DevCtx d) {
       if (v) {
         if (!boxes) { r = ring_of(k, i); j = i - s_off[k][r]; }
         if (k < 3) {
-          const int idx = d.st_idx[((size_t)slot * NS + r) * d.st_stride + stoff + j];
+          const int idx = st_idx_of(d, slot, r)[stoff + j];
           p = seg[idx];
           dsti[i] = idx;
         } else {
-          p = d.st_lfds[((size_t)slot * NS + r) * d.H + j];
+          p = st_lfds_of(d, slot, r)[j];
         }
         dst[i] = p;
       }

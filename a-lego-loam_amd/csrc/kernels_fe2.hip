@@ -69,10 +69,10 @@ DEV_INLINE void ff_sector(const alego_params& P, int S, int E, int j, int& sp, i
 //   key  sharp: |cd| bits + 1, flat: ~|cd| bits (0 = no candidate; the pick is an arg-MAX for both; curvature = (double)cd^2 orders like |cd|)
 //   pay  sharp: (index in sector) << 6 | reach forward << 3 | reach backward; flat: ~ of that (ties: sharp -> larger index, flat -> smaller)
 DEV_INLINE uint2* ff_list(const DevCtx& d, int slot, int ring, int j, int sector_cap) {
-  return reinterpret_cast<uint2*>(d.st_lfds + ((size_t)slot * d.NS + ring) * d.H) + (size_t)j * sector_cap;   // (the filtered-ring staging of the four-kernel path: 2 H entries per ring)
+  return st_cand_of(d, slot, ring) + (size_t)j * sector_cap;
 }
 DEV_INLINE int* ff_counts(const DevCtx& d, int slot, int ring) {   // [sector][2]: sharp, flat candidates (the less_flat_scan index list of the four-kernel path)
-  return d.st_idx + ((size_t)slot * d.NS + ring) * d.st_stride + d.cap_sharp + d.cap_lsharp + d.cap_flat;
+  return st_idx_of(d, slot, ring, F_LFLAT);
 }
 
 // One sector [sp, ep] of one ring, all 64 lanes of the calling wavefront: the ring's ranges / columns are staged once in LDS; the 11-tap
@@ -173,11 +173,11 @@ __global__ void __launch_bounds__(64 * FC_NW) fe_cand(DevCtx d, int sector_cap) 
   const int NS = d.NS, NSEC = d.P.n_sectors;
   const int item = blockIdx.x * FC_NW + wave, ring = item / NSEC, j = item - ring * NSEC;
   const size_t base = (size_t)slot * d.N;
-  const int M = d.scal[slot * SC_COUNT + SC_M];
+  const int M = scal_of(d, slot)[SC_M];
   extern __shared__ __attribute__((aligned(16))) unsigned char ff_smem[];
   const FfLayout L = ff_layout(sector_cap);
   int sp = 0, ep = -1;
-  if (ring < NS) ff_sector(d.P, d.ring_start[slot * NS + ring], d.ring_end[slot * NS + ring], j, sp, ep);
+  if (ring < NS) ff_sector(d.P, *ring_start_of(d, slot, ring), *ring_end_of(d, slot, ring), j, sp, ep);
   int ns = 0, nf = 0;
   if (sp < ep) ff_wide(d, base, M, sp, ep, ff_smem + wave * L.wave_bytes, L, ff_list(d, slot, ring, j, sector_cap), sector_cap, ns, nf, d.n_launch == 1);
   else { __syncthreads(); __syncthreads(); }
@@ -325,15 +325,15 @@ __global__ void __launch_bounds__(64) fe_pickc(DevCtx d, int sector_cap) {
   const int g = lane / FF_LPR, gl = lane % FF_LPR;
   const int NS = d.NS;
   const alego_params& P = d.P;
-  int* sc = d.scal + slot * SC_COUNT;
+  int* sc = scal_of(d, slot);
   __shared__ uint32_t s_mark[FF_G][FF_MW_MAX];
   const int mw = min((sector_cap + FF_HALO + 31) / 32 + 1, FF_MW_MAX);
   if (blockIdx.x == 0 && lane == 0) { sc[SC_FE_EPOCH] = sc[SC_FE_EPOCH] + 1; sc[SC_FE_TICKET] = 0; }   // (fe_ring_out of this launch tags its ring counts with the epoch and hands out its rings by ticket)
   const int ring = ring0 + g;
   const bool rv = ring < NS;
   const int rc = rv ? ring : 0;
-  const int S = rv ? d.ring_start[slot * NS + ring] : 0, E = rv ? d.ring_end[slot * NS + ring] : 0;
-  int* st = d.st_idx + ((size_t)slot * NS + rc) * d.st_stride;
+  const int S = rv ? *ring_start_of(d, slot, ring) : 0, E = rv ? *ring_end_of(d, slot, ring) : 0;
+  int* st = st_idx_of(d, slot, rc);
   const int* cc = ff_counts(d, slot, rc);
   FfPick R;
   R.act0 = false; R.sp = 0; R.carry = -1; R.carry_in = -1; R.n_sharp = 0; R.n_ls = 0; R.n_flat = 0;
@@ -360,8 +360,8 @@ __global__ void __launch_bounds__(64) fe_pickc(DevCtx d, int sector_cap) {
     __builtin_amdgcn_wave_barrier();
   }
   if (rv && gl == 0) {
-    int* c = d.st_cnt + ((size_t)slot * NS + ring) * 8;
-    c[0] = R.n_sharp; c[1] = R.n_ls; c[2] = R.n_flat;
+    int* c = st_cnt_of(d, slot, ring);
+    c[F_SHARP] = R.n_sharp; c[F_LSHARP] = R.n_ls; c[F_FLAT] = R.n_flat;
   }
 }
 
@@ -421,7 +421,7 @@ extern "C" void alego_fo_times(long long* out) { (void)hipMemcpyFromSymbol(out, 
 #define FO_TICK(k) do { if (threadIdx.x == 0 && ring == FO_TICK_RING && blockIdx.x == 0) fo_times[k] = wall_clock64(); } while (0)
 #elif defined(FO_STOP_AFTER)
 // development (instruction counts per phase, tools/fo_phase_counts.sh): the ring stops after phase FO_STOP_AFTER — its count is published first so that no ring above it spins
-#define FO_TICK(k) do { if ((k) == FO_STOP_AFTER) { if (threadIdx.x == 0) __hip_atomic_store(&d.fe_sync[(size_t)slot * NS + ring], (epoch << 16), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return; } } while (0)
+#define FO_TICK(k) do { if ((k) == FO_STOP_AFTER) { if (threadIdx.x == 0) __hip_atomic_store(fe_sync_of(d, slot, ring), (epoch << 16), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return; } } while (0)
 #else
 #define FO_TICK(k)
 #endif
@@ -431,14 +431,14 @@ extern "C" void alego_fo_times(long long* out) { (void)hipMemcpyFromSymbol(out, 
 DEV_INLINE void fo_picks_out(const DevCtx& d, int slot, unsigned char* smem) {
   const int tid = threadIdx.x, NS = d.NS;
   const size_t base = (size_t)slot * d.N;
-  const size_t fb = (size_t)slot * 2 + cur_in_flight(d, slot);
-  const int* allc = d.st_cnt + (size_t)slot * NS * 8;
+  const size_t fb = fbuf(slot, cur_in_flight(d, slot));
+  const int* allc = st_cnt_of(d, slot, 0);
   const float4* seg = d.seg_lo + base;
   int (*s_off)[65] = reinterpret_cast<int (*)[65]>(smem);   // [0..2]: first pick of every ring in the three clouds, [3]: first less_sharp box
   if (tid < 64) {
     const int r = tid;
     int c[4];
-    c[0] = r < NS ? allc[r * 8 + 0] : 0; c[1] = r < NS ? allc[r * 8 + 1] : 0; c[2] = r < NS ? allc[r * 8 + 2] : 0;
+    c[0] = r < NS ? allc[r * ST_W + F_SHARP] : 0; c[1] = r < NS ? allc[r * ST_W + F_LSHARP] : 0; c[2] = r < NS ? allc[r * ST_W + F_FLAT] : 0;
     c[3] = (c[1] + LO_CH - 1) / LO_CH;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -449,21 +449,21 @@ DEV_INLINE void fo_picks_out(const DevCtx& d, int slot, unsigned char* smem) {
   }
   __syncthreads();
   if (tid <= NS) {
-    d.ring_off[(fb * 2) * (NS + 1) + tid] = tid < NS ? s_off[1][tid] : s_off[1][64];
-    d.ring_boff[(fb * 2) * (NS + 1) + tid] = tid < NS ? s_off[3][tid] : s_off[3][64];
+    ring_off_of(d, fb, RO_LSHARP)[tid] = tid < NS ? s_off[1][tid] : s_off[1][64];
+    ring_boff_of(d, fb, RO_LSHARP)[tid] = tid < NS ? s_off[3][tid] : s_off[3][64];
   }
-  if (tid < 3) d.feat_cnt[fb * 4 + tid] = s_off[tid][64];
+  if (tid < 3) feat_cnt_of(d, fb)[tid] = s_off[tid][64];
   auto ring_of = [&](int k, int i) -> int {   // largest r with s_off[k][r] <= i (rings beyond NS hold the total: never chosen for i < total)
     int lo = 0, hi = NS - 1;
     while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (s_off[k][mid] <= i) lo = mid; else hi = mid - 1; }
     return lo;
   };
-  const int stoff[3] = {0, d.cap_sharp, d.cap_sharp + d.cap_lsharp};
+  const int stoff[3] = {st_part(d, F_SHARP), st_part(d, F_LSHARP), st_part(d, F_FLAT)};
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    float4* dst = d.feat[k] + fb * d.fcap[k];
-    int* dsti = d.feat_idx[k] + fb * d.fcap[k];
-    float4* bx = d.lo_box + (fb * 2 + 1) * d.lo_box_cap * 2;
+    float4* dst = feat_of(d, k, fb);
+    int* dsti = feat_idx_of(d, k, fb);
+    float4* bx = lo_box_of(d, lo_row(fb, box_set_of(F_LSHARP)));
     const bool boxes = k == F_LSHARP;
     // less_sharp is walked box by box (LO_CH consecutive threads = the up to LO_CH picks of one ring's box), the others pick by pick
     const int nwork = boxes ? s_off[3][64] * LO_CH : s_off[k][64];
@@ -478,7 +478,7 @@ DEV_INLINE void fo_picks_out(const DevCtx& d, int slot, unsigned char* smem) {
       } else if (v) { r = ring_of(k, i); j = i - s_off[k][r]; }
       float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
       if (v) {
-        const int idx = d.st_idx[((size_t)slot * NS + r) * d.st_stride + stoff[k] + j];
+        const int idx = st_idx_of(d, slot, r)[stoff[k] + j];
         p = seg[idx];
         dsti[i] = idx; dst[i] = p;
       }
@@ -497,14 +497,14 @@ DEV_INLINE void fo_picks_out(const DevCtx& d, int slot, unsigned char* smem) {
   }
   // cloud_label_ for the single-scan entry points / tests (:196-204,:245): 2 sharp, 1 less sharp, -1 flat, 0 otherwise
   if (d.n_launch == 1) {
-    const int M = d.scal[slot * SC_COUNT + SC_M];
+    const int M = scal_of(d, slot)[SC_M];
     for (int k = tid; k < M; k += FO_BLOCK) d.plabel[base + k] = 0;
     __syncthreads();
     for (int pass = 0; pass < 3; ++pass) {   // less sharp first: a sharp pick is on both lists
       const int k = pass == 0 ? 1 : (pass == 1 ? 0 : 2), lab = pass == 0 ? 1 : (pass == 1 ? 2 : -1);
       for (int i = tid; i < s_off[k][64]; i += FO_BLOCK) {
         const int r = ring_of(k, i);
-        d.plabel[base + d.st_idx[((size_t)slot * NS + r) * d.st_stride + stoff[k] + i - s_off[k][r]]] = lab;
+        d.plabel[base + st_idx_of(d, slot, r)[stoff[k] + i - s_off[k][r]]] = lab;
       }
       __syncthreads();
     }
@@ -518,7 +518,7 @@ __global__ void __launch_bounds__(FO_BLOCK) fe_ring_out(DevCtx d) {
   extern __shared__ __attribute__((aligned(16))) unsigned char fo_smem[];
   if ((int)blockIdx.x >= d.n_launch) return;   // (ALEGO_FE_PAD8=1 pads the grid's x extent to a multiple of 8, see launch_fe_fused)
   if ((int)blockIdx.y == NS) { fo_picks_out(d, slot, fo_smem); return; }
-  int* scv = d.scal + slot * SC_COUNT;
+  int* scv = scal_of(d, slot);
   // Which ring this workgroup takes is decided by a per-stream TICKET, not by blockIdx.y: a ring waits for the voxel counts of the rings below it, and with
   // tickets those rings belong to workgroups that took theirs earlier — they are running, and they in turn wait only for still earlier ones.  No assumption
   // about the order in which the (per-XCD) dispatchers place the workgroups of a launch is left (round 4 relied on "lower blockIdx.y first on the stream's
@@ -530,12 +530,12 @@ __global__ void __launch_bounds__(FO_BLOCK) fe_ring_out(DevCtx d) {
   const size_t base = (size_t)slot * d.N;
   const alego_params& P = d.P;
   const int cur = cur_in_flight(d, slot);
-  const size_t fb = (size_t)slot * 2 + cur;
+  const size_t fb = fbuf(slot, cur);
   const unsigned epoch = (unsigned)scv[SC_FE_EPOCH] & 0xFFFFu;
-  const int S = d.ring_start[slot * NS + ring], E = d.ring_end[slot * NS + ring];
+  const int S = *ring_start_of(d, slot, ring), E = *ring_end_of(d, slot, ring);
   const int n_all = min(max(E - S, 0), H);               // the sectors of a ring cover [S, E - 1] (:177-178)
-  const int n_ls = d.st_cnt[((size_t)slot * NS + ring) * 8 + 1];
-  const int* st_ls = d.st_idx + ((size_t)slot * NS + ring) * d.st_stride + d.cap_sharp;
+  const int n_ls = st_cnt_of(d, slot, ring)[F_LSHARP];
+  const int* st_ls = st_idx_of(d, slot, ring, F_LSHARP);
   const float4* seg = d.seg_lo + base;
   float4* s_pt = reinterpret_cast<float4*>(fo_smem);                            // the ring's points [cap]
   const FoLayout lay = fo_layout(H);
@@ -821,7 +821,7 @@ __global__ void __launch_bounds__(FO_BLOCK) fe_ring_out(DevCtx d) {
   }
   FO_TICK(5);
   // ---- the ring's less_flat offset: its count for the rings above, the counts of the rings below
-  if (tid == 0) __hip_atomic_store(&d.fe_sync[(size_t)slot * NS + ring], (epoch << 16) | (unsigned)nout, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (tid == 0) __hip_atomic_store(fe_sync_of(d, slot, ring), (epoch << 16) | (unsigned)nout, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (tid < 64) {
     int c = 0, nbx = 0, bad = 0;
     if (tid < ring) {
@@ -829,7 +829,7 @@ __global__ void __launch_bounds__(FO_BLOCK) fe_ring_out(DevCtx d) {
       int spins = 0;
       const int limit = d.opt_fo_spin > 0 ? d.opt_fo_spin : FO_SPIN_LIMIT;
       while (true) {
-        v = __hip_atomic_load(&d.fe_sync[(size_t)slot * NS + tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        v = __hip_atomic_load(fe_sync_of(d, slot, tid), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if ((v >> 16) == epoch || ++spins > limit) break;
         __builtin_amdgcn_s_sleep(2);
       }
@@ -848,7 +848,7 @@ __global__ void __launch_bounds__(FO_BLOCK) fe_ring_out(DevCtx d) {
   // fetch_pose, resets the slot; this ring still writes its (meaningless, in-bounds) part so that the tables of the scan are all written.
   if (s_look[2] && tid == 0) scv[SC_FE_ERR] = 1;
   FO_TICK(6);
-  float4* out = d.feat[F_LFLAT] + fb * d.fcap[F_LFLAT] + off3;
+  float4* out = feat_of(d, F_LFLAT, fb) + off3;
   // box corners of every LO_CH consecutive output points, gathered with LDS atomics while the points are written
   auto box_add = [&](int rank, const float4& p) {
     uint32_t* b = s_bx + rank / LO_CH;
@@ -907,18 +907,18 @@ __global__ void __launch_bounds__(FO_BLOCK) fe_ring_out(DevCtx d) {
   __syncthreads();
   FO_TICK(7);
   {
-    float4* bx = d.lo_box + (fb * 2 + 0) * d.lo_box_cap * 2 + (size_t)2 * boff3;
+    float4* bx = lo_box_of(d, lo_row(fb, box_set_of(F_LFLAT))) + (size_t)2 * boff3;
     for (int b = tid; b < nbox; b += FO_BLOCK) {
       const uint32_t* c = s_bx + b;
       bx[2 * b] = make_float4(fo_unord(c[0]), fo_unord(c[FO_MAXBOX]), fo_unord(c[2 * FO_MAXBOX]), __int_as_float(off3 + b * LO_CH));
       bx[2 * b + 1] = make_float4(fo_unord(c[3 * FO_MAXBOX]), fo_unord(c[4 * FO_MAXBOX]), fo_unord(c[5 * FO_MAXBOX]), __int_as_float(min(LO_CH, nout - b * LO_CH)));
     }
     if (tid == 0) {
-      int* ro = d.ring_off + (fb * 2 + 1) * (NS + 1);
-      int* rb = d.ring_boff + (fb * 2 + 1) * (NS + 1);
+      int* ro = ring_off_of(d, fb, RO_LFLAT);
+      int* rb = ring_boff_of(d, fb, RO_LFLAT);
       ro[ring] = off3; rb[ring] = boff3;
-      if (ring == NS - 1) { ro[NS] = off3 + nout; rb[NS] = boff3 + nbox; d.feat_cnt[fb * 4 + 3] = off3 + nout; }
-      d.st_cnt[((size_t)slot * NS + ring) * 8 + 4] = nout;
+      if (ring == NS - 1) { ro[NS] = off3 + nout; rb[NS] = boff3 + nbox; feat_cnt_of(d, fb)[F_LFLAT] = off3 + nout; }
+      st_cnt_of(d, slot, ring)[ST_LFDS] = nout;
     }
   }
   FO_TICK(8);

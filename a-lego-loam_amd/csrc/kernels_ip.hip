@@ -84,7 +84,7 @@ __global__ void __launch_bounds__(IP_BLOCK) ip_project(DevCtx d, int ring_pos) {
   // first / last valid point for the orientation block (:62-63): one atomic per wavefront
   vmin = bfly_min_i32(vmin); vmax = bfly_max_i32(vmax); nvalid = bfly_sum_i32(nvalid);
   if (lane_id() == 0 && nvalid) {
-    int* sc = d.scal + slot * SC_COUNT;
+    int* sc = scal_of(d, slot);
     atomicMin(&sc[SC_FIRST], vmin);
     atomicMax(&sc[SC_LAST], vmax);
     atomicAdd(&sc[SC_PVALID], nvalid);
@@ -118,8 +118,8 @@ __global__ void __launch_bounds__(IPF_W) ip_front(DevCtx d, int ring_pos, int in
   float* s_r = reinterpret_cast<float*>(ipf_smem);                                   // [NS][IPF_W] ranges (-1 empty)
   unsigned long long* s_act = reinterpret_cast<unsigned long long*>(s_r + (size_t)d.NS * IPF_W);   // [IPF_W] active mask of a column
   if (blockIdx.x == 0 && tid == 0) {  // orientation, :62-72
-    int* sc = d.scal + slot * SC_COUNT;
-    float* ori = d.ori + slot * 4;
+    int* sc = scal_of(d, slot);
+    float* ori = ori_of(d, slot);
     const int first = sc[SC_FIRST], last = sc[SC_LAST];
     sc[SC_PVALID_OUT] = sc[SC_PVALID];
     sc[SC_FIRST] = 0x7fffffff; sc[SC_LAST] = -1; sc[SC_PVALID] = 0;   // re-armed for the next scan's ip_project
@@ -436,9 +436,9 @@ __global__ void __launch_bounds__(CC_LDS_THREADS) cc_lds(DevCtx d, int ring_pos,
       int t3[3] = {0, 0, 0};
 #pragma unroll
       for (int a = 0; a < 3; ++a) for (int w = 0; w < NW; ++w) t3[a] += s_wtot[a][w];
-      int* sc = d.scal + slot * SC_COUNT;
+      int* sc = scal_of(d, slot);
       sc[SC_M] = t3[0]; sc[SC_NOUT] = t3[1]; sc[SC_NFEAS] = t3[2];
-      d.ring_end[slot * d.NS + d.NS - 1] = t3[0] - 1 - 5;   // :190 for the last row
+      *ring_end_before(d, slot, d.NS) = t3[0] - 1 - 5;   // :190 for the last row
     }
   }
   __syncthreads();
@@ -453,8 +453,8 @@ __global__ void __launch_bounds__(CC_LDS_THREADS) cc_lds(DevCtx d, int ring_pos,
     const int row = v / H, col = v - row * H;
     const int line = s_cnt[0][k * NW + wave] + (int)__popcll(bk & below);   // kept cells before this one
     if (col == 0) {   // ring convention of :161,:190
-      d.ring_start[slot * d.NS + row] = line + 5;
-      if (row > 0) d.ring_end[slot * d.NS + row - 1] = line - 1 - 5;
+      *ring_start_of(d, slot, row) = line + 5;
+      if (row > 0) *ring_end_before(d, slot, row) = line - 1 - 5;
     }
     if (kp || ol) {
       float4 p = pts[ip_owner_index(d.owner[base + v])];
@@ -738,9 +738,9 @@ __global__ void __attribute__((amdgpu_waves_per_eu(8, 8))) __launch_bounds__(CC_
       int t3[3] = {0, 0, 0};
 #pragma unroll
       for (int a = 0; a < 3; ++a) for (int w = 0; w < NW; ++w) t3[a] += s_wtot[a][w];
-      int* sc = d.scal + slot * SC_COUNT;
+      int* sc = scal_of(d, slot);
       sc[SC_M] = t3[0]; sc[SC_NOUT] = t3[1]; sc[SC_NFEAS] = t3[2];
-      d.ring_end[slot * d.NS + d.NS - 1] = t3[0] - 1 - 5;
+      *ring_end_before(d, slot, d.NS) = t3[0] - 1 - 5;
     }
   }
   __syncthreads();
@@ -760,8 +760,8 @@ __global__ void __attribute__((amdgpu_waves_per_eu(8, 8))) __launch_bounds__(CC_
     const int row = cell_row(d, v), col = v - row * H;
     const int line = s_cnt[0][k * NW + wave] + (int)__popcll(bk & below);
     if (col == 0) {
-      d.ring_start[slot * d.NS + row] = line + 5;
-      if (row > 0) d.ring_end[slot * d.NS + row - 1] = line - 1 - 5;
+      *ring_start_of(d, slot, row) = line + 5;
+      if (row > 0) *ring_end_before(d, slot, row) = line - 1 - 5;
     }
     if (kp || ol) {
       const float4 p = make_float4(q.x, q.y, q.z, (float)(row + d.ip_colfrac[col]));
@@ -872,7 +872,7 @@ __global__ void __launch_bounds__(IP_BLOCK) ip_rowcount(DevCtx d) {
   if (threadIdx.x < 3) {
     int t = 0;
     for (int w = 0; w < IP_BLOCK / 64; ++w) t += s[threadIdx.x][w];
-    d.row_cnt[((size_t)slot * d.NS + row) * 4 + threadIdx.x] = t;
+    row_cnt_of(d, slot, row)[threadIdx.x] = t;
   }
 }
 
@@ -885,20 +885,20 @@ __global__ void __launch_bounds__(IP_BLOCK) ip_compact(DevCtx d, int ring_pos) {
   __shared__ int s_wave[3][IP_BLOCK / 64];
   // exclusive prefix over rows (NS <= 64 rows, recomputed by every block)
   if (threadIdx.x < 64) {
-    const int* rc = d.row_cnt + (size_t)slot * d.NS * 4;
+    const int* rc = row_cnt_of(d, slot, 0);
     const int r = threadIdx.x;
-    int k = r < d.NS ? rc[r * 4 + 0] : 0, o = r < d.NS ? rc[r * 4 + 1] : 0, f = r < d.NS ? rc[r * 4 + 2] : 0;
+    int k = r < d.NS ? rc[r * RC_W + RC_KEEP] : 0, o = r < d.NS ? rc[r * RC_W + RC_OUT] : 0, f = r < d.NS ? rc[r * RC_W + RC_FEAS] : 0;
     int pk = (r < row) ? k : 0, po = (r < row) ? o : 0, pf = (r < row) ? f : 0;
     int tk = k, to = o, tf = f;
     pk = bfly_sum_i32(pk); po = bfly_sum_i32(po); pf = bfly_sum_i32(pf);
     tk = bfly_sum_i32(tk); to = bfly_sum_i32(to); tf = bfly_sum_i32(tf);
     if (threadIdx.x == 0) {
       s_off[0] = pk; s_off[1] = po; s_off[2] = pf;
-      const int mykeep = rc[row * 4 + 0];
-      d.ring_start[slot * d.NS + row] = pk + 5;                // :161
-      d.ring_end[slot * d.NS + row] = pk + mykeep - 1 - 5;     // :190
+      const int mykeep = rc[row * RC_W + RC_KEEP];
+      *ring_start_of(d, slot, row) = pk + 5;                // :161
+      *ring_end_of(d, slot, row) = pk + mykeep - 1 - 5;     // :190
       if (row == 0) {
-        int* sc = d.scal + slot * SC_COUNT;
+        int* sc = scal_of(d, slot);
         sc[SC_M] = tk; sc[SC_NOUT] = to; sc[SC_NFEAS] = tf;
       }
     }

@@ -46,7 +46,6 @@ extern "C" void alego_ipb_times(long long* out) { (void)hipMemcpyFromSymbol(out,
 #endif
 DEV_INLINE u64 ipb_low(int r) { return (2ull << r) - 1ull; }                 // bits 0..r (r = 63: all)
 DEV_INLINE int ipb_head(u64 rs, int r) { return 63 - __clzll((long long)(rs & ipb_low(r))); }   // the run start at or below row r
-DEV_INLINE u64* ipb_mask(const DevCtx& d, int slot, int k) { return (u64*)d.ipb_col + ((size_t)slot * IPB_NM + k) * d.H; }
 DEV_INLINE int ipb_ld(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 DEV_INLINE u64 ipb_ld64(const u64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 DEV_INLINE void ipb_st(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -100,8 +99,8 @@ __global__ void __launch_bounds__(IPB_TW) ipb_band(DevCtx d, int ring_pos, int k
   __shared__ float s_first[IPB_NWV + 1][64];          // ranges of the first column of every wavefront; [IPB_NWV] = the halo column (right of the band, wrap-around)
   __shared__ u64 s_a[IPB_TW + 1], s_y[IPB_TW + 1], s_rs[IPB_TW + 1];
   if (blockIdx.x == 0 && tid == 0) {  // orientation, :62-72 (as ip_front)
-    int* sc = d.scal + slot * SC_COUNT;
-    float* ori = d.ori + slot * 4;
+    int* sc = scal_of(d, slot);
+    float* ori = ori_of(d, slot);
     const int first = sc[SC_FIRST], last = sc[SC_LAST];
     sc[SC_PVALID_OUT] = sc[SC_PVALID];
     sc[SC_FIRST] = 0x7fffffff; sc[SC_LAST] = -1; sc[SC_PVALID] = 0;   // re-armed for the next scan's ip_project
@@ -375,13 +374,13 @@ __global__ void __launch_bounds__(IPB_MT) ipb_merge(DevCtx d, int keep) {
   }
   __syncthreads();
   IPB_TICK(15);
-  int* off = d.ipb_off + (size_t)slot * 3 * 64 * nch;
-  for (int j = tid; j < 3 * 64 * nch; j += IPB_MT) { const int tr = j / nch; off[j] = s_rowbase[tr >> 6][tr & 63] + (int)s_cnt[j]; }
+  int* off = ipb_off_of<RC_KEEP>(d, slot, nch);
+  for (int j = tid; j < IPO_PLANES * IPO_ROWS * nch; j += IPB_MT) { const unsigned tr = j / nch; off[j] = s_rowbase[tr / IPO_ROWS][tr % IPO_ROWS] + (int)s_cnt[j]; }
   if (tid < NS) {
-    d.ring_start[slot * NS + tid] = s_rowbase[0][tid] + 5;                          // :161
-    d.ring_end[slot * NS + tid] = s_rowbase[0][tid] + s_rowtot[0][tid] - 1 - 5;     // :190
+    *ring_start_of(d, slot, tid) = s_rowbase[0][tid] + 5;                          // :161
+    *ring_end_of(d, slot, tid) = s_rowbase[0][tid] + s_rowtot[0][tid] - 1 - 5;     // :190
   }
-  if (tid == 0) { int* sc = d.scal + slot * SC_COUNT; sc[SC_M] = s_tot[0]; sc[SC_NOUT] = s_tot[1]; sc[SC_NFEAS] = s_tot[2]; }
+  if (tid == 0) { int* sc = scal_of(d, slot); sc[SC_M] = s_tot[0]; sc[SC_NOUT] = s_tot[1]; sc[SC_NFEAS] = s_tot[2]; }
   IPB_TICK(16);
   // the statistics entries go back to zero for the next scan (every entry ipb_band or the merge above touched belongs to a band root)
   for (int col = tid; col < H; col += IPB_MT) {
@@ -409,8 +408,8 @@ __global__ void __launch_bounds__(IPB_ET) ipb_emit(DevCtx d, int ring_pos, int k
   const u64 K = have ? ipb_mask(d, slot, 5)[cc] : 0ull, O = have ? ipb_mask(d, slot, 6)[cc] : 0ull, G = ipb_mask(d, slot, 0)[cc];
   const u64 KO = K | O;
   const double cf = d.ip_colfrac[cc];
-  const int* offk = d.ipb_off + ((size_t)slot * 3 + 0) * 64 * nch + ch;
-  const int* offo = d.ipb_off + ((size_t)slot * 3 + 1) * 64 * nch + ch;
+  const int* offk = ipb_off_of<RC_KEEP>(d, slot, nch) + ch;
+  const int* offo = ipb_off_of<RC_OUT>(d, slot, nch) + ch;
   const u64 below = (1ull << lane) - 1ull;
   int obn[4];
 #pragma unroll
@@ -450,7 +449,7 @@ __global__ void __launch_bounds__(IPB_ET) ipb_emit(DevCtx d, int ring_pos, int k
   }
   if ((keep & 1) && part == 0) {   // label_cnt_ numbering of the feasible roots in discovery (row-major) order, 0 for the others (:303-306)
     const u64 F = have ? ipb_mask(d, slot, 7)[cc] : 0ull, Rf = have ? ipb_mask(d, slot, 8)[cc] : 0ull;
-    const int* offf = d.ipb_off + ((size_t)slot * 3 + 2) * 64 * nch + ch;
+    const int* offf = ipb_off_of<RC_FEAS>(d, slot, nch) + ch;
     for (int row = 0; row < NS; ++row) {
       const bool f = (F >> row) & 1ull;
       const u64 bf = __ballot(f);
@@ -461,7 +460,7 @@ __global__ void __launch_bounds__(IPB_ET) ipb_emit(DevCtx d, int ring_pos, int k
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------
 bool ipb_eligible(const DevCtx& d) { return d.ipb_col != nullptr && d.NS > 16 && d.NS <= 64 && d.H >= 64 && (d.H + IPB_TW - 1) / IPB_TW * d.NS <= IPB_LINK_CAP; }   // (seam edges = bands x rings: the linked-root list of ipb_merge)
-size_t ipb_merge_lds(const DevCtx& d) { return (size_t)3 * 64 * ((d.H + 63) / 64) * sizeof(unsigned short); }
+size_t ipb_merge_lds(const DevCtx& d) { return ipb_off_n(d) * sizeof(unsigned short); }
 void launch_ipb(const DevCtx& d, int ring_pos, bool keep_images, hipStream_t st) {
   const int nb = (d.H + IPB_TW - 1) / IPB_TW, nch = (d.H + 63) / 64;
   ALEGO_LAUNCH(ipb_band, dim3(nb, d.n_launch), dim3(IPB_TW), 0, st, d, ring_pos, keep_images ? 1 : 0);

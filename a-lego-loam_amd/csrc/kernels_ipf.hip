@@ -142,9 +142,9 @@ __global__ void __launch_bounds__(IPF2_T) ip_fused(DevCtx d, int ring_pos, int k
                              // in phase B at 16 x 1800, so that the other fifteen do not wait for it at their next barrier
     int first = 0x7fffffff, last = -1, pv = 0;
     for (int w = 0; w < IPF2_NW; ++w) { first = min(first, S.red[0][w]); last = max(last, S.red[1][w]); pv += S.red[2][w]; }
-    d.scal[slot * SC_COUNT + SC_PVALID_OUT] = pv;
+    scal_of(d, slot)[SC_PVALID_OUT] = pv;
     if (last >= 0) {
-      float* ori = d.ori + slot * 4;
+      float* ori = ori_of(d, slot);
       const float4 p0 = pts[first], p1 = pts[last];
       float so = -d_atan2f(p0.y, p0.x);
       float eo = (float)((double)(-d_atan2f(p1.y, p1.x)) + 2 * M_PI);
@@ -382,11 +382,11 @@ __global__ void __launch_bounds__(IPF2_T) ip_fused(DevCtx d, int ring_pos, int k
   __syncthreads();
   if (tid < NS) {   // startRingIndex / endRingIndex (:161,:190)
     const int row = tid;
-    d.ring_start[slot * NS + row] = S.cnt[0][row * IPF2_NW] + 5;
-    d.ring_end[slot * NS + row] = (row + 1 < IPF2_ROWS ? S.cnt[0][(row + 1) * IPF2_NW] : S.tot[0]) - 1 - 5;
+    *ring_start_of(d, slot, row) = S.cnt[0][row * IPF2_NW] + 5;
+    *ring_end_of(d, slot, row) = (row + 1 < IPF2_ROWS ? S.cnt[0][(row + 1) * IPF2_NW] : S.tot[0]) - 1 - 5;
   }
   if (tid == 0) {
-    int* sc = d.scal + slot * SC_COUNT;
+    int* sc = scal_of(d, slot);
     sc[SC_M] = S.tot[0]; sc[SC_NOUT] = S.tot[1]; sc[SC_NFEAS] = S.tot[2];
   }
   IPF_TICK(9);
@@ -676,9 +676,9 @@ __global__ void __launch_bounds__(T, IPH_MINW) ip_fused_t(DevCtx d, int ring_pos
   if (tid == T - 1) {   // orientation block (:62-72)
     int first = 0x7fffffff, last = -1, pv = 0;
     for (int w = 0; w < NW; ++w) { first = min(first, S.red[0][w]); last = max(last, S.red[1][w]); pv += S.red[2][w]; }
-    d.scal[slot * SC_COUNT + SC_PVALID_OUT] = pv;
+    scal_of(d, slot)[SC_PVALID_OUT] = pv;
     if (last >= 0) {
-      float* ori = d.ori + slot * 4;
+      float* ori = ori_of(d, slot);
       const float4 p0 = pts[first], p1 = pts[last];
       float so = -d_atan2f(p0.y, p0.x);
       float eo = (float)((double)(-d_atan2f(p1.y, p1.x)) + 2 * M_PI);
@@ -1010,7 +1010,7 @@ __global__ void __launch_bounds__(T, IPH_MINW) ip_fused_t(DevCtx d, int ring_pos
     }
   }
   __syncthreads();
-  int* const o_rs = IPH_LATE(ring_start) + slot * NS; int* const o_re = IPH_LATE(ring_end) + slot * NS; int* const o_sc = IPH_LATE(scal) + slot * SC_COUNT;   // (fetched in uniform code)
+  int* const o_rs = IPH_LATE(ring_start) + ring_at(NS, slot, 0); int* const o_re = IPH_LATE(ring_end) + ring_at(NS, slot, 0); int* const o_sc = IPH_LATE(scal) + scal_at(slot);   // (fetched in uniform code)
   if (tid < NS) {   // startRingIndex / endRingIndex (:161,:190)
     const int row = tid;
     o_rs[row] = (int)S.u.cnt[0][row * NP * NW] + 5;

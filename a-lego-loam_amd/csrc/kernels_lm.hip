@@ -60,16 +60,16 @@ DEV_INLINE void lm_map_update(const LmCtx& L, int slot, int* li, int merge) {
 // buffers; 2: lm_stage (below) has copied both — LaserMapping runs on its own HIP stream while the front end works on later scans.
 __global__ void __launch_bounds__(LM_BLOCK) lm_prepare(DevCtx d, LmCtx L, int stage, int run_hint, int par) {
   const int slot = blockIdx.z + d.slot0, kind = blockIdx.y;
-  const int cur = d.scal[slot * SC_COUNT + SC_CUR];  // LO has completed: features of this scan
+  const int cur = scal_of(d, slot)[SC_CUR];  // LO has completed: features of this scan
   const int sslot = scan_slot_of(d, slot);           // where this scan's features, outliers and odometry hand-over live (its lane, or the slot itself)
   int* li = lip(L, slot);
   if (stage == 1 && run_hint != 0) {   // run_hint == 0: the host knows that no slot of this launch maps this scan (odd frame)
     // (written with unconditional loads + selects: a 3-way if/else chain here was lowered by hipcc 7.2 into
     //  a scalar switch that left the count pointer of the last arm undefined)
-    const size_t fb = d.fs_cur >= 0 ? (size_t)d.fs_cur * 2 : (size_t)slot * 2 + cur;
-    const int n_c = d.feat_cnt[fb * 4 + F_LSHARP], n_s = d.scal[sslot * SC_COUNT + SC_FE_ERR] ? 0 : d.feat_cnt[fb * 4 + F_LFLAT], n_o = d.scal[sslot * SC_COUNT + SC_NOUT];   // (SC_FE_ERR: dev_common.h)
-    const float4* src_c = d.feat[F_LSHARP] + fb * d.fcap[F_LSHARP];
-    const float4* src_s = d.feat[F_LFLAT] + fb * d.fcap[F_LFLAT];
+    const size_t fb = d.fs_cur >= 0 ? fbuf(d.fs_cur, 0) : fbuf(slot, cur);
+    const int n_c = feat_cnt_of(d, fb)[F_LSHARP], n_s = scal_of(d, sslot)[SC_FE_ERR] ? 0 : feat_cnt_of(d, fb)[F_LFLAT], n_o = scal_of(d, sslot)[SC_NOUT];   // (SC_FE_ERR: dev_common.h)
+    const float4* src_c = feat_of(d, F_LSHARP, fb);
+    const float4* src_s = feat_of(d, F_LFLAT, fb);
     const float4* src_o = d.outlier + (size_t)sslot * d.N;
     const float4* src = kind == 0 ? src_c : (kind == 1 ? src_s : src_o);
     float4* dst = kind == 0 ? L.in_corner + (size_t)slot * L.in_cap_c : (kind == 1 ? L.in_surf + (size_t)slot * L.in_cap_s : L.in_outl + (size_t)slot * L.in_cap_o);
@@ -81,20 +81,20 @@ __global__ void __launch_bounds__(LM_BLOCK) lm_prepare(DevCtx d, LmCtx L, int st
   }
   if (blockIdx.x != 0 || kind != 0 || threadIdx.x != 0) return;
   double* ld = ldp(L, slot);
-  double* po = d.poses + (size_t)sslot * 16;
+  double* po = poses_of(d, sslot);
   const double* pin = stage == 2 ? L.stage_odom + ((size_t)slot * 2 + par) * 8 : po;   // this scan's /odom/lidar
   li[LI_RUN] = 0; li[LI_REBUILD] = 0; li[LI_REBUILD_FB] = 0; li[LI_KF_ADDED] = 0; li[LI_OPTIMIZED] = 0; li[LI_FLAGS] = 0;
-  if (stage == 2 ? pin[7] == 0.0 : !d.scal[sslot * SC_COUNT + SC_ODOM_VALID]) return;  // no /odom/lidar on the initialising scan -> no mapping frame
+  if (stage == 2 ? pin[7] == 0.0 : !scal_of(d, sslot)[SC_ODOM_VALID]) return;  // no /odom/lidar on the initialising scan -> no mapping frame
   // laserOdomHandler :154-166
-  for (int k = 0; k < 3; ++k) ld[LD_T_O2L + k] = pin[k];
-  for (int k = 0; k < 4; ++k) ld[LD_Q_O2L + k] = pin[3 + k];
+  for (int k = 0; k < 3; ++k) ld[LD_T_O2L + k] = pin[PO_ODOM_T + k];
+  for (int k = 0; k < 4; ++k) ld[LD_Q_O2L + k] = pin[PO_ODOM_Q + k];
   const DQuat qm2o = ldq(ld + LD_Q_M2O), qo2l = ldq(ld + LD_Q_O2L);
   double r[3];
   dq_rotate(qm2o, ld + LD_T_O2L, r);
   for (int k = 0; k < 3; ++k) ld[LD_T_M2L + k] = r[k] + ld[LD_T_M2O + k];
   stq(ld + LD_Q_M2L, dq_mul(qm2o, qo2l));
-  for (int k = 0; k < 3; ++k) po[7 + k] = ld[LD_T_M2L + k];   // /odom_aft_mapped
-  for (int k = 0; k < 4; ++k) po[10 + k] = ld[LD_Q_M2L + k];
+  for (int k = 0; k < 3; ++k) po[PO_MAP_T + k] = ld[LD_T_M2L + k];   // /odom_aft_mapped
+  for (int k = 0; k < 4; ++k) po[PO_MAP_Q + k] = ld[LD_Q_M2L + k];
   // mainLoop gate :107-127
   const int run = (li[LI_FRAME] % d.P.lm_every) == 0;
   li[LI_FRAME] += 1;
@@ -112,13 +112,13 @@ __global__ void __launch_bounds__(LM_BLOCK) lm_prepare(DevCtx d, LmCtx L, int st
 // After it the front end may overwrite its per-scan buffers; lm_prepare(stage 2) reads only what was staged here.
 __global__ void __launch_bounds__(LM_BLOCK) lm_stage(DevCtx d, LmCtx L, int run_hint, int par) {
   const int slot = blockIdx.z + d.slot0, kind = blockIdx.y;
-  const int cur = d.scal[slot * SC_COUNT + SC_CUR];  // LO has completed: features of this scan
+  const int cur = scal_of(d, slot)[SC_CUR];  // LO has completed: features of this scan
   int* li = lip(L, slot);
   if (run_hint != 0) {
-    const size_t fb = (size_t)slot * 2 + cur;
-    const int n_c = d.feat_cnt[fb * 4 + F_LSHARP], n_s = d.scal[slot * SC_COUNT + SC_FE_ERR] ? 0 : d.feat_cnt[fb * 4 + F_LFLAT], n_o = d.scal[slot * SC_COUNT + SC_NOUT];
-    const float4* src_c = d.feat[F_LSHARP] + fb * d.fcap[F_LSHARP];
-    const float4* src_s = d.feat[F_LFLAT] + fb * d.fcap[F_LFLAT];
+    const size_t fb = fbuf(slot, cur);
+    const int n_c = feat_cnt_of(d, fb)[F_LSHARP], n_s = scal_of(d, slot)[SC_FE_ERR] ? 0 : feat_cnt_of(d, fb)[F_LFLAT], n_o = scal_of(d, slot)[SC_NOUT];
+    const float4* src_c = feat_of(d, F_LSHARP, fb);
+    const float4* src_s = feat_of(d, F_LFLAT, fb);
     const float4* src_o = d.outlier + (size_t)slot * d.N;
     const float4* src = kind == 0 ? src_c : (kind == 1 ? src_s : src_o);
     float4* dst = kind == 0 ? L.in_corner + (size_t)slot * L.in_cap_c : (kind == 1 ? L.in_surf + (size_t)slot * L.in_cap_s : L.in_outl + (size_t)slot * L.in_cap_o);
@@ -130,7 +130,7 @@ __global__ void __launch_bounds__(LM_BLOCK) lm_stage(DevCtx d, LmCtx L, int run_
   }
   if (blockIdx.x != 0 || kind != 0 || threadIdx.x >= 8) return;
   double* so = L.stage_odom + ((size_t)slot * 2 + par) * 8;
-  so[threadIdx.x] = threadIdx.x < 7 ? d.poses[(size_t)slot * 16 + threadIdx.x] : (d.scal[slot * SC_COUNT + SC_ODOM_VALID] ? 1.0 : 0.0);
+  so[threadIdx.x] = threadIdx.x < PO_MAP_T ? poses_of(d, slot)[threadIdx.x] : (scal_of(d, slot)[SC_ODOM_VALID] ? 1.0 : 0.0);
 }
 
 

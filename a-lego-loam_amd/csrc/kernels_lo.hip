@@ -130,22 +130,22 @@ extern "C" void alego_la_counts(unsigned long long* out) { (void)hipMemcpyFromSy
 // LG_KEEP:  // 5120 points: every cloud of a 16-ring sensor
 __global__ void __launch_bounds__(LG_T) lo_grid_build(DevCtx d) {
   const int slot = blockIdx.x + d.slot0, kind = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const size_t fb = (size_t)slot * 2 + cur_in_flight(d, slot);
-  const int tk = kind == 0 ? F_LFLAT : F_LSHARP;
-  const int n = (kind == 0 && d.scal[slot * SC_COUNT + SC_FE_ERR]) ? 0 : d.feat_cnt[fb * 4 + tk];   // (a slot whose fe_ring_out gave up has no less_flat cloud: dev_common.h)
-  const float4* pts = d.feat[tk] + fb * d.fcap[tk];
-  float4* cp = d.lo_cpts[kind] + fb * d.fcap[tk];
-  unsigned short* cell = d.lo_cell + (fb * 2 + kind) * (LO_GC + 2);
-  float* geom = d.lo_geom + (fb * 2 + kind) * 8;
+  const size_t fb = fbuf(slot, cur_in_flight(d, slot));
+  const int tk = lo_target(kind);
+  const int n = (kind == 0 && scal_of(d, slot)[SC_FE_ERR]) ? 0 : feat_cnt_of(d, fb)[tk];   // (a slot whose fe_ring_out gave up has no less_flat cloud: dev_common.h)
+  const float4* pts = lo_targets_of(d, kind, fb);
+  float4* cp = lo_cpts_of(d, kind, fb);
+  unsigned short* cell = lo_cell_of(d, lo_row(fb, kind));
+  float* geom = lo_geom_of(d, lo_row(fb, kind));
   __shared__ unsigned s_cnt[LO_GC / 2];
   __shared__ float s_red[4][LG_T / 64];
   __shared__ int s_tot[LG_T / 64];
-  if (n <= 0 || n > 65535) { if (tid == 0) geom[4] = __int_as_float(0); return; }
+  if (n <= 0 || n > 65535) { if (tid == 0) geom[LG_GX] = __int_as_float(0); return; }
   // the cloud's (x, y) extent from its bounding boxes (feature extraction wrote them next to the cloud: ~150 boxes instead of every point once more)
   float mn[2] = {3.402823466e+38f, 3.402823466e+38f}, mx[2] = {-3.402823466e+38f, -3.402823466e+38f};
   {
-    const float4* bx = d.lo_box + (fb * 2 + kind) * d.lo_box_cap * 2;
-    const int nbox = d.ring_boff[(fb * 2 + (kind == 0 ? 1 : 0)) * (d.NS + 1) + d.NS];
+    const float4* bx = lo_box_of(d, lo_row(fb, kind));
+    const int nbox = ring_boff_of(d, fb, lo_plane(kind))[d.NS];
     for (int b = tid; b < nbox; b += LG_T) { const float4 l = bx[2 * b], u = bx[2 * b + 1]; mn[0] = fminf(mn[0], l.x); mn[1] = fminf(mn[1], l.y); mx[0] = fmaxf(mx[0], u.x); mx[1] = fmaxf(mx[1], u.y); }
   }
 #pragma unroll
@@ -170,7 +170,7 @@ __global__ void __launch_bounds__(LG_T) lo_grid_build(DevCtx d) {
     csz *= 2.0f;
   }
   ok = ok && (long long)gx * gy <= LO_GC;
-  if (!ok) { if (tid == 0) geom[4] = __int_as_float(0); return; }
+  if (!ok) { if (tid == 0) geom[LG_GX] = __int_as_float(0); return; }
   const float inv = 1.0f / csz;   // (csz is a power of two: exact)
   const int ncell = gx * gy;
   auto cell_of = [&](const float4& p) -> int {
@@ -218,8 +218,8 @@ __global__ void __launch_bounds__(LG_T) lo_grid_build(DevCtx d) {
   for (int u = 0; u < LG_KEEP; ++u) { const int i = tid + u * LG_T; if (i < n) place(i, keep[u]); }
   for (int i = tid + LG_KEEP * LG_T; i < n; i += LG_T) place(i, pts[i]);
   if (tid == 0) {
-    geom[0] = mn[0]; geom[1] = mn[1]; geom[2] = inv; geom[3] = 0.999f * csz * csz;
-    geom[4] = __int_as_float(gx); geom[5] = __int_as_float(gy);
+    geom[LG_OX] = mn[0]; geom[LG_OY] = mn[1]; geom[LG_INV_CELL] = inv; geom[LG_SETTLE] = 0.999f * csz * csz;
+    geom[LG_GX] = __int_as_float(gx); geom[LG_GY] = __int_as_float(gy);
   }
 }
 // (ALEGO_LO_GRID toggled off: the buffer's clouds have just been rewritten, so the grid a later scan could find there — if the switch goes back on — is marked absent)
@@ -227,7 +227,7 @@ __global__ void lo_grid_off(DevCtx d) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= d.n_launch * 2) return;
   const int slot = i / 2 + d.slot0, kind = i & 1;
-  d.lo_geom[(((size_t)slot * 2 + cur_in_flight(d, slot)) * 2 + kind) * 8 + 4] = __int_as_float(0);
+  lo_geom_of(d, lo_row(fbuf(slot, cur_in_flight(d, slot)), kind))[LG_GX] = __int_as_float(0);
 }
 void launch_lo_grid(const DevCtx& d, hipStream_t st) {
   if (!d.opt_lo_grid) { ALEGO_LAUNCH(lo_grid_off, dim3((d.n_launch * 2 + 63) / 64), dim3(64), 0, st, d); return; }
@@ -243,31 +243,31 @@ DEV_INLINE void lo_assoc_body(const DevCtx& d, int box_lds_max, int slot, int qb
   constexpr int TPL = LO_CH / 16;
   constexpr int LO_QPB = BLKA / 16;
   const size_t fc = fidx_cur(d, slot), fl = fidx_last(d, slot);
-  const int* sc = d.scal + slot * SC_COUNT;
+  const int* sc = scal_of(d, slot);
   if (!sc[SC_LO_INIT]) return;
   const int lane = lane_id(), l16 = lane & 15;
-  const int qk = kind == 0 ? F_FLAT : F_SHARP, tk = kind == 0 ? F_LFLAT : F_LSHARP;
-  const int nq = d.feat_cnt[fc * 4 + qk];
+  const int qk = kind == 0 ? F_FLAT : F_SHARP, tk = lo_target(kind);
+  const int nq = feat_cnt_of(d, fc)[qk];
   if (qb0 * LO_QPB >= nq) return;
-  const int nt = (kind == 0 && sc[SC_FE_ERR]) ? 0 : d.feat_cnt[fl * 4 + tk];   // (fe_ring_out gave up on this slot: no less_flat targets, dev_common.h)
-  const float4* tg = d.feat[tk] + fl * d.fcap[tk];
-  const float4* bx = d.lo_box + (fl * 2 + kind) * d.lo_box_cap * 2;
-  const int* roff = d.ring_off + (fl * 2 + (kind == 0 ? 1 : 0)) * (d.NS + 1);
-  const int* boff = d.ring_boff + (fl * 2 + (kind == 0 ? 1 : 0)) * (d.NS + 1);
+  const int nt = (kind == 0 && sc[SC_FE_ERR]) ? 0 : feat_cnt_of(d, fl)[tk];   // (fe_ring_out gave up on this slot: no less_flat targets, dev_common.h)
+  const float4* tg = feat_of(d, tk, fl);
+  const float4* bx = lo_box_of(d, lo_row(fl, kind));
+  const int* roff = ring_off_of(d, fl, lo_plane(kind));
+  const int* boff = ring_boff_of(d, fl, lo_plane(kind));
   const int nch = nt > 0 ? boff[d.NS] : 0;
-  const double* st = d.lo_state + (size_t)slot * LO_STATE_N;
+  const double* st = lo_state_of(d, slot);
   LA_TICK0;
   __shared__ float s_sel[LO_QPB][4];
   __shared__ double s_pose[12];
   __shared__ float4 s_box[2 * BOXCAP];   // the boxes are read by every query of the workgroup: LDS when they fit
   __shared__ int s_roff[65], s_boff[65];
-  __shared__ float s_geom[8];
+  __shared__ float s_geom[LG_W];
   const bool box_lds = nch <= box_lds_max;   // (<= LO_BOX_LDS; the parity tests also run with 0 = boxes straight from HBM)
   if (box_lds) for (int i = threadIdx.x; i < 2 * nch; i += BLKA) s_box[i] = bx[i];
   for (int i = threadIdx.x; i <= d.NS; i += BLKA) { s_roff[i] = roff[i]; s_boff[i] = boff[i]; }
-  if (threadIdx.x < 8) s_geom[threadIdx.x] = d.opt_lo_grid ? d.lo_geom[(fl * 2 + kind) * 8 + threadIdx.x] : 0.f;
-  const float4* gpts = d.lo_cpts[kind] + fl * d.fcap[tk];
-  const unsigned short* gcell = d.lo_cell + (fl * 2 + kind) * (LO_GC + 2);
+  if (threadIdx.x < LG_W) s_geom[threadIdx.x] = d.opt_lo_grid ? lo_geom_of(d, lo_row(fl, kind))[threadIdx.x] : 0.f;
+  const float4* gpts = lo_cpts_of(d, kind, fl);
+  const unsigned short* gcell = lo_cell_of(d, lo_row(fl, kind));
   if (threadIdx.x == 0) {
     bool same = true;   // NaN (nothing cached yet) or a pose written by alego_set_lo_params compares unequal
 #pragma unroll
@@ -290,7 +290,7 @@ DEV_INLINE void lo_assoc_body(const DevCtx& d, int box_lds_max, int slot, int qb
   if (threadIdx.x < LO_QPB) {  // transformToStart once per query, shared through LDS
     const int q = min((int)(qb * LO_QPB + threadIdx.x), nq - 1);
     float o[3];
-    transform_to_start(s_pose, s_pose + 9, d.feat[qk][fc * d.fcap[qk] + q], o);
+    transform_to_start(s_pose, s_pose + 9, feat_of(d, qk, fc)[q], o);
     s_sel[threadIdx.x][0] = o[0]; s_sel[threadIdx.x][1] = o[1]; s_sel[threadIdx.x][2] = o[2];
   }
   __syncthreads();
@@ -356,9 +356,9 @@ DEV_INLINE void lo_assoc_body(const DevCtx& d, int box_lds_max, int slot, int qb
     unsigned long long gbest = ~0ull;
     bool settled = false;
     {
-      const int ggx = __float_as_int(s_geom[4]), ggy = __float_as_int(s_geom[5]);
+      const int ggx = __float_as_int(s_geom[LG_GX]), ggy = __float_as_int(s_geom[LG_GY]);
       if (ggx > 0) {
-        const int cx = (int)floorf((sx - s_geom[0]) * s_geom[2]), cy = (int)floorf((sy - s_geom[1]) * s_geom[2]);
+        const int cx = (int)floorf((sx - s_geom[LG_OX]) * s_geom[LG_INV_CELL]), cy = (int)floorf((sy - s_geom[LG_OY]) * s_geom[LG_INV_CELL]);
         const int x0 = max(cx - 1, 0), x1 = min(cx + 1, ggx - 1);
         int a0[3], a1[3];
 #pragma unroll
@@ -380,7 +380,7 @@ DEV_INLINE void lo_assoc_body(const DevCtx& d, int box_lds_max, int slot, int qb
           }
         }
         gbest = group_min_u64<16>(gbest);
-        settled = gbest != ~0ull && d_i2f((int32_t)(gbest >> 32)) < s_geom[3];
+        settled = gbest != ~0ull && d_i2f((int32_t)(gbest >> 32)) < s_geom[LG_SETTLE];
       }
     }
     unsigned long long bj = gbest;
@@ -524,7 +524,7 @@ DEV_INLINE void lo_assoc_body(const DevCtx& d, int box_lds_max, int slot, int qb
   }
   LA_TICK(8);
   if (l16 == 0 && store) {
-    int* row = d.lo_corr + ((size_t)slot * (d.lo_qcap_surf + d.lo_qcap_corner) + (kind == 0 ? 0 : d.lo_qcap_surf) + q) * 4;
+    int* row = lo_corr_of(d, slot, kind, q);
     const bool ok = kind == 0 ? (idx2 >= 0 && idx3 >= 0) : (idx2 >= 0);
     row[0] = q; row[1] = ok ? closest : -1; row[2] = idx2; row[3] = idx3;
   }
@@ -540,11 +540,11 @@ __global__ void __launch_bounds__(LO_BLOCK) lo_assoc(DevCtx d, int box_lds_max) 
 template <int BLK>
 DEV_INLINE void lo_eval_rows(const DevCtx& d, int slot, int kind, int n, const PoseTerms& T, double acc[28]) {
   const int qk = kind == 0 ? F_FLAT : F_SHARP, tk = kind == 0 ? F_LFLAT : F_LSHARP;
-  const float4* qpts = d.feat[qk] + fidx_cur(d, slot) * d.fcap[qk];
-  const float4* tg = d.feat[tk] + fidx_last(d, slot) * d.fcap[tk];
-  const int* rows = d.lo_corr + ((size_t)slot * (d.lo_qcap_surf + d.lo_qcap_corner) + (kind == 0 ? 0 : d.lo_qcap_surf)) * 4;
+  const float4* qpts = feat_of(d, qk, fidx_cur(d, slot));
+  const float4* tg = feat_of(d, tk, fidx_last(d, slot));
+  const int* rows = lo_corr_of(d, slot, kind);
   for (int i = threadIdx.x; i < n; i += BLK) {
-    const int4 r = *reinterpret_cast<const int4*>(rows + (size_t)i * 4);
+    const int4 r = *reinterpret_cast<const int4*>(rows + (size_t)i * LC_W);
     if (r.y < 0) continue;
     const float4 pc = qpts[r.x], pa = tg[r.y], pb = tg[r.z];
     const double cp[3] = {pc.x, pc.y, pc.z}, a[3] = {pa.x, pa.y, pa.z}, b[3] = {pb.x, pb.y, pb.z};
@@ -576,13 +576,13 @@ struct LoRowsLds { float v[12][LO_LDS_ROWS]; };   // c xyz, a xyz, b xyz, m xyz
 template <int BLK>
 DEV_INLINE void lo_stage_rows(const DevCtx& d, int slot, int kind, int n, int off, LoRowsLds& R, unsigned& okm) {
   const int qk = kind == 0 ? F_FLAT : F_SHARP, tk = kind == 0 ? F_LFLAT : F_LSHARP;
-  const float4* qpts = d.feat[qk] + fidx_cur(d, slot) * d.fcap[qk];
-  const float4* tg = d.feat[tk] + fidx_last(d, slot) * d.fcap[tk];
-  const int* rows = d.lo_corr + ((size_t)slot * (d.lo_qcap_surf + d.lo_qcap_corner) + (kind == 0 ? 0 : d.lo_qcap_surf)) * 4;
+  const float4* qpts = feat_of(d, qk, fidx_cur(d, slot));
+  const float4* tg = feat_of(d, tk, fidx_last(d, slot));
+  const int* rows = lo_corr_of(d, slot, kind);
   okm = 0;
   int k = 0;
   for (int i = threadIdx.x; i < n; i += BLK, ++k) {
-    const int4 r = *reinterpret_cast<const int4*>(rows + (size_t)i * 4);
+    const int4 r = *reinterpret_cast<const int4*>(rows + (size_t)i * LC_W);
     const bool ok = r.y >= 0;
     const float4 pc = qpts[ok ? r.x : 0], pa = tg[ok ? r.y : 0], pb = tg[ok ? r.z : 0], pm = tg[(ok && kind == 0) ? r.w : 0];
     const int j = off + i;
@@ -608,8 +608,8 @@ DEV_INLINE void lo_eval_staged(int n, int off, const LoRowsLds& R, unsigned okm,
 template <int BLK, bool STAGED>   // STAGED: the handle's row capacities fit LO_LDS_ROWS (decided at launch: fixed by the geometry / parameters)
 DEV_INLINE void lo_solve_body(const DevCtx& d, int phase, int slot) {
   const int cur = cur_in_flight(d, slot);
-  int* sc = d.scal + slot * SC_COUNT;
-  double* st = d.lo_state + (size_t)slot * LO_STATE_N;
+  int* sc = scal_of(d, slot);
+  double* st = lo_state_of(d, slot);
   extern __shared__ __attribute__((aligned(16))) unsigned char lo_smem[];
   double* s_acc = reinterpret_cast<double*>(lo_smem);                // [28][BLK]
   double* s_seg = s_acc + 28 * (BLK / 4);                        // [28][BLK/128]
@@ -620,7 +620,7 @@ DEV_INLINE void lo_solve_body(const DevCtx& d, int phase, int slot) {
   if (!sc[SC_LO_INIT]) {  // :316-324
     if (phase == 1 && threadIdx.x == 0) {
       sc[SC_LO_INIT] = 1; sc[SC_LO_FLAGS] = 1; sc[SC_LO_NSURF] = 0; sc[SC_LO_NCORNER] = 0; sc[SC_CUR] = cur;
-      sc[SC_ODOM_VALID] = 0; d.scal[scan_slot_of(d, slot) * SC_COUNT + SC_ODOM_VALID] = 0;   // (the scan's own entry is what LaserMapping reads)
+      sc[SC_ODOM_VALID] = 0; scal_of(d, scan_slot_of(d, slot))[SC_ODOM_VALID] = 0;   // (the scan's own entry is what LaserMapping reads)
     }
     return;
   }
@@ -628,14 +628,14 @@ DEV_INLINE void lo_solve_body(const DevCtx& d, int phase, int slot) {
   const long long tk0_ = wall_clock64();
   if (threadIdx.x == 0 && slot == d.slot0) lo_times[7] += 1;
 #endif
-  const int nq_s = d.feat_cnt[fidx_cur(d, slot) * 4 + F_FLAT];
-  const int nq_c = d.feat_cnt[fidx_cur(d, slot) * 4 + F_SHARP];
+  const int nq_s = feat_cnt_of(d, fidx_cur(d, slot))[F_FLAT];
+  const int nq_c = feat_cnt_of(d, fidx_cur(d, slot))[F_SHARP];
   // count the correspondences of the kind associated just before this call
   {
     const int n = phase == 0 ? nq_s : nq_c;
-    const int* rows = d.lo_corr + ((size_t)slot * (d.lo_qcap_surf + d.lo_qcap_corner) + (phase == 0 ? 0 : d.lo_qcap_surf)) * 4;
+    const int* rows = lo_corr_of(d, slot, phase);
     int c = 0;
-    for (int i = threadIdx.x; i < n; i += BLK) c += rows[(size_t)i * 4 + 1] >= 0;
+    for (int i = threadIdx.x; i < n; i += BLK) c += rows[(size_t)i * LC_W + LC_CLOSEST] >= 0;
     c = bfly_sum_i32(c);
     if (lane_id() == 0) s_cnt[threadIdx.x >> 6] = c;
     __syncthreads();
@@ -731,9 +731,9 @@ DEV_INLINE void lo_solve_body(const DevCtx& d, int phase, int slot) {
 #pragma unroll
       for (int k = 0; k < 9; ++k) st[LS_RW + k] = nr[k];
       const DQuat q = dq_from_mat(nr);
-      double* po = d.poses + (size_t)scan_slot_of(d, slot) * 16;   // /odom/lidar of this scan (its lane's entry when scans are processed ahead)
-      po[0] = nt[0]; po[1] = nt[1]; po[2] = nt[2]; po[3] = q.w; po[4] = q.x; po[5] = q.y; po[6] = q.z;
-      sc[SC_ODOM_VALID] = 1; d.scal[scan_slot_of(d, slot) * SC_COUNT + SC_ODOM_VALID] = 1;
+      double* po = poses_of(d, scan_slot_of(d, slot));   // /odom/lidar of this scan (its lane's entry when scans are processed ahead)
+      po[PO_ODOM_T] = nt[0]; po[PO_ODOM_T + 1] = nt[1]; po[PO_ODOM_T + 2] = nt[2]; po[PO_ODOM_Q] = q.w; po[PO_ODOM_Q + 1] = q.x; po[PO_ODOM_Q + 2] = q.y; po[PO_ODOM_Q + 3] = q.z;
+      sc[SC_ODOM_VALID] = 1; scal_of(d, scan_slot_of(d, slot))[SC_ODOM_VALID] = 1;
       sc[SC_CUR] = cur;  // surf_last_ / corner_last_ <- this scan's features (:531-534)
     }
   }
@@ -794,25 +794,25 @@ int lo_configure() {
 // removal, the f32 rotation of the acceleration) is done by the host in alego_lo_push_imu: smp[i] = time, roll, pitch, yaw, acc xyz.
 __global__ void lo_imu_push(DevCtx d, int slot, const double* smp, int n) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  int* ptr = d.imu_ptr + (size_t)slot * 4;
-  double* ring = d.imu_ring + (size_t)slot * ALEGO_IMU_Q * 10;
-  int last = ptr[0], front = ptr[1];
+  int* ptr = imu_ptr_of(d, slot);
+  double* ring = imu_ring_of(d, slot);
+  int last = ptr[IMP_LAST], front = ptr[IMP_FRONT];
   for (int i = 0; i < n; ++i) {
     const double* s = smp + 7 * i;
     last = (last + 1) % ALEGO_IMU_Q;                                                  // :773-777
     if ((last + 1) % ALEGO_IMU_Q == front) front = (front + 1) % ALEGO_IMU_Q;
-    double* r = ring + last * 10;
-    r[0] = s[0]; r[1] = s[1]; r[2] = s[2]; r[3] = s[3];
-    const double* b = ring + ((last - 1 + ALEGO_IMU_Q) % ALEGO_IMU_Q) * 10;
-    const double td = r[0] - b[0];
+    double* r = imu_row(ring, last);
+    r[IMU_TIME] = s[0]; r[IMU_RPY] = s[1]; r[IMU_RPY + 1] = s[2]; r[IMU_RPY + 2] = s[3];
+    const double* b = imu_row(ring, (last - 1 + ALEGO_IMU_Q) % ALEGO_IMU_Q);
+    const double td = r[IMU_TIME] - b[IMU_TIME];
     if (td < 1.) {                                                                    // :793-802
       for (int k = 0; k < 3; ++k) {
-        r[4 + k] = b[4 + k] + b[7 + k] * td + s[4 + k] * td * td * 0.5;
-        r[7 + k] = b[7 + k] + s[4 + k] * td;
+        r[IMU_SHIFT + k] = b[IMU_SHIFT + k] + b[IMU_VELO + k] * td + s[4 + k] * td * td * 0.5;
+        r[IMU_VELO + k] = b[IMU_VELO + k] + s[4 + k] * td;
       }
     }
   }
-  ptr[0] = last; ptr[1] = front;
+  ptr[IMP_LAST] = last; ptr[IMP_FRONT] = front;
 }
 
 DEV_INLINE void dsk_mul3(const float m[3][3], const float v[3], float o[3]) {   // Eigen's unrolled 3-term reduction: a0 + (a1 + a2)
@@ -826,16 +826,16 @@ DEV_INLINE void dsk_mul3(const float m[3][3], const float v[3], float o[3]) {   
 // point's own first ring step with cur_time < imu_time_: a binary search per point + a max-scan in point order.  The first point
 // whose cursor entry is more than scan_period away aborts the function (:604-608): it and everything after it stay as they are.
 #define DSK_T 256
-__global__ void __launch_bounds__(DSK_T) lo_deskew(DevCtx d) {
+__global__ void __launch_bounds__(DSK_T, 5) lo_deskew(DevCtx d) {   // (5 wavefronts per SIMD = 96 VGPRs, which it needs and no more)
   const int slot = blockIdx.x + d.slot0, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const size_t base = (size_t)slot * d.N;
-  const int M = d.scal[(size_t)slot * SC_COUNT + SC_M];
+  const int M = scal_of(d, (size_t)slot)[SC_M];
   const float4* in = d.seg_pts + base;
   float4* out = d.seg_dsk + base;
-  int* ptr = d.imu_ptr + (size_t)slot * 4;
-  const double* ring = d.imu_ring + (size_t)slot * ALEGO_IMU_Q * 10;
-  const int last = ptr[0], it0 = ptr[2];
-  if (tid == 0) d.scal[(size_t)slot * SC_COUNT + SC_M_DSK] = M;   // (what alego_lo_get_undistorted copies: SC_M belongs to ImageProjection, which may already be a scan ahead)
+  int* ptr = imu_ptr_of(d, slot);
+  const double* ring = imu_ring_of(d, slot);
+  const int last = ptr[IMP_LAST], it0 = ptr[IMP_LAST_ITER];
+  if (tid == 0) scal_of(d, (size_t)slot)[SC_M_DSK] = M;   // (what alego_lo_get_undistorted copies: SC_M belongs to ImageProjection, which may already be a scan ahead)
   if (!(last > 0)) {                                                                  // :593
     for (int i = tid; i < M; i += DSK_T) out[i] = in[i];
     return;
@@ -843,10 +843,10 @@ __global__ void __launch_bounds__(DSK_T) lo_deskew(DevCtx d) {
   __shared__ double s_time[ALEGO_IMU_Q];
   __shared__ int s_wmax[DSK_T / 64], s_abort, s_front_a, s_iter_a;
   __shared__ float s_start[15];   // shift_start, velo_start, r_s_i
-  for (int j = tid; j < ALEGO_IMU_Q; j += DSK_T) s_time[j] = ring[j * 10];
+  for (int j = tid; j < ALEGO_IMU_Q; j += DSK_T) s_time[j] = imu_row(ring, j)[IMU_TIME];
   if (tid == 0) { s_abort = 0x7fffffff; s_front_a = -1; s_iter_a = -1; }
   const int H = d.H;
-  const float so = d.ori[(size_t)slot * 4], eo = d.ori[(size_t)slot * 4 + 1];
+  const float so = ori_of(d, (size_t)slot)[0], eo = ori_of(d, (size_t)slot)[1];
   int start_ori = (int)(((double)so + 2 * M_PI) / H), end_ori = (int)(((double)eo + 2 * M_PI) / H);   // :562-563 (sic)
   if (start_ori >= H) start_ori -= H;
   if (end_ori >= H) end_ori -= H;
@@ -885,17 +885,17 @@ __global__ void __launch_bounds__(DSK_T) lo_deskew(DevCtx d) {
     const bool process = valid && i < a;
     float rpy[3] = {0, 0, 0}, sh[3] = {0, 0, 0}, ve[3] = {0, 0, 0}, rc[3][3];
     if (process) {
-      const double* R = ring + front * 10;
+      const double* R = imu_row(ring, front);
       if (cur_time > s_time[front]) {                                                 // :610-621
-        rpy[0] = (float)R[1]; rpy[1] = (float)R[2]; rpy[2] = (float)R[3];
+        rpy[0] = (float)R[IMU_RPY]; rpy[1] = (float)R[IMU_RPY + 1]; rpy[2] = (float)R[IMU_RPY + 2];
 #pragma unroll
-        for (int q = 0; q < 3; ++q) { sh[q] = (float)R[4 + q]; ve[q] = (float)R[7 + q]; }
+        for (int q = 0; q < 3; ++q) { sh[q] = (float)R[IMU_SHIFT + q]; ve[q] = (float)R[IMU_VELO + q]; }
       } else {                                                                        // :622-637
-        const double* B = ring + ((front - 1 + ALEGO_IMU_Q) % ALEGO_IMU_Q) * 10;
-        const double rf = (cur_time - B[0]) / (R[0] - B[0]), rb = 1. - rf;
-        rpy[0] = (float)(R[1] * rf + B[1] * rb); rpy[1] = (float)(R[2] * rf + B[2] * rb); rpy[2] = (float)(R[3] * rf + B[3] * rb);
+        const double* B = imu_row(ring, (front - 1 + ALEGO_IMU_Q) % ALEGO_IMU_Q);
+        const double rf = (cur_time - B[IMU_TIME]) / (R[IMU_TIME] - B[IMU_TIME]), rb = 1. - rf;
+        rpy[0] = (float)(R[IMU_RPY] * rf + B[IMU_RPY] * rb); rpy[1] = (float)(R[IMU_RPY + 1] * rf + B[IMU_RPY + 1] * rb); rpy[2] = (float)(R[IMU_RPY + 2] * rf + B[IMU_RPY + 2] * rb);
 #pragma unroll
-        for (int q = 0; q < 3; ++q) { sh[q] = (float)(R[4 + q] * rf + B[4 + q] * rb); ve[q] = (float)(R[7 + q] * rf + B[7 + q] * rb); }
+        for (int q = 0; q < 3; ++q) { sh[q] = (float)(R[IMU_SHIFT + q] * rf + B[IMU_SHIFT + q] * rb); ve[q] = (float)(R[IMU_VELO + q] * rf + B[IMU_VELO + q] * rb); }
       }
       const float kp[6] = {0.f, 0.f, 0.f, rpy[0], rpy[1], rpy[2]};
       float m[3][4];
@@ -937,15 +937,15 @@ __global__ void __launch_bounds__(DSK_T) lo_deskew(DevCtx d) {
     if (a != 0x7fffffff) {   // aborted inside this chunk: the rest of the cloud stays as it is
       for (int j = c0 + DSK_T + tid; j < M; j += DSK_T) out[j] = in[j];
       if (tid == 0) {
-        ptr[1] = s_front_a;
-        ptr[2] = s_iter_a >= 0 ? s_iter_a : (a == 0 ? it0 : (it0 + carry) % ALEGO_IMU_Q);
+        ptr[IMP_FRONT] = s_front_a;
+        ptr[IMP_LAST_ITER] = s_iter_a >= 0 ? s_iter_a : (a == 0 ? it0 : (it0 + carry) % ALEGO_IMU_Q);
       }
       return;
     }
     carry = total;
     __syncthreads();
   }
-  if (tid == 0 && M > 0) { ptr[1] = (it0 + carry) % ALEGO_IMU_Q; ptr[2] = (it0 + carry) % ALEGO_IMU_Q; }
+  if (tid == 0 && M > 0) { ptr[IMP_FRONT] = (it0 + carry) % ALEGO_IMU_Q; ptr[IMP_LAST_ITER] = (it0 + carry) % ALEGO_IMU_Q; }
 }
 
 // per-scan pose log (alego_trajectory_*): what a bag replay publishes on /odom/lidar and /odom_aft_mapped, kept on the device so that
@@ -956,16 +956,16 @@ __global__ void traj_log(DevCtx d, const double* staged_odom, int par) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= d.n_launch) return;
   const int slot = i + d.slot0;
-  const int k = d.traj_n[slot];
-  d.traj_n[slot] = k + 1;
+  const int k = *traj_n_of(d, slot);
+  *traj_n_of(d, slot) = k + 1;
   if (k >= d.traj_cap) return;
-  const double* po = d.poses + (size_t)slot * 16;
+  const double* po = poses_of(d, slot);
   const double* od = staged_odom ? staged_odom + ((size_t)slot * 2 + par) * 8 : po;
-  double* o = d.traj + ((size_t)slot * d.traj_cap + k) * 14;
+  double* o = traj_of(d, slot, k);
 #pragma unroll
-  for (int j = 0; j < 7; ++j) o[j] = od[j];
+  for (int j = 0; j < PO_MAP_T; ++j) o[j] = od[j];
 #pragma unroll
-  for (int j = 7; j < 14; ++j) o[j] = po[j];
+  for (int j = PO_MAP_T; j < PO_LOG_W; ++j) o[j] = po[j];
 }
 void launch_traj_log(const DevCtx& d, hipStream_t st, const double* staged_odom, int par) {
   hipLaunchKernelGGL(traj_log, dim3((d.n_launch + 63) / 64), dim3(64), 0, st, d, staged_odom, par);

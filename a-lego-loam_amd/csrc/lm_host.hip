@@ -311,16 +311,16 @@ int lm_host_process_host(LmHost* lm, const DevCtx& dfull, const alego_point* cor
   const int nin[3] = {n_corner, n_surf, n_outlier};
   up(L.li + LI_NIN_C, nin, sizeof(nin));
   double po[7] = {odom->t[0], odom->t[1], odom->t[2], odom->q[0], odom->q[1], odom->q[2], odom->q[3]};
-  up(d.poses, po, sizeof(po));
+  up(poses_of(d, 0) + PO_ODOM_T, po, sizeof(po));   // (the single-scan entry points work on slot 0)
   const int one = 1;
-  up(d.scal + SC_ODOM_VALID, &one, sizeof(int));
+  up(scal_of(d, 0) + SC_ODOM_VALID, &one, sizeof(int));
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) { *err = std::string("alego_lm_process: upload failed: ") + hipGetErrorString(e); return ALEGO_ERR_HIP; }
   clear_run_flags_outside(lm, d);
   if (int r = lm_sequence(lm, d, 0, std::vector<char>(1, 1), err)) return r;
-  double out[16], ld[LD_COUNT];
+  double out[PO_W], ld[LD_COUNT];
   int li[LI_COUNT];
-  e = hipMemcpyAsync(out, d.poses, sizeof(out), hipMemcpyDeviceToHost, st);
+  e = hipMemcpyAsync(out, poses_of(d, 0), sizeof(out), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipMemcpyAsync(ld, L.ld, sizeof(ld), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipMemcpyAsync(li, L.li, sizeof(li), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -332,8 +332,8 @@ int lm_host_process_host(LmHost* lm, const DevCtx& dfull, const alego_point* cor
     return ALEGO_ERR_CAPACITY;
   }
   if (map_pose) {
-    for (int i = 0; i < 3; ++i) map_pose->t[i] = out[7 + i];
-    for (int i = 0; i < 4; ++i) map_pose->q[i] = out[10 + i];
+    for (int i = 0; i < 3; ++i) map_pose->t[i] = out[PO_MAP_T + i];
+    for (int i = 0; i < 4; ++i) map_pose->q[i] = out[PO_MAP_Q + i];
     for (int i = 0; i < 6; ++i) map_pose->params[i] = ld[LD_PARAMS + i];
     map_pose->valid = 1;
   }

@@ -68,6 +68,33 @@ def test_device_memory_has_one_owner():
             assert name not in txt or f in where, f"{f} names {name}"
 
 
+FRONT_END_ARRAYS = ("scal", "feat", "feat_idx", "feat_cnt", "ring_off", "ring_boff", "lo_box", "lo_cpts", "lo_cell", "lo_geom", "lo_corr", "st_idx", "st_cnt",
+                    "st_lfds", "row_cnt", "ipb_col", "ipb_off", "poses", "traj", "traj_n", "lo_state", "imu_ring", "imu_ptr", "ring_start", "ring_end", "ori",
+                    "fe_sync")
+
+
+def test_front_end_arrays_have_one_layout():
+    """The layout of DevCtx's structured per-slot arrays is defined in one place: csrc/fe_store.h.  No other file under csrc/ indexes or offsets one of
+    them (the member followed by `[` or `+`; a null test and the address taken for allocation remain), and none multiplies by SC_COUNT, LO_STATE_N or
+    ALEGO_IMU_Q."""
+    import re
+    csrc = os.path.join(ROOT, "a-lego-loam_amd", "csrc")
+    files = sorted(os.listdir(csrc))
+    assert "fe_store.h" in files
+    member = re.compile(r"(?:\.|->)\s*(" + "|".join(FRONT_END_ARRAYS) + r")\s*[\[+]")
+    address = re.compile(r"&\s*[\w.>-]*(?:\.|->)(feat|feat_idx|lo_cpts)\[\w+\]\s*[,)]")   # &d.feat[k] handed to the allocator: the member arrays of pointers
+    stride = re.compile(r"\*\s*(SC_COUNT|LO_STATE_N|ALEGO_IMU_Q)\b|\b(SC_COUNT|LO_STATE_N|ALEGO_IMU_Q)\s*\*")
+    bad = []
+    for f in files:
+        if f == "fe_store.h":
+            continue
+        for no, line in enumerate(open(os.path.join(csrc, f), errors="ignore"), 1):
+            code = address.sub("", line.split("//")[0])
+            if member.search(code) or stride.search(code):
+                bad.append(f"{f}:{no}: {line.strip()[:120]}")
+    assert not bad, "\n".join(bad)
+
+
 def test_cpp_example_fails_loudly_without_a_gpu():
     """examples/replay.cpp drives the C ABI from plain C++.  In a container without an MI355X it must stop at alego_create with
     ALEGO_ERR_NO_DEVICE — there is no CPU fallback for the product path (on the GPU box tests/test_gpu_parity.py runs it for real)."""
