@@ -36,6 +36,7 @@ EXPORTS = [
     "alego_graph_optimize", "alego_graph_get_estimate", "alego_graph_residuals",
     "alego_loc_select", "alego_loc_enable", "alego_loc_status",
     "alego_reloc_enable", "alego_loc_relocalize", "alego_reloc_descriptor", "alego_reloc_match", "alego_debug_reloc_search",
+    "alego_loop_appearance_enable", "alego_loop_search_appearance", "alego_loop_appearance_candidates",
 ]
 
 REPLAY_PINGPONG = 0x100
@@ -124,6 +125,15 @@ class RelocResult(C.Structure):
                 ("verified", C.c_int32), ("converged", C.c_int32), ("iterations", C.c_int32), ("n_source", C.c_int32), ("n_target", C.c_int32),
                 ("applied", C.c_int32), ("fitness", C.c_double), ("correction", C.c_float * 16), ("guess6", C.c_float * 6), ("t_map", C.c_float * 16),
                 ("rc", C.c_double * 12), ("params6", C.c_double * 6)]
+
+
+class LoopAppOpts(C.Structure):
+    _fields_ = [("n_cand", C.c_int32), ("verify", C.c_int32), ("max_dist", C.c_int32), ("max_jump", C.c_double), ("fitness_max", C.c_double)]
+
+
+class LoopAppInfo(C.Structure):
+    _fields_ = [("n_eligible", C.c_int32), ("n_cand", C.c_int32), ("cand_id", C.c_int32 * 8), ("cand_dist", C.c_int32 * 8), ("cand_shift", C.c_int32 * 8),
+                ("verified", C.c_int32), ("guess6", C.c_float * 6), ("icp_final", C.c_float * 16)]
 
 
 class GraphEdge(C.Structure):
@@ -346,6 +356,10 @@ def lib():
         L.alego_reloc_descriptor.argtypes = [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
         L.alego_reloc_match.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.alego_debug_reloc_search.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.alego_loop_appearance_enable.argtypes = [C.c_void_p, C.c_double, C.c_double]
+        L.alego_loop_search_appearance.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(LoopAppOpts), C.POINTER(LoopResult), C.POINTER(LoopAppInfo)]
+        L.alego_loop_appearance_candidates.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32,
+                                                       C.c_void_p, C.c_void_p, C.c_void_p]
         L.alego_write_pcd.argtypes = [C.c_char_p, C.c_void_p, C.c_int32]
         L.alego_bag_read_pc2.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
         if L.alego_params_sizeof() != C.sizeof(AlegoParams):
@@ -423,6 +437,20 @@ def reloc_match(q, m):
     if rc != 0:
         raise AlegoError(f"alego_reloc_match failed ({rc})")
     return int(d.value), int(sh.value)
+
+
+def loop_appearance_candidates(desc, keyposes6, stamps, min_time_gap, max_jump=0.0, max_dist=0, n_cand=4):
+    """alego_loop_appearance_candidates: (ids, dists, shifts) of the candidates of the newest frame among the older ones (host code of the library)"""
+    d = np.ascontiguousarray(desc, np.uint8).reshape(-1, RELOC_SECTORS * RELOC_RINGS)
+    kp = np.ascontiguousarray(keyposes6, np.float32).reshape(-1, 6)
+    st = np.ascontiguousarray(stamps, np.float64).reshape(-1)
+    assert kp.shape[0] == d.shape[0] == st.shape[0]
+    ids, dists, shifts = (np.zeros(RELOC_MAX_CAND, np.int32) for _ in range(3))
+    k = lib().alego_loop_appearance_candidates(d.ctypes.data, kp.ctypes.data, st.ctypes.data, d.shape[0], float(min_time_gap), float(max_jump), int(max_dist),
+                                               int(n_cand), ids.ctypes.data, dists.ctypes.data, shifts.ctypes.data)
+    if k < 0:
+        raise AlegoError(f"alego_loop_appearance_candidates failed ({k})")
+    return ids[:k].copy(), dists[:k].copy(), shifts[:k].copy()
 
 
 def _reloc_result(r):
@@ -884,6 +912,28 @@ class Handle:
         out = (LoopResult * max(sl.shape[0], 1))()
         self._check(lib().alego_loop_search(self._h, sl.ctypes.data, sl.shape[0], out), "alego_loop_search")
         return [_loop_result(out[i]) for i in range(sl.shape[0])]
+
+    # ---- loop closures by appearance (needs map_enable) ----
+    def loop_appearance_enable(self, max_range=0.0, z_offset=float("nan")):
+        self._check(lib().alego_loop_appearance_enable(self._h, float(max_range), float(z_offset)), "alego_loop_appearance_enable")
+
+    def loop_search_appearance(self, slots, n_cand=0, verify=-1, max_dist=0, max_jump=0.0, fitness_max=0.0):
+        """alego_loop_search_appearance: one dict per listed slot — loop_search's keys (T = the world correction: graph_add_loops takes the dicts
+        unchanged) plus n_eligible, n_cand, cand_id, cand_dist, cand_shift, verified, guess6, icp_final"""
+        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        out = (LoopResult * max(sl.shape[0], 1))()
+        info = (LoopAppInfo * max(sl.shape[0], 1))()
+        opts = LoopAppOpts(int(n_cand), int(verify), int(max_dist), float(max_jump), float(fitness_max))
+        self._check(lib().alego_loop_search_appearance(self._h, sl.ctypes.data, sl.shape[0], C.byref(opts), out, info), "alego_loop_search_appearance")
+        res = []
+        for i in range(sl.shape[0]):
+            d, f = _loop_result(out[i]), info[i]
+            k = int(f.n_cand)
+            d.update(n_eligible=int(f.n_eligible), n_cand=k, cand_id=np.array(f.cand_id[:k], np.int32), cand_dist=np.array(f.cand_dist[:k], np.int32),
+                     cand_shift=np.array(f.cand_shift[:k], np.int32), verified=int(f.verified), guess6=np.array(f.guess6[:], np.float32),
+                     icp_final=np.array(f.icp_final[:], np.float32).reshape(4, 4))
+            res.append(d)
+        return res
 
     # ---- localisation against a frozen key-frame map ----
     def loc_enable(self, frames, radius=0.0):

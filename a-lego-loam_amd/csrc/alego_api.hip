@@ -1299,6 +1299,33 @@ int alego_debug_reloc_search(alego_handle* h, const uint8_t* map_desc, int32_t n
   return reloc_debug_search(&h->rl, map_desc, n_map, q_desc, n_q, n_cand, ids, dists, shifts, h->stream, &h->err);
 }
 
+// ---- loop closures by appearance (kernels_reloc.hip) ----
+int alego_loop_appearance_enable(alego_handle* h, double max_range, double z_offset) {
+  if (!h) return ALEGO_ERR_ARG;
+  if (int r = not_localising(h, "alego_loop_appearance_enable")) return r;
+  if (!h->map_on) { h->err = "alego_loop_appearance_enable: the key-frame archive is off (alego_map_enable first)"; return ALEGO_ERR_ARG; }
+  if (loop_app_enabled(h->rl)) { h->err = "alego_loop_appearance_enable: already enabled"; return ALEGO_ERR_ARG; }
+  hipSetDevice(h->device);
+  return loop_app_enable(&h->rl, *lm_host_ctx(h->lm), h->d.n_slots, max_range, z_offset, &h->err);
+}
+int alego_loop_search_appearance(alego_handle* h, const int32_t* slots, int32_t n, const alego_loop_app_opts* opts, alego_loop_result* out, alego_loop_app_info* info) {
+  if (!h || n < 0 || (n > 0 && (!slots || !out))) return ALEGO_ERR_ARG;
+  if (!loop_app_enabled(h->rl)) { h->err = "alego_loop_search_appearance: the appearance search is off (alego_map_enable, then alego_loop_appearance_enable)"; return ALEGO_ERR_ARG; }
+  alego_loop_app_opts o = {4, 1, 0, 0.0, 0.0};
+  if (opts) { if (opts->n_cand > 0) o.n_cand = opts->n_cand; if (opts->verify >= 0) o.verify = opts->verify; o.max_dist = opts->max_dist; o.max_jump = opts->max_jump; o.fitness_max = opts->fitness_max; }
+  if (o.n_cand > ALEGO_RELOC_MAX_CAND || o.verify > o.n_cand) { h->err = "alego_loop_search_appearance: n_cand is 1 .. ALEGO_RELOC_MAX_CAND, verify 0 .. n_cand"; return ALEGO_ERR_ARG; }
+  std::vector<char> seen((size_t)h->d.n_slots, 0);
+  for (int i = 0; i < n; ++i) {
+    if (slots[i] < 0 || slots[i] >= h->d.n_slots) { h->err = "alego_loop_search_appearance: slot out of range"; return ALEGO_ERR_ARG; }
+    if (seen[slots[i]]) { h->err = "alego_loop_search_appearance: slot " + std::to_string(slots[i]) + " is listed twice"; return ALEGO_ERR_ARG; }
+    seen[slots[i]] = 1;
+  }
+  hipSetDevice(h->device);
+  g_prof = &h->prof;
+  HIP_TRY(h, sync_all(h));   // behind everything already queued on every stream group
+  return loop_app_run(h->rl, &h->lc, *lm_host_ctx(h->lm), h->P, slots, n, o, out, info, h->stream, &h->err);
+}
+
 int alego_loc_status(alego_handle* h, int slot, int32_t out[4]) {
   if (int r = check_slot(h, slot)) return r;
   if (!out) return ALEGO_ERR_ARG;
@@ -1421,6 +1448,15 @@ int alego_debug_get(alego_handle* h, int slot, const char* name, void* out, int 
   HIP_TRY(h, hipMemcpyAsync(sc, scal_of(d, slot), sizeof(sc), hipMemcpyDeviceToHost, stream_of(h, slot)));
   HIP_TRY(h, hipStreamSynchronize(stream_of(h, slot)));
   const std::string s(name);
+  if (s.rfind("la_", 0) == 0) {   // the appearance search: the descriptors / ring keys of the slot's archived frames described so far, as bytes
+    const void* rsrc = nullptr;
+    size_t bytes = 0;
+    if (loop_app_debug_get(h->rl, slot, name, &rsrc, &bytes)) { h->err = std::string("debug_get: ") + name + " needs alego_loop_appearance_enable"; return ALEGO_ERR_ARG; }
+    if ((size_t)cap_bytes < bytes) { h->err = "debug_get: buffer too small"; return ALEGO_ERR_CAPACITY; }
+    if (bytes) HIP_TRY(h, hipMemcpy(out, rsrc, bytes, hipMemcpyDeviceToHost));
+    *count = (int)bytes; *dtype = 3;
+    return 0;
+  }
   if (s.rfind("rl_", 0) == 0) {   // relocalisation: descriptors as bytes; "rl_stats": pairs evaluated by the second round / pairs in all of the last search
     if (s == "rl_stats") {
       if (cap_bytes < 8) { h->err = "debug_get: buffer too small"; return ALEGO_ERR_CAPACITY; }

@@ -1,11 +1,12 @@
 // kernels_reloc.hip — alego_loc_relocalize: slots of a localising handle are placed in the frozen key-frame map
 // without an initial pose.  The rule is reloc_math.h's; everything here returns exactly what its brute force returns.
 //
-//   rl_desc      one workgroup per map frame (at alego_reloc_enable) or per listed slot: every point is read once, binned, and its code
-//                raised into an LDS word per bin with atomicMax (a maximum of integers does not depend on the order); the tile is then
-//                packed to bytes and the ring key summed from it
+//   rl_desc      one workgroup per map frame (at alego_reloc_enable), per listed slot, or per pending (slot, archived frame) of the
+//                appearance search: every point is read once, binned, and its code raised into an LDS word per bin with atomicMax (a
+//                maximum of integers does not depend on the order); the tile is then packed to bytes and the ring key summed from it
 //   rl_bound     one thread per (query, frame): B = sum over rings of |keyQ - keyM| (<= dist(Q, M, s) for every s)
-//   rl_pick      one workgroup per query: the n_cand frames smallest in (B, id)
+//   la_elig      (appearance search) one thread per (query, frame): B <- RL_INELIGIBLE unless the frame is eligible
+//   rl_pick      one workgroup per query: the n_cand eligible frames smallest in (B, id)
 //   rl_search    the hot path.  One wavefront per (query, frame) pair of a list, ONE LANE PER SHIFT: Q sits twice over in LDS (120 columns of
 //                5 words), so lane s reads column c + s — 5 words apart from its neighbour, and 5 is coprime to the 64 banks: no conflicts —
 //                while M's 300 words are wave-uniform (scalar loads).  v_sad_u8 sums four absolute byte differences per instruction; the
@@ -17,6 +18,27 @@
 //                (raw sub-map), from the map store through kf_store.h's views; VoxelGrid, lc_grid and lc_icp are kernels_loop.hip's (loop_ctx.h)
 //   rl_apply     one lane per accepted slot: map -> odom corrected as lm_apply_correction does, params_ replaced
 // Phase boundaries are kernel boundaries; no workgroup waits for another.
+//
+// Every query of the search kernels has a record (RlQuery): its row of the query descriptors, the first row and the number of the map
+// rows it is searched in, and where its rows of the scratch start.  Relocalisation searches every query in rows 0 .. N - 1 of one map.
+//
+// alego_loop_search_appearance is the same search for the slots of a SLAM handle against their OWN archive, for
+// revisits that detectLoopClosure's radius (kernels_loop.hip) cannot find because the drift exceeds it.  The rule is the project's own:
+//   store        a descriptor and a ring key per archived frame (its corner, surf and outlier clouds through rl_bin, unchanged), row
+//                slot * max_keyframes + frame; built lazily: a search first describes frames [described, nf) of the listed slots
+//                (archived clouds never change once stored), so the per-scan path launches nothing new
+//   query        the newest archived frame nf - 1 of a slot with no dropped frame
+//   eligible     frame i < nf - 1 with stamp[nf - 1] - stamp[i] > lc_min_time_gap (lc_detect's comparison) and, when max_jump > 0, the
+//                f32 squared distance ((dx dx) + dy dy) + dz dz of key poses i and nf - 1 < (float)(max_jump max_jump); a predicate
+//                per frame, not a prefix (alego_map_set_stamps)
+//   candidates   the n_cand eligible frames smallest in (D_i, i), D_i and s_i as reloc_math.h's MATCH: exactly the brute force over
+//                all eligible frames and all 60 shifts, with the ring-key bound and without; those with D_i > max_dist > 0 are dropped
+//   verify       candidate v in round v, the first accepted ends the slot: source = frame nf - 1 (surf, corner, outlier) under guess6 =
+//                key pose i with yaw rl_guess_yaw(yaw_i, s_i); target = frames [i - lc_search_num, i + lc_search_num] within [0, nf - 2]
+//                under their archived poses through VoxelGrid(lc_leaf); ICP and fitness are loop_attempts'; accepted when converged &&
+//                fitness <= fitness_max
+//   result       an alego_loop_result: t_correct / between = alego_loop_constraint(icp_final, guess6, key pose i); correction = the WORLD
+//                correction t_correct * matrix(key pose nf - 1)^-1 (f64 rigid inverse and product, rounded to f32)
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -47,15 +69,50 @@ struct RlSlot {
   double t_m2l[3], q_m2l[4];
 };
 
+// one record per query of the search kernels; off is filled in by rl_search_run
+struct RlQuery {
+  int qrow;        // row of qdesc / qkey
+  int base, n;     // searched in rows base .. base + n - 1 of mdesc / mkey; list entries and candidate ids are 0 .. n - 1
+  int off;         // where the query's n-wide rows of bound / list2 / res2 start
+  int tag, pad[3]; // the caller's (appearance search: the slot)
+};
+#define RL_INELIGIBLE 0xFFFFFFFFu   // a bound no frame reaches (B <= 20 * 15300): rl_pick and rl_list2 pass such a frame over
+
 // ---- descriptors ----------------------------------------------------------------------------------------------------------------------
 // mode 0: frame blockIdx.x of the map store -> desc / key row blockIdx.x; mode 1: the current scan of slot list[blockIdx.x] -> row `slot`,
-// and for the host the slot's record state[blockIdx.x] and a copy of its ring key klist[blockIdx.x]
+// and for the host the slot's record state[blockIdx.x] and a copy of its ring key klist[blockIdx.x]; mode 2: archived frame list[2 b + 1] of
+// slot list[2 b] (b = blockIdx.x; one contiguous run of the archive) -> row slot * arc_frames_cap + frame
+// the finished tile of a workgroup -> row `row` of desc / key; returns ring tid's key (tid < RL_NR)
+DEV_INLINE int rl_desc_store(const int* s_bin, uint32_t* desc, uint16_t* key, size_t row, int tid) {
+  uint32_t* d = desc + row * RL_WORDS;
+  for (int i = tid; i < RL_WORDS; i += RL_T)
+    d[i] = (uint32_t)s_bin[4 * i] | ((uint32_t)s_bin[4 * i + 1] << 8) | ((uint32_t)s_bin[4 * i + 2] << 16) | ((uint32_t)s_bin[4 * i + 3] << 24);
+  int s = 0;
+  if (tid < RL_NR) {
+    for (int c = 0; c < RL_NS; ++c) s += s_bin[c * RL_NR + tid];
+    key[row * RL_NR + tid] = (uint16_t)s;
+  }
+  return s;
+}
 __global__ void __launch_bounds__(RL_T) rl_desc(LmCtx L, int mode, const int* list, float w, float zoff, uint32_t* desc, uint16_t* key, RlSlot* state, uint16_t* klist) {
   __shared__ int s_bin[RL_BYTES];
   const int tid = threadIdx.x;
-  const int e = mode == 0 ? (int)blockIdx.x : list[blockIdx.x];   // map frame / slot
   for (int i = tid; i < RL_BYTES; i += RL_T) s_bin[i] = 0;
   __syncthreads();
+  if (mode == 2) {
+    const int slot = list[2 * blockIdx.x], f = list[2 * blockIdx.x + 1];
+    const KfArcFrame A = kf_arc_frame(L, slot, f);
+    const int n = kf_sel_count(A, KF_SEL_ALL);
+    for (int i = tid; i < n; i += RL_T) {
+      const float4 p = A.pts[i];
+      int bin, code;
+      if (rl_bin(p.x, p.y, p.z, w, zoff, &bin, &code)) atomicMax(&s_bin[bin], code);
+    }
+    __syncthreads();
+    rl_desc_store(s_bin, desc, key, arc_row(L, slot, f), tid);
+    return;
+  }
+  const int e = mode == 0 ? (int)blockIdx.x : list[blockIdx.x];   // map frame / slot
   const int* li = L.li + (size_t)(mode == 0 ? 0 : e) * LI_COUNT;
 #pragma unroll
   for (int kind = 0; kind < KF_KINDS; ++kind) {
@@ -76,15 +133,8 @@ __global__ void __launch_bounds__(RL_T) rl_desc(LmCtx L, int mode, const int* li
     }
   }
   __syncthreads();
-  uint32_t* d = desc + (size_t)e * RL_WORDS;
-  for (int i = tid; i < RL_WORDS; i += RL_T)
-    d[i] = (uint32_t)s_bin[4 * i] | ((uint32_t)s_bin[4 * i + 1] << 8) | ((uint32_t)s_bin[4 * i + 2] << 16) | ((uint32_t)s_bin[4 * i + 3] << 24);
-  if (tid < RL_NR) {
-    int s = 0;
-    for (int c = 0; c < RL_NS; ++c) s += s_bin[c * RL_NR + tid];
-    key[(size_t)e * RL_NR + tid] = (uint16_t)s;
-    if (mode == 1) klist[(size_t)blockIdx.x * RL_NR + tid] = (uint16_t)s;
-  }
+  const int s = rl_desc_store(s_bin, desc, key, (size_t)e, tid);
+  if (mode == 1 && tid < RL_NR) klist[(size_t)blockIdx.x * RL_NR + tid] = (uint16_t)s;
   if (mode == 1 && tid == 0) {
     const double* ld = L.ld + (size_t)e * LD_COUNT;
     RlSlot S;
@@ -108,12 +158,38 @@ __global__ void __launch_bounds__(64) rl_keys(const uint32_t* desc, uint16_t* ke
 }
 
 // ---- the search -------------------------------------------------------------------------------------------------------------------------
-// Queries of a chunk are numbered q = 0 .. nq - 1; qsel[q] = the row of qdesc / qkey (the slot).  Per query the scratch rows are N wide.
-// grid (ceil(N / RL_T), nq)
-__global__ void __launch_bounds__(RL_T) rl_bound(const int* qsel, const uint16_t* qkey, const uint16_t* mkey, int N, uint32_t* bound) {
-  const int q = blockIdx.y, i = blockIdx.x * RL_T + threadIdx.x;
-  if (i >= N) return;
-  bound[(size_t)q * N + i] = rl_key_bound(qkey + (size_t)qsel[q] * RL_NR, mkey + (size_t)i * RL_NR);
+// Queries of a chunk are numbered q = 0 .. nq - 1 and described by qr[q] (RlQuery).
+// grid (ceil(largest n / RL_T), nq)
+__global__ void __launch_bounds__(RL_T) rl_bound(const RlQuery* qr, const uint16_t* qkey, const uint16_t* mkey, uint32_t* bound) {
+  const RlQuery Q = qr[blockIdx.y];
+  const int i = blockIdx.x * RL_T + threadIdx.x;
+  if (i >= Q.n) return;
+  bound[(size_t)Q.off + i] = rl_key_bound(qkey + (size_t)Q.qrow * RL_NR, mkey + ((size_t)Q.base + i) * RL_NR);
+}
+
+// Eligibility of the appearance search (the header comment's rule); grid as rl_bound.  Query q is the newest archived frame Q.n of slot
+// Q.tag, frame i < Q.n a frame of the same slot.  A query whose ring key is all zero (no point in range: every code is >= 1) has no
+// eligible frame.  nelig[q] += the eligible frames (a sum of integers does not depend on the order; zeroed by the host).
+__global__ void __launch_bounds__(RL_T) la_elig(LmCtx L, const RlQuery* qr, const uint16_t* key, double min_time_gap, float jump2, uint32_t* bound, int* nelig) {
+  const RlQuery Q = qr[blockIdx.y];
+  const int i = blockIdx.x * RL_T + threadIdx.x;
+  bool el = false;
+  if (i < Q.n) {
+    const uint16_t* kq = key + (size_t)Q.qrow * RL_NR;
+    int any = 0;
+#pragma unroll
+    for (int r = 0; r < RL_NR; ++r) any |= kq[r];
+    const size_t fb = arc_row(L, Q.tag, 0);
+    el = any != 0 && L.arc_stamp[fb + Q.n] - L.arc_stamp[fb + i] > min_time_gap;   // lc_detect's comparison (:782)
+    if (jump2 >= 0.f) {
+      const float *a = arc_pose_of(L, Q.tag, i), *b = arc_pose_of(L, Q.tag, Q.n);
+      const float dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2];
+      el = el && ((dx * dx) + dy * dy) + dz * dz < jump2;
+    }
+    if (!el) bound[(size_t)Q.off + i] = RL_INELIGIBLE;
+  }
+  const int c = __popcll(__ballot(el));
+  if (c && lane_id() == 0) atomicAdd(&nelig[blockIdx.y], c);
 }
 
 // the smallest key of the workgroup in every thread (s_min: RL_WAVES words of LDS; a barrier on entry protects the previous call's readers)
@@ -128,40 +204,45 @@ DEV_INLINE unsigned long long rl_block_min(unsigned long long v, unsigned long l
   return v;
 }
 
-// grid (nq): listA[q][0 .. cntA[q]) = the n_cand frames smallest in (B, id), by n_cand rounds of "smallest key above the last one"
-__global__ void __launch_bounds__(RL_T) rl_pick(const uint32_t* bound, int N, int n_cand, int* listA, int* cntA) {
+// grid (nq): listA[q][0 .. cntA[q]) = the min(n_cand, eligible) eligible frames smallest in (B, id), by rounds of "smallest key above the last one"
+__global__ void __launch_bounds__(RL_T) rl_pick(const RlQuery* qr, const uint32_t* bound, int n_cand, int* listA, int* cntA) {
   __shared__ unsigned long long s_min[RL_WAVES];
   const int q = blockIdx.x, tid = threadIdx.x;
-  const uint32_t* b = bound + (size_t)q * N;
-  const int k = min(n_cand, N);
+  const RlQuery Q = qr[q];
+  const uint32_t* b = bound + (size_t)Q.off;
+  const int N = Q.n;
   unsigned long long last = 0ull;
-  for (int r = 0; r < k; ++r) {
+  int r = 0;
+  for (; r < min(n_cand, N); ++r) {
     unsigned long long best = ~0ull;
     for (int i = tid; i < N; i += RL_T) {
       const unsigned long long key = ((unsigned long long)b[i] << 32) | (uint32_t)i;
-      if (r == 0 || key > last) best = min(best, key);
+      if (b[i] != RL_INELIGIBLE && (r == 0 || key > last)) best = min(best, key);
     }
     last = rl_block_min(best, s_min);
+    if (last == ~0ull) break;   // (the same value in every thread) no eligible frame is left
     if (tid == 0) listA[q * ALEGO_RELOC_MAX_CAND + r] = (int)(last & 0xffffffffu);
   }
-  if (tid == 0) cntA[q] = k;
+  if (tid == 0) cntA[q] = r;
 }
 
-// grid (workgroups per query, nq): res[q * stride + j] = D << 8 | s of frame list[q * stride + j], j < cnt[q]
-__global__ void __launch_bounds__(RL_T) rl_search(const int* qsel, const uint32_t* qdesc, const uint32_t* __restrict__ mdesc, const int* list, const int* cnt, int stride,
+// grid (workgroups per query, nq): res[o + j] = D << 8 | s of frame list[o + j], j < cnt[q]; o = q * stride, or the query's Q.off when stride == 0
+__global__ void __launch_bounds__(RL_T) rl_search(const RlQuery* qr, const uint32_t* qdesc, const uint32_t* __restrict__ mdesc, const int* list, const int* cnt, int stride,
                                                   uint32_t* res) {
   __shared__ uint32_t s_q[2 * RL_WORDS];
   const int q = blockIdx.y, tid = threadIdx.x;
-  const uint32_t* qd = qdesc + (size_t)qsel[q] * RL_WORDS;
+  const RlQuery Q = qr[q];
+  const uint32_t* qd = qdesc + (size_t)Q.qrow * RL_WORDS;
   for (int i = tid; i < 2 * RL_WORDS; i += RL_T) s_q[i] = qd[i < RL_WORDS ? i : i - RL_WORDS];
   __syncthreads();
   const int n = cnt[q];
+  const size_t o = stride ? (size_t)q * stride : (size_t)Q.off;
   const int lane = lane_id();
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const uint32_t* col = s_q + (lane < RL_NS ? lane : 0) * RL_SW;   // (lanes 60 .. 63 repeat shift 0 and are left out of the arg-min)
   for (int j = blockIdx.x * RL_WAVES + wave; j < n; j += gridDim.x * RL_WAVES) {
-    const int f = __builtin_amdgcn_readfirstlane(list[(size_t)q * stride + j]);
-    const uint32_t* m = mdesc + (size_t)f * RL_WORDS;
+    const int f = __builtin_amdgcn_readfirstlane(list[o + j]);
+    const uint32_t* m = mdesc + ((size_t)Q.base + f) * RL_WORDS;
     uint32_t acc = 0;
 #pragma unroll 4
     for (int c = 0; c < RL_NS; ++c) {
@@ -169,42 +250,45 @@ __global__ void __launch_bounds__(RL_T) rl_search(const int* qsel, const uint32_
       for (int k = 0; k < RL_SW; ++k) acc = __builtin_amdgcn_sad_u8(col[c * RL_SW + k], m[c * RL_SW + k], acc);
     }
     const uint32_t best = wave_min_u32(lane < RL_NS ? (acc << 8) | (uint32_t)lane : 0xFFFFFFFFu);
-    if (lane == 0) res[(size_t)q * stride + j] = best;
+    if (lane == 0) res[o + j] = best;
   }
 }
 
-// grid (nq): list2[q][0 .. cnt2[q]) = every frame with B <= tau in id order; tau = the largest D of the first round (brute: every frame)
-__global__ void __launch_bounds__(RL_T) rl_list2(const uint32_t* bound, int N, const uint32_t* resA, const int* cntA, int brute, int* list2, int* cnt2) {
+// grid (nq): list2[q][0 .. cnt2[q]) = every eligible frame with B <= tau in id order; tau = the largest D of the first round (brute: every eligible frame)
+__global__ void __launch_bounds__(RL_T) rl_list2(const RlQuery* qr, const uint32_t* bound, const uint32_t* resA, const int* cntA, int brute, int* list2, int* cnt2) {
   __shared__ int s_w[RL_WAVES];
   const int q = blockIdx.x, tid = threadIdx.x;
+  const RlQuery Q = qr[q];
+  const int N = Q.n;
   uint32_t tau = 0;
   for (int j = 0; j < cntA[q]; ++j) tau = max(tau, resA[q * ALEGO_RELOC_MAX_CAND + j] >> 8);
   if (brute) tau = 0xFFFFFFFFu;
-  const uint32_t* b = bound + (size_t)q * N;
+  const uint32_t* b = bound + (size_t)Q.off;
   int carry = 0;
   for (int i0 = 0; i0 < N; i0 += RL_T) {
     const int i = i0 + tid;
-    const int sel = (i < N && b[i] <= tau) ? 1 : 0;
+    const int sel = (i < N && b[i] != RL_INELIGIBLE && b[i] <= tau) ? 1 : 0;
     int tot;
     const int ex = carry + block_excl_scan<RL_WAVES>(sel, s_w, &tot);
-    if (sel) list2[(size_t)q * N + ex] = i;
+    if (sel) list2[(size_t)Q.off + ex] = i;
     carry += tot;
   }
   if (tid == 0) cnt2[q] = carry;
 }
 
 // grid (nq): the n_cand smallest (D, id) of the second list -> cand[q][r] = D << 32 | id << 8 | s (~0: none)
-__global__ void __launch_bounds__(RL_T) rl_topk(const int* list2, const int* cnt2, const uint32_t* res2, int N, int n_cand, unsigned long long* cand) {
+__global__ void __launch_bounds__(RL_T) rl_topk(const RlQuery* qr, const int* list2, const int* cnt2, const uint32_t* res2, int n_cand, unsigned long long* cand) {
   __shared__ unsigned long long s_min[RL_WAVES];
   const int q = blockIdx.x, tid = threadIdx.x;
+  const size_t o = (size_t)qr[q].off;
   const int n = cnt2[q];
   unsigned long long last = 0ull;
   for (int r = 0; r < n_cand; ++r) {
     unsigned long long best = ~0ull;
     if (r < n)
       for (int j = tid; j < n; j += RL_T) {
-        const uint32_t v = res2[(size_t)q * N + j];
-        const unsigned long long key = ((unsigned long long)(v >> 8) << 32) | ((unsigned long long)(uint32_t)list2[(size_t)q * N + j] << 8) | (v & 0xffu);
+        const uint32_t v = res2[o + j];
+        const unsigned long long key = ((unsigned long long)(v >> 8) << 32) | ((unsigned long long)(uint32_t)list2[o + j] << 8) | (v & 0xffu);
         if (r == 0 || key > last) best = min(best, key);
       }
     last = rl_block_min(best, s_min);
@@ -256,6 +340,56 @@ __global__ void __launch_bounds__(RL_T) rl_gather(LmCtx L, const LcJob* jobs, co
   }
 }
 
+// ---- the appearance search of a SLAM handle: planning and verification ----------------------------------------------------------------
+// one thread per (listed entry e, candidate k): det[e * ALEGO_RELOC_MAX_CAND + k] = the attempt on candidate k as loop_attempts takes it
+// (status 0: no such candidate), latest[e] = the key pose of the newest frame
+__global__ void __launch_bounds__(64) la_plan(LmCtx L, const int* list, const unsigned long long* cand, int n, int search_num, LcDet* det, float* latest) {
+  const int idx = blockIdx.x * 64 + threadIdx.x, e = idx / ALEGO_RELOC_MAX_CAND, k = idx % ALEGO_RELOC_MAX_CAND;
+  if (e >= n) return;
+  const int slot = list[e], nf = arc_stat_of(L, slot)[AS_FRAMES];
+  if (k == 0)
+    for (int j = 0; j < 6; ++j) latest[e * 6 + j] = nf > 0 ? arc_pose_of(L, slot, nf - 1)[j] : 0.f;
+  LcDet D;
+  memset(&D, 0, sizeof(D));
+  const unsigned long long c = cand[idx];
+  if (c != ~0ull && nf >= 2) {
+    const int f = (int)((c >> 8) & 0xffffffu);
+    D.status = 1; D.latest = nf - 1; D.closest = f;
+    D.jlo = max(0, f - search_num); D.jhi = min(nf - 2, f + search_num);   // as lc_detect (:798-803)
+    for (int j = 0; j < 6; ++j) D.pose_latest[j] = D.pose_closest[j] = arc_pose_of(L, slot, f)[j];
+    D.pose_latest[5] = rl_guess_yaw(D.pose_latest[5], (int)(c & 0xffu));
+    D.n_src = arc_tab_points(arc_tab_of(L, slot, nf - 1));
+    long long nr = 0;
+    for (int j = D.jlo; j <= D.jhi; ++j) nr += arc_tab_points(arc_tab_of(L, slot, j));
+    D.n_raw = (int)nr;
+  }
+  det[idx] = D;
+}
+
+// grid (1 + frames, jobs): x = 0 the source — the newest archived frame under the guess (det.pose_latest); x = 1 + k the archived frame
+// jlo + k under its key pose; both read out surf, corner, outlier (as lc_gather)
+__global__ void __launch_bounds__(RL_T) la_gather(LmCtx L, const LcJob* jobs, const LcDet* det, float4* src, float4* raw) {
+  const LcJob J = jobs[blockIdx.y];
+  const LcDet& D = det[J.li];
+  int f;
+  float4* out;
+  if (blockIdx.x == 0) {
+    f = D.latest;
+    out = src + J.src_off;
+  } else {
+    f = D.jlo + (int)blockIdx.x - 1;
+    if (f > D.jhi) return;
+    int off = 0;
+    for (int j = D.jlo; j < f; ++j) off += arc_tab_points(arc_tab_of(L, J.slot, j));
+    out = raw + J.raw_off + off;
+  }
+  const KfArcFrame A = kf_arc_frame(L, J.slot, f);
+  const int n = kf_sel_count(A, KF_SEL_ALL);
+  float m[3][4];
+  keypose_matrix(blockIdx.x == 0 ? D.pose_latest : A.pose, m);
+  for (int i = threadIdx.x; i < n; i += RL_T) out[i] = kf_transform(m, A.pts[kf_arc_index(A.nc, A.ns, KF_SEL_ALL, i)]);
+}
+
 struct RlApply { int slot, pad; double rc[12], params6[6]; };
 // one lane per accepted slot: correctPoses :579-580 on map -> odom exactly as lm_apply_correction computes it, then params_
 __global__ void __launch_bounds__(64) rl_apply(LmCtx L, const RlApply* a, int n) {
@@ -284,21 +418,34 @@ struct RlCtx {
   int brute = 0;
   size_t pairs_cap = 0, q_cap = 0;
   uint32_t *bound = nullptr, *res2 = nullptr, *resA = nullptr;
-  int *list2 = nullptr, *cnt2 = nullptr, *listA = nullptr, *cntA = nullptr, *qsel = nullptr;
+  int *list2 = nullptr, *cnt2 = nullptr, *listA = nullptr, *cntA = nullptr, *nelig = nullptr;
+  RlQuery* qr = nullptr;
   unsigned long long* cand = nullptr;
   int stats[2] = {0, 0};                // of the last search: (query, frame) pairs the second round evaluated, pairs in all
+  // the appearance search of a SLAM handle (alego_loop_appearance_enable; la_cap == 0: off, nothing of it is allocated)
+  int la_slots = 0, la_cap = 0;         // slots; rows per slot (max_keyframes of the archive)
+  float la_w = 0.f, la_zoff = 0.f;
+  uint32_t* la_desc = nullptr;          // [la_slots][la_cap][RL_WORDS] descriptor of archived frame f of slot s at row s * la_cap + f
+  uint16_t* la_key = nullptr;           // [la_slots][la_cap][RL_NR]
+  std::vector<int> la_described;        // [la_slots] frames described so far: rows [0, la_described) of the slot are valid
+  int* la_list = nullptr;               // [la_slots] the listed slots of a call
+  unsigned long long* la_cand = nullptr;   // [la_slots][ALEGO_RELOC_MAX_CAND] their candidates
+  LcDet* la_det = nullptr;              // [la_slots][ALEGO_RELOC_MAX_CAND] the attempts la_plan planned
+  float* la_latest = nullptr;           // [la_slots][6] key pose of the newest frame
+  DevBuf<int> la_pend;                  // (slot, frame) pairs still to describe
+  DevPool la_store;                     // owns the la_* arrays above (valid while la_cap > 0)
   DevPool store, scratch;               // own what reloc_enable allocates (valid while n_slots > 0) and the search scratch (valid while pairs_cap > 0)
 };
 
 template <class T>
 static bool rl_alloc(DevPool& mem, T** p, size_t count, std::string* err) {
   const hipError_t e = mem.get(p, count, false);
-  if (e != hipSuccess) { *err = std::string("relocalisation: ") + hipGetErrorString(e); return false; }
+  if (e != hipSuccess) { *err = std::string("descriptor search: ") + hipGetErrorString(e); return false; }
   return true;
 }
 void reloc_ctx_destroy(RlCtx* R) {
   if (!R) return;
-  R->scratch.clear(); R->store.clear();
+  R->scratch.clear(); R->store.clear(); R->la_store.clear(); R->la_pend.clear();
   delete R;
 }
 void reloc_ctx_set(RlCtx** pr, int what, long long v) {   // what 0: pairs per chunk of the search, 1: brute force
@@ -334,42 +481,73 @@ int reloc_enable(RlCtx** pr, const LmCtx& L, int n_slots, double max_range, doub
   return 0;
 }
 
-// The exact search of nq queries (rows sel[q] of qdesc / qkey) over N frames: cand[q][r] = D << 32 | id << 8 | s, ~0 where N < n_cand.
-// Queries are taken in chunks of at most budget / N; a query's result does not depend on its chunk.
-static int rl_search_run(RlCtx* R, const uint32_t* qdesc, const uint16_t* qkey, const int* sel, int nq, const uint32_t* mdesc, const uint16_t* mkey, int N, int n_cand,
-                         unsigned long long* cand, hipStream_t st, std::string* err) {
+// The exact search of nq queries (qr[q]; off is filled in here): cand[q][r] = D << 32 | id << 8 | s, ~0 where fewer frames are eligible.
+// Queries are taken in chunks of consecutive queries whose frames sum to at most the budget; a query's result does not depend on its chunk.
+// mask (may be empty) runs behind rl_bound on the records and bounds of a chunk of c queries whose largest n is nmax; nelig (may be
+// null) receives what it summed into R->nelig per query.
+typedef std::function<void(const RlQuery* qr, int c, int nmax, uint32_t* bound, int* nelig, hipStream_t st)> RlMask;
+static int rl_search_run(RlCtx* R, const uint32_t* qdesc, const uint16_t* qkey, RlQuery* qr, int nq, const uint32_t* mdesc, const uint16_t* mkey, int n_cand,
+                         unsigned long long* cand, const RlMask& mask, int* nelig, hipStream_t st, std::string* err) {
   for (size_t i = 0; i < (size_t)nq * ALEGO_RELOC_MAX_CAND; ++i) cand[i] = ~0ull;
-  R->stats[0] = 0; R->stats[1] = (int)std::min<long long>((long long)nq * N, 0x7fffffff);
-  if (nq == 0 || N == 0) return 0;
-  std::vector<int> cnt2;
-  const int QC = (int)std::max<long long>(1, std::min<long long>(nq, R->budget / N));
-  if (R->pairs_cap < (size_t)QC * N || R->q_cap < (size_t)QC) {
-    const size_t pc = std::max(R->pairs_cap, (size_t)QC * N), qc = std::max(R->q_cap, (size_t)QC);
-    if (hipStreamSynchronize(st) != hipSuccess) { *err = "relocalisation: a stream failed"; return ALEGO_ERR_HIP; }
+  long long all = 0;
+  for (int q = 0; q < nq; ++q) { all += qr[q].n; if (nelig) nelig[q] = 0; }
+  R->stats[0] = 0; R->stats[1] = (int)std::min<long long>(all, 0x7fffffff);
+  if (nq == 0 || all == 0) return 0;
+  // chunks [first, first + count): consecutive queries; pairs and queries of the largest chunk size the scratch
+  const long long budget = std::min<long long>(R->budget, 1LL << 30);
+  std::vector<std::pair<int, int>> chunks;
+  size_t pc = 1, qc = 1;
+  for (int q0 = 0; q0 < nq;) {
+    long long sum = 0;
+    int c = 0;
+    while (q0 + c < nq && (c == 0 || sum + qr[q0 + c].n <= budget)) { qr[q0 + c].off = (int)sum; sum += qr[q0 + c].n; ++c; }
+    if (sum > 0x7fffffffLL) { *err = "descriptor search: a query's map is too large"; return ALEGO_ERR_ARG; }
+    chunks.emplace_back(q0, c);
+    pc = std::max(pc, (size_t)sum); qc = std::max(qc, (size_t)c);
+    q0 += c;
+  }
+  if (R->pairs_cap < pc || R->q_cap < qc) {
+    pc = std::max(R->pairs_cap, pc); qc = std::max(R->q_cap, qc);
+    if (hipStreamSynchronize(st) != hipSuccess) { *err = "descriptor search: a stream failed"; return ALEGO_ERR_HIP; }
     R->scratch.clear(); R->pairs_cap = R->q_cap = 0;
     if (!rl_alloc(R->scratch, &R->bound, pc, err) || !rl_alloc(R->scratch, &R->res2, pc, err) || !rl_alloc(R->scratch, &R->list2, pc, err) || !rl_alloc(R->scratch, &R->resA, qc * ALEGO_RELOC_MAX_CAND, err) ||
-        !rl_alloc(R->scratch, &R->listA, qc * ALEGO_RELOC_MAX_CAND, err) || !rl_alloc(R->scratch, &R->cntA, qc, err) || !rl_alloc(R->scratch, &R->cnt2, qc, err) || !rl_alloc(R->scratch, &R->qsel, qc, err) ||
-        !rl_alloc(R->scratch, &R->cand, qc * ALEGO_RELOC_MAX_CAND, err)) { R->scratch.clear(); return ALEGO_ERR_HIP; }
+        !rl_alloc(R->scratch, &R->listA, qc * ALEGO_RELOC_MAX_CAND, err) || !rl_alloc(R->scratch, &R->cntA, qc, err) || !rl_alloc(R->scratch, &R->cnt2, qc, err) || !rl_alloc(R->scratch, &R->qr, qc, err) ||
+        !rl_alloc(R->scratch, &R->nelig, qc, err) || !rl_alloc(R->scratch, &R->cand, qc * ALEGO_RELOC_MAX_CAND, err)) { R->scratch.clear(); return ALEGO_ERR_HIP; }
     R->pairs_cap = pc; R->q_cap = qc;
   }
-  const int nblk = std::max(1, std::min(RL_SEARCH_BLOCKS, (N + RL_WAVES - 1) / RL_WAVES));
-  for (int q0 = 0; q0 < nq; q0 += QC) {
-    const int c = std::min(QC, nq - q0);
-    if (hipMemcpyAsync(R->qsel, sel + q0, (size_t)c * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess) { *err = "relocalisation: upload failed"; return ALEGO_ERR_HIP; }
-    ALEGO_LAUNCH(rl_bound, dim3((N + RL_T - 1) / RL_T, c), dim3(RL_T), 0, st, R->qsel, qkey, mkey, N, R->bound);
-    ALEGO_LAUNCH(rl_pick, dim3(c), dim3(RL_T), 0, st, R->bound, N, n_cand, R->listA, R->cntA);
-    ALEGO_LAUNCH(rl_search, dim3(1, c), dim3(RL_T), 0, st, R->qsel, qdesc, mdesc, R->listA, R->cntA, ALEGO_RELOC_MAX_CAND, R->resA);
-    ALEGO_LAUNCH(rl_list2, dim3(c), dim3(RL_T), 0, st, R->bound, N, R->resA, R->cntA, R->brute, R->list2, R->cnt2);
-    ALEGO_LAUNCH(rl_search, dim3(nblk, c), dim3(RL_T), 0, st, R->qsel, qdesc, mdesc, R->list2, R->cnt2, N, R->res2);
-    ALEGO_LAUNCH(rl_topk, dim3(c), dim3(RL_T), 0, st, R->list2, R->cnt2, R->res2, N, n_cand, R->cand);
+  std::vector<int> cnt2;
+  for (const auto& ch : chunks) {
+    const int q0 = ch.first, c = ch.second;
+    int nmax = 0;
+    for (int q = q0; q < q0 + c; ++q) nmax = std::max(nmax, qr[q].n);
+    const int nblk = std::max(1, std::min(RL_SEARCH_BLOCKS, (nmax + RL_WAVES - 1) / RL_WAVES));
+    const dim3 gb(std::max(1, (nmax + RL_T - 1) / RL_T), c);
+    if (hipMemcpyAsync(R->qr, qr + q0, (size_t)c * sizeof(RlQuery), hipMemcpyHostToDevice, st) != hipSuccess) { *err = "descriptor search: upload failed"; return ALEGO_ERR_HIP; }
+    ALEGO_LAUNCH(rl_bound, gb, dim3(RL_T), 0, st, (const RlQuery*)R->qr, qkey, mkey, R->bound);
+    if (mask) {
+      if (hipMemsetAsync(R->nelig, 0, (size_t)c * sizeof(int), st) != hipSuccess) { *err = "descriptor search: the search failed"; return ALEGO_ERR_HIP; }
+      mask(R->qr, c, nmax, R->bound, R->nelig, st);
+    }
+    ALEGO_LAUNCH(rl_pick, dim3(c), dim3(RL_T), 0, st, (const RlQuery*)R->qr, R->bound, n_cand, R->listA, R->cntA);
+    ALEGO_LAUNCH(rl_search, dim3(1, c), dim3(RL_T), 0, st, (const RlQuery*)R->qr, qdesc, mdesc, R->listA, R->cntA, ALEGO_RELOC_MAX_CAND, R->resA);
+    ALEGO_LAUNCH(rl_list2, dim3(c), dim3(RL_T), 0, st, (const RlQuery*)R->qr, R->bound, R->resA, R->cntA, R->brute, R->list2, R->cnt2);
+    ALEGO_LAUNCH(rl_search, dim3(nblk, c), dim3(RL_T), 0, st, (const RlQuery*)R->qr, qdesc, mdesc, R->list2, R->cnt2, 0, R->res2);
+    ALEGO_LAUNCH(rl_topk, dim3(c), dim3(RL_T), 0, st, (const RlQuery*)R->qr, R->list2, R->cnt2, R->res2, n_cand, R->cand);
     // (the next chunk reuses the scratch: copies and kernels are ordered on `st`; cand is pageable, so the copy below has left the device when it returns)
     cnt2.resize((size_t)c);
     if (hipMemcpyAsync(cand + (size_t)q0 * ALEGO_RELOC_MAX_CAND, R->cand, (size_t)c * ALEGO_RELOC_MAX_CAND * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipMemcpyAsync(cnt2.data(), R->cnt2, (size_t)c * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess) { *err = "relocalisation: the search failed"; return ALEGO_ERR_HIP; }
+        (mask && nelig && hipMemcpyAsync(nelig + q0, R->nelig, (size_t)c * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess) ||
+        hipStreamSynchronize(st) != hipSuccess) { *err = "descriptor search: the search failed"; return ALEGO_ERR_HIP; }
     for (int v : cnt2) R->stats[0] = (int)std::min<long long>((long long)R->stats[0] + v, 0x7fffffff);
   }
   return 0;
+}
+// every query in rows 0 .. N - 1 of one map: query q is row sel[q]
+static std::vector<RlQuery> rl_whole_map(const int* sel, int nq, int N) {
+  std::vector<RlQuery> qr((size_t)nq);
+  for (int q = 0; q < nq; ++q) { std::memset(&qr[q], 0, sizeof(RlQuery)); qr[q].qrow = sel[q]; qr[q].n = N; }
+  return qr;
 }
 
 void reloc_debug_stats(const RlCtx* R, int out[2]) { out[0] = R ? R->stats[0] : 0; out[1] = R ? R->stats[1] : 0; }
@@ -391,7 +569,8 @@ int reloc_debug_search(RlCtx** pr, const uint8_t* map_desc, int n_map, const uin
   std::vector<int> sel((size_t)n_q);
   for (int q = 0; q < n_q; ++q) sel[q] = q;
   std::vector<unsigned long long> cand((size_t)n_q * ALEGO_RELOC_MAX_CAND);
-  int rc = rl_search_run(R, qd, qk, sel.data(), n_q, md, mk, n_map, n_cand, cand.data(), st, err);
+  std::vector<RlQuery> qr = rl_whole_map(sel.data(), n_q, n_map);
+  int rc = rl_search_run(R, qd, qk, qr.data(), n_q, md, mk, n_cand, cand.data(), RlMask(), nullptr, st, err);
   if (hipStreamSynchronize(st) != hipSuccess && !rc) { *err = "debug_reloc_search: kernels failed"; rc = ALEGO_ERR_HIP; }
   if (rc) return rc;
   for (int q = 0; q < n_q; ++q)
@@ -454,7 +633,8 @@ int reloc_run(RlCtx* R, LcCtx** lc, const LmCtx& L, const alego_params& P, const
     if (state[i].frame > 0 && any && N > 0) { qi.push_back(i); sel.push_back(slots[i]); }
   }
   std::vector<unsigned long long> cand(qi.size() * ALEGO_RELOC_MAX_CAND + 1);
-  if (int rc = rl_search_run(R, R->qdesc, R->qkey, sel.data(), (int)qi.size(), R->mdesc, R->mkey, N, n_cand, cand.data(), st, err)) return rc;
+  std::vector<RlQuery> qr = rl_whole_map(sel.data(), (int)qi.size(), N);
+  if (int rc = rl_search_run(R, R->qdesc, R->qkey, qr.data(), (int)qi.size(), R->mdesc, R->mkey, n_cand, cand.data(), RlMask(), nullptr, st, err)) return rc;
   for (size_t a = 0; a < qi.size(); ++a) {
     alego_reloc_result& r = out[qi[a]];
     for (int k = 0; k < n_cand; ++k) {
@@ -522,6 +702,161 @@ int reloc_run(RlCtx* R, LcCtx** lc, const LmCtx& L, const alego_params& P, const
   return 0;
 }
 
+// ---- the appearance search of a SLAM handle: host -----------------------------------------------------------------------------------------
+bool loop_app_enabled(const RlCtx* R) { return R && R->la_cap > 0; }
+
+int loop_app_enable(RlCtx** pr, const LmCtx& L, int n_slots, double max_range, double z_offset, std::string* err) {
+  if (!*pr) *pr = new RlCtx();
+  RlCtx* R = *pr;
+  const size_t rows = (size_t)n_slots * L.arc_frames_cap, ent = (size_t)n_slots * ALEGO_RELOC_MAX_CAND;
+  if (!rl_alloc(R->la_store, &R->la_desc, rows * RL_WORDS, err) || !rl_alloc(R->la_store, &R->la_key, rows * RL_NR, err) || !rl_alloc(R->la_store, &R->la_list, (size_t)n_slots, err) ||
+      !rl_alloc(R->la_store, &R->la_cand, ent, err) || !rl_alloc(R->la_store, &R->la_det, ent, err) || !rl_alloc(R->la_store, &R->la_latest, (size_t)n_slots * 6, err)) {
+    R->la_store.clear();
+    return ALEGO_ERR_HIP;
+  }
+  R->la_w = rl_ring_width(max_range); R->la_zoff = rl_z_offset(z_offset);
+  R->la_described.assign((size_t)n_slots, 0);
+  R->la_slots = n_slots; R->la_cap = L.arc_frames_cap;
+  return 0;
+}
+
+int loop_app_debug_get(RlCtx* R, int slot, const char* name, const void** src, size_t* bytes) {
+  if (!loop_app_enabled(R)) return ALEGO_ERR_ARG;
+  const std::string s(name);
+  const size_t row = (size_t)slot * R->la_cap, n = (size_t)R->la_described[slot];
+  if (s == "la_desc") { *src = R->la_desc + row * RL_WORDS; *bytes = n * RL_BYTES; }
+  else if (s == "la_key") { *src = R->la_key + row * RL_NR; *bytes = n * RL_NR * 2; }
+  else return ALEGO_ERR_ARG;
+  return 0;
+}
+
+// correction = t_correct * matrix(latest6)^-1: the f32 matrices widened to f64, the rigid inverse, the product rounded to f32
+static void la_world_correction(const float* t_correct, const float* latest6, float* correction) {
+  const float eye[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  float G[16];
+  double unused[12];
+  alego_loop_constraint(eye, latest6, latest6, G, unused);   // G = matrix(latest6) as t_correct's initial_guess is built (:680-687)
+  for (int r = 0; r < 3; ++r) {
+    double t = (double)t_correct[r * 4 + 3];
+    for (int c = 0; c < 3; ++c) {
+      double v = 0.0;
+      for (int k = 0; k < 3; ++k) v += (double)t_correct[r * 4 + k] * (double)G[c * 4 + k];   // R_t R_g^T
+      correction[r * 4 + c] = (float)v;
+      t -= v * (double)G[c * 4 + 3];                                                         // t_t - R_t R_g^T t_g
+    }
+    correction[r * 4 + 3] = (float)t;
+  }
+  correction[12] = correction[13] = correction[14] = 0.f; correction[15] = 1.f;
+}
+
+int loop_app_run(RlCtx* R, LcCtx** lc, const LmCtx& L, const alego_params& P, const int* slots, int n, const alego_loop_app_opts& o, alego_loop_result* out,
+                 alego_loop_app_info* info, hipStream_t st, std::string* err) {
+  for (int i = 0; i < n; ++i) {
+    std::memset(&out[i], 0, sizeof(out[i]));
+    out[i].latest_id = out[i].closest_id = -1;
+    if (info) { std::memset(&info[i], 0, sizeof(info[i])); info[i].verified = -1; }
+  }
+  if (n == 0) return 0;
+  // frames stored / dropped of every slot (the caller has drained every stream), then the descriptors of the listed slots' frames [described, nf)
+  std::vector<int> stat((size_t)R->la_slots * AS_W);
+  if (hipMemcpyAsync(stat.data(), arc_stat_of(L, 0), stat.size() * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+    *err = "alego_loop_search_appearance: reading the archive failed"; return ALEGO_ERR_HIP;
+  }
+  std::vector<int> pend;
+  std::vector<RlQuery> qr;
+  std::vector<int> qi;
+  for (int i = 0; i < n; ++i) {
+    const int slot = slots[i], nf = std::min(stat[(size_t)slot * AS_W + AS_FRAMES], R->la_cap);
+    out[i].latest_id = nf - 1;
+    if (stat[(size_t)slot * AS_W + AS_DROPPED] > 0) { out[i].status = -1; continue; }   // the newest key frame is not in the archive
+    for (int f = std::min(R->la_described[slot], nf); f < nf; ++f) { pend.push_back(slot); pend.push_back(f); }
+    if (nf < 2) continue;
+    RlQuery q;
+    std::memset(&q, 0, sizeof(q));
+    q.base = slot * R->la_cap; q.n = nf - 1; q.qrow = q.base + nf - 1; q.tag = slot;
+    qr.push_back(q); qi.push_back(i);
+  }
+  if (!pend.empty()) {
+    if (R->la_pend.reserve(pend.size()) != hipSuccess) { *err = "alego_loop_search_appearance: out of device memory"; return ALEGO_ERR_HIP; }
+    if (hipMemcpyAsync(R->la_pend.p, pend.data(), pend.size() * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess) { *err = "alego_loop_search_appearance: upload failed"; return ALEGO_ERR_HIP; }
+    ALEGO_LAUNCH(rl_desc, dim3((unsigned)(pend.size() / 2)), dim3(RL_T), 0, st, L, 2, (const int*)R->la_pend.p, R->la_w, R->la_zoff, R->la_desc, R->la_key, (RlSlot*)nullptr, (uint16_t*)nullptr);
+    // (pend is pageable: the copy has left the host buffer when the call returns; the kernel is ordered behind it on `st`)
+    for (size_t k = 0; k < pend.size(); k += 2) R->la_described[pend[k]] = std::max(R->la_described[pend[k]], pend[k + 1] + 1);   // only now: the rows are queued
+  }
+  // the search: every query against the older frames of its own slot
+  const float jump2 = o.max_jump > 0.0 ? (float)(o.max_jump * o.max_jump) : -1.f;
+  const double gap = P.lc_min_time_gap;
+  std::vector<unsigned long long> cand(qr.size() * ALEGO_RELOC_MAX_CAND + 1);
+  std::vector<int> nelig(qr.size() + 1);
+  if (int rc = rl_search_run(R, R->la_desc, R->la_key, qr.data(), (int)qr.size(), R->la_desc, R->la_key, o.n_cand, cand.data(),
+                             [&](const RlQuery* dq, int c, int nmax, uint32_t* bound, int* ne, hipStream_t s2) {
+                               ALEGO_LAUNCH(la_elig, dim3(std::max(1, (nmax + RL_T - 1) / RL_T), c), dim3(RL_T), 0, s2, L, dq, (const uint16_t*)R->la_key, gap, jump2, bound, ne);
+                             }, nelig.data(), st, err)) return rc;
+  if (hipStreamSynchronize(st) != hipSuccess) { *err = "alego_loop_search_appearance: descriptors failed"; return ALEGO_ERR_HIP; }   // (no query: the descriptors alone)
+  std::vector<unsigned long long> ecand((size_t)n * ALEGO_RELOC_MAX_CAND, ~0ull);   // per listed entry, after the max_dist cut
+  std::vector<int> ncand((size_t)n, 0);
+  bool any = false;
+  for (size_t a = 0; a < qi.size(); ++a) {
+    const int i = qi[a];
+    int k = 0;
+    for (; k < o.n_cand; ++k) {
+      const unsigned long long c = cand[a * ALEGO_RELOC_MAX_CAND + k];
+      if (c == ~0ull || (o.max_dist > 0 && (long long)(c >> 32) > (long long)o.max_dist)) break;
+      ecand[(size_t)i * ALEGO_RELOC_MAX_CAND + k] = c;
+      if (info) { info[i].cand_id[k] = (int32_t)((c >> 8) & 0xffffffu); info[i].cand_dist[k] = (int32_t)(c >> 32); info[i].cand_shift[k] = (int32_t)(c & 0xffu); }
+    }
+    ncand[i] = k;
+    if (info) { info[i].n_eligible = nelig[a]; info[i].n_cand = k; }
+    if (k > 0) { out[i].status = 1; out[i].closest_id = (int32_t)((ecand[(size_t)i * ALEGO_RELOC_MAX_CAND] >> 8) & 0xffffffu); any = true; }
+  }
+  if (!any || o.verify == 0) return 0;
+  // the attempts on every candidate, planned on the device from the archive's tables
+  std::vector<LcDet> plan((size_t)n * ALEGO_RELOC_MAX_CAND);
+  std::vector<float> latest((size_t)n * 6);
+  if (hipMemcpyAsync(R->la_list, slots, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemcpyAsync(R->la_cand, ecand.data(), ecand.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st) != hipSuccess) { *err = "alego_loop_search_appearance: upload failed"; return ALEGO_ERR_HIP; }
+  ALEGO_LAUNCH(la_plan, dim3((n * ALEGO_RELOC_MAX_CAND + 63) / 64), dim3(64), 0, st, L, (const int*)R->la_list, (const unsigned long long*)R->la_cand, n, P.lc_search_num, R->la_det, R->la_latest);
+  if (hipMemcpyAsync(plan.data(), R->la_det, plan.size() * sizeof(LcDet), hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipMemcpyAsync(latest.data(), R->la_latest, latest.size() * sizeof(float), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+    *err = "alego_loop_search_appearance: planning failed"; return ALEGO_ERR_HIP;
+  }
+  const double fitness_max = o.fitness_max > 0.0 ? o.fitness_max : P.lc_fitness_max;
+  std::vector<LcDet> det((size_t)n);
+  std::vector<LcOut> res((size_t)n);
+  for (int v = 0; v < o.verify; ++v) {   // round v tries candidate v of every slot that has one and is not accepted yet
+    bool some = false;
+    for (int i = 0; i < n; ++i) {
+      std::memset(&det[i], 0, sizeof(LcDet));
+      if (out[i].status != 1 || ncand[i] <= v) continue;
+      det[i] = plan[(size_t)i * ALEGO_RELOC_MAX_CAND + v];
+      some = some || det[i].status == 1;
+    }
+    if (!some) break;
+    if (int rc = loop_attempts(lc, P, R->la_slots, slots, det.data(), n, [&](const LcJob* jobs, const LcDet* dd, int J, int nfr, float4* src, float4* raw, hipStream_t s2) {
+          ALEGO_LAUNCH(la_gather, dim3(nfr, J), dim3(RL_T), 0, s2, L, jobs, dd, src, raw);
+        }, res.data(), st, err)) return rc;
+    for (int i = 0; i < n; ++i) {
+      const LcDet& D = det[i];
+      if (D.status != 1) continue;
+      alego_loop_result& r = out[i];
+      const LcOut& O = res[i];
+      r.closest_id = D.closest;
+      r.converged = O.converged; r.iterations = O.iterations; r.n_source = O.n_source; r.n_target = O.n_target; r.fitness = O.fitness;
+      alego_loop_constraint(O.correction, D.pose_latest, D.pose_closest, r.t_correct, r.between);
+      la_world_correction(r.t_correct, latest.data() + (size_t)i * 6, r.correction);
+      r.noise_variance = (double)(float)O.fitness;
+      const bool ok = O.converged && O.fitness <= fitness_max;
+      if (ok) r.status = 2;
+      if (info) {
+        for (int k = 0; k < 6; ++k) info[i].guess6[k] = D.pose_latest[k];
+        for (int k = 0; k < 16; ++k) info[i].icp_final[k] = O.correction[k];
+        if (ok) info[i].verified = v;
+      }
+    }
+  }
+  return 0;
+}
+
 // ---- host twins (plain C++) -----------------------------------------------------------------------------------------------------------
 extern "C" int alego_reloc_descriptor(const alego_point* pts, int32_t n, double max_range, double z_offset, uint8_t* desc1200, uint16_t* key20) {
   if (n < 0 || (n > 0 && !pts) || !desc1200 || !key20) return ALEGO_ERR_ARG;
@@ -552,4 +887,36 @@ extern "C" int alego_reloc_match(const uint8_t* q1200, const uint8_t* m1200, int
   }
   *dist = best; *shift = bs;
   return ALEGO_OK;
+}
+// the candidates of the appearance search for frame n - 1 over frames 0 .. n - 2: the brute force over every eligible frame and shift
+extern "C" int alego_loop_appearance_candidates(const uint8_t* desc, const float* keyposes6, const double* stamps, int32_t n, double min_time_gap, double max_jump,
+                                                int32_t max_dist, int32_t n_cand, int32_t* ids, int32_t* dists, int32_t* shifts) {
+  if (n < 0 || n_cand < 1 || n_cand > ALEGO_RELOC_MAX_CAND || (n > 0 && (!desc || !keyposes6 || !stamps)) || !ids || !dists || !shifts) return ALEGO_ERR_ARG;
+  if (n < 2) return 0;
+  const uint8_t* q = desc + (size_t)(n - 1) * RL_BYTES;
+  bool any = false;
+  for (int i = 0; i < RL_BYTES; ++i) any = any || q[i] != 0;
+  if (!any) return 0;   // no point in range
+  const float jump2 = (float)(max_jump * max_jump);
+  const float* b = keyposes6 + (size_t)(n - 1) * 6;
+  std::vector<unsigned long long> all;   // D << 32 | id << 8 | s
+  for (int i = 0; i < n - 1; ++i) {
+    if (!(stamps[n - 1] - stamps[i] > min_time_gap)) continue;
+    if (max_jump > 0.0) {
+      const float* a = keyposes6 + (size_t)i * 6;
+      const float dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2];
+      if (!(((dx * dx) + dy * dy) + dz * dz < jump2)) continue;
+    }
+    int32_t d, s;
+    alego_reloc_match(q, desc + (size_t)i * RL_BYTES, &d, &s);
+    all.push_back(((unsigned long long)(uint32_t)d << 32) | ((unsigned long long)(uint32_t)i << 8) | (unsigned)s);
+  }
+  std::sort(all.begin(), all.end());
+  int k = 0;
+  for (; k < n_cand && k < (int)all.size(); ++k) {
+    const int32_t d = (int32_t)(all[k] >> 32);
+    if (max_dist > 0 && d > max_dist) break;
+    ids[k] = (int32_t)((all[k] >> 8) & 0xffffffu); dists[k] = d; shifts[k] = (int32_t)(all[k] & 0xffu);
+  }
+  return k;
 }

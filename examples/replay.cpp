@@ -22,6 +22,13 @@
 //       alego_loop_search -> alego_graph_add_loops -> alego_graph_optimize with apply = 1 (correctPoses, :561-584).  Every applied
 //       correction prints one line "closed: scan K slot S poses N loops L iterations I cost C0 -> C"; with --save-map the map comes
 //       out at the corrected poses.
+//   --loop-search / --close-loops + --appearance [--app-max-jump M] [--app-range R]
+//       the radius search runs first; a slot for which it returns status 0 (no archived key pose within lc_search_radius: the drift may
+//       exceed it) goes to alego_loop_search_appearance, which recognises the place from the clouds (alego_loop_appearance_enable with
+//       max_range R, default the library's; M = its max_jump gate in metres, default off).  A closure accepted that way prints the same
+//       line followed by " appearance D S": the descriptor distance and the yaw shift of the accepted candidate.
+//   --loop-radius R
+//       lc_search_radius of the radius search in metres (history_search_radius_, default 20): a small R leaves the revisits to --appearance.
 //   either source + --localize [--loc-radius R]
 //       map once, then localise in that map: the run above keeps the archive on; afterwards every archived key frame is pulled with
 //       alego_map_get_keyframe, a SECOND handle is opened, alego_loc_enable hands it those frames, and the same scans are replayed through
@@ -53,8 +60,8 @@ int main(int argc, char** argv) {
   std::string bag_path, topic = "/lslidar_point_cloud", map_dir;
   float map_leaf = 0.f;
   int map_frames = 4096, map_points = 1 << 24, loop_every = 0, close_every = 0, max_loops = 16;
-  bool list_only = false, standalone = false, localize = false, relocalize = false;
-  double loc_radius = 0.0, reloc_range = 0.0;
+  bool list_only = false, standalone = false, localize = false, relocalize = false, appearance = false;
+  double loc_radius = 0.0, reloc_range = 0.0, app_max_jump = 0.0, app_range = 0.0, loop_radius = 0.0;
   long reloc_start = -1;
   long max_scans = -1;
   int n_scan = 16, horizon = -1;
@@ -76,6 +83,10 @@ int main(int argc, char** argv) {
     else if (a == "--loop-search") loop_every = std::atoi(val());
     else if (a == "--close-loops") close_every = std::atoi(val());
     else if (a == "--max-loops") max_loops = std::atoi(val());
+    else if (a == "--appearance") appearance = true;
+    else if (a == "--app-max-jump") app_max_jump = std::atof(val());
+    else if (a == "--app-range") app_range = std::atof(val());
+    else if (a == "--loop-radius") loop_radius = std::atof(val());
     else if (a == "--localize") localize = true;
     else if (a == "--loc-radius") loc_radius = std::atof(val());
     else if (a == "--relocalize") relocalize = true;
@@ -107,6 +118,7 @@ int main(int argc, char** argv) {
   alego_params P;
   alego_default_params(&P, n_scan, horizon);
   if (standalone) { P.laser_type = ALEGO_LASER_RFANS_16M; P.near_filter = 1; }
+  if (loop_radius > 0.0) P.lc_search_radius = loop_radius;
   if (alego_params_sizeof() != (int)sizeof(alego_params)) { std::fprintf(stderr, "header / library mismatch\n"); return 2; }
   const int N = P.n_scan * P.horizon_scan;
   const int cap_in = bag ? (1 << 20) : N;      // a driver may publish more returns than cells; the library takes at most N per scan
@@ -128,6 +140,20 @@ int main(int argc, char** argv) {
   if (close_every > 0 && alego_graph_enable(h, max_loops, nullptr) != ALEGO_OK) {
     std::fprintf(stderr, "graph_enable: %s\n", alego_last_error(h)); alego_destroy(h); return 1;
   }
+  if (appearance && (loop_every > 0 || close_every > 0) && alego_loop_appearance_enable(h, app_range, 0.0 / 0.0) != ALEGO_OK) {
+    std::fprintf(stderr, "loop_appearance_enable: %s\n", alego_last_error(h)); alego_destroy(h); return 1;
+  }
+  // the radius search first; with --appearance a slot it has no candidate for is searched by appearance.  app = " appearance D S" of a closure found that way
+  auto find_loop = [&](int32_t slot, alego_loop_result* lr, std::string* app) -> int {
+    app->clear();
+    if (int rc = alego_loop_search(h, &slot, 1, lr)) return rc;
+    if (!appearance || lr->status != 0) return ALEGO_OK;
+    const alego_loop_app_opts ao{0, -1, 0, app_max_jump, 0.0};   // 0 / -1: the defaults (4 candidates, 1 verified)
+    alego_loop_app_info ai{};
+    if (int rc = alego_loop_search_appearance(h, &slot, 1, &ao, lr, &ai)) return rc;
+    if (lr->status == 2) *app = " appearance " + std::to_string(ai.cand_dist[ai.verified]) + " " + std::to_string(ai.cand_shift[ai.verified]);
+    return ALEGO_OK;
+  };
   alego_pose odom{}, mapped{};
   int key_frames = 0, last_flags = 0, dropped = 0;
   float last_key_pose[6] = {0, 0, 0, 0, 0, 0};
@@ -158,19 +184,21 @@ int main(int argc, char** argv) {
     if (loop_every > 0 && (k + 1) % loop_every == 0) {
       const int32_t slot = 0;
       alego_loop_result lr{};
-      if (alego_loop_search(h, &slot, 1, &lr) != ALEGO_OK) { std::fprintf(stderr, "loop_search: %s\n", alego_last_error(h)); alego_destroy(h); return 1; }
-      if (lr.status == 2) std::printf("loop: scan %ld slot %d latest %d closest %d fitness %.9g\n", k, slot, lr.latest_id, lr.closest_id, lr.fitness);
+      std::string app;
+      if (find_loop(slot, &lr, &app) != ALEGO_OK) { std::fprintf(stderr, "loop_search: %s\n", alego_last_error(h)); alego_destroy(h); return 1; }
+      if (lr.status == 2) std::printf("loop: scan %ld slot %d latest %d closest %d fitness %.9g%s\n", k, slot, lr.latest_id, lr.closest_id, lr.fitness, app.c_str());
     }
     if (close_every > 0 && (k + 1) % close_every == 0) {   // search -> add the Between factor -> optimise and correct, all on the device
       const int32_t slot = 0;
       alego_loop_result lr{};
       alego_graph_result gr{};
       const alego_graph_opts go{0, 0.0, 1};
-      if (alego_loop_search(h, &slot, 1, &lr) != ALEGO_OK || alego_graph_add_loops(h, &slot, 1, &lr) != ALEGO_OK ||
+      std::string app;
+      if (find_loop(slot, &lr, &app) != ALEGO_OK || alego_graph_add_loops(h, &slot, 1, &lr) != ALEGO_OK ||
           (lr.status == 2 && alego_graph_optimize(h, &slot, 1, &go, &gr) != ALEGO_OK)) {
         std::fprintf(stderr, "close loops: %s\n", alego_last_error(h)); alego_destroy(h); return 1;
       }
-      if (gr.applied) std::printf("closed: scan %ld slot %d poses %d loops %d iterations %d cost %.9g -> %.9g\n", k, slot, gr.n_poses, gr.n_loops, gr.iterations, gr.cost0, gr.cost);
+      if (gr.applied) std::printf("closed: scan %ld slot %d poses %d loops %d iterations %d cost %.9g -> %.9g%s\n", k, slot, gr.n_poses, gr.n_loops, gr.iterations, gr.cost0, gr.cost, app.c_str());
     }
   }
   std::string loc_json;

@@ -564,6 +564,56 @@ int alego_reloc_match(const uint8_t* q1200, const uint8_t* m1200, int32_t* dist,
 int alego_debug_reloc_search(alego_handle* h, const uint8_t* map_desc, int32_t n_map, const uint8_t* q_desc, int32_t n_q, int32_t n_cand,
                              int32_t* ids, int32_t* dists, int32_t* shifts);
 
+/* ---- loop closures by appearance: a SLAM slot searched against its OWN archive (needs alego_map_enable) -----
+ * alego_loop_search finds a revisit only while the accumulated drift is smaller than lc_search_radius.  This search recognises the place from
+ * the clouds instead, with the descriptor, the exact pruned search and the yaw-shifted guess of relocalisation (above) and the ICP of
+ * alego_loop_search.  The rule (the project's own; csrc/kernels_reloc.hip states it next to the kernels), for a listed slot with nf archived
+ * frames and none dropped:
+ *   query       the descriptor of the newest archived frame nf - 1 (its corner, surf and outlier clouds)
+ *   eligible    frame i < nf - 1 with stamp[nf - 1] - stamp[i] > lc_min_time_gap and, when max_jump > 0, the f32 squared distance
+ *               ((dx dx) + dy dy) + dz dz of key poses i and nf - 1 < (float)(max_jump * max_jump).  A predicate per frame, not a prefix.
+ *   candidates  the n_cand eligible frames smallest in (D_i, i), D_i and s_i as alego_reloc_match: exactly the brute force over all eligible
+ *               frames and all 60 shifts; candidates with D_i > max_dist are dropped when max_dist > 0
+ *   verify      candidate v in round v, at most `verify` rounds, the first accepted ends the slot: source = frame nf - 1 (surf, corner, outlier)
+ *               under guess6 = key pose i with yaw - (float)s_i * (float)(2 pi / 60); target = frames [i - lc_search_num, i + lc_search_num]
+ *               within [0, nf - 2] under their archived poses through VoxelGrid(lc_leaf); ICP and fitness exactly as alego_loop_search runs
+ *               them.  Accepted when converged && fitness <= fitness_max (fitness_max <= 0: lc_fitness_max).
+ *   result      an alego_loop_result that alego_graph_add_loops takes unchanged: latest_id = nf - 1; closest_id = the accepted candidate, or
+ *               the last one verified, or the first candidate when verify == 0, or -1; t_correct and between = alego_loop_constraint(the ICP's
+ *               final transformation, guess6, key pose closest_id); noise_variance = (float)fitness; correction = the WORLD correction
+ *               t_correct * matrix(key pose nf - 1)^-1 (f32 matrices widened to f64, rigid inverse, product rounded to f32) - with guess6 equal
+ *               to the newest key pose that is the ICP's final transformation, which alego_loop_search stores there, and it is what apply = 1 of
+ *               alego_graph_optimize hands to map -> odom.  status: 0 no key frame, no eligible frame, an empty query descriptor or no
+ *               candidate left after max_dist; 1 attempted and rejected, or verify == 0; 2 accepted; -1 the archive dropped frames.
+ * alego_loop_appearance_enable   once, any time after alego_map_enable (ALEGO_ERR_ARG: a second call, without the archive, on a localising
+ *                        handle).  max_range <= 0: 80.0; z_offset not finite: 4.0.  Device memory: max_keyframes * 1240 B + 732 B per slot.
+ *                        Descriptors are built lazily: a search first describes the listed slots' frames [described, nf) (archived clouds never
+ *                        change once stored); nothing is added to the per-scan path.  Without the call nothing is allocated or launched.
+ * alego_loop_search_appearance   synchronous; runs behind the work queued on every stream group and changes no device state.  out[i] (and
+ *                        info[i], when info is not NULL) belongs to slots[i]; a slot's result does not depend on the other slots, their order or
+ *                        the chunking.  opts == NULL: n_cand 4, verify 1, gates off; n_cand <= 0: 4; verify < 0: 1; verify == 0: search only.
+ *                        ALEGO_ERR_ARG: not enabled, a slot out of range or listed twice, n_cand > ALEGO_RELOC_MAX_CAND, verify > n_cand.
+ * alego_loop_appearance_candidates   host only, plain C++: the candidates of frame n - 1 of desc[n][1200] over frames 0 .. n - 2; returns their
+ *                        count (ids / dists / shifts hold n_cand entries each), 0 for n < 2 or an all-zero descriptor of frame n - 1.
+ * alego_debug_get names: "la_desc" ([frames described][1200] bytes of the slot), "la_key" ([frames described] x 20 u16).  "ALEGO_RL_BRUTE" and
+ * "ALEGO_RL_BUDGET" act on this search as on relocalisation's. */
+typedef struct alego_loop_app_opts {
+  int32_t n_cand, verify, max_dist;
+  double max_jump, fitness_max;
+} alego_loop_app_opts;
+typedef struct alego_loop_app_info {
+  int32_t n_eligible, n_cand;   /* eligible frames; candidates left after max_dist */
+  int32_t cand_id[ALEGO_RELOC_MAX_CAND], cand_dist[ALEGO_RELOC_MAX_CAND], cand_shift[ALEGO_RELOC_MAX_CAND];
+  int32_t verified;             /* index of the accepted candidate or -1 */
+  float guess6[6];              /* the ICP's initial guess (the last candidate verified) */
+  float icp_final[16];          /* its getFinalTransformation(), row-major */
+} alego_loop_app_info;
+int alego_loop_appearance_enable(alego_handle* h, double max_range, double z_offset);
+int alego_loop_search_appearance(alego_handle* h, const int32_t* slots, int32_t n, const alego_loop_app_opts* opts, alego_loop_result* out,
+                                 alego_loop_app_info* info);
+int alego_loop_appearance_candidates(const uint8_t* desc, const float* keyposes6, const double* stamps, int32_t n, double min_time_gap,
+                                     double max_jump, int32_t max_dist, int32_t n_cand, int32_t* ids, int32_t* dists, int32_t* shifts);
+
 /* ---- one scan-to-map registration sharded over the GPUs of a node (BASELINE.json config 5) ----------------
  * One process per GPU; every rank feeds its handle the SAME scans and so keeps a bit-identical replica of the stream's state
  * (ImageProjection, feature extraction, LaserOdometry and the local map are cheap and are computed redundantly).  What is split
