@@ -1,8 +1,10 @@
 // dev_mem.h — the one owner of device memory on the host side: every device block of the library, kept with a handle or taken for one call,
-// belongs to a DevPool or a DevBuf and so comes from guard_alloc.h (ALEGO_DEBUG_CANARY=1).  Header-only; it names no HIP call of its own.
+// belongs to a DevPool or a DevBuf and so comes from guard_alloc.h (ALEGO_DEBUG_CANARY=1).  Header-only; it names no HIP call of its own but
+// hipGetErrorString, for the message of a failed request (DevGet).
 #ifndef ALEGO_DEV_MEM_H_
 #define ALEGO_DEV_MEM_H_
 #include <algorithm>
+#include <string>
 #include <utility>
 #include <vector>
 
@@ -35,6 +37,16 @@ class DevPool {
   void adopt(void* p) { if (p) p_.push_back(p); }
  private:
   std::vector<void*> p_;
+};
+
+// "Get from a pool or set the error": get(&p, count) is mem.get(&p, count, false); on failure *err = what + the runtime's message.
+struct DevGet {
+  DevPool& mem; const char* what; std::string* err;
+  template <class T> bool operator()(T** p, size_t count) const {
+    const hipError_t e = mem.get(p, count, false);
+    if (e != hipSuccess) *err = std::string(what) + hipGetErrorString(e);
+    return e == hipSuccess;
+  }
 };
 
 // A grow-only device array.  Growing frees the old block before it allocates the new one (the peak stays at the larger of the two) and

@@ -48,14 +48,7 @@ __global__ void __launch_bounds__(LS_T) loc_select(DevCtx d, LmCtx L) {
         const unsigned long long key = loc_key(kp + (size_t)i * KF_POSE_W, i, px, py, pz, r2);
         if (r == 0 || key > last) best = min(best, key);
       }
-      best = bfly_min_u64(best);
-      __syncthreads();   // (the previous round's readers of s_min are done)
-      if (lane_id() == 0) s_min[tid >> 6] = best;
-      __syncthreads();
-      best = s_min[0];
-#pragma unroll
-      for (int w = 1; w < LS_T / 64; ++w) best = min(best, s_min[w]);
-      last = best;
+      last = block_min_u64<LS_T / 64>(best, s_min);
     }
     thr = last;
   }

@@ -4,8 +4,9 @@
 //   lc_detect    one workgroup per listed slot: the (d², id) arg-min over the archived key poses within lc_search_radius of the
 //                slot's t_map2laser_ whose stamp is more than lc_min_time_gap older than the newest frame's (:771-790), the history
 //                window closest ± lc_search_num (< latest, >= 0) and the sizes of the source and of the raw sub-map
-//   lc_gather    one workgroup per (slot, frame): the newest frame (source) and the history frames transformed by their archived key
-//                poses (keypose_matrix / kf_transform, as map_gather), surf, corner, outlier per frame (:794-807)
+//   lc_gather    one workgroup per (attempt, frame): the newest frame (source) under det.pose_latest — its archived key pose for
+//                alego_loop_search, the guess for the appearance search (kernels_reloc.hip) — and the history frames under their archived
+//                key poses (keypose_matrix / kf_transform, as map_gather), surf, corner, outlier per frame (:794-807) through kf_store.h's view
 //   (voxel.h)    VoxelGrid(lc_leaf) of every slot's raw sub-map: one job per slot of the one-workgroup kernels (bit-exact)
 //   lc_grid      one workgroup per slot: stable counting sort of the filtered target into a uniform grid of power-of-two cells,
 //                with every cell's actual f32 bounding box
@@ -13,6 +14,8 @@
 //                exact 1-NN of every source point through the grid (lc_nn), the 17 f64 sums (each thread sums its own points in
 //                index order, then a fixed butterfly / wave order), Horn's step and the convergence test (icp_math.h) on one thread;
 //                then getFitnessScore().  No workgroup waits for another; results do not depend on which slots share a launch.
+// The host side offers the attempts to the other callers (loop_ctx.h): loop_attempts with a gather of the caller's (loop_archive_gather: lc_gather),
+// loop_rounds, the verification rounds of relocalisation and of the appearance search, and loop_result_fill, the alego_loop_result of a verdict.
 //
 // Exactness of lc_nn.  The answer must be the brute force's: the smallest f32 ((dx*dx + dy*dy) + dz*dz), ties
 // to the lowest target index, for queries anywhere.  Candidates are compared as the (d², index) pair, so the visiting order does not
@@ -68,47 +71,32 @@ __global__ void __launch_bounds__(LC_DT) lc_detect(LmCtx L, const int* list, ale
     // radiusSearch (f32 d² < r², :778) + the first candidate in (d², id) order that is old enough (:781-788); d² >= 0: its bits order it
     if (r < r2 && t_last - L.arc_stamp[fb + i] > P.lc_min_time_gap) best = min(best, ((unsigned long long)__float_as_uint(r) << 32) | (unsigned)i);
   }
-  best = bfly_min_u64(best);
-  if (lane_id() == 0) s_min[threadIdx.x >> 6] = best;
-  __syncthreads();
+  best = block_min_u64<LC_DT / 64>(best, s_min);
   if (threadIdx.x != 0) return;
-  for (int w = 1; w < LC_DT / 64; ++w) best = min(best, s_min[w]);
   for (int k = 0; k < 6; ++k) D.pose_latest[k] = arc_pose_of(L, slot, nf - 1)[k];
-  D.n_src = arc_tab_points(arc_tab_of(L, slot, nf - 1));
-  if (best == ~0ull) { D.status = 0; det[b] = D; return; }
-  D.status = 1;
-  D.closest = (int)(best & 0xffffffffu);
-  for (int k = 0; k < 6; ++k) D.pose_closest[k] = arc_pose_of(L, slot, D.closest)[k];
-  D.jlo = max(0, D.closest - P.lc_search_num);                 // :798-803: j < 0 || j >= latest_history_frame_id_ are skipped
-  D.jhi = min(D.latest - 1, D.closest + P.lc_search_num);
-  long long n = 0;
-  for (int j = D.jlo; j <= D.jhi; ++j) n += arc_tab_points(arc_tab_of(L, slot, j));
-  D.n_raw = (int)n;
+  if (best != ~0ull) {
+    D.status = 1;
+    D.closest = (int)(best & 0xffffffffu);
+    for (int k = 0; k < 6; ++k) D.pose_closest[k] = arc_pose_of(L, slot, D.closest)[k];
+    lc_window(D.closest, P.lc_search_num, D.latest - 1, &D.jlo, &D.jhi);   // :798-803: j < 0 || j >= latest_history_frame_id_ are skipped
+  }
+  lc_det_sizes(L, slot, nf - 1, &D);   // (no candidate: the window is empty)
   det[b] = D;
 }
 
 // ---- sub-map --------------------------------------------------------------------------------------------------------------------
-// grid (1 + frames, jobs): x = 0 the source (newest frame), x = 1 + k the history frame jlo + k
+// grid (1 + frames, jobs): x = 0 the source — archived frame det.latest under det.pose_latest; x = 1 + k the history frame jlo + k under its key pose
 __global__ void __launch_bounds__(LC_DT) lc_gather(LmCtx L, const LcJob* jobs, const LcDet* det, float4* src, float4* raw) {
   const LcJob J = jobs[blockIdx.y];
   const LcDet& D = det[J.li];
-  int f;
-  float4* out;
-  if (blockIdx.x == 0) {
-    f = D.latest;
-    out = src + J.src_off;
-  } else {
-    f = D.jlo + (int)blockIdx.x - 1;
-    if (f > D.jhi) return;
-    int off = 0;
-    for (int j = D.jlo; j < f; ++j) off += arc_tab_points(arc_tab_of(L, J.slot, j));
-    out = raw + J.raw_off + off;
-  }
+  const bool source = blockIdx.x == 0;
+  const int f = source ? D.latest : D.jlo + (int)blockIdx.x - 1;
+  if (!source && f > D.jhi) return;
+  float4* out = source ? src + J.src_off : lc_frame_out(raw, J, D, f, [&](int j) { return arc_tab_points(arc_tab_of(L, J.slot, j)); });
   const KfArcFrame A = kf_arc_frame(L, J.slot, f);
-  const int n = kf_sel_count(A, KF_SEL_ALL);
   float m[3][4];
-  keypose_matrix(A.pose, m);
-  for (int i = threadIdx.x; i < n; i += LC_DT) out[i] = kf_transform(m, A.pts[kf_arc_index(A.nc, A.ns, KF_SEL_ALL, i)]);   // surf, corner, outlier
+  keypose_matrix(source ? D.pose_latest : A.pose, m);
+  kf_clouds_write<LC_DT>(kf_clouds(A), m, out);
 }
 
 // ---- uniform grid ---------------------------------------------------------------------------------------------------------------
@@ -410,20 +398,13 @@ void loop_ctx_set_budget(LcCtx** pc, long long points) {
   (*pc)->budget = std::max(1LL, points);
 }
 
-template <class T>
-static bool lc_alloc(DevPool& mem, T** p, size_t count, std::string* err) {
-  const hipError_t e = mem.get(p, count, false);
-  if (e != hipSuccess) { *err = std::string("loop search: ") + hipGetErrorString(e); return false; }
-  return true;
-}
-
 // list arrays for list_cap entries; need > 0: per-chunk regions of at least `need` points (+ the VoxelGrid context)
 static int lc_reserve(LcCtx* C, int list_cap, long long need, std::string* err) {
   if (C->list_cap < list_cap) {
     C->lists.clear();
     C->list_cap = 0;
-    if (!lc_alloc(C->lists, &C->list, list_cap, err) || !lc_alloc(C->lists, &C->det, list_cap, err) || !lc_alloc(C->lists, &C->out, list_cap, err) || !lc_alloc(C->lists, &C->jobs, list_cap, err) ||
-        !lc_alloc(C->lists, &C->geo, list_cap, err) || !lc_alloc(C->lists, &C->ntgt, list_cap, err)) return ALEGO_ERR_HIP;
+    const DevGet get{C->lists, "loop search: ", err};
+    if (!get(&C->list, list_cap) || !get(&C->det, list_cap) || !get(&C->out, list_cap) || !get(&C->jobs, list_cap) || !get(&C->geo, list_cap) || !get(&C->ntgt, list_cap)) return ALEGO_ERR_HIP;
     C->list_cap = list_cap;
     if (C->vox) { vox_destroy(&C->V); C->vox = false; }
   }
@@ -431,8 +412,10 @@ static int lc_reserve(LcCtx* C, int list_cap, long long need, std::string* err) 
     const long long cap = std::max(C->cap, need);
     lc_free_chunk(C);
     const size_t n = (size_t)cap;
-    if (!lc_alloc(C->chunk, &C->src, n, err) || !lc_alloc(C->chunk, &C->cur, n, err) || !lc_alloc(C->chunk, &C->raw, n, err) || !lc_alloc(C->chunk, &C->tgt, n, err) || !lc_alloc(C->chunk, &C->spts, n, err) ||
-        !lc_alloc(C->chunk, &C->cbox, 2 * n, err) || !lc_alloc(C->chunk, &C->cstart, n + 1, err) || !lc_alloc(C->chunk, &C->ccur, n + 1, err)) { lc_free_chunk(C); return ALEGO_ERR_HIP; }
+    const DevGet get{C->chunk, "loop search: ", err};
+    if (!get(&C->src, n) || !get(&C->cur, n) || !get(&C->raw, n) || !get(&C->tgt, n) || !get(&C->spts, n) || !get(&C->cbox, 2 * n) || !get(&C->cstart, n + 1) || !get(&C->ccur, n + 1)) {
+      lc_free_chunk(C); return ALEGO_ERR_HIP;
+    }
     // one VoxelGrid job per attempted slot of a chunk; its sort scratch is the slot's region of the raw sub-map (job.off = raw_off)
     std::vector<VoxJob> jz((size_t)C->list_cap);
     std::memset(jz.data(), 0, jz.size() * sizeof(VoxJob));
@@ -505,24 +488,32 @@ static int lc_piece(LcCtx* C, const LmCtx& L, const alego_params& P, const int* 
     *err = "loop search: detection failed"; return ALEGO_ERR_HIP;
   }
   std::vector<LcOut> o((size_t)n);
-  if (int rc = lc_attempts(C, P, slots, det.data(), n, [&](const LcJob* jobs, const LcDet* dd, int J, int nfr, float4* src, float4* raw, hipStream_t s2) {
-        ALEGO_LAUNCH(lc_gather, dim3(nfr, J), dim3(LC_DT), 0, s2, L, jobs, dd, src, raw);
-      }, o.data(), st, err)) return rc;
+  if (int rc = lc_attempts(C, P, slots, det.data(), n, loop_archive_gather(L), o.data(), st, err)) return rc;
   for (int i = 0; i < n; ++i) {
     alego_loop_result& r = res[i];
     std::memset(&r, 0, sizeof(r));
     const LcDet& D = det[i];
     r.status = D.status; r.latest_id = D.latest; r.closest_id = D.closest;
-    if (D.status != 1) continue;
-    const LcOut& O = o[i];
-    r.converged = O.converged; r.iterations = O.iterations; r.n_source = O.n_source; r.n_target = O.n_target;
-    r.fitness = O.fitness;
-    for (int k = 0; k < 16; ++k) r.correction[k] = O.correction[k];
-    r.status = (O.converged && O.fitness <= P.lc_fitness_max) ? 2 : 1;   // :697
-    alego_loop_constraint(r.correction, D.pose_latest, D.pose_closest, r.t_correct, r.between);
-    r.noise_variance = (double)(float)O.fitness;
+    if (D.status == 1) loop_result_fill(D, o[i], P.lc_fitness_max, &r);
   }
   return 0;
+}
+
+LcGather loop_archive_gather(const LmCtx& L) {   // (L outlives the attempts it is handed to)
+  return [&L](const LcJob* jobs, const LcDet* dd, int J, int nfr, float4* src, float4* raw, hipStream_t s2) {
+    ALEGO_LAUNCH(lc_gather, dim3(nfr, J), dim3(LC_DT), 0, s2, L, jobs, dd, src, raw);
+  };
+}
+
+bool loop_result_fill(const LcDet& D, const LcOut& O, double fitness_max, alego_loop_result* r) {
+  r->closest_id = D.closest;
+  r->converged = O.converged; r->iterations = O.iterations; r->n_source = O.n_source; r->n_target = O.n_target;
+  r->fitness = O.fitness;
+  for (int k = 0; k < 16; ++k) r->correction[k] = O.correction[k];
+  r->status = (O.converged && O.fitness <= fitness_max) ? 2 : 1;   // :697
+  alego_loop_constraint(r->correction, D.pose_latest, D.pose_closest, r->t_correct, r->between);
+  r->noise_variance = (double)(float)O.fitness;
+  return r->status == 2;
 }
 
 int loop_search(LcCtx** pc, const LmCtx& L, const alego_params& P, int n_slots, const int* slots, int n, alego_loop_result* res, hipStream_t st, std::string* err) {
@@ -541,6 +532,27 @@ int loop_attempts(LcCtx** pc, const alego_params& P, int n_slots, const int* slo
   if (int rc = lc_reserve(C, n_slots, 0, err)) return rc;
   if (n > 0 && hipMemcpyAsync(C->det, det, (size_t)n * sizeof(LcDet), hipMemcpyHostToDevice, st) != hipSuccess) { *err = "loop attempts: upload failed"; return ALEGO_ERR_HIP; }
   return lc_attempts(C, P, slots, det, n, gather, out, st, err);
+}
+
+int loop_rounds(LcCtx** pc, const alego_params& P, int n_slots, const int* slots, int n, int rounds, const LcGather& gather, const LcPlan& plan, const LcVerdict& verdict, hipStream_t st,
+                std::string* err) {
+  std::vector<LcDet> det((size_t)n);
+  std::vector<LcOut> res((size_t)n);
+  std::vector<char> accepted((size_t)n, 0);
+  for (int v = 0; v < rounds; ++v) {
+    bool any = false;
+    for (int i = 0; i < n; ++i) {
+      std::memset(&det[i], 0, sizeof(LcDet));
+      const bool go = !accepted[i] && plan(i, v, &det[i]);
+      det[i].status = go ? 1 : 0;
+      any = any || go;
+    }
+    if (!any) break;   // nothing left to try
+    if (int rc = loop_attempts(pc, P, n_slots, slots, det.data(), n, gather, res.data(), st, err)) return rc;
+    for (int i = 0; i < n; ++i)
+      if (det[i].status == 1) accepted[i] = verdict(i, v, det[i], res[i]);
+  }
+  return 0;
 }
 
 int loop_debug_nn1(const alego_point* tgt, int n_tgt, const alego_point* q, int nq, int32_t* idx, float* d2, hipStream_t st, std::string* err) {

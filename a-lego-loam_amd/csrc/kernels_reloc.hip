@@ -2,8 +2,9 @@
 // without an initial pose.  The rule is reloc_math.h's; everything here returns exactly what its brute force returns.
 //
 //   rl_desc      one workgroup per map frame (at alego_reloc_enable), per listed slot, or per pending (slot, archived frame) of the
-//                appearance search: every point is read once, binned, and its code raised into an LDS word per bin with atomicMax (a
-//                maximum of integers does not depend on the order); the tile is then packed to bytes and the ring key summed from it
+//                appearance search — a view of the frame's clouds each (KfClouds, kf_store.h): every point is read once, binned, and its
+//                code raised into an LDS word per bin with atomicMax (a maximum of integers does not depend on the order); the tile is
+//                then packed to bytes and the ring key summed from it
 //   rl_bound     one thread per (query, frame): B = sum over rings of |keyQ - keyM| (<= dist(Q, M, s) for every s)
 //   la_elig      (appearance search) one thread per (query, frame): B <- RL_INELIGIBLE unless the frame is eligible
 //   rl_pick      one workgroup per query: the n_cand eligible frames smallest in (B, id)
@@ -13,9 +14,10 @@
 //                wave arg-min of (dist << 8 | s) gives D and the smallest s attaining it.
 //   rl_list2     one workgroup per query: tau = the largest D among the n_cand frames rl_pick chose; the list of ALL frames with B <= tau, in id
 //                order.  A frame with B > tau has D >= B > tau: it can neither enter the n_cand smallest (D, id) nor tie with them.
-//   rl_topk      one workgroup per query: the n_cand smallest (D, id) of the second list
+//   rl_topk      one workgroup per query: the n_cand smallest (D, id) of the second list, as candidate words (reloc_math.h)
 //   rl_gather    verification: the slot's current scan under the guess (source) and the map frames around the candidate under their key poses
-//                (raw sub-map), from the map store through kf_store.h's views; VoxelGrid, lc_grid and lc_icp are kernels_loop.hip's (loop_ctx.h)
+//                (raw sub-map), from the map store through kf_store.h's views; the rounds (loop_rounds), VoxelGrid, lc_grid and lc_icp are
+//                kernels_loop.hip's (loop_ctx.h)
 //   rl_apply     one lane per accepted slot: map -> odom corrected as lm_apply_correction does, params_ replaced
 // Phase boundaries are kernel boundaries; no workgroup waits for another.
 //
@@ -33,9 +35,10 @@
 //                per frame, not a prefix (alego_map_set_stamps)
 //   candidates   the n_cand eligible frames smallest in (D_i, i), D_i and s_i as reloc_math.h's MATCH: exactly the brute force over
 //                all eligible frames and all 60 shifts, with the ring-key bound and without; those with D_i > max_dist > 0 are dropped
-//   verify       candidate v in round v, the first accepted ends the slot: source = frame nf - 1 (surf, corner, outlier) under guess6 =
-//                key pose i with yaw rl_guess_yaw(yaw_i, s_i); target = frames [i - lc_search_num, i + lc_search_num] within [0, nf - 2]
-//                under their archived poses through VoxelGrid(lc_leaf); ICP and fitness are loop_attempts'; accepted when converged &&
+//   verify       candidate v in round v, the first accepted ends the slot (loop_rounds): la_plan plans every attempt on the device, source =
+//                frame nf - 1 (surf, corner, outlier) under guess6 = key pose i with yaw rl_guess_yaw(yaw_i, s_i); target = frames
+//                [i - lc_search_num, i + lc_search_num] within [0, nf - 2] (lc_window) under their archived poses through VoxelGrid(lc_leaf);
+//                the gather is alego_loop_search's (loop_archive_gather), ICP and fitness are loop_attempts'; accepted when converged &&
 //                fitness <= fitness_max
 //   result       an alego_loop_result: t_correct / between = alego_loop_constraint(icp_final, guess6, key pose i); correction = the WORLD
 //                correction t_correct * matrix(key pose nf - 1)^-1 (f64 rigid inverse and product, rounded to f32)
@@ -76,6 +79,7 @@ struct RlQuery {
   int off;         // where the query's n-wide rows of bound / list2 / res2 start
   int tag, pad[3]; // the caller's (appearance search: the slot)
 };
+#define RL_ERR "descriptor search: "   // prefix of an allocation's error
 #define RL_INELIGIBLE 0xFFFFFFFFu   // a bound no frame reaches (B <= 20 * 15300): rl_pick and rl_list2 pass such a frame over
 
 // ---- descriptors ----------------------------------------------------------------------------------------------------------------------
@@ -96,56 +100,35 @@ DEV_INLINE int rl_desc_store(const int* s_bin, uint32_t* desc, uint16_t* key, si
 }
 __global__ void __launch_bounds__(RL_T) rl_desc(LmCtx L, int mode, const int* list, float w, float zoff, uint32_t* desc, uint16_t* key, RlSlot* state, uint16_t* klist) {
   __shared__ int s_bin[RL_BYTES];
-  const int tid = threadIdx.x;
+  const int tid = threadIdx.x, b = blockIdx.x;
   for (int i = tid; i < RL_BYTES; i += RL_T) s_bin[i] = 0;
   __syncthreads();
-  if (mode == 2) {
-    const int slot = list[2 * blockIdx.x], f = list[2 * blockIdx.x + 1];
-    const KfArcFrame A = kf_arc_frame(L, slot, f);
-    const int n = kf_sel_count(A, KF_SEL_ALL);
-    for (int i = tid; i < n; i += RL_T) {
-      const float4 p = A.pts[i];
-      int bin, code;
-      if (rl_bin(p.x, p.y, p.z, w, zoff, &bin, &code)) atomicMax(&s_bin[bin], code);
-    }
-    __syncthreads();
-    rl_desc_store(s_bin, desc, key, arc_row(L, slot, f), tid);
-    return;
-  }
-  const int e = mode == 0 ? (int)blockIdx.x : list[blockIdx.x];   // map frame / slot
-  const int* li = L.li + (size_t)(mode == 0 ? 0 : e) * LI_COUNT;
+  const int e = mode == 0 ? b : list[mode == 1 ? b : 2 * b];   // map frame / slot
+  KfClouds C;
+  size_t row = (size_t)e;
+  if (mode == 0) C = kf_clouds_row_at(L, 0, e);
+  else if (mode == 1) C = kf_clouds_cur(L, e);
+  else { const int f = list[2 * b + 1]; C = kf_clouds(kf_arc_frame(L, e, f)); row = arc_row(L, e, f); }
 #pragma unroll
-  for (int kind = 0; kind < KF_KINDS; ++kind) {
-    const float4* pts;
-    int n;
-    if (mode == 0) {
-      const KfRingRow R = kf_ring_row_at(L, 0, e, kind);
-      pts = R.raw; n = min(R.cnt[kind], R.cap);
-    } else {
-      const int cap = kf_cap_of(L, kind);
-      pts = kf_pick(kind, L.cur_corner_ds, L.cur_surf_ds, L.cur_outl_ds) + (size_t)e * cap;
-      n = min(li[LI_NCUR_C + kind], cap);
-    }
-    for (int i = tid; i < n; i += RL_T) {
-      const float4 p = pts[i];
+  for (int kind = 0; kind < KF_KINDS; ++kind)
+    for (int i = tid; i < C.n[kind]; i += RL_T) {
+      const float4 p = C.pts[kind][i];
       int bin, code;
       if (rl_bin(p.x, p.y, p.z, w, zoff, &bin, &code)) atomicMax(&s_bin[bin], code);
     }
-  }
   __syncthreads();
-  const int s = rl_desc_store(s_bin, desc, key, (size_t)e, tid);
-  if (mode == 1 && tid < RL_NR) klist[(size_t)blockIdx.x * RL_NR + tid] = (uint16_t)s;
+  const int s = rl_desc_store(s_bin, desc, key, row, tid);
+  if (mode == 1 && tid < RL_NR) klist[(size_t)b * RL_NR + tid] = (uint16_t)s;
   if (mode == 1 && tid == 0) {
     const double* ld = L.ld + (size_t)e * LD_COUNT;
     RlSlot S;
-    S.frame = li[LI_FRAME];
-    S.n[KF_CORNER] = min(li[LI_NCUR_C], L.kf_cap_c); S.n[KF_SURF] = min(li[LI_NCUR_S], L.kf_cap_s); S.n[KF_OUTL] = min(li[LI_NCUR_O], L.kf_cap_o);
+    S.frame = L.li[(size_t)e * LI_COUNT + LI_FRAME];
+    for (int k = 0; k < KF_KINDS; ++k) S.n[k] = C.n[k];
     for (int k = 0; k < 3; ++k) S.t_m2l[k] = ld[LD_T_M2L + k];
     for (int k = 0; k < 4; ++k) S.q_m2l[k] = ld[LD_Q_M2L + k];
-    state[blockIdx.x] = S;
+    state[b] = S;
   }
 }
-static_assert(LI_NCUR_S == LI_NCUR_C + KF_SURF && LI_NCUR_O == LI_NCUR_C + KF_OUTL, "rl_desc / rl_gather index the current scan's counts by kind");
 
 // ring keys of descriptors handed in by the host (alego_debug_reloc_search): one workgroup of 64 per descriptor
 __global__ void __launch_bounds__(64) rl_keys(const uint32_t* desc, uint16_t* key) {
@@ -192,18 +175,6 @@ __global__ void __launch_bounds__(RL_T) la_elig(LmCtx L, const RlQuery* qr, cons
   if (c && lane_id() == 0) atomicAdd(&nelig[blockIdx.y], c);
 }
 
-// the smallest key of the workgroup in every thread (s_min: RL_WAVES words of LDS; a barrier on entry protects the previous call's readers)
-DEV_INLINE unsigned long long rl_block_min(unsigned long long v, unsigned long long* s_min) {
-  v = bfly_min_u64(v);
-  __syncthreads();
-  if (lane_id() == 0) s_min[threadIdx.x >> 6] = v;
-  __syncthreads();
-  v = s_min[0];
-#pragma unroll
-  for (int w = 1; w < RL_WAVES; ++w) v = min(v, s_min[w]);
-  return v;
-}
-
 // grid (nq): listA[q][0 .. cntA[q]) = the min(n_cand, eligible) eligible frames smallest in (B, id), by rounds of "smallest key above the last one"
 __global__ void __launch_bounds__(RL_T) rl_pick(const RlQuery* qr, const uint32_t* bound, int n_cand, int* listA, int* cntA) {
   __shared__ unsigned long long s_min[RL_WAVES];
@@ -219,7 +190,7 @@ __global__ void __launch_bounds__(RL_T) rl_pick(const RlQuery* qr, const uint32_
       const unsigned long long key = ((unsigned long long)b[i] << 32) | (uint32_t)i;
       if (b[i] != RL_INELIGIBLE && (r == 0 || key > last)) best = min(best, key);
     }
-    last = rl_block_min(best, s_min);
+    last = block_min_u64<RL_WAVES>(best, s_min);
     if (last == ~0ull) break;   // (the same value in every thread) no eligible frame is left
     if (tid == 0) listA[q * ALEGO_RELOC_MAX_CAND + r] = (int)(last & 0xffffffffu);
   }
@@ -276,7 +247,7 @@ __global__ void __launch_bounds__(RL_T) rl_list2(const RlQuery* qr, const uint32
   if (tid == 0) cnt2[q] = carry;
 }
 
-// grid (nq): the n_cand smallest (D, id) of the second list -> cand[q][r] = D << 32 | id << 8 | s (~0: none)
+// grid (nq): the n_cand smallest (D, id) of the second list -> cand[q][r] = the candidate word (reloc_math.h; RL_CAND_NONE: none)
 __global__ void __launch_bounds__(RL_T) rl_topk(const RlQuery* qr, const int* list2, const int* cnt2, const uint32_t* res2, int n_cand, unsigned long long* cand) {
   __shared__ unsigned long long s_min[RL_WAVES];
   const int q = blockIdx.x, tid = threadIdx.x;
@@ -288,59 +259,33 @@ __global__ void __launch_bounds__(RL_T) rl_topk(const RlQuery* qr, const int* li
     if (r < n)
       for (int j = tid; j < n; j += RL_T) {
         const uint32_t v = res2[o + j];
-        const unsigned long long key = ((unsigned long long)(v >> 8) << 32) | ((unsigned long long)(uint32_t)list2[o + j] << 8) | (v & 0xffu);
+        const unsigned long long key = rl_cand_pack(v >> 8, (uint32_t)list2[o + j], v & 0xffu);
         if (r == 0 || key > last) best = min(best, key);
       }
-    last = rl_block_min(best, s_min);
-    if (tid == 0) cand[q * ALEGO_RELOC_MAX_CAND + r] = r < n ? last : ~0ull;
+    last = block_min_u64<RL_WAVES>(best, s_min);
+    if (tid == 0) cand[q * ALEGO_RELOC_MAX_CAND + r] = r < n ? last : RL_CAND_NONE;
   }
 }
 
-// points of map frame f as every reader of the store counts them (rl_desc, rl_gather, the host's plan): each cloud clamped to its capacity
-KF_FN int rl_frame_points(const int* cnt, int cap_c, int cap_s, int cap_o) {
-  const int c = cnt[KF_CORNER] < cap_c ? cnt[KF_CORNER] : cap_c, s = cnt[KF_SURF] < cap_s ? cnt[KF_SURF] : cap_s, o = cnt[KF_OUTL] < cap_o ? cnt[KF_OUTL] : cap_o;
-  return c + s + o;
-}
-DEV_INLINE int rl_frame_points(const LmCtx& L, int f) { return rl_frame_points(kf_cnt_of(L, kf_row_at(L, 0, f)), L.kf_cap_c, L.kf_cap_s, L.kf_cap_o); }
-
 // ---- verification ---------------------------------------------------------------------------------------------------------------------
-// grid (1 + frames, jobs): x = 0 the source — the slot's current scan read out surf, corner, outlier under the guess (det.pose_latest);
-// x = 1 + k the map frame jlo + k under its key pose, surf, corner, outlier (as lc_gather reads an archived frame)
+// grid (1 + frames, jobs): x = 0 the source — the slot's current scan under the guess (det.pose_latest); x = 1 + k the map frame jlo + k under
+// its key pose; both read out surf, corner, outlier (as lc_gather reads an archived frame)
 __global__ void __launch_bounds__(RL_T) rl_gather(LmCtx L, const LcJob* jobs, const LcDet* det, float4* src, float4* raw) {
   const LcJob J = jobs[blockIdx.y];
   const LcDet& D = det[J.li];
-  const int order[KF_KINDS] = {KF_SURF, KF_CORNER, KF_OUTL};
   float m[3][4];
   if (blockIdx.x == 0) {
-    const int* li = L.li + (size_t)J.slot * LI_COUNT;
     keypose_matrix(D.pose_latest, m);
-    float4* out = src + J.src_off;
-#pragma unroll
-    for (int o = 0; o < KF_KINDS; ++o) {
-      const int kind = order[o], cap = kf_cap_of(L, kind);
-      const float4* pts = kf_pick(kind, L.cur_corner_ds, L.cur_surf_ds, L.cur_outl_ds) + (size_t)J.slot * cap;
-      const int n = min(li[LI_NCUR_C + kind], cap);
-      for (int i = threadIdx.x; i < n; i += RL_T) out[i] = kf_transform(m, pts[i]);
-      out += n;
-    }
+    kf_clouds_write<RL_T>(kf_clouds_cur(L, J.slot), m, src + J.src_off);
     return;
   }
   const int f = D.jlo + (int)blockIdx.x - 1;
   if (f > D.jhi) return;
-  int off = 0;
-  for (int j = D.jlo; j < f; ++j) off += rl_frame_points(L, j);
-  float4* out = raw + J.raw_off + off;
   keypose_matrix(kf_pose_of(L, kf_row_at(L, J.slot, f)), m);
-#pragma unroll
-  for (int o = 0; o < KF_KINDS; ++o) {
-    const KfRingRow R = kf_ring_row_at(L, J.slot, f, order[o]);
-    const int n = min(R.cnt[order[o]], R.cap);
-    for (int i = threadIdx.x; i < n; i += RL_T) out[i] = kf_transform(m, R.raw[i]);
-    out += n;
-  }
+  kf_clouds_write<RL_T>(kf_clouds_row_at(L, J.slot, f), m, lc_frame_out(raw, J, D, f, [&](int j) { return kf_clouds_points(kf_clouds_row_at(L, J.slot, j)); }));
 }
 
-// ---- the appearance search of a SLAM handle: planning and verification ----------------------------------------------------------------
+// ---- the appearance search of a SLAM handle: planning ---------------------------------------------------------------------------------
 // one thread per (listed entry e, candidate k): det[e * ALEGO_RELOC_MAX_CAND + k] = the attempt on candidate k as loop_attempts takes it
 // (status 0: no such candidate), latest[e] = the key pose of the newest frame
 __global__ void __launch_bounds__(64) la_plan(LmCtx L, const int* list, const unsigned long long* cand, int n, int search_num, LcDet* det, float* latest) {
@@ -352,42 +297,14 @@ __global__ void __launch_bounds__(64) la_plan(LmCtx L, const int* list, const un
   LcDet D;
   memset(&D, 0, sizeof(D));
   const unsigned long long c = cand[idx];
-  if (c != ~0ull && nf >= 2) {
-    const int f = (int)((c >> 8) & 0xffffffu);
-    D.status = 1; D.latest = nf - 1; D.closest = f;
-    D.jlo = max(0, f - search_num); D.jhi = min(nf - 2, f + search_num);   // as lc_detect (:798-803)
-    for (int j = 0; j < 6; ++j) D.pose_latest[j] = D.pose_closest[j] = arc_pose_of(L, slot, f)[j];
-    D.pose_latest[5] = rl_guess_yaw(D.pose_latest[5], (int)(c & 0xffu));
-    D.n_src = arc_tab_points(arc_tab_of(L, slot, nf - 1));
-    long long nr = 0;
-    for (int j = D.jlo; j <= D.jhi; ++j) nr += arc_tab_points(arc_tab_of(L, slot, j));
-    D.n_raw = (int)nr;
+  if (c != RL_CAND_NONE && nf >= 2) {
+    D.status = 1; D.latest = nf - 1; D.closest = rl_cand_id(c);
+    lc_window(D.closest, search_num, nf - 2, &D.jlo, &D.jhi);   // as lc_detect
+    for (int j = 0; j < 6; ++j) D.pose_latest[j] = D.pose_closest[j] = arc_pose_of(L, slot, D.closest)[j];
+    D.pose_latest[5] = rl_guess_yaw(D.pose_latest[5], rl_cand_shift(c));
+    lc_det_sizes(L, slot, nf - 1, &D);
   }
   det[idx] = D;
-}
-
-// grid (1 + frames, jobs): x = 0 the source — the newest archived frame under the guess (det.pose_latest); x = 1 + k the archived frame
-// jlo + k under its key pose; both read out surf, corner, outlier (as lc_gather)
-__global__ void __launch_bounds__(RL_T) la_gather(LmCtx L, const LcJob* jobs, const LcDet* det, float4* src, float4* raw) {
-  const LcJob J = jobs[blockIdx.y];
-  const LcDet& D = det[J.li];
-  int f;
-  float4* out;
-  if (blockIdx.x == 0) {
-    f = D.latest;
-    out = src + J.src_off;
-  } else {
-    f = D.jlo + (int)blockIdx.x - 1;
-    if (f > D.jhi) return;
-    int off = 0;
-    for (int j = D.jlo; j < f; ++j) off += arc_tab_points(arc_tab_of(L, J.slot, j));
-    out = raw + J.raw_off + off;
-  }
-  const KfArcFrame A = kf_arc_frame(L, J.slot, f);
-  const int n = kf_sel_count(A, KF_SEL_ALL);
-  float m[3][4];
-  keypose_matrix(blockIdx.x == 0 ? D.pose_latest : A.pose, m);
-  for (int i = threadIdx.x; i < n; i += RL_T) out[i] = kf_transform(m, A.pts[kf_arc_index(A.nc, A.ns, KF_SEL_ALL, i)]);
 }
 
 struct RlApply { int slot, pad; double rc[12], params6[6]; };
@@ -437,12 +354,6 @@ struct RlCtx {
   DevPool store, scratch;               // own what reloc_enable allocates (valid while n_slots > 0) and the search scratch (valid while pairs_cap > 0)
 };
 
-template <class T>
-static bool rl_alloc(DevPool& mem, T** p, size_t count, std::string* err) {
-  const hipError_t e = mem.get(p, count, false);
-  if (e != hipSuccess) { *err = std::string("descriptor search: ") + hipGetErrorString(e); return false; }
-  return true;
-}
 void reloc_ctx_destroy(RlCtx* R) {
   if (!R) return;
   R->scratch.clear(); R->store.clear(); R->la_store.clear(); R->la_pend.clear();
@@ -460,9 +371,9 @@ int reloc_enable(RlCtx** pr, const LmCtx& L, int n_slots, double max_range, doub
   const int N = L.loc_n;
   R->w = rl_ring_width(max_range); R->zoff = rl_z_offset(z_offset);
   auto undo = [&](int rc) { R->store.clear(); return rc; };   // (the handle stays what it was)
-  if (!rl_alloc(R->store, &R->mdesc, (size_t)N * RL_WORDS, err) || !rl_alloc(R->store, &R->mkey, (size_t)N * RL_NR, err) || !rl_alloc(R->store, &R->qdesc, (size_t)n_slots * RL_WORDS, err) ||
-      !rl_alloc(R->store, &R->qkey, (size_t)n_slots * RL_NR, err) || !rl_alloc(R->store, &R->list, (size_t)n_slots, err) || !rl_alloc(R->store, &R->apply, (size_t)n_slots, err) ||
-      !rl_alloc(R->store, &R->state, (size_t)n_slots, err) || !rl_alloc(R->store, &R->klist, (size_t)n_slots * RL_NR, err)) return undo(ALEGO_ERR_HIP);
+  const DevGet get{R->store, RL_ERR, err};
+  if (!get(&R->mdesc, (size_t)N * RL_WORDS) || !get(&R->mkey, (size_t)N * RL_NR) || !get(&R->qdesc, (size_t)n_slots * RL_WORDS) || !get(&R->qkey, (size_t)n_slots * RL_NR) ||
+      !get(&R->list, (size_t)n_slots) || !get(&R->apply, (size_t)n_slots) || !get(&R->state, (size_t)n_slots) || !get(&R->klist, (size_t)n_slots * RL_NR)) return undo(ALEGO_ERR_HIP);
   hipError_t e = hipMemsetAsync(R->qdesc, 0, std::max<size_t>(16, (size_t)n_slots * RL_BYTES), st);
   if (e == hipSuccess) e = hipMemsetAsync(R->qkey, 0, std::max<size_t>(16, (size_t)n_slots * RL_NR * 2), st);
   if (e == hipSuccess && N > 0) ALEGO_LAUNCH(rl_desc, dim3(N), dim3(RL_T), 0, st, L, 0, (const int*)nullptr, R->w, R->zoff, R->mdesc, R->mkey, (RlSlot*)nullptr, (uint16_t*)nullptr);
@@ -474,21 +385,21 @@ int reloc_enable(RlCtx** pr, const LmCtx& L, int n_slots, double max_range, doub
   if (e != hipSuccess) { *err = std::string("alego_reloc_enable: ") + hipGetErrorString(e); return undo(ALEGO_ERR_HIP); }
   R->cnt.resize(N); R->pose.resize((size_t)N * 6);
   for (int i = 0; i < N; ++i) {
-    R->cnt[i] = rl_frame_points(cnt.data() + (size_t)i * KF_CNT_W, L.kf_cap_c, L.kf_cap_s, L.kf_cap_o);
+    R->cnt[i] = kf_clouds_points(kf_clouds_row_at(L, 0, i, cnt.data() + (size_t)i * KF_CNT_W));   // as rl_gather counts them
     for (int k = 0; k < 6; ++k) R->pose[(size_t)i * 6 + k] = pose[(size_t)i * KF_POSE_W + k];
   }
   R->N = N; R->n_slots = n_slots;
   return 0;
 }
 
-// The exact search of nq queries (qr[q]; off is filled in here): cand[q][r] = D << 32 | id << 8 | s, ~0 where fewer frames are eligible.
+// The exact search of nq queries (qr[q]; off is filled in here): cand[q][r] = the candidate word, RL_CAND_NONE where fewer frames are eligible.
 // Queries are taken in chunks of consecutive queries whose frames sum to at most the budget; a query's result does not depend on its chunk.
 // mask (may be empty) runs behind rl_bound on the records and bounds of a chunk of c queries whose largest n is nmax; nelig (may be
 // null) receives what it summed into R->nelig per query.
 typedef std::function<void(const RlQuery* qr, int c, int nmax, uint32_t* bound, int* nelig, hipStream_t st)> RlMask;
 static int rl_search_run(RlCtx* R, const uint32_t* qdesc, const uint16_t* qkey, RlQuery* qr, int nq, const uint32_t* mdesc, const uint16_t* mkey, int n_cand,
                          unsigned long long* cand, const RlMask& mask, int* nelig, hipStream_t st, std::string* err) {
-  for (size_t i = 0; i < (size_t)nq * ALEGO_RELOC_MAX_CAND; ++i) cand[i] = ~0ull;
+  for (size_t i = 0; i < (size_t)nq * ALEGO_RELOC_MAX_CAND; ++i) cand[i] = RL_CAND_NONE;
   long long all = 0;
   for (int q = 0; q < nq; ++q) { all += qr[q].n; if (nelig) nelig[q] = 0; }
   R->stats[0] = 0; R->stats[1] = (int)std::min<long long>(all, 0x7fffffff);
@@ -510,9 +421,9 @@ static int rl_search_run(RlCtx* R, const uint32_t* qdesc, const uint16_t* qkey, 
     pc = std::max(R->pairs_cap, pc); qc = std::max(R->q_cap, qc);
     if (hipStreamSynchronize(st) != hipSuccess) { *err = "descriptor search: a stream failed"; return ALEGO_ERR_HIP; }
     R->scratch.clear(); R->pairs_cap = R->q_cap = 0;
-    if (!rl_alloc(R->scratch, &R->bound, pc, err) || !rl_alloc(R->scratch, &R->res2, pc, err) || !rl_alloc(R->scratch, &R->list2, pc, err) || !rl_alloc(R->scratch, &R->resA, qc * ALEGO_RELOC_MAX_CAND, err) ||
-        !rl_alloc(R->scratch, &R->listA, qc * ALEGO_RELOC_MAX_CAND, err) || !rl_alloc(R->scratch, &R->cntA, qc, err) || !rl_alloc(R->scratch, &R->cnt2, qc, err) || !rl_alloc(R->scratch, &R->qr, qc, err) ||
-        !rl_alloc(R->scratch, &R->nelig, qc, err) || !rl_alloc(R->scratch, &R->cand, qc * ALEGO_RELOC_MAX_CAND, err)) { R->scratch.clear(); return ALEGO_ERR_HIP; }
+    const DevGet get{R->scratch, RL_ERR, err};
+    if (!get(&R->bound, pc) || !get(&R->res2, pc) || !get(&R->list2, pc) || !get(&R->resA, qc * ALEGO_RELOC_MAX_CAND) || !get(&R->listA, qc * ALEGO_RELOC_MAX_CAND) || !get(&R->cntA, qc) ||
+        !get(&R->cnt2, qc) || !get(&R->qr, qc) || !get(&R->nelig, qc) || !get(&R->cand, qc * ALEGO_RELOC_MAX_CAND)) { R->scratch.clear(); return ALEGO_ERR_HIP; }
     R->pairs_cap = pc; R->q_cap = qc;
   }
   std::vector<int> cnt2;
@@ -559,8 +470,8 @@ int reloc_debug_search(RlCtx** pr, const uint8_t* map_desc, int n_map, const uin
   DevPool tmp;   // temporaries of this call
   uint32_t *md = nullptr, *qd = nullptr;
   uint16_t *mk = nullptr, *qk = nullptr;
-  if (!rl_alloc(tmp, &md, (size_t)n_map * RL_WORDS, err) || !rl_alloc(tmp, &qd, (size_t)n_q * RL_WORDS, err) || !rl_alloc(tmp, &mk, (size_t)n_map * RL_NR, err) || !rl_alloc(tmp, &qk, (size_t)n_q * RL_NR, err))
-    return ALEGO_ERR_HIP;
+  const DevGet get{tmp, RL_ERR, err};
+  if (!get(&md, (size_t)n_map * RL_WORDS) || !get(&qd, (size_t)n_q * RL_WORDS) || !get(&mk, (size_t)n_map * RL_NR) || !get(&qk, (size_t)n_q * RL_NR)) return ALEGO_ERR_HIP;
   hipError_t e = n_map ? hipMemcpyAsync(md, map_desc, (size_t)n_map * RL_BYTES, hipMemcpyHostToDevice, st) : hipSuccess;
   if (e == hipSuccess && n_q) e = hipMemcpyAsync(qd, q_desc, (size_t)n_q * RL_BYTES, hipMemcpyHostToDevice, st);
   if (e != hipSuccess) { *err = "debug_reloc_search: upload failed"; return ALEGO_ERR_HIP; }
@@ -575,10 +486,8 @@ int reloc_debug_search(RlCtx** pr, const uint8_t* map_desc, int n_map, const uin
   if (rc) return rc;
   for (int q = 0; q < n_q; ++q)
     for (int r = 0; r < n_cand; ++r) {
-      const unsigned long long c = cand[(size_t)q * ALEGO_RELOC_MAX_CAND + r];
-      const size_t o = (size_t)q * n_cand + r;
-      if (c == ~0ull) { ids[o] = -1; dists[o] = -1; shifts[o] = -1; }
-      else { ids[o] = (int32_t)((c >> 8) & 0xffffffu); dists[o] = (int32_t)(c >> 32); shifts[o] = (int32_t)(c & 0xffu); }
+      const size_t o = (size_t)q * n_cand;
+      if (!rl_cand_unpack(&cand[(size_t)q * ALEGO_RELOC_MAX_CAND], r, ids + o, dists + o, shifts + o)) ids[o + r] = dists[o + r] = shifts[o + r] = -1;
     }
   return 0;
 }
@@ -637,52 +546,35 @@ int reloc_run(RlCtx* R, LcCtx** lc, const LmCtx& L, const alego_params& P, const
   if (int rc = rl_search_run(R, R->qdesc, R->qkey, qr.data(), (int)qi.size(), R->mdesc, R->mkey, n_cand, cand.data(), RlMask(), nullptr, st, err)) return rc;
   for (size_t a = 0; a < qi.size(); ++a) {
     alego_reloc_result& r = out[qi[a]];
-    for (int k = 0; k < n_cand; ++k) {
-      const unsigned long long c = cand[a * ALEGO_RELOC_MAX_CAND + k];
-      if (c == ~0ull) break;
-      r.cand_id[k] = (int32_t)((c >> 8) & 0xffffffu); r.cand_dist[k] = (int32_t)(c >> 32); r.cand_shift[k] = (int32_t)(c & 0xffu);
-      r.n_cand = k + 1;
-    }
+    while (r.n_cand < n_cand && rl_cand_unpack(&cand[a * ALEGO_RELOC_MAX_CAND], r.n_cand, r.cand_id, r.cand_dist, r.cand_shift)) ++r.n_cand;
     r.status = r.n_cand > 0 ? 1 : 0;
   }
-  // verification: round v tries candidate v of every slot that has one and is not accepted yet
-  std::vector<LcDet> det((size_t)n);
-  std::vector<LcOut> res((size_t)n);
-  for (int v = 0; v < verify; ++v) {
-    bool any = false;
-    for (int i = 0; i < n; ++i) {
-      LcDet& D = det[i];
-      std::memset(&D, 0, sizeof(D));
-      alego_reloc_result& r = out[i];
-      if (r.status != 1 || r.n_cand <= v) continue;
-      any = true;
-      const int f = r.cand_id[v];
-      D.status = 1; D.latest = -1; D.closest = f;
-      D.jlo = std::max(0, f - P.lc_search_num); D.jhi = std::min(N - 1, f + P.lc_search_num);
-      for (int k = 0; k < 6; ++k) D.pose_latest[k] = D.pose_closest[k] = R->pose[(size_t)f * 6 + k];
-      D.pose_latest[5] = rl_guess_yaw(D.pose_latest[5], r.cand_shift[v]);
-      D.n_src = state[i].n[KF_CORNER] + state[i].n[KF_SURF] + state[i].n[KF_OUTL];
-      for (int j = D.jlo; j <= D.jhi; ++j) D.n_raw += R->cnt[j];
-    }
-    if (!any) break;
-    if (int rc = loop_attempts(lc, P, R->n_slots, slots, det.data(), n, [&](const LcJob* jobs, const LcDet* dd, int J, int nfr, float4* src, float4* raw, hipStream_t s2) {
-          ALEGO_LAUNCH(rl_gather, dim3(nfr, J), dim3(RL_T), 0, s2, L, jobs, dd, src, raw);
-        }, res.data(), st, err)) return rc;
-    for (int i = 0; i < n; ++i) {
-      if (det[i].status != 1) continue;
-      alego_reloc_result& r = out[i];
-      const LcOut& O = res[i];
-      r.converged = O.converged; r.iterations = O.iterations; r.n_source = O.n_source; r.n_target = O.n_target; r.fitness = O.fitness;
-      for (int k = 0; k < 16; ++k) r.correction[k] = O.correction[k];
-      for (int k = 0; k < 6; ++k) r.guess6[k] = det[i].pose_latest[k];
-      double between[12];
-      alego_loop_constraint(r.correction, r.guess6, r.guess6, r.t_map, between);   // t_map = correction * matrix(guess6), as t_correct (:714-715)
-      if (O.converged && O.fitness <= P.lc_fitness_max) {   // :697
+  // verification (loop_rounds): candidate v of slot i is the scan under the guess against the map frames around the candidate
+  if (int rc = loop_rounds(lc, P, R->n_slots, slots, n, verify, [&](const LcJob* jobs, const LcDet* dd, int J, int nfr, float4* src, float4* raw, hipStream_t s2) {
+        ALEGO_LAUNCH(rl_gather, dim3(nfr, J), dim3(RL_T), 0, s2, L, jobs, dd, src, raw);
+      }, [&](int i, int v, LcDet* D) {
+        const alego_reloc_result& r = out[i];
+        if (r.n_cand <= v) return false;
+        const int f = r.cand_id[v];
+        D->latest = -1; D->closest = f;
+        lc_window(f, P.lc_search_num, N - 1, &D->jlo, &D->jhi);
+        for (int k = 0; k < 6; ++k) D->pose_latest[k] = D->pose_closest[k] = R->pose[(size_t)f * 6 + k];
+        D->pose_latest[5] = rl_guess_yaw(D->pose_latest[5], r.cand_shift[v]);
+        D->n_src = state[i].n[KF_CORNER] + state[i].n[KF_SURF] + state[i].n[KF_OUTL];
+        for (int j = D->jlo; j <= D->jhi; ++j) D->n_raw += R->cnt[j];
+        return true;
+      }, [&](int i, int v, const LcDet& D, const LcOut& O) {
+        alego_reloc_result& r = out[i];
+        r.converged = O.converged; r.iterations = O.iterations; r.n_source = O.n_source; r.n_target = O.n_target; r.fitness = O.fitness;
+        for (int k = 0; k < 16; ++k) r.correction[k] = O.correction[k];
+        for (int k = 0; k < 6; ++k) r.guess6[k] = D.pose_latest[k];
+        double between[12];
+        alego_loop_constraint(r.correction, r.guess6, r.guess6, r.t_map, between);   // t_map = correction * matrix(guess6), as t_correct (:714-715)
+        if (!(O.converged && O.fitness <= P.lc_fitness_max)) return false;   // :697
         r.status = 2; r.verified = v;
         rl_placement(r.t_map, state[i].t_m2l, state[i].q_m2l, r.rc, r.params6);
-      }
-    }
-  }
+        return true;
+      }, st, err)) return rc;
   if (apply) {
     std::vector<RlApply> ap;
     for (int i = 0; i < n; ++i)
@@ -709,8 +601,8 @@ int loop_app_enable(RlCtx** pr, const LmCtx& L, int n_slots, double max_range, d
   if (!*pr) *pr = new RlCtx();
   RlCtx* R = *pr;
   const size_t rows = (size_t)n_slots * L.arc_frames_cap, ent = (size_t)n_slots * ALEGO_RELOC_MAX_CAND;
-  if (!rl_alloc(R->la_store, &R->la_desc, rows * RL_WORDS, err) || !rl_alloc(R->la_store, &R->la_key, rows * RL_NR, err) || !rl_alloc(R->la_store, &R->la_list, (size_t)n_slots, err) ||
-      !rl_alloc(R->la_store, &R->la_cand, ent, err) || !rl_alloc(R->la_store, &R->la_det, ent, err) || !rl_alloc(R->la_store, &R->la_latest, (size_t)n_slots * 6, err)) {
+  const DevGet get{R->la_store, RL_ERR, err};
+  if (!get(&R->la_desc, rows * RL_WORDS) || !get(&R->la_key, rows * RL_NR) || !get(&R->la_list, (size_t)n_slots) || !get(&R->la_cand, ent) || !get(&R->la_det, ent) || !get(&R->la_latest, (size_t)n_slots * 6)) {
     R->la_store.clear();
     return ALEGO_ERR_HIP;
   }
@@ -793,21 +685,22 @@ int loop_app_run(RlCtx* R, LcCtx** lc, const LmCtx& L, const alego_params& P, co
                                ALEGO_LAUNCH(la_elig, dim3(std::max(1, (nmax + RL_T - 1) / RL_T), c), dim3(RL_T), 0, s2, L, dq, (const uint16_t*)R->la_key, gap, jump2, bound, ne);
                              }, nelig.data(), st, err)) return rc;
   if (hipStreamSynchronize(st) != hipSuccess) { *err = "alego_loop_search_appearance: descriptors failed"; return ALEGO_ERR_HIP; }   // (no query: the descriptors alone)
-  std::vector<unsigned long long> ecand((size_t)n * ALEGO_RELOC_MAX_CAND, ~0ull);   // per listed entry, after the max_dist cut
+  std::vector<unsigned long long> ecand((size_t)n * ALEGO_RELOC_MAX_CAND, RL_CAND_NONE);   // per listed entry, after the max_dist cut
   std::vector<int> ncand((size_t)n, 0);
   bool any = false;
   for (size_t a = 0; a < qi.size(); ++a) {
     const int i = qi[a];
+    unsigned long long* ec = &ecand[(size_t)i * ALEGO_RELOC_MAX_CAND];
     int k = 0;
     for (; k < o.n_cand; ++k) {
       const unsigned long long c = cand[a * ALEGO_RELOC_MAX_CAND + k];
-      if (c == ~0ull || (o.max_dist > 0 && (long long)(c >> 32) > (long long)o.max_dist)) break;
-      ecand[(size_t)i * ALEGO_RELOC_MAX_CAND + k] = c;
-      if (info) { info[i].cand_id[k] = (int32_t)((c >> 8) & 0xffffffu); info[i].cand_dist[k] = (int32_t)(c >> 32); info[i].cand_shift[k] = (int32_t)(c & 0xffu); }
+      if (c == RL_CAND_NONE || (o.max_dist > 0 && rl_cand_dist(c) > o.max_dist)) break;
+      ec[k] = c;
+      if (info) rl_cand_unpack(ec, k, info[i].cand_id, info[i].cand_dist, info[i].cand_shift);
     }
     ncand[i] = k;
     if (info) { info[i].n_eligible = nelig[a]; info[i].n_cand = k; }
-    if (k > 0) { out[i].status = 1; out[i].closest_id = (int32_t)((ecand[(size_t)i * ALEGO_RELOC_MAX_CAND] >> 8) & 0xffffffu); any = true; }
+    if (k > 0) { out[i].status = 1; out[i].closest_id = rl_cand_id(ec[0]); any = true; }
   }
   if (!any || o.verify == 0) return 0;
   // the attempts on every candidate, planned on the device from the archive's tables
@@ -821,40 +714,21 @@ int loop_app_run(RlCtx* R, LcCtx** lc, const LmCtx& L, const alego_params& P, co
     *err = "alego_loop_search_appearance: planning failed"; return ALEGO_ERR_HIP;
   }
   const double fitness_max = o.fitness_max > 0.0 ? o.fitness_max : P.lc_fitness_max;
-  std::vector<LcDet> det((size_t)n);
-  std::vector<LcOut> res((size_t)n);
-  for (int v = 0; v < o.verify; ++v) {   // round v tries candidate v of every slot that has one and is not accepted yet
-    bool some = false;
-    for (int i = 0; i < n; ++i) {
-      std::memset(&det[i], 0, sizeof(LcDet));
-      if (out[i].status != 1 || ncand[i] <= v) continue;
-      det[i] = plan[(size_t)i * ALEGO_RELOC_MAX_CAND + v];
-      some = some || det[i].status == 1;
+  return loop_rounds(lc, P, R->la_slots, slots, n, o.verify, loop_archive_gather(L), [&](int i, int v, LcDet* D) {
+    if (ncand[i] <= v) return false;
+    *D = plan[(size_t)i * ALEGO_RELOC_MAX_CAND + v];
+    return D->status == 1;
+  }, [&](int i, int v, const LcDet& D, const LcOut& O) {
+    alego_loop_result& r = out[i];
+    const bool ok = loop_result_fill(D, O, fitness_max, &r);
+    la_world_correction(r.t_correct, latest.data() + (size_t)i * 6, r.correction);
+    if (info) {
+      for (int k = 0; k < 6; ++k) info[i].guess6[k] = D.pose_latest[k];
+      for (int k = 0; k < 16; ++k) info[i].icp_final[k] = O.correction[k];
+      if (ok) info[i].verified = v;
     }
-    if (!some) break;
-    if (int rc = loop_attempts(lc, P, R->la_slots, slots, det.data(), n, [&](const LcJob* jobs, const LcDet* dd, int J, int nfr, float4* src, float4* raw, hipStream_t s2) {
-          ALEGO_LAUNCH(la_gather, dim3(nfr, J), dim3(RL_T), 0, s2, L, jobs, dd, src, raw);
-        }, res.data(), st, err)) return rc;
-    for (int i = 0; i < n; ++i) {
-      const LcDet& D = det[i];
-      if (D.status != 1) continue;
-      alego_loop_result& r = out[i];
-      const LcOut& O = res[i];
-      r.closest_id = D.closest;
-      r.converged = O.converged; r.iterations = O.iterations; r.n_source = O.n_source; r.n_target = O.n_target; r.fitness = O.fitness;
-      alego_loop_constraint(O.correction, D.pose_latest, D.pose_closest, r.t_correct, r.between);
-      la_world_correction(r.t_correct, latest.data() + (size_t)i * 6, r.correction);
-      r.noise_variance = (double)(float)O.fitness;
-      const bool ok = O.converged && O.fitness <= fitness_max;
-      if (ok) r.status = 2;
-      if (info) {
-        for (int k = 0; k < 6; ++k) info[i].guess6[k] = D.pose_latest[k];
-        for (int k = 0; k < 16; ++k) info[i].icp_final[k] = O.correction[k];
-        if (ok) info[i].verified = v;
-      }
-    }
-  }
-  return 0;
+    return ok;
+  }, st, err);
 }
 
 // ---- host twins (plain C++) -----------------------------------------------------------------------------------------------------------
@@ -899,7 +773,7 @@ extern "C" int alego_loop_appearance_candidates(const uint8_t* desc, const float
   if (!any) return 0;   // no point in range
   const float jump2 = (float)(max_jump * max_jump);
   const float* b = keyposes6 + (size_t)(n - 1) * 6;
-  std::vector<unsigned long long> all;   // D << 32 | id << 8 | s
+  std::vector<unsigned long long> all;   // candidate words
   for (int i = 0; i < n - 1; ++i) {
     if (!(stamps[n - 1] - stamps[i] > min_time_gap)) continue;
     if (max_jump > 0.0) {
@@ -909,14 +783,13 @@ extern "C" int alego_loop_appearance_candidates(const uint8_t* desc, const float
     }
     int32_t d, s;
     alego_reloc_match(q, desc + (size_t)i * RL_BYTES, &d, &s);
-    all.push_back(((unsigned long long)(uint32_t)d << 32) | ((unsigned long long)(uint32_t)i << 8) | (unsigned)s);
+    all.push_back(rl_cand_pack((uint32_t)d, (uint32_t)i, (uint32_t)s));
   }
   std::sort(all.begin(), all.end());
   int k = 0;
   for (; k < n_cand && k < (int)all.size(); ++k) {
-    const int32_t d = (int32_t)(all[k] >> 32);
-    if (max_dist > 0 && d > max_dist) break;
-    ids[k] = (int32_t)((all[k] >> 8) & 0xffffffu); dists[k] = d; shifts[k] = (int32_t)(all[k] & 0xffu);
+    if (max_dist > 0 && rl_cand_dist(all[k]) > max_dist) break;
+    rl_cand_unpack(all.data(), k, ids, dists, shifts);
   }
   return k;
 }

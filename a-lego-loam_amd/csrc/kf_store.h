@@ -48,6 +48,40 @@ KF_FN int kf_arc_index(int nc, int ns, int kinds, int i) {
   const int c0 = kf_out_start(nc, ns, kinds, KF_CORNER), o0 = kf_out_start(nc, ns, kinds, KF_OUTL);
   return i < c0 ? nc + i : (i < o0 ? i - c0 : nc + ns + (i - o0));
 }
+// One view of a frame's clouds, whichever store holds it: (pointer, points) per kind in kind order, counted as every reader counts them.
+// (built with `kind` a constant after unrolling, so kf_pick selects values and no copy of L goes to scratch)
+struct KfClouds { const float4* pts[KF_KINDS]; int n[KF_KINDS]; };
+KF_FN int kf_clouds_points(const KfClouds& C) { return C.n[KF_CORNER] + C.n[KF_SURF] + C.n[KF_OUTL]; }
+KF_FN KfClouds kf_clouds(const KfArcFrame& A) { return KfClouds{{A.pts, A.pts + A.nc, A.pts + A.nc + A.ns}, {A.nc, A.ns, A.no}}; }
+// a row of the ring or the map store, each count clamped to its capacity; cnt: the row's kf_cnt as the caller can read it (the device's, or a host copy)
+KF_FN KfClouds kf_clouds_row_at(const LmCtx& L, int slot, int entry, const int* cnt) {
+  const size_t r = kf_row_at(L, slot, entry);
+  KfClouds C;
+#pragma unroll
+  for (int k = 0; k < KF_KINDS; ++k) { const int cap = kf_cap_of(L, k); C.pts[k] = kf_raw_of(L, r, k); C.n[k] = cnt[k] < cap ? cnt[k] : cap; }
+  return C;
+}
+DEV_INLINE KfClouds kf_clouds_row_at(const LmCtx& L, int slot, int entry) { return kf_clouds_row_at(L, slot, entry, kf_cnt_of(L, kf_row_at(L, slot, entry))); }
+// a slot's current scan (laser_corner_ds_, laser_surf_ds_, laser_outlier_ds_), each count clamped to the capacity of its cloud
+static_assert(LI_NCUR_S == LI_NCUR_C + KF_SURF && LI_NCUR_O == LI_NCUR_C + KF_OUTL, "kf_clouds_cur indexes the current scan's counts by kind");
+DEV_INLINE KfClouds kf_clouds_cur(const LmCtx& L, int slot) {
+  const int* li = L.li + (size_t)slot * LI_COUNT;
+  KfClouds C;
+#pragma unroll
+  for (int k = 0; k < KF_KINDS; ++k) { const int cap = kf_cap_of(L, k); C.pts[k] = kf_pick(k, L.cur_corner_ds, L.cur_surf_ds, L.cur_outl_ds) + (size_t)slot * cap; C.n[k] = min(li[LI_NCUR_C + k], cap); }
+  return C;
+}
+// the frame under m in read-out order (surf, corner, outlier: see kf_sel_count) -> out[0 .. kf_clouds_points(C)); one workgroup of T threads
+template <int T> DEV_INLINE void kf_clouds_write(const KfClouds& C, const float m[3][4], float4* out) {
+  const int order[KF_KINDS] = {KF_SURF, KF_CORNER, KF_OUTL};
+#pragma unroll
+  for (int o = 0; o < KF_KINDS; ++o) {
+    const float4* pts = C.pts[order[o]];
+    const int n = C.n[order[o]];
+    for (int i = threadIdx.x; i < n; i += T) out[i] = kf_transform(m, pts[i]);
+    out += n;
+  }
+}
 // The body of lm_store_kf (kernels_lm.hip: described there) and pg_retransform; grid (x, 3 kinds, .), T threads.  fresh: the slot's current scan is stored into the row first.
 template <int T> DEV_INLINE void kf_row_to_tmp(const LmCtx& L, int slot, int entry, int kind, bool fresh) {
   int* li = L.li + (size_t)slot * LI_COUNT;

@@ -1,6 +1,8 @@
 // loop_ctx.h — one ICP attempt per listed slot as kernels_loop.hip runs it (VoxelGrid(lc_leaf) of the raw sub-map, lc_grid, lc_icp), for the
-// callers that bring their own source and sub-map: alego_loop_search gathers them from the archive, alego_loc_relocalize (kernels_reloc.hip)
-// from the current scan and the frozen map store.
+// callers that bring their own source and sub-map: alego_loop_search and the appearance search gather them from the archive
+// (loop_archive_gather), alego_loc_relocalize (kernels_reloc.hip) from the current scan and the frozen map store.  What an attempt is made
+// of has one definition here, whoever plans it: the window (lc_window, reloc_math.h), the sizes, where a frame lands in the raw sub-map,
+// the verification rounds and the alego_loop_result of a verdict.
 #ifndef ALEGO_LOOP_CTX_H_
 #define ALEGO_LOOP_CTX_H_
 #include <hip/hip_runtime.h>
@@ -9,6 +11,8 @@
 #include <string>
 
 #include "../../include/alego_mi355x.h"
+#include "kf_store.h"
+#include "reloc_math.h"
 
 struct LcDet {        // lc_detect's verdict on one listed slot
   int status;         // 0 no candidate, 1 attempt, -1 the archive dropped frames
@@ -19,7 +23,20 @@ struct LcDet {        // lc_detect's verdict on one listed slot
 struct LcJob { int li, slot, src_off, raw_off, cell_off, cell_cap; };   // one attempted slot of a chunk and its scratch regions
 struct LcOut { int converged, iterations, n_source, n_target; double fitness; float correction[16]; };   // lc_icp's verdict on one attempt
 
-struct LmCtx;
+// n_src = the points of archived frame `src` of the slot, n_raw = those of the window D->jlo .. D->jhi, from the archive's tables
+DEV_INLINE void lc_det_sizes(const LmCtx& L, int slot, int src, LcDet* D) {
+  D->n_src = arc_tab_points(arc_tab_of(L, slot, src));
+  long long n = 0;
+  for (int j = D->jlo; j <= D->jhi; ++j) n += arc_tab_points(arc_tab_of(L, slot, j));
+  D->n_raw = (int)n;
+}
+// where frame f of the window starts in the job's raw sub-map: behind frames jlo .. f - 1, points(j) = the points the gather writes for frame j
+template <class F> DEV_INLINE float4* lc_frame_out(float4* raw, const LcJob& J, const LcDet& D, int f, F points) {
+  int off = 0;
+  for (int j = D.jlo; j < f; ++j) off += points(j);
+  return raw + J.raw_off + off;
+}
+
 struct LcCtx;   // the batched loop-closure search: detection / chunk scratch, allocated by the first call and kept with the handle
 void loop_ctx_destroy(LcCtx* C);
 void loop_ctx_set_budget(LcCtx** pc, long long points);
@@ -33,4 +50,16 @@ typedef std::function<void(const LcJob* jobs, const LcDet* det, int J, int nfr, 
 // det[0 .. n) on the host (n <= n_slots; status == 1: attempted, with n_src, n_raw and whatever the gather reads filled in) -> out[i] of every attempt.
 // Chunked under the context's point budget (ALEGO_LC_BUDGET): chunking never changes a result.  Synchronous on `st`.
 int loop_attempts(LcCtx** pc, const alego_params& P, int n_slots, const int* slots, const LcDet* det, int n, const LcGather& gather, LcOut* out, hipStream_t st, std::string* err);
+// the gather of attempts read from the archive (lc_gather): source = frame det.latest under det.pose_latest, sub-map = frames jlo .. jhi under their archived poses
+LcGather loop_archive_gather(const LmCtx& L);
+// Verification rounds over n entries (n <= n_slots): round v < rounds tries candidate v of every entry that has one and is not accepted yet; the
+// first acceptance ends the entry, and a round with nothing left to try ends the rounds.  plan(i, v, D): fill attempt (i, v) into the zeroed *D as
+// loop_attempts takes it and return true, or decline; verdict(i, v, D, O): the verdict O on attempt D of (i, v) -> was it accepted?
+typedef std::function<bool(int i, int v, LcDet* D)> LcPlan;
+typedef std::function<bool(int i, int v, const LcDet& D, const LcOut& O)> LcVerdict;
+int loop_rounds(LcCtx** pc, const alego_params& P, int n_slots, const int* slots, int n, int rounds, const LcGather& gather, const LcPlan& plan, const LcVerdict& verdict, hipStream_t st,
+                std::string* err);
+// r <- the verdict O on attempt D: closest_id, the ICP's numbers, t_correct / between (alego_loop_constraint), noise_variance, status 2 when
+// converged && fitness <= fitness_max (:697) and 1 otherwise; returns whether it was accepted
+bool loop_result_fill(const LcDet& D, const LcOut& O, double fitness_max, alego_loop_result* r);
 #endif

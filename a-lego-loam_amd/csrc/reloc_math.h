@@ -14,6 +14,10 @@
 // |sum a - sum b| <= sum |a - b|, B = sum over r of |keyQ[r] - keyM[r]| <= dist(Q, M, s) for every s: the bound the search prunes with.
 // GUESS: the key pose of the matched frame with yaw - (float)s * (float)(2 pi / 60), f32.
 // This rule is the project's own (in the family of Scan Context), chosen so that the device result is exactly defined.
+// CANDIDATE WORD: a search result (D, frame id, s) as one u64 whose order by `<` is the order by (D, id, s): D <= 20 * 15300 above bit 32,
+// id < 2^24 in bits 8 .. 31, s < 60 in the low byte; RL_CAND_NONE is above every candidate.
+// ATTEMPT WINDOW: the history frames an ICP attempt on frame `closest` is aligned to (detectLoopClosure, src/laserMapping.cpp:798-803), for
+// alego_loop_search, the appearance search and relocalisation alike.  Plain C++ that a host compiler reads without the HIP runtime.
 #ifndef ALEGO_RELOC_MATH_H_
 #define ALEGO_RELOC_MATH_H_
 #include <math.h>
@@ -68,5 +72,24 @@ RL_FN uint32_t rl_key_bound(const uint16_t* kq, const uint16_t* km) {
 }
 // f32 yaw of the guess
 RL_FN float rl_guess_yaw(float yaw, int shift) { return yaw - (float)shift * RL_RAD_PER_SECTOR; }
+
+// the candidate word
+#define RL_CAND_NONE (~0ull)
+RL_FN unsigned long long rl_cand_pack(uint32_t dist, uint32_t id, uint32_t shift) { return ((unsigned long long)dist << 32) | ((unsigned long long)id << 8) | shift; }
+RL_FN int32_t rl_cand_dist(unsigned long long c) { return (int32_t)(c >> 32); }
+RL_FN int32_t rl_cand_id(unsigned long long c) { return (int32_t)((c >> 8) & 0xffffffu); }
+RL_FN int32_t rl_cand_shift(unsigned long long c) { return (int32_t)(c & 0xffu); }
+// candidate r of a query's row of words -> ids[r], dists[r], shifts[r]; false, and nothing written, when the query has no such candidate
+RL_FN bool rl_cand_unpack(const unsigned long long* cand, int r, int32_t* ids, int32_t* dists, int32_t* shifts) {
+  if (cand[r] == RL_CAND_NONE) return false;
+  ids[r] = rl_cand_id(cand[r]); dists[r] = rl_cand_dist(cand[r]); shifts[r] = rl_cand_shift(cand[r]);
+  return true;
+}
+
+// the attempt window: frames closest - search_num .. closest + search_num within 0 .. last (the last admissible frame; -1: none, and *jhi < *jlo)
+RL_FN void lc_window(int closest, int search_num, int last, int* jlo, int* jhi) {
+  *jlo = closest - search_num > 0 ? closest - search_num : 0;
+  *jhi = closest + search_num < last ? closest + search_num : last;
+}
 
 #endif

@@ -4,6 +4,7 @@
 // Names say what a function returns:
 //   wave_incl_scan / wave_excl_scan  per-lane prefix sums over the wavefront
 //   block_excl_scan<NW>              per-thread prefix sum over a workgroup of NW wavefronts
+//   block_min_u64<NW>                the smallest u64 key of a workgroup of NW wavefronts, in every thread
 //   bfly_*                           butterfly (__shfl_xor, offsets W/2 -> 1): the result in every lane of each group of W lanes
 //   group_*<G>                       DPP inside groups of G consecutive lanes: the result in every lane of the group
 //   wave_{min,max,sum}_*             DPP over the wavefront: a uniform value
@@ -69,6 +70,21 @@ template <int W = 64>
 __device__ __forceinline__ unsigned long long bfly_min_u64(unsigned long long v) {
 #pragma unroll
   for (int o = W / 2; o > 0; o >>= 1) v = min(v, (unsigned long long)__shfl_xor(v, o, 64));
+  return v;
+}
+// The smallest of one u64 key per thread over a workgroup of NW wavefronts, in every thread (an arg-min when the key ends in an index;
+// a minimum of integers does not depend on the order).  s_min: NW words of LDS.  Barriers: one on entry (the previous call's readers
+// of s_min are done), one after the wave minima are written.  None on return: s_min is read until the caller's next barrier, so a
+// loop of calls (rounds of "smallest key above the last one") needs nothing else.
+template <int NW>
+__device__ __forceinline__ unsigned long long block_min_u64(unsigned long long v, unsigned long long* s_min) {
+  v = bfly_min_u64(v);
+  __syncthreads();
+  if (lane_id() == 0) s_min[threadIdx.x >> 6] = v;
+  __syncthreads();
+  v = s_min[0];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) v = min(v, s_min[w]);
   return v;
 }
 // one axis of a bounding box: fminf / fmaxf, min and max interleaved

@@ -95,6 +95,35 @@ def test_front_end_arrays_have_one_layout():
     assert not bad, "\n".join(bad)
 
 
+def test_icp_attempts_have_one_definition():
+    """What an ICP attempt of alego_loop_search, the appearance search and relocalisation is made of is defined once: a frame's clouds in kf_store.h
+    (KfClouds), the archive gather, the window, the rounds and the result in loop_ctx.h / kernels_loop.hip, the candidate word in reloc_math.h, the
+    workgroup arg-min in wave.h, "get from a pool or set the error" in dev_mem.h.  The copies these replaced are named nowhere under csrc/, and no
+    code outside reloc_math.h takes a candidate word apart or puts one together by hand."""
+    csrc = os.path.join(ROOT, "a-lego-loam_amd", "csrc")
+    text = {f: open(os.path.join(csrc, f), errors="ignore").read() for f in sorted(os.listdir(csrc))}
+    assert {"kernels_reloc.hip", "kernels_loop.hip", "reloc_math.h", "kf_store.h", "loop_ctx.h", "wave.h", "dev_mem.h"} <= set(text)
+    for f, txt in text.items():
+        for gone in ("la_gather", "rl_alloc", "lc_alloc", "rl_block_min"):
+            assert gone not in txt, f"{f} names {gone}"
+    assert "LI_NCUR_" not in text["kernels_reloc.hip"], "the current scan's clouds are read through kf_clouds_cur"
+    bad = []
+    for f, txt in text.items():
+        if f == "reloc_math.h":
+            continue
+        code = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", lambda m: "\n" * m.group(0).count("\n"), txt, flags=re.S))
+        for no, line in enumerate(code.split("\n"), 1):
+            by8 = re.search(r"(>>|<<)\s*8\b", line)
+            if ("0xffffffu" in line.lower() and by8) or (re.search(r"<<\s*32\b", line) and by8):   # id = (c >> 8) & 0xffffff; D << 32 | id << 8 | s
+                bad.append(f"{f}:{no}: {line.strip()[:120]}")
+    assert not bad, "\n".join(bad)
+    kernels = re.findall(r"__global__\s+void\s+(?:__launch_bounds__\([^)]*\)\s+)?(\w+)\s*\(", text["kernels_reloc.hip"])
+    assert len(kernels) >= 10 and [k for k in kernels if k.endswith("_gather")] == ["rl_gather"], kernels
+    for name, where in (("KfClouds", "kf_store.h"), ("lc_window", "reloc_math.h"), ("rl_cand_pack", "reloc_math.h"), ("block_min_u64", "wave.h"), ("DevGet", "dev_mem.h"),
+                        ("loop_rounds", "loop_ctx.h"), ("loop_archive_gather", "loop_ctx.h"), ("loop_result_fill", "loop_ctx.h")):
+        assert name in text[where], f"{where} defines {name}"
+
+
 def test_cpp_example_fails_loudly_without_a_gpu():
     """examples/replay.cpp drives the C ABI from plain C++.  In a container without an MI355X it must stop at alego_create with
     ALEGO_ERR_NO_DEVICE — there is no CPU fallback for the product path (on the GPU box tests/test_gpu_parity.py runs it for real)."""

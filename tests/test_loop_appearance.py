@@ -446,6 +446,95 @@ def test_search_is_the_brute_force_over_the_eligible_frames(search_handle):
                 assert_bit_equal(np.asarray(res[s][k]), np.asarray(whole[s][k]), f"{refs[s]['name']} ({tag}): {k}")
 
 
+ROUND_FRAMES = 8
+
+
+def round_slots():
+    """per slot: (the (corner, surf, outlier) of 8 frames, key poses (8, 6), the frame built to be the best candidate or None).  A few hundred points per
+    frame, one per non-zero bin of a random descriptor.  Slot 0: frames without a corner cloud (1, 5 and the newest, 7) and without an outlier cloud
+    (2, 5).  Slots 1 and 2: the newest frame's descriptor is frame 0's / frame 6's turned by 11 sectors with one bin in twenty redrawn."""
+    rng = np.random.default_rng(23)
+    kp = lambda: np.c_[rng.uniform(-30, 30, (ROUND_FRAMES, 3)), rng.uniform(-0.05, 0.05, (ROUND_FRAMES, 2)), rng.uniform(-3, 3, (ROUND_FRAMES, 1))].astype(F32)
+    frames = []
+    for f, a in enumerate(cloud_of(D) for D in _sparse(rng, ROUND_FRAMES)):
+        if f == 5:
+            frames.append((EMPTY, a, EMPTY))
+        elif f in (1, 7):
+            frames.append((EMPTY, a[0::2], a[1::2]))
+        elif f == 2:
+            frames.append((a[0::2], a[1::2], EMPTY))
+        else:
+            frames.append(split3(a))
+    out = [(frames, kp(), None)]
+    for best in (0, ROUND_FRAMES - 2):
+        D = _sparse(rng, ROUND_FRAMES)
+        q = np.roll(D[best], 11, axis=0)
+        redraw = rng.random(q.shape) < 0.05
+        q[redraw] = rng.integers(1, 256, int(redraw.sum()))
+        D[ROUND_FRAMES - 1] = q
+        out.append(([split3(cloud_of(x)) for x in D], kp(), best))
+    return out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("search_num", [None, 0])
+def test_every_round_is_the_attempt_on_its_candidate(search_num):
+    """fitness_max = 1e-12 rejects every attempt, so verify = 4 runs all four rounds and the result left behind is round 3's: the guess is candidate 3's and
+    the ICP numbers are those of alego_loop_closure_icp on the same frames (the archive's, the newest under guess6) — for frames with an empty corner or
+    outlier cloud, for windows clipped at frame 0 and at frame nf - 2, with the default lc_search_num and with 0.  verify = 1: the same for candidate 0."""
+    p = _params(False) if search_num is None else _params(False, lc_search_num=search_num)
+    sn, nf = p.lc_search_num, ROUND_FRAMES
+    assert sn == (25 if search_num is None else 0)
+    slots = round_slots()
+    stamps = np.arange(nf) * 100.0   # every older frame is eligible
+    # the CPU side: numpy alone yields four candidates for every slot, and the shapes are what the docstring of round_slots says
+    want = []
+    for s, (fr, kp, best) in enumerate(slots):
+        desc = np.array([desc_np(np.concatenate(f), MAX_RANGE, Z_OFFSET)[0] for f in fr])
+        ids, dists, shifts, nel = candidates_np(desc, kp, stamps, p.lc_min_time_gap, n_cand=N_CAND)
+        assert nel == nf - 1 and len(ids) == N_CAND == 4, (s, ids, nel)
+        assert best is None or ids[0] == best, (s, ids, dists)
+        assert min(sum(len(c) for c in f) for f in fr) >= 200, s
+        want.append((ids, dists, shifts))
+    n_of = lambda k: [len(f[k]) for f in slots[0][0]]
+    assert [i for i, n in enumerate(n_of(0)) if n == 0] == [1, 5, 7] and [i for i, n in enumerate(n_of(2)) if n == 0] == [2, 5] and min(n_of(1)) > 0
+    assert (slots[1][2], slots[2][2]) == (0, nf - 2)
+    h = binding.Handle(p, n_slots=3)
+    h.map_enable(16, 1 << 14)
+    h.loop_appearance_enable(MAX_RANGE, Z_OFFSET)
+    for s, (fr, kp, _) in enumerate(slots):
+        for f in range(nf):
+            h.lm_add_keyframe(kp[f], *fr[f], slot=s)
+        assert h.map_status(s)[:2] == (nf, 0), s
+        h.map_set_stamps(0, stamps, slot=s)
+    arch = [[h.map_get_keyframe(j, slot=s) for j in range(nf)] for s in range(3)]
+    for verify, k in ((4, 3), (1, 0)):
+        res = h.loop_search_appearance([0, 1, 2], n_cand=4, verify=verify, fitness_max=1e-12)
+        assert len(res) == 3
+        for s, r in enumerate(res):
+            tag = f"lc_search_num {sn}, verify {verify}, slot {s}"
+            for g, w, what in zip((r["cand_id"], r["cand_dist"], r["cand_shift"]), want[s], ("ids", "dists", "shifts")):
+                assert np.array_equal(g, w), (tag, what, g, w)
+            assert (r["n_cand"], r["verified"], r["status"], r["latest_id"]) == (4, -1, 1, nf - 1), (tag, r)
+            c = int(r["cand_id"][k])
+            assert r["closest_id"] == c, (tag, r["closest_id"], r["cand_id"])
+            assert_bit_equal(r["guess6"], guess_of(slots[s][1], c, int(r["cand_shift"][k])), f"{tag}: guess6")
+            lo, hi = max(0, c - sn), min(nf - 2, c + sn)
+            a = arch[s]
+            assert_bit_equal(a[c]["pose"], slots[s][1][c], f"{tag}: the archived pose")
+            frames = [(r["guess6"], a[nf - 1]["corner"], a[nf - 1]["surf"], a[nf - 1]["outlier"])] + [(a[j]["pose"], a[j]["corner"], a[j]["surf"], a[j]["outlier"]) for j in range(lo, hi + 1)]
+            one, _ = h.loop_closure_icp(frames)
+            print(f"{tag}: candidate {c} window [{lo}, {hi}]; search: n_source {r['n_source']} n_target {r['n_target']} converged {r['converged']} iterations {r['iterations']} "
+                  f"fitness {r['fitness']:.9g}; single attempt: {one['n_source']} {one['n_target']} {one['converged']} {one['iterations']} {one['fitness']:.9g}; "
+                  f"|icp_final - T| {np.abs(r['icp_final'] - one['T']).max():.3g}")
+            assert r["n_source"] == sum(len(x) for x in slots[s][0][nf - 1]) and r["n_target"] > 0, (tag, r)
+            assert (one["n_source"], one["n_target"], one["converged"]) == (r["n_source"], r["n_target"], r["converged"]), (tag, one, r)
+            assert abs(one["iterations"] - r["iterations"]) <= 1, (tag, one, r)
+            assert np.abs(r["icp_final"] - one["T"]).max() < 1e-5, (tag, r["icp_final"], one["T"])
+            assert abs(one["fitness"] - r["fitness"]) < 1e-6 * max(1.0, r["fitness"]), (tag, one["fitness"], r["fitness"])
+    h.close()
+
+
 def moved_lap_handle(p, starts, steps):
     """replay_handle with the appearance search on and every slot's frames above 30 moved by the ramp; returns (handle, unmoved key poses per slot)"""
     h = replay_handle(p, starts, steps)
