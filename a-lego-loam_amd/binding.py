@@ -37,6 +37,7 @@ EXPORTS = [
     "alego_loc_select", "alego_loc_enable", "alego_loc_status",
     "alego_reloc_enable", "alego_loc_relocalize", "alego_reloc_descriptor", "alego_reloc_match", "alego_debug_reloc_search",
     "alego_loop_appearance_enable", "alego_loop_search_appearance", "alego_loop_appearance_candidates",
+    "alego_map_align", "alego_map_align_queries", "alego_map_align_consensus", "alego_map_align_poses",
 ]
 
 REPLAY_PINGPONG = 0x100
@@ -45,6 +46,8 @@ MAP_SURF, MAP_CORNER, MAP_OUTLIER, MAP_FRAME_ID = 1, 2, 4, 8
 ERR_CAPACITY, ERR_ARG = -3, -4
 RELOC_MAX_CAND = 8
 RELOC_SECTORS, RELOC_RINGS = 60, 20
+ALIGN_MAX_QUERIES = 32
+ALIGN_TOL_TRANS, ALIGN_TOL_ROT = 0.24, 0.0165   # ALEGO_ALIGN_TOL_TRANS, ALEGO_ALIGN_TOL_ROT
 FLAG_LO_INIT, FLAG_FEW_SURF, FLAG_FEW_CORNER, FLAG_LM_SKIPPED, FLAG_LM_FEW_FEATURES, FLAG_LM_KEYFRAME = 1, 2, 4, 8, 16, 32
 
 
@@ -134,6 +137,21 @@ class LoopAppOpts(C.Structure):
 class LoopAppInfo(C.Structure):
     _fields_ = [("n_eligible", C.c_int32), ("n_cand", C.c_int32), ("cand_id", C.c_int32 * 8), ("cand_dist", C.c_int32 * 8), ("cand_shift", C.c_int32 * 8),
                 ("verified", C.c_int32), ("guess6", C.c_float * 6), ("icp_final", C.c_float * 16)]
+
+
+class MapAlignOpts(C.Structure):
+    _fields_ = [("n_queries", C.c_int32), ("n_cand", C.c_int32), ("max_dist", C.c_int32), ("min_support", C.c_int32), ("fitness_max", C.c_double),
+                ("tol_trans", C.c_double), ("tol_rot", C.c_double)]
+
+
+class MapAlignHyp(C.Structure):
+    _fields_ = [("src_frame", C.c_int32), ("dst_frame", C.c_int32), ("dist", C.c_int32), ("shift", C.c_int32), ("tried", C.c_int32), ("accepted", C.c_int32),
+                ("converged", C.c_int32), ("iterations", C.c_int32), ("n_source", C.c_int32), ("n_target", C.c_int32), ("support", C.c_int32), ("inlier", C.c_int32),
+                ("fitness", C.c_double), ("guess6", C.c_float * 6), ("icp_final", C.c_float * 16), ("T", C.c_float * 16)]
+
+
+class MapAlignResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_queries", C.c_int32), ("n_accepted", C.c_int32), ("best", C.c_int32), ("support", C.c_int32), ("T", C.c_double * 12)]
 
 
 class GraphEdge(C.Structure):
@@ -360,6 +378,10 @@ def lib():
         L.alego_loop_search_appearance.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(LoopAppOpts), C.POINTER(LoopResult), C.POINTER(LoopAppInfo)]
         L.alego_loop_appearance_candidates.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32,
                                                        C.c_void_p, C.c_void_p, C.c_void_p]
+        L.alego_map_align.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(MapAlignOpts), C.POINTER(MapAlignResult), C.POINTER(MapAlignHyp)]
+        L.alego_map_align_queries.argtypes = [C.c_int32, C.c_int32, C.c_void_p]
+        L.alego_map_align_consensus.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.POINTER(C.c_int32)]
+        L.alego_map_align_poses.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
         L.alego_write_pcd.argtypes = [C.c_char_p, C.c_void_p, C.c_int32]
         L.alego_bag_read_pc2.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
         if L.alego_params_sizeof() != C.sizeof(AlegoParams):
@@ -451,6 +473,41 @@ def loop_appearance_candidates(desc, keyposes6, stamps, min_time_gap, max_jump=0
     if k < 0:
         raise AlegoError(f"alego_loop_appearance_candidates failed ({k})")
     return ids[:k].copy(), dists[:k].copy(), shifts[:k].copy()
+
+
+def map_align_queries(n_frames, n_queries=0):
+    """alego_map_align_queries: the source frames alego_map_align queries in an archive of n_frames (host code of the library)"""
+    fr = np.zeros(ALIGN_MAX_QUERIES, np.int32)
+    q = lib().alego_map_align_queries(int(n_frames), int(n_queries), fr.ctypes.data)
+    if q < 0:
+        raise AlegoError(f"alego_map_align_queries failed ({q})")
+    return fr[:q].copy()
+
+
+def map_align_consensus(T, src_pos, fitness, accepted, tol_trans=0.0, tol_rot=0.0):
+    """alego_map_align_consensus: (support (n,), best) of n hypotheses T (n, 4, 4) with query positions src_pos (n, 3) (host code of the library)"""
+    T = np.ascontiguousarray(T, np.float32).reshape(-1, 16)
+    p = np.ascontiguousarray(src_pos, np.float32).reshape(-1, 3)
+    f = np.ascontiguousarray(fitness, np.float64).reshape(-1)
+    a = np.ascontiguousarray(accepted, np.int32).reshape(-1)
+    n = T.shape[0]
+    assert p.shape[0] == f.shape[0] == a.shape[0] == n
+    sup, best = np.zeros(max(n, 1), np.int32), C.c_int32(-2)
+    rc = lib().alego_map_align_consensus(T.ctypes.data, p.ctypes.data, f.ctypes.data, a.ctypes.data, n, float(tol_trans), float(tol_rot), sup.ctypes.data, C.byref(best))
+    if rc != 0:
+        raise AlegoError(f"alego_map_align_consensus failed ({rc})")
+    return sup[:n].copy(), int(best.value)
+
+
+def map_align_poses(T, poses6):
+    """alego_map_align_poses: the key poses (n, 6) moved by T (3 x 4 or 4 x 4, f64) (host code of the library)"""
+    T12 = np.ascontiguousarray(np.asarray(T, np.float64).reshape(-1)[:12])
+    kp = np.ascontiguousarray(poses6, np.float32).reshape(-1, 6)
+    out = np.zeros_like(kp)
+    rc = lib().alego_map_align_poses(T12.ctypes.data, kp.ctypes.data, kp.shape[0], out.ctypes.data)
+    if rc != 0:
+        raise AlegoError(f"alego_map_align_poses failed ({rc})")
+    return out
 
 
 def _reloc_result(r):
@@ -932,6 +989,34 @@ class Handle:
             d.update(n_eligible=int(f.n_eligible), n_cand=k, cand_id=np.array(f.cand_id[:k], np.int32), cand_dist=np.array(f.cand_dist[:k], np.int32),
                      cand_shift=np.array(f.cand_shift[:k], np.int32), verified=int(f.verified), guess6=np.array(f.guess6[:], np.float32),
                      icp_final=np.array(f.icp_final[:], np.float32).reshape(4, 4))
+            res.append(d)
+        return res
+
+    # ---- one slot's archive aligned to another's (needs loop_appearance_enable) ----
+    def map_align(self, pairs, n_queries=0, n_cand=0, max_dist=0, min_support=0, fitness_max=0.0, tol_trans=0.0, tol_rot=0.0, hyps=True):
+        """alego_map_align: one dict per pair (src, dst) — status, n_queries, n_accepted, best, support, T (3, 4) f64 and, with hyps, `hyp`: one dict per
+        query (src_frame, dst_frame, dist, shift, tried, accepted, converged, iterations, n_source, n_target, support, inlier, fitness, guess6, icp_final, T)"""
+        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        src, dst = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
+        n = pr.shape[0]
+        out = (MapAlignResult * max(n, 1))()
+        hyp = (MapAlignHyp * (max(n, 1) * ALIGN_MAX_QUERIES))() if hyps else None
+        opts = MapAlignOpts(int(n_queries), int(n_cand), int(max_dist), int(min_support), float(fitness_max), float(tol_trans), float(tol_rot))
+        self._check(lib().alego_map_align(self._h, src.ctypes.data, dst.ctypes.data, n, C.byref(opts), out, hyp), "alego_map_align")
+        res = []
+        for i in range(n):
+            r = out[i]
+            d = dict(status=int(r.status), n_queries=int(r.n_queries), n_accepted=int(r.n_accepted), best=int(r.best), support=int(r.support),
+                     T=np.array(r.T[:], np.float64).reshape(3, 4))
+            if hyps:
+                d["hyp"] = []
+                for q in range(int(r.n_queries)):
+                    x = hyp[i * ALIGN_MAX_QUERIES + q]
+                    d["hyp"].append(dict(src_frame=int(x.src_frame), dst_frame=int(x.dst_frame), dist=int(x.dist), shift=int(x.shift), tried=int(x.tried),
+                                         accepted=int(x.accepted), converged=int(x.converged), iterations=int(x.iterations), n_source=int(x.n_source),
+                                         n_target=int(x.n_target), support=int(x.support), inlier=int(x.inlier), fitness=float(x.fitness),
+                                         guess6=np.array(x.guess6[:], np.float32), icp_final=np.array(x.icp_final[:], np.float32).reshape(4, 4),
+                                         T=np.array(x.T[:], np.float32).reshape(4, 4)))
             res.append(d)
         return res
 

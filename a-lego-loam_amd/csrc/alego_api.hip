@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <cstring>
 #include <mutex>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -1324,6 +1325,31 @@ int alego_loop_search_appearance(alego_handle* h, const int32_t* slots, int32_t 
   g_prof = &h->prof;
   HIP_TRY(h, sync_all(h));   // behind everything already queued on every stream group
   return loop_app_run(h->rl, &h->lc, *lm_host_ctx(h->lm), h->P, slots, n, o, out, info, h->stream, &h->err);
+}
+
+// ---- aligning one slot's archive to another's (kernels_reloc.hip) ----
+int alego_map_align(alego_handle* h, const int32_t* src_slots, const int32_t* dst_slots, int32_t n, const alego_map_align_opts* opts, alego_map_align_result* out,
+                    alego_map_align_hyp* hyp) {
+  if (!h || n < 0 || (n > 0 && (!src_slots || !dst_slots || !out))) return ALEGO_ERR_ARG;
+  if (int r = not_localising(h, "alego_map_align")) return r;
+  if (!loop_app_enabled(h->rl)) { h->err = "alego_map_align: the appearance search is off (alego_map_enable, then alego_loop_appearance_enable)"; return ALEGO_ERR_ARG; }
+  alego_map_align_opts o;
+  std::memset(&o, 0, sizeof(o));
+  if (opts) o = *opts;
+  if (o.n_queries <= 0) o.n_queries = 8;
+  if (o.n_cand <= 0) o.n_cand = 2;
+  if (o.n_queries > ALEGO_ALIGN_MAX_QUERIES || o.n_cand > ALEGO_RELOC_MAX_CAND) { h->err = "alego_map_align: n_queries is 1 .. ALEGO_ALIGN_MAX_QUERIES, n_cand 1 .. ALEGO_RELOC_MAX_CAND"; return ALEGO_ERR_ARG; }
+  std::set<std::pair<int, int>> seen;
+  for (int i = 0; i < n; ++i) {
+    const int a = src_slots[i], b = dst_slots[i];
+    if (a < 0 || a >= h->d.n_slots || b < 0 || b >= h->d.n_slots) { h->err = "alego_map_align: slot out of range"; return ALEGO_ERR_ARG; }
+    if (a == b) { h->err = "alego_map_align: slot " + std::to_string(a) + " is paired with itself"; return ALEGO_ERR_ARG; }
+    if (!seen.insert({a, b}).second) { h->err = "alego_map_align: the pair (" + std::to_string(a) + ", " + std::to_string(b) + ") is listed twice"; return ALEGO_ERR_ARG; }
+  }
+  hipSetDevice(h->device);
+  g_prof = &h->prof;
+  HIP_TRY(h, sync_all(h));   // behind everything already queued on every stream group
+  return map_align_run(h->rl, &h->lc, *lm_host_ctx(h->lm), h->P, src_slots, dst_slots, n, o, out, hyp, h->stream, &h->err);
 }
 
 int alego_loc_status(alego_handle* h, int slot, int32_t out[4]) {

@@ -85,7 +85,8 @@ __global__ void __launch_bounds__(LC_DT) lc_detect(LmCtx L, const int* list, ale
 }
 
 // ---- sub-map --------------------------------------------------------------------------------------------------------------------
-// grid (1 + frames, jobs): x = 0 the source — archived frame det.latest under det.pose_latest; x = 1 + k the history frame jlo + k under its key pose
+// grid (1 + frames, jobs): x = 0 the source — archived frame det.latest of the source's slot (lc_src_slot: the job's own unless the attempt
+// names another) under det.pose_latest; x = 1 + k the history frame jlo + k of the job's slot under its key pose
 __global__ void __launch_bounds__(LC_DT) lc_gather(LmCtx L, const LcJob* jobs, const LcDet* det, float4* src, float4* raw) {
   const LcJob J = jobs[blockIdx.y];
   const LcDet& D = det[J.li];
@@ -93,7 +94,7 @@ __global__ void __launch_bounds__(LC_DT) lc_gather(LmCtx L, const LcJob* jobs, c
   const int f = source ? D.latest : D.jlo + (int)blockIdx.x - 1;
   if (!source && f > D.jhi) return;
   float4* out = source ? src + J.src_off : lc_frame_out(raw, J, D, f, [&](int j) { return arc_tab_points(arc_tab_of(L, J.slot, j)); });
-  const KfArcFrame A = kf_arc_frame(L, J.slot, f);
+  const KfArcFrame A = kf_arc_frame(L, source ? lc_src_slot(D, J.slot) : J.slot, f);
   float m[3][4];
   keypose_matrix(source ? D.pose_latest : A.pose, m);
   kf_clouds_write<LC_DT>(kf_clouds(A), m, out);
@@ -528,10 +529,16 @@ int loop_search(LcCtx** pc, const LmCtx& L, const alego_params& P, int n_slots, 
 int loop_attempts(LcCtx** pc, const alego_params& P, int n_slots, const int* slots, const LcDet* det, int n, const LcGather& gather, LcOut* out, hipStream_t st, std::string* err) {
   if (!*pc) *pc = new LcCtx();
   LcCtx* C = *pc;
-  if (n > n_slots) { *err = "loop attempts: more entries than slots"; return ALEGO_ERR_ARG; }
   if (int rc = lc_reserve(C, n_slots, 0, err)) return rc;
-  if (n > 0 && hipMemcpyAsync(C->det, det, (size_t)n * sizeof(LcDet), hipMemcpyHostToDevice, st) != hipSuccess) { *err = "loop attempts: upload failed"; return ALEGO_ERR_HIP; }
-  return lc_attempts(C, P, slots, det, n, gather, out, st, err);
+  if (n <= 0) return lc_attempts(C, P, slots, det, 0, gather, out, st, err);
+  // pieces of list_cap entries (>= n_slots: the list arrays only grow): every list array and scratch region is keyed by entry or job, none by slot, so
+  // entries may repeat a slot
+  for (int i0 = 0; i0 < n; i0 += C->list_cap) {
+    const int c = std::min(C->list_cap, n - i0);
+    if (hipMemcpyAsync(C->det, det + i0, (size_t)c * sizeof(LcDet), hipMemcpyHostToDevice, st) != hipSuccess) { *err = "loop attempts: upload failed"; return ALEGO_ERR_HIP; }
+    if (int rc = lc_attempts(C, P, slots + i0, det + i0, c, gather, out + i0, st, err)) return rc;
+  }
+  return 0;
 }
 
 int loop_rounds(LcCtx** pc, const alego_params& P, int n_slots, const int* slots, int n, int rounds, const LcGather& gather, const LcPlan& plan, const LcVerdict& verdict, hipStream_t st,

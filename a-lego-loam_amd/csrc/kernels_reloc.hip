@@ -19,6 +19,10 @@
 //                (raw sub-map), from the map store through kf_store.h's views; the rounds (loop_rounds), VoxelGrid, lc_grid and lc_icp are
 //                kernels_loop.hip's (loop_ctx.h)
 //   rl_apply     one lane per accepted slot: map -> odom corrected as lm_apply_correction does, params_ replaced
+//   ma_mask      (alego_map_align) one thread per (query, frame): B <- RL_INELIGIBLE for every frame of a query whose ring key is all zero
+//   ma_plan      (alego_map_align) one thread per (pair, query, candidate): the LcDet of the attempt from both archives' tables and the source key pose
+//   ma_consensus (alego_map_align) one wavefront per pair, one lane per hypothesis: align_math.h's agreement, support, best and inliers with
+//                wave.h's reductions; no LDS, no atomics
 // Phase boundaries are kernel boundaries; no workgroup waits for another.
 //
 // Every query of the search kernels has a record (RlQuery): its row of the query descriptors, the first row and the number of the map
@@ -42,17 +46,30 @@
 //                fitness <= fitness_max
 //   result       an alego_loop_result: t_correct / between = alego_loop_constraint(icp_final, guess6, key pose i); correction = the WORLD
 //                correction t_correct * matrix(key pose nf - 1)^-1 (f64 rigid inverse and product, rounded to f32)
+//
+// alego_map_align asks the same descriptors which rigid transform takes one slot's archive into the frame of another's.
+// The rule is the project's own, for a pair (src, dst) with ns and nd archived frames and none dropped:
+//   queries      Q = min(n_queries, ns) source frames, query q = frame ((2 q + 1) ns) / (2 Q) (align_math.h)
+//   search       every query over ALL nd destination frames (qrow in the source slot's rows, base / n the destination's): no eligibility but
+//                "a query whose ring key is all zero has no candidate" (ma_mask); the n_cand smallest in (D, id), cut at max_dist > 0
+//   verify       per query, candidate v in round v, the first accepted ends the query (loop_rounds over (pair, query) entries): ma_plan plans
+//                every attempt on the device, source = source frame f under guess6 = destination key pose i with yaw rl_guess_yaw(yaw_i, s_i)
+//                (LcDet.src1 names the source's slot; lc_gather reads it), target = destination frames lc_window(i, lc_search_num, nd - 1)
+//   hypothesis   T = t_correct * matrix(source key pose f)^-1 (la_world_correction, as the appearance search's world correction)
+//   consensus    ma_consensus: one wavefront per pair, one lane per hypothesis; agreement, support and the best one are align_math.h's
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
 
 #include "../../include/alego_mi355x.h"
+#include "align_math.h"
 #include "dev_common.h"
 #include "dev_cost.h"
 #include "dev_mem.h"
 #include "kf_store.h"
 #include "loop_ctx.h"
+#include "pg_math.h"
 #include "prof.h"
 #include "reloc.h"
 #include "reloc_math.h"
@@ -150,6 +167,14 @@ __global__ void __launch_bounds__(RL_T) rl_bound(const RlQuery* qr, const uint16
   bound[(size_t)Q.off + i] = rl_key_bound(qkey + (size_t)Q.qrow * RL_NR, mkey + ((size_t)Q.base + i) * RL_NR);
 }
 
+// does a ring key hold anything?  (every code is >= 1: an all-zero key is a frame with no point in range)
+DEV_INLINE bool rl_key_any(const uint16_t* k) {
+  int any = 0;
+#pragma unroll
+  for (int r = 0; r < RL_NR; ++r) any |= k[r];
+  return any != 0;
+}
+
 // Eligibility of the appearance search (the header comment's rule); grid as rl_bound.  Query q is the newest archived frame Q.n of slot
 // Q.tag, frame i < Q.n a frame of the same slot.  A query whose ring key is all zero (no point in range: every code is >= 1) has no
 // eligible frame.  nelig[q] += the eligible frames (a sum of integers does not depend on the order; zeroed by the host).
@@ -158,12 +183,8 @@ __global__ void __launch_bounds__(RL_T) la_elig(LmCtx L, const RlQuery* qr, cons
   const int i = blockIdx.x * RL_T + threadIdx.x;
   bool el = false;
   if (i < Q.n) {
-    const uint16_t* kq = key + (size_t)Q.qrow * RL_NR;
-    int any = 0;
-#pragma unroll
-    for (int r = 0; r < RL_NR; ++r) any |= kq[r];
     const size_t fb = arc_row(L, Q.tag, 0);
-    el = any != 0 && L.arc_stamp[fb + Q.n] - L.arc_stamp[fb + i] > min_time_gap;   // lc_detect's comparison (:782)
+    el = rl_key_any(key + (size_t)Q.qrow * RL_NR) && L.arc_stamp[fb + Q.n] - L.arc_stamp[fb + i] > min_time_gap;   // lc_detect's comparison (:782)
     if (jump2 >= 0.f) {
       const float *a = arc_pose_of(L, Q.tag, i), *b = arc_pose_of(L, Q.tag, Q.n);
       const float dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2];
@@ -307,6 +328,71 @@ __global__ void __launch_bounds__(64) la_plan(LmCtx L, const int* list, const un
   det[idx] = D;
 }
 
+// ---- alego_map_align: mask, planning, consensus -----------------------------------------------------------------------------------------------
+struct MaEntry { int src, dst, frame, pair; };                              // one (pair, query): source frame `frame` of slot src searched in slot dst
+struct MaHyp { float T[16], p[3]; int accepted; double fitness; };         // a hypothesis as ma_consensus reads it
+struct MaCons { int support[MA_MAX_QUERIES], inlier[MA_MAX_QUERIES], best, pad; };   // its verdict on one pair
+
+// grid as rl_bound: a query with an all-zero ring key has no candidate
+__global__ void __launch_bounds__(RL_T) ma_mask(const RlQuery* qr, const uint16_t* key, uint32_t* bound) {
+  const RlQuery Q = qr[blockIdx.y];
+  const int i = blockIdx.x * RL_T + threadIdx.x;
+  if (i < Q.n && !rl_key_any(key + (size_t)Q.qrow * RL_NR)) bound[(size_t)Q.off + i] = RL_INELIGIBLE;
+}
+
+// one thread per (entry e, candidate k): det[e * ALEGO_RELOC_MAX_CAND + k] = the attempt on candidate k as loop_attempts takes it (status 0: no such
+// candidate) from both archives' tables, spose[e] = the source key pose of the entry
+__global__ void __launch_bounds__(64) ma_plan(LmCtx L, const MaEntry* ent, const unsigned long long* cand, int n, int search_num, LcDet* det, float* spose) {
+  const int idx = blockIdx.x * 64 + threadIdx.x, e = idx / ALEGO_RELOC_MAX_CAND, k = idx % ALEGO_RELOC_MAX_CAND;
+  if (e >= n) return;
+  const MaEntry E = ent[e];
+  if (k == 0)
+    for (int j = 0; j < 6; ++j) spose[e * 6 + j] = arc_pose_of(L, E.src, E.frame)[j];
+  LcDet D;
+  memset(&D, 0, sizeof(D));
+  const unsigned long long c = cand[idx];
+  if (c != RL_CAND_NONE) {
+    const int nd = arc_stat_of(L, E.dst)[AS_FRAMES];
+    D.status = 1; D.latest = E.frame; D.closest = rl_cand_id(c); D.src1 = E.src + 1;
+    lc_window(D.closest, search_num, nd - 1, &D.jlo, &D.jhi);   // every destination frame is admissible
+    for (int j = 0; j < 6; ++j) D.pose_latest[j] = D.pose_closest[j] = arc_pose_of(L, E.dst, D.closest)[j];
+    D.pose_latest[5] = rl_guess_yaw(D.pose_latest[5], rl_cand_shift(c));
+    lc_det_sizes(L, E.dst, E.frame, &D);
+  }
+  det[idx] = D;
+}
+
+// grid (pairs), one wavefront each, lane b = hypothesis b of the pair (nq[pair] <= 32 of them).  Hypothesis a is wave-uniform (scalar loads) in
+// round a: lane b tests AGREE(a, b), the wavefront's sum is support(a).  Then the arg-best in three uniform steps (align_math.h's order) and the
+// inliers: one more test per lane.  No LDS, no atomics.
+__global__ void __launch_bounds__(64) ma_consensus(const MaHyp* hyp, const int* nq, double tol_trans, double tol_rot, MaCons* out) {
+  const int lane = lane_id(), n = nq[blockIdx.x];
+  const MaHyp* H = hyp + (size_t)blockIdx.x * MA_MAX_QUERIES;
+  MaHyp B;
+  memset(&B, 0, sizeof(B));
+  if (lane < n) B = H[lane];
+  const bool mine = lane < n && B.accepted != 0;
+  int support = 0;
+  for (int a = 0; a < n; ++a) {
+    const int ag = (H[a].accepted && mine && ma_agree(H[a].T, H[a].p, B.T, B.p, tol_trans, tol_rot)) ? 1 : 0;
+    const int s = wave_sum_i32(ag);
+    if (lane == a) support = s;
+  }
+  const bool in = mine && support >= 1;
+  const uint32_t smax = wave_max_u32(in ? (uint32_t)support : 0u);
+  const bool top = in && (uint32_t)support == smax;
+  const unsigned long long key = ma_fit_key(B.fitness);
+  const unsigned long long kmin = wave_min_u64(top ? key : ~0ull);
+  const uint32_t bl = wave_min_u32(top && key == kmin ? (uint32_t)lane : 0xFFFFFFFFu);
+  const int best = smax == 0u ? -1 : (int)bl;
+  MaCons* O = out + blockIdx.x;
+  if (lane < MA_MAX_QUERIES) {
+    O->support[lane] = support;
+    O->inlier[lane] = (best >= 0 && mine && ma_agree(H[best].T, H[best].p, B.T, B.p, tol_trans, tol_rot)) ? 1 : 0;
+  }
+  if (lane == 0) { O->best = best; O->pad = 0; }
+}
+
 struct RlApply { int slot, pad; double rc[12], params6[6]; };
 // one lane per accepted slot: correctPoses :579-580 on map -> odom exactly as lm_apply_correction computes it, then params_
 __global__ void __launch_bounds__(64) rl_apply(LmCtx L, const RlApply* a, int n) {
@@ -349,6 +435,14 @@ struct RlCtx {
   unsigned long long* la_cand = nullptr;   // [la_slots][ALEGO_RELOC_MAX_CAND] their candidates
   LcDet* la_det = nullptr;              // [la_slots][ALEGO_RELOC_MAX_CAND] the attempts la_plan planned
   float* la_latest = nullptr;           // [la_slots][6] key pose of the newest frame
+  // alego_map_align: grown by the calls and kept
+  DevBuf<MaEntry> ma_ent;
+  DevBuf<unsigned long long> ma_cand;   // [entries][ALEGO_RELOC_MAX_CAND]
+  DevBuf<LcDet> ma_det;                 // [entries][ALEGO_RELOC_MAX_CAND]
+  DevBuf<float> ma_spose;               // [entries][6]
+  DevBuf<MaHyp> ma_hyp;                 // [pairs][MA_MAX_QUERIES]
+  DevBuf<int> ma_nq;                    // [pairs]
+  DevBuf<MaCons> ma_cons;               // [pairs]
   DevBuf<int> la_pend;                  // (slot, frame) pairs still to describe
   DevPool la_store;                     // owns the la_* arrays above (valid while la_cap > 0)
   DevPool store, scratch;               // own what reloc_enable allocates (valid while n_slots > 0) and the search scratch (valid while pairs_cap > 0)
@@ -357,6 +451,7 @@ struct RlCtx {
 void reloc_ctx_destroy(RlCtx* R) {
   if (!R) return;
   R->scratch.clear(); R->store.clear(); R->la_store.clear(); R->la_pend.clear();
+  R->ma_ent.clear(); R->ma_cand.clear(); R->ma_det.clear(); R->ma_spose.clear(); R->ma_hyp.clear(); R->ma_nq.clear(); R->ma_cons.clear();
   delete R;
 }
 void reloc_ctx_set(RlCtx** pr, int what, long long v) {   // what 0: pairs per chunk of the search, 1: brute force
@@ -622,7 +717,8 @@ int loop_app_debug_get(RlCtx* R, int slot, const char* name, const void** src, s
   return 0;
 }
 
-// correction = t_correct * matrix(latest6)^-1: the f32 matrices widened to f64, the rigid inverse, the product rounded to f32
+// correction = t_correct * matrix(latest6)^-1: the f32 matrices widened to f64, the rigid inverse, the product rounded to f32.  The world
+// correction of the appearance search (latest6 = the newest key pose) and the hypothesis of alego_map_align (latest6 = the source key pose).
 static void la_world_correction(const float* t_correct, const float* latest6, float* correction) {
   const float eye[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   float G[16];
@@ -639,6 +735,17 @@ static void la_world_correction(const float* t_correct, const float* latest6, fl
     correction[r * 4 + 3] = (float)t;
   }
   correction[12] = correction[13] = correction[14] = 0.f; correction[15] = 1.f;
+}
+
+// queues the descriptors of the pending (slot, frame) pairs on `st` and counts them as described
+static int la_describe(RlCtx* R, const LmCtx& L, const std::vector<int>& pend, const char* who, hipStream_t st, std::string* err) {
+  if (pend.empty()) return 0;
+  if (R->la_pend.reserve(pend.size()) != hipSuccess) { *err = std::string(who) + ": out of device memory"; return ALEGO_ERR_HIP; }
+  if (hipMemcpyAsync(R->la_pend.p, pend.data(), pend.size() * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess) { *err = std::string(who) + ": upload failed"; return ALEGO_ERR_HIP; }
+  ALEGO_LAUNCH(rl_desc, dim3((unsigned)(pend.size() / 2)), dim3(RL_T), 0, st, L, 2, (const int*)R->la_pend.p, R->la_w, R->la_zoff, R->la_desc, R->la_key, (RlSlot*)nullptr, (uint16_t*)nullptr);
+  // (pend is pageable: the copy has left the host buffer when the call returns; the kernel is ordered behind it on `st`)
+  for (size_t k = 0; k < pend.size(); k += 2) R->la_described[pend[k]] = std::max(R->la_described[pend[k]], pend[k + 1] + 1);   // only now: the rows are queued
+  return 0;
 }
 
 int loop_app_run(RlCtx* R, LcCtx** lc, const LmCtx& L, const alego_params& P, const int* slots, int n, const alego_loop_app_opts& o, alego_loop_result* out,
@@ -668,13 +775,7 @@ int loop_app_run(RlCtx* R, LcCtx** lc, const LmCtx& L, const alego_params& P, co
     q.base = slot * R->la_cap; q.n = nf - 1; q.qrow = q.base + nf - 1; q.tag = slot;
     qr.push_back(q); qi.push_back(i);
   }
-  if (!pend.empty()) {
-    if (R->la_pend.reserve(pend.size()) != hipSuccess) { *err = "alego_loop_search_appearance: out of device memory"; return ALEGO_ERR_HIP; }
-    if (hipMemcpyAsync(R->la_pend.p, pend.data(), pend.size() * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess) { *err = "alego_loop_search_appearance: upload failed"; return ALEGO_ERR_HIP; }
-    ALEGO_LAUNCH(rl_desc, dim3((unsigned)(pend.size() / 2)), dim3(RL_T), 0, st, L, 2, (const int*)R->la_pend.p, R->la_w, R->la_zoff, R->la_desc, R->la_key, (RlSlot*)nullptr, (uint16_t*)nullptr);
-    // (pend is pageable: the copy has left the host buffer when the call returns; the kernel is ordered behind it on `st`)
-    for (size_t k = 0; k < pend.size(); k += 2) R->la_described[pend[k]] = std::max(R->la_described[pend[k]], pend[k + 1] + 1);   // only now: the rows are queued
-  }
+  if (int rc = la_describe(R, L, pend, "alego_loop_search_appearance", st, err)) return rc;
   // the search: every query against the older frames of its own slot
   const float jump2 = o.max_jump > 0.0 ? (float)(o.max_jump * o.max_jump) : -1.f;
   const double gap = P.lc_min_time_gap;
@@ -729,6 +830,172 @@ int loop_app_run(RlCtx* R, LcCtx** lc, const LmCtx& L, const alego_params& P, co
     }
     return ok;
   }, st, err);
+}
+
+// ---- alego_map_align: host ------------------------------------------------------------------------------------------------------------------
+int map_align_run(RlCtx* R, LcCtx** lc, const LmCtx& L, const alego_params& P, const int* src, const int* dst, int n, const alego_map_align_opts& o, alego_map_align_result* out,
+                  alego_map_align_hyp* hyp_out, hipStream_t st, std::string* err) {
+  const char* who = "alego_map_align";
+  std::vector<alego_map_align_hyp> hyp((size_t)n * MA_MAX_QUERIES);
+  std::memset(hyp.data(), 0, hyp.size() * sizeof(alego_map_align_hyp));
+  for (auto& h : hyp) h.src_frame = h.dst_frame = -1;
+  for (int i = 0; i < n; ++i) { std::memset(&out[i], 0, sizeof(out[i])); out[i].best = -1; }
+  auto finish = [&]() { if (hyp_out && n > 0) std::memcpy(hyp_out, hyp.data(), hyp.size() * sizeof(alego_map_align_hyp)); return 0; };
+  if (n == 0) return 0;
+  std::vector<int> stat((size_t)R->la_slots * AS_W);
+  if (hipMemcpyAsync(stat.data(), arc_stat_of(L, 0), stat.size() * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+    *err = std::string(who) + ": reading the archive failed"; return ALEGO_ERR_HIP;
+  }
+  // the entries: one per (pair, query), in pair order
+  std::vector<MaEntry> ent;
+  std::vector<RlQuery> qr;
+  std::vector<int> pend, first((size_t)n, 0);
+  std::vector<char> listed((size_t)R->la_slots, 0);
+  for (int i = 0; i < n; ++i) {
+    const int ns = std::min(stat[(size_t)src[i] * AS_W + AS_FRAMES], R->la_cap), nd = std::min(stat[(size_t)dst[i] * AS_W + AS_FRAMES], R->la_cap);
+    first[i] = (int)ent.size();
+    if (stat[(size_t)src[i] * AS_W + AS_DROPPED] > 0 || stat[(size_t)dst[i] * AS_W + AS_DROPPED] > 0) { out[i].status = -1; continue; }
+    if (ns == 0 || nd == 0) continue;
+    for (int slot : {src[i], dst[i]})
+      if (!listed[slot]) {
+        listed[slot] = 1;
+        const int nf = slot == src[i] ? ns : nd;
+        for (int f = std::min(R->la_described[slot], nf); f < nf; ++f) { pend.push_back(slot); pend.push_back(f); }
+      }
+    const int Q = ma_query_count(ns, o.n_queries);
+    out[i].n_queries = Q;
+    for (int q = 0; q < Q; ++q) {
+      const int f = ma_query_frame(ns, Q, q);
+      ent.push_back(MaEntry{src[i], dst[i], f, i});
+      RlQuery rq;
+      std::memset(&rq, 0, sizeof(rq));
+      rq.qrow = src[i] * R->la_cap + f; rq.base = dst[i] * R->la_cap; rq.n = nd; rq.tag = i;
+      qr.push_back(rq);
+      hyp[(size_t)i * MA_MAX_QUERIES + q].src_frame = f;
+    }
+  }
+  if (int rc = la_describe(R, L, pend, who, st, err)) return rc;
+  const int ne = (int)ent.size();
+  std::vector<unsigned long long> cand((size_t)ne * ALEGO_RELOC_MAX_CAND + 1);
+  if (int rc = rl_search_run(R, R->la_desc, R->la_key, qr.data(), ne, R->la_desc, R->la_key, o.n_cand, cand.data(),
+                             [&](const RlQuery* dq, int c, int nmax, uint32_t* bound, int*, hipStream_t s2) {
+                               ALEGO_LAUNCH(ma_mask, dim3(std::max(1, (nmax + RL_T - 1) / RL_T), c), dim3(RL_T), 0, s2, dq, (const uint16_t*)R->la_key, bound);
+                             }, nullptr, st, err)) return rc;
+  if (hipStreamSynchronize(st) != hipSuccess) { *err = std::string(who) + ": descriptors failed"; return ALEGO_ERR_HIP; }
+  auto hyp_of = [&](int e) -> alego_map_align_hyp& { return hyp[(size_t)ent[e].pair * MA_MAX_QUERIES + (e - first[ent[e].pair])]; };
+  std::vector<unsigned long long> ecand((size_t)ne * ALEGO_RELOC_MAX_CAND + 1, RL_CAND_NONE);   // per entry, after the max_dist cut
+  std::vector<int> ncand((size_t)ne + 1, 0);
+  std::vector<char> tried((size_t)n, 0);
+  bool any = false;
+  for (int e = 0; e < ne; ++e) {
+    int k = 0;
+    for (; k < o.n_cand; ++k) {
+      const unsigned long long c = cand[(size_t)e * ALEGO_RELOC_MAX_CAND + k];
+      if (c == RL_CAND_NONE || (o.max_dist > 0 && rl_cand_dist(c) > o.max_dist)) break;
+      ecand[(size_t)e * ALEGO_RELOC_MAX_CAND + k] = c;
+    }
+    ncand[e] = k;
+    if (k > 0) {
+      alego_map_align_hyp& H = hyp_of(e);
+      H.dst_frame = rl_cand_id(ecand[(size_t)e * ALEGO_RELOC_MAX_CAND]); H.dist = rl_cand_dist(ecand[(size_t)e * ALEGO_RELOC_MAX_CAND]); H.shift = rl_cand_shift(ecand[(size_t)e * ALEGO_RELOC_MAX_CAND]);
+      tried[ent[e].pair] = 1; any = true;
+    }
+  }
+  if (!any) return finish();
+  // the attempts on every candidate, planned on the device from both archives' tables
+  const size_t na = (size_t)ne * ALEGO_RELOC_MAX_CAND;
+  if (R->ma_ent.reserve((size_t)ne) != hipSuccess || R->ma_cand.reserve(na) != hipSuccess || R->ma_det.reserve(na) != hipSuccess || R->ma_spose.reserve((size_t)ne * 6) != hipSuccess ||
+      R->ma_hyp.reserve((size_t)n * MA_MAX_QUERIES) != hipSuccess || R->ma_nq.reserve((size_t)n) != hipSuccess || R->ma_cons.reserve((size_t)n) != hipSuccess) {
+    *err = std::string(who) + ": out of device memory"; return ALEGO_ERR_HIP;
+  }
+  std::vector<LcDet> plan(na);
+  std::vector<float> spose((size_t)ne * 6);
+  if (hipMemcpyAsync(R->ma_ent.p, ent.data(), (size_t)ne * sizeof(MaEntry), hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemcpyAsync(R->ma_cand.p, ecand.data(), na * sizeof(unsigned long long), hipMemcpyHostToDevice, st) != hipSuccess) { *err = std::string(who) + ": upload failed"; return ALEGO_ERR_HIP; }
+  ALEGO_LAUNCH(ma_plan, dim3(((int)na + 63) / 64), dim3(64), 0, st, L, (const MaEntry*)R->ma_ent.p, (const unsigned long long*)R->ma_cand.p, ne, P.lc_search_num, R->ma_det.p, R->ma_spose.p);
+  if (hipMemcpyAsync(plan.data(), R->ma_det.p, na * sizeof(LcDet), hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipMemcpyAsync(spose.data(), R->ma_spose.p, spose.size() * sizeof(float), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+    *err = std::string(who) + ": planning failed"; return ALEGO_ERR_HIP;
+  }
+  std::vector<int> eslot((size_t)ne);
+  for (int e = 0; e < ne; ++e) eslot[e] = ent[e].dst;
+  const double fitness_max = o.fitness_max > 0.0 ? o.fitness_max : P.lc_fitness_max;
+  if (int rc = loop_rounds(lc, P, R->la_slots, eslot.data(), ne, o.n_cand, loop_archive_gather(L), [&](int e, int v, LcDet* D) {
+        if (ncand[e] <= v) return false;
+        *D = plan[(size_t)e * ALEGO_RELOC_MAX_CAND + v];
+        return D->status == 1;
+      }, [&](int e, int v, const LcDet& D, const LcOut& O) {
+        alego_map_align_hyp& H = hyp_of(e);
+        alego_loop_result r;
+        std::memset(&r, 0, sizeof(r));
+        const bool ok = loop_result_fill(D, O, fitness_max, &r);
+        la_world_correction(r.t_correct, spose.data() + (size_t)e * 6, H.T);
+        const unsigned long long c = ecand[(size_t)e * ALEGO_RELOC_MAX_CAND + v];
+        H.dst_frame = rl_cand_id(c); H.dist = rl_cand_dist(c); H.shift = rl_cand_shift(c);
+        H.tried = v + 1; H.accepted = ok ? 1 : 0;
+        H.converged = O.converged; H.iterations = O.iterations; H.n_source = O.n_source; H.n_target = O.n_target; H.fitness = O.fitness;
+        for (int k = 0; k < 6; ++k) H.guess6[k] = D.pose_latest[k];
+        for (int k = 0; k < 16; ++k) H.icp_final[k] = O.correction[k];
+        return ok;
+      }, st, err)) return rc;
+  // the consensus of every pair's hypotheses
+  std::vector<MaHyp> mh((size_t)n * MA_MAX_QUERIES);
+  std::memset(mh.data(), 0, mh.size() * sizeof(MaHyp));
+  std::vector<int> nq((size_t)n);
+  std::vector<MaCons> cons((size_t)n);
+  for (int i = 0; i < n; ++i) nq[i] = out[i].n_queries;
+  for (int e = 0; e < ne; ++e) {
+    const alego_map_align_hyp& H = hyp_of(e);
+    MaHyp& M = mh[(size_t)ent[e].pair * MA_MAX_QUERIES + (e - first[ent[e].pair])];
+    std::memcpy(M.T, H.T, sizeof(M.T));
+    for (int k = 0; k < 3; ++k) M.p[k] = spose[(size_t)e * 6 + k];
+    M.accepted = H.accepted; M.fitness = H.fitness;
+  }
+  const double tol_trans = o.tol_trans > 0.0 ? o.tol_trans : ALEGO_ALIGN_TOL_TRANS, tol_rot = o.tol_rot > 0.0 ? o.tol_rot : ALEGO_ALIGN_TOL_ROT;
+  if (hipMemcpyAsync(R->ma_hyp.p, mh.data(), mh.size() * sizeof(MaHyp), hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemcpyAsync(R->ma_nq.p, nq.data(), nq.size() * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess) { *err = std::string(who) + ": upload failed"; return ALEGO_ERR_HIP; }
+  ALEGO_LAUNCH(ma_consensus, dim3(n), dim3(64), 0, st, (const MaHyp*)R->ma_hyp.p, (const int*)R->ma_nq.p, tol_trans, tol_rot, R->ma_cons.p);
+  if (hipMemcpyAsync(cons.data(), R->ma_cons.p, cons.size() * sizeof(MaCons), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+    *err = std::string(who) + ": the consensus failed"; return ALEGO_ERR_HIP;
+  }
+  const int min_support = o.min_support > 0 ? o.min_support : 2;
+  for (int i = 0; i < n; ++i) {
+    alego_map_align_result& r = out[i];
+    if (r.status < 0 || !tried[i]) continue;
+    alego_map_align_hyp* H = &hyp[(size_t)i * MA_MAX_QUERIES];
+    for (int q = 0; q < r.n_queries; ++q) { H[q].support = cons[i].support[q]; H[q].inlier = cons[i].inlier[q]; r.n_accepted += H[q].accepted; }
+    r.best = cons[i].best;
+    r.support = r.best >= 0 ? H[r.best].support : 0;
+    r.status = r.best >= 0 && r.support >= min_support ? 2 : 1;
+    if (r.best >= 0)
+      for (int k = 0; k < 12; ++k) r.T[k] = (double)H[r.best].T[k];
+  }
+  return finish();
+}
+
+extern "C" int alego_map_align_queries(int32_t n_frames, int32_t n_queries, int32_t* frames) {
+  if (n_queries <= 0) n_queries = 8;
+  if (n_frames < 0 || n_queries > ALEGO_ALIGN_MAX_QUERIES) return ALEGO_ERR_ARG;
+  const int Q = ma_query_count(n_frames, n_queries);
+  if (Q > 0 && !frames) return ALEGO_ERR_ARG;
+  for (int q = 0; q < Q; ++q) frames[q] = ma_query_frame(n_frames, Q, q);
+  return Q;
+}
+extern "C" int alego_map_align_consensus(const float* T16, const float* src_pos3, const double* fitness, const int32_t* accepted, int32_t n, double tol_trans, double tol_rot,
+                                         int32_t* support, int32_t* best) {
+  if (n < 0 || n > ALEGO_ALIGN_MAX_QUERIES || !best || (n > 0 && (!T16 || !src_pos3 || !fitness || !accepted || !support))) return ALEGO_ERR_ARG;
+  *best = ma_consensus_ref(T16, src_pos3, fitness, accepted, n, tol_trans > 0.0 ? tol_trans : ALEGO_ALIGN_TOL_TRANS, tol_rot > 0.0 ? tol_rot : ALEGO_ALIGN_TOL_ROT, support);
+  return ALEGO_OK;
+}
+extern "C" int alego_map_align_poses(const double T12[12], const float* poses6, int32_t n, float* out6) {
+  if (!T12 || n < 0 || (n > 0 && (!poses6 || !out6))) return ALEGO_ERR_ARG;
+  for (int i = 0; i < n; ++i) {
+    double X[12], Y[12];
+    pg_from_pose6(poses6 + (size_t)i * 6, X);
+    pg_compose(T12, X, Y);
+    pg_to_pose6(Y, out6 + (size_t)i * 6);
+  }
+  return ALEGO_OK;
 }
 
 // ---- host twins (plain C++) -----------------------------------------------------------------------------------------------------------

@@ -17,15 +17,17 @@
 struct LcDet {        // lc_detect's verdict on one listed slot
   int status;         // 0 no candidate, 1 attempt, -1 the archive dropped frames
   int latest, closest, jlo, jhi;   // history frames jlo .. jhi (jhi < jlo: none)
-  int n_src, n_raw, pad;
+  int n_src, n_raw;
+  int src1;           // 0: the source is frame `latest` of the attempt's own slot; s + 1: of slot s (alego_map_align: another slot's archive)
   float pose_latest[6], pose_closest[6];
 };
+DEV_INLINE int lc_src_slot(const LcDet& D, int slot) { return D.src1 > 0 ? D.src1 - 1 : slot; }
 struct LcJob { int li, slot, src_off, raw_off, cell_off, cell_cap; };   // one attempted slot of a chunk and its scratch regions
 struct LcOut { int converged, iterations, n_source, n_target; double fitness; float correction[16]; };   // lc_icp's verdict on one attempt
 
-// n_src = the points of archived frame `src` of the slot, n_raw = those of the window D->jlo .. D->jhi, from the archive's tables
+// n_src = the points of archived frame `src` of the source's slot (lc_src_slot), n_raw = those of the window D->jlo .. D->jhi of `slot`, from the archive's tables
 DEV_INLINE void lc_det_sizes(const LmCtx& L, int slot, int src, LcDet* D) {
-  D->n_src = arc_tab_points(arc_tab_of(L, slot, src));
+  D->n_src = arc_tab_points(arc_tab_of(L, lc_src_slot(*D, slot), src));
   long long n = 0;
   for (int j = D->jlo; j <= D->jhi; ++j) n += arc_tab_points(arc_tab_of(L, slot, j));
   D->n_raw = (int)n;
@@ -47,12 +49,13 @@ int icp_run(const alego_params& P, const alego_kf_in* latest, const alego_kf_in*
             alego_point* target_out, int target_cap, hipStream_t st, std::string* err);
 // fills src + jobs[j].src_off (det[jobs[j].li].n_src points) and raw + jobs[j].raw_off (n_raw points) of the J jobs of a chunk on `st`; nfr = 2 + 2 lc_search_num
 typedef std::function<void(const LcJob* jobs, const LcDet* det, int J, int nfr, float4* src, float4* raw, hipStream_t st)> LcGather;
-// det[0 .. n) on the host (n <= n_slots; status == 1: attempted, with n_src, n_raw and whatever the gather reads filled in) -> out[i] of every attempt.
+// det[0 .. n) on the host (any n: entries run in pieces of the context's list capacity, which is at least n_slots, and may repeat a slot; status == 1: attempted, with n_src, n_raw and whatever the gather reads filled in) -> out[i] of every attempt.
 // Chunked under the context's point budget (ALEGO_LC_BUDGET): chunking never changes a result.  Synchronous on `st`.
 int loop_attempts(LcCtx** pc, const alego_params& P, int n_slots, const int* slots, const LcDet* det, int n, const LcGather& gather, LcOut* out, hipStream_t st, std::string* err);
-// the gather of attempts read from the archive (lc_gather): source = frame det.latest under det.pose_latest, sub-map = frames jlo .. jhi under their archived poses
+// the gather of attempts read from the archive (lc_gather): source = frame det.latest of the source's slot (lc_src_slot) under det.pose_latest,
+// sub-map = frames jlo .. jhi of the job's slot under their archived poses
 LcGather loop_archive_gather(const LmCtx& L);
-// Verification rounds over n entries (n <= n_slots): round v < rounds tries candidate v of every entry that has one and is not accepted yet; the
+// Verification rounds over n entries: round v < rounds tries candidate v of every entry that has one and is not accepted yet; the
 // first acceptance ends the entry, and a round with nothing left to try ends the rounds.  plan(i, v, D): fill attempt (i, v) into the zeroed *D as
 // loop_attempts takes it and return true, or decline; verdict(i, v, D, O): the verdict O on attempt D of (i, v) -> was it accepted?
 typedef std::function<bool(int i, int v, LcDet* D)> LcPlan;

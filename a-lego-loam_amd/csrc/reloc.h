@@ -18,6 +18,9 @@ bool loop_app_enabled(const RlCtx* R);
 int loop_app_run(RlCtx* R, LcCtx** lc, const LmCtx& L, const alego_params& P, const int* slots, int n, const alego_loop_app_opts& o, alego_loop_result* out,
                  alego_loop_app_info* info, hipStream_t st, std::string* err);
 int loop_app_debug_get(RlCtx* R, int slot, const char* name, const void** src, size_t* bytes);   // "la_desc", "la_key"
+// alego_map_align: one slot's archive aligned to another's by appearance (needs loop_app_enable); o: n_queries and n_cand resolved
+int map_align_run(RlCtx* R, LcCtx** lc, const LmCtx& L, const alego_params& P, const int* src, const int* dst, int n, const alego_map_align_opts& o, alego_map_align_result* out,
+                  alego_map_align_hyp* hyp, hipStream_t st, std::string* err);
 void reloc_debug_stats(const RlCtx* R, int out[2]);
 void reloc_ctx_set(RlCtx** pr, int what, long long v);   // what 0: pairs per chunk of the search, 1: brute force
 void reloc_ctx_destroy(RlCtx* R);

@@ -29,6 +29,10 @@
 //       line followed by " appearance D S": the descriptor distance and the yaw shift of the accepted candidate.
 //   --loop-radius R
 //       lc_search_radius of the radius search in metres (history_search_radius_, default 20): a small R leaves the revisits to --appearance.
+//   either source + --align START2
+//       a second slot of the same handle replays the source from scan START2 (a second session through the same site), both with the archive
+//       and the appearance descriptors on.  At the end alego_map_align(src = slot 1, dst = slot 0) asks which rigid transform takes the second
+//       archive into the frame of the first and prints one line "align: status S queries Q accepted A support K T t00 .. t23" (T row-major 3 x 4).
 //   either source + --localize [--loc-radius R]
 //       map once, then localise in that map: the run above keeps the archive on; afterwards every archived key frame is pulled with
 //       alego_map_get_keyframe, a SECOND handle is opened, alego_loc_enable hands it those frames, and the same scans are replayed through
@@ -62,7 +66,7 @@ int main(int argc, char** argv) {
   int map_frames = 4096, map_points = 1 << 24, loop_every = 0, close_every = 0, max_loops = 16;
   bool list_only = false, standalone = false, localize = false, relocalize = false, appearance = false;
   double loc_radius = 0.0, reloc_range = 0.0, app_max_jump = 0.0, app_range = 0.0, loop_radius = 0.0;
-  long reloc_start = -1;
+  long reloc_start = -1, align_start = -1;
   long max_scans = -1;
   int n_scan = 16, horizon = -1;
   std::vector<const char*> pos;
@@ -87,6 +91,7 @@ int main(int argc, char** argv) {
     else if (a == "--app-max-jump") app_max_jump = std::atof(val());
     else if (a == "--app-range") app_range = std::atof(val());
     else if (a == "--loop-radius") loop_radius = std::atof(val());
+    else if (a == "--align") align_start = std::atol(val());
     else if (a == "--localize") localize = true;
     else if (a == "--loc-radius") loc_radius = std::atof(val());
     else if (a == "--relocalize") relocalize = true;
@@ -130,17 +135,17 @@ int main(int argc, char** argv) {
     P.input_is_dense = dense;
   }
   alego_handle* h = nullptr;
-  if (int rc = alego_create(&P, /*device*/ 0, /*slots*/ 1, /*ring*/ 1, &h)) {
+  if (int rc = alego_create(&P, /*device*/ 0, /*slots*/ align_start >= 0 ? 2 : 1, /*ring*/ 1, &h)) {
     std::fprintf(stderr, "alego_create failed (%d): there is no CPU fallback, an MI355X is required\n", rc);
     return 1;
   }
-  if ((!map_dir.empty() || loop_every > 0 || close_every > 0 || localize) && alego_map_enable(h, map_frames, map_points) != ALEGO_OK) {
+  if ((!map_dir.empty() || loop_every > 0 || close_every > 0 || localize || align_start >= 0) && alego_map_enable(h, map_frames, map_points) != ALEGO_OK) {
     std::fprintf(stderr, "map_enable: %s\n", alego_last_error(h)); alego_destroy(h); return 1;
   }
   if (close_every > 0 && alego_graph_enable(h, max_loops, nullptr) != ALEGO_OK) {
     std::fprintf(stderr, "graph_enable: %s\n", alego_last_error(h)); alego_destroy(h); return 1;
   }
-  if (appearance && (loop_every > 0 || close_every > 0) && alego_loop_appearance_enable(h, app_range, 0.0 / 0.0) != ALEGO_OK) {
+  if (((appearance && (loop_every > 0 || close_every > 0)) || align_start >= 0) && alego_loop_appearance_enable(h, app_range, 0.0 / 0.0) != ALEGO_OK) {
     std::fprintf(stderr, "loop_appearance_enable: %s\n", alego_last_error(h)); alego_destroy(h); return 1;
   }
   // the radius search first; with --appearance a slot it has no candidate for is searched by appearance.  app = " appearance D S" of a closure found that way
@@ -157,6 +162,8 @@ int main(int argc, char** argv) {
   alego_pose odom{}, mapped{};
   int key_frames = 0, last_flags = 0, dropped = 0;
   float last_key_pose[6] = {0, 0, 0, 0, 0, 0};
+  std::vector<alego_point> pts2(align_start >= 0 ? cap_in : 0);   // --align: the second slot's scan
+  bool align_ended = false;
   std::vector<double> map_track;   // --localize: the mapping run's map pose of every scan (NaN for a dropped message)
   for (long k = 0; k < n_scans; ++k) {
     int n;
@@ -174,6 +181,27 @@ int main(int argc, char** argv) {
     if (flags < 0) { std::fprintf(stderr, "scan %ld: %s\n", k, alego_last_error(h)); alego_destroy(h); return 1; }
     last_flags = flags;
     map_track.insert(map_track.end(), mapped.t, mapped.t + 3);
+    if (align_start >= 0 && !align_ended) {   // the second session: slot 1, START2 scans further on, from buffers of its own
+      const long k2 = align_start + k;
+      double stamp2 = 0.1 * k;
+      int n2;
+      if (!bag) {
+        n2 = alego_synth_scan(&P, 0, k2, 0, pts2.data(), N);
+      } else if (k2 >= (long)alego_bag_message_count(bag, topic.c_str())) {
+        std::fprintf(stderr, "align: the bag ends at message %ld: the second slot stops after %ld scans\n", k2, k);
+        align_ended = true;
+        n2 = -1;
+      } else {
+        n2 = alego_bag_read_pc2(bag, topic.c_str(), k2, pts2.data(), cap_in, &stamp2, nullptr);
+        if (n2 < 0) std::fprintf(stderr, "message %ld (slot 1): %s\n", k2, alego_bag_last_error(bag));
+        else if (n2 > N) std::fprintf(stderr, "message %ld (slot 1): %d points > n_scan * horizon_scan = %d\n", k2, n2, N);
+      }
+      if (n2 >= 0 && n2 <= N) {
+        alego_scan_in in2{pts2.data(), n2, stamp2};
+        alego_pose o2{}, m2{};
+        if (alego_scan_process(h, 1, &in2, 7, nullptr, nullptr, &o2, &m2) < 0) { std::fprintf(stderr, "scan %ld (slot 1): %s\n", k2, alego_last_error(h)); alego_destroy(h); return 1; }
+      }
+    }
     if (flags & ALEGO_FLAG_LM_KEYFRAME) {   // saveKeyFramesAndFactor stored a frame: fetch it as the pose-graph thread would
       alego_keyframe kf{};
       kf.corner = kc.data(); kf.corner_cap = N; kf.surf = ks.data(); kf.surf_cap = N; kf.outlier = ko.data(); kf.outlier_cap = N;
@@ -200,6 +228,14 @@ int main(int argc, char** argv) {
       }
       if (gr.applied) std::printf("closed: scan %ld slot %d poses %d loops %d iterations %d cost %.9g -> %.9g%s\n", k, slot, gr.n_poses, gr.n_loops, gr.iterations, gr.cost0, gr.cost, app.c_str());
     }
+  }
+  if (align_start >= 0) {
+    const int32_t src = 1, dst = 0;
+    alego_map_align_result ar{};
+    if (alego_map_align(h, &src, &dst, 1, nullptr, &ar, nullptr) != ALEGO_OK) { std::fprintf(stderr, "map_align: %s\n", alego_last_error(h)); alego_destroy(h); return 1; }
+    std::printf("align: status %d queries %d accepted %d support %d T", ar.status, ar.n_queries, ar.n_accepted, ar.support);
+    for (int i = 0; i < 12; ++i) std::printf(" %.9g", ar.T[i]);
+    std::printf("\n");
   }
   std::string loc_json;
   if (localize) {   // the second half: a fresh handle localises the same scans in the map the first one built

@@ -614,6 +614,86 @@ int alego_loop_search_appearance(alego_handle* h, const int32_t* slots, int32_t 
 int alego_loop_appearance_candidates(const uint8_t* desc, const float* keyposes6, const double* stamps, int32_t n, double min_time_gap,
                                      double max_jump, int32_t max_dist, int32_t n_cand, int32_t* ids, int32_t* dists, int32_t* shifts);
 
+/* ---- aligning one slot's key-frame archive to another's by appearance (needs alego_loop_appearance_enable) -------
+ * Every archive sits in the frame of its own first scan.  alego_map_align asks, for pairs (src, dst) of slots, which rigid transform takes the
+ * source archive into the destination's frame: several source frames are searched in the destination's descriptors and verified by the ICP
+ * of alego_loop_search, and the answers of the queries decide among themselves - true answers agree on one transform, aliased ones do not.
+ * The rule (the project's own; csrc/align_math.h and csrc/kernels_reloc.hip state it next to the code), for a pair with ns source and nd
+ * destination frames archived and none dropped:
+ *   queries     Q = min(n_queries, ns); query q is source frame ((2 q + 1) ns) / (2 Q) in integer arithmetic, the middle of the q-th of Q equal
+ *               stretches: distinct and ascending.  alego_map_align_queries is the same function.
+ *   search      every query over ALL nd destination frames, no eligibility predicate: the n_cand frames smallest in (D_i, i), D_i and s_i as
+ *               alego_reloc_match - exactly the brute force over all frames and all 60 shifts; candidates with D_i > max_dist are dropped when
+ *               max_dist > 0; a query whose ring key is all zero (no point in range) has none.
+ *   verify      per query, candidates in order, the first accepted ends the query: source = source frame f (surf, corner, outlier) under
+ *               guess6 = destination key pose i with yaw - (float)s_i * (float)(2 pi / 60); target = destination frames [i - lc_search_num,
+ *               i + lc_search_num] within [0, nd - 1] under their archived poses through VoxelGrid(lc_leaf); ICP and fitness exactly as
+ *               alego_loop_search runs them.  Accepted when converged && fitness <= fitness_max (fitness_max <= 0: lc_fitness_max).
+ *   hypothesis  T = t_correct * matrix(source key pose f)^-1, t_correct = icp_final * matrix(guess6) as alego_loop_constraint builds it; f32
+ *               matrices widened to f64, the rigid inverse, the product rounded to f32 - the arithmetic of the appearance search's correction.
+ *   consensus   accepted hypotheses a and b AGREE when the angle of R_a^T R_b, taken as atan2(|v|, c) with v = vee(M - M^T) / 2 and
+ *               c = (tr M - 1) / 2, is <= tol_rot and, at both query positions p_a and p_b (the source key-pose xyz), |T_a p - T_b p| <=
+ *               tol_trans; f64 without contraction.  Positions are compared rather than the translation columns, so that a small rotation error
+ *               far from the origin counts.  A non-finite T agrees with nothing, itself included.  support(a) = the accepted b that agree with a,
+ *               a included; best = the largest support (>= 1), ties to the smaller own fitness, then to the smaller index; inlier marks the
+ *               hypotheses that agree with the best one.  The result's T is the best hypothesis itself: no averaging.
+ *   status      -1 an archive of the pair dropped frames; 0 nothing to try (an empty archive, or no query had a candidate); 2 when
+ *               support(best) >= min_support; 1 otherwise.
+ * Defaults of tol_trans / tol_rot, measured on the reference-side emulation of tests/test_map_align.py (two oracle-mapped stretches of the
+ * synthetic lap; DESIGN.md section 17 has the tables): A = the largest pairwise disagreement among hypotheses within 0.25 m / 0.02 rad of the
+ * ground truth, B = the smallest disagreement between such a hypothesis and one that is not; the defaults are 2 A and must stay below B / 2.
+ *   A = 0.1197 m / 0.00825 rad, B = 29.27 m / 3.1385 rad (an aliased place lies half a turn away), so
+ *   ALEGO_ALIGN_TOL_TRANS   0.24 m       (2 A rounded up; B / 2 = 14.6 m)
+ *   ALEGO_ALIGN_TOL_ROT     0.0165 rad   (2 A rounded up; B / 2 = 1.57 rad)
+ * alego_map_align         synchronous; runs behind the work queued on every stream group and changes no device state.  out[i] (and
+ *                         hyp[i][0 .. ALEGO_ALIGN_MAX_QUERIES), when hyp is not NULL) belongs to the pair (src_slots[i], dst_slots[i]); a pair's
+ *                         result does not depend on the other pairs, their order or the chunking, and a slot may appear in many pairs.
+ *                         opts == NULL or a field <= 0: n_queries 8, n_cand 2, max_dist off, min_support 2, fitness_max lc_fitness_max, the
+ *                         tolerances above.  ALEGO_ERR_ARG: a localising handle, the appearance search not enabled, a slot out
+ *                         of range, src == dst in a pair, a pair listed twice, n_queries > ALEGO_ALIGN_MAX_QUERIES, n_cand > ALEGO_RELOC_MAX_CAND.
+ *                         Descriptors of both archives are built lazily as by alego_loop_search_appearance; scratch grows with the calls and
+ *                         stays with the handle.  Without a call nothing is allocated or launched.
+ * alego_map_align_queries   host only, plain C++: the query frames of an archive of n_frames; returns Q (n_queries <= 0: 8).
+ * alego_map_align_consensus host only, plain C++: support[n] and *best (-1: none) of n <= ALEGO_ALIGN_MAX_QUERIES hypotheses T16[n][16] (row-major
+ *                         4 x 4, rows 0 .. 2 read) with query positions src_pos3[n][3] - the arithmetic the kernel runs.  tol <= 0: the defaults.
+ *                         The sums, products and the square root are the same f64 on both sides; atan2 comes from two libraries (the device's and
+ *                         the host's), so a pair whose angle lies within an ulp of tol_rot may be judged differently by the two.
+ * alego_map_align_poses   host only, plain C++: out6[i] = the f32 key pose of T12 * Pose3(RzRyRx(roll, pitch, yaw), xyz) of poses6[i], f64, back
+ *                         to (x y z, roll = atan2(R21, R22), pitch = atan2(-R20, sqrt(R21^2 + R22^2)), yaw = atan2(R10, R00)) as alego_graph_optimize
+ *                         writes poses.  The caller moves an archive with the calls that exist: alego_map_set_keyposes, alego_lm_set_keypose,
+ *                         alego_lm_reset_window, alego_lm_apply_correction.  Moving a slot on the device is not part of this interface. */
+#define ALEGO_ALIGN_MAX_QUERIES 32
+#define ALEGO_ALIGN_TOL_TRANS 0.24    /* m */
+#define ALEGO_ALIGN_TOL_ROT 0.0165    /* rad */
+typedef struct alego_map_align_opts {
+  int32_t n_queries;       /* 1 .. ALEGO_ALIGN_MAX_QUERIES; <= 0: 8 */
+  int32_t n_cand;          /* candidates per query, 1 .. ALEGO_RELOC_MAX_CAND; <= 0: 2 */
+  int32_t max_dist;        /* > 0: candidates with D above it are dropped */
+  int32_t min_support;     /* <= 0: 2 */
+  double fitness_max;      /* <= 0: lc_fitness_max */
+  double tol_trans, tol_rot;   /* agreement of two hypotheses, m / rad; <= 0: ALEGO_ALIGN_TOL_TRANS / ALEGO_ALIGN_TOL_ROT */
+} alego_map_align_opts;
+typedef struct alego_map_align_hyp {   /* one per query */
+  int32_t src_frame, dst_frame, dist, shift;   /* the last candidate verified (the accepted one when accepted); dst_frame -1: the query had no candidate */
+  int32_t tried, accepted;                     /* candidates verified; 1 when one was accepted */
+  int32_t converged, iterations, n_source, n_target;
+  int32_t support, inlier;                     /* accepted hypotheses agreeing with this one (itself included); 1 when it agrees with the best */
+  double fitness;
+  float guess6[6], icp_final[16];
+  float T[16];                                 /* dst <- src of this hypothesis, row-major */
+} alego_map_align_hyp;
+typedef struct alego_map_align_result {
+  int32_t status;          /* 2 aligned; 1 hypotheses but support < min_support; 0 nothing to try; -1 an archive of the pair dropped frames */
+  int32_t n_queries, n_accepted, best, support;   /* best: index of the chosen hypothesis or -1 */
+  double T[12];            /* dst <- src, row-major 3x4: the chosen hypothesis' T widened to f64 */
+} alego_map_align_result;
+int alego_map_align(alego_handle* h, const int32_t* src_slots, const int32_t* dst_slots, int32_t n, const alego_map_align_opts* opts,
+                    alego_map_align_result* out, alego_map_align_hyp* hyp /* NULL or [n][ALEGO_ALIGN_MAX_QUERIES] */);
+int alego_map_align_queries(int32_t n_frames, int32_t n_queries, int32_t* frames);
+int alego_map_align_consensus(const float* T16, const float* src_pos3, const double* fitness, const int32_t* accepted, int32_t n,
+                              double tol_trans, double tol_rot, int32_t* support, int32_t* best);
+int alego_map_align_poses(const double T12[12], const float* poses6, int32_t n, float* out6);
+
 /* ---- one scan-to-map registration sharded over the GPUs of a node (BASELINE.json config 5) ----------------
  * One process per GPU; every rank feeds its handle the SAME scans and so keeps a bit-identical replica of the stream's state
  * (ImageProjection, feature extraction, LaserOdometry and the local map are cheap and are computed redundantly).  What is split
