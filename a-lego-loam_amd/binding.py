@@ -38,6 +38,7 @@ EXPORTS = [
     "alego_reloc_enable", "alego_loc_relocalize", "alego_reloc_descriptor", "alego_reloc_match", "alego_debug_reloc_search",
     "alego_loop_appearance_enable", "alego_loop_search_appearance", "alego_loop_appearance_candidates",
     "alego_map_align", "alego_map_align_queries", "alego_map_align_consensus", "alego_map_align_poses",
+    "alego_map_move", "alego_map_merge", "alego_map_align_edge", "alego_map_merge_edges",
 ]
 
 REPLAY_PINGPONG = 0x100
@@ -48,6 +49,7 @@ RELOC_MAX_CAND = 8
 RELOC_SECTORS, RELOC_RINGS = 60, 20
 ALIGN_MAX_QUERIES = 32
 ALIGN_TOL_TRANS, ALIGN_TOL_ROT = 0.24, 0.0165   # ALEGO_ALIGN_TOL_TRANS, ALEGO_ALIGN_TOL_ROT
+MERGE_COPY_ITEM = 1024                          # ALEGO_MERGE_COPY_ITEM
 FLAG_LO_INIT, FLAG_FEW_SURF, FLAG_FEW_CORNER, FLAG_LM_SKIPPED, FLAG_LM_FEW_FEATURES, FLAG_LM_KEYFRAME = 1, 2, 4, 8, 16, 32
 
 
@@ -152,6 +154,14 @@ class MapAlignHyp(C.Structure):
 
 class MapAlignResult(C.Structure):
     _fields_ = [("status", C.c_int32), ("n_queries", C.c_int32), ("n_accepted", C.c_int32), ("best", C.c_int32), ("support", C.c_int32), ("T", C.c_double * 12)]
+
+
+class MapMergeOpts(C.Structure):
+    _fields_ = [("stamp_offset", C.c_double), ("seam_variance", C.c_void_p)]
+
+
+class MapMergeResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("frames", C.c_int32), ("points", C.c_int32), ("loop_edges", C.c_int32), ("cross_edges", C.c_int32)]
 
 
 class GraphEdge(C.Structure):
@@ -382,6 +392,11 @@ def lib():
         L.alego_map_align_queries.argtypes = [C.c_int32, C.c_int32, C.c_void_p]
         L.alego_map_align_consensus.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.POINTER(C.c_int32)]
         L.alego_map_align_poses.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        L.alego_map_move.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        L.alego_map_merge.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(MapMergeOpts), C.POINTER(MapAlignHyp), C.POINTER(MapMergeResult)]
+        L.alego_map_align_edge.argtypes = [C.POINTER(MapAlignHyp), C.c_void_p, C.c_int32, C.POINTER(GraphEdge)]
+        L.alego_map_merge_edges.argtypes = [C.POINTER(GraphEdge), C.c_int32, C.POINTER(GraphEdge), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.POINTER(GraphEdge), C.POINTER(GraphEdge)]
         L.alego_write_pcd.argtypes = [C.c_char_p, C.c_void_p, C.c_int32]
         L.alego_bag_read_pc2.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
         if L.alego_params_sizeof() != C.sizeof(AlegoParams):
@@ -508,6 +523,46 @@ def map_align_poses(T, poses6):
     if rc != 0:
         raise AlegoError(f"alego_map_align_poses failed ({rc})")
     return out
+
+
+def _hyp_struct(x, d):
+    """fills the MapAlignHyp x from a hypothesis dict of Handle.map_align"""
+    for k in ("src_frame", "dst_frame", "dist", "shift", "tried", "accepted", "converged", "iterations", "n_source", "n_target", "support", "inlier"):
+        setattr(x, k, int(d[k]))
+    x.fitness = float(d["fitness"])
+    x.guess6[:] = np.asarray(d["guess6"], np.float32).reshape(6).tolist()
+    x.icp_final[:] = np.asarray(d["icp_final"], np.float32).reshape(16).tolist()
+    x.T[:] = np.asarray(d["T"], np.float32).reshape(16).tolist()
+
+
+def map_align_edge(hyp, dst_pose6, nd):
+    """alego_map_align_edge: the cross edge (dict frm, to, between (3, 4), variance (6,)) of one accepted inlier hypothesis of Handle.map_align for a
+    destination of nd frames whose key pose of hyp["dst_frame"] is dst_pose6 (host code of the library)"""
+    x = MapAlignHyp()
+    _hyp_struct(x, hyp)
+    kp = np.ascontiguousarray(dst_pose6, np.float32).reshape(6)
+    e = (GraphEdge * 1)()
+    rc = lib().alego_map_align_edge(C.byref(x), kp.ctypes.data, int(nd), e)
+    if rc != 0:
+        raise AlegoError(f"alego_map_align_edge failed ({rc})")
+    g = _graph_edges_out(e, 1)
+    return dict(frm=int(g["frm"][0]), to=int(g["to"][0]), between=g["between"][0], variance=g["variance"][0])
+
+
+def map_merge_edges(src_chain, src_loops, nd, prev_pose6, first_pose6, seam_variance):
+    """alego_map_merge_edges: (chain, loops) as graph_get_edges dicts - the graph part of a merge behind nd destination frames from the source's chain and
+    loop edges (dicts of graph_get_edges), the destination's key pose nd - 1, the first moved pose and the seam's variances (host code of the library)"""
+    ns, nl = len(np.asarray(src_chain["frm"]).reshape(-1)), len(np.asarray(src_loops["frm"]).reshape(-1))
+    ch = graph_edges(src_chain["frm"], src_chain["to"], src_chain["between"], src_chain["variance"])
+    lp = graph_edges(src_loops["frm"], src_loops["to"], src_loops["between"], src_loops["variance"])
+    a = np.ascontiguousarray(np.zeros(6) if prev_pose6 is None else prev_pose6, np.float32).reshape(6)
+    b = np.ascontiguousarray(first_pose6, np.float32).reshape(6)
+    v = np.ascontiguousarray(seam_variance, np.float64).reshape(6)
+    oc, ol = (GraphEdge * max(ns, 1))(), (GraphEdge * max(nl, 1))()
+    rc = lib().alego_map_merge_edges(ch, ns, lp, nl, int(nd), a.ctypes.data, b.ctypes.data, v.ctypes.data, oc, ol)
+    if rc != 0:
+        raise AlegoError(f"alego_map_merge_edges failed ({rc})")
+    return _graph_edges_out(oc, ns), _graph_edges_out(ol, nl)
 
 
 def _reloc_result(r):
@@ -1019,6 +1074,40 @@ class Handle:
                                          T=np.array(x.T[:], np.float32).reshape(4, 4)))
             res.append(d)
         return res
+
+    # ---- a slot moved, one slot's archive appended to another's, on the device (needs map_enable) ----
+    def map_move(self, slots, T):
+        """alego_map_move: T (n, 3, 4) or one (3, 4) / (4, 4) for every listed slot; returns the status per slot (2 moved, 0 no key frame, -1 dropped frames)"""
+        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        T = np.asarray(T, np.float64)
+        if T.ndim == 2:
+            T = np.broadcast_to(T, (sl.shape[0],) + T.shape)
+        T12 = np.ascontiguousarray(T.reshape(sl.shape[0], T.shape[-2] * T.shape[-1])[:, :12])
+        st = np.zeros(max(sl.shape[0], 1), np.int32)
+        self._check(lib().alego_map_move(self._h, sl.ctypes.data, sl.shape[0], T12.ctypes.data, st.ctypes.data), "alego_map_move")
+        return [int(v) for v in st[:sl.shape[0]]]
+
+    def map_merge(self, pairs, T, stamp_offset=0.0, seam_variance=None, hyps=None):
+        """alego_map_merge: pairs (src, dst); T (n, 3, 4) or one for all; hyps: None or, per pair, the `hyp` list of map_align (or None).
+        One dict per pair: status (2 merged, 0 empty source, -1 dropped frames, -3 does not fit), frames, points, loop_edges, cross_edges"""
+        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        src, dst = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
+        n = pr.shape[0]
+        T = np.asarray(T, np.float64)
+        if T.ndim == 2:
+            T = np.broadcast_to(T, (n,) + T.shape)
+        T12 = np.ascontiguousarray(T.reshape(n, T.shape[-2] * T.shape[-1])[:, :12])
+        sv = None if seam_variance is None else np.ascontiguousarray(np.broadcast_to(np.asarray(seam_variance, np.float64), (6,)))
+        opts = MapMergeOpts(float(stamp_offset), None if sv is None else sv.ctypes.data)
+        hyp = None
+        if hyps is not None:
+            hyp = (MapAlignHyp * (max(n, 1) * ALIGN_MAX_QUERIES))()
+            for i, hs in enumerate(hyps):
+                for q, d in enumerate(hs or []):
+                    _hyp_struct(hyp[i * ALIGN_MAX_QUERIES + q], d)
+        out = (MapMergeResult * max(n, 1))()
+        self._check(lib().alego_map_merge(self._h, src.ctypes.data, dst.ctypes.data, n, T12.ctypes.data, C.byref(opts), hyp, out), "alego_map_merge")
+        return [dict(status=int(r.status), frames=int(r.frames), points=int(r.points), loop_edges=int(r.loop_edges), cross_edges=int(r.cross_edges)) for r in out[:n]]
 
     # ---- localisation against a frozen key-frame map ----
     def loc_enable(self, frames, radius=0.0):

@@ -19,6 +19,7 @@
 #include "front_end.h"
 #include "lm_ctx.h"
 #include "lm_host.h"
+#include "merge_math.h"
 #include "loop_ctx.h"
 #include "pgraph.h"
 #include "prof.h"
@@ -1350,6 +1351,72 @@ int alego_map_align(alego_handle* h, const int32_t* src_slots, const int32_t* ds
   g_prof = &h->prof;
   HIP_TRY(h, sync_all(h));   // behind everything already queued on every stream group
   return map_align_run(h->rl, &h->lc, *lm_host_ctx(h->lm), h->P, src_slots, dst_slots, n, o, out, hyp, h->stream, &h->err);
+}
+
+// ---- a slot moved, one archive appended to another's (kernels_merge.hip) ----
+static int merge_ready(alego_handle* h, const char* what) {
+  if (int r = not_localising(h, what)) return r;
+  if (!h->map_on) { h->err = std::string(what) + ": the key-frame archive is off (alego_map_enable)"; return ALEGO_ERR_ARG; }
+  hipSetDevice(h->device);
+  g_prof = &h->prof;
+  return 0;
+}
+int alego_map_move(alego_handle* h, const int32_t* slots, int32_t n, const double* T12, int32_t* out_status) {
+  if (!h || n < 0 || (n > 0 && (!slots || !T12 || !out_status))) return ALEGO_ERR_ARG;
+  if (int r = merge_ready(h, "alego_map_move")) return r;
+  std::vector<char> seen((size_t)h->d.n_slots, 0);
+  for (int i = 0; i < n; ++i) {
+    if (slots[i] < 0 || slots[i] >= h->d.n_slots) { h->err = "alego_map_move: slot out of range"; return ALEGO_ERR_ARG; }
+    if (seen[slots[i]]) { h->err = "alego_map_move: slot " + std::to_string(slots[i]) + " is listed twice"; return ALEGO_ERR_ARG; }
+    seen[slots[i]] = 1;
+    if (!mg_finite12(T12 + (size_t)i * 12)) { h->err = "alego_map_move: a transform is not finite"; return ALEGO_ERR_ARG; }
+  }
+  if (n == 0) return 0;
+  HIP_TRY(h, sync_all(h));   // behind everything already queued on every stream group
+  return lm_host_map_move(h->lm, slots, n, T12, out_status, &h->err);
+}
+int alego_map_merge(alego_handle* h, const int32_t* src_slots, const int32_t* dst_slots, int32_t n, const double* T12, const alego_map_merge_opts* opts,
+                    const alego_map_align_hyp* hyp, alego_map_merge_result* out) {
+  if (!h || n < 0 || (n > 0 && (!src_slots || !dst_slots || !T12 || !out))) return ALEGO_ERR_ARG;
+  if (int r = merge_ready(h, "alego_map_merge")) return r;
+  const double off = opts ? opts->stamp_offset : 0.0;
+  const double* sv = opts ? opts->seam_variance : nullptr;
+  if (!(off - off == 0.0)) { h->err = "alego_map_merge: stamp_offset is not finite"; return ALEGO_ERR_ARG; }
+  for (int k = 0; sv && k < 6; ++k) if (!(sv[k] > 0.0) || !(sv[k] - sv[k] == 0.0)) { h->err = "alego_map_merge: seam_variance must be positive and finite"; return ALEGO_ERR_ARG; }
+  std::vector<char> role((size_t)h->d.n_slots, 0);   // 1: a source, 2: a destination
+  for (int i = 0; i < n; ++i) {
+    const int a = src_slots[i], b = dst_slots[i];
+    if (a < 0 || a >= h->d.n_slots || b < 0 || b >= h->d.n_slots) { h->err = "alego_map_merge: slot out of range"; return ALEGO_ERR_ARG; }
+    if (a == b) { h->err = "alego_map_merge: slot " + std::to_string(a) + " is paired with itself"; return ALEGO_ERR_ARG; }
+    if (!mg_finite12(T12 + (size_t)i * 12)) { h->err = "alego_map_merge: a transform is not finite"; return ALEGO_ERR_ARG; }
+  }
+  for (int i = 0; i < n; ++i) {
+    if (role[dst_slots[i]] == 2) { h->err = "alego_map_merge: slot " + std::to_string(dst_slots[i]) + " is a destination twice"; return ALEGO_ERR_ARG; }
+    role[dst_slots[i]] = 2;
+  }
+  for (int i = 0; i < n; ++i)
+    if (role[src_slots[i]] == 2) { h->err = "alego_map_merge: slot " + std::to_string(src_slots[i]) + " is a destination of one pair and a source of another"; return ALEGO_ERR_ARG; }
+  if (n == 0) return 0;
+  HIP_TRY(h, sync_all(h));   // behind everything already queued on every stream group
+  return lm_host_map_merge(h->lm, &h->pg, src_slots, dst_slots, n, T12, off, sv, hyp, out, &h->err);
+}
+int alego_map_align_edge(const alego_map_align_hyp* hyp, const float dst_pose6[6], int32_t nd, alego_graph_edge* edge) {
+  if (!hyp || !dst_pose6 || !edge || nd < 0 || !(hyp->accepted && hyp->inlier)) return ALEGO_ERR_ARG;
+  float t_correct[16];
+  edge->from = nd + hyp->src_frame; edge->to = hyp->dst_frame;
+  if (int r = alego_loop_constraint(hyp->icp_final, hyp->guess6, dst_pose6, t_correct, edge->between)) return r;
+  for (int k = 0; k < 6; ++k) edge->variance[k] = (double)(float)hyp->fitness;
+  return ALEGO_OK;
+}
+int alego_map_merge_edges(const alego_graph_edge* src_chain, int32_t ns, const alego_graph_edge* src_loops, int32_t n_loops, int32_t nd,
+                          const float prev_pose6[6], const float first_pose6[6], const double seam_variance6[6],
+                          alego_graph_edge* out_chain, alego_graph_edge* out_loops) {
+  if (ns < 0 || n_loops < 0 || nd < 0 || (ns > 0 && (!src_chain || !out_chain || !first_pose6 || !seam_variance6)) || (ns > 0 && nd > 0 && !prev_pose6) ||
+      (n_loops > 0 && (!src_loops || !out_loops))) return ALEGO_ERR_ARG;
+  if (ns > 0) mg_seam_edge(nd, prev_pose6, first_pose6, seam_variance6, &out_chain[0]);
+  for (int f = 1; f < ns; ++f) mg_shift_edge(&src_chain[f], nd, &out_chain[f]);
+  for (int l = 0; l < n_loops; ++l) mg_shift_edge(&src_loops[l], nd, &out_loops[l]);
+  return ALEGO_OK;
 }
 
 int alego_loc_status(alego_handle* h, int slot, int32_t out[4]) {

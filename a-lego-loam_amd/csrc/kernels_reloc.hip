@@ -64,6 +64,7 @@
 
 #include "../../include/alego_mi355x.h"
 #include "align_math.h"
+#include "merge_math.h"
 #include "dev_common.h"
 #include "dev_cost.h"
 #include "dev_mem.h"
@@ -990,10 +991,9 @@ extern "C" int alego_map_align_consensus(const float* T16, const float* src_pos3
 extern "C" int alego_map_align_poses(const double T12[12], const float* poses6, int32_t n, float* out6) {
   if (!T12 || n < 0 || (n > 0 && (!poses6 || !out6))) return ALEGO_ERR_ARG;
   for (int i = 0; i < n; ++i) {
-    double X[12], Y[12];
-    pg_from_pose6(poses6 + (size_t)i * 6, X);
-    pg_compose(T12, X, Y);
-    pg_to_pose6(Y, out6 + (size_t)i * 6);
+    float kp[6];   // (out6 may be poses6)
+    mg_move_pose6(T12, poses6 + (size_t)i * 6, kp);
+    for (int k = 0; k < 6; ++k) out6[(size_t)i * 6 + k] = kp[k];
   }
   return ALEGO_OK;
 }

@@ -61,6 +61,11 @@ int lm_host_set_gv_small_max(LmHost* lm, int v);
 int lm_host_graph_enable(LmHost* lm, int max_loops, const double* odom_var6, std::string* err);
 // correctPoses for the slots with apply[slot] != 0 (apply_dev: the same flags on the device); n_poses_max: most key frames of an applied slot
 int lm_host_graph_apply(LmHost* lm, const std::vector<int>& apply, const int* apply_dev, int n_poses_max, std::string* err);
+// a slot moved / one archive appended to another's on the device (alego_map_move / alego_map_merge; kernels_merge.hip); arguments checked by the caller
+struct PgCtx;
+int lm_host_map_move(LmHost* lm, const int* slots, int n, const double* T12, int* out_status, std::string* err);
+int lm_host_map_merge(LmHost* lm, PgCtx** pc, const int* src, const int* dst, int n, const double* T12, double stamp_off, const double* seam_var6,
+                      const alego_map_align_hyp* hyp, alego_map_merge_result* out, std::string* err);
 // localisation mode (alego_loc_*; kernels_loc.hip): the frozen map store shared by every slot
 int lm_host_loc_enable(LmHost* lm, const DevCtx& d, const alego_kf_in* frames, int n, double radius, std::string* err);
 int lm_host_loc_status(LmHost* lm, int slot, int* out4, std::string* err);

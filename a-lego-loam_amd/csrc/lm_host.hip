@@ -15,6 +15,8 @@
 #include "gmap.h"
 #include "loc_math.h"
 #include "pgraph.h"
+#include "merge.h"
+#include "merge_math.h"
 
 struct LmHost {
   alego_params P;
@@ -39,6 +41,11 @@ struct LmHost {
   // localisation mode (alego_loc_enable): the two sort jobs that fill the map store, frame after frame
   VoxCtx vloc;
   bool vloc_made = false;
+  // alego_map_move / alego_map_merge: the pairs, copy items, per-slot tail words and moves of a call; allocated by the first call and kept
+  DevBuf<MgPair> mg_pairs;
+  DevBuf<int2> mg_items;
+  DevBuf<int> mg_tail;
+  DevBuf<MgMove> mg_moves;
 };
 
 namespace {
@@ -184,6 +191,7 @@ void lm_host_destroy(LmHost* lm) {
   for (auto& v : lm->vk) vox_destroy(&v);
   if (lm->vloc_made) vox_destroy(&lm->vloc);
   gv_destroy(&lm->gv);
+  lm->mg_pairs.clear(); lm->mg_items.clear(); lm->mg_tail.clear(); lm->mg_moves.clear();
   lm->mem.clear();
   delete lm;
 }
@@ -792,31 +800,154 @@ int lm_host_graph_enable(LmHost* lm, int max_loops, const double* odom_var6, std
   return 0;
 }
 
+// Frames of the slots with mask[slot] != 0 (mask_dev: the same words on the device) go through kf_tmp_* and the key-frame sort jobs, oldest first, one
+// frame of every such slot of a stream group per round (what alego_lm_set_keypose does for one frame of one slot); retransform(slot0, n, j, stream)
+// launches round j for the group's slots.  all: after the flush every slot of the group is noted as sorted (as map_update notes it), not only the masked.
+template <class F> static int resort_rounds(LmHost* lm, const std::vector<int>& mask, const int* mask_dev, int rounds, int all, F retransform, const char* what, std::string* err) {
+  const LmCtx& L = lm->L;
+  for (size_t g = 0; g < lm->st.size(); ++g) {
+    const int s0 = (int)g * lm->gsize, n = std::min(lm->gsize, lm->n_slots - s0);
+    bool any = false;
+    for (int s = s0; s < s0 + n; ++s) any = any || mask[s];
+    if (!any) continue;
+    hipStream_t st = lm->st[g];
+    // a key frame saved by the last mapping frame may still wait in kf_tmp_* for its sort: flush it before the buffer is reused
+    if (int r = vox_run(lm->vk[g], st, err)) return r;
+    launch_pg_sorted(L, mask_dev, s0, n, all, st);
+    for (int j = 0; j < rounds; ++j) {
+      retransform(s0, n, j, st);
+      if (int r = vox_run(lm->vk[g], st, err)) return r;
+      launch_pg_sorted(L, mask_dev, s0, n, 0, st);
+    }
+  }
+  for (hipStream_t s : lm->st) if (hipStreamSynchronize(s) != hipSuccess) { *err = std::string(what) + ": key-frame transform failed"; return ALEGO_ERR_HIP; }
+  return 0;
+}
+
 int lm_host_graph_apply(LmHost* lm, const std::vector<int>& apply, const int* apply_dev, int n_poses_max, std::string* err) {
   const LmCtx& L = lm->L;
   for (hipStream_t s : lm->st) if (hipStreamSynchronize(s) != hipSuccess) { *err = "graph apply: a stream failed"; return ALEGO_ERR_HIP; }
   launch_pg_apply(L, apply_dev, lm->n_slots, lm->st[0]);
   if (hipStreamSynchronize(lm->st[0]) != hipSuccess) { *err = "graph apply: pose write failed"; return ALEGO_ERR_HIP; }
-  // every resident frame of every applied slot goes through kf_tmp_* and the key-frame sort jobs, oldest first, one frame of every slot of
-  // a stream group per round (what alego_lm_set_keypose does for one frame of one slot)
-  const int rounds = std::min(L.K, n_poses_max);
-  for (size_t g = 0; g < lm->st.size(); ++g) {
-    const int s0 = (int)g * lm->gsize, n = std::min(lm->gsize, lm->n_slots - s0);
-    bool any = false;
-    for (int s = s0; s < s0 + n; ++s) any = any || apply[s];
-    if (!any) continue;
-    hipStream_t st = lm->st[g];
-    // a key frame saved by the last mapping frame may still wait in kf_tmp_* for its sort: flush it before the buffer is reused
-    if (int r = vox_run(lm->vk[g], st, err)) return r;
-    launch_pg_sorted(L, apply_dev, s0, n, 1, st);
-    for (int j = 0; j < rounds; ++j) {
-      launch_pg_retransform(L, apply_dev, s0, n, j, st);
-      if (int r = vox_run(lm->vk[g], st, err)) return r;
-      launch_pg_sorted(L, apply_dev, s0, n, 0, st);
-    }
+  // every resident frame of every applied slot
+  return resort_rounds(lm, apply, apply_dev, std::min(L.K, n_poses_max), 1,
+                       [&](int s0, int n, int j, hipStream_t st) { launch_pg_retransform(L, apply_dev, s0, n, j, st); }, "graph apply", err);
+}
+
+// ---- a slot moved, one archive appended to another's (alego_map_move / alego_map_merge; kernels_merge.hip) ----
+namespace {
+// the per-slot words `tail` (frames to re-sort, newest last) on the device, then the rounds
+int merge_rounds(LmHost* lm, const std::vector<int>& tail, const char* what, std::string* err) {
+  const LmCtx& L = lm->L;
+  if (lm->mg_tail.reserve(tail.size()) != hipSuccess || hipMemcpy(lm->mg_tail.p, tail.data(), tail.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
+    *err = std::string(what) + ": upload failed"; return ALEGO_ERR_HIP;
   }
-  for (hipStream_t s : lm->st) if (hipStreamSynchronize(s) != hipSuccess) { *err = "graph apply: key-frame transform failed"; return ALEGO_ERR_HIP; }
+  const int* dev = lm->mg_tail.p;
+  return resort_rounds(lm, tail, dev, *std::max_element(tail.begin(), tail.end()), 0,
+                       [&](int s0, int n, int j, hipStream_t st) { launch_mg_retransform(L, dev, s0, n, j, st); }, what, err);
+}
+int read_stats(LmHost* lm, std::vector<int>* arc, std::vector<int>* pg, const char* what, std::string* err) {
+  const LmCtx& L = lm->L;
+  for (hipStream_t s : lm->st) if (hipStreamSynchronize(s) != hipSuccess) { *err = std::string(what) + ": a stream failed"; return ALEGO_ERR_HIP; }
+  arc->assign((size_t)lm->n_slots * AS_W, 0); pg->assign((size_t)lm->n_slots * PS_W, 0);
+  if (hipMemcpy(arc->data(), L.arc_stat, arc->size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
+      (L.pg_loops_cap > 0 && hipMemcpy(pg->data(), L.pg_stat, pg->size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)) { *err = std::string(what) + ": device read failed"; return ALEGO_ERR_HIP; }
   return 0;
+}
+}  // namespace
+
+int lm_host_map_move(LmHost* lm, const int* slots, int n, const double* T12, int* out_status, std::string* err) {
+  const LmCtx& L = lm->L;
+  std::vector<int> arc, pg;
+  if (int r = read_stats(lm, &arc, &pg, "map_move", err)) return r;
+  std::vector<MgMove> mv;
+  std::vector<int> tail((size_t)lm->n_slots, 0);
+  for (int i = 0; i < n; ++i) {
+    const int* st = arc.data() + (size_t)slots[i] * AS_W;
+    out_status[i] = st[AS_DROPPED] ? -1 : (st[AS_FRAMES] == 0 ? 0 : 2);
+    if (out_status[i] != 2) continue;
+    MgMove m{slots[i], st[AS_FRAMES], 0, 0, {}};
+    std::memcpy(m.T, T12 + (size_t)i * 12, sizeof(m.T));
+    mv.push_back(m);
+    tail[slots[i]] = std::min(L.K, st[AS_FRAMES]);   // the resident frames, as alego_lm_set_keypose accepts them
+  }
+  if (mv.empty()) return 0;
+  if (lm->mg_moves.reserve(mv.size()) != hipSuccess || hipMemcpy(lm->mg_moves.p, mv.data(), mv.size() * sizeof(MgMove), hipMemcpyHostToDevice) != hipSuccess) { *err = "map_move: upload failed"; return ALEGO_ERR_HIP; }
+  launch_mg_move(L, lm->mg_moves.p, (int)mv.size(), lm->st[0]);
+  if (hipStreamSynchronize(lm->st[0]) != hipSuccess) { *err = "map_move: pose write failed"; return ALEGO_ERR_HIP; }
+  return merge_rounds(lm, tail, "map_move", err);
+}
+
+int lm_host_map_merge(LmHost* lm, PgCtx** pc, const int* src, const int* dst, int n, const double* T12, double stamp_off, const double* seam_var6,
+                      const alego_map_align_hyp* hyp, alego_map_merge_result* out, std::string* err) {
+  const LmCtx& L = lm->L;
+  const bool graph = L.pg_loops_cap > 0;
+  std::vector<int> arc, pg;
+  if (int r = read_stats(lm, &arc, &pg, "map_merge", err)) return r;
+  // ---- the plan: every count is known now, so every check comes before anything is written
+  std::vector<MgPair> pairs;
+  std::vector<int2> items;
+  std::vector<PgAppend> edges;
+  std::vector<int> tail((size_t)lm->n_slots, 0);
+  int ns_max = 0, tail_max = 0;
+  for (int i = 0; i < n; ++i) {
+    const int *as = arc.data() + (size_t)src[i] * AS_W, *ad = arc.data() + (size_t)dst[i] * AS_W;
+    const int ns = as[AS_FRAMES], nd = ad[AS_FRAMES], ps = as[AS_POINTS], pd = ad[AS_POINTS];
+    alego_map_merge_result& o = out[i];
+    o = alego_map_merge_result{0, 0, 0, 0, 0};
+    if (as[AS_DROPPED] || ad[AS_DROPPED]) { o.status = -1; continue; }
+    if (ns == 0) continue;
+    const int ls = graph ? pg[(size_t)src[i] * PS_W + PS_LOOPS] : 0, ld = graph ? pg[(size_t)dst[i] * PS_W + PS_LOOPS] : 0;
+    int nx = 0;
+    if (graph && hyp) for (int q = 0; q < ALEGO_ALIGN_MAX_QUERIES; ++q) { const alego_map_align_hyp& x = hyp[(size_t)i * ALEGO_ALIGN_MAX_QUERIES + q]; nx += (x.accepted && x.inlier) ? 1 : 0; }
+    if ((long long)nd + ns > L.arc_frames_cap || (long long)pd + ps > L.arc_points_cap || ld + ls + nx > L.pg_loops_cap) { o.status = -3; continue; }
+    if (graph && ls + nx > 0) {
+      std::vector<alego_graph_edge> sl((size_t)ls);
+      std::vector<float> kp((size_t)(nx ? nd : 0) * KF_POSE_W);
+      if ((ls && hipMemcpy(sl.data(), L.pg_loops + (size_t)src[i] * L.pg_loops_cap, sl.size() * sizeof(alego_graph_edge), hipMemcpyDeviceToHost) != hipSuccess) ||
+          (!kp.empty() && hipMemcpy(kp.data(), arc_pose_of(L, dst[i], 0), kp.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)) { *err = "map_merge: device read failed"; return ALEGO_ERR_HIP; }
+      PgAppend a;
+      std::memset(&a, 0, sizeof(a));
+      a.slot = dst[i];
+      for (int k = 0; k < 16; ++k) a.corr[k] = k % 5 == 0 ? 1.f : 0.f;   // alego_graph_add_edge(dst, e, NULL)
+      for (int l = 0; l < ls; ++l) { mg_shift_edge(&sl[l], nd, &a.e); edges.push_back(a); }
+      for (int q = 0; q < ALEGO_ALIGN_MAX_QUERIES && nx; ++q) {
+        const alego_map_align_hyp& x = hyp[(size_t)i * ALEGO_ALIGN_MAX_QUERIES + q];
+        if (!(x.accepted && x.inlier)) continue;
+        if (x.src_frame < 0 || x.src_frame >= ns || x.dst_frame < 0 || x.dst_frame >= nd) { *err = "map_merge: an inlier hypothesis names a frame outside the pair's archives"; return ALEGO_ERR_ARG; }
+        if (alego_map_align_edge(&x, kp.data() + (size_t)x.dst_frame * KF_POSE_W, nd, &a.e) != ALEGO_OK) { *err = "map_merge: a hypothesis gives no edge"; return ALEGO_ERR_ARG; }
+        const double v = a.e.variance[0];
+        bool fin = v > 0.0 && v - v == 0.0;
+        for (int k = 0; k < 12; ++k) fin = fin && a.e.between[k] - a.e.between[k] == 0.0;
+        if (!fin) { *err = "map_merge: an inlier hypothesis has a fitness that is not positive and finite, or a measurement that is not finite"; return ALEGO_ERR_ARG; }
+        edges.push_back(a);
+      }
+    }
+    o = alego_map_merge_result{2, ns, ps, ls, nx};
+    MgPair P;
+    std::memset(&P, 0, sizeof(P));
+    P.src = src[i]; P.dst = dst[i]; P.ns = ns; P.nd = nd; P.ps = ps; P.pd = pd; P.tail = std::min(ns, L.KR);
+    std::memcpy(P.T, T12 + (size_t)i * 12, sizeof(P.T));
+    P.stamp_off = stamp_off;
+    for (int k = 0; k < 6; ++k) P.seam_var[k] = seam_var6 ? seam_var6[k] : L.pg_odom_var[k];
+    for (int it = 0; it * MG_ITEM < ps; ++it) items.push_back(make_int2((int)pairs.size(), it));
+    pairs.push_back(P);
+    tail[dst[i]] = P.tail;
+    ns_max = std::max(ns_max, ns); tail_max = std::max(tail_max, P.tail);
+  }
+  if (pairs.empty()) return 0;
+  // ---- points, rows and edges, ring rows: three launches for all pairs
+  hipStream_t st = lm->st[0];
+  if (lm->mg_pairs.reserve(pairs.size()) != hipSuccess || lm->mg_items.reserve(std::max<size_t>(items.size(), 1)) != hipSuccess ||
+      hipMemcpy(lm->mg_pairs.p, pairs.data(), pairs.size() * sizeof(MgPair), hipMemcpyHostToDevice) != hipSuccess ||
+      (!items.empty() && hipMemcpy(lm->mg_items.p, items.data(), items.size() * sizeof(int2), hipMemcpyHostToDevice) != hipSuccess)) { *err = "map_merge: upload failed"; return ALEGO_ERR_HIP; }
+  launch_mg_copy(L, lm->mg_pairs.p, lm->mg_items.p, (int)items.size(), st);
+  launch_mg_frames(L, lm->mg_pairs.p, (int)pairs.size(), ns_max, st);
+  launch_mg_ring(L, lm->mg_pairs.p, (int)pairs.size(), tail_max, st);
+  if (hipStreamSynchronize(st) != hipSuccess) { *err = "map_merge: append failed"; return ALEGO_ERR_HIP; }
+  // ---- every ring row that now holds a source frame is transformed and sorted, oldest first
+  if (int r = merge_rounds(lm, tail, "map_merge", err)) return r;
+  return graph ? graph_append(pc, L, lm->n_slots, edges, st, err) : 0;
 }
 int lm_host_map_get_keyframe(LmHost* lm, int slot, int id, alego_keyframe* out, std::string* err) {
   int st[AS_W];

@@ -33,6 +33,11 @@
 //       a second slot of the same handle replays the source from scan START2 (a second session through the same site), both with the archive
 //       and the appearance descriptors on.  At the end alego_map_align(src = slot 1, dst = slot 0) asks which rigid transform takes the second
 //       archive into the frame of the first and prints one line "align: status S queries Q accepted A support K T t00 .. t23" (T row-major 3 x 4).
+//   --align START2 + --merge
+//       after an alignment with status 2 the second slot's archive is merged into the first's on the device: alego_map_merge(src = slot 1,
+//       dst = slot 0) with the alignment's T, its hypotheses as cross edges and a loose seam (variances 0.01 rad^2 / 0.25 m^2), then
+//       alego_graph_optimize with apply = 1 over the union (the key-pose graph is on for both slots).  One line "merge: status S frames F points P
+//       loop_edges L cross_edges X optimise status O poses N loops M iterations I cost C0 -> C"; with --save-map the files hold the union.
 //   either source + --localize [--loc-radius R]
 //       map once, then localise in that map: the run above keeps the archive on; afterwards every archived key frame is pulled with
 //       alego_map_get_keyframe, a SECOND handle is opened, alego_loc_enable hands it those frames, and the same scans are replayed through
@@ -49,6 +54,7 @@
 //
 //   g++ -O2 -std=c++17 -Iinclude examples/replay.cpp -o examples/replay -La-lego-loam_amd -lalego_mi355x -lalego_synth
 //       -Wl,-rpath,'$ORIGIN/../a-lego-loam_amd'                                  (__graft_entry__.build() does this)
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -64,7 +70,7 @@ int main(int argc, char** argv) {
   std::string bag_path, topic = "/lslidar_point_cloud", map_dir;
   float map_leaf = 0.f;
   int map_frames = 4096, map_points = 1 << 24, loop_every = 0, close_every = 0, max_loops = 16;
-  bool list_only = false, standalone = false, localize = false, relocalize = false, appearance = false;
+  bool list_only = false, standalone = false, localize = false, relocalize = false, appearance = false, merge = false;
   double loc_radius = 0.0, reloc_range = 0.0, app_max_jump = 0.0, app_range = 0.0, loop_radius = 0.0;
   long reloc_start = -1, align_start = -1;
   long max_scans = -1;
@@ -92,6 +98,7 @@ int main(int argc, char** argv) {
     else if (a == "--app-range") app_range = std::atof(val());
     else if (a == "--loop-radius") loop_radius = std::atof(val());
     else if (a == "--align") align_start = std::atol(val());
+    else if (a == "--merge") merge = true;
     else if (a == "--localize") localize = true;
     else if (a == "--loc-radius") loc_radius = std::atof(val());
     else if (a == "--relocalize") relocalize = true;
@@ -142,7 +149,8 @@ int main(int argc, char** argv) {
   if ((!map_dir.empty() || loop_every > 0 || close_every > 0 || localize || align_start >= 0) && alego_map_enable(h, map_frames, map_points) != ALEGO_OK) {
     std::fprintf(stderr, "map_enable: %s\n", alego_last_error(h)); alego_destroy(h); return 1;
   }
-  if (close_every > 0 && alego_graph_enable(h, max_loops, nullptr) != ALEGO_OK) {
+  if (merge && align_start < 0) { std::fprintf(stderr, "--merge needs --align START2\n"); alego_destroy(h); return 2; }
+  if ((close_every > 0 || merge) && alego_graph_enable(h, merge ? std::max(max_loops, ALEGO_ALIGN_MAX_QUERIES) : max_loops, nullptr) != ALEGO_OK) {
     std::fprintf(stderr, "graph_enable: %s\n", alego_last_error(h)); alego_destroy(h); return 1;
   }
   if (((appearance && (loop_every > 0 || close_every > 0)) || align_start >= 0) && alego_loop_appearance_enable(h, app_range, 0.0 / 0.0) != ALEGO_OK) {
@@ -232,10 +240,23 @@ int main(int argc, char** argv) {
   if (align_start >= 0) {
     const int32_t src = 1, dst = 0;
     alego_map_align_result ar{};
-    if (alego_map_align(h, &src, &dst, 1, nullptr, &ar, nullptr) != ALEGO_OK) { std::fprintf(stderr, "map_align: %s\n", alego_last_error(h)); alego_destroy(h); return 1; }
+    std::vector<alego_map_align_hyp> hyp(merge ? ALEGO_ALIGN_MAX_QUERIES : 0);
+    if (alego_map_align(h, &src, &dst, 1, nullptr, &ar, merge ? hyp.data() : nullptr) != ALEGO_OK) { std::fprintf(stderr, "map_align: %s\n", alego_last_error(h)); alego_destroy(h); return 1; }
     std::printf("align: status %d queries %d accepted %d support %d T", ar.status, ar.n_queries, ar.n_accepted, ar.support);
     for (int i = 0; i < 12; ++i) std::printf(" %.9g", ar.T[i]);
     std::printf("\n");
+    if (merge && ar.status == 2) {   // the two sessions become one map: append, tie by the hypotheses, optimise, correct
+      const double seam[6] = {1e-2, 1e-2, 1e-2, 0.25, 0.25, 0.25};
+      const alego_map_merge_opts mo{0.0, seam};
+      alego_map_merge_result mr{};
+      alego_graph_result gr{};
+      const alego_graph_opts go{0, 0.0, 1};
+      if (alego_map_merge(h, &src, &dst, 1, ar.T, &mo, hyp.data(), &mr) != ALEGO_OK || (mr.status == 2 && alego_graph_optimize(h, &dst, 1, &go, &gr) != ALEGO_OK)) {
+        std::fprintf(stderr, "map_merge: %s\n", alego_last_error(h)); alego_destroy(h); return 1;
+      }
+      std::printf("merge: status %d frames %d points %d loop_edges %d cross_edges %d optimise status %d poses %d loops %d iterations %d cost %.9g -> %.9g\n",
+                  mr.status, mr.frames, mr.points, mr.loop_edges, mr.cross_edges, gr.status, gr.n_poses, gr.n_loops, gr.iterations, gr.cost0, gr.cost);
+    }
   }
   std::string loc_json;
   if (localize) {   // the second half: a fresh handle localises the same scans in the map the first one built

@@ -661,7 +661,7 @@ int alego_loop_appearance_candidates(const uint8_t* desc, const float* keyposes6
  * alego_map_align_poses   host only, plain C++: out6[i] = the f32 key pose of T12 * Pose3(RzRyRx(roll, pitch, yaw), xyz) of poses6[i], f64, back
  *                         to (x y z, roll = atan2(R21, R22), pitch = atan2(-R20, sqrt(R21^2 + R22^2)), yaw = atan2(R10, R00)) as alego_graph_optimize
  *                         writes poses.  The caller moves an archive with the calls that exist: alego_map_set_keyposes, alego_lm_set_keypose,
- *                         alego_lm_reset_window, alego_lm_apply_correction.  Moving a slot on the device is not part of this interface. */
+ *                         alego_lm_reset_window, alego_lm_apply_correction - or, for whole slots on the device, with alego_map_move (below). */
 #define ALEGO_ALIGN_MAX_QUERIES 32
 #define ALEGO_ALIGN_TOL_TRANS 0.24    /* m */
 #define ALEGO_ALIGN_TOL_ROT 0.0165    /* rad */
@@ -693,6 +693,67 @@ int alego_map_align_queries(int32_t n_frames, int32_t n_queries, int32_t* frames
 int alego_map_align_consensus(const float* T16, const float* src_pos3, const double* fitness, const int32_t* accepted, int32_t n,
                               double tol_trans, double tol_rot, int32_t* support, int32_t* best);
 int alego_map_align_poses(const double T12[12], const float* poses6, int32_t n, float* out6);
+
+/* ---- moving a slot and merging one slot's archive into another's, on the device (needs alego_map_enable) ----------
+ * alego_map_align says which rigid transform takes one archive into the frame of another; these two calls act on it without a frame leaving
+ * the device.  Both are synchronous, run behind the work queued on every stream group, are refused (ALEGO_ERR_ARG) on a localising handle and
+ * with the archive off; their graph parts apply only after alego_graph_enable.  Without a call nothing is allocated or launched.  Each call is
+ * DEFINED by a sequence of the calls above and leaves the device state that sequence leaves, as every getter and every later scan sees it.
+ * The pose arithmetic is alego_map_align_poses' (csrc/merge_math.h); its sin, cos and atan2 come from the device's library here and from the
+ * host's there, so a pose component may differ from alego_map_align_poses in its last f32 bit; everything else is exact.
+ *
+ * alego_map_move   applies the row-major 3x4 T12[i] to the whole slot slots[i] of N archived frames; the state of
+ *     alego_map_set_keyposes(s, 0, N, alego_map_align_poses(T, archived poses)); alego_lm_set_keypose with the same pose for every resident frame,
+ *     oldest first; alego_lm_reset_window; alego_lm_apply_correction(s, T); and, with the graph on, chain edge 0 (the prior) rewritten to
+ *     between <- T * between as alego_graph_set_edges writes it (without that the next alego_graph_optimize pulls the slot back).  No other edge
+ *     changes, and neither does the last estimate.  out_status[i]: 2 moved, 0 no key frame, -1 the archive dropped frames (nothing written).
+ *     ALEGO_ERR_ARG: a slot out of range or listed twice, a non-finite T; nothing is written then.
+ * alego_map_merge  appends, for every pair, the source archive moved by T12[i] behind the destination's; the source slot is not changed.  With
+ *     ns source and nd destination frames the state of dst is that of
+ *       alego_lm_reset_window(dst);
+ *       alego_lm_add_keyframe(dst, moved pose of f, clouds of source frame f as archived) for f = 0 .. ns - 1;
+ *       alego_map_set_stamps(dst, nd, ns, source stamps + opts.stamp_offset) (one f64 add);
+ *     and, with the graph on,
+ *       chain edges nd + 1 .. nd + ns - 1 overwritten by the source's chain edges 1 .. ns - 1 with both ids raised by nd (a measurement stays
+ *       what was measured; it is not recomputed from the poses);
+ *       chain edge nd, the SEAM, as the archive recorded it - between(pose nd - 1 as archived now, the first moved pose), or the prior when
+ *       nd == 0 - with the variances opts.seam_variance.  NULL there means the graph's odometry variance, which asserts T with odometry
+ *       certainty: a caller who passes hypotheses wants the cross edges to decide and must pass a LOOSE seam;
+ *       the source's loop edges in their order, ids raised by nd, as alego_graph_add_edge(dst, e, NULL) appends them;
+ *       with hyp != NULL (the pair's [ALEGO_ALIGN_MAX_QUERIES] hypotheses of alego_map_align; entries beyond the pair's queries zero), for every
+ *       hypothesis with accepted && inlier, in index order, the edge of alego_map_align_edge, appended the same way.
+ *     The last estimate of dst stays what it was.  Descriptors of the appended frames are built lazily by the next appearance search or alignment.
+ *     out[i].status: 2 merged; 0 empty source; -1 an archive of the pair dropped frames; -3 does not fit (nd + ns > max_keyframes, points over
+ *     max_points, or destination loops + source loops + inlier edges over max_loops).  For every status but 2 dst is byte-unchanged, and the
+ *     other pairs proceed: all counts are known after the initial synchronisation, so every check happens before anything is written.
+ *     ALEGO_ERR_ARG (nothing written): a slot out of range, src == dst, a destination listed twice, a slot that is a destination of one pair
+ *     and a source of another, a non-finite T, a seam_variance that is not positive and finite, a non-finite stamp_offset, an inlier
+ *     hypothesis whose frames lie outside the archives or whose edge alego_graph_add_edge would refuse.  A source may feed many destinations.
+ * alego_map_align_edge   host only, plain C++: the cross edge of one hypothesis for a destination of nd frames: from = nd + src_frame,
+ *     to = dst_frame, between = that of alego_loop_constraint(icp_final, guess6, dst_pose6) with dst_pose6 the destination's key pose of
+ *     dst_frame, all six variances (float)fitness as alego_graph_add_loops sets them.  ALEGO_ERR_ARG unless accepted && inlier.
+ * alego_map_merge_edges  host only, plain C++ over csrc/merge_math.h (the arithmetic the kernel runs): the graph part of a merge from plain
+ *     arrays.  out_chain[ns]: [0] the seam (prev_pose6 = destination key pose nd - 1, unused for nd == 0; first_pose6 = the first moved pose;
+ *     seam_variance6), [f] = src_chain[f] shifted by nd; out_loops[n_loops] = src_loops shifted by nd.
+ * Out of scope: continuing the SOURCE's live stream inside the union (its LaserOdometry / LaserMapping state would have to move as well), and
+ * removing duplicate frames of the overlap. */
+#define ALEGO_MERGE_COPY_ITEM 1024   /* points per work item of the archive-to-archive copy: one workgroup copies this many at 16 B per lane and access */
+typedef struct alego_map_merge_opts {
+  double stamp_offset;           /* added to every source stamp */
+  const double* seam_variance;   /* [6] rotation x y z, translation x y z of chain edge nd; NULL: the graph's odometry variance */
+} alego_map_merge_opts;
+typedef struct alego_map_merge_result {
+  int32_t status;                /* 2 merged, 0 empty source, -1 an archive of the pair dropped frames, -3 does not fit */
+  int32_t frames, points;        /* appended to dst */
+  int32_t loop_edges, cross_edges;   /* the source's loop edges / the hypotheses' edges appended to dst */
+} alego_map_merge_result;
+int alego_map_move(alego_handle* h, const int32_t* slots, int32_t n, const double* T12 /* [n][12] */, int32_t* out_status);
+int alego_map_merge(alego_handle* h, const int32_t* src_slots, const int32_t* dst_slots, int32_t n, const double* T12 /* [n][12] */,
+                    const alego_map_merge_opts* opts, const alego_map_align_hyp* hyp /* NULL or [n][ALEGO_ALIGN_MAX_QUERIES] */, alego_map_merge_result* out);
+int alego_map_align_edge(const alego_map_align_hyp* hyp, const float dst_pose6[6], int32_t nd, alego_graph_edge* edge);
+int alego_map_merge_edges(const alego_graph_edge* src_chain, int32_t ns, const alego_graph_edge* src_loops, int32_t n_loops, int32_t nd,
+                          const float prev_pose6[6], const float first_pose6[6], const double seam_variance6[6],
+                          alego_graph_edge* out_chain, alego_graph_edge* out_loops);
 
 /* ---- one scan-to-map registration sharded over the GPUs of a node (BASELINE.json config 5) ----------------
  * One process per GPU; every rank feeds its handle the SAME scans and so keeps a bit-identical replica of the stream's state
