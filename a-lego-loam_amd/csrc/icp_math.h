@@ -1,11 +1,19 @@
 // icp_math.h — the per-iteration arithmetic of pcl::IterativeClosestPoint as performLoopClosure configures it
 // (laserMapping.cpp:670-692), shared by the single-attempt path (kernels_icp.hip) and the batched search (kernels_loop.hip):
 // Horn's closed-form rigid transform from the 17 correspondence sums, accumulation of final_transformation_ and
-// DefaultConvergenceCriteria.  One thread runs it.
+// DefaultConvergenceCriteria.  One thread runs it.  Plain C++ that a host compiler reads without the HIP runtime (tests/icp_math/icp_math_check.cpp
+// runs it against an SVD reference); f64 without contraction (-ffp-contract=off) on both sides.
 #ifndef ALEGO_ICP_MATH_H_
 #define ALEGO_ICP_MATH_H_
-#include "dev_common.h"
+#include <float.h>
+#include <math.h>
 #include "../../include/alego_params.h"
+
+#ifdef __HIPCC__
+#define ICP_FN __host__ __device__ inline
+#else
+#define ICP_FN inline
+#endif
 
 struct IcpState {
   float M[16];        // transformation_ of the last iteration (applied to the source by the next icp_corr)
@@ -15,7 +23,7 @@ struct IcpState {
 };
 
 // symmetric 4x4 eigen-decomposition, cyclic Jacobi (same algorithm as oracle_icp.h)
-DEV_INLINE void jacobi4(double A[4][4], double V[4][4], double lam[4]) {
+ICP_FN void jacobi4(double A[4][4], double V[4][4], double lam[4]) {
   for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) V[i][j] = i == j ? 1.0 : 0.0;
   for (int sweep = 0; sweep < 60; ++sweep) {
     double off = 0;
@@ -37,7 +45,7 @@ DEV_INLINE void jacobi4(double A[4][4], double V[4][4], double lam[4]) {
 }
 
 // T[17]: sum of source xyz (0..2), target xyz (3..5), source_u * target_w (6 + 3 u + w), squared distances (15), count (16)
-DEV_INLINE void icp_update(IcpState* S, const double* T, const alego_params& P) {
+ICP_FN void icp_update(IcpState* S, const double* T, const alego_params& P) {
   const double n = T[16];
   if (n < 3.0) { S->done = 1; S->converged = 0; return; }   // "Not enough correspondences found"
   const double mse = T[15] / n;

@@ -2098,7 +2098,7 @@ int oracle_loop_icp(const alego_params* P, const float* poses6, const alego_poin
     long n = 0;
     for (const Pt& p : cur) {   // determineCorrespondences: 1-NN in the target, kept within the maximum correspondence distance
       int idx; float d2;
-      if (kd.knn(p, 1, &idx, &d2) < 1 || (double)d2 > max_d2) continue;
+      if (kd.knn(p, 1, &idx, &d2) < 1 || !(d2 < FLT_MAX) || (double)d2 > max_d2) continue;   // (a NaN or infinite distance is no neighbour: the kernels' rule)
       const Pt& q = tgt[idx];
       const double a[3] = {p.x, p.y, p.z}, b[3] = {q.x, q.y, q.z};
       for (int k = 0; k < 3; ++k) { S[k] += a[k]; S[3 + k] += b[k]; }
@@ -2137,7 +2137,7 @@ int oracle_loop_icp(const alego_params* P, const float* poses6, const alego_poin
     p.x = Tf[0] * p0.x + Tf[1] * p0.y + Tf[2] * p0.z + Tf[3]; p.y = Tf[4] * p0.x + Tf[5] * p0.y + Tf[6] * p0.z + Tf[7]; p.z = Tf[8] * p0.x + Tf[9] * p0.y + Tf[10] * p0.z + Tf[11];
     p.intensity = p0.intensity;
     int idx; float d2;
-    if (kd.knn(p, 1, &idx, &d2) == 1) { fit += (double)d2; ++nf; }
+    if (kd.knn(p, 1, &idx, &d2) == 1 && d2 < FLT_MAX) { fit += (double)d2; ++nf; }
   }
   return finish(converged, it, nf ? fit / (double)nf : DBL_MAX);
 }

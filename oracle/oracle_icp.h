@@ -3,7 +3,8 @@
 // top of that pcl::IterativeClosestPoint / TransformationEstimationSVD / DefaultConvergenceCriteria are [upstream] (PCL 1.8,
 // un-vendored): restated from their published algorithm with two declared choices — the rigid transform of an iteration is Horn's
 // closed form (largest eigenvector of the 4x4 quaternion matrix, f64 sums in input order) instead of Eigen::umeyama in f32, whose
-// summation order is Eigen's own, and nearest-neighbour ties go to the lowest index.
+// summation order is Eigen's own, and nearest-neighbour ties go to the lowest index.  A source point without a finite distance to the target (a NaN or
+// infinite coordinate) has no neighbour: it enters neither the sums nor the fitness (oracle_loop_icp), the rule of the kernels' searches.
 #ifndef ORACLE_ICP_H_
 #define ORACLE_ICP_H_
 #include <algorithm>
