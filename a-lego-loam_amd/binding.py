@@ -39,6 +39,7 @@ EXPORTS = [
     "alego_loop_appearance_enable", "alego_loop_search_appearance", "alego_loop_appearance_candidates",
     "alego_map_align", "alego_map_align_queries", "alego_map_align_consensus", "alego_map_align_poses",
     "alego_map_move", "alego_map_merge", "alego_map_align_edge", "alego_map_merge_edges",
+    "alego_map_thin", "alego_map_thin_select", "alego_map_thin_edges", "alego_debug_thin_select",
 ]
 
 REPLAY_PINGPONG = 0x100
@@ -162,6 +163,14 @@ class MapMergeOpts(C.Structure):
 
 class MapMergeResult(C.Structure):
     _fields_ = [("status", C.c_int32), ("frames", C.c_int32), ("points", C.c_int32), ("loop_edges", C.c_int32), ("cross_edges", C.c_int32)]
+
+
+class MapThinOpts(C.Structure):
+    _fields_ = [("min_dist", C.c_double)]
+
+
+class MapThinResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("frames_before", C.c_int32), ("frames", C.c_int32), ("points_before", C.c_int32), ("points", C.c_int32)]
 
 
 class GraphEdge(C.Structure):
@@ -397,6 +406,10 @@ def lib():
         L.alego_map_align_edge.argtypes = [C.POINTER(MapAlignHyp), C.c_void_p, C.c_int32, C.POINTER(GraphEdge)]
         L.alego_map_merge_edges.argtypes = [C.POINTER(GraphEdge), C.c_int32, C.POINTER(GraphEdge), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.POINTER(GraphEdge), C.POINTER(GraphEdge)]
+        L.alego_map_thin.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(MapThinOpts), C.POINTER(MapThinResult)]
+        L.alego_map_thin_select.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p]
+        L.alego_map_thin_edges.argtypes = [C.POINTER(GraphEdge), C.c_int32, C.POINTER(GraphEdge), C.c_int32, C.c_void_p, C.POINTER(GraphEdge), C.POINTER(GraphEdge)]
+        L.alego_debug_thin_select.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p]
         L.alego_write_pcd.argtypes = [C.c_char_p, C.c_void_p, C.c_int32]
         L.alego_bag_read_pc2.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
         if L.alego_params_sizeof() != C.sizeof(AlegoParams):
@@ -563,6 +576,40 @@ def map_merge_edges(src_chain, src_loops, nd, prev_pose6, first_pose6, seam_vari
     if rc != 0:
         raise AlegoError(f"alego_map_merge_edges failed ({rc})")
     return _graph_edges_out(oc, ns), _graph_edges_out(ol, nl)
+
+
+def _thin_arrays(keyposes6, protect):
+    kp = np.ascontiguousarray(keyposes6, np.float32).reshape(-1, 6)
+    pr = np.zeros(kp.shape[0], np.uint8) if protect is None else np.ascontiguousarray(np.asarray(protect) != 0, np.uint8).reshape(-1)
+    if pr.shape[0] != kp.shape[0]:
+        raise ValueError("protect: one byte per frame")
+    return kp, pr, np.zeros(max(kp.shape[0], 1), np.uint8)
+
+
+def map_thin_select(keyposes6, protect, min_dist):
+    """alego_map_thin_select: the keep mask (n,) uint8 of alego_map_thin's selection rule for key poses (n, 6) and a protect mask (host code of the library)"""
+    kp, pr, keep = _thin_arrays(keyposes6, protect)
+    rc = lib().alego_map_thin_select(kp.ctypes.data, pr.ctypes.data, kp.shape[0], float(min_dist), keep.ctypes.data)
+    if rc < 0:
+        raise AlegoError(f"alego_map_thin_select failed ({rc})")
+    assert rc == int(keep[:kp.shape[0]].sum())
+    return keep[:kp.shape[0]]
+
+
+def map_thin_edges(chain, loops, keep):
+    """alego_map_thin_edges: (chain, loops) as graph_get_edges dicts - the graph of the kept frames from a slot's chain and loop edges (dicts of
+    graph_get_edges) and a keep mask (host code of the library)"""
+    n, nl = len(np.asarray(chain["frm"]).reshape(-1)), len(np.asarray(loops["frm"]).reshape(-1))
+    ch = graph_edges(chain["frm"], chain["to"], chain["between"], chain["variance"])
+    lp = graph_edges(loops["frm"], loops["to"], loops["between"], loops["variance"])
+    k = np.ascontiguousarray(np.asarray(keep) != 0, np.uint8).reshape(-1)
+    if k.shape[0] != n:
+        raise ValueError("keep: one byte per chain edge")
+    oc, ol = (GraphEdge * max(n, 1))(), (GraphEdge * max(nl, 1))()
+    rc = lib().alego_map_thin_edges(ch, n, lp, nl, k.ctypes.data, oc, ol)
+    if rc < 0:
+        raise AlegoError(f"alego_map_thin_edges failed ({rc})")
+    return _graph_edges_out(oc, rc), _graph_edges_out(ol, nl)
 
 
 def _reloc_result(r):
@@ -1108,6 +1155,24 @@ class Handle:
         out = (MapMergeResult * max(n, 1))()
         self._check(lib().alego_map_merge(self._h, src.ctypes.data, dst.ctypes.data, n, T12.ctypes.data, C.byref(opts), hyp, out), "alego_map_merge")
         return [dict(status=int(r.status), frames=int(r.frames), points=int(r.points), loop_edges=int(r.loop_edges), cross_edges=int(r.cross_edges)) for r in out[:n]]
+
+    # ---- a slot's archive thinned in place on the device (needs map_enable) ----
+    def map_thin(self, slots, min_dist):
+        """alego_map_thin: one dict per slot: status (2 thinned, 1 nothing to drop, 0 no key frame, -1 dropped frames), frames_before, frames,
+        points_before, points"""
+        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        opts = MapThinOpts(float(min_dist))
+        out = (MapThinResult * max(sl.shape[0], 1))()
+        self._check(lib().alego_map_thin(self._h, sl.ctypes.data, sl.shape[0], C.byref(opts), out), "alego_map_thin")
+        return [dict(status=int(r.status), frames_before=int(r.frames_before), frames=int(r.frames), points_before=int(r.points_before), points=int(r.points))
+                for r in out[:sl.shape[0]]]
+
+    def debug_thin_select(self, keyposes6, protect, min_dist):
+        """the selection kernel of alego_map_thin alone on the caller's arrays: the keep mask (n,) uint8"""
+        kp, pr, keep = _thin_arrays(keyposes6, protect)
+        rc = self._check(lib().alego_debug_thin_select(self._h, kp.ctypes.data, pr.ctypes.data, kp.shape[0], float(min_dist), keep.ctypes.data), "alego_debug_thin_select")
+        assert rc == int(keep[:kp.shape[0]].sum())
+        return keep[:kp.shape[0]]
 
     # ---- localisation against a frozen key-frame map ----
     def loc_enable(self, frames, radius=0.0):

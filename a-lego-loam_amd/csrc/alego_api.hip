@@ -20,6 +20,7 @@
 #include "lm_ctx.h"
 #include "lm_host.h"
 #include "merge_math.h"
+#include "thin_math.h"
 #include "loop_ctx.h"
 #include "pgraph.h"
 #include "prof.h"
@@ -1417,6 +1418,56 @@ int alego_map_merge_edges(const alego_graph_edge* src_chain, int32_t ns, const a
   for (int f = 1; f < ns; ++f) mg_shift_edge(&src_chain[f], nd, &out_chain[f]);
   for (int l = 0; l < n_loops; ++l) mg_shift_edge(&src_loops[l], nd, &out_loops[l]);
   return ALEGO_OK;
+}
+
+// ---- a slot's archive thinned in place (kernels_thin.hip) ----
+int alego_map_thin(alego_handle* h, const int32_t* slots, int32_t n, const alego_map_thin_opts* opts, alego_map_thin_result* out) {
+  if (!h || n < 0 || (n > 0 && (!slots || !out))) return ALEGO_ERR_ARG;
+  if (int r = merge_ready(h, "alego_map_thin")) return r;
+  const double md = opts ? opts->min_dist : 0.0;
+  if (!(md - md == 0.0)) { h->err = "alego_map_thin: min_dist is not finite"; return ALEGO_ERR_ARG; }
+  std::vector<char> seen((size_t)h->d.n_slots, 0);
+  for (int i = 0; i < n; ++i) {
+    if (slots[i] < 0 || slots[i] >= h->d.n_slots) { h->err = "alego_map_thin: slot out of range"; return ALEGO_ERR_ARG; }
+    if (seen[slots[i]]) { h->err = "alego_map_thin: slot " + std::to_string(slots[i]) + " is listed twice"; return ALEGO_ERR_ARG; }
+    seen[slots[i]] = 1;
+  }
+  if (n == 0) return 0;
+  HIP_TRY(h, sync_all(h));   // behind everything already queued on every stream group
+  std::vector<int> first((size_t)n, 0);
+  const int rc = lm_host_map_thin(h->lm, slots, n, md, out, first.data(), &h->err);
+  // the descriptors depend on the clouds only: a thinned slot keeps those below its first dropped frame (also after a failure half way)
+  for (int i = 0; i < n; ++i) if (rc || out[i].status == 2) loop_app_forget(h->rl, slots[i], rc ? 0 : first[i]);
+  return rc;
+}
+int alego_map_thin_select(const float* keyposes6, const uint8_t* protect, int32_t n, double min_dist, uint8_t* keep) {
+  if (n < 0 || (n > 0 && (!keyposes6 || !keep)) || !(min_dist - min_dist == 0.0)) return ALEGO_ERR_ARG;
+  return th_select_host(keyposes6, 6, protect, n, min_dist, keep);
+}
+int alego_map_thin_edges(const alego_graph_edge* chain, int32_t n, const alego_graph_edge* loops, int32_t n_loops, const uint8_t* keep,
+                         alego_graph_edge* out_chain, alego_graph_edge* out_loops) {
+  if (n < 0 || n_loops < 0 || (n > 0 && (!chain || !keep || !out_chain || !keep[0])) || (n_loops > 0 && (!loops || !out_loops))) return ALEGO_ERR_ARG;
+  std::vector<int> new_id((size_t)n, -1);
+  int m = 0;
+  for (int i = 0; i < n; ++i) if (keep[i]) new_id[i] = m++;
+  for (int l = 0; l < n_loops; ++l) {   // checked before anything is written: a loop edge's endpoints are kept
+    alego_graph_edge x;
+    if (!th_remap_edge(&loops[l], new_id.data(), n, &x)) return ALEGO_ERR_ARG;
+  }
+  for (int i = 0, prev = -1; i < n; ++i) {
+    if (!keep[i]) continue;
+    if (prev < 0) out_chain[0] = chain[0]; else th_compose_edge(chain, prev, i, new_id[i], &out_chain[new_id[i]]);
+    prev = i;
+  }
+  for (int l = 0; l < n_loops; ++l) (void)th_remap_edge(&loops[l], new_id.data(), n, &out_loops[l]);
+  return m;
+}
+int alego_debug_thin_select(alego_handle* h, const float* keyposes6, const uint8_t* protect, int32_t n, double min_dist, uint8_t* keep) {
+  if (!h || n < 0 || (n > 0 && (!keyposes6 || !protect || !keep)) || !(min_dist - min_dist == 0.0)) return ALEGO_ERR_ARG;
+  hipSetDevice(h->device);
+  g_prof = &h->prof;
+  HIP_TRY(h, sync_all(h));
+  return lm_host_debug_thin_select(h->lm, keyposes6, protect, n, min_dist, keep, &h->err);
 }
 
 int alego_loc_status(alego_handle* h, int slot, int32_t out[4]) {

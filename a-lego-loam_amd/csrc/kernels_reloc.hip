@@ -708,6 +708,10 @@ int loop_app_enable(RlCtx** pr, const LmCtx& L, int n_slots, double max_range, d
   return 0;
 }
 
+void loop_app_forget(RlCtx* R, int slot, int first) {
+  if (loop_app_enabled(R) && slot >= 0 && slot < R->la_slots) R->la_described[slot] = std::min(R->la_described[slot], std::max(first, 0));
+}
+
 int loop_app_debug_get(RlCtx* R, int slot, const char* name, const void** src, size_t* bytes) {
   if (!loop_app_enabled(R)) return ALEGO_ERR_ARG;
   const std::string s(name);

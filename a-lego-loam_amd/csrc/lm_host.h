@@ -66,6 +66,10 @@ struct PgCtx;
 int lm_host_map_move(LmHost* lm, const int* slots, int n, const double* T12, int* out_status, std::string* err);
 int lm_host_map_merge(LmHost* lm, PgCtx** pc, const int* src, const int* dst, int n, const double* T12, double stamp_off, const double* seam_var6,
                       const alego_map_align_hyp* hyp, alego_map_merge_result* out, std::string* err);
+// a slot's archive thinned in place (alego_map_thin; kernels_thin.hip); arguments checked by the caller.  first_dropped[i]: the first dropped id of
+// slots[i] (its frame count when none was dropped).  debug_thin_select: th_select alone on the caller's arrays, returns the frames kept
+int lm_host_map_thin(LmHost* lm, const int* slots, int n, double min_dist, alego_map_thin_result* out, int* first_dropped, std::string* err);
+int lm_host_debug_thin_select(LmHost* lm, const float* keyposes6, const uint8_t* protect, int n, double min_dist, uint8_t* keep, std::string* err);
 // localisation mode (alego_loc_*; kernels_loc.hip): the frozen map store shared by every slot
 int lm_host_loc_enable(LmHost* lm, const DevCtx& d, const alego_kf_in* frames, int n, double radius, std::string* err);
 int lm_host_loc_status(LmHost* lm, int slot, int* out4, std::string* err);

@@ -17,6 +17,8 @@
 #include "pgraph.h"
 #include "merge.h"
 #include "merge_math.h"
+#include "thin.h"
+#include "thin_math.h"
 
 struct LmHost {
   alego_params P;
@@ -46,6 +48,15 @@ struct LmHost {
   DevBuf<int2> mg_items;
   DevBuf<int> mg_tail;
   DevBuf<MgMove> mg_moves;
+  // alego_map_thin / alego_debug_thin_select: the jobs, their id tables and offsets, protect masks, copy items, the staged points and rows of a
+  // call, the caller's poses of the debug entry; allocated by the first call and kept
+  DevBuf<ThJob> th_jobs;
+  DevBuf<int> th_ints;
+  DevBuf<uint8_t> th_prot;
+  DevBuf<int2> th_items;
+  DevBuf<float4> th_pts;
+  DevBuf<ThRow> th_rows;
+  DevBuf<float> th_pose;
 };
 
 namespace {
@@ -192,6 +203,7 @@ void lm_host_destroy(LmHost* lm) {
   if (lm->vloc_made) vox_destroy(&lm->vloc);
   gv_destroy(&lm->gv);
   lm->mg_pairs.clear(); lm->mg_items.clear(); lm->mg_tail.clear(); lm->mg_moves.clear();
+  lm->th_jobs.clear(); lm->th_ints.clear(); lm->th_prot.clear(); lm->th_items.clear(); lm->th_pts.clear(); lm->th_rows.clear(); lm->th_pose.clear();
   lm->mem.clear();
   delete lm;
 }
@@ -948,6 +960,113 @@ int lm_host_map_merge(LmHost* lm, PgCtx** pc, const int* src, const int* dst, in
   // ---- every ring row that now holds a source frame is transformed and sorted, oldest first
   if (int r = merge_rounds(lm, tail, "map_merge", err)) return r;
   return graph ? graph_append(pc, L, lm->n_slots, edges, st, err) : 0;
+}
+// ---- a slot's archive thinned in place (alego_map_thin / alego_debug_thin_select; kernels_thin.hip) ----
+namespace {
+// th_select for `jobs` (pose, tab, pose_stride, n, slot, r2 set by the caller): the tables are laid out in th_ints / th_prot, the counts of
+// every job come back in cnt[job][4] = N', P', the first dropped id, the point offset there
+int thin_select(LmHost* lm, std::vector<ThJob>& jobs, std::vector<int>* cnt, const char* what, std::string* err) {
+  const size_t nj = jobs.size();
+  size_t ints = 4 * nj, prot = 0;
+  for (const ThJob& J : jobs) { ints += 3 * (size_t)J.n + 1; prot += (size_t)J.n; }
+  if (lm->th_jobs.reserve(nj) != hipSuccess || lm->th_ints.reserve(ints) != hipSuccess || lm->th_prot.reserve(std::max<size_t>(prot, 1)) != hipSuccess) { *err = std::string(what) + ": allocation failed"; return ALEGO_ERR_HIP; }
+  size_t io = 4 * nj, po = 0;
+  for (size_t w = 0; w < nj; ++w) {
+    ThJob& J = jobs[w];
+    J.cnt = lm->th_ints.p + 4 * w;
+    J.new_id = lm->th_ints.p + io; J.old_id = J.new_id + J.n; J.new_off = J.old_id + J.n;
+    J.protect = lm->th_prot.p + po;
+    io += 3 * (size_t)J.n + 1; po += (size_t)J.n;
+  }
+  hipStream_t st = lm->st[0];
+  cnt->assign(4 * nj, 0);
+  if (hipMemcpy(lm->th_jobs.p, jobs.data(), nj * sizeof(ThJob), hipMemcpyHostToDevice) != hipSuccess) { *err = std::string(what) + ": upload failed"; return ALEGO_ERR_HIP; }
+  launch_th_select(lm->L, lm->th_jobs.p, (int)nj, st);
+  if (hipStreamSynchronize(st) != hipSuccess || hipMemcpy(cnt->data(), lm->th_ints.p, 4 * nj * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { *err = std::string(what) + ": the selection failed"; return ALEGO_ERR_HIP; }
+  return 0;
+}
+}  // namespace
+
+int lm_host_map_thin(LmHost* lm, const int* slots, int n, double min_dist, alego_map_thin_result* out, int* first_dropped, std::string* err) {
+  const LmCtx& L = lm->L;
+  const bool graph = L.pg_loops_cap > 0;
+  std::vector<int> arc, pg;
+  if (int r = read_stats(lm, &arc, &pg, "map_thin", err)) return r;
+  std::vector<ThJob> jobs;
+  std::vector<int> who;
+  for (int i = 0; i < n; ++i) {
+    const int* as = arc.data() + (size_t)slots[i] * AS_W;
+    out[i] = alego_map_thin_result{0, as[AS_FRAMES], as[AS_FRAMES], as[AS_POINTS], as[AS_POINTS]};
+    first_dropped[i] = as[AS_FRAMES];
+    if (as[AS_DROPPED]) { out[i].status = -1; continue; }
+    if (as[AS_FRAMES] == 0) continue;
+    out[i].status = 1;
+    ThJob J;
+    std::memset(&J, 0, sizeof(J));
+    J.pose = arc_pose_of(L, slots[i], 0); J.pose_stride = KF_POSE_W; J.tab = arc_tab_of(L, slots[i], 0);
+    J.n = as[AS_FRAMES]; J.slot = slots[i]; J.r2 = th_r2(min_dist);
+    jobs.push_back(J); who.push_back(i);
+  }
+  if (jobs.empty()) return 0;
+  std::vector<int> cnt;
+  if (int r = thin_select(lm, jobs, &cnt, "map_thin", err)) return r;
+  // ---- every size is known now: the slots that drop a frame, their copy items, their places in the staging buffers
+  std::vector<ThJob> go;
+  std::vector<MgPair> ring;
+  std::vector<int2> items;
+  std::vector<int> tail((size_t)lm->n_slots, 0);
+  int rows_max = 0, lanes_max = 1, tail_max = 0, stage_pt = 0, stage_row = 0;
+  for (size_t w = 0; w < jobs.size(); ++w) {
+    ThJob J = jobs[w];
+    const int* c = cnt.data() + 4 * w;
+    if (c[0] == J.n) continue;   // nothing to drop: the slot stays byte-unchanged
+    alego_map_thin_result& o = out[who[w]];
+    o.status = 2; o.frames = c[0]; o.points = c[1];
+    first_dropped[who[w]] = c[2];
+    J.n_new = c[0]; J.p_new = c[1]; J.first = c[2]; J.p0 = c[3];
+    J.n_loops = graph ? pg[(size_t)J.slot * PS_W + PS_LOOPS] : 0;
+    J.stage_pt = stage_pt; J.stage_row = stage_row;
+    stage_pt += J.p_new - J.p0; stage_row += J.n_new - J.first;
+    for (int it = 0; it * MG_ITEM < J.p_new - J.p0; ++it) items.push_back(make_int2((int)go.size(), it));
+    rows_max = std::max(rows_max, J.n_new - J.first); lanes_max = std::max(lanes_max, std::max(J.n_new - J.first, J.n_loops));
+    MgPair P;   // mg_ring reading the slot's own archive: "source" frames 0 .. N' - 1 behind an empty destination
+    std::memset(&P, 0, sizeof(P));
+    P.src = J.slot; P.dst = J.slot; P.ns = J.n_new; P.nd = 0; P.tail = std::min(J.n_new, L.KR);
+    ring.push_back(P);
+    tail[J.slot] = P.tail; tail_max = std::max(tail_max, P.tail);
+    go.push_back(J);
+  }
+  if (go.empty()) return 0;
+  hipStream_t st = lm->st[0];
+  if (lm->th_items.reserve(std::max<size_t>(items.size(), 1)) != hipSuccess || lm->th_pts.reserve(std::max(stage_pt, 1)) != hipSuccess ||
+      lm->th_rows.reserve(std::max(stage_row, 1)) != hipSuccess || lm->mg_pairs.reserve(ring.size()) != hipSuccess) { *err = "map_thin: allocation failed"; return ALEGO_ERR_HIP; }
+  if (hipMemcpy(lm->th_jobs.p, go.data(), go.size() * sizeof(ThJob), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(lm->mg_pairs.p, ring.data(), ring.size() * sizeof(MgPair), hipMemcpyHostToDevice) != hipSuccess ||
+      (!items.empty() && hipMemcpy(lm->th_items.p, items.data(), items.size() * sizeof(int2), hipMemcpyHostToDevice) != hipSuccess)) { *err = "map_thin: upload failed"; return ALEGO_ERR_HIP; }
+  // ---- points and rows through the staging buffers (each read launch ends before its write launch starts), then the ring rows
+  launch_th_gather(L, lm->th_jobs.p, lm->th_items.p, (int)items.size(), lm->th_pts.p, st);
+  launch_th_rows_read(L, lm->th_jobs.p, (int)go.size(), rows_max, lm->th_rows.p, st);
+  launch_th_scatter(L, lm->th_jobs.p, lm->th_items.p, (int)items.size(), lm->th_pts.p, st);
+  launch_th_rows_write(L, lm->th_jobs.p, (int)go.size(), lanes_max, lm->th_rows.p, st);
+  launch_mg_ring(L, lm->mg_pairs.p, (int)ring.size(), tail_max, st);
+  if (hipStreamSynchronize(st) != hipSuccess) { *err = "map_thin: compaction failed"; return ALEGO_ERR_HIP; }
+  return merge_rounds(lm, tail, "map_thin", err);
+}
+
+int lm_host_debug_thin_select(LmHost* lm, const float* keyposes6, const uint8_t* protect, int n, double min_dist, uint8_t* keep, std::string* err) {
+  if (n == 0) return 0;
+  if (lm->th_pose.reserve((size_t)n * 6) != hipSuccess || hipMemcpy(lm->th_pose.p, keyposes6, (size_t)n * 6 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { *err = "debug_thin_select: upload failed"; return ALEGO_ERR_HIP; }
+  std::vector<ThJob> jobs(1);
+  std::memset(&jobs[0], 0, sizeof(ThJob));
+  jobs[0].pose = lm->th_pose.p; jobs[0].pose_stride = 6; jobs[0].n = n; jobs[0].slot = -1; jobs[0].r2 = th_r2(min_dist);
+  // (the tables are laid out first, so that the caller's protect mask can go to its place before the launch)
+  if (lm->th_prot.reserve((size_t)n) != hipSuccess || hipMemcpy(lm->th_prot.p, protect, (size_t)n, hipMemcpyHostToDevice) != hipSuccess) { *err = "debug_thin_select: upload failed"; return ALEGO_ERR_HIP; }
+  std::vector<int> cnt;
+  if (int r = thin_select(lm, jobs, &cnt, "debug_thin_select", err)) return r;
+  std::vector<int> id((size_t)n);
+  if (hipMemcpy(id.data(), jobs[0].new_id, (size_t)n * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { *err = "debug_thin_select: device read failed"; return ALEGO_ERR_HIP; }
+  for (int i = 0; i < n; ++i) keep[i] = id[i] >= 0 ? 1 : 0;
+  return cnt[0];
 }
 int lm_host_map_get_keyframe(LmHost* lm, int slot, int id, alego_keyframe* out, std::string* err) {
   int st[AS_W];

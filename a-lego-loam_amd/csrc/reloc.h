@@ -18,6 +18,8 @@ bool loop_app_enabled(const RlCtx* R);
 int loop_app_run(RlCtx* R, LcCtx** lc, const LmCtx& L, const alego_params& P, const int* slots, int n, const alego_loop_app_opts& o, alego_loop_result* out,
                  alego_loop_app_info* info, hipStream_t st, std::string* err);
 int loop_app_debug_get(RlCtx* R, int slot, const char* name, const void** src, size_t* bytes);   // "la_desc", "la_key"
+// the slot's archive changed from frame `first` on (alego_map_thin): its descriptors stay valid below it, the rest is described again lazily
+void loop_app_forget(RlCtx* R, int slot, int first);
 // alego_map_align: one slot's archive aligned to another's by appearance (needs loop_app_enable); o: n_queries and n_cand resolved
 int map_align_run(RlCtx* R, LcCtx** lc, const LmCtx& L, const alego_params& P, const int* src, const int* dst, int n, const alego_map_align_opts& o, alego_map_align_result* out,
                   alego_map_align_hyp* hyp, hipStream_t st, std::string* err);

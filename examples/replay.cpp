@@ -38,6 +38,10 @@
 //       dst = slot 0) with the alignment's T, its hypotheses as cross edges and a loose seam (variances 0.01 rad^2 / 0.25 m^2), then
 //       alego_graph_optimize with apply = 1 over the union (the key-pose graph is on for both slots).  One line "merge: status S frames F points P
 //       loop_edges L cross_edges X optimise status O poses N loops M iterations I cost C0 -> C"; with --save-map the files hold the union.
+//   either source + --thin DIST
+//       after the run's end (or after --merge) alego_map_thin(slot 0, min_dist = DIST) removes the archived frames that lie closer than DIST
+//       to a frame that stays.  One line "thin: status S frames N -> N' points P -> P'"; with --save-map the files hold the thinned map.
+//       The newest recent_keyframe_num + 1 frames (50 + 1 by default; --recent-keyframes K sets the parameter) are resident and always stay.
 //   either source + --localize [--loc-radius R]
 //       map once, then localise in that map: the run above keeps the archive on; afterwards every archived key frame is pulled with
 //       alego_map_get_keyframe, a SECOND handle is opened, alego_loc_enable hands it those frames, and the same scans are replayed through
@@ -71,10 +75,10 @@ int main(int argc, char** argv) {
   float map_leaf = 0.f;
   int map_frames = 4096, map_points = 1 << 24, loop_every = 0, close_every = 0, max_loops = 16;
   bool list_only = false, standalone = false, localize = false, relocalize = false, appearance = false, merge = false;
-  double loc_radius = 0.0, reloc_range = 0.0, app_max_jump = 0.0, app_range = 0.0, loop_radius = 0.0;
+  double loc_radius = 0.0, reloc_range = 0.0, app_max_jump = 0.0, app_range = 0.0, loop_radius = 0.0, thin_dist = -1.0;
   long reloc_start = -1, align_start = -1;
   long max_scans = -1;
-  int n_scan = 16, horizon = -1;
+  int n_scan = 16, horizon = -1, recent_keyframes = 0;
   std::vector<const char*> pos;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
@@ -99,6 +103,8 @@ int main(int argc, char** argv) {
     else if (a == "--loop-radius") loop_radius = std::atof(val());
     else if (a == "--align") align_start = std::atol(val());
     else if (a == "--merge") merge = true;
+    else if (a == "--thin") thin_dist = std::atof(val());
+    else if (a == "--recent-keyframes") recent_keyframes = std::atoi(val());
     else if (a == "--localize") localize = true;
     else if (a == "--loc-radius") loc_radius = std::atof(val());
     else if (a == "--relocalize") relocalize = true;
@@ -131,6 +137,7 @@ int main(int argc, char** argv) {
   alego_default_params(&P, n_scan, horizon);
   if (standalone) { P.laser_type = ALEGO_LASER_RFANS_16M; P.near_filter = 1; }
   if (loop_radius > 0.0) P.lc_search_radius = loop_radius;
+  if (recent_keyframes > 0) P.recent_keyframe_num = recent_keyframes;
   if (alego_params_sizeof() != (int)sizeof(alego_params)) { std::fprintf(stderr, "header / library mismatch\n"); return 2; }
   const int N = P.n_scan * P.horizon_scan;
   const int cap_in = bag ? (1 << 20) : N;      // a driver may publish more returns than cells; the library takes at most N per scan
@@ -146,7 +153,7 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "alego_create failed (%d): there is no CPU fallback, an MI355X is required\n", rc);
     return 1;
   }
-  if ((!map_dir.empty() || loop_every > 0 || close_every > 0 || localize || align_start >= 0) && alego_map_enable(h, map_frames, map_points) != ALEGO_OK) {
+  if ((!map_dir.empty() || loop_every > 0 || close_every > 0 || localize || align_start >= 0 || thin_dist >= 0.0) && alego_map_enable(h, map_frames, map_points) != ALEGO_OK) {
     std::fprintf(stderr, "map_enable: %s\n", alego_last_error(h)); alego_destroy(h); return 1;
   }
   if (merge && align_start < 0) { std::fprintf(stderr, "--merge needs --align START2\n"); alego_destroy(h); return 2; }
@@ -257,6 +264,13 @@ int main(int argc, char** argv) {
       std::printf("merge: status %d frames %d points %d loop_edges %d cross_edges %d optimise status %d poses %d loops %d iterations %d cost %.9g -> %.9g\n",
                   mr.status, mr.frames, mr.points, mr.loop_edges, mr.cross_edges, gr.status, gr.n_poses, gr.n_loops, gr.iterations, gr.cost0, gr.cost);
     }
+  }
+  if (thin_dist >= 0.0) {   // after the run's end or the merge: frames closer than DIST to a frame that stays leave slot 0's archive (--save-map then writes the thinned map)
+    const int32_t slot = 0;
+    const alego_map_thin_opts to{thin_dist};
+    alego_map_thin_result tr{};
+    if (alego_map_thin(h, &slot, 1, &to, &tr) != ALEGO_OK) { std::fprintf(stderr, "map_thin: %s\n", alego_last_error(h)); alego_destroy(h); return 1; }
+    std::printf("thin: status %d frames %d -> %d points %d -> %d\n", tr.status, tr.frames_before, tr.frames, tr.points_before, tr.points);
   }
   std::string loc_json;
   if (localize) {   // the second half: a fresh handle localises the same scans in the map the first one built

@@ -735,8 +735,8 @@ int alego_map_align_poses(const double T12[12], const float* poses6, int32_t n, 
  * alego_map_merge_edges  host only, plain C++ over csrc/merge_math.h (the arithmetic the kernel runs): the graph part of a merge from plain
  *     arrays.  out_chain[ns]: [0] the seam (prev_pose6 = destination key pose nd - 1, unused for nd == 0; first_pose6 = the first moved pose;
  *     seam_variance6), [f] = src_chain[f] shifted by nd; out_loops[n_loops] = src_loops shifted by nd.
- * Out of scope: continuing the SOURCE's live stream inside the union (its LaserOdometry / LaserMapping state would have to move as well), and
- * removing duplicate frames of the overlap. */
+ * Out of scope: continuing the SOURCE's live stream inside the union (its LaserOdometry / LaserMapping state would have to move as well).
+ * Duplicate frames of the overlap are removed by alego_map_thin (below). */
 #define ALEGO_MERGE_COPY_ITEM 1024   /* points per work item of the archive-to-archive copy: one workgroup copies this many at 16 B per lane and access */
 typedef struct alego_map_merge_opts {
   double stamp_offset;           /* added to every source stamp */
@@ -754,6 +754,53 @@ int alego_map_align_edge(const alego_map_align_hyp* hyp, const float dst_pose6[6
 int alego_map_merge_edges(const alego_graph_edge* src_chain, int32_t ns, const alego_graph_edge* src_loops, int32_t n_loops, int32_t nd,
                           const float prev_pose6[6], const float first_pose6[6], const double seam_variance6[6],
                           alego_graph_edge* out_chain, alego_graph_edge* out_loops);
+
+/* ---- thinning a slot's key-frame archive on the device (needs alego_map_enable) ----------------------------------
+ * A merged archive covers the overlap twice, a long session the same road N times, and an archive that reached max_keyframes or max_points
+ * drops every later frame.  alego_map_thin removes frames that lie closer than min_dist to a frame that stays, in place, for many slots per
+ * call, and gives the room back.  Synchronous; runs behind the work queued on every stream group; its graph part applies only after
+ * alego_graph_enable.  Without a call nothing is allocated or launched.  The rule (the project's own; csrc/thin_math.h states it next to the
+ * code), for a listed slot with N archived frames and none dropped:
+ *   protected   frame 0; the newest min(N, recent_keyframe_num + 1) frames (the resident ring); both endpoints of every stored loop edge.
+ *               A protected frame is always kept.
+ *   selection   frames are visited in id order; an unprotected frame i is DROPPED iff some KEPT frame j < i has the f32 squared distance of
+ *               the key-pose positions ((dx dx) + dy dy) + dz dz < (float)(min_dist * min_dist) - the comparison of alego_loc_select.  Greedy: a
+ *               dropped frame suppresses nobody.  A non-finite position makes every comparison false (kept, suppresses nothing); min_dist <= 0
+ *               drops nothing.  Position only, so device and host agree bit for bit.
+ *   archive     the kept frames k_0 = 0 < k_1 < ... keep pose, stamp and clouds and become frames 0 .. N' - 1; their points are one contiguous
+ *               prefix in id order; alego_map_status says {N', 0, P'}.
+ *   chain       new chain edge m (m - 1 -> m): the f64 product of the old chain measurements k_(m-1) + 1 .. k_m in that order, associated left to
+ *               right; its six variances are the component-wise sums of the composed edges' variances - a FIRST-ORDER rule that ignores how the
+ *               intermediate rotations mix the components.  A measurement stays what was measured: nothing is recomputed from poses.  Edge 0,
+ *               the prior, is unchanged.
+ *   loops       every loop edge keeps measurement and variances; its ids are renumbered (its endpoints are protected, so they exist).
+ *               loop_closed_ stays as it was; the last estimate is discarded (alego_graph_status out[3] becomes 0).
+ *   live slot   alego_lm_keyframe_count becomes N'; the window is reset as by alego_lm_reset_window; the ring holds the newest min(N', K + 1)
+ *               frames under their NEW ids, re-transformed and sorted oldest first - the state of alego_lm_reset_window followed by
+ *               alego_lm_add_keyframe of every kept frame in a fresh slot.  map -> odom, params_, the LaserOdometry state and the trajectory
+ *               are untouched: the stream continues, its next key frame gets id N' and a chain edge from frame N' - 1.
+ *   descriptors the appearance descriptors stay valid below the first dropped frame; the rest is described again lazily.
+ * out[i].status: 2 thinned (frames_before, frames, points_before, points filled); 1 nothing to drop - the slot is byte-unchanged and its
+ * window is not reset; 0 no key frame; -1 the archive dropped frames, untouched.  A slot's result does not depend on the other slots of the
+ * call or their order.  opts == NULL: min_dist 0.  ALEGO_ERR_ARG (nothing written): a localising handle, the archive off, a slot out of range
+ * or listed twice, a min_dist that is not finite.
+ * alego_map_thin_select   host only, plain C++ over csrc/thin_math.h (the arithmetic the kernel runs): keep[n] (1 kept, 0 dropped) for
+ *     keyposes6[n][6] and the protect byte mask (NULL: no frame protected); returns the frames kept.
+ * alego_map_thin_edges    host only: out_chain[N'] and out_loops[n_loops] from a chain of n edges (edge 0 the prior), loop edges and a keep mask
+ *     with keep[0] set; returns N'.  ALEGO_ERR_ARG when an endpoint of a loop edge is dropped or out of range.
+ * alego_debug_thin_select runs the selection kernel alone on arrays of the caller (protect required); returns the frames kept. */
+typedef struct alego_map_thin_opts {
+  double min_dist;               /* m; <= 0: nothing is dropped */
+} alego_map_thin_opts;
+typedef struct alego_map_thin_result {
+  int32_t status;                /* 2 thinned, 1 nothing to drop, 0 no key frame, -1 the archive dropped frames */
+  int32_t frames_before, frames, points_before, points;
+} alego_map_thin_result;
+int alego_map_thin(alego_handle* h, const int32_t* slots, int32_t n, const alego_map_thin_opts* opts, alego_map_thin_result* out);
+int alego_map_thin_select(const float* keyposes6, const uint8_t* protect, int32_t n, double min_dist, uint8_t* keep);
+int alego_map_thin_edges(const alego_graph_edge* chain, int32_t n, const alego_graph_edge* loops, int32_t n_loops, const uint8_t* keep,
+                         alego_graph_edge* out_chain, alego_graph_edge* out_loops);
+int alego_debug_thin_select(alego_handle* h, const float* keyposes6, const uint8_t* protect, int32_t n, double min_dist, uint8_t* keep);
 
 /* ---- one scan-to-map registration sharded over the GPUs of a node (BASELINE.json config 5) ----------------
  * One process per GPU; every rank feeds its handle the SAME scans and so keeps a bit-identical replica of the stream's state
