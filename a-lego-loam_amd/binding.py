@@ -21,7 +21,7 @@ EXPORTS = [
     "alego_create", "alego_destroy", "alego_last_error", "alego_device_count", "alego_params_sizeof",
     "alego_ip_process", "alego_lo_process", "alego_lm_process", "alego_scan_process",
     "alego_batch_load", "alego_batch_run", "alego_synchronize", "alego_batch_get_pose", "alego_batch_get_counts",
-    "alego_stream", "alego_stream_groups", "alego_profile_enable", "alego_profile_report", "alego_set_lo_params", "alego_set_lm_params", "alego_debug_get", "alego_debug_voxel", "alego_debug_atan2f",
+    "alego_stream", "alego_stream_groups", "alego_stream_plan", "alego_profile_enable", "alego_profile_report", "alego_set_lo_params", "alego_set_lm_params", "alego_debug_get", "alego_debug_voxel", "alego_debug_atan2f",
     "alego_lo_push_imu", "alego_lo_get_undistorted", "alego_pose_o2b", "alego_trajectory_enable", "alego_trajectory_get", "alego_debug_check_guards", "alego_debug_math", "alego_debug_std_sort", "alego_debug_eval_blocks", "alego_debug_transform_to_start", "alego_debug_set_option",
     "alego_lm_keyframe_count", "alego_lm_get_keyframe", "alego_lm_set_keypose", "alego_lm_reset_window", "alego_lm_apply_correction",
     "alego_lm_add_keyframe", "alego_pc2_to_points", "alego_replay_create", "alego_replay_load", "alego_replay_assign",
@@ -274,6 +274,8 @@ def lib():
         L.alego_stream.argtypes = [C.c_void_p]
         L.alego_stream_groups.restype = C.c_int
         L.alego_stream_groups.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+        L.alego_stream_plan.restype = C.c_int
+        L.alego_stream_plan.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         L.alego_set_lo_params.restype = C.c_int
         L.alego_set_lo_params.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.alego_set_lm_params.restype = C.c_int
@@ -893,6 +895,12 @@ class Handle:
         per = C.c_int(0)
         g = lib().alego_stream_groups(self._h, C.byref(per))
         return g, per.value
+
+    def stream_plan(self):
+        """alego_stream_plan: dict(groups, slots_per_group, lm_async, hw_queues) — the streams the handle drives and the queue count they were fitted to"""
+        out = (C.c_int * 4)()
+        self._check(lib().alego_stream_plan(self._h, out), "alego_stream_plan")
+        return dict(groups=out[0], slots_per_group=out[1], lm_async=bool(out[2]), hw_queues=out[3])
 
     # ---- test access ----
     def set_lo_params(self, p6, slot=0):

@@ -25,13 +25,15 @@
 #include "pgraph.h"
 #include "prof.h"
 #include "reloc.h"
+#include "stream_plan.h"
 #include "voxel.h"
 
 thread_local Profiler* g_prof = nullptr;
 
-// A handle of several stream groups drives two HIP streams per group (front end + LaserMapping); the HIP runtime maps them onto the
-// process's hardware queues, so streams may share a queue and serialise.  How many queues a process opens is the host's setting
-// (include/alego_mi355x.h) — the library does not touch the environment.
+// A handle drives one HIP stream per stream group and, where the process's hardware queues leave room, a second one per group for
+// LaserMapping; the HIP runtime maps streams onto those queues, and streams that share a queue serialise.  stream_plan.h fits the number of
+// streams to the queues (alego_stream_plan reports the choice).  How many queues a process opens is the host's setting
+// (include/alego_mi355x.h): the library reads GPU_MAX_HW_QUEUES and never writes the environment.
 
 struct alego_handle {
   std::recursive_mutex host_lock;   // alego_handle_lock / alego_handle_unlock: for hosts that drive ONE handle from several threads (the three nodelets)
@@ -64,7 +66,9 @@ struct alego_handle {
   int last_lane = -1;          // lane of the previous scan (LaserOdometry's surf_last_ / corner_last_)
   std::vector<double> imu_last_stamp;   // per slot: stamp of the newest IMU sample (alego_lo_push_imu wants them non-decreasing)
   int next_set = 0;            // lane set the next group of scans uses (the other one still holds the previous scan's features)
-  hipStream_t s_lo = nullptr, s_lm = nullptr;
+  hipStream_t s_lo = nullptr, s_lm = nullptr;   // streams alego_stream_setup created itself (the handle's front and back stream come first)
+  hipStream_t sB = nullptr, sC = nullptr;       // the streams LaserOdometry and LaserMapping of a look-ahead stream run on
+  StreamPlan plan = {1, 1, 0, STREAM_PLAN_DEFAULT_QUEUES};
   std::vector<hipEvent_t> ev_pool;
   size_t ev_next = 0;
   bool map_on = false;         // alego_map_enable: the key-frame archive exists
@@ -112,7 +116,8 @@ int env_int(const char* name, int dflt) { const char* e = getenv(name); return e
 
 // LaserMapping work still in flight on the groups' back streams (alego_batch_run without sync): every entry point that reads or writes
 // LaserOdometry / LaserMapping state waits for it first — per-slot calls for their own group's back stream (check_slot), whole-handle
-// calls (alego_lo_process, alego_lm_process, alego_stream_run, alego_dist_*) for all of them.  alego_batch_load only writes the
+// calls (alego_lo_process, alego_lm_process, alego_dist_*) for all of them; alego_stream_run runs LaserMapping on the back stream itself and
+// orders its streams behind it with events.  A handle without back streams (stream_plan.h) has nothing to wait for.  alego_batch_load only writes the
 // front end's input ring and does not wait (a host-fed batch_load + batch_run(sync = 0) loop keeps its overlap).
 void drain_back(alego_handle* h, int slot = -1) {
   if (slot >= 0 && !h->back.empty()) { (void)hipStreamSynchronize(h->back[std::min<size_t>((size_t)(slot / h->gsize), h->back.size() - 1)]); return; }
@@ -149,6 +154,12 @@ int alego_stream_groups(const alego_handle* h, int* slots_per_group) {
   if (!h) return ALEGO_ERR_ARG;
   if (slots_per_group) *slots_per_group = h->gsize;
   return (int)h->streams.size();
+}
+
+int alego_stream_plan(const alego_handle* h, int out[4]) {
+  if (!h || !out) return ALEGO_ERR_ARG;
+  out[0] = (int)h->streams.size(); out[1] = h->gsize; out[2] = h->lm_async ? 1 : 0; out[3] = h->plan.queues;
+  return 0;
 }
 
 int alego_create(const alego_params* params, int device, int n_slots, int ring_len, alego_handle** out) {
@@ -191,22 +202,19 @@ int alego_create(const alego_params* params, int device, int n_slots, int ring_l
   h->lo_scans.assign(n_slots, 0);
   if (hipSetDevice(device) != hipSuccess) { delete h; return ALEGO_ERR_HIP; }
   {
-    // stream groups: ALEGO_STREAM_GROUPS overrides; default one group per 64 slots, at most 4 (the HIP runtime's hardware queues)
-    int G = n_slots / 64;
-    if (const char* e = getenv("ALEGO_STREAM_GROUPS")) G = atoi(e);
-    if (G > 8) G = 8;
-    if (G > n_slots) G = n_slots;
-    if (G < 1) G = 1;
-    if (!getenv("ALEGO_STREAM_GROUPS") && G > 4) G = 4;
-    h->gsize = (n_slots + G - 1) / G;
-    G = (n_slots + h->gsize - 1) / h->gsize;
+    // stream groups and back streams, fitted to the hardware queues of the process (stream_plan.h); ALEGO_STREAM_GROUPS / ALEGO_LM_ASYNC are explicit requests
+    const char *eg = getenv("ALEGO_STREAM_GROUPS"), *ea = getenv("ALEGO_LM_ASYNC");
+    h->plan = stream_plan(n_slots, stream_plan_queues(getenv("ALEGO_HW_QUEUES"), getenv("GPU_MAX_HW_QUEUES")),
+                          eg ? std::max(atoi(eg), 0) : -1, ea ? (atoi(ea) != 0 ? 1 : 0) : -1);
+    h->gsize = h->plan.gsize;
+    const int G = h->plan.groups;
     for (int g = 0; g < G; ++g) {
       hipStream_t s = nullptr;
       if (hipStreamCreate(&s) != hipSuccess) { for (hipStream_t t : h->streams) hipStreamDestroy(t); delete h; return ALEGO_ERR_HIP; }
       h->streams.push_back(s);
     }
     h->stream = h->streams[0];
-    h->lm_async = env_int("ALEGO_LM_ASYNC", 1) != 0;
+    h->lm_async = h->plan.async != 0;
     if (h->lm_async) {
       for (int g = 0; g < G; ++g) {
         hipStream_t s = nullptr;
@@ -420,7 +428,21 @@ int alego_stream_setup(alego_handle* h, int bag, int start_scan) {
   for (int set = 0; set < 2; ++set)
     for (int j = 0; j < W; ++j)   // lane j of either set processes scan (start + group base + j)
       if (int r = alego_replay_assign(h, 1 + set * W + j, bag, start_scan + j)) return r;
-  if (!h->s_lo && (hipStreamCreate(&h->s_lo) != hipSuccess || hipStreamCreate(&h->s_lm) != hipSuccess)) { h->err = "alego_stream_setup: hipStreamCreate failed"; return ALEGO_ERR_HIP; }
+  {
+    // three chains (ImageProjection + feature extraction ahead, LaserOdometry, LaserMapping) on min(3, Q) streams: the handle's front stream, its
+    // back stream where it has one (LaserMapping stays there), and only what is missing beyond them.  With fewer than three, LaserOdometry and
+    // LaserMapping — one follows the other anyway — share a stream; with one, everything does (the event waits between the chains stay: harmless).
+    std::vector<hipStream_t> pool(1, h->streams[0]);
+    if (!h->back.empty()) pool.push_back(h->back[0]);
+    const size_t want = (size_t)stream_plan_lookahead_streams(h->plan.queues, (int)pool.size());
+    for (hipStream_t* own : {&h->s_lo, &h->s_lm}) {
+      if (pool.size() >= want) break;
+      if (!*own && hipStreamCreate(own) != hipSuccess) { h->err = "alego_stream_setup: hipStreamCreate failed"; return ALEGO_ERR_HIP; }
+      pool.push_back(*own);
+    }
+    if (pool.size() >= 3) { h->sC = h->back.empty() ? pool[2] : pool[1]; h->sB = h->back.empty() ? pool[1] : pool[2]; }
+    else h->sB = h->sC = pool.back();
+  }
   h->stream_mode = true; h->lanes = W; h->pose_slot = 0; h->last_lane = -1; h->next_set = 0;
   return 0;
 }
@@ -429,10 +451,11 @@ int alego_stream_run(alego_handle* h, int first_step, int n_scans, int stages, i
   if (!h) return ALEGO_ERR_ARG;
   if (!h->stream_mode) { h->err = "alego_stream_run: call alego_stream_setup first"; return ALEGO_ERR_ARG; }
   hipSetDevice(h->device);
-  drain_back(h);
+  // (no drain_back: a one-group handle's back stream is sC here, and the three streams start behind each other below — a host wait
+  // would only stall a caller that enqueues run after run with sync = 0)
   g_prof = &h->prof;
   const int W = h->lanes;
-  hipStream_t sA = h->streams[0], sB = h->s_lo, sC = h->s_lm;
+  hipStream_t sA = h->streams[0], sB = h->sB, sC = h->sC;
   auto ev = [&]() -> hipEvent_t {
     if (h->ev_next == h->ev_pool.size()) { hipEvent_t e; (void)hipEventCreateWithFlags(&e, hipEventDisableTiming); h->ev_pool.push_back(e); }
     return h->ev_pool[h->ev_next++];

@@ -132,9 +132,11 @@ int alego_batch_load(alego_handle* h, int slot, int ring_pos, const alego_point*
  * all kernels enqueued on the handle's streams; returns without synchronising when sync == 0.  With sync == 0 LaserMapping of the
  * last scans may still be in flight on the stream groups' second ("back") HIP streams when the call returns: every entry point that
  * touches LaserOdometry / LaserMapping state waits for it first (per-slot calls for their own group, alego_lo_process /
- * alego_lm_process / alego_stream_run / alego_dist_init / alego_dist_shutdown for all groups); alego_batch_load, which only writes the
- * input ring, does not.  A handle of G stream groups drives 2 G HIP streams; the HIP runtime maps them onto the process's hardware
- * queues, and streams that share a queue serialise.  The number of queues is the host's setting; the library never sets it. */
+ * alego_lm_process / alego_dist_init / alego_dist_shutdown for all groups; alego_stream_run orders its streams behind it on the device);
+ * alego_batch_load, which only writes the input ring, does not.  A handle of G stream groups drives G HIP streams, or 2 G where every
+ * group has a back stream; the HIP runtime maps them onto the process's hardware queues, and streams that share a queue serialise.
+ * The number of queues is the host's setting (GPU_MAX_HW_QUEUES; the HIP runtime's default is 4): the library reads it, never sets
+ * it, and fits its streams to it (alego_stream_plan). */
 int alego_batch_run(alego_handle* h, int first_pos, int n_scans, int stages, int sync);
 int alego_synchronize(alego_handle* h);
 /* OR into `stages` of alego_batch_run: replay the resident ring back and forth (0..R-1,R-2..0,1..)
@@ -176,8 +178,15 @@ int alego_batch_get_counts(alego_handle* h, int slot, int32_t* out, int cap);
 void* alego_stream(alego_handle* h);
 /* The slots of a handle are split into contiguous groups, each enqueued on its own HIP stream so that the kernels of
  * different groups overlap (slots never interact).  Returns the number of groups; *slots_per_group (may be NULL) =
- * slots one kernel launch covers.  Default: one group per 64 slots, at most 4; ALEGO_STREAM_GROUPS=<n> overrides. */
+ * slots one kernel launch covers.  Default: one group per 64 slots, at most 4 and no more than the hardware queues of the process
+ * serve (alego_stream_plan); ALEGO_STREAM_GROUPS=<n> overrides. */
 int alego_stream_groups(const alego_handle* h, int* slots_per_group);
+/* The handle's stream plan: out[0] = stream groups, out[1] = slots per group, out[2] = 1 if every group has a back stream (LaserMapping
+ * of scan k overlaps the front end of scans k + 1, k + 2 in alego_batch_run), out[3] = Q, the hardware queues the plan was fitted to:
+ * ALEGO_HW_QUEUES if set, else GPU_MAX_HW_QUEUES, else 4.  What the caller does not ask for (ALEGO_STREAM_GROUPS, ALEGO_LM_ASYNC) is
+ * chosen so that groups x (1 + back stream) <= Q; from Q = 8 on that is 4 groups with a back stream each.  Both variables set are taken
+ * as they are at any Q.  alego_stream_run uses min(3, Q) streams.  Results never depend on the plan. */
+int alego_stream_plan(const alego_handle* h, int out[4]);
 
 /* ---- per-kernel timing (bench.py's roofline leg) --------------------------- */
 /* When enabled every kernel launch of this handle is bracketed by hipEventRecord on the handle's
