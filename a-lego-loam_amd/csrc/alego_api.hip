@@ -262,6 +262,7 @@ int alego_create(const alego_params* params, int device, int n_slots, int ring_l
   d.opt_fo_spin = env_int("ALEGO_FE_SPIN", 0);
   d.opt_fo_pad8 = env_int("ALEGO_FE_PAD8", 0) != 0;
   d.opt_map_merge = env_int("ALEGO_MAP_MERGE", 1) != 0;
+  d.opt_solve_full_eval = env_int("ALEGO_SOLVE_FULL_EVAL", 0) != 0;
   d.fcap[F_SHARP] = d.cap_sharp * d.NS; d.fcap[F_LSHARP] = d.cap_lsharp * d.NS; d.fcap[F_FLAT] = d.cap_flat * d.NS; d.fcap[F_LFLAT] = d.N;
   d.lo_qcap_surf = d.fcap[F_FLAT]; d.lo_qcap_corner = d.fcap[F_SHARP];
   d.lo_box_cap = (d.N + LO_CH - 1) / LO_CH + d.NS;   // boxes never straddle rings: up to one partly filled box per ring
@@ -1028,6 +1029,7 @@ int alego_debug_set_option(alego_handle* h, const char* name, int value) {
   else if (s == "ALEGO_LO_BOX_LDS") d.opt_lo_box_lds = value;
   else if (s == "ALEGO_LO_GRID") d.opt_lo_grid = value != 0;
   else if (s == "ALEGO_FE_SPIN") d.opt_fo_spin = value;
+  else if (s == "ALEGO_SOLVE_FULL_EVAL") d.opt_solve_full_eval = value != 0;
   else if (s == "ALEGO_FE_PAD8") d.opt_fo_pad8 = value != 0;
   else if (s == "ALEGO_FE_ERR_CLEAR") {   // the per-slot reset of the sticky SC_FE_ERR (dev_common.h): value = slot, -1 = every slot; the caller has drained the handle's streams
     if (value < -1 || value >= d.n_slots) return ALEGO_ERR_ARG;

@@ -43,6 +43,7 @@ struct DevCtx {
   int opt_fe_cand;      // ALEGO_FE_CAND    sharp candidates of a ring sector kept in LDS by fe_front (0: by geometry; the tests set 8 to drive the overflow path)
   int opt_lo_box_lds;   // ALEGO_LO_BOX_LDS boxes staged in LDS by lo_assoc (0: straight from HBM)
   int opt_map_merge;    // ALEGO_MAP_MERGE  1: local map from the pre-sorted key frames; 0: concat + radix VoxelGrid
+  int opt_solve_full_eval;   // ALEGO_SOLVE_FULL_EVAL  0: lo_solve_t / lm_solve evaluate a candidate for its cost and the normal equations only where a step is computed from them; 1: every point in full
   // ---- input ring ----
   float4* in_pts;  // [slot][ring][Pcap]
   int* in_n;       // [slot][ring]

@@ -536,8 +536,9 @@ __global__ void __launch_bounds__(LO_BLOCK) lo_assoc(DevCtx d, int box_lds_max) 
   lo_assoc_body<kind, LO_BLOCK, BOXCAP>(d, box_lds_max, blockIdx.x + d.slot0, blockIdx.y, gridDim.y);   // slot fastest: a stream's workgroups share an XCD / L2 (see lm_knn)
 }
 
-// evaluate every valid correspondence row of [row0, row0+n) at pose p
-template <int BLK>
+// evaluate every valid correspondence row of [row0, row0+n) at pose p (FULL = false: the residuals alone, into acc[27])
+// (GENERIC: accumulate_block for every row, as the solver before the split; otherwise the accumulators of the block type's non-zero columns)
+template <int BLK, bool FULL = true, bool GENERIC = true>
 DEV_INLINE void lo_eval_rows(const DevCtx& d, int slot, int kind, int n, const PoseTerms& T, double acc[28]) {
   const int qk = kind == 0 ? F_FLAT : F_SHARP, tk = kind == 0 ? F_LFLAT : F_LSHARP;
   const float4* qpts = feat_of(d, qk, fidx_cur(d, slot));
@@ -550,9 +551,13 @@ DEV_INLINE void lo_eval_rows(const DevCtx& d, int slot, int kind, int n, const P
     const double cp[3] = {pc.x, pc.y, pc.z}, a[3] = {pa.x, pa.y, pa.z}, b[3] = {pb.x, pb.y, pb.z};
     double c[3] = {0, 0, 0};
     if (kind == 0) { const float4 pm = tg[r.w]; c[0] = pm.x; c[1] = pm.y; c[2] = pm.z; }
-    double res, J[6];
-    eval_block(kind == 0 ? BLK_SURF : BLK_CORNER, cp, a, b, c, 0.0, T, &res, J);
-    accumulate_block(res, J, d.P.huber_delta, acc);
+    if constexpr (FULL) {
+      double res, J[6];
+      eval_block(kind == 0 ? BLK_SURF : BLK_CORNER, cp, a, b, c, 0.0, T, &res, J);
+      if constexpr (GENERIC) accumulate_block(res, J, d.P.huber_delta, acc);
+      else if (kind == 0) accumulate_block_cols<COLS_SURF>(res, J, d.P.huber_delta, acc);
+      else accumulate_block_cols<COLS_CORNER>(res, J, d.P.huber_delta, acc);
+    } else accumulate_cost(kind == 0 ? eval_block_residual<BLK_SURF>(cp, a, b, c, 0.0, T) : eval_block_residual<BLK_CORNER>(cp, a, b, c, 0.0, T), d.P.huber_delta, acc[27]);
   }
 }
 
@@ -591,7 +596,7 @@ DEV_INLINE void lo_stage_rows(const DevCtx& d, int slot, int kind, int n, int of
     if (ok) okm |= 1u << k;
   }
 }
-template <int BLK, int kind>
+template <int BLK, int kind, bool FULL = true, bool GENERIC = true>
 DEV_INLINE void lo_eval_staged(int n, int off, const LoRowsLds& R, unsigned okm, const PoseTerms& T, double huber, double acc[28]) {
   int k = 0;
   for (int i = threadIdx.x; i < n; i += BLK, ++k) {
@@ -599,13 +604,18 @@ DEV_INLINE void lo_eval_staged(int n, int off, const LoRowsLds& R, unsigned okm,
     const int j = off + i;
     const double cp[3] = {R.v[0][j], R.v[1][j], R.v[2][j]}, a[3] = {R.v[3][j], R.v[4][j], R.v[5][j]}, b[3] = {R.v[6][j], R.v[7][j], R.v[8][j]};
     const double c[3] = {kind == 0 ? (double)R.v[9][j] : 0.0, kind == 0 ? (double)R.v[10][j] : 0.0, kind == 0 ? (double)R.v[11][j] : 0.0};
-    double res, J[6];
-    eval_block(kind == 0 ? BLK_SURF : BLK_CORNER, cp, a, b, c, 0.0, T, &res, J);
-    accumulate_block(res, J, huber, acc);
+    if constexpr (FULL) {
+      double res, J[6];
+      eval_block(kind == 0 ? BLK_SURF : BLK_CORNER, cp, a, b, c, 0.0, T, &res, J);
+      if constexpr (GENERIC) accumulate_block(res, J, huber, acc);
+      else accumulate_block_cols<kind == 0 ? COLS_SURF : COLS_CORNER>(res, J, huber, acc);
+    } else accumulate_cost(eval_block_residual<kind == 0 ? BLK_SURF : BLK_CORNER>(cp, a, b, c, 0.0, T), huber, acc[27]);
   }
 }
 
-template <int BLK, bool STAGED>   // STAGED: the handle's row capacities fit LO_LDS_ROWS (decided at launch: fixed by the geometry / parameters)
+// Candidates are evaluated for their cost alone and the normal equations only at points a step is computed from, as in lm_solve (kernels_lm.hip);
+// FULL_EVAL: every point in full, the cross-check kernels behind ALEGO_SOLVE_FULL_EVAL=1.
+template <int BLK, bool STAGED, bool FULL_EVAL = false>   // STAGED: the handle's row capacities fit LO_LDS_ROWS (decided at launch: fixed by the geometry / parameters)
 DEV_INLINE void lo_solve_body(const DevCtx& d, int phase, int slot) {
   const int cur = cur_in_flight(d, slot);
   int* sc = scal_of(d, slot);
@@ -660,43 +670,40 @@ DEV_INLINE void lo_solve_body(const DevCtx& d, int phase, int slot) {
       LO_ACC(1);
       // (every thread reads back only what it wrote itself: no barrier needed)
     }
-    auto evaluate = [&](const double* x) {
+    auto evaluate = [&](const double* x, auto full) {
+      constexpr bool FULL = decltype(full)::value;
 #pragma unroll
       for (int k = 0; k < 28; ++k) acc[k] = 0;
       PoseTerms T;
       { LO_T0; T = pose_terms_coop(x, s_trig); LO_ACC(0); }
       { LO_T0;
         if constexpr (STAGED) {
-          lo_eval_staged<BLK, 0>(nq_s, 0, s_rows, oks, T, d.P.huber_delta, acc);
-          if (phase == 1) lo_eval_staged<BLK, 1>(nq_c, nq_s, s_rows, okc, T, d.P.huber_delta, acc);
+          lo_eval_staged<BLK, 0, FULL, FULL_EVAL>(nq_s, 0, s_rows, oks, T, d.P.huber_delta, acc);
+          if (phase == 1) lo_eval_staged<BLK, 1, FULL, FULL_EVAL>(nq_c, nq_s, s_rows, okc, T, d.P.huber_delta, acc);
         } else {
-          lo_eval_rows<BLK>(d, slot, 0, nq_s, T, acc);
-          if (phase == 1) lo_eval_rows<BLK>(d, slot, 1, nq_c, T, acc);
+          lo_eval_rows<BLK, FULL, FULL_EVAL>(d, slot, 0, nq_s, T, acc);
+          if (phase == 1) lo_eval_rows<BLK, FULL, FULL_EVAL>(d, slot, 1, nq_c, T, acc);
         }
         LO_ACC(1); }
-      { LO_T0; block_reduce28_lds<BLK>(acc, s_acc, s_seg, s_out); LO_ACC(2); }
+      { LO_T0;
+        if constexpr (FULL) block_reduce28_lds<BLK>(acc, s_acc, s_seg, s_out); else block_reduce_cost_lds<BLK>(acc[27], s_acc, s_out);
+        LO_ACC(2); }
     };
-    double x0[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) x0[k] = st[LS_PARAMS + k];
-    evaluate(x0);
-    if (threadIdx.x == 0) lm_begin(S, x0, s_out, phase == 0 ? d.P.lo_iters_surf : d.P.lo_iters_corner);
-    __syncthreads();
+    const std::true_type full_eval{};
+    const std::false_type cost_eval{};
+    int kind = LM_EV_BEGIN;
     while (true) {
-      { LO_T0; if (threadIdx.x == 0) s_action = lm_propose(S);
-      __syncthreads(); LO_ACC(3); }
+      double x[6];
+#pragma unroll
+      for (int k = 0; k < 6; ++k) x[k] = kind == LM_EV_BEGIN ? st[LS_PARAMS + k] : kind == LM_EV_JAC ? S.x[k] : S.cand[k];
+      if (kind == LM_EV_CAND_COST) evaluate(x, cost_eval);
+      else evaluate(x, full_eval);
+      { LO_T0;
+        if (threadIdx.x == 0) s_action = lm_control<FULL_EVAL, ALEGO_SOLVE_SPECULATE != 0>(S, kind, st + LS_PARAMS, s_out, phase == 0 ? d.P.lo_iters_surf : d.P.lo_iters_corner);
+        __syncthreads(); LO_ACC(3); }
       const int act = s_action;
       if (act == LM_STOP) break;
-      if (act == LM_EVAL) {
-        double xc[6];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) xc[k] = S.cand[k];
-        evaluate(xc);
-        { LO_T0; if (threadIdx.x == 0) s_action = lm_consume(S, s_out);
-        __syncthreads(); LO_ACC(4); }
-        if (s_action == LM_STOP) break;
-      }
-      __syncthreads();
+      kind = lm_next_eval<FULL_EVAL>(act);   // (an evaluation and its barriers lie between this read of s_action and the next write)
     }
     if (threadIdx.x == 0) {
 #pragma unroll
@@ -744,6 +751,8 @@ DEV_INLINE void lo_solve_body(const DevCtx& d, int phase, int slot) {
 
 template <int BLK, bool STAGED = false>
 __global__ void __launch_bounds__(BLK) lo_solve_t(DevCtx d, int phase) { lo_solve_body<BLK, STAGED>(d, phase, blockIdx.x + d.slot0); }
+template <int BLK, bool STAGED = false>
+__global__ void __launch_bounds__(BLK) lo_solve_full_eval_t(DevCtx d, int phase) { lo_solve_body<BLK, STAGED, true>(d, phase, blockIdx.x + d.slot0); }
 
 // (One stream, alego_stream_run: the four dependent launches of a scan's LaserOdometry were also tried as ONE launch of 48 one-wavefront
 //  workgroups separated by grid barriers on a counter in HBM — bit-identical, and no faster: 5.60 k against 5.66 k scans/s.  The scan's
@@ -786,7 +795,10 @@ void launch_dbg_transform_to_start(const double* params6, const float4* pts, int
 int lo_configure() {
   return (hipFuncSetAttribute(reinterpret_cast<const void*>(lo_solve_t<LO_SOLVE_BLOCK>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LO_SOLVE_LDS_OF(LO_SOLVE_BLOCK)) == hipSuccess &&
           hipFuncSetAttribute(reinterpret_cast<const void*>(lo_solve_t<LO_SOLVE_BLOCK, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LO_SOLVE_LDS_OF(LO_SOLVE_BLOCK)) == hipSuccess &&
-          hipFuncSetAttribute(reinterpret_cast<const void*>(lo_solve_t<LO_SOLVE_WIDE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LO_SOLVE_LDS_OF(LO_SOLVE_WIDE)) == hipSuccess) ? 0 : -1;
+          hipFuncSetAttribute(reinterpret_cast<const void*>(lo_solve_t<LO_SOLVE_WIDE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LO_SOLVE_LDS_OF(LO_SOLVE_WIDE)) == hipSuccess &&
+          hipFuncSetAttribute(reinterpret_cast<const void*>(lo_solve_full_eval_t<LO_SOLVE_BLOCK>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LO_SOLVE_LDS_OF(LO_SOLVE_BLOCK)) == hipSuccess &&
+          hipFuncSetAttribute(reinterpret_cast<const void*>(lo_solve_full_eval_t<LO_SOLVE_BLOCK, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LO_SOLVE_LDS_OF(LO_SOLVE_BLOCK)) == hipSuccess &&
+          hipFuncSetAttribute(reinterpret_cast<const void*>(lo_solve_full_eval_t<LO_SOLVE_WIDE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LO_SOLVE_LDS_OF(LO_SOLVE_WIDE)) == hipSuccess) ? 0 : -1;
 }
 
 // ---- IMU ring + motion de-skew (laserOdometry.cpp:557-726,761-802; dead in the reference: the call at :115 is commented out) ----
@@ -988,7 +1000,12 @@ void launch_lo(const DevCtx& d, hipStream_t st) {
   if (big_boxes) { ALEGO_LAUNCH((lo_assoc<0, LO_BOX_LDS_BIG>), g0, dim3(LO_BLOCK), 0, st, d, box_lds_max); }
   else { ALEGO_LAUNCH(lo_assoc<0>, g0, dim3(LO_BLOCK), 0, st, d, box_lds_max); }
   auto solve = [&](int phase) {
-    if (wide) { ALEGO_LAUNCH(lo_solve_t<LO_SOLVE_WIDE>, dim3(d.n_launch), dim3(LO_SOLVE_WIDE), LO_SOLVE_LDS_OF(LO_SOLVE_WIDE), st, d, phase); }
+    if (d.opt_solve_full_eval) {   // ALEGO_SOLVE_FULL_EVAL=1: every point of the solve evaluated in full (the cross-check of the cost-first default)
+      if (wide) { ALEGO_LAUNCH(lo_solve_full_eval_t<LO_SOLVE_WIDE>, dim3(d.n_launch), dim3(LO_SOLVE_WIDE), LO_SOLVE_LDS_OF(LO_SOLVE_WIDE), st, d, phase); }
+      else if (staged) { ALEGO_LAUNCH((lo_solve_full_eval_t<LO_SOLVE_BLOCK, true>), dim3(d.n_launch), dim3(LO_SOLVE_BLOCK), LO_SOLVE_LDS_OF(LO_SOLVE_BLOCK), st, d, phase); }
+      else { ALEGO_LAUNCH(lo_solve_full_eval_t<LO_SOLVE_BLOCK>, dim3(d.n_launch), dim3(LO_SOLVE_BLOCK), LO_SOLVE_LDS_OF(LO_SOLVE_BLOCK), st, d, phase); }
+    }
+    else if (wide) { ALEGO_LAUNCH(lo_solve_t<LO_SOLVE_WIDE>, dim3(d.n_launch), dim3(LO_SOLVE_WIDE), LO_SOLVE_LDS_OF(LO_SOLVE_WIDE), st, d, phase); }
     else if (staged) { ALEGO_LAUNCH((lo_solve_t<LO_SOLVE_BLOCK, true>), dim3(d.n_launch), dim3(LO_SOLVE_BLOCK), LO_SOLVE_LDS_OF(LO_SOLVE_BLOCK), st, d, phase); }
     else { ALEGO_LAUNCH(lo_solve_t<LO_SOLVE_BLOCK>, dim3(d.n_launch), dim3(LO_SOLVE_BLOCK), LO_SOLVE_LDS_OF(LO_SOLVE_BLOCK), st, d, phase); }
   };

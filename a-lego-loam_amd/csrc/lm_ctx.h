@@ -123,7 +123,7 @@ struct LmCtx {
   // ---- one registration sharded over the ranks of a communicator (alego_dist_*; kernels lm_shard_*) ----
   int shard_rank, shard_world;                    // world 0: not sharded
   double* shard_part;                             // [slot][32] this rank's partial sums of an evaluation: 21 J^T J, 6 J^T r, cost, corner / surf rows; all-reduced in place
-  void* shard_state;                              // [slot] LmState of the solve in flight (dev_cost.h)
+  void* shard_state;                              // [slot] LmState of the solve in flight (solve_rows.h)
   int* shard_ctl;                                 // [slot][8]: 0 local rows, 1 action of the last step, 2 solve finished, 3 outer iteration, 4 guard failed
   unsigned* map_bbox;                             // [slot][2][8] bounding box of the window's points in the VoxelGrid kernels' encoding (vgrid.h; merge path)
   // the same key frames as saveKeyFramesAndFactor stores them (sensor frame, :553-555): host read-back + pose correction

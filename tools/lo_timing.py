@@ -10,6 +10,6 @@ for k in range(24): h.batch_load(0, k, synth.scan(p, k))
 h.batch_run(0, 200, 3 | binding.REPLAY_PINGPONG)
 t = (C.c_longlong * 8)(); binding.lib().alego_lo_times(t); t = np.array(list(t), dtype=np.float64)
 calls = t[7]
-names = ["trig(coop)", "rows", "reduce", "propose+sync", "consume+sync", "store rotation", "kernel total"]
+names = ["trig(coop)", "rows", "reduce", "control+sync", "(unused)", "store rotation", "kernel total"]
 for n, v in zip(names, t[:7]): print(f"{n:16s} {v / 100.0 / calls:8.2f} us per lo_solve call")
 print("calls", int(calls))
