@@ -34,6 +34,7 @@ EXPORTS = [
     "alego_map_get_stamps", "alego_map_set_stamps", "alego_loop_search", "alego_loop_constraint", "alego_debug_nn1",
     "alego_graph_enable", "alego_graph_status", "alego_graph_get_edges", "alego_graph_set_edges", "alego_graph_add_loops", "alego_graph_add_edge",
     "alego_graph_optimize", "alego_graph_get_estimate", "alego_graph_residuals",
+    "alego_graph_marginals", "alego_graph_check_edges", "alego_graph_check_loops", "alego_graph_covariance_host", "alego_graph_check_host",
     "alego_loc_select", "alego_loc_enable", "alego_loc_status",
     "alego_reloc_enable", "alego_loc_relocalize", "alego_reloc_descriptor", "alego_reloc_match", "alego_debug_reloc_search",
     "alego_loop_appearance_enable", "alego_loop_search_appearance", "alego_loop_appearance_candidates",
@@ -186,6 +187,19 @@ class GraphResult(C.Structure):
                 ("cost0", C.c_double), ("cost", C.c_double), ("last_step", C.c_double)]
 
 
+class GraphCovResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_poses", C.c_int32), ("n_loops", C.c_int32), ("pad", C.c_int32)]
+
+
+class GraphCheck(C.Structure):
+    _fields_ = [("status", C.c_int32), ("pad", C.c_int32), ("d2", C.c_double), ("error", C.c_double * 6), ("cov", C.c_double * 36)]
+
+
+def _graph_checks_out(out, n):
+    return [dict(status=int(r.status), d2=float(r.d2), error=np.array(r.error[:], np.float64), cov=np.array(r.cov[:], np.float64).reshape(6, 6)) for r in out[:n]]
+
+
+GRAPH_CHI2_6_999 = 22.457744484825323   # ALEGO_GRAPH_CHI2_6_999
 GRAPH_MAX_LOOPS = 64
 GRAPH_MAX_ITERS, GRAPH_STEP_TOL = 20, 1e-9   # ALEGO_GRAPH_MAX_ITERS, ALEGO_GRAPH_STEP_TOL
 
@@ -202,6 +216,30 @@ def graph_edges(frm, to, between, variance):
         out[i].between[:] = b[i].tolist()
         out[i].variance[:] = v[i].tolist()
     return out
+
+
+def graph_covariance_host(poses12, frm, to, between, variance, pairs=()):
+    """alego_graph_covariance_host (host only): marginals (n_poses, 6, 6) and Sigma_ij (n_pairs, 6, 6) of a graph whose chain edges come first"""
+    X = np.ascontiguousarray(poses12, np.float64).reshape(-1, 12)
+    n = len(np.asarray(frm).reshape(-1))
+    pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    marg, pair = np.zeros((X.shape[0], 36)), np.zeros((max(len(pr), 1), 36))
+    rc = lib().alego_graph_covariance_host(X.ctypes.data, X.shape[0], graph_edges(frm, to, between, variance), n, pr.ctypes.data, len(pr), marg.ctypes.data, pair.ctypes.data)
+    if rc != 0:
+        raise AlegoError(f"alego_graph_covariance_host failed ({rc})")
+    return marg.reshape(-1, 6, 6), pair[:len(pr)].reshape(-1, 6, 6)
+
+
+def graph_check_host(poses12, frm, to, between, variance, cand_frm, cand_to, cand_between, cand_variance):
+    """alego_graph_check_host (host only): one dict (status, d2, error (6,), cov (6, 6)) per candidate edge"""
+    X = np.ascontiguousarray(poses12, np.float64).reshape(-1, 12)
+    n, nc = len(np.asarray(frm).reshape(-1)), len(np.asarray(cand_frm).reshape(-1))
+    out = (GraphCheck * max(nc, 1))()
+    rc = lib().alego_graph_check_host(X.ctypes.data, X.shape[0], graph_edges(frm, to, between, variance), n,
+                                      graph_edges(cand_frm, cand_to, cand_between, cand_variance), nc, out)
+    if rc != 0:
+        raise AlegoError(f"alego_graph_check_host failed ({rc})")
+    return _graph_checks_out(out, nc)
 
 
 def _graph_edges_out(e, n):
@@ -386,6 +424,11 @@ def lib():
         L.alego_graph_optimize.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(GraphOpts), C.POINTER(GraphResult)]
         L.alego_graph_get_estimate.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.c_void_p]
         L.alego_graph_residuals.argtypes = [C.c_void_p, C.c_int32, C.POINTER(GraphEdge), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.alego_graph_marginals.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(GraphCovResult)]
+        L.alego_graph_check_edges.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(GraphEdge), C.POINTER(GraphCheck)]
+        L.alego_graph_check_loops.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(LoopResult), C.POINTER(GraphCheck)]
+        L.alego_graph_covariance_host.argtypes = [C.c_void_p, C.c_int32, C.POINTER(GraphEdge), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        L.alego_graph_check_host.argtypes = [C.c_void_p, C.c_int32, C.POINTER(GraphEdge), C.c_int32, C.POINTER(GraphEdge), C.c_int32, C.POINTER(GraphCheck)]
         L.alego_loc_select.restype = C.c_int
         L.alego_loc_select.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_int32, C.c_void_p]
         L.alego_loc_enable.argtypes = [C.c_void_p, C.POINTER(KfIn), C.c_int32, C.c_double]
@@ -1278,6 +1321,36 @@ class Handle:
         out = np.zeros((max(n, 1), 12), np.float64)
         self._check(lib().alego_graph_get_estimate(self._h, slot, first, n, out.ctypes.data), "alego_graph_get_estimate")
         return out[:n].reshape(n, 3, 4)
+
+    def graph_marginals(self, slots, cap=None):
+        """alego_graph_marginals: (one dict (status, n_poses, n_loops) per listed slot, cov (n, cap, 6, 6)); cap = None: the longest archive listed"""
+        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        if cap is None:
+            cap = max([self.map_status(int(s))[0] for s in sl] + [1])
+        cov = np.zeros((max(sl.shape[0], 1), max(int(cap), 1), 36), np.float64)
+        out = (GraphCovResult * max(sl.shape[0], 1))()
+        self._check(lib().alego_graph_marginals(self._h, sl.ctypes.data, sl.shape[0], int(cap), cov.ctypes.data, out), "alego_graph_marginals")
+        return ([dict(status=int(r.status), n_poses=int(r.n_poses), n_loops=int(r.n_loops)) for r in out[:sl.shape[0]]],
+                cov[:sl.shape[0]].reshape(sl.shape[0], max(int(cap), 1), 6, 6))
+
+    def graph_check_edges(self, slots, frm, to, between, variance):
+        """alego_graph_check_edges: candidate i for slots[i]; one dict (status, d2, error (6,), cov (6, 6)) per candidate"""
+        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        out = (GraphCheck * max(sl.shape[0], 1))()
+        self._check(lib().alego_graph_check_edges(self._h, sl.ctypes.data, sl.shape[0], graph_edges(frm, to, between, variance), out), "alego_graph_check_edges")
+        return _graph_checks_out(out, sl.shape[0])
+
+    def graph_check_loops(self, slots, results):
+        """alego_graph_check_loops: the edge graph_add_loops would append for every dict of loop_search (status == 2; others give status 0)"""
+        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        r = (LoopResult * max(sl.shape[0], 1))()
+        for i, d in enumerate(results):
+            r[i].status, r[i].latest_id, r[i].closest_id = d["status"], d["latest_id"], d["closest_id"]
+            r[i].fitness, r[i].noise_variance = d["fitness"], d["noise_variance"]
+            r[i].between[:] = np.asarray(d["between"], np.float64).reshape(12).tolist()
+        out = (GraphCheck * max(sl.shape[0], 1))()
+        self._check(lib().alego_graph_check_loops(self._h, sl.ctypes.data, sl.shape[0], r, out), "alego_graph_check_loops")
+        return _graph_checks_out(out, sl.shape[0])
 
     def debug_nn1(self, tgt, queries):
         """the grid 1-NN of alego_loop_search alone: (index, f32 squared distance) per query"""

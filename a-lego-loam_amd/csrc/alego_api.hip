@@ -1254,6 +1254,55 @@ int alego_graph_residuals(const double* poses12, int32_t n_poses, const alego_gr
   for (long i = 0; i < (long)n_poses * 12; ++i) if (!std::isfinite(poses12[i])) return ALEGO_ERR_ARG;
   return graph_residuals_host(poses12, n_poses, edges, n_edges, whitened6, jac_from36, jac_to36);
 }
+// marginal covariances and the loop-edge gate: nothing of a slot changes
+int alego_graph_marginals(alego_handle* h, const int32_t* slots, int32_t n, int32_t cap, double* cov36, alego_graph_cov_result* out) {
+  if (int r = graph_ready(h, "alego_graph_marginals")) return r;
+  if (n < 0 || cap <= 0 || (n > 0 && (!slots || !cov36 || !out))) return ALEGO_ERR_ARG;
+  std::vector<char> listed(h->d.n_slots, 0);
+  for (int i = 0; i < n; ++i) {
+    if (slots[i] < 0 || slots[i] >= h->d.n_slots) { h->err = "alego_graph_marginals: slot out of range"; return ALEGO_ERR_ARG; }
+    if (listed[slots[i]]) { h->err = "alego_graph_marginals: a slot is listed twice"; return ALEGO_ERR_ARG; }
+    listed[slots[i]] = 1;
+  }
+  if (n == 0) return 0;
+  HIP_TRY(h, sync_all(h));   // behind everything already queued on every stream group
+  return graph_marginals(&h->pg, *lm_host_ctx(h->lm), h->d.n_slots, slots, n, cap, cov36, out, h->stream, &h->err);
+}
+static int graph_check_common(alego_handle* h, const char* what, const int32_t* slots, int32_t n, const alego_graph_edge* e, const char* active, alego_graph_check* out) {
+  for (int i = 0; i < n; ++i)
+    if (slots[i] < 0 || slots[i] >= h->d.n_slots) { h->err = std::string(what) + ": slot out of range"; return ALEGO_ERR_ARG; }
+  if (n == 0) return 0;
+  HIP_TRY(h, sync_all(h));
+  return graph_check(&h->pg, *lm_host_ctx(h->lm), h->d.n_slots, slots, n, e, active, out, h->stream, &h->err);
+}
+int alego_graph_check_edges(alego_handle* h, const int32_t* slots, int32_t n, const alego_graph_edge* e, alego_graph_check* out) {
+  if (int r = graph_ready(h, "alego_graph_check_edges")) return r;
+  if (n < 0 || (n > 0 && (!slots || !e || !out))) return ALEGO_ERR_ARG;
+  return graph_check_common(h, "alego_graph_check_edges", slots, n, e, nullptr, out);
+}
+int alego_graph_check_loops(alego_handle* h, const int32_t* slots, int32_t n, const alego_loop_result* r, alego_graph_check* out) {
+  if (int rc = graph_ready(h, "alego_graph_check_loops")) return rc;
+  if (n < 0 || (n > 0 && (!slots || !r || !out))) return ALEGO_ERR_ARG;
+  std::vector<alego_graph_edge> e(std::max(n, 1));
+  std::vector<char> active(std::max(n, 1), 0);
+  for (int i = 0; i < n; ++i) {
+    std::memset(&e[i], 0, sizeof(e[i]));
+    if (r[i].status != 2) continue;
+    active[i] = 1;
+    e[i].from = r[i].latest_id; e[i].to = r[i].closest_id;
+    std::memcpy(e[i].between, r[i].between, sizeof(e[i].between));
+    for (int k = 0; k < 6; ++k) e[i].variance[k] = r[i].noise_variance;
+  }
+  return graph_check_common(h, "alego_graph_check_loops", slots, n, e.data(), active.data(), out);
+}
+int alego_graph_covariance_host(const double* poses12, int32_t n_poses, const alego_graph_edge* edges, int32_t n_edges, const int32_t* pairs, int32_t n_pairs,
+                                double* marg36, double* pair36) {
+  return graph_covariance_host(poses12, n_poses, edges, n_edges, pairs, n_pairs, marg36, pair36);
+}
+int alego_graph_check_host(const double* poses12, int32_t n_poses, const alego_graph_edge* edges, int32_t n_edges, const alego_graph_edge* cand, int32_t n_cand,
+                           alego_graph_check* out) {
+  return graph_check_host(poses12, n_poses, edges, n_edges, cand, n_cand, out);
+}
 
 // ---- one registration sharded over the GPUs of a node ---------------------------------------------------------------
 int alego_dist_unique_id(char id[ALEGO_DIST_ID_BYTES]) { return id ? lm_host_dist_unique_id(id) : ALEGO_ERR_ARG; }

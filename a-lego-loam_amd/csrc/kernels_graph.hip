@@ -30,32 +30,9 @@
 #include "dev_mem.h"
 #include "kf_store.h"
 #include "pg_math.h"
+#include "pg_work.h"
 #include "pgraph.h"
 #include "prof.h"
-
-#define PG_T 256                       // workgroup of the per-edge / per-node / per-slot-reduction kernels
-#define PG_SOLVE_MAX 448               // lanes of pg_solve: 1 + 6 * ALEGO_GRAPH_MAX_LOOPS right-hand sides, rounded up to wavefronts
-#define PG_BUDGET_DEFAULT (1LL << 30)  // bytes of chunk scratch
-static_assert(1 + 6 * ALEGO_GRAPH_MAX_LOOPS <= PG_SOLVE_MAX, "pg_solve sweeps one right-hand side per lane");
-
-enum { PC_STATUS = 0, PC_ITERS, PC_DONE, PC_N, PC_NL, PC_SLOT, PC_COUNT = 8 };   // int control words of a chunk entry
-enum { PD_COST0 = 0, PD_COST, PD_STEP, PD_COUNT = 4 };                            // double control words
-
-// the scratch of one chunk entry q lives at fixed strides (Nmax poses, Lmax loop edges, R = 1 + 6 Lmax right-hand sides)
-struct PgWork {
-  int S, Nmax, Lmax, R;
-  int* ctl;        // [S][PC_COUNT]
-  double* dctl;    // [S][PD_COUNT]
-  double* X;       // [S][Nmax][12]
-  double* res;     // [S][Nmax + Lmax][6]     edge e < Nmax: chain edge e (the prior is edge 0); Nmax + l: loop edge l
-  double* Jf;      // [S][Nmax + Lmax][36]
-  double* Jt;      // [S][Nmax + Lmax][36]
-  double* Td;      // [S][Nmax][36]  diagonal blocks of T, then L_kk
-  double* To;      // [S][Nmax][36]  T_{k+1,k}, then L_{k+1,k}
-  double* g;       // [S][Nmax][6]   gradient, then delta
-  double* Z;       // [S][Nmax][6][R]
-  double* C;       // [S][6 Lmax][6 Lmax]
-};
 
 DEV_INLINE const alego_graph_edge* pg_edge_of(const LmCtx& L, int slot, int Nmax, int e) {
   return e < Nmax ? L.pg_chain + arc_row(L, slot, e) : L.pg_loops + (size_t)slot * L.pg_loops_cap + (e - Nmax);
@@ -184,26 +161,6 @@ __global__ void __launch_bounds__(64) pg_factor_chain(PgWork W) {
         for (int j = 0; j < 6; ++j) a -= Lo[r * 6 + j] * Lo[c * 6 + j];
         D[r * 6 + c] = a;
       }
-  }
-}
-
-// y <- L_kk^-1 y (forward) / L_kk^-T y (backward) for one 6-vector
-DEV_INLINE void pg_lsolve(const double* Lk, double* y) {
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    double a = y[i];
-#pragma unroll
-    for (int j = 0; j < i; ++j) a -= Lk[i * 6 + j] * y[j];
-    y[i] = a / Lk[i * 6 + i];
-  }
-}
-DEV_INLINE void pg_ltsolve(const double* Lk, double* y) {
-#pragma unroll
-  for (int i = 5; i >= 0; --i) {
-    double a = y[i];
-#pragma unroll
-    for (int j = i + 1; j < 6; ++j) a -= Lk[j * 6 + i] * y[j];
-    y[i] = a / Lk[i * 6 + i];
   }
 }
 
@@ -453,6 +410,14 @@ __global__ void pg_sorted(LmCtx L, const int* apply, int slot0, int n, int all) 
   if (apply[slot0 + s]) li[LI_UVALID] = 0;
 }
 
+void launch_pg_linear_pass(const LmCtx& L, const PgWork& W, hipStream_t st) {
+  const dim3 gn((W.Nmax + PG_T - 1) / PG_T, W.S), ge((W.Nmax + W.Lmax + PG_T - 1) / PG_T, W.S);
+  ALEGO_LAUNCH(pg_init, gn, dim3(PG_T), 0, st, L, W);
+  ALEGO_LAUNCH(pg_linearize, ge, dim3(PG_T), 0, st, L, W, 0);
+  ALEGO_LAUNCH(pg_assemble, gn, dim3(PG_T), 0, st, L, W);
+  ALEGO_LAUNCH(pg_factor_chain, dim3((W.S + 63) / 64), dim3(64), 0, st, W);
+  ALEGO_LAUNCH(pg_solve, dim3(W.S), dim3(std::max(64, (W.R + 63) / 64 * 64)), 0, st, L, W);
+}
 void launch_pg_apply(const LmCtx& L, const int* apply_dev, int n_slots, hipStream_t st) {
   ALEGO_LAUNCH(pg_apply, dim3(n_slots), dim3(PG_T), 0, st, L, apply_dev);
 }
@@ -476,12 +441,6 @@ __global__ void pg_append(LmCtx L, const PgAppend* a, int n) {
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------
-struct PgCtx {
-  long long budget = PG_BUDGET_DEFAULT;
-  DevBuf<char> buf;          // chunk scratch (pg_layout)
-  DevBuf<int> apply;         // [n_slots]
-  DevBuf<PgAppend> stage;    // loop edges on their way to pg_append
-};
 void graph_ctx_destroy(PgCtx* C) {
   if (!C) return;
   C->buf.clear(); C->apply.clear(); C->stage.clear();
@@ -493,39 +452,10 @@ void graph_ctx_set_budget(PgCtx** pc, long long bytes) {
 }
 
 namespace {
-size_t pg_align(size_t b) { return (b + 255) & ~(size_t)255; }
-// bytes of a chunk of S entries; with base != nullptr the pointers are laid out too
-size_t pg_layout(PgWork* W, char* base, int S, int Nmax, int Lmax) {
-  size_t o = 0;
-  const size_t s = (size_t)S, N = (size_t)Nmax, E = (size_t)Nmax + Lmax, R = 1 + 6 * (size_t)Lmax;
-  auto take = [&](auto** p, size_t count) {
-    using T = std::remove_pointer_t<std::remove_pointer_t<decltype(p)>>;
-    if (base) *p = (T*)(base + o);
-    o += pg_align(count * sizeof(T));
-  };
-  W->S = S; W->Nmax = Nmax; W->Lmax = Lmax; W->R = (int)R;
-  take(&W->ctl, s * PC_COUNT); take(&W->dctl, s * PD_COUNT); take(&W->X, s * N * 12);
-  take(&W->res, s * E * 6); take(&W->Jf, s * E * 36); take(&W->Jt, s * E * 36);
-  take(&W->Td, s * N * 36); take(&W->To, s * N * 36); take(&W->g, s * N * 6);
-  take(&W->Z, s * N * 6 * R); take(&W->C, s * 36 * (size_t)Lmax * Lmax);
-  return o;
-}
-bool pg_finite_edge(const alego_graph_edge& e) {
-  for (int k = 0; k < 12; ++k) if (!std::isfinite(e.between[k])) return false;
-  for (int k = 0; k < 6; ++k) if (!(e.variance[k] > 0.0) || !std::isfinite(e.variance[k])) return false;
-  return true;
-}
-int pg_fail(std::string* err, const char* msg, int rc) { *err = msg; return rc; }
 // the counters of one slot: arc4 = LmCtx::arc_stat, pg4 = LmCtx::pg_stat
 int pg_read_slot(const LmCtx& L, int slot, int* arc4, int* pg4, std::string* err) {
   if (hipMemcpy(arc4, arc_stat_of(L, slot), AS_W * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
       hipMemcpy(pg4, pg_stat_of(L, slot), PS_W * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return pg_fail(err, "graph: device read failed", ALEGO_ERR_HIP);
-  return 0;
-}
-int pg_read_stats(const LmCtx& L, int n_slots, std::vector<int>* arc, std::vector<int>* pg, std::string* err) {
-  arc->resize((size_t)n_slots * AS_W); pg->resize((size_t)n_slots * PS_W);
-  if (hipMemcpy(arc->data(), L.arc_stat, arc->size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
-      hipMemcpy(pg->data(), L.pg_stat, pg->size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return pg_fail(err, "graph: device read failed", ALEGO_ERR_HIP);
   return 0;
 }
 }  // namespace

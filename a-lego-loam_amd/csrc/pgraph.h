@@ -30,4 +30,12 @@ void launch_pg_apply(const LmCtx& L, const int* apply_dev, int n_slots, hipStrea
 void launch_pg_retransform(const LmCtx& L, const int* apply_dev, int slot0, int n, int j, hipStream_t st);
 void launch_pg_sorted(const LmCtx& L, const int* apply_dev, int slot0, int n, int all, hipStream_t st);
 int graph_residuals_host(const double* poses12, int n_poses, const alego_graph_edge* edges, int n_edges, double* whitened6, double* jac_from36, double* jac_to36);
+// marginal covariances and the consistency of candidate edges (kernels_pgcov.hip).  graph_check: active[i] == 0 (active
+// may be null) leaves candidate i unjudged with status 0
+int graph_marginals(PgCtx** pc, const LmCtx& L, int n_slots, const int* slots, int n, int cap, double* cov36, alego_graph_cov_result* out, hipStream_t st,
+                    std::string* err);
+int graph_check(PgCtx** pc, const LmCtx& L, int n_slots, const int* slots, int n, const alego_graph_edge* e, const char* active, alego_graph_check* out,
+                hipStream_t st, std::string* err);
+int graph_covariance_host(const double* poses12, int n_poses, const alego_graph_edge* edges, int n_edges, const int* pairs, int n_pairs, double* marg36, double* pair36);
+int graph_check_host(const double* poses12, int n_poses, const alego_graph_edge* edges, int n_edges, const alego_graph_edge* cand, int n_cand, alego_graph_check* out);
 #endif

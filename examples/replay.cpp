@@ -17,6 +17,11 @@
 //       keeps the archive on too and calls alego_loop_search every EVERY scans (performLoopClosure, laserMapping.cpp:652-733, on the
 //       device); every accepted constraint prints one line "loop: scan K slot S latest L closest C fitness F".  A host with a pose
 //       graph would add the Between factor here and write the corrected poses back.
+//   --loop-search EVERY + --gate CHI2 [--max-loops N]
+//       the key-pose graph is on as well, and every found constraint is judged before it is added: alego_graph_check_loops gives the squared
+//       Mahalanobis distance d2 of the edge against the covariance the graph predicts; one line "gate: scan K slot S
+//       d2 D accepted A" follows the "loop:" line, and only an edge with d2 <= CHI2 goes to alego_graph_add_loops (ALEGO_GRAPH_CHI2_6_999 =
+//       22.46 is the 0.999 quantile for 6 degrees of freedom).  Nothing is optimised or applied.
 //   either source + --close-loops EVERY [--max-loops N]
 //       the whole loop closure on the device: the key-pose graph next to the archive (alego_graph_enable), and every EVERY scans
 //       alego_loop_search -> alego_graph_add_loops -> alego_graph_optimize with apply = 1 (correctPoses, :561-584).  Every applied
@@ -75,7 +80,7 @@ int main(int argc, char** argv) {
   float map_leaf = 0.f;
   int map_frames = 4096, map_points = 1 << 24, loop_every = 0, close_every = 0, max_loops = 16;
   bool list_only = false, standalone = false, localize = false, relocalize = false, appearance = false, merge = false;
-  double loc_radius = 0.0, reloc_range = 0.0, app_max_jump = 0.0, app_range = 0.0, loop_radius = 0.0, thin_dist = -1.0;
+  double gate_chi2 = -1.0, loc_radius = 0.0, reloc_range = 0.0, app_max_jump = 0.0, app_range = 0.0, loop_radius = 0.0, thin_dist = -1.0;
   long reloc_start = -1, align_start = -1;
   long max_scans = -1;
   int n_scan = 16, horizon = -1, recent_keyframes = 0;
@@ -95,6 +100,7 @@ int main(int argc, char** argv) {
     else if (a == "--map-frames") map_frames = std::atoi(val());
     else if (a == "--map-points") map_points = std::atoi(val());
     else if (a == "--loop-search") loop_every = std::atoi(val());
+    else if (a == "--gate") gate_chi2 = std::atof(val());
     else if (a == "--close-loops") close_every = std::atoi(val());
     else if (a == "--max-loops") max_loops = std::atoi(val());
     else if (a == "--appearance") appearance = true;
@@ -157,7 +163,8 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "map_enable: %s\n", alego_last_error(h)); alego_destroy(h); return 1;
   }
   if (merge && align_start < 0) { std::fprintf(stderr, "--merge needs --align START2\n"); alego_destroy(h); return 2; }
-  if ((close_every > 0 || merge) && alego_graph_enable(h, merge ? std::max(max_loops, ALEGO_ALIGN_MAX_QUERIES) : max_loops, nullptr) != ALEGO_OK) {
+  if (gate_chi2 >= 0.0 && loop_every <= 0) { std::fprintf(stderr, "--gate needs --loop-search EVERY\n"); alego_destroy(h); return 2; }
+  if ((close_every > 0 || merge || gate_chi2 >= 0.0) && alego_graph_enable(h, merge ? std::max(max_loops, ALEGO_ALIGN_MAX_QUERIES) : max_loops, nullptr) != ALEGO_OK) {
     std::fprintf(stderr, "graph_enable: %s\n", alego_last_error(h)); alego_destroy(h); return 1;
   }
   if (((appearance && (loop_every > 0 || close_every > 0)) || align_start >= 0) && alego_loop_appearance_enable(h, app_range, 0.0 / 0.0) != ALEGO_OK) {
@@ -230,6 +237,13 @@ int main(int argc, char** argv) {
       std::string app;
       if (find_loop(slot, &lr, &app) != ALEGO_OK) { std::fprintf(stderr, "loop_search: %s\n", alego_last_error(h)); alego_destroy(h); return 1; }
       if (lr.status == 2) std::printf("loop: scan %ld slot %d latest %d closest %d fitness %.9g%s\n", k, slot, lr.latest_id, lr.closest_id, lr.fitness, app.c_str());
+      if (lr.status == 2 && gate_chi2 >= 0.0) {   // judge the edge against the graph as it stands; add it only when it is believable
+        alego_graph_check gc{};
+        if (alego_graph_check_loops(h, &slot, 1, &lr, &gc) != ALEGO_OK) { std::fprintf(stderr, "graph_check_loops: %s\n", alego_last_error(h)); alego_destroy(h); return 1; }
+        const bool accepted = gc.status == 1 && gc.d2 <= gate_chi2;
+        std::printf("gate: scan %ld slot %d d2 %.9g accepted %d\n", k, slot, gc.d2, accepted ? 1 : 0);
+        if (accepted && alego_graph_add_loops(h, &slot, 1, &lr) != ALEGO_OK) { std::fprintf(stderr, "graph_add_loops: %s\n", alego_last_error(h)); alego_destroy(h); return 1; }
+      }
     }
     if (close_every > 0 && (k + 1) % close_every == 0) {   // search -> add the Between factor -> optimise and correct, all on the device
       const int32_t slot = 0;

@@ -478,6 +478,44 @@ int alego_graph_get_estimate(alego_handle* h, int slot, int32_t first, int32_t n
 int alego_graph_residuals(const double* poses12, int32_t n_poses, const alego_graph_edge* edges, int32_t n_edges,
                           double* whitened6, double* jac_from36, double* jac_to36);
 
+/* ---- marginal covariances of the key-pose graph and a gate for candidate loop edges (what gtsam::Marginals gives a
+ * GTSAM user).  Linearisation point: the slot's archived key poses as they stand now, as Pose3 — where alego_graph_optimize starts; after an
+ * optimise with apply = 1 that is the optimum to f32 rounding.  Covariances are GTSAM's: tangent space of the pose, right perturbation
+ * (x <- x Expmap(delta)), rotation first; row-major 6x6, symmetric to the last bit.
+ * The device calls are synchronous, run behind the work queued on every stream group (as alego_graph_optimize) and change nothing of a slot:
+ * poses, estimate, loop_closed_ and edges all stay; nothing is kept on the device.  A slot's outputs do not depend on the other slots of the
+ * call, their order or the chunking.  ALEGO_ERR_ARG with the graph off (so on a localising handle too).  Without a call nothing is allocated
+ * or launched.
+ * Gate: for a candidate from -> to with measurement and variances, d2 = e^T P^-1 e with e the unwhitened error Logmap(measured^-1 (x_from^-1
+ * x_to)) and P = the covariance of e the graph predicts + diag(variance); compare d2 with a chi-square quantile of 6 degrees of freedom.
+ * NOTE on noise: with the default odometry variances (1e-6 / 1e-8) the graph claims millimetres of drift over a lap and the gate refuses every
+ * real loop; a host that gates passes honest odometry variances to alego_graph_enable. */
+#define ALEGO_GRAPH_CHI2_6_999 22.457744484825323   /* chi-square, 6 dof, 0.999 */
+typedef struct alego_graph_cov_result { int32_t status, n_poses, n_loops, pad; } alego_graph_cov_result;
+   /* status: 1 computed, 0 no key frame, -1 the archive dropped frames, -2 not finite */
+/* cov36: [n][cap][36] row-major, poses 0 .. min(n_poses, cap) - 1 of slots[i] (the rest of a slot's rows is left as it was).
+ * ALEGO_ERR_ARG: a slot out of range or listed twice, cap <= 0, a null argument. */
+int alego_graph_marginals(alego_handle* h, const int32_t* slots, int32_t n, int32_t cap, double* cov36, alego_graph_cov_result* out);
+typedef struct alego_graph_check {
+  int32_t status, pad;     /* 1 computed, 0 not judged (alego_graph_check_loops: r[i].status != 2), -1 the archive dropped frames, -2 P not finite or
+                              not positive definite (d2 = 0) */
+  double d2;               /* squared Mahalanobis distance */
+  double error[6];         /* e, rotation first */
+  double cov[36];          /* P */
+} alego_graph_check;
+/* candidate e[i] for slots[i]; a slot may be listed several times (at most ALEGO_GRAPH_MAX_LOOPS candidates per slot and call, else
+ * ALEGO_ERR_CAPACITY); every candidate is judged against the same graph, independently of the others.  Same argument errors as alego_graph_add_edge. */
+int alego_graph_check_edges(alego_handle* h, const int32_t* slots, int32_t n, const alego_graph_edge* e, alego_graph_check* out);
+/* the edge alego_graph_add_loops would append for r[i] (status == 2; others give status 0) */
+int alego_graph_check_loops(alego_handle* h, const int32_t* slots, int32_t n, const alego_loop_result* r, alego_graph_check* out);
+/* host only, the same arithmetic (csrc/pg_cov_math.h): marginals [n_poses][36] and, for pairs[n_pairs][2] = (i, j), Sigma_ij [n_pairs][36] (rows of
+ * node i, columns of node j); edges: the n_poses chain edges first (edge 0 the prior, edge k: k - 1 -> k), then the loop edges; any output may be
+ * NULL.  ALEGO_ERR_ARG: a null input, a malformed edge list, ids out of range, from == to, a variance not positive and finite, values not finite. */
+int alego_graph_covariance_host(const double* poses12, int32_t n_poses, const alego_graph_edge* edges, int32_t n_edges,
+                                const int32_t* pairs, int32_t n_pairs, double* marg36, double* pair36);
+int alego_graph_check_host(const double* poses12, int32_t n_poses, const alego_graph_edge* edges, int32_t n_edges,
+                           const alego_graph_edge* cand, int32_t n_cand, alego_graph_check* out);
+
 /* ---- localisation: many streams against ONE frozen key-frame map -------------------------------------
  * A handle-wide mode, off by default (nothing of it is allocated or launched then).  alego_loc_enable hands the handle N key frames — pose
  * and sensor-frame clouds, exactly what alego_map_get_keyframe returns from a mapping run; from then on EVERY slot localises in that map.
