@@ -173,8 +173,12 @@ __global__ void __launch_bounds__(MU_T) map_update(DevCtx d, LmCtx L, MapWork W)
     // A window that passes through keeps no voxel list: its map is the raw concatenation, and one of its runs may be a key frame that was
     // itself too large for a voxel id (stored unsorted by the VoxelGrid sort, voxel.h) — the merges below would read it as sorted.  U is
     // rebuilt from the window's runs by the next window that is filtered (LI_UVALID is cleared below when a map passed).
+    // A window that is filtered but has a voxel outside the key's 21 bits per axis (vgrid.h) cannot be merged by key: vkey_pack would put every cell
+    // beyond the range onto the last one and their voxels would come out as one, silently.  It is refused instead: no list, no map, LI_OVERFLOW 8
+    // (the host reports it), and its U is stale like that of a window that passed through.
+    const bool far = kraw > 0 && !pass && !vkey_holds_box(mn, mx, inv);
     int nU = 0;
-    if (!pass) {
+    if (!pass && !far) {
       {
         // the two windows into LDS (s_add / s_rem double as staging), then their multiset difference by one thread:
         // both are non-decreasing lists of frame ids
@@ -378,7 +382,9 @@ __global__ void __launch_bounds__(MU_T) map_update(DevCtx d, LmCtx L, MapWork W)
       li[LI_KRAW_C + m] = kraw;
       li[LI_KDS_C + m] = pass ? min(kraw, cap) : nU;
       if (pass) atomicOr(&li[LI_MAP_PASS], 1 << m); else atomicAnd(&li[LI_MAP_PASS], ~(1 << m));
-      if (!pass && s_err) li[LI_OVERFLOW] = s_err == 2 ? 1 : 4;   // 4: voxel list out of sync with the window (internal error)
+      if (far) atomicOr(&li[LI_MAP_PASS], 4 << m); else atomicAnd(&li[LI_MAP_PASS], ~(4 << m));
+      if (far) li[LI_OVERFLOW] = 8;   // 8: the window does not fit the voxel key
+      else if (!pass && s_err) li[LI_OVERFLOW] = s_err == 2 ? 1 : 4;   // 4: voxel list out of sync with the window (internal error)
       unsigned* bb = L.map_bbox + ((size_t)slot * 2 + m) * 8;
       for (int a = 0; a < 3; ++a) { bb[a] = vgr_enc(mn[a]); bb[4 + a] = ~vgr_enc(mx[a]); }
     }
@@ -410,7 +416,7 @@ __global__ void __launch_bounds__(MU_T) map_update(DevCtx d, LmCtx L, MapWork W)
         int* prev = L.rec_prev + (size_t)(s + d.slot0) * L.K;
         const int nc = l2[LI_REC_CNT];
         for (int j = 0; j < nc; ++j) prev[j] = rec[j];
-        l2[LI_PREV_CNT] = nc; l2[LI_UVALID] = l2[LI_MAP_PASS] == 0;   // (a map that passed through left its U stale)
+        l2[LI_PREV_CNT] = nc; l2[LI_UVALID] = l2[LI_MAP_PASS] == 0;   // (a map that passed through or was refused left its U stale)
       }
     }
     int tot;

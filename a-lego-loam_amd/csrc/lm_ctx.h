@@ -18,7 +18,7 @@ enum {
   LI_NCUR_C, LI_NCUR_S, LI_NCUR_O,       // laser_corner_ds_, laser_surf_ds_, laser_outlier_ds_
   LI_NTOTAL, LI_NTOTAL_DS,               // laser_surf_total_, laser_surf_total_ds_
   LI_NREBUILD,     // map rebuilds so far (bench: expected work of the map VoxelGrid kernels)
-  LI_OVERFLOW,     // a capacity was exceeded (clouds truncated): reported as an error by the host
+  LI_OVERFLOW,     // a capacity was exceeded (1: clouds truncated, 8: a window beyond the voxel-key range) or an internal check failed (2, 4): reported as an error by the host
   LI_REC_CNT,      // recent_*_keyframes_.size() (laserMapping.cpp:208)
   LI_LATEST,       // latest_frame_id_ (laserMapping.cpp:226), -1 until the deque has been full once
   LI_NU_C, LI_NU_S,      // occupied voxels of the corner / surf local map (size of the sorted voxel-key lists U)
@@ -28,7 +28,8 @@ enum {
   LI_KF_PEND_RING,
   LI_TMPN_C, LI_TMPN_S,  // points in kf_tmp_c / kf_tmp_s
   LI_REBUILD_FB,   // LI_REBUILD on the concat + radix VoxelGrid path (ALEGO_MAP_MERGE=0)
-  LI_MAP_PASS,     // bit m: map m took PCL's "leaf size too small" path in map_update (output = input), map_accum skips it
+  LI_MAP_PASS,     // bit m: map m took PCL's "leaf size too small" path in map_update (output = input), map_accum skips it;
+                   // bit 2 + m: map m was refused because its window does not fit the voxel key (LI_OVERFLOW 8, no list and no map)
   LI_SORT_N,       // (2 entries) point counts written by the key-frame sort jobs
   LI_SORT_N1,
   LI_COUNT = 48

@@ -348,7 +348,9 @@ int lm_host_process_host(LmHost* lm, const DevCtx& dfull, const alego_point* cor
   if (li[LI_OVERFLOW]) {   // reported by the call that caused it, then cleared
     const int zero = 0;
     (void)hipMemcpy(L.li + LI_OVERFLOW, &zero, sizeof(int), hipMemcpyHostToDevice);
-    *err = li[LI_OVERFLOW] == 2 ? "alego_lm_process: launch logic out of sync" : "alego_lm_process: device capacity exceeded (cloud truncated)";
+    *err = li[LI_OVERFLOW] == 2 ? "alego_lm_process: launch logic out of sync"
+         : li[LI_OVERFLOW] == 8 ? "alego_lm_process: the key-frame window has a point outside the voxel-key range of -2^20 .. 2^20 - 1 leaves per axis (no local map was built)"
+                                : "alego_lm_process: device capacity exceeded (cloud truncated)";
     return ALEGO_ERR_CAPACITY;
   }
   if (map_pose) {

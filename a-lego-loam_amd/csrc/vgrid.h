@@ -69,9 +69,19 @@ __device__ __forceinline__ unsigned vgr_id(const VgrGeom& g, float4 p, float inv
 // ---- the bbox-free voxel key of LaserMapping's sorted key frames ----
 // PCL's VoxelGrid orders the output by idx = i + j dx + k dx dy with (i, j, k) the integer voxel coordinates relative to the cloud's
 // bounding box, i.e. lexicographically by (floor(z inv), floor(y inv), floor(x inv)) — an order that does not depend on the bounding
-// box.  21 bits per axis (|coordinate| < 2^20 voxels: 419 km at a 0.4 m leaf).
+// box.  21 bits per axis: cells -2^20 .. 2^20 - 1 (419 km at a 0.4 m leaf, 52 km at 0.05).  vkey_pack clamps a cell beyond that range onto the
+// last one, which keeps the key well-formed but merges distinct voxels: whoever builds a map by key checks the cloud's box with vkey_holds_box
+// first and refuses a cloud that does not fit (map_update: LI_OVERFLOW 8, reported by the host as ALEGO_ERR_CAPACITY).  The key-frame sort needs
+// no such check: it orders by box-relative voxel ids, the same order anywhere.
+#define VKEY_B (1 << 20)
+__device__ __forceinline__ bool vkey_holds_box(const float mn[3], const float mx[3], float inv) {   // floorf(p * inv) is monotonic in p: the box decides for every point
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+    if (floorf(mn[a] * inv) < -(float)VKEY_B || floorf(mx[a] * inv) > (float)(VKEY_B - 1)) return false;
+  return true;
+}
 __device__ __forceinline__ unsigned long long vkey_pack(int ix, int iy, int iz) {
-  const int B = 1 << 20;
+  const int B = VKEY_B;
   const unsigned long long x = (unsigned long long)(unsigned)min(max(ix + B, 0), 2 * B - 1), y = (unsigned long long)(unsigned)min(max(iy + B, 0), 2 * B - 1),
                            z = (unsigned long long)(unsigned)min(max(iz + B, 0), 2 * B - 1);
   return (z << 42) | (y << 21) | x;

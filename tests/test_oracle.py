@@ -9,7 +9,7 @@ import pytest
 
 from alego_amd import synth
 from oracle import oracle_py as O
-from util import (KNN_SCENES, assert_bit_equal, assert_knn_scene_premise, knn_brute_rows, knn_scene, knn_sparse_box_scene, lm_unit_cells_needed,
+from util import (KNN_SCENES, MERGE_SCENES, assert_bit_equal, assert_knn_scene_premise, knn_brute_rows, knn_scene, knn_sparse_box_scene, lm_unit_cells_needed,
                   run_knn_scene)
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "oracle_cfgA.npz")
@@ -686,3 +686,25 @@ def test_lm_pass_through_scenes_on_the_oracle(name):
         setattr(p, k, v)
     o = O.Oracle(p)
     assert run_pass_scene_oracle(o, scene, name) == sum(any(v) for v in scene["expect"].values())
+
+
+def test_merge_kernel_constants_are_found():
+    """The merge-map scenes are built around seven constants of kernels_map.hip; the helper that reads them finds each exactly once."""
+    from util import MERGE_CONSTANTS, merge_kernel_constants
+    C = merge_kernel_constants()
+    assert len(MERGE_CONSTANTS) == 7 and all(isinstance(C[k], int) and C[k] > 0 for k in MERGE_CONSTANTS)
+    assert C["MA_BCAP"] == C["MA_PT"] * C["MA_T"] and C["MAP_R"] == C["MA_T"]
+
+
+@pytest.mark.parametrize("name", MERGE_SCENES)
+def test_lm_merge_scenes_on_the_oracle(name):
+    """The scenes of tests/test_lm_merge_map.py on the oracle alone: every frame's premise holds (run sizes, voxel-list sizes and list events as
+    planned, tests/util.py), every planned frame is reached, and the oracle's filtered maps equal the numpy restatement of pcl::VoxelGrid applied
+    to its raw windows, bit for bit."""
+    from util import merge_scene, run_merge_scene_oracle
+    scene = merge_scene(name)
+    p = synth.default_params(16, 1800)
+    for k, v in scene["mods"].items():
+        setattr(p, k, v)
+    facts = run_merge_scene_oracle(O.Oracle(p), scene, name)
+    assert set(scene["want"]) <= {i for i, f in facts.items() if f is not None}

@@ -1278,3 +1278,344 @@ def assert_lo_scene_premise(name, sc, o, rows):
         nq = len(surf)
         assert nq > 128 and nq % 16, f"{name}: {nq} surf queries"
         assert (surf[:, 1] >= 0).sum() >= 20 and (corner[:, 1] >= 0).sum() >= 5, ((surf[:, 1] >= 0).sum(), (corner[:, 1] >= 0).sum())
+
+
+# ---- LaserMapping's merge-path local map (map_update / map_accum, kernels_map.hip) at its list and batch edges --------------------------------
+#
+# Recipe of every scene: 16 x 1800, lm_every 1, min_keyframe_dist 0, lm_max_iters 0, identity rotation, leaves that are powers of two.  Every mapping
+# frame then saves a key frame at exactly the odometry pose whose clouds are the frame's own VoxelGrid-filtered inputs, and the window of frame i is
+# the key frames max(0, i - K) .. i - 1: every run size and every position in the sorted voxel list follows from the construction, and the premise
+# function proves it from the oracle's outputs.  Points sit on a lattice of voxels that is enumerated in key order (x fastest, then y, then z), so a
+# lattice index orders like the voxel key; each point is its voxel's centre plus a jitter of +-0.2 leaf per axis (exact centres would make the f32
+# sums blind to the summation order) with a random intensity.
+
+MERGE_CONSTANTS = ("MU_FCAP", "MU_E", "MU_T", "MAP_R", "MA_JB", "MA_PT", "MA_T")
+LAT_N, LAT_ORIGIN = 64, np.array([-32, -32, -1])   # lattice index -> cell (i % 64, (i / 64) % 64, i / 4096) + origin
+VKEY_B = 1 << 20                                   # vgrid.h: a voxel key holds cells -2^20 .. 2^20 - 1 per axis
+
+
+def merge_kernel_constants():
+    """The constants of map_update / map_accum the scenes are built around, read from the kernels' source, so that a retune either moves the
+    scenes with it or fails here; MA_BCAP (points per batch) is derived as the source derives it."""
+    import os
+    import re
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "a-lego-loam_amd", "csrc", "kernels_map.hip")
+    with open(path) as f:
+        src = f.read()
+    out = {}
+    for name in MERGE_CONSTANTS:
+        found = re.findall(rf"^[ \t]*#define[ \t]+{name}[ \t]+(\d+)\b", src, re.M)
+        assert len(found) == 1, f"kernels_map.hip: {len(found)} numeric #defines of {name}"
+        out[name] = int(found[0])
+    assert re.search(r"#define[ \t]+MA_BCAP[ \t]+\(MA_PT \* MA_T\)", src), "kernels_map.hip: MA_BCAP is no longer MA_PT * MA_T"
+    out["MA_BCAP"] = out["MA_PT"] * out["MA_T"]
+    return out
+
+
+def _lat_cells(idx):
+    idx = np.asarray(idx, np.int64).reshape(-1)
+    return np.stack([idx % LAT_N, (idx // LAT_N) % LAT_N, idx // (LAT_N * LAT_N)], axis=1) + LAT_ORIGIN
+
+
+def lat_points(idx, leaf, rng, quant=None):
+    """one point per lattice index, shuffled; quant: the jitter is a multiple of `quant` metres (-1, 0 or 1 times) instead of uniform"""
+    cell = _lat_cells(idx)
+    jit = rng.integers(-1, 2, cell.shape) * (quant / leaf) if quant else rng.uniform(-0.2, 0.2, cell.shape)
+    p = np.c_[(cell + 0.5 + jit) * leaf, rng.uniform(0, 100, len(cell))].astype(F32)
+    return p[rng.permutation(len(p))]
+
+
+def dense_points(vox, n, rng, leaf, sub):
+    """n points on distinct `sub`-sized cells inside lattice voxel `vox` of size `leaf` (sub divides leaf)"""
+    m = int(round(leaf / sub))
+    cells = rng.choice(m ** 3, n, replace=False)
+    c3 = np.stack([cells % m, (cells // m) % m, cells // (m * m)], axis=1)
+    xyz = _lat_cells([vox]) * leaf + (c3 + 0.5 + rng.uniform(-0.2, 0.2, c3.shape)) * sub
+    return np.c_[xyz, rng.uniform(0, 100, n)].astype(F32)
+
+
+def vkeys(pts, leaf):
+    """the voxel key of vgrid.h (z, y, x cells, 21 bits each) per point, from the f32 floor that pcl::VoxelGrid computes; the cells must be in range"""
+    c = np.floor(np.asarray(pts, F32).reshape(-1, 4)[:, :3] * (F32(1.0) / F32(leaf))).astype(np.int64)
+    assert (c >= -VKEY_B).all() and (c < VKEY_B).all()
+    return ((c[:, 2] + VKEY_B) << 42) | ((c[:, 1] + VKEY_B) << 21) | (c[:, 0] + VKEY_B)
+
+
+def _merge_mods(K, leaf_c=0.5, leaf_s=0.5, leaf_o=0.5, **extra):
+    mods = dict(lm_leaf_corner=float(leaf_c), lm_leaf_surf=float(leaf_s), lm_leaf_outlier=float(leaf_o), lm_every=1, min_keyframe_dist=0.0,
+                lm_max_iters=0, recent_keyframe_num=int(K))
+    mods.update(extra)
+    return mods
+
+
+def _merge_frames(specs, mods, rng, quant=None):
+    """specs[i] = dict(c=, s=, o=, t=): lattice indices (or ready n x 4 points) of the corner / surf / outlier cloud and the odometry translation"""
+    frames = []
+    for sp in specs:
+        clouds = []
+        for k, leaf in (("c", mods["lm_leaf_corner"]), ("s", mods["lm_leaf_surf"]), ("o", mods["lm_leaf_outlier"])):
+            v = sp.get(k, ())
+            clouds.append(v if isinstance(v, np.ndarray) and v.ndim == 2 else lat_points(v, leaf, rng, quant))
+        frames.append((*clouds, _odom7(np.asarray(sp.get("t", (0.0, 0.0, 0.0)), float), 0.0)))
+    return frames
+
+
+_FILL_C = 8000 + np.arange(40)     # a line of 40 corner voxels
+_FILL_S = 12288 + np.arange(200)   # a patch of 200 surf voxels on one z level
+_FILL_O = 12288 + 3 * np.arange(20)
+
+
+def merge_fcap_scene(C, rng):
+    """surf map, K = 2: run sizes (surf + outlier points of a key frame) step through MU_FCAP - 96, MU_FCAP, MU_FCAP + 1 so that the (leaving, entering)
+    pairs take map_update's fast path at its limit and its general path with one removal just beyond it.  Run k covers the voxels 1500 k .. 1500 k + 2999
+    with one surf point each and spreads its outlier points over 1500 k .. 1500 k + 3199: the run that leaves shares about half its voxels with the one
+    that stays, and the one that enters finds about half of its voxels in the list."""
+    F = C["MU_FCAP"]
+    sizes = [F, F + 1, F, F - 96, F + 1, F + 1, F + 1, F - 96, F, F]
+    specs = [dict(c=_FILL_C, s=1500 * k + np.arange(3000), o=1500 * k + rng.choice(3200, n - 3000, replace=False)) for k, n in enumerate(sizes)]
+    want = {i: dict(m=1, sizes=(sizes[i - 3], sizes[i - 1]), fast=max(sizes[i - 3], sizes[i - 1]) <= F, events=("dec_shared", "emptied", "inc_known", "new"))
+            for i in range(3, len(sizes))}
+    kinds = {(min(a, F), min(b, F)) if max(a, b) <= F else (a > F, b > F) for a, b in (w["sizes"] for w in want.values())}
+    assert {(F, F), (True, False), (False, True), (True, True)} <= kinds, kinds
+    mods = _merge_mods(2)
+    return dict(mods=mods, frames=_merge_frames(specs, mods, rng), want=want)
+
+
+def merge_interval_scene(N, K, C, rng):
+    """surf map, runs of at most MU_FCAP points: the update at frame K + 1 finds a list of exactly N voxels (list index k = lattice voxel 200 + 2 k) and
+      empties U[0], U[N - 1], U[b - 1] and U[b] for the thread-interval boundaries b (MU_E and the last multiple of MU_E below N) and, for N >= 3 MU_E,
+              all MU_E entries of thread 2
+      inserts new voxels below U[0], above U[N - 1] and between U[b - 1] and U[b]
+      keeps   a voxel that only the leaving and the entering run hold (count unchanged)
+    K = 1: the entering run replaces the whole list.  K = 3 splits the staying voxels into two runs, the second of one voxel (N = 2 MU_FCAP + 1)."""
+    E, FC = C["MU_E"], C["MU_FCAP"]
+    v = lambda k: 200 + 2 * np.asarray(sorted(k), np.int64)
+    bnds = sorted({b for b in (E, (N - 1) // E * E) if 0 < b < N})
+    whole = set(range(2 * E, 3 * E)) if N >= 3 * E else set()
+    r = 5
+    must = {0, N - 1, r} | whole | {x for b in bnds for x in (b - 1, b)}
+    cand = [k for k in range(0, N, 2) if k not in must]
+    if K == 1:
+        L, S = set(range(N)), set()
+    else:
+        L = must | set(cand[:max(0, FC - len(must))])
+        S = (set(range(N)) - L) | ({k for k in cand if k % 4 == 0 and k in L} if N <= FC else set())
+    assert len(L) <= FC and len(S) <= FC + (K == 3), (N, len(L), len(S))
+    gone = (must - {r}) if K > 1 else (must - {r}) | {k for k in range(N) if k % 8 == 1}
+    Ein = ({r} | {k for k in L - S if k % 8 == 2} | {k for k in S if k % 3 == 0}) if K > 1 else set(range(N)) - gone
+    Ein -= gone
+    new = [198, int(v([N - 1])[0]) + 2] + [int(v([b])[0]) - 1 for b in bnds]
+    Ev = np.r_[v(Ein), new]
+    assert len(Ev) <= FC
+    runs = [v(L)] + ([v(S)] if K == 2 else [v(sorted(S)[:-1]), v(sorted(S)[-1:])] if K == 3 else []) + [Ev, v(range(0, N, 7))]
+    specs = [dict(c=_FILL_C, s=run) for run in runs] + [dict(c=_FILL_C, s=runs[-1])]
+    want = {K + 1: dict(m=1, nU_before=N, sizes=(len(L), len(Ev)), fast=True, emptied_has=sorted(gone), new_lb_has=[0, N] + bnds, readded_has=[r])}
+    mods = _merge_mods(K)
+    return dict(mods=mods, frames=_merge_frames(specs, mods, rng), want=want)
+
+
+def merge_chunk_scene(C, rng):
+    """corner map, K = 2 (one point per voxel and run): the voxel count after the update is 1, MAP_R - 1, MAP_R, MAP_R + 1, 2 MAP_R and 2 MAP_R + 1;
+    "both": voxels MAP_R - 1 and MAP_R (the last of map_accum's first work item and the first of its second) hold a point of either run; "split": one
+    run ends in voxel MAP_R - 1 and the other begins in voxel MAP_R, in both window orders."""
+    R = C["MAP_R"]
+    a = np.arange
+    kfs = [a(1), a(R - 1), a(R), a(R + 1), a(300, R + 1), np.array([k for k in range(2 * R) if k % 7 or k < 400 or k in (R - 1, R)]), a(400, 2 * R),
+           a(2 * R + 1), a(R), a(R, 2 * R + 1), a(R)]
+    specs = [dict(c=k, s=_FILL_S, o=_FILL_O) for k in kfs] + [dict(c=kfs[-1], s=_FILL_S, o=_FILL_O)]
+    want = {i: dict(m=0, nU_after=len(set(kfs[max(0, i - 2)]) | set(kfs[i - 1]))) for i in range(1, len(specs))}
+    for i in (5, 7, 8):
+        want[i]["both"] = True
+    for i in (10, 11):
+        want[i]["split"] = True
+    assert {1, R - 1, R, R + 1, 2 * R, 2 * R + 1} <= {w["nU_after"] for w in want.values()}
+    mods = _merge_mods(2)
+    return dict(mods=mods, frames=_merge_frames(specs, mods, rng), want=want)
+
+
+def merge_dense_scene(K, C, rng):
+    """surf leaf 2, outlier leaf 1/16: every frame's outlier cloud puts 3000 points on distinct 1/16 cells of ONE surf voxel, so the key frame keeps them
+    all and that voxel's piece of every run exceeds map_accum's batch of MA_BCAP points: the voxel's run is cut into sub-pieces and its thread carries
+    the sum across batches.  K = 10: more than MA_JB runs feed the chunk."""
+    n, D = 3000, 100
+    assert n > 2 * C["MA_BCAP"] and (K <= 2 or K > C["MA_JB"])
+    mods = _merge_mods(K, leaf_s=2.0, leaf_o=1 / 16)
+    specs = [dict(c=_FILL_C, s=np.arange(300), o=dense_points(D, n, rng, 2.0, 1 / 16)) for _ in range(K + 3)]
+    want = {i: dict(m=1, nU_after=300, runs=min(i, K), max_voxel_run=n + 1, kraw=min(i, K) * (300 + n)) for i in range(1, K + 3)}
+    return dict(mods=mods, frames=_merge_frames(specs, mods, rng), want=want)
+
+
+def merge_dense_cut_scene(C, rng):
+    """as dense, K = 1 (the window is one run, so batch offsets are offsets into the sorted run): ten single-point voxels, then three adjacent voxels
+    X, Y, Z whose lengths put the voxel changes at MA_BCAP - 1, MA_BCAP and MA_BCAP + 1 (layout A: the batch cut falls one after, exactly on and one
+    before a change) or at MA_BCAP - 1, 2 MA_BCAP and 3 MA_BCAP + 1 (layout B: the same three cases at three successive cuts of long voxel runs)."""
+    B, X = C["MA_BCAP"], 10
+    mods = _merge_mods(1, leaf_s=2.0, leaf_o=1 / 16)
+    surf = np.r_[np.arange(X), np.arange(X + 3, 300)]
+    lay = {"A": ((B - 1 - X, 1, 1), [B - 1, B, B + 1]), "B": ((B - 1 - X, B + 1, B + 1), [B - 1, 2 * B, 3 * B + 1])}
+    specs, want = [], {}
+    for i, which in enumerate("ABABA"):
+        lens, changes = lay[which]
+        specs.append(dict(c=_FILL_C, s=surf, o=np.concatenate([dense_points(X + j, n, rng, 2.0, 1 / 16) for j, n in enumerate(lens)])))
+        want[i + 1] = dict(m=1, nU_after=300, runs=1, changes_has=changes, kraw=297 + sum(lens))
+    specs.append(specs[-1])
+    return dict(mods=mods, frames=_merge_frames(specs, mods, rng), want=want)
+
+
+def merge_empty_scene(C, rng):
+    """K = 2, frames without any corner point: windows of zero-length runs, an empty corner map (no work item), the step from empty to non-empty (an
+    empty list refuses the fast path), a zero-length run that enters on the fast path, and the step back to an empty list"""
+    sizes = [0, 0, 0, 40, 40, 0, 0, 0, 30, 30]
+    specs = [dict(c=50 * k + np.arange(n), s=_FILL_S, o=_FILL_O) for k, n in enumerate(sizes)]
+    want = {}
+    for i in range(1, len(sizes)):
+        prev, cur = sizes[max(0, i - 3):i - 1], sizes[max(0, i - 2):i]
+        want[i] = dict(m=0, kraw=sum(cur), nU_before=sum(prev), nU_after=sum(cur))
+    want[4].update(fast=False, sizes=(0, 40)); want[6].update(fast=True, sizes=(40, 0)); want[7].update(fast=True, sizes=(40, 0)); want[9].update(fast=False)
+    mods = _merge_mods(2)
+    return dict(mods=mods, frames=_merge_frames(specs, mods, rng), want=want)
+
+
+def merge_far_scene(side, C, rng):
+    """leaf 0.5 (cell 2^20 begins at 524288 m, where f32 values are 1/16 apart: the jitter is -1/16, 0 or 1/16), K = 2: compact clouds (64 x 8 x 1 surf
+    cells, a few outliers, five corner points: below lm_min_corner, so no association at coordinates where lattice points tie) that the odometry
+    translation places so that the frame's extreme x cell is the given one.  side +1: windows whose largest x cell is 2^20 - 1 (in range), 2^20, and
+    2^20 + 31 (the window straddles the limit); side -1: smallest x cell -2^20 (in range), -2^20 - 1, -2^20 - 32.  want[i]["raises"]: the window of
+    frame i has a cell that the 21-bit voxel key cannot hold."""
+    P = VKEY_B
+    ext = [P - 1, P - 1, P - 1, P, P, P + 31, P + 31, P - 1, P - 1, P - 1, P - 1] if side > 0 else [-P, -P, -P, -P - 1, -P - 1, -P - 32, -P - 32, -P, -P, -P, -P]
+    local = 31 if side > 0 else -32
+    mods = _merge_mods(2)
+    specs = [dict(c=np.arange(5), s=np.arange(512), o=3 * np.arange(60), t=((e - local) * 0.5, 0.0, 0.0)) for e in ext]
+    want = {}
+    for i in range(1, len(ext)):
+        w = ext[max(0, i - 2):i]
+        x = max(w) if side > 0 else min(w)
+        want[i] = dict(m=1, far_x=x, raises=not (-P <= x <= P - 1))
+    assert {w["far_x"] for w in want.values()} == set(ext)
+    return dict(mods=mods, frames=_merge_frames(specs, mods, rng, quant=1 / 16), want=want, far=side)
+
+
+MERGE_SCENES = ["fcap", "interval_one_thread", "interval_three_threads", "interval_round", "interval_round_plus_one", "interval_replace",
+                "chunk", "dense_k1", "dense_k2", "dense_k10", "dense_cut", "empty", "far_pos", "far_neg"]
+
+
+def merge_scene(name, C=None):
+    C = C or merge_kernel_constants()
+    rng = np.random.default_rng(31 + MERGE_SCENES.index(name))
+    E, T = C["MU_E"], C["MU_T"]
+    if name == "fcap":
+        sc = merge_fcap_scene(C, rng)
+    elif name.startswith("interval"):
+        N, K = {"one_thread": (E, 2), "three_threads": (3 * E, 2), "round": (T * E, 2), "round_plus_one": (T * E + 1, 3), "replace": (3 * E, 1)}[name[9:]]
+        sc = merge_interval_scene(N, K, C, rng)
+    elif name == "chunk":
+        sc = merge_chunk_scene(C, rng)
+    elif name == "dense_cut":
+        sc = merge_dense_cut_scene(C, rng)
+    elif name.startswith("dense"):
+        sc = merge_dense_scene(int(name[7:]), C, rng)
+    elif name == "empty":
+        sc = merge_empty_scene(C, rng)
+    elif name.startswith("far"):
+        sc = merge_far_scene(1 if name == "far_pos" else -1, C, rng)
+    else:
+        raise KeyError(name)
+    sc.update(keyframes=[], K=sc["mods"]["recent_keyframe_num"], C=C)
+    assert max(sum(len(x) for x in f[:3]) for f in sc["frames"]) <= 15000
+    return sc
+
+
+def merge_window_facts(scene, o, i, m):
+    """What map_update and map_accum meet at mapping frame i (>= 1) for map m (0 corner, 1 surf), from the oracle's key frames and maps alone: the runs
+    of the previous and of the current window, the voxel list before and after, and every list event of the update."""
+    K, C = scene["K"], scene["C"]
+    leaf = scene["mods"]["lm_leaf_surf" if m else "lm_leaf_corner"]
+    raw, ds = o.get("lm_surf_map" if m else "lm_corner_map"), o.get("lm_surf_map_ds" if m else "lm_corner_map_ds")
+    run = {}
+    for k in range(max(0, i - 1 - K), i):
+        kc, ks, ko = o.lm_keyframe(k)
+        run[k] = kc if m == 0 else np.concatenate([ks, ko])
+    prev, cur = list(range(max(0, i - 1 - K), i - 1)), list(range(max(0, i - K), i))
+    f = dict(kraw=len(raw), nds=len(ds), run_sizes=[len(run[k]) for k in cur])
+    assert len(raw) == sum(f["run_sizes"]), f"frame {i} map {m}: raw map of {len(raw)} points vs runs {f['run_sizes']}"
+    if scene.get("far"):
+        return f
+    cat = np.concatenate([run[k] for k in cur])
+    assert (bits(cat) == bits(raw)).all(), f"frame {i} map {m}: the window is not key frames {cur} at the zero pose"
+    keys = {k: vkeys(run[k], leaf).tolist() for k in run}
+    setof = lambda ids: set().union(*[set(keys[k]) for k in ids]) if ids else set()
+    Ub, Ua = sorted(setof(prev)), sorted(setof(cur))
+    leaving, entering, staying = [k for k in prev if k not in cur], [k for k in cur if k not in prev], [k for k in cur if k in prev]
+    kL, kE, kS = setof(leaving), setof(entering), setof(staying)
+    pos = {key: p for p, key in enumerate(Ub)}
+    import bisect
+    f.update(nU_before=len(Ub), nU_after=len(Ua), chunks=-(-len(Ua) // C["MAP_R"]), runs=sum(1 for k in cur if len(run[k])),
+             sizes=(len(run[leaving[0]]) if len(leaving) == 1 else None, len(run[entering[0]]) if len(entering) == 1 else None),
+             emptied=sorted(pos[key] for key in set(Ub) - set(Ua)), new_lb=sorted(bisect.bisect_left(Ub, key) for key in set(Ua) - set(Ub)),
+             readded=sorted(pos[key] for key in (kL & kE) - kS), dec_shared=len(kL & kS), inc_known=len(kE & (kS | kL) & set(Ub)))
+    f["new"] = len(f["new_lb"])
+    f["fast"] = len(Ub) > 0 and len(leaving) <= 1 and len(entering) <= 1 and max(f["sizes"][0] or 0, f["sizes"][1] or 0) <= C["MU_FCAP"]
+    cnt = [np.unique(keys[k], return_counts=True)[1].max() if len(keys[k]) else 0 for k in cur]
+    f["max_voxel_run"] = int(max(cnt)) if cnt else 0
+    if cur and len(keys[cur[0]]):
+        ks0 = sorted(keys[cur[0]])
+        f["changes"] = [j for j in range(1, len(ks0)) if ks0[j] != ks0[j - 1]]
+    R = C["MAP_R"]
+    if len(Ua) > R and len(cur) == 2:
+        a, b = keys[cur[0]], keys[cur[1]]
+        f["both"] = all(Ua[x] in set(a) and Ua[x] in set(b) for x in (R - 1, R))
+        f["split"] = (max(a) == Ua[R - 1] and min(b) == Ua[R]) or (max(b) == Ua[R - 1] and min(a) == Ua[R])
+    return f
+
+
+def assert_merge_scene_premise(name, scene, o, i):
+    """Frame i of the scene reaches what it was built for, proven from the oracle's outputs after that frame (key-frame clouds, raw and filtered
+    maps); returns the recorded facts of the map the scene is about (None at a frame without a window)."""
+    if i == 0:
+        assert len(o.get("lm_corner_map")) == 0 and len(o.get("lm_surf_map")) == 0
+        return None
+    P = scene["mods"]
+    for m, (raw_name, ds_name, leaf) in enumerate((("lm_corner_map", "lm_corner_map_ds", P["lm_leaf_corner"]), ("lm_surf_map", "lm_surf_map_ds", P["lm_leaf_surf"]))):
+        assert not pcl_passes(o.get(raw_name), leaf), f"{name} frame {i}: {raw_name} passes through"
+    assert o.get("lm_info")[11] == i + 1, f"{name} frame {i}: {o.get('lm_info')[11]} key frames"
+    want = scene["want"].get(i, dict(m=1))
+    f = merge_window_facts(scene, o, i, want["m"])
+    tag = f"{name} frame {i} map {want['m']}: "
+    if scene.get("far"):
+        raw = o.get("lm_surf_map")
+        cx = np.floor(raw[:, 0] * (F32(1.0) / F32(P["lm_leaf_surf"]))).astype(np.int64)
+        f["far_x"] = int(cx.max() if scene["far"] > 0 else cx.min())
+        f["refused"] = []   # per map (corner, surf): the window has a cell that the voxel key cannot hold
+        for r, leaf in ((o.get("lm_corner_map"), P["lm_leaf_corner"]), (raw, P["lm_leaf_surf"])):
+            c3 = np.floor(r[:, :3] * (F32(1.0) / F32(leaf))).astype(np.int64)
+            f["refused"].append(bool((c3 < -VKEY_B).any() or (c3 > VKEY_B - 1).any()))
+        f["raises"] = any(f["refused"])
+        assert max(pcl_dims(raw, P["lm_leaf_surf"])) <= 2 * LAT_N, tag + f"window grid {pcl_dims(raw, P['lm_leaf_surf'])} is not compact"
+    else:
+        assert f["nds"] == f["nU_after"], tag + f"{f['nds']} filtered points vs {f['nU_after']} occupied voxels"
+    for k, w in want.items():
+        if k == "m":
+            continue
+        if k.endswith("_has"):
+            assert set(w) <= set(f[k[:-4]]), tag + f"{k[:-4]} = {f[k[:-4]][:40]} lacks {sorted(set(w) - set(f[k[:-4]]))}"
+        elif k == "events":
+            assert all(f[e] > 0 if not isinstance(f[e], list) else len(f[e]) > 0 for e in w), tag + f"events {[(e, f[e] if not isinstance(f[e], list) else len(f[e])) for e in w]}"
+        elif k == "max_voxel_run":
+            assert f[k] >= w, tag + f"{k} = {f[k]} < {w}"
+        else:
+            assert f[k] == w, tag + f"{k} = {f[k]} vs planned {w}"
+    return f
+
+
+def run_merge_scene_oracle(o, scene, name):
+    """the whole scene on an oracle: every premise, and the oracle's filtered maps against voxel_grid_np of its raw windows, bit for bit; returns the
+    recorded facts per frame"""
+    P = scene["mods"]
+    facts = {}
+    for i, (c, s, ol, od) in enumerate(scene["frames"]):
+        o.lm_process(c, s, ol, od)
+        facts[i] = assert_merge_scene_premise(name, scene, o, i)
+        for raw_name, ds_name, leaf in (("lm_corner_map", "lm_corner_map_ds", P["lm_leaf_corner"]), ("lm_surf_map", "lm_surf_map_ds", P["lm_leaf_surf"])):
+            assert_bit_equal(o.get(ds_name), voxel_grid_np(o.get(raw_name), leaf), f"{name} frame {i}: {ds_name} vs the numpy VoxelGrid")
+    return facts
