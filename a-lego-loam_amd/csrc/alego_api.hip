@@ -249,6 +249,8 @@ int alego_create(const alego_params* params, int device, int n_slots, int ring_l
   d.h_magic = (unsigned)((1ull << 32) / (unsigned long long)d.H) + 1u;
   d.inv_res_x = 1.0 / params->ang_res_x; d.inv_res_y = 1.0 / params->ang_res_y;
   d.tan_theta = (params->seg_theta > 0.0 && params->seg_theta < 1.5) ? std::tan(params->seg_theta) : std::nan("");
+  d.opt_ip_screen = env_int("ALEGO_IP_SCREEN", 1) != 0;
+  d.ip_scr = ip_screen_consts(d.sin_ax, d.cos_ax, d.sin_ay, d.cos_ay, d.tan_theta, d.tan_g_lo, d.tan_g_hi, d.opt_ip_screen);
   d.opt_ip_fused = env_int("ALEGO_IP_FUSED", 1) != 0;
   d.opt_ip_half = env_int("ALEGO_IP_HALF", 1) != 0;
   d.opt_cc_fused = env_int("ALEGO_CC_FUSED", 1) != 0;
@@ -1016,6 +1018,7 @@ int alego_debug_set_option(alego_handle* h, const char* name, int value) {
   if (s == "ALEGO_CC_FUSED") d.opt_cc_fused = value != 0;
   else if (s == "ALEGO_IP_FUSED") d.opt_ip_fused = value != 0;
   else if (s == "ALEGO_IP_HALF") d.opt_ip_half = value != 0;
+  else if (s == "ALEGO_IP_SCREEN") { d.opt_ip_screen = value != 0; d.ip_scr = ip_screen_consts(d.sin_ax, d.cos_ax, d.sin_ay, d.cos_ay, d.tan_theta, d.tan_g_lo, d.tan_g_hi, d.opt_ip_screen); }
   else if (s == "ALEGO_CC_TILE") d.opt_cc_tile = value != 0;
   else if (s == "ALEGO_IP_BAND") {   // the banded path expects the component statistics at zero between scans (it re-zeroes what it touched); the cc_stats path leaves them set
     HIP_TRY(h, hipDeviceSynchronize());

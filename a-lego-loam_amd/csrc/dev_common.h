@@ -11,6 +11,7 @@
 
 #include "../../include/alego_params.h"
 #include "wave.h"
+#include "ip_pred.h"
 
 #define IPB_NM 9
 #define IP_OWNER_TAG 0x40000000   // any tagged entry beats every plain one (index or -1) in ip_project's atomicMax
@@ -33,6 +34,7 @@ struct DevCtx {
   unsigned h_magic;                       // floor(2^32 / H) + 1: cell / H == umulhi(cell, h_magic) for every cell < 2^32 / H
   double tan_g_lo, tan_g_hi;              // tan of (sensor_mount_ang -/+ ground_angle_thres) (ground test shortcut; NaN disables)
   double tan_theta;                       // tan(seg_theta) for the edge predicate shortcut; NaN disables the shortcut
+  IpScreenConsts ip_scr;                  // the f32 screens of those two decisions (ip_pred.h) in ip_fused_h / ip_fused_w / ipb_band; ALEGO_IP_SCREEN=0: the "undecided" constants
   // ---- kernel-variant switches (read once from the environment by alego_create, alego_debug_set_option overrides) ----
   int opt_ip_fused;     // ALEGO_IP_FUSED   1: ImageProjection as one launch, one workgroup per stream (ip_fused; <= 16 rings, <= 32768 cells); 0: ip_project + ip_front + cc_*
   int opt_ip_half;      // ALEGO_IP_HALF    1: ip_fused_h (512 threads, 2 N + 8 H bytes of LDS: two workgroups per CU) where it applies; 0: ip_fused
@@ -43,6 +45,7 @@ struct DevCtx {
   int opt_fe_cand;      // ALEGO_FE_CAND    sharp candidates of a ring sector kept in LDS by fe_front (0: by geometry; the tests set 8 to drive the overflow path)
   int opt_lo_box_lds;   // ALEGO_LO_BOX_LDS boxes staged in LDS by lo_assoc (0: straight from HBM)
   int opt_map_merge;    // ALEGO_MAP_MERGE  1: local map from the pre-sorted key frames; 0: concat + radix VoxelGrid
+  int opt_ip_screen;    // ALEGO_IP_SCREEN  1: ip_fused_h / ip_fused_w / ipb_band decide ground and edge tests in f32 where f32 can (ip_pred.h), in fp64 where it cannot; 0: every site in fp64
   int opt_solve_full_eval;   // ALEGO_SOLVE_FULL_EVAL  0: lo_solve_t / lm_solve evaluate a candidate for its cost and the normal equations only where a step is computed from them; 1: every point in full
   // ---- input ring ----
   float4* in_pts;  // [slot][ring][Pcap]

@@ -41,8 +41,16 @@ typedef unsigned long long u64;
 __device__ long long ipb_times[48];
 extern "C" void alego_ipb_times(long long* out) { (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(ipb_times), sizeof(long long) * 48); }
 #define IPB_TICK(k) do { if (threadIdx.x == 0 && blockIdx.x == 0 && blockIdx.y == 0) ipb_times[k] = wall_clock64(); } while (0)
+// wavefronts of ipb_band: [0] all, [1] entered the fp64 block of the ground pairs, [2] entered that of the edge sites (tools/ip_screen_rate.py)
+__device__ unsigned long long ipb_slow_cnt[4];
+#define IPB_SLOW_COUNT(k) do { if ((threadIdx.x & 63) == 0) atomicAdd(&ipb_slow_cnt[k], 1ull); } while (0)
+extern "C" void alego_ipb_slow_counts(unsigned long long* out, int reset) {
+  (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(ipb_slow_cnt), sizeof(unsigned long long) * 4);
+  if (reset) { const unsigned long long z[4] = {0, 0, 0, 0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(ipb_slow_cnt), z, sizeof(z)); }
+}
 #else
 #define IPB_TICK(k)
+#define IPB_SLOW_COUNT(k)
 #endif
 DEV_INLINE u64 ipb_low(int r) { return (2ull << r) - 1ull; }                 // bits 0..r (r = 63: all)
 DEV_INLINE int ipb_head(u64 rs, int r) { return 63 - __clzll((long long)(rs & ipb_low(r))); }   // the run start at or below row r
@@ -78,6 +86,15 @@ DEV_INLINE int ipb_union(int* parent, int a, int b) {
     }
   } while (repeat);
   return linked;
+}
+// ipb_band's fp64 blocks gather a flagged site's cells once more.  The cell is filled in this scan: its owner entry is the tagged index or, once the
+// column's thread has written the plain form back, the index itself.  A stale or empty entry (-1, or an untagged index of an earlier scan) is never read
+// here: a site is flagged only where the screen ran on two filled cells (the ground bits need ok && lower_ok, the edge bits are masked by `act` of both
+// cells), and a filled cell's entry is one of the two forms above from ip_project until ipb_merge.  A change that flags a site with an unfilled cell breaks this.
+DEV_INLINE float4 ipb_cell_point(const int* owner, const float4* pts, int H, int row, int col) { return pts[max(ipb_ld(owner + row * H + col), 0) & ~IP_OWNER_TAG]; }
+DEV_INLINE float ipb_cell_range(const int* owner, const float4* pts, int H, int row, int col) {
+  const float4 q = ipb_cell_point(owner, pts, H, row, col);
+  return sqrtf(q.x * q.x + q.y * q.y + q.z * q.z);   // :99, the expression of the row loop
 }
 DEV_INLINE bool ipb_feasible(const alego_params& P, int sz, u64 rows) {   // imageProjection.cpp:282-301
   return sz >= P.seg_big_num || (sz >= P.seg_valid_point_num && (int)__popcll(rows) >= P.seg_valid_line_num);
@@ -118,7 +135,12 @@ __global__ void __launch_bounds__(IPB_TW) ipb_band(DevCtx d, int ring_pos, int k
   // ---- ranges + ground, bottom-up; rows in batches of 8: the owner indices of a batch, then its point gathers, are independent loads ----
   float rng[64];
   u64 filled = 0, ground = 0;
+  IPB_SLOW_COUNT(0);
   {
+    // ground pairs: the f32 screen of ip_pred.h at every pair, without a branch; the pairs it cannot decide (bits of gund) take the fp64 test behind the loop
+    float k_glo = d.ip_scr.g_lo, k_ghi = d.ip_scr.g_hi, k_gmax = d.ip_scr.g_max;
+    asm volatile("" : "+s"(k_glo), "+s"(k_ghi), "+s"(k_gmax));
+    u64 gund = 0;
     float lx = 0, ly = 0, lz = 0;
     bool lower_ok = false;
     int obn[8];   // the NEXT batch's owner words: in flight while this batch's points are gathered (and issued before this batch's write-backs, which the compiler must keep behind them)
@@ -152,8 +174,11 @@ __global__ void __launch_bounds__(IPB_TW) ipb_band(DevCtx d, int ring_pos, int k
           const float r = ok ? sqrtf(x * x + y * y + z * z) : -1.0f;   // :99
           rng[row] = r;
           if (ok) filled |= 1ull << row;
-          if (row >= 1 && row - 1 < P.ground_scan_id && ok && lower_ok) {   // :111-131, pair (row - 1, row)
-            if (ip_is_ground(d, x - lx, y - ly, z - lz)) ground |= 3ull << (row - 1);
+          if (row >= 1 && row - 1 < P.ground_scan_id) {   // :111-131, pair (row - 1, row)
+            const IpScreenBits g = ip_ground_screen(k_glo, k_ghi, k_gmax, x - lx, y - ly, z - lz);
+            const bool en = ok && lower_ok;
+            ground |= (en && g.yes) ? 3ull << (row - 1) : 0ull;
+            gund |= (en && g.und) ? 1ull << row : 0ull;
           }
           lx = x; ly = y; lz = z; lower_ok = ok;
           if ((keep & 1) && have && row < NS) d.range_img[base + row * H + col] = r;
@@ -161,6 +186,15 @@ __global__ void __launch_bounds__(IPB_TW) ipb_band(DevCtx d, int ring_pos, int k
       } else {
 #pragma unroll
         for (int u = 0; u < 8; ++u) rng[row0 + u] = -1.0f;
+      }
+    }
+    if (__ballot(gund != 0ull)) {   // rare: some lane holds a pair within the screen's tolerance of a bound (or the screen is switched off)
+      IPB_SLOW_COUNT(1);
+#pragma unroll 1
+      for (u64 m = gund; m; m &= m - 1) {
+        const int row = __ffsll((long long)m) - 1;
+        const float4 q = ipb_cell_point(owner, pts, H, row, col), l = ipb_cell_point(owner, pts, H, row - 1, col);
+        if (ip_is_ground(d, q.x - l.x, q.y - l.y, q.z - l.z)) ground |= 3ull << (row - 1);
       }
     }
   }
@@ -182,8 +216,12 @@ __global__ void __launch_bounds__(IPB_TW) ipb_band(DevCtx d, int ring_pos, int k
     const bool ok = o >= 0;
     const float px = __shfl_up(p.x, 1, 64), py = __shfl_up(p.y, 1, 64), pz = __shfl_up(p.z, 1, 64);
     const int okl = __shfl_up(ok ? 1 : 0, 1, 64);
-    bool gp = false;
-    if (lane >= 1 && lane - 1 < P.ground_scan_id && ok && okl) gp = ip_is_ground(d, p.x - px, p.y - py, p.z - pz);
+    const IpScreenBits gs = ip_ground_screen(d.ip_scr.g_lo, d.ip_scr.g_hi, d.ip_scr.g_max, p.x - px, p.y - py, p.z - pz);
+    const bool gen = lane >= 1 && lane - 1 < P.ground_scan_id && ok && okl;
+    bool gp = gen && gs.yes;
+    if (__ballot(gen && gs.und)) {   // (rare, as above: the lanes the screen leaves undecided take the fp64 test)
+      if (gen && gs.und) gp = ip_is_ground(d, p.x - px, p.y - py, p.z - pz);
+    }
     const u64 gb = __ballot(gp), fb = __ballot(ok);
     s_first[IPB_NWV][lane] = ok ? sqrtf(p.x * p.x + p.y * p.y + p.z * p.z) : -1.0f;
     if (lane == 0) s_a[TW] = fb & ~(gb | (gb >> 1));
@@ -196,22 +234,44 @@ __global__ void __launch_bounds__(IPB_TW) ipb_band(DevCtx d, int ring_pos, int k
     const u64 act_r = s_a[min(tid + 1, TW)];
     const bool edge_lane = lane == 63 || tid == TW - 1;
     const float* sf = s_first[(tid >= TW - 1) ? IPB_NWV : wave + 1];
+    // every site takes the f32 screen of ip_pred.h (no fp64, no branch) and is masked by its cells' activity afterwards; a site the screen cannot decide
+    // is evaluated with the fp64 predicate behind the loop, from its two cells gathered once more
+    float k_kxh = d.ip_scr.kxh, k_kxl = d.ip_scr.kxl, k_kyh = d.ip_scr.kyh, k_kyl = d.ip_scr.kyl, k_eb = d.ip_scr.eband;
+    asm volatile("" : "+s"(k_kxh), "+s"(k_kxl), "+s"(k_kyh), "+s"(k_kyl), "+s"(k_eb));
+    u64 ux = 0, uy = 0;
 #pragma unroll
     for (int row = 0; row < 64; ++row) {
       const float nbd = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(rng[row]), 0x130, 0xF, 0xF, false));   // wave_shl:1: lane i <- lane i + 1
       const float nbl = sf[row];
       const float nb = edge_lane ? nbl : nbd;
-      if ((act >> row) & 1ull) {
-        const double r0 = (double)rng[row];
-        if ((act_r >> row) & 1ull) {
-          const double r1 = (double)nb;
-          const double d1 = fmax(r0, r1), d2 = fmin(r0, r1);
-          if (edge_angle_gt(d2 * d.sin_ax, d1 - d2 * d.cos_ax, P.seg_theta, d.tan_theta)) ex |= 1ull << row;
+      const float r0 = rng[row];
+      if (__ballot((act >> row) & 1ull)) {   // (one test per row and wavefront: the rows that are all ground or all empty hold no site)
+        {
+          const IpScreenBits e = ip_edge_screen(fmaxf(r0, nb), fminf(r0, nb), k_kxh, k_kxl, k_eb);
+          ex |= e.yes ? 1ull << row : 0ull; ux |= e.und ? 1ull << row : 0ull;
         }
-        if (row + 1 < 64 && ((act >> (row + 1)) & 1ull)) {
-          const double r1 = (double)rng[row + 1 < 64 ? row + 1 : 63];
+        if (row + 1 < 64) {
+          const float r1 = rng[row + 1 < 64 ? row + 1 : 63];
+          const IpScreenBits e = ip_edge_screen(fmaxf(r0, r1), fminf(r0, r1), k_kyh, k_kyl, k_eb);
+          ey |= e.yes ? 1ull << row : 0ull; uy |= e.und ? 1ull << row : 0ull;
+        }
+      }
+    }
+    const u64 sx = act & act_r, sy = act & (act >> 1);   // the sites that exist
+    ex &= sx; ey &= sy; ux &= sx; uy &= sy;
+    if (__ballot((ux | uy) != 0ull)) {   // rare: some lane holds a site inside the screen's band (or the screen is switched off)
+      IPB_SLOW_COUNT(2);
+      const int cr = col + 1 == H ? 0 : col + 1;   // the right neighbour; the halo column behind the band's last one, column 0 behind the image's
+#pragma unroll 1
+      for (int k = 0; k < 2; ++k) {
+        const double sa = k ? d.sin_ay : d.sin_ax, ca = k ? d.cos_ay : d.cos_ax;
+#pragma unroll 1
+        for (u64 m = k ? uy : ux; m; m &= m - 1) {
+          const int row = __ffsll((long long)m) - 1;
+          const double r0 = (double)ipb_cell_range(owner, pts, H, row, col);
+          const double r1 = (double)(k ? ipb_cell_range(owner, pts, H, row + 1, col) : ipb_cell_range(owner, pts, H, row, cr));
           const double d1 = fmax(r0, r1), d2 = fmin(r0, r1);
-          if (edge_angle_gt(d2 * d.sin_ay, d1 - d2 * d.cos_ay, P.seg_theta, d.tan_theta)) ey |= 1ull << row;
+          if (edge_angle_gt(d2 * sa, d1 - d2 * ca, P.seg_theta, d.tan_theta)) { if (k) ey |= 1ull << row; else ex |= 1ull << row; }
         }
       }
     }

@@ -50,8 +50,16 @@ struct IpfShared {
 __device__ long long ipf_times[16];
 #define IPF_TICK(k) do { if (threadIdx.x == 0 && blockIdx.x == 0) ipf_times[k] = wall_clock64(); } while (0)
 extern "C" void alego_ipf_times(long long* out) { (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(ipf_times), sizeof(long long) * 16); }
+// wavefront passes of ip_fused_t's phase B: [0] all, [1] entered the fp64 block of the ground pairs, [2] entered that of the edge sites (tools/ip_screen_rate.py)
+__device__ unsigned long long iph_slow_cnt[4];
+#define IPH_SLOW_COUNT(k) do { if ((threadIdx.x & 63) == 0) atomicAdd(&iph_slow_cnt[k], 1ull); } while (0)
+extern "C" void alego_iph_slow_counts(unsigned long long* out, int reset) {
+  (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(iph_slow_cnt), sizeof(unsigned long long) * 4);
+  if (reset) { const unsigned long long z[4] = {0, 0, 0, 0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(iph_slow_cnt), z, sizeof(z)); }
+}
 #else
 #define IPF_TICK(k)
+#define IPH_SLOW_COUNT(k)
 #endif
 
 DEV_INLINE int ipf_run_start(unsigned rs, int row) { return 31 - __clz((int)(rs & ((2u << row) - 1u))); }       // highest run start at or below row
@@ -544,6 +552,15 @@ DEV_INLINE void iph_max16(unsigned* w32, int cell, unsigned val) {
     old = got;
   }
 }
+// phase B's fp64 blocks gather a flagged site's cells once more: the point that owns cell (row, col) (the cell is filled)
+DEV_INLINE float4 iph_cell_point(const unsigned* own16w, const float4* pts, int H, int row, int col) {
+  const unsigned ow = (own16w[(row * H + col) >> 1] >> ((col & 1) * 16)) & 0xFFFFu;
+  return pts[max((int)ow - 1, 0)];
+}
+DEV_INLINE float iph_cell_range(const unsigned* own16w, const float4* pts, int H, int row, int col) {
+  const float4 q = iph_cell_point(own16w, pts, H, row, col);
+  return sqrtf(q.x * q.x + q.y * q.y + q.z * q.z);   // :99, the expression of the row loop
+}
 // the four row masks of a column
 struct IphCol { unsigned a, b, x, y; };   // a = ground, b = active, x = right-edges (phase C: roots), y = down-edges (after phase C: feasible cells)
 DEV_INLINE IphCol iph_load(const unsigned long long* fcol, int c) { const unsigned long long v = fcol[c]; IphCol m; m.a = (unsigned)v & 0xFFFFu; m.b = (unsigned)(v >> 16) & 0xFFFFu; m.x = (unsigned)(v >> 32) & 0xFFFFu; m.y = (unsigned)(v >> 48); return m; }
@@ -564,7 +581,6 @@ __global__ void __launch_bounds__(T, IPH_MINW) ip_fused_t(DevCtx d, int ring_pos
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int N = d.N, H = d.H, NS = d.NS;
   const size_t base = (size_t)slot * N;
-  const alego_params& P = d.P;
   extern __shared__ __attribute__((aligned(16))) unsigned char ipf_smem[];
   unsigned* own16w = reinterpret_cast<unsigned*>(ipf_smem);                                  // [N / 2] phases A, B: two 16-bit owners (index + 1, 0 = empty) per word
   uint16_t* par = reinterpret_cast<uint16_t*>(ipf_smem);                                     // [N] from phase C on
@@ -699,7 +715,13 @@ __global__ void __launch_bounds__(T, IPH_MINW) ip_fused_t(DevCtx d, int ring_pos
     const bool colv = pi < hpairs;
     float rng0[IPF2_ROWS], rng1[IPF2_ROWS];
     unsigned filled0 = 0, filled1 = 0, ground0 = 0, ground1 = 0;
+    IPH_SLOW_COUNT(0);
     {
+      // Ground pairs: the f32 screen of ip_pred.h at every pair, without a branch; a pair it cannot decide leaves a bit in gund (column 1 in the upper half)
+      // and is decided in fp64 behind the row loop.  (the screen's constants as values of their own, like those of the edge predicate below)
+      float k_glo = d.ip_scr.g_lo, k_ghi = d.ip_scr.g_hi, k_gmax = d.ip_scr.g_max;
+      asm volatile("" : "+s"(k_glo), "+s"(k_ghi), "+s"(k_gmax));
+      unsigned gund = 0;
       float lx0 = 0, ly0 = 0, lz0 = 0, lx1 = 0, ly1 = 0, lz1 = 0;
       bool lok0 = false, lok1 = false;
 #pragma unroll
@@ -719,7 +741,12 @@ __global__ void __launch_bounds__(T, IPH_MINW) ip_fused_t(DevCtx d, int ring_pos
             const float x = pa[u].x, y = pa[u].y, z = pa[u].z;
             rng0[row] = ok ? sqrtf(x * x + y * y + z * z) : -1.0f;   // :99
             if (ok) filled0 |= 1u << row;
-            if (row >= 1 && row - 1 < P.ground_scan_id && ok && lok0 && ip_is_ground(d, x - lx0, y - ly0, z - lz0)) ground0 |= 3u << (row - 1);   // :111-131
+            if (row >= 1 && row - 1 < P.ground_scan_id) {   // :111-131
+              const IpScreenBits g = ip_ground_screen(k_glo, k_ghi, k_gmax, x - lx0, y - ly0, z - lz0);
+              const bool en = ok && lok0;
+              ground0 |= (en && g.yes) ? 3u << (row - 1) : 0u;
+              gund |= (en && g.und) ? 1u << row : 0u;
+            }
             lx0 = x; ly0 = y; lz0 = z; lok0 = ok;
           }
           {
@@ -727,9 +754,23 @@ __global__ void __launch_bounds__(T, IPH_MINW) ip_fused_t(DevCtx d, int ring_pos
             const float x = pb[u].x, y = pb[u].y, z = pb[u].z;
             rng1[row] = ok ? sqrtf(x * x + y * y + z * z) : -1.0f;
             if (ok) filled1 |= 1u << row;
-            if (row >= 1 && row - 1 < P.ground_scan_id && ok && lok1 && ip_is_ground(d, x - lx1, y - ly1, z - lz1)) ground1 |= 3u << (row - 1);
+            if (row >= 1 && row - 1 < P.ground_scan_id) {
+              const IpScreenBits g = ip_ground_screen(k_glo, k_ghi, k_gmax, x - lx1, y - ly1, z - lz1);
+              const bool en = ok && lok1;
+              ground1 |= (en && g.yes) ? 3u << (row - 1) : 0u;
+              gund |= (en && g.und) ? 0x10000u << row : 0u;
+            }
             lx1 = x; ly1 = y; lz1 = z; lok1 = ok;
           }
+        }
+      }
+      if (__ballot(gund != 0u)) {   // rare: some lane holds a pair within the screen's tolerance of a bound (or the screen is switched off)
+        IPH_SLOW_COUNT(1);
+#pragma unroll 1
+        for (unsigned m = gund; m; m &= m - 1) {
+          const int b = __ffs((int)m) - 1, row = b & 15, c = c0 + (b >> 4);
+          const float4 q = iph_cell_point(own16w, pts, H, row, c), l = iph_cell_point(own16w, pts, H, row - 1, c);
+          if (ip_is_ground(d, q.x - l.x, q.y - l.y, q.z - l.z)) { if (b >> 4) ground1 |= 3u << (row - 1); else ground0 |= 3u << (row - 1); }
         }
       }
     }
@@ -757,7 +798,12 @@ __global__ void __launch_bounds__(T, IPH_MINW) ip_fused_t(DevCtx d, int ring_pos
         const bool ok = ow != 0u;
         const float lx = __shfl_up(q.x, 1, 64), ly = __shfl_up(q.y, 1, 64), lz = __shfl_up(q.z, 1, 64);
         const bool lok = __shfl_up(ok ? 1 : 0, 1, 64) != 0;
-        const bool g = row >= 1 && row - 1 < P.ground_scan_id && ok && lok && ip_is_ground(d, q.x - lx, q.y - ly, q.z - lz);
+        const IpScreenBits gs = ip_ground_screen(d.ip_scr.g_lo, d.ip_scr.g_hi, d.ip_scr.g_max, q.x - lx, q.y - ly, q.z - lz);
+        const bool gen = row >= 1 && row - 1 < P.ground_scan_id && ok && lok;
+        bool g = gen && gs.yes;
+        if (__ballot(gen && gs.und)) {   // (rare, as above: the lanes the screen leaves undecided take the fp64 test)
+          if (gen && gs.und) g = ip_is_ground(d, q.x - lx, q.y - ly, q.z - lz);
+        }
         const unsigned gm = (unsigned)__ballot(g) & 0xFFFFu, fm = (unsigned)__ballot(ok) & 0xFFFFu;
         S.np.np_r[row] = ok ? sqrtf(q.x * q.x + q.y * q.y + q.z * q.z) : -1.0f;
         if (lane == 0) S.np.np_act = fm & ~(gm | (gm >> 1));   // (a ground pair (row - 1, row) marks both of its rows, :128-129)
@@ -784,39 +830,67 @@ __global__ void __launch_bounds__(T, IPH_MINW) ip_fused_t(DevCtx d, int ring_pos
       nb_act = S.np.np_act;
     }
     unsigned redge0 = 0, redge1 = 0, down0 = 0, down1 = 0;
+    unsigned ux0 = 0, ux1 = 0, uy0 = 0, uy1 = 0;   // the sites the screen leaves to fp64
     if (colv) {
-      // (the constants of the edge predicate as values of their own: read straight from `d` they belong to the 16-register tuple one s_load of the kernel
+      // (the constants of the screen as values of their own: read straight from `d` they belong to the 16-register tuple one s_load of the kernel
       // argument brought in; the kernel uses more uniform values than there are SGPRs, the allocator parks that tuple in VGPR lanes and read all 16 lanes
       // back in front of every one of the 64 edge sites)
-      double k_sax = d.sin_ax, k_cax = d.cos_ax, k_say = d.sin_ay, k_cay = d.cos_ay, k_tan = d.tan_theta, k_theta = P.seg_theta;
-      asm volatile("" : "+s"(k_sax), "+s"(k_cax), "+s"(k_say), "+s"(k_cay), "+s"(k_tan), "+s"(k_theta));
+      // Every site takes the f32 screen of ip_pred.h (no fp64, no branch); the sites are masked by their cells' activity afterwards.  A site the screen cannot
+      // decide is evaluated with the fp64 predicate in the block behind the loop, from its two cells gathered once more.
+      float k_kxh = d.ip_scr.kxh, k_kxl = d.ip_scr.kxl, k_kyh = d.ip_scr.kyh, k_kyl = d.ip_scr.kyl, k_eb = d.ip_scr.eband;
+      asm volatile("" : "+s"(k_kxh), "+s"(k_kxl), "+s"(k_kyh), "+s"(k_kyl), "+s"(k_eb));
 #pragma unroll
       for (int row = 0; row < IPF2_ROWS; ++row) {
-        if (row < NS) {
-          if ((act0 >> row) & 1u) {
-            const double r0 = (double)rng0[row];
-            if ((act1 >> row) & 1u) {   // same row, seg_alpha_x (:258-261)
-              const double r1 = (double)rng1[row], d1 = fmax(r0, r1), d2 = fmin(r0, r1);
-              if (edge_angle_gt(d2 * k_sax, d1 - d2 * k_cax, k_theta, k_tan)) redge0 |= 1u << row;
-            }
-            if (row + 1 < NS && ((act0 >> (row + 1)) & 1u)) {   // same column, seg_alpha_y (:262-265)
-              const double r1 = (double)rng0[row + 1 < IPF2_ROWS ? row + 1 : row], d1 = fmax(r0, r1), d2 = fmin(r0, r1);
-              if (edge_angle_gt(d2 * k_say, d1 - d2 * k_cay, k_theta, k_tan)) down0 |= 1u << row;
-            }
+        if (row < NS && __ballot(((act0 | act1) >> row) & 1u)) {   // (one test per row and wavefront: the rows that are all ground or all empty hold no site)
+          const float a0 = rng0[row], a1 = rng1[row];
+          {   // same row, seg_alpha_x (:258-261)
+            const IpScreenBits e = ip_edge_screen(fmaxf(a0, a1), fminf(a0, a1), k_kxh, k_kxl, k_eb);
+            redge0 |= e.yes ? 1u << row : 0u; ux0 |= e.und ? 1u << row : 0u;
           }
-          if ((act1 >> row) & 1u) {
-            const double r0 = (double)rng1[row];
-            if ((nb_act >> row) & 1u) {
-              const double r1 = (double)nbr[row], d1 = fmax(r0, r1), d2 = fmin(r0, r1);
-              if (edge_angle_gt(d2 * k_sax, d1 - d2 * k_cax, k_theta, k_tan)) redge1 |= 1u << row;
-            }
-            if (row + 1 < NS && ((act1 >> (row + 1)) & 1u)) {
-              const double r1 = (double)rng1[row + 1 < IPF2_ROWS ? row + 1 : row], d1 = fmax(r0, r1), d2 = fmin(r0, r1);
-              if (edge_angle_gt(d2 * k_say, d1 - d2 * k_cay, k_theta, k_tan)) down1 |= 1u << row;
+          {
+            const float nb = nbr[row];
+            const IpScreenBits e = ip_edge_screen(fmaxf(a1, nb), fminf(a1, nb), k_kxh, k_kxl, k_eb);
+            redge1 |= e.yes ? 1u << row : 0u; ux1 |= e.und ? 1u << row : 0u;
+          }
+          if (row + 1 < IPF2_ROWS) {   // same column, seg_alpha_y (:262-265)
+            const float b0 = rng0[row + 1 < IPF2_ROWS ? row + 1 : row], b1 = rng1[row + 1 < IPF2_ROWS ? row + 1 : row];
+            const IpScreenBits e = ip_edge_screen(fmaxf(a0, b0), fminf(a0, b0), k_kyh, k_kyl, k_eb);
+            down0 |= e.yes ? 1u << row : 0u; uy0 |= e.und ? 1u << row : 0u;
+            const IpScreenBits f = ip_edge_screen(fmaxf(a1, b1), fminf(a1, b1), k_kyh, k_kyl, k_eb);
+            down1 |= f.yes ? 1u << row : 0u; uy1 |= f.und ? 1u << row : 0u;
+          }
+        }
+      }
+      {
+        const unsigned sx0 = act0 & act1, sx1 = act1 & nb_act, sy0 = act0 & (act0 >> 1), sy1 = act1 & (act1 >> 1);   // the sites that exist (rows >= NS are never active)
+        redge0 &= sx0; redge1 &= sx1; down0 &= sy0; down1 &= sy1;
+        ux0 &= sx0; ux1 &= sx1; uy0 &= sy0; uy1 &= sy1;
+      }
+    }
+    {
+      const unsigned und_x = ux0 | (ux1 << 16), und_y = uy0 | (uy1 << 16);   // (0 in the lanes without a column pair)
+      if (__ballot((und_x | und_y) != 0u)) {   // rare: some lane holds a site inside the screen's band (or the screen is switched off)
+        IPH_SLOW_COUNT(2);
+        const double theta = P.seg_theta, tan_theta = d.tan_theta;
+#pragma unroll 1
+        for (int k = 0; k < 2; ++k) {
+          const double sa = k ? d.sin_ay : d.sin_ax, ca = k ? d.cos_ay : d.cos_ax;
+#pragma unroll 1
+          for (unsigned m = k ? und_y : und_x; m; m &= m - 1) {
+            const int b = __ffs((int)m) - 1, row = b & 15, c = c0 + (b >> 4);
+            const int cr = c + 1 == H ? 0 : c + 1;   // the right neighbour; column 0 behind the last one (:241-248)
+            const double r0 = (double)iph_cell_range(own16w, pts, H, row, c);
+            const double r1 = (double)(k ? iph_cell_range(own16w, pts, H, row + 1, c) : iph_cell_range(own16w, pts, H, row, cr));
+            const double d1 = fmax(r0, r1), d2 = fmin(r0, r1);
+            if (edge_angle_gt(d2 * sa, d1 - d2 * ca, theta, tan_theta)) {
+              const unsigned bit = 1u << row;
+              if (k) { if (b >> 4) down1 |= bit; else down0 |= bit; } else { if (b >> 4) redge1 |= bit; else redge0 |= bit; }
             }
           }
         }
       }
+    }
+    if (colv) {
       fcol[c0] = (unsigned long long)ground0 | ((unsigned long long)act0 << 16) | ((unsigned long long)redge0 << 32) | ((unsigned long long)down0 << 48);
       fcol[c1] = (unsigned long long)ground1 | ((unsigned long long)act1 << 16) | ((unsigned long long)redge1 << 32) | ((unsigned long long)down1 << 48);
       if (keep & 1) {
