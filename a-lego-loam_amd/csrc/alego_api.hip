@@ -259,6 +259,7 @@ int alego_create(const alego_params* params, int device, int n_slots, int ring_l
   d.opt_fe_pick1 = env_int("ALEGO_FE_PICK1", 0) != 0;
   d.opt_fe_fused = env_int("ALEGO_FE_FUSED", 1) != 0;
   d.opt_fe_cand = env_int("ALEGO_FE_CAND", 0);
+  d.opt_fe_span = env_int("ALEGO_FE_SPAN", 0);
   d.opt_lo_box_lds = env_int("ALEGO_LO_BOX_LDS", 1 << 20);
   d.opt_lo_grid = env_int("ALEGO_LO_GRID", 1) != 0;
   d.opt_fo_spin = env_int("ALEGO_FE_SPIN", 0);
@@ -1029,6 +1030,7 @@ int alego_debug_set_option(alego_handle* h, const char* name, int value) {
   else if (s == "ALEGO_FE_PICK1") d.opt_fe_pick1 = value != 0;
   else if (s == "ALEGO_FE_FUSED") d.opt_fe_fused = value != 0;
   else if (s == "ALEGO_FE_CAND") d.opt_fe_cand = value;
+  else if (s == "ALEGO_FE_SPAN") d.opt_fe_span = value;
   else if (s == "ALEGO_LO_BOX_LDS") d.opt_lo_box_lds = value;
   else if (s == "ALEGO_LO_GRID") d.opt_lo_grid = value != 0;
   else if (s == "ALEGO_FE_SPIN") d.opt_fo_spin = value;
@@ -1691,6 +1693,23 @@ int alego_debug_get(alego_handle* h, int slot, const char* name, void* out, int 
     if ((size_t)cap_bytes < bytes) { h->err = "debug_get: buffer too small"; return ALEGO_ERR_CAPACITY; }
     if (bytes) HIP_TRY(h, hipMemcpy(out, rsrc, bytes, hipMemcpyDeviceToHost));
     *count = (int)bytes; *dtype = 3;
+    return 0;
+  }
+  if (s == "fe_cand_span") {   // sectors per fe_cand wavefront (0: the whole ring), the list entries of a sector
+    if (cap_bytes < 8) { h->err = "debug_get: buffer too small"; return ALEGO_ERR_CAPACITY; }
+    ((int*)out)[0] = fe_cand_span(d); ((int*)out)[1] = fe_sector_cap(d);
+    *count = 2; *dtype = 2;
+    return 0;
+  }
+  if (s == "fe_cand_counts" || s == "fe_cand_lists") {   // what fe_cand wrote for the slot's last scan, ring by ring: [ring][sector][2] i32 counts (sharp, flat) / [ring][sector][sector_cap][2] u32 (key, pay) as i32
+    if (!fe_fused_eligible(d)) { h->err = "debug_get: " + s + " needs the fused feature extraction"; return ALEGO_ERR_ARG; }
+    const bool lists = s == "fe_cand_lists";
+    const size_t row = lists ? (size_t)d.P.n_sectors * fe_sector_cap(d) * sizeof(uint2) : (size_t)d.P.n_sectors * 2 * sizeof(int);
+    const void* src = lists ? (const void*)st_cand_of(d, slot, 0) : (const void*)st_idx_of(d, slot, 0, F_LFLAT);
+    const size_t pitch = lists ? (size_t)((const char*)st_cand_of(d, slot, 1) - (const char*)st_cand_of(d, slot, 0)) : (size_t)((const char*)st_idx_of(d, slot, 1, F_LFLAT) - (const char*)st_idx_of(d, slot, 0, F_LFLAT));
+    if ((size_t)cap_bytes < row * d.NS) { h->err = "debug_get: buffer too small"; return ALEGO_ERR_CAPACITY; }
+    HIP_TRY(h, hipMemcpy2D(out, row, src, pitch, row, d.NS, hipMemcpyDeviceToHost));
+    *count = (int)(row * d.NS / 4); *dtype = 2;
     return 0;
   }
   const size_t base = (size_t)slot * d.N, M = sc[SC_M];

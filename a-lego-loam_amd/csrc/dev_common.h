@@ -43,6 +43,7 @@ struct DevCtx {
   int opt_fe_pick1;     // ALEGO_FE_PICK1   1: one ring per wavefront (fe_pick) instead of fe_pick4
   int opt_fe_fused;     // ALEGO_FE_FUSED   1: feature extraction as fe_front + fe_ring_out (kernels_fe2.hip); 0: fe_curv + fe_pick* + fe_voxel + fe_collect
   int opt_fe_cand;      // ALEGO_FE_CAND    sharp candidates of a ring sector kept in LDS by fe_front (0: by geometry; the tests set 8 to drive the overflow path)
+  int opt_fe_span;      // ALEGO_FE_SPAN    1: fe_cand takes one wavefront per ring sector; anything else: per FC_SPAN sectors, the default (kernels_fe2.hip; the same template)
   int opt_lo_box_lds;   // ALEGO_LO_BOX_LDS boxes staged in LDS by lo_assoc (0: straight from HBM)
   int opt_map_merge;    // ALEGO_MAP_MERGE  1: local map from the pre-sorted key frames; 0: concat + radix VoxelGrid
   int opt_ip_screen;    // ALEGO_IP_SCREEN  1: ip_fused_h / ip_fused_w / ipb_band decide ground and edge tests in f32 where f32 can (ip_pred.h), in fp64 where it cannot; 0: every site in fp64

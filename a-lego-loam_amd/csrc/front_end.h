@@ -17,6 +17,8 @@ void launch_fe(const DevCtx& d, hipStream_t st);
 void launch_fe_curv_debug(const DevCtx& d, hipStream_t st);   // fe_curv alone (curvature sums / occlusion marks of the points outside every sector, tests only)
 int launch_stdsort_probe(const uint32_t* keys, int n, int depth_limit, int* pos_out, hipStream_t st);
 bool fe_fused_eligible(const DevCtx& d);
+int fe_cand_span(const DevCtx& d);    // sectors of a ring per fe_cand wavefront as the handle runs it (0: the whole ring; alego_debug_get "fe_cand_span")
+int fe_sector_cap(const DevCtx& d);   // entries of a ring sector's candidate list (fe_cand; alego_debug_get "fe_cand_lists")
 void launch_fe_fused(const DevCtx& d, hipStream_t st);
 // kernels_lo.hip
 void launch_lo(const DevCtx& d, hipStream_t st);

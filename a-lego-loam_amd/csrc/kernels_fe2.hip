@@ -1,9 +1,10 @@
 // kernels_fe2.hip — feature extraction in two launches (round 4; replaces fe_curv + fe_pick4 + fe_voxel + fe_collect of kernels_fe.hip,
 // which stay behind ALEGO_FE_FUSED=0 as the cross-check and as the path of sort_mode 2).  src/laserOdometry.cpp:122-293.
 //
-//   fe_cand      a7-a8 + candidates: one wavefront per (stream, ring, sector), all of them at once.  The sector's ranges / columns are staged
-//                once in LDS; the 11-tap curvature sum (:122-129), the occlusion / parallel-beam marks (:131-159, as ballot masks — no
-//                per-point flag array), the thresholds and each point's suppression reach (how far the +-5 marking of :211-234 gets before a
+//   fe_cand      a7-a8 + candidates: one wavefront per (stream, ring) — per FC_SPAN sectors of a ring — all of them at once.  The ring's ranges / columns
+//                roll through a 256-point window in LDS, each staged once; the 11-tap curvature sum (:122-129), the occlusion / parallel-beam marks
+//                (:131-159, as ballot masks in scalar registers — no per-point flag array, in LDS or elsewhere), the thresholds and each point's
+//                suppression reach (how far the +-5 marking of :211-234 gets before a
 //                column jump stops it) are evaluated per point, and the sector's sharp / flat CANDIDATES — a 16 x 1800 sector has ~190 points,
 //                ~32 sharp and ~12 flat candidates — go to a short list (8 B per candidate; it stays in the L2).  Reads range / column /
 //                ground (9 B per point); no curvature or flag array is written.
@@ -30,38 +31,48 @@
 // ---------------------------------------------------------------------------------------------------------------------------------
 #ifndef FF_G
 #define FF_G 4        // rings per picking wavefront (64 / FF_G lanes each): 4 (default) or 8 — eight rings per wavefront issue a quarter fewer instructions, but the
-                      // kernel is a latency chain: four rings finish in 166 instead of 292 us alone and the bench gains 1.1 % (424.9 k -> 429.4 k scans/s, same box)
+                      // kernel is a latency chain: four rings finish in 166 instead of 292 us alone and the bench gains 1.1 % (424.9 k -> 429.4 k scans/s, same box).
+                      // Measured again at 4 096 streams on top of the ring-span fe_cand (profiles/r10_fe_cand_span.md, four alternating runs each): 4 gives 491.7 -
+                      // 494.7 k scans/s (median 493.1), 8 gives 490.8 - 492.9 k (median 491.9): still not a gain, 4 stays
 #endif
 #define FF_LPR (64 / FF_G)
-#define FF_HALO 8     // staged points either side of a sector (11-tap sum: 5, occlusion marks of the neighbours: 6)
-#define FF_Q0 64      // staging position of a sector's first point: the sector's 64-point chunks are the ballot masks' chunks
-#ifndef FC_NW
-#define FC_NW 4       // ring sectors (wavefronts) per fe_cand workgroup
+#define FF_HALO 8     // staged points either side of a span (11-tap sum: 5, occlusion marks of the neighbours: 6)
+#ifndef FC_SPAN
+#define FC_SPAN 0     // consecutive sectors of a ring per fe_cand wavefront: 0 (default) the whole ring, 1 one sector each (what ALEGO_FE_SPAN=1 runs, the cross-check);
+                      // 2, 3 and 0 measured: the longer the span the fewer instructions and the higher the throughput (profiles/r10_fe_cand_span.md)
 #endif
+#ifndef FC_NW
+#define FC_NW 4       // spans (wavefronts) per fe_cand workgroup
+#endif
+#define FF_WIN 256    // staged positions of a wavefront: a rolling window of four 64-point chunks (the one emitted, its two neighbours, the one being staged)
 
-struct FfLayout {     // dynamic LDS of one fe_cand wavefront, in bytes
-  int scap, mch, wave_bytes;      // staged positions (multiple of 64), mask chunks
+// LDS of one fe_cand wavefront, in bytes: the window of ranges (f32) and of columns | ground << 15 (u16), each with FF_HALO mirrored entries in front of
+// and behind it (the head of the window's first chunk again behind its last, the tail of its last in front of its first), so that a lane reads its
+// neighbours q - 5 .. q + 5 at constant offsets from one address.  It depends on no geometry: a span of any length rolls through it.
+struct FfLayout {
+  int cols, wave_bytes;      // offset of the columns, size
 };
-__host__ __device__ inline FfLayout ff_layout(int sector_cap) {
-  FfLayout L;
-  L.scap = (FF_Q0 + sector_cap + FF_HALO + 63) & ~63;
-  L.mch = L.scap / 64 + 1;
-  L.wave_bytes = (8 * 4 * L.mch + 4 * L.scap + 2 * L.scap + 7) & ~7;   // masks u64 [4][mch], ranges f32 [scap], columns | ground << 15 u16 [scap]
-  return L;
+__host__ __device__ constexpr FfLayout ff_layout() {
+  return FfLayout{4 * (FF_WIN + 2 * FF_HALO), (4 + 2) * (FF_WIN + 2 * FF_HALO)};
 }
+static_assert(ff_layout().wave_bytes % 8 == 0, "a wavefront's LDS slice keeps the alignment of the first");
 
 // bits [pos, pos + 64) of the 128-bit value hi:lo
 DEV_INLINE unsigned long long ext128(unsigned long long lo, unsigned long long hi, int pos) { return (lo >> pos) | (pos ? hi << (64 - pos) : 0ull); }
 
-DEV_INLINE void ff_sector(const alego_params& P, int S, int E, int j, int& sp, int& ep) {
+// first point of sector j of the ring [S, E] (laserOdometry.cpp:177, LO.cpp:245); j = n_sectors gives E.  Sectors are contiguous: the last point of
+// sector j (:178, :249) is the one before the first point of sector j + 1, in both formulas
+DEV_INLINE int ff_sector_start(const alego_params& P, int S, int E, int j) {
   const int NSEC = P.n_sectors;
   if (NSEC == 6) {   // the reference's six sectors: divisions by a constant (a handful of instructions instead of ~35 each)
-    if (P.sector_formula == 0) { sp = (S * (6 - j) + E * j) / 6; ep = (S * (5 - j) + E * (j + 1)) / 6 - 1; }
-    else { const int diff = E - S; sp = S + j * diff / 6; ep = S + (j + 1) * diff / 6 - 1; }
-    return;
+    if (P.sector_formula == 0) return (S * (6 - j) + E * j) / 6;
+    return S + j * (E - S) / 6;
   }
-  if (P.sector_formula == 0) { sp = (S * (NSEC - j) + E * j) / NSEC; ep = (S * (NSEC - 1 - j) + E * (j + 1)) / NSEC - 1; }   // laserOdometry.cpp:177-178
-  else { const int diff = E - S; sp = S + j * diff / NSEC; ep = S + (j + 1) * diff / NSEC - 1; }                               // LO.cpp:245-249
+  if (P.sector_formula == 0) return (S * (NSEC - j) + E * j) / NSEC;
+  return S + j * (E - S) / NSEC;
+}
+DEV_INLINE void ff_sector(const alego_params& P, int S, int E, int j, int& sp, int& ep) {
+  sp = ff_sector_start(P, S, E, j); ep = ff_sector_start(P, S, E, j + 1) - 1;
 }
 
 // The candidate list of one ring sector, in HBM (it stays in the L2 between fe_cand and fe_pickc): `sector_cap` entries (key, pay); the sharp
@@ -75,42 +86,65 @@ DEV_INLINE int* ff_counts(const DevCtx& d, int slot, int ring) {   // [sector][2
   return st_idx_of(d, slot, ring, F_LFLAT);
 }
 
-// One sector [sp, ep] of one ring, all 64 lanes of the calling wavefront: the ring's ranges / columns are staged once in LDS; the 11-tap
-// curvature sum (:122-129), the occlusion / parallel-beam marks (:131-159) as ballot masks — no per-point flag array — the thresholds and each
-// point's suppression reach (how far the +-5 marking of :211-234 gets before a column jump stops it) are evaluated per point, and the
-// sector's sharp / flat candidates are compacted into `list`.  Two workgroup barriers (matched by callers that skip a sector).
-DEV_INLINE void ff_wide(const DevCtx& d, size_t base, int M, int sp, int ep, unsigned char* wl, const FfLayout& L, uint2* list, int sector_cap, int& ns_out, int& nf_out, bool dbg) {
+// what orders a wavefront's LDS stores before the loads of its other lanes: LDS operations of one wavefront execute in order, so all it takes is
+// that the compiler keeps them in program order (no instruction but, at most, a wait)
+DEV_INLINE unsigned long long ff_ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }   // (of a bool: the lane mask itself, no 0 / 1 value per lane in between)
+DEV_INLINE void ff_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// The sectors [j0, j1) of one ring [S, E] — a span: contiguous points [lo, hi] — all 64 lanes of the calling wavefront.  Point k sits at staging position
+// q = k - lo + FF_HALO; the 64-point chunks are those of q, whatever sector a point belongs to.  One sweep over the chunks: chunk c + 3 is staged
+// (ranges / columns / ground, once per point), the per-point predicates of markOccludedPoints (:131-159) and the column jumps of the suppression
+// (:214, :226) of chunk c + 1 become four ballot masks — scalars, carried for the chunks c - 1, c, c + 1; no per-point flag array — and chunk c is emitted:
+// the 11-tap curvature sum (:122-129), the thresholds and each point's suppression reach (how far the +-5 marking of :211-234 gets before a column
+// jump stops it), and the sharp / flat candidates compacted into the list of the sector each lane's point lies in.  Everything per point depends on
+// k, M and the staged neighbours within +-6 alone, so the bits do not depend on where a span begins or ends.
+DEV_INLINE void ff_span(const DevCtx& d, size_t base, int M, int S, int E, int j0, int j1, unsigned char* wl, uint2* list, int* cc, int sector_cap, bool dbg) {
   const int lane = threadIdx.x & 63;
   const alego_params& P = d.P;
-  unsigned long long* mA = reinterpret_cast<unsigned long long*>(wl);
-  unsigned long long* mB = mA + L.mch, *mC = mB + L.mch, *mJ = mC + L.mch;
-  float* sr = reinterpret_cast<float*>(wl + 8 * 4 * L.mch);
-  uint16_t* scl = reinterpret_cast<uint16_t*>(wl + 8 * 4 * L.mch + 4 * L.scap);
+  constexpr FfLayout L = ff_layout();
+  float* sr = reinterpret_cast<float*>(wl) + FF_HALO;                    // sr[-FF_HALO .. FF_WIN + FF_HALO)
+  uint16_t* scl = reinterpret_cast<uint16_t*>(wl + L.cols) + FF_HALO;
   const float* rng = d.seg_range + base;
   const int* colv = d.seg_col + base;
   const uint8_t* gndv = d.seg_ground + base;
-  const int len = ep - sp + 1;
-  const int q0 = FF_Q0 - FF_HALO, q1 = FF_Q0 + len + FF_HALO;   // staged positions [q0, q1): point k sits at q = k - sp + FF_Q0
-#pragma unroll 2
-  for (int q = q0 + lane; q < q1; q += 64) {
-    const int k = sp + q - FF_Q0;
-    const bool in = k >= 0 && k < M;
-    const unsigned ku = in ? (unsigned)k : 0u;   // (uniform base + unsigned 32-bit index: no 64-bit address arithmetic per lane)
-    const float r = rng[ku];
-    const int c = colv[ku];
-    const uint8_t g = gndv[ku];
-    sr[q] = in ? r : 0.f;
-    scl[q] = in ? (uint16_t)((c & 0x7fff) | (g ? 0x8000 : 0)) : (uint16_t)0;
+  const int lo = ff_sector_start(P, S, E, j0), hi = ff_sector_start(P, S, E, j1) - 1;
+  const int len = hi - lo + 1;
+  if (len < 2) {   // no sector of the span has two points (an empty ring: hi < lo): no candidates
+    for (int j = j0 + lane; j < j1; j += 64) { cc[2 * j] = 0; cc[2 * j + 1] = 0; }
+    return;
   }
-  __syncthreads();
-  // per-point predicates of markOccludedPoints (:131-159) and the column jumps of the suppression (:214,:226) as one bit per point
-  const int nch = (q1 + 63) >> 6;
-  for (int ch = 0; ch < nch; ++ch) {
-    const int q = ch * 64 + lane, k = sp + q - FF_Q0;
-    const bool inr = q > q0 && q < q1 - 1;
-    const int qa = min(max(q, q0 + 1), q1 - 2);
-    const float r0 = sr[qa], r1 = sr[qa + 1], rm = sr[qa - 1];
-    const int c0 = scl[qa] & 0x7fff, c1 = scl[qa + 1] & 0x7fff;
+  const int q1 = len + 2 * FF_HALO;   // staged positions [0, q1)
+  const int nc = (FF_HALO + len + 63) >> 6;   // chunks with points of the span
+  const unsigned long long below = (1ull << lane) - 1ull;
+  const int SR = P.suppress_radius;
+
+  // staging in two halves, a turn apart: the loads of chunk t (unconditional, from clamped addresses) are in flight while the turn before computes;
+  // nothing looks at what they return before stage() does
+  auto fetch = [&](int t, float& r, int& c, uint8_t& g) {
+    const int k = lo + t * 64 + lane - FF_HALO;
+    const unsigned ku = (k >= 0 && k < M) ? (unsigned)k : 0u;   // (uniform base + unsigned 32-bit index: no 64-bit address arithmetic per lane)
+    r = rng[ku]; c = colv[ku]; g = gndv[ku];
+  };
+  auto stage = [&](int t, float r, int c, uint8_t g) {   // chunk t of the positions into its quarter of the window
+    const int k = lo + t * 64 + lane - FF_HALO;
+    const bool in = k >= 0 && k < M;
+    const float rv = in ? r : 0.f;
+    const uint16_t cv = in ? (uint16_t)((c & 0x7fff) | (g ? 0x8000 : 0)) : (uint16_t)0;
+    const int w = t & 3, p = w * 64 + lane;
+    sr[p] = rv; scl[p] = cv;
+    if (w == 0 && lane < FF_HALO) { sr[p + FF_WIN] = rv; scl[p + FF_WIN] = cv; }
+    if (w == 3 && lane >= 64 - FF_HALO) { sr[p - FF_WIN] = rv; scl[p - FF_WIN] = cv; }
+  };
+  auto marks = [&](int m, unsigned long long& a, unsigned long long& b, unsigned long long& c, unsigned long long& j) {   // the four masks of chunk m
+    const int q = m * 64 + lane, k = lo + q - FF_HALO;
+    const bool inr = q > 0 && q < q1 - 1;
+    const int pa = (m & 3) * 64 + lane;   // (pa - 1 and pa + 1 stay inside the window and its mirrors; a lane outside inr reads entries nothing staged and drops what it computes)
+    const float r0 = sr[pa], r1 = sr[pa + 1], rm = sr[pa - 1];
+    const int c0 = scl[pa] & 0x7fff, c1 = scl[pa + 1] & 0x7fff;
     int cdiff = c0 - c1;
     cdiff = cdiff < 0 ? -cdiff : cdiff;
     bool c1b, c2b;
@@ -129,59 +163,88 @@ DEV_INLINE void ff_wide(const DevCtx& d, size_t base, int M, int sp, int ep, uns
     const bool B = okp && near && !c1b && c2b;     // marks i+1..i+5 (:148)
     const bool C = okp && !A && diff1 > P.parallel_ratio * (double)r0 && diff2 > P.parallel_ratio * (double)r0;  // (:154-157)
     const bool J = inr && k + 1 < M && cdiff > P.suppress_col_diff;   // |col[k + 1] - col[k]|
-    const unsigned long long a = __ballot(A), b = __ballot(B), c = __ballot(C), j = __ballot(J);
-    if (lane == 0) { mA[ch] = a; mB[ch] = b; mC[ch] = c; mJ[ch] = j; }
-  }
-  __syncthreads();
-  int ns = 0, nf = 0;
-  const int SR = P.suppress_radius;
-  for (int it = 0; it * 64 < len; ++it) {
-    const int ch = it + 1, q = ch * 64 + lane, loc = it * 64 + lane, k = sp + loc;
-    const bool own = loc < len;
-    const bool gnd = (scl[q] & 0x8000) != 0;
+    a = ff_ballot(A); b = ff_ballot(B); c = ff_ballot(C); j = ff_ballot(J);
+  };
+
+  float fr = 0.f, fr1 = 0.f, fr2 = 0.f;
+  int fc = 0, fc1 = 0, fc2 = 0;
+  uint8_t fg = 0, fg1 = 0, fg2 = 0;
+  fetch(0, fr, fc, fg);          // the window's first three chunks: their loads together, then staged
+  if (64 < q1) fetch(1, fr1, fc1, fg1);
+  if (128 < q1) fetch(2, fr2, fc2, fg2);
+  stage(0, fr, fc, fg);
+  if (64 < q1) stage(1, fr1, fc1, fg1);
+  if (128 < q1) stage(2, fr2, fc2, fg2);
+  if (192 < q1) fetch(3, fr, fc, fg);
+  ff_wave_sync();
+  unsigned long long bp = 0ull, jp = 0ull, a0, b0, c0m, j0m, a1 = 0ull, b1 = 0ull, c1m = 0ull, j1m = 0ull;   // masks of the chunks c - 1 (B and J: the ones read backwards), c, c + 1
+  marks(0, a0, b0, c0m, j0m);
+  int jc = j0, spc = lo, nxt = ff_sector_start(P, S, E, j0 + 1), ns = 0, nf = 0;   // the sector the sweep is in: [spc, nxt - 1], its candidates so far
+  for (int c = 0; c < nc; ++c) {   // the window holds the chunks c - 1 .. c + 2; the loads of chunk c + 3 are in flight
+    ff_wave_sync();
+    if ((c + 1) * 64 < q1) marks(c + 1, a1, b1, c1m, j1m);
+    else { a1 = 0ull; b1 = 0ull; c1m = 0ull; j1m = 0ull; }
+    const int q = c * 64 + lane, k = lo + q - FF_HALO, p = (c & 3) * 64 + lane;
+    const bool gnd = (scl[p] & 0x8000) != 0;
     // strictly left-to-right f32 sum (:124); built with -ffp-contract=off
-    const float cdv = sr[q - 5] + sr[q - 4] + sr[q - 3] + sr[q - 2] + sr[q - 1] - sr[q] * 10 + sr[q + 1] + sr[q + 2] + sr[q + 3] + sr[q + 4] + sr[q + 5];
-    const unsigned long long a0 = mA[ch], a1 = ch + 1 < nch ? mA[ch + 1] : 0ull;
-    const unsigned long long bp = mB[ch - 1], b0 = mB[ch];
-    const unsigned long long j0 = mJ[ch], j1 = ch + 1 < nch ? mJ[ch + 1] : 0ull, jp = mJ[ch - 1];
+    const float cdv = sr[p - 5] + sr[p - 4] + sr[p - 3] + sr[p - 2] + sr[p - 1] - sr[p] * 10 + sr[p + 1] + sr[p + 2] + sr[p + 3] + sr[p + 4] + sr[p + 5];
     const bool anyA = (ext128(a0, a1, lane) & 0x3full) != 0;                                    // A(i'), i' in [i, i+5]
     const bool anyB = (ext128((bp >> 59) | (b0 << 5), b0 >> 59, lane) & 0x1full) != 0;         // B(i'), i' in [i-5, i-1]
-    const bool pk = ((mC[ch] >> lane) & 1ull) || anyA || anyB;
-    const unsigned f5 = (unsigned)(ext128(j0, j1, lane) & 0x1full);                             // jumps at i .. i+4
-    const unsigned w5 = (unsigned)(ext128((jp >> 59) | (j0 << 5), j0 >> 59, lane) & 0x1full);  // jumps at i-5 .. i-1 (bit 4 = i-1)
+    const bool pk = ((c0m >> lane) & 1ull) || anyA || anyB;
+    const unsigned f5 = (unsigned)(ext128(j0m, j1m, lane) & 0x1full);                           // jumps at i .. i+4
+    const unsigned w5 = (unsigned)(ext128((jp >> 59) | (j0m << 5), j0m >> 59, lane) & 0x1full);  // jumps at i-5 .. i-1 (bit 4 = i-1)
     const int rf = min(SR, __ffs((int)(f5 | 0x20u)) - 1), rb = min(SR, __clz((int)(w5 << 27)));
     const double ad = (double)fabsf(cdv), curv = ad * ad;                                       // (double)diff_range * diff_range, exact (:125)
-    const bool free_ = own && !pk;
-    const bool cs = free_ && !gnd && curv > P.edge_thres;
-    const bool cf = free_ && gnd && curv < P.surf_thres;
+    const bool cs0 = !pk && !gnd && curv > P.edge_thres;
+    const bool cf0 = !pk && gnd && curv < P.surf_thres;
     const uint32_t kb = (uint32_t)d_f2i(fabsf(cdv));
-    const uint32_t pay = ((uint32_t)loc << 6) | ((uint32_t)rf << 3) | (uint32_t)rb;
-    const unsigned long long ms = __ballot(cs), mf = __ballot(cf), below = (1ull << lane) - 1ull;
-    if (cs) list[(unsigned)(ns + (int)__popcll(ms & below))] = make_uint2(kb + 1u, pay);
-    if (cf) list[(unsigned)(sector_cap - 1 - (nf + (int)__popcll(mf & below)))] = make_uint2(~kb, ~pay);
-    ns += (int)__popcll(ms); nf += (int)__popcll(mf);
+    const uint32_t reach = ((uint32_t)rf << 3) | (uint32_t)rb;
+    const int klast = lo + c * 64 + 63 - FF_HALO;   // the chunk's last point
+    // chunk c + 3 takes the place of chunk c - 1, which this turn's lanes have read the tail of; staging waits for its loads here, behind the turn's
+    // arithmetic and before the turn's stores, so that the wait never covers a store just issued
+    ff_wave_sync();
+    if ((c + 3) * 64 < q1) stage(c + 3, fr, fc, fg);
+    if ((c + 4) * 64 < q1) fetch(c + 4, fr, fc, fg);
+    bool own = false;
+    while (true) {   // the sectors with points in this chunk: one, mostly; each lane's sector from k and the scalar bounds
+      const bool in = k >= spc && k < nxt && nxt - spc >= 2;   // (:181: a sector of one point is skipped)
+      const bool cs = cs0 && in, cf = cf0 && in;
+      const uint32_t pay = ((uint32_t)(k - spc) << 6) | reach;
+      const unsigned long long ms = ff_ballot(cs), mf = ff_ballot(cf);
+      if (cs) list[(unsigned)(ns + (int)__popcll(ms & below))] = make_uint2(kb + 1u, pay);
+      if (cf) list[(unsigned)(sector_cap - 1 - (nf + (int)__popcll(mf & below)))] = make_uint2(~kb, ~pay);
+      ns += (int)__popcll(ms); nf += (int)__popcll(mf);
+      own = own || in;
+      if (nxt > klast || jc + 1 >= j1) break;   // the sector goes on in the next chunk, or is the span's last
+      if (lane == 0) { cc[2 * jc] = ns; cc[2 * jc + 1] = nf; }
+      ++jc; spc = nxt; nxt = ff_sector_start(P, S, E, jc + 1); ns = 0; nf = 0; list += sector_cap;
+    }
     if (dbg && own) { d.cd[base + k] = cdv; d.picked0[base + k] = pk ? 1 : 0; }
+    bp = b0; jp = j0m; a0 = a1; b0 = b1; c0m = c1m; j0m = j1m;
   }
-  ns_out = ns; nf_out = nf;
+  if (lane == 0) {
+    cc[2 * jc] = ns; cc[2 * jc + 1] = nf;
+    for (int j = jc + 1; j < j1; ++j) { cc[2 * j] = 0; cc[2 * j + 1] = 0; }   // (empty sectors behind the span's last point)
+  }
 }
 
-// one wavefront per (ring, sector) — every sector of every ring of every stream at once, nothing sequential
+// one wavefront per span of SPAN consecutive sectors of a ring (SPAN <= 0: the whole ring; a ring's last span may be shorter) — every span of every
+// ring of every stream at once, nothing sequential, and nothing shared between the FC_NW wavefronts of a workgroup but the launch
+template <int SPAN>
 __global__ void __launch_bounds__(64 * FC_NW) fe_cand(DevCtx d, int sector_cap) {
-  // (the wavefront's number through readfirstlane: ring, sector, their bounds and every pointer derived from them are then scalar — the compiler cannot
+  // (the wavefront's number through readfirstlane: ring, span, their bounds and every pointer derived from them are then scalar — the compiler cannot
   // know that threadIdx.x >> 6 is uniform, and computed all of it per lane with 64-bit vector arithmetic)
-  const int slot = blockIdx.y + d.slot0, lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int slot = blockIdx.y + d.slot0, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int NS = d.NS, NSEC = d.P.n_sectors;
-  const int item = blockIdx.x * FC_NW + wave, ring = item / NSEC, j = item - ring * NSEC;
+  const int nspan = SPAN > 0 ? (NSEC + SPAN - 1) / SPAN : 1;
+  const int item = blockIdx.x * FC_NW + wave, ring = item / nspan, s = item - ring * nspan;
+  if (ring >= NS) return;
+  const int j0 = SPAN > 0 ? s * SPAN : 0, j1 = SPAN > 0 ? min(j0 + SPAN, NSEC) : NSEC;
   const size_t base = (size_t)slot * d.N;
   const int M = scal_of(d, slot)[SC_M];
-  extern __shared__ __attribute__((aligned(16))) unsigned char ff_smem[];
-  const FfLayout L = ff_layout(sector_cap);
-  int sp = 0, ep = -1;
-  if (ring < NS) ff_sector(d.P, *ring_start_of(d, slot, ring), *ring_end_of(d, slot, ring), j, sp, ep);
-  int ns = 0, nf = 0;
-  if (sp < ep) ff_wide(d, base, M, sp, ep, ff_smem + wave * L.wave_bytes, L, ff_list(d, slot, ring, j, sector_cap), sector_cap, ns, nf, d.n_launch == 1);
-  else { __syncthreads(); __syncthreads(); }
-  if (ring < NS && lane == 0) { int* cc = ff_counts(d, slot, ring); cc[2 * j] = ns; cc[2 * j + 1] = nf; }
+  __shared__ __attribute__((aligned(16))) unsigned char ff_smem[FC_NW * ff_layout().wave_bytes];
+  ff_span(d, base, M, *ring_start_of(d, slot, ring), *ring_end_of(d, slot, ring), j0, j1, ff_smem + wave * ff_layout().wave_bytes,
+          ff_list(d, slot, ring, j0, sector_cap), ff_counts(d, slot, ring), sector_cap, d.n_launch == 1);
 }
 
 // what the eight ring groups of the picking wavefront carry from sector to sector
@@ -924,6 +987,9 @@ __global__ void __launch_bounds__(FO_BLOCK) fe_ring_out(DevCtx d) {
   FO_TICK(8);
 }
 
+int fe_sector_cap(const DevCtx& d) { return (d.H + d.P.n_sectors - 1) / (d.P.n_sectors > 0 ? d.P.n_sectors : 1) + 2; }
+int fe_cand_span(const DevCtx& d) { return d.opt_fe_span == 1 ? 1 : FC_SPAN; }
+
 // fused path: everything but alego_params.sort_mode = 2 (the libstdc++ tie order needs the whole sector's keys: four-kernel path)
 // (and only sector counts whose candidate lists fit where they are kept: n_sectors * sector_cap 8-byte entries in a ring's 16 H-byte staging row (ff_list),
 // 2 n_sectors counts in the H-int tail of its index row (ff_counts), one thread per sector for the one-point sectors (fe_ring_out) — anything else, e.g.
@@ -931,17 +997,20 @@ __global__ void __launch_bounds__(FO_BLOCK) fe_ring_out(DevCtx d) {
 bool fe_fused_eligible(const DevCtx& d) {
   const int nsec = d.P.n_sectors;
   if (!(d.opt_fe_fused && !d.opt_fe_pick1 && d.P.sort_mode != 2 && d.NS <= 64 && d.H <= FE_MAXH && nsec >= 1)) return false;
-  const long long sector_cap = (d.H + nsec - 1) / nsec + 2;
+  const long long sector_cap = fe_sector_cap(d);
   return nsec <= FO_BLOCK && (long long)nsec * sector_cap <= 2LL * d.H && 2LL * nsec <= d.H;
 }
 
 void launch_fe_fused(const DevCtx& d, hipStream_t st) {
   static const bool cfg = hipFuncSetAttribute(reinterpret_cast<const void*>(fe_ring_out), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fo_lds_bytes(FE_MAXH)) == hipSuccess;
   (void)cfg;
-  const int sector_cap = (d.H + d.P.n_sectors - 1) / (d.P.n_sectors > 0 ? d.P.n_sectors : 1) + 2;
+  const int sector_cap = fe_sector_cap(d);
   if (d.n_launch == 1) launch_fe_curv_debug(d, st);
-  const FfLayout L = ff_layout(sector_cap);
-  ALEGO_LAUNCH(fe_cand, dim3((d.NS * d.P.n_sectors + FC_NW - 1) / FC_NW, d.n_launch), dim3(64 * FC_NW), (size_t)FC_NW * L.wave_bytes, st, d, sector_cap);
+  // one wavefront per FC_SPAN sectors of a ring; ALEGO_FE_SPAN=1: per sector, the same template (the cross-check of tests/test_fe_cand_span.py)
+  const int nsec = d.P.n_sectors, nspan = (d.opt_fe_span == 1 || FC_SPAN == 1) ? nsec : (FC_SPAN > 0 ? (nsec + FC_SPAN - 1) / FC_SPAN : 1);
+  const dim3 gc((d.NS * nspan + FC_NW - 1) / FC_NW, d.n_launch);
+  if (d.opt_fe_span == 1) { ALEGO_LAUNCH(fe_cand<1>, gc, dim3(64 * FC_NW), 0, st, d, sector_cap); }
+  else { ALEGO_LAUNCH(fe_cand<FC_SPAN>, gc, dim3(64 * FC_NW), 0, st, d, sector_cap); }
   // registers hold up to 96 sharp + 32 flat candidates of a ring sector (192 + 64 for sectors of more than 400 points: 16 x 4000 has up to ~140 /
   // ~200); longer lists are picked from memory (ff_pick_mem; ALEGO_FE_CAND != 0 sends everything beyond 64 / 8 there: tests)
   const dim3 gp((d.NS + FF_G - 1) / FF_G, d.n_launch);

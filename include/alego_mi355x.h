@@ -221,7 +221,10 @@ int alego_pose_o2b(const alego_pose* o2l, const double* tf_b2l, alego_pose* o2b)
 int alego_set_lo_params(alego_handle* h, int slot, const double* p6);
 int alego_set_lm_params(alego_handle* h, int slot, const double* p6);
 /* copy a named device intermediate of `slot` to host; *count = number of scalars written.
- * dtype: 0 f32, 1 f64, 2 i32, 3 u8.  Names mirror oracle_get(). */
+ * dtype: 0 f32, 1 f64, 2 i32, 3 u8.  Names mirror oracle_get().  Of the fused feature extraction's candidate kernel (fe_cand) for the slot's
+ * last scan, as i32: "fe_cand_span" = {sectors of a ring per wavefront (0: all; ALEGO_FE_SPAN=1: one), sector_cap}, "fe_cand_counts" =
+ * [ring][sector]{sharp, flat candidates}, "fe_cand_lists" = [ring][sector][sector_cap]{key, pay}: the sharp candidates from the front of a
+ * sector's list, the flat ones from its back (fe_pickc clears the keys of entries it picks from memory). */
 int alego_debug_get(alego_handle* h, int slot, const char* name, void* out, int cap_bytes,
                     int* count, int* dtype);
 /* the device pcl::VoxelGrid replacement on a host cloud (the LDS-resident radix sort for <= 8192 points, the HBM-scratch
