@@ -35,7 +35,7 @@ EXPORTS = [
     "alego_graph_enable", "alego_graph_status", "alego_graph_get_edges", "alego_graph_set_edges", "alego_graph_add_loops", "alego_graph_add_edge",
     "alego_graph_optimize", "alego_graph_get_estimate", "alego_graph_residuals",
     "alego_graph_marginals", "alego_graph_check_edges", "alego_graph_check_loops", "alego_graph_covariance_host", "alego_graph_check_host",
-    "alego_loc_select", "alego_loc_enable", "alego_loc_status",
+    "alego_loc_select", "alego_loc_enable", "alego_loc_status", "alego_loc_enable_from_map", "alego_loc_update_from_map",
     "alego_reloc_enable", "alego_loc_relocalize", "alego_reloc_descriptor", "alego_reloc_match", "alego_debug_reloc_search",
     "alego_loop_appearance_enable", "alego_loop_search_appearance", "alego_loop_appearance_candidates",
     "alego_map_align", "alego_map_align_queries", "alego_map_align_consensus", "alego_map_align_poses",
@@ -433,6 +433,8 @@ def lib():
         L.alego_loc_select.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_int32, C.c_void_p]
         L.alego_loc_enable.argtypes = [C.c_void_p, C.POINTER(KfIn), C.c_int32, C.c_double]
         L.alego_loc_status.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.alego_loc_enable_from_map.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int32]
+        L.alego_loc_update_from_map.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.alego_reloc_enable.argtypes = [C.c_void_p, C.c_double, C.c_double]
         L.alego_loc_relocalize.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(RelocOpts), C.POINTER(RelocResult)]
         L.alego_reloc_descriptor.argtypes = [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
@@ -1237,6 +1239,22 @@ class Handle:
             kfs[i].surf, kfs[i].n_surf = arrs[1].ctypes.data, arrs[1].shape[0]
             kfs[i].outlier, kfs[i].n_outlier = arrs[2].ctypes.data, arrs[2].shape[0]
         self._check(lib().alego_loc_enable(self._h, kfs, len(frames), float(radius)), "alego_loc_enable")
+
+    def loc_enable_from_map(self, map_handle, slot=0, radius=0.0, capacity=0):
+        """the map store from the archive of `slot` of the mapping Handle `map_handle` as it is now, built on the device (capacity: frames allocated, 0 = as many as archived)"""
+        self._check(lib().alego_loc_enable_from_map(self._h, map_handle._h if map_handle is not None else None, slot, float(radius), int(capacity)), "alego_loc_enable_from_map")
+
+    def loc_update_from_map(self, map_handle, slot=0):
+        """the whole store again from the archive as it is now; every slot's window is reset"""
+        self._check(lib().alego_loc_update_from_map(self._h, map_handle._h if map_handle is not None else None, slot), "alego_loc_update_from_map")
+
+    def loc_store_frame(self, f):
+        """row f of the map store (debug read-outs): sorted runs, their counts and boxes, the raw clouds, the pose"""
+        g = lambda name, cap: self.debug_get(f"{name}:{f}", cap_bytes=cap)
+        big = 16 * self.N + 4096
+        return dict(corner=g("ls_corner", big).reshape(-1, 4), surf=g("ls_surf", 2 * big).reshape(-1, 4), box_c=g("ls_box_c", 64), box_s=g("ls_box_s", 64),
+                    raw_c=g("ls_raw_c", big).reshape(-1, 4), raw_s=g("ls_raw_s", big).reshape(-1, 4), raw_o=g("ls_raw_o", big).reshape(-1, 4),
+                    pose=g("ls_pose", 64), counts=g("ls_counts", 64))
 
     def loc_status(self, slot=0):
         """dict(frames, window, rebuilds, optimized) of the slot's last mapping frame"""

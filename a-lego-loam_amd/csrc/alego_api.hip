@@ -1046,6 +1046,7 @@ int alego_debug_set_option(alego_handle* h, const char* name, int value) {
   else if (s == "ALEGO_IP_FAST") d.ip_fast = h->ip_fast_capable & value;
   else if (s == "ALEGO_POKE_GUARD") { HIP_TRY(h, hipMemset(scal_of(d, d.n_slots) + value, 0xFF, 4)); }   // tests of the guard pages: a write `value` ints past the end of an array
   else if (s == "ALEGO_GV_SMALL_MAX") { HIP_TRY(h, sync_all(h)); return lm_host_set_gv_small_max(h->lm, value); }   // tools/gmap_timing.py: largest cloud alego_voxel_grid gives to one workgroup
+  else if (s == "ALEGO_LOC_CHUNK") return lm_host_set_loc_chunk(h->lm, value);   // tests / tools: frames per chunk of alego_loc_enable_from_map / _update_from_map (set on the localising handle)
   else if (s == "ALEGO_PG_BUDGET") graph_ctx_set_budget(&h->pg, value);   // tests / tools: bytes of scratch per chunk of alego_graph_optimize
   else if (s == "ALEGO_LC_BUDGET") loop_ctx_set_budget(&h->lc, value);   // tests / tools: raw sub-map points per chunk of alego_loop_search
   else if (s == "ALEGO_RL_BUDGET") reloc_ctx_set(&h->rl, 0, value);   // tests / tools: (query, frame) pairs per chunk of the relocalisation search
@@ -1344,6 +1345,48 @@ int alego_loc_enable(alego_handle* h, const alego_kf_in* frames, int32_t n, doub
   g_prof = &h->prof;
   HIP_TRY(h, sync_all(h));
   return lm_host_loc_enable(h->lm, h->d, frames, n, radius, &h->err);
+}
+// ... the store built on the device from a slot's archive of a mapping handle of the same process
+static int handover_source(alego_handle* h, alego_handle* map, int slot, const char* what) {
+  const std::string w(what);
+  if (!map) { h->err = w + ": the mapping handle is null"; return ALEGO_ERR_ARG; }
+  if (map == h) { h->err = w + ": the mapping handle and the localising handle are the same"; return ALEGO_ERR_ARG; }
+  if (!map->map_on) { h->err = w + ": the mapping handle has no key-frame archive (alego_map_enable)"; return ALEGO_ERR_ARG; }
+  if (slot < 0 || slot >= map->d.n_slots) { h->err = w + ": slot out of range of the mapping handle"; return ALEGO_ERR_ARG; }
+  if (map->device != h->device) { h->err = w + ": the two handles sit on different devices (" + std::to_string(map->device) + ", " + std::to_string(h->device) + ")"; return ALEGO_ERR_ARG; }
+  return 0;
+}
+int alego_loc_enable_from_map(alego_handle* h, alego_handle* map, int slot, double radius, int32_t capacity) {
+  if (!h) return ALEGO_ERR_ARG;
+  if (h->stream_mode) { h->err = "alego_loc_enable_from_map: not available with alego_stream_setup"; return ALEGO_ERR_ARG; }
+  if (h->map_on || h->graph_on) { h->err = "alego_loc_enable_from_map: the key-frame archive / key-pose graph belong to a mapping handle"; return ALEGO_ERR_ARG; }
+  bool used = false;
+  for (long v : h->lo_scans) used = used || v != 0;
+  for (long v : h->grp_scans) used = used || v != 0;
+  if (used) { h->err = "alego_loc_enable_from_map: call it before the first scan of any slot"; return ALEGO_ERR_ARG; }
+  if (int r = handover_source(h, map, slot, "alego_loc_enable_from_map")) return r;
+  hipSetDevice(h->device);
+  g_prof = &h->prof;
+  HIP_TRY(h, sync_all(map));   // a key frame still queued by alego_batch_run(.., sync = 0) is part of the hand-over
+  HIP_TRY(h, sync_all(h));
+  return lm_host_loc_enable_from_map(h->lm, h->d, map->lm, slot, radius, capacity, &h->err);
+}
+int alego_loc_update_from_map(alego_handle* h, alego_handle* map, int slot) {
+  if (!h) return ALEGO_ERR_ARG;
+  if (!h->lm || !lm_host_localising(h->lm)) { h->err = "alego_loc_update_from_map: the handle does not localise (alego_loc_enable / alego_loc_enable_from_map)"; return ALEGO_ERR_ARG; }
+  if (int r = handover_source(h, map, slot, "alego_loc_update_from_map")) return r;
+  hipSetDevice(h->device);
+  g_prof = &h->prof;
+  HIP_TRY(h, sync_all(map));
+  HIP_TRY(h, sync_all(h));   // behind the work queued on every stream group, front and back
+  bool rewritten = false;
+  const int rc = lm_host_loc_update_from_map(h->lm, map->lm, slot, &rewritten, &h->err);
+  if (!rewritten) return rc;   // refused before anything was written
+  std::string rerr;
+  const int rr = reloc_refresh(h->rl, *lm_host_ctx(h->lm), h->stream, &rerr);
+  if (rc) return rc;
+  if (rr) h->err = rerr;
+  return rr;
 }
 // ---- relocalisation (kernels_reloc.hip) ----
 int alego_reloc_enable(alego_handle* h, double max_range, double z_offset) {

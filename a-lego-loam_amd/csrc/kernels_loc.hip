@@ -8,6 +8,10 @@
 // The local map of the window is built by map_update / map_accum (kernels_map.hip) from the store's pre-sorted runs — LmCtx::fr_stride /
 // fr_mod tell them where a frame lives — and registered by the unchanged lm_knn / lm_fit / lm_solve.  The store itself is filled once by
 // lm_host_loc_enable (lm_host.hip) with lm_store_kf's re-transform path and the key-frame sort jobs the ring uses.
+//
+//   loc_fill       the same store built (alego_loc_enable_from_map) or rebuilt (alego_loc_update_from_map) from a slot's archive of a mapping
+//                  handle without a frame crossing to the host, a chunk of frames per launch
+//   loc_reset_windows   after a rebuild: every slot's window is emptied, its next mapping frame selects in the new map
 #include <algorithm>
 #include <vector>
 
@@ -15,6 +19,7 @@
 #include "dev_common.h"
 #include "kf_store.h"
 #include "loc_math.h"
+#include "loc_store.h"
 #include "prof.h"
 #include "wave.h"
 
@@ -81,6 +86,66 @@ __global__ void __launch_bounds__(LS_T) loc_select(DevCtx d, LmCtx L) {
 
 void launch_loc_select(const DevCtx& d, const LmCtx& L, hipStream_t st) {
   ALEGO_LAUNCH(loc_select, dim3(d.n_launch), dim3(LS_T), 0, st, d, L);
+}
+
+// ---- the batched build of the map store from a slot's archive of a mapping handle --------------------------------
+// loc_fill: grid (point blocks, 3 kinds, frames of the chunk), one point per lane.  Frame f = f0 + blockIdx.z of the source archive S goes
+//   * as it is stored (sensor frame) into row f of the store: kf_raw_* / kf_cnt / kf_pose, what frame_to_row writes for a frame of the host;
+//   * transformed by its key pose into slot blockIdx.z of the staging area: corner, and surf followed by outlier — what kf_row_to_tmp
+//     writes into kf_tmp_* for one frame — for the chunk's sort jobs (VoxelGrid mode 1), whose device words it writes as well.
+// The load comes from a clamped index and is issued before the bounds test, so no lane waits for a load behind a branch; counts are
+// clamped to the store's capacities and every source index to the source's (the host has refused an oversize frame before the launch).
+// No atomics, no wait between workgroups: every output element has one writer.
+#define LF_T 256
+__global__ void __launch_bounds__(LF_T) loc_fill(LmCtx L, KfArcSrc S, int f0, int n_frames, float4* stage_c, float4* stage_s, int* words) {
+  const int j = blockIdx.z, f = f0 + j, kind = blockIdx.y;
+  const bool first = blockIdx.x == 0 && kind == KF_CORNER && threadIdx.x == 0;
+  int* w = words + (size_t)j * LJ_W;
+  if (f >= n_frames) {   // the tail of the last chunk: its jobs are off
+    if (first) w[LJ_ENABLE] = 0;
+    return;
+  }
+  const int* tab = kf_src_tab(S, f);
+  const int r_c = max(tab[AT_N + KF_CORNER], 0), r_s = max(tab[AT_N + KF_SURF], 0), r_o = max(tab[AT_N + KF_OUTL], 0);
+  const int n_c = min(r_c, L.kf_cap_c), n_s = min(r_s, L.kf_cap_s), n_o = min(r_o, L.kf_cap_o);
+  const int n = kf_pick(kind, n_c, n_s, n_o);
+  const size_t row = kf_row_at(L, 0, f);   // (the store: fr_stride = 0, frame f < fr_mod is entry f)
+  if (first) {
+    int* cnt = kf_cnt_of(L, row);
+    float* kp = kf_pose_of(L, row);
+    const float* sp = kf_src_pose(S, f);
+    cnt[KF_CORNER] = n_c; cnt[KF_SURF] = n_s; cnt[KF_OUTL] = n_o; cnt[KF_KINDS] = 0;
+#pragma unroll
+    for (int k = 0; k < KF_POSE_W; ++k) kp[k] = k < 6 ? sp[k] : 0.f;
+    w[LJ_N_C] = n_c; w[LJ_N_S] = n_s + n_o; w[LJ_ROW] = f; w[LJ_ENABLE] = 1;
+  }
+  if ((int)blockIdx.x * LF_T >= n) return;   // (uniform per workgroup)
+  float m[3][4];
+  keypose_matrix(kf_src_pose(S, f), m);
+  const long long off = (long long)tab[AT_OFF] + kf_pick(kind, 0, r_c, r_c + r_s);
+  const int i = blockIdx.x * LF_T + threadIdx.x;
+  const float4 p = S.pts[kf_src_point(S, off + min(i, n - 1))];
+  float4* raw = kf_raw_of(L, row, kind);
+  float4* dst = kf_pick(kind, stage_c + (size_t)j * L.kf_cap_c, stage_s + (size_t)j * L.total_cap, stage_s + (size_t)j * L.total_cap + n_s);
+  if (i < n) { raw[i] = p; dst[i] = kf_transform(m, p); }
+}
+static_assert(KF_CNT_W == KF_KINDS + 1 && KF_POSE_W == 8, "loc_fill writes a whole row of kf_cnt / kf_pose");
+
+void launch_loc_fill(const LmCtx& L, const KfArcSrc& S, int f0, int n_frames, int chunk, int n_max, float4* stage_c, float4* stage_s, int* words, hipStream_t st) {
+  const int cap = std::max(L.kf_cap_c, std::max(L.kf_cap_s, L.kf_cap_o));
+  const int gx = std::max(1, (std::min(std::max(n_max, 0), cap) + LF_T - 1) / LF_T);
+  ALEGO_LAUNCH(loc_fill, dim3(gx, KF_KINDS, chunk), dim3(LF_T), 0, st, L, S, f0, n_frames, stage_c, stage_s, words);
+}
+
+// kf_reset_window for every slot: the window is emptied, the voxel lists and the local maps are stale; the slot's next mapping frame selects and rebuilds
+__global__ void __launch_bounds__(LF_T) loc_reset_windows(LmCtx L, int n_slots) {
+  const int s = blockIdx.x * LF_T + threadIdx.x;
+  if (s >= n_slots) return;
+  int* li = L.li + (size_t)s * LI_COUNT;
+  kf_reset_window([&](int w, int v) { li[w] = v; });
+}
+void launch_loc_reset_windows(const LmCtx& L, int n_slots, hipStream_t st) {
+  ALEGO_LAUNCH(loc_reset_windows, dim3((n_slots + LF_T - 1) / LF_T), dim3(LF_T), 0, st, L, n_slots);
 }
 
 extern "C" int alego_loc_select(const float* keyposes6, int32_t n, const float xyz[3], double radius, int32_t k, int32_t* ids) {

@@ -461,31 +461,50 @@ void reloc_ctx_set(RlCtx** pr, int what, long long v) {   // what 0: pairs per c
 }
 bool reloc_enabled(const RlCtx* R) { return R && R->n_slots > 0; }
 
-int reloc_enable(RlCtx** pr, const LmCtx& L, int n_slots, double max_range, double z_offset, hipStream_t st, std::string* err) {
-  if (!*pr) *pr = new RlCtx();
-  RlCtx* R = *pr;
+// descriptors and ring keys of the store's L.loc_n frames (queued on st, finished on return), and the host copy of their counts and poses
+static hipError_t rl_describe_map(RlCtx* R, const LmCtx& L, hipStream_t st) {
   const int N = L.loc_n;
-  R->w = rl_ring_width(max_range); R->zoff = rl_z_offset(z_offset);
-  auto undo = [&](int rc) { R->store.clear(); return rc; };   // (the handle stays what it was)
-  const DevGet get{R->store, RL_ERR, err};
-  if (!get(&R->mdesc, (size_t)N * RL_WORDS) || !get(&R->mkey, (size_t)N * RL_NR) || !get(&R->qdesc, (size_t)n_slots * RL_WORDS) || !get(&R->qkey, (size_t)n_slots * RL_NR) ||
-      !get(&R->list, (size_t)n_slots) || !get(&R->apply, (size_t)n_slots) || !get(&R->state, (size_t)n_slots) || !get(&R->klist, (size_t)n_slots * RL_NR)) return undo(ALEGO_ERR_HIP);
-  hipError_t e = hipMemsetAsync(R->qdesc, 0, std::max<size_t>(16, (size_t)n_slots * RL_BYTES), st);
-  if (e == hipSuccess) e = hipMemsetAsync(R->qkey, 0, std::max<size_t>(16, (size_t)n_slots * RL_NR * 2), st);
-  if (e == hipSuccess && N > 0) ALEGO_LAUNCH(rl_desc, dim3(N), dim3(RL_T), 0, st, L, 0, (const int*)nullptr, R->w, R->zoff, R->mdesc, R->mkey, (RlSlot*)nullptr, (uint16_t*)nullptr);
+  hipError_t e = hipSuccess;
+  if (N > 0) ALEGO_LAUNCH(rl_desc, dim3(N), dim3(RL_T), 0, st, L, 0, (const int*)nullptr, R->w, R->zoff, R->mdesc, R->mkey, (RlSlot*)nullptr, (uint16_t*)nullptr);
   std::vector<int> cnt((size_t)N * KF_CNT_W);
   std::vector<float> pose((size_t)N * KF_POSE_W);
   if (e == hipSuccess && N > 0) e = hipMemcpyAsync(cnt.data(), kf_cnt_of(L, kf_row_at(L, 0, 0)), cnt.size() * sizeof(int), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess && N > 0) e = hipMemcpyAsync(pose.data(), kf_pose_of(L, kf_row_at(L, 0, 0)), pose.size() * sizeof(float), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) { *err = std::string("alego_reloc_enable: ") + hipGetErrorString(e); return undo(ALEGO_ERR_HIP); }
+  if (e != hipSuccess) return e;
   R->cnt.resize(N); R->pose.resize((size_t)N * 6);
   for (int i = 0; i < N; ++i) {
     R->cnt[i] = kf_clouds_points(kf_clouds_row_at(L, 0, i, cnt.data() + (size_t)i * KF_CNT_W));   // as rl_gather counts them
     for (int k = 0; k < 6; ++k) R->pose[(size_t)i * 6 + k] = pose[(size_t)i * KF_POSE_W + k];
   }
-  R->N = N; R->n_slots = n_slots;
+  R->N = N;
+  return hipSuccess;
+}
+
+int reloc_enable(RlCtx** pr, const LmCtx& L, int n_slots, double max_range, double z_offset, hipStream_t st, std::string* err) {
+  if (!*pr) *pr = new RlCtx();
+  RlCtx* R = *pr;
+  const size_t F = (size_t)std::max(L.fr_mod, L.loc_n);   // the store's capacity: alego_loc_update_from_map may hand it up to that many frames
+  R->w = rl_ring_width(max_range); R->zoff = rl_z_offset(z_offset);
+  auto undo = [&](int rc) { R->store.clear(); return rc; };   // (the handle stays what it was)
+  const DevGet get{R->store, RL_ERR, err};
+  if (!get(&R->mdesc, F * RL_WORDS) || !get(&R->mkey, F * RL_NR) || !get(&R->qdesc, (size_t)n_slots * RL_WORDS) || !get(&R->qkey, (size_t)n_slots * RL_NR) ||
+      !get(&R->list, (size_t)n_slots) || !get(&R->apply, (size_t)n_slots) || !get(&R->state, (size_t)n_slots) || !get(&R->klist, (size_t)n_slots * RL_NR)) return undo(ALEGO_ERR_HIP);
+  hipError_t e = hipMemsetAsync(R->qdesc, 0, std::max<size_t>(16, (size_t)n_slots * RL_BYTES), st);
+  if (e == hipSuccess) e = hipMemsetAsync(R->qkey, 0, std::max<size_t>(16, (size_t)n_slots * RL_NR * 2), st);
+  if (e == hipSuccess) e = rl_describe_map(R, L, st);
+  if (e != hipSuccess) { *err = std::string("alego_reloc_enable: ") + hipGetErrorString(e); return undo(ALEGO_ERR_HIP); }
+  R->n_slots = n_slots;
   return 0;
+}
+// the store changed (alego_loc_update_from_map): the descriptors and ring keys of its frames are built again; a failure leaves none (no frame is a candidate)
+int reloc_refresh(RlCtx* R, const LmCtx& L, hipStream_t st, std::string* err) {
+  if (!reloc_enabled(R)) return 0;
+  const hipError_t e = rl_describe_map(R, L, st);
+  if (e == hipSuccess) return 0;
+  R->N = 0; R->cnt.clear(); R->pose.clear();
+  *err = std::string("alego_loc_update_from_map: describing the map failed: ") + hipGetErrorString(e);
+  return ALEGO_ERR_HIP;
 }
 
 // The exact search of nq queries (qr[q]; off is filled in here): cand[q][r] = the candidate word, RL_CAND_NONE where fewer frames are eligible.

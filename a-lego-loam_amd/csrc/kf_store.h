@@ -38,6 +38,16 @@ KF_FN KfRingRow kf_ring_row_at(const LmCtx& L, int slot, int entry, int kind) {
 struct KfArcFrame { const float4* pts; int nc, ns, no; float* pose; };
 KF_FN KfArcFrame kf_arc_frame(const LmCtx& L, int slot, int f, const int* tab) { return KfArcFrame{L.arc_pts + (size_t)slot * L.arc_points_cap + tab[AT_OFF], tab[AT_N + KF_CORNER], tab[AT_N + KF_SURF], tab[AT_N + KF_OUTL], arc_pose_of(L, slot, f)}; }
 DEV_INLINE KfArcFrame kf_arc_frame(const LmCtx& L, int slot, int f) { return kf_arc_frame(L, slot, f, arc_tab_of(L, slot, f)); }
+// One slot's archive of ANOTHER handle (alego_loc_enable_from_map / _update_from_map: the launch's LmCtx is the localising handle's): plain pointers to the slot's own
+// first row of arc_pts / arc_tab / arc_pose and the source's capacities per slot.  A frame or point index beyond them is clamped, never followed.
+struct KfArcSrc { const float4* pts; const int* tab; const float* pose; int frames_cap, points_cap; };
+inline KfArcSrc kf_arc_src(const LmCtx& L, int slot) { return KfArcSrc{L.arc_pts + (size_t)slot * L.arc_points_cap, arc_tab_of(L, slot, 0), arc_pose_of(L, slot, 0), L.arc_frames_cap, L.arc_points_cap}; }
+KF_FN const int* kf_src_tab(const KfArcSrc& S, int f) { return S.tab + (size_t)(f < S.frames_cap ? f : S.frames_cap - 1) * AT_W; }
+KF_FN const float* kf_src_pose(const KfArcSrc& S, int f) { return S.pose + (size_t)(f < S.frames_cap ? f : S.frames_cap - 1) * KF_POSE_W; }
+KF_FN size_t kf_src_point(const KfArcSrc& S, long long i) { return (size_t)(i < 0 ? 0 : (i < S.points_cap ? i : S.points_cap - 1)); }
+// the device words of one frame of a chunk of the batched store build (loc_fill writes them, the frame's two sort jobs read them): points of the corner and of the
+// surf + outlier staging run, the store row the sorted runs go to (VoxJob::out_sel), the jobs' enable flag, the counts the jobs write back
+enum { LJ_N_C = 0, LJ_N_S, LJ_ROW, LJ_ENABLE, LJ_SORT_N, LJ_SORT_N1, LJ_W = 8 };
 // a key frame handed in by the host: no negative count, no missing cloud
 inline bool kf_in_valid(const alego_kf_in& k) { return k.n_corner >= 0 && k.n_surf >= 0 && k.n_outlier >= 0 && (!k.n_corner || k.corner) && (!k.n_surf || k.surf) && (!k.n_outlier || k.outlier); }
 // A frame is read out as surf, corner, outlier (laserMapping.cpp:607-612, :794-796), restricted to `kinds`: the points that gives, where cloud `kind`

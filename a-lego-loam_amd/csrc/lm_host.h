@@ -72,6 +72,11 @@ int lm_host_map_thin(LmHost* lm, const int* slots, int n, double min_dist, alego
 int lm_host_debug_thin_select(LmHost* lm, const float* keyposes6, const uint8_t* protect, int n, double min_dist, uint8_t* keep, std::string* err);
 // localisation mode (alego_loc_*; kernels_loc.hip): the frozen map store shared by every slot
 int lm_host_loc_enable(LmHost* lm, const DevCtx& d, const alego_kf_in* frames, int n, double radius, std::string* err);
+// ... built on the device from the archive of `slot` of the mapping handle `src` as it is now, in chunks (the caller has synchronised every stream of both
+// handles); capacity: frames the store is allocated for (<= 0: the archived frames).  update: the store of a handle that localises is rebuilt from it
+int lm_host_loc_enable_from_map(LmHost* lm, const DevCtx& d, LmHost* src, int slot, double radius, int capacity, std::string* err);
+int lm_host_loc_update_from_map(LmHost* lm, LmHost* src, int slot, bool* rewritten, std::string* err);   // rewritten: the store was touched (it is empty after a failure then)
+int lm_host_set_loc_chunk(LmHost* lm, int frames);   // ALEGO_LOC_CHUNK: frames per chunk of that build
 int lm_host_loc_status(LmHost* lm, int slot, int* out4, std::string* err);
 bool lm_host_localising(LmHost* lm);
 #endif

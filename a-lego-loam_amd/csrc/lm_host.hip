@@ -19,6 +19,7 @@
 #include "merge_math.h"
 #include "thin.h"
 #include "thin_math.h"
+#include "loc_store.h"
 
 struct LmHost {
   alego_params P;
@@ -43,6 +44,7 @@ struct LmHost {
   // localisation mode (alego_loc_enable): the two sort jobs that fill the map store, frame after frame
   VoxCtx vloc;
   bool vloc_made = false;
+  int loc_chunk = 128;         // alego_loc_enable_from_map / _update_from_map: frames per chunk of the batched build (ALEGO_LOC_CHUNK), before the byte budget clamps it
   // alego_map_move / alego_map_merge: the pairs, copy items, per-slot tail words and moves of a call; allocated by the first call and kept
   DevBuf<MgPair> mg_pairs;
   DevBuf<int2> mg_items;
@@ -78,17 +80,24 @@ bool ring_alloc(LmHost* lm, LmCtx& L, size_t rows, std::string* err) {   // (a p
   return ok;
 }
 void ring_release(LmHost* lm, LmCtx& L) { ring_each(L, [&](auto*& p, size_t) { lm->mem.release(p); p = nullptr; }); }
-// the two sort jobs of a slot's kf_tmp_* (corner, surf + outlier): sorted by voxel key of the map's leaf into the row of the slot that LI_KF_PEND_RING names (VoxelGrid mode 1)
-void kf_sort_jobs(const LmCtx& L, const alego_params& P, int slot, std::vector<VoxJob>* out) {
-  int* li = L.li + (size_t)slot * LI_COUNT;
-  for (int m = 0; m < 2; ++m) {   // (LI_TMPN_S = LI_TMPN_C + 1, LI_SORT_N1 = LI_SORT_N + 1)
+// the two sort jobs of one staged key frame (in_c: corner, in_s: surf + outlier): sorted by voxel key of the map's leaf into the row *out_sel names, counted from the
+// first row of `slot` (VoxelGrid mode 1).  n_in / n_out: two device words each (corner, surf + outlier); enable, out_sel, overflow: one each.
+void kf_sort_job_pair(const LmCtx& L, const alego_params& P, int slot, const float4* in_c, const float4* in_s, const int* n_in, int* n_out, const int* enable, const int* out_sel, int* overflow,
+                      std::vector<VoxJob>* out) {
+  for (int m = 0; m < 2; ++m) {
     const int cap = m ? L.total_cap : L.kf_cap_c;
-    VoxJob j{(m ? L.kf_tmp_s : L.kf_tmp_c) + (size_t)slot * cap, li + LI_TMPN_C + m, (m ? L.kfs_s : L.kfs_c) + kf_row_at(L, slot, 0) * cap, li + LI_SORT_N + m, li + LI_KF_PENDING,
-             m ? P.lm_leaf_surf : P.lm_leaf_corner, cap, cap, li + LI_OVERFLOW, 0};
-    j.mode = 1; j.out_sel = li + LI_KF_PEND_RING; j.out_stride = cap;
+    VoxJob j{m ? in_s : in_c, n_in + m, (m ? L.kfs_s : L.kfs_c) + kf_row_at(L, slot, 0) * cap, n_out + m, enable,
+             m ? P.lm_leaf_surf : P.lm_leaf_corner, cap, cap, overflow, 0};
+    j.mode = 1; j.out_sel = out_sel; j.out_stride = cap;
     j.box_out = L.kfs_box + kf_run_at(L, slot, m, 0) * 8; j.n_sel_out = L.kfs_n + kf_run_at(L, slot, m, 0); j.n_sel_stride = 1;
     out->push_back(j);
   }
+}
+// ... of a slot's kf_tmp_*, into the row of the slot that LI_KF_PEND_RING names
+void kf_sort_jobs(const LmCtx& L, const alego_params& P, int slot, std::vector<VoxJob>* out) {
+  int* li = L.li + (size_t)slot * LI_COUNT;
+  static_assert(LI_TMPN_S == LI_TMPN_C + 1 && LI_SORT_N1 == LI_SORT_N + 1, "kf_sort_job_pair reads / writes the counts as pairs");
+  kf_sort_job_pair(L, P, slot, L.kf_tmp_c + (size_t)slot * L.kf_cap_c, L.kf_tmp_s + (size_t)slot * L.total_cap, li + LI_TMPN_C, li + LI_SORT_N, li + LI_KF_PENDING, li + LI_KF_PEND_RING, li + LI_OVERFLOW, out);
 }
 }  // namespace
 
@@ -631,6 +640,28 @@ int lm_host_debug_get(LmHost* lm, int slot, const char* name, void* out, int cap
     const int m = s == "lm_voxel_keys_c" ? 0 : 1;
     set(m == 0 ? (const void*)(L.U_c + b * L.map_cap_c) : (const void*)(L.U_s + b * L.map_cap_s), (size_t)li[LI_NU_C + m] * 2, 2);
   }
+  else if (s.rfind("ls_", 0) == 0 && s.find(':') != std::string::npos) {   // "ls_<what>:<f>": row f of a localising handle's map store (the slot argument plays no part)
+    const std::string w = s.substr(0, s.find(':'));
+    const int f = atoi(s.c_str() + s.find(':') + 1);
+    if (!L.loc_on || f < 0 || f >= L.loc_n) { *err = std::string("debug_get: ") + name + ": no such frame in a map store"; return ALEGO_ERR_ARG; }
+    int cnt[KF_CNT_W], run[2];
+    for (int m = 0; m < 2; ++m) (void)hipMemcpy(run + m, L.kfs_n + kf_run_at(L, 0, m, f), sizeof(int), hipMemcpyDeviceToHost);
+    (void)hipMemcpy(cnt, kf_cnt_of(L, kf_row_at(L, 0, f)), sizeof(cnt), hipMemcpyDeviceToHost);
+    const KfClouds C = kf_clouds_row_at(L, 0, f, cnt);
+    if (w == "ls_corner") set(L.kfs_c + kf_row_at(L, 0, f) * L.kf_cap_c, (size_t)std::min(std::max(run[0], 0), L.kf_cap_c) * 4, 0);
+    else if (w == "ls_surf") set(L.kfs_s + kf_row_at(L, 0, f) * L.total_cap, (size_t)std::min(std::max(run[1], 0), L.total_cap) * 4, 0);
+    else if (w == "ls_box_c" || w == "ls_box_s") set(L.kfs_box + kf_run_at(L, 0, w == "ls_box_s", f) * 8, 8, 0);
+    else if (w == "ls_raw_c" || w == "ls_raw_s" || w == "ls_raw_o") { const int k = w == "ls_raw_c" ? KF_CORNER : (w == "ls_raw_s" ? KF_SURF : KF_OUTL); set(C.pts[k], (size_t)std::max(C.n[k], 0) * 4, 0); }
+    else if (w == "ls_pose") set(kf_pose_of(L, kf_row_at(L, 0, f)), KF_POSE_W, 0);
+    else if (w == "ls_counts") {   // the two run counts, then the stored points per kind
+      const int o[2 + KF_KINDS] = {run[0], run[1], cnt[KF_CORNER], cnt[KF_SURF], cnt[KF_OUTL]};
+      if ((size_t)cap_bytes < sizeof(o)) { *err = "debug_get: buffer too small"; return ALEGO_ERR_CAPACITY; }
+      std::memcpy(out, o, sizeof(o));
+      *count = 2 + KF_KINDS; *dtype = 2;
+      return 0;
+    }
+    else { *err = std::string("debug_get: unknown name ") + name; return ALEGO_ERR_ARG; }
+  }
   else { *err = std::string("debug_get: unknown name ") + name; return ALEGO_ERR_ARG; }
   if ((size_t)cap_bytes < n * esz) { *err = "debug_get: buffer too small"; return ALEGO_ERR_CAPACITY; }
   if (n && hipMemcpy(out, src, n * esz, hipMemcpyDeviceToHost) != hipSuccess) { *err = "debug_get: copy failed"; return ALEGO_ERR_HIP; }
@@ -710,45 +741,75 @@ const LmCtx* lm_host_ctx(LmHost* lm) { return &lm->L; }
 // The map store: every frame transformed by its key pose and sorted by voxel key exactly as a ring entry is (lm_store_kf's re-transform path
 // into kf_tmp_*, then the key-frame sort, VoxelGrid mode 1), once for the whole handle.  The rings of the slots are released: kfs_* / kf_raw_* /
 // kf_cnt / kf_pose name the store from now on, and fr_stride = 0 sends every slot's frame f to row f of it.
+// ---- what alego_loc_enable and alego_loc_enable_from_map share: the preconditions on the handle, the store and its view T, the undo, the swap of L
+namespace {
+// a fresh SLAM handle that may become a localising one (`what`: the call, for the messages)
+int loc_handle_ready(LmHost* lm, const DevCtx& dfull, const std::string& what, std::string* err) {
+  const LmCtx& L = lm->L;
+  if (L.arc_frames_cap > 0 || L.pg_loops_cap > 0) { *err = what + ": the key-frame archive / key-pose graph belong to a mapping handle"; return ALEGO_ERR_ARG; }
+  if (lm->comm) { *err = what + ": not available on a handle with a sharded registration (alego_dist_init)"; return ALEGO_ERR_ARG; }
+  if (!dfull.opt_map_merge) { *err = what + ": ALEGO_MAP_MERGE=0 (concat + radix VoxelGrid) is a mapping-only path"; return ALEGO_ERR_ARG; }
+  for (long f : lm->frames) if (f != 0) { *err = what + ": call it before the first scan of any slot"; return ALEGO_ERR_ARG; }
+  for (hipStream_t s : lm->st) if (hipStreamSynchronize(s) != hipSuccess) { *err = what + ": a stream failed"; return ALEGO_ERR_HIP; }
+  return rings_empty(lm, what.c_str(), true, err);
+}
+// a frame of nc / ns / no points against the key-frame capacities of the handle
+int loc_frame_fits(const LmCtx& L, const std::string& what, int i, int nc, int ns, int no, std::string* err) {
+  if (nc <= L.kf_cap_c && ns <= L.kf_cap_s && no <= L.kf_cap_o) return 0;
+  *err = what + ": frame " + std::to_string(i) + " (" + std::to_string(nc) + " corner, " + std::to_string(ns) + " surf, " + std::to_string(no) +
+         " outlier points) exceeds the handle's key-frame capacities (" + std::to_string(L.kf_cap_c) + ", " + std::to_string(L.kf_cap_s) + ", " + std::to_string(L.kf_cap_o) + ")";
+  return ALEGO_ERR_CAPACITY;
+}
+// The store of `rows` frames, n of them used, behind a view T of its own: the handle becomes a localising one — and its rings go (loc_store_commit) — only once
+// every frame is in.  Until then any failure undoes the store (loc_store_undo) and leaves the handle the SLAM handle it was.
+int loc_store_view(LmHost* lm, LmCtx* T, int rows, int n, double radius, const std::string& what, std::string* err) {
+  *T = lm->L;
+  const size_t F = (size_t)std::max(rows, 1);
+  std::string aerr;
+  if (!ring_alloc(lm, *T, F, &aerr)) {   // the handle stays what it was
+    ring_release(lm, *T);
+    *err = what + ": the map store of " + std::to_string(rows) + " frames does not fit (" + aerr + ")";
+    return ALEGO_ERR_CAPACITY;
+  }
+  T->fr_stride = 0; T->fr_mod = (int)F; T->loc_on = 1; T->loc_n = n; T->loc_r2 = loc_r2(radius);
+  return 0;
+}
+int loc_store_undo(LmHost* lm, LmCtx& T, int rc) {
+  (void)hipStreamSynchronize(lm->st[0]);
+  ring_release(lm, T);
+  return rc;
+}
+// The slots' rings give their memory back (no scan has used them).  The per-slot key-frame sort jobs in the job tables of vm[g] / vk[g]
+// (lm_host_create) still name those rings: they run only for a slot whose LI_KF_PENDING is set, which lm_store_kf alone sets, and neither
+// lm_store_kf nor a vk round is ever launched on a localising handle (launch_lm_register returns before it; retransform and
+// lm_host_graph_apply sit behind API calls that refuse such a handle).
+void loc_store_commit(LmHost* lm, const LmCtx& T) {
+  ring_release(lm, lm->L);
+  lm->L = T;
+}
+}  // namespace
+
 int lm_host_loc_enable(LmHost* lm, const DevCtx& dfull, const alego_kf_in* frames, int n, double radius, std::string* err) {
   LmCtx& L = lm->L;
+  const std::string what = "alego_loc_enable";
   if (L.loc_on) { *err = "alego_loc_enable: already enabled"; return ALEGO_ERR_ARG; }
   if (n < 0 || (n > 0 && !frames)) { *err = "alego_loc_enable: null frames / negative count"; return ALEGO_ERR_ARG; }
-  if (L.arc_frames_cap > 0 || L.pg_loops_cap > 0) { *err = "alego_loc_enable: the key-frame archive / key-pose graph belong to a mapping handle"; return ALEGO_ERR_ARG; }
-  if (lm->comm) { *err = "alego_loc_enable: not available on a handle with a sharded registration (alego_dist_init)"; return ALEGO_ERR_ARG; }
-  if (!dfull.opt_map_merge) { *err = "alego_loc_enable: ALEGO_MAP_MERGE=0 (concat + radix VoxelGrid) is a mapping-only path"; return ALEGO_ERR_ARG; }
-  for (long f : lm->frames) if (f != 0) { *err = "alego_loc_enable: call it before the first scan of any slot"; return ALEGO_ERR_ARG; }
-  for (hipStream_t s : lm->st) if (hipStreamSynchronize(s) != hipSuccess) { *err = "alego_loc_enable: a stream failed"; return ALEGO_ERR_HIP; }
-  if (int r = rings_empty(lm, "alego_loc_enable", true, err)) return r;
+  if (int r = loc_handle_ready(lm, dfull, what, err)) return r;
   if (n > LOC_MAX_FRAMES) { *err = "alego_loc_enable: more than " + std::to_string(LOC_MAX_FRAMES) + " frames"; return ALEGO_ERR_CAPACITY; }
   for (int i = 0; i < n; ++i) {
     const alego_kf_in& f = frames[i];
     if (!kf_in_valid(f)) { *err = "alego_loc_enable: frame " + std::to_string(i) + ": null cloud / negative count"; return ALEGO_ERR_ARG; }
-    if (f.n_corner > L.kf_cap_c || f.n_surf > L.kf_cap_s || f.n_outlier > L.kf_cap_o) {
-      *err = "alego_loc_enable: frame " + std::to_string(i) + " (" + std::to_string(f.n_corner) + " corner, " + std::to_string(f.n_surf) + " surf, " + std::to_string(f.n_outlier) +
-             " outlier points) exceeds the handle's key-frame capacities (" + std::to_string(L.kf_cap_c) + ", " + std::to_string(L.kf_cap_s) + ", " + std::to_string(L.kf_cap_o) + ")";
-      return ALEGO_ERR_CAPACITY;
-    }
+    if (int r = loc_frame_fits(L, what, i, f.n_corner, f.n_surf, f.n_outlier, err)) return r;
   }
-  LmCtx T = L;
-  const size_t F = (size_t)std::max(n, 1);
-  std::string aerr;
-  if (!ring_alloc(lm, T, F, &aerr)) {   // the handle stays what it was
-    ring_release(lm, T);
-    *err = "alego_loc_enable: the map store of " + std::to_string(n) + " frames does not fit (" + aerr + ")";
-    return ALEGO_ERR_CAPACITY;
-  }
-  // The store is built through a view T of its own; the handle becomes a localising one — and its rings go — only once every frame is in.
-  // Until then any failure undoes the store and leaves the handle the SLAM handle it was.
-  T.fr_stride = 0; T.fr_mod = (int)F; T.loc_on = 1; T.loc_n = n; T.loc_r2 = loc_r2(radius);
+  LmCtx T;
+  if (int r = loc_store_view(lm, &T, n, n, radius, what, err)) return r;
   int* li0 = T.li;
   auto undo = [&](int rc) {
     (void)hipStreamSynchronize(lm->st[0]);
     (void)hipMemset(li0 + LI_KF_PENDING, 0, 8 * sizeof(int));
     (void)hipMemset(li0 + LI_OVERFLOW, 0, sizeof(int));
     if (lm->vloc_made) { vox_destroy(&lm->vloc); lm->vloc_made = false; }
-    ring_release(lm, T);
-    return rc;
+    return loc_store_undo(lm, T, rc);
   };
   // the sort jobs of slot 0's kf_tmp_*, with the store as their ring
   std::vector<VoxJob> jobs;
@@ -775,14 +836,127 @@ int lm_host_loc_enable(LmHost* lm, const DevCtx& dfull, const alego_kf_in* frame
   int ovf = 0;
   if (hipMemcpy(&ovf, li0 + LI_OVERFLOW, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { *err = "alego_loc_enable: device read failed"; return undo(ALEGO_ERR_HIP); }
   if (ovf) { *err = "alego_loc_enable: a frame was truncated while it was sorted"; return undo(ALEGO_ERR_CAPACITY); }
-  // The slots' rings give their memory back (no scan has used them).  The per-slot key-frame sort jobs in the job tables of vm[g] / vk[g]
-  // (lm_host_create) still name those rings: they run only for a slot whose LI_KF_PENDING is set, which lm_store_kf alone sets, and neither
-  // lm_store_kf nor a vk round is ever launched on a localising handle (launch_lm_register returns before it; retransform and
-  // lm_host_graph_apply sit behind API calls that refuse such a handle).
-  ring_release(lm, L);
-  L = T;
+  loc_store_commit(lm, T);
   return 0;
 }
+
+// ---- the store from a slot's archive of a mapping handle, on the device (alego_loc_enable_from_map / alego_loc_update_from_map) ----
+namespace {
+// Staging + sort scratch of one chunk of the batched build stay within this many bytes: the chunk size is clamped to it (16x1800: 0.8 MB per
+// frame, 128 frames fit; 64x2048: 5.7 MB per frame, 44 frames).
+constexpr size_t LOC_BUILD_BUDGET = (size_t)256 << 20;
+int loc_chunk_frames(const LmHost* lm, int n) {
+  const LmCtx& L = lm->L;
+  size_t per = 16 * ((size_t)L.kf_cap_c + L.total_cap) + LJ_W * sizeof(int);
+  for (int cap : {L.kf_cap_c, L.total_cap}) if (cap > 8192) per += 20 * (size_t)cap;   // vox_create: key + two pair buffers for a job that can reach vox_big
+  const long long fit = (long long)(LOC_BUILD_BUDGET / per);
+  return (int)std::max<long long>(1, std::min<long long>(std::min<long long>(std::max(lm->loc_chunk, 1), fit), std::max(n, 1)));
+}
+// the archive of `slot` of the source as it is now (its streams have been synchronised): frames stored, their arc_tab rows on the host
+int loc_src_read(LmHost* src, int slot, const std::string& what, std::vector<int>* tab, std::string* err) {
+  int st[AS_W];
+  if (hipMemcpy(st, arc_stat_of(src->L, slot), sizeof(st), hipMemcpyDeviceToHost) != hipSuccess) { *err = what + ": device read failed"; return ALEGO_ERR_HIP; }
+  const int n = std::max(0, std::min(st[AS_FRAMES], src->L.arc_frames_cap));   // (a source that dropped frames: the stored prefix is handed over)
+  tab->assign((size_t)n * AT_W, 0);
+  if (n > 0 && hipMemcpy(tab->data(), arc_tab_of(src->L, slot, 0), tab->size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { *err = what + ": device read failed"; return ALEGO_ERR_HIP; }
+  return n;
+}
+int loc_src_ok(LmHost* lm, LmHost* src, int slot, const std::string& what, std::string* err) {
+  if (!src || src == lm) { *err = what + ": the source is a second handle, a mapping one"; return ALEGO_ERR_ARG; }
+  if (src->L.arc_frames_cap <= 0) { *err = what + ": the source handle has no key-frame archive (alego_map_enable)"; return ALEGO_ERR_ARG; }
+  if (slot < 0 || slot >= src->n_slots) { *err = what + ": slot out of range of the source handle"; return ALEGO_ERR_ARG; }
+  return 0;
+}
+// Frames 0 .. n - 1 of S into rows 0 .. n - 1 of the store T names, in chunks: loc_fill, then one VoxelGrid round of the chunk's 2 C sort jobs, one workgroup
+// per job.  Everything is queued on st and finished when this returns; tab: the host copy of the frames' arc_tab rows.
+int loc_store_fill(LmHost* lm, const LmCtx& T, const KfArcSrc& S, const std::vector<int>& tab, int n, hipStream_t st, const std::string& what, std::string* err) {
+  if (n == 0) return hipStreamSynchronize(st) == hipSuccess ? 0 : ALEGO_ERR_HIP;
+  const int C = loc_chunk_frames(lm, n);
+  DevPool tmp;
+  float4 *stage_c = nullptr, *stage_s = nullptr;
+  int* words = nullptr;   // [C][LJ_W], then the overflow word of all jobs
+  if (tmp.get(&stage_c, (size_t)C * T.kf_cap_c, false) != hipSuccess || tmp.get(&stage_s, (size_t)C * T.total_cap, false) != hipSuccess ||
+      tmp.get(&words, (size_t)C * LJ_W + 1, true) != hipSuccess) { *err = what + ": the staging area of " + std::to_string(C) + " frames does not fit"; return ALEGO_ERR_HIP; }
+  int* ovf = words + (size_t)C * LJ_W;
+  std::vector<VoxJob> jobs;
+  for (int j = 0; j < C; ++j) {
+    int* w = words + (size_t)j * LJ_W;
+    static_assert(LJ_N_S == LJ_N_C + 1 && LJ_SORT_N1 == LJ_SORT_N + 1, "kf_sort_job_pair reads / writes the counts as pairs");
+    kf_sort_job_pair(T, lm->P, 0, stage_c + (size_t)j * T.kf_cap_c, stage_s + (size_t)j * T.total_cap, w + LJ_N_C, w + LJ_SORT_N, w + LJ_ENABLE, w + LJ_ROW, ovf, &jobs);
+  }
+  VoxCtx V;
+  if (vox_create(&V, jobs.data(), (int)jobs.size(), err)) return ALEGO_ERR_HIP;   // (grid_small = grid_big = the job count: one job per workgroup across the chip)
+  int rc = 0;
+  for (int f0 = 0; f0 < n && !rc; f0 += C) {
+    int n_max = 0;
+    for (int f = f0; f < std::min(n, f0 + C); ++f) for (int k = 0; k < KF_KINDS; ++k) n_max = std::max(n_max, tab[(size_t)f * AT_W + AT_N + k]);
+    launch_loc_fill(T, S, f0, n, C, n_max, stage_c, stage_s, words, st);
+    rc = vox_run(V, st, err);
+  }
+  int o = 0;
+  const hipError_t e = hipStreamSynchronize(st);
+  if (!rc && e != hipSuccess) { *err = what + ": building the map store failed: " + hipGetErrorString(e); rc = ALEGO_ERR_HIP; }
+  if (!rc && hipMemcpy(&o, ovf, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { *err = what + ": device read failed"; rc = ALEGO_ERR_HIP; }
+  if (!rc && o) { *err = what + ": a frame was truncated while it was sorted"; rc = ALEGO_ERR_CAPACITY; }
+  vox_destroy(&V);
+  tmp.clear();
+  return rc;
+}
+}  // namespace
+
+int lm_host_loc_enable_from_map(LmHost* lm, const DevCtx& dfull, LmHost* src, int slot, double radius, int capacity, std::string* err) {
+  const std::string what = "alego_loc_enable_from_map";
+  LmCtx& L = lm->L;
+  if (L.loc_on) { *err = what + ": already enabled"; return ALEGO_ERR_ARG; }
+  if (int r = loc_src_ok(lm, src, slot, what, err)) return r;
+  if (int r = loc_handle_ready(lm, dfull, what, err)) return r;
+  std::vector<int> tab;
+  const int n = loc_src_read(src, slot, what, &tab, err);
+  if (n < 0) return n;
+  if (n > LOC_MAX_FRAMES) { *err = what + ": more than " + std::to_string(LOC_MAX_FRAMES) + " frames"; return ALEGO_ERR_CAPACITY; }
+  if (capacity <= 0) capacity = n;
+  if (capacity < n || capacity > LOC_MAX_FRAMES) {
+    *err = what + ": capacity " + std::to_string(capacity) + " is not within the " + std::to_string(n) + " archived frames .. " + std::to_string(LOC_MAX_FRAMES);
+    return ALEGO_ERR_CAPACITY;
+  }
+  for (int i = 0; i < n; ++i) if (int r = loc_frame_fits(L, what, i, tab[(size_t)i * AT_W + AT_N + KF_CORNER], tab[(size_t)i * AT_W + AT_N + KF_SURF], tab[(size_t)i * AT_W + AT_N + KF_OUTL], err)) return r;
+  LmCtx T;
+  if (int r = loc_store_view(lm, &T, capacity, n, radius, what, err)) return r;
+  if (int r = loc_store_fill(lm, T, kf_arc_src(src->L, slot), tab, n, lm->st[0], what, err)) return loc_store_undo(lm, T, r);
+  loc_store_commit(lm, T);
+  return 0;
+}
+
+int lm_host_loc_update_from_map(LmHost* lm, LmHost* src, int slot, bool* rewritten, std::string* err) {
+  const std::string what = "alego_loc_update_from_map";
+  *rewritten = false;
+  LmCtx& L = lm->L;
+  if (!L.loc_on) { *err = what + ": the handle does not localise (alego_loc_enable / alego_loc_enable_from_map)"; return ALEGO_ERR_ARG; }
+  if (int r = loc_src_ok(lm, src, slot, what, err)) return r;
+  for (hipStream_t s : lm->st) if (hipStreamSynchronize(s) != hipSuccess) { *err = what + ": a stream failed"; return ALEGO_ERR_HIP; }
+  std::vector<int> tab;
+  const int n = loc_src_read(src, slot, what, &tab, err);
+  if (n < 0) return n;
+  if (n > L.fr_mod) { *err = what + ": " + std::to_string(n) + " archived frames exceed the store's capacity of " + std::to_string(L.fr_mod); return ALEGO_ERR_CAPACITY; }
+  for (int i = 0; i < n; ++i) if (int r = loc_frame_fits(L, what, i, tab[(size_t)i * AT_W + AT_N + KF_CORNER], tab[(size_t)i * AT_W + AT_N + KF_SURF], tab[(size_t)i * AT_W + AT_N + KF_OUTL], err)) return r;
+  // From here on the store is rewritten.  Counts, poses, run counts and boxes start from zero as in a fresh store (an empty run writes no box; rows
+  // beyond the new frames name nothing); points beyond a row's counts are never read.
+  hipStream_t st = lm->st[0];
+  const size_t F = (size_t)L.fr_mod;
+  *rewritten = true;
+  hipError_t e = hipMemsetAsync(L.kfs_n, 0, 2 * F * sizeof(int), st);
+  if (e == hipSuccess) e = hipMemsetAsync(L.kfs_box, 0, 2 * F * 8 * sizeof(float), st);
+  if (e == hipSuccess) e = hipMemsetAsync(kf_cnt_of(L, 0), 0, F * KF_CNT_W * sizeof(int), st);
+  if (e == hipSuccess) e = hipMemsetAsync(kf_pose_of(L, 0), 0, F * KF_POSE_W * sizeof(float), st);
+  int rc = e == hipSuccess ? 0 : ALEGO_ERR_HIP;
+  if (rc) *err = what + ": " + hipGetErrorString(e);
+  if (!rc) rc = loc_store_fill(lm, L, kf_arc_src(src->L, slot), tab, n, st, what, err);
+  L.loc_n = rc ? 0 : n;   // a failure in the middle leaves the store empty: every slot is off the map and dead-reckons
+  launch_loc_reset_windows(L, lm->n_slots, st);
+  if (hipStreamSynchronize(st) != hipSuccess && !rc) { *err = what + ": the window reset failed"; L.loc_n = 0; rc = ALEGO_ERR_HIP; }
+  return rc;
+}
+int lm_host_set_loc_chunk(LmHost* lm, int frames) { lm->loc_chunk = std::max(1, frames); return 0; }
 int lm_host_loc_status(LmHost* lm, int slot, int* out4, std::string* err) {
   const LmCtx& L = lm->L;
   if (!L.loc_on) { *err = "alego_loc_status: the handle does not localise (alego_loc_enable)"; return ALEGO_ERR_ARG; }

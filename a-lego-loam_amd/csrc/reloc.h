@@ -7,6 +7,8 @@
 struct RlCtx;   // map / query descriptors (reloc_enable); search scratch allocated by the first search and kept
 int reloc_enable(RlCtx** pr, const LmCtx& L, int n_slots, double max_range, double z_offset, hipStream_t st, std::string* err);
 bool reloc_enabled(const RlCtx* R);
+// the map store was rebuilt (alego_loc_update_from_map): its descriptors and ring keys again, for the L.loc_n frames it holds now; nothing when relocalisation is off
+int reloc_refresh(RlCtx* R, const LmCtx& L, hipStream_t st, std::string* err);
 int reloc_run(RlCtx* R, LcCtx** lc, const LmCtx& L, const alego_params& P, const int* slots, int n, int n_cand, int verify, int apply, alego_reloc_result* out,
               hipStream_t st, std::string* err);
 int reloc_debug_search(RlCtx** pr, const uint8_t* map_desc, int n_map, const uint8_t* q_desc, int n_q, int n_cand, int32_t* ids, int32_t* dists, int32_t* shifts,

@@ -52,6 +52,9 @@
 //       alego_map_get_keyframe, a SECOND handle is opened, alego_loc_enable hands it those frames, and the same scans are replayed through
 //       it.  It never saves a key frame; every mapping frame registers against the map frames nearest to its pose.  The JSON line gains
 //       "loc_map_t" (its final map pose) and "loc_max_dev" (the largest per-axis distance between the two runs' map poses).
+//   --localize + --on-device
+//       the mapping handle stays alive and alego_loc_enable_from_map hands its archive to the second handle on the device, no frame crossing to
+//       the host; the printed poses equal those of --localize digit for digit, and the JSON line gains "loc_on_device": 1.
 //   --localize + --relocalize [--reloc-start K] [--reloc-range R]
 //       the localising handle's stream starts UNPLACED at scan K of the source (default: half way) — nothing tells the handle where it is.
 //       alego_reloc_enable builds the map's descriptors (R = max_range, default the library's); after the stream's first mapping frame
@@ -79,7 +82,7 @@ int main(int argc, char** argv) {
   std::string bag_path, topic = "/lslidar_point_cloud", map_dir;
   float map_leaf = 0.f;
   int map_frames = 4096, map_points = 1 << 24, loop_every = 0, close_every = 0, max_loops = 16;
-  bool list_only = false, standalone = false, localize = false, relocalize = false, appearance = false, merge = false;
+  bool list_only = false, standalone = false, localize = false, relocalize = false, appearance = false, merge = false, on_device = false;
   double gate_chi2 = -1.0, loc_radius = 0.0, reloc_range = 0.0, app_max_jump = 0.0, app_range = 0.0, loop_radius = 0.0, thin_dist = -1.0;
   long reloc_start = -1, align_start = -1;
   long max_scans = -1;
@@ -112,6 +115,7 @@ int main(int argc, char** argv) {
     else if (a == "--thin") thin_dist = std::atof(val());
     else if (a == "--recent-keyframes") recent_keyframes = std::atoi(val());
     else if (a == "--localize") localize = true;
+    else if (a == "--on-device") on_device = true;
     else if (a == "--loc-radius") loc_radius = std::atof(val());
     else if (a == "--relocalize") relocalize = true;
     else if (a == "--reloc-start") reloc_start = std::atol(val());
@@ -293,7 +297,7 @@ int main(int argc, char** argv) {
     const int nf = st[0];
     std::vector<std::vector<alego_point>> clouds((size_t)nf * 3);
     std::vector<alego_kf_in> frames(nf);
-    for (int i = 0; i < nf; ++i) {
+    for (int i = 0; i < nf && !on_device; ++i) {
       alego_keyframe kf{};
       kf.corner = kc.data(); kf.corner_cap = N; kf.surf = ks.data(); kf.surf_cap = N; kf.outlier = ko.data(); kf.outlier_cap = N;
       if (alego_map_get_keyframe(h, 0, i, &kf) < 0) { std::fprintf(stderr, "map_get_keyframe: %s\n", alego_last_error(h)); alego_destroy(h); return 1; }
@@ -307,7 +311,10 @@ int main(int argc, char** argv) {
     }
     alego_handle* hl = nullptr;
     if (alego_create(&P, 0, 1, 1, &hl)) { std::fprintf(stderr, "alego_create (localising handle) failed\n"); alego_destroy(h); return 1; }
-    if (alego_loc_enable(hl, frames.data(), nf, loc_radius) != ALEGO_OK) { std::fprintf(stderr, "loc_enable: %s\n", alego_last_error(hl)); alego_destroy(hl); alego_destroy(h); return 1; }
+    // --on-device: the mapping handle stays alive and hands its archive over on the device; no frame comes to the host
+    if ((on_device ? alego_loc_enable_from_map(hl, h, 0, loc_radius, 0) : alego_loc_enable(hl, frames.data(), nf, loc_radius)) != ALEGO_OK) {
+      std::fprintf(stderr, "%s: %s\n", on_device ? "loc_enable_from_map" : "loc_enable", alego_last_error(hl)); alego_destroy(hl); alego_destroy(h); return 1;
+    }
     if (relocalize && alego_reloc_enable(hl, reloc_range, 0.0 / 0.0) != ALEGO_OK) { std::fprintf(stderr, "reloc_enable: %s\n", alego_last_error(hl)); alego_destroy(hl); alego_destroy(h); return 1; }
     if (reloc_start < 0) reloc_start = n_scans / 2;
     int reloc_status = -1;   // -1: not asked for; 0: no verdict yet
@@ -353,7 +360,8 @@ int main(int argc, char** argv) {
     }
     char buf[320];
     int len = std::snprintf(buf, sizeof(buf), ", \"loc_frames\": %d, \"loc_map_t\": [%.17g, %.17g, %.17g], \"loc_max_dev\": %.9g", nf, lm.t[0], lm.t[1], lm.t[2], max_dev);
-    if (relocalize) std::snprintf(buf + len, sizeof(buf) - len, ", \"reloc_status\": %d", reloc_status);
+    if (relocalize) len += std::snprintf(buf + len, sizeof(buf) - len, ", \"reloc_status\": %d", reloc_status);
+    if (on_device) std::snprintf(buf + len, sizeof(buf) - len, ", \"loc_on_device\": 1");
     loc_json = buf;
     alego_destroy(hl);
   }

@@ -542,12 +542,44 @@ int alego_graph_check_host(const double* poses12, int32_t n_poses, const alego_g
  *                      or the store does not fit.  Device memory: 32 * (corner capacity + surf capacity + outlier capacity) + 112 B per
  *                      frame, once per handle; the slots' own key-frame rings are released.
  *   alego_loc_status   out = {map frames, frames in the window of the last mapping frame, local-map rebuilds so far, 1 if that frame optimised}
+ *   alego_loc_enable_from_map   alego_loc_enable with the frames taken on the device from the archive of `slot` of the mapping handle `map`
+ *                      (same process, same device) as it is NOW: N = its stored frames, frame i = what alego_map_get_keyframe(map, slot, i)
+ *                      returns now, i.e. with the poses alego_graph_optimize, alego_map_set_keyposes, _move, _merge or _thin left.  Every
+ *                      observable of the handle afterwards is bit-identical to alego_loc_enable on those frames; no frame crosses to the host.
+ *                      The frames go through the store in chunks.  Every stream of `map` is synchronised first (a key
+ *                      frame queued by alego_batch_run(.., sync = 0) is handed over); then `map` is only read and keeps mapping.  An archive
+ *                      that dropped frames hands over its stored prefix.  capacity: frames the store is allocated for; <= 0: N; it sizes the
+ *                      memory (below, per frame of capacity) and changes no result.  Preconditions, codes and messages of alego_loc_enable,
+ *                      and ALEGO_ERR_ARG: map null, map == h, map without archive, slot out of range of map, handles on different devices;
+ *                      ALEGO_ERR_CAPACITY: a frame exceeds h's key-frame capacities (the message names the first one and its counts; decided
+ *                      from a host copy of the archive's frame table before anything is allocated), N > 8192, capacity < N or > 8192.  After
+ *                      any failure h is the SLAM handle it was.  A store built by alego_loc_enable has capacity max(N, 1).  During the call a
+ *                      temporary staging area and sort scratch of at most 256 MiB are held (16 B per point of staging, 20 B per point of
+ *                      scratch for a run of more than 8192 points, per frame of a chunk).
+ *   alego_loc_update_from_map   on a handle that localises, at any time; synchronous; runs behind the work queued on every stream group of h
+ *                      and behind map's.  The WHOLE store is rebuilt from the archive as it is now (N may shrink or grow up to the store's
+ *                      capacity), and every slot of h gets what alego_lm_reset_window does to a SLAM slot: its window is emptied, its voxel
+ *                      lists and local maps are stale, and its next mapping frame selects in the new map at its own pose and rebuilds.  Map ->
+ *                      odom, params_, LaserOdometry's state and the scan counters of every slot stay bit for bit; alego_loc_status reports the
+ *                      new frame count at once and window 0 until the slot's next mapping frame.  After alego_reloc_enable the map descriptors
+ *                      and ring keys are rebuilt too (their buffers are sized by the store's capacity).  ALEGO_ERR_ARG: h does not localise,
+ *                      or a source case of alego_loc_enable_from_map.  ALEGO_ERR_CAPACITY: N exceeds the store's capacity or a frame h's
+ *                      key-frame capacities — decided before anything is written, the store is untouched.  A device error in the middle
+ *                      returns ALEGO_ERR_HIP and leaves the store EMPTY (0 frames: every slot is off the map and dead-reckons, rule 5) until
+ *                      an update succeeds.
+ *   A host that drives the handles from several threads holds both handles' locks around either call (alego_handle_lock), map's first.
+ *   alego_debug_get names of a localising handle (tests; the slot argument is ignored, <f> is a frame of the store): "ls_corner:<f>" /
+ *   "ls_surf:<f>" the sorted corner / surf + outlier run, "ls_box_c:<f>" / "ls_box_s:<f>" their boxes (8 floats), "ls_raw_c:<f>" / "ls_raw_s:<f>" /
+ *   "ls_raw_o:<f>" the clouds as stored, "ls_pose:<f>" (8 floats), "ls_counts:<f>" (i32: the two run counts, then corner, surf, outlier points).
+ *   alego_debug_set_option("ALEGO_LOC_CHUNK", c) on the localising handle sets the frames per chunk of both calls (default 128).
  * On a localising handle alego_map_enable / alego_graph_enable, every alego_map_* / alego_graph_* call that takes a handle,
  * alego_loop_search, alego_lm_add_keyframe / _set_keypose / _reset_window / _get_keyframe, alego_stream_setup, alego_dist_init and
  * alego_debug_set_option("ALEGO_MAP_MERGE", 0) return ALEGO_ERR_ARG.  alego_debug_get(.., "lm_window") returns the window's map-frame ids;
  * doubles 44..46 of "lm_state" hold p of the last mapping frame. */
 int alego_loc_select(const float* keyposes6, int32_t n, const float xyz[3], double radius, int32_t k, int32_t* ids);
 int alego_loc_enable(alego_handle* h, const alego_kf_in* frames, int32_t n, double radius);
+int alego_loc_enable_from_map(alego_handle* h, alego_handle* map, int slot, double radius, int32_t capacity);
+int alego_loc_update_from_map(alego_handle* h, alego_handle* map, int slot);
 int alego_loc_status(alego_handle* h, int slot, int32_t out[4]);
 
 /* ---- relocalisation: placing slots of a localising handle without an initial pose ------------------------
@@ -573,7 +605,7 @@ int alego_loc_status(alego_handle* h, int slot, int32_t out[4]);
  *               sqrt(R21^2 + R22^2)), yaw = atan2(R10, R00) of its rotation); map -> odom and params_ are set as alego_lm_apply_correction(rc)
  *               and alego_set_lm_params(params6) set them.  The window is left alone: the next mapping frame selects at the new pose.
  * alego_reloc_enable     once, after alego_loc_enable (else ALEGO_ERR_ARG; a second call too): builds the N map descriptors and ring keys on the
- *                        device.  max_range <= 0: 80.0; z_offset not finite: 4.0.  Device memory: 1240 B per map frame and per slot; search and
+ *                        device.  max_range <= 0: 80.0; z_offset not finite: 4.0.  Device memory: 1240 B per frame of the store's capacity and per slot; search and
  *                        ICP scratch grows on first use and stays with the handle.  Without the call nothing is allocated or launched.
  * alego_loc_relocalize   synchronous; runs behind the work queued on every stream group.  out[i] belongs to slots[i]; a slot's result does not
  *                        depend on the other slots, their order or the chunking.  ALEGO_ERR_ARG: not enabled, a slot out of range or listed
