@@ -1,9 +1,10 @@
 // ip_common.h — device pieces shared by the ImageProjection kernels (kernels_ip.hip: the multi-kernel path; kernels_ipf.hip: the
-// one-workgroup-per-stream fused path): the cell of an input point, the ground test, the segmentation's edge predicate and the
-// 16-bit LDS union-find.
+// one-workgroup-per-stream fused path; kernels_ipb.hip: the banded path): the cell of an input point, the ground test, the segmentation's
+// edge predicate, the records and the count scan of the ordered compaction (their rules: ip_rules.h) and the 16-bit LDS union-find.
 #ifndef ALEGO_IP_COMMON_H_
 #define ALEGO_IP_COMMON_H_
 #include "dev_common.h"
+#include "ip_rules.h"
 
 // The cell of one input point (imageProjection.cpp:76-97; IP.cpp:91,142-172): row * H + col, or -1 when the point is rejected (row /
 // column out of range, non-finite, near filter).  *valid_out = the point survives pcl::removeNaNFromPointCloud / removeClosedPointCloud,
@@ -219,6 +220,65 @@ DEV_INLINE bool ip_is_ground(const DevCtx& d, float fx, float fy, float fz) {
   return ip_ground_decide(d.tan_g_lo, d.tan_g_hi, d.P.sensor_mount_ang, d.P.ground_angle_thres, fx, fy, fz);
 }
 
+// ---- what the compaction writes (imageProjection.cpp:158-191).  Which cell gets which record is ip_rules.h's; here is the record.  Every pointer is
+// already offset to the stream's slot (ip_fused_t hands in the ones it fetched late from the kernel-argument segment); q = the cell's input point. ----
+DEV_INLINE bool ip_feasible(const alego_params& P, int size, int n_rows) { return ip_seg_feasible(P.seg_big_num, P.seg_valid_point_num, P.seg_valid_line_num, size, n_rows); }
+DEV_INLINE int ip_size_class(const alego_params& P, int size) { return ip_seg_size_class(P.seg_big_num, P.seg_valid_point_num, size); }
+DEV_INLINE bool ip_class_feasible(const alego_params& P, int size_class, int n_rows) { return ip_seg_class_feasible(size_class, P.seg_valid_line_num, n_rows); }
+DEV_INLINE float ip_point_range(float4 q) { return sqrtf(q.x * q.x + q.y * q.y + q.z * q.z); }   // the range image's value (:99), recomputed from the point
+// a kept cell: segmentedCloud, GroundFlag, ColInd, Range at output line `line` (:178-186); `range` where the caller has it in hand
+DEV_INLINE void ip_store_kept(float4* seg_pts, uint8_t* seg_ground, int* seg_col, float* seg_range, int line, float4 q, int row, int col, double colfrac, bool ground, float range) {
+  seg_pts[line] = make_float4(q.x, q.y, q.z, ip_intensity(row, colfrac));
+  seg_ground[line] = ground ? 1 : 0;
+  seg_col[line] = col;
+  seg_range[line] = range;
+}
+DEV_INLINE void ip_store_kept(float4* seg_pts, uint8_t* seg_ground, int* seg_col, float* seg_range, int line, float4 q, int row, int col, double colfrac, bool ground) {
+  ip_store_kept(seg_pts, seg_ground, seg_col, seg_range, line, q, row, col, colfrac, ground, ip_point_range(q));
+}
+// an outlier: outlierCloud at its own line (:165-171)
+DEV_INLINE void ip_store_outlier(float4* outlier, int line, float4 q, int row, double colfrac) { outlier[line] = make_float4(q.x, q.y, q.z, ip_intensity(row, colfrac)); }
+// startRingIndex / endRingIndex of one ring; ring_start / ring_end point at that ring's entries
+DEV_INLINE void ip_store_ring(int* ring_start, int* ring_end, int first_line, int next_first_line) { *ring_start = ip_ring_start(first_line); *ring_end = ip_ring_end(next_first_line); }
+// kept cells, outliers, feasible segments of the scan; sc = the slot's scalars
+DEV_INLINE void ip_store_totals(int* sc, int n_kept, int n_outliers, int n_feasible) { sc[SC_M] = n_kept; sc[SC_NOUT] = n_outliers; sc[SC_NFEAS] = n_feasible; }
+
+// Exclusive scan, in place, of three count tables of n <= 64 * NWS entries each (kept cells, outliers, feasible roots, in output order).  Thread e takes
+// entry e: the first NWS wavefronts work, every thread of the workgroup calls.  T = the tables' storage type (sums below its range).  wtot: LDS; it is
+// left holding the wavefronts' sums, which ip_scan_total adds up for whoever needs a table's total, until the caller's next barrier.  One barrier
+// inside; the caller's next one publishes the tables.
+template <int NWS, class T>
+DEV_INLINE void ip_scan3(T* c0, T* c1, T* c2, int n, int (*wtot)[NWS]) {
+  const int e = threadIdx.x, lane = lane_id(), wave = e >> 6;
+  const bool work = e < 64 * NWS, in = e < n;
+  T* const c[3] = {c0, c1, c2};
+  int v3[3] = {0, 0, 0}, in3[3] = {0, 0, 0};
+  if (work) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      v3[a] = in ? (int)c[a][e] : 0;
+      in3[a] = wave_incl_scan(v3[a]);
+      if (lane == 63) wtot[a][wave] = in3[a];
+    }
+  }
+  __syncthreads();
+  if (work) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      int woff = 0;
+#pragma unroll
+      for (int w = 0; w < NWS; ++w) if (w < wave) woff += wtot[a][w];
+      if (in) c[a][e] = (T)(woff + in3[a] - v3[a]);
+    }
+  }
+}
+template <int NWS>
+DEV_INLINE int ip_scan_total(const int* wtot_a) {
+  int t = 0;
+#pragma unroll
+  for (int w = 0; w < NWS; ++w) t += wtot_a[w];
+  return t;
+}
 
 // 16-bit variant for n_scan <= 16 (every such image has < 65536 cells): the parent array takes 2 B/cell (58 KB at 16x1800
 // instead of 115 KB), so that two of these workgroups — or one of them and the other stream groups' workgroups — fit a CU;

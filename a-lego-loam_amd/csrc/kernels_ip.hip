@@ -9,9 +9,10 @@
 //   cc_lds        a5 for small images with more than 16 rings (4 B/cell in LDS)
 //   cc_tile / cc_seam   a5 for larger images (64x2048): column bands labelled in LDS, seams linked in global memory
 //   cc_runs / cc_link   a5, the global-memory union-find they replaced (ALEGO_CC_TILE=0): root = minimum linear index == BFS discovery order (:147-156)
-//   cc_stats      a5: per-component size and row mask -> feasibility (:282-301)
-//   ip_rowcount / ip_compact  a6: per-row ballot compaction with the +5/-6 ring convention (:158-191)
-//   ip_labels     label_mat_ numbering 1,2,.. in discovery order / 999999 / -1 (:303-314)
+//   cc_stats      a5: per-component size and row mask (:282-301)
+//   ip_rowcount / ip_compact  a6: per-row ballot compaction (:158-191)
+//   ip_labels     label_mat_ (:303-314)
+// The output rules — feasible segment, a cell's class, ring indices, label numbers, intensity — are ip_rules.h's, the records ip_common.h's.
 //
 // All kernels are launched with blockIdx.y = slot (independent stream).
 // HBM-bound: one scan moves 16 B/point in and 25 B/segmented point out; the images
@@ -173,7 +174,7 @@ __global__ void __launch_bounds__(IPF_W) ip_front(DevCtx d, int ring_pos, int in
       }
       s_r[row * IPF_W + tid] = r;
       if (mine && (init & 8)) rimg[row * d.H + col] = r;
-      if (row >= 1 && row - 1 < P.ground_scan_id && ok && lower_ok) {  // :111-131, pair (row-1,row)
+      if (ip_ground_pair(row, P.ground_scan_id) && ok && lower_ok) {  // :111-131, pair (row-1,row)
         if (ip_is_ground(d, x - lx, y - ly, z - lz)) ground |= 3ull << (row - 1);
       }
       lx = x; ly = y; lz = z; lower_ok = ok;
@@ -302,11 +303,11 @@ __global__ void __launch_bounds__(IP_BLOCK) cc_link(DevCtx d) {
   cc_union(parent, v, u);
 }
 
-// Whole-image union-find in LDS for images of up to CC_LDS_MAXN cells (16x1800): one workgroup per stream keeps
-// the parent array on chip (4 B/cell, 115 KB at 16x1800), so every find hop is an LDS access (~64 cycles) instead
-// of an L2 round trip, and the compare-and-swap of a union is an LDS atomic.  Same algorithm as cc_link
-// (ECL-CC: pointer jumping find, link the larger root under the smaller), so the roots are identical.
-// Larger images (16x4000, 64x2048) use the global-memory path cc_runs + cc_link.
+// Whole-image union-find in LDS for images of more than 16 rings and up to CC_LDS_MAXN cells (17x70, 24x320; <= 16 rings: cc_lds16): one
+// workgroup per stream keeps the parent array on chip (4 B/cell), so every find hop is an LDS access (~64 cycles) instead of an L2 round
+// trip, and the compare-and-swap of a union is an LDS atomic.  Same algorithm as cc_link (ECL-CC: pointer jumping find, link the larger
+// root under the smaller), so the roots are identical.  Written: the root image; cc_stats, ip_rowcount and ip_compact follow (launch_ip).
+// Larger images (64x2048) use cc_tile + cc_seam or the global-memory path cc_runs + cc_link.
 #define CC_LDS_THREADS 1024
 #define CC_LDS_MAXN 36864
 #define CC_LDS16_MAXN 64512   // cc_lds16 (2 B/cell, <= 16 rings): 63 cells per thread; covers the reference geometry 16 x 4000 (126 KB of LDS)
@@ -330,7 +331,7 @@ DEV_INLINE void ccl_union(int* parent, int a, int b) {
     }
   } while (repeat);
 }
-__global__ void __launch_bounds__(CC_LDS_THREADS) cc_lds(DevCtx d, int ring_pos, int fused) {
+__global__ void __launch_bounds__(CC_LDS_THREADS) cc_lds(DevCtx d) {
   const int slot = blockIdx.x + d.slot0;
   const size_t base = (size_t)slot * d.N;
   extern __shared__ __attribute__((aligned(16))) unsigned char cc_smem[];
@@ -346,130 +347,11 @@ __global__ void __launch_bounds__(CC_LDS_THREADS) cc_lds(DevCtx d, int ring_pos,
     if (f & 8) ccl_union(parent, v, v + H);
   }
   __syncthreads();
-  // roots into registers, then the LDS array is reused for the per-root statistics of :282-301
-  // (low 16 bits = size < 65536, high 16 bits = row mask: needs n_scan <= 16, otherwise cc_stats does it)
-  constexpr int PER = (CC_LDS_MAXN + CC_LDS_THREADS - 1) / CC_LDS_THREADS;
-  int rt[PER];
-#pragma unroll
-  for (int k = 0; k < PER; ++k) {
-    const int v = threadIdx.x + k * CC_LDS_THREADS;
-    rt[k] = -1;
-    if (v < N && (fi[v] & 2)) { int r = parent[v], nx; while (r > (nx = parent[r])) r = nx; rt[k] = r; }
-  }
-  __syncthreads();
-  const bool stats = d.NS <= 16;
-  if (stats) {
-#pragma unroll
-    for (int k = 0; k < PER; ++k) { const int v = threadIdx.x + k * CC_LDS_THREADS; if (v < N) parent[v] = 0; }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < PER; ++k) {
-      const int v = threadIdx.x + k * CC_LDS_THREADS;
-      if (rt[k] >= 0) {  // LDS atomics resolve same-address lanes in hardware; no wave aggregation needed here
-        atomicAdd(&parent[rt[k]], 1);
-        atomicOr((unsigned*)&parent[rt[k]], 1u << (16 + v / H));
-      }
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int k = 0; k < PER; ++k) {
-    const int v = threadIdx.x + k * CC_LDS_THREADS;
-    if (v < N) {
-      d.parent[base + v] = rt[k];
-      if (stats && rt[k] == v) { const unsigned w = (unsigned)parent[v]; d.cc_size[base + v] = (int)(w & 0xFFFFu); d.cc_rows[base + v] = (unsigned long long)(w >> 16); }
-    }
-  }
-  if (!stats || !fused) return;  // ip_rowcount / ip_compact follow (launch_ip)
-  // ---- fused a6: ordered compaction of the whole image (replaces ip_rowcount + ip_compact for this geometry).
-  // Chunk k = cells [1024 k, 1024 k + 1024) in row-major order, one cell per thread: per-(chunk, wavefront) counts of
-  // kept cells / outliers / feasible roots, one exclusive scan over the (chunk, wavefront) table, then every cell
-  // knows its output line.  Classification as ip_classify, with the component statistics still in LDS.
-  constexpr int NW = CC_LDS_THREADS / 64;
-  __shared__ int s_cnt[3][PER * NW];
-  __shared__ int s_wtot[3][NW];
-  const int lane = lane_id(), wave = threadIdx.x >> 6;
-  const alego_params& P = d.P;
-  unsigned long long keep_m = 0, outl_m = 0, root_m = 0;
-#pragma unroll
-  for (int k = 0; k < PER; ++k) {
-    const int v = threadIdx.x + k * CC_LDS_THREADS;
-    int c = 0;
-    bool fr = false;
-    if (v < N) {
-      const uint8_t f = fi[v];
-      const int row = v / H, col = v - row * H;
-      if (f & 1) c = (col % 5 == 0 || col <= 4 || col >= H - 5) ? 1 : 0;
-      else if (f & 2) {
-        const unsigned w = (unsigned)parent[rt[k]];
-        const int sz = (int)(w & 0xFFFFu);
-        const bool feas = sz >= P.seg_big_num || (sz >= P.seg_valid_point_num && __popc(w >> 16) >= P.seg_valid_line_num);
-        fr = feas && rt[k] == v;
-        c = feas ? 1 : ((row > P.ground_scan_id && col % 5 == 0) ? 2 : 0);
-      }
-    }
-    if (c == 1) keep_m |= 1ull << k;
-    if (c == 2) outl_m |= 1ull << k;
-    if (fr) root_m |= 1ull << k;
-    const unsigned long long bk = __ballot(c == 1), bo = __ballot(c == 2), bf = __ballot(fr);
-    if (lane == 0) { s_cnt[0][k * NW + wave] = (int)__popcll(bk); s_cnt[1][k * NW + wave] = (int)__popcll(bo); s_cnt[2][k * NW + wave] = (int)__popcll(bf); }
-  }
-  __syncthreads();
-  {  // exclusive scan of the three count tables (PER * NW <= 1024 entries: one per thread)
-    const int e = threadIdx.x;
-    int v3[3], in3[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      v3[a] = e < PER * NW ? s_cnt[a][e] : 0;
-      in3[a] = wave_incl_scan(v3[a]);
-      if (lane == 63) s_wtot[a][wave] = in3[a];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      int woff = 0;
-#pragma unroll
-      for (int w = 0; w < NW; ++w) if (w < wave) woff += s_wtot[a][w];
-      if (e < PER * NW) s_cnt[a][e] = woff + in3[a] - v3[a];
-    }
-    if (threadIdx.x == 0) {
-      int t3[3] = {0, 0, 0};
-#pragma unroll
-      for (int a = 0; a < 3; ++a) for (int w = 0; w < NW; ++w) t3[a] += s_wtot[a][w];
-      int* sc = scal_of(d, slot);
-      sc[SC_M] = t3[0]; sc[SC_NOUT] = t3[1]; sc[SC_NFEAS] = t3[2];
-      *ring_end_before(d, slot, d.NS) = t3[0] - 1 - 5;   // :190 for the last row
-    }
-  }
-  __syncthreads();
-  const float4* pts = scan_pts(d, slot, ring_pos);
-  const unsigned long long below = (1ull << lane) - 1ull;
-#pragma unroll 4
-  for (int k = 0; k < PER; ++k) {
-    const int v = threadIdx.x + k * CC_LDS_THREADS;
-    const bool kp = (keep_m >> k) & 1ull, ol = (outl_m >> k) & 1ull, fr = (root_m >> k) & 1ull;
-    const unsigned long long bk = __ballot(kp), bo = __ballot(ol), bf = __ballot(fr);
-    if (v >= N) continue;
-    const int row = v / H, col = v - row * H;
-    const int line = s_cnt[0][k * NW + wave] + (int)__popcll(bk & below);   // kept cells before this one
-    if (col == 0) {   // ring convention of :161,:190
-      *ring_start_of(d, slot, row) = line + 5;
-      if (row > 0) *ring_end_before(d, slot, row) = line - 1 - 5;
-    }
-    if (kp || ol) {
-      float4 p = pts[ip_owner_index(d.owner[base + v])];
-      p.w = (float)(row + d.ip_colfrac[col]);  // :101
-      if (kp) {
-        d.seg_pts[base + line] = p;
-        d.seg_ground[base + line] = fi[v] & 1;
-        d.seg_col[base + line] = col;
-        d.seg_range[base + line] = sqrtf(p.x * p.x + p.y * p.y + p.z * p.z);   // = the range image's value (:99), recomputed from the point
-      } else {
-        d.outlier[base + s_cnt[1][k * NW + wave] + (int)__popcll(bo & below)] = p;
-      }
-    }
-    // label_cnt_ numbering (:303-306); 0 for the root of an infeasible component (ip_labels turns it into 999999)
-    if (rt[k] == v) d.cc_label[base + v] = fr ? s_cnt[2][k * NW + wave] + (int)__popcll(bf & below) + 1 : 0;
+  // the root image: -1 for the cells that are not active (read-only find: nobody writes any more)
+  for (int v = threadIdx.x; v < N; v += CC_LDS_THREADS) {
+    int r = -1;
+    if (fi[v] & 2) { int nx; r = parent[v]; while (r > (nx = parent[r])) r = nx; }
+    d.parent[base + v] = r;
   }
 }
 
@@ -562,7 +444,7 @@ extern "C" void alego_cc_times(long long* out) { (void)hipMemcpyFromSymbol(out, 
 // streams' wavefronts share the CU.
 // Compaction: chunk k = cells [1024 k, 1024 k + 1024) in row-major order, one cell per thread: per-(chunk, wavefront)
 // counts of kept cells / outliers / feasible roots, one exclusive scan over the (chunk, wavefront) table, then every cell
-// knows its output line.  Classification as ip_classify.
+// knows its output line.  The rules (feasible segment, a cell's class, ring indices, labels): ip_rules.h.
 __global__ void __attribute__((amdgpu_waves_per_eu(8, 8))) __launch_bounds__(CC_T) cc_lds16(DevCtx d, int ring_pos, int fused) {
   const int slot = blockIdx.x + d.slot0;
   const size_t base = (size_t)slot * d.N;
@@ -660,8 +542,9 @@ __global__ void __attribute__((amdgpu_waves_per_eu(8, 8))) __launch_bounds__(CC_
     if (flag_of(k) & 2) {
       const int r = root_of(k, v);
       const int sz = (int)par[r];
-      if (sz >= P.seg_big_num) big_m |= 1ull << k;
-      else if (sz >= P.seg_valid_point_num) mid_m |= 1ull << k;
+      const int cls = ip_size_class(P, sz);
+      if (cls == IP_SEG_BIG) big_m |= 1ull << k;
+      else if (cls == IP_SEG_MID) mid_m |= 1ull << k;
       if (!(fused & 1) && r == v) d.cc_size[base + v] = sz;
     }
   }
@@ -674,7 +557,7 @@ __global__ void __attribute__((amdgpu_waves_per_eu(8, 8))) __launch_bounds__(CC_
     if ((head_m >> k) & 1ull) { const int r = root_of(k, v); atomicOr(&parw[r >> 1], (1u << cell_row(d, v)) << ((r & 1) * 16)); }
   }
   __syncthreads();
-  unsigned long long feas_m = big_m;
+  unsigned long long feas_m = 0;
 #pragma unroll 1
   for (int k = 0; k < per; ++k) {
     const int v = threadIdx.x + k * CC_T;
@@ -682,7 +565,8 @@ __global__ void __attribute__((amdgpu_waves_per_eu(8, 8))) __launch_bounds__(CC_
     if (flag_of(k) & 2) {
       r = root_of(k, v);
       const unsigned rows = par[r];
-      if (((mid_m >> k) & 1ull) && __popc(rows) >= P.seg_valid_line_num) feas_m |= 1ull << k;
+      const int cls = ((big_m >> k) & 1ull) ? IP_SEG_BIG : (((mid_m >> k) & 1ull) ? IP_SEG_MID : IP_SEG_SMALL);
+      if (ip_class_feasible(P, cls, __popc(rows))) feas_m |= 1ull << k;
       if (!(fused & 1) && r == v) d.cc_rows[base + v] = (unsigned long long)rows;
     }
     if ((fused & 2) && v < N) d.parent[base + v] = r;
@@ -702,46 +586,23 @@ __global__ void __attribute__((amdgpu_waves_per_eu(8, 8))) __launch_bounds__(CC_
     if (v < N) {
       const unsigned f = flag_of(k);
       const int row = cell_row(d, v), col = v - row * H;
-      if (f & 1) c = (col % 5 == 0 || col <= 4 || col >= H - 5) ? 1 : 0;
-      else if (f & 2) {
-        const bool feas = (feas_m >> k) & 1ull;
-        fr = feas && ((self_m >> k) & 1ull);
-        c = feas ? 1 : ((row > P.ground_scan_id && col % 5 == 0) ? 2 : 0);
-      }
+      const bool feas = (feas_m >> k) & 1ull;
+      c = ip_cell_class(f & 1, f & 2, feas, row, col, H, P.ground_scan_id);
+      fr = feas && ((self_m >> k) & 1ull);   // (feas_m: active cells only)
     }
-    if (c == 1) keep_m |= 1ull << k;
-    if (c == 2) outl_m |= 1ull << k;
+    if (c == IP_KEEP) keep_m |= 1ull << k;
+    if (c == IP_OUTLIER) outl_m |= 1ull << k;
     if (fr) root_m |= 1ull << k;
-    const unsigned long long bk = __ballot(c == 1), bo = __ballot(c == 2), bf = __ballot(fr);
+    const unsigned long long bk = __ballot(c == IP_KEEP), bo = __ballot(c == IP_OUTLIER), bf = __ballot(fr);
     if (lane == 0) { s_cnt[0][k * NW + wave] = (int)__popcll(bk); s_cnt[1][k * NW + wave] = (int)__popcll(bo); s_cnt[2][k * NW + wave] = (int)__popcll(bf); }
   }
   __syncthreads();
   CC_TICK(6);
-  {
-    const int e = threadIdx.x;
-    int v3[3], in3[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      v3[a] = e < per * NW ? s_cnt[a][e] : 0;
-      in3[a] = wave_incl_scan(v3[a]);
-      if (lane == 63) s_wtot[a][wave] = in3[a];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      int woff = 0;
-#pragma unroll
-      for (int w = 0; w < NW; ++w) if (w < wave) woff += s_wtot[a][w];
-      if (e < per * NW) s_cnt[a][e] = woff + in3[a] - v3[a];
-    }
-    if (threadIdx.x == 0) {
-      int t3[3] = {0, 0, 0};
-#pragma unroll
-      for (int a = 0; a < 3; ++a) for (int w = 0; w < NW; ++w) t3[a] += s_wtot[a][w];
-      int* sc = scal_of(d, slot);
-      sc[SC_M] = t3[0]; sc[SC_NOUT] = t3[1]; sc[SC_NFEAS] = t3[2];
-      *ring_end_before(d, slot, d.NS) = t3[0] - 1 - 5;
-    }
+  ip_scan3<NW>(s_cnt[0], s_cnt[1], s_cnt[2], per * NW, s_wtot);
+  if (threadIdx.x == 0) {
+    const int n_kept = ip_scan_total<NW>(s_wtot[0]);
+    ip_store_totals(scal_of(d, slot), n_kept, ip_scan_total<NW>(s_wtot[1]), ip_scan_total<NW>(s_wtot[2]));
+    *ring_end_before(d, slot, d.NS) = ip_ring_end(n_kept);   // :190 for the last row
   }
   __syncthreads();
   CC_TICK(7);
@@ -759,22 +620,16 @@ __global__ void __attribute__((amdgpu_waves_per_eu(8, 8))) __launch_bounds__(CC_
     if (v >= N) return;
     const int row = cell_row(d, v), col = v - row * H;
     const int line = s_cnt[0][k * NW + wave] + (int)__popcll(bk & below);
-    if (col == 0) {
-      *ring_start_of(d, slot, row) = line + 5;
-      if (row > 0) *ring_end_before(d, slot, row) = line - 1 - 5;
+    if (col == 0) {   // a ring starts here and closes the one below (:161,:190)
+      *ring_start_of(d, slot, row) = ip_ring_start(line);
+      if (row > 0) *ring_end_before(d, slot, row) = ip_ring_end(line);
     }
     if (kp || ol) {
-      const float4 p = make_float4(q.x, q.y, q.z, (float)(row + d.ip_colfrac[col]));
-      if (kp) {
-        d.seg_pts[base + line] = p;
-        d.seg_ground[base + line] = (uint8_t)(flag_of(k) & 1);
-        d.seg_col[base + line] = col;
-        d.seg_range[base + line] = rg;
-      } else {
-        d.outlier[base + s_cnt[1][k * NW + wave] + (int)__popcll(bo & below)] = p;
-      }
+      const double cf = d.ip_colfrac[col];
+      if (kp) ip_store_kept(d.seg_pts + base, d.seg_ground + base, d.seg_col + base, d.seg_range + base, line, q, row, col, cf, flag_of(k) & 1, rg);
+      else ip_store_outlier(d.outlier + base, s_cnt[1][k * NW + wave] + (int)__popcll(bo & below), q, row, cf);
     }
-    if ((self_m >> k) & 1ull) d.cc_label[base + v] = fr ? s_cnt[2][k * NW + wave] + (int)__popcll(bf & below) + 1 : 0;
+    if ((self_m >> k) & 1ull) d.cc_label[base + v] = ip_root_label(fr, s_cnt[2][k * NW + wave] + (int)__popcll(bf & below));
   };
   // clamped addresses instead of branches: the three owner loads, then the three point gathers and ranges, are in flight together
   auto cell_of = [&](int k) -> int { return ((out_m >> k) & 1ull) ? threadIdx.x + k * CC_T : min((int)threadIdx.x, N - 1); };   // (images of fewer than CC_T cells exist: 1 x 720)
@@ -784,8 +639,7 @@ __global__ void __attribute__((amdgpu_waves_per_eu(8, 8))) __launch_bounds__(CC_
     const int o0 = d.owner[base + c0], o1 = d.owner[base + c1], o2 = d.owner[base + c2];
     const float4 q0 = pts[ip_owner_index(max(o0, 0))], q1 = pts[ip_owner_index(max(o1, 0))], q2 = pts[ip_owner_index(max(o2, 0))];
     // segmentedCloudRange = the range image's value (:99,:184), recomputed from the point instead of read back
-    emit(k0, q0, sqrtf(q0.x * q0.x + q0.y * q0.y + q0.z * q0.z)); emit(k0 + 1, q1, sqrtf(q1.x * q1.x + q1.y * q1.y + q1.z * q1.z));
-    emit(k0 + 2, q2, sqrtf(q2.x * q2.x + q2.y * q2.y + q2.z * q2.z));
+    emit(k0, q0, ip_point_range(q0)); emit(k0 + 1, q1, ip_point_range(q1)); emit(k0 + 2, q2, ip_point_range(q2));
   }
   __syncthreads();
   CC_TICK(8);
@@ -829,26 +683,18 @@ __global__ void __launch_bounds__(IP_BLOCK) cc_stats(DevCtx d) {
   }
 }
 
-DEV_INLINE bool cc_feasible(const DevCtx& d, size_t base, int root) {
-  const int sz = d.cc_size[base + root];
-  if (sz >= d.P.seg_big_num) return true;
-  if (sz >= d.P.seg_valid_point_num) return __popcll(d.cc_rows[base + root]) >= d.P.seg_valid_line_num;
-  return false;
-}
-
-// classification of a cell for the compaction sweep (:164-188): 1 keep, 2 outlier, 0 drop
+// class of a cell for the compaction sweep (ip_cell_class, ip_rules.h) from the flag, root and statistics images
 DEV_INLINE int ip_classify(const DevCtx& d, size_t base, int v, int row, int col, bool* is_feas_root) {
   const uint8_t f = d.flag_img[base + v];
+  bool feas = false;
   *is_feas_root = false;
-  if (f & 1) return (col % 5 == 0 || col <= 4 || col >= d.H - 5) ? 1 : 0;
   if (f & 2) {
     const int root = d.parent[base + v];
-    const bool feas = cc_feasible(d, base, root);
+    const int cls = ip_size_class(d.P, d.cc_size[base + root]);   // (the row mask is read only where it decides)
+    feas = ip_class_feasible(d.P, cls, cls == IP_SEG_MID ? (int)__popcll(d.cc_rows[base + root]) : 0);
     *is_feas_root = feas && root == v;
-    if (feas) return 1;
-    return (row > d.P.ground_scan_id && col % 5 == 0) ? 2 : 0;
   }
-  return 0;
+  return ip_cell_class(f & 1, f & 2, feas, row, col, d.H, d.P.ground_scan_id);
 }
 
 // per-row counts: kept cells, outliers, feasible roots.  grid (NS, slots)
@@ -860,7 +706,7 @@ __global__ void __launch_bounds__(IP_BLOCK) ip_rowcount(DevCtx d) {
     bool fr;
     const int v = row * d.H + col;
     const int c = ip_classify(d, base, v, row, col, &fr);
-    nk += c == 1; no += c == 2; nf += fr;
+    nk += c == IP_KEEP; no += c == IP_OUTLIER; nf += fr;
     // the class of the cell for ip_compact (bits 4-5, bit 6: feasible root): the sweep that follows asks the flag byte instead of walking
     // flag -> root -> size -> row mask again (every other reader of the flag image masks the low bits; ip_front rewrites the image every scan)
     d.flag_img[base + v] = (uint8_t)((d.flag_img[base + v] & 0x0F) | (c << 4) | (fr ? 0x40 : 0));
@@ -895,12 +741,8 @@ __global__ void __launch_bounds__(IP_BLOCK) ip_compact(DevCtx d, int ring_pos) {
     if (threadIdx.x == 0) {
       s_off[0] = pk; s_off[1] = po; s_off[2] = pf;
       const int mykeep = rc[row * RC_W + RC_KEEP];
-      *ring_start_of(d, slot, row) = pk + 5;                // :161
-      *ring_end_of(d, slot, row) = pk + mykeep - 1 - 5;     // :190
-      if (row == 0) {
-        int* sc = scal_of(d, slot);
-        sc[SC_M] = tk; sc[SC_NOUT] = to; sc[SC_NFEAS] = tf;
-      }
+      ip_store_ring(ring_start_of(d, slot, row), ring_end_of(d, slot, row), pk, pk + mykeep);   // :161,:190
+      if (row == 0) ip_store_totals(scal_of(d, slot), tk, to, tf);
     }
   }
   __syncthreads();
@@ -913,7 +755,7 @@ __global__ void __launch_bounds__(IP_BLOCK) ip_compact(DevCtx d, int ring_pos) {
     const int v = row * d.H + col;
     uint8_t fl = 0;
     if (col < d.H) { fl = d.flag_img[base + v]; c = (fl >> 4) & 3; fr = (fl & 0x40) != 0; }   // (classified by ip_rowcount)
-    const unsigned long long bk = __ballot(c == 1), bo = __ballot(c == 2), bf = __ballot(fr);
+    const unsigned long long bk = __ballot(c == IP_KEEP), bo = __ballot(c == IP_OUTLIER), bf = __ballot(fr);
     const unsigned long long below = (1ull << lane) - 1ull;
     if (lane == 0) { s_wave[0][wave] = (int)__popcll(bk); s_wave[1][wave] = (int)__popcll(bo); s_wave[2][wave] = (int)__popcll(bf); }
     __syncthreads();
@@ -924,21 +766,12 @@ __global__ void __launch_bounds__(IP_BLOCK) ip_compact(DevCtx d, int ring_pos) {
       if (w < wave) { wk += a; wo += b; wf += e; }
       tk += a; to += b; tf += e;
     }
-    if (c == 1 || c == 2) {
-      const int o = ip_owner_index(d.owner[base + v]);
-      float4 p = pts[o];
-      p.w = (float)(row + d.ip_colfrac[col]);  // :101
-      if (c == 1) {
-        const int line = run_k + wk + (int)__popcll(bk & below);
-        d.seg_pts[base + line] = p;
-        d.seg_ground[base + line] = fl & 1;
-        d.seg_col[base + line] = col;
-        d.seg_range[base + line] = sqrtf(p.x * p.x + p.y * p.y + p.z * p.z);   // = the range image's value (:99)
-      } else {
-        d.outlier[base + run_o + wo + (int)__popcll(bo & below)] = p;
-      }
+    if (c == IP_KEEP || c == IP_OUTLIER) {
+      const float4 q = pts[ip_owner_index(d.owner[base + v])];
+      if (c == IP_KEEP) ip_store_kept(d.seg_pts + base, d.seg_ground + base, d.seg_col + base, d.seg_range + base, run_k + wk + (int)__popcll(bk & below), q, row, col, d.ip_colfrac[col], fl & 1);
+      else ip_store_outlier(d.outlier + base, run_o + wo + (int)__popcll(bo & below), q, row, d.ip_colfrac[col]);
     }
-    if (fr) d.cc_label[base + v] = run_f + wf + (int)__popcll(bf & below) + 1;  // label_cnt_ numbering (:303-306)
+    if (fr) d.cc_label[base + v] = ip_root_label(true, run_f + wf + (int)__popcll(bf & below));   // (the other roots keep ip_front's 0)
     run_k += tk; run_o += to; run_f += tf;
     __syncthreads();
   }
@@ -954,8 +787,7 @@ __global__ void __launch_bounds__(IP_BLOCK) ip_labels(DevCtx d) {
   int lab = -1;
   if (f & 2) {
     const int root = d.parent[base + v];
-    const int l = d.cc_label[base + root];
-    lab = l > 0 ? l : 999999;
+    lab = ip_cell_label(d.cc_label[base + root]);
   }
   d.label_img[base + v] = lab;
 }
@@ -992,7 +824,7 @@ void launch_ip(const DevCtx& d, int ring_pos, bool want_labels, hipStream_t st) 
     const int cc_flags = (fused ? 1 : 0) | ((!fused || keep_images) ? 2 : 0);
     ALEGO_LAUNCH(cc_lds16, dim3(d.n_launch), dim3(CC_LDS_THREADS), (size_t)4 * ((d.N + 1) / 2), st, d, ring_pos, cc_flags);
   } else if (lds_cc) {
-    ALEGO_LAUNCH(cc_lds, dim3(d.n_launch), dim3(CC_LDS_THREADS), (size_t)4 * d.N, st, d, ring_pos, 0);
+    ALEGO_LAUNCH(cc_lds, dim3(d.n_launch), dim3(CC_LDS_THREADS), (size_t)4 * d.N, st, d);
   } else if (d.opt_cc_tile && d.NS <= CC_TILE_CELLS / 16) {
     const int tw = std::max(1, CC_TILE_CELLS / d.NS);
     ALEGO_LAUNCH(cc_tile, dim3((d.H + tw - 1) / tw, d.n_launch), dim3(CC_TILE_T), 0, st, d);

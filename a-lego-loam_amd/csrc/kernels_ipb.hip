@@ -18,7 +18,7 @@
 //                label_cnt_ numbers of the feasible roots when a label image is wanted (:303-314).
 //
 // Results are bit-identical to the seven-kernel path (ALEGO_IP_BAND=0 keeps it): same arithmetic per cell (ip_common.h), same roots (minimum linear index),
-// same ordered compaction.  tests/test_gpu_parity.py::test_ip_bit_exact[(64,2048) / (32,2048) / (40,1800) x band / tile].
+// same output rules (ip_rules.h: here on 64-bit row masks), same ordered compaction.  tests/test_gpu_parity.py::test_ip_bit_exact[(64,2048) / (32,2048) / (40,1800) x band / tile].
 #include <cstdlib>
 #include "dev_common.h"
 #include "front_end.h"
@@ -96,9 +96,6 @@ DEV_INLINE float ipb_cell_range(const int* owner, const float4* pts, int H, int 
   const float4 q = ipb_cell_point(owner, pts, H, row, col);
   return sqrtf(q.x * q.x + q.y * q.y + q.z * q.z);   // :99, the expression of the row loop
 }
-DEV_INLINE bool ipb_feasible(const alego_params& P, int sz, u64 rows) {   // imageProjection.cpp:282-301
-  return sz >= P.seg_big_num || (sz >= P.seg_valid_point_num && (int)__popcll(rows) >= P.seg_valid_line_num);
-}
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // ipb_band: grid (bands, slots).  keep bit 0: also write the range and flag images (single-scan entry points / tests read them back)
@@ -174,7 +171,7 @@ __global__ void __launch_bounds__(IPB_TW) ipb_band(DevCtx d, int ring_pos, int k
           const float r = ok ? sqrtf(x * x + y * y + z * z) : -1.0f;   // :99
           rng[row] = r;
           if (ok) filled |= 1ull << row;
-          if (row >= 1 && row - 1 < P.ground_scan_id) {   // :111-131, pair (row - 1, row)
+          if (ip_ground_pair(row, P.ground_scan_id)) {   // :111-131, pair (row - 1, row)
             const IpScreenBits g = ip_ground_screen(k_glo, k_ghi, k_gmax, x - lx, y - ly, z - lz);
             const bool en = ok && lower_ok;
             ground |= (en && g.yes) ? 3ull << (row - 1) : 0ull;
@@ -217,7 +214,7 @@ __global__ void __launch_bounds__(IPB_TW) ipb_band(DevCtx d, int ring_pos, int k
     const float px = __shfl_up(p.x, 1, 64), py = __shfl_up(p.y, 1, 64), pz = __shfl_up(p.z, 1, 64);
     const int okl = __shfl_up(ok ? 1 : 0, 1, 64);
     const IpScreenBits gs = ip_ground_screen(d.ip_scr.g_lo, d.ip_scr.g_hi, d.ip_scr.g_max, p.x - px, p.y - py, p.z - pz);
-    const bool gen = lane >= 1 && lane - 1 < P.ground_scan_id && ok && okl;
+    const bool gen = ip_ground_pair(lane, P.ground_scan_id) && ok && okl;
     bool gp = gen && gs.yes;
     if (__ballot(gen && gs.und)) {   // (rare, as above: the lanes the screen leaves undecided take the fp64 test)
       if (gen && gs.und) gp = ip_is_ground(d, p.x - px, p.y - py, p.z - pz);
@@ -377,7 +374,7 @@ __global__ void __launch_bounds__(IPB_MT) ipb_merge(DevCtx d, int keep) {
   __syncthreads();
   IPB_TICK(13);
   // per column: keep / outlier masks (:164-188), feasible roots; per (row, chunk) counts by ballots
-  const u64 above = P.ground_scan_id >= 63 ? 0ull : ~ipb_low(P.ground_scan_id);   // rows > ground_scan_id
+  const u64 above = ip_rows_above<u64>(P.ground_scan_id);
   for (int ch = wave; ch < nch; ch += IPB_MT / 64) {
     const int col = ch * 64 + lane;
     u64 K = 0, O = 0, F = 0, Rf = 0;
@@ -396,7 +393,7 @@ __global__ void __launch_bounds__(IPB_MT) ipb_merge(DevCtx d, int keep) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           if (!on[q]) continue;
-          const bool f = ipb_feasible(P, z[q], w[q]);
+          const bool f = ip_feasible(P, z[q], (int)__popcll(w[q]));
           const int e = __ffsll((long long)(~y & ~(ipb_low(r[q]) >> 1))) - 1;
           if (f) K |= ipb_low(e) & ~(ipb_low(r[q]) >> 1);
           if (b[q] == v[q]) { Rf |= 1ull << r[q]; if (f) F |= 1ull << r[q]; }
@@ -406,8 +403,8 @@ __global__ void __launch_bounds__(IPB_MT) ipb_merge(DevCtx d, int keep) {
           }
         }
       }
-      if (col % 5 == 0) O = a & ~K & above;                              // :165-171
-      if (col % 5 == 0 || col <= 4 || col >= H - 5) K |= g;               // :173-176
+      O = ip_col_outliers(a, K, above, col);   // (K: still the cells of feasible segments alone)
+      K = ip_col_keep(g, K, col, H);
       MK[col] = K; MO[col] = O; MF[col] = F; MRf[col] = Rf;
     }
     int ck = 0, co = 0, cf = 0;
@@ -436,11 +433,8 @@ __global__ void __launch_bounds__(IPB_MT) ipb_merge(DevCtx d, int keep) {
   IPB_TICK(15);
   int* off = ipb_off_of<RC_KEEP>(d, slot, nch);
   for (int j = tid; j < IPO_PLANES * IPO_ROWS * nch; j += IPB_MT) { const unsigned tr = j / nch; off[j] = s_rowbase[tr / IPO_ROWS][tr % IPO_ROWS] + (int)s_cnt[j]; }
-  if (tid < NS) {
-    *ring_start_of(d, slot, tid) = s_rowbase[0][tid] + 5;                          // :161
-    *ring_end_of(d, slot, tid) = s_rowbase[0][tid] + s_rowtot[0][tid] - 1 - 5;     // :190
-  }
-  if (tid == 0) { int* sc = scal_of(d, slot); sc[SC_M] = s_tot[0]; sc[SC_NOUT] = s_tot[1]; sc[SC_NFEAS] = s_tot[2]; }
+  if (tid < NS) ip_store_ring(ring_start_of(d, slot, tid), ring_end_of(d, slot, tid), s_rowbase[0][tid], s_rowbase[0][tid] + s_rowtot[0][tid]);   // :161,:190
+  if (tid == 0) ip_store_totals(scal_of(d, slot), s_tot[0], s_tot[1], s_tot[2]);
   IPB_TICK(16);
   // the statistics entries go back to zero for the next scan (every entry ipb_band or the merge above touched belongs to a band root)
   for (int col = tid; col < H; col += IPB_MT) {
@@ -493,17 +487,8 @@ __global__ void __launch_bounds__(IPB_ET) ipb_emit(DevCtx d, int ring_pos, int k
       const bool k = (K >> row) & 1ull, o = (O >> row) & 1ull;
       const u64 bk = __ballot(k), bo = __ballot(o);
       if (k | o) {
-        float4 p = pb[u];
-        p.w = (float)(row + cf);   // :101
-        if (k) {
-          const int line = offk[row * nch] + (int)__popcll(bk & below);
-          d.seg_pts[base + line] = p;
-          d.seg_ground[base + line] = (uint8_t)((G >> row) & 1ull);
-          d.seg_col[base + line] = col;
-          d.seg_range[base + line] = sqrtf(p.x * p.x + p.y * p.y + p.z * p.z);   // = the range image's value (:99)
-        } else {
-          d.outlier[base + offo[row * nch] + (int)__popcll(bo & below)] = p;
-        }
+        if (k) ip_store_kept(d.seg_pts + base, d.seg_ground + base, d.seg_col + base, d.seg_range + base, offk[row * nch] + (int)__popcll(bk & below), pb[u], row, col, cf, (G >> row) & 1ull);
+        else ip_store_outlier(d.outlier + base, offo[row * nch] + (int)__popcll(bo & below), pb[u], row, cf);
       }
     }
   }
@@ -513,7 +498,7 @@ __global__ void __launch_bounds__(IPB_ET) ipb_emit(DevCtx d, int ring_pos, int k
     for (int row = 0; row < NS; ++row) {
       const bool f = (F >> row) & 1ull;
       const u64 bf = __ballot(f);
-      if ((Rf >> row) & 1ull) d.cc_label[base + row * H + col] = f ? offf[row * nch] + (int)__popcll(bf & below) + 1 : 0;
+      if ((Rf >> row) & 1ull) d.cc_label[base + row * H + col] = ip_root_label(f, offf[row * nch] + (int)__popcll(bf & below));
     }
   }
 }

@@ -14,6 +14,7 @@
 //                   entries (2 B / cell of LDS for the parents: owner 2 N + parents 2 N + masks 8 H = 130 KB)      (:210-316)
 //   phase D  a6     ordered compaction: per row and wavefront ballots -> one 256-entry scan -> every kept cell's output line;
 //                   second (and last) gather of the kept cells' points, cloud_info arrays written once              (:158-191)
+// What is feasible, kept, an outlier, a ring index, a label: ip_rules.h (here on 16-bit row masks); the records and the scan: ip_common.h.
 //
 // Against ip_project + ip_front + cc_lds16: no owner / flag images in HBM, no tag reset protocol between workgroups, one launch
 // instead of three, and the per-cell passes of cc_lds16 (29 cells x 10 passes per thread) become bit operations on 16-bit
@@ -41,7 +42,7 @@ struct IpfShared {
   unsigned first_act[IPF2_NW];
   int red[3][IPF2_NW];
   int cnt[3][IPF2_ROWS * IPF2_NW];     // per (row, wavefront): kept cells, outliers, feasible roots -> exclusive prefix in row-major order
-  int wtot[3][4];
+  int wtot[3][IPF2_ROWS * IPF2_NW / 64];
   int tot[3];
   int nlist;                            // phase A: points deferred to the exact projection
 };
@@ -189,7 +190,7 @@ __global__ void __launch_bounds__(IPF2_T) ip_fused(DevCtx d, int ring_pos, int k
           const float x = pa[u].x, y = pa[u].y, z = pa[u].z;
           rng0[row] = ok ? sqrtf(x * x + y * y + z * z) : -1.0f;   // :99
           if (ok) filled0 |= 1u << row;
-          if (row >= 1 && row - 1 < P.ground_scan_id && ok && lok0 && ip_is_ground(d, x - lx0, y - ly0, z - lz0)) ground0 |= 3u << (row - 1);   // :111-131
+          if (ip_ground_pair(row, P.ground_scan_id) && ok && lok0 && ip_is_ground(d, x - lx0, y - ly0, z - lz0)) ground0 |= 3u << (row - 1);   // :111-131
           lx0 = x; ly0 = y; lz0 = z; lok0 = ok;
         }
         {
@@ -197,7 +198,7 @@ __global__ void __launch_bounds__(IPF2_T) ip_fused(DevCtx d, int ring_pos, int k
           const float x = pb[u].x, y = pb[u].y, z = pb[u].z;
           rng1[row] = ok ? sqrtf(x * x + y * y + z * z) : -1.0f;
           if (ok) filled1 |= 1u << row;
-          if (row >= 1 && row - 1 < P.ground_scan_id && ok && lok1 && ip_is_ground(d, x - lx1, y - ly1, z - lz1)) ground1 |= 3u << (row - 1);
+          if (ip_ground_pair(row, P.ground_scan_id) && ok && lok1 && ip_is_ground(d, x - lx1, y - ly1, z - lz1)) ground1 |= 3u << (row - 1);
           lx1 = x; ly1 = y; lz1 = z; lok1 = ok;
         }
       }
@@ -323,8 +324,8 @@ __global__ void __launch_bounds__(IPF2_T) ip_fused(DevCtx d, int ring_pos, int k
   __syncthreads();
   unsigned big0 = 0, big1 = 0, mid0 = 0, mid1 = 0;   // per run (bit at its start row): size >= 30 / 5 <= size < 30
   if (colv) {
-    for (unsigned m = rs0; m; m &= m - 1) { const int row = __ffs((int)m) - 1, sz = (int)par[root_of(root0, row, c0)]; if (sz >= P.seg_big_num) big0 |= 1u << row; else if (sz >= P.seg_valid_point_num) mid0 |= 1u << row; }
-    for (unsigned m = rs1; m; m &= m - 1) { const int row = __ffs((int)m) - 1, sz = (int)par[root_of(root1, row, c1)]; if (sz >= P.seg_big_num) big1 |= 1u << row; else if (sz >= P.seg_valid_point_num) mid1 |= 1u << row; }
+    for (unsigned m = rs0; m; m &= m - 1) { const int row = __ffs((int)m) - 1, cls = ip_size_class(P, (int)par[root_of(root0, row, c0)]); if (cls == IP_SEG_BIG) big0 |= 1u << row; else if (cls == IP_SEG_MID) mid0 |= 1u << row; }
+    for (unsigned m = rs1; m; m &= m - 1) { const int row = __ffs((int)m) - 1, cls = ip_size_class(P, (int)par[root_of(root1, row, c1)]); if (cls == IP_SEG_BIG) big1 |= 1u << row; else if (cls == IP_SEG_MID) mid1 |= 1u << row; }
   }
   __syncthreads();
   zero_roots();
@@ -337,21 +338,19 @@ __global__ void __launch_bounds__(IPF2_T) ip_fused(DevCtx d, int ring_pos, int k
   if (colv) {
     for (unsigned m = big0 | mid0; m; m &= m - 1) {
       const int row = __ffs((int)m) - 1, e = ipf_run_end(down0, row);
-      if (((big0 >> row) & 1u) || __popc((unsigned)par[root_of(root0, row, c0)]) >= P.seg_valid_line_num) feas0 |= ((2u << e) - 1u) & ~((1u << row) - 1u);
+      if (ip_class_feasible(P, ((big0 >> row) & 1u) ? IP_SEG_BIG : IP_SEG_MID, __popc((unsigned)par[root_of(root0, row, c0)]))) feas0 |= ((2u << e) - 1u) & ~((1u << row) - 1u);
     }
     for (unsigned m = big1 | mid1; m; m &= m - 1) {
       const int row = __ffs((int)m) - 1, e = ipf_run_end(down1, row);
-      if (((big1 >> row) & 1u) || __popc((unsigned)par[root_of(root1, row, c1)]) >= P.seg_valid_line_num) feas1 |= ((2u << e) - 1u) & ~((1u << row) - 1u);
+      if (ip_class_feasible(P, ((big1 >> row) & 1u) ? IP_SEG_BIG : IP_SEG_MID, __popc((unsigned)par[root_of(root1, row, c1)]))) feas1 |= ((2u << e) - 1u) & ~((1u << row) - 1u);
     }
   }
 
   IPF_TICK(8);
   // ---------------- phase D: ordered compaction (:158-191) ----------------
-  const unsigned all16 = 0xFFFFu;
-  const unsigned rowgt = P.ground_scan_id >= 15 ? 0u : (P.ground_scan_id < 0 ? all16 : (all16 & ~((2u << P.ground_scan_id) - 1u)));   // rows > ground_scan_id
-  const bool gk0 = c0 % 5 == 0 || c0 <= 4 || c0 >= H - 5, gk1 = c1 % 5 == 0 || c1 <= 4 || c1 >= H - 5;
-  const unsigned keep0 = colv ? ((gk0 ? ground0 : 0u) | feas0) : 0u, keep1 = colv ? ((gk1 ? ground1 : 0u) | feas1) : 0u;
-  const unsigned outl0 = (colv && c0 % 5 == 0) ? (act0 & ~feas0 & rowgt) : 0u, outl1 = (colv && c1 % 5 == 0) ? (act1 & ~feas1 & rowgt) : 0u;
+  const unsigned rowgt = ip_rows_above<unsigned>(P.ground_scan_id);
+  const unsigned keep0 = colv ? ip_col_keep(ground0, feas0, c0, H) : 0u, keep1 = colv ? ip_col_keep(ground1, feas1, c1, H) : 0u;
+  const unsigned outl0 = colv ? ip_col_outliers(act0, feas0, rowgt, c0) : 0u, outl1 = colv ? ip_col_outliers(act1, feas1, rowgt, c1) : 0u;
   const unsigned fr0 = colv ? (root0 & feas0) : 0u, fr1 = colv ? (root1 & feas1) : 0u;   // roots of feasible components: label_cnt_ numbering (:303-306)
 #pragma unroll
   for (int row = 0; row < IPF2_ROWS; ++row) {
@@ -365,38 +364,15 @@ __global__ void __launch_bounds__(IPF2_T) ip_fused(DevCtx d, int ring_pos, int k
     }
   }
   __syncthreads();
-  {   // exclusive scan of the three 256-entry tables by the first four wavefronts
-    int v3[3] = {0, 0, 0}, in3[3] = {0, 0, 0};
-    if (tid < IPF2_ROWS * IPF2_NW) {
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        v3[a] = S.cnt[a][tid];
-        in3[a] = wave_incl_scan(v3[a]);
-        if (lane == 63) S.wtot[a][wave] = in3[a];
-      }
-    }
-    __syncthreads();
-    if (tid < IPF2_ROWS * IPF2_NW) {
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        int woff = 0;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) if (w < wave) woff += S.wtot[a][w];
-        S.cnt[a][tid] = woff + in3[a] - v3[a];
-        if (tid == IPF2_ROWS * IPF2_NW - 1) S.tot[a] = woff + in3[a];
-      }
-    }
-  }
+  constexpr int NSW = IPF2_ROWS * IPF2_NW / 64;   // the first four wavefronts take the three 256-entry tables
+  ip_scan3<NSW>(S.cnt[0], S.cnt[1], S.cnt[2], IPF2_ROWS * IPF2_NW, S.wtot);
+  if (tid < 3) S.tot[tid] = ip_scan_total<NSW>(S.wtot[tid]);
   __syncthreads();
   if (tid < NS) {   // startRingIndex / endRingIndex (:161,:190)
     const int row = tid;
-    *ring_start_of(d, slot, row) = S.cnt[0][row * IPF2_NW] + 5;
-    *ring_end_of(d, slot, row) = (row + 1 < IPF2_ROWS ? S.cnt[0][(row + 1) * IPF2_NW] : S.tot[0]) - 1 - 5;
+    ip_store_ring(ring_start_of(d, slot, row), ring_end_of(d, slot, row), S.cnt[0][row * IPF2_NW], row + 1 < IPF2_ROWS ? S.cnt[0][(row + 1) * IPF2_NW] : S.tot[0]);
   }
-  if (tid == 0) {
-    int* sc = scal_of(d, slot);
-    sc[SC_M] = S.tot[0]; sc[SC_NOUT] = S.tot[1]; sc[SC_NFEAS] = S.tot[2];
-  }
+  if (tid == 0) ip_store_totals(scal_of(d, slot), S.tot[0], S.tot[1], S.tot[2]);
   IPF_TICK(9);
   const unsigned long long below = (1ull << lane) - 1ull;
   const unsigned* own16w = reinterpret_cast<const unsigned*>(own16);
@@ -419,31 +395,10 @@ __global__ void __launch_bounds__(IPF2_T) ip_fused(DevCtx d, int ring_pos, int k
       const unsigned long long bk0 = __ballot(k0), bk1 = __ballot(k1), bo0 = __ballot(o0), bo1 = __ballot(o1);
       const int lk = S.cnt[0][row * IPF2_NW + wave] + (int)(__popcll(bk0 & below) + __popcll(bk1 & below));
       const int lo = S.cnt[1][row * IPF2_NW + wave] + (int)(__popcll(bo0 & below) + __popcll(bo1 & below));
-      if (k0 | o0) {
-        const float4 q = qa[u];
-        const float4 p = make_float4(q.x, q.y, q.z, (float)(row + cf0));   // :101
-        if (k0) {
-          d.seg_pts[base + lk] = p;
-          d.seg_ground[base + lk] = (uint8_t)((ground0 >> row) & 1u);
-          d.seg_col[base + lk] = c0;
-          d.seg_range[base + lk] = sqrtf(q.x * q.x + q.y * q.y + q.z * q.z);   // = the range image's value (:99,:184)
-        } else {
-          d.outlier[base + lo] = p;
-        }
-      }
-      if (k1 | o1) {
-        const float4 q = qb[u];
-        const float4 p = make_float4(q.x, q.y, q.z, (float)(row + cf1));
-        const int l1 = lk + (k0 ? 1 : 0), lo1 = lo + (o0 ? 1 : 0);
-        if (k1) {
-          d.seg_pts[base + l1] = p;
-          d.seg_ground[base + l1] = (uint8_t)((ground1 >> row) & 1u);
-          d.seg_col[base + l1] = c1;
-          d.seg_range[base + l1] = sqrtf(q.x * q.x + q.y * q.y + q.z * q.z);
-        } else {
-          d.outlier[base + lo1] = p;
-        }
-      }
+      if (k0) ip_store_kept(d.seg_pts + base, d.seg_ground + base, d.seg_col + base, d.seg_range + base, lk, qa[u], row, c0, cf0, (ground0 >> row) & 1u);
+      else if (o0) ip_store_outlier(d.outlier + base, lo, qa[u], row, cf0);
+      if (k1) ip_store_kept(d.seg_pts + base, d.seg_ground + base, d.seg_col + base, d.seg_range + base, lk + (k0 ? 1 : 0), qb[u], row, c1, cf1, (ground1 >> row) & 1u);
+      else if (o1) ip_store_outlier(d.outlier + base, lo + (o0 ? 1 : 0), qb[u], row, cf1);
     }
   }
   IPF_TICK(10);
@@ -457,8 +412,8 @@ __global__ void __launch_bounds__(IPF2_T) ip_fused(DevCtx d, int ring_pos, int k
         d.parent[base + v0] = ((act0 >> row) & 1u) ? root_of(root0, s0, c0) : -1;
         d.parent[base + v1] = ((act1 >> row) & 1u) ? root_of(root1, s1, c1) : -1;
         const int nf = S.cnt[2][row * IPF2_NW + wave] + (int)(__popcll(bf0 & below) + __popcll(bf1 & below));
-        if ((root0 >> row) & 1u) d.cc_label[base + v0] = ((fr0 >> row) & 1u) ? nf + 1 : 0;
-        if ((root1 >> row) & 1u) d.cc_label[base + v1] = ((fr1 >> row) & 1u) ? nf + ((fr0 >> row) & 1u) + 1 : 0;
+        if ((root0 >> row) & 1u) d.cc_label[base + v0] = ip_root_label((fr0 >> row) & 1u, nf);
+        if ((root1 >> row) & 1u) d.cc_label[base + v1] = ip_root_label((fr1 >> row) & 1u, nf + (int)((fr0 >> row) & 1u));
       }
     }
   }
@@ -741,7 +696,7 @@ __global__ void __launch_bounds__(T, IPH_MINW) ip_fused_t(DevCtx d, int ring_pos
             const float x = pa[u].x, y = pa[u].y, z = pa[u].z;
             rng0[row] = ok ? sqrtf(x * x + y * y + z * z) : -1.0f;   // :99
             if (ok) filled0 |= 1u << row;
-            if (row >= 1 && row - 1 < P.ground_scan_id) {   // :111-131
+            if (ip_ground_pair(row, P.ground_scan_id)) {   // :111-131
               const IpScreenBits g = ip_ground_screen(k_glo, k_ghi, k_gmax, x - lx0, y - ly0, z - lz0);
               const bool en = ok && lok0;
               ground0 |= (en && g.yes) ? 3u << (row - 1) : 0u;
@@ -754,7 +709,7 @@ __global__ void __launch_bounds__(T, IPH_MINW) ip_fused_t(DevCtx d, int ring_pos
             const float x = pb[u].x, y = pb[u].y, z = pb[u].z;
             rng1[row] = ok ? sqrtf(x * x + y * y + z * z) : -1.0f;
             if (ok) filled1 |= 1u << row;
-            if (row >= 1 && row - 1 < P.ground_scan_id) {
+            if (ip_ground_pair(row, P.ground_scan_id)) {
               const IpScreenBits g = ip_ground_screen(k_glo, k_ghi, k_gmax, x - lx1, y - ly1, z - lz1);
               const bool en = ok && lok1;
               ground1 |= (en && g.yes) ? 3u << (row - 1) : 0u;
@@ -799,7 +754,7 @@ __global__ void __launch_bounds__(T, IPH_MINW) ip_fused_t(DevCtx d, int ring_pos
         const float lx = __shfl_up(q.x, 1, 64), ly = __shfl_up(q.y, 1, 64), lz = __shfl_up(q.z, 1, 64);
         const bool lok = __shfl_up(ok ? 1 : 0, 1, 64) != 0;
         const IpScreenBits gs = ip_ground_screen(d.ip_scr.g_lo, d.ip_scr.g_hi, d.ip_scr.g_max, q.x - lx, q.y - ly, q.z - lz);
-        const bool gen = row >= 1 && row - 1 < P.ground_scan_id && ok && lok;
+        const bool gen = ip_ground_pair(row, P.ground_scan_id) && ok && lok;
         bool g = gen && gs.yes;
         if (__ballot(gen && gs.und)) {   // (rare, as above: the lanes the screen leaves undecided take the fp64 test)
           if (gen && gs.und) g = ip_is_ground(d, q.x - lx, q.y - ly, q.z - lz);
@@ -989,7 +944,7 @@ __global__ void __launch_bounds__(T, IPH_MINW) ip_fused_t(DevCtx d, int ring_pos
     unsigned big = 0, mid = 0;
     if (c < H) {
       const IphCol m = iph_load(fcol, c);
-      for (unsigned rm = m.b & ~(m.y << 1); rm; rm &= rm - 1) { const int row = __ffs((int)rm) - 1, sz = (int)par[root_of(m.x, row, c)]; if (sz >= P.seg_big_num) big |= 1u << row; else if (sz >= P.seg_valid_point_num) mid |= 1u << row; }
+      for (unsigned rm = m.b & ~(m.y << 1); rm; rm &= rm - 1) { const int row = __ffs((int)rm) - 1, cls = ip_size_class(P, (int)par[root_of(m.x, row, c)]); if (cls == IP_SEG_BIG) big |= 1u << row; else if (cls == IP_SEG_MID) mid |= 1u << row; }
     }
     bm[q] = big | (mid << 16);
   }
@@ -1013,7 +968,7 @@ __global__ void __launch_bounds__(T, IPH_MINW) ip_fused_t(DevCtx d, int ring_pos
       unsigned feas = 0;
       for (unsigned rm = big | mid; rm; rm &= rm - 1) {
         const int row = __ffs((int)rm) - 1, e = ipf_run_end(m.y, row);
-        if (((big >> row) & 1u) || __popc((unsigned)par[root_of(m.x, row, c)]) >= P.seg_valid_line_num) feas |= ((2u << e) - 1u) & ~((1u << row) - 1u);
+        if (ip_class_feasible(P, ((big >> row) & 1u) ? IP_SEG_BIG : IP_SEG_MID, __popc((unsigned)par[root_of(m.x, row, c)]))) feas |= ((2u << e) - 1u) & ~((1u << row) - 1u);
       }
       if (keep & 1) {   // root image for ip_labels / the tests (:303-314), while the down-edges are still there
         const unsigned rs = m.b & ~(m.y << 1);
@@ -1032,13 +987,11 @@ __global__ void __launch_bounds__(T, IPH_MINW) ip_fused_t(DevCtx d, int ring_pos
   IPF_TICK(8);
   // ---------------- phase D: ordered compaction (:158-191) ----------------
   { IPH_PHASE_CTX;   // (d and P of this phase: the kernel argument read afresh — see IPH_PHASE_CTX)
-  const unsigned all16 = 0xFFFFu;
-  const unsigned rowgt = P.ground_scan_id >= 15 ? 0u : (P.ground_scan_id < 0 ? all16 : (all16 & ~((2u << P.ground_scan_id) - 1u)));   // rows > ground_scan_id
-  // keep | outliers << 16 of column c; feasible roots (label_cnt_ numbering, :303-306)
+  const unsigned rowgt = ip_rows_above<unsigned>(P.ground_scan_id);
+  // kept cells and outliers of column c (ip_rules.h); feasible roots (label_cnt_ numbering, :303-306)
   auto col_sets = [&](int c, const IphCol& m, unsigned& keepm, unsigned& outlm, unsigned& frm) {
-    const bool gk = c % 5 == 0 || c <= 4 || c >= H - 5;
-    keepm = (gk ? m.a : 0u) | m.y;
-    outlm = c % 5 == 0 ? (m.b & ~m.y & rowgt) : 0u;
+    keepm = ip_col_keep(m.a, m.y, c, H);
+    outlm = ip_col_outliers(m.b, m.y, rowgt, c);
     frm = m.x & m.y;
   };
 #pragma unroll 1
@@ -1061,39 +1014,15 @@ __global__ void __launch_bounds__(T, IPH_MINW) ip_fused_t(DevCtx d, int ring_pos
   }
   __syncthreads();
   constexpr int NCNT = IPF2_ROWS * NP * NW;   // 256 (ip_fused_h) / 512 (ip_fused_w) <= T
-  {   // exclusive scan of the three tables by the first NCNT threads
-    int v3[3] = {0, 0, 0}, in3[3] = {0, 0, 0};
-    if (tid < NCNT) {
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        v3[a] = S.u.cnt[a][tid];
-        in3[a] = wave_incl_scan(v3[a]);
-        if (lane == 63) S.wtot[a][wave] = in3[a];
-      }
-    }
-    __syncthreads();
-    if (tid < NCNT) {
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        int woff = 0;
-#pragma unroll
-        for (int w = 0; w < NCNT / 64; ++w) if (w < wave) woff += S.wtot[a][w];
-        S.u.cnt[a][tid] = (unsigned short)(woff + in3[a] - v3[a]);
-        if (tid == NCNT - 1) S.tot[a] = woff + in3[a];
-      }
-    }
-  }
+  ip_scan3<NCNT / 64>(S.u.cnt[0], S.u.cnt[1], S.u.cnt[2], NCNT, S.wtot);   // (the first NCNT threads take the three tables)
+  if (tid < 3) S.tot[tid] = ip_scan_total<NCNT / 64>(S.wtot[tid]);
   __syncthreads();
   int* const o_rs = IPH_LATE(ring_start) + ring_at(NS, slot, 0); int* const o_re = IPH_LATE(ring_end) + ring_at(NS, slot, 0); int* const o_sc = IPH_LATE(scal) + scal_at(slot);   // (fetched in uniform code)
   if (tid < NS) {   // startRingIndex / endRingIndex (:161,:190)
     const int row = tid;
-    o_rs[row] = (int)S.u.cnt[0][row * NP * NW] + 5;
-    o_re[row] = (row + 1 < IPF2_ROWS ? (int)S.u.cnt[0][(row + 1) * NP * NW] : S.tot[0]) - 1 - 5;
+    ip_store_ring(o_rs + row, o_re + row, (int)S.u.cnt[0][row * NP * NW], row + 1 < IPF2_ROWS ? (int)S.u.cnt[0][(row + 1) * NP * NW] : S.tot[0]);
   }
-  if (tid == 0) {
-    int* sc = o_sc;
-    sc[SC_M] = S.tot[0]; sc[SC_NOUT] = S.tot[1]; sc[SC_NFEAS] = S.tot[2];
-  }
+  if (tid == 0) ip_store_totals(o_sc, S.tot[0], S.tot[1], S.tot[2]);
   IPF_TICK(9);
   const unsigned long long below = (1ull << lane) - 1ull;
   float4* const o_pts = IPH_LATE(seg_pts) + base; uint8_t* const o_gnd = IPH_LATE(seg_ground) + base; int* const o_col = IPH_LATE(seg_col) + base;
@@ -1154,31 +1083,10 @@ __global__ void __launch_bounds__(T, IPH_MINW) ip_fused_t(DevCtx d, int ring_pos
         const int e = (row * NP + p) * NW + wave;
         const int lk = (int)S.u.cnt[0][e] + (int)(__popcll(bk0 & below) + __popcll(bk1 & below));
         const int lo = (int)S.u.cnt[1][e] + (int)(__popcll(bo0 & below) + __popcll(bo1 & below));
-        if (k0 | o0) {
-          const float4 q = qa[u];
-          const float4 pp = make_float4(q.x, q.y, q.z, (float)(row + cf0));   // :101
-          if (k0) {
-            o_pts[lk] = pp;
-            o_gnd[lk] = (uint8_t)((ground0 >> row) & 1u);
-            o_col[lk] = c0;
-            o_rng[lk] = sqrtf(q.x * q.x + q.y * q.y + q.z * q.z);   // = the range image's value (:99,:184)
-          } else {
-            o_out[lo] = pp;
-          }
-        }
-        if (k1 | o1) {
-          const float4 q = qb[u];
-          const float4 pp = make_float4(q.x, q.y, q.z, (float)(row + cf1));
-          const int l1 = lk + (k0 ? 1 : 0), lo1 = lo + (o0 ? 1 : 0);
-          if (k1) {
-            o_pts[l1] = pp;
-            o_gnd[l1] = (uint8_t)((ground1 >> row) & 1u);
-            o_col[l1] = c1;
-            o_rng[l1] = sqrtf(q.x * q.x + q.y * q.y + q.z * q.z);
-          } else {
-            o_out[lo1] = pp;
-          }
-        }
+        if (k0) ip_store_kept(o_pts, o_gnd, o_col, o_rng, lk, qa[u], row, c0, cf0, (ground0 >> row) & 1u);
+        else if (o0) ip_store_outlier(o_out, lo, qa[u], row, cf0);
+        if (k1) ip_store_kept(o_pts, o_gnd, o_col, o_rng, lk + (k0 ? 1 : 0), qb[u], row, c1, cf1, (ground1 >> row) & 1u);
+        else if (o1) ip_store_outlier(o_out, lo + (o0 ? 1 : 0), qb[u], row, cf1);
       }
     }
     if (keep & 1) {   // label_cnt_ numbers of the feasible roots for ip_labels (:303-314)
@@ -1187,8 +1095,8 @@ __global__ void __launch_bounds__(T, IPH_MINW) ip_fused_t(DevCtx d, int ring_pos
         const unsigned long long bf0 = __ballot((fr0 >> row) & 1u), bf1 = __ballot((fr1 >> row) & 1u);
         if (colv && row < NS) {
           const int nf = (int)S.u.cnt[2][(row * NP + p) * NW + wave] + (int)(__popcll(bf0 & below) + __popcll(bf1 & below));
-          if ((root0 >> row) & 1u) o_lab[row * H + c0] = ((fr0 >> row) & 1u) ? nf + 1 : 0;
-          if ((root1 >> row) & 1u) o_lab[row * H + c1] = ((fr1 >> row) & 1u) ? nf + ((fr0 >> row) & 1u) + 1 : 0;
+          if ((root0 >> row) & 1u) o_lab[row * H + c0] = ip_root_label((fr0 >> row) & 1u, nf);
+          if ((root1 >> row) & 1u) o_lab[row * H + c1] = ip_root_label((fr1 >> row) & 1u, nf + (int)((fr0 >> row) & 1u));
         }
       }
     }

@@ -19,7 +19,7 @@ import pytest
 
 from alego_amd import binding, synth
 from oracle import oracle_py as O
-from util import assert_bit_equal
+from util import assert_bit_equal, assert_ip_outputs_equal_oracle, assert_same_outputs as _same, ip_outputs, ip_run as _run
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
@@ -215,21 +215,6 @@ def _params(geom):
     return p
 
 
-def _run(p, pts):
-    h = binding.Handle(p)
-    seg = h.ip_process(pts, want_labels=True)
-    out = {k: np.array(seg[k]) for k in ("seg", "ground", "col", "range", "ring_start", "ring_end", "outlier", "label_image")}
-    out["range_img"] = h.debug_get("range_img").copy()
-    out["flag_img"] = h.debug_get("flag_img") & 15   # ground, active, right-edge, down-edge (the multi-kernel paths keep working bits of their own above them)
-    h.close()
-    return out
-
-
-def _same(a, b, tag):
-    for k in a:
-        assert_bit_equal(a[k], b[k], f"{tag}: {k}")
-
-
 GEOMS = [((5, 64), "ALEGO_IP_HALF"), ((16, 64), "ALEGO_IP_HALF"), ((16, 130), "ALEGO_IP_HALF"),   # ip_fused_h: a wavefront boundary at columns 127 | 128, the wrap column
          ((16, 1800), "ALEGO_IP_FUSED"),                                                            # ip_fused_h's two passes: the pass boundary 1023 | 1024 and the sixteen-lane column
          ((17, 70), "ALEGO_IP_BAND"), ((24, 320), "ALEGO_IP_BAND")]                                  # ipb_band: one partial band; a band boundary 255 | 256, the halo column
@@ -260,13 +245,7 @@ def test_near_threshold_scans_bit_for_bit(geom, untouched, monkeypatch):
         monkeypatch.setenv(untouched, "0")
         _same(_run(p, pts), dflt, f"{geom} seed {seed} {untouched}=0 vs default")
         monkeypatch.delenv(untouched)
-        tag = f"{geom} seed {seed} default vs oracle"
-        assert_bit_equal(dflt["range_img"], o.get("range_img"), f"{tag}: range image")
-        assert_bit_equal(dflt["flag_img"] & 1, o.get("ground_img"), f"{tag}: ground image")
-        assert_bit_equal(dflt["label_image"], o.get("label_img"), f"{tag}: label image")
-        for k, n in (("seg", "seg_cloud"), ("ground", "seg_ground"), ("col", "seg_col"), ("range", "seg_range"), ("ring_start", "ring_start"),
-                     ("ring_end", "ring_end"), ("outlier", "outlier")):
-            assert_bit_equal(dflt[k], o.get(n), f"{tag}: {n}")
+        assert_ip_outputs_equal_oracle(dflt, o, f"{geom} seed {seed} default vs oracle")
 
 
 @pytest.mark.parametrize("geom,untouched", [((16, 130), "ALEGO_IP_HALF"), ((24, 320), "ALEGO_IP_BAND")])
@@ -303,11 +282,7 @@ def test_option_switched_on_a_live_handle(geom, monkeypatch):
     o.ip(pts)
 
     def outputs(h):
-        seg = h.ip_process(pts, want_labels=True)
-        out = {k: np.array(seg[k]) for k in ("seg", "ground", "col", "range", "ring_start", "ring_end", "outlier", "label_image")}
-        out["range_img"] = h.debug_get("range_img").copy()
-        out["flag_img"] = h.debug_get("flag_img") & 15
-        return out
+        return ip_outputs(h, pts)
 
     monkeypatch.delenv("ALEGO_IP_SCREEN", raising=False)
     h = binding.Handle(p)

@@ -21,6 +21,43 @@ def assert_bit_equal(got, want, what):
     assert bad.size == 0, f"{what}: {bad.size} of {got.size} elements differ, first at {bad[:5]}: got {got.reshape(-1)[bad[:5]]} want {want.reshape(-1)[bad[:5]]}"
 
 
+IP_OUTPUTS = ("seg", "ground", "col", "range", "ring_start", "ring_end", "outlier", "label_image")
+IP_ORACLE_NAMES = (("seg", "seg_cloud"), ("ground", "seg_ground"), ("col", "seg_col"), ("range", "seg_range"), ("ring_start", "ring_start"),
+                   ("ring_end", "ring_end"), ("outlier", "outlier"))
+
+
+def ip_outputs(h, pts):
+    """what ImageProjection hands on for one scan on a live handle: cloud_info, the outliers, the label image, and the range and flag images"""
+    seg = h.ip_process(pts, want_labels=True)
+    out = {k: np.array(seg[k]) for k in IP_OUTPUTS}
+    out["range_img"] = h.debug_get("range_img").copy()
+    out["flag_img"] = h.debug_get("flag_img") & 15   # ground, active, right-edge, down-edge (the multi-kernel paths keep working bits of their own above them)
+    return out
+
+
+def ip_run(p, pts):
+    """ip_outputs of one scan on a handle of its own (created under whatever ALEGO_* switches the environment holds)"""
+    from alego_amd import binding
+    h = binding.Handle(p)
+    out = ip_outputs(h, pts)
+    h.close()
+    return out
+
+
+def assert_same_outputs(a, b, tag):
+    for k in a:
+        assert_bit_equal(a[k], b[k], f"{tag}: {k}")
+
+
+def assert_ip_outputs_equal_oracle(out, o, tag):
+    """ip_outputs of the scan the oracle `o` processed last, against its images and clouds"""
+    assert_bit_equal(out["range_img"], o.get("range_img"), f"{tag}: range image")
+    assert_bit_equal(out["flag_img"] & 1, o.get("ground_img"), f"{tag}: ground image")
+    assert_bit_equal(out["label_image"], o.get("label_img"), f"{tag}: label image")
+    for k, n in IP_ORACLE_NAMES:
+        assert_bit_equal(out[k], o.get(n), f"{tag}: {n}")
+
+
 def quat_angle(q1, q2):
     """Rotation angle (rad) between two unit quaternions (w,x,y,z)."""
     d = abs(float(np.dot(q1, q2)))
