@@ -41,6 +41,7 @@ EXPORTS = [
     "alego_map_align", "alego_map_align_queries", "alego_map_align_consensus", "alego_map_align_poses",
     "alego_map_move", "alego_map_merge", "alego_map_align_edge", "alego_map_merge_edges",
     "alego_map_thin", "alego_map_thin_select", "alego_map_thin_edges", "alego_debug_thin_select",
+    "alego_regcov_enable", "alego_regcov_get", "alego_regcov_host", "alego_regcov_normal_host", "alego_debug_regcov",
 ]
 
 REPLAY_PINGPONG = 0x100
@@ -193,6 +194,55 @@ class GraphCovResult(C.Structure):
 
 class GraphCheck(C.Structure):
     _fields_ = [("status", C.c_int32), ("pad", C.c_int32), ("d2", C.c_double), ("error", C.c_double * 6), ("cov", C.c_double * 36)]
+
+
+class RegCovOpts(C.Structure):
+    _fields_ = [("sigma0", C.c_double), ("scale", C.c_double), ("eig_min", C.c_double), ("lambda_rel_floor", C.c_double),
+                ("var_min", C.c_double * 6), ("var_max", C.c_double * 6), ("graph", C.c_int32), ("pad", C.c_int32)]
+
+
+class RegCov(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_edge", C.c_int32), ("n_plane", C.c_int32), ("n_degenerate", C.c_int32), ("frame", C.c_int32), ("pad", C.c_int32),
+                ("cost", C.c_double), ("sigma2", C.c_double), ("info", C.c_double * 36), ("eigval", C.c_double * 6), ("eigvec", C.c_double * 36),
+                ("cov", C.c_double * 36), ("variance", C.c_double * 6)]
+
+
+def regcov_opts(sigma0=0.0, scale=0.0, eig_min=0.0, lambda_rel_floor=0.0, var_min=None, var_max=None, graph=0):
+    """alego_regcov_opts; a field left at 0 takes the library's default"""
+    o = RegCovOpts()
+    o.sigma0, o.scale, o.eig_min, o.lambda_rel_floor, o.graph = float(sigma0), float(scale), float(eig_min), float(lambda_rel_floor), int(graph)
+    if var_min is not None:
+        o.var_min[:] = [float(v) for v in var_min]
+    if var_max is not None:
+        o.var_max[:] = [float(v) for v in var_max]
+    return o
+
+
+def _regcov_out(r):
+    return dict(status=int(r.status), n_edge=int(r.n_edge), n_plane=int(r.n_plane), n_degenerate=int(r.n_degenerate), frame=int(r.frame),
+                cost=float(r.cost), sigma2=float(r.sigma2), info=np.array(r.info[:], np.float64).reshape(6, 6), eigval=np.array(r.eigval[:], np.float64),
+                eigvec=np.array(r.eigvec[:], np.float64).reshape(6, 6), cov=np.array(r.cov[:], np.float64).reshape(6, 6), variance=np.array(r.variance[:], np.float64))
+
+
+def regcov_host(acc28, params6, n_edge, n_plane, opts=None):
+    """alego_regcov_host (host only): the record of 28 normal-equation scalars at params6 as a dict"""
+    a, p = np.ascontiguousarray(acc28, np.float64).reshape(28), np.ascontiguousarray(params6, np.float64).reshape(6)
+    out = RegCov()
+    rc = lib().alego_regcov_host(a.ctypes.data, p.ctypes.data, int(n_edge), int(n_plane), None if opts is None else C.byref(opts), C.byref(out))
+    if rc != 0:
+        raise AlegoError(f"alego_regcov_host failed ({rc})")
+    return _regcov_out(out)
+
+
+def regcov_normal_host(params6, edge_rows9, plane_rows7, huber):
+    """alego_regcov_normal_host (host only): the 28 scalars of rows (a, b, p) (n, 9) and (n, d, p) (m, 7) at params6"""
+    p = np.ascontiguousarray(params6, np.float64).reshape(6)
+    e, s = np.ascontiguousarray(edge_rows9, np.float64).reshape(-1, 9), np.ascontiguousarray(plane_rows7, np.float64).reshape(-1, 7)
+    acc = np.zeros(28)
+    rc = lib().alego_regcov_normal_host(p.ctypes.data, e.ctypes.data if len(e) else None, len(e), s.ctypes.data if len(s) else None, len(s), float(huber), acc.ctypes.data)
+    if rc != 0:
+        raise AlegoError(f"alego_regcov_normal_host failed ({rc})")
+    return acc
 
 
 def _graph_checks_out(out, n):
@@ -429,6 +479,11 @@ def lib():
         L.alego_graph_check_loops.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(LoopResult), C.POINTER(GraphCheck)]
         L.alego_graph_covariance_host.argtypes = [C.c_void_p, C.c_int32, C.POINTER(GraphEdge), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
         L.alego_graph_check_host.argtypes = [C.c_void_p, C.c_int32, C.POINTER(GraphEdge), C.c_int32, C.POINTER(GraphEdge), C.c_int32, C.POINTER(GraphCheck)]
+        L.alego_regcov_enable.argtypes = [C.c_void_p, C.POINTER(RegCovOpts)]
+        L.alego_regcov_get.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(RegCov)]
+        L.alego_regcov_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(RegCovOpts), C.POINTER(RegCov)]
+        L.alego_regcov_normal_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_void_p]
+        L.alego_debug_regcov.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(RegCov)]
         L.alego_loc_select.restype = C.c_int
         L.alego_loc_select.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_int32, C.c_void_p]
         L.alego_loc_enable.argtypes = [C.c_void_p, C.POINTER(KfIn), C.c_int32, C.c_double]
@@ -1380,6 +1435,27 @@ class Handle:
         return idx[:q.shape[0]].copy(), d2[:q.shape[0]].copy()
 
     # ---- one registration sharded over the ranks of an RCCL communicator (BASELINE config 5) ----
+    # ---- covariance and degeneracy of the scan-to-map registration ----
+    def regcov_enable(self, opts=None):
+        """alego_regcov_enable: opts = regcov_opts(...) or None for the defaults; before the first scan reaches LaserMapping"""
+        self._check(lib().alego_regcov_enable(self._h, None if opts is None else C.byref(opts)), "alego_regcov_enable")
+
+    def regcov_get(self, slots=(0,)):
+        """alego_regcov_get: one dict per listed slot (status, n_edge, n_plane, n_degenerate, frame, cost, sigma2, info, eigval, eigvec, cov, variance)"""
+        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        out = (RegCov * max(sl.shape[0], 1))()
+        self._check(lib().alego_regcov_get(self._h, sl.ctypes.data, sl.shape[0], out), "alego_regcov_get")
+        return [_regcov_out(r) for r in out[:sl.shape[0]]]
+
+    def debug_regcov(self, params6, edge_rows9, plane_rows7):
+        """alego_debug_regcov: lm_regcov alone on rows (a, b, p) (n, 9) and (n, d, p) (m, 7) at params6 (p is rounded to f32)"""
+        p = np.ascontiguousarray(params6, np.float64).reshape(6)
+        e, s = np.ascontiguousarray(edge_rows9, np.float64).reshape(-1, 9), np.ascontiguousarray(plane_rows7, np.float64).reshape(-1, 7)
+        out = RegCov()
+        self._check(lib().alego_debug_regcov(self._h, p.ctypes.data, e.ctypes.data if len(e) else None, len(e), s.ctypes.data if len(s) else None, len(s), C.byref(out)),
+                    "alego_debug_regcov")
+        return _regcov_out(out)
+
     def dist_init(self, rank, world, unique_id: bytes):
         self._check(lib().alego_dist_init(self._h, rank, world, C.create_string_buffer(unique_id, DIST_ID_BYTES)), "alego_dist_init")
 

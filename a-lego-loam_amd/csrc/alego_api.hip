@@ -24,6 +24,7 @@
 #include "loop_ctx.h"
 #include "pgraph.h"
 #include "prof.h"
+#include "reg_cov_math.h"
 #include "reloc.h"
 #include "stream_plan.h"
 #include "voxel.h"
@@ -1308,6 +1309,73 @@ int alego_graph_covariance_host(const double* poses12, int32_t n_poses, const al
 int alego_graph_check_host(const double* poses12, int32_t n_poses, const alego_graph_edge* edges, int32_t n_edges, const alego_graph_edge* cand, int32_t n_cand,
                            alego_graph_check* out) {
   return graph_check_host(poses12, n_poses, edges, n_edges, cand, n_cand, out);
+}
+
+// ---- covariance and degeneracy of the scan-to-map registration --------------------------------
+int alego_regcov_enable(alego_handle* h, const alego_regcov_opts* opts) {
+  if (!h) return ALEGO_ERR_ARG;
+  if (!h->lm) { h->err = "alego_regcov_enable: the handle has no LaserMapping"; return ALEGO_ERR_ARG; }
+  hipSetDevice(h->device);
+  HIP_TRY(h, sync_all(h));
+  return lm_host_regcov_enable(h->lm, opts, &h->err);
+}
+int alego_regcov_get(alego_handle* h, const int32_t* slots, int32_t n, alego_regcov* out) {
+  if (!h) return ALEGO_ERR_ARG;
+  if (!h->lm || n < 0 || (n > 0 && (!slots || !out))) { h->err = "alego_regcov_get: null argument / negative count"; return ALEGO_ERR_ARG; }
+  hipSetDevice(h->device);
+  HIP_TRY(h, sync_all(h));   // behind everything already queued on every stream group
+  return lm_host_regcov_get(h->lm, slots, n, out, &h->err);
+}
+int alego_regcov_host(const double acc28[28], const double params6[6], int32_t n_edge, int32_t n_plane, const alego_regcov_opts* opts, alego_regcov* out) {
+  if (!acc28 || !params6 || !out || n_edge < 0 || n_plane < 0) return ALEGO_ERR_ARG;
+  double dflt[RC_OPT_W], opt[RC_OPT_W];
+  (void)lm_host_regcov_opts(nullptr, dflt);
+  if (rc_resolve(opts ? &opts->sigma0 : nullptr, dflt + RC_VAR_MIN, opt)) return ALEGO_ERR_ARG;
+  regcov_host(acc28, params6, n_edge, n_plane, opt, out);
+  return 0;
+}
+int alego_regcov_normal_host(const double params6[6], const double* edge_rows9, int32_t n_edge, const double* plane_rows7, int32_t n_plane, double huber, double acc28[28]) {
+  if (!params6 || !acc28 || n_edge < 0 || n_plane < 0 || (n_edge > 0 && !edge_rows9) || (n_plane > 0 && !plane_rows7)) return ALEGO_ERR_ARG;
+  regcov_normal_host(params6, edge_rows9, n_edge, plane_rows7, n_plane, huber, acc28);
+  return 0;
+}
+int alego_debug_regcov(alego_handle* h, const double params6[6], const double* edge_rows9, int32_t n_edge, const double* plane_rows7, int32_t n_plane, alego_regcov* out) {
+  if (!h) return ALEGO_ERR_ARG;
+  if (!params6 || !out || n_edge < 0 || n_plane < 0 || (n_edge > 0 && !edge_rows9) || (n_plane > 0 && !plane_rows7)) { h->err = "alego_debug_regcov: null argument / negative count"; return ALEGO_ERR_ARG; }
+  hipSetDevice(h->device);
+  double opt[RC_OPT_W];
+  (void)lm_host_regcov_opts(h->lm, opt);
+  // rows as lm_fit leaves them (8 doubles: a / normal, b, d, type), edges first, and the query points as f32
+  const size_t nr = (size_t)n_edge + (size_t)n_plane;
+  std::vector<double> blocks(std::max<size_t>(nr, 1) * 8, 0.0);
+  std::vector<float> qc(std::max<size_t>((size_t)n_edge, 1) * 4, 0.f), qs(std::max<size_t>((size_t)n_plane, 1) * 4, 0.f);
+  for (int i = 0; i < n_edge; ++i) {
+    const double* r = edge_rows9 + (size_t)i * 9;
+    for (int k = 0; k < 6; ++k) blocks[(size_t)i * 8 + k] = r[k];
+    blocks[(size_t)i * 8 + 7] = 2.0;
+    for (int k = 0; k < 3; ++k) qc[(size_t)i * 4 + k] = (float)r[6 + k];
+  }
+  for (int i = 0; i < n_plane; ++i) {
+    const double* r = plane_rows7 + (size_t)i * 7;
+    double* b = &blocks[((size_t)n_edge + i) * 8];
+    b[0] = r[0]; b[1] = r[1]; b[2] = r[2]; b[6] = r[3]; b[7] = 3.0;
+    for (int k = 0; k < 3; ++k) qs[(size_t)i * 4 + k] = (float)r[4 + k];
+  }
+  DevPool T;   // temporaries of this call
+  double *db, *dp, *dopt;
+  float4 *dqc, *dqs;
+  alego_regcov* drec;
+  HIP_TRY(h, T.get(&db, blocks.size(), false)); HIP_TRY(h, T.get(&dp, 6, false)); HIP_TRY(h, T.get(&dopt, (size_t)RC_OPT_W, false));
+  HIP_TRY(h, T.get(&dqc, qc.size() / 4, false)); HIP_TRY(h, T.get(&dqs, qs.size() / 4, false)); HIP_TRY(h, T.get(&drec, 1, true));
+  HIP_TRY(h, hipMemcpy(db, blocks.data(), blocks.size() * 8, hipMemcpyHostToDevice));
+  HIP_TRY(h, hipMemcpy(dp, params6, 48, hipMemcpyHostToDevice));
+  HIP_TRY(h, hipMemcpy(dopt, opt, sizeof(opt), hipMemcpyHostToDevice));
+  HIP_TRY(h, hipMemcpy(dqc, qc.data(), qc.size() * 4, hipMemcpyHostToDevice));
+  HIP_TRY(h, hipMemcpy(dqs, qs.data(), qs.size() * 4, hipMemcpyHostToDevice));
+  launch_lm_regcov_debug(db, dqc, n_edge, dqs, n_plane, dp, h->d.P.huber_delta, dopt, drec, h->stream);
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  HIP_TRY(h, hipMemcpy(out, drec, sizeof(*out), hipMemcpyDeviceToHost));
+  return 0;
 }
 
 // ---- one registration sharded over the GPUs of a node ---------------------------------------------------------------

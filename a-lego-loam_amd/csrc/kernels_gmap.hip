@@ -82,6 +82,12 @@ __global__ void __launch_bounds__(GM_T) map_archive(DevCtx d, LmCtx L, int force
         pg_between(xp, xn, e->between);
       }
       for (int k = 0; k < 6; ++k) e->variance[k] = L.pg_odom_var[k];
+      // alego_regcov_enable with graph = 1: an odometry edge of a frame the registration itself saved carries that registration's variances (the
+      // newer frame's covariance alone, in its tangent space); the prior, a forced archive and a record without a result keep pg_odom_var
+      if (L.rc_graph && !force && nf > 0) {
+        const alego_regcov* rc = L.rc_rec + slot;
+        if (rc->status == 1 && rc->frame == li[LI_FRAME]) for (int k = 0; k < 6; ++k) e->variance[k] = rc->variance[k];
+      }
     }
   }
 }

@@ -12,7 +12,12 @@
 //   lm_finish / lm_store_kf  saveKeyFramesAndFactor (no-loop-closure pass-through) + transformUpdate
 // The registration guards read "no map yet" as (LI_NKF | LI_REC_CNT) == 0: no key frame in SLAM mode (a window entry implies one), an empty
 // window in localisation mode, where LI_NKF stays 0 (kernels_loc.hip).
+#include <cstddef>
+#include <cstring>
+
+#include "../../include/alego_mi355x.h"
 #include "dev_cost.h"
+#include "reg_cov_math.h"
 #include "prof.h"
 #include "kf_store.h"
 #include "gmap.h"
@@ -900,6 +905,161 @@ DEV_INLINE void lm_solve_body(const DevCtx& d, const LmCtx& L) {
 __global__ void __launch_bounds__(LM_SOLVE_T) lm_solve(DevCtx d, LmCtx L) { lm_solve_body<false>(d, L); }
 __global__ void __launch_bounds__(LM_SOLVE_T) lm_solve_full_eval(DevCtx d, LmCtx L) { lm_solve_body<true>(d, L); }
 
+// ---- covariance and degeneracy of the registration (alego_regcov_enable; reg_cov_math.h) -----------------------------
+// One full evaluation of the accepted rows at the solver's final point, then the 6x6 part on wave 0.  The rows are streamed once from where
+// lm_fit left them (L.blocks and the two query clouds), thread-strided over the QUERIES: thread t takes queries t, t + T, ... and the 28 sums
+// go through block_reduce28_oct, so the result is a function of the slot's rows alone.  (lm_solve packs the rows into LDS because it reads them
+// ~30 times; one pass gains nothing from it.)
+struct RcSrc {
+  const double* blocks;      // [rows][8]: a / normal (3), b (3), d, type (0 = not accepted)
+  const float4 *qc, *qs;     // corner queries, surf queries
+  int nqc, nqs, surf_row0;   // query i < nqc: row i of blocks, else row surf_row0 + (i - nqc)
+  const double* params;      // p[6]
+};
+static_assert(offsetof(alego_regcov, cost) == 24 && sizeof(alego_regcov) == 24 + 122 * sizeof(double), "rc_store_empty walks the record's doubles from `cost`");
+
+// wave 0: a record without a result
+DEV_INLINE void rc_store_empty(alego_regcov* rec, int status, int n_edge, int n_plane, int frame) {
+  double* dv = &rec->cost;
+  for (int k = threadIdx.x; k < 122; k += 64) dv[k] = 0.0;
+  if (threadIdx.x == 0) { rec->status = status; rec->n_edge = n_edge; rec->n_plane = n_plane; rec->n_degenerate = 0; rec->frame = frame; rec->pad = 0; }
+}
+
+// wave 0, all 64 lanes active.  Lane 6 i + j owns entry (i, j) of info, of the Jacobi iterate A, of the eigenvectors V and of cov (lanes 36 .. 63
+// shadow lane 35 and store nothing); a rotation fetches its partners with wave shuffles, every lane forms (c, s) from the same three entries.
+// The operations and their order are rc_compute's (reg_cov_math.h), entry by entry.
+DEV_INLINE void rc_tail(const double* s_out /* LDS [28] */, double* s_N /* LDS [36] */, const double* p,int n_edge, int n_plane, int frame, const double* opt, alego_regcov* rec) {
+  const int lane = threadIdx.x, l = lane < 36 ? lane : 35, i = l / 6, j = l - 6 * i;
+  const int rows = n_edge + n_plane;
+  double p6[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) p6[k] = p[k];
+  if (rows <= 6) { rc_store_empty(rec, 0, n_edge, n_plane, frame); return; }
+  if (fabs(cos(p6[4])) < RC_COS_PITCH_MIN) { rc_store_empty(rec, -3, n_edge, n_plane, frame); return; }
+  {   // N = M^-1 into LDS (an entry of info indexes it by lane; a private array indexed that way would live in scratch)
+    double N[36];
+    rc_minv(p6, N);
+#pragma unroll
+    for (int k = 0; k < 36; ++k) if (lane == k) s_N[k] = N[k];
+    __threadfence_block();
+  }
+  const double info = rc_info_entry(s_out, s_N, i < j ? i : j, i < j ? j : i);
+  bool bad = !rc_finite(info) || (lane < 28 && !rc_finite(s_out[lane])) || (lane < 6 && !rc_finite(p[lane]));
+  if (__any(bad)) { rc_store_empty(rec, -2, n_edge, n_plane, frame); return; }
+  double A = info, V = i == j ? 1.0 : 0.0;
+  for (int sweep = 0; sweep < RC_SWEEPS_MAX; ++sweep) {
+    double off = 0.0, dg = 0.0;
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+      for (int b = a + 1; b < 6; ++b) { const double x = __shfl(A, a * 6 + b); off += x * x; }
+#pragma unroll
+    for (int a = 0; a < 6; ++a) { const double x = __shfl(A, a * 7); dg += x * x; }
+    if (!(off > RC_OFF_REL * dg)) break;
+#pragma unroll
+    for (int pp = 0; pp < 5; ++pp)
+#pragma unroll
+      for (int q = pp + 1; q < 6; ++q) {
+        const double apq = __shfl(A, pp * 6 + q);
+        if (apq == 0.0) continue;   // (uniform)
+        double c, s;
+        rc_rot_cs(__shfl(A, pp * 7), __shfl(A, q * 7), apq, &c, &s);
+        { const double xp = __shfl(A, i * 6 + pp), xq = __shfl(A, i * 6 + q); A = rc_rot_col(j, pp, q, c, s, xp, xq, A); }
+        { const double xp = __shfl(A, pp * 6 + j), xq = __shfl(A, q * 6 + j); A = rc_rot_row(i, pp, q, c, s, xp, xq, A); }
+        { const double xp = __shfl(V, i * 6 + pp), xq = __shfl(V, i * 6 + q); V = rc_rot_col(j, pp, q, c, s, xp, xq, V); }
+      }
+  }
+  // ascending order, ties by index: sorted column r is the column whose diagonal entry has rank r
+  double dd[6], lam[6], w[6], vi[6], vj[6];
+  int rk[6], src = 0;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) dd[k] = __shfl(A, k * 7);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) { rk[k] = rc_rank(dd, k); if (rk[k] == j) src = k; }
+#pragma unroll
+  for (int r = 0; r < 6; ++r) {
+    double v = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) v = rk[k] == r ? dd[k] : v;
+    lam[r] = v;
+  }
+  const double vs = __shfl(V, i * 6 + src);
+  const double s2 = rc_sigma2(s_out[27], rows, opt[RC_SIGMA0]);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) { w[k] = rc_weight(lam[k], lam[5], opt[RC_LAMBDA_FLOOR]); vi[k] = __shfl(vs, i * 6 + k); vj[k] = __shfl(vs, j * 6 + k); }
+  const double cv = s2 * rc_cov_entry(vi, vj, w);
+  bad = !rc_finite(s2) || !rc_finite(vs) || !rc_finite(cv);
+  int ndeg = 0;
+  double lam_j = 0.0;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) { bad = bad || !rc_finite(lam[k]); ndeg += lam[k] < opt[RC_EIG_MIN] ? 1 : 0; lam_j = j == k ? lam[k] : lam_j; }
+  if (__any(bad)) { rc_store_empty(rec, -2, n_edge, n_plane, frame); return; }
+  if (lane < 36) {
+    rec->info[l] = info; rec->eigvec[l] = vs; rec->cov[l] = cv;
+    if (i == 0) rec->eigval[j] = lam_j;
+    if (i == j) rec->variance[i] = rc_clamp(opt[RC_SCALE] * cv, opt[RC_VAR_MIN + i], opt[RC_VAR_MAX + i]);
+  }
+  if (lane == 0) {
+    rec->status = 1; rec->n_edge = n_edge; rec->n_plane = n_plane; rec->n_degenerate = ndeg; rec->frame = frame; rec->pad = 0;
+    rec->cost = s_out[27]; rec->sigma2 = s2;
+  }
+}
+
+template <int T>
+DEV_INLINE void rc_body(const RcSrc& S, double huber, const double* opt, int frame, alego_regcov* rec) {
+  __shared__ double s_acc[28 * (T / 8)], s_out[28], s_trig[12], s_N[36];
+  __shared__ int s_n[2];
+  const int tid = threadIdx.x;
+  if (tid < 2) s_n[tid] = 0;
+  double acc[28];
+#pragma unroll
+  for (int k = 0; k < 28; ++k) acc[k] = 0;
+  const PoseTerms Tm = pose_terms_coop(S.params, s_trig);   // (its barrier also publishes the zeroed counters)
+  const double c3[3] = {0, 0, 0};
+  const int n_all = S.nqc + S.nqs;
+  int ne = 0, np = 0;
+  for (int q = tid; q < n_all; q += T) {
+    const bool is_c = q < S.nqc;
+    const size_t row = is_c ? (size_t)q : (size_t)S.surf_row0 + (size_t)(q - S.nqc);
+    const double4* b = reinterpret_cast<const double4*>(S.blocks + row * 8);
+    const double4 bhi = b[1];
+    if (bhi.w == 0.0) continue;
+    const double4 blo = b[0];
+    const float4 pt = is_c ? S.qc[q] : S.qs[q - S.nqc];
+    const double cp[3] = {pt.x, pt.y, pt.z}, a3[3] = {blo.x, blo.y, blo.z};
+    double res, J[6];
+    if (is_c) {   // EdgeCostFunction, as lm_eval_rows evaluates it
+      const double b3[3] = {blo.w, bhi.x, bhi.y};
+      eval_block(BLK_EDGE, cp, a3, b3, c3, 0.0, Tm, &res, J);
+      ++ne;
+    } else {      // PlaneCostFunction
+      eval_block(BLK_PLANE, cp, a3, c3, c3, bhi.z, Tm, &res, J);
+      ++np;
+    }
+    accumulate_block(res, J, huber, acc);
+  }
+  if (ne) atomicAdd(&s_n[0], ne);
+  if (np) atomicAdd(&s_n[1], np);
+  block_reduce28_oct<T>(acc, s_acc, s_out);   // (ends with a barrier: the counts are complete)
+  if (tid >= 64) return;
+  rc_tail(s_out, s_N, S.params, s_n[0], s_n[1], frame, opt, rec);
+}
+
+// grid (slots), between the solver and lm_finish (which overwrites LD_PARAMS with the f32 key pose when it saves a frame).  A slot without a mapping
+// frame keeps its record (its `frame` tells); one the solver skipped (LI_FLAGS & 16) gets status 0.
+__global__ void __launch_bounds__(LM_SOLVE_T) lm_regcov(DevCtx d, LmCtx L) {
+  const int slot = blockIdx.x + d.slot0;
+  const int* li = lip(L, slot);
+  if (!li[LI_RUN]) return;
+  alego_regcov* rec = L.rc_rec + slot;
+  if (!li[LI_OPTIMIZED]) { if (threadIdx.x < 64) rc_store_empty(rec, 0, 0, 0, li[LI_FRAME]); return; }
+  const RcSrc S{L.blocks + (size_t)slot * L.qcap * 8, L.cur_corner_ds + (size_t)slot * L.kf_cap_c, L.cur_total_ds + (size_t)slot * L.total_cap,
+                li[LI_NCUR_C], li[LI_NTOTAL_DS], L.kf_cap_c, ldp(L, slot) + LD_PARAMS};
+  rc_body<LM_SOLVE_T>(S, d.P.huber_delta, L.rc_opt, li[LI_FRAME], rec);
+}
+// the same on caller-supplied rows (alego_debug_regcov)
+__global__ void __launch_bounds__(LM_SOLVE_T) lm_regcov_debug(RcSrc S, double huber, const double* opt, alego_regcov* rec) { rc_body<LM_SOLVE_T>(S, huber, opt, 0, rec); }
+
 // grid (ceil(slots/64)): saveKeyFramesAndFactor :491-559 (no-loop-closure pass-through) + transformUpdate :481-489
 __global__ void lm_finish(DevCtx d, LmCtx L) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1141,11 +1301,40 @@ int launch_lm_register(const DevCtx& d, const LmCtx& L, hipStream_t st, int (*al
   } else {
     ALEGO_LAUNCH(lm_solve, dim3(d.n_launch), dim3(LM_SOLVE_T), LM_SOLVE_RED_BYTES + L.solve_row_bytes, st, d, L);
   }
+  if (L.rc_rec) ALEGO_LAUNCH(lm_regcov, dim3(d.n_launch), dim3(LM_SOLVE_T), 0, st, d, L);   // (alego_regcov_enable; nothing is launched without it)
   ALEGO_LAUNCH(lm_finish, dim3((d.n_launch + 63) / 64), dim3(64), 0, st, d, L);
-  if (L.loc_on) return 0;   // no key frame is ever stored, sorted or archived
+  if (L.loc_on) return 0;  // no key frame is ever stored, sorted or archived
   ALEGO_LAUNCH(lm_store_kf, dim3(8, 3, d.n_launch), dim3(LM_BLOCK), 0, st, d, L, -1);
   if (L.arc_frames_cap > 0) launch_map_archive(d, L, 0, st);   // (alego_map_enable; nothing is launched without it)
   return 0;
+}
+// host twins (alego_regcov_host, alego_regcov_normal_host): rc_compute on the caller's 28 scalars; the functors of solve_rows.h over the caller's rows
+void regcov_host(const double* acc28, const double* params6, int n_edge, int n_plane, const double* opt, alego_regcov* out) {
+  std::memset(out, 0, sizeof(*out));
+  out->n_edge = n_edge; out->n_plane = n_plane;
+  out->status = rc_compute(acc28, params6, n_edge, n_plane, opt, &out->sigma2, out->info, out->eigval, out->eigvec, out->cov, out->variance, &out->n_degenerate, nullptr);
+  if (out->status == 1) out->cost = acc28[27];
+}
+void regcov_normal_host(const double* params6, const double* edge_rows9, int n_edge, const double* plane_rows7, int n_plane, double huber, double* acc28) {
+  for (int k = 0; k < 28; ++k) acc28[k] = 0.0;
+  const PoseTerms Tm = pose_terms(params6);
+  const double c3[3] = {0, 0, 0};
+  double res, J[6];
+  for (int i = 0; i < n_edge; ++i) {
+    const double* r = edge_rows9 + (size_t)i * 9;
+    eval_block(BLK_EDGE, r + 6, r, r + 3, c3, 0.0, Tm, &res, J);
+    accumulate_block(res, J, huber, acc28);
+  }
+  for (int i = 0; i < n_plane; ++i) {
+    const double* r = plane_rows7 + (size_t)i * 7;
+    eval_block(BLK_PLANE, r + 4, r, c3, c3, r[3], Tm, &res, J);
+    accumulate_block(res, J, huber, acc28);
+  }
+}
+void launch_lm_regcov_debug(const double* blocks, const float4* qc, int n_edge, const float4* qs, int n_plane, const double* params, double huber, const double* opt,
+                            alego_regcov* rec, hipStream_t st) {
+  const RcSrc S{blocks, qc, qs, n_edge, n_plane, n_edge, params};
+  ALEGO_LAUNCH(lm_regcov_debug, dim3(1), dim3(LM_SOLVE_T), 0, st, S, huber, opt, rec);
 }
 void launch_lm_retransform(const DevCtx& d, const LmCtx& L, int ring, hipStream_t st) {
   ALEGO_LAUNCH(lm_store_kf, dim3(8, 3, d.n_launch), dim3(LM_BLOCK), 0, st, d, L, ring);

@@ -46,6 +46,7 @@ enum {
 };
 
 struct alego_graph_edge;   // include/alego_mi355x.h
+struct alego_regcov;
 
 struct MapWork {     // work list of map_accum, written by map_update (kernels_map.hip)
   int* items;      // [cap] packed (slot - slot0) << 12 | m << 11 | chunk   (chunk < 2048)
@@ -166,6 +167,11 @@ struct LmCtx {
   float* pg_corr;                                 // [slot][16] ICP correction of the last loop edge added (correctPoses :579-580)
   int* pg_stat;                                   // [slot][4] loop edges stored, loop_closed_ (a loop edge was added since the last apply), poses of the estimate, -
   double* pg_est;                                 // [slot][arc_frames_cap][12] Pose3 estimate of the slot's last optimise, row-major [R | t]
+  // registration covariance (alego_regcov_enable; rc_rec == nullptr: off, nothing is launched or allocated): one record per slot, written by
+  // lm_regcov between the solver and lm_finish
+  alego_regcov* rc_rec;                           // [slot]
+  const double* rc_opt;                           // [RC_OPT_W] the resolved options (reg_cov_math.h)
+  int rc_graph;                                   // 1: map_archive writes a fresh record's variances into the odometry edge it records
 };
 
 // host entry points of LaserMapping's kernels (kernels_lm.hip, then kernels_map.hip and kernels_loc.hip), called by lm_host.hip; lm_configure: by alego_create
@@ -179,6 +185,12 @@ void launch_lm_grid(const DevCtx& d, const LmCtx& L, hipStream_t st);
 int launch_lm_register(const DevCtx& d, const LmCtx& L, hipStream_t st, int (*allreduce)(void*, double*, size_t, hipStream_t), void* ar_ctx);
 void launch_lm_retransform(const DevCtx& d, const LmCtx& L, int ring, hipStream_t st);
 void launch_lm_apply_correction(const DevCtx& d, const LmCtx& L, int slot, const double* rc_dev, hipStream_t st);
+// lm_regcov's evaluation and 6x6 part on caller-supplied rows: blocks [n_edge + n_plane][8] (edges first), their query points, p[6], options, one record
+void launch_lm_regcov_debug(const double* blocks, const float4* qc, int n_edge, const float4* qs, int n_plane, const double* params, double huber, const double* opt,
+                            alego_regcov* rec, hipStream_t st);
+// host twins: the record from 28 scalars and resolved options (reg_cov_math.h); the 28 scalars from rows (a, b, p | n, d, p), edges then planes, in row order
+void regcov_host(const double* acc28, const double* params6, int n_edge, int n_plane, const double* opt, alego_regcov* out);
+void regcov_normal_host(const double* params6, const double* edge_rows9, int n_edge, const double* plane_rows7, int n_plane, double huber, double* acc28);
 void launch_map_update(const DevCtx& d, const LmCtx& L, const MapWork& W, hipStream_t st);
 void launch_map_accum(const DevCtx& d, const LmCtx& L, const MapWork& W, hipStream_t st);
 void launch_loc_select(const DevCtx& d, const LmCtx& L, hipStream_t st);

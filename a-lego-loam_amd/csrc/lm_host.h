@@ -79,4 +79,9 @@ int lm_host_loc_update_from_map(LmHost* lm, LmHost* src, int slot, bool* rewritt
 int lm_host_set_loc_chunk(LmHost* lm, int frames);   // ALEGO_LOC_CHUNK: frames per chunk of that build
 int lm_host_loc_status(LmHost* lm, int slot, int* out4, std::string* err);
 bool lm_host_localising(LmHost* lm);
+// covariance of the registration (alego_regcov_*; lm_regcov in kernels_lm.hip).  The caller has synchronised the handle's streams before enable.
+int lm_host_regcov_enable(LmHost* lm, const alego_regcov_opts* opts, std::string* err);
+int lm_host_regcov_get(LmHost* lm, const int* slots, int n, alego_regcov* out, std::string* err);
+bool lm_host_regcov_on(LmHost* lm);
+bool lm_host_regcov_opts(LmHost* lm, double* opt16);   // the handle's resolved options (the defaults while the feature is off; lm may be null); true: the feature is on
 #endif

@@ -2,6 +2,7 @@
 #include "lm_host.h"
 #include "dev_mem.h"
 
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
@@ -20,6 +21,7 @@
 #include "thin.h"
 #include "thin_math.h"
 #include "loc_store.h"
+#include "reg_cov_math.h"
 
 struct LmHost {
   alego_params P;
@@ -59,6 +61,9 @@ struct LmHost {
   DevBuf<float4> th_pts;
   DevBuf<ThRow> th_rows;
   DevBuf<float> th_pose;
+  // alego_regcov_enable: the resolved options (reg_cov_math.h) as the device holds them
+  bool rc_on = false;
+  double rc_opt[RC_OPT_W] = {};
 };
 
 namespace {
@@ -542,6 +547,7 @@ int lm_host_dist_unique_id(char* id128) {
 }
 int lm_host_dist_init(LmHost* lm, int rank, int world, const char* id128, std::string* err) {
   if (lm->comm) { *err = "alego_dist_init: already initialised"; return ALEGO_ERR_ARG; }
+  if (lm->rc_on) { *err = "alego_dist_init: not available with alego_regcov_enable (the sharded solver never holds a registration's normal equations in one place)"; return ALEGO_ERR_ARG; }
   if (world < 1 || rank < 0 || rank >= world) { *err = "alego_dist_init: rank / world out of range"; return ALEGO_ERR_ARG; }
   if (lm->st.size() != 1) { *err = "alego_dist_init: a sharded registration needs a handle with one stream group (collectives of one communicator must not overlap)"; return ALEGO_ERR_ARG; }
   ncclUniqueId u;
@@ -987,6 +993,56 @@ int lm_host_graph_enable(LmHost* lm, int max_loops, const double* odom_var6, std
   L = T;
   return 0;
 }
+
+// ---- covariance of the registration (alego_regcov_*; lm_regcov in kernels_lm.hip) ----
+static const double kOdomVarDefault[6] = {1e-6, 1e-6, 1e-6, 1e-8, 1e-8, 1e-6};   // laserMapping.cpp:68-70, the default of lm_host_graph_enable
+bool lm_host_regcov_opts(LmHost* lm, double* opt16) {
+  if (lm && lm->rc_on) { std::memcpy(opt16, lm->rc_opt, sizeof(lm->rc_opt)); return true; }
+  (void)rc_resolve(nullptr, kOdomVarDefault, opt16);
+  return false;
+}
+int lm_host_regcov_enable(LmHost* lm, const alego_regcov_opts* opts, std::string* err) {
+  static_assert(offsetof(alego_regcov_opts, graph) == RC_OPT_W * sizeof(double), "rc_resolve reads the options' doubles in the RC_* order");
+  LmCtx& L = lm->L;
+  if (lm->rc_on) { *err = "alego_regcov_enable: already enabled"; return ALEGO_ERR_ARG; }
+  if (lm->comm || L.shard_world > 0) { *err = "alego_regcov_enable: not available on a handle with a sharded registration (alego_dist_init)"; return ALEGO_ERR_ARG; }
+  const bool graph = opts && opts->graph != 0;
+  if (graph && L.pg_loops_cap <= 0) { *err = "alego_regcov_enable: graph = 1 needs the key-pose graph (alego_graph_enable first)"; return ALEGO_ERR_ARG; }
+  double opt[RC_OPT_W];
+  if (rc_resolve(opts ? &opts->sigma0 : nullptr, L.pg_loops_cap > 0 ? L.pg_odom_var : kOdomVarDefault, opt)) {
+    *err = "alego_regcov_enable: an option is not finite, or var_min exceeds var_max"; return ALEGO_ERR_ARG;
+  }
+  for (long f : lm->frames) if (f != 0) { *err = "alego_regcov_enable: call it before the first scan reaches LaserMapping"; return ALEGO_ERR_ARG; }
+  if (int r = rings_empty(lm, "alego_regcov_enable", true, err)) return r;
+  LmCtx T = L;
+  double* dopt = nullptr;
+  if (!A(lm, &T.rc_rec, (size_t)lm->n_slots, err) || !A(lm, &dopt, (size_t)RC_OPT_W, err)) return ALEGO_ERR_HIP;
+  if (hipMemcpy(dopt, opt, sizeof(opt), hipMemcpyHostToDevice) != hipSuccess) { *err = "alego_regcov_enable: copy failed"; return ALEGO_ERR_HIP; }
+  T.rc_opt = dopt; T.rc_graph = graph ? 1 : 0;
+  L = T;
+  std::memcpy(lm->rc_opt, opt, sizeof(opt));
+  lm->rc_on = true;
+  return 0;
+}
+// one copy: the records of slots [lo, hi] of the list, picked apart on the host
+int lm_host_regcov_get(LmHost* lm, const int* slots, int n, alego_regcov* out, std::string* err) {
+  if (!lm->rc_on) { *err = "alego_regcov_get: the feature is off (alego_regcov_enable)"; return ALEGO_ERR_ARG; }
+  std::vector<char> listed(lm->n_slots, 0);
+  int lo = lm->n_slots, hi = -1;
+  for (int i = 0; i < n; ++i) {
+    if (slots[i] < 0 || slots[i] >= lm->n_slots) { *err = "alego_regcov_get: slot out of range"; return ALEGO_ERR_ARG; }
+    if (listed[slots[i]]) { *err = "alego_regcov_get: a slot is listed twice"; return ALEGO_ERR_ARG; }
+    listed[slots[i]] = 1;
+    lo = std::min(lo, slots[i]); hi = std::max(hi, slots[i]);
+  }
+  if (n == 0) return 0;
+  for (hipStream_t s : lm->st) if (hipStreamSynchronize(s) != hipSuccess) { *err = "alego_regcov_get: a stream failed"; return ALEGO_ERR_HIP; }
+  std::vector<alego_regcov> tmp((size_t)(hi - lo + 1));
+  if (hipMemcpy(tmp.data(), lm->L.rc_rec + lo, tmp.size() * sizeof(alego_regcov), hipMemcpyDeviceToHost) != hipSuccess) { *err = "alego_regcov_get: device read failed"; return ALEGO_ERR_HIP; }
+  for (int i = 0; i < n; ++i) out[i] = tmp[(size_t)(slots[i] - lo)];
+  return 0;
+}
+bool lm_host_regcov_on(LmHost* lm) { return lm->rc_on; }
 
 // Frames of the slots with mask[slot] != 0 (mask_dev: the same words on the device) go through kf_tmp_* and the key-frame sort jobs, oldest first, one
 // frame of every such slot of a stream group per round (what alego_lm_set_keypose does for one frame of one slot); retransform(slot0, n, j, stream)

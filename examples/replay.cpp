@@ -60,6 +60,12 @@
 //       alego_reloc_enable builds the map's descriptors (R = max_range, default the library's); after the stream's first mapping frame
 //       alego_loc_relocalize with apply = 1 finds the place, verifies it by ICP and places the slot on the device.  The result is printed
 //       as one line "reloc: {...}"; loc_max_dev then covers the scans after the placement, and the JSON line gains "reloc_status".
+//   either source + --regcov [--regcov-graph]
+//       alego_regcov_enable: every mapping frame leaves the covariance of its scan-to-map registration on the device.
+//       Every key frame prints one line "regcov: scan K status S rows R n_degenerate D eig_min E variance v0 .. v5" (the smallest eigenvalue of
+//       the information matrix; rotation x y z in rad^2, then translation x y z in m^2).  --regcov-graph turns the archive and the key-pose
+//       graph on as well and writes those variances into the odometry edges (opts.graph = 1): with --loop-search N --gate CHI2 the gate then
+//       judges every found loop against noise the registrations measured instead of the constant default.
 // Every scan goes through ImageProjection -> LaserOdometry -> LaserMapping with one alego_scan_process call, as a single nodelet
 // manager would run them (launch/test.launch:6-10); every new key frame is pulled across the boundary the way the reference's
 // pose-graph thread reads cloud_keyposes_6d_ (laserMapping.cpp:586-596); one JSON line with the final poses is printed.
@@ -82,7 +88,7 @@ int main(int argc, char** argv) {
   std::string bag_path, topic = "/lslidar_point_cloud", map_dir;
   float map_leaf = 0.f;
   int map_frames = 4096, map_points = 1 << 24, loop_every = 0, close_every = 0, max_loops = 16;
-  bool list_only = false, standalone = false, localize = false, relocalize = false, appearance = false, merge = false, on_device = false;
+  bool list_only = false, standalone = false, localize = false, relocalize = false, appearance = false, merge = false, on_device = false, regcov = false, regcov_graph = false;
   double gate_chi2 = -1.0, loc_radius = 0.0, reloc_range = 0.0, app_max_jump = 0.0, app_range = 0.0, loop_radius = 0.0, thin_dist = -1.0;
   long reloc_start = -1, align_start = -1;
   long max_scans = -1;
@@ -120,6 +126,8 @@ int main(int argc, char** argv) {
     else if (a == "--relocalize") relocalize = true;
     else if (a == "--reloc-start") reloc_start = std::atol(val());
     else if (a == "--reloc-range") reloc_range = std::atof(val());
+    else if (a == "--regcov") regcov = true;
+    else if (a == "--regcov-graph") regcov = regcov_graph = true;
     else pos.push_back(argv[i]);
   }
   alego_bag* bag = nullptr;
@@ -163,13 +171,18 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "alego_create failed (%d): there is no CPU fallback, an MI355X is required\n", rc);
     return 1;
   }
-  if ((!map_dir.empty() || loop_every > 0 || close_every > 0 || localize || align_start >= 0 || thin_dist >= 0.0) && alego_map_enable(h, map_frames, map_points) != ALEGO_OK) {
+  if ((!map_dir.empty() || loop_every > 0 || close_every > 0 || localize || align_start >= 0 || thin_dist >= 0.0 || regcov_graph) && alego_map_enable(h, map_frames, map_points) != ALEGO_OK) {
     std::fprintf(stderr, "map_enable: %s\n", alego_last_error(h)); alego_destroy(h); return 1;
   }
   if (merge && align_start < 0) { std::fprintf(stderr, "--merge needs --align START2\n"); alego_destroy(h); return 2; }
   if (gate_chi2 >= 0.0 && loop_every <= 0) { std::fprintf(stderr, "--gate needs --loop-search EVERY\n"); alego_destroy(h); return 2; }
-  if ((close_every > 0 || merge || gate_chi2 >= 0.0) && alego_graph_enable(h, merge ? std::max(max_loops, ALEGO_ALIGN_MAX_QUERIES) : max_loops, nullptr) != ALEGO_OK) {
+  if ((close_every > 0 || merge || gate_chi2 >= 0.0 || regcov_graph) && alego_graph_enable(h, merge ? std::max(max_loops, ALEGO_ALIGN_MAX_QUERIES) : max_loops, nullptr) != ALEGO_OK) {
     std::fprintf(stderr, "graph_enable: %s\n", alego_last_error(h)); alego_destroy(h); return 1;
+  }
+  if (regcov) {   // after the graph: graph = 1 needs it, and var_min defaults to its odometry variances
+    alego_regcov_opts ro{};
+    ro.graph = regcov_graph ? 1 : 0;
+    if (alego_regcov_enable(h, &ro) != ALEGO_OK) { std::fprintf(stderr, "regcov_enable: %s\n", alego_last_error(h)); alego_destroy(h); return 1; }
   }
   if (((appearance && (loop_every > 0 || close_every > 0)) || align_start >= 0) && alego_loop_appearance_enable(h, app_range, 0.0 / 0.0) != ALEGO_OK) {
     std::fprintf(stderr, "loop_appearance_enable: %s\n", alego_last_error(h)); alego_destroy(h); return 1;
@@ -234,6 +247,13 @@ int main(int argc, char** argv) {
       if (alego_lm_get_keyframe(h, 0, -1, &kf) < 0) { std::fprintf(stderr, "get_keyframe: %s\n", alego_last_error(h)); alego_destroy(h); return 1; }
       ++key_frames;
       for (int i = 0; i < 6; ++i) last_key_pose[i] = kf.pose[i];
+      if (regcov) {   // the registration that produced this key frame: how well was it constrained?
+        const int32_t slot = 0;
+        alego_regcov rc{};
+        if (alego_regcov_get(h, &slot, 1, &rc) != ALEGO_OK) { std::fprintf(stderr, "regcov_get: %s\n", alego_last_error(h)); alego_destroy(h); return 1; }
+        std::printf("regcov: scan %ld status %d rows %d n_degenerate %d eig_min %.6g variance %.6g %.6g %.6g %.6g %.6g %.6g\n", k, rc.status, rc.n_edge + rc.n_plane,
+                    rc.n_degenerate, rc.eigval[0], rc.variance[0], rc.variance[1], rc.variance[2], rc.variance[3], rc.variance[4], rc.variance[5]);
+      }
     }
     if (loop_every > 0 && (k + 1) % loop_every == 0) {
       const int32_t slot = 0;

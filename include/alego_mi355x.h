@@ -492,7 +492,8 @@ int alego_graph_residuals(const double* poses12, int32_t n_poses, const alego_gr
  * Gate: for a candidate from -> to with measurement and variances, d2 = e^T P^-1 e with e the unwhitened error Logmap(measured^-1 (x_from^-1
  * x_to)) and P = the covariance of e the graph predicts + diag(variance); compare d2 with a chi-square quantile of 6 degrees of freedom.
  * NOTE on noise: with the default odometry variances (1e-6 / 1e-8) the graph claims millimetres of drift over a lap and the gate refuses every
- * real loop; a host that gates passes honest odometry variances to alego_graph_enable. */
+ * real loop.  A host that gates either passes honest odometry variances to alego_graph_enable, or lets the library measure them: with
+ * alego_regcov_enable (opts.graph = 1, below) every odometry edge carries the variances of the registration that produced its frame. */
 #define ALEGO_GRAPH_CHI2_6_999 22.457744484825323   /* chi-square, 6 dof, 0.999 */
 typedef struct alego_graph_cov_result { int32_t status, n_poses, n_loops, pad; } alego_graph_cov_result;
    /* status: 1 computed, 0 no key frame, -1 the archive dropped frames, -2 not finite */
@@ -518,6 +519,52 @@ int alego_graph_covariance_host(const double* poses12, int32_t n_poses, const al
                                 const int32_t* pairs, int32_t n_pairs, double* marg36, double* pair36);
 int alego_graph_check_host(const double* poses12, int32_t n_poses, const alego_graph_edge* edges, int32_t n_edges,
                            const alego_graph_edge* cand, int32_t n_cand, alego_graph_check* out);
+
+/* ---- covariance and degeneracy of LaserMapping's scan-to-map registration (csrc/reg_cov_math.h) -----------------
+ * Opt-in per handle; without alego_regcov_enable nothing is allocated or launched.  With it, every mapping frame of every slot that registers
+ * (SLAM and localising handles alike) leaves one record, computed on the device between the solver and the key-frame decision from ONE full
+ * evaluation of the accepted rows at the solver's final point p = (x, y, z, roll, pitch, yaw): H = J^T J (Huber-corrected as the solver
+ * forms it), J^T r and the cost 1/2 sum rho.
+ *   info      N^T H N, N = M^-1, xi = M dp the pose's tangent vector in GTSAM's convention (right perturbation, rotation x y z first, then
+ *             translation x y z — the space of alego_graph_edge.variance and alego_graph_marginals)
+ *   eigval    of info, ascending (ties by index), eigvec column k the unit vector of eigval[k] (cyclic Jacobi, f64)
+ *   n_degenerate   eigenvalues below eig_min (LOAM / LeGO-LOAM's isDegenerate; default 100 = LeGO-LOAM's eignThre, a parameter)
+ *   sigma2    max(sigma0^2, 2 cost / (rows - 6)): the residual variance, floored by the sensor's sigma0 (default 0.02 m)
+ *   cov       sigma2 V diag(1 / max(eigval_k, lambda_rel_floor eigval_max)) V^T, symmetric to the last bit
+ *   variance  clamp(scale cov[k][k], var_min[k], var_max[k]); defaults: scale 1, lambda_rel_floor 1e-12, var_max 1 (rad^2, m^2), var_min = the
+ *             odometry variances of alego_graph_enable when the graph is on at the time of the call, else its default {1e-6 x 3, 1e-8 x 2, 1e-6}
+ * All of these are parameters of a noise model, not measurements.  Query points are f32 on the device, everything else f64.
+ * opts.graph = 1 (needs alego_graph_enable before this call): the odometry edge map_archive records for a key frame carries `variance` of
+ * that frame's record when its status is 1; the prior, a frame inserted by alego_lm_add_keyframe and any other status keep odom_variance.
+ * Model: the edge's noise is the registration covariance of the NEWER frame alone, read in its own tangent space — at zero error the
+ * Jacobian of the between-error with respect to the `to` pose is the identity — and diagonal (alego_graph_edge holds six variances); the
+ * correlation with the older frame through the shared local map is ignored.
+ * Not available with a sharded registration: alego_regcov_enable returns ALEGO_ERR_ARG after alego_dist_init, and alego_dist_init after it. */
+typedef struct alego_regcov_opts {
+  double sigma0, scale, eig_min, lambda_rel_floor;
+  double var_min[6], var_max[6];
+  int32_t graph, pad;
+} alego_regcov_opts;
+typedef struct alego_regcov {
+  int32_t status;          /* 1 computed, 0 no registration in the slot's last mapping frame or fewer than 7 rows, -2 not finite, -3 |cos pitch| too small;
+                              with a status other than 1 every double below is 0 */
+  int32_t n_edge, n_plane, n_degenerate, frame, pad;   /* frame: the slot's mapping-frame counter (lm_info LI_FRAME) the record belongs to */
+  double cost, sigma2, info[36], eigval[6], eigvec[36] /* column k = vector of eigval[k] */, cov[36], variance[6];
+} alego_regcov;
+/* once, before the first scan reaches LaserMapping in any slot, else ALEGO_ERR_ARG; NULL or a field <= 0 = defaults; ALEGO_ERR_ARG also for a
+ * field that is not finite, var_min[k] > var_max[k], graph = 1 without the graph, a sharded handle */
+int alego_regcov_enable(alego_handle* h, const alego_regcov_opts* opts);
+/* the records of the listed slots as the last mapping frame left them (status 0 before the first); synchronous, one copy for the whole list.
+ * ALEGO_ERR_ARG: feature off, a null argument, a slot out of range or listed twice */
+int alego_regcov_get(alego_handle* h, const int32_t* slots, int32_t n, alego_regcov* out);
+/* host twin of the kernel's 6x6 part (the same arithmetic, csrc/reg_cov_math.h): acc28 = upper triangle of H (21, row by row), J^T r (6), cost;
+ * var_min defaults to the graph's default odometry variances; frame = 0.  Returns 0, or ALEGO_ERR_ARG for a null argument / bad options */
+int alego_regcov_host(const double acc28[28], const double params6[6], int32_t n_edge, int32_t n_plane, const alego_regcov_opts* opts, alego_regcov* out);
+/* host: eval_block + accumulate_block (csrc/solve_rows.h) over rows (a, b, p | n, d, p), edges then planes, summed in row order */
+int alego_regcov_normal_host(const double params6[6], const double* edge_rows9, int32_t n_edge, const double* plane_rows7, int32_t n_plane, double huber, double acc28[28]);
+/* the kernel alone on given rows (p rounded to f32, as the device keeps query points), as alego_debug_eval_blocks is for the functors: the
+ * handle's Huber delta, its options when the feature is on and the defaults otherwise; touches no slot */
+int alego_debug_regcov(alego_handle* h, const double params6[6], const double* edge_rows9, int32_t n_edge, const double* plane_rows7, int32_t n_plane, alego_regcov* out);
 
 /* ---- localisation: many streams against ONE frozen key-frame map -------------------------------------
  * A handle-wide mode, off by default (nothing of it is allocated or launched then).  alego_loc_enable hands the handle N key frames — pose
