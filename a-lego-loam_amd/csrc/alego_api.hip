@@ -1345,20 +1345,18 @@ int alego_debug_regcov(alego_handle* h, const double params6[6], const double* e
   hipSetDevice(h->device);
   double opt[RC_OPT_W];
   (void)lm_host_regcov_opts(h->lm, opt);
-  // rows as lm_fit leaves them (8 doubles: a / normal, b, d, type), edges first, and the query points as f32
+  // block records as lm_fit leaves them (lm_rows.h), the planes' rows from n_edge, and the query points as f32
   const size_t nr = (size_t)n_edge + (size_t)n_plane;
-  std::vector<double> blocks(std::max<size_t>(nr, 1) * 8, 0.0);
+  std::vector<double> blocks(std::max<size_t>(nr, 1) * LMB_W, 0.0);
   std::vector<float> qc(std::max<size_t>((size_t)n_edge, 1) * 4, 0.f), qs(std::max<size_t>((size_t)n_plane, 1) * 4, 0.f);
   for (int i = 0; i < n_edge; ++i) {
     const double* r = edge_rows9 + (size_t)i * 9;
-    for (int k = 0; k < 6; ++k) blocks[(size_t)i * 8 + k] = r[k];
-    blocks[(size_t)i * 8 + 7] = 2.0;
+    lmb_put_edge(&blocks[lm_row_of(0, i, n_edge) * LMB_W], r, r + 3);
     for (int k = 0; k < 3; ++k) qc[(size_t)i * 4 + k] = (float)r[6 + k];
   }
   for (int i = 0; i < n_plane; ++i) {
     const double* r = plane_rows7 + (size_t)i * 7;
-    double* b = &blocks[((size_t)n_edge + i) * 8];
-    b[0] = r[0]; b[1] = r[1]; b[2] = r[2]; b[6] = r[3]; b[7] = 3.0;
+    lmb_put_plane(&blocks[lm_row_of(1, i, n_edge) * LMB_W], r, r[3]);
     for (int k = 0; k < 3; ++k) qs[(size_t)i * 4 + k] = (float)r[4 + k];
   }
   DevPool T;   // temporaries of this call

@@ -4,6 +4,7 @@
 #define ALEGO_DEV_COST_H_
 
 #include "dev_common.h"
+#include <type_traits>
 #include "solve_rows.h"
 
 DEV_INLINE void dq_to_mat(const DQuat& q, double R[9]) {
@@ -82,7 +83,7 @@ template <class T, bool FLAT = false> DEV_INLINE void dq_apply_correction(double
 // quaternion, the three full angles of the Jacobian terms), everybody assembles the result from LDS.  Evaluating the
 // nine sin/cos pairs in every thread cost ~2000 fp64 instructions per wavefront and solver evaluation — most of what
 // lo_solve / lm_solve issued.  Same sin()/cos() calls on the same arguments: bit-identical to pose_terms().
-// Ends with a barrier; the caller must pass another barrier before the next call (block_reduce28_lds does).
+// Ends with a barrier; the caller must pass another barrier before the next call (block_reduce28 does).
 DEV_INLINE PoseTerms pose_terms_coop(const double* p, double* s_trig /*[12] LDS*/) {
   const int tid = threadIdx.x;
   if (tid < 6) {
@@ -101,7 +102,7 @@ DEV_INLINE PoseTerms pose_terms_coop(const double* p, double* s_trig /*[12] LDS*
 
 // Deterministic workgroup reduction of the 28 normal-equation scalars.  Each quad of lanes first adds its four
 // partials with two DPP quad_perm steps (no LDS), one lane per quad stores the sums k-major (conflict-free),
-// then a group of 8 / 16 lanes per scalar finishes (below).  The quad step keeps the LDS footprint at 28 x T/4 doubles
+// then a group of lanes per scalar finishes (below).  The quad step keeps the LDS footprint at 28 x T/4 doubles
 // (28 KB for 512 threads): these solver workgroups live for hundreds of microseconds, and their LDS is what keeps other
 // streams' workgroups off the CU.  (An earlier version let 4 threads per scalar add 32 entries each and a third stage add
 // the 4 sums: 30 % of lm_solve's time.)
@@ -112,110 +113,114 @@ DEV_INLINE double dpp_add_f64(double v) {   // v + (v of the lane selected by th
   const int plo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xF, 0xF, false), phi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xF, 0xF, false);
   return v + __longlong_as_double((long long)(((unsigned long long)(unsigned)phi << 32) | (unsigned)plo));
 }
-// T threads -> Q = T/4 partials per scalar after the quad step; G = Q/8 lanes per scalar (16 for 512 threads ... 2 for 64)
-// add 8 strided partials each and finish with log2(G) DPP steps inside their row: two barriers per reduction.
-template <int T>
-DEV_INLINE void block_reduce28_lds(const double acc[28], double* s_acc /*[28*T/4]*/, double* /*unused*/, double* s_out /*[28]*/) {
-  constexpr int Q = T / 4, G = Q / 8;
-  static_assert(G == 2 || G == 4 || G == 8 || G == 16, "64, 128, 256 or 512 threads");
+// PRE DPP steps come before LDS: 2 (the quad step above, 64 .. 512 threads) or 3 (a row_half_mirror step more: 14 KB for 512 threads; 128 .. 1024
+// threads — lm_solve keeps its residual rows in LDS, so every KB of reduction scratch is 20 rows streamed from the L2 instead).  Q = T >> PRE partials
+// per scalar; G = Q/8 lanes per scalar (16 ... 2) add 8 strided partials each and finish with log2(G) DPP steps inside their row: two barriers.
+template <int PRE>
+DEV_INLINE double block_reduce_head(double v) {
+  static_assert(PRE == 2 || PRE == 3, "a quad or eight lanes before LDS");
+  v = dpp_add_f64<0xB1>(v);                 // lane ^ 1: both lanes of a pair hold a + b (commutative: identical bits)
+  v = dpp_add_f64<0x4E>(v);                 // lane ^ 2: all four lanes hold (a + b) + (c + d)
+  if (PRE == 3) v = dpp_add_f64<0x141>(v);  // row_half_mirror: all eight lanes hold ((a + b) + (c + d)) + ((e + f) + (g + h))
+  return v;
+}
+template <int G>
+DEV_INLINE double block_reduce_tail(const double* s /* partials of one scalar, + the lane's index in its group */) {
+  static_assert(G == 2 || G == 4 || G == 8 || G == 16, "8 partials per lane, 2 .. 16 lanes per scalar");
+  double t = 0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) t += s[j * G];
+  t = dpp_add_f64<0xB1>(t);
+  if (G >= 4) t = dpp_add_f64<0x4E>(t);
+  if (G >= 8) t = dpp_add_f64<0x141>(t);   // row_half_mirror: the two quads of an 8-lane group
+  if (G == 16) t = dpp_add_f64<0x140>(t);  // row_mirror: the two halves of a row
+  return t;
+}
+template <int T, int PRE>
+DEV_INLINE void block_reduce28(const double acc[28], double* s_acc /*[28 * (T >> PRE)]*/, double* s_out /*[28]*/) {
+  constexpr int Q = T >> PRE, G = Q / 8;
   static_assert(28 * G <= T, "one lane group per scalar");
   const int tid = threadIdx.x;
 #pragma unroll
   for (int k = 0; k < 28; ++k) {
-    double v = dpp_add_f64<0xB1>(acc[k]);   // lane ^ 1: both lanes of a pair hold a + b (commutative: identical bits)
-    v = dpp_add_f64<0x4E>(v);               // lane ^ 2: all four lanes hold (a + b) + (c + d)
-    if ((tid & 3) == 0) s_acc[k * Q + (tid >> 2)] = v;
+    const double v = block_reduce_head<PRE>(acc[k]);
+    if ((tid & ((1 << PRE) - 1)) == 0) s_acc[k * Q + (tid >> PRE)] = v;
   }
   __syncthreads();
-  if (tid < 28 * G) {   // whole lane groups: the DPP steps below never leave a group
+  if (tid < 28 * G) {   // whole lane groups: the DPP steps of the tail never leave a group
     const int k = tid / G, g = tid - k * G;
-    double t = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) t += s_acc[k * Q + j * G + g];
-    t = dpp_add_f64<0xB1>(t);
-    if (G >= 4) t = dpp_add_f64<0x4E>(t);
-    if (G >= 8) t = dpp_add_f64<0x141>(t);   // row_half_mirror: the two quads of an 8-lane group
-    if (G == 16) t = dpp_add_f64<0x140>(t);  // row_mirror: the two halves of a row
+    const double t = block_reduce_tail<G>(s_acc + k * Q + g);
     if (g == 0) s_out[k] = t;
   }
   __syncthreads();
 }
-
-// The same with a third DPP step (row_half_mirror: the two quads of eight lanes) before LDS: 28 x T/8 doubles of scratch (14 KB for
-// 512 threads).  lm_solve keeps its residual rows in LDS, so every KB of reduction scratch is 20 rows streamed from the L2 instead.
-template <int T>
-DEV_INLINE void block_reduce28_oct(const double acc[28], double* s_acc /*[28*T/8]*/, double* s_out /*[28]*/) {
-  constexpr int Q = T / 8, G = Q / 8;
-  static_assert(G == 2 || G == 4 || G == 8 || G == 16, "128, 256, 512 or 1024 threads");
-  static_assert(28 * G <= T, "one lane group per scalar");
+// The reduction tree of scalar 27 (the cost) on its own: the same DPP steps, the same eight strided LDS partials per lane of a group of G, the
+// same DPP finish — s_out[27] is the double block_reduce28 delivers for the same per-thread partials (lanes [0, G) stand in for lanes
+// [27 G, 28 G): both groups start at a multiple of G, so every DPP step pairs the same partials).
+template <int T, int PRE>
+DEV_INLINE void block_reduce_cost(double cost, double* s_acc /*[T >> PRE]*/, double* s_out /*[28]*/) {
+  constexpr int G = (T >> PRE) / 8;
   const int tid = threadIdx.x;
-#pragma unroll
-  for (int k = 0; k < 28; ++k) {
-    double v = dpp_add_f64<0xB1>(acc[k]);
-    v = dpp_add_f64<0x4E>(v);
-    v = dpp_add_f64<0x141>(v);              // all eight lanes hold ((a + b) + (c + d)) + ((e + f) + (g + h))
-    if ((tid & 7) == 0) s_acc[k * Q + (tid >> 3)] = v;
-  }
-  __syncthreads();
-  if (tid < 28 * G) {
-    const int k = tid / G, g = tid - k * G;
-    double t = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) t += s_acc[k * Q + j * G + g];
-    t = dpp_add_f64<0xB1>(t);
-    if (G >= 4) t = dpp_add_f64<0x4E>(t);
-    if (G >= 8) t = dpp_add_f64<0x141>(t);
-    if (G == 16) t = dpp_add_f64<0x140>(t);
-    if (g == 0) s_out[k] = t;
-  }
-  __syncthreads();
-}
-
-// The reduction tree of scalar 27 (the cost) of block_reduce28_lds / block_reduce28_oct on its own: the same DPP steps, the same eight strided
-// LDS partials per lane of a group of G, the same DPP finish — s_out[27] is the double the 28-scalar reduction delivers for the same per-thread
-// partials (lanes [0, G) stand in for lanes [27 G, 28 G): both groups start at a multiple of G, so every DPP step pairs the same partials).
-template <int T>
-DEV_INLINE void block_reduce_cost_lds(double cost, double* s_acc /*[T/4]*/, double* s_out /*[28]*/) {
-  constexpr int Q = T / 4, G = Q / 8;
-  static_assert(G == 2 || G == 4 || G == 8 || G == 16, "64, 128, 256 or 512 threads");
-  const int tid = threadIdx.x;
-  double v = dpp_add_f64<0xB1>(cost);
-  v = dpp_add_f64<0x4E>(v);
-  if ((tid & 3) == 0) s_acc[tid >> 2] = v;
+  const double v = block_reduce_head<PRE>(cost);
+  if ((tid & ((1 << PRE) - 1)) == 0) s_acc[tid >> PRE] = v;
   __syncthreads();
   if (tid < G) {
-    double t = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) t += s_acc[j * G + tid];
-    t = dpp_add_f64<0xB1>(t);
-    if (G >= 4) t = dpp_add_f64<0x4E>(t);
-    if (G >= 8) t = dpp_add_f64<0x141>(t);
-    if (G == 16) t = dpp_add_f64<0x140>(t);
+    const double t = block_reduce_tail<G>(s_acc + tid);
     if (tid == 0) s_out[27] = t;
   }
   __syncthreads();
 }
-template <int T>
-DEV_INLINE void block_reduce_cost_oct(double cost, double* s_acc /*[T/8]*/, double* s_out /*[28]*/) {
-  constexpr int Q = T / 8, G = Q / 8;
-  static_assert(G == 2 || G == 4 || G == 8 || G == 16, "128, 256, 512 or 1024 threads");
-  const int tid = threadIdx.x;
-  double v = dpp_add_f64<0xB1>(cost);
-  v = dpp_add_f64<0x4E>(v);
-  v = dpp_add_f64<0x141>(v);
-  if ((tid & 7) == 0) s_acc[tid >> 3] = v;
-  __syncthreads();
-  if (tid < G) {
-    double t = 0;
+
+// ---- one evaluation and one solve by a workgroup of T threads (lo_solve_t, lm_solve, lm_shard_eval, lm_regcov) ----
+// The phases a -DALEGO_TIMING build clocks, in ticks per thread: lo_times[k] (wall clock) and lm_solve's ld[43 + k]; empty in the default build
+enum { WG_T_POSE = 0, WG_T_ROWS, WG_T_REDUCE, WG_T_CONTROL, WG_T_COUNT = 6 };
+template <bool WALL> struct WgClock {
+#ifdef ALEGO_TIMING
+  long long tm[WG_T_COUNT] = {0, 0, 0, 0, 0, 0}, t0 = 0;
+  DEV_INLINE static long long now() { return WALL ? (long long)wall_clock64() : (long long)clock64(); }
+  DEV_INLINE void begin() { t0 = now(); }
+  DEV_INLINE void end(int k) { tm[k] += now() - t0; }
+#else
+  DEV_INLINE void begin() {}
+  DEV_INLINE void end(int) {}
+#endif
+};
+
+// x -> s_out[28] (FULL) or s_out[27] alone: the pose terms, then rows(T, acc, std::bool_constant<FULL>) sums this thread's rows, then the reduction
+template <int T, int PRE, bool FULL, class Rows, class Clock>
+DEV_INLINE void wg_evaluate(const double* x, double* s_trig /*[12]*/, double* s_acc, double* s_out, Rows&& rows, Clock& ck) {
+  double acc[28];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) t += s_acc[j * G + tid];
-    t = dpp_add_f64<0xB1>(t);
-    if (G >= 4) t = dpp_add_f64<0x4E>(t);
-    if (G >= 8) t = dpp_add_f64<0x141>(t);
-    if (G == 16) t = dpp_add_f64<0x140>(t);
-    if (tid == 0) s_out[27] = t;
+  for (int k = 0; k < 28; ++k) acc[k] = 0;
+  ck.begin();
+  const PoseTerms P = pose_terms_coop(x, s_trig);
+  ck.end(WG_T_POSE);
+  ck.begin();
+  rows(P, acc, std::bool_constant<FULL>{});
+  ck.end(WG_T_ROWS);
+  ck.begin();
+  if constexpr (FULL) block_reduce28<T, PRE>(acc, s_acc, s_out); else block_reduce_cost<T, PRE>(acc[27], s_acc, s_out);
+  ck.end(WG_T_REDUCE);
+}
+
+// One ceres::Solve into S: evaluate what `kind` asks for, let thread 0 take the sums in and propose (lm_control), until the solve has ended.
+// kind: LM_EV_BEGIN (from x0) or LM_EV_AGAIN (from S.x, whose normal equations S still holds: no evaluation; LaserMapping alone enters it).
+template <int T, int PRE, bool FULL_EVAL, class Rows, class Clock>
+DEV_INLINE void wg_solve(LmState& S, int* s_action, int kind, const double* x0, int max_iter, double* s_trig, double* s_acc, double* s_out, Rows&& rows, Clock& ck) {
+  while (true) {
+    double x[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) x[k] = kind == LM_EV_BEGIN ? x0[k] : kind == LM_EV_JAC ? S.x[k] : kind == LM_EV_AGAIN ? 0.0 : S.cand[k];
+    if (kind == LM_EV_CAND_COST) wg_evaluate<T, PRE, false>(x, s_trig, s_acc, s_out, rows, ck);
+    else if (kind != LM_EV_AGAIN) wg_evaluate<T, PRE, true>(x, s_trig, s_acc, s_out, rows, ck);
+    ck.begin();
+    if (threadIdx.x == 0) *s_action = lm_control<FULL_EVAL, ALEGO_SOLVE_SPECULATE != 0>(S, kind, x0, s_out, max_iter);
+    __syncthreads();
+    ck.end(WG_T_CONTROL);
+    const int act = *s_action;
+    if (act == LM_STOP) break;
+    kind = lm_next_eval<FULL_EVAL>(act);   // (an evaluation and its barriers lie between this read of s_action and the next write)
   }
-  __syncthreads();
 }
 
 #endif

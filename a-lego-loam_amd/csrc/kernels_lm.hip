@@ -472,8 +472,7 @@ __global__ void __launch_bounds__(128) lm_knn(DevCtx d, LmCtx L) {
   const int* li = lip(L, slot);
   if (!li[LI_RUN]) return;
   const alego_params& P = d.P;
-  // registration guard :350
-  if (li[LI_NCUR_C] < P.lm_min_corner || li[LI_NTOTAL] < P.lm_min_surf || li[LI_KDS_C] < P.lm_min_map_corner || (li[LI_NKF] | li[LI_REC_CNT]) == 0) return;
+  if (lm_reg_skipped(li, P)) return;
   const int nq = kind == 0 ? li[LI_NCUR_C] : li[LI_NTOTAL_DS];
   int qlo, qhi;
   lm_shard_slice(L, li[LI_NCUR_C], li[LI_NTOTAL_DS], kind, &qlo, &qhi);
@@ -590,7 +589,7 @@ __global__ void __launch_bounds__(128) lm_knn(DevCtx d, LmCtx L) {
   }
   // neighbour indices (ascending distance) for lm_fit; idx[0] < 0 = rejected (:376,:426)
   if (sub == 0 && qq < nq) {
-    int* kn = L.knn + ((size_t)slot * L.qcap + (kind == 0 ? 0 : L.kf_cap_c) + q) * 5;
+    int* kn = lm_knn_of(L, slot, kind, q);
     const bool ok = bi[4] != -1 && (double)bd[4] < P.knn_max_dist && q >= qlo && q < qhi;   // (queries of other ranks' slices give no row here)
 #pragma unroll
     for (int k = 0; k < 5; ++k) kn[k] = ok ? bi[k] : -1;
@@ -608,16 +607,16 @@ __global__ void __launch_bounds__(128) lm_fit(DevCtx d, LmCtx L) {
   const int* li = lip(L, slot);
   if (!li[LI_RUN]) return;
   const alego_params& P = d.P;
-  if (li[LI_NCUR_C] < P.lm_min_corner || li[LI_NTOTAL] < P.lm_min_surf || li[LI_KDS_C] < P.lm_min_map_corner || (li[LI_NKF] | li[LI_REC_CNT]) == 0) return;
+  if (lm_reg_skipped(li, P)) return;
   const int nq = kind == 0 ? li[LI_NCUR_C] : li[LI_NTOTAL_DS];
   const float4* mp = kind == 0 ? L.map_corner_ds + (size_t)slot * L.map_cap_c : L.map_surf_ds + (size_t)slot * L.map_cap_s;
   for (int q = bx * 128 + threadIdx.x; q < nq; q += gx * 128) {
-  const int* kn = L.knn + ((size_t)slot * L.qcap + (kind == 0 ? 0 : L.kf_cap_c) + q) * 5;
-  double* blk = L.blocks + ((size_t)slot * L.qcap + (kind == 0 ? 0 : L.kf_cap_c) + q) * 8;
+  const int* kn = lm_knn_of(L, slot, kind, q);
+  double* blk = lm_blocks_of(L, slot) + lm_row_of(kind, q, L.kf_cap_c) * LMB_W;
   int bi[5];
 #pragma unroll
   for (int k = 0; k < 5; ++k) bi[k] = kn[k];
-  blk[7] = 0.0;
+  lmb_put_none(blk);
   do {
     if (bi[0] < 0) break;
   if (kind == 0) {  // :378-411
@@ -643,10 +642,10 @@ __global__ void __launch_bounds__(128) lm_fit(DevCtx d, LmCtx L) {
     double lam[3], v[3], lmid;
     d_eig3(cov, lam, v, &lmid);
     if (lam[2] > P.line_ratio * lam[1]) {
+      double pa[3], pb[3];
 #pragma unroll
-      for (int a = 0; a < 3; ++a) { blk[a] = P.line_half_len * v[a] + center[a]; blk[3 + a] = -P.line_half_len * v[a] + center[a]; }
-      blk[6] = 0.0;
-      blk[7] = 2.0;  // BLK_EDGE
+      for (int a = 0; a < 3; ++a) { pa[a] = P.line_half_len * v[a] + center[a]; pb[a] = -P.line_half_len * v[a] + center[a]; }
+      lmb_put_edge(blk, pa, pb);
     }
   } else {  // :424-460
     double A[3][5], b[5], nrm[3];
@@ -666,11 +665,7 @@ __global__ void __launch_bounds__(128) lm_fit(DevCtx d, LmCtx L) {
 #pragma unroll
     for (int j = 0; j < 5; ++j)
       if (fabs(nrm[0] * mx[j] + nrm[1] * my[j] + nrm[2] * mz[j] + dd) > P.plane_tol) ok = false;
-    if (ok) {
-      blk[0] = nrm[0]; blk[1] = nrm[1]; blk[2] = nrm[2]; blk[3] = 0; blk[4] = 0; blk[5] = 0;
-      blk[6] = dd;
-      blk[7] = 3.0;  // BLK_PLANE
-    }
+    if (ok) lmb_put_plane(blk, nrm, dd);
   }
   } while (false);
   }
@@ -680,8 +675,8 @@ __global__ void __launch_bounds__(128) lm_fit(DevCtx d, LmCtx L) {
 // Round 3: lm_solve used to pack its ~2.9 k accepted rows (80 B each = 230 KB per stream) into HBM and stream them through every one
 // of the ~30 evaluations of a mapping frame: 512 streams x 230 KB x 30 = 3.5 GB per launch out of the L2 / Infinity Cache, which is what
 // bounded the kernel (514 us per launch with the rows, 0.94 MB of HBM traffic per scan).  Now the rows live in LDS for the whole solve,
-// structure of arrays, edges (a, b: 6 f64 + the query point 3 f32 = 60 B) apart from planes (normal, d: 4 f64 + 3 f32 = 44 B): 143 KB
-// at 16 x 1800.  Rows beyond the workgroup's LDS budget stay in `crows` (80 B rows, edges at [0, Rc), planes behind them) and are read
+// structure of arrays, edges apart from planes (lm_rows.h: the layouts, 60 B and 44 B a row): 143 KB at 16 x 1800.  Rows beyond the
+// workgroup's LDS budget stay in `crows` as streamed records and are read
 // from there — same arithmetic, same order.  The compaction is STABLE in the query index (every thread takes a contiguous range of
 // queries), thread t evaluates edges t, t + T, ... and then planes t, t + T, ...: the summation order of the normal equations is a
 // function of the accepted-query lists alone, and lm_shard_eval (all rows in `crows`) follows the same order.
@@ -698,29 +693,21 @@ __global__ void __launch_bounds__(128) lm_fit(DevCtx d, LmCtx L) {
 #define LM_SOLVE_RED_BYTES ((size_t)28 * (LM_SOLVE_T / 8) * sizeof(double))
 #define LM_SOLVE_DYN_BYTES ((size_t)158 * 1024)   // upper limit (ALEGO_LM_ROW_LDS): of the CU's 160 KB; the kernel's static LDS (solver state, scan tables) is < 2 KB
 #define LM_SOLVE_ROW_BYTES_DEFAULT ((size_t)96 * 1024)
-struct LmRows {
-  int Rc, Rs;             // accepted corner (edge) / surf (plane) rows
-  int Ce, Cp;             // the first Ce edges / Cp planes are resident in LDS
-  double *ea, *eb, *pn;   // LDS: ea[k * Ce + i], eb[k * Ce + i] (k < 3); pn[k * Cp + j] (k < 4: normal, negative_OA_dot_norm)
-  float *ep, *pp;         // LDS: query points ep[k * Ce + i], pp[k * Cp + j] (k < 3)
-  double* crows;          // HBM: rows that do not fit (all of them on the sharded path)
-};
-
 template <int T>
 DEV_INLINE void lm_pack_rows(const LmCtx& L, int slot, int nqc, int nqs, unsigned char* row_lds, size_t row_budget, int (*s_cnt)[T / 64], LmRows& W) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const double* blocks = L.blocks + (size_t)slot * L.qcap * 8;
+  const double* blocks = lm_blocks_of(L, slot);
   const float4* qc = L.cur_corner_ds + (size_t)slot * L.kf_cap_c;
   const float4* qs = L.cur_total_ds + (size_t)slot * L.total_cap;
   const int n_all = nqc + nqs, per = (n_all + T - 1) / T;
   const int lo = min(tid * per, n_all), hi = min(lo + per, n_all);
-  auto qrow = [&](int i) -> size_t { return (size_t)(i < nqc ? i : L.kf_cap_c + (i - nqc)); };
+  auto block_of = [&](int i) { return blocks + lm_row_of_query(i, nqc, L.kf_cap_c) * LMB_W; };
   constexpr int U = 4;   // loads in flight per thread
   int cc = 0, cs = 0;
   for (int i0 = lo; i0 < hi; i0 += U) {
     double ty[U];
 #pragma unroll
-    for (int u = 0; u < U; ++u) ty[u] = blocks[qrow(min(i0 + u, n_all - 1)) * 8 + 7];
+    for (int u = 0; u < U; ++u) ty[u] = block_of(min(i0 + u, n_all - 1))[LMB_TYPE];
 #pragma unroll
     for (int u = 0; u < U; ++u) if (i0 + u < hi && ty[u] != 0.0) { if (i0 + u < nqc) ++cc; else ++cs; }
   }
@@ -730,41 +717,25 @@ DEV_INLINE void lm_pack_rows(const LmCtx& L, int slot, int nqc, int nqs, unsigne
   int epos = ic - cc, ppos = is - cs, Rc = 0, Rs = 0;
 #pragma unroll
   for (int w = 0; w < T / 64; ++w) { const int a = s_cnt[0][w], b = s_cnt[1][w]; if (w < wave) { epos += a; ppos += b; } Rc += a; Rs += b; }
-  W.Rc = Rc; W.Rs = Rs;
-  W.Ce = (int)min((size_t)Rc, row_budget / 60);
-  W.Cp = (int)min((size_t)Rs, (row_budget - (size_t)60 * W.Ce) / 44);
-  W.ea = reinterpret_cast<double*>(row_lds); W.eb = W.ea + 3 * (size_t)W.Ce; W.pn = W.eb + 3 * (size_t)W.Ce;
-  W.ep = reinterpret_cast<float*>(W.pn + 4 * (size_t)W.Cp); W.pp = W.ep + 3 * (size_t)W.Ce;
-  W.crows = L.crows + (size_t)slot * L.qcap * 10;
+  W = lml_make(Rc, Rs, row_lds, row_budget, lm_crows_of(L, slot));
   for (int i0 = lo; i0 < hi; i0 += U) {
-    double4 blo[U], bhi[U];
+    LmBlock B[U];
     float4 pt[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int i = min(i0 + u, n_all - 1);
-      const double4* b = reinterpret_cast<const double4*>(blocks + qrow(i) * 8);
-      blo[u] = b[0]; bhi[u] = b[1];
+      B[u] = lmb_load(block_of(i));
       pt[u] = i < nqc ? qc[i] : qs[i - nqc];
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int i = i0 + u;
-      if (i < hi && bhi[u].w != 0.0) {
+      if (i < hi && lmb_type(B[u]) != 0.0) {
         const bool is_c = i < nqc;
         const int r = is_c ? epos++ : ppos++;
-        if (is_c && r < W.Ce) {
-          W.ea[r] = blo[u].x; W.ea[W.Ce + r] = blo[u].y; W.ea[2 * W.Ce + r] = blo[u].z;
-          W.eb[r] = blo[u].w; W.eb[W.Ce + r] = bhi[u].x; W.eb[2 * W.Ce + r] = bhi[u].y;
-          W.ep[r] = pt[u].x; W.ep[W.Ce + r] = pt[u].y; W.ep[2 * W.Ce + r] = pt[u].z;
-        } else if (!is_c && r < W.Cp) {
-          W.pn[r] = blo[u].x; W.pn[W.Cp + r] = blo[u].y; W.pn[2 * W.Cp + r] = blo[u].z; W.pn[3 * W.Cp + r] = bhi[u].z;
-          W.pp[r] = pt[u].x; W.pp[W.Cp + r] = pt[u].y; W.pp[2 * W.Cp + r] = pt[u].z;
-        } else {
-          double2* o = reinterpret_cast<double2*>(W.crows + (size_t)(is_c ? r : Rc + r) * 10);   // 80 B rows: 16-byte aligned
-          o[0] = make_double2(blo[u].x, blo[u].y); o[1] = make_double2(blo[u].z, blo[u].w);
-          o[2] = make_double2(bhi[u].x, bhi[u].y); o[3] = make_double2(bhi[u].z, bhi[u].w);
-          *reinterpret_cast<float4*>(o + 4) = pt[u];
-        }
+        if (is_c && r < W.Ce) lml_put_edge(W, r, B[u], pt[u]);
+        else if (!is_c && r < W.Cp) lml_put_plane(W, r, B[u], pt[u]);
+        else lms_put(W.crows + (is_c ? lms_edge_at(r) : lms_plane_at(Rc, r)) * LMS_W, B[u], pt[u]);
       }
     }
   }
@@ -774,46 +745,32 @@ DEV_INLINE void lm_pack_rows(const LmCtx& L, int slot, int nqc, int nqs, unsigne
 
 // residuals + Jacobians of all rows at the pose of Tm, accumulated into this thread's 28 normal-equation scalars
 // (FULL = false: the residuals alone, into acc[27] — the cost of a candidate point; same rows, same order)
+// The two evaluations are lm_eval_edge / lm_eval_plane (lm_rows.h) written out: called from here, the same code behind a helper takes lm_solve
+// from 254 to 255 VGPRs and lm_shard_eval from 2 to 3 wavefronts per SIMD (profiles/r13_solver_rows.md).
 template <int T, bool FULL = true>
 DEV_INLINE void lm_eval_rows(const LmRows& W, const PoseTerms& Tm, double huber, double acc[28]) {
   const double c3[3] = {0, 0, 0};
-  for (int i = threadIdx.x; i < W.Rc; i += T) {   // EdgeCostFunction (utility.h:242-297)
-    double a3[3], b3[3], cp[3];
-    if (i < W.Ce) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) { a3[k] = W.ea[k * W.Ce + i]; b3[k] = W.eb[k * W.Ce + i]; cp[k] = (double)W.ep[k * W.Ce + i]; }
-    } else {
-      const double2* b = reinterpret_cast<const double2*>(W.crows + (size_t)i * 10);
-      const double2 q0 = b[0], q1 = b[1], q2 = b[2];
-      const float4 pc = *reinterpret_cast<const float4*>(b + 4);
-      a3[0] = q0.x; a3[1] = q0.y; a3[2] = q1.x; b3[0] = q1.y; b3[1] = q2.x; b3[2] = q2.y; cp[0] = pc.x; cp[1] = pc.y; cp[2] = pc.z;
-    }
+  for (int i = threadIdx.x; i < W.Rc; i += T) {
+    LmEdge e;
+    if (i < W.Ce) e = lml_edge(W, i); else e = lms_edge(W.crows + lms_edge_at(i) * LMS_W);
     if constexpr (FULL) {
       double res, J[6];
-      eval_block(BLK_EDGE, cp, a3, b3, c3, 0.0, Tm, &res, J);
+      eval_block(BLK_EDGE, e.p, e.a, e.b, c3, 0.0, Tm, &res, J);
       accumulate_block(res, J, huber, acc);
-    } else accumulate_cost(eval_block_residual<BLK_EDGE>(cp, a3, b3, c3, 0.0, Tm), huber, acc[27]);
+    } else accumulate_cost(eval_block_residual<BLK_EDGE>(e.p, e.a, e.b, c3, 0.0, Tm), huber, acc[27]);
   }
-  for (int j = threadIdx.x; j < W.Rs; j += T) {   // PlaneCostFunction (utility.h:299-349)
-    double a3[3], cp[3], dd;
-    if (j < W.Cp) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) { a3[k] = W.pn[k * W.Cp + j]; cp[k] = (double)W.pp[k * W.Cp + j]; }
-      dd = W.pn[3 * W.Cp + j];
-    } else {
-      const double2* b = reinterpret_cast<const double2*>(W.crows + (size_t)(W.Rc + j) * 10);
-      const double2 q0 = b[0], q1 = b[1], q3 = b[3];
-      const float4 pc = *reinterpret_cast<const float4*>(b + 4);
-      a3[0] = q0.x; a3[1] = q0.y; a3[2] = q1.x; dd = q3.x; cp[0] = pc.x; cp[1] = pc.y; cp[2] = pc.z;
-    }
+  for (int j = threadIdx.x; j < W.Rs; j += T) {
+    LmPlane p;
+    if (j < W.Cp) p = lml_plane(W, j); else p = lms_plane(W.crows + lms_plane_at(W.Rc, j) * LMS_W);
     if constexpr (FULL) {
       double res, J[6];
-      eval_block(BLK_PLANE, cp, a3, c3, c3, dd, Tm, &res, J);
+      eval_block(BLK_PLANE, p.p, p.n, c3, c3, p.d, Tm, &res, J);
       accumulate_block(res, J, huber, acc);
-    } else accumulate_cost(eval_block_residual<BLK_PLANE>(cp, a3, c3, c3, dd, Tm), huber, acc[27]);
+    } else accumulate_cost(eval_block_residual<BLK_PLANE>(p.p, p.n, c3, c3, p.d, Tm), huber, acc[27]);
   }
 }
 
+enum { LM_T_PACK = 4, LM_T_LD0 = 43 };   // -DALEGO_TIMING: the phases of lm_solve (dev_cost.h WG_T_*, and the pack) in ld[43 .. 47]
 // scan2MapOptimization's solver part, one workgroup per stream.
 // The normal equations are evaluated only where a step is computed from them: at the point a ceres::Solve starts from and at an adopted point
 // the solve goes on from.  A candidate is evaluated for its cost (a third of a full row's instructions and one scalar to reduce instead of 28)
@@ -829,8 +786,8 @@ DEV_INLINE void lm_solve_body(const DevCtx& d, const LmCtx& L) {
   if (!li[LI_RUN]) return;
   const alego_params& P = d.P;
   double* ld = ldp(L, slot);
-  if (li[LI_NCUR_C] < P.lm_min_corner || li[LI_NTOTAL] < P.lm_min_surf || li[LI_KDS_C] < P.lm_min_map_corner || (li[LI_NKF] | li[LI_REC_CNT]) == 0) {
-    if (threadIdx.x == 0) { li[LI_FLAGS] |= 16; li[LI_NCC] = 0; li[LI_NSC] = 0; li[LI_SUM0] = 0; li[LI_SUM1] = 0; }
+  if (lm_reg_skipped(li, P)) {
+    if (threadIdx.x == 0) lm_store_skipped(li);
     return;
   }
   extern __shared__ __attribute__((aligned(16))) unsigned char lm_smem[];
@@ -840,62 +797,25 @@ DEV_INLINE void lm_solve_body(const DevCtx& d, const LmCtx& L) {
   __shared__ int s_action, s_again, s_cnt[2][LM_SOLVE_T / 64];
   // ---- correspondence counts (:465) and the accepted rows, into LDS ----
   LmRows W;
-#ifdef ALEGO_TIMING
-  const long long cpack_ = clock64();
-#endif
+  WgClock<false> ck;
+  ck.begin();
   lm_pack_rows<LM_SOLVE_T>(L, slot, li[LI_NCUR_C], li[LI_NTOTAL_DS], lm_smem + LM_SOLVE_RED_BYTES, L.solve_row_bytes, s_cnt, W);
+  ck.end(LM_T_PACK);
   if (threadIdx.x == 0) { li[LI_NCC] = W.Rc; li[LI_NSC] = W.Rs; li[LI_OPTIMIZED] = 1; }
   const int R = W.Rc + W.Rs;
-  double acc[28];
-#ifdef ALEGO_TIMING
-  long long tm[5] = {0, 0, 0, 0, clock64() - cpack_};   // pose terms, rows, reduction, trust-region control (one thread), pack
-#define TM(k, expr) { const long long c_ = clock64(); expr; tm[k] += clock64() - c_; }
-#else
-#define TM(k, expr) { expr; }
-#endif
-  auto evaluate = [&](const double* x, auto full) {
-#pragma unroll
-    for (int k = 0; k < 28; ++k) acc[k] = 0;
-    PoseTerms T;
-    TM(0, T = pose_terms_coop(x, s_trig));
-    TM(1, (lm_eval_rows<LM_SOLVE_T, decltype(full)::value>(W, T, P.huber_delta, acc)));
-    if constexpr (decltype(full)::value) { TM(2, block_reduce28_oct<LM_SOLVE_T>(acc, s_acc, s_out)); }
-    else { TM(2, block_reduce_cost_oct<LM_SOLVE_T>(acc[27], s_acc, s_out)); }
-  };
-  const std::true_type full_eval{};
-  const std::false_type cost_eval{};
+  auto rows = [&](const PoseTerms& T, double* acc, auto full) { lm_eval_rows<LM_SOLVE_T, decltype(full)::value>(W, T, P.huber_delta, acc); };
   for (int outer = 0; outer < P.lm_outer_iters; ++outer) {  // :360 — identical correspondences both times
-    if (R == 0) {  // ceres::Solve on an empty problem is a no-op
-      if (threadIdx.x == 0 && outer < 2) {
-        li[LI_SUM0 + outer] = 4 << 16;
-        for (int k = 0; k < 6; ++k) ld[LD_PARAMS_IT + outer * 6 + k] = ld[LD_PARAMS + k];
-      }
+    if (R == 0) {
+      if (threadIdx.x == 0) lm_store_outer_empty(li, ld, outer);
       continue;
     }
     // (s_again: thread 0's verdict at the end of the outer iteration before, behind that iteration's closing barrier)
-    int kind = (!FULL_EVAL && outer > 0 && s_again) ? LM_EV_AGAIN : LM_EV_BEGIN;
-    while (true) {
-      double x[6];
-#pragma unroll
-      for (int k = 0; k < 6; ++k) x[k] = kind == LM_EV_BEGIN ? ld[LD_PARAMS + k] : kind == LM_EV_JAC ? S.x[k] : kind == LM_EV_AGAIN ? 0.0 : S.cand[k];
-      if (kind == LM_EV_CAND_COST) evaluate(x, cost_eval);
-      else if (kind != LM_EV_AGAIN) evaluate(x, full_eval);
-      TM(3, if (threadIdx.x == 0) s_action = (lm_control<FULL_EVAL, ALEGO_SOLVE_SPECULATE != 0>(S, kind, ld + LD_PARAMS, s_out, P.lm_max_iters)); __syncthreads());
-      const int act = s_action;
-      if (act == LM_STOP) break;
-      kind = lm_next_eval<FULL_EVAL>(act);   // (an evaluation and its barriers lie between this read of s_action and the next write)
-    }
+    wg_solve<LM_SOLVE_T, 3, FULL_EVAL>(S, &s_action, (!FULL_EVAL && outer > 0 && s_again) ? LM_EV_AGAIN : LM_EV_BEGIN, ld + LD_PARAMS, P.lm_max_iters, s_trig, s_acc, s_out, rows, ck);
     if (threadIdx.x == 0) {
 #ifdef ALEGO_TIMING
-      for (int k = 0; k < 5; ++k) ld[43 + k] = (double)tm[k];   // (accumulated over both outer iterations)
+      for (int k = 0; k <= LM_T_PACK; ++k) ld[LM_T_LD0 + k] = (double)ck.tm[k];   // (accumulated over both outer iterations)
 #endif
-#pragma unroll
-      for (int k = 0; k < 6; ++k) ld[LD_PARAMS + k] = S.x[k];
-      if (outer < 2) {
-        for (int k = 0; k < 6; ++k) ld[LD_PARAMS_IT + outer * 6 + k] = S.x[k];
-        ld[LD_COSTS + outer * 2] = S.initial_cost; ld[LD_COSTS + outer * 2 + 1] = S.x_cost;
-        li[LI_SUM0 + outer] = S.iter | (S.successful << 8) | (S.termination << 16);
-      }
+      lm_store_outer(li, ld, outer, S);
       s_again = S.jac_valid;   // a point adopted in the last permitted iteration has no normal equations yet: the next outer iteration evaluates it
     }
     __syncthreads();
@@ -908,12 +828,12 @@ __global__ void __launch_bounds__(LM_SOLVE_T) lm_solve_full_eval(DevCtx d, LmCtx
 // ---- covariance and degeneracy of the registration (alego_regcov_enable; reg_cov_math.h) -----------------------------
 // One full evaluation of the accepted rows at the solver's final point, then the 6x6 part on wave 0.  The rows are streamed once from where
 // lm_fit left them (L.blocks and the two query clouds), thread-strided over the QUERIES: thread t takes queries t, t + T, ... and the 28 sums
-// go through block_reduce28_oct, so the result is a function of the slot's rows alone.  (lm_solve packs the rows into LDS because it reads them
+// go through block_reduce28, so the result is a function of the slot's rows alone.  (lm_solve packs the rows into LDS because it reads them
 // ~30 times; one pass gains nothing from it.)
 struct RcSrc {
-  const double* blocks;      // [rows][8]: a / normal (3), b (3), d, type (0 = not accepted)
+  const double* blocks;      // block records (lm_rows.h)
   const float4 *qc, *qs;     // corner queries, surf queries
-  int nqc, nqs, surf_row0;   // query i < nqc: row i of blocks, else row surf_row0 + (i - nqc)
+  int nqc, nqs, surf_row0;   // query i of the nqc + nqs: row lm_row_of_query(i, nqc, surf_row0)
   const double* params;      // p[6]
 };
 static_assert(offsetof(alego_regcov, cost) == 24 && sizeof(alego_regcov) == 24 + 122 * sizeof(double), "rc_store_empty walks the record's doubles from `cost`");
@@ -1010,37 +930,21 @@ DEV_INLINE void rc_body(const RcSrc& S, double huber, const double* opt, int fra
   __shared__ double s_acc[28 * (T / 8)], s_out[28], s_trig[12], s_N[36];
   __shared__ int s_n[2];
   const int tid = threadIdx.x;
-  if (tid < 2) s_n[tid] = 0;
-  double acc[28];
-#pragma unroll
-  for (int k = 0; k < 28; ++k) acc[k] = 0;
-  const PoseTerms Tm = pose_terms_coop(S.params, s_trig);   // (its barrier also publishes the zeroed counters)
-  const double c3[3] = {0, 0, 0};
-  const int n_all = S.nqc + S.nqs;
-  int ne = 0, np = 0;
-  for (int q = tid; q < n_all; q += T) {
-    const bool is_c = q < S.nqc;
-    const size_t row = is_c ? (size_t)q : (size_t)S.surf_row0 + (size_t)(q - S.nqc);
-    const double4* b = reinterpret_cast<const double4*>(S.blocks + row * 8);
-    const double4 bhi = b[1];
-    if (bhi.w == 0.0) continue;
-    const double4 blo = b[0];
-    const float4 pt = is_c ? S.qc[q] : S.qs[q - S.nqc];
-    const double cp[3] = {pt.x, pt.y, pt.z}, a3[3] = {blo.x, blo.y, blo.z};
-    double res, J[6];
-    if (is_c) {   // EdgeCostFunction, as lm_eval_rows evaluates it
-      const double b3[3] = {blo.w, bhi.x, bhi.y};
-      eval_block(BLK_EDGE, cp, a3, b3, c3, 0.0, Tm, &res, J);
-      ++ne;
-    } else {      // PlaneCostFunction
-      eval_block(BLK_PLANE, cp, a3, c3, c3, bhi.z, Tm, &res, J);
-      ++np;
+  if (tid < 2) s_n[tid] = 0;   // (published by the barrier of the pose terms)
+  auto rows = [&](const PoseTerms& Tm, double* acc, auto) {
+    const int n_all = S.nqc + S.nqs;
+    int ne = 0, np = 0;
+    for (int q = tid; q < n_all; q += T) {
+      const LmBlock B = lmb_load(S.blocks + lm_row_of_query(q, S.nqc, S.surf_row0) * LMB_W);
+      if (lmb_type(B) == 0.0) continue;
+      if (q < S.nqc) { lm_eval_edge<true>(lm_edge_of(B, S.qc[q]), Tm, huber, acc); ++ne; }
+      else { lm_eval_plane<true>(lm_plane_of(B, S.qs[q - S.nqc]), Tm, huber, acc); ++np; }
     }
-    accumulate_block(res, J, huber, acc);
-  }
-  if (ne) atomicAdd(&s_n[0], ne);
-  if (np) atomicAdd(&s_n[1], np);
-  block_reduce28_oct<T>(acc, s_acc, s_out);   // (ends with a barrier: the counts are complete)
+    if (ne) atomicAdd(&s_n[0], ne);
+    if (np) atomicAdd(&s_n[1], np);
+  };
+  WgClock<false> ck;
+  wg_evaluate<T, 3, true>(S.params, s_trig, s_acc, s_out, rows, ck);   // (ends with a barrier: the counts are complete)
   if (tid >= 64) return;
   rc_tail(s_out, s_N, S.params, s_n[0], s_n[1], frame, opt, rec);
 }
@@ -1053,7 +957,7 @@ __global__ void __launch_bounds__(LM_SOLVE_T) lm_regcov(DevCtx d, LmCtx L) {
   if (!li[LI_RUN]) return;
   alego_regcov* rec = L.rc_rec + slot;
   if (!li[LI_OPTIMIZED]) { if (threadIdx.x < 64) rc_store_empty(rec, 0, 0, 0, li[LI_FRAME]); return; }
-  const RcSrc S{L.blocks + (size_t)slot * L.qcap * 8, L.cur_corner_ds + (size_t)slot * L.kf_cap_c, L.cur_total_ds + (size_t)slot * L.total_cap,
+  const RcSrc S{lm_blocks_of(L, slot), L.cur_corner_ds + (size_t)slot * L.kf_cap_c, L.cur_total_ds + (size_t)slot * L.total_cap,
                 li[LI_NCUR_C], li[LI_NTOTAL_DS], L.kf_cap_c, ldp(L, slot) + LD_PARAMS};
   rc_body<LM_SOLVE_T>(S, d.P.huber_delta, L.rc_opt, li[LI_FRAME], rec);
 }
@@ -1143,8 +1047,8 @@ DEV_INLINE void lm_shard_pack_dev(const DevCtx& d, const LmCtx& L, int slot) {
   if (threadIdx.x == 0) { ctl[0] = 0; ctl[1] = LM_STOP; ctl[2] = 1; ctl[3] = 0; ctl[4] = 1; ctl[5] = 0; }
   if (!li[LI_RUN]) return;
   const alego_params& P = d.P;
-  if (li[LI_NCUR_C] < P.lm_min_corner || li[LI_NTOTAL] < P.lm_min_surf || li[LI_KDS_C] < P.lm_min_map_corner || (li[LI_NKF] | li[LI_REC_CNT]) == 0) {
-    if (threadIdx.x == 0) { li[LI_FLAGS] |= 16; li[LI_NCC] = 0; li[LI_NSC] = 0; li[LI_SUM0] = 0; li[LI_SUM1] = 0; }
+  if (lm_reg_skipped(li, P)) {
+    if (threadIdx.x == 0) lm_store_skipped(li);
     return;
   }
   __shared__ int s_cnt[2][LM_SOLVE_T / 64];
@@ -1184,15 +1088,10 @@ __global__ void __launch_bounds__(LM_SOLVE_T) lm_shard_eval(DevCtx d, LmCtx L, i
   double x[6];
 #pragma unroll
   for (int k = 0; k < 6; ++k) x[k] = which == 0 ? ld[LD_PARAMS + k] : S->cand[k];
-  LmRows W{};
-  W.Rc = ctl[5]; W.Rs = ctl[0] - ctl[5];
-  W.crows = L.crows + (size_t)slot * L.qcap * 10;
-  double acc[28];
-#pragma unroll
-  for (int k = 0; k < 28; ++k) acc[k] = 0;
-  const PoseTerms T = pose_terms_coop(x, s_trig);
-  lm_eval_rows<LM_SOLVE_T>(W, T, d.P.huber_delta, acc);
-  block_reduce28_oct<LM_SOLVE_T>(acc, s_acc, s_out);
+  const LmRows W = lml_make(ctl[5], ctl[0] - ctl[5], nullptr, 0, lm_crows_of(L, slot));   // (nothing resident)
+  auto rows = [&](const PoseTerms& T, double* acc, auto) { lm_eval_rows<LM_SOLVE_T>(W, T, d.P.huber_delta, acc); };
+  WgClock<false> ck;
+  wg_evaluate<LM_SOLVE_T, 3, true>(x, s_trig, s_acc, s_out, rows, ck);
   double* part = L.shard_part + (size_t)slot * 32;
   if (threadIdx.x < 28) part[threadIdx.x] = s_out[threadIdx.x];
   if (threadIdx.x == 0 && which == 1) { part[28] = 0.0; part[29] = 0.0; }
@@ -1209,8 +1108,8 @@ DEV_INLINE void lm_shard_step_dev(const DevCtx& d, const LmCtx& L, int slot, int
   const int outer = ctl[3];
   if (first) {
     if (outer == 0) { li[LI_NCC] = (int)(red[28] + 0.5); li[LI_NSC] = (int)(red[29] + 0.5); }
-    if (li[LI_NCC] + li[LI_NSC] == 0) {   // ceres::Solve on an empty problem is a no-op
-      if (outer < 2) { li[LI_SUM0 + outer] = 4 << 16; for (int k = 0; k < 6; ++k) ld[LD_PARAMS_IT + outer * 6 + k] = ld[LD_PARAMS + k]; }
+    if (li[LI_NCC] + li[LI_NSC] == 0) {
+      lm_store_outer_empty(li, ld, outer);
       ctl[2] = 1; ctl[1] = LM_STOP;
       return;
     }
@@ -1227,12 +1126,7 @@ DEV_INLINE void lm_shard_step_dev(const DevCtx& d, const LmCtx& L, int slot, int
   ctl[1] = act;
   if (act == LM_STOP) {   // this outer iteration's ceres::Solve has returned
     ctl[2] = 1;
-    for (int k = 0; k < 6; ++k) ld[LD_PARAMS + k] = S.x[k];
-    if (outer < 2) {
-      for (int k = 0; k < 6; ++k) ld[LD_PARAMS_IT + outer * 6 + k] = S.x[k];
-      ld[LD_COSTS + outer * 2] = S.initial_cost; ld[LD_COSTS + outer * 2 + 1] = S.x_cost;
-      li[LI_SUM0 + outer] = S.iter | (S.successful << 8) | (S.termination << 16);
-    }
+    lm_store_outer(li, ld, outer, S);
   }
 }
 
@@ -1318,17 +1212,13 @@ void regcov_host(const double* acc28, const double* params6, int n_edge, int n_p
 void regcov_normal_host(const double* params6, const double* edge_rows9, int n_edge, const double* plane_rows7, int n_plane, double huber, double* acc28) {
   for (int k = 0; k < 28; ++k) acc28[k] = 0.0;
   const PoseTerms Tm = pose_terms(params6);
-  const double c3[3] = {0, 0, 0};
-  double res, J[6];
   for (int i = 0; i < n_edge; ++i) {
     const double* r = edge_rows9 + (size_t)i * 9;
-    eval_block(BLK_EDGE, r + 6, r, r + 3, c3, 0.0, Tm, &res, J);
-    accumulate_block(res, J, huber, acc28);
+    lm_eval_edge<true>(LmEdge{{r[0], r[1], r[2]}, {r[3], r[4], r[5]}, {r[6], r[7], r[8]}}, Tm, huber, acc28);
   }
   for (int i = 0; i < n_plane; ++i) {
     const double* r = plane_rows7 + (size_t)i * 7;
-    eval_block(BLK_PLANE, r + 4, r, c3, c3, r[3], Tm, &res, J);
-    accumulate_block(res, J, huber, acc28);
+    lm_eval_plane<true>(LmPlane{{r[0], r[1], r[2]}, r[3], {r[4], r[5], r[6]}}, Tm, huber, acc28);
   }
 }
 void launch_lm_regcov_debug(const double* blocks, const float4* qc, int n_edge, const float4* qs, int n_plane, const double* params, double huber, const double* opt,

@@ -536,48 +536,55 @@ __global__ void __launch_bounds__(LO_BLOCK) lo_assoc(DevCtx d, int box_lds_max) 
   lo_assoc_body<kind, LO_BLOCK, BOXCAP>(d, box_lds_max, blockIdx.x + d.slot0, blockIdx.y, gridDim.y);   // slot fastest: a stream's workgroups share an XCD / L2 (see lm_knn)
 }
 
-// evaluate every valid correspondence row of [row0, row0+n) at pose p (FULL = false: the residuals alone, into acc[27])
-// (GENERIC: accumulate_block for every row, as the solver before the split; otherwise the accumulators of the block type's non-zero columns)
-template <int BLK, bool FULL = true, bool GENERIC = true>
-DEV_INLINE void lo_eval_rows(const DevCtx& d, int slot, int kind, int n, const PoseTerms& T, double acc[28]) {
-  const int qk = kind == 0 ? F_FLAT : F_SHARP, tk = kind == 0 ? F_LFLAT : F_LSHARP;
-  const float4* qpts = feat_of(d, qk, fidx_cur(d, slot));
-  const float4* tg = feat_of(d, tk, fidx_last(d, slot));
+// The points of correspondence row r of `kind` (0 surf, 1 corner): the query point, the targets a and b, and m (surf rows alone; a corner row
+// reads entry 0 for it and never uses it).  ok = false: a row without a correspondence, every index replaced by 0.
+struct LoRowPts { float4 c, a, b, m; };
+DEV_INLINE LoRowPts lo_row_points(const float4* qpts, const float4* tg, const int4& r, int kind, bool ok) {
+  return LoRowPts{qpts[ok ? r.x : 0], tg[ok ? r.y : 0], tg[ok ? r.z : 0], tg[(ok && kind == 0) ? r.w : 0]};
+}
+// SurfCostFunction / CornerCostFunction of one row at the pose of T (FULL = false: the residual alone, into acc[27])
+// (GENERIC: accumulate_block, as the solver before the split; otherwise the accumulators of the block type's non-zero columns)
+template <int kind, bool FULL, bool GENERIC>
+DEV_INLINE void lo_eval_row(const double cp[3], const double a[3], const double b[3], const double c[3], const PoseTerms& T, double huber, double acc[28]) {
+  if constexpr (FULL) {
+    double res, J[6];
+    eval_block(kind == 0 ? BLK_SURF : BLK_CORNER, cp, a, b, c, 0.0, T, &res, J);
+    if constexpr (GENERIC) accumulate_block(res, J, huber, acc);
+    else accumulate_block_cols<kind == 0 ? COLS_SURF : COLS_CORNER>(res, J, huber, acc);
+  } else accumulate_cost(eval_block_residual<kind == 0 ? BLK_SURF : BLK_CORNER>(cp, a, b, c, 0.0, T), huber, acc[27]);
+}
+// evaluate every valid correspondence row of [0, n) of `kind`, from where lo_assoc left them
+template <int BLK, int kind, bool FULL = true, bool GENERIC = true>
+DEV_INLINE void lo_eval_rows(const DevCtx& d, int slot, int n, const PoseTerms& T, double acc[28]) {
+  const float4* qpts = feat_of(d, kind == 0 ? F_FLAT : F_SHARP, fidx_cur(d, slot));
+  const float4* tg = feat_of(d, kind == 0 ? F_LFLAT : F_LSHARP, fidx_last(d, slot));
   const int* rows = lo_corr_of(d, slot, kind);
   for (int i = threadIdx.x; i < n; i += BLK) {
     const int4 r = *reinterpret_cast<const int4*>(rows + (size_t)i * LC_W);
     if (r.y < 0) continue;
-    const float4 pc = qpts[r.x], pa = tg[r.y], pb = tg[r.z];
-    const double cp[3] = {pc.x, pc.y, pc.z}, a[3] = {pa.x, pa.y, pa.z}, b[3] = {pb.x, pb.y, pb.z};
-    double c[3] = {0, 0, 0};
-    if (kind == 0) { const float4 pm = tg[r.w]; c[0] = pm.x; c[1] = pm.y; c[2] = pm.z; }
-    if constexpr (FULL) {
-      double res, J[6];
-      eval_block(kind == 0 ? BLK_SURF : BLK_CORNER, cp, a, b, c, 0.0, T, &res, J);
-      if constexpr (GENERIC) accumulate_block(res, J, d.P.huber_delta, acc);
-      else if (kind == 0) accumulate_block_cols<COLS_SURF>(res, J, d.P.huber_delta, acc);
-      else accumulate_block_cols<COLS_CORNER>(res, J, d.P.huber_delta, acc);
-    } else accumulate_cost(kind == 0 ? eval_block_residual<BLK_SURF>(cp, a, b, c, 0.0, T) : eval_block_residual<BLK_CORNER>(cp, a, b, c, 0.0, T), d.P.huber_delta, acc[27]);
+    const LoRowPts p = lo_row_points(qpts, tg, r, kind, true);
+    const double cp[3] = {p.c.x, p.c.y, p.c.z}, a[3] = {p.a.x, p.a.y, p.a.z}, b[3] = {p.b.x, p.b.y, p.b.z};
+    const double c[3] = {kind == 0 ? (double)p.m.x : 0.0, kind == 0 ? (double)p.m.y : 0.0, kind == 0 ? (double)p.m.z : 0.0};
+    lo_eval_row<kind, FULL, GENERIC>(cp, a, b, c, T, d.P.huber_delta, acc);
   }
 }
 
 // phase 0: ceres::Solve #1 on the surf blocks (:410-421); phase 1: Solve #2 on surf + corner
 // blocks (:484-495) followed by the pose integration (:504-508).
+// -DALEGO_TIMING: wall-clock ticks of thread 0 of the launch's first slot.  lo_times[0 .. 3]: the phases of an evaluation and the control
+// (dev_cost.h WG_T_*; staging counts as rows), 5: the pose rotation, 6: the whole kernel, 7: calls; slot 4 is not written
+enum { LO_T_STAGE = WG_T_ROWS, LO_T_ROTATION = 5, LO_T_KERNEL = 6, LO_T_CALLS = 7 };
 #ifdef ALEGO_TIMING
 __device__ long long lo_times[8];
 extern "C" void alego_lo_times(long long* out) { (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(lo_times), sizeof(long long) * 8); }
-#define LO_T0 const long long t0_ = wall_clock64()
-#define LO_ACC(k) do { if (threadIdx.x == 0 && slot == d.slot0) lo_times[k] += wall_clock64() - t0_; } while (0)
-#else
-#define LO_T0
-#define LO_ACC(k)
 #endif
 // The correspondence rows of a solve do not change between its evaluations (six per ceres::Solve): the points of the rows are
 // gathered ONCE into LDS (structure of arrays: lane-consecutive rows read consecutive words) instead of from HBM / L2 on every
 // evaluation (four dependent loads per row and evaluation: 20 of lo_solve's 53 us for one stream).  Rows keep their order, so
 // every thread sums the same rows in the same order as lo_eval_rows does.  Problems with more than LO_LDS_ROWS rows stream.
 #define LO_LDS_ROWS 640   // >= n_flat * n_sectors * 16 rings + n_sharp * n_sectors * 16 rings at the reference's parameters (576)
-struct LoRowsLds { float v[12][LO_LDS_ROWS]; };   // c xyz, a xyz, b xyz, m xyz
+struct LoRowsLds { float cx[LO_LDS_ROWS], cy[LO_LDS_ROWS], cz[LO_LDS_ROWS], ax[LO_LDS_ROWS], ay[LO_LDS_ROWS], az[LO_LDS_ROWS],
+                         bx[LO_LDS_ROWS], by[LO_LDS_ROWS], bz[LO_LDS_ROWS], mx[LO_LDS_ROWS], my[LO_LDS_ROWS], mz[LO_LDS_ROWS]; };
 template <int BLK>
 DEV_INLINE void lo_stage_rows(const DevCtx& d, int slot, int kind, int n, int off, LoRowsLds& R, unsigned& okm) {
   const int qk = kind == 0 ? F_FLAT : F_SHARP, tk = kind == 0 ? F_LFLAT : F_LSHARP;
@@ -589,10 +596,10 @@ DEV_INLINE void lo_stage_rows(const DevCtx& d, int slot, int kind, int n, int of
   for (int i = threadIdx.x; i < n; i += BLK, ++k) {
     const int4 r = *reinterpret_cast<const int4*>(rows + (size_t)i * LC_W);
     const bool ok = r.y >= 0;
-    const float4 pc = qpts[ok ? r.x : 0], pa = tg[ok ? r.y : 0], pb = tg[ok ? r.z : 0], pm = tg[(ok && kind == 0) ? r.w : 0];
+    const LoRowPts p = lo_row_points(qpts, tg, r, kind, ok);
     const int j = off + i;
-    R.v[0][j] = pc.x; R.v[1][j] = pc.y; R.v[2][j] = pc.z; R.v[3][j] = pa.x; R.v[4][j] = pa.y; R.v[5][j] = pa.z;
-    R.v[6][j] = pb.x; R.v[7][j] = pb.y; R.v[8][j] = pb.z; R.v[9][j] = pm.x; R.v[10][j] = pm.y; R.v[11][j] = pm.z;
+    R.cx[j] = p.c.x; R.cy[j] = p.c.y; R.cz[j] = p.c.z; R.ax[j] = p.a.x; R.ay[j] = p.a.y; R.az[j] = p.a.z;
+    R.bx[j] = p.b.x; R.by[j] = p.b.y; R.bz[j] = p.b.z; R.mx[j] = p.m.x; R.my[j] = p.m.y; R.mz[j] = p.m.z;
     if (ok) okm |= 1u << k;
   }
 }
@@ -602,14 +609,9 @@ DEV_INLINE void lo_eval_staged(int n, int off, const LoRowsLds& R, unsigned okm,
   for (int i = threadIdx.x; i < n; i += BLK, ++k) {
     if (!((okm >> k) & 1u)) continue;
     const int j = off + i;
-    const double cp[3] = {R.v[0][j], R.v[1][j], R.v[2][j]}, a[3] = {R.v[3][j], R.v[4][j], R.v[5][j]}, b[3] = {R.v[6][j], R.v[7][j], R.v[8][j]};
-    const double c[3] = {kind == 0 ? (double)R.v[9][j] : 0.0, kind == 0 ? (double)R.v[10][j] : 0.0, kind == 0 ? (double)R.v[11][j] : 0.0};
-    if constexpr (FULL) {
-      double res, J[6];
-      eval_block(kind == 0 ? BLK_SURF : BLK_CORNER, cp, a, b, c, 0.0, T, &res, J);
-      if constexpr (GENERIC) accumulate_block(res, J, huber, acc);
-      else accumulate_block_cols<kind == 0 ? COLS_SURF : COLS_CORNER>(res, J, huber, acc);
-    } else accumulate_cost(eval_block_residual<kind == 0 ? BLK_SURF : BLK_CORNER>(cp, a, b, c, 0.0, T), huber, acc[27]);
+    const double cp[3] = {R.cx[j], R.cy[j], R.cz[j]}, a[3] = {R.ax[j], R.ay[j], R.az[j]}, b[3] = {R.bx[j], R.by[j], R.bz[j]};
+    const double c[3] = {kind == 0 ? (double)R.mx[j] : 0.0, kind == 0 ? (double)R.my[j] : 0.0, kind == 0 ? (double)R.mz[j] : 0.0};
+    lo_eval_row<kind, FULL, GENERIC>(cp, a, b, c, T, huber, acc);
   }
 }
 
@@ -621,8 +623,7 @@ DEV_INLINE void lo_solve_body(const DevCtx& d, int phase, int slot) {
   int* sc = scal_of(d, slot);
   double* st = lo_state_of(d, slot);
   extern __shared__ __attribute__((aligned(16))) unsigned char lo_smem[];
-  double* s_acc = reinterpret_cast<double*>(lo_smem);                // [28][BLK]
-  double* s_seg = s_acc + 28 * (BLK / 4);                        // [28][BLK/128]
+  double* s_acc = reinterpret_cast<double*>(lo_smem);                // [28][BLK / 4]
   __shared__ double s_out[28], s_trig[12];
   __shared__ LmState S;
   __shared__ int s_action, s_cnt[BLK / 64];
@@ -634,9 +635,9 @@ DEV_INLINE void lo_solve_body(const DevCtx& d, int phase, int slot) {
     }
     return;
   }
+  WgClock<true> ck;
 #ifdef ALEGO_TIMING
   const long long tk0_ = wall_clock64();
-  if (threadIdx.x == 0 && slot == d.slot0) lo_times[7] += 1;
 #endif
   const int nq_s = feat_cnt_of(d, fidx_cur(d, slot))[F_FLAT];
   const int nq_c = feat_cnt_of(d, fidx_cur(d, slot))[F_SHARP];
@@ -661,54 +662,29 @@ DEV_INLINE void lo_solve_body(const DevCtx& d, int phase, int slot) {
   }
   const bool do_solve = s_cnt[0] >= d.P.lo_min_corr;
   if (do_solve) {
-    double acc[28];
     unsigned oks = 0, okc = 0;
     if constexpr (STAGED) {
-      LO_T0;
+      ck.begin();
       lo_stage_rows<BLK>(d, slot, 0, nq_s, 0, s_rows, oks);
       if (phase == 1) lo_stage_rows<BLK>(d, slot, 1, nq_c, nq_s, s_rows, okc);
-      LO_ACC(1);
+      ck.end(LO_T_STAGE);
       // (every thread reads back only what it wrote itself: no barrier needed)
     }
-    auto evaluate = [&](const double* x, auto full) {
+    auto rows = [&](const PoseTerms& T, double* acc, auto full) {
       constexpr bool FULL = decltype(full)::value;
-#pragma unroll
-      for (int k = 0; k < 28; ++k) acc[k] = 0;
-      PoseTerms T;
-      { LO_T0; T = pose_terms_coop(x, s_trig); LO_ACC(0); }
-      { LO_T0;
-        if constexpr (STAGED) {
-          lo_eval_staged<BLK, 0, FULL, FULL_EVAL>(nq_s, 0, s_rows, oks, T, d.P.huber_delta, acc);
-          if (phase == 1) lo_eval_staged<BLK, 1, FULL, FULL_EVAL>(nq_c, nq_s, s_rows, okc, T, d.P.huber_delta, acc);
-        } else {
-          lo_eval_rows<BLK, FULL, FULL_EVAL>(d, slot, 0, nq_s, T, acc);
-          if (phase == 1) lo_eval_rows<BLK, FULL, FULL_EVAL>(d, slot, 1, nq_c, T, acc);
-        }
-        LO_ACC(1); }
-      { LO_T0;
-        if constexpr (FULL) block_reduce28_lds<BLK>(acc, s_acc, s_seg, s_out); else block_reduce_cost_lds<BLK>(acc[27], s_acc, s_out);
-        LO_ACC(2); }
+      if constexpr (STAGED) {
+        lo_eval_staged<BLK, 0, FULL, FULL_EVAL>(nq_s, 0, s_rows, oks, T, d.P.huber_delta, acc);
+        if (phase == 1) lo_eval_staged<BLK, 1, FULL, FULL_EVAL>(nq_c, nq_s, s_rows, okc, T, d.P.huber_delta, acc);
+      } else {
+        lo_eval_rows<BLK, 0, FULL, FULL_EVAL>(d, slot, nq_s, T, acc);
+        if (phase == 1) lo_eval_rows<BLK, 1, FULL, FULL_EVAL>(d, slot, nq_c, T, acc);
+      }
     };
-    const std::true_type full_eval{};
-    const std::false_type cost_eval{};
-    int kind = LM_EV_BEGIN;
-    while (true) {
-      double x[6];
-#pragma unroll
-      for (int k = 0; k < 6; ++k) x[k] = kind == LM_EV_BEGIN ? st[LS_PARAMS + k] : kind == LM_EV_JAC ? S.x[k] : S.cand[k];
-      if (kind == LM_EV_CAND_COST) evaluate(x, cost_eval);
-      else evaluate(x, full_eval);
-      { LO_T0;
-        if (threadIdx.x == 0) s_action = lm_control<FULL_EVAL, ALEGO_SOLVE_SPECULATE != 0>(S, kind, st + LS_PARAMS, s_out, phase == 0 ? d.P.lo_iters_surf : d.P.lo_iters_corner);
-        __syncthreads(); LO_ACC(3); }
-      const int act = s_action;
-      if (act == LM_STOP) break;
-      kind = lm_next_eval<FULL_EVAL>(act);   // (an evaluation and its barriers lie between this read of s_action and the next write)
-    }
+    wg_solve<BLK, 2, FULL_EVAL>(S, &s_action, LM_EV_BEGIN, st + LS_PARAMS, phase == 0 ? d.P.lo_iters_surf : d.P.lo_iters_corner, s_trig, s_acc, s_out, rows, ck);
     if (threadIdx.x == 0) {
 #pragma unroll
       for (int k = 0; k < 6; ++k) st[LS_PARAMS + k] = S.x[k];
-      { LO_T0; store_pose_rotation(st); LO_ACC(5); }   // for the next lo_assoc (corner association / next scan)
+      ck.begin(); store_pose_rotation(st); ck.end(LO_T_ROTATION);   // for the next lo_assoc (corner association / next scan)
       st[LS_COSTS + phase * 2] = S.initial_cost; st[LS_COSTS + phase * 2 + 1] = S.x_cost;
       sc[phase == 0 ? SC_LO_ITERS : SC_LO_ITERS2] = S.iter | (S.successful << 8) | (S.termination << 16);
     }
@@ -745,7 +721,10 @@ DEV_INLINE void lo_solve_body(const DevCtx& d, int phase, int slot) {
     }
   }
 #ifdef ALEGO_TIMING
-  if (threadIdx.x == 0 && slot == d.slot0) lo_times[6] += wall_clock64() - tk0_;
+  if (threadIdx.x == 0 && slot == d.slot0) {
+    for (int k = 0; k < WG_T_COUNT; ++k) lo_times[k] += ck.tm[k];
+    lo_times[LO_T_KERNEL] += wall_clock64() - tk0_; lo_times[LO_T_CALLS] += 1;
+  }
 #endif
 }
 
@@ -789,7 +768,7 @@ void launch_dbg_transform_to_start(const double* params6, const float4* pts, int
   hipLaunchKernelGGL(dbg_transform_to_start, dim3((n + 63) / 64), dim3(64), 0, st, params6, pts, n, out);
 }
 
-#define LO_SOLVE_LDS_OF(B) ((size_t)(28 * ((B) / 4) + 28 * ((B) / 128 + 1)) * sizeof(double))
+#define LO_SOLVE_LDS_OF(B) ((size_t)(28 * ((B) / 4)) * sizeof(double))   // block_reduce28<B, 2>
 #define LO_SOLVE_WIDE 256   // solver workgroup of sensors with more than LO_WIDE_ROWS correspondence rows (64 rings: ~1.5 k rows, 23 per lane of one wavefront)
 #define LO_WIDE_ROWS 1024
 int lo_configure() {

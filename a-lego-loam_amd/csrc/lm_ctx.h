@@ -2,6 +2,7 @@
 #ifndef ALEGO_LM_CTX_H_
 #define ALEGO_LM_CTX_H_
 #include "dev_common.h"
+#include "lm_rows.h"
 
 enum {
   LI_NKF = 0,      // key frames saved so far (cloud_keyposes_3d_->size())
@@ -144,10 +145,10 @@ struct LmCtx {
   float4* cell_pts;                               // [slot][2][map_cap_s] map points in cell order (w = index in the ds map)
   const unsigned* vox_bbox;                       // VoxCtx::bbox of round 1 of this stream group (the map VoxelGrid context: jobs (slot-vox_slot0)*2 + {0,1})
   int vox_slot0;                                  // first slot of the stream group
-  int* knn;                                       // [slot][qcap][5] neighbour indices of every query (lm_knn -> lm_fit)
+  int* knn;                                       // [slot][qcap][LM_KNN_W] neighbour indices of every query, at the rows of `blocks` (lm_knn -> lm_fit)
   // residual blocks
-  double* blocks;                                 // [slot][qcap][8]: a/normal (3), b (3), d, type (0 = none)
-  double* crows;                                  // [slot][qcap][10]: accepted rows that do not fit lm_solve's LDS (all rows on the sharded path): the 8 doubles above + the query point (float4)
+  double* blocks;                                 // [slot][qcap][LMB_W]: the block record of every query (lm_rows.h)
+  double* crows;                                  // [slot][qcap][LMS_W]: accepted rows that do not fit lm_solve's LDS (all rows on the sharded path), as streamed records (lm_rows.h)
   // key-frame archive (alego_map_enable; arc_frames_cap == 0: off, nothing is launched): EVERY key frame of a slot as the ring stores it
   // (sensor frame, kf_raw_* / kf_cnt) + its f32 key pose, appended by map_archive behind lm_store_kf; the stored frames are always a prefix
   int arc_frames_cap, arc_points_cap;             // per slot
@@ -173,6 +174,35 @@ struct LmCtx {
   const double* rc_opt;                           // [RC_OPT_W] the resolved options (reg_cov_math.h)
   int rc_graph;                                   // 1: map_archive writes a fresh record's variances into the odometry edge it records
 };
+
+// a slot's rows (lm_rows.h: a corner query q has row q, a surf query q row kf_cap_c + q)
+DEV_INLINE double* lm_blocks_of(const LmCtx& L, int slot) { return L.blocks + (size_t)slot * L.qcap * LMB_W; }
+DEV_INLINE double* lm_crows_of(const LmCtx& L, int slot) { return L.crows + (size_t)slot * L.qcap * LMS_W; }
+DEV_INLINE int* lm_knn_of(const LmCtx& L, int slot, int kind, int q) { return L.knn + ((size_t)slot * L.qcap + lm_row_of(kind, q, L.kf_cap_c)) * LM_KNN_W; }
+
+// The registration guard (:350) of lm_knn, lm_fit and both solver paths ("no map yet": see kernels_lm.hip), and what the solver path leaves of a
+// skipped registration
+DEV_INLINE bool lm_reg_skipped(const int* li, const alego_params& P) {
+  return lm_guard_fails(li[LI_NCUR_C], li[LI_NTOTAL], li[LI_KDS_C], (li[LI_NKF] | li[LI_REC_CNT]) == 0, P.lm_min_corner, P.lm_min_surf, P.lm_min_map_corner);
+}
+DEV_INLINE void lm_store_skipped(int* li) { li[LI_FLAGS] |= 16; li[LI_NCC] = 0; li[LI_NSC] = 0; li[LI_SUM0] = 0; li[LI_SUM1] = 0; }
+// one thread, when outer iteration `outer` has ended: params_ and the summaries of its ceres::Solve ...
+DEV_INLINE void lm_store_outer(int* li, double* ld, int outer, const LmState& S) {
+#pragma unroll
+  for (int k = 0; k < 6; ++k) ld[LD_PARAMS + k] = S.x[k];
+  if (outer < 2) {
+    for (int k = 0; k < 6; ++k) ld[LD_PARAMS_IT + outer * 6 + k] = S.x[k];
+    ld[LD_COSTS + outer * 2] = S.initial_cost; ld[LD_COSTS + outer * 2 + 1] = S.x_cost;
+    li[LI_SUM0 + outer] = S.iter | (S.successful << 8) | (S.termination << 16);
+  }
+}
+// ... and of one without rows: ceres::Solve on an empty problem is a no-op
+DEV_INLINE void lm_store_outer_empty(int* li, double* ld, int outer) {
+  if (outer < 2) {
+    li[LI_SUM0 + outer] = 4 << 16;
+    for (int k = 0; k < 6; ++k) ld[LD_PARAMS_IT + outer * 6 + k] = ld[LD_PARAMS + k];
+  }
+}
 
 // host entry points of LaserMapping's kernels (kernels_lm.hip, then kernels_map.hip and kernels_loc.hip), called by lm_host.hip; lm_configure: by alego_create
 size_t lm_solve_row_bytes_max(), lm_solve_row_bytes_default();

@@ -161,7 +161,7 @@ LmHost* lm_host_create(const alego_params& P, const DevCtx& d, int n_slots, int 
   ok = ok && A(lm, &L.cur_total, B * L.total_cap, err) && A(lm, &L.cur_total_ds, B * L.total_cap, err);
   ok = ok && A(lm, &L.grid, B * 2, err) && A(lm, &L.cell_start, B * 2 * ((size_t)L.gcap + 1), err) && A(lm, &L.cell_cur, B * 2 * ((size_t)L.gcap + 1), err);
   ok = ok && A(lm, &L.cell_pts, B * 2 * L.map_cap_s, err);
-  ok = ok && A(lm, &L.blocks, B * L.qcap * 8, err) && A(lm, &L.crows, B * L.qcap * 10, err) && A(lm, &L.knn, B * L.qcap * 5, err);
+  ok = ok && A(lm, &L.blocks, B * L.qcap * LMB_W, err) && A(lm, &L.crows, B * L.qcap * LMS_W, err) && A(lm, &L.knn, B * L.qcap * LM_KNN_W, err);   // (lm_rows.h)
   if (!ok) { lm_host_destroy(lm); return nullptr; }
   // identity quaternions (laserMapping.cpp:56-61)
   std::vector<double> ld(B * LD_COUNT, 0.0);
@@ -629,8 +629,8 @@ int lm_host_debug_get(LmHost* lm, int slot, const char* name, void* out, int cap
   else if (s == "lm_surf_ds") set(L.cur_surf_ds + b * L.kf_cap_s, (size_t)li[LI_NCUR_S] * 4, 0);
   else if (s == "lm_outlier_ds") set(L.cur_outl_ds + b * L.kf_cap_o, (size_t)li[LI_NCUR_O] * 4, 0);
   else if (s == "lm_surf_total_ds") set(L.cur_total_ds + b * L.total_cap, (size_t)li[LI_NTOTAL_DS] * 4, 0);
-  else if (s == "lm_blocks") set(L.blocks + b * L.qcap * 8, (size_t)L.qcap * 8, 1);
-  else if (s == "lm_knn") set(L.knn + b * L.qcap * 5, (size_t)L.qcap * 5, 2);   // lm_knn's rows: corner queries from 0, surf queries from kf_cap_c; -1 x 5 = rejected
+  else if (s == "lm_blocks") set(L.blocks + b * L.qcap * LMB_W, (size_t)L.qcap * LMB_W, 1);   // rows as lm_row_of gives them (lm_rows.h): corner queries from 0, surf queries from kf_cap_c
+  else if (s == "lm_knn") set(L.knn + b * L.qcap * LM_KNN_W, (size_t)L.qcap * LM_KNN_W, 2);   // the same rows; -1 x LM_KNN_W = rejected
   else if (s == "lm_keyposes") set(kf_pose_of(L, kf_row_at(L, slot, 0)), (size_t)(L.loc_on ? L.loc_n : L.fr_mod) * KF_POSE_W, 0);   // (localisation: the map store's)
   else if (s == "lm_window") set(L.rec + b * L.K, (size_t)li[LI_REC_CNT], 2);   // frame ids of recent_*_keyframes_
   else if (s == "lm_kf_corner_map" || s == "lm_kf_surf_map") {   // newest key frame in the map frame, sorted by voxel key (surf = surf + outlier)

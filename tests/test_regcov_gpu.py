@@ -2,7 +2,7 @@
 section 22), through alego_regcov_enable / alego_regcov_get / alego_debug_regcov and the odometry edges map_archive records.
 
 Floating-point tolerances are measured, then asserted at 16 x (the margin covers the kernel's summation order — thread-strided partial sums
-through block_reduce28_oct instead of row order — and the device's sin / cos).  Figures of the MI355X run, relative as in
+through block_reduce28 instead of row order — and the device's sin / cos).  Figures of the MI355X run, relative as in
 tests/test_reg_cov_math.py (info to its largest entry, eigenvalues to lambda_max, cov and the variances to cov's largest entry, cost and sigma2 to
 themselves):
                                                                    cost      info      eigenvalues  cov       sigma2
