@@ -6,11 +6,18 @@
 //              descending/ascending" is evaluated as repeated row-wide arg-max / arg-min over the
 //              not-yet-picked candidates of the sector (identical result for the total order
 //              (curvature, index)); +-5 neighbour suppression by ballot         (:172-286)
-//   fe_pick    the same with one ring per wavefront (suppress_radius > 7, very long sectors)
+//   fe_pick    the same with one ring per wavefront (ALEGO_FE_PICK1, very long sectors)
 //   fe_voxel   a10: per-ring pcl::VoxelGrid(0.4): runs of consecutive equal voxel ids ordered through
 //              monotone buckets in LDS, centroid in sorted (= original) order    (:288-293)
 //   fe_collect ring-ascending concatenation into the four feature clouds (:199-205,:245,:293) + bounding boxes of 32 consecutive
 //              less_flat / less_sharp points for the next scan's LaserOdometry
+//
+// Where the rules live.  fe_rules.h (host-readable, pinned by tests/test_fe_rules.py): the sectors of a ring and which are skipped, the
+// curvature sum / key / thresholds, the occlusion marks and "a point is picked", the flag byte and its candidate tests, the suppression
+// reach, label / spread / continuation of a pick by its count, the tie rules (by index; by std::sort's arrangement under sort_mode 2),
+// less_flat_scan membership.  fe_common.h (device): fe_curv's body, the concatenation of the pick clouds with the less_sharp boxes
+// (fe_concat_picks / fe_concat_cloud, shared with fe_ring_out's row NS), the bucket tables of the run ordering (fe_buckets*, shared with
+// fe_ring_out).  This file keeps what is a kernel's own: who owns which sector element, the reductions, the LDS updates.
 #include <cstdlib>
 #include <type_traits>
 #include "dev_common.h"
@@ -37,9 +44,29 @@ __global__ void __launch_bounds__(FE_BLOCK) fe_curv(DevCtx d) {
   fe_curv_chunk<FE_BLOCK, FE_CW>(d, slot, M, t0, s_r, s_c, s_f);
 }
 
-// one wavefront per (ring, slot).  Dynamic LDS: 3 bytes per ring point (column u16, flags + label u8); the
+// The greedy pick of fe_pick and fe_pick4 (:189-277).  The reference's "sort, then scan descending / ascending" only ever asks for the best remaining
+// candidate of the sector; the kernels below find it by repeated arg-max (sharp / less sharp) or arg-min (flat) over the curvature keys, one loop
+// templated on FLAT.  What is best, who wins a tie, what label a pick gets, whether it spreads and whether the loop goes on: fe_rules.h.
+template <bool FLAT> DEV_INLINE uint32_t fe_better(uint32_t a, uint32_t b) { return FLAT ? min(a, b) : max(a, b); }
+template <bool FLAT> DEV_INLINE uint32_t fe_wave_best(uint32_t v) { return FLAT ? wave_min_u32(v) : wave_max_u32(v); }
+template <bool FLAT> DEV_INLINE uint32_t fe_row_best(uint32_t v) { return FLAT ? group_min_u32<16>(v) : group_max_u32<16>(v); }
+#define FE_NMAX_ALL 0x7fffffff   // fe_pick_label's nmax: these kernels take the unlabelled (n_less_sharp + 1)-th pick as the reference does
+
+// less_flat_scan of one picked sector, in position order (:279-285): the local indices [lsp, lep] of a ring whose flag bytes are sf and whose
+// first staged point is rf, appended to st_lfs; all 64 lanes of a wavefront
+DEV_INLINE void fe_less_flat_sector(const uint8_t* sf, int lsp, int lep, int rf, int* st_lfs, int& n_lfs) {
+  const int lane = threadIdx.x & 63;
+  for (int c0 = lsp; c0 <= lep; c0 += 64) {
+    const int c = c0 + lane;
+    const bool take = c <= lep && fe_less_flat_member(fe_flag_label(sf[c]));
+    const unsigned long long m = __ballot(take);
+    if (take) st_lfs[n_lfs + (int)__popcll(m & ((1ull << lane) - 1ull))] = c + rf;
+    n_lfs += (int)__popcll(m);
+  }
+}
+
+// one wavefront per (ring, slot).  Dynamic LDS: 3 bytes per ring point (column u16, the flag byte of fe_curv u8); the
 // kernel's duration under load is set by how many rings fit a CU next to the other streams' workgroups.
-// flag bits: 0 picked, 1 ground, 2 curvature > edge_thres, 3 curvature < surf_thres, 4-5 cloud_label_ + 1
 // STDSORT (alego_params.sort_mode = 2): candidates with EQUAL curvature are taken in the order libstdc++'s std::sort leaves them in
 // (laserOdometry.cpp:185 sorts with a comparator on the curvature alone) instead of by index.  The picks only ever ask for the
 // best remaining candidate, so the sort itself is not needed — only, when several candidates tie for it, where std::sort's
@@ -56,15 +83,11 @@ __global__ void __launch_bounds__(64) fe_pick(DevCtx d) {
   extern __shared__ __attribute__((aligned(16))) unsigned char fe_smem[];
   uint16_t* s_col = reinterpret_cast<uint16_t*>(fe_smem);
   uint8_t* s_flag = fe_smem + 2 * (size_t)d.H;
-  const float* cdv = d.cd + base + rf;  // |cd| bit pattern = sort key: curvature order == unsigned order
+  const float* cdv = d.cd + base + rf;  // fe_curv_key of it = the sort key
 #pragma unroll 4
-  for (int k = lane; k < cnt; k += 64) {
-    const float a = fabsf(d.cd[base + rf + k]);
-    const double ad = (double)a;
-    const double curv = ad * ad;  // (double)diff_range * diff_range, exact (:125)
+  for (int k = lane; k < cnt; k += 64) {   // the flag byte as fe_curv stored it (its jump bit is not looked at here: the columns are)
     s_col[k] = (uint16_t)d.seg_col[base + rf + k];
-    s_flag[k] = (uint8_t)((d.fe_flag[base + rf + k] & 1) | (d.seg_ground[base + rf + k] ? 2 : 0) |
-                          (curv > P.edge_thres ? 4 : 0) | (curv < P.surf_thres ? 8 : 0) | (1 << 4));  // bits 4-5: label + 1
+    s_flag[k] = d.fe_flag[base + rf + k];
   }
   __syncthreads();
   int* st = st_idx_of(d, slot, ring);
@@ -73,9 +96,8 @@ __global__ void __launch_bounds__(64) fe_pick(DevCtx d) {
   const int NSEC = P.n_sectors, SR = P.suppress_radius;
   for (int j = 0; j < NSEC; ++j) {
     int sp, ep;
-    if (P.sector_formula == 0) { sp = (S * (NSEC - j) + E * j) / NSEC; ep = (S * (NSEC - 1 - j) + E * (j + 1)) / NSEC - 1; }
-    else { const int diff = E - S; sp = S + j * diff / NSEC; ep = S + (j + 1) * diff / NSEC - 1; }
-    if (sp >= ep) continue;
+    fe_sector(P, S, E, j, sp, ep);
+    if (fe_sector_skipped(sp, ep)) continue;
     const int lsp = sp - rf, lep = ep - rf;
     // Lane l owns the sector elements lsp + l + 64 t; their keys and candidate bits live in registers for the
     // whole sector, so an iteration of the greedy pick touches LDS only for the +-SR column test.
@@ -86,26 +108,24 @@ __global__ void __launch_bounds__(64) fe_pick(DevCtx d) {
       const int c = lsp + lane + 64 * t;
       const bool ok = c <= lep;   // unconditional loads (clamped address): all of them in flight together
       const uint8_t f = s_flag[ok ? c : lsp];
-      const uint32_t kv = (uint32_t)d_f2i(fabsf(cdv[ok ? c : lsp]));  // straight from HBM/L2: the LDS footprint decides how many rings fit a CU
+      const uint32_t kv = fe_curv_key(cdv[ok ? c : lsp]);  // straight from HBM/L2: the LDS footprint decides how many rings fit a CU
       key[t] = ok ? kv : 0u;
-      if (ok && (f & 7) == 4) sharp_m |= 1u << t;    // not picked, not ground, curvature > edge_thres
-      if (ok && (f & 11) == 10) flat_m |= 1u << t;   // not picked, ground, curvature < surf_thres
+      if (ok && fe_sharp_candidate(f)) sharp_m |= 1u << t;
+      if (ok && fe_flat_candidate(f)) flat_m |= 1u << t;
     }
-    // marks local index c and its +-SR neighbours picked (:211-234: stop at the first column jump), in LDS for
-    // the later sectors and in the owners' candidate masks for this one
+    // marks local index c and its fe_reach neighbours picked, in LDS for the later sectors and in the owners' candidate masks for this one
     auto mark = [&](int c, bool spread) {
       int nf = 0, nbk = 0;
-      if (spread) {
+      if (spread) {   // lanes 0 .. SR - 1 look forward, 32 .. 32 + SR - 1 backward
         bool bad = false;
-        if (lane < SR) { const int cdf = (int)s_col[c + lane + 1] - (int)s_col[c + lane]; bad = (cdf < 0 ? -cdf : cdf) > P.suppress_col_diff; }
-        else if (lane >= 32 && lane < 32 + SR) { const int l = lane - 32; const int cdf = (int)s_col[c - l - 1] - (int)s_col[c - l]; bad = (cdf < 0 ? -cdf : cdf) > P.suppress_col_diff; }
+        if (lane < SR) bad = fe_col_jump(s_col[c + lane + 1], s_col[c + lane], P.suppress_col_diff);
+        else if (lane >= 32 && lane < 32 + SR) { const int l = lane - 32; bad = fe_col_jump(s_col[c - l - 1], s_col[c - l], P.suppress_col_diff); }
         const unsigned long long mb = __ballot(bad);
-        const unsigned lo = (unsigned)(mb & 0xffffffffull), hi = (unsigned)(mb >> 32);
-        nf = lo ? min(SR, __ffs((int)lo) - 1) : SR;
-        nbk = hi ? min(SR, __ffs((int)hi) - 1) : SR;
+        const FeReach reach = fe_reach((unsigned)(mb & 0xffffffffull), (unsigned)(mb >> 32), SR);
+        nf = reach.fwd; nbk = reach.bwd;
       }
       const int first = c - nbk, last = c + nf;
-      if (lane <= last - first) s_flag[first + lane] |= 1;
+      if (lane <= last - first) s_flag[first + lane] |= FE_FLAG_PICKED;
       // the (single) owned element inside [first, last]
       const int off = (lane - (first - lsp)) & 63;
       const int ct = first + off;
@@ -116,115 +136,74 @@ __global__ void __launch_bounds__(64) fe_pick(DevCtx d) {
       if constexpr (STDSORT) {
         const int n = lep - lsp + 1;
         __syncthreads();
-        for (int i = lane; i < n; i += 64) s_emu.ak[i] = (uint32_t)d_f2i(fabsf(cdv[lsp + i]));   // |cd| bits order like the f64 curvature, equal iff it is
+        for (int i = lane; i < n; i += 64) s_emu.ak[i] = fe_curv_key(cdv[lsp + i]);   // |cd| bits order like the f64 curvature, equal iff it is
         __syncthreads();
         stdsort_arrangement(s_emu, n);
       }
     };
-    // ---- sharp / less-sharp: descending curvature, ties -> larger index (:189-236) ----
-    int picked_num = 0;
-    while (true) {
-      uint32_t bk = 0;
-      int bt = 0;
+    // FLAT = false: sharp / less-sharp, descending curvature (:189-236); FLAT = true: flat, ascending, ground only (:238-277)
+    auto pick = [&](auto flat_tag) {
+      constexpr bool FLAT = decltype(flat_tag)::value;
+      constexpr uint32_t NONE = fe_key_none<FLAT>();
+      int picked_num = 0;
+      while (true) {
+        const uint32_t cand_m = FLAT ? flat_m : sharp_m;
+        uint32_t bk = NONE;
+        int bt = 0;
 #pragma unroll
-      for (int t = 0; t < FE_T; ++t) if (((sharp_m >> t) & 1) && key[t] >= bk) { bk = key[t]; bt = t; }
-      const uint32_t kmax = wave_max_u32(bk);
-      if (kmax == 0) break;
-      // almost always exactly one lane holds the maximum: its index comes through v_readlane; equal keys in several
-      // lanes (ties -> larger index) take the second reduction
-      const unsigned long long tie = __ballot(sharp_m && bk == kmax);
-      int c = 0;
-      bool by_arrangement = false;
-      if constexpr (STDSORT) {
-        int cnt = 0;
+        for (int t = 0; t < FE_T; ++t) if (((cand_m >> t) & 1) && fe_scan_takes<FLAT>(key[t], bk)) { bk = key[t]; bt = t; }
+        const uint32_t kbest = fe_wave_best<FLAT>(bk);
+        if (kbest == NONE) break;
+        // almost always exactly one lane holds the best key: its index comes through v_readlane; equal keys in several
+        // lanes (fe_tie_takes) take the second reduction
+        const unsigned long long tie = __ballot(cand_m && bk == kbest);
+        int c = 0;
+        bool by_arrangement = false;
+        if constexpr (STDSORT) {
+          int cnt = 0;
 #pragma unroll
-        for (int t = 0; t < FE_T; ++t) cnt += (((sharp_m >> t) & 1) && key[t] == kmax) ? 1 : 0;
-        const unsigned long long a1 = __ballot(cnt > 0), a2 = __ballot(cnt > 1);
-        by_arrangement = a2 != 0 || (a1 & (a1 - 1)) != 0;
-        if (by_arrangement) {   // the scan runs k = ep .. sp: of the tied candidates the one std::sort placed last comes first
-          if (!have_arr) { sector_arrangement(); have_arr = true; }
-          uint32_t best = 0;
+          for (int t = 0; t < FE_T; ++t) cnt += (((cand_m >> t) & 1) && key[t] == kbest) ? 1 : 0;
+          const unsigned long long a1 = __ballot(cnt > 0), a2 = __ballot(cnt > 1);
+          by_arrangement = a2 != 0 || (a1 & (a1 - 1)) != 0;
+          if (by_arrangement) {   // fe_tie_takes_arranged, on fe_arranged_code
+            if (!have_arr) { sector_arrangement(); have_arr = true; }
+            uint32_t best = NONE;
 #pragma unroll
-          for (int t = 0; t < FE_T; ++t)
-            if (((sharp_m >> t) & 1) && key[t] == kmax) best = max(best, (((uint32_t)s_emu.pos[lane + 64 * t] + 1u) << 16) | (uint32_t)(lane + 64 * t));
-          c = lsp + (int)(wave_max_u32(best) & 0xFFFFu);
+            for (int t = 0; t < FE_T; ++t)
+              if (((cand_m >> t) & 1) && key[t] == kbest) best = fe_better<FLAT>(best, fe_arranged_code<FLAT>((uint32_t)s_emu.pos[lane + 64 * t], (uint32_t)(lane + 64 * t)));
+            c = lsp + (int)(fe_wave_best<FLAT>(best) & 0xFFFFu);
+          }
         }
-      }
-      if (by_arrangement) {
-      } else if ((tie & (tie - 1)) == 0) {
-        const int wl = __ffsll((long long)tie) - 1;
-        c = lsp + wl + 64 * __builtin_amdgcn_readlane(bt, wl);
-      } else {
-        const uint32_t cand = (sharp_m && bk == kmax) ? (uint32_t)(lsp + lane + 64 * bt) : 0u;
-        c = (int)wave_max_u32(cand);
-      }
-      ++picked_num;
-      int lab = 0;
-      if (picked_num <= P.n_sharp) lab = 2; else if (picked_num <= P.n_less_sharp) lab = 1;
-      if (lane == 0) {
-        if (lab) s_flag[c] = (uint8_t)((s_flag[c] & 0xCF) | ((lab + 1) << 4));
-        if (lab == 2) st_sharp[n_sharp] = c + rf;
-        if (lab) st_lsharp[n_ls] = c + rf;
-      }
-      if (lab == 2) ++n_sharp;
-      if (lab) ++n_ls;
-      mark(c, lab != 0);  // the 21st pick is marked but breaks before the suppression (:207-210)
-      if (!lab) break;
-    }
-    // ---- flat: ascending curvature, ground only, ties -> smaller index (:238-277) ----
-    picked_num = 0;
-    while (true) {
-      uint32_t bk = 0xFFFFFFFFu;
-      int bt = 0;
-#pragma unroll
-      for (int t = 0; t < FE_T; ++t) if (((flat_m >> t) & 1) && key[t] < bk) { bk = key[t]; bt = t; }
-      const uint32_t kmin = wave_min_u32(bk);
-      if (kmin == 0xFFFFFFFFu) break;
-      const unsigned long long tie = __ballot(flat_m && bk == kmin);
-      int c = 0;
-      bool by_arrangement = false;
-      if constexpr (STDSORT) {
-        int cnt = 0;
-#pragma unroll
-        for (int t = 0; t < FE_T; ++t) cnt += (((flat_m >> t) & 1) && key[t] == kmin) ? 1 : 0;
-        const unsigned long long a1 = __ballot(cnt > 0), a2 = __ballot(cnt > 1);
-        by_arrangement = a2 != 0 || (a1 & (a1 - 1)) != 0;
-        if (by_arrangement) {   // k = sp .. ep: the tied candidate std::sort placed first
-          if (!have_arr) { sector_arrangement(); have_arr = true; }
-          uint32_t best = 0xFFFFFFFFu;
-#pragma unroll
-          for (int t = 0; t < FE_T; ++t)
-            if (((flat_m >> t) & 1) && key[t] == kmin) best = min(best, ((uint32_t)s_emu.pos[lane + 64 * t] << 16) | (uint32_t)(lane + 64 * t));
-          c = lsp + (int)(wave_min_u32(best) & 0xFFFFu);
+        if (by_arrangement) {
+        } else if ((tie & (tie - 1)) == 0) {
+          const int wl = __ffsll((long long)tie) - 1;
+          c = lsp + wl + 64 * __builtin_amdgcn_readlane(bt, wl);
+        } else {
+          const uint32_t cand = (cand_m && bk == kbest) ? (uint32_t)(lsp + lane + 64 * bt) : NONE;
+          c = (int)fe_wave_best<FLAT>(cand);
         }
+        ++picked_num;
+        int lab;
+        bool spread, more;
+        fe_pick_label<FLAT>(P, picked_num, FE_NMAX_ALL, lab, spread, more);
+        if (lane == 0) {
+          if (FLAT || lab) s_flag[c] = fe_flag_with_label(s_flag[c], lab);
+          if (FLAT) st_flat[n_flat] = c + rf;
+          else { if (lab == 2) st_sharp[n_sharp] = c + rf; if (lab) st_lsharp[n_ls] = c + rf; }
+        }
+        if (FLAT) ++n_flat;
+        else { if (lab == 2) ++n_sharp; if (lab) ++n_ls; }
+        mark(c, spread);
+        if (!more) break;
       }
-      if (by_arrangement) {
-      } else if ((tie & (tie - 1)) == 0) {
-        const int wl = __ffsll((long long)tie) - 1;
-        c = lsp + wl + 64 * __builtin_amdgcn_readlane(bt, wl);
-      } else {
-        const uint32_t cand = (flat_m && bk == kmin) ? (uint32_t)(lsp + lane + 64 * bt) : 0xFFFFFFFFu;
-        c = (int)wave_min_u32(cand);
-      }
-      ++picked_num;
-      if (lane == 0) { s_flag[c] = (uint8_t)(s_flag[c] & 0xCF); st_flat[n_flat] = c + rf; }   // label -1
-      ++n_flat;
-      const bool stop = picked_num >= P.n_flat;
-      mark(c, !stop);  // the n_flat-th pick breaks before the suppression (:248-251)
-      if (stop) break;
-    }
+    };
+    pick(std::false_type{});
+    pick(std::true_type{});
     __syncthreads();
-    // ---- less-flat candidates in position order (:279-285) ----
-    for (int c0 = lsp; c0 <= lep; c0 += 64) {
-      const int c = c0 + lane;
-      const bool take = c <= lep && ((s_flag[c] >> 4) & 3) <= 1;   // label <= 0
-      const unsigned long long m = __ballot(take);
-      if (take) st_lfs[n_lfs + (int)__popcll(m & ((1ull << lane) - 1ull))] = c + rf;
-      n_lfs += (int)__popcll(m);
-    }
+    fe_less_flat_sector(s_flag, lsp, lep, rf, st_lfs, n_lfs);
   }
   __syncthreads();
-  for (int k = lane; k < cnt; k += 64) d.plabel[base + rf + k] = (int)((s_flag[k] >> 4) & 3) - 1;
+  for (int k = lane; k < cnt; k += 64) d.plabel[base + rf + k] = fe_flag_label(s_flag[k]);
   if (lane == 0) {
     int* c = st_cnt_of(d, slot, ring);
     c[F_SHARP] = n_sharp; c[F_LSHARP] = n_ls; c[F_FLAT] = n_flat; c[F_LFLAT] = n_lfs;
@@ -234,7 +213,7 @@ __global__ void __launch_bounds__(64) fe_pick(DevCtx d) {
 // fe_pick4<FE_T>: the same greedy pick with FOUR rings per wavefront, one DPP row (16 lanes) each.  The per-pick
 // overhead of the one-ring kernel (wave-wide arg-max, ballot, suppression window, uniform control flow: ~70 of its
 // ~100 instructions per pick) is issued once for four rings; the reductions stay inside a DPP row.  Lane gl of a row owns
-// the sector elements lsp + gl + 16 t (sector length <= 16 * FE_T).  Needs suppress_radius <= 7: the forward checks sit in
+// the sector elements lsp + gl + 16 t (sector length <= 16 * FE_T).  Needs suppress_radius <= 5, what alego_create accepts and fe_reach looks at: the forward checks sit in
 // lanes 0-7 of the row, the backward checks in lanes 8-15, and the 2 * radius + 1 marked elements get one lane each.  Dynamic LDS: 1 B per ring point, 4 rings.
 // STDSORT (sort_mode 2): as in fe_pick — when several candidates of a row tie for the best curvature, the whole wavefront computes
 // where libstdc++'s std::sort would have left that ring's sector (stdsort_emu.h), once per ring and sector, and the row picks by it.
@@ -252,19 +231,18 @@ __global__ void __launch_bounds__(64) fe_pick4(DevCtx d) {
   const alego_params& P = d.P;
   extern __shared__ __attribute__((aligned(16))) unsigned char fe_smem[];
   // 1 B per ring point: the kernel's LDS footprint (one wavefront, four rings) is what limits how many of these workgroups —
-  // and how much of the other stream groups' work — fit a CU.  The suppression only ever asks whether |col[k+1] - col[k]|
-  // exceeds suppress_col_diff: that is bit 6 of the point's flag byte.
+  // and how much of the other stream groups' work — fit a CU.  The suppression only ever asks for fe_col_jump between a point
+  // and the next: FE_FLAG_JUMP of the point's flag byte.
   uint8_t* s_flag = fe_smem;                                  // [FP_G][H]
   for (int r = 0; r < FP_G && ring0 + r < d.NS; ++r) {       // whole wavefront stages one ring after the other
     const int Sr = ring_start_of(d, slot, ring0)[r], Er = ring_end_of(d, slot, ring0)[r];
     const int rfr = Sr - 5, cntr = Er - Sr + 11;
     uint8_t* sf = s_flag + (size_t)r * d.H;
-    // the flag byte of every point comes ready from fe_curv_chunk (picked | ground << 1 | curvature > edge_thres << 2 | curvature <
-    // surf_thres << 3 | label 0 << 4 | column jump to the next point << 6); the jump bit of the ring's last point compares with
+    // the flag byte of every point comes ready from fe_curv_chunk (fe_flag_of); the jump bit of the ring's last point compares with
     // the point itself in the reference's suppression loop (clamped index): cleared here
     const uint8_t* ff = d.fe_flag + base + rfr;
 #pragma unroll 8
-    for (int k = lane; k < cntr; k += 64) sf[k] = k == cntr - 1 ? (uint8_t)(ff[k] & ~64) : ff[k];
+    for (int k = lane; k < cntr; k += 64) sf[k] = k == cntr - 1 ? (uint8_t)(ff[k] & ~FE_FLAG_JUMP) : ff[k];
   }
   __syncthreads();
   const int S = rv ? *ring_start_of(d, slot, ring) : 0, E = rv ? *ring_end_of(d, slot, ring) : 0;
@@ -276,9 +254,8 @@ __global__ void __launch_bounds__(64) fe_pick4(DevCtx d) {
   const int NSEC = P.n_sectors, SR = P.suppress_radius;
   for (int j = 0; j < NSEC; ++j) {
     int sp, ep;
-    if (P.sector_formula == 0) { sp = (S * (NSEC - j) + E * j) / NSEC; ep = (S * (NSEC - 1 - j) + E * (j + 1)) / NSEC - 1; }
-    else { const int diff = E - S; sp = S + j * diff / NSEC; ep = S + (j + 1) * diff / NSEC - 1; }
-    const bool act0 = rv && sp < ep;
+    fe_sector(P, S, E, j, sp, ep);
+    const bool act0 = rv && !fe_sector_skipped(sp, ep);
     if (!__any(act0)) continue;
     const int lsp = sp - rf, lep = ep - rf;
     uint32_t key[FE_T];
@@ -290,10 +267,11 @@ __global__ void __launch_bounds__(64) fe_pick4(DevCtx d) {
       const int c = lsp + gl + 16 * t;
       const bool ok = act0 && c <= lep;
       const uint8_t f = sf[ok ? c : 0];
-      const uint32_t kv = (uint32_t)d_f2i(fabsf(d.cd[base + (ok ? rf + c : 0)]));
+      const uint32_t kv = fe_curv_key(d.cd[base + (ok ? rf + c : 0)]);
       key[t] = ok ? kv : 0u;
-      if (ok && (f & 7) == 4) sharp_m |= (mask_t)1 << t;
-      if (ok && (f & 11) == 10) flat_m |= (mask_t)1 << t;
+      const bool cs = fe_sharp_candidate(f), cf = fe_flat_candidate(f);   // (evaluated outside the && : behind it the compiler kept 16 - 40 more registers)
+      if (ok && cs) sharp_m |= (mask_t)1 << t;
+      if (ok && cf) flat_m |= (mask_t)1 << t;
     }
     // One greedy pick is a few hundred DEPENDENT instructions of a single wavefront (126 of them per ring quad): the loop body
     // is written branch-free.  LDS flag bytes are changed with no-return 32-bit atomics on the containing word (no read /
@@ -301,29 +279,29 @@ __global__ void __launch_bounds__(64) fe_pick4(DevCtx d) {
     // addresses, and only the list stores sit behind a (single) branch.
     unsigned* fw = reinterpret_cast<unsigned*>(s_flag);
     const int fo = g * d.H;                               // this ring's first flag byte
-    // marks c and its +-SR neighbours picked (:211-234) for the rows where `on`; `spread` rows look for column jumps first
+    // marks c and its fe_reach neighbours picked for the rows where `on`; `spread` rows look for column jumps first
     auto mark = [&](int c, bool on, bool spread) {
       const int role = gl & 7, rr = max(min(role, SR - 1), 0);   // lanes 0-7 look forward, 8-15 backward
       const int a = spread ? (gl < 8 ? c + rr : c - rr - 1) : 0;
-      const bool bad = spread && role < SR && (sf[a] & 64);
+      const bool bad = spread && role < SR && (sf[a] & FE_FLAG_JUMP);
       const unsigned long long mb = __ballot(bad);
       const unsigned gb = (unsigned)(mb >> (16 * g)) & 0xffffu;
-      const unsigned lo = gb & 0xffu, hi = gb >> 8;
-      const int nf = spread ? (lo ? min(SR, __ffs((int)lo) - 1) : SR) : 0, nbk = spread ? (hi ? min(SR, __ffs((int)hi) - 1) : SR) : 0;
+      const FeReach reach = fe_reach(gb & 0xffu, gb >> 8, SR);
+      const int nf = spread ? reach.fwd : 0, nbk = spread ? reach.bwd : 0;
       const int first = c - nbk, last = c + nf;
       const bool w = on && gl <= last - first;
       const int bo = fo + (w ? first + gl : 0);
-      atomicOr(&fw[bo >> 2], (w ? 1u : 0u) << ((bo & 3) * 8));
+      atomicOr(&fw[bo >> 2], (w ? (unsigned)FE_FLAG_PICKED : 0u) << ((bo & 3) * 8));
       const int off = (gl - (first - lsp)) & 15;   // the (single) owned element inside [first, last]
       const int ct = first + off;
       const mask_t bit = (on && ct <= last && ct >= lsp && ct <= lep) ? (mask_t)1 << (((ct - lsp - gl) >> 4) & (8 * (int)sizeof(mask_t) - 1)) : (mask_t)0;
       sharp_m &= ~bit; flat_m &= ~bit;
     };
-    // the label bits (4-5) of an unlabelled element hold 1 (label 0): 1 ^ 2 = 3 (sharp), 1 ^ 3 = 2 (less sharp), 1 ^ 1 = 0 (flat);
+    // the label bits of an unlabelled element hold label 0: x = 0 + 1 xor the new label + 1 turns them into it, 0 leaves them;
     // an element is labelled at most once (it is marked picked with it)
     auto relabel = [&](int c, unsigned x) {
       const int bo = fo + (x ? c : 0);
-      atomicXor(&fw[bo >> 2], (x << 4) << ((bo & 3) * 8));
+      atomicXor(&fw[bo >> 2], (x << FE_FLAG_LABEL_SHIFT) << ((bo & 3) * 8));
     };
     int* st_dummy = st_cnt_of(d, slot, rv ? ring : 0) + ST_DUMMY;   // unused field
     // (STDSORT) the sector arrangement of every ring whose row reports a tie and has none yet, ring by ring with all 64 lanes
@@ -336,7 +314,7 @@ __global__ void __launch_bounds__(64) fe_pick4(DevCtx d) {
           const int lsp_r = __shfl(lsp, 16 * r, 64), lep_r = __shfl(lep, 16 * r, 64), rf_r = __shfl(rf, 16 * r, 64);
           const int n = lep_r - lsp_r + 1;
           __syncthreads();
-          for (int i = lane; i < n; i += 64) s_emu.ak[i] = (uint32_t)d_f2i(fabsf(d.cd[base + rf_r + lsp_r + i]));
+          for (int i = lane; i < n; i += 64) s_emu.ak[i] = fe_curv_key(d.cd[base + rf_r + lsp_r + i]);
           __syncthreads();
           stdsort_arrangement(s_emu, n);
           for (int i = lane; i < n; i += 64) s_pos[r][i] = s_emu.pos[i];
@@ -345,94 +323,71 @@ __global__ void __launch_bounds__(64) fe_pick4(DevCtx d) {
         }
       }
     };
-    // ---- sharp / less-sharp: descending curvature, ties -> larger index (:189-236) ----
-    int picked_num = 0;
-    bool act = act0;
-    while (true) {
-      uint32_t bk = 0;
-      int bt = 0;
+    // FLAT = false: sharp / less-sharp, descending curvature (:189-236); FLAT = true: flat, ascending, ground only (:238-277)
+    // (what the loop only reads is captured by value: through references the sort_mode 2 instances kept 20 - 24 more registers and lost a wavefront per SIMD.
+    //  CAREFUL: key, P and the helper lambdas are COPIES here — the helpers still reach sharp_m / flat_m / have_arr through their own references — so a
+    //  local of the sector that the loop is to change has to be named in the capture list by reference, or the loop changes a copy.)
+    auto pick = [=, &sharp_m, &flat_m, &n_sharp, &n_ls, &n_flat](auto flat_tag) {
+      constexpr bool FLAT = decltype(flat_tag)::value;
+      constexpr uint32_t NONE = fe_key_none<FLAT>();
+      int picked_num = 0;
+      bool act = act0;
+      while (true) {
+        const mask_t cand_m = FLAT ? flat_m : sharp_m;
+        uint32_t bk = NONE;
+        int bt = 0;
 #pragma unroll
-      for (int t = 0; t < FE_T; ++t) if (((sharp_m >> t) & 1) && key[t] >= bk) { bk = key[t]; bt = t; }
-      if (!act) bk = 0;
-      const uint32_t kmax = group_max_u32<16>(bk);
-      act = act && kmax != 0;
-      if (!__any(act)) break;
-      int c = (int)group_max_u32<16>(bk == kmax ? (uint32_t)(lsp + gl + 16 * bt) : 0u);   // ties -> larger index
-      if constexpr (STDSORT) {
-        int cnt = 0;
+        for (int t = 0; t < FE_T; ++t) if (((cand_m >> t) & 1) && fe_scan_takes<FLAT>(key[t], bk)) { bk = key[t]; bt = t; }
+        if (!act) bk = NONE;
+        const uint32_t kbest = fe_row_best<FLAT>(bk);
+        act = act && kbest != NONE;
+        if (!__any(act)) break;
+        int c = (int)fe_row_best<FLAT>(bk == kbest ? (uint32_t)(lsp + gl + 16 * bt) : NONE);   // fe_tie_takes
+        if constexpr (STDSORT) {
+          int cnt = 0;
 #pragma unroll
-        for (int t = 0; t < FE_T; ++t) cnt += (((sharp_m >> t) & 1) && key[t] == kmax) ? 1 : 0;
-        if (!act) cnt = 0;
-        const bool tied = group_max_u32<16>((uint32_t)cnt) > 1u || __popc((unsigned)(__ballot(cnt > 0) >> (16 * g)) & 0xffffu) > 1;
-        if (__any(tied)) {
-          ring_arrangements(tied);
-          uint32_t best = 0;   // k = ep .. sp: of the tied candidates the one std::sort placed last comes first
+          for (int t = 0; t < FE_T; ++t) cnt += (((cand_m >> t) & 1) && key[t] == kbest) ? 1 : 0;
+          if (!act) cnt = 0;
+          const bool tied = group_max_u32<16>((uint32_t)cnt) > 1u || __popc((unsigned)(__ballot(cnt > 0) >> (16 * g)) & 0xffffu) > 1;
+          if (__any(tied)) {
+            ring_arrangements(tied);
+            uint32_t best = NONE;   // fe_tie_takes_arranged, on fe_arranged_code
 #pragma unroll
-          for (int t = 0; t < FE_T; ++t)
-            if (((sharp_m >> t) & 1) && key[t] == kmax) best = max(best, (((uint32_t)s_pos[g][gl + 16 * t] + 1u) << 16) | (uint32_t)(gl + 16 * t));
-          const int ca = lsp + (int)(group_max_u32<16>(tied ? best : 0u) & 0xFFFFu);
-          c = tied ? ca : c;
+            for (int t = 0; t < FE_T; ++t)
+              if (((cand_m >> t) & 1) && key[t] == kbest) best = fe_better<FLAT>(best, fe_arranged_code<FLAT>((uint32_t)s_pos[g][gl + 16 * t], (uint32_t)(gl + 16 * t)));
+            const int ca = lsp + (int)(fe_row_best<FLAT>(tied ? best : NONE) & 0xFFFFu);
+            c = tied ? ca : c;
+          }
         }
-      }
-      picked_num += act ? 1 : 0;
-      const int lab = picked_num <= P.n_sharp ? 2 : (picked_num <= P.n_less_sharp ? 1 : 0);
-      const bool w1 = act && gl == 0 && lab != 0;
-      relabel(c, w1 ? (lab == 2 ? 2u : 3u) : 0u);
-      if (w1) {
-        int* ps = lab == 2 ? st_sharp + n_sharp : st_dummy;
-        *ps = c + rf;
-        st_lsharp[n_ls] = c + rf;
-      }
-      n_sharp += (act && lab == 2) ? 1 : 0;
-      n_ls += (act && lab) ? 1 : 0;
-      mark(c, act, act && lab != 0);  // the 21st pick is marked but breaks before the suppression (:207-210)
-      act = act && lab != 0;
-    }
-    // ---- flat: ascending curvature, ground only, ties -> smaller index (:238-277) ----
-    picked_num = 0;
-    act = act0;
-    while (true) {
-      uint32_t bk = 0xFFFFFFFFu;
-      int bt = 0;
-#pragma unroll
-      for (int t = 0; t < FE_T; ++t) if (((flat_m >> t) & 1) && key[t] < bk) { bk = key[t]; bt = t; }
-      if (!act) bk = 0xFFFFFFFFu;
-      const uint32_t kmin = group_min_u32<16>(bk);
-      act = act && kmin != 0xFFFFFFFFu;
-      if (!__any(act)) break;
-      int c = (int)group_min_u32<16>(bk == kmin ? (uint32_t)(lsp + gl + 16 * bt) : 0xFFFFFFFFu);   // ties -> smaller index
-      if constexpr (STDSORT) {
-        int cnt = 0;
-#pragma unroll
-        for (int t = 0; t < FE_T; ++t) cnt += (((flat_m >> t) & 1) && key[t] == kmin) ? 1 : 0;
-        if (!act) cnt = 0;
-        const bool tied = group_max_u32<16>((uint32_t)cnt) > 1u || __popc((unsigned)(__ballot(cnt > 0) >> (16 * g)) & 0xffffu) > 1;
-        if (__any(tied)) {
-          ring_arrangements(tied);
-          uint32_t best = 0xFFFFFFFFu;   // k = sp .. ep: the tied candidate std::sort placed first
-#pragma unroll
-          for (int t = 0; t < FE_T; ++t)
-            if (((flat_m >> t) & 1) && key[t] == kmin) best = min(best, ((uint32_t)s_pos[g][gl + 16 * t] << 16) | (uint32_t)(gl + 16 * t));
-          const int ca = lsp + (int)(group_min_u32<16>(tied ? best : 0xFFFFFFFFu) & 0xFFFFu);
-          c = tied ? ca : c;
+        picked_num += act ? 1 : 0;
+        int lab;
+        bool spread, more;
+        fe_pick_label<FLAT>(P, picked_num, FE_NMAX_ALL, lab, spread, more);
+        const bool w1 = act && gl == 0 && lab != 0;
+        relabel(c, w1 ? 1u ^ (unsigned)(lab + 1) : 0u);
+        if (w1) {
+          if (FLAT) st_flat[n_flat] = c + rf;
+          else {
+            int* ps = lab == 2 ? st_sharp + n_sharp : st_dummy;
+            *ps = c + rf;
+            st_lsharp[n_ls] = c + rf;
+          }
         }
+        if (FLAT) n_flat += act ? 1 : 0;
+        else { n_sharp += (act && lab == 2) ? 1 : 0; n_ls += (act && lab) ? 1 : 0; }
+        mark(c, act, act && spread);
+        act = act && more;
       }
-      picked_num += act ? 1 : 0;
-      const bool w1 = act && gl == 0;
-      relabel(c, w1 ? 1u : 0u);   // label -1
-      if (w1) st_flat[n_flat] = c + rf;
-      n_flat += act ? 1 : 0;
-      const bool stop = picked_num >= P.n_flat;
-      mark(c, act, act && !stop);  // the n_flat-th pick breaks before the suppression (:248-251)
-      act = act && !stop;
-    }
+    };
+    pick(std::false_type{});
+    pick(std::true_type{});
   }
   __syncthreads();
   if (rv && gl == 0) {
     int* c = st_cnt_of(d, slot, ring);
     c[F_SHARP] = n_sharp; c[F_LSHARP] = n_ls; c[F_FLAT] = n_flat;
   }
-  // ---- less-flat candidates in position order (:279-285) and the labels, one ring after the other with all 64 lanes.
+  // ---- less_flat_scan and the labels, one ring after the other with all 64 lanes.
   // A sector's labels only change while that sector is picked, so reading them at the end is the same as reading them
   // after the sector.
   for (int r = 0; r < FP_G && ring0 + r < d.NS; ++r) {
@@ -443,19 +398,11 @@ __global__ void __launch_bounds__(64) fe_pick4(DevCtx d) {
     int n_lfs = 0;
     for (int j = 0; j < NSEC; ++j) {
       int sp, ep;
-      if (P.sector_formula == 0) { sp = (Sr * (NSEC - j) + Er * j) / NSEC; ep = (Sr * (NSEC - 1 - j) + Er * (j + 1)) / NSEC - 1; }
-      else { const int diff = Er - Sr; sp = Sr + j * diff / NSEC; ep = Sr + (j + 1) * diff / NSEC - 1; }
-      if (sp >= ep) continue;
-      const int lsp = sp - rfr, lep = ep - rfr;
-      for (int c0 = lsp; c0 <= lep; c0 += 64) {
-        const int c = c0 + lane;
-        const bool take = c <= lep && ((sfr[c] >> 4) & 3) <= 1;   // label <= 0
-        const unsigned long long m = __ballot(take);
-        if (take) st_lfs[n_lfs + (int)__popcll(m & ((1ull << lane) - 1ull))] = c + rfr;
-        n_lfs += (int)__popcll(m);
-      }
+      fe_sector(P, Sr, Er, j, sp, ep);
+      if (fe_sector_skipped(sp, ep)) continue;
+      fe_less_flat_sector(sfr, sp - rfr, ep - rfr, rfr, st_lfs, n_lfs);
     }
-    for (int k = lane; k < cntr; k += 64) d.plabel[base + rfr + k] = (int)((sfr[k] >> 4) & 3) - 1;
+    for (int k = lane; k < cntr; k += 64) d.plabel[base + rfr + k] = fe_flag_label(sfr[k]);
     if (lane == 0) st_cnt_of(d, slot, (size_t)ring0 + r)[F_LFLAT] = n_lfs;
   }
 }
@@ -564,20 +511,28 @@ __global__ void __launch_bounds__(FV_BLOCK) fe_voxel(DevCtx d) {
   for (int i = tid; i < n; i += FV_BLOCK) s_key[i] = vgr_id(g, point(i), inv);
   __syncthreads();
   FV_TICK(2);
+  // the heads of a chunk of FV_BLOCK positions numbered in position order: -> heads before this thread's, *tot = heads of the chunk (ballots: a
+  // head is a bit, and wave.h's block_excl_scan would pay six shuffle steps for it); one barrier inside, the caller's barrier ends the chunk
+  auto heads_before = [&](bool head, int* tot) -> int {
+    const unsigned long long m = __ballot(head);
+    if ((tid & 63) == 0) s_scan[tid >> 6] = (int)__popcll(m);
+    __syncthreads();
+    int woff = 0, t = 0;
+#pragma unroll
+    for (int w = 0; w < FV_BLOCK / 64; ++w) { if (w < (tid >> 6)) woff += s_scan[w]; t += s_scan[w]; }
+    *tot = t;
+    return woff + (int)__popcll(m & ((1ull << (tid & 63)) - 1ull));
+  };
   // runs of consecutive equal voxel ids
   int nruns = 0;
   for (int c0 = 0; c0 < n; c0 += FV_BLOCK) {
     const int i = c0 + tid;
     const uint32_t mykey = i < n ? s_key[i] : 0u;   // read before the barrier: the run ids are compacted into the same array
     const bool head = i < n && (i == 0 || mykey != s_key[i - 1]);
-    const unsigned long long m = __ballot(head);
-    if ((tid & 63) == 0) s_scan[tid >> 6] = (int)__popcll(m);
-    __syncthreads();
-    int woff = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < FV_BLOCK / 64; ++w) { if (w < (tid >> 6)) woff += s_scan[w]; tot += s_scan[w]; }
+    int tot;
+    const int before = heads_before(head, &tot);
     if (head) {
-      const int r = nruns + woff + (int)__popcll(m & ((1ull << (tid & 63)) - 1ull));
+      const int r = nruns + before;
       s_rvid[r] = mykey;
       s_rstart[r] = (uint16_t)i;
     }
@@ -589,40 +544,19 @@ __global__ void __launch_bounds__(FV_BLOCK) fe_voxel(DevCtx d) {
   // into <= FV_NB buckets that are monotone in the voxel id (LDS atomics; arbitrary order inside a bucket), then
   // every run ranks itself among the one or two runs of its bucket — instead of against all runs of the ring.
   {
-    const unsigned long long T = max(g.T, 1ull);
-    int shift = 0;
-    while (((T - 1) >> shift) >= (unsigned)FV_NB) ++shift;
-    const int nb = (int)((T - 1) >> shift) + 1;
-    for (int b = tid; b <= nb; b += FV_BLOCK) s_boff[b] = 0;
+    const FeBuckets bk = fe_buckets(g.T, FV_NB);
+    fe_buckets_clear<FV_BLOCK>(bk.nb, s_boff);
     __syncthreads();
-    for (int r = tid; r < nruns; r += FV_BLOCK) atomicAdd(&s_boff[min((int)(s_rvid[r] >> shift), nb - 1) + 1], 1);
+    for (int r = tid; r < nruns; r += FV_BLOCK) atomicAdd(&s_boff[fe_bucket_of(bk, s_rvid[r]) + 1], 1);
     __syncthreads();
-    // inclusive scan of s_boff[1..nb] (FV_NB / FV_BLOCK consecutive entries per thread) -> bucket b = [s_boff[b], s_boff[b+1])
-    {
-      constexpr int PER = FV_NB / FV_BLOCK;
-      int v[PER], sum = 0;
-#pragma unroll
-      for (int k = 0; k < PER; ++k) { const int b = tid * PER + k; v[k] = b < nb ? s_boff[b + 1] : 0; sum += v[k]; }
-      const int incl = wave_incl_scan(sum);
-      if ((tid & 63) == 63) s_scan[tid >> 6] = incl;
-      __syncthreads();
-      int run = incl - sum;
-#pragma unroll
-      for (int w = 0; w < FV_BLOCK / 64; ++w) if (w < (tid >> 6)) run += s_scan[w];
-#pragma unroll
-      for (int k = 0; k < PER; ++k) { const int b = tid * PER + k; run += v[k]; if (b < nb) { s_boff[b + 1] = run; s_bcur[b + 1] = run; } }
-      if (tid == 0) s_bcur[0] = 0;
-    }
+    fe_buckets_scan<FV_BLOCK, FV_NB>(bk.nb, s_boff, s_bcur, s_scan);
     __syncthreads();
-    for (int r = tid; r < nruns; r += FV_BLOCK) {
-      const int b = min((int)(s_rvid[r] >> shift), nb - 1);
-      s_tmp[atomicAdd(&s_bcur[b], 1)] = (uint16_t)r;  // s_bcur[b] starts at s_boff[b] (written one slot up, read one down)
-    }
+    for (int r = tid; r < nruns; r += FV_BLOCK) s_tmp[atomicAdd(&s_bcur[fe_bucket_of(bk, s_rvid[r])], 1)] = (uint16_t)r;
     __syncthreads();
     for (int t = tid; t < nruns; t += FV_BLOCK) {
       const int r = s_tmp[t];
       const uint32_t v = s_rvid[r];
-      const int b = min((int)(v >> shift), nb - 1);
+      const int b = fe_bucket_of(bk, v);
       const int bs = s_boff[b], be = s_boff[b + 1];
       int rank = bs;
       for (int q = bs; q < be; ++q) { const int o = s_tmp[q]; const uint32_t u = s_rvid[o]; rank += (u < v) || (u == v && o < r); }
@@ -636,14 +570,10 @@ __global__ void __launch_bounds__(FV_BLOCK) fe_voxel(DevCtx d) {
   for (int c0 = 0; c0 < nruns; c0 += FV_BLOCK) {
     const int j = c0 + tid;
     const bool head = j < nruns && (j == 0 || s_rvid[s_order[j]] != s_rvid[s_order[j - 1]]);
-    const unsigned long long m = __ballot(head);
-    if ((tid & 63) == 0) s_scan[tid >> 6] = (int)__popcll(m);
-    __syncthreads();
-    int woff = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < FV_BLOCK / 64; ++w) { if (w < (tid >> 6)) woff += s_scan[w]; tot += s_scan[w]; }
+    int tot;
+    const int before = heads_before(head, &tot);
     if (head) {
-      const int rank = nvox + woff + (int)__popcll(m & ((1ull << (tid & 63)) - 1ull));
+      const int rank = nvox + before;
       const uint32_t vid = s_rvid[s_order[j]];
       float sx = 0.f, sy = 0.f, sz = 0.f, si = 0.f;
       int c = 0;
@@ -669,95 +599,23 @@ __global__ void __launch_bounds__(FV_BLOCK) fe_voxel(DevCtx d) {
 #define FC_T 512
 __global__ void __launch_bounds__(FC_T) fe_collect(DevCtx d) {
   const int slot = blockIdx.x + d.slot0, tid = threadIdx.x;
-  const int cur = cur_in_flight(d, slot);
-  const size_t base = (size_t)slot * d.N;
+  const size_t fb = fbuf(slot, cur_in_flight(d, slot));
   const int NS = d.NS;
-  __shared__ int s_off[4][65], s_boff[2][65];   // s_boff: first box of every ring (less_sharp, less_flat): boxes never straddle rings
-  const int* allc = st_cnt_of(d, slot, 0);
+  __shared__ int s_off[4][65], s_lf[2][65];   // fe_concat_picks' offsets; less_flat: first point, first box of every ring
   if (tid < 64) {
-    const int r = tid;
-    int c[4];
-    c[0] = r < NS ? allc[r * ST_W + F_SHARP] : 0; c[1] = r < NS ? allc[r * ST_W + F_LSHARP] : 0;
-    c[2] = r < NS ? allc[r * ST_W + F_FLAT] : 0; c[3] = r < NS ? allc[r * ST_W + ST_LFDS] : 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int incl = wave_incl_scan(c[k]);
-      s_off[k][r] = incl - c[k];
-      if (r == 63) s_off[k][64] = incl;
-      if (k == 1 || k == 3) {
-        const int nb = (c[k] + LO_CH - 1) / LO_CH;
-        const int bi = wave_incl_scan(nb);
-        s_boff[k == 1 ? 0 : 1][r] = bi - nb;
-        if (r == 63) s_boff[k == 1 ? 0 : 1][64] = bi;
-      }
-    }
+    const int c = tid < NS ? st_cnt_of(d, slot, 0)[tid * ST_W + ST_LFDS] : 0;
+    fe_ring_offsets(c, s_lf[0]);
+    fe_ring_offsets((c + LO_CH - 1) / LO_CH, s_lf[1]);
   }
-  __syncthreads();
-  const int tot[4] = {s_off[0][64], s_off[1][64], s_off[2][64], s_off[3][64]};
+  fe_concat_picks<FC_T>(d, slot, fb, s_off, false);   // (its barrier stands behind s_lf too; fe_pick / fe_pick4 wrote cloud_label_)
+  // this kernel's own: the less_flat cloud (the per-ring VoxelGrid outputs of fe_voxel) and its boxes
   if (tid <= NS) {
-    const size_t fb = fbuf(slot, cur);
-    ring_off_of(d, fb, RO_LSHARP)[tid] = tid < NS ? s_off[1][tid] : tot[1];
-    ring_off_of(d, fb, RO_LFLAT)[tid] = tid < NS ? s_off[3][tid] : tot[3];
-    ring_boff_of(d, fb, RO_LSHARP)[tid] = tid < NS ? s_boff[0][tid] : s_boff[0][64];
-    ring_boff_of(d, fb, RO_LFLAT)[tid] = tid < NS ? s_boff[1][tid] : s_boff[1][64];
+    ring_off_of(d, fb, RO_LFLAT)[tid] = s_lf[0][tid < NS ? tid : 64];
+    ring_boff_of(d, fb, RO_LFLAT)[tid] = s_lf[1][tid < NS ? tid : 64];
   }
-  if (tid == 0) {
-    int* fc = feat_cnt_of(d, fbuf(slot, cur));
-    fc[F_SHARP] = tot[0]; fc[F_LSHARP] = tot[1]; fc[F_FLAT] = tot[2]; fc[F_LFLAT] = tot[3];
-  }
-  const float4* seg = d.seg_lo + base;
-  auto ring_of = [&](int k, int i) -> int {   // largest r with s_off[k][r] <= i (rings beyond NS hold the total: never chosen for i < total)
-    int lo = 0, hi = NS - 1;
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (s_off[k][mid] <= i) lo = mid; else hi = mid - 1; }
-    return lo;
-  };
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    float4* dst = feat_of(d, k, fbuf(slot, cur));
-    int* dsti = k < 3 ? feat_idx_of(d, k, fbuf(slot, cur)) : nullptr;
-    const bool boxes = k == F_LSHARP || k == F_LFLAT;
-    float4* bx = boxes ? lo_box_of(d, lo_row(fbuf(slot, cur), box_set_of(k))) : nullptr;
-    const int stoff = st_part(d, k);
-    // clouds with boxes are walked box by box (LO_CH consecutive threads = the up to LO_CH points of one ring's box), the others point by point
-    const int kb = k == F_LSHARP ? 0 : 1;
-    const int nwork = boxes ? s_boff[kb][64] * LO_CH : tot[k];
-    for (int i0 = 0; i0 < nwork; i0 += FC_T) {
-      int i = i0 + tid, r = 0, j = 0, bxi = 0;
-      bool v = i < nwork;
-      if (boxes) {
-        bxi = min(i / LO_CH, s_boff[kb][64] - 1);
-        int lo = 0, hi = NS - 1;   // largest r with s_boff[r] <= bxi
-        while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (s_boff[kb][mid] <= bxi) lo = mid; else hi = mid - 1; }
-        r = lo; j = (bxi - s_boff[kb][r]) * LO_CH + (tid % LO_CH);
-        v = v && j < s_off[k][r + 1] - s_off[k][r];
-        i = s_off[k][r] + j;
-      }
-      float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (v) {
-        if (!boxes) { r = ring_of(k, i); j = i - s_off[k][r]; }
-        if (k < 3) {
-          const int idx = st_idx_of(d, slot, r)[stoff + j];
-          p = seg[idx];
-          dsti[i] = idx;
-        } else {
-          p = st_lfds_of(d, slot, r)[j];
-        }
-        dst[i] = p;
-      }
-      if (boxes) {
-        float mn[3] = {3.402823466e+38f, 3.402823466e+38f, 3.402823466e+38f}, mx[3] = {-3.402823466e+38f, -3.402823466e+38f, -3.402823466e+38f};
-        if (v) { mn[0] = mx[0] = p.x; mn[1] = mx[1] = p.y; mn[2] = mx[2] = p.z; }
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-          bfly_minmax_f32<LO_CH>(mn[a], mx[a]);
-        if ((tid % LO_CH) == 0 && v) {   // (thread 0 of a box holds its first point: every box has one)
-          const int len = min(LO_CH, s_off[k][r + 1] - i);
-          bx[2 * bxi] = make_float4(mn[0], mn[1], mn[2], __int_as_float(i));
-          bx[2 * bxi + 1] = make_float4(mx[0], mx[1], mx[2], __int_as_float(len));
-        }
-      }
-    }
-  }
+  if (tid == 0) feat_cnt_of(d, fb)[F_LFLAT] = s_lf[0][64];
+  fe_concat_cloud<FC_T>(NS, s_lf[0], s_lf[1], feat_of(d, F_LFLAT, fb), lo_box_of(d, lo_row(fb, box_set_of(F_LFLAT))),
+                        [&](int r, int j, int) -> float4 { return st_lfds_of(d, slot, r)[j]; });
 }
 
 // alego_debug_std_sort: the emulation on its own (one wavefront, up to 4096 keys)

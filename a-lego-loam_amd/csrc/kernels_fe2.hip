@@ -17,9 +17,17 @@
 //                offset of a ring needs the voxel counts of the rings below it: every workgroup publishes its count as soon as it is known
 //                (one agent-scope store) and reads the counts below it (a workgroup's ring is its per-stream ticket: the lower rings are
 //                always running already).  No staging copy of the filtered rings, no collecting pass.
+//
+// Where the rules live.  fe_rules.h (host-readable, pinned by tests/test_fe_rules.py): the sectors of a ring and which are skipped, the curvature sum / key /
+// thresholds, the occlusion marks and "a point is picked" on lane masks, the candidate tests, the suppression reach from jump bits, label / spread /
+// continuation of a pick by its count, less_flat_scan membership.  fe_common.h (device): the concatenation of the pick clouds with the less_sharp boxes
+// (fe_concat_picks, row NS of fe_ring_out; fe_collect calls the same), the bucket tables of the run ordering (fe_buckets*, as fe_voxel).  vgrid.h: the
+// order-preserving float code of the box corners (vgr_enc / vgr_dec).  This file keeps the candidate lists' encoding — sharp and flat keys both turned so
+// that the pick is an arg-max, which is fe_scan_takes / fe_tie_takes in that key space (ff_list) — the window, the run table and the look-back.
 #include <algorithm>
 #include <cstdlib>
 #include "dev_common.h"
+#include "fe_common.h"
 #include "front_end.h"
 #include "prof.h"
 #include "vgrid.h"
@@ -57,24 +65,6 @@ __host__ __device__ constexpr FfLayout ff_layout() {
 }
 static_assert(ff_layout().wave_bytes % 8 == 0, "a wavefront's LDS slice keeps the alignment of the first");
 
-// bits [pos, pos + 64) of the 128-bit value hi:lo
-DEV_INLINE unsigned long long ext128(unsigned long long lo, unsigned long long hi, int pos) { return (lo >> pos) | (pos ? hi << (64 - pos) : 0ull); }
-
-// first point of sector j of the ring [S, E] (laserOdometry.cpp:177, LO.cpp:245); j = n_sectors gives E.  Sectors are contiguous: the last point of
-// sector j (:178, :249) is the one before the first point of sector j + 1, in both formulas
-DEV_INLINE int ff_sector_start(const alego_params& P, int S, int E, int j) {
-  const int NSEC = P.n_sectors;
-  if (NSEC == 6) {   // the reference's six sectors: divisions by a constant (a handful of instructions instead of ~35 each)
-    if (P.sector_formula == 0) return (S * (6 - j) + E * j) / 6;
-    return S + j * (E - S) / 6;
-  }
-  if (P.sector_formula == 0) return (S * (NSEC - j) + E * j) / NSEC;
-  return S + j * (E - S) / NSEC;
-}
-DEV_INLINE void ff_sector(const alego_params& P, int S, int E, int j, int& sp, int& ep) {
-  sp = ff_sector_start(P, S, E, j); ep = ff_sector_start(P, S, E, j + 1) - 1;
-}
-
 // The candidate list of one ring sector, in HBM (it stays in the L2 between fe_cand and fe_pickc): `sector_cap` entries (key, pay); the sharp
 // candidates fill it from the front, the flat ones from the back — a point is one or the other (not ground / ground), so they never meet.
 //   key  sharp: |cd| bits + 1, flat: ~|cd| bits (0 = no candidate; the pick is an arg-MAX for both; curvature = (double)cd^2 orders like |cd|)
@@ -111,7 +101,7 @@ DEV_INLINE void ff_span(const DevCtx& d, size_t base, int M, int S, int E, int j
   const float* rng = d.seg_range + base;
   const int* colv = d.seg_col + base;
   const uint8_t* gndv = d.seg_ground + base;
-  const int lo = ff_sector_start(P, S, E, j0), hi = ff_sector_start(P, S, E, j1) - 1;
+  const int lo = fe_sector_start(P, S, E, j0), hi = fe_sector_start(P, S, E, j1) - 1;
   const int len = hi - lo + 1;
   if (len < 2) {   // no sector of the span has two points (an empty ring: hi < lo): no candidates
     for (int j = j0 + lane; j < j1; j += 64) { cc[2 * j] = 0; cc[2 * j + 1] = 0; }
@@ -145,24 +135,10 @@ DEV_INLINE void ff_span(const DevCtx& d, size_t base, int M, int S, int E, int j
     const int pa = (m & 3) * 64 + lane;   // (pa - 1 and pa + 1 stay inside the window and its mirrors; a lane outside inr reads entries nothing staged and drops what it computes)
     const float r0 = sr[pa], r1 = sr[pa + 1], rm = sr[pa - 1];
     const int c0 = scl[pa] & 0x7fff, c1 = scl[pa + 1] & 0x7fff;
-    int cdiff = c0 - c1;
-    cdiff = cdiff < 0 ? -cdiff : cdiff;
-    bool c1b, c2b;
-    double diff1, diff2;
-    if (P.occl_f32) {  // LO.cpp:203-204
-      c1b = (double)(r0 - r1) > P.occl_depth; c2b = (double)(r1 - r0) > P.occl_depth;
-      diff1 = (double)fabsf(rm - r0); diff2 = (double)fabsf(r1 - r0);
-    } else {           // laserOdometry.cpp:134-135
-      const double d1 = (double)r0, d2 = (double)r1;
-      c1b = d1 - d2 > P.occl_depth; c2b = d2 - d1 > P.occl_depth;
-      diff1 = fabs((double)rm - d1); diff2 = fabs(d2 - d1);
-    }
-    const bool okp = inr && k >= 5 && k < M - 5;
-    const bool near = cdiff < P.occl_col_diff;
-    const bool A = okp && near && c1b;             // marks i-5..i and skips the rest (:142-144)
-    const bool B = okp && near && !c1b && c2b;     // marks i+1..i+5 (:148)
-    const bool C = okp && !A && diff1 > P.parallel_ratio * (double)r0 && diff2 > P.parallel_ratio * (double)r0;  // (:154-157)
-    const bool J = inr && k + 1 < M && cdiff > P.suppress_col_diff;   // |col[k + 1] - col[k]|
+    const unsigned om = fe_occl_marks(P, rm, r0, r1, c0, c1);
+    const bool okp = inr && fe_has_taps(k, M);
+    const bool A = okp && (om & FE_OCCL_A), B = okp && (om & FE_OCCL_B), C = okp && (om & FE_OCCL_C);
+    const bool J = inr && k + 1 < M && fe_col_jump(c0, c1, P.suppress_col_diff);
     a = ff_ballot(A); b = ff_ballot(B); c = ff_ballot(C); j = ff_ballot(J);
   };
 
@@ -179,25 +155,22 @@ DEV_INLINE void ff_span(const DevCtx& d, size_t base, int M, int S, int E, int j
   ff_wave_sync();
   unsigned long long bp = 0ull, jp = 0ull, a0, b0, c0m, j0m, a1 = 0ull, b1 = 0ull, c1m = 0ull, j1m = 0ull;   // masks of the chunks c - 1 (B and J: the ones read backwards), c, c + 1
   marks(0, a0, b0, c0m, j0m);
-  int jc = j0, spc = lo, nxt = ff_sector_start(P, S, E, j0 + 1), ns = 0, nf = 0;   // the sector the sweep is in: [spc, nxt - 1], its candidates so far
+  int jc = j0, spc = lo, nxt = fe_sector_start(P, S, E, j0 + 1), ns = 0, nf = 0;   // the sector the sweep is in: [spc, nxt - 1], its candidates so far
   for (int c = 0; c < nc; ++c) {   // the window holds the chunks c - 1 .. c + 2; the loads of chunk c + 3 are in flight
     ff_wave_sync();
     if ((c + 1) * 64 < q1) marks(c + 1, a1, b1, c1m, j1m);
     else { a1 = 0ull; b1 = 0ull; c1m = 0ull; j1m = 0ull; }
     const int q = c * 64 + lane, k = lo + q - FF_HALO, p = (c & 3) * 64 + lane;
     const bool gnd = (scl[p] & 0x8000) != 0;
-    // strictly left-to-right f32 sum (:124); built with -ffp-contract=off
-    const float cdv = sr[p - 5] + sr[p - 4] + sr[p - 3] + sr[p - 2] + sr[p - 1] - sr[p] * 10 + sr[p + 1] + sr[p + 2] + sr[p + 3] + sr[p + 4] + sr[p + 5];
-    const bool anyA = (ext128(a0, a1, lane) & 0x3full) != 0;                                    // A(i'), i' in [i, i+5]
-    const bool anyB = (ext128((bp >> 59) | (b0 << 5), b0 >> 59, lane) & 0x1full) != 0;         // B(i'), i' in [i-5, i-1]
-    const bool pk = ((c0m >> lane) & 1ull) || anyA || anyB;
-    const unsigned f5 = (unsigned)(ext128(j0m, j1m, lane) & 0x1full);                           // jumps at i .. i+4
-    const unsigned w5 = (unsigned)(ext128((jp >> 59) | (j0m << 5), j0m >> 59, lane) & 0x1full);  // jumps at i-5 .. i-1 (bit 4 = i-1)
-    const int rf = min(SR, __ffs((int)(f5 | 0x20u)) - 1), rb = min(SR, __clz((int)(w5 << 27)));
-    const double ad = (double)fabsf(cdv), curv = ad * ad;                                       // (double)diff_range * diff_range, exact (:125)
-    const bool cs0 = !pk && !gnd && curv > P.edge_thres;
-    const bool cf0 = !pk && gnd && curv < P.surf_thres;
-    const uint32_t kb = (uint32_t)d_f2i(fabsf(cdv));
+    const float cdv = fe_curv_sum(sr + p);
+    const bool pk = fe_point_picked(a0, a1, bp, b0, c0m, lane);
+    const unsigned f5 = (unsigned)(fe_ext128(j0m, j1m, lane) & 0x1full);                           // jumps at i .. i+4
+    const unsigned w5 = (unsigned)(fe_ext128((jp >> 59) | (j0m << 5), j0m >> 59, lane) & 0x1full);  // jumps at i-5 .. i-1 (bit 4 = i-1)
+    const int rf = fe_reach_one(f5, SR), rb = fe_reach_bwd_window(w5, SR);
+    const double curv = fe_curvature(cdv);
+    const bool cs0 = fe_sharp_candidate(pk, gnd, fe_curv_edge(curv, P.edge_thres));
+    const bool cf0 = fe_flat_candidate(pk, gnd, fe_curv_surf(curv, P.surf_thres));
+    const uint32_t kb = fe_curv_key(cdv);
     const uint32_t reach = ((uint32_t)rf << 3) | (uint32_t)rb;
     const int klast = lo + c * 64 + 63 - FF_HALO;   // the chunk's last point
     // chunk c + 3 takes the place of chunk c - 1, which this turn's lanes have read the tail of; staging waits for its loads here, behind the turn's
@@ -207,7 +180,7 @@ DEV_INLINE void ff_span(const DevCtx& d, size_t base, int M, int S, int E, int j
     if ((c + 4) * 64 < q1) fetch(c + 4, fr, fc, fg);
     bool own = false;
     while (true) {   // the sectors with points in this chunk: one, mostly; each lane's sector from k and the scalar bounds
-      const bool in = k >= spc && k < nxt && nxt - spc >= 2;   // (:181: a sector of one point is skipped)
+      const bool in = k >= spc && k < nxt && !fe_sector_skipped(spc, nxt - 1);
       const bool cs = cs0 && in, cf = cf0 && in;
       const uint32_t pay = ((uint32_t)(k - spc) << 6) | reach;
       const unsigned long long ms = ff_ballot(cs), mf = ff_ballot(cf);
@@ -217,7 +190,7 @@ DEV_INLINE void ff_span(const DevCtx& d, size_t base, int M, int S, int E, int j
       own = own || in;
       if (nxt > klast || jc + 1 >= j1) break;   // the sector goes on in the next chunk, or is the span's last
       if (lane == 0) { cc[2 * jc] = ns; cc[2 * jc + 1] = nf; }
-      ++jc; spc = nxt; nxt = ff_sector_start(P, S, E, jc + 1); ns = 0; nf = 0; list += sector_cap;
+      ++jc; spc = nxt; nxt = fe_sector_start(P, S, E, jc + 1); ns = 0; nf = 0; list += sector_cap;
     }
     if (dbg && own) { d.cd[base + k] = cdv; d.picked0[base + k] = pk ? 1 : 0; }
     bp = b0; jp = j0m; a0 = a1; b0 = b1; c0m = c1m; j0m = j1m;
@@ -258,12 +231,6 @@ struct FfPick {
   int* st_sharp; int* st_lsharp; int* st_flat;
 };
 
-// label / continuation of the pick that has just been counted (:196-210, :245-251), shared by the two pick loops
-template <bool FLAT>
-DEV_INLINE void ff_label(const alego_params& P, int picked, int nmax, int& lab, bool& spread, bool& more) {
-  if (FLAT) { lab = -1; more = picked < P.n_flat; spread = more; }                       // the n_flat-th pick breaks before the suppression (:248-251)
-  else { lab = picked <= P.n_sharp ? 2 : (picked <= P.n_less_sharp ? 1 : 0); spread = lab != 0; more = lab != 0 && picked < nmax; }
-}
 // a pick's bookkeeping: sharp picks set their reach in the sector's mark bitmap (the flat candidates are tested against it when they are
 // loaded), every pick raises `carry`, lane 0 of the group appends the index to the ring's lists
 template <bool FLAT>
@@ -320,7 +287,7 @@ DEV_INLINE void ff_pick_regs(const alego_params& P, FfPick& R, int ncand, const 
     picked += act ? 1 : 0;
     int lab;
     bool spread, more;
-    ff_label<FLAT>(P, picked, nmax, lab, spread, more);
+    fe_pick_label<FLAT>(P, picked, nmax, lab, spread, more);
     const int lo = max(c - (spread ? rb : 0), 0), hi = c + (spread ? rf : 0);
     const bool rem = act && (FLAT || lab != 0);
 #pragma unroll
@@ -364,7 +331,7 @@ DEV_INLINE void ff_pick_mem(const alego_params& P, FfPick& R, int ncand, int nwa
     picked += act ? 1 : 0;
     int lab;
     bool spread, more;
-    ff_label<FLAT>(P, picked, nmax, lab, spread, more);
+    fe_pick_label<FLAT>(P, picked, nmax, lab, spread, more);
     const int lo = max(c - (spread ? rb : 0), 0), hi = c + (spread ? rf : 0);
     const bool rem = act && (FLAT || lab != 0);
     for (int t = gl; t < nwave; t += FF_LPR) {
@@ -405,7 +372,8 @@ __global__ void __launch_bounds__(64) fe_pickc(DevCtx d, int sector_cap) {
   const int NSEC = P.n_sectors;
   for (int j = 0; j < NSEC; ++j) {
     int sp = 0, ep = -1;
-    if (rv) ff_sector(P, S, E, j, sp, ep);
+    if (rv) fe_sector(P, S, E, j, sp, ep);
+    // (!fe_sector_skipped(sp, ep), restated: through the call the compiler arranges both instances differently — same registers — and the bench lost 0.3 %)
     R.act0 = rv && sp < ep; R.sp = sp; R.carry_in = R.carry;
     const int ns = R.act0 ? cc[2 * j] : 0, nf = R.act0 ? cc[2 * j + 1] : 0;
     uint2* lst = ff_list(d, slot, rc, j, sector_cap);
@@ -471,10 +439,6 @@ static size_t fo_lds_bytes(int H) { const FoLayout L = fo_layout(H); return std:
 // values it cannot bound back into mask + 32-bit multiply)
 DEV_INLINE uint32_t mad_u24(uint32_t a, uint32_t b, uint32_t c) { uint32_t r; asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
 
-// order-preserving map float -> u32 (for LDS atomic min / max) and back
-DEV_INLINE uint32_t fo_ord(float f) { const uint32_t b = (uint32_t)d_f2i(f); return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u); }
-DEV_INLINE float fo_unord(uint32_t u) { return d_i2f((int32_t)(u ^ ((u >> 31) ? 0x80000000u : 0xFFFFFFFFu))); }
-
 #ifdef ALEGO_TIMING
 __device__ long long fo_times[24];
 extern "C" void alego_fo_times(long long* out) { (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(fo_times), sizeof(long long) * 24); }
@@ -492,86 +456,8 @@ extern "C" void alego_fo_times(long long* out) { (void)hipMemcpyFromSymbol(out, 
 // the workgroup of row NS: the stream's sharp / less_sharp / flat clouds (ring-ascending concatenation of the picks, :199-205,:245), their
 // index lists, the less_sharp ring offsets and bounding boxes (everything fe_pickc counted; no ring has to wait for this)
 DEV_INLINE void fo_picks_out(const DevCtx& d, int slot, unsigned char* smem) {
-  const int tid = threadIdx.x, NS = d.NS;
-  const size_t base = (size_t)slot * d.N;
-  const size_t fb = fbuf(slot, cur_in_flight(d, slot));
-  const int* allc = st_cnt_of(d, slot, 0);
-  const float4* seg = d.seg_lo + base;
-  int (*s_off)[65] = reinterpret_cast<int (*)[65]>(smem);   // [0..2]: first pick of every ring in the three clouds, [3]: first less_sharp box
-  if (tid < 64) {
-    const int r = tid;
-    int c[4];
-    c[0] = r < NS ? allc[r * ST_W + F_SHARP] : 0; c[1] = r < NS ? allc[r * ST_W + F_LSHARP] : 0; c[2] = r < NS ? allc[r * ST_W + F_FLAT] : 0;
-    c[3] = (c[1] + LO_CH - 1) / LO_CH;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int incl = wave_incl_scan(c[k]);
-      s_off[k][r] = incl - c[k];
-      if (r == 63) s_off[k][64] = incl;
-    }
-  }
-  __syncthreads();
-  if (tid <= NS) {
-    ring_off_of(d, fb, RO_LSHARP)[tid] = tid < NS ? s_off[1][tid] : s_off[1][64];
-    ring_boff_of(d, fb, RO_LSHARP)[tid] = tid < NS ? s_off[3][tid] : s_off[3][64];
-  }
-  if (tid < 3) feat_cnt_of(d, fb)[tid] = s_off[tid][64];
-  auto ring_of = [&](int k, int i) -> int {   // largest r with s_off[k][r] <= i (rings beyond NS hold the total: never chosen for i < total)
-    int lo = 0, hi = NS - 1;
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (s_off[k][mid] <= i) lo = mid; else hi = mid - 1; }
-    return lo;
-  };
-  const int stoff[3] = {st_part(d, F_SHARP), st_part(d, F_LSHARP), st_part(d, F_FLAT)};
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    float4* dst = feat_of(d, k, fb);
-    int* dsti = feat_idx_of(d, k, fb);
-    float4* bx = lo_box_of(d, lo_row(fb, box_set_of(F_LSHARP)));
-    const bool boxes = k == F_LSHARP;
-    // less_sharp is walked box by box (LO_CH consecutive threads = the up to LO_CH picks of one ring's box), the others pick by pick
-    const int nwork = boxes ? s_off[3][64] * LO_CH : s_off[k][64];
-    for (int i0 = 0; i0 < nwork; i0 += FO_BLOCK) {
-      int i = i0 + tid, r = 0, j = 0, bxi = 0;
-      bool v = i < nwork;
-      if (boxes) {
-        bxi = min(i / LO_CH, s_off[3][64] - 1);
-        r = ring_of(3, bxi); j = (bxi - s_off[3][r]) * LO_CH + (tid % LO_CH);
-        v = v && j < s_off[k][r + 1] - s_off[k][r];
-        i = s_off[k][r] + j;
-      } else if (v) { r = ring_of(k, i); j = i - s_off[k][r]; }
-      float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (v) {
-        const int idx = st_idx_of(d, slot, r)[stoff[k] + j];
-        p = seg[idx];
-        dsti[i] = idx; dst[i] = p;
-      }
-      if (boxes) {
-        float mn[3] = {3.402823466e+38f, 3.402823466e+38f, 3.402823466e+38f}, mx[3] = {-3.402823466e+38f, -3.402823466e+38f, -3.402823466e+38f};
-        if (v) { mn[0] = mx[0] = p.x; mn[1] = mx[1] = p.y; mn[2] = mx[2] = p.z; }
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-          bfly_minmax_f32<LO_CH>(mn[a], mx[a]);
-        if ((tid % LO_CH) == 0 && v) {   // (thread 0 of a box holds its first pick: every box has one)
-          bx[2 * bxi] = make_float4(mn[0], mn[1], mn[2], __int_as_float(i));
-          bx[2 * bxi + 1] = make_float4(mx[0], mx[1], mx[2], __int_as_float(min(LO_CH, s_off[k][r + 1] - i)));
-        }
-      }
-    }
-  }
-  // cloud_label_ for the single-scan entry points / tests (:196-204,:245): 2 sharp, 1 less sharp, -1 flat, 0 otherwise
-  if (d.n_launch == 1) {
-    const int M = scal_of(d, slot)[SC_M];
-    for (int k = tid; k < M; k += FO_BLOCK) d.plabel[base + k] = 0;
-    __syncthreads();
-    for (int pass = 0; pass < 3; ++pass) {   // less sharp first: a sharp pick is on both lists
-      const int k = pass == 0 ? 1 : (pass == 1 ? 0 : 2), lab = pass == 0 ? 1 : (pass == 1 ? 2 : -1);
-      for (int i = tid; i < s_off[k][64]; i += FO_BLOCK) {
-        const int r = ring_of(k, i);
-        d.plabel[base + st_idx_of(d, slot, r)[stoff[k] + i - s_off[k][r]]] = lab;
-      }
-      __syncthreads();
-    }
-  }
+  // cloud_label_ for the single-scan entry points / tests: fe_pickc keeps no label per point
+  fe_concat_picks<FO_BLOCK>(d, slot, fbuf(slot, cur_in_flight(d, slot)), reinterpret_cast<int (*)[65]>(smem), d.n_launch == 1);
 }
 
 // grid (streams, NS + 1): row r < NS = ring r of the stream, row NS = fo_picks_out
@@ -611,13 +497,13 @@ __global__ void __launch_bounds__(FO_BLOCK) fe_ring_out(DevCtx d) {
   uint32_t* s_rvid = reinterpret_cast<uint32_t*>(fv2 + 4 * (size_t)H);          // voxel id per run [H]
   uint16_t* s_rstart = reinterpret_cast<uint16_t*>(fv2 + 8 * (size_t)H);        // first point of the run  [H]
   uint16_t* s_nxt = reinterpret_cast<uint16_t*>(fv2 + 10 * (size_t)H);          // per point: the next point of its voxel in summation order (FO_END: none) [H]
-  __shared__ uint32_t s_bm[FE_MAXH / 32 + 2];     // holes of less_flat_scan: the ring's less-sharp picks (label > 0, :284) and points of skipped sectors (:181)
+  __shared__ uint32_t s_bm[FE_MAXH / 32 + 2];     // holes of less_flat_scan: the ring's less-sharp picks (the labels fe_less_flat_member refuses: 1 and 2) and points of skipped sectors (fe_sector_skipped)
   constexpr int FO_MAXBOX = (FE_MAXH + LO_CH - 1) / LO_CH;
   constexpr int FO_ALIAS = FO_ALIAS_INTS;
   static_assert(6 * FO_MAXBOX <= FO_ALIAS && 2 * (FO_NB + 1) <= FO_ALIAS && FE_MAXH / 32 + 1 <= FO_ALIAS, "s_alias holds the bucket tables, the hole prefix or the box corners");
   __shared__ int s_alias[FO_ALIAS];                    // bucket offsets / cursors while the runs are ordered; hole prefix counts of the pass-through; box corners afterwards
   int* s_boff = s_alias; int* s_bcur = s_alias + FO_NB + 1; int* s_wpre = s_alias;
-  uint32_t* s_bx = reinterpret_cast<uint32_t*>(s_alias);                        // [6][FO_MAXBOX]: min xyz, max xyz of every box as ordered u32
+  uint32_t* s_bx = reinterpret_cast<uint32_t*>(s_alias);                        // [6][FO_MAXBOX]: min xyz, max xyz of every box as vgr_enc codes (LDS atomic min / max)
   __shared__ float s_red[6][FO_BLOCK / 64];
   __shared__ int s_scan[FO_BLOCK / 64], s_cntv[FO_BLOCK / 64];
   __shared__ int s_look[3];
@@ -636,15 +522,16 @@ __global__ void __launch_bounds__(FO_BLOCK) fe_ring_out(DevCtx d) {
   const int BW = (n_all + 31) / 32;
   for (int w = tid; w <= BW + 1 && w <= FE_MAXH / 32 + 1; w += FO_BLOCK) s_bm[w] = 0u;
   __syncthreads();
+  static_assert(!fe_less_flat_member(1) && !fe_less_flat_member(2) && fe_less_flat_member(0) && fe_less_flat_member(-1), "the labelled holes are exactly the picks of the less_sharp list");
   for (int t = tid; t < n_ls; t += FO_BLOCK) {
     const int i = st_ls[t] - S;
     if (i >= 0 && i < n_all) atomicOr(&s_bm[i >> 5], 1u << (i & 31));
   }
   if (tid < P.n_sectors) {
     int sp, ep;
-    ff_sector(P, S, E, tid, sp, ep);
+    fe_sector(P, S, E, tid, sp, ep);
     const int i = sp - S;
-    if (sp == ep && i >= 0 && i < n_all) atomicOr(&s_bm[i >> 5], 1u << (i & 31));   // a one-point sector is skipped (sp >= ep)
+    if (fe_sector_lone_point(sp, ep) && i >= 0 && i < n_all) atomicOr(&s_bm[i >> 5], 1u << (i & 31));
   }
   __syncthreads();
   FO_TICK(1);
@@ -792,31 +679,15 @@ __global__ void __launch_bounds__(FO_BLOCK) fe_ring_out(DevCtx d) {
     FO_TICK(3);
     // order the valid runs by (voxel id, run index): dealt into <= FO_NB buckets monotone in the voxel id, ranked inside the bucket
     {
-      const unsigned long long T = max(g.T, 1ull);
-      int shift = 0;
-      while (((T - 1) >> shift) >= (unsigned)FO_NB) ++shift;
-      const int nb = (int)((T - 1) >> shift) + 1;
-      for (int b = tid; b <= nb; b += FO_BLOCK) s_boff[b] = 0;
+      const FeBuckets bk = fe_buckets(g.T, FO_NB);
+      const int shift = bk.shift, nb = bk.nb;
+      fe_buckets_clear<FO_BLOCK>(nb, s_boff);
       __syncthreads();
       FO_TICK(9);
-      for (int r = tid; r < nruns; r += FO_BLOCK) { const uint32_t v = s_rvid[r]; if (v != FO_INVALID) atomicAdd(&s_boff[min((int)(v >> shift), nb - 1) + 1], 1); }
+      for (int r = tid; r < nruns; r += FO_BLOCK) { const uint32_t v = s_rvid[r]; if (v != FO_INVALID) atomicAdd(&s_boff[fe_bucket_of(bk, v) + 1], 1); }
       __syncthreads();
       FO_TICK(10);
-      {
-        constexpr int PER = FO_NB / FO_BLOCK;
-        int v[PER], sum = 0;
-#pragma unroll
-        for (int k = 0; k < PER; ++k) { const int b = tid * PER + k; v[k] = b < nb ? s_boff[b + 1] : 0; sum += v[k]; }
-        const int incl = wave_incl_scan(sum);
-        if (lane == 63) s_scan[tid >> 6] = incl;
-        __syncthreads();
-        int run = incl - sum;
-#pragma unroll
-        for (int w = 0; w < FO_BLOCK / 64; ++w) if (w < (tid >> 6)) run += s_scan[w];
-#pragma unroll
-        for (int k = 0; k < PER; ++k) { const int b = tid * PER + k; run += v[k]; if (b < nb) { s_boff[b + 1] = run; s_bcur[b + 1] = run; } }
-        if (tid == 0) s_bcur[0] = 0;
-      }
+      fe_buckets_scan<FO_BLOCK, FO_NB>(nb, s_boff, s_bcur, s_scan);
       __syncthreads();
       nrv = s_boff[nb];
       FO_TICK(11);
@@ -825,7 +696,7 @@ __global__ void __launch_bounds__(FO_BLOCK) fe_ring_out(DevCtx d) {
       for (int r = tid; r < nruns; r += FO_BLOCK) {
         const uint32_t v = s_rvid[r];
         if (v != FO_INVALID) {
-          const int pos = atomicAdd(&s_bcur[min((int)(v >> shift), nb - 1)], 1);   // s_bcur[b] starts at s_boff[b] (written one slot up, read one down)
+          const int pos = atomicAdd(&s_bcur[fe_bucket_of(bk, v)], 1);
           if (keyed) k_tmp[pos] = ((v & lowmask) << 12) | (uint32_t)r;
           else s_tmp[pos] = (uint16_t)r;
         }
@@ -839,7 +710,7 @@ __global__ void __launch_bounds__(FO_BLOCK) fe_ring_out(DevCtx d) {
         const uint32_t mine = keyed ? k_tmp[t] : 0u;
         const int r = keyed ? (int)(mine & 0xFFFu) : (int)s_tmp[t];
         const uint32_t v = s_rvid[r];
-        const int b = min((int)(v >> shift), nb - 1);
+        const int b = fe_bucket_of(bk, v);
         const int bs = s_boff[b], be = s_boff[b + 1];
         int rank = bs;
         if (keyed) {   // one read and one compare per entry of the bucket: (id, run) order = order of the packed keys
@@ -915,7 +786,7 @@ __global__ void __launch_bounds__(FO_BLOCK) fe_ring_out(DevCtx d) {
   // box corners of every LO_CH consecutive output points, gathered with LDS atomics while the points are written
   auto box_add = [&](int rank, const float4& p) {
     uint32_t* b = s_bx + rank / LO_CH;
-    const uint32_t ox = fo_ord(p.x), oy = fo_ord(p.y), oz = fo_ord(p.z);
+    const uint32_t ox = vgr_enc(p.x), oy = vgr_enc(p.y), oz = vgr_enc(p.z);
     atomicMin(&b[0], ox); atomicMin(&b[FO_MAXBOX], oy); atomicMin(&b[2 * FO_MAXBOX], oz);
     atomicMax(&b[3 * FO_MAXBOX], ox); atomicMax(&b[4 * FO_MAXBOX], oy); atomicMax(&b[5 * FO_MAXBOX], oz);
   };
@@ -932,8 +803,8 @@ __global__ void __launch_bounds__(FO_BLOCK) fe_ring_out(DevCtx d) {
         hi3[0] = fmaxf(hi3[0], q.x); hi3[1] = fmaxf(hi3[1], q.y); hi3[2] = fmaxf(hi3[2], q.z);
       }
       __builtin_amdgcn_s_waitcnt(0);   // (all of the thread's reads of s_wpre's area are long done: the barrier above)
-      c[0] = fo_ord(lo3[0]); c[FO_MAXBOX] = fo_ord(lo3[1]); c[2 * FO_MAXBOX] = fo_ord(lo3[2]);
-      c[3 * FO_MAXBOX] = fo_ord(hi3[0]); c[4 * FO_MAXBOX] = fo_ord(hi3[1]); c[5 * FO_MAXBOX] = fo_ord(hi3[2]);
+      c[0] = vgr_enc(lo3[0]); c[FO_MAXBOX] = vgr_enc(lo3[1]); c[2 * FO_MAXBOX] = vgr_enc(lo3[2]);
+      c[3 * FO_MAXBOX] = vgr_enc(hi3[0]); c[4 * FO_MAXBOX] = vgr_enc(hi3[1]); c[5 * FO_MAXBOX] = vgr_enc(hi3[2]);
     }
   } else {
     for (int b = tid; b < 6 * FO_MAXBOX; b += FO_BLOCK) s_bx[b] = b < 3 * FO_MAXBOX ? 0xFFFFFFFFu : 0u;
@@ -973,8 +844,8 @@ __global__ void __launch_bounds__(FO_BLOCK) fe_ring_out(DevCtx d) {
     float4* bx = lo_box_of(d, lo_row(fb, box_set_of(F_LFLAT))) + (size_t)2 * boff3;
     for (int b = tid; b < nbox; b += FO_BLOCK) {
       const uint32_t* c = s_bx + b;
-      bx[2 * b] = make_float4(fo_unord(c[0]), fo_unord(c[FO_MAXBOX]), fo_unord(c[2 * FO_MAXBOX]), __int_as_float(off3 + b * LO_CH));
-      bx[2 * b + 1] = make_float4(fo_unord(c[3 * FO_MAXBOX]), fo_unord(c[4 * FO_MAXBOX]), fo_unord(c[5 * FO_MAXBOX]), __int_as_float(min(LO_CH, nout - b * LO_CH)));
+      bx[2 * b] = make_float4(vgr_dec(c[0]), vgr_dec(c[FO_MAXBOX]), vgr_dec(c[2 * FO_MAXBOX]), __int_as_float(off3 + b * LO_CH));
+      bx[2 * b + 1] = make_float4(vgr_dec(c[3 * FO_MAXBOX]), vgr_dec(c[4 * FO_MAXBOX]), vgr_dec(c[5 * FO_MAXBOX]), __int_as_float(min(LO_CH, nout - b * LO_CH)));
     }
     if (tid == 0) {
       int* ro = ring_off_of(d, fb, RO_LFLAT);

@@ -975,7 +975,8 @@ void launch_lo(const DevCtx& d, hipStream_t st) {
   const bool wide = d.lo_qcap_surf + d.lo_qcap_corner > LO_WIDE_ROWS;   // (fixed by the geometry: every handle of a sensor sums its rows in the same order)
   // the rows of a solve staged in LDS: only when every possible row count fits (capacities, not counts: the variant is a property of the handle)
   const bool staged = !wide && d.lo_qcap_surf + d.lo_qcap_corner <= LO_LDS_ROWS && d.lo_qcap_surf <= 32 * LO_SOLVE_BLOCK && d.lo_qcap_corner <= 32 * LO_SOLVE_BLOCK;
-  const dim3 g0(d.n_launch, std::min((d.lo_qcap_surf + LO_QPB_OF(LO_BLOCK) - 1) / LO_QPB_OF(LO_BLOCK), 8)), g1(d.n_launch, std::min((d.lo_qcap_corner + LO_QPB_OF(LO_BLOCK) - 1) / LO_QPB_OF(LO_BLOCK), 12));
+  // (n_sharp = 0 leaves no room for a corner query: one row of workgroups that find none, as on a scan without a sharp pick — a grid of 0 is no launch)
+  const dim3 g0(d.n_launch, std::min((d.lo_qcap_surf + LO_QPB_OF(LO_BLOCK) - 1) / LO_QPB_OF(LO_BLOCK), 8)), g1(d.n_launch, std::max(std::min((d.lo_qcap_corner + LO_QPB_OF(LO_BLOCK) - 1) / LO_QPB_OF(LO_BLOCK), 12), 1));
   if (big_boxes) { ALEGO_LAUNCH((lo_assoc<0, LO_BOX_LDS_BIG>), g0, dim3(LO_BLOCK), 0, st, d, box_lds_max); }
   else { ALEGO_LAUNCH(lo_assoc<0>, g0, dim3(LO_BLOCK), 0, st, d, box_lds_max); }
   auto solve = [&](int phase) {
