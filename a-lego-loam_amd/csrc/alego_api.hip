@@ -20,6 +20,7 @@
 #include "lm_ctx.h"
 #include "lm_host.h"
 #include "merge_math.h"
+#include "nn_rules.h"
 #include "thin_math.h"
 #include "loop_ctx.h"
 #include "pgraph.h"
@@ -1062,12 +1063,11 @@ int alego_loop_detect(const alego_params* P, const float* keyposes6, const doubl
   // detectLoopClosure :771-790 (pcl::KdTreeFLANN::radiusSearch: f32 squared distances, ascending; ties by index)
   if (!P || n <= 0 || !keyposes6 || !stamps || !cur_xyz) return -1;
   const float cx = (float)cur_xyz[0], cy = (float)cur_xyz[1], cz = (float)cur_xyz[2];
-  const float r2 = (float)(P->lc_search_radius * P->lc_search_radius);
+  const float r2 = nn_r2(P->lc_search_radius);
   std::vector<std::pair<float, int>> cand;
   for (int i = 0; i < n; ++i) {
-    float r = 0.f, df;
-    df = keyposes6[i * 6 + 0] - cx; r += df * df; df = keyposes6[i * 6 + 1] - cy; r += df * df; df = keyposes6[i * 6 + 2] - cz; r += df * df;
-    if (r < r2) cand.emplace_back(r, i);
+    const float r = nn_d2(keyposes6[i * 6 + 0], keyposes6[i * 6 + 1], keyposes6[i * 6 + 2], cx, cy, cz);
+    if (nn_in_radius(r, r2)) cand.emplace_back(r, i);
   }
   std::sort(cand.begin(), cand.end());
   for (const auto& c : cand)

@@ -17,13 +17,13 @@
 
 #include "dev_common.h"
 #include "kf_store.h"
+#include "nn_rules.h"
 #include "prof.h"
 #include "voxel.h"
 #include "icp_math.h"
 
 #define ICP_T 256
 #define ICP_TILE 2048
-
 
 struct IcpFrame { float pose[6]; int off[4]; int dst[3]; };   // raw cloud offsets (corner, surf, outlier, end) and destination offsets of the three clouds
 
@@ -40,9 +40,9 @@ __global__ void __launch_bounds__(ICP_T) icp_build(const IcpFrame* frames, int n
   }
 }
 
-// exact 1-NN of p in tgt[0..n): f32 squared distance as flann::L2_Simple, ties -> lowest index; the target goes through LDS in tiles
+// exact 1-NN of p in tgt[0..n): nn_d2, ties -> lowest index, from the pair form's start state (nn_rules.h); the target goes through LDS in tiles
 DEV_INLINE void icp_nn(const float4 p, const float4* tgt, int n, float4* s_tile, float* best_d, int* best_i) {
-  float bd = 3.402823466e+38f;
+  float bd = FLT_MAX;
   int bi = -1;
   for (int t0 = 0; t0 < n; t0 += ICP_TILE) {
     const int m = min(ICP_TILE, n - t0);
@@ -51,9 +51,8 @@ DEV_INLINE void icp_nn(const float4 p, const float4* tgt, int n, float4* s_tile,
     __syncthreads();
     for (int j = 0; j < m; ++j) {
       const float4 q = s_tile[j];
-      float r = 0.f, df;
-      df = q.x - p.x; r += df * df; df = q.y - p.y; r += df * df; df = q.z - p.z; r += df * df;
-      if (r < bd) { bd = r; bi = t0 + j; }
+      const float r = nn_d2(q.x, q.y, q.z, p.x, p.y, p.z);
+      if (r < bd) { bd = r; bi = t0 + j; }   // nn_better for candidates in ascending index: its tie term is never true
     }
   }
   *best_d = bd; *best_i = bi;

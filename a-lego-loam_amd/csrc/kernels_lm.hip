@@ -17,6 +17,7 @@
 
 #include "../../include/alego_mi355x.h"
 #include "dev_cost.h"
+#include "nn_rules.h"
 #include "reg_cov_math.h"
 #include "prof.h"
 #include "kf_store.h"
@@ -179,16 +180,10 @@ __global__ void __launch_bounds__(LM_BLOCK) lm_total(DevCtx d, LmCtx L) {
   if (blockIdx.x == 0 && threadIdx.x == 0) li[LI_NTOTAL] = ns + no;
 }
 
-// The cell of a point is floorf(x * inv) - ox in integers: inv is a power of two, so x * inv and its floor are exact and every point lies in its true
-// cell of a global lattice.  (floorf((x - ox) * inv) with a float origin rounds in the subtraction: across a binade boundary of x - ox a point at
-// f32 d^2 < cell^2 from a query could sit two cells away from it, outside the 27 cells lm_knn searches.)  The float is clamped before the
-// conversion so that any finite input gives a defined int.
-DEV_INLINE int cell_coord(float x, float inv) { return (int)fminf(fmaxf(floorf(x * inv), -1073741824.0f), 1073741824.0f); }
+// the cell of a point in the grid g of nn_rules.h's exact lattice (nn_lm_coord): its coordinates relative to the grid's origin cell and its clamped index
 DEV_INLINE int grid_cell(const GridGeom& g, float x, float y, float z, int* cx, int* cy, int* cz) {
-  int ix = cell_coord(x, g.inv) - g.ox, iy = cell_coord(y, g.inv) - g.oy, iz = cell_coord(z, g.inv) - g.oz;
-  *cx = ix; *cy = iy; *cz = iz;
-  ix = min(max(ix, 0), g.gx - 1); iy = min(max(iy, 0), g.gy - 1); iz = min(max(iz, 0), g.gz - 1);
-  return ix + g.gx * (iy + g.gy * iz);
+  *cx = nn_lm_coord(x, g.inv) - g.ox; *cy = nn_lm_coord(y, g.inv) - g.oy; *cz = nn_lm_coord(z, g.inv) - g.oz;
+  return nn_lm_index(*cx, *cy, *cz, g.gx, g.gy, g.gz);
 }
 
 // grid (2, slots): the whole uniform-grid build of one map by one workgroup — geometry from the VoxelGrid bounding box, cell
@@ -207,15 +202,12 @@ __global__ void __launch_bounds__(LM_BLOCK) lm_grid_build(DevCtx d, LmCtx L) {
     float mn[3], mx[3];
     vgr_box_load(bb, mn, mx);
     if (li[LI_KRAW_C + m] <= 0) { for (int a = 0; a < 3; ++a) { mn[a] = 0.f; mx[a] = 0.f; } }
-    // cell^2 >= knn_max_dist: lm_knn keeps only candidates with f32 d^2 < flim <= cell^2, so |dx| < cell along every axis in real arithmetic
-    // (rounding is monotonic and cell is a power of two) and the candidate is at most one cell away from the query
-    float cell = 1.0f;
-    while ((double)cell * cell < d.P.knn_max_dist) cell *= 2.0f;
+    float cell = nn_lm_cell(d.P.knn_max_dist);   // cell^2 >= knn_max_dist: the 27 cells around a query hold every candidate lm_knn keeps (nn_rules.h)
     // the box is the RAW window's: an f32 voxel centroid can lie an ulp outside it, so one cell of margin on either side keeps every map point
     // unclamped in its true cell
     int lo[3], hi[3];
     for (;;) {
-      for (int a = 0; a < 3; ++a) { lo[a] = cell_coord(mn[a], 1.0f / cell) - 1; hi[a] = cell_coord(mx[a], 1.0f / cell) + 1; }
+      for (int a = 0; a < 3; ++a) { lo[a] = nn_lm_coord(mn[a], 1.0f / cell) - 1; hi[a] = nn_lm_coord(mx[a], 1.0f / cell) + 1; }
       const long long ex = (long long)hi[0] - lo[0] + 1, ey = (long long)hi[1] - lo[1] + 1, ez = (long long)hi[2] - lo[2] + 1;
       if (ex <= L.gcap && ey <= L.gcap && ez <= L.gcap && ex * ey * ez <= (long long)L.gcap) { g.gx = (int)ex; g.gy = (int)ey; g.gz = (int)ez; break; }
       cell *= 2.0f;
@@ -485,11 +477,7 @@ __global__ void __launch_bounds__(128) lm_knn(DevCtx d, LmCtx L) {
   const DQuat qm = ldq(ld + LD_Q_M2L);
   constexpr int QPB = 128 / LM_KNN_LANES;
   const int sub = threadIdx.x & (LM_KNN_LANES - 1);
-  // bit pattern of the smallest f32 f with (double)f >= knn_max_dist: dist < f  <=>  (double)dist < knn_max_dist (:376,:426 accept a query only
-  // when its FIFTH neighbour is closer than that, so farther candidates need not enter the top-5 sets at all)
-  float flim = (float)P.knn_max_dist;
-  if ((double)flim < P.knn_max_dist) flim = __int_as_float(__float_as_int(flim) + 1);
-  const uint32_t limbits = P.knn_max_dist > 0.0 ? (uint32_t)__float_as_int(flim) : 0u;
+  const uint32_t limbits = nn_lm_limit_bits(P.knn_max_dist);   // farther candidates are part of no accepted row: they need not enter the top-5 sets
   // every lane of a wavefront runs the same number of iterations (DPP reads neighbours' registers): clamp, don't exit
   const int nq_round = (nq + QPB - 1) / QPB * QPB;
   for (int qq = bx * QPB + threadIdx.x / LM_KNN_LANES; qq < nq_round; qq += gx * QPB) {
@@ -501,12 +489,11 @@ __global__ void __launch_bounds__(128) lm_knn(DevCtx d, LmCtx L) {
   dq_rotate(qm, vin, r);
   const float sx = (float)(r[0] + ld[LD_T_M2L + 0]), sy = (float)(r[1] + ld[LD_T_M2L + 1]), sz = (float)(r[2] + ld[LD_T_M2L + 2]);
   // exact 5-NN among all points with d^2 < knn_max_dist: they all lie in the 27 surrounding cells (lm_grid_build: cell^2 >= knn_max_dist, exact cell coordinates).
-  // A lane's five best candidates are an UNSORTED set of 64-bit keys (f32 distance bits << 32 | map index: the lexicographic
-  // (distance, index) order is the integer order) with the set's maximum tracked next to it: a candidate that beats the maximum
+  // A lane's five best candidates are an UNSORTED set of nn_key(distance, map index) with the set's maximum tracked next to it: a candidate that beats the maximum
   // replaces it (five compare-selects) and the maximum is recomputed (four), instead of a five-step insertion sort — the kernel is
   // VALU-bound and the insertion ran for every candidate of every lane (any lane of the wavefront inserting makes all of them pay).
-  typedef unsigned long long u64k;
-  const u64k KNONE = ~0ull;
+  typedef nn_key_t u64k;
+  const u64k KNONE = NN_NONE;
   u64k k0 = KNONE, k1 = KNONE, k2 = KNONE, k3 = KNONE, k4 = KNONE, kmax = KNONE;
   if (nmap >= 5 && q >= qlo && q < qhi) {   // (another rank's query: nothing to search, the row stays empty)
     int cx, cy, cz;
@@ -524,25 +511,15 @@ __global__ void __launch_bounds__(128) lm_knn(DevCtx d, LmCtx L) {
       rs[r] = in ? a0 : 0;
       re[r] = in ? a1 : 0;
     }
-    // (x, y) as one packed pair: v_pk_add_f32 / v_pk_mul_f32 are IEEE operations on both halves, the sum keeps the reference's order
-    // ((dx^2 + dy^2) + dz^2; 0 + dx^2 = dx^2 exactly) — 6 instead of 8 VALU instructions per candidate, same bits
-    typedef float v2f __attribute__((ext_vector_type(2)));
-    const v2f sxy = {sx, sy};
+    const nn_v2f sxy = {sx, sy};   // (x, y) as one packed pair: nn_d2_pk, the same bits as nn_d2
     auto consider = [&](const float4& a) {
 #if LM_KNN_PK
-      const v2f axy = {a.x, a.y};
-      const v2f dxy = sxy - axy, sq = dxy * dxy;
-      const float dzv = sz - a.z;
-      float dist = sq.x + sq.y;
-      dist += dzv * dzv;
+      const float dist = nn_d2_pk(sxy, sz, nn_v2f{a.x, a.y}, a.z);
 #else
-      float dist = 0.f, df;
-      df = sx - a.x; dist += df * df;
-      df = sy - a.y; dist += df * df;
-      df = sz - a.z; dist += df * df;
+      const float dist = nn_d2(sx, sy, sz, a.x, a.y, a.z);
 #endif
-      const u64k key = ((u64k)(uint32_t)d_f2i(dist) << 32) | (uint32_t)__float_as_int(a.w);   // dist >= 0: its bit pattern orders like its value
-      if (key < kmax && (uint32_t)d_f2i(dist) < limbits) {   // (limbits: a neighbour at knn_max_dist or beyond can never be part of an ACCEPTED query — see `ok` below)
+      const u64k key = nn_key(dist, (uint32_t)__float_as_int(a.w));
+      if (key < kmax && nn_lm_within(dist, limbits)) {
         // (a set that is not full yet holds KNONE entries, which are its maximum; equal KNONE entries are all "the maximum": only one may be replaced)
         const bool e0 = k0 == kmax, e1 = !e0 && k1 == kmax, e2 = !e0 && !e1 && k2 == kmax, e3 = !e0 && !e1 && !e2 && k3 == kmax, e4 = !e0 && !e1 && !e2 && !e3;
         k0 = e0 ? key : k0; k1 = e1 ? key : k1; k2 = e2 ? key : k2; k3 = e3 ? key : k3; k4 = e4 ? key : k4;
@@ -581,7 +558,7 @@ __global__ void __launch_bounds__(128) lm_knn(DevCtx d, LmCtx L) {
     for (int k = 0; k < 5; ++k) {
       const u64k m01 = k0 < k1 ? k0 : k1, m23 = k2 < k3 ? k2 : k3, m03 = m01 < m23 ? m01 : m23, mine = m03 < k4 ? m03 : k4;
       const u64k m = group_min_u64<LM_KNN_LANES>(mine);
-      bd[k] = d_i2f((int32_t)(m >> 32)); bi[k] = (int)(uint32_t)m;   // (KNONE: distance bits 0xFFFFFFFF = NaN, index 0xFFFFFFFF — see `ok` below)
+      bd[k] = nn_key_d2(m); bi[k] = nn_key_index(m);   // (KNONE: distance bits 0xFFFFFFFF = NaN, index -1 — see `ok` below)
       if (mine == m && m != KNONE) {   // keys are unique (one per map point): exactly one lane of the group, exactly one of its entries
         k0 = k0 == m ? KNONE : k0; k1 = k1 == m ? KNONE : k1; k2 = k2 == m ? KNONE : k2; k3 = k3 == m ? KNONE : k3; k4 = k4 == m ? KNONE : k4;
       }
@@ -590,7 +567,7 @@ __global__ void __launch_bounds__(128) lm_knn(DevCtx d, LmCtx L) {
   // neighbour indices (ascending distance) for lm_fit; idx[0] < 0 = rejected (:376,:426)
   if (sub == 0 && qq < nq) {
     int* kn = lm_knn_of(L, slot, kind, q);
-    const bool ok = bi[4] != -1 && (double)bd[4] < P.knn_max_dist && q >= qlo && q < qhi;   // (queries of other ranks' slices give no row here)
+    const bool ok = nn_lm_row_ok(bi[4], bd[4], P.knn_max_dist) && q >= qlo && q < qhi;   // (queries of other ranks' slices give no row here)
 #pragma unroll
     for (int k = 0; k < 5; ++k) kn[k] = ok ? bi[k] : -1;
   }

@@ -14,6 +14,7 @@
 #include "dev_cost.h"
 #include "front_end.h"
 #include "lm_ctx.h"
+#include "nn_rules.h"
 #include "prof.h"
 
 #define LO_BLOCK 256
@@ -43,20 +44,6 @@ DEV_INLINE void transform_to_start(const double* R, const double* p, const float
 }
 
 struct WalkBest { double dist; int rank; int idx; };
-DEV_INLINE void walk_consider(WalkBest& b, double dist, int rank, int idx) {
-  if (dist < b.dist || (dist == b.dist && rank < b.rank)) { b.dist = dist; b.rank = rank; b.idx = idx; }
-}
-// lexicographic (distance, visiting rank) arg-min over the wavefront: non-negative doubles order like their bit
-// patterns, so this is a u64 min, then a u32 min of the rank among the lanes that hold the winning distance
-DEV_INLINE WalkBest walk_reduce(WalkBest b) {
-  const unsigned long long bits = (unsigned long long)__double_as_longlong(b.dist);
-  const unsigned long long mn = wave_min_u64(bits);
-  const uint32_t rk = wave_min_u32(bits == mn ? (uint32_t)b.rank : 0xFFFFFFFFu);
-  const uint32_t ix = wave_min_u32((bits == mn && (uint32_t)b.rank == rk) ? (uint32_t)b.idx : 0xFFFFFFFFu);
-  WalkBest r;
-  r.dist = __longlong_as_double((long long)mn); r.rank = (int)rk; r.idx = (int)ix;  // idx -1 (0xFFFFFFFF) = none
-  return r;
-}
 
 // kind 0: flat -> surf_last (less_flat of the previous scan); kind 1: sharp -> corner_last (less_sharp).
 // One DPP row (16 lanes) per query, four queries per wavefront in lock-step, LO_QPB per workgroup: the kernel is
@@ -66,15 +53,10 @@ DEV_INLINE WalkBest walk_reduce(WalkBest b) {
 // extraction next to the clouds: box c covers the targets [start, start + len), start / len carried in the .w fields of its two corners;
 // ring r owns the boxes [ring_boff[r], ring_boff[r + 1]) — a ring's feature-extraction workgroup writes its own boxes without waiting for
 // any other ring, and a ring window is a contiguous range of boxes):
-// a box is skipped when its lower bound exceeds the best distance found so far.  The lower bound is evaluated with
-// the same operations, in the same order and precision as the distance itself (clamped per-axis difference, squares,
-// left-to-right sum), and IEEE rounding is monotone, so bound <= distance of every point of the box: no candidate
-// that could win or tie is ever skipped.
-//   1-NN      (flann::L2_Simple<float>, ties -> lowest index): seed = the box with the smallest bound and its
-//             neighbour, then every box whose bound <= seed distance
-//   ring walk (:344-373,:433-475): the reference walks up and down from the closest point inside +-2.5 rings and keeps
-//             the minimum of the double-precision distance per class, first visited on ties; here a lexicographic
-//             (distance, visiting rank) arg-min over the surviving boxes of the ring interval
+// a box is skipped when its lower bound exceeds the best distance found so far.  Distances, keys, bounds and the walk's rules are nn_rules.h's,
+// where the argument that no candidate that could win or tie is skipped stands.
+//   1-NN      (nn_d2 / nn_key): seed = the box with the smallest nn_box_lb and its neighbour, then every box whose bound <= seed distance
+//   ring walk (nn_walk_*): the (distance, visiting rank) arg-min per class over the surviving boxes of the ring interval
 #define LO_QPB_OF(B) ((B) / 16)
 #ifndef LO_NB
 #define LO_NB 2       // surviving boxes evaluated per turn (2 x LO_NB loads in flight per lane); 3: same, 4: slower
@@ -84,6 +66,8 @@ DEV_INLINE WalkBest walk_reduce(WalkBest b) {
 #define LO_BOX_LDS 160   // boxes (of LO_CH targets) staged in LDS: 5 KB (16 x 1800 has ~135 less_flat boxes; larger feature sets read the boxes from the L2).
                          // 512 boxes = 16 KB made eight of these workgroups fill a CU's LDS: 351 k -> 354 k scans/s with 160
 #endif
+// lexicographic (distance, visiting rank) arg-min over a 16-lane row: non-negative doubles order like their bit patterns, so this is a u64 min,
+// then a u32 min of the rank among the lanes that hold the winning distance
 DEV_INLINE WalkBest walk_reduce_row(WalkBest b) {
   const unsigned long long bits = (unsigned long long)__double_as_longlong(b.dist);
   const unsigned long long mn = group_min_u64<16>(bits);
@@ -125,9 +109,8 @@ extern "C" void alego_la_counts(unsigned long long* out) { (void)hipMemcpyFromSy
 // scan, scatter; the order inside a cell is whatever the atomics give and does not matter (the key is (distance, index)).
 #define LG_T 256
 #ifndef LG_KEEP
-#define LG_KEEP 20
+#define LG_KEEP 20   // points a thread keeps in registers: 5120 in all, every cloud of a 16-ring sensor
 #endif
-// LG_KEEP:  // 5120 points: every cloud of a 16-ring sensor
 __global__ void __launch_bounds__(LG_T) lo_grid_build(DevCtx d) {
   const int slot = blockIdx.x + d.slot0, kind = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const size_t fb = fbuf(slot, cur_in_flight(d, slot));
@@ -174,8 +157,7 @@ __global__ void __launch_bounds__(LG_T) lo_grid_build(DevCtx d) {
   const float inv = 1.0f / csz;   // (csz is a power of two: exact)
   const int ncell = gx * gy;
   auto cell_of = [&](const float4& p) -> int {
-    const int ix = min(max((int)floorf((p.x - mn[0]) * inv), 0), gx - 1), iy = min(max((int)floorf((p.y - mn[1]) * inv), 0), gy - 1);
-    return ix + gx * iy;
+    return nn_clampi(nn_lo_cell(p.x, mn[0], inv), 0, gx - 1) + gx * nn_clampi(nn_lo_cell(p.y, mn[1], inv), 0, gy - 1);
   };
   // the points stay in registers between the count and the scatter (LG_KEEP per thread; a larger cloud reads the rest again)
   float4 keep[LG_KEEP];
@@ -218,7 +200,7 @@ __global__ void __launch_bounds__(LG_T) lo_grid_build(DevCtx d) {
   for (int u = 0; u < LG_KEEP; ++u) { const int i = tid + u * LG_T; if (i < n) place(i, keep[u]); }
   for (int i = tid + LG_KEEP * LG_T; i < n; i += LG_T) place(i, pts[i]);
   if (tid == 0) {
-    geom[LG_OX] = mn[0]; geom[LG_OY] = mn[1]; geom[LG_INV_CELL] = inv; geom[LG_SETTLE] = 0.999f * csz * csz;
+    geom[LG_OX] = mn[0]; geom[LG_OY] = mn[1]; geom[LG_INV_CELL] = inv; geom[LG_SETTLE] = nn_lo_settle(csz);
     geom[LG_GX] = __int_as_float(gx); geom[LG_GY] = __int_as_float(gy);
   }
 }
@@ -307,9 +289,7 @@ DEV_INLINE void lo_assoc_body(const DevCtx& d, int box_lds_max, int slot, int qb
     auto box_diff = [&](int c, float& dx, float& dy, float& dz) {
       float4 lo, hi;
       if (box_lds) { lo = s_box[2 * c]; hi = s_box[2 * c + 1]; } else { lo = bx[2 * c]; hi = bx[2 * c + 1]; }
-      dx = fmaxf(fmaxf(lo.x - sx, sx - hi.x), 0.f);
-      dy = fmaxf(fmaxf(lo.y - sy, sy - hi.y), 0.f);
-      dz = fmaxf(fmaxf(lo.z - sz, sz - hi.z), 0.f);
+      dx = nn_gap(lo.x, hi.x, sx); dy = nn_gap(lo.y, hi.y, sy); dz = nn_gap(lo.z, hi.z, sz);
     };
     // first target and number of targets of box c (< 0: none)
     auto box_span = [&](int c, int& start, int& len) {
@@ -322,13 +302,11 @@ DEV_INLINE void lo_assoc_body(const DevCtx& d, int box_lds_max, int slot, int qb
       if (c >= nch) return INF;
       float dx, dy, dz;
       box_diff(c, dx, dy, dz);
-      float r = 0.f;
-      r += dx * dx; r += dy * dy; r += dz * dz;
-      return r;
+      return nn_box_lb(dx, dy, dz);
     };
     // this lane's two targets of each of the boxes ca, cb (< 0: none) folded into its running (distance, index) minimum;
     // the four loads are issued together
-    auto nn_eval = [&](const int (&cb)[LO_NB], unsigned long long best) -> unsigned long long {
+    auto nn_eval = [&](const int (&cb)[LO_NB], nn_key_t best) -> nn_key_t {
       int t[TPL * LO_NB], bs[LO_NB], bl[LO_NB];
       bool v[TPL * LO_NB];
       float4 a[TPL * LO_NB];
@@ -340,9 +318,7 @@ DEV_INLINE void lo_assoc_body(const DevCtx& d, int box_lds_max, int slot, int qb
       for (int u = 0; u < TPL * LO_NB; ++u) a[u] = tg[v[u] ? t[u] : 0];
 #pragma unroll
       for (int u = 0; u < TPL * LO_NB; ++u) {
-        float r = 0.f, df;
-        df = a[u].x - sx; r += df * df; df = a[u].y - sy; r += df * df; df = a[u].z - sz; r += df * df;
-        const unsigned long long k = ((unsigned long long)(uint32_t)d_f2i(r) << 32) | (uint32_t)t[u];
+        const nn_key_t k = nn_key(nn_d2(a[u].x, a[u].y, a[u].z, sx, sy, sz), (uint32_t)t[u]);
         if (v[u]) best = k < best ? k : best;
       }
       return best;
@@ -353,12 +329,12 @@ DEV_INLINE void lo_assoc_body(const DevCtx& d, int box_lds_max, int slot, int qb
       for (int u = 0; u < LO_NB; ++u) { cb[u] = surv ? c0 + __ffs((int)surv) - 1 : -1; surv &= surv - 1; }   // 0 stays 0
     };
     // ---- the 3 x 3 grid cells around the query first: a candidate closer than (almost) a cell size is the nearest neighbour
-    unsigned long long gbest = ~0ull;
+    nn_key_t gbest = NN_NONE;
     bool settled = false;
     {
       const int ggx = __float_as_int(s_geom[LG_GX]), ggy = __float_as_int(s_geom[LG_GY]);
       if (ggx > 0) {
-        const int cx = (int)floorf((sx - s_geom[LG_OX]) * s_geom[LG_INV_CELL]), cy = (int)floorf((sy - s_geom[LG_OY]) * s_geom[LG_INV_CELL]);
+        const int cx = nn_lo_cell(sx, s_geom[LG_OX], s_geom[LG_INV_CELL]), cy = nn_lo_cell(sy, s_geom[LG_OY], s_geom[LG_INV_CELL]);   // (not clamped: nn_rules.h)
         const int x0 = max(cx - 1, 0), x1 = min(cx + 1, ggx - 1);
         int a0[3], a1[3];
 #pragma unroll
@@ -373,28 +349,26 @@ DEV_INLINE void lo_assoc_body(const DevCtx& d, int box_lds_max, int slot, int qb
           for (int t = a0[r] + l16; __ballot(t < a1[r]); t += 16) {
             const bool v = t < a1[r];
             const float4 a = gpts[v ? t : 0];
-            float r2 = 0.f, df;
-            df = a.x - sx; r2 += df * df; df = a.y - sy; r2 += df * df; df = a.z - sz; r2 += df * df;
-            const unsigned long long k = ((unsigned long long)(uint32_t)d_f2i(r2) << 32) | (uint32_t)__float_as_int(a.w);
+            const nn_key_t k = nn_key(nn_d2(a.x, a.y, a.z, sx, sy, sz), (uint32_t)__float_as_int(a.w));
             if (v) gbest = k < gbest ? k : gbest;
           }
         }
         gbest = group_min_u64<16>(gbest);
-        settled = gbest != ~0ull && d_i2f((int32_t)(gbest >> 32)) < s_geom[LG_SETTLE];
+        settled = gbest != NN_NONE && nn_key_d2(gbest) < s_geom[LG_SETTLE];
       }
     }
-    unsigned long long bj = gbest;
+    nn_key_t bj = gbest;
     if (__ballot(!settled)) {   // (rare: a query with no target within a cell size — its row, and with it the wavefront's other rows, search the boxes; both answers are exact)
-    unsigned long long m1 = ~0ull;
+    nn_key_t m1 = NN_NONE;
     for (int c = l16; c < nch; c += 16) {
-      const unsigned long long k = ((unsigned long long)(uint32_t)d_f2i(lb_f32(c)) << 32) | (uint32_t)c;
+      const nn_key_t k = nn_key(lb_f32(c), (uint32_t)c);
       m1 = k < m1 ? k : m1;
     }
-    const int cs = (int)(uint32_t)group_min_u64<16>(m1);
+    const int cs = nn_key_index(group_min_u64<16>(m1));
     LA_TICK(2);   // box with the smallest bound: nt > 0, so it exists
-    unsigned long long best;
-    { int cb[LO_NB]; for (int u = 0; u < LO_NB; ++u) cb[u] = -1; cb[0] = cs; cb[1] = (cs ^ 1) < nch ? (cs ^ 1) : -1; best = nn_eval(cb, ~0ull); }
-    const float bound = d_i2f((int32_t)(group_min_u64<16>(best) >> 32));
+    nn_key_t best;
+    { int cb[LO_NB]; for (int u = 0; u < LO_NB; ++u) cb[u] = -1; cb[0] = cs; cb[1] = (cs ^ 1) < nch ? (cs ^ 1) : -1; best = nn_eval(cb, NN_NONE); }
+    const float bound = nn_key_d2(group_min_u64<16>(best));
     LA_TICK(3);
     for (int c0 = 0; c0 < nch; c0 += 16) {
       const int c = c0 + l16;
@@ -408,30 +382,26 @@ DEV_INLINE void lo_assoc_body(const DevCtx& d, int box_lds_max, int slot, int qb
     bj = group_min_u64<16>(best);
     }
     LA_TICK(4);
-    const bool found = (double)d_i2f((int32_t)(bj >> 32)) < nfd;
-    if (found) closest = (int)(uint32_t)bj;
+    const bool found = nn_lo_found(nn_key_d2(bj), nfd);
+    if (found) closest = nn_key_index(bj);
     // ---- ring walk; rows without a closest point walk an empty window
     const int cref = found ? closest : 0;
     const int cr = (int)tg[cref].w;  // int(intensity) = ring (:347,:436)
     const int W = d.P.ring_window;
-    const int rlo = min(max(cr - W, 0), d.NS - 1), rhi = min(max(cr + W, 0), d.NS - 1), crc = min(max(cr, 0), d.NS - 1);
+    const int rlo = nn_walk_ring(cr, -W, d.NS), rhi = nn_walk_ring(cr, W, d.NS), crc = nn_walk_ring(cr, 0, d.NS);
     const int lo = found ? s_roff[rlo] : 0, hi = found ? s_roff[rhi + 1] : 0;           // the walks stay inside [lo, hi)
     const int same_lo = s_roff[crc], same_hi = s_roff[crc + 1];
     WalkBest b2{nfd, 0x7fffffff, -1}, b3{nfd, 0x7fffffff, -1};
     auto walk_one = [&](int k, bool valid, const float4& a) {
       if (!valid || k < lo || k >= hi || k == closest) return;
-      const double ex = (double)(a.x - sx), ey = (double)(a.y - sy), ez = (double)(a.z - sz);
-      const double pd = ex * ex + ey * ey + ez * ez;  // pow(f32 diff, 2) summed in double (:354)
+      const double pd = nn_walk_d2(a.x - sx, a.y - sy, a.z - sz);
       if (!(pd < nfd)) return;
-      // visiting order of the reference: closest+1, closest+2, ... then closest-1, closest-2, ...
-      const int rank = k > closest ? k - closest - 1 : (hi - closest - 1) + (closest - 1 - k);
+      const int rank = nn_walk_rank(k, closest, hi);
       const bool same = k >= same_lo && k < same_hi;
-      // surf: same ring -> b2, other rings -> b3; corner: other rings -> b2 (strictly above going up / strictly below going
-      // down, :446,:462).  Both updates are evaluated and committed by value: choosing the struct to update at run time
-      // is a select of addresses, which put b2 / b3 into scratch memory.
-      const bool to2 = kind == 0 ? same : !same, to3 = kind == 0 && !same;
-      const bool w2 = to2 && (pd < b2.dist || (pd == b2.dist && rank < b2.rank));
-      const bool w3 = to3 && (pd < b3.dist || (pd == b3.dist && rank < b3.rank));
+      // Both updates are evaluated and committed by value: choosing the struct to update at run time is a select of addresses, which put
+      // b2 / b3 into scratch memory.
+      const bool w2 = nn_walk_second(kind, same) && nn_walk_better(pd, rank, b2.dist, b2.rank);
+      const bool w3 = nn_walk_third(kind, same) && nn_walk_better(pd, rank, b3.dist, b3.rank);
       b2.dist = w2 ? pd : b2.dist; b2.rank = w2 ? rank : b2.rank; b2.idx = w2 ? k : b2.idx;
       b3.dist = w3 ? pd : b3.dist; b3.rank = w3 ? rank : b3.rank; b3.idx = w3 ? k : b3.idx;
     };
@@ -459,8 +429,7 @@ DEV_INLINE void lo_assoc_body(const DevCtx& d, int box_lds_max, int slot, int qb
     auto lb_f64 = [&](int c) -> double {
       float dx, dy, dz;
       box_diff(c, dx, dy, dz);
-      const double ex = (double)dx, ey = (double)dy, ez = (double)dz;
-      return ex * ex + ey * ey + ez * ez;
+      return nn_walk_d2(dx, dy, dz);
     };
     // seeds: the box of the closest point (its ring neighbours) and the other-ring box with the smallest bound
     unsigned long long mo = ~0ull;
@@ -525,7 +494,7 @@ DEV_INLINE void lo_assoc_body(const DevCtx& d, int box_lds_max, int slot, int qb
   LA_TICK(8);
   if (l16 == 0 && store) {
     int* row = lo_corr_of(d, slot, kind, q);
-    const bool ok = kind == 0 ? (idx2 >= 0 && idx3 >= 0) : (idx2 >= 0);
+    const bool ok = nn_lo_row_ok(kind, idx2, idx3);
     row[0] = q; row[1] = ok ? closest : -1; row[2] = idx2; row[3] = idx3;
   }
   }

@@ -17,14 +17,10 @@
 // The host side offers the attempts to the other callers (loop_ctx.h): loop_attempts with a gather of the caller's (loop_archive_gather: lc_gather),
 // loop_rounds, the verification rounds of relocalisation and of the appearance search, and loop_result_fill, the alego_loop_result of a verdict.
 //
-// Exactness of lc_nn.  The answer must be the brute force's: the smallest f32 ((dx*dx + dy*dy) + dz*dz), ties
-// to the lowest target index, for queries anywhere.  Candidates are compared as the (d², index) pair, so the visiting order does not
-// matter.  A cell is skipped only when the f64 lower bound of the distance to its actual f32 box, shrunk by a relative 1e-6 (the
-// f32 rounding of the three-term sum is below 4e-7) and by 1e-37 (underflow), still exceeds the best d² so far: every point of it then
-// has an f32 d² strictly larger and cannot win or tie.  Shells of cells are visited outward from the query's (clamped) cell and
-// the search stops when the same shrunk bound to the half-spaces beyond the visited box exceeds the best d².  That bound relies on
-// the cell assignment: cells are 2^k wide and the cell of x is floor((x - min) * 2^-k) in f64, which is exact (x - min of two f32 is
-// exact in f64 unless their exponents differ by more than 29; the faces carry an absolute slack of 1e-12 (|min| + extent + h)).
+// Exactness of lc_nn.  The answer must be the brute force's: the smallest nn_d2, ties to the lowest target index, for
+// queries anywhere.  Candidates are compared as the (d², index) pair (nn_better), so the visiting order does not matter.  A cell is skipped
+// only when nn_beyond holds for the bound to its actual f32 box; shells of cells are visited outward from the query's (clamped) cell and the
+// search stops when nn_beyond holds for the half-spaces beyond the visited block.  The bounds, the cells and their argument: nn_rules.h.
 #include <algorithm>
 #include <cfloat>
 #include <cstring>
@@ -35,12 +31,12 @@
 #include "icp_math.h"
 #include "kf_store.h"
 #include "loop_ctx.h"
+#include "nn_rules.h"
 #include "prof.h"
 #include "voxel.h"
 
 #define LC_DT 256     // lc_detect / lc_gather / lc_grid
 #define LC_IT 512     // lc_icp
-#define LC_PRUNE 0.999999
 
 struct LcGrid { double mn[3], slack[3], h, inv_h; int g[3], ncell; };
 
@@ -60,23 +56,22 @@ __global__ void __launch_bounds__(LC_DT) lc_detect(LmCtx L, const int* list, ale
   }
   const double* ld = L.ld + (size_t)slot * LD_COUNT;
   const float cx = (float)ld[LD_T_M2L + 0], cy = (float)ld[LD_T_M2L + 1], cz = (float)ld[LD_T_M2L + 2];
-  const float r2 = (float)(P.lc_search_radius * P.lc_search_radius);
+  const float r2 = nn_r2(P.lc_search_radius);
   const size_t fb = arc_row(L, slot, 0);
   const double t_last = L.arc_stamp[fb + nf - 1];
-  unsigned long long best = ~0ull;
+  nn_key_t best = NN_NONE;
   for (int i = threadIdx.x; i < nf; i += LC_DT) {
     const float* kp = arc_pose_of(L, slot, i);
-    float r = 0.f, df;
-    df = kp[0] - cx; r += df * df; df = kp[1] - cy; r += df * df; df = kp[2] - cz; r += df * df;
-    // radiusSearch (f32 d² < r², :778) + the first candidate in (d², id) order that is old enough (:781-788); d² >= 0: its bits order it
-    if (r < r2 && t_last - L.arc_stamp[fb + i] > P.lc_min_time_gap) best = min(best, ((unsigned long long)__float_as_uint(r) << 32) | (unsigned)i);
+    const float r = nn_d2(kp[0], kp[1], kp[2], cx, cy, cz);
+    // radiusSearch (:778) + the first candidate in (d², id) order that is old enough (:781-788)
+    if (nn_in_radius(r, r2) && t_last - L.arc_stamp[fb + i] > P.lc_min_time_gap) best = min(best, nn_key(r, (uint32_t)i));
   }
   best = block_min_u64<LC_DT / 64>(best, s_min);
   if (threadIdx.x != 0) return;
   for (int k = 0; k < 6; ++k) D.pose_latest[k] = arc_pose_of(L, slot, nf - 1)[k];
-  if (best != ~0ull) {
+  if (best != NN_NONE) {
     D.status = 1;
-    D.closest = (int)(best & 0xffffffffu);
+    D.closest = nn_key_index(best);
     for (int k = 0; k < 6; ++k) D.pose_closest[k] = arc_pose_of(L, slot, D.closest)[k];
     lc_window(D.closest, P.lc_search_num, D.latest - 1, &D.jlo, &D.jhi);   // :798-803: j < 0 || j >= latest_history_frame_id_ are skipped
   }
@@ -101,15 +96,8 @@ __global__ void __launch_bounds__(LC_DT) lc_gather(LmCtx L, const LcJob* jobs, c
 }
 
 // ---- uniform grid ---------------------------------------------------------------------------------------------------------------
-DEV_INLINE int lc_axis(float x, double mn, double inv_h, int g) {
-  double v = floor(((double)x - mn) * inv_h);
-  if (!(v >= 0.0)) v = 0.0;
-  if (v > (double)(g - 1)) v = (double)(g - 1);
-  return (int)v;
-}
-DEV_INLINE int lc_cell(const LcGrid& G, const float4& p) {
-  return (lc_axis(p.z, G.mn[2], G.inv_h, G.g[2]) * G.g[1] + lc_axis(p.y, G.mn[1], G.inv_h, G.g[1])) * G.g[0] + lc_axis(p.x, G.mn[0], G.inv_h, G.g[0]);
-}
+DEV_INLINE int lc_axis(const LcGrid& G, int a, float x) { return nn_lc_axis(x, G.mn[a], G.inv_h, G.g[a]); }
+DEV_INLINE int lc_cell(const LcGrid& G, const float4& p) { return nn_lc_index(lc_axis(G, 0, p.x), lc_axis(G, 1, p.y), lc_axis(G, 2, p.z), G.g[0], G.g[1]); }
 
 // the grid of n points (one workgroup of LC_DT threads): cells of 2^k (the smallest k with at most max(1, min(n / 8, cell_cap - 1)) cells),
 // cstart[ncell + 1] = first sorted position of every cell, cbox[2 c], [2 c + 1] = min / max xyz of the cell's points, spts = the points in
@@ -139,21 +127,13 @@ DEV_INLINE void lc_grid_build(const float4* P, int n, int cell_cap, LcGrid* geo,
       if (n == 0) { lo = 0.f; hi = 0.f; }
       G.mn[a] = lo; e[a] = (double)hi - (double)lo; emax = fmax(emax, e[a]);
     }
-    const double target = (double)max(1, min(n / 8, cell_cap - 1));
-    int k = emax > 0.0 ? ilogb(emax) + 1 : 0;   // 2^k > every extent: one cell
-    for (int it = 0; it < 160; ++it) {          // halve while the cell count stays within the target
-      const double h2 = ldexp(1.0, k - 1);
-      double cnt = 1.0;
-      for (int a = 0; a < 3; ++a) cnt *= floor(e[a] / h2) + 1.0;
-      if (cnt > target || k - 1 < -120) break;
-      --k;
-    }
+    const int k = nn_lc_cell_exp(e, emax, (double)max(1, min(n / 8, cell_cap - 1)));
     G.h = ldexp(1.0, k); G.inv_h = ldexp(1.0, -k);
     G.ncell = 1;
     for (int a = 0; a < 3; ++a) {
       G.g[a] = (int)(floor(e[a] * G.inv_h) + 1.0);
       G.ncell *= G.g[a];
-      G.slack[a] = 1e-12 * (fabs(G.mn[a]) + e[a] + G.h);
+      G.slack[a] = nn_face_slack(G.mn[a], e[a], G.h);
     }
     if (n == 0) G.ncell = 0;
     s_g = G;
@@ -214,22 +194,18 @@ __global__ void __launch_bounds__(LC_DT) lc_grid(const LcJob* jobs, const int* n
 
 // ---- exact 1-NN -----------------------------------------------------------------------------------------------------------------
 DEV_INLINE double lc_box_d2(const float4& lo, const float4& hi, const float4& q) {
-  const double dx = fmax(0.0, fmax((double)lo.x - (double)q.x, (double)q.x - (double)hi.x));
-  const double dy = fmax(0.0, fmax((double)lo.y - (double)q.y, (double)q.y - (double)hi.y));
-  const double dz = fmax(0.0, fmax((double)lo.z - (double)q.z, (double)q.z - (double)hi.z));
-  return dx * dx + dy * dy + dz * dz;
+  return nn_box_lb_f64(nn_gap_f64(lo.x, hi.x, q.x), nn_gap_f64(lo.y, hi.y, q.y), nn_gap_f64(lo.z, hi.z, q.z));
 }
-DEV_INLINE bool lc_beyond(double lb, float bd) { return lb * LC_PRUNE - 1e-37 > (double)bd; }
 
-// 1-NN of q among the grid's points: *bd = f32 d² as flann::L2_Simple ((dx dx + dy dy) + dz dz), *bi = target index (lowest on ties),
-// *bp = sorted position; (FLT_MAX, -1, -1) when nothing is closer than FLT_MAX (empty target, non-finite query), as icp_nn
+// 1-NN of q among the grid's points: *bd = nn_d2, *bi = target index (lowest on ties), *bp = sorted position; (FLT_MAX, -1, -1) when
+// nothing is closer than FLT_MAX (empty target, non-finite query), as icp_nn: the pair form's start state (nn_rules.h)
 DEV_INLINE void lc_nn(const LcGrid& G, const int* cstart, const float4* cbox, const float4* spts, const float4 q, float* bd_out, int* bi_out, int* bp_out) {
   float bd = FLT_MAX;
   int bi = -1, bp = -1;
   if (G.ncell > 0 && isfinite(q.x) && isfinite(q.y) && isfinite(q.z)) {
     const float qa[3] = {q.x, q.y, q.z};
     int c[3];
-    for (int a = 0; a < 3; ++a) c[a] = lc_axis(qa[a], G.mn[a], G.inv_h, G.g[a]);
+    for (int a = 0; a < 3; ++a) c[a] = lc_axis(G, a, qa[a]);
     const int rmax = max(max(G.g[0], G.g[1]), G.g[2]);
     for (int r = 0; r <= rmax; ++r) {
       const int z0 = max(0, c[2] - r), z1 = min(G.g[2] - 1, c[2] + r), y0 = max(0, c[1] - r), y1 = min(G.g[1] - 1, c[1] + r);
@@ -240,14 +216,13 @@ DEV_INLINE void lc_nn(const LcGrid& G, const int* cstart, const float4* cbox, co
           const int xs = face ? 1 : max(1, 2 * r);
           for (int x = face ? x0 : c[0] - r; x <= (face ? x1 : c[0] + r); x += xs) {
             if (x < x0 || x > x1) continue;
-            const int cell = (z * G.g[1] + y) * G.g[0] + x;
-            if (lc_beyond(lc_box_d2(cbox[2 * (size_t)cell], cbox[2 * (size_t)cell + 1], q), bd)) continue;
+            const int cell = nn_lc_index(x, y, z, G.g[0], G.g[1]);
+            if (nn_beyond(lc_box_d2(cbox[2 * (size_t)cell], cbox[2 * (size_t)cell + 1], q), bd)) continue;
             for (int j = cstart[cell]; j < cstart[cell + 1]; ++j) {
               const float4 p = spts[j];
-              float d = 0.f, df;
-              df = p.x - q.x; d += df * df; df = p.y - q.y; d += df * df; df = p.z - q.z; d += df * df;
+              const float d = nn_d2(p.x, p.y, p.z, q.x, q.y, q.z);
               const int idx = __float_as_int(p.w);
-              if (d < bd || (d == bd && idx < bi)) { bd = d; bi = idx; bp = j; }
+              if (nn_better(d, idx, bd, bi)) { bd = d; bi = idx; bp = j; }
             }
           }
         }
@@ -255,10 +230,10 @@ DEV_INLINE void lc_nn(const LcGrid& G, const int* cstart, const float4* cbox, co
       double rb = DBL_MAX;
       bool open = false;
       for (int a = 0; a < 3; ++a) {
-        if (c[a] - r - 1 >= 0) { open = true; const double d = fmax(0.0, (double)qa[a] - (G.mn[a] + (double)(c[a] - r) * G.h) - G.slack[a]); rb = fmin(rb, d * d); }
-        if (c[a] + r + 1 <= G.g[a] - 1) { open = true; const double d = fmax(0.0, (G.mn[a] + (double)(c[a] + r + 1) * G.h) - (double)qa[a] - G.slack[a]); rb = fmin(rb, d * d); }
+        if (c[a] - r - 1 >= 0) { open = true; rb = fmin(rb, nn_face_lb((double)qa[a] - (G.mn[a] + (double)(c[a] - r) * G.h), G.slack[a])); }
+        if (c[a] + r + 1 <= G.g[a] - 1) { open = true; rb = fmin(rb, nn_face_lb((G.mn[a] + (double)(c[a] + r + 1) * G.h) - (double)qa[a], G.slack[a])); }
       }
-      if (!open || lc_beyond(rb, bd)) break;
+      if (!open || nn_beyond(rb, bd)) break;
     }
   }
   *bd_out = bd; *bi_out = bi; *bp_out = bp;

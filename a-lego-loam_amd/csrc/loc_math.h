@@ -3,13 +3,12 @@
 //
 // p is the f32 of t_map2laser_ after transformAssociateToMap.  Frame i of the frozen map is a CANDIDATE when the f32 squared distance of
 // its key pose to p, accumulated as lc_detect accumulates it (kernels_loop.hip; no contraction: the build has -ffp-contract=off), is below
-// (float)(radius * radius).  Of the candidates the K smallest in the order (d² bits, id) are kept — d² >= 0, so its bit pattern orders it
-// and the packed 64-bit key (bits << 32 | id) is unique per frame.  The window is their ids in ascending order.  A non-finite p selects
+// (float)(radius * radius).  Of the candidates the K smallest in the order (d², id) are kept: nn_rules.h's distance, radius test and key, which
+// is unique per frame.  The window is their ids in ascending order.  A non-finite p selects
 // nothing.  This rule is the project's own, not the reference's surround-key-frame bookkeeping.
 #ifndef ALEGO_LOC_MATH_H_
 #define ALEGO_LOC_MATH_H_
-#include <stdint.h>
-#include <string.h>
+#include "nn_rules.h"
 
 #ifdef __HIPCC__
 #define LOC_FN __host__ __device__ inline
@@ -24,21 +23,14 @@
 
 LOC_FN float loc_r2(double radius) {
   const double r = radius > 0.0 ? radius : LOC_DEFAULT_RADIUS;
-  return (float)(r * r);
+  return nn_r2(r);
 }
-LOC_FN float loc_d2(const float* kp, float px, float py, float pz) {
-  float r = 0.f, df;
-  df = kp[0] - px; r += df * df; df = kp[1] - py; r += df * df; df = kp[2] - pz; r += df * df;
-  return r;
-}
+LOC_FN float loc_d2(const float* kp, float px, float py, float pz) { return nn_d2(kp[0], kp[1], kp[2], px, py, pz); }
 LOC_FN bool loc_finite(float v) { return v - v == 0.f; }
-// the packed key of frame `id`, or ~0 when it is no candidate
+// the key of frame `id`, or NN_NONE when it is no candidate
 LOC_FN unsigned long long loc_key(const float* kp, int id, float px, float py, float pz, float r2) {
   const float d2 = loc_d2(kp, px, py, pz);
-  if (!(d2 < r2)) return ~0ull;
-  uint32_t bits;
-  memcpy(&bits, &d2, sizeof(bits));
-  return ((unsigned long long)bits << 32) | (uint32_t)id;
+  return nn_in_radius(d2, r2) ? nn_key(d2, (uint32_t)id) : NN_NONE;
 }
 
 #endif
