@@ -13,7 +13,8 @@
 //   pg_update      one workgroup per slot: |delta|_inf, the finiteness check, X <- X Expmap(delta), the stopping rule
 //   pg_cost        one workgroup per slot: sum of squared whitened errors in a fixed order
 //   pg_store       the estimate of a finished slot goes to LmCtx::pg_est
-// All sums of a slot run in an order that depends on the slot's own graph only.
+// All sums of a slot run in an order that depends on the slot's own graph only; the block arithmetic of pg_assemble, pg_factor_chain and
+// pg_solve, with the order of every sum, is pg_chain.h (shared with kernels_pgcov.hip and the host twin).
 // correctPoses (:561-584) for the slots that converged: pg_apply (poses, window reset words, map -> odom), then pg_retransform +
 // the key-frame sort jobs once per resident frame (lm_host.hip).
 #include <hip/hip_runtime.h>
@@ -61,23 +62,6 @@ __global__ void __launch_bounds__(PG_T) pg_linearize(LmCtx L, PgWork W, int forc
   for (int i = 0; i < 36; ++i) { W.Jf[o * 36 + i] = Jf[i]; W.Jt[o * 36 + i] = Jt[i]; }
 }
 
-// out (6x6) (+)= A^T B; v (6) (+)= A^T r
-DEV_INLINE void pg_atb(const double* A, const double* B, double* out, bool add) {
-  for (int i = 0; i < 6; ++i)
-    for (int j = 0; j < 6; ++j) {
-      double a = add ? out[i * 6 + j] : 0.0;
-      for (int k = 0; k < 6; ++k) a += A[k * 6 + i] * B[k * 6 + j];
-      out[i * 6 + j] = a;
-    }
-}
-DEV_INLINE void pg_atr(const double* A, const double* r, double* v) {
-  for (int i = 0; i < 6; ++i) {
-    double a = v[i];
-    for (int k = 0; k < 6; ++k) a += A[k * 6 + i] * r[k];
-    v[i] = a;
-  }
-}
-
 // grid (node tiles, chunk entries): node k takes edge k (its `to` side), edge k + 1 (its `from` side) and, for the gradient, the loop
 // edges in index order
 __global__ void __launch_bounds__(PG_T) pg_assemble(LmCtx L, PgWork W) {
@@ -106,8 +90,8 @@ __global__ void __launch_bounds__(PG_T) pg_assemble(LmCtx L, PgWork W) {
   for (int i = 0; i < 6; ++i) W.g[nb * 6 + i] = gk[i];
 }
 
-// one lane per chunk entry: D_0 = T_00; L_kk = chol(D_k); L_{k+1,k} = T_{k+1,k} L_kk^-T; D_{k+1} = T_{k+1,k+1} - L_{k+1,k} L_{k+1,k}^T.
-// A pivot that is not positive gives NaN, which pg_update reports as a non-finite step.
+// one lane per chunk entry: the block Cholesky of T along the chain (pg_chain.h), D_0 = T_00.  pg_chol6's flag is not looked at: a pivot
+// that is not positive gives NaN, which pg_update reports as a non-finite step.
 __global__ void __launch_bounds__(64) pg_factor_chain(PgWork W) {
   const int q = blockIdx.x * 64 + threadIdx.x;
   if (q >= W.S) return;
@@ -120,47 +104,14 @@ __global__ void __launch_bounds__(64) pg_factor_chain(PgWork W) {
 #pragma unroll
   for (int i = 0; i < 36; ++i) D[i] = Td[i];
   for (int k = 0; k < N; ++k) {
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-      double d = D[j * 6 + j];
-#pragma unroll
-      for (int p = 0; p < j; ++p) d -= Lk[j * 6 + p] * Lk[j * 6 + p];
-      d = sqrt(d);
-      Lk[j * 6 + j] = d;
-#pragma unroll
-      for (int i = 0; i < 6; ++i) {
-        if (i < j) Lk[i * 6 + j] = 0.0;
-        if (i > j) {
-          double a = D[i * 6 + j];
-#pragma unroll
-          for (int p = 0; p < j; ++p) a -= Lk[i * 6 + p] * Lk[j * 6 + p];
-          Lk[i * 6 + j] = a / d;
-        }
-      }
-    }
+    pg_chol6(D, Lk);
 #pragma unroll
     for (int i = 0; i < 36; ++i) Td[(size_t)k * 36 + i] = Lk[i];
     if (k + 1 == N) break;
-#pragma unroll
-    for (int r = 0; r < 6; ++r)
-#pragma unroll
-      for (int c = 0; c < 6; ++c) {
-        double a = To[(size_t)k * 36 + r * 6 + c];
-#pragma unroll
-        for (int j = 0; j < c; ++j) a -= Lo[r * 6 + j] * Lk[c * 6 + j];
-        Lo[r * 6 + c] = a / Lk[c * 6 + c];
-      }
+    pg_chain_lo(To + (size_t)k * 36, Lk, Lo);
 #pragma unroll
     for (int i = 0; i < 36; ++i) To[(size_t)k * 36 + i] = Lo[i];
-#pragma unroll
-    for (int r = 0; r < 6; ++r)
-#pragma unroll
-      for (int c = 0; c < 6; ++c) {
-        double a = Td[(size_t)(k + 1) * 36 + r * 6 + c];
-#pragma unroll
-        for (int j = 0; j < 6; ++j) a -= Lo[r * 6 + j] * Lo[c * 6 + j];
-        D[r * 6 + c] = a;
-      }
+    pg_chain_schur(Td + (size_t)(k + 1) * 36, Lo, D);
   }
 }
 
@@ -185,45 +136,21 @@ __global__ void __launch_bounds__(PG_SOLVE_MAX) pg_solve(LmCtx L, PgWork W) {
     const double* jf = W.Jf + (eb + l) * 36 + row * 6;
     const double* jt = W.Jt + (eb + l) * 36 + row * 6;
     double y[6] = {0, 0, 0, 0, 0, 0};
-    for (int k = 0; k < N; ++k) {   // forward: y_k = L_kk^-1 (b_k - L_{k,k-1} y_{k-1})
+    for (int k = 0; k < N; ++k) {   // forward
       double b[6];
 #pragma unroll
       for (int i = 0; i < 6; ++i) b[i] = c == 0 ? -g[k * 6 + i] : (k == from ? jf[i] : (k == to ? jt[i] : 0.0));
-      if (k > 0) {
-        const double* Lo = To + (size_t)(k - 1) * 36;
+      pg_fwd_step(Td + (size_t)k * 36, k > 0 ? To + (size_t)(k - 1) * 36 : nullptr, y, b);
 #pragma unroll
-        for (int i = 0; i < 6; ++i) {
-          double a = b[i];
-#pragma unroll
-          for (int j = 0; j < 6; ++j) a -= Lo[i * 6 + j] * y[j];
-          b[i] = a;
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < 6; ++i) y[i] = b[i];
-      pg_lsolve(Td + (size_t)k * 36, y);
-#pragma unroll
-      for (int i = 0; i < 6; ++i) Z[((size_t)k * 6 + i) * R + c] = y[i];
+      for (int i = 0; i < 6; ++i) Z[((size_t)k * 6 + i) * R + c] = y[i] = b[i];
     }
-    for (int k = N - 1; k >= 0; --k) {   // backward: x_k = L_kk^-T (y_k - L_{k+1,k}^T x_{k+1})
+    for (int k = N - 1; k >= 0; --k) {   // backward
       double b[6];
 #pragma unroll
       for (int i = 0; i < 6; ++i) b[i] = Z[((size_t)k * 6 + i) * R + c];
-      if (k + 1 < N) {
-        const double* Lo = To + (size_t)k * 36;
+      pg_bwd_step(Td + (size_t)k * 36, k + 1 < N ? To + (size_t)k * 36 : nullptr, y, b);
 #pragma unroll
-        for (int i = 0; i < 6; ++i) {
-          double a = b[i];
-#pragma unroll
-          for (int j = 0; j < 6; ++j) a -= Lo[j * 6 + i] * y[j];
-          b[i] = a;
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < 6; ++i) y[i] = b[i];
-      pg_ltsolve(Td + (size_t)k * 36, y);
-#pragma unroll
-      for (int i = 0; i < 6; ++i) Z[((size_t)k * 6 + i) * R + c] = y[i];
+      for (int i = 0; i < 6; ++i) Z[((size_t)k * 6 + i) * R + c] = y[i] = b[i];
     }
   }
   __syncthreads();
@@ -232,30 +159,13 @@ __global__ void __launch_bounds__(PG_SOLVE_MAX) pg_solve(LmCtx L, PgWork W) {
     for (int t = c; t < n * (n + 1); t += blockDim.x) {
       const int a = t / (n + 1), b = t % (n + 1);
       const int l = a / 6, row = a % 6, col = b < n ? 1 + b : 0;
-      const double* jf = W.Jf + (eb + l) * 36 + row * 6;
-      const double* jt = W.Jt + (eb + l) * 36 + row * 6;
-      const double* zf = Z + (size_t)lp[l].from * 6 * R + col;
-      const double* zt = Z + (size_t)lp[l].to * 6 * R + col;
-      double s = b == a ? 1.0 : 0.0;
-      for (int j = 0; j < 6; ++j) s += jf[j] * zf[(size_t)j * R];
-      for (int j = 0; j < 6; ++j) s += jt[j] * zt[(size_t)j * R];
+      const double s = pg_cap_entry(b == a ? 1.0 : 0.0, W.Jf + (eb + l) * 36 + row * 6, Z + (size_t)lp[l].from * 6 * R + col,
+                                    W.Jt + (eb + l) * 36 + row * 6, Z + (size_t)lp[l].to * 6 * R + col, R);
       if (b < n) Cm[(size_t)a * n + b] = s; else s_y[a] = s;
     }
     __syncthreads();
-    // dense Cholesky of C in place (lower triangle), right-looking, then the two triangular solves for y
-    for (int j = 0; j < n; ++j) {
-      if (c == 0) Cm[(size_t)j * n + j] = sqrt(Cm[(size_t)j * n + j]);
-      __syncthreads();
-      const double d = Cm[(size_t)j * n + j];
-      for (int i = j + 1 + c; i < n; i += blockDim.x) Cm[(size_t)i * n + j] /= d;
-      __syncthreads();
-      const int m = n - j - 1;
-      for (int t = c; t < m * m; t += blockDim.x) {
-        const int i = j + 1 + t / m, k2 = j + 1 + t % m;
-        if (k2 <= i) Cm[(size_t)i * n + k2] -= Cm[(size_t)i * n + j] * Cm[(size_t)k2 * n + j];
-      }
-      __syncthreads();
-    }
+    // dense Cholesky of C in place (lower triangle), then the two triangular solves for y, which only the optimiser needs
+    pg_chol_dense(Cm, n, c, (int)blockDim.x, [] { __syncthreads(); });
     for (int j = 0; j < n; ++j) {
       if (c == 0) s_y[j] /= Cm[(size_t)j * n + j];
       __syncthreads();
@@ -410,13 +320,25 @@ __global__ void pg_sorted(LmCtx L, const int* apply, int slot0, int n, int all) 
   if (apply[slot0 + s]) li[LI_UVALID] = 0;
 }
 
-void launch_pg_linear_pass(const LmCtx& L, const PgWork& W, hipStream_t st) {
-  const dim3 gn((W.Nmax + PG_T - 1) / PG_T, W.S), ge((W.Nmax + W.Lmax + PG_T - 1) / PG_T, W.S);
-  ALEGO_LAUNCH(pg_init, gn, dim3(PG_T), 0, st, L, W);
-  ALEGO_LAUNCH(pg_linearize, ge, dim3(PG_T), 0, st, L, W, 0);
-  ALEGO_LAUNCH(pg_assemble, gn, dim3(PG_T), 0, st, L, W);
+// ---- the optimiser's kernels and their grids, once each, for the W.S entries of a chunk ------------------------------------------
+static void pg_launch_init(const LmCtx& L, const PgWork& W, hipStream_t st) {
+  ALEGO_LAUNCH(pg_init, dim3((W.Nmax + PG_T - 1) / PG_T, W.S), dim3(PG_T), 0, st, L, W);
+}
+// errors and Jacobians at X (force: of the finished entries too); cost >= 0: then their squared sum into that double control word
+static void pg_launch_linearize(const LmCtx& L, const PgWork& W, hipStream_t st, int force, int cost) {
+  ALEGO_LAUNCH(pg_linearize, dim3((W.Nmax + W.Lmax + PG_T - 1) / PG_T, W.S), dim3(PG_T), 0, st, L, W, force);
+  if (cost >= 0) ALEGO_LAUNCH(pg_cost, dim3(W.S), dim3(PG_T), 0, st, W, cost);
+}
+// T and g, the factor of T, the sweeps and the capacitance system: delta in g
+static void pg_launch_solve(const LmCtx& L, const PgWork& W, hipStream_t st) {
+  ALEGO_LAUNCH(pg_assemble, dim3((W.Nmax + PG_T - 1) / PG_T, W.S), dim3(PG_T), 0, st, L, W);
   ALEGO_LAUNCH(pg_factor_chain, dim3((W.S + 63) / 64), dim3(64), 0, st, W);
   ALEGO_LAUNCH(pg_solve, dim3(W.S), dim3(std::max(64, (W.R + 63) / 64 * 64)), 0, st, L, W);
+}
+void launch_pg_linear_pass(const LmCtx& L, const PgWork& W, hipStream_t st) {
+  pg_launch_init(L, W, st);
+  pg_launch_linearize(L, W, st, 0, -1);
+  pg_launch_solve(L, W, st);
 }
 void launch_pg_apply(const LmCtx& L, const int* apply_dev, int n_slots, hipStream_t st) {
   ALEGO_LAUNCH(pg_apply, dim3(n_slots), dim3(PG_T), 0, st, L, apply_dev);
@@ -484,8 +406,8 @@ int graph_set_edges(const LmCtx& L, int slot, int first, int n, const alego_grap
   const int have = arc[AS_FRAMES];
   if (first < 0 || n < 0 || first > have || n > have - first || (n > 0 && !chain)) return pg_fail(err, "graph_set_edges: range beyond the archived frames", ALEGO_ERR_ARG);
   for (int i = 0; i < n; ++i) {
-    if (chain[i].to != first + i || chain[i].from != first + i - 1) return pg_fail(err, "graph_set_edges: chain edge i is the prior (from = -1, to = 0) or i - 1 -> i", ALEGO_ERR_ARG);
-    if (!pg_finite_edge(chain[i])) return pg_fail(err, "graph_set_edges: measurement not finite or variance not positive and finite", ALEGO_ERR_ARG);
+    if (!pg_chain_ids(chain[i].from, chain[i].to, first + i)) return pg_fail(err, "graph_set_edges: chain edge i is the prior (from = -1, to = 0) or i - 1 -> i", ALEGO_ERR_ARG);
+    if (!pg_edge_finite(chain[i].between, chain[i].variance)) return pg_fail(err, "graph_set_edges: measurement not finite or variance not positive and finite", ALEGO_ERR_ARG);
   }
   if (n == 0) return 0;
   if (hipMemcpy(L.pg_chain + arc_row(L, slot, first), chain, (size_t)n * sizeof(alego_graph_edge), hipMemcpyHostToDevice) != hipSuccess)
@@ -506,8 +428,8 @@ int graph_append(PgCtx** pc, const LmCtx& L, int n_slots, const std::vector<PgAp
   for (size_t i = 0; i < a.size(); ++i) {
     const alego_graph_edge& e = a[i].e;
     const int nf = arc[a[i].slot * AS_W + AS_FRAMES];
-    if (e.from < 0 || e.to < 0 || e.from >= nf || e.to >= nf || e.from == e.to) return pg_fail(err, "graph: loop edge ids outside the archived frames, or from == to", ALEGO_ERR_ARG);
-    if (!pg_finite_edge(e)) return pg_fail(err, "graph: measurement not finite or variance not positive and finite", ALEGO_ERR_ARG);
+    if (!pg_loop_ids(e.from, e.to, nf)) return pg_fail(err, "graph: loop edge ids outside the archived frames, or from == to", ALEGO_ERR_ARG);
+    if (!pg_edge_finite(e.between, e.variance)) return pg_fail(err, "graph: measurement not finite or variance not positive and finite", ALEGO_ERR_ARG);
     if (cnt[a[i].slot] >= L.pg_loops_cap) return pg_fail(err, "graph: max_loops loop edges are stored already", ALEGO_ERR_CAPACITY);
     a[i].index = cnt[a[i].slot]++;
     a[i].last = 0;
@@ -544,7 +466,7 @@ int graph_optimize(PgCtx** pc, const LmCtx& L, int n_slots, const int* slots, in
   if (int r = pg_read_stats(L, n_slots, &arc, &pg, err)) return r;
   apply_out->assign(n_slots, 0);
   std::vector<int> todo;
-  int Nmax = 1, Lmax = 0;
+  PgPlan P;
   for (int i = 0; i < n; ++i) {
     const int s = slots[i];
     alego_graph_result& r = out[i];
@@ -553,35 +475,25 @@ int graph_optimize(PgCtx** pc, const LmCtx& L, int n_slots, const int* slots, in
     if (arc[s * AS_W + AS_DROPPED] > 0) { r.status = -1; continue; }
     if (r.n_poses == 0) { r.status = 0; continue; }
     todo.push_back(i);
-    Nmax = std::max(Nmax, r.n_poses); Lmax = std::max(Lmax, r.n_loops);
+    P.cover(r.n_poses, r.n_loops);
   }
   if (todo.empty()) return 0;
   PgWork W;
-  const size_t per = pg_layout(&W, nullptr, 1, Nmax, Lmax) + 16 * 256;
-  const int chunk = (int)std::max<long long>(1, std::min<long long>((long long)todo.size(), C->budget / (long long)per));
-  const size_t need = pg_layout(&W, nullptr, chunk, Nmax, Lmax);
-  if (C->buf.reserve(need) != hipSuccess) return pg_fail(err, "graph_optimize: scratch allocation failed (lower the budget or max_loops)", ALEGO_ERR_HIP);
-  const int R = 1 + 6 * Lmax, lanes = std::max(64, (R + 63) / 64 * 64);
+  if (P.reserve(C, todo.size(), 16 * 256, [&](char* base, int S) { return pg_layout(&W, base, S, P.Nmax, P.Lmax); }) != hipSuccess)
+    return pg_fail(err, "graph_optimize: scratch allocation failed (lower the budget or max_loops)", ALEGO_ERR_HIP);
   std::vector<int> ctl;
   std::vector<double> dctl;
-  for (size_t c0 = 0; c0 < todo.size(); c0 += chunk) {
-    const int S = (int)std::min<size_t>(chunk, todo.size() - c0);
-    pg_layout(&W, C->buf.p, S, Nmax, Lmax);
+  for (size_t c0 = 0; c0 < todo.size(); c0 += P.chunk) {
+    const int S = (int)std::min<size_t>(P.chunk, todo.size() - c0);
+    pg_layout(&W, C->buf.p, S, P.Nmax, P.Lmax);
     ctl.assign((size_t)S * PC_COUNT, 0);
-    for (int q = 0; q < S; ++q) {
-      const alego_graph_result& r = out[todo[c0 + q]];
-      ctl[q * PC_COUNT + PC_N] = r.n_poses; ctl[q * PC_COUNT + PC_NL] = r.n_loops; ctl[q * PC_COUNT + PC_SLOT] = slots[todo[c0 + q]];
-    }
-    if (hipMemcpyAsync(W.ctl, ctl.data(), ctl.size() * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemsetAsync(W.dctl, 0, (size_t)S * PD_COUNT * sizeof(double), st) != hipSuccess) return pg_fail(err, "graph_optimize: upload failed", ALEGO_ERR_HIP);
-    const dim3 gn((Nmax + PG_T - 1) / PG_T, S), ge((Nmax + Lmax + PG_T - 1) / PG_T, S);
-    ALEGO_LAUNCH(pg_init, gn, dim3(PG_T), 0, st, L, W);
+    for (int q = 0; q < S; ++q) pg_ctl_entry(&ctl, q, out[todo[c0 + q]].n_poses, out[todo[c0 + q]].n_loops, slots[todo[c0 + q]]);
+    if (pg_ctl_upload(W, ctl, st) != hipSuccess || hipMemsetAsync(W.dctl, 0, (size_t)S * PD_COUNT * sizeof(double), st) != hipSuccess)
+      return pg_fail(err, "graph_optimize: upload failed", ALEGO_ERR_HIP);
+    pg_launch_init(L, W, st);
     for (int it = 0; it < opt.max_iters; ++it) {
-      ALEGO_LAUNCH(pg_linearize, ge, dim3(PG_T), 0, st, L, W, 0);
-      if (it == 0) ALEGO_LAUNCH(pg_cost, dim3(S), dim3(PG_T), 0, st, W, (int)PD_COST0);
-      ALEGO_LAUNCH(pg_assemble, gn, dim3(PG_T), 0, st, L, W);
-      ALEGO_LAUNCH(pg_factor_chain, dim3((S + 63) / 64), dim3(64), 0, st, W);
-      ALEGO_LAUNCH(pg_solve, dim3(S), dim3(lanes), 0, st, L, W);
+      pg_launch_linearize(L, W, st, 0, it == 0 ? (int)PD_COST0 : -1);
+      pg_launch_solve(L, W, st);
       ALEGO_LAUNCH(pg_update, dim3(S), dim3(PG_T), 0, st, W, opt.max_iters, opt.step_tol);
       // one read per iteration for the whole chunk: stop launching once every slot of it has finished
       if (hipMemcpyAsync(ctl.data(), W.ctl, ctl.size() * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
@@ -590,9 +502,8 @@ int graph_optimize(PgCtx** pc, const LmCtx& L, int n_slots, const int* slots, in
       for (int q = 0; q < S; ++q) all = all && ctl[q * PC_COUNT + PC_DONE];
       if (all) break;
     }
-    ALEGO_LAUNCH(pg_linearize, ge, dim3(PG_T), 0, st, L, W, 1);
-    ALEGO_LAUNCH(pg_cost, dim3(S), dim3(PG_T), 0, st, W, (int)PD_COST);
-    ALEGO_LAUNCH(pg_store, dim3((Nmax * 12 + PG_T - 1) / PG_T, S), dim3(PG_T), 0, st, L, W);
+    pg_launch_linearize(L, W, st, 1, (int)PD_COST);
+    ALEGO_LAUNCH(pg_store, dim3((P.Nmax * 12 + PG_T - 1) / PG_T, S), dim3(PG_T), 0, st, L, W);
     dctl.assign((size_t)S * PD_COUNT, 0.0);
     if (hipMemcpyAsync(ctl.data(), W.ctl, ctl.size() * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipMemcpyAsync(dctl.data(), W.dctl, dctl.size() * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
@@ -621,7 +532,7 @@ int graph_upload_apply(PgCtx* C, const std::vector<int>& apply, const int** dev,
 int graph_residuals_host(const double* poses12, int n_poses, const alego_graph_edge* edges, int n_edges, double* whitened6, double* jac_from36, double* jac_to36) {
   for (int i = 0; i < n_edges; ++i) {
     const alego_graph_edge& e = edges[i];
-    if (e.to < 0 || e.to >= n_poses || e.from < -1 || e.from >= n_poses || e.from == e.to || !pg_finite_edge(e)) return ALEGO_ERR_ARG;
+    if (!pg_edge_ids(e.from, e.to, n_poses, -1) || !pg_edge_finite(e.between, e.variance)) return ALEGO_ERR_ARG;
   }
   for (int i = 0; i < n_edges; ++i) {
     const alego_graph_edge& e = edges[i];

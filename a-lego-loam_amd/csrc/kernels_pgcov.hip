@@ -120,14 +120,7 @@ __global__ void __launch_bounds__(PGC_ROWS) pgc_correct(PgWork W, PgCov V, int m
   const bool on = t < N * 6;
   double* Z = W.Z + (size_t)q * W.Nmax * 6 * R;
   const double* Lc = W.C + (size_t)q * 36 * W.Lmax * W.Lmax;
-  if (on) {
-    double* z = Z + (size_t)t * R + 1;
-    for (int j = 0; j < n; ++j) {
-      double a = z[j];
-      for (int p = 0; p < j; ++p) a -= Lc[(size_t)j * n + p] * z[p];
-      z[j] = a / Lc[(size_t)j * n + j];
-    }
-  }
+  if (on) pg_lc_row(Lc, n, Z + (size_t)t * R + 1);
   if (!marg) return;
   __syncthreads();
   if (!on) return;
@@ -136,10 +129,7 @@ __global__ void __launch_bounds__(PGC_ROWS) pgc_correct(PgWork W, PgCov V, int m
   const double* wi = Z + (size_t)t * R + 1;
   bool bad = false;
   for (int c = 0; c < 6; ++c) {
-    const double* wc = Z + ((size_t)k * 6 + c) * R + 1;
-    double s = 0.0;
-    for (int b = 0; b < n; ++b) s += wi[b] * wc[b];
-    const double v = S[c] - s;
+    const double v = S[c] - pg_wtw_entry(wi, Z + ((size_t)k * 6 + c) * R + 1, n);
     S[c] = v;
     if (!(fabs(v) <= 1.79769313486231570815e+308)) bad = true;
   }
@@ -160,45 +150,21 @@ __global__ void __launch_bounds__(PGC_COL_MAX) pgc_columns(PgWork W, PgCov V) {
   if (c < 6 * U) {
     const int u = nodes[c / 6], row = c % 6, last = nodes[0];
     double y[6] = {0, 0, 0, 0, 0, 0};
-    for (int k = u; k < N; ++k) {   // forward: y_k = L_kk^-1 (b_k - L_{k,k-1} y_{k-1})
+    for (int k = u; k < N; ++k) {   // forward
       double b[6];
 #pragma unroll
       for (int i = 0; i < 6; ++i) b[i] = (k == u && i == row) ? 1.0 : 0.0;
-      if (k > u) {
-        const double* Lo = To + (size_t)(k - 1) * 36;
+      pg_fwd_step(Td + (size_t)k * 36, k > u ? To + (size_t)(k - 1) * 36 : nullptr, y, b);
 #pragma unroll
-        for (int i = 0; i < 6; ++i) {
-          double a = b[i];
-#pragma unroll
-          for (int j = 0; j < 6; ++j) a -= Lo[i * 6 + j] * y[j];
-          b[i] = a;
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < 6; ++i) y[i] = b[i];
-      pg_lsolve(Td + (size_t)k * 36, y);
-#pragma unroll
-      for (int i = 0; i < 6; ++i) Y[((size_t)k * 6 + i) * Rc + c] = y[i];
+      for (int i = 0; i < 6; ++i) Y[((size_t)k * 6 + i) * Rc + c] = y[i] = b[i];
     }
-    for (int k = N - 1; k >= last; --k) {   // backward: x_k = L_kk^-T (y_k - L_{k+1,k}^T x_{k+1})
+    for (int k = N - 1; k >= last; --k) {   // backward
       double b[6];
 #pragma unroll
       for (int i = 0; i < 6; ++i) b[i] = k >= u ? Y[((size_t)k * 6 + i) * Rc + c] : 0.0;
-      if (k + 1 < N) {
-        const double* Lo = To + (size_t)k * 36;
+      pg_bwd_step(Td + (size_t)k * 36, k + 1 < N ? To + (size_t)k * 36 : nullptr, y, b);
 #pragma unroll
-        for (int i = 0; i < 6; ++i) {
-          double a = b[i];
-#pragma unroll
-          for (int j = 0; j < 6; ++j) a -= Lo[j * 6 + i] * y[j];
-          b[i] = a;
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < 6; ++i) y[i] = b[i];
-      pg_ltsolve(Td + (size_t)k * 36, y);
-#pragma unroll
-      for (int i = 0; i < 6; ++i) Y[((size_t)k * 6 + i) * Rc + c] = y[i];
+      for (int i = 0; i < 6; ++i) Y[((size_t)k * 6 + i) * Rc + c] = y[i] = b[i];
     }
   }
   __syncthreads();
@@ -207,11 +173,8 @@ __global__ void __launch_bounds__(PGC_COL_MAX) pgc_columns(PgWork W, PgCov V) {
     const int kc = t / 108, w = (t / 36) % 3, r = (t % 36) / 6, cc = t % 6;
     const PgcCand& cd = V.cand[(size_t)q * V.Kmax + kc];
     const int a = w == 1 ? cd.e.to : cd.e.from, b = w == 0 ? cd.e.from : cd.e.to, col = w == 0 ? cd.ci : cd.cj;
-    const double* wa = Z + ((size_t)a * 6 + r) * R + 1;
-    const double* wb = Z + ((size_t)b * 6 + cc) * R + 1;
-    double s = 0.0;
-    for (int p = 0; p < n; ++p) s += wa[p] * wb[p];
-    V.blk[(((size_t)q * V.Kmax + kc) * 3 + w) * 36 + r * 6 + cc] = Y[((size_t)a * 6 + r) * Rc + col * 6 + cc] - s;
+    V.blk[(((size_t)q * V.Kmax + kc) * 3 + w) * 36 + r * 6 + cc] =
+        Y[((size_t)a * 6 + r) * Rc + col * 6 + cc] - pg_wtw_entry(Z + ((size_t)a * 6 + r) * R + 1, Z + ((size_t)b * 6 + cc) * R + 1, n);
   }
 }
 
@@ -252,31 +215,30 @@ int pgc_run(PgCtx** pc, const LmCtx& L, const std::vector<PgcEntry>& ent, bool m
   if (ent.empty()) return 0;
   if (!*pc) *pc = new PgCtx();
   PgCtx* C = *pc;
-  int Nmax = 1, Lmax = 0, Kmax = 0, Umax = 0;
+  PgPlan P;
+  int Kmax = 0, Umax = 0;
   for (const PgcEntry& e : ent) {
-    Nmax = std::max(Nmax, e.N); Lmax = std::max(Lmax, e.NL); Kmax = std::max(Kmax, (int)e.cand.size()); Umax = std::max(Umax, (int)e.nodes.size());
+    P.cover(e.N, e.NL); Kmax = std::max(Kmax, (int)e.cand.size()); Umax = std::max(Umax, (int)e.nodes.size());
   }
+  const int Nmax = P.Nmax, Lmax = P.Lmax;
   PgWork W; PgCov V;
   auto layout = [&](char* base, int S) { const size_t a = pg_layout(&W, base, S, Nmax, Lmax); return a + pgc_layout(&V, base, a, S, Nmax, Kmax, Umax, marg); };
-  const size_t per = layout(nullptr, 1) + 24 * 256;
-  const int chunk = (int)std::max<long long>(1, std::min<long long>((long long)ent.size(), C->budget / (long long)per));
-  if (C->buf.reserve(layout(nullptr, chunk)) != hipSuccess) return pg_fail(err, "graph covariance: scratch allocation failed (lower the budget)", ALEGO_ERR_HIP);
+  if (P.reserve(C, ent.size(), 24 * 256, layout) != hipSuccess) return pg_fail(err, "graph covariance: scratch allocation failed (lower the budget)", ALEGO_ERR_HIP);
   std::vector<int> ctl, nodes;
   std::vector<PgcCand> cand;
-  for (size_t c0 = 0; c0 < ent.size(); c0 += chunk) {
-    const int S = (int)std::min<size_t>(chunk, ent.size() - c0);
+  for (size_t c0 = 0; c0 < ent.size(); c0 += P.chunk) {
+    const int S = (int)std::min<size_t>(P.chunk, ent.size() - c0);
     layout(C->buf.p, S);
     ctl.assign((size_t)S * PC_COUNT, 0);
     nodes.assign((size_t)S * std::max(Umax, 1), 0);
     cand.assign((size_t)S * std::max(Kmax, 1), PgcCand());
     for (int q = 0; q < S; ++q) {
       const PgcEntry& e = ent[c0 + q];
-      int* w = &ctl[(size_t)q * PC_COUNT];
-      w[PC_N] = e.N; w[PC_NL] = e.NL; w[PC_SLOT] = e.slot; w[PC_NC] = (int)e.cand.size(); w[PC_NU] = (int)e.nodes.size();
+      pg_ctl_entry(&ctl, q, e.N, e.NL, e.slot, (int)e.cand.size(), (int)e.nodes.size());
       std::copy(e.nodes.begin(), e.nodes.end(), nodes.begin() + (size_t)q * Umax);
       std::copy(e.cand.begin(), e.cand.end(), cand.begin() + (size_t)q * Kmax);
     }
-    hipError_t he = hipMemcpyAsync(W.ctl, ctl.data(), ctl.size() * sizeof(int), hipMemcpyHostToDevice, st);
+    hipError_t he = pg_ctl_upload(W, ctl, st);
     if (he == hipSuccess && Kmax > 0) he = hipMemcpyAsync(V.nodes, nodes.data(), (size_t)S * Umax * sizeof(int), hipMemcpyHostToDevice, st);
     if (he == hipSuccess && Kmax > 0) he = hipMemcpyAsync(V.cand, cand.data(), (size_t)S * Kmax * sizeof(PgcCand), hipMemcpyHostToDevice, st);
     if (he != hipSuccess) return pg_fail(err, "graph covariance: upload failed", ALEGO_ERR_HIP);
@@ -339,8 +301,8 @@ int graph_check(PgCtx** pc, const LmCtx& L, int n_slots, const int* slots, int n
     std::memset(&out[i], 0, sizeof(out[i]));
     if (active && !active[i]) continue;
     const int s = slots[i], nf = arc[s * AS_W + AS_FRAMES];
-    if (e[i].from < 0 || e[i].to < 0 || e[i].from >= nf || e[i].to >= nf || e[i].from == e[i].to) return pg_fail(err, "graph check: edge ids outside the archived frames, or from == to", ALEGO_ERR_ARG);
-    if (!pg_finite_edge(e[i])) return pg_fail(err, "graph check: measurement not finite or variance not positive and finite", ALEGO_ERR_ARG);
+    if (!pg_loop_ids(e[i].from, e[i].to, nf)) return pg_fail(err, "graph check: edge ids outside the archived frames, or from == to", ALEGO_ERR_ARG);
+    if (!pg_edge_finite(e[i].between, e[i].variance)) return pg_fail(err, "graph check: measurement not finite or variance not positive and finite", ALEGO_ERR_ARG);
     if (entry_of[s] < 0) {
       entry_of[s] = (int)ent.size();
       PgcEntry x; x.slot = s; x.N = nf; x.NL = pg[s * PS_W + PS_LOOPS];

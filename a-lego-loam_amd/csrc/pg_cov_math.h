@@ -10,9 +10,11 @@
 // A candidate i -> j with the unwhitened error e and Jacobian blocks A (d e / d delta_i), B (d e / d delta_j):
 //   P = A Sigma_ii A^T + B Sigma_jj B^T + A Sigma_ij B^T + B Sigma_ij^T A^T + diag(variance),  d2 = e^T P^-1 e
 // Every symmetric block is computed on its upper triangle and mirrored, so S_kk, Sigma_kk and P are symmetric to the last bit.
+// The chain factor, the sweeps, C and its factor, the row through Lc^-1 and the W^T W entry are pg_chain.h's, here as in the kernels.
 #ifndef ALEGO_PG_COV_MATH_H_
 #define ALEGO_PG_COV_MATH_H_
 #include "../../include/alego_mi355x.h"
+#include "pg_chain.h"
 #include "pg_math.h"
 
 // M = L^-1 of a lower-triangular 6x6 (row-major; the upper triangle of M is zero)
@@ -96,32 +98,13 @@ PG_FN void pgc_innovation(const double* A, const double* B, const double* Sii, c
 // d2 = e^T P^-1 e by a 6x6 Cholesky; false when P is not finite or not positive definite (d2 is then 0)
 PG_FN bool pgc_mahalanobis(const double* P, const double* e, double* d2) {
   double L[36], y[6];
-  bool ok = true;
+  bool ok = pg_chol6(P, L);
 #pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    double d = P[j * 6 + j];
-#pragma unroll
-    for (int p = 0; p < j; ++p) d -= L[j * 6 + p] * L[j * 6 + p];
-    if (!(d > 0.0) || !(d <= 1.79769313486231570815e+308)) ok = false;
-    d = sqrt(d);
-    L[j * 6 + j] = d;
-#pragma unroll
-    for (int i = j + 1; i < 6; ++i) {
-      double a = P[i * 6 + j];
-#pragma unroll
-      for (int p = 0; p < j; ++p) a -= L[i * 6 + p] * L[j * 6 + p];
-      L[i * 6 + j] = a / d;
-    }
-  }
+  for (int i = 0; i < 6; ++i) y[i] = e[i];
+  pg_lsolve(L, y);
   double s = 0.0;
 #pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    double a = e[i];
-#pragma unroll
-    for (int p = 0; p < i; ++p) a -= L[i * 6 + p] * y[p];
-    y[i] = a / L[i * 6 + i];
-    s += y[i] * y[i];
-  }
+  for (int i = 0; i < 6; ++i) s += y[i] * y[i];
   if (!(s >= 0.0) || !(s <= 1.79769313486231570815e+308)) ok = false;
   *d2 = ok ? s : 0.0;
   return ok;
@@ -144,21 +127,11 @@ struct PgcHost {
 inline void pgc_host_sweep(const PgcHost& H, double* x, int k0, int k1) {
   for (int k = k0; k < H.N; ++k) {
     double* y = x + (size_t)k * 6;
-    if (k > k0) {
-      const double* Lo = &H.To[(size_t)(k - 1) * 36];
-      for (int i = 0; i < 6; ++i) { double a = y[i]; for (int j = 0; j < 6; ++j) a -= Lo[i * 6 + j] * y[j - 6]; y[i] = a; }
-    }
-    const double* Lk = &H.Td[(size_t)k * 36];
-    for (int i = 0; i < 6; ++i) { double a = y[i]; for (int j = 0; j < i; ++j) a -= Lk[i * 6 + j] * y[j]; y[i] = a / Lk[i * 6 + i]; }
+    pg_fwd_step(&H.Td[(size_t)k * 36], k > k0 ? &H.To[(size_t)(k - 1) * 36] : nullptr, k > k0 ? y - 6 : nullptr, y);
   }
   for (int k = H.N - 1; k >= k1; --k) {
     double* y = x + (size_t)k * 6;
-    if (k + 1 < H.N) {
-      const double* Lo = &H.To[(size_t)k * 36];
-      for (int i = 0; i < 6; ++i) { double a = y[i]; for (int j = 0; j < 6; ++j) a -= Lo[j * 6 + i] * y[6 + j]; y[i] = a; }
-    }
-    const double* Lk = &H.Td[(size_t)k * 36];
-    for (int i = 5; i >= 0; --i) { double a = y[i]; for (int j = i + 1; j < 6; ++j) a -= Lk[j * 6 + i] * y[j]; y[i] = a / Lk[i * 6 + i]; }
+    pg_bwd_step(&H.Td[(size_t)k * 36], k + 1 < H.N ? &H.To[(size_t)k * 36] : nullptr, y + 6, y);
   }
 }
 // linearise at poses12, factorise T along the chain, Z, the capacitance factor and W (pg_linearize .. pg_solve, then pgc_correct's
@@ -166,12 +139,10 @@ inline void pgc_host_sweep(const PgcHost& H, double* x, int k0, int k1) {
 // malformed graph.
 inline int pgc_host_factor(const double* poses12, int N, const alego_graph_edge* edges, int n_edges, PgcHost* H) {
   if (!poses12 || N <= 0 || !edges || n_edges < N) return ALEGO_ERR_ARG;
-  for (long i = 0; i < (long)N * 12; ++i) if (!(poses12[i] - poses12[i] == 0.0)) return ALEGO_ERR_ARG;
+  for (long i = 0; i < (long)N * 12; ++i) if (!pg_finite(poses12[i])) return ALEGO_ERR_ARG;
   for (int i = 0; i < n_edges; ++i) {
     const alego_graph_edge& e = edges[i];
-    if (i < N ? (e.to != i || e.from != i - 1) : (e.from < 0 || e.to < 0 || e.from >= N || e.to >= N || e.from == e.to)) return ALEGO_ERR_ARG;
-    for (int k = 0; k < 12; ++k) if (!(e.between[k] - e.between[k] == 0.0)) return ALEGO_ERR_ARG;
-    for (int k = 0; k < 6; ++k) if (!(e.variance[k] > 0.0) || !(e.variance[k] - e.variance[k] == 0.0)) return ALEGO_ERR_ARG;
+    if (!(i < N ? pg_chain_ids(e.from, e.to, i) : pg_loop_ids(e.from, e.to, N)) || !pg_edge_finite(e.between, e.variance)) return ALEGO_ERR_ARG;
   }
   const int NL = n_edges - N, n = 6 * NL;
   H->N = N; H->NL = NL; H->n = n;
@@ -181,43 +152,24 @@ inline int pgc_host_factor(const double* poses12, int N, const alego_graph_edge*
     pg_factor(edges[i].from < 0 ? nullptr : poses12 + (size_t)edges[i].from * 12, poses12 + (size_t)edges[i].to * 12, edges[i].between, edges[i].variance, r,
               &Jf[(size_t)i * 36], &Jt[(size_t)i * 36]);
   }
-  auto atb = [](const double* A, const double* B, double* out, bool add) {
-    for (int i = 0; i < 6; ++i)
-      for (int j = 0; j < 6; ++j) { double a = add ? out[i * 6 + j] : 0.0; for (int k = 0; k < 6; ++k) a += A[k * 6 + i] * B[k * 6 + j]; out[i * 6 + j] = a; }
-  };
   H->Td.assign((size_t)N * 36, 0.0); H->To.assign((size_t)N * 36, 0.0);
   for (int k = 0; k < N; ++k) {
-    atb(&Jt[(size_t)k * 36], &Jt[(size_t)k * 36], &H->Td[(size_t)k * 36], false);
+    pg_atb(&Jt[(size_t)k * 36], &Jt[(size_t)k * 36], &H->Td[(size_t)k * 36], false);
     if (k + 1 < N) {
-      atb(&Jf[(size_t)(k + 1) * 36], &Jf[(size_t)(k + 1) * 36], &H->Td[(size_t)k * 36], true);
-      atb(&Jt[(size_t)(k + 1) * 36], &Jf[(size_t)(k + 1) * 36], &H->To[(size_t)k * 36], false);
+      pg_atb(&Jf[(size_t)(k + 1) * 36], &Jf[(size_t)(k + 1) * 36], &H->Td[(size_t)k * 36], true);
+      pg_atb(&Jt[(size_t)(k + 1) * 36], &Jf[(size_t)(k + 1) * 36], &H->To[(size_t)k * 36], false);
     }
   }
-  // block Cholesky along the chain (pg_factor_chain)
-  double D[36], Lk[36], Lo[36];
+  // block Cholesky along the chain (pg_factor_chain): a bad pivot leaves NaN, as there
+  double D[36];
   std::memcpy(D, H->Td.data(), sizeof(D));
   for (int k = 0; k < N; ++k) {
-    for (int j = 0; j < 6; ++j) {
-      double d = D[j * 6 + j];
-      for (int p = 0; p < j; ++p) d -= Lk[j * 6 + p] * Lk[j * 6 + p];
-      d = sqrt(d);
-      Lk[j * 6 + j] = d;
-      for (int i = 0; i < 6; ++i) {
-        if (i < j) Lk[i * 6 + j] = 0.0;
-        if (i > j) { double a = D[i * 6 + j]; for (int p = 0; p < j; ++p) a -= Lk[i * 6 + p] * Lk[j * 6 + p]; Lk[i * 6 + j] = a / d; }
-      }
-    }
-    std::memcpy(&H->Td[(size_t)k * 36], Lk, sizeof(Lk));
+    double* Lk = &H->Td[(size_t)k * 36];
+    pg_chol6(D, Lk);
     if (k + 1 == N) break;
-    for (int r = 0; r < 6; ++r)
-      for (int c = 0; c < 6; ++c) {
-        double a = H->To[(size_t)k * 36 + r * 6 + c];
-        for (int j = 0; j < c; ++j) a -= Lo[r * 6 + j] * Lk[c * 6 + j];
-        Lo[r * 6 + c] = a / Lk[c * 6 + c];
-      }
-    std::memcpy(&H->To[(size_t)k * 36], Lo, sizeof(Lo));
-    for (int r = 0; r < 6; ++r)
-      for (int c = 0; c < 6; ++c) { double a = H->Td[(size_t)(k + 1) * 36 + r * 6 + c]; for (int j = 0; j < 6; ++j) a -= Lo[r * 6 + j] * Lo[c * 6 + j]; D[r * 6 + c] = a; }
+    double* Lo = &H->To[(size_t)k * 36];
+    pg_chain_lo(Lo, Lk, Lo);
+    pg_chain_schur(&H->Td[(size_t)(k + 1) * 36], Lo, D);
   }
   H->Z.assign((size_t)N * 6 * n, 0.0); H->C.assign((size_t)n * n, 0.0);
   if (n == 0) return 0;
@@ -234,26 +186,12 @@ inline int pgc_host_factor(const double* poses12, int N, const alego_graph_edge*
   for (int a = 0; a < n; ++a)
     for (int b = 0; b < n; ++b) {
       const alego_graph_edge& e = edges[N + a / 6];
-      const double* jf = &Jf[(size_t)(N + a / 6) * 36 + (a % 6) * 6];
-      const double* jt = &Jt[(size_t)(N + a / 6) * 36 + (a % 6) * 6];
-      double s = a == b ? 1.0 : 0.0;
-      for (int j = 0; j < 6; ++j) s += jf[j] * H->Z[((size_t)e.from * 6 + j) * n + b];
-      for (int j = 0; j < 6; ++j) s += jt[j] * H->Z[((size_t)e.to * 6 + j) * n + b];
-      H->C[(size_t)a * n + b] = s;
+      H->C[(size_t)a * n + b] = pg_cap_entry(a == b ? 1.0 : 0.0, &Jf[(size_t)(N + a / 6) * 36 + (a % 6) * 6], &H->Z[(size_t)e.from * 6 * n + b],
+                                             &Jt[(size_t)(N + a / 6) * 36 + (a % 6) * 6], &H->Z[(size_t)e.to * 6 * n + b], n);
     }
-  for (int j = 0; j < n; ++j) {
-    double* Cm = H->C.data();
-    Cm[(size_t)j * n + j] = sqrt(Cm[(size_t)j * n + j]);
-    const double d = Cm[(size_t)j * n + j];
-    for (int i = j + 1; i < n; ++i) Cm[(size_t)i * n + j] /= d;
-    for (int i = j + 1; i < n; ++i)
-      for (int k2 = j + 1; k2 <= i; ++k2) Cm[(size_t)i * n + k2] -= Cm[(size_t)i * n + j] * Cm[(size_t)k2 * n + j];
-  }
+  pg_chol_dense(H->C.data(), n, 0, 1, [] {});
   // W = rows of Z through Lc^-1, in place
-  for (int t = 0; t < N * 6; ++t) {
-    double* z = &H->Z[(size_t)t * n];
-    for (int j = 0; j < n; ++j) { double a = z[j]; for (int p = 0; p < j; ++p) a -= H->C[(size_t)j * n + p] * z[p]; z[j] = a / H->C[(size_t)j * n + j]; }
-  }
+  for (int t = 0; t < N * 6; ++t) pg_lc_row(H->C.data(), n, &H->Z[(size_t)t * n]);
   return 0;
 }
 // out (6x6) = (T^-1)_ab from the unit-column solutions col [6][N][6] of node b; pgc_host_sub_wtw then subtracts W_a^T W_b
@@ -264,9 +202,7 @@ inline void pgc_host_block(const PgcHost& H, const double* col, int a, double* o
 inline void pgc_host_sub_wtw(const PgcHost& H, int a, int b, double* out) {
   for (int r = 0; r < 6; ++r)
     for (int c = 0; c < 6; ++c) {
-      double s = 0.0;
-      for (int p = 0; p < H.n; ++p) s += H.Z[((size_t)a * 6 + r) * H.n + p] * H.Z[((size_t)b * 6 + c) * H.n + p];
-      out[r * 6 + c] -= s;
+      out[r * 6 + c] -= pg_wtw_entry(H.Z.data() + ((size_t)a * 6 + r) * H.n, H.Z.data() + ((size_t)b * 6 + c) * H.n, H.n);
     }
 }
 // the six unit-column solutions of node u: col [6][N][6] (entries of the nodes before `lo` are not computed)
@@ -315,9 +251,7 @@ inline int pgc_host_check(const double* poses12, int N, const alego_graph_edge* 
   if (n_cand < 0 || (n_cand > 0 && (!cand || !out))) return ALEGO_ERR_ARG;
   for (int c = 0; c < n_cand; ++c) {
     const alego_graph_edge& e = cand[c];
-    if (e.from < 0 || e.to < 0 || e.from >= N || e.to >= N || e.from == e.to) return ALEGO_ERR_ARG;
-    for (int k = 0; k < 12; ++k) if (!(e.between[k] - e.between[k] == 0.0)) return ALEGO_ERR_ARG;
-    for (int k = 0; k < 6; ++k) if (!(e.variance[k] > 0.0) || !(e.variance[k] - e.variance[k] == 0.0)) return ALEGO_ERR_ARG;
+    if (!pg_loop_ids(e.from, e.to, N) || !pg_edge_finite(e.between, e.variance)) return ALEGO_ERR_ARG;
   }
   PgcHost H;
   if (int r = pgc_host_factor(poses12, N, edges, n_edges, &H)) return r;

@@ -1,11 +1,12 @@
 // pg_work.h — what kernels_graph.hip (the optimiser) and kernels_pgcov.hip (marginal covariances and the loop-edge
 // gate, section 20) share: the chunk scratch of the key-pose graph, its control words, the context kept with the handle and the host
-// helpers that size the scratch and read a slot's counters.
+// helpers that size the scratch, cut a call into chunks, fill a chunk's control words and read a slot's counters.  The block arithmetic
+// of the chain factor and its sweeps, and what an edge must be to enter a graph, is pg_chain.h.
 #ifndef ALEGO_PG_WORK_H_
 #define ALEGO_PG_WORK_H_
 #include <hip/hip_runtime.h>
 
-#include <cmath>
+#include <algorithm>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -13,6 +14,7 @@
 #include "../../include/alego_mi355x.h"
 #include "dev_mem.h"
 #include "kf_store.h"
+#include "pg_chain.h"
 #include "pgraph.h"
 
 #define PG_T 256                       // workgroup of the per-edge / per-node / per-slot-reduction kernels
@@ -64,10 +66,24 @@ inline size_t pg_layout(PgWork* W, char* base, int S, int Nmax, int Lmax) {
   pg_take(base, &o, &W->Z, s * N * 6 * R); pg_take(base, &o, &W->C, s * 36 * (size_t)Lmax * Lmax);
   return o;
 }
-inline bool pg_finite_edge(const alego_graph_edge& e) {
-  for (int k = 0; k < 12; ++k) if (!std::isfinite(e.between[k])) return false;
-  for (int k = 0; k < 6; ++k) if (!(e.variance[k] > 0.0) || !std::isfinite(e.variance[k])) return false;
-  return true;
+// how a call is cut into chunks: the largest graph among its entries sizes every entry, the budget the entries of a chunk
+struct PgPlan {
+  int Nmax = 1, Lmax = 0, chunk = 0;
+  void cover(int N, int NL) { Nmax = std::max(Nmax, N); Lmax = std::max(Lmax, NL); }
+  // layout(base, S) -> bytes of a chunk of S entries; slack: what the alignment of one entry's arrays can add.  Reserves the scratch of a chunk.
+  template <class F> hipError_t reserve(PgCtx* C, size_t entries, size_t slack, F layout) {
+    const size_t per = layout(nullptr, 1) + slack;
+    chunk = (int)std::max<long long>(1, std::min<long long>((long long)entries, C->budget / (long long)per));
+    return C->buf.reserve(layout(nullptr, chunk));
+  }
+};
+// the control words of a chunk on the host ([S][PC_COUNT], zero before): entry q's graph and candidates; then their way to the device
+inline void pg_ctl_entry(std::vector<int>* ctl, int q, int N, int NL, int slot, int NC = 0, int NU = 0) {
+  int* w = ctl->data() + (size_t)q * PC_COUNT;
+  w[PC_N] = N; w[PC_NL] = NL; w[PC_SLOT] = slot; w[PC_NC] = NC; w[PC_NU] = NU;
+}
+inline hipError_t pg_ctl_upload(const PgWork& W, const std::vector<int>& ctl, hipStream_t st) {
+  return hipMemcpyAsync(W.ctl, ctl.data(), ctl.size() * sizeof(int), hipMemcpyHostToDevice, st);
 }
 inline int pg_fail(std::string* err, const char* msg, int rc) { *err = msg; return rc; }
 // the counters of every slot: arc = LmCtx::arc_stat, pg = LmCtx::pg_stat
@@ -76,26 +92,6 @@ inline int pg_read_stats(const LmCtx& L, int n_slots, std::vector<int>* arc, std
   if (hipMemcpy(arc->data(), L.arc_stat, arc->size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
       hipMemcpy(pg->data(), L.pg_stat, pg->size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return pg_fail(err, "graph: device read failed", ALEGO_ERR_HIP);
   return 0;
-}
-
-// y <- L_kk^-1 y (forward) / L_kk^-T y (backward) for one 6-vector
-DEV_INLINE void pg_lsolve(const double* Lk, double* y) {
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    double a = y[i];
-#pragma unroll
-    for (int j = 0; j < i; ++j) a -= Lk[i * 6 + j] * y[j];
-    y[i] = a / Lk[i * 6 + i];
-  }
-}
-DEV_INLINE void pg_ltsolve(const double* Lk, double* y) {
-#pragma unroll
-  for (int i = 5; i >= 0; --i) {
-    double a = y[i];
-#pragma unroll
-    for (int j = i + 1; j < 6; ++j) a -= Lk[j * 6 + i] * y[j];
-    y[i] = a / Lk[i * 6 + i];
-  }
 }
 
 // pg_init -> pg_linearize -> pg_assemble -> pg_factor_chain -> pg_solve once for the S entries of W (kernels_graph.hip): leaves the factor of

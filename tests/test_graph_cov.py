@@ -246,9 +246,10 @@ def _case_text(X, g, pairs, cands):
 
 
 def test_header_under_sanitizers(tmp_path):
-    """csrc/pg_cov_math.h compiled for the host with -fsanitize=address,undefined as a program of its own, over the cases of the tests above"""
+    """csrc/pg_cov_math.h compiled for the host with -fsanitize=address,undefined as a program of its own, over the cases of the tests above;
+    before them the program holds every function of csrc/pg_chain.h against its plain statement, bit for bit ("pg_chain ok <checks>" on stderr)"""
     exe = str(tmp_path / "pg_cov_math_check")
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-Wno-unknown-pragmas", "-ffp-contract=off", "-fsanitize=address,undefined",
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-pthread", "-Wall", "-Wextra", "-Werror", "-Wno-unknown-pragmas", "-ffp-contract=off", "-fsanitize=address,undefined",
            "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan",   # the sanitizers' runtimes are part of the program: nothing has to be preloaded
            "-I" + os.path.join(ROOT, "a-lego-loam_amd", "csrc"), os.path.join(ROOT, "tests", "pg_cov_math", "pg_cov_math_check.cpp"), "-o", exe]
     b = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
@@ -263,6 +264,9 @@ def test_header_under_sanitizers(tmp_path):
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
     r = subprocess.run([exe, str(path)], capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0 and f"pg_cov_math ok {len(jobs)}" in r.stdout, (r.returncode, r.stdout[-1000:], r.stderr[-3000:])
+    done = [ln for ln in r.stderr.splitlines() if ln.startswith("pg_chain ok ")]
+    assert len(done) == 1 and int(done[0].split()[2]) > 0, r.stderr[-3000:]
+    print(done[0])
     rows = r.stdout.strip().split("\n")
     assert len(rows) == len(jobs) + 1
     for (name, X, g, D, pairs, cands), row in zip(jobs, rows):
