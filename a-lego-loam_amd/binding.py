@@ -117,6 +117,12 @@ class LoopResult(C.Structure):
                 ("t_correct", C.c_float * 16), ("between", C.c_double * 12), ("noise_variance", C.c_double)]
 
 
+def _slot_list(slots, pairs=False):
+    """a list of slots as (int32 array, count); with pairs, a list of (src, dst) pairs as (src array, dst array, count)"""
+    a = np.ascontiguousarray(slots, np.int32).reshape((-1, 2) if pairs else -1)
+    return (np.ascontiguousarray(a[:, 0]), np.ascontiguousarray(a[:, 1]), a.shape[0]) if pairs else (a, a.shape[0])
+
+
 def _loop_result(r):
     return dict(status=int(r.status), latest_id=int(r.latest_id), closest_id=int(r.closest_id), converged=int(r.converged),
                 iterations=int(r.iterations), n_source=int(r.n_source), n_target=int(r.n_target), fitness=float(r.fitness),
@@ -1175,10 +1181,10 @@ class Handle:
     def loop_search(self, slots):
         """alego_loop_search: one dict per listed slot (status, ids, converged, iterations, n_source, n_target, fitness, T, t_correct,
         between, noise_variance)"""
-        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
-        out = (LoopResult * max(sl.shape[0], 1))()
-        self._check(lib().alego_loop_search(self._h, sl.ctypes.data, sl.shape[0], out), "alego_loop_search")
-        return [_loop_result(out[i]) for i in range(sl.shape[0])]
+        sl, n = _slot_list(slots)
+        out = (LoopResult * max(n, 1))()
+        self._check(lib().alego_loop_search(self._h, sl.ctypes.data, n, out), "alego_loop_search")
+        return [_loop_result(out[i]) for i in range(n)]
 
     # ---- loop closures by appearance (needs map_enable) ----
     def loop_appearance_enable(self, max_range=0.0, z_offset=float("nan")):
@@ -1187,13 +1193,13 @@ class Handle:
     def loop_search_appearance(self, slots, n_cand=0, verify=-1, max_dist=0, max_jump=0.0, fitness_max=0.0):
         """alego_loop_search_appearance: one dict per listed slot — loop_search's keys (T = the world correction: graph_add_loops takes the dicts
         unchanged) plus n_eligible, n_cand, cand_id, cand_dist, cand_shift, verified, guess6, icp_final"""
-        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
-        out = (LoopResult * max(sl.shape[0], 1))()
-        info = (LoopAppInfo * max(sl.shape[0], 1))()
+        sl, n = _slot_list(slots)
+        out = (LoopResult * max(n, 1))()
+        info = (LoopAppInfo * max(n, 1))()
         opts = LoopAppOpts(int(n_cand), int(verify), int(max_dist), float(max_jump), float(fitness_max))
-        self._check(lib().alego_loop_search_appearance(self._h, sl.ctypes.data, sl.shape[0], C.byref(opts), out, info), "alego_loop_search_appearance")
+        self._check(lib().alego_loop_search_appearance(self._h, sl.ctypes.data, n, C.byref(opts), out, info), "alego_loop_search_appearance")
         res = []
-        for i in range(sl.shape[0]):
+        for i in range(n):
             d, f = _loop_result(out[i]), info[i]
             k = int(f.n_cand)
             d.update(n_eligible=int(f.n_eligible), n_cand=k, cand_id=np.array(f.cand_id[:k], np.int32), cand_dist=np.array(f.cand_dist[:k], np.int32),
@@ -1206,9 +1212,7 @@ class Handle:
     def map_align(self, pairs, n_queries=0, n_cand=0, max_dist=0, min_support=0, fitness_max=0.0, tol_trans=0.0, tol_rot=0.0, hyps=True):
         """alego_map_align: one dict per pair (src, dst) — status, n_queries, n_accepted, best, support, T (3, 4) f64 and, with hyps, `hyp`: one dict per
         query (src_frame, dst_frame, dist, shift, tried, accepted, converged, iterations, n_source, n_target, support, inlier, fitness, guess6, icp_final, T)"""
-        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
-        src, dst = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
-        n = pr.shape[0]
+        src, dst, n = _slot_list(pairs, pairs=True)
         out = (MapAlignResult * max(n, 1))()
         hyp = (MapAlignHyp * (max(n, 1) * ALIGN_MAX_QUERIES))() if hyps else None
         opts = MapAlignOpts(int(n_queries), int(n_cand), int(max_dist), int(min_support), float(fitness_max), float(tol_trans), float(tol_rot))
@@ -1233,21 +1237,19 @@ class Handle:
     # ---- a slot moved, one slot's archive appended to another's, on the device (needs map_enable) ----
     def map_move(self, slots, T):
         """alego_map_move: T (n, 3, 4) or one (3, 4) / (4, 4) for every listed slot; returns the status per slot (2 moved, 0 no key frame, -1 dropped frames)"""
-        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        sl, n = _slot_list(slots)
         T = np.asarray(T, np.float64)
         if T.ndim == 2:
-            T = np.broadcast_to(T, (sl.shape[0],) + T.shape)
-        T12 = np.ascontiguousarray(T.reshape(sl.shape[0], T.shape[-2] * T.shape[-1])[:, :12])
-        st = np.zeros(max(sl.shape[0], 1), np.int32)
-        self._check(lib().alego_map_move(self._h, sl.ctypes.data, sl.shape[0], T12.ctypes.data, st.ctypes.data), "alego_map_move")
-        return [int(v) for v in st[:sl.shape[0]]]
+            T = np.broadcast_to(T, (n,) + T.shape)
+        T12 = np.ascontiguousarray(T.reshape(n, T.shape[-2] * T.shape[-1])[:, :12])
+        st = np.zeros(max(n, 1), np.int32)
+        self._check(lib().alego_map_move(self._h, sl.ctypes.data, n, T12.ctypes.data, st.ctypes.data), "alego_map_move")
+        return [int(v) for v in st[:n]]
 
     def map_merge(self, pairs, T, stamp_offset=0.0, seam_variance=None, hyps=None):
         """alego_map_merge: pairs (src, dst); T (n, 3, 4) or one for all; hyps: None or, per pair, the `hyp` list of map_align (or None).
         One dict per pair: status (2 merged, 0 empty source, -1 dropped frames, -3 does not fit), frames, points, loop_edges, cross_edges"""
-        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
-        src, dst = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
-        n = pr.shape[0]
+        src, dst, n = _slot_list(pairs, pairs=True)
         T = np.asarray(T, np.float64)
         if T.ndim == 2:
             T = np.broadcast_to(T, (n,) + T.shape)
@@ -1268,12 +1270,12 @@ class Handle:
     def map_thin(self, slots, min_dist):
         """alego_map_thin: one dict per slot: status (2 thinned, 1 nothing to drop, 0 no key frame, -1 dropped frames), frames_before, frames,
         points_before, points"""
-        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        sl, n = _slot_list(slots)
         opts = MapThinOpts(float(min_dist))
-        out = (MapThinResult * max(sl.shape[0], 1))()
-        self._check(lib().alego_map_thin(self._h, sl.ctypes.data, sl.shape[0], C.byref(opts), out), "alego_map_thin")
+        out = (MapThinResult * max(n, 1))()
+        self._check(lib().alego_map_thin(self._h, sl.ctypes.data, n, C.byref(opts), out), "alego_map_thin")
         return [dict(status=int(r.status), frames_before=int(r.frames_before), frames=int(r.frames), points_before=int(r.points_before), points=int(r.points))
-                for r in out[:sl.shape[0]]]
+                for r in out[:n]]
 
     def debug_thin_select(self, keyposes6, protect, min_dist):
         """the selection kernel of alego_map_thin alone on the caller's arrays: the keep mask (n,) uint8"""
@@ -1323,11 +1325,11 @@ class Handle:
 
     def loc_relocalize(self, slots, n_cand=0, verify=-1, apply=False):
         """alego_loc_relocalize: one dict per listed slot (status, candidates, the verified candidate's ICP, t_map, rc, params6)"""
-        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
-        out = (RelocResult * max(sl.shape[0], 1))()
+        sl, n = _slot_list(slots)
+        out = (RelocResult * max(n, 1))()
         opts = RelocOpts(int(n_cand), int(verify), int(bool(apply)))
-        self._check(lib().alego_loc_relocalize(self._h, sl.ctypes.data, sl.shape[0], C.byref(opts), out), "alego_loc_relocalize")
-        return [_reloc_result(out[i]) for i in range(sl.shape[0])]
+        self._check(lib().alego_loc_relocalize(self._h, sl.ctypes.data, n, C.byref(opts), out), "alego_loc_relocalize")
+        return [_reloc_result(out[i]) for i in range(n)]
 
     def debug_reloc_search(self, map_desc, q_desc, n_cand):
         """the search kernels of alego_loc_relocalize alone: (ids, dists, shifts), each (n_q, n_cand) int32, -1 where the map has fewer frames"""
@@ -1363,14 +1365,14 @@ class Handle:
 
     def graph_add_loops(self, slots, results):
         """results: the dicts loop_search returned for `slots`; entries with status == 2 are appended"""
-        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
-        r = (LoopResult * max(sl.shape[0], 1))()
+        sl, n = _slot_list(slots)
+        r = (LoopResult * max(n, 1))()
         for i, d in enumerate(results):
             r[i].status, r[i].latest_id, r[i].closest_id = d["status"], d["latest_id"], d["closest_id"]
             r[i].fitness, r[i].noise_variance = d["fitness"], d["noise_variance"]
             r[i].correction[:] = np.asarray(d["T"], np.float32).reshape(16).tolist()
             r[i].between[:] = np.asarray(d["between"], np.float64).reshape(12).tolist()
-        self._check(lib().alego_graph_add_loops(self._h, sl.ctypes.data, sl.shape[0], r), "alego_graph_add_loops")
+        self._check(lib().alego_graph_add_loops(self._h, sl.ctypes.data, n, r), "alego_graph_add_loops")
 
     def graph_add_edge(self, frm, to, between, variance, correction=None, slot=0):
         e = graph_edges([frm], [to], [between], [variance])
@@ -1380,12 +1382,12 @@ class Handle:
     def graph_optimize(self, slots, max_iters=0, step_tol=0.0, apply=False):
         """alego_graph_optimize: one dict per listed slot (status, iterations, n_poses, n_loops, applied, cost0, cost, last_step);
         max_iters / step_tol 0 = the library's defaults"""
-        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        sl, n = _slot_list(slots)
         o = GraphOpts(int(max_iters), float(step_tol), int(bool(apply)))
-        out = (GraphResult * max(sl.shape[0], 1))()
-        self._check(lib().alego_graph_optimize(self._h, sl.ctypes.data, sl.shape[0], C.byref(o), out), "alego_graph_optimize")
+        out = (GraphResult * max(n, 1))()
+        self._check(lib().alego_graph_optimize(self._h, sl.ctypes.data, n, C.byref(o), out), "alego_graph_optimize")
         return [dict(status=int(r.status), iterations=int(r.iterations), n_poses=int(r.n_poses), n_loops=int(r.n_loops), applied=int(r.applied),
-                     cost0=float(r.cost0), cost=float(r.cost), last_step=float(r.last_step)) for r in out[:sl.shape[0]]]
+                     cost0=float(r.cost0), cost=float(r.cost), last_step=float(r.last_step)) for r in out[:n]]
 
     def graph_get_estimate(self, first=0, n=None, slot=0):
         """(n, 3, 4) f64 poses of the slot's last optimise"""
@@ -1397,33 +1399,33 @@ class Handle:
 
     def graph_marginals(self, slots, cap=None):
         """alego_graph_marginals: (one dict (status, n_poses, n_loops) per listed slot, cov (n, cap, 6, 6)); cap = None: the longest archive listed"""
-        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        sl, n = _slot_list(slots)
         if cap is None:
             cap = max([self.map_status(int(s))[0] for s in sl] + [1])
-        cov = np.zeros((max(sl.shape[0], 1), max(int(cap), 1), 36), np.float64)
-        out = (GraphCovResult * max(sl.shape[0], 1))()
-        self._check(lib().alego_graph_marginals(self._h, sl.ctypes.data, sl.shape[0], int(cap), cov.ctypes.data, out), "alego_graph_marginals")
-        return ([dict(status=int(r.status), n_poses=int(r.n_poses), n_loops=int(r.n_loops)) for r in out[:sl.shape[0]]],
-                cov[:sl.shape[0]].reshape(sl.shape[0], max(int(cap), 1), 6, 6))
+        cov = np.zeros((max(n, 1), max(int(cap), 1), 36), np.float64)
+        out = (GraphCovResult * max(n, 1))()
+        self._check(lib().alego_graph_marginals(self._h, sl.ctypes.data, n, int(cap), cov.ctypes.data, out), "alego_graph_marginals")
+        return ([dict(status=int(r.status), n_poses=int(r.n_poses), n_loops=int(r.n_loops)) for r in out[:n]],
+                cov[:n].reshape(n, max(int(cap), 1), 6, 6))
 
     def graph_check_edges(self, slots, frm, to, between, variance):
         """alego_graph_check_edges: candidate i for slots[i]; one dict (status, d2, error (6,), cov (6, 6)) per candidate"""
-        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
-        out = (GraphCheck * max(sl.shape[0], 1))()
-        self._check(lib().alego_graph_check_edges(self._h, sl.ctypes.data, sl.shape[0], graph_edges(frm, to, between, variance), out), "alego_graph_check_edges")
-        return _graph_checks_out(out, sl.shape[0])
+        sl, n = _slot_list(slots)
+        out = (GraphCheck * max(n, 1))()
+        self._check(lib().alego_graph_check_edges(self._h, sl.ctypes.data, n, graph_edges(frm, to, between, variance), out), "alego_graph_check_edges")
+        return _graph_checks_out(out, n)
 
     def graph_check_loops(self, slots, results):
         """alego_graph_check_loops: the edge graph_add_loops would append for every dict of loop_search (status == 2; others give status 0)"""
-        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
-        r = (LoopResult * max(sl.shape[0], 1))()
+        sl, n = _slot_list(slots)
+        r = (LoopResult * max(n, 1))()
         for i, d in enumerate(results):
             r[i].status, r[i].latest_id, r[i].closest_id = d["status"], d["latest_id"], d["closest_id"]
             r[i].fitness, r[i].noise_variance = d["fitness"], d["noise_variance"]
             r[i].between[:] = np.asarray(d["between"], np.float64).reshape(12).tolist()
-        out = (GraphCheck * max(sl.shape[0], 1))()
-        self._check(lib().alego_graph_check_loops(self._h, sl.ctypes.data, sl.shape[0], r, out), "alego_graph_check_loops")
-        return _graph_checks_out(out, sl.shape[0])
+        out = (GraphCheck * max(n, 1))()
+        self._check(lib().alego_graph_check_loops(self._h, sl.ctypes.data, n, r, out), "alego_graph_check_loops")
+        return _graph_checks_out(out, n)
 
     def debug_nn1(self, tgt, queries):
         """the grid 1-NN of alego_loop_search alone: (index, f32 squared distance) per query"""
@@ -1442,10 +1444,10 @@ class Handle:
 
     def regcov_get(self, slots=(0,)):
         """alego_regcov_get: one dict per listed slot (status, n_edge, n_plane, n_degenerate, frame, cost, sigma2, info, eigval, eigvec, cov, variance)"""
-        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
-        out = (RegCov * max(sl.shape[0], 1))()
-        self._check(lib().alego_regcov_get(self._h, sl.ctypes.data, sl.shape[0], out), "alego_regcov_get")
-        return [_regcov_out(r) for r in out[:sl.shape[0]]]
+        sl, n = _slot_list(slots)
+        out = (RegCov * max(n, 1))()
+        self._check(lib().alego_regcov_get(self._h, sl.ctypes.data, n, out), "alego_regcov_get")
+        return [_regcov_out(r) for r in out[:n]]
 
     def debug_regcov(self, params6, edge_rows9, plane_rows7):
         """alego_debug_regcov: lm_regcov alone on rows (a, b, p) (n, 9) and (n, d, p) (m, 7) at params6 (p is rounded to f32)"""

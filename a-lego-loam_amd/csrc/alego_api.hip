@@ -9,11 +9,11 @@
 #include <algorithm>
 #include <cstring>
 #include <mutex>
-#include <set>
 #include <string>
 #include <vector>
 
 #include "../../include/alego_mi355x.h"
+#include "api_gate.h"
 #include "dev_common.h"
 #include "dev_mem.h"
 #include "front_end.h"
@@ -119,22 +119,66 @@ int env_int(const char* name, int dflt) { const char* e = getenv(name); return e
 // LaserMapping work still in flight on the groups' back streams (alego_batch_run without sync): every entry point that reads or writes
 // LaserOdometry / LaserMapping state waits for it first — per-slot calls for their own group's back stream (check_slot), whole-handle
 // calls (alego_lo_process, alego_lm_process, alego_dist_*) for all of them; alego_stream_run runs LaserMapping on the back stream itself and
-// orders its streams behind it with events.  A handle without back streams (stream_plan.h) has nothing to wait for.  alego_batch_load only writes the
-// front end's input ring and does not wait (a host-fed batch_load + batch_run(sync = 0) loop keeps its overlap).
+// orders its streams behind it with events.  A handle without back streams (stream_plan.h) has nothing to wait for.
 void drain_back(alego_handle* h, int slot = -1) {
   if (slot >= 0 && !h->back.empty()) { (void)hipStreamSynchronize(h->back[std::min<size_t>((size_t)(slot / h->gsize), h->back.size() - 1)]); return; }
   for (hipStream_t s : h->back) (void)hipStreamSynchronize(s);
 }
-int check_slot(alego_handle* h, int slot, bool drain = true) {
-  if (!h) return ALEGO_ERR_ARG;
+// the per-slot wait: the slot exists and, unless the caller keeps the back stream running (it says why), its group's back stream is drained
+enum BackStream { BACK_DRAINED, BACK_KEPT_RUNNING };
+int check_slot(alego_handle* h, int slot, BackStream back = BACK_DRAINED) {
   if (slot < 0 || slot >= h->d.n_slots) { h->err = "slot out of range"; return ALEGO_ERR_ARG; }
-  if (drain) drain_back(h, slot);
+  if (back == BACK_DRAINED) drain_back(h, slot);
   return 0;
 }
+// behind everything already queued on every stream group: the host waits for all the handle's streams, front, back and look-ahead
+#define WAIT_ALL(h) HIP_TRY(h, sync_all(h))
 
-// a localising handle (alego_loc_enable) owns no key frames of its own: the calls that read, write or archive them refuse
-int not_localising(alego_handle* h, const char* what) {
-  if (h->lm && lm_host_localising(h->lm)) { h->err = std::string(what) + ": not available on a localising handle (alego_loc_enable)"; return ALEGO_ERR_ARG; }
+// ---- the gate (api_gate.h has the order of checks and the list rules) --------------------------------------------------------------
+// Opened on the first line of every entry point that takes a handle: a null handle is refused; otherwise the handle's device is current and
+// every ALEGO_LAUNCH of this thread is timed into the handle's own profiler until the call returns.  It nests (an entry point may call
+// another), never synchronises and never allocates.  Between calls g_prof is null: nothing outlives the handle it points into.
+struct Gate {
+  Profiler* const prev;
+  explicit Gate(alego_handle* h) : prev(g_prof) { if (h) { (void)hipSetDevice(h->device); timed_into(&h->prof); } }
+  ~Gate() { timed_into(prev); }
+  static void timed_into(Profiler* p) { g_prof = p; }
+};
+#define ALEGO_GATE(h) const Gate gate_(h); if (!(h)) return ALEGO_ERR_ARG
+#define ALEGO_GATE_SLOT(h, slot) ALEGO_GATE(h); if (int r_ = check_slot(h, slot)) return r_   // a per-slot call: the gate, then the per-slot wait
+
+// The state a call needs, checked in the order of the bits; the texts are those the calls have always given.
+enum Need : unsigned {
+  NOT_STREAM_MODE = 1u << 0,   // not after alego_stream_setup
+  MAPPING         = 1u << 1,   // a localising handle owns no key frames of its own: the calls that read, write or archive them refuse
+  LOCALISING      = 1u << 2,   // alego_loc_enable / alego_loc_enable_from_map has run ...
+  LOCALISING_SEED = 1u << 3,   // ... the same for alego_reloc_enable, whose text names the first of the two only
+  UNUSED_HANDLE   = 1u << 4,   // no archive, no graph, no scan run yet in any slot
+  ARCHIVE         = 1u << 5,   // alego_map_enable has run ...
+  ARCHIVE_FIRST   = 1u << 6,   // ... the same for an *_enable that builds on it ("alego_map_enable first")
+  GRAPH           = 1u << 7,   // alego_graph_enable has run
+  APPEARANCE      = 1u << 8,   // alego_loop_appearance_enable has run
+  RELOCALISATION  = 1u << 9,   // alego_reloc_enable has run
+};
+int gate_need(alego_handle* h, const char* what, unsigned need) {
+  auto refuse = [&](const char* why) { h->err = std::string(what) + ": " + why; return ALEGO_ERR_ARG; };
+  const bool localising = h->lm && lm_host_localising(h->lm);
+  if ((need & NOT_STREAM_MODE) && h->stream_mode) return refuse("not available with alego_stream_setup");
+  if ((need & MAPPING) && localising) return refuse("not available on a localising handle (alego_loc_enable)");
+  if ((need & LOCALISING) && !localising) return refuse("the handle does not localise (alego_loc_enable / alego_loc_enable_from_map)");
+  if ((need & LOCALISING_SEED) && !localising) return refuse("the handle does not localise (alego_loc_enable)");
+  if (need & UNUSED_HANDLE) {
+    if (h->map_on || h->graph_on) return refuse("the key-frame archive / key-pose graph belong to a mapping handle");
+    bool used = false;
+    for (long v : h->lo_scans) used = used || v != 0;
+    for (long v : h->grp_scans) used = used || v != 0;
+    if (used) return refuse("call it before the first scan of any slot");
+  }
+  if ((need & ARCHIVE) && !h->map_on) return refuse("the key-frame archive is off (alego_map_enable)");
+  if ((need & ARCHIVE_FIRST) && !h->map_on) return refuse("the key-frame archive is off (alego_map_enable first)");
+  if ((need & GRAPH) && !h->graph_on) return refuse("the key-pose graph is off (alego_map_enable, then alego_graph_enable)");
+  if ((need & APPEARANCE) && !loop_app_enabled(h->rl)) return refuse("the appearance search is off (alego_map_enable, then alego_loop_appearance_enable)");
+  if ((need & RELOCALISATION) && !reloc_enabled(h->rl)) return refuse("relocalisation is off (alego_loc_enable, then alego_reloc_enable)");
   return 0;
 }
 
@@ -142,6 +186,7 @@ int not_localising(alego_handle* h, const char* what) {
 
 extern "C" {
 
+// These read the handle's host fields only: they stay outside the gate and touch no device state.
 int alego_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -358,7 +403,6 @@ void alego_destroy(alego_handle* h) {
   if (!h) return;
   hipSetDevice(h->device);
   (void)sync_all(h);
-  if (g_prof == &h->prof) g_prof = nullptr;
   if (h->lm) lm_host_destroy(h->lm);
   loop_ctx_destroy(h->lc);
   reloc_ctx_destroy(h->rl);
@@ -375,16 +419,16 @@ void alego_destroy(alego_handle* h) {
 }
 
 int alego_synchronize(alego_handle* h) {
-  if (!h) return ALEGO_ERR_ARG;
-  HIP_TRY(h, sync_all(h));
+  ALEGO_GATE(h);
+  WAIT_ALL(h);
   return 0;
 }
 
 int alego_batch_load(alego_handle* h, int slot, int ring_pos, const alego_point* pts, int32_t n) {
-  if (int r = check_slot(h, slot, false)) return r;
+  ALEGO_GATE(h);
+  if (int r = check_slot(h, slot, BACK_KEPT_RUNNING)) return r;   // only the front end's input ring is written: a host-fed batch_load + batch_run(sync = 0) loop keeps its overlap
   if (ring_pos < 0 || ring_pos >= h->d.ring_len || n < 0 || (n > 0 && !pts)) { h->err = "ring_pos / n out of range or null points"; return ALEGO_ERR_ARG; }
   if (n > h->d.Pcap) { h->err = "scan larger than n_scan*horizon_scan"; return ALEGO_ERR_CAPACITY; }
-  hipSetDevice(h->device);
   float4* dst = h->d.in_pts + ((size_t)slot * h->d.ring_len + ring_pos) * h->d.Pcap;
   if (n > 0) HIP_TRY(h, hipMemcpyAsync(dst, pts, (size_t)n * sizeof(alego_point), hipMemcpyHostToDevice, stream_of(h, slot)));
   HIP_TRY(h, hipMemcpyAsync(h->d.in_n + slot * h->d.ring_len + ring_pos, &n, sizeof(int), hipMemcpyHostToDevice, stream_of(h, slot)));
@@ -393,27 +437,26 @@ int alego_batch_load(alego_handle* h, int slot, int ring_pos, const alego_point*
 }
 
 int alego_replay_create(alego_handle* h, int n_bags, int bag_len) {
-  if (!h || n_bags < 1 || bag_len < 1) return ALEGO_ERR_ARG;
+  ALEGO_GATE(h);
+  if (n_bags < 1 || bag_len < 1) return ALEGO_ERR_ARG;
   if (h->d.bag_pts) { h->err = "alego_replay_create: the bag store exists already"; return ALEGO_ERR_ARG; }
-  hipSetDevice(h->device);
   float4* pts = nullptr; int* cnt = nullptr; int2* src = nullptr;
   if (dalloc(h, &pts, (size_t)n_bags * bag_len * h->d.Pcap, false) || dalloc(h, &cnt, (size_t)n_bags * bag_len) || dalloc(h, &src, (size_t)h->d.n_slots)) return ALEGO_ERR_HIP;
   h->d.bag_pts = pts; h->d.bag_n = cnt; h->d.bag_src = src; h->d.n_bags = n_bags; h->d.bag_len = bag_len;
   return 0;
 }
 int alego_replay_load(alego_handle* h, int bag, int scan, const alego_point* pts, int32_t n) {
-  if (!h || !h->d.bag_pts || bag < 0 || bag >= h->d.n_bags || scan < 0 || scan >= h->d.bag_len || n < 0 || (n > 0 && !pts)) return ALEGO_ERR_ARG;
+  ALEGO_GATE(h);
+  if (!h->d.bag_pts || bag < 0 || bag >= h->d.n_bags || scan < 0 || scan >= h->d.bag_len || n < 0 || (n > 0 && !pts)) return ALEGO_ERR_ARG;
   if (n > h->d.Pcap) { h->err = "scan larger than n_scan*horizon_scan"; return ALEGO_ERR_CAPACITY; }
-  hipSetDevice(h->device);
   const size_t idx = (size_t)bag * h->d.bag_len + scan;
   HIP_TRY(h, hipMemcpy(const_cast<float4*>(h->d.bag_pts) + idx * h->d.Pcap, pts, (size_t)n * sizeof(alego_point), hipMemcpyHostToDevice));
   HIP_TRY(h, hipMemcpy(const_cast<int*>(h->d.bag_n) + idx, &n, sizeof(int), hipMemcpyHostToDevice));
   return 0;
 }
 int alego_replay_assign(alego_handle* h, int slot, int bag, int start_scan) {
-  if (int r = check_slot(h, slot)) return r;
+  ALEGO_GATE_SLOT(h, slot);
   if (!h->d.bag_pts || bag < 0 || bag >= h->d.n_bags || start_scan < 0) return ALEGO_ERR_ARG;
-  hipSetDevice(h->device);
   const int2 v = make_int2(bag, start_scan % h->d.bag_len);
   HIP_TRY(h, hipMemcpy(const_cast<int2*>(h->d.bag_src) + slot, &v, sizeof(v), hipMemcpyHostToDevice));
   h->replay_assigned = true;
@@ -421,14 +464,13 @@ int alego_replay_assign(alego_handle* h, int slot, int bag, int start_scan) {
 }
 
 int alego_stream_setup(alego_handle* h, int bag, int start_scan) {
-  if (!h) return ALEGO_ERR_ARG;
-  if (int r = not_localising(h, "alego_stream_setup")) return r;
+  ALEGO_GATE(h);
+  if (int r = gate_need(h, "alego_stream_setup", MAPPING)) return r;
   if (!h->d.bag_pts || bag < 0 || bag >= h->d.n_bags || start_scan < 0) { h->err = "alego_stream_setup: needs alego_replay_create and a valid bag"; return ALEGO_ERR_ARG; }
   if (h->d.n_slots < 3 || h->streams.size() != 1) { h->err = "alego_stream_setup: the handle needs n_slots = 1 + 2 W >= 3 (one stream group)"; return ALEGO_ERR_ARG; }
   if (h->d.traj) { h->err = "alego_stream_setup: the per-scan pose log belongs to the batch path"; return ALEGO_ERR_ARG; }
   if (h->map_on) { h->err = "alego_stream_setup: the key-frame archive belongs to the batch / single-scan paths"; return ALEGO_ERR_ARG; }
   if (h->P.deskew_mode) { h->err = "alego_stream_setup: bags carry no stamps / IMU data; the motion de-skew runs through alego_scan_process / alego_lo_process"; return ALEGO_ERR_ARG; }
-  hipSetDevice(h->device);
   const int W = (h->d.n_slots - 1) / 2;
   if (int r = alego_replay_assign(h, 0, bag, start_scan)) return r;
   for (int set = 0; set < 2; ++set)
@@ -454,12 +496,10 @@ int alego_stream_setup(alego_handle* h, int bag, int start_scan) {
 }
 
 int alego_stream_run(alego_handle* h, int first_step, int n_scans, int stages, int sync) {
-  if (!h) return ALEGO_ERR_ARG;
+  ALEGO_GATE(h);
   if (!h->stream_mode) { h->err = "alego_stream_run: call alego_stream_setup first"; return ALEGO_ERR_ARG; }
-  hipSetDevice(h->device);
   // (no drain_back: a one-group handle's back stream is sC here, and the three streams start behind each other below — a host wait
   // would only stall a caller that enqueues run after run with sync = 0)
-  g_prof = &h->prof;
   const int W = h->lanes;
   hipStream_t sA = h->streams[0], sB = h->sB, sC = h->sC;
   auto ev = [&]() -> hipEvent_t {
@@ -515,7 +555,7 @@ int alego_stream_run(alego_handle* h, int first_step, int n_scans, int stages, i
     lm_done[set] = done;
   }
   HIP_TRY(h, hipGetLastError());
-  if (sync) HIP_TRY(h, sync_all(h));
+  if (sync) WAIT_ALL(h);
   return 0;
 }
 
@@ -524,7 +564,6 @@ static int enqueue_scan(alego_handle* h, int slot0, int n, int pos, int stages, 
   DevCtx d = view(h, slot0, n);
   d.replay_bag = (stages & ALEGO_REPLAY_BAG) ? 1 : 0;
   hipStream_t S = stream_of(h, slot0);  // [slot0, slot0+n) lies inside one stream group
-  g_prof = &h->prof;
   static const bool dbg = getenv("ALEGO_DEBUG_SYNC") != nullptr;
   auto chk = [&](const char* what) { if (dbg) { hipError_t e = hipStreamSynchronize(S); fprintf(stderr, "[alego dbg] %s: %s\n", what, hipGetErrorString(e)); } };
   if (stages & 1) { launch_ip(d, pos, want_labels, S); chk("ip"); }
@@ -553,8 +592,8 @@ static int enqueue_scan(alego_handle* h, int slot0, int n, int pos, int stages, 
 }
 
 int alego_batch_run(alego_handle* h, int first_pos, int n_scans, int stages, int sync) {
-  if (!h || n_scans < 0) return ALEGO_ERR_ARG;
-  hipSetDevice(h->device);
+  ALEGO_GATE(h);
+  if (n_scans < 0) return ALEGO_ERR_ARG;
   const int R = h->d.ring_len;
   if (h->P.deskew_mode && (stages & 2)) { h->err = "alego_batch_run: the motion de-skew needs every scan's stamp (alego_scan_process / alego_lo_process)"; return ALEGO_ERR_ARG; }
   if ((stages & ALEGO_REPLAY_BAG) && (!h->d.bag_pts || !h->replay_assigned)) { h->err = "alego_batch_run: ALEGO_REPLAY_BAG without alego_replay_create / alego_replay_assign"; return ALEGO_ERR_ARG; }
@@ -572,7 +611,7 @@ int alego_batch_run(alego_handle* h, int first_pos, int n_scans, int stages, int
     for (int s0 = 0; s0 < h->d.n_slots; s0 += h->gsize)
       if (int r = enqueue_scan(h, s0, std::min(h->gsize, h->d.n_slots - s0), pos, stages & (7 | ALEGO_REPLAY_BAG), false, /*async_lm=*/true)) return r;
   }
-  if (sync) HIP_TRY(h, sync_all(h));
+  if (sync) WAIT_ALL(h);
   return 0;
 }
 
@@ -580,7 +619,7 @@ static int fetch_pose(alego_handle* h, int slot, alego_pose* odom, alego_pose* m
   double po[PO_W], st[LO_STATE_N];
   int sc[SC_COUNT];
   const int pslot = (h->stream_mode && slot == 0) ? h->pose_slot : slot;   // alego_stream_run: the last scan's poses live in its lane
-  if (h->stream_mode) HIP_TRY(h, sync_all(h));
+  if (h->stream_mode) WAIT_ALL(h);
   HIP_TRY(h, hipMemcpyAsync(po, poses_of(h->d, pslot), sizeof(po), hipMemcpyDeviceToHost, stream_of(h, slot)));
   HIP_TRY(h, hipMemcpyAsync(st, lo_state_of(h->d, slot), sizeof(st), hipMemcpyDeviceToHost, stream_of(h, slot)));
   HIP_TRY(h, hipMemcpyAsync(sc, scal_of(h->d, slot), sizeof(sc), hipMemcpyDeviceToHost, stream_of(h, slot)));
@@ -604,17 +643,16 @@ static int fetch_pose(alego_handle* h, int slot, alego_pose* odom, alego_pose* m
 }
 
 int alego_batch_get_pose(alego_handle* h, int slot, alego_pose* odom, alego_pose* map_pose) {
-  if (int r = check_slot(h, slot)) return r;
-  hipSetDevice(h->device);
+  ALEGO_GATE_SLOT(h, slot);
   return fetch_pose(h, slot, odom, map_pose);
 }
 
 int alego_trajectory_enable(alego_handle* h, int32_t capacity_scans) {
-  if (!h || capacity_scans <= 0) return ALEGO_ERR_ARG;
+  ALEGO_GATE(h);
+  if (capacity_scans <= 0) return ALEGO_ERR_ARG;
   if (h->stream_mode) { h->err = "alego_trajectory_enable: not available with alego_stream_setup (the poses of a look-ahead stream live in its lanes)"; return ALEGO_ERR_ARG; }
   if (h->d.traj) { h->err = "alego_trajectory_enable: already enabled"; return ALEGO_ERR_ARG; }
-  hipSetDevice(h->device);
-  HIP_TRY(h, sync_all(h));
+  WAIT_ALL(h);
   double* t = nullptr;
   int* n = nullptr;
   if (dalloc(h, &t, (size_t)h->d.n_slots * capacity_scans * PO_LOG_W) || dalloc(h, &n, (size_t)h->d.n_slots)) return ALEGO_ERR_HIP;
@@ -622,9 +660,8 @@ int alego_trajectory_enable(alego_handle* h, int32_t capacity_scans) {
   return 0;
 }
 int alego_trajectory_get(alego_handle* h, int slot, int32_t first, int32_t n, double* out14) {
-  if (int r = check_slot(h, slot)) return r;
+  ALEGO_GATE_SLOT(h, slot);
   if (!h->d.traj || first < 0 || n < 0 || (n > 0 && !out14)) return ALEGO_ERR_ARG;
-  hipSetDevice(h->device);
   hipStream_t S = stream_of(h, slot);
   int logged = 0;
   HIP_TRY(h, hipMemcpyAsync(&logged, traj_n_of(h->d, slot), sizeof(int), hipMemcpyDeviceToHost, S));
@@ -639,12 +676,11 @@ int alego_trajectory_get(alego_handle* h, int slot, int32_t first, int32_t n, do
 }
 
 int alego_batch_get_counts(alego_handle* h, int slot, int32_t* out, int cap) {
-  if (int r = check_slot(h, slot)) return r;
-  hipSetDevice(h->device);
+  ALEGO_GATE_SLOT(h, slot);
   int sc[SC_COUNT], fc[F_KINDS], sl[SC_COUNT];
   const bool lane = h->stream_mode && slot == 0;   // alego_stream_run: the per-scan counters of the last scan live in its lane (buffer 0)
   const int cslot = lane ? h->pose_slot : slot;
-  if (lane) HIP_TRY(h, sync_all(h));
+  if (lane) WAIT_ALL(h);
   HIP_TRY(h, hipMemcpyAsync(sc, scal_of(h->d, cslot), sizeof(sc), hipMemcpyDeviceToHost, stream_of(h, slot)));
   HIP_TRY(h, hipMemcpyAsync(sl, scal_of(h->d, slot), sizeof(sl), hipMemcpyDeviceToHost, stream_of(h, slot)));
   HIP_TRY(h, hipStreamSynchronize(stream_of(h, slot)));
@@ -698,11 +734,10 @@ static int download_feat(alego_handle* h, int slot, alego_feat_out* f) {
 }
 
 int alego_ip_process(alego_handle* h, const alego_scan_in* in, alego_seg_out* out) {
-  if (!h || !in || !out) return ALEGO_ERR_ARG;
-  hipSetDevice(h->device);
+  ALEGO_GATE(h);
+  if (!in || !out) return ALEGO_ERR_ARG;
   if (int r = alego_batch_load(h, 0, 0, in->pts, in->n)) return r;
   const DevCtx d = view(h, 0, 1);
-  g_prof = &h->prof;
   launch_ip(d, 0, out->label_image != nullptr, h->stream);
   HIP_TRY(h, hipGetLastError());
   out->stamp = in->stamp;   // /segmented_cloud and /seg_info carry the input's stamp (imageProjection.cpp:318-336)
@@ -710,8 +745,8 @@ int alego_ip_process(alego_handle* h, const alego_scan_in* in, alego_seg_out* ou
 }
 
 int alego_lo_process(alego_handle* h, const alego_seg_out* in, alego_feat_out* feat, alego_pose* odom) {
-  if (!h || !in) return ALEGO_ERR_ARG;
-  hipSetDevice(h->device);
+  ALEGO_GATE(h);
+  if (!in) return ALEGO_ERR_ARG;
   drain_back(h);
   const DevCtx& d = h->d;
   const int slot = 0;   // the single-scan entry points work on slot 0
@@ -737,18 +772,16 @@ int alego_lo_process(alego_handle* h, const alego_seg_out* in, alego_feat_out* f
 
 int alego_lm_process(alego_handle* h, const alego_point* corner_last, int32_t n_corner, const alego_point* surf_last,
                      int32_t n_surf, const alego_point* outlier, int32_t n_outlier, const alego_pose* odom, alego_pose* map_pose) {
-  if (!h || !odom) return ALEGO_ERR_ARG;
-  hipSetDevice(h->device);
+  ALEGO_GATE(h);
+  if (!odom) return ALEGO_ERR_ARG;
   drain_back(h);
-  g_prof = &h->prof;
   return lm_host_process_host(h->lm, h->d, corner_last, n_corner, surf_last, n_surf, outlier, n_outlier, odom, map_pose, &h->err);
 }
 
 int alego_scan_process(alego_handle* h, int slot, const alego_scan_in* in, int stages, alego_seg_out* seg,
                        alego_feat_out* feat, alego_pose* odom, alego_pose* map_pose) {
-  if (int r = check_slot(h, slot)) return r;
+  ALEGO_GATE_SLOT(h, slot);
   if (!in) return ALEGO_ERR_ARG;
-  hipSetDevice(h->device);
   if (int r = alego_batch_load(h, slot, 0, in->pts, in->n)) return r;
   HIP_TRY(h, hipMemcpyAsync(h->d.scan_stamp + slot, &in->stamp, 8, hipMemcpyHostToDevice, stream_of(h, slot)));
   if (h->map_on && lm_host_map_mark_stamped(h->lm, slot, stream_of(h, slot))) { h->err = "alego_scan_process: upload failed"; return ALEGO_ERR_HIP; }
@@ -760,24 +793,21 @@ int alego_scan_process(alego_handle* h, int slot, const alego_scan_in* in, int s
 }
 
 int alego_set_lo_params(alego_handle* h, int slot, const double* p6) {
-  if (int r = check_slot(h, slot)) return r;
-  hipSetDevice(h->device);
+  ALEGO_GATE_SLOT(h, slot);
   HIP_TRY(h, hipMemcpyAsync(lo_state_of(h->d, slot) + LS_PARAMS, p6, 48, hipMemcpyHostToDevice, stream_of(h, slot)));
   HIP_TRY(h, hipStreamSynchronize(stream_of(h, slot)));
   return 0;
 }
 int alego_set_lm_params(alego_handle* h, int slot, const double* p6) {
-  if (int r = check_slot(h, slot)) return r;
-  hipSetDevice(h->device);
+  ALEGO_GATE_SLOT(h, slot);
   return lm_host_set_params(h->lm, slot, p6, &h->err);
 }
 
 // /undistorted (laserOdometry.cpp:56,718-725): the de-skewed segmented cloud of the slot's last scan
 int alego_lo_get_undistorted(alego_handle* h, int slot, alego_point* out, int32_t cap) {
-  if (int r = check_slot(h, slot)) return r;
+  ALEGO_GATE_SLOT(h, slot);
   if (!h->P.deskew_mode) { h->err = "alego_lo_get_undistorted: deskew_mode is 0 (adjustDistortion is not run: laserOdometry.cpp:115)"; return ALEGO_ERR_ARG; }
   if (cap < 0 || (cap > 0 && !out)) return ALEGO_ERR_ARG;
-  hipSetDevice(h->device);
   int M = 0;
   HIP_TRY(h, hipMemcpyAsync(&M, scal_of(h->d, slot) + SC_M_DSK, 4, hipMemcpyDeviceToHost, stream_of(h, slot)));   // lo_deskew's own count, not SC_M
   HIP_TRY(h, hipStreamSynchronize(stream_of(h, slot)));
@@ -831,10 +861,9 @@ int alego_pose_o2b(const alego_pose* o2l, const double* tf_b2l, alego_pose* o2b)
 
 // imuHandler (laserOdometry.cpp:761-802): the per-sample trigonometry here, ring bookkeeping + dead reckoning on the device
 int alego_lo_push_imu(alego_handle* h, int slot, const alego_imu* smp, int32_t n) {
-  if (int r = check_slot(h, slot)) return r;
+  ALEGO_GATE_SLOT(h, slot);
   if (n < 0 || (n > 0 && !smp)) return ALEGO_ERR_ARG;
   if (n == 0) return 0;
-  hipSetDevice(h->device);
   std::vector<double> pre((size_t)n * 7);
   double prev = h->imu_last_stamp[slot];
   for (int i = 0; i < n; ++i) {
@@ -884,18 +913,16 @@ int alego_lo_push_imu(alego_handle* h, int slot, const alego_imu* smp, int32_t n
 }
 
 int alego_profile_enable(alego_handle* h, int on) {
-  if (!h) return ALEGO_ERR_ARG;
-  hipSetDevice(h->device);
-  HIP_TRY(h, sync_all(h));
+  ALEGO_GATE(h);
+  WAIT_ALL(h);
   h->prof.reset();
   h->prof.on = on != 0;
   return 0;
 }
 
 int alego_profile_report(alego_handle* h, char* names, int names_cap, double* total_ms, int* launches, int cap) {
-  if (!h) return ALEGO_ERR_ARG;
-  hipSetDevice(h->device);
-  HIP_TRY(h, sync_all(h));
+  ALEGO_GATE(h);
+  WAIT_ALL(h);
   Profiler& P = h->prof;
   const int nk = (int)P.names.size();
   std::vector<double> tot(nk, 0.0);
@@ -913,9 +940,8 @@ int alego_profile_report(alego_handle* h, char* names, int names_cap, double* to
 }
 
 int alego_debug_voxel(alego_handle* h, const alego_point* pts, int n, float leaf, alego_point* out, int cap) {
-  if (!h || n < 0 || (n > 0 && !pts)) return ALEGO_ERR_ARG;
-  hipSetDevice(h->device);
-  g_prof = &h->prof;
+  ALEGO_GATE(h);
+  if (n < 0 || (n > 0 && !pts)) return ALEGO_ERR_ARG;
   DevPool T;   // temporaries of this call
   float4 *din = nullptr, *dout = nullptr;
   int* cnt = nullptr;
@@ -939,9 +965,9 @@ int alego_debug_voxel(alego_handle* h, const alego_point* pts, int n, float leaf
 }
 
 int alego_debug_math(alego_handle* h, int mode, const float* a, const float* b, float* out, int n) {
-  if (!h || n < 0 || mode < 0 || mode > 3 || (n > 0 && (!a || !out || (mode < 2 && !b)))) return ALEGO_ERR_ARG;
+  ALEGO_GATE(h);
+  if (n < 0 || mode < 0 || mode > 3 || (n > 0 && (!a || !out || (mode < 2 && !b)))) return ALEGO_ERR_ARG;
   if (n == 0) return 0;
-  hipSetDevice(h->device);
   DevPool T;   // temporaries of this call
   float *da, *db, *dout;
   HIP_TRY(h, T.get(&da, (size_t)n, false)); HIP_TRY(h, T.get(&db, (size_t)n, false)); HIP_TRY(h, T.get(&dout, (size_t)n, false));
@@ -953,12 +979,12 @@ int alego_debug_math(alego_handle* h, int mode, const float* a, const float* b, 
   HIP_TRY(h, hipMemcpy(out, dout, (size_t)n * 4, hipMemcpyDeviceToHost));
   return 0;
 }
-int alego_debug_atan2f(alego_handle* h, const float* y, const float* x, float* out, int n) { return alego_debug_math(h, 0, y, x, out, n); }
+int alego_debug_atan2f(alego_handle* h, const float* y, const float* x, float* out, int n) { ALEGO_GATE(h); return alego_debug_math(h, 0, y, x, out, n); }
 
 int alego_debug_std_sort(alego_handle* h, const uint32_t* keys, int n, int depth_limit, int32_t* order) {
-  if (!h || n < 0 || n > 4096 || (n > 0 && (!keys || !order))) return ALEGO_ERR_ARG;
+  ALEGO_GATE(h);
+  if (n < 0 || n > 4096 || (n > 0 && (!keys || !order))) return ALEGO_ERR_ARG;
   if (n == 0) return 0;
-  hipSetDevice(h->device);
   DevPool T;   // temporaries of this call
   uint32_t* dk;
   int* dp;
@@ -976,9 +1002,9 @@ int alego_debug_std_sort(alego_handle* h, const uint32_t* keys, int n, int depth
 }
 
 int alego_debug_eval_blocks(alego_handle* h, int type, int n, const double* geom13, const double* params6, double* res, double* jac6) {
-  if (!h || n < 0 || type < 0 || type > 3 || !params6 || (n > 0 && (!geom13 || !res || !jac6))) return ALEGO_ERR_ARG;
+  ALEGO_GATE(h);
+  if (n < 0 || type < 0 || type > 3 || !params6 || (n > 0 && (!geom13 || !res || !jac6))) return ALEGO_ERR_ARG;
   if (n == 0) return 0;
-  hipSetDevice(h->device);
   DevPool T;   // temporaries of this call
   double *dg, *dp, *dr, *dj;
   HIP_TRY(h, T.get(&dg, (size_t)n * 13, false)); HIP_TRY(h, T.get(&dp, 6, false)); HIP_TRY(h, T.get(&dr, (size_t)n, false)); HIP_TRY(h, T.get(&dj, (size_t)n * 6, false));
@@ -992,9 +1018,9 @@ int alego_debug_eval_blocks(alego_handle* h, int type, int n, const double* geom
 }
 
 int alego_debug_transform_to_start(alego_handle* h, const double* params6, const alego_point* pts, int n, alego_point* out) {
-  if (!h || n < 0 || !params6 || (n > 0 && (!pts || !out))) return ALEGO_ERR_ARG;
+  ALEGO_GATE(h);
+  if (n < 0 || !params6 || (n > 0 && (!pts || !out))) return ALEGO_ERR_ARG;
   if (n == 0) return 0;
-  hipSetDevice(h->device);
   DevPool T;   // temporaries of this call
   double* dp;
   float4 *di, *dout;
@@ -1015,7 +1041,8 @@ int alego_debug_check_guards(char* report, int cap) {
 }
 
 int alego_debug_set_option(alego_handle* h, const char* name, int value) {
-  if (!h || !name) return ALEGO_ERR_ARG;
+  ALEGO_GATE(h);
+  if (!name) return ALEGO_ERR_ARG;
   const std::string s(name);
   DevCtx& d = h->d;
   if (s == "ALEGO_CC_FUSED") d.opt_cc_fused = value != 0;
@@ -1047,7 +1074,7 @@ int alego_debug_set_option(alego_handle* h, const char* name, int value) {
   else if (s == "ALEGO_MAP_MERGE") { if (int r = lm_host_set_map_merge(h->lm, value != 0, &h->err)) return r; d.opt_map_merge = value != 0; }
   else if (s == "ALEGO_IP_FAST") d.ip_fast = h->ip_fast_capable & value;
   else if (s == "ALEGO_POKE_GUARD") { HIP_TRY(h, hipMemset(scal_of(d, d.n_slots) + value, 0xFF, 4)); }   // tests of the guard pages: a write `value` ints past the end of an array
-  else if (s == "ALEGO_GV_SMALL_MAX") { HIP_TRY(h, sync_all(h)); return lm_host_set_gv_small_max(h->lm, value); }   // tools/gmap_timing.py: largest cloud alego_voxel_grid gives to one workgroup
+  else if (s == "ALEGO_GV_SMALL_MAX") { WAIT_ALL(h); return lm_host_set_gv_small_max(h->lm, value); }   // tools/gmap_timing.py: largest cloud alego_voxel_grid gives to one workgroup
   else if (s == "ALEGO_LOC_CHUNK") return lm_host_set_loc_chunk(h->lm, value);   // tests / tools: frames per chunk of alego_loc_enable_from_map / _update_from_map (set on the localising handle)
   else if (s == "ALEGO_PG_BUDGET") graph_ctx_set_budget(&h->pg, value);   // tests / tools: bytes of scratch per chunk of alego_graph_optimize
   else if (s == "ALEGO_LC_BUDGET") loop_ctx_set_budget(&h->lc, value);   // tests / tools: raw sub-map points per chunk of alego_loop_search
@@ -1076,19 +1103,17 @@ int alego_loop_detect(const alego_params* P, const float* keyposes6, const doubl
 }
 int alego_loop_closure_icp(alego_handle* h, const alego_kf_in* latest, const alego_kf_in* history, int32_t n_history, alego_icp_result* out,
                            alego_point* target_out, int32_t target_cap) {
-  if (!h || !latest || !out || n_history < 0 || (n_history > 0 && !history)) return ALEGO_ERR_ARG;
-  hipSetDevice(h->device);
-  g_prof = &h->prof;
+  ALEGO_GATE(h);
+  if (!latest || !out || n_history < 0 || (n_history > 0 && !history)) return ALEGO_ERR_ARG;
   return icp_run(h->P, latest, history, n_history, out, target_out, target_out ? target_cap : 0, h->stream, &h->err);
 }
 
 int alego_loop_search(alego_handle* h, const int32_t* slots, int32_t n, alego_loop_result* out) {
-  if (!h || n < 0 || (n > 0 && (!slots || !out))) return ALEGO_ERR_ARG;
-  if (!h->map_on) { h->err = "alego_loop_search: the key-frame archive is off (alego_map_enable)"; return ALEGO_ERR_ARG; }
-  for (int i = 0; i < n; ++i) if (slots[i] < 0 || slots[i] >= h->d.n_slots) { h->err = "alego_loop_search: slot out of range"; return ALEGO_ERR_ARG; }
-  hipSetDevice(h->device);
-  g_prof = &h->prof;
-  HIP_TRY(h, sync_all(h));   // behind everything already queued on every stream group
+  ALEGO_GATE(h);
+  if (n < 0 || (n > 0 && (!slots || !out))) return ALEGO_ERR_ARG;
+  if (int r = gate_need(h, "alego_loop_search", ARCHIVE)) return r;
+  if (int r = gate_slot_list("alego_loop_search", slots, n, h->d.n_slots, false, &h->err)) return r;
+  WAIT_ALL(h);
   return loop_search(&h->lc, *lm_host_ctx(h->lm), h->P, h->d.n_slots, slots, n, out, h->stream, &h->err);
 }
 // :714-730 on the host: t_correct = correction * initial_guess (Matrix4f), r_correct = Quaternionf(t_correct rotation), pose_from =
@@ -1157,54 +1182,47 @@ int alego_loop_constraint(const float correction[16], const float latest_pose6[6
   return ALEGO_OK;
 }
 int alego_debug_nn1(alego_handle* h, const alego_point* tgt, int32_t n_tgt, const alego_point* queries, int32_t n_q, int32_t* idx, float* d2) {
-  if (!h || n_tgt < 0 || n_q < 0 || (n_tgt > 0 && !tgt) || (n_q > 0 && (!queries || !idx || !d2))) return ALEGO_ERR_ARG;
-  hipSetDevice(h->device);
+  ALEGO_GATE(h);
+  if (n_tgt < 0 || n_q < 0 || (n_tgt > 0 && !tgt) || (n_q > 0 && (!queries || !idx || !d2))) return ALEGO_ERR_ARG;
   return loop_debug_nn1(tgt, n_tgt, queries, n_q, idx, d2, h->stream, &h->err);
 }
 
 // ---- the key-pose graph -----------------------------------------------------------------------------------------------
-static int graph_ready(alego_handle* h, const char* what) {
-  if (!h) return ALEGO_ERR_ARG;
-  if (!h->graph_on) { h->err = std::string(what) + ": the key-pose graph is off (alego_map_enable, then alego_graph_enable)"; return ALEGO_ERR_ARG; }
-  hipSetDevice(h->device);
-  g_prof = &h->prof;
-  return 0;
-}
 int alego_graph_enable(alego_handle* h, int32_t max_loops, const double odom_variance[6]) {
-  if (!h) return ALEGO_ERR_ARG;
-  if (!h->map_on) { h->err = "alego_graph_enable: the key-frame archive is off (alego_map_enable first)"; return ALEGO_ERR_ARG; }
+  ALEGO_GATE(h);
+  if (int r = gate_need(h, "alego_graph_enable", ARCHIVE_FIRST)) return r;
   if (h->graph_on) { h->err = "alego_graph_enable: already enabled"; return ALEGO_ERR_ARG; }
-  hipSetDevice(h->device);
-  HIP_TRY(h, sync_all(h));
+  WAIT_ALL(h);
   if (int r = lm_host_graph_enable(h->lm, max_loops, odom_variance, &h->err)) return r;
   h->graph_on = true;
   return 0;
 }
 int alego_graph_status(alego_handle* h, int slot, int32_t out[4]) {
-  if (int r = graph_ready(h, "alego_graph_status")) return r;
-  if (int r = check_slot(h, slot)) return r;
+  ALEGO_GATE_SLOT(h, slot);
   if (!out) return ALEGO_ERR_ARG;
+  if (int r = gate_need(h, "alego_graph_status", GRAPH)) return r;
   HIP_TRY(h, hipStreamSynchronize(stream_of(h, slot)));
   return graph_status(*lm_host_ctx(h->lm), slot, out, &h->err);
 }
 int alego_graph_get_edges(alego_handle* h, int slot, int kind, int32_t first, int32_t n, alego_graph_edge* out) {
-  if (int r = graph_ready(h, "alego_graph_get_edges")) return r;
-  if (int r = check_slot(h, slot)) return r;
+  ALEGO_GATE_SLOT(h, slot);
+  if (int r = gate_need(h, "alego_graph_get_edges", GRAPH)) return r;
   HIP_TRY(h, hipStreamSynchronize(stream_of(h, slot)));
   return graph_get_edges(*lm_host_ctx(h->lm), slot, kind, first, n, out, &h->err);
 }
 int alego_graph_set_edges(alego_handle* h, int slot, int32_t first, int32_t n, const alego_graph_edge* chain) {
-  if (int r = graph_ready(h, "alego_graph_set_edges")) return r;
-  if (int r = check_slot(h, slot)) return r;
+  ALEGO_GATE_SLOT(h, slot);
+  if (int r = gate_need(h, "alego_graph_set_edges", GRAPH)) return r;
   HIP_TRY(h, hipStreamSynchronize(stream_of(h, slot)));
   return graph_set_edges(*lm_host_ctx(h->lm), slot, first, n, chain, &h->err);
 }
 int alego_graph_add_loops(alego_handle* h, const int32_t* slots, int32_t n, const alego_loop_result* r) {
-  if (int rc = graph_ready(h, "alego_graph_add_loops")) return rc;
+  ALEGO_GATE(h);
   if (n < 0 || (n > 0 && (!slots || !r))) return ALEGO_ERR_ARG;
+  if (int rc = gate_need(h, "alego_graph_add_loops", GRAPH)) return rc;
+  if (int rc = gate_slot_list("alego_graph_add_loops", slots, n, h->d.n_slots, false, &h->err)) return rc;
   std::vector<PgAppend> a;
   for (int i = 0; i < n; ++i) {
-    if (slots[i] < 0 || slots[i] >= h->d.n_slots) { h->err = "alego_graph_add_loops: slot out of range"; return ALEGO_ERR_ARG; }
     if (r[i].status != 2) continue;
     PgAppend p;
     std::memset(&p, 0, sizeof(p));
@@ -1215,33 +1233,29 @@ int alego_graph_add_loops(alego_handle* h, const int32_t* slots, int32_t n, cons
     std::memcpy(p.corr, r[i].correction, sizeof(p.corr));
     a.push_back(p);
   }
-  HIP_TRY(h, sync_all(h));
+  WAIT_ALL(h);
   return graph_append(&h->pg, *lm_host_ctx(h->lm), h->d.n_slots, a, h->stream, &h->err);
 }
 int alego_graph_add_edge(alego_handle* h, int slot, const alego_graph_edge* e, const float correction[16]) {
-  if (int r = graph_ready(h, "alego_graph_add_edge")) return r;
-  if (int r = check_slot(h, slot)) return r;
+  ALEGO_GATE_SLOT(h, slot);
   if (!e) return ALEGO_ERR_ARG;
+  if (int r = gate_need(h, "alego_graph_add_edge", GRAPH)) return r;
   PgAppend p;
   std::memset(&p, 0, sizeof(p));
   p.slot = slot; p.e = *e;
   for (int k = 0; k < 16; ++k) p.corr[k] = correction ? correction[k] : (k % 5 == 0 ? 1.f : 0.f);
-  HIP_TRY(h, sync_all(h));
+  WAIT_ALL(h);
   return graph_append(&h->pg, *lm_host_ctx(h->lm), h->d.n_slots, std::vector<PgAppend>(1, p), h->stream, &h->err);
 }
 int alego_graph_optimize(alego_handle* h, const int32_t* slots, int32_t n, const alego_graph_opts* opts, alego_graph_result* out) {
-  if (int r = graph_ready(h, "alego_graph_optimize")) return r;
+  ALEGO_GATE(h);
   if (n < 0 || (n > 0 && (!slots || !out))) return ALEGO_ERR_ARG;
-  std::vector<char> listed(h->d.n_slots, 0);
-  for (int i = 0; i < n; ++i) {
-    if (slots[i] < 0 || slots[i] >= h->d.n_slots) { h->err = "alego_graph_optimize: slot out of range"; return ALEGO_ERR_ARG; }
-    if (listed[slots[i]]) { h->err = "alego_graph_optimize: a slot is listed twice"; return ALEGO_ERR_ARG; }
-    listed[slots[i]] = 1;
-  }
+  if (int r = gate_need(h, "alego_graph_optimize", GRAPH)) return r;
+  if (int r = gate_slot_list("alego_graph_optimize", slots, n, h->d.n_slots, true, &h->err)) return r;
   alego_graph_opts o = {ALEGO_GRAPH_MAX_ITERS, ALEGO_GRAPH_STEP_TOL, 0};
   if (opts) { if (opts->max_iters > 0) o.max_iters = opts->max_iters; if (opts->step_tol > 0.0) o.step_tol = opts->step_tol; o.apply = opts->apply != 0; }
   if (n == 0) return 0;
-  HIP_TRY(h, sync_all(h));   // behind everything already queued on every stream group
+  WAIT_ALL(h);
   std::vector<int> apply;
   if (int r = graph_optimize(&h->pg, *lm_host_ctx(h->lm), h->d.n_slots, slots, n, o, out, &apply, h->stream, &h->err)) return r;
   int most = 0;
@@ -1252,8 +1266,8 @@ int alego_graph_optimize(alego_handle* h, const int32_t* slots, int32_t n, const
   return lm_host_graph_apply(h->lm, apply, apply_dev, most, &h->err);
 }
 int alego_graph_get_estimate(alego_handle* h, int slot, int32_t first, int32_t n, double* poses12) {
-  if (int r = graph_ready(h, "alego_graph_get_estimate")) return r;
-  if (int r = check_slot(h, slot)) return r;
+  ALEGO_GATE_SLOT(h, slot);
+  if (int r = gate_need(h, "alego_graph_get_estimate", GRAPH)) return r;
   return graph_get_estimate(*lm_host_ctx(h->lm), slot, first, n, poses12, &h->err);
 }
 int alego_graph_residuals(const double* poses12, int32_t n_poses, const alego_graph_edge* edges, int32_t n_edges, double* whitened6, double* jac_from36, double* jac_to36) {
@@ -1263,33 +1277,30 @@ int alego_graph_residuals(const double* poses12, int32_t n_poses, const alego_gr
 }
 // marginal covariances and the loop-edge gate: nothing of a slot changes
 int alego_graph_marginals(alego_handle* h, const int32_t* slots, int32_t n, int32_t cap, double* cov36, alego_graph_cov_result* out) {
-  if (int r = graph_ready(h, "alego_graph_marginals")) return r;
+  ALEGO_GATE(h);
   if (n < 0 || cap <= 0 || (n > 0 && (!slots || !cov36 || !out))) return ALEGO_ERR_ARG;
-  std::vector<char> listed(h->d.n_slots, 0);
-  for (int i = 0; i < n; ++i) {
-    if (slots[i] < 0 || slots[i] >= h->d.n_slots) { h->err = "alego_graph_marginals: slot out of range"; return ALEGO_ERR_ARG; }
-    if (listed[slots[i]]) { h->err = "alego_graph_marginals: a slot is listed twice"; return ALEGO_ERR_ARG; }
-    listed[slots[i]] = 1;
-  }
+  if (int r = gate_need(h, "alego_graph_marginals", GRAPH)) return r;
+  if (int r = gate_slot_list("alego_graph_marginals", slots, n, h->d.n_slots, true, &h->err)) return r;
   if (n == 0) return 0;
-  HIP_TRY(h, sync_all(h));   // behind everything already queued on every stream group
+  WAIT_ALL(h);
   return graph_marginals(&h->pg, *lm_host_ctx(h->lm), h->d.n_slots, slots, n, cap, cov36, out, h->stream, &h->err);
 }
 static int graph_check_common(alego_handle* h, const char* what, const int32_t* slots, int32_t n, const alego_graph_edge* e, const char* active, alego_graph_check* out) {
-  for (int i = 0; i < n; ++i)
-    if (slots[i] < 0 || slots[i] >= h->d.n_slots) { h->err = std::string(what) + ": slot out of range"; return ALEGO_ERR_ARG; }
+  if (int r = gate_slot_list(what, slots, n, h->d.n_slots, false, &h->err)) return r;
   if (n == 0) return 0;
-  HIP_TRY(h, sync_all(h));
+  WAIT_ALL(h);
   return graph_check(&h->pg, *lm_host_ctx(h->lm), h->d.n_slots, slots, n, e, active, out, h->stream, &h->err);
 }
 int alego_graph_check_edges(alego_handle* h, const int32_t* slots, int32_t n, const alego_graph_edge* e, alego_graph_check* out) {
-  if (int r = graph_ready(h, "alego_graph_check_edges")) return r;
+  ALEGO_GATE(h);
   if (n < 0 || (n > 0 && (!slots || !e || !out))) return ALEGO_ERR_ARG;
+  if (int r = gate_need(h, "alego_graph_check_edges", GRAPH)) return r;
   return graph_check_common(h, "alego_graph_check_edges", slots, n, e, nullptr, out);
 }
 int alego_graph_check_loops(alego_handle* h, const int32_t* slots, int32_t n, const alego_loop_result* r, alego_graph_check* out) {
-  if (int rc = graph_ready(h, "alego_graph_check_loops")) return rc;
+  ALEGO_GATE(h);
   if (n < 0 || (n > 0 && (!slots || !r || !out))) return ALEGO_ERR_ARG;
+  if (int rc = gate_need(h, "alego_graph_check_loops", GRAPH)) return rc;
   std::vector<alego_graph_edge> e(std::max(n, 1));
   std::vector<char> active(std::max(n, 1), 0);
   for (int i = 0; i < n; ++i) {
@@ -1313,17 +1324,15 @@ int alego_graph_check_host(const double* poses12, int32_t n_poses, const alego_g
 
 // ---- covariance and degeneracy of the scan-to-map registration --------------------------------
 int alego_regcov_enable(alego_handle* h, const alego_regcov_opts* opts) {
-  if (!h) return ALEGO_ERR_ARG;
+  ALEGO_GATE(h);
   if (!h->lm) { h->err = "alego_regcov_enable: the handle has no LaserMapping"; return ALEGO_ERR_ARG; }
-  hipSetDevice(h->device);
-  HIP_TRY(h, sync_all(h));
+  WAIT_ALL(h);
   return lm_host_regcov_enable(h->lm, opts, &h->err);
 }
 int alego_regcov_get(alego_handle* h, const int32_t* slots, int32_t n, alego_regcov* out) {
-  if (!h) return ALEGO_ERR_ARG;
+  ALEGO_GATE(h);
   if (!h->lm || n < 0 || (n > 0 && (!slots || !out))) { h->err = "alego_regcov_get: null argument / negative count"; return ALEGO_ERR_ARG; }
-  hipSetDevice(h->device);
-  HIP_TRY(h, sync_all(h));   // behind everything already queued on every stream group
+  WAIT_ALL(h);
   return lm_host_regcov_get(h->lm, slots, n, out, &h->err);
 }
 int alego_regcov_host(const double acc28[28], const double params6[6], int32_t n_edge, int32_t n_plane, const alego_regcov_opts* opts, alego_regcov* out) {
@@ -1340,9 +1349,8 @@ int alego_regcov_normal_host(const double params6[6], const double* edge_rows9, 
   return 0;
 }
 int alego_debug_regcov(alego_handle* h, const double params6[6], const double* edge_rows9, int32_t n_edge, const double* plane_rows7, int32_t n_plane, alego_regcov* out) {
-  if (!h) return ALEGO_ERR_ARG;
+  ALEGO_GATE(h);
   if (!params6 || !out || n_edge < 0 || n_plane < 0 || (n_edge > 0 && !edge_rows9) || (n_plane > 0 && !plane_rows7)) { h->err = "alego_debug_regcov: null argument / negative count"; return ALEGO_ERR_ARG; }
-  hipSetDevice(h->device);
   double opt[RC_OPT_W];
   (void)lm_host_regcov_opts(h->lm, opt);
   // block records as lm_fit leaves them (lm_rows.h), the planes' rows from n_edge, and the query points as f32
@@ -1379,37 +1387,28 @@ int alego_debug_regcov(alego_handle* h, const double params6[6], const double* e
 // ---- one registration sharded over the GPUs of a node ---------------------------------------------------------------
 int alego_dist_unique_id(char id[ALEGO_DIST_ID_BYTES]) { return id ? lm_host_dist_unique_id(id) : ALEGO_ERR_ARG; }
 int alego_dist_init(alego_handle* h, int rank, int world, const char id[ALEGO_DIST_ID_BYTES]) {
-  if (!h || !id) return ALEGO_ERR_ARG;
-  if (int r = not_localising(h, "alego_dist_init")) return r;
-  hipSetDevice(h->device);
+  ALEGO_GATE(h);
+  if (!id) return ALEGO_ERR_ARG;
+  if (int r = gate_need(h, "alego_dist_init", MAPPING)) return r;
   drain_back(h);
   return lm_host_dist_init(h->lm, rank, world, id, &h->err);
 }
 int alego_dist_allreduce_probe(alego_handle* h, int iters, double* usec_per_allreduce) {
-  if (!h) return ALEGO_ERR_ARG;
-  hipSetDevice(h->device);
+  ALEGO_GATE(h);
   drain_back(h);
   return lm_host_dist_probe(h->lm, iters, usec_per_allreduce, &h->err);
 }
 int alego_dist_shutdown(alego_handle* h) {
-  if (!h) return ALEGO_ERR_ARG;
-  hipSetDevice(h->device);
+  ALEGO_GATE(h);
   drain_back(h);
   return lm_host_dist_shutdown(h->lm);
 }
 
 // ---- localisation against a frozen key-frame map (kernels_loc.hip) ---------------------------
 int alego_loc_enable(alego_handle* h, const alego_kf_in* frames, int32_t n, double radius) {
-  if (!h) return ALEGO_ERR_ARG;
-  if (h->stream_mode) { h->err = "alego_loc_enable: not available with alego_stream_setup"; return ALEGO_ERR_ARG; }
-  if (h->map_on || h->graph_on) { h->err = "alego_loc_enable: the key-frame archive / key-pose graph belong to a mapping handle"; return ALEGO_ERR_ARG; }
-  bool used = false;
-  for (long v : h->lo_scans) used = used || v != 0;
-  for (long v : h->grp_scans) used = used || v != 0;
-  if (used) { h->err = "alego_loc_enable: call it before the first scan of any slot"; return ALEGO_ERR_ARG; }
-  hipSetDevice(h->device);
-  g_prof = &h->prof;
-  HIP_TRY(h, sync_all(h));
+  ALEGO_GATE(h);
+  if (int r = gate_need(h, "alego_loc_enable", NOT_STREAM_MODE | UNUSED_HANDLE)) return r;
+  WAIT_ALL(h);
   return lm_host_loc_enable(h->lm, h->d, frames, n, radius, &h->err);
 }
 // ... the store built on the device from a slot's archive of a mapping handle of the same process
@@ -1423,28 +1422,19 @@ static int handover_source(alego_handle* h, alego_handle* map, int slot, const c
   return 0;
 }
 int alego_loc_enable_from_map(alego_handle* h, alego_handle* map, int slot, double radius, int32_t capacity) {
-  if (!h) return ALEGO_ERR_ARG;
-  if (h->stream_mode) { h->err = "alego_loc_enable_from_map: not available with alego_stream_setup"; return ALEGO_ERR_ARG; }
-  if (h->map_on || h->graph_on) { h->err = "alego_loc_enable_from_map: the key-frame archive / key-pose graph belong to a mapping handle"; return ALEGO_ERR_ARG; }
-  bool used = false;
-  for (long v : h->lo_scans) used = used || v != 0;
-  for (long v : h->grp_scans) used = used || v != 0;
-  if (used) { h->err = "alego_loc_enable_from_map: call it before the first scan of any slot"; return ALEGO_ERR_ARG; }
+  ALEGO_GATE(h);
+  if (int r = gate_need(h, "alego_loc_enable_from_map", NOT_STREAM_MODE | UNUSED_HANDLE)) return r;
   if (int r = handover_source(h, map, slot, "alego_loc_enable_from_map")) return r;
-  hipSetDevice(h->device);
-  g_prof = &h->prof;
   HIP_TRY(h, sync_all(map));   // a key frame still queued by alego_batch_run(.., sync = 0) is part of the hand-over
-  HIP_TRY(h, sync_all(h));
+  WAIT_ALL(h);
   return lm_host_loc_enable_from_map(h->lm, h->d, map->lm, slot, radius, capacity, &h->err);
 }
 int alego_loc_update_from_map(alego_handle* h, alego_handle* map, int slot) {
-  if (!h) return ALEGO_ERR_ARG;
-  if (!h->lm || !lm_host_localising(h->lm)) { h->err = "alego_loc_update_from_map: the handle does not localise (alego_loc_enable / alego_loc_enable_from_map)"; return ALEGO_ERR_ARG; }
+  ALEGO_GATE(h);
+  if (int r = gate_need(h, "alego_loc_update_from_map", LOCALISING)) return r;
   if (int r = handover_source(h, map, slot, "alego_loc_update_from_map")) return r;
-  hipSetDevice(h->device);
-  g_prof = &h->prof;
   HIP_TRY(h, sync_all(map));
-  HIP_TRY(h, sync_all(h));   // behind the work queued on every stream group, front and back
+  WAIT_ALL(h);   // behind the work queued on every stream group, front and back
   bool rewritten = false;
   const int rc = lm_host_loc_update_from_map(h->lm, map->lm, slot, &rewritten, &h->err);
   if (!rewritten) return rc;   // refused before anything was written
@@ -1456,137 +1446,91 @@ int alego_loc_update_from_map(alego_handle* h, alego_handle* map, int slot) {
 }
 // ---- relocalisation (kernels_reloc.hip) ----
 int alego_reloc_enable(alego_handle* h, double max_range, double z_offset) {
-  if (!h) return ALEGO_ERR_ARG;
-  if (!h->lm || !lm_host_localising(h->lm)) { h->err = "alego_reloc_enable: the handle does not localise (alego_loc_enable)"; return ALEGO_ERR_ARG; }
+  ALEGO_GATE(h);
+  if (int r = gate_need(h, "alego_reloc_enable", LOCALISING_SEED)) return r;
   if (reloc_enabled(h->rl)) { h->err = "alego_reloc_enable: already enabled"; return ALEGO_ERR_ARG; }
-  hipSetDevice(h->device);
-  g_prof = &h->prof;
-  HIP_TRY(h, sync_all(h));
+  WAIT_ALL(h);
   return reloc_enable(&h->rl, *lm_host_ctx(h->lm), h->d.n_slots, max_range, z_offset, h->stream, &h->err);
 }
 int alego_loc_relocalize(alego_handle* h, const int32_t* slots, int32_t n, const alego_reloc_opts* opts, alego_reloc_result* out) {
-  if (!h || n < 0 || (n > 0 && (!slots || !out))) return ALEGO_ERR_ARG;
-  if (!reloc_enabled(h->rl)) { h->err = "alego_loc_relocalize: relocalisation is off (alego_loc_enable, then alego_reloc_enable)"; return ALEGO_ERR_ARG; }
+  ALEGO_GATE(h);
+  if (n < 0 || (n > 0 && (!slots || !out))) return ALEGO_ERR_ARG;
+  if (int r = gate_need(h, "alego_loc_relocalize", RELOCALISATION)) return r;
   int n_cand = 4, verify = 1, apply = 0;
   if (opts) { if (opts->n_cand > 0) n_cand = opts->n_cand; if (opts->verify >= 0) verify = opts->verify; apply = opts->apply != 0; }
   if (n_cand > ALEGO_RELOC_MAX_CAND || verify > n_cand) { h->err = "alego_loc_relocalize: n_cand is 1 .. ALEGO_RELOC_MAX_CAND, verify 0 .. n_cand"; return ALEGO_ERR_ARG; }
-  std::vector<char> seen((size_t)h->d.n_slots, 0);
-  for (int i = 0; i < n; ++i) {
-    if (slots[i] < 0 || slots[i] >= h->d.n_slots) { h->err = "alego_loc_relocalize: slot out of range"; return ALEGO_ERR_ARG; }
-    if (seen[slots[i]]) { h->err = "alego_loc_relocalize: slot " + std::to_string(slots[i]) + " is listed twice"; return ALEGO_ERR_ARG; }
-    seen[slots[i]] = 1;
-  }
-  hipSetDevice(h->device);
-  g_prof = &h->prof;
-  HIP_TRY(h, sync_all(h));   // behind everything already queued on every stream group
+  if (int r = gate_slot_list("alego_loc_relocalize", slots, n, h->d.n_slots, true, &h->err)) return r;
+  WAIT_ALL(h);
   return reloc_run(h->rl, &h->lc, *lm_host_ctx(h->lm), h->P, slots, n, n_cand, verify, apply, out, h->stream, &h->err);
 }
 int alego_debug_reloc_search(alego_handle* h, const uint8_t* map_desc, int32_t n_map, const uint8_t* q_desc, int32_t n_q, int32_t n_cand,
                              int32_t* ids, int32_t* dists, int32_t* shifts) {
-  if (!h || n_map < 0 || n_map > (1 << 24) - 1 || n_q < 0 || n_cand < 1 || n_cand > ALEGO_RELOC_MAX_CAND || (n_map > 0 && !map_desc) || (n_q > 0 && (!q_desc || !ids || !dists || !shifts)))
+  ALEGO_GATE(h);
+  if (n_map < 0 || n_map > (1 << 24) - 1 || n_q < 0 || n_cand < 1 || n_cand > ALEGO_RELOC_MAX_CAND || (n_map > 0 && !map_desc) || (n_q > 0 && (!q_desc || !ids || !dists || !shifts)))
     return ALEGO_ERR_ARG;
-  hipSetDevice(h->device);
-  g_prof = &h->prof;
   return reloc_debug_search(&h->rl, map_desc, n_map, q_desc, n_q, n_cand, ids, dists, shifts, h->stream, &h->err);
 }
 
 // ---- loop closures by appearance (kernels_reloc.hip) ----
 int alego_loop_appearance_enable(alego_handle* h, double max_range, double z_offset) {
-  if (!h) return ALEGO_ERR_ARG;
-  if (int r = not_localising(h, "alego_loop_appearance_enable")) return r;
-  if (!h->map_on) { h->err = "alego_loop_appearance_enable: the key-frame archive is off (alego_map_enable first)"; return ALEGO_ERR_ARG; }
+  ALEGO_GATE(h);
+  if (int r = gate_need(h, "alego_loop_appearance_enable", MAPPING | ARCHIVE_FIRST)) return r;
   if (loop_app_enabled(h->rl)) { h->err = "alego_loop_appearance_enable: already enabled"; return ALEGO_ERR_ARG; }
-  hipSetDevice(h->device);
   return loop_app_enable(&h->rl, *lm_host_ctx(h->lm), h->d.n_slots, max_range, z_offset, &h->err);
 }
 int alego_loop_search_appearance(alego_handle* h, const int32_t* slots, int32_t n, const alego_loop_app_opts* opts, alego_loop_result* out, alego_loop_app_info* info) {
-  if (!h || n < 0 || (n > 0 && (!slots || !out))) return ALEGO_ERR_ARG;
-  if (!loop_app_enabled(h->rl)) { h->err = "alego_loop_search_appearance: the appearance search is off (alego_map_enable, then alego_loop_appearance_enable)"; return ALEGO_ERR_ARG; }
+  ALEGO_GATE(h);
+  if (n < 0 || (n > 0 && (!slots || !out))) return ALEGO_ERR_ARG;
+  if (int r = gate_need(h, "alego_loop_search_appearance", APPEARANCE)) return r;
   alego_loop_app_opts o = {4, 1, 0, 0.0, 0.0};
   if (opts) { if (opts->n_cand > 0) o.n_cand = opts->n_cand; if (opts->verify >= 0) o.verify = opts->verify; o.max_dist = opts->max_dist; o.max_jump = opts->max_jump; o.fitness_max = opts->fitness_max; }
   if (o.n_cand > ALEGO_RELOC_MAX_CAND || o.verify > o.n_cand) { h->err = "alego_loop_search_appearance: n_cand is 1 .. ALEGO_RELOC_MAX_CAND, verify 0 .. n_cand"; return ALEGO_ERR_ARG; }
-  std::vector<char> seen((size_t)h->d.n_slots, 0);
-  for (int i = 0; i < n; ++i) {
-    if (slots[i] < 0 || slots[i] >= h->d.n_slots) { h->err = "alego_loop_search_appearance: slot out of range"; return ALEGO_ERR_ARG; }
-    if (seen[slots[i]]) { h->err = "alego_loop_search_appearance: slot " + std::to_string(slots[i]) + " is listed twice"; return ALEGO_ERR_ARG; }
-    seen[slots[i]] = 1;
-  }
-  hipSetDevice(h->device);
-  g_prof = &h->prof;
-  HIP_TRY(h, sync_all(h));   // behind everything already queued on every stream group
+  if (int r = gate_slot_list("alego_loop_search_appearance", slots, n, h->d.n_slots, true, &h->err)) return r;
+  WAIT_ALL(h);
   return loop_app_run(h->rl, &h->lc, *lm_host_ctx(h->lm), h->P, slots, n, o, out, info, h->stream, &h->err);
 }
 
 // ---- aligning one slot's archive to another's (kernels_reloc.hip) ----
 int alego_map_align(alego_handle* h, const int32_t* src_slots, const int32_t* dst_slots, int32_t n, const alego_map_align_opts* opts, alego_map_align_result* out,
                     alego_map_align_hyp* hyp) {
-  if (!h || n < 0 || (n > 0 && (!src_slots || !dst_slots || !out))) return ALEGO_ERR_ARG;
-  if (int r = not_localising(h, "alego_map_align")) return r;
-  if (!loop_app_enabled(h->rl)) { h->err = "alego_map_align: the appearance search is off (alego_map_enable, then alego_loop_appearance_enable)"; return ALEGO_ERR_ARG; }
+  ALEGO_GATE(h);
+  if (n < 0 || (n > 0 && (!src_slots || !dst_slots || !out))) return ALEGO_ERR_ARG;
+  if (int r = gate_need(h, "alego_map_align", MAPPING | APPEARANCE)) return r;
   alego_map_align_opts o;
   std::memset(&o, 0, sizeof(o));
   if (opts) o = *opts;
   if (o.n_queries <= 0) o.n_queries = 8;
   if (o.n_cand <= 0) o.n_cand = 2;
   if (o.n_queries > ALEGO_ALIGN_MAX_QUERIES || o.n_cand > ALEGO_RELOC_MAX_CAND) { h->err = "alego_map_align: n_queries is 1 .. ALEGO_ALIGN_MAX_QUERIES, n_cand 1 .. ALEGO_RELOC_MAX_CAND"; return ALEGO_ERR_ARG; }
-  std::set<std::pair<int, int>> seen;
-  for (int i = 0; i < n; ++i) {
-    const int a = src_slots[i], b = dst_slots[i];
-    if (a < 0 || a >= h->d.n_slots || b < 0 || b >= h->d.n_slots) { h->err = "alego_map_align: slot out of range"; return ALEGO_ERR_ARG; }
-    if (a == b) { h->err = "alego_map_align: slot " + std::to_string(a) + " is paired with itself"; return ALEGO_ERR_ARG; }
-    if (!seen.insert({a, b}).second) { h->err = "alego_map_align: the pair (" + std::to_string(a) + ", " + std::to_string(b) + ") is listed twice"; return ALEGO_ERR_ARG; }
-  }
-  hipSetDevice(h->device);
-  g_prof = &h->prof;
-  HIP_TRY(h, sync_all(h));   // behind everything already queued on every stream group
+  if (int r = gate_pair_list("alego_map_align", src_slots, dst_slots, n, h->d.n_slots, GATE_PAIRS_ALIGN, &h->err)) return r;
+  WAIT_ALL(h);
   return map_align_run(h->rl, &h->lc, *lm_host_ctx(h->lm), h->P, src_slots, dst_slots, n, o, out, hyp, h->stream, &h->err);
 }
 
 // ---- a slot moved, one archive appended to another's (kernels_merge.hip) ----
-static int merge_ready(alego_handle* h, const char* what) {
-  if (int r = not_localising(h, what)) return r;
-  if (!h->map_on) { h->err = std::string(what) + ": the key-frame archive is off (alego_map_enable)"; return ALEGO_ERR_ARG; }
-  hipSetDevice(h->device);
-  g_prof = &h->prof;
-  return 0;
-}
 int alego_map_move(alego_handle* h, const int32_t* slots, int32_t n, const double* T12, int32_t* out_status) {
-  if (!h || n < 0 || (n > 0 && (!slots || !T12 || !out_status))) return ALEGO_ERR_ARG;
-  if (int r = merge_ready(h, "alego_map_move")) return r;
-  std::vector<char> seen((size_t)h->d.n_slots, 0);
-  for (int i = 0; i < n; ++i) {
-    if (slots[i] < 0 || slots[i] >= h->d.n_slots) { h->err = "alego_map_move: slot out of range"; return ALEGO_ERR_ARG; }
-    if (seen[slots[i]]) { h->err = "alego_map_move: slot " + std::to_string(slots[i]) + " is listed twice"; return ALEGO_ERR_ARG; }
-    seen[slots[i]] = 1;
-    if (!mg_finite12(T12 + (size_t)i * 12)) { h->err = "alego_map_move: a transform is not finite"; return ALEGO_ERR_ARG; }
-  }
+  ALEGO_GATE(h);
+  if (n < 0 || (n > 0 && (!slots || !T12 || !out_status))) return ALEGO_ERR_ARG;
+  if (int r = gate_need(h, "alego_map_move", MAPPING | ARCHIVE)) return r;
+  for (int i = 0; i < n; ++i) if (!mg_finite12(T12 + (size_t)i * 12)) { h->err = "alego_map_move: a transform is not finite"; return ALEGO_ERR_ARG; }
+  if (int r = gate_slot_list("alego_map_move", slots, n, h->d.n_slots, true, &h->err)) return r;
   if (n == 0) return 0;
-  HIP_TRY(h, sync_all(h));   // behind everything already queued on every stream group
+  WAIT_ALL(h);
   return lm_host_map_move(h->lm, slots, n, T12, out_status, &h->err);
 }
 int alego_map_merge(alego_handle* h, const int32_t* src_slots, const int32_t* dst_slots, int32_t n, const double* T12, const alego_map_merge_opts* opts,
                     const alego_map_align_hyp* hyp, alego_map_merge_result* out) {
-  if (!h || n < 0 || (n > 0 && (!src_slots || !dst_slots || !T12 || !out))) return ALEGO_ERR_ARG;
-  if (int r = merge_ready(h, "alego_map_merge")) return r;
+  ALEGO_GATE(h);
+  if (n < 0 || (n > 0 && (!src_slots || !dst_slots || !T12 || !out))) return ALEGO_ERR_ARG;
+  if (int r = gate_need(h, "alego_map_merge", MAPPING | ARCHIVE)) return r;
   const double off = opts ? opts->stamp_offset : 0.0;
   const double* sv = opts ? opts->seam_variance : nullptr;
   if (!(off - off == 0.0)) { h->err = "alego_map_merge: stamp_offset is not finite"; return ALEGO_ERR_ARG; }
   for (int k = 0; sv && k < 6; ++k) if (!(sv[k] > 0.0) || !(sv[k] - sv[k] == 0.0)) { h->err = "alego_map_merge: seam_variance must be positive and finite"; return ALEGO_ERR_ARG; }
-  std::vector<char> role((size_t)h->d.n_slots, 0);   // 1: a source, 2: a destination
-  for (int i = 0; i < n; ++i) {
-    const int a = src_slots[i], b = dst_slots[i];
-    if (a < 0 || a >= h->d.n_slots || b < 0 || b >= h->d.n_slots) { h->err = "alego_map_merge: slot out of range"; return ALEGO_ERR_ARG; }
-    if (a == b) { h->err = "alego_map_merge: slot " + std::to_string(a) + " is paired with itself"; return ALEGO_ERR_ARG; }
-    if (!mg_finite12(T12 + (size_t)i * 12)) { h->err = "alego_map_merge: a transform is not finite"; return ALEGO_ERR_ARG; }
-  }
-  for (int i = 0; i < n; ++i) {
-    if (role[dst_slots[i]] == 2) { h->err = "alego_map_merge: slot " + std::to_string(dst_slots[i]) + " is a destination twice"; return ALEGO_ERR_ARG; }
-    role[dst_slots[i]] = 2;
-  }
-  for (int i = 0; i < n; ++i)
-    if (role[src_slots[i]] == 2) { h->err = "alego_map_merge: slot " + std::to_string(src_slots[i]) + " is a destination of one pair and a source of another"; return ALEGO_ERR_ARG; }
+  for (int i = 0; i < n; ++i) if (!mg_finite12(T12 + (size_t)i * 12)) { h->err = "alego_map_merge: a transform is not finite"; return ALEGO_ERR_ARG; }
+  if (int r = gate_pair_list("alego_map_merge", src_slots, dst_slots, n, h->d.n_slots, GATE_PAIRS_MERGE, &h->err)) return r;
   if (n == 0) return 0;
-  HIP_TRY(h, sync_all(h));   // behind everything already queued on every stream group
+  WAIT_ALL(h);
   return lm_host_map_merge(h->lm, &h->pg, src_slots, dst_slots, n, T12, off, sv, hyp, out, &h->err);
 }
 int alego_map_align_edge(const alego_map_align_hyp* hyp, const float dst_pose6[6], int32_t nd, alego_graph_edge* edge) {
@@ -1610,18 +1554,14 @@ int alego_map_merge_edges(const alego_graph_edge* src_chain, int32_t ns, const a
 
 // ---- a slot's archive thinned in place (kernels_thin.hip) ----
 int alego_map_thin(alego_handle* h, const int32_t* slots, int32_t n, const alego_map_thin_opts* opts, alego_map_thin_result* out) {
-  if (!h || n < 0 || (n > 0 && (!slots || !out))) return ALEGO_ERR_ARG;
-  if (int r = merge_ready(h, "alego_map_thin")) return r;
+  ALEGO_GATE(h);
+  if (n < 0 || (n > 0 && (!slots || !out))) return ALEGO_ERR_ARG;
+  if (int r = gate_need(h, "alego_map_thin", MAPPING | ARCHIVE)) return r;
   const double md = opts ? opts->min_dist : 0.0;
   if (!(md - md == 0.0)) { h->err = "alego_map_thin: min_dist is not finite"; return ALEGO_ERR_ARG; }
-  std::vector<char> seen((size_t)h->d.n_slots, 0);
-  for (int i = 0; i < n; ++i) {
-    if (slots[i] < 0 || slots[i] >= h->d.n_slots) { h->err = "alego_map_thin: slot out of range"; return ALEGO_ERR_ARG; }
-    if (seen[slots[i]]) { h->err = "alego_map_thin: slot " + std::to_string(slots[i]) + " is listed twice"; return ALEGO_ERR_ARG; }
-    seen[slots[i]] = 1;
-  }
+  if (int r = gate_slot_list("alego_map_thin", slots, n, h->d.n_slots, true, &h->err)) return r;
   if (n == 0) return 0;
-  HIP_TRY(h, sync_all(h));   // behind everything already queued on every stream group
+  WAIT_ALL(h);
   std::vector<int> first((size_t)n, 0);
   const int rc = lm_host_map_thin(h->lm, slots, n, md, out, first.data(), &h->err);
   // the descriptors depend on the clouds only: a thinned slot keeps those below its first dropped frame (also after a failure half way)
@@ -1651,130 +1591,107 @@ int alego_map_thin_edges(const alego_graph_edge* chain, int32_t n, const alego_g
   return m;
 }
 int alego_debug_thin_select(alego_handle* h, const float* keyposes6, const uint8_t* protect, int32_t n, double min_dist, uint8_t* keep) {
-  if (!h || n < 0 || (n > 0 && (!keyposes6 || !protect || !keep)) || !(min_dist - min_dist == 0.0)) return ALEGO_ERR_ARG;
-  hipSetDevice(h->device);
-  g_prof = &h->prof;
-  HIP_TRY(h, sync_all(h));
+  ALEGO_GATE(h);
+  if (n < 0 || (n > 0 && (!keyposes6 || !protect || !keep)) || !(min_dist - min_dist == 0.0)) return ALEGO_ERR_ARG;
+  WAIT_ALL(h);
   return lm_host_debug_thin_select(h->lm, keyposes6, protect, n, min_dist, keep, &h->err);
 }
 
 int alego_loc_status(alego_handle* h, int slot, int32_t out[4]) {
-  if (int r = check_slot(h, slot)) return r;
+  ALEGO_GATE_SLOT(h, slot);
   if (!out) return ALEGO_ERR_ARG;
-  hipSetDevice(h->device);
   return lm_host_loc_status(h->lm, slot, out, &h->err);
 }
 
 // ---- key-frame pass-through ---------------------------------------------------------------------------------------
 int alego_lm_keyframe_count(alego_handle* h, int slot) {
-  if (int r = check_slot(h, slot)) return r;
-  hipSetDevice(h->device);
+  ALEGO_GATE_SLOT(h, slot);
   return lm_host_keyframe_count(h->lm, slot);
 }
 int alego_lm_get_keyframe(alego_handle* h, int slot, int kf_id, alego_keyframe* out) {
-  if (int r = check_slot(h, slot)) return r;
+  ALEGO_GATE_SLOT(h, slot);
   if (!out) return ALEGO_ERR_ARG;
-  if (int r = not_localising(h, "alego_lm_get_keyframe")) return r;
-  hipSetDevice(h->device);
+  if (int r = gate_need(h, "alego_lm_get_keyframe", MAPPING)) return r;
   return lm_host_get_keyframe(h->lm, slot, kf_id, out, &h->err);
 }
 int alego_lm_set_keypose(alego_handle* h, int slot, int kf_id, const float pose6[6]) {
-  if (int r = check_slot(h, slot)) return r;
+  ALEGO_GATE_SLOT(h, slot);
   if (!pose6) return ALEGO_ERR_ARG;
-  if (int r = not_localising(h, "alego_lm_set_keypose")) return r;
-  hipSetDevice(h->device);
-  g_prof = &h->prof;
+  if (int r = gate_need(h, "alego_lm_set_keypose", MAPPING)) return r;
   return lm_host_set_keypose(h->lm, h->d, slot, kf_id, pose6, &h->err);
 }
 int alego_lm_reset_window(alego_handle* h, int slot) {
-  if (int r = check_slot(h, slot)) return r;
-  if (int r = not_localising(h, "alego_lm_reset_window")) return r;
-  hipSetDevice(h->device);
+  ALEGO_GATE_SLOT(h, slot);
+  if (int r = gate_need(h, "alego_lm_reset_window", MAPPING)) return r;
   return lm_host_reset_window(h->lm, slot, &h->err);
 }
 int alego_lm_apply_correction(alego_handle* h, int slot, const double rc[12]) {
-  if (int r = check_slot(h, slot)) return r;
+  ALEGO_GATE_SLOT(h, slot);
   if (!rc) return ALEGO_ERR_ARG;
-  hipSetDevice(h->device);
-  g_prof = &h->prof;
   return lm_host_apply_correction(h->lm, h->d, slot, rc, &h->err);
 }
 int alego_lm_add_keyframe(alego_handle* h, int slot, const float pose6[6], const alego_point* corner, int32_t n_corner,
                           const alego_point* surf, int32_t n_surf, const alego_point* outlier, int32_t n_outlier) {
-  if (int r = check_slot(h, slot)) return r;
+  ALEGO_GATE_SLOT(h, slot);
   if (!pose6) return ALEGO_ERR_ARG;
-  if (int r = not_localising(h, "alego_lm_add_keyframe")) return r;
-  hipSetDevice(h->device);
-  g_prof = &h->prof;
+  if (int r = gate_need(h, "alego_lm_add_keyframe", MAPPING)) return r;
   return lm_host_add_keyframe(h->lm, h->d, slot, pose6, corner, n_corner, surf, n_surf, outlier, n_outlier, &h->err);
 }
 
 // ---- the global map -------------------------------------------------------------------------------------------------
 int alego_map_enable(alego_handle* h, int32_t max_keyframes, int32_t max_points) {
-  if (!h || max_keyframes <= 0 || max_points <= 0) return ALEGO_ERR_ARG;
-  if (h->stream_mode) { h->err = "alego_map_enable: not available with alego_stream_setup"; return ALEGO_ERR_ARG; }
-  if (int r = not_localising(h, "alego_map_enable")) return r;
+  ALEGO_GATE(h);
+  if (max_keyframes <= 0 || max_points <= 0) return ALEGO_ERR_ARG;
+  if (int r = gate_need(h, "alego_map_enable", NOT_STREAM_MODE | MAPPING)) return r;
   if (h->map_on) { h->err = "alego_map_enable: already enabled"; return ALEGO_ERR_ARG; }
-  hipSetDevice(h->device);
-  HIP_TRY(h, sync_all(h));
+  WAIT_ALL(h);
   if (int r = lm_host_map_enable(h->lm, max_keyframes, max_points, &h->err)) return r;
   h->map_on = true;
   return 0;
 }
 int alego_map_status(alego_handle* h, int slot, int32_t out[4]) {
-  if (int r = check_slot(h, slot)) return r;
+  ALEGO_GATE_SLOT(h, slot);
   if (!out) return ALEGO_ERR_ARG;
-  hipSetDevice(h->device);
   return lm_host_map_status(h->lm, slot, out, &h->err);
 }
 int alego_map_set_keyposes(alego_handle* h, int slot, int32_t first, int32_t n, const float* poses6) {
-  if (int r = check_slot(h, slot)) return r;
-  hipSetDevice(h->device);
+  ALEGO_GATE_SLOT(h, slot);
   return lm_host_map_set_keyposes(h->lm, slot, first, n, poses6, &h->err);
 }
 int alego_map_get_keyframe(alego_handle* h, int slot, int32_t id, alego_keyframe* out) {
-  if (int r = check_slot(h, slot)) return r;
+  ALEGO_GATE_SLOT(h, slot);
   if (!out) return ALEGO_ERR_ARG;
-  hipSetDevice(h->device);
   return lm_host_map_get_keyframe(h->lm, slot, id, out, &h->err);
 }
 int alego_map_assemble(alego_handle* h, int slot, int kinds, float leaf, alego_point* out, int32_t cap) {
-  if (int r = check_slot(h, slot)) return r;
-  hipSetDevice(h->device);
-  g_prof = &h->prof;
+  ALEGO_GATE_SLOT(h, slot);
   return lm_host_map_assemble(h->lm, slot, kinds, leaf, out, cap, &h->err);
 }
 int alego_map_get_stamps(alego_handle* h, int slot, int32_t first, int32_t n, double* out) {
-  if (int r = check_slot(h, slot)) return r;
-  hipSetDevice(h->device);
+  ALEGO_GATE_SLOT(h, slot);
   return lm_host_map_stamps(h->lm, slot, first, n, out, 0, &h->err);
 }
 int alego_map_set_stamps(alego_handle* h, int slot, int32_t first, int32_t n, const double* stamps) {
-  if (int r = check_slot(h, slot)) return r;
-  hipSetDevice(h->device);
+  ALEGO_GATE_SLOT(h, slot);
   return lm_host_map_stamps(h->lm, slot, first, n, const_cast<double*>(stamps), 1, &h->err);
 }
 int alego_map_keyposes(alego_handle* h, int slot, alego_point* out, int32_t cap) {
-  if (int r = check_slot(h, slot)) return r;
-  hipSetDevice(h->device);
+  ALEGO_GATE_SLOT(h, slot);
   return lm_host_map_keyposes(h->lm, slot, out, cap, &h->err);
 }
 int alego_lm_get_local_map(alego_handle* h, int slot, alego_point* corner, int32_t corner_cap, alego_point* surf, int32_t surf_cap, int32_t n_out[2]) {
-  if (int r = check_slot(h, slot)) return r;
+  ALEGO_GATE_SLOT(h, slot);
   if (!n_out || corner_cap < 0 || surf_cap < 0) return ALEGO_ERR_ARG;
-  hipSetDevice(h->device);
   return lm_host_get_local_map(h->lm, slot, corner, corner_cap, surf, surf_cap, n_out, &h->err);
 }
 int alego_voxel_grid(alego_handle* h, const alego_point* pts, int32_t n, float leaf, alego_point* out, int32_t cap) {
-  if (!h || n < 0 || cap < 0 || (n > 0 && !pts) || !(leaf > 0.f)) return ALEGO_ERR_ARG;
-  hipSetDevice(h->device);
-  g_prof = &h->prof;
+  ALEGO_GATE(h);
+  if (n < 0 || cap < 0 || (n > 0 && !pts) || !(leaf > 0.f)) return ALEGO_ERR_ARG;
   return lm_host_voxel_grid(h->lm, h->stream, pts, n, leaf, out, cap, &h->err);
 }
 
 int alego_debug_get(alego_handle* h, int slot, const char* name, void* out, int cap_bytes, int* count, int* dtype) {
-  if (int r = check_slot(h, slot)) return r;
-  hipSetDevice(h->device);
+  ALEGO_GATE_SLOT(h, slot);
   const DevCtx& d = h->d;
   int sc[SC_COUNT];
   HIP_TRY(h, hipMemcpyAsync(sc, scal_of(d, slot), sizeof(sc), hipMemcpyDeviceToHost, stream_of(h, slot)));

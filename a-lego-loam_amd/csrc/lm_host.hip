@@ -1,5 +1,6 @@
 // lm_host.hip — LaserMapping: HBM allocation and kernel sequencing (no numerics here).
 #include "lm_host.h"
+#include "api_gate.h"
 #include "dev_mem.h"
 
 #include <cstddef>
@@ -688,9 +689,9 @@ static int rings_empty(LmHost* lm, const char* what, bool scans_too, std::string
 }
 
 // ---- the global map (alego_map_* / alego_lm_get_local_map / alego_voxel_grid) ----
+// (once per handle: the API owns that flag and refuses a second call, as it does for lm_host_graph_enable)
 int lm_host_map_enable(LmHost* lm, int max_frames, int max_points, std::string* err) {
   LmCtx& L = lm->L;
-  if (L.arc_frames_cap > 0) { *err = "map_enable: already enabled"; return ALEGO_ERR_ARG; }
   if (max_frames <= 0 || max_points <= 0) { *err = "map_enable: capacities must be positive"; return ALEGO_ERR_ARG; }
   if (int r = rings_empty(lm, "map_enable", false, err)) return r;   // the archive holds frame ids 0, 1, ...: it has to exist before the first key frame
   const size_t B = lm->n_slots;
@@ -976,8 +977,6 @@ bool lm_host_localising(LmHost* lm) { return lm->L.loc_on != 0; }
 // ---- the key-pose graph (alego_graph_*) ----
 int lm_host_graph_enable(LmHost* lm, int max_loops, const double* odom_var6, std::string* err) {
   LmCtx& L = lm->L;
-  if (L.arc_frames_cap <= 0) { *err = "graph_enable: the key-frame archive is off (alego_map_enable first)"; return ALEGO_ERR_ARG; }
-  if (L.pg_loops_cap > 0) { *err = "graph_enable: already enabled"; return ALEGO_ERR_ARG; }
   if (max_loops < 1 || max_loops > ALEGO_GRAPH_MAX_LOOPS) { *err = "graph_enable: max_loops out of range"; return ALEGO_ERR_ARG; }
   static const double dflt[6] = {1e-6, 1e-6, 1e-6, 1e-8, 1e-8, 1e-6};   // laserMapping.cpp:68-70
   const double* v = odom_var6 ? odom_var6 : dflt;
@@ -1027,15 +1026,9 @@ int lm_host_regcov_enable(LmHost* lm, const alego_regcov_opts* opts, std::string
 // one copy: the records of slots [lo, hi] of the list, picked apart on the host
 int lm_host_regcov_get(LmHost* lm, const int* slots, int n, alego_regcov* out, std::string* err) {
   if (!lm->rc_on) { *err = "alego_regcov_get: the feature is off (alego_regcov_enable)"; return ALEGO_ERR_ARG; }
-  std::vector<char> listed(lm->n_slots, 0);
-  int lo = lm->n_slots, hi = -1;
-  for (int i = 0; i < n; ++i) {
-    if (slots[i] < 0 || slots[i] >= lm->n_slots) { *err = "alego_regcov_get: slot out of range"; return ALEGO_ERR_ARG; }
-    if (listed[slots[i]]) { *err = "alego_regcov_get: a slot is listed twice"; return ALEGO_ERR_ARG; }
-    listed[slots[i]] = 1;
-    lo = std::min(lo, slots[i]); hi = std::max(hi, slots[i]);
-  }
+  if (int r = gate_slot_list("alego_regcov_get", slots, n, lm->n_slots, true, err)) return r;
   if (n == 0) return 0;
+  const int lo = *std::min_element(slots, slots + n), hi = *std::max_element(slots, slots + n);
   for (hipStream_t s : lm->st) if (hipStreamSynchronize(s) != hipSuccess) { *err = "alego_regcov_get: a stream failed"; return ALEGO_ERR_HIP; }
   std::vector<alego_regcov> tmp((size_t)(hi - lo + 1));
   if (hipMemcpy(tmp.data(), lm->L.rc_rec + lo, tmp.size() * sizeof(alego_regcov), hipMemcpyDeviceToHost) != hipSuccess) { *err = "alego_regcov_get: device read failed"; return ALEGO_ERR_HIP; }

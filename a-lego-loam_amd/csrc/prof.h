@@ -33,7 +33,7 @@ struct Profiler {
   ~Profiler() { for (auto e : pool) (void)hipEventDestroy(e); }
 };
 
-extern thread_local Profiler* g_prof;  // set by the API while it enqueues work for a handle
+extern thread_local Profiler* g_prof;  // the profiler of the handle whose entry point this thread is in (the gate of alego_api.hip); null between calls
 
 struct ProfScope {
   hipStream_t st; bool on;
