@@ -42,6 +42,7 @@ EXPORTS = [
     "alego_map_move", "alego_map_merge", "alego_map_align_edge", "alego_map_merge_edges",
     "alego_map_thin", "alego_map_thin_select", "alego_map_thin_edges", "alego_debug_thin_select",
     "alego_regcov_enable", "alego_regcov_get", "alego_regcov_host", "alego_regcov_normal_host", "alego_debug_regcov",
+    "alego_remap_enable", "alego_remap_get", "alego_remap_host", "alego_remap_step_host", "alego_debug_remap_solve",
 ]
 
 REPLAY_PINGPONG = 0x100
@@ -249,6 +250,48 @@ def regcov_normal_host(params6, edge_rows9, plane_rows7, huber):
     if rc != 0:
         raise AlegoError(f"alego_regcov_normal_host failed ({rc})")
     return acc
+
+
+class RemapOpts(C.Structure):
+    _fields_ = [("eig_min", C.c_double)]
+
+
+class Remap(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_held", C.c_int32), ("frame", C.c_int32), ("pad", C.c_int32),
+                ("start", C.c_double * 6), ("eigval", C.c_double * 6), ("eigvec", C.c_double * 36), ("proj", C.c_double * 36)]
+
+
+def remap_opts(eig_min=0.0):
+    """alego_remap_opts; 0 takes the library's default (100)"""
+    o = RemapOpts()
+    o.eig_min = float(eig_min)
+    return o
+
+
+def _remap_out(r):
+    return dict(status=int(r.status), n_held=int(r.n_held), frame=int(r.frame), start=np.array(r.start[:], np.float64), eigval=np.array(r.eigval[:], np.float64),
+                eigvec=np.array(r.eigvec[:], np.float64).reshape(6, 6), proj=np.array(r.proj[:], np.float64).reshape(6, 6))
+
+
+def remap_host(acc28, params6, n_edge, n_plane, opts=None):
+    """alego_remap_host (host only): the projector of 28 normal-equation scalars at params6 as a dict"""
+    a, p = np.ascontiguousarray(acc28, np.float64).reshape(28), np.ascontiguousarray(params6, np.float64).reshape(6)
+    out = Remap()
+    rc = lib().alego_remap_host(a.ctypes.data, p.ctypes.data, int(n_edge), int(n_plane), None if opts is None else C.byref(opts), C.byref(out))
+    if rc != 0:
+        raise AlegoError(f"alego_remap_host failed ({rc})")
+    return _remap_out(out)
+
+
+def remap_step_host(H21, g6, scale6, radius, proj36=None):
+    """alego_remap_step_host (host only): one lm_step at x = 0 -> (valid, step in parameter space (6,), model cost change)"""
+    H, g, sc = (np.ascontiguousarray(v, np.float64).reshape(n) for v, n in ((H21, 21), (g6, 6), (scale6, 6)))
+    P = None if proj36 is None else np.ascontiguousarray(proj36, np.float64).reshape(36)
+    step, mcc = np.zeros(6), C.c_double(0.0)
+    rc = lib().alego_remap_step_host(H.ctypes.data, g.ctypes.data, sc.ctypes.data, float(radius), None if P is None else P.ctypes.data, step.ctypes.data, C.byref(mcc))
+    if rc < 0:
+        raise AlegoError(f"alego_remap_step_host failed ({rc})")
+    return bool(rc), step, mcc.value
 
 
 def _graph_checks_out(out, n):
@@ -490,6 +533,11 @@ def lib():
         L.alego_regcov_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(RegCovOpts), C.POINTER(RegCov)]
         L.alego_regcov_normal_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_void_p]
         L.alego_debug_regcov.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(RegCov)]
+        L.alego_remap_enable.argtypes = [C.c_void_p, C.POINTER(RemapOpts)]
+        L.alego_remap_get.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Remap)]
+        L.alego_remap_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(RemapOpts), C.POINTER(Remap)]
+        L.alego_remap_step_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
+        L.alego_debug_remap_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Remap)]
         L.alego_loc_select.restype = C.c_int
         L.alego_loc_select.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_int32, C.c_void_p]
         L.alego_loc_enable.argtypes = [C.c_void_p, C.POINTER(KfIn), C.c_int32, C.c_double]
@@ -1448,6 +1496,27 @@ class Handle:
         out = (RegCov * max(n, 1))()
         self._check(lib().alego_regcov_get(self._h, sl.ctypes.data, n, out), "alego_regcov_get")
         return [_regcov_out(r) for r in out[:n]]
+
+    def remap_enable(self, opts=None):
+        """alego_remap_enable: opts = remap_opts(eig_min) or None for the default; before the first scan reaches LaserMapping"""
+        self._check(lib().alego_remap_enable(self._h, None if opts is None else C.byref(opts)), "alego_remap_enable")
+
+    def remap_get(self, slots=(0,)):
+        """alego_remap_get: one dict per listed slot (status, n_held, frame, start, eigval, eigvec, proj)"""
+        sl, n = _slot_list(slots)
+        out = (Remap * max(n, 1))()
+        self._check(lib().alego_remap_get(self._h, sl.ctypes.data, n, out), "alego_remap_get")
+        return [_remap_out(r) for r in out[:n]]
+
+    def debug_remap_solve(self, start6, edge_rows9, plane_rows7, remap=1):
+        """alego_debug_remap_solve: the solver kernel alone (remap = 0: lm_solve, 1: lm_solve_remap) on rows (a, b, p) (n, 9) and (n, d, p) (m, 7) from
+        start6 -> dict(params_it (2, 6), costs (4,), iterations, successful, termination (2,) each, rec)"""
+        p = np.ascontiguousarray(start6, np.float64).reshape(6)
+        e, s = np.ascontiguousarray(edge_rows9, np.float64).reshape(-1, 9), np.ascontiguousarray(plane_rows7, np.float64).reshape(-1, 7)
+        pit, costs, summ, rec = np.zeros((2, 6)), np.zeros(4), np.zeros(2, np.int32), Remap()
+        self._check(lib().alego_debug_remap_solve(self._h, p.ctypes.data, e.ctypes.data if len(e) else None, len(e), s.ctypes.data if len(s) else None, len(s), int(remap),
+                                                  pit.ctypes.data, costs.ctypes.data, summ.ctypes.data, C.byref(rec)), "alego_debug_remap_solve")
+        return dict(params_it=pit, costs=costs, iterations=summ & 0xFF, successful=(summ >> 8) & 0xFF, termination=summ >> 16, rec=_remap_out(rec))
 
     def debug_regcov(self, params6, edge_rows9, plane_rows7):
         """alego_debug_regcov: lm_regcov alone on rows (a, b, p) (n, 9) and (n, d, p) (m, 7) at params6 (p is rounded to f32)"""

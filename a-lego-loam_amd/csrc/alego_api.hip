@@ -1384,6 +1384,85 @@ int alego_debug_regcov(alego_handle* h, const double params6[6], const double* e
   return 0;
 }
 
+// ---- solution remapping of the scan-to-map registration ----------------------------------------
+int alego_remap_enable(alego_handle* h, const alego_remap_opts* opts) {
+  ALEGO_GATE(h);
+  if (!h->lm) { h->err = "alego_remap_enable: the handle has no LaserMapping"; return ALEGO_ERR_ARG; }
+  WAIT_ALL(h);
+  return lm_host_remap_enable(h->lm, opts, &h->err);
+}
+int alego_remap_get(alego_handle* h, const int32_t* slots, int32_t n, alego_remap* out) {
+  ALEGO_GATE(h);
+  if (!h->lm || n < 0 || (n > 0 && (!slots || !out))) { h->err = "alego_remap_get: null argument / negative count"; return ALEGO_ERR_ARG; }
+  WAIT_ALL(h);
+  return lm_host_remap_get(h->lm, slots, n, out, &h->err);
+}
+int alego_remap_host(const double acc28[28], const double params6[6], int32_t n_edge, int32_t n_plane, const alego_remap_opts* opts, alego_remap* out) {
+  if (!acc28 || !params6 || !out || n_edge < 0 || n_plane < 0) return ALEGO_ERR_ARG;
+  double eig_min;
+  if (rm_resolve(opts ? &opts->eig_min : nullptr, &eig_min)) return ALEGO_ERR_ARG;
+  remap_host(acc28, params6, n_edge, n_plane, eig_min, out);
+  return 0;
+}
+int alego_remap_step_host(const double H21[21], const double g6[6], const double scale6[6], double radius, const double* proj36, double step6[6], double* mcc) {
+  if (!H21 || !g6 || !scale6 || !step6 || !mcc) return ALEGO_ERR_ARG;
+  return remap_step_host(H21, g6, scale6, radius, proj36, step6, mcc) == LM_EVAL ? 1 : 0;
+}
+int alego_debug_remap_solve(alego_handle* h, const double start6[6], const double* edge_rows9, int32_t n_edge, const double* plane_rows7, int32_t n_plane, int32_t remap,
+                            double* params_it, double* costs, int32_t* summary, alego_remap* rec) {
+  ALEGO_GATE(h);
+  if (!h->lm) { h->err = "alego_debug_remap_solve: the handle has no LaserMapping"; return ALEGO_ERR_ARG; }
+  if (!start6 || !params_it || !costs || !summary || n_edge < 0 || n_plane < 0 || (n_edge > 0 && !edge_rows9) || (n_plane > 0 && !plane_rows7)) {
+    h->err = "alego_debug_remap_solve: null argument / negative count"; return ALEGO_ERR_ARG;
+  }
+  // one slot as lm_fit leaves it (lm_rows.h): the corner queries padded with queries that gave no row up to the registration guard's minimum, the
+  // planes' block records from row nqc, the query points as f32; the guard's other counts at values that pass it
+  const alego_params& P = h->d.P;
+  const int nqc = std::max({(int)n_edge, P.lm_min_corner, 1}), nqs = n_plane;
+  const size_t nr = (size_t)nqc + (size_t)std::max(nqs, 1);
+  std::vector<double> blocks(nr * LMB_W, 0.0), ld(LD_COUNT, 0.0);
+  std::vector<float> qc((size_t)nqc * 4, 0.f), qs((size_t)std::max(nqs, 1) * 4, 0.f);
+  std::vector<int> li(LI_COUNT, 0);
+  for (int i = 0; i < n_edge; ++i) {
+    const double* r = edge_rows9 + (size_t)i * 9;
+    lmb_put_edge(&blocks[lm_row_of(0, i, nqc) * LMB_W], r, r + 3);
+    for (int k = 0; k < 3; ++k) qc[(size_t)i * 4 + k] = (float)r[6 + k];
+  }
+  for (int i = 0; i < n_plane; ++i) {
+    const double* r = plane_rows7 + (size_t)i * 7;
+    lmb_put_plane(&blocks[lm_row_of(1, i, nqc) * LMB_W], r, r[3]);
+    for (int k = 0; k < 3; ++k) qs[(size_t)i * 4 + k] = (float)r[4 + k];
+  }
+  li[LI_RUN] = 1; li[LI_NKF] = 1; li[LI_REC_CNT] = 1; li[LI_NCUR_C] = nqc; li[LI_NTOTAL_DS] = nqs;
+  li[LI_NTOTAL] = std::max(nqs, P.lm_min_surf); li[LI_KDS_C] = std::max(1, P.lm_min_map_corner);
+  for (int k = 0; k < 6; ++k) ld[LD_PARAMS + k] = start6[k];
+  DevPool T;   // temporaries of this call
+  LmCtx L;
+  std::memset(&L, 0, sizeof L);
+  L.kf_cap_c = nqc; L.total_cap = std::max(nqs, 1); L.qcap = (int)nr;
+  L.solve_row_bytes = lm_host_ctx(h->lm)->solve_row_bytes;
+  L.rm_eig_min = lm_host_remap_eig_min(h->lm);
+  HIP_TRY(h, T.get(&L.li, li.size(), false)); HIP_TRY(h, T.get(&L.ld, ld.size(), false)); HIP_TRY(h, T.get(&L.blocks, blocks.size(), false));
+  HIP_TRY(h, T.get(&L.crows, nr * LMS_W, true)); HIP_TRY(h, T.get(&L.cur_corner_ds, qc.size() / 4, false)); HIP_TRY(h, T.get(&L.cur_total_ds, qs.size() / 4, false));
+  HIP_TRY(h, T.get(&L.rm_rec, 1, true));
+  HIP_TRY(h, hipMemcpy(L.li, li.data(), li.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIP_TRY(h, hipMemcpy(L.ld, ld.data(), ld.size() * 8, hipMemcpyHostToDevice));
+  HIP_TRY(h, hipMemcpy(L.blocks, blocks.data(), blocks.size() * 8, hipMemcpyHostToDevice));
+  HIP_TRY(h, hipMemcpy(L.cur_corner_ds, qc.data(), qc.size() * 4, hipMemcpyHostToDevice));
+  HIP_TRY(h, hipMemcpy(L.cur_total_ds, qs.data(), qs.size() * 4, hipMemcpyHostToDevice));
+  DevCtx d = h->d;
+  d.slot0 = 0; d.n_launch = 1;
+  launch_lm_solve(d, L, remap != 0, h->stream);
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  HIP_TRY(h, hipMemcpy(li.data(), L.li, li.size() * sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(h, hipMemcpy(ld.data(), L.ld, ld.size() * 8, hipMemcpyDeviceToHost));
+  for (int k = 0; k < 12; ++k) params_it[k] = ld[LD_PARAMS_IT + k];
+  for (int k = 0; k < 4; ++k) costs[k] = ld[LD_COSTS + k];
+  summary[0] = li[LI_SUM0]; summary[1] = li[LI_SUM1];
+  if (rec) HIP_TRY(h, hipMemcpy(rec, L.rm_rec, sizeof(*rec), hipMemcpyDeviceToHost));
+  return 0;
+}
+
 // ---- one registration sharded over the GPUs of a node ---------------------------------------------------------------
 int alego_dist_unique_id(char id[ALEGO_DIST_ID_BYTES]) { return id ? lm_host_dist_unique_id(id) : ALEGO_ERR_ARG; }
 int alego_dist_init(alego_handle* h, int rank, int world, const char id[ALEGO_DIST_ID_BYTES]) {

@@ -205,8 +205,18 @@ DEV_INLINE void wg_evaluate(const double* x, double* s_trig /*[12]*/, double* s_
 
 // One ceres::Solve into S: evaluate what `kind` asks for, let thread 0 take the sums in and propose (lm_control), until the solve has ended.
 // kind: LM_EV_BEGIN (from x0) or LM_EV_AGAIN (from S.x, whose normal equations S still holds: no evaluation; LaserMapping alone enters it).
-template <int T, int PRE, bool FULL_EVAL, class Rows, class Clock>
-DEV_INLINE void wg_solve(LmState& S, int* s_action, int kind, const double* x0, int max_iter, double* s_trig, double* s_acc, double* s_out, Rows&& rows, Clock& ck) {
+// Hook (lm_solve_remap alone; WgNoHook: nothing, the solve as it always was): after_begin(x0, s_trig, s_out) is called by every thread between the
+// evaluation of LM_EV_BEGIN and the control thread's turn — behind the barrier that published s_out, s_trig still holding pose_terms_coop's sines and
+// cosines of x0, and thread 0 runs it before lm_control; proj()
+// is what that thread hands lm_step (solve_rows.h).
+struct WgNoHook {
+  static constexpr bool remap = false;
+  DEV_INLINE void after_begin(const double*, const double*, const double*) const {}
+  DEV_INLINE const double* proj() const { return nullptr; }
+};
+template <int T, int PRE, bool FULL_EVAL, class Rows, class Clock, class Hook = WgNoHook>
+DEV_INLINE void wg_solve(LmState& S, int* s_action, int kind, const double* x0, int max_iter, double* s_trig, double* s_acc, double* s_out, Rows&& rows, Clock& ck,
+                         const Hook& hook = Hook{}) {
   while (true) {
     double x[6];
 #pragma unroll
@@ -214,7 +224,8 @@ DEV_INLINE void wg_solve(LmState& S, int* s_action, int kind, const double* x0, 
     if (kind == LM_EV_CAND_COST) wg_evaluate<T, PRE, false>(x, s_trig, s_acc, s_out, rows, ck);
     else if (kind != LM_EV_AGAIN) wg_evaluate<T, PRE, true>(x, s_trig, s_acc, s_out, rows, ck);
     ck.begin();
-    if (threadIdx.x == 0) *s_action = lm_control<FULL_EVAL, ALEGO_SOLVE_SPECULATE != 0>(S, kind, x0, s_out, max_iter);
+    if constexpr (Hook::remap) hook.after_begin(x0, s_trig, s_out);
+    if (threadIdx.x == 0) *s_action = lm_control<FULL_EVAL, ALEGO_SOLVE_SPECULATE != 0, Hook::remap>(S, kind, x0, s_out, max_iter, hook.proj());
     __syncthreads();
     ck.end(WG_T_CONTROL);
     const int act = *s_action;

@@ -18,7 +18,7 @@
 #include "../../include/alego_mi355x.h"
 #include "dev_cost.h"
 #include "nn_rules.h"
-#include "reg_cov_math.h"
+#include "remap_math.h"
 #include "prof.h"
 #include "kf_store.h"
 #include "gmap.h"
@@ -747,6 +747,160 @@ DEV_INLINE void lm_eval_rows(const LmRows& W, const PoseTerms& Tm, double huber,
   }
 }
 
+// wave 0, all 64 lanes, lane 6 i + j owning entry (i, j) (lanes 36 .. 63 shadow lane 35): the cyclic Jacobi of reg_cov_math.h on the lane-owned entries
+// of the symmetric A — a rotation fetches its partners with wave shuffles, every lane forms (c, s) from the same three entries — and the ordering:
+// lam[6] the eigenvalues ascending, ties by index (every lane holds all six); returns entry (i, j) of the eigenvectors sorted likewise.  The one
+// decomposition of lm_regcov (rc_tail) and lm_solve_remap (rm_tail); the operations and their order are rc_jacobi's and rc_sort's, entry by entry.
+// shfl(v, lane): the value of `lane`.  ShflHip is __shfl; ShflDirect forms ds_bpermute's byte address here — __shfl adds (lane id & ~63) to the source,
+// a term of the lane alone: inside lm_solve_remap the compiler hoists it, and every index built on it, out of the solver's loops (rm_tail).
+struct ShflHip { DEV_INLINE double operator()(double v, int src) const { return __shfl(v, src); } };
+struct ShflDirect {
+  DEV_INLINE double operator()(double v, int src) const {
+    const long long b = __double_as_longlong(v);
+    const int lo = __builtin_amdgcn_ds_bpermute(src << 2, (int)(unsigned)(unsigned long long)b), hi = __builtin_amdgcn_ds_bpermute(src << 2, (int)(unsigned)((unsigned long long)b >> 32));
+    return __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo));
+  }
+};
+template <class Shfl>
+DEV_INLINE double rc_eigen_lanes(double A, int i, int j, double lam[6], const Shfl& shfl) {
+  double V = i == j ? 1.0 : 0.0;
+  for (int sweep = 0; sweep < RC_SWEEPS_MAX; ++sweep) {
+    double off = 0.0, dg = 0.0;
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+      for (int b = a + 1; b < 6; ++b) { const double x = shfl(A, a * 6 + b); off += x * x; }
+#pragma unroll
+    for (int a = 0; a < 6; ++a) { const double x = shfl(A, a * 7); dg += x * x; }
+    if (!(off > RC_OFF_REL * dg)) break;
+#pragma unroll
+    for (int pp = 0; pp < 5; ++pp)
+#pragma unroll
+      for (int q = pp + 1; q < 6; ++q) {
+        const double apq = shfl(A, pp * 6 + q);
+        if (apq == 0.0) continue;   // (uniform)
+        double c, s;
+        rc_rot_cs(shfl(A, pp * 7), shfl(A, q * 7), apq, &c, &s);
+        { const double xp = shfl(A, i * 6 + pp), xq = shfl(A, i * 6 + q); A = rc_rot_col(j, pp, q, c, s, xp, xq, A); }
+        { const double xp = shfl(A, pp * 6 + j), xq = shfl(A, q * 6 + j); A = rc_rot_row(i, pp, q, c, s, xp, xq, A); }
+        { const double xp = shfl(V, i * 6 + pp), xq = shfl(V, i * 6 + q); V = rc_rot_col(j, pp, q, c, s, xp, xq, V); }
+      }
+  }
+  // ascending order, ties by index: sorted column r is the column whose diagonal entry has rank r
+  double dd[6];
+  int rk[6], src = 0;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) dd[k] = shfl(A, k * 7);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) { rk[k] = rc_rank(dd, k); if (rk[k] == j) src = k; }
+#pragma unroll
+  for (int r = 0; r < 6; ++r) {
+    double v = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) v = rk[k] == r ? dd[k] : v;
+    lam[r] = v;
+  }
+  return shfl(V, i * 6 + src);
+}
+
+// ---- solution remapping (alego_remap_enable; remap_math.h) ------------------------------------------------------------
+// The projector of a mapping frame from the 28 sums of the solver's own first evaluation, on wave 0 between that evaluation and the control
+// thread's first turn; it stays in LDS for every iteration of every outer solve of the frame.
+// (What the tail needs of the frame lies in LDS next to it, written by thread 0 before the solve: carried in registers through the evaluations, where
+// the kernel's register need peaks, it costs lm_solve_remap a wavefront per SIMD.)
+struct RmLds {
+  double P[36], N[36], M[36];   // P: what lm_step reads when `on` (something is held)
+  double eig_min;
+  alego_remap* rec;
+  int on, first, n_edge, n_plane, frame;   // first: the frame's first evaluation has not been taken in yet
+};
+static_assert(offsetof(alego_remap, start) == 16 && sizeof(alego_remap) == 16 + 84 * sizeof(double), "rm_store_empty walks the record's doubles from `start`");
+template <bool REMAP> DEV_INLINE RmLds* rm_lds() {
+  if constexpr (REMAP) { __shared__ RmLds R; return &R; }
+  else return nullptr;
+}
+// wave 0: a record without a result (nothing is held)
+DEV_INLINE void rm_store_empty(alego_remap* rec, int status, int frame, const double* x0, int lane) {
+  double* dv = rec->start;
+  for (int k = lane; k < 84; k += 64) dv[k] = k < 6 ? x0[k] : 0.0;
+  if (lane == 0) { rec->status = status; rec->n_held = 0; rec->frame = frame; rec->pad = 0; }
+}
+// wave 0, all 64 lanes active, lane 6 i + j owning entry (i, j) as in rc_tail.  The operations and their order are rm_compute's, entry by entry.
+// s_trig: pose_terms_coop's table of the evaluation at x0 — entries 6 .. 11 are cos, sin of roll, pitch, yaw by the very calls rc_trig makes.
+DEV_INLINE void rm_tail(const double* s_out /* LDS [28] */, const double* s_trig /* LDS [12] */, RmLds& R, const double* x0, int n_edge, int n_plane, int frame, double eig_min, alego_remap* rec) {
+  // (the lane index through an opaque move: everything below that depends on the lane alone — shuffle indices, entry selects — is invariant in the
+  // solver's loops, and hoisted out of them it stays in ~50 registers through the evaluations, which costs the kernel a wavefront per SIMD)
+  int lane = threadIdx.x;
+  asm volatile("" : "+v"(lane));
+  const int l = lane < 36 ? lane : 35, i = l / 6, j = l - 6 * i;
+  const double t6[6] = {s_trig[7], s_trig[6], s_trig[9], s_trig[8], s_trig[11], s_trig[10]};   // rc_trig's order
+  if (lane == 0) { R.on = 0; R.first = 0; }   // (once per frame)
+  if (n_edge + n_plane <= 6) { rm_store_empty(rec, 0, frame, x0, lane); return; }
+  if (fabs(t6[3]) < RC_COS_PITCH_MIN) { rm_store_empty(rec, -3, frame, x0, lane); return; }
+  {   // N = M^-1 and M into LDS: entries of info and of P index them by lane (one after the other: 36 doubles in registers at a time)
+    double N[36];
+    rc_minv_t(t6, N);
+    double v = 0.0;
+#pragma unroll
+    for (int k = 0; k < 36; ++k) v = lane == k ? N[k] : v;
+    if (lane < 36) R.N[lane] = v;
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  {
+    double M[36];
+    rc_m_t(t6, M);
+    double v = 0.0;
+#pragma unroll
+    for (int k = 0; k < 36; ++k) v = lane == k ? M[k] : v;
+    if (lane < 36) R.M[lane] = v;
+    __threadfence_block();
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  const double info = rc_info_entry(s_out, R.N, i < j ? i : j, i < j ? j : i);
+  bool bad = !rc_finite(info) || (lane < 28 && !rc_finite(s_out[lane])) || (lane < 6 && !rc_finite(x0[lane]));
+  if (__any(bad)) { rm_store_empty(rec, -2, frame, x0, lane); return; }
+  double lam[6], vi[6], vj[6], col[6];
+  __builtin_amdgcn_sched_barrier(0);
+  const ShflDirect shfl;
+  const double vs = rc_eigen_lanes(info, i, j, lam, shfl);
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) { vi[k] = shfl(vs, i * 6 + k); vj[k] = shfl(vs, j * 6 + k); }
+  const double pt = rm_pt_entry(vi, vj, lam, eig_min);
+#pragma unroll
+  for (int a = 0; a < 6; ++a) {   // (Pt M)(a, j) for the six a of this lane's column
+    double row[6];
+#pragma unroll
+    for (int b = 0; b < 6; ++b) row[b] = shfl(pt, a * 6 + b);
+    col[a] = rm_ptm_entry(row, R.M, j);
+    __builtin_amdgcn_sched_barrier(0);   // (one row of shuffles in flight: all 36 hoisted to the front cost the kernel a wavefront per SIMD)
+  }
+  int held = 0;
+  double lam_j = 0.0;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) { bad = bad || !rc_finite(lam[k]); held += rm_kept(lam[k], eig_min) ? 0 : 1; lam_j = j == k ? lam[k] : lam_j; }
+  const double pe = rm_p_entry(R.N, i, col);
+  const double P = held == 0 ? (i == j ? 1.0 : 0.0) : (held == 6 ? 0.0 : pe);
+  bad = bad || !rc_finite(vs) || !rc_finite(P);
+  if (__any(bad)) { rm_store_empty(rec, -2, frame, x0, lane); return; }
+  if (lane < 36) {
+    R.P[l] = P; rec->eigvec[l] = vs; rec->proj[l] = P;
+    if (i == 0) rec->eigval[j] = lam_j;
+  }
+  if (lane < 6) rec->start[lane] = x0[lane];
+  if (lane == 0) { rec->status = 1; rec->n_held = held; rec->frame = frame; rec->pad = 0; R.on = held > 0 ? 1 : 0; }
+  __threadfence_block();
+}
+// wg_solve's hook (dev_cost.h): the decomposition behind the first evaluation of the frame, the projector for every step after it
+struct RmHook {
+  static constexpr bool remap = true;
+  RmLds* R;
+  DEV_INLINE void after_begin(const double* x0, const double* s_trig, const double* s_out) const {
+    if (threadIdx.x < 64 && R->first) rm_tail(s_out, s_trig, *R, x0, R->n_edge, R->n_plane, R->frame, R->eig_min, R->rec);
+  }
+  DEV_INLINE const double* proj() const { return R->on ? R->P : nullptr; }
+};
+
 enum { LM_T_PACK = 4, LM_T_LD0 = 43 };   // -DALEGO_TIMING: the phases of lm_solve (dev_cost.h WG_T_*, and the pack) in ld[43 .. 47]
 // scan2MapOptimization's solver part, one workgroup per stream.
 // The normal equations are evaluated only where a step is computed from them: at the point a ceres::Solve starts from and at an adopted point
@@ -756,7 +910,9 @@ enum { LM_T_PACK = 4, LM_T_LD0 = 43 };   // -DALEGO_TIMING: the phases of lm_sol
 // iteration that starts where the last one ended with the normal equations in hand takes them from there.  Every evaluation is a function of
 // (x, rows): the points visited, their costs and the steps between them are what evaluating everything in full gives, bit for bit
 // (FULL_EVAL: exactly that, the cross-check kernel behind ALEGO_SOLVE_FULL_EVAL=1; tests/test_solver_eval_split.py).
-template <bool FULL_EVAL>
+// REMAP (lm_solve_remap, alego_remap_enable): the steps of the whole frame are projected off the directions the first evaluation does not observe
+// (the section above); every `if constexpr (REMAP)` below is absent from lm_solve and lm_solve_full_eval.
+template <bool FULL_EVAL, bool REMAP = false>
 DEV_INLINE void lm_solve_body(const DevCtx& d, const LmCtx& L) {
   const int slot = blockIdx.x + d.slot0;
   int* li = lip(L, slot);
@@ -765,6 +921,7 @@ DEV_INLINE void lm_solve_body(const DevCtx& d, const LmCtx& L) {
   double* ld = ldp(L, slot);
   if (lm_reg_skipped(li, P)) {
     if (threadIdx.x == 0) lm_store_skipped(li);
+    if constexpr (REMAP) { if (threadIdx.x < 64) rm_store_empty(L.rm_rec + slot, 0, li[LI_FRAME], ld + LD_PARAMS, threadIdx.x); }
     return;
   }
   extern __shared__ __attribute__((aligned(16))) unsigned char lm_smem[];
@@ -781,12 +938,23 @@ DEV_INLINE void lm_solve_body(const DevCtx& d, const LmCtx& L) {
   if (threadIdx.x == 0) { li[LI_NCC] = W.Rc; li[LI_NSC] = W.Rs; li[LI_OPTIMIZED] = 1; }
   const int R = W.Rc + W.Rs;
   auto rows = [&](const PoseTerms& T, double* acc, auto full) { lm_eval_rows<LM_SOLVE_T, decltype(full)::value>(W, T, P.huber_delta, acc); };
+  if constexpr (REMAP) {
+    if (threadIdx.x == 0) {
+      RmLds& Rm = *rm_lds<REMAP>();
+      Rm.eig_min = L.rm_eig_min; Rm.rec = L.rm_rec + slot; Rm.n_edge = W.Rc; Rm.n_plane = W.Rs; Rm.frame = li[LI_FRAME]; Rm.on = 0; Rm.first = 1;
+    }
+    if (R == 0 && threadIdx.x < 64) rm_store_empty(L.rm_rec + slot, 0, li[LI_FRAME], ld + LD_PARAMS, threadIdx.x);   // (no solve: the record of fewer than 7 rows)
+  }
   for (int outer = 0; outer < P.lm_outer_iters; ++outer) {  // :360 — identical correspondences both times
     if (R == 0) {
       if (threadIdx.x == 0) lm_store_outer_empty(li, ld, outer);
       continue;
     }
     // (s_again: thread 0's verdict at the end of the outer iteration before, behind that iteration's closing barrier)
+    if constexpr (REMAP) {
+      const RmHook hook{rm_lds<REMAP>()};
+      wg_solve<LM_SOLVE_T, 3, FULL_EVAL>(S, &s_action, (!FULL_EVAL && outer > 0 && s_again) ? LM_EV_AGAIN : LM_EV_BEGIN, ld + LD_PARAMS, P.lm_max_iters, s_trig, s_acc, s_out, rows, ck, hook);
+    } else
     wg_solve<LM_SOLVE_T, 3, FULL_EVAL>(S, &s_action, (!FULL_EVAL && outer > 0 && s_again) ? LM_EV_AGAIN : LM_EV_BEGIN, ld + LD_PARAMS, P.lm_max_iters, s_trig, s_acc, s_out, rows, ck);
     if (threadIdx.x == 0) {
 #ifdef ALEGO_TIMING
@@ -801,6 +969,9 @@ DEV_INLINE void lm_solve_body(const DevCtx& d, const LmCtx& L) {
 // grid (slots).  The default kernel keeps the plain name the profiles and the bench look up.
 __global__ void __launch_bounds__(LM_SOLVE_T) lm_solve(DevCtx d, LmCtx L) { lm_solve_body<false>(d, L); }
 __global__ void __launch_bounds__(LM_SOLVE_T) lm_solve_full_eval(DevCtx d, LmCtx L) { lm_solve_body<true>(d, L); }
+// (two wavefronts per SIMD asked for: left to itself the compiler takes 256 VGPRs + 2 AGPRs and halves the occupancy; with the bound it fits 256 without scratch)
+__global__ void __launch_bounds__(LM_SOLVE_T, 2) lm_solve_remap(DevCtx d, LmCtx L) { lm_solve_body<false, true>(d, L); }
+__global__ void __launch_bounds__(LM_SOLVE_T, 2) lm_solve_remap_full_eval(DevCtx d, LmCtx L) { lm_solve_body<true, true>(d, L); }
 
 // ---- covariance and degeneracy of the registration (alego_regcov_enable; reg_cov_math.h) -----------------------------
 // One full evaluation of the accepted rows at the solver's final point, then the 6x6 part on wave 0.  The rows are streamed once from where
@@ -843,44 +1014,8 @@ DEV_INLINE void rc_tail(const double* s_out /* LDS [28] */, double* s_N /* LDS [
   const double info = rc_info_entry(s_out, s_N, i < j ? i : j, i < j ? j : i);
   bool bad = !rc_finite(info) || (lane < 28 && !rc_finite(s_out[lane])) || (lane < 6 && !rc_finite(p[lane]));
   if (__any(bad)) { rc_store_empty(rec, -2, n_edge, n_plane, frame); return; }
-  double A = info, V = i == j ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < RC_SWEEPS_MAX; ++sweep) {
-    double off = 0.0, dg = 0.0;
-#pragma unroll
-    for (int a = 0; a < 6; ++a)
-#pragma unroll
-      for (int b = a + 1; b < 6; ++b) { const double x = __shfl(A, a * 6 + b); off += x * x; }
-#pragma unroll
-    for (int a = 0; a < 6; ++a) { const double x = __shfl(A, a * 7); dg += x * x; }
-    if (!(off > RC_OFF_REL * dg)) break;
-#pragma unroll
-    for (int pp = 0; pp < 5; ++pp)
-#pragma unroll
-      for (int q = pp + 1; q < 6; ++q) {
-        const double apq = __shfl(A, pp * 6 + q);
-        if (apq == 0.0) continue;   // (uniform)
-        double c, s;
-        rc_rot_cs(__shfl(A, pp * 7), __shfl(A, q * 7), apq, &c, &s);
-        { const double xp = __shfl(A, i * 6 + pp), xq = __shfl(A, i * 6 + q); A = rc_rot_col(j, pp, q, c, s, xp, xq, A); }
-        { const double xp = __shfl(A, pp * 6 + j), xq = __shfl(A, q * 6 + j); A = rc_rot_row(i, pp, q, c, s, xp, xq, A); }
-        { const double xp = __shfl(V, i * 6 + pp), xq = __shfl(V, i * 6 + q); V = rc_rot_col(j, pp, q, c, s, xp, xq, V); }
-      }
-  }
-  // ascending order, ties by index: sorted column r is the column whose diagonal entry has rank r
-  double dd[6], lam[6], w[6], vi[6], vj[6];
-  int rk[6], src = 0;
-#pragma unroll
-  for (int k = 0; k < 6; ++k) dd[k] = __shfl(A, k * 7);
-#pragma unroll
-  for (int k = 0; k < 6; ++k) { rk[k] = rc_rank(dd, k); if (rk[k] == j) src = k; }
-#pragma unroll
-  for (int r = 0; r < 6; ++r) {
-    double v = 0.0;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) v = rk[k] == r ? dd[k] : v;
-    lam[r] = v;
-  }
-  const double vs = __shfl(V, i * 6 + src);
+  double lam[6], w[6], vi[6], vj[6];
+  const double vs = rc_eigen_lanes(info, i, j, lam, ShflHip{});
   const double s2 = rc_sigma2(s_out[27], rows, opt[RC_SIGMA0]);
 #pragma unroll
   for (int k = 0; k < 6; ++k) { w[k] = rc_weight(lam[k], lam[5], opt[RC_LAMBDA_FLOOR]); vi[k] = __shfl(vs, i * 6 + k); vj[k] = __shfl(vs, j * 6 + k); }
@@ -1121,8 +1256,10 @@ DEV_INLINE void lm_shard_next_outer_dev(const LmCtx& L, int slot) {
 size_t lm_solve_row_bytes_max() { return LM_SOLVE_DYN_BYTES - LM_SOLVE_RED_BYTES; }
 size_t lm_solve_row_bytes_default() { return LM_SOLVE_ROW_BYTES_DEFAULT; }
 int lm_configure() {
-  return (hipFuncSetAttribute(reinterpret_cast<const void*>(lm_solve), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LM_SOLVE_DYN_BYTES) == hipSuccess &&
-          hipFuncSetAttribute(reinterpret_cast<const void*>(lm_solve_full_eval), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LM_SOLVE_DYN_BYTES) == hipSuccess) ? 0 : -1;
+  for (const void* k : {reinterpret_cast<const void*>(lm_solve), reinterpret_cast<const void*>(lm_solve_full_eval), reinterpret_cast<const void*>(lm_solve_remap),
+                        reinterpret_cast<const void*>(lm_solve_remap_full_eval)})
+    if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LM_SOLVE_DYN_BYTES) != hipSuccess) return -1;
+  return 0;
 }
 
 // ---- launchers ---------------------------------------------------------------------
@@ -1144,6 +1281,18 @@ void launch_lm_total(const DevCtx& d, const LmCtx& L, hipStream_t st) {
 }
 void launch_lm_grid(const DevCtx& d, const LmCtx& L, hipStream_t st) {
   ALEGO_LAUNCH(lm_grid_build, dim3(2, d.n_launch), dim3(LM_BLOCK), 0, st, d, L);
+}
+// the solver kernel alone on the slots of d: lm_solve, its ALEGO_SOLVE_FULL_EVAL twin, or the _remap variant of either
+void launch_lm_solve(const DevCtx& d, const LmCtx& L, bool remap, hipStream_t st) {
+  const size_t lds = LM_SOLVE_RED_BYTES + L.solve_row_bytes;
+  if (remap) {
+    if (d.opt_solve_full_eval) ALEGO_LAUNCH(lm_solve_remap_full_eval, dim3(d.n_launch), dim3(LM_SOLVE_T), lds, st, d, L);
+    else ALEGO_LAUNCH(lm_solve_remap, dim3(d.n_launch), dim3(LM_SOLVE_T), lds, st, d, L);
+  } else if (d.opt_solve_full_eval) {
+    ALEGO_LAUNCH(lm_solve_full_eval, dim3(d.n_launch), dim3(LM_SOLVE_T), lds, st, d, L);
+  } else {
+    ALEGO_LAUNCH(lm_solve, dim3(d.n_launch), dim3(LM_SOLVE_T), lds, st, d, L);
+  }
 }
 // allreduce(buffer, count of doubles, stream): sums shard_part over the ranks in place (RCCL, lm_host.hip); nullptr = not sharded
 // Returns the first non-zero allreduce code: a failed collective (communicator aborted, peer gone) would leave the ranks stepping on
@@ -1167,11 +1316,7 @@ int launch_lm_register(const DevCtx& d, const LmCtx& L, hipStream_t st, int (*al
       }
     }
     ALEGO_LAUNCH(lm_shard_step, g1, b1, 0, st, d, L, d.P.lm_max_iters <= 0 ? 1 : 0);
-  } else if (d.opt_solve_full_eval) {
-    ALEGO_LAUNCH(lm_solve_full_eval, dim3(d.n_launch), dim3(LM_SOLVE_T), LM_SOLVE_RED_BYTES + L.solve_row_bytes, st, d, L);
-  } else {
-    ALEGO_LAUNCH(lm_solve, dim3(d.n_launch), dim3(LM_SOLVE_T), LM_SOLVE_RED_BYTES + L.solve_row_bytes, st, d, L);
-  }
+  } else launch_lm_solve(d, L, L.rm_rec != nullptr, st);   // (alego_remap_enable picks the _remap variant; nothing of it is launched without it)
   if (L.rc_rec) ALEGO_LAUNCH(lm_regcov, dim3(d.n_launch), dim3(LM_SOLVE_T), 0, st, d, L);   // (alego_regcov_enable; nothing is launched without it)
   ALEGO_LAUNCH(lm_finish, dim3((d.n_launch + 63) / 64), dim3(64), 0, st, d, L);
   if (L.loc_on) return 0;  // no key frame is ever stored, sorted or archived
@@ -1185,6 +1330,25 @@ void regcov_host(const double* acc28, const double* params6, int n_edge, int n_p
   out->n_edge = n_edge; out->n_plane = n_plane;
   out->status = rc_compute(acc28, params6, n_edge, n_plane, opt, &out->sigma2, out->info, out->eigval, out->eigvec, out->cov, out->variance, &out->n_degenerate, nullptr);
   if (out->status == 1) out->cost = acc28[27];
+}
+// alego_remap_host: rm_compute (remap_math.h) on the caller's 28 scalars
+void remap_host(const double* acc28, const double* params6, int n_edge, int n_plane, double eig_min, alego_remap* out) {
+  std::memset(out, 0, sizeof(*out));
+  for (int k = 0; k < 6; ++k) out->start[k] = params6[k];
+  out->status = rm_compute(acc28, params6, n_edge, n_plane, eig_min, out->eigval, out->eigvec, out->proj, &out->n_held);
+}
+// alego_remap_step_host: one lm_step (solve_rows.h) at x = 0 from given normal equations, scale and radius.  step6: the candidate, i.e. the step in
+// parameter space (scale_i step_i, as lm_step forms it); returns lm_step's answer (LM_EVAL, or LM_AGAIN for an invalid step: step6 and mcc are then zero)
+int remap_step_host(const double* H21, const double* g6, const double* scale6, double radius, const double* proj36, double* step6, double* mcc) {
+  LmState S;
+  std::memset(&S, 0, sizeof S);
+  for (int k = 0; k < 21; ++k) S.H[k] = H21[k];
+  for (int k = 0; k < 6; ++k) { S.g[k] = g6[k]; S.scale[k] = scale6[k]; }
+  S.radius = radius; S.dec = 2.0;
+  const int act = lm_step<true>(S, proj36);
+  for (int k = 0; k < 6; ++k) step6[k] = act == LM_EVAL ? S.cand[k] : 0.0;
+  *mcc = act == LM_EVAL ? S.mcc : 0.0;
+  return act;
 }
 void regcov_normal_host(const double* params6, const double* edge_rows9, int n_edge, const double* plane_rows7, int n_plane, double huber, double* acc28) {
   for (int k = 0; k < 28; ++k) acc28[k] = 0.0;

@@ -48,6 +48,7 @@ enum {
 
 struct alego_graph_edge;   // include/alego_mi355x.h
 struct alego_regcov;
+struct alego_remap;
 
 struct MapWork {     // work list of map_accum, written by map_update (kernels_map.hip)
   int* items;      // [cap] packed (slot - slot0) << 12 | m << 11 | chunk   (chunk < 2048)
@@ -173,6 +174,10 @@ struct LmCtx {
   alego_regcov* rc_rec;                           // [slot]
   const double* rc_opt;                           // [RC_OPT_W] the resolved options (reg_cov_math.h)
   int rc_graph;                                   // 1: map_archive writes a fresh record's variances into the odometry edge it records
+  // solution remapping (alego_remap_enable; rm_rec == nullptr: off, nothing is allocated and lm_solve runs): one record per slot, written by
+  // lm_solve_remap behind the first evaluation of a mapping frame
+  alego_remap* rm_rec;                            // [slot]
+  double rm_eig_min;                              // the resolved option (remap_math.h)
 };
 
 // a slot's rows (lm_rows.h: a corner query q has row q, a surf query q row kf_cap_c + q)
@@ -212,6 +217,7 @@ void launch_lm_stage(const DevCtx& d, const LmCtx& L, int run_hint, int par, hip
 void launch_lm_concat(const DevCtx& d, const LmCtx& L, hipStream_t st);
 void launch_lm_total(const DevCtx& d, const LmCtx& L, hipStream_t st);
 void launch_lm_grid(const DevCtx& d, const LmCtx& L, hipStream_t st);
+void launch_lm_solve(const DevCtx& d, const LmCtx& L, bool remap, hipStream_t st);   // the solver kernel alone (launch_lm_register's, and alego_debug_remap_solve's on a one-slot view)
 int launch_lm_register(const DevCtx& d, const LmCtx& L, hipStream_t st, int (*allreduce)(void*, double*, size_t, hipStream_t), void* ar_ctx);
 void launch_lm_retransform(const DevCtx& d, const LmCtx& L, int ring, hipStream_t st);
 void launch_lm_apply_correction(const DevCtx& d, const LmCtx& L, int slot, const double* rc_dev, hipStream_t st);
@@ -221,6 +227,9 @@ void launch_lm_regcov_debug(const double* blocks, const float4* qc, int n_edge, 
 // host twins: the record from 28 scalars and resolved options (reg_cov_math.h); the 28 scalars from rows (a, b, p | n, d, p), edges then planes, in row order
 void regcov_host(const double* acc28, const double* params6, int n_edge, int n_plane, const double* opt, alego_regcov* out);
 void regcov_normal_host(const double* params6, const double* edge_rows9, int n_edge, const double* plane_rows7, int n_plane, double huber, double* acc28);
+// host twins of lm_solve_remap's 6x6 part and of one lm_step (remap_math.h, solve_rows.h)
+void remap_host(const double* acc28, const double* params6, int n_edge, int n_plane, double eig_min, alego_remap* out);
+int remap_step_host(const double* H21, const double* g6, const double* scale6, double radius, const double* proj36, double* step6, double* mcc);
 void launch_map_update(const DevCtx& d, const LmCtx& L, const MapWork& W, hipStream_t st);
 void launch_map_accum(const DevCtx& d, const LmCtx& L, const MapWork& W, hipStream_t st);
 void launch_loc_select(const DevCtx& d, const LmCtx& L, hipStream_t st);

@@ -83,5 +83,9 @@ bool lm_host_localising(LmHost* lm);
 int lm_host_regcov_enable(LmHost* lm, const alego_regcov_opts* opts, std::string* err);
 int lm_host_regcov_get(LmHost* lm, const int* slots, int n, alego_regcov* out, std::string* err);
 bool lm_host_regcov_on(LmHost* lm);
+// solution remapping (alego_remap_*; lm_solve_remap in kernels_lm.hip), as above
+int lm_host_remap_enable(LmHost* lm, const alego_remap_opts* opts, std::string* err);
+int lm_host_remap_get(LmHost* lm, const int* slots, int n, alego_remap* out, std::string* err);
+double lm_host_remap_eig_min(LmHost* lm);   // the handle's resolved option (the default while the feature is off; lm may be null)
 bool lm_host_regcov_opts(LmHost* lm, double* opt16);   // the handle's resolved options (the defaults while the feature is off; lm may be null); true: the feature is on
 #endif

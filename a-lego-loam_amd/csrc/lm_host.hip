@@ -22,7 +22,7 @@
 #include "thin.h"
 #include "thin_math.h"
 #include "loc_store.h"
-#include "reg_cov_math.h"
+#include "remap_math.h"
 
 struct LmHost {
   alego_params P;
@@ -65,6 +65,8 @@ struct LmHost {
   // alego_regcov_enable: the resolved options (reg_cov_math.h) as the device holds them
   bool rc_on = false;
   double rc_opt[RC_OPT_W] = {};
+  // alego_remap_enable
+  bool rm_on = false;
 };
 
 namespace {
@@ -549,6 +551,7 @@ int lm_host_dist_unique_id(char* id128) {
 int lm_host_dist_init(LmHost* lm, int rank, int world, const char* id128, std::string* err) {
   if (lm->comm) { *err = "alego_dist_init: already initialised"; return ALEGO_ERR_ARG; }
   if (lm->rc_on) { *err = "alego_dist_init: not available with alego_regcov_enable (the sharded solver never holds a registration's normal equations in one place)"; return ALEGO_ERR_ARG; }
+  if (lm->rm_on) { *err = "alego_dist_init: not available with alego_remap_enable (the sharded solver's step is taken apart from its evaluations)"; return ALEGO_ERR_ARG; }
   if (world < 1 || rank < 0 || rank >= world) { *err = "alego_dist_init: rank / world out of range"; return ALEGO_ERR_ARG; }
   if (lm->st.size() != 1) { *err = "alego_dist_init: a sharded registration needs a handle with one stream group (collectives of one communicator must not overlap)"; return ALEGO_ERR_ARG; }
   ncclUniqueId u;
@@ -1036,6 +1039,35 @@ int lm_host_regcov_get(LmHost* lm, const int* slots, int n, alego_regcov* out, s
   return 0;
 }
 bool lm_host_regcov_on(LmHost* lm) { return lm->rc_on; }
+
+// ---- solution remapping (alego_remap_*; lm_solve_remap in kernels_lm.hip) ----
+double lm_host_remap_eig_min(LmHost* lm) { return lm && lm->rm_on ? lm->L.rm_eig_min : RC_DEFAULT_EIG_MIN; }
+int lm_host_remap_enable(LmHost* lm, const alego_remap_opts* opts, std::string* err) {
+  LmCtx& L = lm->L;
+  if (lm->rm_on) { *err = "alego_remap_enable: already enabled"; return ALEGO_ERR_ARG; }
+  if (lm->comm || L.shard_world > 0) { *err = "alego_remap_enable: not available on a handle with a sharded registration (alego_dist_init)"; return ALEGO_ERR_ARG; }
+  double eig_min;
+  if (rm_resolve(opts ? &opts->eig_min : nullptr, &eig_min)) { *err = "alego_remap_enable: eig_min is not finite"; return ALEGO_ERR_ARG; }
+  for (long f : lm->frames) if (f != 0) { *err = "alego_remap_enable: call it before the first scan reaches LaserMapping"; return ALEGO_ERR_ARG; }
+  if (int r = rings_empty(lm, "alego_remap_enable", true, err)) return r;
+  LmCtx T = L;
+  if (!A(lm, &T.rm_rec, (size_t)lm->n_slots, err)) return ALEGO_ERR_HIP;
+  T.rm_eig_min = eig_min;
+  L = T;
+  lm->rm_on = true;
+  return 0;
+}
+int lm_host_remap_get(LmHost* lm, const int* slots, int n, alego_remap* out, std::string* err) {
+  if (!lm->rm_on) { *err = "alego_remap_get: the feature is off (alego_remap_enable)"; return ALEGO_ERR_ARG; }
+  if (int r = gate_slot_list("alego_remap_get", slots, n, lm->n_slots, true, err)) return r;
+  if (n == 0) return 0;
+  const int lo = *std::min_element(slots, slots + n), hi = *std::max_element(slots, slots + n);
+  for (hipStream_t s : lm->st) if (hipStreamSynchronize(s) != hipSuccess) { *err = "alego_remap_get: a stream failed"; return ALEGO_ERR_HIP; }
+  std::vector<alego_remap> tmp((size_t)(hi - lo + 1));
+  if (hipMemcpy(tmp.data(), lm->L.rm_rec + lo, tmp.size() * sizeof(alego_remap), hipMemcpyDeviceToHost) != hipSuccess) { *err = "alego_remap_get: device read failed"; return ALEGO_ERR_HIP; }
+  for (int i = 0; i < n; ++i) out[i] = tmp[(size_t)(slots[i] - lo)];
+  return 0;
+}
 
 // Frames of the slots with mask[slot] != 0 (mask_dev: the same words on the device) go through kf_tmp_* and the key-frame sort jobs, oldest first, one
 // frame of every such slot of a stream group per round (what alego_lm_set_keypose does for one frame of one slot); retransform(slot0, n, j, stream)

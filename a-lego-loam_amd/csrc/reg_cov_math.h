@@ -56,18 +56,24 @@ RC_FN double rc_h(const double* acc, int i, int j) {
   const int a = i < j ? i : j, b = i < j ? j : i;
   return acc[a * 6 - (a * (a - 1)) / 2 + (b - a)];
 }
-// M (row-major 6x6): xi = M dp
-RC_FN void rc_m(const double* p, double* M) {
-  const double sr = sin(p[3]), cr = cos(p[3]), sp = sin(p[4]), cp = cos(p[4]), sy = sin(p[5]), cy = cos(p[5]);
+// the sines and cosines M and N are made of: t = (sin roll, cos roll, sin pitch, cos pitch, sin yaw, cos yaw)
+RC_FN void rc_trig(const double* p, double* t) { t[0] = sin(p[3]); t[1] = cos(p[3]); t[2] = sin(p[4]); t[3] = cos(p[4]); t[4] = sin(p[5]); t[5] = cos(p[5]); }
+// M (row-major 6x6): xi = M dp.  (rc_m_t / rc_minv_t: from rc_trig's six values — a solver kernel has them in LDS from its evaluation at p)
+RC_FN void rc_m_t(const double* t, double* M) {
+  const double sr = t[0], cr = t[1], sp = t[2], cp = t[3], sy = t[4], cy = t[5];
   const double R[9] = {cy * cp, cy * sp * sr - sy * cr, cy * sp * cr + sy * sr, sy * cp, sy * sp * sr + cy * cr, sy * sp * cr - cy * sr, -sp, cp * sr, cp * cr};
   const double E[9] = {1.0, 0.0, -sp, 0.0, cr, sr * cp, 0.0, -sr, cr * cp};
+RC_UNROLL
   for (int k = 0; k < 36; ++k) M[k] = 0.0;
+RC_UNROLL
   for (int r = 0; r < 3; ++r)
+RC_UNROLL
     for (int c = 0; c < 3; ++c) { M[r * 6 + 3 + c] = E[r * 3 + c]; M[(3 + r) * 6 + c] = R[c * 3 + r]; }
 }
+RC_FN void rc_m(const double* p, double* M) { double t[6]; rc_trig(p, t); rc_m_t(t, M); }
 // N = M^-1 (row-major 6x6): dp = N xi
-RC_FN void rc_minv(const double* p, double* N) {
-  const double sr = sin(p[3]), cr = cos(p[3]), sp = sin(p[4]), cp = cos(p[4]), sy = sin(p[5]), cy = cos(p[5]);
+RC_FN void rc_minv_t(const double* t, double* N) {
+  const double sr = t[0], cr = t[1], sp = t[2], cp = t[3], sy = t[4], cy = t[5];
   const double R[9] = {cy * cp, cy * sp * sr - sy * cr, cy * sp * cr + sy * sr, sy * cp, sy * sp * sr + cy * cr, sy * sp * cr - cy * sr, -sp, cp * sr, cp * cr};
   const double Ei[9] = {1.0, sr * sp / cp, cr * sp / cp, 0.0, cr, -sr, 0.0, sr / cp, cr / cp};
 RC_UNROLL
@@ -77,6 +83,7 @@ RC_UNROLL
 RC_UNROLL
     for (int c = 0; c < 3; ++c) { N[r * 6 + 3 + c] = R[r * 3 + c]; N[(3 + r) * 6 + c] = Ei[r * 3 + c]; }
 }
+RC_FN void rc_minv(const double* p, double* N) { double t[6]; rc_trig(p, t); rc_minv_t(t, N); }
 // info(i, j) = (N^T H N)(i, j); callers pass i <= j and mirror
 RC_FN double rc_info_entry(const double* acc, const double* N, int i, int j) {
   double s = 0.0;
@@ -123,28 +130,11 @@ RC_FN double rc_sigma2(double cost, int rows, double sigma0) { const double a = 
 RC_FN double rc_clamp(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }
 RC_FN bool rc_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }   // false for NaN
 
-// The record as plain arrays (the host twin; the kernel does the same entry by entry on 36 lanes).  Returns the status; *sweeps (optional):
-// sweeps in which a rotation was made.
-RC_FN int rc_compute(const double* acc, const double* p, int n_edge, int n_plane, const double* opt, double* sigma2, double* info, double* eigval, double* eigvec,
-                     double* cov, double* variance, int* n_degenerate, int* sweeps) {
-  *sigma2 = 0.0; *n_degenerate = 0;
-  if (sweeps) *sweeps = 0;
-  for (int k = 0; k < 36; ++k) { info[k] = 0.0; eigvec[k] = 0.0; cov[k] = 0.0; }
-  for (int k = 0; k < 6; ++k) { eigval[k] = 0.0; variance[k] = 0.0; }
-  const int rows = n_edge + n_plane;
-  if (rows <= 6) return 0;
-  if (fabs(cos(p[4])) < RC_COS_PITCH_MIN) return -3;
-  bool bad = false;
-  for (int k = 0; k < 28; ++k) bad = bad || !rc_finite(acc[k]);
-  for (int k = 0; k < 6; ++k) bad = bad || !rc_finite(p[k]);
-  double N[36], A[36], V[36], B[36];
-  rc_minv(p, N);
-  for (int i = 0; i < 6; ++i)
-    for (int j = i; j < 6; ++j) { const double v = rc_info_entry(acc, N, i, j); A[i * 6 + j] = v; A[j * 6 + i] = v; }
-  for (int k = 0; k < 36; ++k) { bad = bad || !rc_finite(A[k]); V[k] = (k % 7 == 0) ? 1.0 : 0.0; }
-  if (bad) return -2;
-  double inf0[36];
-  for (int k = 0; k < 36; ++k) inf0[k] = A[k];
+// The cyclic Jacobi of a symmetric 6x6 A (row-major, overwritten: its diagonal ends as the eigenvalues) with V <- V G for every rotation G
+// (V = I on entry: the eigenvectors by columns).  *sweeps (optional) is advanced by the sweeps in which a rotation was made.  The one loop of the
+// host twins (rc_compute; rm_compute, remap_math.h); the kernels run the same rotations entry by entry on 36 lanes.
+RC_FN void rc_jacobi(double* A, double* V, int* sweeps) {
+  double B[36];
   for (int sweep = 0; sweep < RC_SWEEPS_MAX; ++sweep) {
     double off = 0.0, dg = 0.0;
     for (int i = 0; i < 6; ++i)
@@ -166,9 +156,39 @@ RC_FN int rc_compute(const double* acc, const double* p, int n_edge, int n_plane
         for (int i = 0; i < 6; ++i) for (int j = 0; j < 6; ++j) V[i * 6 + j] = rc_rot_col(j, pp, q, c, s, B[i * 6 + pp], B[i * 6 + q], B[i * 6 + j]);
       }
   }
-  double d[6], lam[6], Vs[36], w[6], cv[36];
+}
+// ... and its result in ascending order, ties by index: lam[r] and column r of Vs from the diagonal entry of rank r
+RC_FN void rc_sort(const double* A, const double* V, double* lam, double* Vs) {
+  double d[6];
   for (int k = 0; k < 6; ++k) d[k] = A[k * 6 + k];
   for (int k = 0; k < 6; ++k) { const int r = rc_rank(d, k); lam[r] = d[k]; for (int i = 0; i < 6; ++i) Vs[i * 6 + r] = V[i * 6 + k]; }
+}
+
+// The record as plain arrays (the host twin; the kernel does the same entry by entry on 36 lanes).  Returns the status; *sweeps (optional):
+// sweeps in which a rotation was made.
+RC_FN int rc_compute(const double* acc, const double* p, int n_edge, int n_plane, const double* opt, double* sigma2, double* info, double* eigval, double* eigvec,
+                     double* cov, double* variance, int* n_degenerate, int* sweeps) {
+  *sigma2 = 0.0; *n_degenerate = 0;
+  if (sweeps) *sweeps = 0;
+  for (int k = 0; k < 36; ++k) { info[k] = 0.0; eigvec[k] = 0.0; cov[k] = 0.0; }
+  for (int k = 0; k < 6; ++k) { eigval[k] = 0.0; variance[k] = 0.0; }
+  const int rows = n_edge + n_plane;
+  if (rows <= 6) return 0;
+  if (fabs(cos(p[4])) < RC_COS_PITCH_MIN) return -3;
+  bool bad = false;
+  for (int k = 0; k < 28; ++k) bad = bad || !rc_finite(acc[k]);
+  for (int k = 0; k < 6; ++k) bad = bad || !rc_finite(p[k]);
+  double N[36], A[36], V[36];
+  rc_minv(p, N);
+  for (int i = 0; i < 6; ++i)
+    for (int j = i; j < 6; ++j) { const double v = rc_info_entry(acc, N, i, j); A[i * 6 + j] = v; A[j * 6 + i] = v; }
+  for (int k = 0; k < 36; ++k) { bad = bad || !rc_finite(A[k]); V[k] = (k % 7 == 0) ? 1.0 : 0.0; }
+  if (bad) return -2;
+  double inf0[36];
+  for (int k = 0; k < 36; ++k) inf0[k] = A[k];
+  rc_jacobi(A, V, sweeps);
+  double lam[6], Vs[36], w[6], cv[36];
+  rc_sort(A, V, lam, Vs);
   const double s2 = rc_sigma2(acc[27], rows, opt[RC_SIGMA0]);
   for (int k = 0; k < 6; ++k) w[k] = rc_weight(lam[k], lam[5], opt[RC_LAMBDA_FLOOR]);
   for (int i = 0; i < 6; ++i)

@@ -10,6 +10,12 @@
 #include <math.h>
 #define SOLVE_FN inline
 #endif
+#include "remap_math.h"
+#ifdef __HIP_DEVICE_COMPILE__
+#define SOLVE_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
+#else
+#define SOLVE_SCHED_FENCE() ((void)0)
+#endif
 
 // The candidate policy of lo_solve_t and lm_solve, one definition for both.  1: the candidate after a successful step is evaluated in full at once
 // (it is adopted more often than not, and adopting it then costs no second pass); 0: every candidate for its cost first.  The results are the same
@@ -263,7 +269,12 @@ SOLVE_FN void lm_begin(LmState& S, const double* x0, const double* acc, int max_
 }
 
 // the next candidate into S.cand from the normal equations at S.x (the part of lm_propose behind its stopping tests)
-SOLVE_FN int lm_step(LmState& S) {
+// REMAP (lm_solve_remap; remap_math.h) with proj != null: the step is replaced by S^-1 P S step, P = proj[36] in parameter
+// space, before the model cost change is formed — mcc, the candidate and both tests of lm_consume_eval see the projected step.  A projected step
+// that is exactly zero (P = 0: every direction is held) is not an invalid step: the candidate is x itself, and its evaluation ends the solve by
+// the step-size test (termination 2).  proj == null, or REMAP false: the code below is lm_step as it always was.
+template <bool REMAP = false>
+SOLVE_FN int lm_step(LmState& S, const double* proj = nullptr) {
   ++S.iter;
   double A[6][6], gs[6], y[6], Hl[21], sc[6], gl[6];
 #pragma unroll
@@ -308,6 +319,17 @@ SOLVE_FN int lm_step(LmState& S) {
   bool finite = ok;
 #pragma unroll
   for (int i = 0; i < 6; ++i) { step[i] = -y[i]; finite = finite && isfinite(step[i]); }
+  bool null_step = false;
+  if constexpr (REMAP) {
+    if (proj && finite) {
+      SOLVE_SCHED_FENCE();   // (the 36 loads of P stay behind the factorisation: hoisted above it they cost the kernel a wavefront per SIMD)
+      rm_project_step(proj, sc, step);
+      SOLVE_SCHED_FENCE();
+      null_step = true;
+#pragma unroll
+      for (int i = 0; i < 6; ++i) { finite = finite && isfinite(step[i]); null_step = null_step && step[i] == 0.0; }
+    }
+  }
   if (finite) {
     double lin = 0, quad = 0;
 #pragma unroll
@@ -319,6 +341,15 @@ SOLVE_FN int lm_step(LmState& S) {
       quad += step[i] * t;
     }
     mcc = -lin - 0.5 * quad;
+  }
+  if constexpr (REMAP) {
+    if (finite && null_step) {   // (mcc is 0: lm_consume_eval's step-size test ends the solve before it is read)
+      S.num_invalid = 0;
+      S.mcc = mcc;
+#pragma unroll
+      for (int i = 0; i < 6; ++i) S.cand[i] = S.x[i] + step[i] * sc[i];
+      return LM_EVAL;
+    }
   }
   if (!finite || !(mcc > 0.0)) {  // HandleInvalidStep
     if (++S.num_invalid >= 5) { S.termination = 4; return LM_STOP; }
@@ -333,27 +364,28 @@ SOLVE_FN int lm_step(LmState& S) {
 }
 
 // decide whether to stop, and if not compute the next candidate into S.cand
-SOLVE_FN int lm_propose(LmState& S) {
+template <bool REMAP = false>
+SOLVE_FN int lm_propose(LmState& S, const double* proj = nullptr) {
   if (S.termination == 4) return LM_STOP;
   if (S.iter >= S.max_iter) { S.termination = 0; return LM_STOP; }
   if (S.step_successful && S.gmax <= 1e-10) { S.termination = 1; return LM_STOP; }
   if (S.radius <= 1e-32) { S.termination = 5; return LM_STOP; }
-  return lm_step(S);
+  return lm_step<REMAP>(S, proj);
 }
 
 // lm_propose for a solver that evaluates candidates for their cost alone.  The stopping tests that read neither H nor g come first; LM_JAC asks
 // the caller for the normal equations at S.x (lm_load_eval) and another call; the remaining tests then run in lm_propose's order.  (jac_valid is
 // cleared only by a successful step, so after an unsuccessful one the radius test below is reached without an evaluation.)
 // SPECULATE: the candidate after a successful step is evaluated in full (LM_EVAL_FULL), so that adopting it costs no second pass.
-template <bool SPECULATE>
-SOLVE_FN int lm_propose_lazy(LmState& S) {
+template <bool SPECULATE, bool REMAP = false>
+SOLVE_FN int lm_propose_lazy(LmState& S, const double* proj = nullptr) {
   if (S.termination == 4) return LM_STOP;
   if (S.iter >= S.max_iter) { S.termination = 0; return LM_STOP; }
   if (!S.jac_valid) return LM_JAC;
   if (S.step_successful && S.gmax <= 1e-10) { S.termination = 1; return LM_STOP; }
   if (S.radius <= 1e-32) { S.termination = 5; return LM_STOP; }
   const int prev_successful = S.step_successful;
-  const int act = lm_step(S);
+  const int act = lm_step<REMAP>(S, proj);
   return (SPECULATE && act == LM_EVAL && prev_successful) ? LM_EVAL_FULL : act;
 }
 
@@ -399,14 +431,15 @@ SOLVE_FN int lm_consume_eval(LmState& S, const double* acc, bool full) {
 }
 // One turn of the control thread of lo_solve_t / lm_solve: take in the evaluation of `kind`, then propose until there is something to evaluate or
 // the solve has ended.  x0: the point of LM_EV_BEGIN.  FULL_EVAL: lm_propose, every candidate in full — call for call the solver before the split.
-template <bool FULL_EVAL, bool SPECULATE>
-SOLVE_FN int lm_control(LmState& S, int kind, const double* x0, const double* sums, int max_iter) {
+// REMAP, proj: lm_step's.
+template <bool FULL_EVAL, bool SPECULATE, bool REMAP = false>
+SOLVE_FN int lm_control(LmState& S, int kind, const double* x0, const double* sums, int max_iter, const double* proj = nullptr) {
   int act = LM_AGAIN;
   if (kind == LM_EV_BEGIN) lm_begin(S, x0, sums, max_iter);
   else if (kind == LM_EV_AGAIN) lm_begin_again(S, max_iter);
   else if (kind == LM_EV_JAC) lm_load_eval(S, sums);
   else act = lm_consume_eval(S, sums, kind == LM_EV_CAND_FULL);
-  while (act == LM_AGAIN) act = FULL_EVAL ? lm_propose(S) : lm_propose_lazy<SPECULATE>(S);
+  while (act == LM_AGAIN) act = FULL_EVAL ? lm_propose<REMAP>(S, proj) : lm_propose_lazy<SPECULATE, REMAP>(S, proj);
   return act;
 }
 // ... and the evaluation that answer asks for

@@ -60,6 +60,10 @@
 //       alego_reloc_enable builds the map's descriptors (R = max_range, default the library's); after the stream's first mapping frame
 //       alego_loc_relocalize with apply = 1 finds the place, verifies it by ICP and places the slot on the device.  The result is printed
 //       as one line "reloc: {...}"; loc_max_dev then covers the scans after the placement, and the JSON line gains "reloc_status".
+//   either source + --remap [EIG_MIN]
+//       alego_remap_enable: LaserMapping's registration holds the directions its first evaluation does not observe (eigenvalue below EIG_MIN,
+//       default 100) at the point the solve starts from.  Every key frame prints one line "remap: scan K status S n_held H
+//       eig_min E" (the smallest eigenvalue of the information matrix at the point the solve started from).
 //   either source + --regcov [--regcov-graph]
 //       alego_regcov_enable: every mapping frame leaves the covariance of its scan-to-map registration on the device.
 //       Every key frame prints one line "regcov: scan K status S rows R n_degenerate D eig_min E variance v0 .. v5" (the smallest eigenvalue of
@@ -73,6 +77,7 @@
 //   g++ -O2 -std=c++17 -Iinclude examples/replay.cpp -o examples/replay -La-lego-loam_amd -lalego_mi355x -lalego_synth
 //       -Wl,-rpath,'$ORIGIN/../a-lego-loam_amd'                                  (__graft_entry__.build() does this)
 #include <algorithm>
+#include <cctype>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -88,7 +93,8 @@ int main(int argc, char** argv) {
   std::string bag_path, topic = "/lslidar_point_cloud", map_dir;
   float map_leaf = 0.f;
   int map_frames = 4096, map_points = 1 << 24, loop_every = 0, close_every = 0, max_loops = 16;
-  bool list_only = false, standalone = false, localize = false, relocalize = false, appearance = false, merge = false, on_device = false, regcov = false, regcov_graph = false;
+  bool list_only = false, standalone = false, localize = false, relocalize = false, appearance = false, merge = false, on_device = false, regcov = false, regcov_graph = false, remap = false;
+  double remap_eig_min = 0.0;
   double gate_chi2 = -1.0, loc_radius = 0.0, reloc_range = 0.0, app_max_jump = 0.0, app_range = 0.0, loop_radius = 0.0, thin_dist = -1.0;
   long reloc_start = -1, align_start = -1;
   long max_scans = -1;
@@ -128,6 +134,7 @@ int main(int argc, char** argv) {
     else if (a == "--reloc-range") reloc_range = std::atof(val());
     else if (a == "--regcov") regcov = true;
     else if (a == "--regcov-graph") regcov = regcov_graph = true;
+    else if (a == "--remap") { remap = true; if (i + 1 < argc && (std::isdigit((unsigned char)argv[i + 1][0]) || argv[i + 1][0] == '.')) remap_eig_min = std::atof(argv[++i]); }
     else pos.push_back(argv[i]);
   }
   alego_bag* bag = nullptr;
@@ -178,6 +185,11 @@ int main(int argc, char** argv) {
   if (gate_chi2 >= 0.0 && loop_every <= 0) { std::fprintf(stderr, "--gate needs --loop-search EVERY\n"); alego_destroy(h); return 2; }
   if ((close_every > 0 || merge || gate_chi2 >= 0.0 || regcov_graph) && alego_graph_enable(h, merge ? std::max(max_loops, ALEGO_ALIGN_MAX_QUERIES) : max_loops, nullptr) != ALEGO_OK) {
     std::fprintf(stderr, "graph_enable: %s\n", alego_last_error(h)); alego_destroy(h); return 1;
+  }
+  if (remap) {
+    alego_remap_opts mo{};
+    mo.eig_min = remap_eig_min;
+    if (alego_remap_enable(h, &mo) != ALEGO_OK) { std::fprintf(stderr, "remap_enable: %s\n", alego_last_error(h)); alego_destroy(h); return 1; }
   }
   if (regcov) {   // after the graph: graph = 1 needs it, and var_min defaults to its odometry variances
     alego_regcov_opts ro{};
@@ -253,6 +265,12 @@ int main(int argc, char** argv) {
         if (alego_regcov_get(h, &slot, 1, &rc) != ALEGO_OK) { std::fprintf(stderr, "regcov_get: %s\n", alego_last_error(h)); alego_destroy(h); return 1; }
         std::printf("regcov: scan %ld status %d rows %d n_degenerate %d eig_min %.6g variance %.6g %.6g %.6g %.6g %.6g %.6g\n", k, rc.status, rc.n_edge + rc.n_plane,
                     rc.n_degenerate, rc.eigval[0], rc.variance[0], rc.variance[1], rc.variance[2], rc.variance[3], rc.variance[4], rc.variance[5]);
+      }
+      if (remap) {   // ... and which directions did it hold at its start?
+        const int32_t slot = 0;
+        alego_remap rm{};
+        if (alego_remap_get(h, &slot, 1, &rm) != ALEGO_OK) { std::fprintf(stderr, "remap_get: %s\n", alego_last_error(h)); alego_destroy(h); return 1; }
+        std::printf("remap: scan %ld status %d n_held %d eig_min %.6g\n", k, rm.status, rm.n_held, rm.eigval[0]);
       }
     }
     if (loop_every > 0 && (k + 1) % loop_every == 0) {

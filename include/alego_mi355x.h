@@ -566,6 +566,54 @@ int alego_regcov_normal_host(const double params6[6], const double* edge_rows9, 
  * handle's Huber delta, its options when the feature is on and the defaults otherwise; touches no slot */
 int alego_debug_regcov(alego_handle* h, const double params6[6], const double* edge_rows9, int32_t n_edge, const double* plane_rows7, int32_t n_plane, alego_regcov* out);
 
+/* ---- solution remapping: LaserMapping's registration holds degenerate directions at its start (csrc/remap_math.h) ----
+ * Opt-in per handle (SLAM and localising handles alike); without alego_remap_enable nothing is allocated or launched and lm_solve runs as it
+ * always did.  With it the solver kernel of a mapping frame is lm_solve_remap: from the 28 sums of its own first evaluation, at the point x0 the
+ * first outer solve starts from — params_ on entry, which is what the slot's last mapping frame left there (the reference's ceres problem
+ * keeps optimising one persistent params_; transformAssociateToMap's odometry prediction selects the map, it does not re-seed the solver) — it forms
+ *   info      N^T H N, N = M(x0)^-1 — the tangent space of alego_regcov above, so a direction held here is one alego_regcov would count
+ *   eigval    of info, ascending (ties by index), eigvec column k the unit vector of eigval[k] (the same cyclic Jacobi)
+ *   n_held    eigenvalues below eig_min (default 100, LeGO-LOAM's eignThre)
+ *   proj      P = N (sum over the kept k of v_k v_k^T) M, row-major, in PARAMETER space (x, y, z, roll, pitch, yaw); the exact identity when
+ *             nothing is held, exactly zero when everything is
+ * and every step of every iteration of every outer solve of that frame is replaced by S^-1 P S step (S the solver's Jacobi scaling) before the
+ * model cost change is formed: the cost change, the candidate, the step-size and the cost-change tests see the projected step; stopping rules,
+ * radius updates and the handling of invalid steps are unchanged, except that a projected step that is exactly zero (everything held) is not
+ * invalid — the candidate is the start, and the solve ends by the step-size test (termination 2) with the pose at x0.  A frame with
+ * n_held = 0 is solved bit for bit as without the mode.  Zhang, Kaess, Singh, "On degeneracy of optimization-based state estimation problems"
+ * (ICRA 2016); LOAM and LeGO-LOAM decide at iterCount == 0 likewise.
+ * Independent of alego_regcov_enable (both may be on: alego_regcov reports the final point as before).  Not available with a sharded
+ * registration: alego_remap_enable returns ALEGO_ERR_ARG after alego_dist_init, and alego_dist_init after it. */
+typedef struct alego_remap_opts {
+  double eig_min;          /* <= 0: the default */
+} alego_remap_opts;
+typedef struct alego_remap {
+  int32_t status;          /* 1 computed, 0 no registration in the slot's last mapping frame or fewer than 7 rows, -2 not finite, -3 |cos pitch| too small;
+                              with a status other than 1 nothing is held and every double below but `start` is 0 */
+  int32_t n_held, frame, pad;   /* frame: the slot's mapping-frame counter (lm_info LI_FRAME) the record belongs to */
+  double start[6] /* x0 */, eigval[6], eigvec[36] /* column k = vector of eigval[k] */, proj[36];
+} alego_remap;
+/* once, before the first scan reaches LaserMapping in any slot, else ALEGO_ERR_ARG; NULL or eig_min <= 0 = the default; ALEGO_ERR_ARG also for an
+ * eig_min that is not finite and for a sharded handle */
+int alego_remap_enable(alego_handle* h, const alego_remap_opts* opts);
+/* the records of the listed slots as the last mapping frame left them (status 0 before the first); synchronous, one copy for the whole list.
+ * ALEGO_ERR_ARG: feature off, a null argument, a slot out of range or listed twice */
+int alego_remap_get(alego_handle* h, const int32_t* slots, int32_t n, alego_remap* out);
+/* host twin of the kernel's 6x6 part (the same functions in the same order, csrc/remap_math.h): acc28 as for alego_regcov_host, params6 = x0;
+ * frame = 0.  Returns 0, or ALEGO_ERR_ARG for a null argument / a negative count / an eig_min that is not finite */
+int alego_remap_host(const double acc28[28], const double params6[6], int32_t n_edge, int32_t n_plane, const alego_remap_opts* opts, alego_remap* out);
+/* host twin of one step of the solver (lm_step, csrc/solve_rows.h) at x = 0: H21 the upper triangle of J^T J row by row, g6 = J^T r, scale6 the
+ * Jacobi scaling, radius the trust-region radius, proj36 = P or NULL (the plain step).  step6: the step in parameter space (the candidate),
+ * *mcc: the model cost change.  Returns 1 for a valid step, 0 for an invalid one (step6 and *mcc are then 0), ALEGO_ERR_ARG for a null argument */
+int alego_remap_step_host(const double H21[21], const double g6[6], const double scale6[6], double radius, const double* proj36, double step6[6], double* mcc);
+/* the solver kernel alone on given rows (rows as for alego_debug_regcov, p rounded to f32), from start6: remap = 0 lm_solve, 1 lm_solve_remap with
+ * the handle's eig_min (the default while the mode is off); ALEGO_SOLVE_FULL_EVAL selects the _full_eval twin of either; the handle's lm_max_iters,
+ * lm_outer_iters and Huber delta.  params_it[2][6], costs[4] (initial / final cost of both solves) and summary[2] (iterations | successful steps
+ * << 8 | termination << 16) are what a mapping frame leaves in lm_state and lm_info; rec (may be NULL; zeroed when remap = 0): the record.
+ * Touches no slot. */
+int alego_debug_remap_solve(alego_handle* h, const double start6[6], const double* edge_rows9, int32_t n_edge, const double* plane_rows7, int32_t n_plane,
+                            int32_t remap, double* params_it, double* costs, int32_t* summary, alego_remap* rec);
+
 /* ---- localisation: many streams against ONE frozen key-frame map -------------------------------------
  * A handle-wide mode, off by default (nothing of it is allocated or launched then).  alego_loc_enable hands the handle N key frames — pose
  * and sensor-frame clouds, exactly what alego_map_get_keyframe returns from a mapping run; from then on EVERY slot localises in that map.
