@@ -225,20 +225,28 @@ def regcov_opts(sigma0=0.0, scale=0.0, eig_min=0.0, lambda_rel_floor=0.0, var_mi
     return o
 
 
-def _regcov_out(r):
-    return dict(status=int(r.status), n_edge=int(r.n_edge), n_plane=int(r.n_plane), n_degenerate=int(r.n_degenerate), frame=int(r.frame),
-                cost=float(r.cost), sigma2=float(r.sigma2), info=np.array(r.info[:], np.float64).reshape(6, 6), eigval=np.array(r.eigval[:], np.float64),
-                eigvec=np.array(r.eigvec[:], np.float64).reshape(6, 6), cov=np.array(r.cov[:], np.float64).reshape(6, 6), variance=np.array(r.variance[:], np.float64))
+def _record_out(r, shapes):
+    """a record structure as a dict; shapes: field -> None (an int), () (a double) or the shape of an array of doubles"""
+    get = lambda v, sh: int(v) if sh is None else float(v) if sh == () else np.array(v[:], np.float64).reshape(sh)  # noqa: E731
+    return {f: get(getattr(r, f), sh) for f, sh in shapes.items()}
+
+
+def _record_host(name, Rec, shapes, acc28, params6, n_edge, n_plane, opts):
+    """a host twin's (acc28, params6, counts, opts) -> record call, the record as a dict"""
+    a, p = np.ascontiguousarray(acc28, np.float64).reshape(28), np.ascontiguousarray(params6, np.float64).reshape(6)
+    out = Rec()
+    rc = getattr(lib(), name)(a.ctypes.data, p.ctypes.data, int(n_edge), int(n_plane), None if opts is None else C.byref(opts), C.byref(out))
+    if rc != 0:
+        raise AlegoError(f"{name} failed ({rc})")
+    return _record_out(out, shapes)
+
+
+_REGCOV_SHAPES = dict(status=None, n_edge=None, n_plane=None, n_degenerate=None, frame=None, cost=(), sigma2=(), info=(6, 6), eigval=(6,), eigvec=(6, 6), cov=(6, 6), variance=(6,))
 
 
 def regcov_host(acc28, params6, n_edge, n_plane, opts=None):
     """alego_regcov_host (host only): the record of 28 normal-equation scalars at params6 as a dict"""
-    a, p = np.ascontiguousarray(acc28, np.float64).reshape(28), np.ascontiguousarray(params6, np.float64).reshape(6)
-    out = RegCov()
-    rc = lib().alego_regcov_host(a.ctypes.data, p.ctypes.data, int(n_edge), int(n_plane), None if opts is None else C.byref(opts), C.byref(out))
-    if rc != 0:
-        raise AlegoError(f"alego_regcov_host failed ({rc})")
-    return _regcov_out(out)
+    return _record_host("alego_regcov_host", RegCov, _REGCOV_SHAPES, acc28, params6, n_edge, n_plane, opts)
 
 
 def regcov_normal_host(params6, edge_rows9, plane_rows7, huber):
@@ -268,19 +276,12 @@ def remap_opts(eig_min=0.0):
     return o
 
 
-def _remap_out(r):
-    return dict(status=int(r.status), n_held=int(r.n_held), frame=int(r.frame), start=np.array(r.start[:], np.float64), eigval=np.array(r.eigval[:], np.float64),
-                eigvec=np.array(r.eigvec[:], np.float64).reshape(6, 6), proj=np.array(r.proj[:], np.float64).reshape(6, 6))
+_REMAP_SHAPES = dict(status=None, n_held=None, frame=None, start=(6,), eigval=(6,), eigvec=(6, 6), proj=(6, 6))
 
 
 def remap_host(acc28, params6, n_edge, n_plane, opts=None):
     """alego_remap_host (host only): the projector of 28 normal-equation scalars at params6 as a dict"""
-    a, p = np.ascontiguousarray(acc28, np.float64).reshape(28), np.ascontiguousarray(params6, np.float64).reshape(6)
-    out = Remap()
-    rc = lib().alego_remap_host(a.ctypes.data, p.ctypes.data, int(n_edge), int(n_plane), None if opts is None else C.byref(opts), C.byref(out))
-    if rc != 0:
-        raise AlegoError(f"alego_remap_host failed ({rc})")
-    return _remap_out(out)
+    return _record_host("alego_remap_host", Remap, _REMAP_SHAPES, acc28, params6, n_edge, n_plane, opts)
 
 
 def remap_step_host(H21, g6, scale6, radius, proj36=None):
@@ -1490,12 +1491,16 @@ class Handle:
         """alego_regcov_enable: opts = regcov_opts(...) or None for the defaults; before the first scan reaches LaserMapping"""
         self._check(lib().alego_regcov_enable(self._h, None if opts is None else C.byref(opts)), "alego_regcov_enable")
 
+    def _records_get(self, name, Rec, shapes, slots):
+        """a slot-list *_get: one record dict per listed slot"""
+        sl, n = _slot_list(slots)
+        out = (Rec * max(n, 1))()
+        self._check(getattr(lib(), name)(self._h, sl.ctypes.data, n, out), name)
+        return [_record_out(r, shapes) for r in out[:n]]
+
     def regcov_get(self, slots=(0,)):
         """alego_regcov_get: one dict per listed slot (status, n_edge, n_plane, n_degenerate, frame, cost, sigma2, info, eigval, eigvec, cov, variance)"""
-        sl, n = _slot_list(slots)
-        out = (RegCov * max(n, 1))()
-        self._check(lib().alego_regcov_get(self._h, sl.ctypes.data, n, out), "alego_regcov_get")
-        return [_regcov_out(r) for r in out[:n]]
+        return self._records_get("alego_regcov_get", RegCov, _REGCOV_SHAPES, slots)
 
     def remap_enable(self, opts=None):
         """alego_remap_enable: opts = remap_opts(eig_min) or None for the default; before the first scan reaches LaserMapping"""
@@ -1503,10 +1508,7 @@ class Handle:
 
     def remap_get(self, slots=(0,)):
         """alego_remap_get: one dict per listed slot (status, n_held, frame, start, eigval, eigvec, proj)"""
-        sl, n = _slot_list(slots)
-        out = (Remap * max(n, 1))()
-        self._check(lib().alego_remap_get(self._h, sl.ctypes.data, n, out), "alego_remap_get")
-        return [_remap_out(r) for r in out[:n]]
+        return self._records_get("alego_remap_get", Remap, _REMAP_SHAPES, slots)
 
     def debug_remap_solve(self, start6, edge_rows9, plane_rows7, remap=1):
         """alego_debug_remap_solve: the solver kernel alone (remap = 0: lm_solve, 1: lm_solve_remap) on rows (a, b, p) (n, 9) and (n, d, p) (m, 7) from
@@ -1516,7 +1518,7 @@ class Handle:
         pit, costs, summ, rec = np.zeros((2, 6)), np.zeros(4), np.zeros(2, np.int32), Remap()
         self._check(lib().alego_debug_remap_solve(self._h, p.ctypes.data, e.ctypes.data if len(e) else None, len(e), s.ctypes.data if len(s) else None, len(s), int(remap),
                                                   pit.ctypes.data, costs.ctypes.data, summ.ctypes.data, C.byref(rec)), "alego_debug_remap_solve")
-        return dict(params_it=pit, costs=costs, iterations=summ & 0xFF, successful=(summ >> 8) & 0xFF, termination=summ >> 16, rec=_remap_out(rec))
+        return dict(params_it=pit, costs=costs, iterations=summ & 0xFF, successful=(summ >> 8) & 0xFF, termination=summ >> 16, rec=_record_out(rec, _REMAP_SHAPES))
 
     def debug_regcov(self, params6, edge_rows9, plane_rows7):
         """alego_debug_regcov: lm_regcov alone on rows (a, b, p) (n, 9) and (n, d, p) (m, 7) at params6 (p is rounded to f32)"""
@@ -1525,7 +1527,7 @@ class Handle:
         out = RegCov()
         self._check(lib().alego_debug_regcov(self._h, p.ctypes.data, e.ctypes.data if len(e) else None, len(e), s.ctypes.data if len(s) else None, len(s), C.byref(out)),
                     "alego_debug_regcov")
-        return _regcov_out(out)
+        return _record_out(out, _REGCOV_SHAPES)
 
     def dist_init(self, rank, world, unique_id: bytes):
         self._check(lib().alego_dist_init(self._h, rank, world, C.create_string_buffer(unique_id, DIST_ID_BYTES)), "alego_dist_init")

@@ -1348,25 +1348,33 @@ int alego_regcov_normal_host(const double params6[6], const double* edge_rows9, 
   regcov_normal_host(params6, edge_rows9, n_edge, plane_rows7, n_plane, huber, acc28);
   return 0;
 }
+// Caller rows as lm_fit leaves a slot (lm_rows.h), for the two debug entries below: block records of the edges from row 0 and of the planes from
+// row nqc (nqc >= n_edge corner queries, those past n_edge without a row), and the query points as f32; no vector is empty.
+static void stage_caller_rows(const double* edge_rows9, int n_edge, const double* plane_rows7, int n_plane, int nqc, std::vector<double>* blocks, std::vector<float>* qc,
+                              std::vector<float>* qs) {
+  const size_t nqs = (size_t)std::max(n_plane, 1);
+  blocks->assign(((size_t)nqc + nqs) * LMB_W, 0.0);
+  qc->assign(std::max<size_t>((size_t)nqc, 1) * 4, 0.f);
+  qs->assign(nqs * 4, 0.f);
+  for (int i = 0; i < n_edge; ++i) {
+    const double* r = edge_rows9 + (size_t)i * 9;
+    lmb_put_edge(&(*blocks)[lm_row_of(0, i, nqc) * LMB_W], r, r + 3);
+    for (int k = 0; k < 3; ++k) (*qc)[(size_t)i * 4 + k] = (float)r[6 + k];
+  }
+  for (int i = 0; i < n_plane; ++i) {
+    const double* r = plane_rows7 + (size_t)i * 7;
+    lmb_put_plane(&(*blocks)[lm_row_of(1, i, nqc) * LMB_W], r, r[3]);
+    for (int k = 0; k < 3; ++k) (*qs)[(size_t)i * 4 + k] = (float)r[4 + k];
+  }
+}
 int alego_debug_regcov(alego_handle* h, const double params6[6], const double* edge_rows9, int32_t n_edge, const double* plane_rows7, int32_t n_plane, alego_regcov* out) {
   ALEGO_GATE(h);
   if (!params6 || !out || n_edge < 0 || n_plane < 0 || (n_edge > 0 && !edge_rows9) || (n_plane > 0 && !plane_rows7)) { h->err = "alego_debug_regcov: null argument / negative count"; return ALEGO_ERR_ARG; }
   double opt[RC_OPT_W];
   (void)lm_host_regcov_opts(h->lm, opt);
-  // block records as lm_fit leaves them (lm_rows.h), the planes' rows from n_edge, and the query points as f32
-  const size_t nr = (size_t)n_edge + (size_t)n_plane;
-  std::vector<double> blocks(std::max<size_t>(nr, 1) * LMB_W, 0.0);
-  std::vector<float> qc(std::max<size_t>((size_t)n_edge, 1) * 4, 0.f), qs(std::max<size_t>((size_t)n_plane, 1) * 4, 0.f);
-  for (int i = 0; i < n_edge; ++i) {
-    const double* r = edge_rows9 + (size_t)i * 9;
-    lmb_put_edge(&blocks[lm_row_of(0, i, n_edge) * LMB_W], r, r + 3);
-    for (int k = 0; k < 3; ++k) qc[(size_t)i * 4 + k] = (float)r[6 + k];
-  }
-  for (int i = 0; i < n_plane; ++i) {
-    const double* r = plane_rows7 + (size_t)i * 7;
-    lmb_put_plane(&blocks[lm_row_of(1, i, n_edge) * LMB_W], r, r[3]);
-    for (int k = 0; k < 3; ++k) qs[(size_t)i * 4 + k] = (float)r[4 + k];
-  }
+  std::vector<double> blocks;
+  std::vector<float> qc, qs;
+  stage_caller_rows(edge_rows9, n_edge, plane_rows7, n_plane, n_edge, &blocks, &qc, &qs);
   DevPool T;   // temporaries of this call
   double *db, *dp, *dopt;
   float4 *dqc, *dqs;
@@ -1420,19 +1428,10 @@ int alego_debug_remap_solve(alego_handle* h, const double start6[6], const doubl
   const alego_params& P = h->d.P;
   const int nqc = std::max({(int)n_edge, P.lm_min_corner, 1}), nqs = n_plane;
   const size_t nr = (size_t)nqc + (size_t)std::max(nqs, 1);
-  std::vector<double> blocks(nr * LMB_W, 0.0), ld(LD_COUNT, 0.0);
-  std::vector<float> qc((size_t)nqc * 4, 0.f), qs((size_t)std::max(nqs, 1) * 4, 0.f);
+  std::vector<double> blocks, ld(LD_COUNT, 0.0);
+  std::vector<float> qc, qs;
   std::vector<int> li(LI_COUNT, 0);
-  for (int i = 0; i < n_edge; ++i) {
-    const double* r = edge_rows9 + (size_t)i * 9;
-    lmb_put_edge(&blocks[lm_row_of(0, i, nqc) * LMB_W], r, r + 3);
-    for (int k = 0; k < 3; ++k) qc[(size_t)i * 4 + k] = (float)r[6 + k];
-  }
-  for (int i = 0; i < n_plane; ++i) {
-    const double* r = plane_rows7 + (size_t)i * 7;
-    lmb_put_plane(&blocks[lm_row_of(1, i, nqc) * LMB_W], r, r[3]);
-    for (int k = 0; k < 3; ++k) qs[(size_t)i * 4 + k] = (float)r[4 + k];
-  }
+  stage_caller_rows(edge_rows9, n_edge, plane_rows7, n_plane, nqc, &blocks, &qc, &qs);
   li[LI_RUN] = 1; li[LI_NKF] = 1; li[LI_REC_CNT] = 1; li[LI_NCUR_C] = nqc; li[LI_NTOTAL_DS] = nqs;
   li[LI_NTOTAL] = std::max(nqs, P.lm_min_surf); li[LI_KDS_C] = std::max(1, P.lm_min_map_corner);
   for (int k = 0; k < 6; ++k) ld[LD_PARAMS + k] = start6[k];

@@ -803,6 +803,42 @@ DEV_INLINE double rc_eigen_lanes(double A, int i, int j, double lam[6], const Sh
   return shfl(V, i * 6 + src);
 }
 
+// The spectrum of a registration on wave 0 (rc_spectrum of reg_cov_math.h, entry by entry; lane, l, i, j as above): the one front of rc_tail and rm_tail and the
+// owner of their guards.  t6: rc_trig's six values at p (pose_terms_coop's table of the evaluation at p holds them, by the very calls rc_trig makes).  Returns the
+// status; with 1, s_N holds N = M(p)^-1 and info, vs, lam[6], vi[6], vj[6] are this lane's entry of N^T H N, its entry of the sorted eigenvectors, the eigenvalues
+// ascending and rows i and j of the sorted eigenvectors.  (lm_solve_remap sits at its 256 VGPRs: the caller passes the lane index through an opaque move, N goes to
+// LDS through a select — 36 doubles in registers at a time — fenced by sched_barriers from what follows, and the shuffle is a template parameter: ShflDirect there.)
+template <class Shfl>
+DEV_INLINE int rc_front_lanes(const double* s_out /* LDS [28] */, const double* t6, const double* p, int n_edge, int n_plane, double* s_N /* LDS [36] */, int lane, int i, int j,
+                              const Shfl& shfl, double* info, double* vs, double lam[6], double vi[6], double vj[6]) {
+  if (n_edge + n_plane <= 6) return 0;
+  if (fabs(t6[3]) < RC_COS_PITCH_MIN) return -3;
+  {   // N = M^-1 into LDS (an entry of info indexes it by lane; a private array indexed that way would live in scratch)
+    double N[36];
+    rc_minv_t(t6, N);
+    double v = 0.0;
+#pragma unroll
+    for (int k = 0; k < 36; ++k) v = lane == k ? N[k] : v;
+    if (lane < 36) s_N[lane] = v;
+    __threadfence_block();
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  *info = rc_info_entry(s_out, s_N, i < j ? i : j, i < j ? j : i);
+  const bool bad = !rc_finite(*info) || (lane < 28 && !rc_finite(s_out[lane])) || (lane < 6 && !rc_finite(p[lane]));
+  if (__any(bad)) return -2;
+  __builtin_amdgcn_sched_barrier(0);
+  *vs = rc_eigen_lanes(*info, i, j, lam, shfl);
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) { vi[k] = shfl(*vs, i * 6 + k); vj[k] = shfl(*vs, j * 6 + k); }
+  return 1;
+}
+// wave 0: a record without a result — its `count` doubles from `dv` zero but for the first `keep` of `head` (null: none); header(): lane 0 writes the ints
+template <class Header> DEV_INLINE void rec_store_empty(double* dv, int count, const double* head, int keep, int lane, Header&& header) {
+  for (int k = lane; k < count; k += 64) dv[k] = k < keep ? head[k] : 0.0;
+  if (lane == 0) header();
+}
+
 // ---- solution remapping (alego_remap_enable; remap_math.h) ------------------------------------------------------------
 // The projector of a mapping frame from the 28 sums of the solver's own first evaluation, on wave 0 between that evaluation and the control
 // thread's first turn; it stays in LDS for every iteration of every outer solve of the frame.
@@ -814,19 +850,16 @@ struct RmLds {
   alego_remap* rec;
   int on, first, n_edge, n_plane, frame;   // first: the frame's first evaluation has not been taken in yet
 };
-static_assert(offsetof(alego_remap, start) == 16 && sizeof(alego_remap) == 16 + 84 * sizeof(double), "rm_store_empty walks the record's doubles from `start`");
+static_assert(offsetof(alego_remap, start) == 16 && sizeof(alego_remap) == 16 + 84 * sizeof(double), "rm_empty hands rec_store_empty the record's doubles from `start`");
 template <bool REMAP> DEV_INLINE RmLds* rm_lds() {
   if constexpr (REMAP) { __shared__ RmLds R; return &R; }
   else return nullptr;
 }
-// wave 0: a record without a result (nothing is held)
-DEV_INLINE void rm_store_empty(alego_remap* rec, int status, int frame, const double* x0, int lane) {
-  double* dv = rec->start;
-  for (int k = lane; k < 84; k += 64) dv[k] = k < 6 ? x0[k] : 0.0;
-  if (lane == 0) { rec->status = status; rec->n_held = 0; rec->frame = frame; rec->pad = 0; }
-}
-// wave 0, all 64 lanes active, lane 6 i + j owning entry (i, j) as in rc_tail.  The operations and their order are rm_compute's, entry by entry.
-// s_trig: pose_terms_coop's table of the evaluation at x0 — entries 6 .. 11 are cos, sin of roll, pitch, yaw by the very calls rc_trig makes.
+// the record's ints (lane 0), and wave 0's record without a result: nothing is held, `start` is kept
+DEV_INLINE void rm_header(alego_remap* rec, int status, int n_held, int frame) { rec->status = status; rec->n_held = n_held; rec->frame = frame; rec->pad = 0; }
+DEV_INLINE void rm_empty(alego_remap* rec, int status, int frame, const double* x0, int lane) { rec_store_empty(rec->start, 84, x0, 6, lane, [&] { rm_header(rec, status, 0, frame); }); }
+// wave 0, all 64 lanes active, lane 6 i + j owning entry (i, j): the projector tail of rc_front_lanes.  The operations and their order are rm_compute's,
+// entry by entry.  s_trig: pose_terms_coop's table of the evaluation at x0 — entries 6 .. 11 are cos, sin of roll, pitch, yaw by the very calls rc_trig makes.
 DEV_INLINE void rm_tail(const double* s_out /* LDS [28] */, const double* s_trig /* LDS [12] */, RmLds& R, const double* x0, int n_edge, int n_plane, int frame, double eig_min, alego_remap* rec) {
   // (the lane index through an opaque move: everything below that depends on the lane alone — shuffle indices, entry selects — is invariant in the
   // solver's loops, and hoisted out of them it stays in ~50 registers through the evaluations, which costs the kernel a wavefront per SIMD)
@@ -835,18 +868,12 @@ DEV_INLINE void rm_tail(const double* s_out /* LDS [28] */, const double* s_trig
   const int l = lane < 36 ? lane : 35, i = l / 6, j = l - 6 * i;
   const double t6[6] = {s_trig[7], s_trig[6], s_trig[9], s_trig[8], s_trig[11], s_trig[10]};   // rc_trig's order
   if (lane == 0) { R.on = 0; R.first = 0; }   // (once per frame)
-  if (n_edge + n_plane <= 6) { rm_store_empty(rec, 0, frame, x0, lane); return; }
-  if (fabs(t6[3]) < RC_COS_PITCH_MIN) { rm_store_empty(rec, -3, frame, x0, lane); return; }
-  {   // N = M^-1 and M into LDS: entries of info and of P index them by lane (one after the other: 36 doubles in registers at a time)
-    double N[36];
-    rc_minv_t(t6, N);
-    double v = 0.0;
-#pragma unroll
-    for (int k = 0; k < 36; ++k) v = lane == k ? N[k] : v;
-    if (lane < 36) R.N[lane] = v;
-  }
+  double info, vs, lam[6], vi[6], vj[6], col[6];
+  const ShflDirect shfl;
+  const int st = rc_front_lanes(s_out, t6, x0, n_edge, n_plane, R.N, lane, i, j, shfl, &info, &vs, lam, vi, vj);
+  if (st != 1) { rm_empty(rec, st, frame, x0, lane); return; }
   __builtin_amdgcn_sched_barrier(0);
-  {
+  {   // M into LDS, as N went: entries of P index it by lane (after N, not with it: 36 doubles in registers at a time)
     double M[36];
     rc_m_t(t6, M);
     double v = 0.0;
@@ -856,16 +883,6 @@ DEV_INLINE void rm_tail(const double* s_out /* LDS [28] */, const double* s_trig
     __threadfence_block();
   }
   __builtin_amdgcn_sched_barrier(0);
-  const double info = rc_info_entry(s_out, R.N, i < j ? i : j, i < j ? j : i);
-  bool bad = !rc_finite(info) || (lane < 28 && !rc_finite(s_out[lane])) || (lane < 6 && !rc_finite(x0[lane]));
-  if (__any(bad)) { rm_store_empty(rec, -2, frame, x0, lane); return; }
-  double lam[6], vi[6], vj[6], col[6];
-  __builtin_amdgcn_sched_barrier(0);
-  const ShflDirect shfl;
-  const double vs = rc_eigen_lanes(info, i, j, lam, shfl);
-  __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-  for (int k = 0; k < 6; ++k) { vi[k] = shfl(vs, i * 6 + k); vj[k] = shfl(vs, j * 6 + k); }
   const double pt = rm_pt_entry(vi, vj, lam, eig_min);
 #pragma unroll
   for (int a = 0; a < 6; ++a) {   // (Pt M)(a, j) for the six a of this lane's column
@@ -877,18 +894,19 @@ DEV_INLINE void rm_tail(const double* s_out /* LDS [28] */, const double* s_trig
   }
   int held = 0;
   double lam_j = 0.0;
+  bool bad = false;
 #pragma unroll
   for (int k = 0; k < 6; ++k) { bad = bad || !rc_finite(lam[k]); held += rm_kept(lam[k], eig_min) ? 0 : 1; lam_j = j == k ? lam[k] : lam_j; }
   const double pe = rm_p_entry(R.N, i, col);
   const double P = held == 0 ? (i == j ? 1.0 : 0.0) : (held == 6 ? 0.0 : pe);
   bad = bad || !rc_finite(vs) || !rc_finite(P);
-  if (__any(bad)) { rm_store_empty(rec, -2, frame, x0, lane); return; }
+  if (__any(bad)) { rm_empty(rec, -2, frame, x0, lane); return; }
   if (lane < 36) {
     R.P[l] = P; rec->eigvec[l] = vs; rec->proj[l] = P;
     if (i == 0) rec->eigval[j] = lam_j;
   }
   if (lane < 6) rec->start[lane] = x0[lane];
-  if (lane == 0) { rec->status = 1; rec->n_held = held; rec->frame = frame; rec->pad = 0; R.on = held > 0 ? 1 : 0; }
+  if (lane == 0) { rm_header(rec, 1, held, frame); R.on = held > 0 ? 1 : 0; }
   __threadfence_block();
 }
 // wg_solve's hook (dev_cost.h): the decomposition behind the first evaluation of the frame, the projector for every step after it
@@ -921,7 +939,7 @@ DEV_INLINE void lm_solve_body(const DevCtx& d, const LmCtx& L) {
   double* ld = ldp(L, slot);
   if (lm_reg_skipped(li, P)) {
     if (threadIdx.x == 0) lm_store_skipped(li);
-    if constexpr (REMAP) { if (threadIdx.x < 64) rm_store_empty(L.rm_rec + slot, 0, li[LI_FRAME], ld + LD_PARAMS, threadIdx.x); }
+    if constexpr (REMAP) { if (threadIdx.x < 64) rm_empty(L.rm_rec + slot, 0, li[LI_FRAME], ld + LD_PARAMS, threadIdx.x); }
     return;
   }
   extern __shared__ __attribute__((aligned(16))) unsigned char lm_smem[];
@@ -943,7 +961,7 @@ DEV_INLINE void lm_solve_body(const DevCtx& d, const LmCtx& L) {
       RmLds& Rm = *rm_lds<REMAP>();
       Rm.eig_min = L.rm_eig_min; Rm.rec = L.rm_rec + slot; Rm.n_edge = W.Rc; Rm.n_plane = W.Rs; Rm.frame = li[LI_FRAME]; Rm.on = 0; Rm.first = 1;
     }
-    if (R == 0 && threadIdx.x < 64) rm_store_empty(L.rm_rec + slot, 0, li[LI_FRAME], ld + LD_PARAMS, threadIdx.x);   // (no solve: the record of fewer than 7 rows)
+    if (R == 0 && threadIdx.x < 64) rm_empty(L.rm_rec + slot, 0, li[LI_FRAME], ld + LD_PARAMS, threadIdx.x);   // (no solve: the record of fewer than 7 rows)
   }
   for (int outer = 0; outer < P.lm_outer_iters; ++outer) {  // :360 — identical correspondences both times
     if (R == 0) {
@@ -984,57 +1002,39 @@ struct RcSrc {
   int nqc, nqs, surf_row0;   // query i of the nqc + nqs: row lm_row_of_query(i, nqc, surf_row0)
   const double* params;      // p[6]
 };
-static_assert(offsetof(alego_regcov, cost) == 24 && sizeof(alego_regcov) == 24 + 122 * sizeof(double), "rc_store_empty walks the record's doubles from `cost`");
+static_assert(offsetof(alego_regcov, cost) == 24 && sizeof(alego_regcov) == 24 + 122 * sizeof(double), "rc_empty hands rec_store_empty the record's doubles from `cost`");
 
-// wave 0: a record without a result
-DEV_INLINE void rc_store_empty(alego_regcov* rec, int status, int n_edge, int n_plane, int frame) {
-  double* dv = &rec->cost;
-  for (int k = threadIdx.x; k < 122; k += 64) dv[k] = 0.0;
-  if (threadIdx.x == 0) { rec->status = status; rec->n_edge = n_edge; rec->n_plane = n_plane; rec->n_degenerate = 0; rec->frame = frame; rec->pad = 0; }
+// the record's ints (lane 0), and wave 0's record without a result
+DEV_INLINE void rc_header(alego_regcov* rec, int status, int n_edge, int n_plane, int n_degenerate, int frame) {
+  rec->status = status; rec->n_edge = n_edge; rec->n_plane = n_plane; rec->n_degenerate = n_degenerate; rec->frame = frame; rec->pad = 0;
 }
+DEV_INLINE void rc_empty(alego_regcov* rec, int st, int n_edge, int n_plane, int frame) { rec_store_empty(&rec->cost, 122, nullptr, 0, threadIdx.x, [&] { rc_header(rec, st, n_edge, n_plane, 0, frame); }); }
 
-// wave 0, all 64 lanes active.  Lane 6 i + j owns entry (i, j) of info, of the Jacobi iterate A, of the eigenvectors V and of cov (lanes 36 .. 63
-// shadow lane 35 and store nothing); a rotation fetches its partners with wave shuffles, every lane forms (c, s) from the same three entries.
-// The operations and their order are rc_compute's (reg_cov_math.h), entry by entry.
-DEV_INLINE void rc_tail(const double* s_out /* LDS [28] */, double* s_N /* LDS [36] */, const double* p,int n_edge, int n_plane, int frame, const double* opt, alego_regcov* rec) {
+// wave 0, all 64 lanes active.  Lane 6 i + j owns entry (i, j) of info, of the eigenvectors and of cov (lanes 36 .. 63 shadow lane 35 and store
+// nothing): the covariance tail of rc_front_lanes.  The operations and their order are rc_compute's (reg_cov_math.h), entry by entry.
+// s_trig: pose_terms_coop's table of the evaluation at p, as for rm_tail.
+DEV_INLINE void rc_tail(const double* s_out /* LDS [28] */, const double* s_trig, double* s_N /* LDS [36] */, const double* p, int n_edge, int n_plane, int frame, const double* opt, alego_regcov* rec) {
   const int lane = threadIdx.x, l = lane < 36 ? lane : 35, i = l / 6, j = l - 6 * i;
-  const int rows = n_edge + n_plane;
-  double p6[6];
+  const double t6[6] = {s_trig[7], s_trig[6], s_trig[9], s_trig[8], s_trig[11], s_trig[10]};   // rc_trig's order
+  double info, vs, lam[6], w[6], vi[6], vj[6];
+  const int st = rc_front_lanes(s_out, t6, p, n_edge, n_plane, s_N, lane, i, j, ShflHip{}, &info, &vs, lam, vi, vj);
+  if (st != 1) { rc_empty(rec, st, n_edge, n_plane, frame); return; }
+  const double s2 = rc_sigma2(s_out[27], n_edge + n_plane, opt[RC_SIGMA0]);
 #pragma unroll
-  for (int k = 0; k < 6; ++k) p6[k] = p[k];
-  if (rows <= 6) { rc_store_empty(rec, 0, n_edge, n_plane, frame); return; }
-  if (fabs(cos(p6[4])) < RC_COS_PITCH_MIN) { rc_store_empty(rec, -3, n_edge, n_plane, frame); return; }
-  {   // N = M^-1 into LDS (an entry of info indexes it by lane; a private array indexed that way would live in scratch)
-    double N[36];
-    rc_minv(p6, N);
-#pragma unroll
-    for (int k = 0; k < 36; ++k) if (lane == k) s_N[k] = N[k];
-    __threadfence_block();
-  }
-  const double info = rc_info_entry(s_out, s_N, i < j ? i : j, i < j ? j : i);
-  bool bad = !rc_finite(info) || (lane < 28 && !rc_finite(s_out[lane])) || (lane < 6 && !rc_finite(p[lane]));
-  if (__any(bad)) { rc_store_empty(rec, -2, n_edge, n_plane, frame); return; }
-  double lam[6], w[6], vi[6], vj[6];
-  const double vs = rc_eigen_lanes(info, i, j, lam, ShflHip{});
-  const double s2 = rc_sigma2(s_out[27], rows, opt[RC_SIGMA0]);
-#pragma unroll
-  for (int k = 0; k < 6; ++k) { w[k] = rc_weight(lam[k], lam[5], opt[RC_LAMBDA_FLOOR]); vi[k] = __shfl(vs, i * 6 + k); vj[k] = __shfl(vs, j * 6 + k); }
+  for (int k = 0; k < 6; ++k) w[k] = rc_weight(lam[k], lam[5], opt[RC_LAMBDA_FLOOR]);
   const double cv = s2 * rc_cov_entry(vi, vj, w);
-  bad = !rc_finite(s2) || !rc_finite(vs) || !rc_finite(cv);
+  bool bad = !rc_finite(s2) || !rc_finite(vs) || !rc_finite(cv);
   int ndeg = 0;
   double lam_j = 0.0;
 #pragma unroll
   for (int k = 0; k < 6; ++k) { bad = bad || !rc_finite(lam[k]); ndeg += lam[k] < opt[RC_EIG_MIN] ? 1 : 0; lam_j = j == k ? lam[k] : lam_j; }
-  if (__any(bad)) { rc_store_empty(rec, -2, n_edge, n_plane, frame); return; }
+  if (__any(bad)) { rc_empty(rec, -2, n_edge, n_plane, frame); return; }
   if (lane < 36) {
     rec->info[l] = info; rec->eigvec[l] = vs; rec->cov[l] = cv;
     if (i == 0) rec->eigval[j] = lam_j;
     if (i == j) rec->variance[i] = rc_clamp(opt[RC_SCALE] * cv, opt[RC_VAR_MIN + i], opt[RC_VAR_MAX + i]);
   }
-  if (lane == 0) {
-    rec->status = 1; rec->n_edge = n_edge; rec->n_plane = n_plane; rec->n_degenerate = ndeg; rec->frame = frame; rec->pad = 0;
-    rec->cost = s_out[27]; rec->sigma2 = s2;
-  }
+  if (lane == 0) { rc_header(rec, 1, n_edge, n_plane, ndeg, frame); rec->cost = s_out[27]; rec->sigma2 = s2; }
 }
 
 template <int T>
@@ -1058,7 +1058,7 @@ DEV_INLINE void rc_body(const RcSrc& S, double huber, const double* opt, int fra
   WgClock<false> ck;
   wg_evaluate<T, 3, true>(S.params, s_trig, s_acc, s_out, rows, ck);   // (ends with a barrier: the counts are complete)
   if (tid >= 64) return;
-  rc_tail(s_out, s_N, S.params, s_n[0], s_n[1], frame, opt, rec);
+  rc_tail(s_out, s_trig, s_N, S.params, s_n[0], s_n[1], frame, opt, rec);
 }
 
 // grid (slots), between the solver and lm_finish (which overwrites LD_PARAMS with the f32 key pose when it saves a frame).  A slot without a mapping
@@ -1068,7 +1068,7 @@ __global__ void __launch_bounds__(LM_SOLVE_T) lm_regcov(DevCtx d, LmCtx L) {
   const int* li = lip(L, slot);
   if (!li[LI_RUN]) return;
   alego_regcov* rec = L.rc_rec + slot;
-  if (!li[LI_OPTIMIZED]) { if (threadIdx.x < 64) rc_store_empty(rec, 0, 0, 0, li[LI_FRAME]); return; }
+  if (!li[LI_OPTIMIZED]) { if (threadIdx.x < 64) rc_empty(rec, 0, 0, 0, li[LI_FRAME]); return; }
   const RcSrc S{lm_blocks_of(L, slot), L.cur_corner_ds + (size_t)slot * L.kf_cap_c, L.cur_total_ds + (size_t)slot * L.total_cap,
                 li[LI_NCUR_C], li[LI_NTOTAL_DS], L.kf_cap_c, ldp(L, slot) + LD_PARAMS};
   rc_body<LM_SOLVE_T>(S, d.P.huber_delta, L.rc_opt, li[LI_FRAME], rec);

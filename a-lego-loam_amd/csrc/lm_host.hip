@@ -996,7 +996,29 @@ int lm_host_graph_enable(LmHost* lm, int max_loops, const double* odom_var6, std
   return 0;
 }
 
-// ---- covariance of the registration (alego_regcov_*; lm_regcov in kernels_lm.hip) ----
+// ---- the two opt-in siblings of the registration: its covariance (alego_regcov_*; lm_regcov in kernels_lm.hip) and solution remapping (alego_remap_*; lm_solve_remap) ----
+// What both *_enable calls refuse, in the order they refuse it: on twice, a sharded handle, bad_options (the feature's own refusal of its options, or
+// null: it comes before the state of the slots), a scan that has reached LaserMapping, a ring that is not empty.
+static int lm_feature_preconditions(LmHost* lm, const char* what, bool on, const char* bad_options, std::string* err) {
+  if (on) { *err = std::string(what) + ": already enabled"; return ALEGO_ERR_ARG; }
+  if (lm->comm || lm->L.shard_world > 0) { *err = std::string(what) + ": not available on a handle with a sharded registration (alego_dist_init)"; return ALEGO_ERR_ARG; }
+  if (bad_options) { *err = bad_options; return ALEGO_ERR_ARG; }
+  for (long f : lm->frames) if (f != 0) { *err = std::string(what) + ": call it before the first scan reaches LaserMapping"; return ALEGO_ERR_ARG; }
+  return rings_empty(lm, what, true, err);
+}
+// What both *_get calls do — one copy: the records of slots [lo, hi] of the list, picked apart on the host.  what: the call, enable: the call that turns it on.
+template <class Rec> static int lm_records_get(LmHost* lm, const char* what, const char* enable, bool on, const Rec* dev_records, const int* slots, int n, Rec* out, std::string* err) {
+  if (!on) { *err = std::string(what) + ": the feature is off (" + enable + ")"; return ALEGO_ERR_ARG; }
+  if (int r = gate_slot_list(what, slots, n, lm->n_slots, true, err)) return r;
+  if (n == 0) return 0;
+  const int lo = *std::min_element(slots, slots + n), hi = *std::max_element(slots, slots + n);
+  for (hipStream_t s : lm->st) if (hipStreamSynchronize(s) != hipSuccess) { *err = std::string(what) + ": a stream failed"; return ALEGO_ERR_HIP; }
+  std::vector<Rec> tmp((size_t)(hi - lo + 1));
+  if (hipMemcpy(tmp.data(), dev_records + lo, tmp.size() * sizeof(Rec), hipMemcpyDeviceToHost) != hipSuccess) { *err = std::string(what) + ": device read failed"; return ALEGO_ERR_HIP; }
+  for (int i = 0; i < n; ++i) out[i] = tmp[(size_t)(slots[i] - lo)];
+  return 0;
+}
+
 static const double kOdomVarDefault[6] = {1e-6, 1e-6, 1e-6, 1e-8, 1e-8, 1e-6};   // laserMapping.cpp:68-70, the default of lm_host_graph_enable
 bool lm_host_regcov_opts(LmHost* lm, double* opt16) {
   if (lm && lm->rc_on) { std::memcpy(opt16, lm->rc_opt, sizeof(lm->rc_opt)); return true; }
@@ -1006,16 +1028,11 @@ bool lm_host_regcov_opts(LmHost* lm, double* opt16) {
 int lm_host_regcov_enable(LmHost* lm, const alego_regcov_opts* opts, std::string* err) {
   static_assert(offsetof(alego_regcov_opts, graph) == RC_OPT_W * sizeof(double), "rc_resolve reads the options' doubles in the RC_* order");
   LmCtx& L = lm->L;
-  if (lm->rc_on) { *err = "alego_regcov_enable: already enabled"; return ALEGO_ERR_ARG; }
-  if (lm->comm || L.shard_world > 0) { *err = "alego_regcov_enable: not available on a handle with a sharded registration (alego_dist_init)"; return ALEGO_ERR_ARG; }
   const bool graph = opts && opts->graph != 0;
-  if (graph && L.pg_loops_cap <= 0) { *err = "alego_regcov_enable: graph = 1 needs the key-pose graph (alego_graph_enable first)"; return ALEGO_ERR_ARG; }
   double opt[RC_OPT_W];
-  if (rc_resolve(opts ? &opts->sigma0 : nullptr, L.pg_loops_cap > 0 ? L.pg_odom_var : kOdomVarDefault, opt)) {
-    *err = "alego_regcov_enable: an option is not finite, or var_min exceeds var_max"; return ALEGO_ERR_ARG;
-  }
-  for (long f : lm->frames) if (f != 0) { *err = "alego_regcov_enable: call it before the first scan reaches LaserMapping"; return ALEGO_ERR_ARG; }
-  if (int r = rings_empty(lm, "alego_regcov_enable", true, err)) return r;
+  const char* bad = graph && L.pg_loops_cap <= 0 ? "alego_regcov_enable: graph = 1 needs the key-pose graph (alego_graph_enable first)"
+                    : rc_resolve(opts ? &opts->sigma0 : nullptr, L.pg_loops_cap > 0 ? L.pg_odom_var : kOdomVarDefault, opt) ? "alego_regcov_enable: an option is not finite, or var_min exceeds var_max" : nullptr;
+  if (int r = lm_feature_preconditions(lm, "alego_regcov_enable", lm->rc_on, bad, err)) return r;
   LmCtx T = L;
   double* dopt = nullptr;
   if (!A(lm, &T.rc_rec, (size_t)lm->n_slots, err) || !A(lm, &dopt, (size_t)RC_OPT_W, err)) return ALEGO_ERR_HIP;
@@ -1026,30 +1043,17 @@ int lm_host_regcov_enable(LmHost* lm, const alego_regcov_opts* opts, std::string
   lm->rc_on = true;
   return 0;
 }
-// one copy: the records of slots [lo, hi] of the list, picked apart on the host
 int lm_host_regcov_get(LmHost* lm, const int* slots, int n, alego_regcov* out, std::string* err) {
-  if (!lm->rc_on) { *err = "alego_regcov_get: the feature is off (alego_regcov_enable)"; return ALEGO_ERR_ARG; }
-  if (int r = gate_slot_list("alego_regcov_get", slots, n, lm->n_slots, true, err)) return r;
-  if (n == 0) return 0;
-  const int lo = *std::min_element(slots, slots + n), hi = *std::max_element(slots, slots + n);
-  for (hipStream_t s : lm->st) if (hipStreamSynchronize(s) != hipSuccess) { *err = "alego_regcov_get: a stream failed"; return ALEGO_ERR_HIP; }
-  std::vector<alego_regcov> tmp((size_t)(hi - lo + 1));
-  if (hipMemcpy(tmp.data(), lm->L.rc_rec + lo, tmp.size() * sizeof(alego_regcov), hipMemcpyDeviceToHost) != hipSuccess) { *err = "alego_regcov_get: device read failed"; return ALEGO_ERR_HIP; }
-  for (int i = 0; i < n; ++i) out[i] = tmp[(size_t)(slots[i] - lo)];
-  return 0;
+  return lm_records_get(lm, "alego_regcov_get", "alego_regcov_enable", lm->rc_on, lm->L.rc_rec, slots, n, out, err);
 }
 bool lm_host_regcov_on(LmHost* lm) { return lm->rc_on; }
 
-// ---- solution remapping (alego_remap_*; lm_solve_remap in kernels_lm.hip) ----
 double lm_host_remap_eig_min(LmHost* lm) { return lm && lm->rm_on ? lm->L.rm_eig_min : RC_DEFAULT_EIG_MIN; }
 int lm_host_remap_enable(LmHost* lm, const alego_remap_opts* opts, std::string* err) {
   LmCtx& L = lm->L;
-  if (lm->rm_on) { *err = "alego_remap_enable: already enabled"; return ALEGO_ERR_ARG; }
-  if (lm->comm || L.shard_world > 0) { *err = "alego_remap_enable: not available on a handle with a sharded registration (alego_dist_init)"; return ALEGO_ERR_ARG; }
   double eig_min;
-  if (rm_resolve(opts ? &opts->eig_min : nullptr, &eig_min)) { *err = "alego_remap_enable: eig_min is not finite"; return ALEGO_ERR_ARG; }
-  for (long f : lm->frames) if (f != 0) { *err = "alego_remap_enable: call it before the first scan reaches LaserMapping"; return ALEGO_ERR_ARG; }
-  if (int r = rings_empty(lm, "alego_remap_enable", true, err)) return r;
+  const char* bad = rm_resolve(opts ? &opts->eig_min : nullptr, &eig_min) ? "alego_remap_enable: eig_min is not finite" : nullptr;
+  if (int r = lm_feature_preconditions(lm, "alego_remap_enable", lm->rm_on, bad, err)) return r;
   LmCtx T = L;
   if (!A(lm, &T.rm_rec, (size_t)lm->n_slots, err)) return ALEGO_ERR_HIP;
   T.rm_eig_min = eig_min;
@@ -1058,15 +1062,7 @@ int lm_host_remap_enable(LmHost* lm, const alego_remap_opts* opts, std::string* 
   return 0;
 }
 int lm_host_remap_get(LmHost* lm, const int* slots, int n, alego_remap* out, std::string* err) {
-  if (!lm->rm_on) { *err = "alego_remap_get: the feature is off (alego_remap_enable)"; return ALEGO_ERR_ARG; }
-  if (int r = gate_slot_list("alego_remap_get", slots, n, lm->n_slots, true, err)) return r;
-  if (n == 0) return 0;
-  const int lo = *std::min_element(slots, slots + n), hi = *std::max_element(slots, slots + n);
-  for (hipStream_t s : lm->st) if (hipStreamSynchronize(s) != hipSuccess) { *err = "alego_remap_get: a stream failed"; return ALEGO_ERR_HIP; }
-  std::vector<alego_remap> tmp((size_t)(hi - lo + 1));
-  if (hipMemcpy(tmp.data(), lm->L.rm_rec + lo, tmp.size() * sizeof(alego_remap), hipMemcpyDeviceToHost) != hipSuccess) { *err = "alego_remap_get: device read failed"; return ALEGO_ERR_HIP; }
-  for (int i = 0; i < n; ++i) out[i] = tmp[(size_t)(slots[i] - lo)];
-  return 0;
+  return lm_records_get(lm, "alego_remap_get", "alego_remap_enable", lm->rm_on, lm->L.rm_rec, slots, n, out, err);
 }
 
 // Frames of the slots with mask[slot] != 0 (mask_dev: the same words on the device) go through kf_tmp_* and the key-frame sort jobs, oldest first, one

@@ -13,7 +13,8 @@
 //   cov       sigma2 V diag(1 / max(lambda_k, floor * lambda_max)) V^T, entry (i, j) as sum_k (V_ik V_jk) w_k in ascending k: the products
 //             commute, so cov is symmetric to the last bit
 // Status: 1 computed; 0 fewer than 7 rows; -3 |cos pitch| < RC_COS_PITCH_MIN (E is singular there, as the solver's own Euler parameterisation is);
-// -2 an input or a result is not finite.  With a status other than 1 every double of the record is zero.
+// -2 an input or a result is not finite.  With a status other than 1 every double of the record is zero.  The first three guards and the order
+// belong to rc_spectrum, the front this header shares with remap_math.h; rc_compute adds only the finite check of its own results.
 #ifndef ALEGO_REG_COV_MATH_H_
 #define ALEGO_REG_COV_MATH_H_
 #include <math.h>
@@ -132,7 +133,7 @@ RC_FN bool rc_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }   /
 
 // The cyclic Jacobi of a symmetric 6x6 A (row-major, overwritten: its diagonal ends as the eigenvalues) with V <- V G for every rotation G
 // (V = I on entry: the eigenvectors by columns).  *sweeps (optional) is advanced by the sweeps in which a rotation was made.  The one loop of the
-// host twins (rc_compute; rm_compute, remap_math.h); the kernels run the same rotations entry by entry on 36 lanes.
+// host twins (rc_spectrum); the kernels run the same rotations entry by entry on 36 lanes.
 RC_FN void rc_jacobi(double* A, double* V, int* sweeps) {
   double B[36];
   for (int sweep = 0; sweep < RC_SWEEPS_MAX; ++sweep) {
@@ -164,36 +165,44 @@ RC_FN void rc_sort(const double* A, const double* V, double* lam, double* Vs) {
   for (int k = 0; k < 6; ++k) { const int r = rc_rank(d, k); lam[r] = d[k]; for (int i = 0; i < 6; ++i) Vs[i * 6 + r] = V[i * 6 + k]; }
 }
 
-// The record as plain arrays (the host twin; the kernel does the same entry by entry on 36 lanes).  Returns the status; *sweeps (optional):
-// sweeps in which a rotation was made.
+// The spectrum of a registration: the one front of the host twins (rc_compute; rm_compute, remap_math.h) and the owner of their guards, in this order:
+// fewer than 7 rows -> 0; |cos pitch| < RC_COS_PITCH_MIN -> -3; an input or an entry of info not finite -> -2; else 1 with N = M(p)^-1, the unrotated
+// info = N^T H N, lam[6] ascending and the eigenvectors Vs sorted likewise (nothing is to be read with another status).  *sweeps (optional, zeroed by the
+// caller) is advanced by the sweeps in which a rotation was made.  The kernels run the same, entry by entry, in rc_front_lanes (kernels_lm.hip).
+RC_FN int rc_spectrum(const double* acc, const double* p, int n_edge, int n_plane, double* N, double* info, double* lam, double* Vs, int* sweeps) {
+  if (n_edge + n_plane <= 6) return 0;
+  if (fabs(cos(p[4])) < RC_COS_PITCH_MIN) return -3;
+  bool bad = false;
+  for (int k = 0; k < 28; ++k) bad = bad || !rc_finite(acc[k]);
+  for (int k = 0; k < 6; ++k) bad = bad || !rc_finite(p[k]);
+  double A[36], V[36];
+  rc_minv(p, N);
+  for (int i = 0; i < 6; ++i)
+    for (int j = i; j < 6; ++j) { const double v = rc_info_entry(acc, N, i, j); A[i * 6 + j] = v; A[j * 6 + i] = v; }
+  for (int k = 0; k < 36; ++k) { bad = bad || !rc_finite(A[k]); V[k] = (k % 7 == 0) ? 1.0 : 0.0; }
+  if (bad) return -2;
+  for (int k = 0; k < 36; ++k) info[k] = A[k];
+  rc_jacobi(A, V, sweeps);
+  rc_sort(A, V, lam, Vs);
+  return 1;
+}
+
+// The record as plain arrays (the host twin; the kernel does the same entry by entry on 36 lanes): the covariance tail of rc_spectrum.  Returns the
+// status; *sweeps (optional): sweeps in which a rotation was made.
 RC_FN int rc_compute(const double* acc, const double* p, int n_edge, int n_plane, const double* opt, double* sigma2, double* info, double* eigval, double* eigvec,
                      double* cov, double* variance, int* n_degenerate, int* sweeps) {
   *sigma2 = 0.0; *n_degenerate = 0;
   if (sweeps) *sweeps = 0;
   for (int k = 0; k < 36; ++k) { info[k] = 0.0; eigvec[k] = 0.0; cov[k] = 0.0; }
   for (int k = 0; k < 6; ++k) { eigval[k] = 0.0; variance[k] = 0.0; }
-  const int rows = n_edge + n_plane;
-  if (rows <= 6) return 0;
-  if (fabs(cos(p[4])) < RC_COS_PITCH_MIN) return -3;
-  bool bad = false;
-  for (int k = 0; k < 28; ++k) bad = bad || !rc_finite(acc[k]);
-  for (int k = 0; k < 6; ++k) bad = bad || !rc_finite(p[k]);
-  double N[36], A[36], V[36];
-  rc_minv(p, N);
-  for (int i = 0; i < 6; ++i)
-    for (int j = i; j < 6; ++j) { const double v = rc_info_entry(acc, N, i, j); A[i * 6 + j] = v; A[j * 6 + i] = v; }
-  for (int k = 0; k < 36; ++k) { bad = bad || !rc_finite(A[k]); V[k] = (k % 7 == 0) ? 1.0 : 0.0; }
-  if (bad) return -2;
-  double inf0[36];
-  for (int k = 0; k < 36; ++k) inf0[k] = A[k];
-  rc_jacobi(A, V, sweeps);
-  double lam[6], Vs[36], w[6], cv[36];
-  rc_sort(A, V, lam, Vs);
-  const double s2 = rc_sigma2(acc[27], rows, opt[RC_SIGMA0]);
+  double N[36], inf0[36], lam[6], Vs[36], w[6], cv[36];
+  const int st = rc_spectrum(acc, p, n_edge, n_plane, N, inf0, lam, Vs, sweeps);
+  if (st != 1) return st;
+  const double s2 = rc_sigma2(acc[27], n_edge + n_plane, opt[RC_SIGMA0]);
   for (int k = 0; k < 6; ++k) w[k] = rc_weight(lam[k], lam[5], opt[RC_LAMBDA_FLOOR]);
   for (int i = 0; i < 6; ++i)
     for (int j = 0; j < 6; ++j) cv[i * 6 + j] = s2 * rc_cov_entry(Vs + i * 6, Vs + j * 6, w);
-  bad = !rc_finite(s2);
+  bool bad = !rc_finite(s2);
   for (int k = 0; k < 36; ++k) bad = bad || !rc_finite(Vs[k]) || !rc_finite(cv[k]);
   for (int k = 0; k < 6; ++k) bad = bad || !rc_finite(lam[k]);
   if (bad) return -2;

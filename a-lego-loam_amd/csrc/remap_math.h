@@ -13,7 +13,8 @@
 //             from 0.0, step_i = u_i / scale_i (rm_project_step), before the model cost change is formed
 // n_held == 0: P is the exact identity and the solver is told nothing is held (its step is not touched); n_held == 6: P is exactly zero.
 // Status: 1 computed; 0 fewer than 7 rows; -3 |cos pitch| < RC_COS_PITCH_MIN; -2 an input or a result is not finite.  With a status other than 1
-// nothing is held and every double of the result is zero.
+// nothing is held and every double of the result is zero.  The first three guards, their order and the tie rule are rc_spectrum's (reg_cov_math.h),
+// the front alego_regcov shares: n_held here and n_degenerate there cannot disagree at equal eig_min.
 #ifndef ALEGO_REMAP_MATH_H_
 #define ALEGO_REMAP_MATH_H_
 #include "reg_cov_math.h"
@@ -65,26 +66,16 @@ RC_UNROLL
   for (int i = 0; i < 6; ++i) step[i] = u[i] / scale[i];
 }
 
-// The decomposition as plain arrays (the host twin; the kernel does the same entry by entry on 36 lanes).  Returns the status.
+// The decomposition as plain arrays (the host twin; the kernel does the same entry by entry on 36 lanes): the projector tail of rc_spectrum
+// (reg_cov_math.h), which owns the guards.  Returns the status.
 RC_FN int rm_compute(const double* acc, const double* p, int n_edge, int n_plane, double eig_min, double* eigval, double* eigvec, double* proj, int* n_held) {
   *n_held = 0;
   for (int k = 0; k < 36; ++k) { eigvec[k] = 0.0; proj[k] = 0.0; }
   for (int k = 0; k < 6; ++k) eigval[k] = 0.0;
-  if (n_edge + n_plane <= 6) return 0;
-  if (fabs(cos(p[4])) < RC_COS_PITCH_MIN) return -3;
-  bool bad = false;
-  for (int k = 0; k < 28; ++k) bad = bad || !rc_finite(acc[k]);
-  for (int k = 0; k < 6; ++k) bad = bad || !rc_finite(p[k]);
-  double N[36], M[36], A[36], V[36];
-  rc_minv(p, N);
+  double N[36], M[36], info[36], lam[6], Vs[36], Pt[36], PtM[36], P[36];
+  const int st = rc_spectrum(acc, p, n_edge, n_plane, N, info, lam, Vs, nullptr);
+  if (st != 1) return st;
   rc_m(p, M);
-  for (int i = 0; i < 6; ++i)
-    for (int j = i; j < 6; ++j) { const double v = rc_info_entry(acc, N, i, j); A[i * 6 + j] = v; A[j * 6 + i] = v; }
-  for (int k = 0; k < 36; ++k) { bad = bad || !rc_finite(A[k]); V[k] = (k % 7 == 0) ? 1.0 : 0.0; }
-  if (bad) return -2;
-  rc_jacobi(A, V, nullptr);
-  double lam[6], Vs[36], Pt[36], PtM[36], P[36];
-  rc_sort(A, V, lam, Vs);
   int held = 0;
   for (int k = 0; k < 6; ++k) held += rm_kept(lam[k], eig_min) ? 0 : 1;
   for (int i = 0; i < 6; ++i)
@@ -98,6 +89,7 @@ RC_FN int rm_compute(const double* acc, const double* p, int n_edge, int n_plane
       const double v = rm_p_entry(N, i, col);
       P[i * 6 + j] = held == 0 ? (i == j ? 1.0 : 0.0) : (held == 6 ? 0.0 : v);
     }
+  bool bad = false;
   for (int k = 0; k < 36; ++k) bad = bad || !rc_finite(Vs[k]) || !rc_finite(P[k]);
   for (int k = 0; k < 6; ++k) bad = bad || !rc_finite(lam[k]);
   if (bad) return -2;

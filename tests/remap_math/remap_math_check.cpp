@@ -3,7 +3,9 @@
 //     when everything is, every status, and nothing held with a status other than 1;
 //  2. lm_step<true> with proj = null against lm_step<false>, bit for bit, over many states;
 //  3. whole solves under the projection: the solver that evaluates every point in full against lm_control in both candidate policies and in its
-//     FULL_EVAL mode, bit for bit, and the shift M0 (x_final - x0) . v_held of every held direction of every problem.
+//     FULL_EVAL mode, bit for bit, and the shift M0 (x_final - x0) . v_held of every held direction of every problem;
+//  4. the front remap_math.h shares with reg_cov_math.h (rc_spectrum): rc_compute and rm_compute on the same inputs at the guards' edges and at
+//     repeated eigenvalues — equal statuses, the same bits in eigval and eigvec, n_degenerate == n_held.
 // Built by tests/test_remap_math.py with -ffp-contract=off and AddressSanitizer + UBSan as a program of its own.
 #include <cstdint>
 #include <cstdio>
@@ -267,8 +269,85 @@ static void check_plain_step() {
   }
 }
 
+// rc_compute and rm_compute are two tails of one front (rc_spectrum, reg_cov_math.h): on the same (acc28, p, counts) and the same eig_min the statuses
+// are equal, eigval and eigvec are the same bits and n_degenerate == n_held — at the guards' edges, where a copy of the front could drift from the other
+static int g_front_cases = 0;
+static void same_front(const char* what, const double* acc, const double* p, int n_edge, int n_plane, double eig_min, int want_status) {
+  const double var_min[6] = {1e-12, 1e-12, 1e-12, 1e-12, 1e-12, 1e-12};
+  double opt[RC_OPT_W], s2, info[36], lc[6], Vc[36], cov[36], var[6], lm[6], Vm[36], Pm[36];
+  int ndeg = -1, held = -2, sweeps = -1;
+  CHECK(rc_resolve(nullptr, var_min, opt) == 0, "%s: options", what);
+  opt[RC_EIG_MIN] = eig_min;
+  const int sc = rc_compute(acc, p, n_edge, n_plane, opt, &s2, info, lc, Vc, cov, var, &ndeg, &sweeps);
+  const int sm = rm_compute(acc, p, n_edge, n_plane, eig_min, lm, Vm, Pm, &held);
+  CHECK(sc == sm && sc == want_status, "%s: status %d (regcov) %d (remap), expected %d", what, sc, sm, want_status);
+  CHECK(ndeg == held, "%s: n_degenerate %d, n_held %d", what, ndeg, held);
+  for (int k = 0; k < 6; ++k) CHECK(same_bits(lc[k], lm[k]), "%s: eigval[%d] %.17g / %.17g", what, k, lc[k], lm[k]);
+  for (int k = 0; k < 36; ++k) CHECK(same_bits(Vc[k], Vm[k]), "%s: eigvec[%d] %.17g / %.17g", what, k, Vc[k], Vm[k]);
+  if (sc == 1) { int n = 0; for (int k = 0; k < 6; ++k) n += lc[k] < eig_min; CHECK(n == held, "%s: %d eigenvalues below eig_min, %d held", what, n, held); }
+  ++g_front_cases;
+}
+static void check_shared_front() {
+  const double truth[6] = {0.3, -0.2, 0.05, 0.01, -0.02, 0.4};
+  const Problem well = make_problem(2, truth, 0), corridor = make_problem(0, truth, 6);
+  double acc[28], cor[28];
+  well.full(truth, acc);
+  corridor.full(truth, cor);
+  // the fixtures of this program: everything observed; a corridor that does not observe translation along it
+  same_front("courtyard", acc, truth, 40 * 2, 120 * 4, 10.0, 1);
+  same_front("corridor", cor, truth, 40, 120 * 3 + 6, 100.0, 1);
+  { double lam[6], V[36], Pm[36]; int held = 0; CHECK(rm_compute(cor, truth, 40, 366, 100.0, lam, V, Pm, &held) == 1 && held >= 1, "the corridor holds %d", held); }
+  // the row-count edge
+  same_front("six rows", acc, truth, 3, 3, 10.0, 0);
+  same_front("seven rows", acc, truth, 3, 4, 10.0, 1);
+  // the two neighbouring pitches whose |cos| straddle RC_COS_PITCH_MIN (cos moves by about one ulp of the pitch per ulp of the pitch there: no
+  // double has a cosine closer to the bound on either side)
+  double below[6], above[6];
+  for (int k = 0; k < 6; ++k) below[k] = above[k] = truth[k];
+  double a = acos(RC_COS_PITCH_MIN);
+  while (fabs(cos(a)) < RC_COS_PITCH_MIN) a = nextafter(a, 0.0);
+  while (!(fabs(cos(a)) < RC_COS_PITCH_MIN)) a = nextafter(a, 2.0);   // a: the first pitch past the bound
+  below[4] = a; above[4] = nextafter(a, 0.0);
+  CHECK(fabs(cos(below[4])) < RC_COS_PITCH_MIN && !(fabs(cos(above[4])) < RC_COS_PITCH_MIN), "pitches %.17g %.17g do not straddle the bound", below[4], above[4]);
+  same_front("|cos pitch| just below the bound", acc, below, 100, 100, 10.0, -3);
+  same_front("|cos pitch| just at or above the bound", acc, above, 100, 100, 10.0, 1);
+  below[4] = -below[4]; above[4] = -above[4];
+  same_front("|cos pitch| just below the bound, pitch < 0", acc, below, 100, 100, 10.0, -3);
+  same_front("|cos pitch| just at or above the bound, pitch < 0", acc, above, 100, 100, 10.0, 1);
+  // a NaN and an infinity in the sums and in the pose (the row and pitch guards come first: six rows with a NaN is status 0, pitch NaN is -2)
+  for (int where = 0; where < 4; ++where)
+    for (int inf = 0; inf < 2; ++inf) {
+      double b[28], q[6];
+      for (int k = 0; k < 28; ++k) b[k] = acc[k];
+      for (int k = 0; k < 6; ++k) q[k] = truth[k];
+      const double v = inf ? (where % 2 ? -INFINITY : INFINITY) : NAN;
+      if (where == 0) b[7] = v; else if (where == 1) b[27] = v; else if (where == 2) q[1] = v; else q[4] = v;
+      same_front(inf ? "an infinity" : "a NaN", b, q, 100, 100, 10.0, -2);
+      if (where == 0) same_front("six rows and a value that is not finite", b, q, 6, 0, 10.0, 0);
+    }
+  // repeated eigenvalues, p = 0 (N is a permutation: info is H with its halves exchanged): a diagonal H, where the Jacobi makes no rotation and
+  // the order is the tie rule's alone, and 4 I + u u^T, whose eigenvalue 4 has multiplicity five; eig_min between, at, and beside the values
+  const double zero[6] = {0, 0, 0, 0, 0, 0}, u[6] = {1, -2, 0.5, 3, -1, 2};
+  double diag[28] = {0}, rank1[28] = {0};
+  const double d[6] = {5, 2, 5, 2, 9, 2};
+  for (int i = 0, k = 0; i < 6; ++i)
+    for (int j = i; j < 6; ++j, ++k) { diag[k] = i == j ? d[i] : 0.0; rank1[k] = (i == j ? 4.0 : 0.0) + u[i] * u[j]; }
+  diag[27] = rank1[27] = 0.5;
+  for (double eig_min : {1.0, 2.0, 3.0, 5.0, 7.0, 100.0}) { same_front("a diagonal H with ties", diag, zero, 50, 50, eig_min, 1); same_front("4 I + u u^T", rank1, zero, 50, 50, eig_min, 1); }
+  {
+    double lam[6], V[36], Pm[36];
+    int held = 0;
+    CHECK(rm_compute(diag, zero, 50, 50, 3.0, lam, V, Pm, &held) == 1 && held == 3, "diagonal ties: %d held", held);
+    const double want[6] = {2, 2, 2, 5, 5, 9};
+    const int col[6] = {0, 2, 4, 3, 5, 1};   // info = diag(2, 9, 2, 5, 2, 5): ascending, ties by index
+    for (int k = 0; k < 6; ++k) { CHECK(same_bits(lam[k], want[k]), "diagonal ties: eigval[%d] %.17g", k, lam[k]); for (int i = 0; i < 6; ++i) CHECK(same_bits(V[i * 6 + k], i == col[k] ? 1.0 : 0.0), "diagonal ties: eigvec(%d, %d) %.17g", i, k, V[i * 6 + k]); }
+  }
+  std::printf("shared front: %d inputs through rc_compute and rm_compute\n", g_front_cases);
+}
+
 int main() {
   check_statuses();
+  check_shared_front();
   check_plain_step();
   check_projector_and_solves();
   if (g_fail) { std::printf("%d checks failed\n", g_fail); return 1; }

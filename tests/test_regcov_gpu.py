@@ -14,9 +14,9 @@ import pytest
 
 import pose_graph_ref as R
 import regcov_ref as ref
-from alego_amd import binding, synth
+from alego_amd import binding
 from test_reg_cov_math import deviations
-from util import assert_bit_equal
+from util import assert_bit_equal, assert_same_record, lm_observables as _observables, reg_params as _params, reg_rows_of_frame, reg_scan as _scan
 
 F32 = np.float32
 LI_NKF, LI_RUN, LI_FRAME, LI_FLAGS, LI_NCC, LI_NSC, LI_OPTIMIZED, LI_NCUR_C, LI_NTOTAL_DS, LI_REC_CNT = 0, 2, 4, 5, 6, 7, 11, 19, 23, 26
@@ -30,28 +30,8 @@ ODOM_VAR = np.array([1e-4, 1e-4, 1e-4, 1e-3, 1e-3, 1e-3])   # of the graph tests
 N_SCANS = 16
 
 
-def _params(**kw):
-    p = synth.default_params(16, 1800)
-    p.min_keyframe_dist = 0.03   # (squared) the synthetic platform moves 0.2 m per mapping frame: every one of them saves a key frame
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
-
-
-_SCANS = {}
-
-
-def _scan(k, stream=0):
-    if (k, stream) not in _SCANS:
-        _SCANS[(k, stream)] = synth.scan(_params(), k, stream)
-    return _SCANS[(k, stream)]
-
-
 def _same_record(a, b, what):
-    for k in REC_INTS:
-        assert a[k] == b[k], (what, k, a[k], b[k])
-    for k in REC_FLOATS:
-        assert_bit_equal(np.asarray(a[k]), np.asarray(b[k]), f"{what}: {k}")
+    assert_same_record(a, b, what, REC_INTS, REC_FLOATS)
 
 
 def _dev(got, want):
@@ -124,17 +104,7 @@ def test_kernel_statuses(plain_handle):
 # ---- 4. mapping frames of the synthetic stream, everything on (the run's archive is also the map of 8) -----------------------------
 def _rows_of_frame(h, slot=0):
     """the accepted rows of the slot's last mapping frame as lm_fit left them, and the solver's final point"""
-    p = h.params
-    gi = h.debug_get("lm_info", slot=slot)
-    kf_cap_c = p.n_less_sharp * p.n_sectors * p.n_scan
-    blocks = h.debug_get("lm_blocks", slot=slot).reshape(-1, 8)
-    qc, qs = h.debug_get("lm_corner_ds", slot=slot), h.debug_get("lm_surf_total_ds", slot=slot)
-    assert len(qc) == gi[LI_NCUR_C] and len(qs) == gi[LI_NTOTAL_DS]
-    bc, bs = blocks[:len(qc)], blocks[kf_cap_c:kf_cap_c + len(qs)]
-    mc, ms = bc[:, 7] == 2.0, bs[:, 7] == 3.0
-    assert ((bc[:, 7] == 0.0) | mc).all() and ((bs[:, 7] == 0.0) | ms).all()
-    E = np.concatenate([bc[mc, 0:6], qc[mc, :3].astype(np.float64)], 1)
-    S = np.concatenate([bs[ms, 0:3], bs[ms, 6:7], qs[ms, :3].astype(np.float64)], 1)
+    gi, E, S = reg_rows_of_frame(h, slot)
     x = h.debug_get("lm_state", slot=slot)[LD_PARAMS_IT + 6:LD_PARAMS_IT + 12]
     return gi, x, E, S
 
@@ -196,11 +166,6 @@ def test_mapping_frames_against_numpy(stream_log):
 
 
 # ---- 5. nothing else moves -------------------------------------------------------------------------------------------------------
-def _observables(h, slot):
-    return dict(info=h.debug_get("lm_info", slot=slot), state=h.debug_get("lm_state", slot=slot), keyposes=h.debug_get("lm_keyposes", slot=slot),
-                cmap=h.debug_get("lm_corner_map_ds", slot=slot), smap=h.debug_get("lm_surf_map_ds", slot=slot), window=h.debug_get("lm_window", slot=slot))
-
-
 @pytest.mark.gpu
 def test_nothing_else_moves():
     p = _params()

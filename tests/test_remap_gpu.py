@@ -20,8 +20,8 @@ import pytest
 
 import regcov_ref as ref
 import remap_ref as rr
-from alego_amd import binding, synth
-from util import assert_bit_equal
+from alego_amd import binding
+from util import assert_bit_equal, assert_same_record, lm_observables as _observables, reg_params as _params, reg_rows_of_frame as _rows_of_frame, reg_scan as _scan
 
 LI_NKF, LI_RUN, LI_FRAME, LI_FLAGS, LI_NCC, LI_NSC, LI_SUM0, LI_SUM1, LI_OPTIMIZED, LI_NCUR_C, LI_NTOTAL_DS, LI_REC_CNT = 0, 2, 4, 5, 6, 7, 8, 9, 11, 19, 23, 26
 LD_PARAMS_IT, LD_COSTS = 27, 39
@@ -32,28 +32,8 @@ REC_FLOATS = ("start", "eigval", "eigvec", "proj")
 N_SCANS = 14
 
 
-def _params(**kw):
-    p = synth.default_params(16, 1800)
-    p.min_keyframe_dist = 0.03   # (squared) the synthetic platform moves 0.2 m per mapping frame: every one of them saves a key frame
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
-
-
-_SCANS = {}
-
-
-def _scan(k, stream=0):
-    if (k, stream) not in _SCANS:
-        _SCANS[(k, stream)] = synth.scan(_params(), k, stream)
-    return _SCANS[(k, stream)]
-
-
 def _same_record(a, b, what):
-    for k in ("status", "n_held", "frame"):
-        assert a[k] == b[k], (what, k, a[k], b[k])
-    for k in REC_FLOATS:
-        assert_bit_equal(np.asarray(a[k]), np.asarray(b[k]), f"{what}: {k}")
+    assert_same_record(a, b, what, ("status", "n_held", "frame"), REC_FLOATS)
 
 
 def _same_solve(a, b, what):
@@ -184,21 +164,6 @@ def test_kernel_statuses(debug_handles):
 
 
 # ---- 2. mapping frames of the synthetic stream ---------------------------------------------------------------------------------------
-def _rows_of_frame(h, slot=0):
-    """the accepted rows of the slot's last mapping frame as lm_fit left them"""
-    p = h.params
-    gi = h.debug_get("lm_info", slot=slot)
-    kf_cap_c = p.n_less_sharp * p.n_sectors * p.n_scan
-    blocks = h.debug_get("lm_blocks", slot=slot).reshape(-1, 8)
-    qc, qs = h.debug_get("lm_corner_ds", slot=slot), h.debug_get("lm_surf_total_ds", slot=slot)
-    assert len(qc) == gi[LI_NCUR_C] and len(qs) == gi[LI_NTOTAL_DS]
-    bc, bs = blocks[:len(qc)], blocks[kf_cap_c:kf_cap_c + len(qs)]
-    mc, ms = bc[:, 7] == 2.0, bs[:, 7] == 3.0
-    E = np.concatenate([bc[mc, 0:6], qc[mc, :3].astype(np.float64)], 1)
-    S = np.concatenate([bs[ms, 0:3], bs[ms, 6:7], qs[ms, :3].astype(np.float64)], 1)
-    return gi, E, S
-
-
 def _run_stream(h, n=N_SCANS, regcov=False):
     log = []
     for k in range(n):
@@ -261,11 +226,6 @@ def test_mapping_frames_against_numpy(stream_log):
 
 
 # ---- 3. nothing else moves -----------------------------------------------------------------------------------------------------------
-def _observables(h, slot):
-    return dict(info=h.debug_get("lm_info", slot=slot), state=h.debug_get("lm_state", slot=slot), keyposes=h.debug_get("lm_keyposes", slot=slot),
-                cmap=h.debug_get("lm_corner_map_ds", slot=slot), smap=h.debug_get("lm_surf_map_ds", slot=slot), window=h.debug_get("lm_window", slot=slot))
-
-
 @pytest.mark.gpu
 def test_nothing_else_moves_when_nothing_is_held():
     p = _params()

@@ -1656,3 +1656,53 @@ def run_merge_scene_oracle(o, scene, name):
         for raw_name, ds_name, leaf in (("lm_corner_map", "lm_corner_map_ds", P["lm_leaf_corner"]), ("lm_surf_map", "lm_surf_map_ds", P["lm_leaf_surf"])):
             assert_bit_equal(o.get(ds_name), voxel_grid_np(o.get(raw_name), leaf), f"{name} frame {i}: {ds_name} vs the numpy VoxelGrid")
     return facts
+
+
+# ---- the opt-in siblings of LaserMapping's registration (tests/test_regcov_gpu.py, tests/test_remap_gpu.py) ----------------------------------------
+
+LI_NCUR_C, LI_NTOTAL_DS = 19, 23
+
+
+def reg_params(**kw):
+    p = synth.default_params(16, 1800)
+    p.min_keyframe_dist = 0.03   # (squared) the synthetic platform moves 0.2 m per mapping frame: every one of them saves a key frame
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+_REG_SCANS = {}
+
+
+def reg_scan(k, stream=0):
+    if (k, stream) not in _REG_SCANS:
+        _REG_SCANS[(k, stream)] = synth.scan(reg_params(), k, stream)
+    return _REG_SCANS[(k, stream)]
+
+
+def assert_same_record(a, b, what, ints, floats):
+    for k in ints:
+        assert a[k] == b[k], (what, k, a[k], b[k])
+    for k in floats:
+        assert_bit_equal(np.asarray(a[k]), np.asarray(b[k]), f"{what}: {k}")
+
+
+def reg_rows_of_frame(h, slot=0):
+    """lm_info and the accepted rows (edges (n, 9), planes (m, 7)) of the slot's last mapping frame as lm_fit left them"""
+    p = h.params
+    gi = h.debug_get("lm_info", slot=slot)
+    kf_cap_c = p.n_less_sharp * p.n_sectors * p.n_scan
+    blocks = h.debug_get("lm_blocks", slot=slot).reshape(-1, 8)
+    qc, qs = h.debug_get("lm_corner_ds", slot=slot), h.debug_get("lm_surf_total_ds", slot=slot)
+    assert len(qc) == gi[LI_NCUR_C] and len(qs) == gi[LI_NTOTAL_DS]
+    bc, bs = blocks[:len(qc)], blocks[kf_cap_c:kf_cap_c + len(qs)]
+    mc, ms = bc[:, 7] == 2.0, bs[:, 7] == 3.0
+    assert ((bc[:, 7] == 0.0) | mc).all() and ((bs[:, 7] == 0.0) | ms).all()
+    E = np.concatenate([bc[mc, 0:6], qc[mc, :3].astype(np.float64)], 1)
+    S = np.concatenate([bs[ms, 0:3], bs[ms, 6:7], qs[ms, :3].astype(np.float64)], 1)
+    return gi, E, S
+
+
+def lm_observables(h, slot):
+    return dict(info=h.debug_get("lm_info", slot=slot), state=h.debug_get("lm_state", slot=slot), keyposes=h.debug_get("lm_keyposes", slot=slot),
+                cmap=h.debug_get("lm_corner_map_ds", slot=slot), smap=h.debug_get("lm_surf_map_ds", slot=slot), window=h.debug_get("lm_window", slot=slot))
