@@ -43,12 +43,16 @@ EXPORTS = [
     "alego_map_thin", "alego_map_thin_select", "alego_map_thin_edges", "alego_debug_thin_select",
     "alego_regcov_enable", "alego_regcov_get", "alego_regcov_host", "alego_regcov_normal_host", "alego_debug_regcov",
     "alego_remap_enable", "alego_remap_get", "alego_remap_host", "alego_remap_step_host", "alego_debug_remap_solve",
+    "alego_occ_enable", "alego_occ_clear", "alego_occ_integrate", "alego_occ_get", "alego_occ_classify", "alego_occ_ray_host", "alego_occ_integrate_host",
+    "alego_occ_classify_host", "alego_debug_occ_piece",
 ]
 
 REPLAY_PINGPONG = 0x100
 REPLAY_BAG = 0x200
 MAP_SURF, MAP_CORNER, MAP_OUTLIER, MAP_FRAME_ID = 1, 2, 4, 8
 ERR_CAPACITY, ERR_ARG = -3, -4
+OCC_RAYS, OCC_SHORT, OCC_TRUNCATED, OCC_CULLED, OCC_BAD, OCC_UPDATES, OCC_STATS = 0, 1, 2, 3, 4, 5, 6   # ALEGO_OCC_*
+OCC_SKIP_SHORT, OCC_SKIP_CULLED, OCC_SKIP_BAD = -10, -11, -12
 RELOC_MAX_CAND = 8
 RELOC_SECTORS, RELOC_RINGS = 60, 20
 ALIGN_MAX_QUERIES = 32
@@ -180,6 +184,14 @@ class MapThinOpts(C.Structure):
 
 class MapThinResult(C.Structure):
     _fields_ = [("status", C.c_int32), ("frames_before", C.c_int32), ("frames", C.c_int32), ("points_before", C.c_int32), ("points", C.c_int32)]
+
+
+class OccOpts(C.Structure):
+    _fields_ = [("origin", C.c_double * 3), ("cell", C.c_double * 3), ("n", C.c_int32 * 3), ("pad", C.c_int32), ("min_range", C.c_double), ("max_range", C.c_double)]
+
+
+class OccRule(C.Structure):
+    _fields_ = [("min_hits", C.c_int32), ("hit_weight", C.c_int32), ("pass_weight", C.c_int32), ("pad", C.c_int32)]
 
 
 class GraphEdge(C.Structure):
@@ -567,6 +579,15 @@ def lib():
         L.alego_map_thin_select.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p]
         L.alego_map_thin_edges.argtypes = [C.POINTER(GraphEdge), C.c_int32, C.POINTER(GraphEdge), C.c_int32, C.c_void_p, C.POINTER(GraphEdge), C.POINTER(GraphEdge)]
         L.alego_debug_thin_select.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p]
+        L.alego_occ_enable.argtypes = [C.c_void_p, C.POINTER(OccOpts)]
+        L.alego_occ_clear.argtypes = [C.c_void_p]
+        L.alego_occ_integrate.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.c_int, C.c_void_p]
+        L.alego_occ_get.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.alego_occ_classify.argtypes = [C.c_void_p, C.POINTER(OccRule), C.c_int, C.c_void_p]
+        L.alego_debug_occ_piece.argtypes = [C.c_void_p, C.c_int32]
+        L.alego_occ_ray_host.argtypes = [C.POINTER(OccOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
+        L.alego_occ_integrate_host.argtypes = [C.POINTER(OccOpts), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.alego_occ_classify_host.argtypes = [C.POINTER(OccOpts), C.POINTER(OccRule), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.alego_write_pcd.argtypes = [C.c_char_p, C.c_void_p, C.c_int32]
         L.alego_bag_read_pc2.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
         if L.alego_params_sizeof() != C.sizeof(AlegoParams):
@@ -767,6 +788,64 @@ def map_thin_edges(chain, loops, keep):
     if rc < 0:
         raise AlegoError(f"alego_map_thin_edges failed ({rc})")
     return _graph_edges_out(oc, rc), _graph_edges_out(ol, nl)
+
+
+def occ_opts(origin, cell, n, min_range=0.0, max_range=0.0):
+    """alego_occ_opts: origin (3,), cell (3,) or one edge length, n (3,) cells per axis"""
+    c = np.broadcast_to(np.asarray(cell, np.float64), (3,))
+    return OccOpts((C.c_double * 3)(*[float(v) for v in origin]), (C.c_double * 3)(*[float(v) for v in c]), (C.c_int32 * 3)(*[int(v) for v in n]), 0,
+                   float(min_range), float(max_range))
+
+
+def _occ_rule(rule):
+    return None if rule is None else C.byref(OccRule(int(rule[0]), int(rule[1]), int(rule[2]), 0))
+
+
+def _occ_shape(opts, collapse_z=False):
+    return (int(opts.n[1]), int(opts.n[0])) if collapse_z else (int(opts.n[2]), int(opts.n[1]), int(opts.n[0]))
+
+
+def occ_ray_host(opts, o, e, cap=None):
+    """alego_occ_ray_host: (cells (m, 3) int32, hit) of the ray o -> e (f32), or (skip code, None) for a ray that is skipped (host code of the library)"""
+    o, e = np.ascontiguousarray(o, np.float32).reshape(3), np.ascontiguousarray(e, np.float32).reshape(3)
+    hit = C.c_int32(0)
+    if cap is None:
+        cap = lib().alego_occ_ray_host(C.byref(opts), o.ctypes.data, e.ctypes.data, None, 0, C.byref(hit))
+        if cap < 0:
+            if cap == ERR_ARG:
+                raise AlegoError("alego_occ_ray_host failed (-4)")
+            return cap, None
+    cells = np.zeros((max(cap, 1), 3), np.int32)
+    n = lib().alego_occ_ray_host(C.byref(opts), o.ctypes.data, e.ctypes.data, cells.ctypes.data, cap, C.byref(hit))
+    if n == ERR_ARG:
+        raise AlegoError("alego_occ_ray_host failed (-4)")
+    return (n, None) if n < 0 else (cells[:min(n, cap)].copy(), int(hit.value))
+
+
+def occ_integrate_host(opts, origins, pts, hits=None, passes=None, stats=None):
+    """alego_occ_integrate_host: (hits, passes, stats) after the points (n, 4) (w = frame id) are cast from origins (frames, 4); given arrays are added to"""
+    shape = _occ_shape(opts)
+    hits = np.zeros(shape, np.uint32) if hits is None else hits
+    passes = np.zeros(shape, np.uint32) if passes is None else passes
+    stats = np.zeros(OCC_STATS, np.int64) if stats is None else stats
+    kp, p = np.ascontiguousarray(origins, np.float32).reshape(-1, 4), np.ascontiguousarray(pts, np.float32).reshape(-1, 4)
+    assert hits.flags.c_contiguous and passes.flags.c_contiguous and hits.dtype == np.uint32 and passes.dtype == np.uint32 and stats.dtype == np.int64
+    if p.shape[0] and (p[:, 3].min() < 0 or p[:, 3].max() >= kp.shape[0]):
+        raise ValueError("a point names a frame without an origin")
+    rc = lib().alego_occ_integrate_host(C.byref(opts), kp.ctypes.data, p.ctypes.data, p.shape[0], hits.ctypes.data, passes.ctypes.data, stats.ctypes.data)
+    if rc < 0:
+        raise AlegoError(f"alego_occ_integrate_host failed ({rc})")
+    return hits, passes, stats
+
+
+def occ_classify_host(opts, hits, passes, rule=None, collapse_z=False):
+    """alego_occ_classify_host: int8 classes (100 / 0 / -1) of the counts; rule = (min_hits, hit_weight, pass_weight) or None for the defaults"""
+    h, p = np.ascontiguousarray(hits, np.uint32), np.ascontiguousarray(passes, np.uint32)
+    out = np.zeros(_occ_shape(opts, collapse_z), np.int8)
+    rc = lib().alego_occ_classify_host(C.byref(opts), _occ_rule(rule), h.ctypes.data, p.ctypes.data, int(bool(collapse_z)), out.ctypes.data)
+    if rc < 0:
+        raise AlegoError(f"alego_occ_classify_host failed ({rc})")
+    return out
 
 
 def _reloc_result(r):
@@ -1332,6 +1411,38 @@ class Handle:
         rc = self._check(lib().alego_debug_thin_select(self._h, kp.ctypes.data, pr.ctypes.data, kp.shape[0], float(min_dist), keep.ctypes.data), "alego_debug_thin_select")
         assert rc == int(keep[:kp.shape[0]].sum())
         return keep[:kp.shape[0]]
+
+    # ---- occupancy grid of the archive by ray casting (needs map_enable) ----
+    def occ_enable(self, opts):
+        """alego_occ_enable: opts from occ_opts(); once per handle"""
+        self._check(lib().alego_occ_enable(self._h, C.byref(opts)), "alego_occ_enable")
+        self._occ_opts = opts
+
+    def occ_clear(self):
+        self._check(lib().alego_occ_clear(self._h), "alego_occ_clear")
+
+    def occ_integrate(self, kinds=7, first=0, n=-1, slot=0):
+        """alego_occ_integrate: the call's counters (OCC_STATS,) int64"""
+        stats = np.zeros(OCC_STATS, np.int64)
+        self._check(lib().alego_occ_integrate(self._h, slot, first, n, kinds, stats.ctypes.data), "alego_occ_integrate")
+        return stats
+
+    def occ_get(self):
+        """alego_occ_get: (hits, passes), each (n2, n1, n0) uint32"""
+        shape = _occ_shape(self._occ_opts)
+        hits, passes = np.zeros(shape, np.uint32), np.zeros(shape, np.uint32)
+        self._check(lib().alego_occ_get(self._h, hits.ctypes.data, passes.ctypes.data), "alego_occ_get")
+        return hits, passes
+
+    def occ_classify(self, rule=None, collapse_z=False):
+        """alego_occ_classify: int8 classes (n2, n1, n0), or (n1, n0) with collapse_z; rule = (min_hits, hit_weight, pass_weight) or None for the defaults"""
+        out = np.zeros(_occ_shape(self._occ_opts, collapse_z), np.int8)
+        self._check(lib().alego_occ_classify(self._h, _occ_rule(rule), int(bool(collapse_z)), out.ctypes.data), "alego_occ_classify")
+        return out
+
+    def debug_occ_piece(self, piece):
+        """development: steps of a ray one lane of occ_cast walks at a time (<= 0: one lane per ray)"""
+        self._check(lib().alego_debug_occ_piece(self._h, int(piece)), "alego_debug_occ_piece")
 
     # ---- localisation against a frozen key-frame map ----
     def loc_enable(self, frames, radius=0.0):

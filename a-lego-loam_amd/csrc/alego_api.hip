@@ -22,6 +22,7 @@
 #include "merge_math.h"
 #include "nn_rules.h"
 #include "thin_math.h"
+#include "occ_math.h"
 #include "loop_ctx.h"
 #include "pgraph.h"
 #include "prof.h"
@@ -1673,6 +1674,78 @@ int alego_debug_thin_select(alego_handle* h, const float* keyposes6, const uint8
   if (n < 0 || (n > 0 && (!keyposes6 || !protect || !keep)) || !(min_dist - min_dist == 0.0)) return ALEGO_ERR_ARG;
   WAIT_ALL(h);
   return lm_host_debug_thin_select(h->lm, keyposes6, protect, n, min_dist, keep, &h->err);
+}
+
+// ---- the occupancy grid of the archive (kernels_occ.hip, occ_math.h) ----
+namespace {
+int occ_need(alego_handle* h, const char* what) {
+  if (int r = gate_need(h, what, MAPPING | ARCHIVE)) return r;
+  if (!lm_host_occ_on(h->lm)) { h->err = std::string(what) + ": the occupancy grid is off (alego_occ_enable)"; return ALEGO_ERR_ARG; }
+  return 0;
+}
+}  // namespace
+int alego_occ_enable(alego_handle* h, const alego_occ_opts* opts) {
+  ALEGO_GATE(h);
+  if (!opts) return ALEGO_ERR_ARG;
+  if (int r = gate_need(h, "alego_occ_enable", MAPPING | ARCHIVE)) return r;
+  if (lm_host_occ_on(h->lm)) { h->err = "alego_occ_enable: already enabled"; return ALEGO_ERR_ARG; }
+  WAIT_ALL(h);
+  return lm_host_occ_enable(h->lm, opts, &h->err);
+}
+int alego_occ_clear(alego_handle* h) {
+  ALEGO_GATE(h);
+  if (int r = occ_need(h, "alego_occ_clear")) return r;
+  return lm_host_occ_clear(h->lm, &h->err);
+}
+int alego_occ_integrate(alego_handle* h, int slot, int32_t first, int32_t n, int kinds, int64_t stats[ALEGO_OCC_STATS]) {
+  ALEGO_GATE_SLOT(h, slot);
+  if (int r = occ_need(h, "alego_occ_integrate")) return r;
+  return lm_host_occ_integrate(h->lm, slot, first, n, kinds, stats, &h->err);
+}
+int alego_occ_get(alego_handle* h, uint32_t* hits, uint32_t* passes) {
+  ALEGO_GATE(h);
+  if (int r = occ_need(h, "alego_occ_get")) return r;
+  return lm_host_occ_get(h->lm, hits, passes, &h->err);
+}
+int alego_occ_classify(alego_handle* h, const alego_occ_rule* rule, int collapse_z, int8_t* out) {
+  ALEGO_GATE(h);
+  if (!out) return ALEGO_ERR_ARG;
+  if (int r = occ_need(h, "alego_occ_classify")) return r;
+  const alego_occ_rule dflt = {1, 2, 1, 0};
+  const alego_occ_rule& R = rule ? *rule : dflt;
+  if (const char* why = occ_rule_fault(&R)) { h->err = std::string("alego_occ_classify: ") + why; return ALEGO_ERR_ARG; }
+  return lm_host_occ_classify(h->lm, R, collapse_z, out, &h->err);
+}
+int alego_debug_occ_piece(alego_handle* h, int32_t piece) {
+  ALEGO_GATE(h);
+  return lm_host_occ_set_piece(h->lm, piece);
+}
+int alego_occ_ray_host(const alego_occ_opts* opts, const float o[3], const float e[3], int32_t* cells3, int32_t cap, int32_t* hit) {
+  if (!opts || !o || !e || cap < 0 || (cap > 0 && !cells3) || occ_opts_fault(opts)) return ALEGO_ERR_ARG;
+  const int64_t n = occ_ray_host(occ_grid(opts), o, e, cells3, cap, hit);
+  return n > 2147483647LL ? 2147483647 : (int)n;
+}
+int alego_occ_integrate_host(const alego_occ_opts* opts, const alego_point* origins, const alego_point* pts, int32_t n_pts, uint32_t* hits, uint32_t* passes,
+                             int64_t stats[ALEGO_OCC_STATS]) {
+  if (!opts || n_pts < 0 || (n_pts > 0 && (!origins || !pts)) || occ_opts_fault(opts)) return ALEGO_ERR_ARG;
+  const OccGrid G = occ_grid(opts);
+  for (int i = 0; i < n_pts; ++i) if (!(pts[i].intensity >= 0.f)) return ALEGO_ERR_ARG;   // (not a frame id: refused before anything is added)
+  int64_t local[ALEGO_OCC_STATS] = {0, 0, 0, 0, 0, 0};
+  for (int i = 0; i < n_pts; ++i) {
+    const alego_point& kp = origins[(int)pts[i].intensity];
+    const float o[3] = {kp.x, kp.y, kp.z}, e[3] = {pts[i].x, pts[i].y, pts[i].z};
+    occ_add_host(G, o, e, hits, passes, local);
+  }
+  if (stats) for (int k = 0; k < ALEGO_OCC_STATS; ++k) stats[k] += local[k];
+  return 0;
+}
+int alego_occ_classify_host(const alego_occ_opts* opts, const alego_occ_rule* rule, const uint32_t* hits, const uint32_t* passes, int collapse_z, int8_t* out) {
+  if (!opts || !hits || !passes || !out || occ_opts_fault(opts)) return ALEGO_ERR_ARG;
+  const alego_occ_rule dflt = {1, 2, 1, 0};
+  const alego_occ_rule& R = rule ? *rule : dflt;
+  if (occ_rule_fault(&R)) return ALEGO_ERR_ARG;
+  occ_classify_host(occ_grid(opts), R, hits, passes, collapse_z, out);
+  return 0;
 }
 
 int alego_loc_status(alego_handle* h, int slot, int32_t out[4]) {

@@ -54,6 +54,14 @@ struct LmCtx;
 const LmCtx* lm_host_ctx(LmHost* lm);   // the device view (the batched loop-closure search reads the archive through it)
 int lm_host_map_assemble(LmHost* lm, int slot, int kinds, float leaf, alego_point* out, int cap, std::string* err);
 int lm_host_map_keyposes(LmHost* lm, int slot, alego_point* out, int cap, std::string* err);
+// the occupancy grid (alego_occ_*; kernels_occ.hip); the caller has checked that the grid exists (lm_host_occ_on) before every call but enable
+bool lm_host_occ_on(LmHost* lm);
+int lm_host_occ_enable(LmHost* lm, const alego_occ_opts* opts, std::string* err);
+int lm_host_occ_clear(LmHost* lm, std::string* err);
+int lm_host_occ_integrate(LmHost* lm, int slot, int first, int n, int kinds, int64_t* stats, std::string* err);
+int lm_host_occ_get(LmHost* lm, uint32_t* hits, uint32_t* passes, std::string* err);
+int lm_host_occ_classify(LmHost* lm, const alego_occ_rule& rule, int collapse_z, int8_t* out, std::string* err);
+int lm_host_occ_set_piece(LmHost* lm, int piece);   // alego_debug_occ_piece
 int lm_host_get_local_map(LmHost* lm, int slot, alego_point* corner, int corner_cap, alego_point* surf, int surf_cap, int* n_out, std::string* err);
 int lm_host_voxel_grid(LmHost* lm, hipStream_t st, const alego_point* pts, int n, float leaf, alego_point* out, int cap, std::string* err);
 int lm_host_set_gv_small_max(LmHost* lm, int v);

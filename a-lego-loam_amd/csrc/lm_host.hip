@@ -21,6 +21,7 @@
 #include "merge_math.h"
 #include "thin.h"
 #include "thin_math.h"
+#include "occ.h"
 #include "loc_store.h"
 #include "remap_math.h"
 
@@ -67,6 +68,14 @@ struct LmHost {
   double rc_opt[RC_OPT_W] = {};
   // alego_remap_enable
   bool rm_on = false;
+  // alego_occ_enable: the grid (hits, passes and the counters of an integrate belong to mem), the options it was made from, the work list of an
+  // integrate and the classes of a classify, both allocated by the first call and kept
+  bool occ_on = false;
+  OccDev occ = {};
+  alego_occ_opts occ_opts = {};
+  int occ_piece = OCC_PIECE_DEFAULT;
+  DevBuf<int2> occ_items;
+  DevBuf<int8_t> occ_cls;
 };
 
 namespace {
@@ -1364,6 +1373,69 @@ int lm_host_map_keyposes(LmHost* lm, int slot, alego_point* out, int cap, std::s
   if (nf > 0 && hipMemcpy(kp.data(), arc_pose_of(lm->L, slot, 0), kp.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) { *err = "map_keyposes: copy failed"; return ALEGO_ERR_HIP; }
   for (int i = 0; i < nf; ++i) out[i] = alego_point{kp[(size_t)i * KF_POSE_W + 0], kp[(size_t)i * KF_POSE_W + 1], kp[(size_t)i * KF_POSE_W + 2], (float)i};   // saveMapCB :833-838
   return nf;
+}
+// ---- the occupancy grid (alego_occ_*; kernels_occ.hip) ----
+bool lm_host_occ_on(LmHost* lm) { return lm && lm->occ_on; }
+int lm_host_occ_enable(LmHost* lm, const alego_occ_opts* opts, std::string* err) {
+  if (const char* why = occ_opts_fault(opts)) { *err = std::string("occ_enable: ") + why; return ALEGO_ERR_ARG; }
+  OccDev D = {};
+  D.G = occ_grid(opts);
+  const size_t cells = occ_cells(D.G);
+  if (!(A(lm, &D.hits, cells, err) && A(lm, &D.passes, cells, err) && A(lm, &D.stats, ALEGO_OCC_STATS, err))) {
+    lm->mem.release(D.hits); lm->mem.release(D.passes);
+    return ALEGO_ERR_HIP;
+  }
+  lm->occ = D; lm->occ_opts = *opts; lm->occ_on = true;
+  return 0;
+}
+int lm_host_occ_set_piece(LmHost* lm, int piece) { lm->occ_piece = piece; return 0; }
+int lm_host_occ_clear(LmHost* lm, std::string* err) {
+  launch_occ_clear(lm->occ, lm->st[0]);
+  if (hipStreamSynchronize(lm->st[0]) != hipSuccess) { *err = "occ_clear: clearing failed"; return ALEGO_ERR_HIP; }
+  return 0;
+}
+int lm_host_occ_integrate(LmHost* lm, int slot, int first, int n, int kinds, int64_t* stats, std::string* err) {
+  int st[AS_W];
+  if (int r = map_stat(lm, slot, st, err)) return r;   // (behind the slot's own stream: archive appends happen there)
+  if (!(kinds & KF_SEL_ALL)) { *err = "occ_integrate: kinds must select surf / corner / outlier"; return ALEGO_ERR_ARG; }
+  kinds &= KF_SEL_ALL;
+  const int nf = st[AS_FRAMES];
+  if (first < 0 || n < -1 || first > nf || (n >= 0 && n > nf - first)) { *err = "occ_integrate: range beyond the archived frames"; return ALEGO_ERR_ARG; }
+  if (n < 0) n = nf - first;
+  if (stats) for (int k = 0; k < ALEGO_OCC_STATS; ++k) stats[k] = 0;
+  if (n == 0) return 0;
+  const LmCtx& L = lm->L;
+  std::vector<int> tab((size_t)n * AT_W);
+  if (hipMemcpy(tab.data(), arc_tab_of(L, slot, first), tab.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { *err = "occ_integrate: device read failed"; return ALEGO_ERR_HIP; }
+  std::vector<int2> items;
+  for (int f = 0; f < n; ++f) {
+    const int sel = kf_sel_count(kf_arc_frame(L, slot, first + f, tab.data() + (size_t)f * AT_W), kinds);
+    for (int c = 0; c * OCC_T < sel; ++c) items.push_back(make_int2(first + f, c));
+  }
+  if (items.empty()) return 0;
+  hipStream_t s = stream_of_slot(lm, slot);
+  if (lm->occ_items.reserve(items.size()) != hipSuccess) { *err = "occ_integrate: allocation failed"; return ALEGO_ERR_HIP; }
+  if (hipMemcpy(lm->occ_items.p, items.data(), items.size() * sizeof(int2), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemsetAsync(lm->occ.stats, 0, ALEGO_OCC_STATS * sizeof(unsigned long long), s) != hipSuccess) { *err = "occ_integrate: upload failed"; return ALEGO_ERR_HIP; }
+  launch_occ_cast(L, lm->occ, slot, kinds, lm->occ_items.p, (int)items.size(), lm->occ_piece, s);
+  unsigned long long got[ALEGO_OCC_STATS];
+  if (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(got, lm->occ.stats, sizeof(got), hipMemcpyDeviceToHost) != hipSuccess) { *err = "occ_integrate: ray casting failed"; return ALEGO_ERR_HIP; }
+  if (stats) for (int k = 0; k < ALEGO_OCC_STATS; ++k) stats[k] = (int64_t)got[k];
+  return 0;
+}
+int lm_host_occ_get(LmHost* lm, uint32_t* hits, uint32_t* passes, std::string* err) {
+  const size_t bytes = occ_cells(lm->occ.G) * sizeof(uint32_t);
+  if ((hits && hipMemcpy(hits, lm->occ.hits, bytes, hipMemcpyDeviceToHost) != hipSuccess) ||
+      (passes && hipMemcpy(passes, lm->occ.passes, bytes, hipMemcpyDeviceToHost) != hipSuccess)) { *err = "occ_get: copy failed"; return ALEGO_ERR_HIP; }
+  return 0;
+}
+int lm_host_occ_classify(LmHost* lm, const alego_occ_rule& rule, int collapse_z, int8_t* out, std::string* err) {
+  const OccGrid& G = lm->occ.G;
+  const size_t n_out = collapse_z ? (size_t)G.n[0] * G.n[1] : occ_cells(G);
+  if (lm->occ_cls.reserve(n_out) != hipSuccess) { *err = "occ_classify: allocation failed"; return ALEGO_ERR_HIP; }
+  launch_occ_classify(lm->occ, rule, collapse_z, lm->occ_cls.p, lm->st[0]);
+  if (hipStreamSynchronize(lm->st[0]) != hipSuccess || hipMemcpy(out, lm->occ_cls.p, n_out, hipMemcpyDeviceToHost) != hipSuccess) { *err = "occ_classify: classification failed"; return ALEGO_ERR_HIP; }
+  return 0;
 }
 int lm_host_get_local_map(LmHost* lm, int slot, alego_point* corner, int corner_cap, alego_point* surf, int surf_cap, int* n_out, std::string* err) {
   const LmCtx& L = lm->L;

@@ -1,0 +1,27 @@
+// occ.h — host interface of the occupancy grid's kernels (kernels_occ.hip), called by lm_host.hip
+#ifndef ALEGO_OCC_H_
+#define ALEGO_OCC_H_
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/alego_mi355x.h"
+#include "occ_math.h"
+
+struct LmCtx;
+
+#define OCC_T 256             // occ_cast's workgroup = the rays of one work item
+#define OCC_PIECE_DEFAULT 32  // steps of a ray one lane walks at a time ("Measured")
+
+// the grid of a handle as the kernels read it
+struct OccDev {
+  OccGrid G;
+  uint32_t *hits, *passes;          // [cells]
+  unsigned long long* stats;        // [ALEGO_OCC_STATS] counters of the integrate in flight
+};
+
+// items: (frame, chunk of OCC_T selected points of it), frames of `slot`; piece <= 0: one lane per ray
+void launch_occ_cast(const LmCtx& L, const OccDev& D, int slot, int kinds, const int2* items, int n_items, int piece, hipStream_t st);
+// out[cells], or out[n0 n1] with collapse_z
+void launch_occ_classify(const OccDev& D, alego_occ_rule rule, int collapse_z, int8_t* out, hipStream_t st);
+void launch_occ_clear(const OccDev& D, hipStream_t st);
+#endif

@@ -70,6 +70,13 @@
 //       the information matrix; rotation x y z in rad^2, then translation x y z in m^2).  --regcov-graph turns the archive and the key-pose
 //       graph on as well and writes those variances into the odometry edges (opts.graph = 1): with --loop-search N --gate CHI2 the gate then
 //       judges every found loop against noise the registrations measured instead of the constant default.
+//   either source + --occupancy CELL DIR [--occ-range R]
+//       keeps the archive on and, at the end (after --merge / --thin), casts every archived point as a ray from its key pose into an occupancy
+//       grid on the device (alego_occ_enable / _integrate / _classify): square cells of CELL metres in x and y over the
+//       key poses' bounding box plus R (max_range, default 30 m), ONE layer in z from 0.5 m below the lowest key pose to 1 m above the
+//       highest, so that ground returns leave the layer from below and count as free space only.  Writes DIR/occupancy.pgm (P5; 254 free,
+//       0 occupied, 205 unknown; the top row is the largest y, as map_server reads it) and DIR/occupancy.yaml, and prints one line
+//       "occupancy: origin X Y Z cell CX CY CZ n NX NY NZ max_range R rays N short S truncated T culled C bad B updates U".
 // Every scan goes through ImageProjection -> LaserOdometry -> LaserMapping with one alego_scan_process call, as a single nodelet
 // manager would run them (launch/test.launch:6-10); every new key frame is pulled across the boundary the way the reference's
 // pose-graph thread reads cloud_keyposes_6d_ (laserMapping.cpp:586-596); one JSON line with the final poses is printed.
@@ -90,7 +97,8 @@
 extern "C" int alego_synth_scan(const alego_params* P, int stream, long scan_index, int flags, alego_point* out, int cap);
 
 int main(int argc, char** argv) {
-  std::string bag_path, topic = "/lslidar_point_cloud", map_dir;
+  std::string bag_path, topic = "/lslidar_point_cloud", map_dir, occ_dir;
+  double occ_cell = 0.0, occ_range = 30.0;
   float map_leaf = 0.f;
   int map_frames = 4096, map_points = 1 << 24, loop_every = 0, close_every = 0, max_loops = 16;
   bool list_only = false, standalone = false, localize = false, relocalize = false, appearance = false, merge = false, on_device = false, regcov = false, regcov_graph = false, remap = false;
@@ -125,6 +133,8 @@ int main(int argc, char** argv) {
     else if (a == "--align") align_start = std::atol(val());
     else if (a == "--merge") merge = true;
     else if (a == "--thin") thin_dist = std::atof(val());
+    else if (a == "--occupancy") { occ_cell = std::atof(val()); occ_dir = val(); }
+    else if (a == "--occ-range") occ_range = std::atof(val());
     else if (a == "--recent-keyframes") recent_keyframes = std::atoi(val());
     else if (a == "--localize") localize = true;
     else if (a == "--on-device") on_device = true;
@@ -178,7 +188,8 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "alego_create failed (%d): there is no CPU fallback, an MI355X is required\n", rc);
     return 1;
   }
-  if ((!map_dir.empty() || loop_every > 0 || close_every > 0 || localize || align_start >= 0 || thin_dist >= 0.0 || regcov_graph) && alego_map_enable(h, map_frames, map_points) != ALEGO_OK) {
+  if (!occ_dir.empty() && !(occ_cell > 0.0 && occ_range > 0.0)) { std::fprintf(stderr, "--occupancy needs a positive CELL (and --occ-range a positive R)\n"); alego_destroy(h); return 2; }
+  if ((!map_dir.empty() || !occ_dir.empty() || loop_every > 0 || close_every > 0 || localize || align_start >= 0 || thin_dist >= 0.0 || regcov_graph) && alego_map_enable(h, map_frames, map_points) != ALEGO_OK) {
     std::fprintf(stderr, "map_enable: %s\n", alego_last_error(h)); alego_destroy(h); return 1;
   }
   if (merge && align_start < 0) { std::fprintf(stderr, "--merge needs --align START2\n"); alego_destroy(h); return 2; }
@@ -427,6 +438,49 @@ int main(int argc, char** argv) {
     int32_t st[4];
     if (!rc && alego_map_status(h, 0, st) == ALEGO_OK && st[1] > 0) std::fprintf(stderr, "map: %d key frames did not fit the archive (--map-frames / --map-points)\n", st[1]);
     if (rc) std::fprintf(stderr, "save map to %s: %s\n", map_dir.c_str(), alego_last_error(h));
+  }
+  if (!occ_dir.empty() && !rc) {   // the occupancy grid of slot 0's archive at the key poses that hold now
+    std::vector<alego_point> kp;
+    int n = alego_map_keyposes(h, 0, nullptr, 0);
+    if (n > 0) { kp.resize(n); n = alego_map_keyposes(h, 0, kp.data(), n); }
+    if (n <= 0) { std::fprintf(stderr, "occupancy: no key frame archived\n"); alego_destroy(h); return 1; }
+    double lo[3] = {kp[0].x, kp[0].y, kp[0].z}, hi[3] = {kp[0].x, kp[0].y, kp[0].z};
+    for (int i = 1; i < n; ++i) {
+      const double v[3] = {kp[i].x, kp[i].y, kp[i].z};
+      for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], v[a]); hi[a] = std::max(hi[a], v[a]); }
+    }
+    alego_occ_opts oo{};
+    for (int a = 0; a < 2; ++a) {
+      oo.cell[a] = occ_cell;
+      oo.origin[a] = std::floor((lo[a] - occ_range) / occ_cell) * occ_cell;
+      oo.n[a] = (int32_t)std::ceil((hi[a] + occ_range - oo.origin[a]) / occ_cell);
+    }
+    oo.origin[2] = lo[2] - 0.5; oo.cell[2] = hi[2] + 1.0 - oo.origin[2]; oo.n[2] = 1;
+    oo.min_range = 0.0; oo.max_range = occ_range;
+    int64_t st[ALEGO_OCC_STATS];
+    std::vector<int8_t> cls((size_t)oo.n[0] * oo.n[1]);
+    if (alego_occ_enable(h, &oo) != ALEGO_OK || alego_occ_integrate(h, 0, 0, -1, ALEGO_MAP_SURF | ALEGO_MAP_CORNER | ALEGO_MAP_OUTLIER, st) != ALEGO_OK ||
+        alego_occ_classify(h, nullptr, 1, cls.data()) != ALEGO_OK) { std::fprintf(stderr, "occupancy: %s\n", alego_last_error(h)); alego_destroy(h); return 1; }
+    std::printf("occupancy: origin %.17g %.17g %.17g cell %.17g %.17g %.17g n %d %d %d max_range %.17g rays %lld short %lld truncated %lld culled %lld bad %lld updates %lld\n",
+                oo.origin[0], oo.origin[1], oo.origin[2], oo.cell[0], oo.cell[1], oo.cell[2], oo.n[0], oo.n[1], oo.n[2], oo.max_range, (long long)st[ALEGO_OCC_RAYS],
+                (long long)st[ALEGO_OCC_SHORT], (long long)st[ALEGO_OCC_TRUNCATED], (long long)st[ALEGO_OCC_CULLED], (long long)st[ALEGO_OCC_BAD], (long long)st[ALEGO_OCC_UPDATES]);
+    std::vector<unsigned char> img(cls.size());
+    for (int y = 0; y < oo.n[1]; ++y)   // the image's top row is the grid's last
+      for (int x = 0; x < oo.n[0]; ++x) {
+        const int8_t c = cls[(size_t)(oo.n[1] - 1 - y) * oo.n[0] + x];
+        img[(size_t)y * oo.n[0] + x] = c == 100 ? 0 : (c == 0 ? 254 : 205);
+      }
+    FILE* f = std::fopen((occ_dir + "/occupancy.pgm").c_str(), "wb");
+    bool ok = f != nullptr;
+    if (ok) { ok = std::fprintf(f, "P5\n%d %d\n255\n", oo.n[0], oo.n[1]) > 0 && std::fwrite(img.data(), 1, img.size(), f) == img.size(); ok = std::fclose(f) == 0 && ok; }
+    f = ok ? std::fopen((occ_dir + "/occupancy.yaml").c_str(), "w") : nullptr;
+    if (f) {
+      ok = std::fprintf(f, "image: occupancy.pgm\nresolution: %.17g\norigin: [%.17g, %.17g, 0.0]\nnegate: 0\noccupied_thresh: 0.65\nfree_thresh: 0.196\n", occ_cell, oo.origin[0], oo.origin[1]) > 0;
+      ok = std::fclose(f) == 0 && ok;
+    } else {
+      ok = false;
+    }
+    if (!ok) { std::fprintf(stderr, "occupancy: cannot write to %s\n", occ_dir.c_str()); rc = 1; }
   }
   alego_destroy(h);
   if (bag) alego_bag_close(bag);

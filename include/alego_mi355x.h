@@ -979,6 +979,56 @@ int alego_map_thin_edges(const alego_graph_edge* chain, int32_t n, const alego_g
                          alego_graph_edge* out_chain, alego_graph_edge* out_loops);
 int alego_debug_thin_select(alego_handle* h, const float* keyposes6, const uint8_t* protect, int32_t n, double min_dist, uint8_t* keep);
 
+/* ---- occupancy grid of the key-frame archive by ray casting (csrc/kernels_occ.hip, csrc/occ_math.h) ------------
+ * Not part of the reference.  Every archived point is a ray from its frame's key-pose position to a surface: the cells a ray passes
+ * were seen free, the cell it ends in holds something, a cell no ray visits was never observed.  Opt-in: without alego_occ_enable
+ * nothing is allocated or launched, and nothing on the per-scan path changes.
+ *
+ * GRID    origin[3] = world position of the corner of cell (0, 0, 0); cell[3] > 0 the edge lengths; n[3] >= 1 cells per axis with
+ *         n[0] n[1] n[2] <= 2^31 - 1; linear index (z n[1] + y) n[0] + x.  One thick layer (n[2] = 1) is the 2-D product.
+ * RAY     from the key pose's translation to the point as alego_map_assemble gives it (f32), widened to f64.  A ray with a non-finite
+ *         coordinate or an end further than 2^30 cells from the origin is BAD; one shorter than min_range is SHORT; one longer than
+ *         max_range (> 0; 0: no limit) is TRUNCATED to that length and carries no hit; one whose end cells lie on the same outer side of
+ *         the grid on some axis is CULLED.  Bad, short and culled rays change nothing.  The cells between are those of an exact
+ *         voxel traversal with ties to the lowest axis (csrc/occ_math.h states the rule; the kernel and the host twins share it).
+ * COUNTS  u32 per cell: every visited cell but the last passes += 1; the last hits += 1, or passes += 1 for a truncated ray.  Integer
+ *         adds: the result does not depend on the order of arrival, device and host agree exactly.  There is no per-scan de-duplication.
+ * CLASSES 100 (occupied) iff hits >= min_hits and hits * hit_weight >= passes * pass_weight (64-bit); else 0 (free) if passes > 0; else
+ *         -1 (unknown).  The defaults 1, 2, 1 (rule = NULL) are parameters of a model, not measurements.  collapse_z = 1 writes one
+ *         value per (x, y) column (100 if any layer is 100, else 0 if any is 0, else -1): the layout of a nav_msgs/OccupancyGrid.
+ *
+ * alego_occ_enable     once per mapping handle with the archive on: allocates and zeroes the grid.
+ * alego_occ_clear      zeroes the counts.
+ * alego_occ_integrate  adds the rays of frames [first, first + n) (n = -1: to the newest) of `slot`, clouds `kinds`
+ *                      (ALEGO_MAP_SURF | _CORNER | _OUTLIER), at the poses that hold NOW; synchronous, behind the slot's own stream.  It
+ *                      accumulates: several calls or slots add up.  stats (may be NULL) gets this call's counters.
+ * alego_occ_get        the counts, n[0] n[1] n[2] each (either pointer may be NULL).
+ * alego_occ_classify   out[cells], or out[n[0] n[1]] with collapse_z.
+ * Every refusal is ALEGO_ERR_ARG with alego_last_error set: archive off, a second enable, a call before enable, options out of range,
+ * frames beyond those stored, kinds without a cloud, a slot out of range, a negative weight or min_hits.
+ * Host twins (no device, no handle): alego_occ_ray_host writes the first `cap` visited cells of one ray to cells3[3 i + k] and returns how
+ * many the ray visits or ALEGO_OCC_SKIP_*; *hit = 1 when the last cell takes a hit.  alego_occ_integrate_host adds points (w = frame id, as
+ * alego_map_assemble gives them with ALEGO_MAP_FRAME_ID) cast from origins[frame] (alego_map_keyposes) into hits / passes / stats, which it
+ * does NOT zero (a negative or NaN frame id: ALEGO_ERR_ARG, nothing added; an id beyond the origins is the caller's to avoid).  alego_occ_classify_host is
+ * alego_occ_classify on host arrays. */
+typedef struct alego_occ_opts { double origin[3], cell[3]; int32_t n[3], pad; double min_range, max_range; } alego_occ_opts;
+typedef struct alego_occ_rule { int32_t min_hits, hit_weight, pass_weight, pad; } alego_occ_rule;
+/* counters of one integrate (int64 each): rays read, of them short / truncated / culled / bad, cell updates inside the grid */
+enum { ALEGO_OCC_RAYS = 0, ALEGO_OCC_SHORT, ALEGO_OCC_TRUNCATED, ALEGO_OCC_CULLED, ALEGO_OCC_BAD, ALEGO_OCC_UPDATES, ALEGO_OCC_STATS };
+enum { ALEGO_OCC_SKIP_SHORT = -10, ALEGO_OCC_SKIP_CULLED = -11, ALEGO_OCC_SKIP_BAD = -12 };
+int alego_occ_enable(alego_handle* h, const alego_occ_opts* opts);
+int alego_occ_clear(alego_handle* h);
+int alego_occ_integrate(alego_handle* h, int slot, int32_t first, int32_t n, int kinds, int64_t stats[ALEGO_OCC_STATS]);
+int alego_occ_get(alego_handle* h, uint32_t* hits, uint32_t* passes);
+int alego_occ_classify(alego_handle* h, const alego_occ_rule* rule, int collapse_z, int8_t* out);
+int alego_occ_ray_host(const alego_occ_opts* opts, const float o[3], const float e[3], int32_t* cells3, int32_t cap, int32_t* hit);
+int alego_occ_integrate_host(const alego_occ_opts* opts, const alego_point* origins, const alego_point* pts, int32_t n_pts, uint32_t* hits, uint32_t* passes,
+                             int64_t stats[ALEGO_OCC_STATS]);
+int alego_occ_classify_host(const alego_occ_opts* opts, const alego_occ_rule* rule, const uint32_t* hits, const uint32_t* passes, int collapse_z, int8_t* out);
+/* development: the piece length of occ_cast's work distribution for this handle (steps of a ray one lane walks at a time; <= 0: one lane
+ * walks a whole ray, the baseline tools/occ_timing.py measures next to the default).  The counts do not depend on it. */
+int alego_debug_occ_piece(alego_handle* h, int32_t piece);
+
 /* ---- one scan-to-map registration sharded over the GPUs of a node (BASELINE.json config 5) ----------------
  * One process per GPU; every rank feeds its handle the SAME scans and so keeps a bit-identical replica of the stream's state
  * (ImageProjection, feature extraction, LaserOdometry and the local map are cheap and are computed redundantly).  What is split
