@@ -44,7 +44,7 @@ EXPORTS = [
     "alego_regcov_enable", "alego_regcov_get", "alego_regcov_host", "alego_regcov_normal_host", "alego_debug_regcov",
     "alego_remap_enable", "alego_remap_get", "alego_remap_host", "alego_remap_step_host", "alego_debug_remap_solve",
     "alego_occ_enable", "alego_occ_clear", "alego_occ_integrate", "alego_occ_get", "alego_occ_classify", "alego_occ_ray_host", "alego_occ_integrate_host",
-    "alego_occ_classify_host", "alego_debug_occ_piece",
+    "alego_occ_classify_host", "alego_debug_occ_piece", "alego_occ_mark", "alego_map_assemble_static", "alego_occ_mark_host",
 ]
 
 REPLAY_PINGPONG = 0x100
@@ -53,6 +53,7 @@ MAP_SURF, MAP_CORNER, MAP_OUTLIER, MAP_FRAME_ID = 1, 2, 4, 8
 ERR_CAPACITY, ERR_ARG = -3, -4
 OCC_RAYS, OCC_SHORT, OCC_TRUNCATED, OCC_CULLED, OCC_BAD, OCC_UPDATES, OCC_STATS = 0, 1, 2, 3, 4, 5, 6   # ALEGO_OCC_*
 OCC_SKIP_SHORT, OCC_SKIP_CULLED, OCC_SKIP_BAD = -10, -11, -12
+STATIC_OCCUPIED, STATIC_UNKNOWN, STATIC_OUTSIDE, STATIC_BELOW, STATIC_NEIGHBOUR, STATIC_REMOVED, STATIC_VERDICTS = 0, 1, 2, 3, 4, 5, 6   # ALEGO_STATIC_*
 RELOC_MAX_CAND = 8
 RELOC_SECTORS, RELOC_RINGS = 60, 20
 ALIGN_MAX_QUERIES = 32
@@ -192,6 +193,10 @@ class OccOpts(C.Structure):
 
 class OccRule(C.Structure):
     _fields_ = [("min_hits", C.c_int32), ("hit_weight", C.c_int32), ("pass_weight", C.c_int32), ("pad", C.c_int32)]
+
+
+class StaticRule(C.Structure):
+    _fields_ = [("occ", OccRule), ("protect_radius", C.c_int32), ("use_keep_below", C.c_int32), ("keep_below", C.c_float), ("pad", C.c_int32)]
 
 
 class GraphEdge(C.Structure):
@@ -588,6 +593,9 @@ def lib():
         L.alego_occ_ray_host.argtypes = [C.POINTER(OccOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
         L.alego_occ_integrate_host.argtypes = [C.POINTER(OccOpts), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.alego_occ_classify_host.argtypes = [C.POINTER(OccOpts), C.POINTER(OccRule), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.alego_occ_mark.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(StaticRule), C.c_void_p, C.c_int32, C.c_void_p]
+        L.alego_map_assemble_static.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.POINTER(StaticRule), C.c_void_p, C.c_int32, C.c_void_p]
+        L.alego_occ_mark_host.argtypes = [C.POINTER(OccOpts), C.POINTER(StaticRule), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
         L.alego_write_pcd.argtypes = [C.c_char_p, C.c_void_p, C.c_int32]
         L.alego_bag_read_pc2.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
         if L.alego_params_sizeof() != C.sizeof(AlegoParams):
@@ -846,6 +854,33 @@ def occ_classify_host(opts, hits, passes, rule=None, collapse_z=False):
     if rc < 0:
         raise AlegoError(f"alego_occ_classify_host failed ({rc})")
     return out
+
+
+def static_rule(occ=(1, 2, 1), protect_radius=0, keep_below=None):
+    """alego_static_rule: occ = (min_hits, hit_weight, pass_weight); keep_below = None leaves that test off"""
+    return StaticRule(OccRule(int(occ[0]), int(occ[1]), int(occ[2]), 0), int(protect_radius), 0 if keep_below is None else 1,
+                      0.0 if keep_below is None else float(keep_below), 0)
+
+
+def _static_rule(rule):
+    return None if rule is None else C.byref(rule)
+
+
+def occ_mark_host(opts, hits, passes, pts, rule=None, sensor_z=None):
+    """alego_occ_mark_host: (verdicts (n,) uint8, stats (STATIC_VERDICTS,) int64) of the world points (n, 3+) against the counts; rule from static_rule() or
+    None for the defaults; sensor_z (n,) f32 is needed when the rule has keep_below"""
+    h, p = np.ascontiguousarray(hits, np.uint32), np.ascontiguousarray(passes, np.uint32)
+    assert h.size == p.size == int(opts.n[0]) * int(opts.n[1]) * int(opts.n[2])
+    a = np.asarray(pts, np.float32)
+    q = np.zeros((a.shape[0], 4), np.float32)
+    q[:, :3] = a[:, :3]
+    z = None if sensor_z is None else np.ascontiguousarray(sensor_z, np.float32).reshape(q.shape[0])
+    verdict, stats = np.zeros(max(q.shape[0], 1), np.uint8), np.zeros(STATIC_VERDICTS, np.int64)
+    rc = lib().alego_occ_mark_host(C.byref(opts), _static_rule(rule), h.ctypes.data, p.ctypes.data, q.ctypes.data, None if z is None else z.ctypes.data, q.shape[0],
+                                   verdict.ctypes.data, stats.ctypes.data)
+    if rc < 0:
+        raise AlegoError(f"alego_occ_mark_host failed ({rc})")
+    return verdict[:q.shape[0]], stats
 
 
 def _reloc_result(r):
@@ -1439,6 +1474,23 @@ class Handle:
         out = np.zeros(_occ_shape(self._occ_opts, collapse_z), np.int8)
         self._check(lib().alego_occ_classify(self._h, _occ_rule(rule), int(bool(collapse_z)), out.ctypes.data), "alego_occ_classify")
         return out
+
+    def occ_mark(self, kinds=7, rule=None, slot=0):
+        """alego_occ_mark: (verdicts (n,) uint8 of the points of map_assemble(kinds & 7), stats (STATIC_VERDICTS,) int64); rule from static_rule() or None"""
+        stats = np.zeros(STATIC_VERDICTS, np.int64)
+        n = self._check(lib().alego_occ_mark(self._h, slot, kinds, _static_rule(rule), None, 0, None), "alego_occ_mark")
+        verdict = np.zeros(max(n, 1), np.uint8)
+        n = self._check(lib().alego_occ_mark(self._h, slot, kinds, _static_rule(rule), verdict.ctypes.data, n, stats.ctypes.data), "alego_occ_mark")
+        return verdict[:n], stats
+
+    def map_assemble_static(self, kinds, leaf=0.0, rule=None, slot=0, cap=None):
+        """alego_map_assemble_static: (map_assemble's cloud without the points the grid saw through, stats (STATIC_VERDICTS,) int64)"""
+        stats = np.zeros(STATIC_VERDICTS, np.int64)
+        if cap is None:
+            cap = self._check(lib().alego_map_assemble_static(self._h, slot, kinds, leaf, _static_rule(rule), None, 0, None), "alego_map_assemble_static")
+        out = np.empty((max(cap, 1), 4), np.float32)
+        n = self._check(lib().alego_map_assemble_static(self._h, slot, kinds, leaf, _static_rule(rule), out.ctypes.data, cap, stats.ctypes.data), "alego_map_assemble_static")
+        return out[:n].copy(), stats
 
     def debug_occ_piece(self, piece):
         """development: steps of a ray one lane of occ_cast walks at a time (<= 0: one lane per ray)"""

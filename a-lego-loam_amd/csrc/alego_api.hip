@@ -1748,6 +1748,33 @@ int alego_occ_classify_host(const alego_occ_opts* opts, const alego_occ_rule* ru
   return 0;
 }
 
+// ---- the static map ----
+int alego_occ_mark(alego_handle* h, int slot, int kinds, const alego_static_rule* rule, uint8_t* verdict, int32_t cap, int64_t stats[ALEGO_STATIC_VERDICTS]) {
+  ALEGO_GATE_SLOT(h, slot);
+  if (int r = occ_need(h, "alego_occ_mark")) return r;
+  const alego_static_rule R = rule ? *rule : occ_static_rule_default();
+  if (const char* why = occ_static_rule_fault(&R)) { h->err = std::string("alego_occ_mark: ") + why; return ALEGO_ERR_ARG; }
+  return lm_host_occ_mark(h->lm, slot, kinds, R, verdict, cap, stats, &h->err);
+}
+int alego_map_assemble_static(alego_handle* h, int slot, int kinds, float leaf, const alego_static_rule* rule, alego_point* out, int32_t cap,
+                              int64_t stats[ALEGO_STATIC_VERDICTS]) {
+  ALEGO_GATE_SLOT(h, slot);
+  if (int r = occ_need(h, "alego_map_assemble_static")) return r;
+  const alego_static_rule R = rule ? *rule : occ_static_rule_default();
+  if (const char* why = occ_static_rule_fault(&R)) { h->err = std::string("alego_map_assemble_static: ") + why; return ALEGO_ERR_ARG; }
+  return lm_host_map_assemble_static(h->lm, slot, kinds, leaf, R, out, cap, stats, &h->err);
+}
+int alego_occ_mark_host(const alego_occ_opts* opts, const alego_static_rule* rule, const uint32_t* hits, const uint32_t* passes, const alego_point* pts,
+                        const float* sensor_z, int32_t n, uint8_t* verdict, int64_t stats[ALEGO_STATIC_VERDICTS]) {
+  if (!opts || !hits || !passes || n < 0 || (n > 0 && (!pts || !verdict)) || occ_opts_fault(opts)) return ALEGO_ERR_ARG;
+  const alego_static_rule R = rule ? *rule : occ_static_rule_default();
+  if (occ_static_rule_fault(&R) || (R.use_keep_below && !sensor_z)) return ALEGO_ERR_ARG;
+  int64_t local[ALEGO_STATIC_VERDICTS] = {0, 0, 0, 0, 0, 0};
+  occ_mark_host(occ_grid(opts), R, hits, passes, pts, sensor_z, n, verdict, local);
+  if (stats) for (int k = 0; k < ALEGO_STATIC_VERDICTS; ++k) stats[k] = local[k];
+  return 0;
+}
+
 int alego_loc_status(alego_handle* h, int slot, int32_t out[4]) {
   ALEGO_GATE_SLOT(h, slot);
   if (!out) return ALEGO_ERR_ARG;

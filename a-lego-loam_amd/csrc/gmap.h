@@ -49,5 +49,7 @@ void launch_map_archive(const DevCtx& d, const LmCtx& L, int force, hipStream_t 
 // global map of one slot: selected points of archived frames [0, nf) transformed by their archived poses, concatenated into `out`
 // (capacity of the archive's max_points); the point count goes to *n_dev
 void launch_map_assemble(const LmCtx& L, int slot, int nf, int kinds, float4* out, int* off_scratch, int* n_dev, hipStream_t st);
+// its first half alone: off[f] = selected points of frames [0, f), off[nf] = *n_dev = the total (the static map, kernels_occ.hip)
+void launch_map_offsets(const LmCtx& L, int slot, int nf, int kinds, int* off, int* n_dev, hipStream_t st);
 
 #endif

@@ -129,8 +129,11 @@ __global__ void __launch_bounds__(GM_T) map_gather(LmCtx L, int slot, int kinds,
   }
 }
 
+void launch_map_offsets(const LmCtx& L, int slot, int nf, int kinds, int* off, int* n_dev, hipStream_t st) {
+  ALEGO_LAUNCH(map_offsets, dim3(1), dim3(GS_T), 0, st, L, slot, nf, kinds, off, n_dev);
+}
 void launch_map_assemble(const LmCtx& L, int slot, int nf, int kinds, float4* out, int* off_scratch, int* n_dev, hipStream_t st) {
-  ALEGO_LAUNCH(map_offsets, dim3(1), dim3(GS_T), 0, st, L, slot, nf, kinds, off_scratch, n_dev);
+  launch_map_offsets(L, slot, nf, kinds, off_scratch, n_dev, st);
   if (nf > 0) ALEGO_LAUNCH(map_gather, dim3(nf), dim3(GM_T), 0, st, L, slot, kinds, off_scratch, out);
 }
 

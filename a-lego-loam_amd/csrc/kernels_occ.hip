@@ -15,6 +15,15 @@
 //                  The counters go through LDS to six u64 adds per workgroup.  Integer adds: the counts do not depend on the order of arrival.
 //   occ_classify   one thread per output cell (or per column with collapse_z): occ_class / occ_class_merge.
 //   (clearing is two hipMemsetAsync)
+// The static map (alego_occ_mark, alego_map_assemble_static) over the same work items, every frame of a slot:
+//   occ_mark       one workgroup per work item: lane i reads point i of the chunk, transforms it as occ_cast does, forms its verdict from its own cell's
+//                  counts (occ_static_verdict; the neighbour cells are read only by lanes whose own class is 0) and stores the byte and the
+//                  transformed point at the point's position in assembly order (map_offsets' frame offset + index in the frame).  The six
+//                  verdict counts go by ballot + popcount per wavefront through LDS to at most six u64 adds per workgroup, the kept count to
+//                  one int per item.
+//   occ_offsets    one workgroup: exclusive scan of the kept counts, chunk by chunk with a carry (as map_offsets); the total is the cloud's size.
+//   occ_emit       one workgroup per work item: the rank of a kept point among the item's kept lanes (block_excl_scan) places it, stably, at
+//                  out[off[item] + rank]; out is where gv_filter reads its input.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -25,6 +34,7 @@
 #include "occ_math.h"
 #include "prof.h"
 
+#define OCC_SCAN_T 1024  // occ_offsets' workgroup: items scanned per round of its carry
 #define OCC_WALK_MIN 8   // a piece that starts within the ray's first steps walks them instead of seeking
 // development build -DALEGO_OCC_DRY_RUN (tools/occ_timing.py --dry): the adds of the pieces are left out, the walk and its counter stay - what the traversal
 // alone costs ("Measured")
@@ -152,6 +162,89 @@ __global__ void __launch_bounds__(OCC_T) occ_classify(OccDev D, alego_occ_rule r
     for (int z = 0; z < D.G.n[2]; ++z) col = occ_class_merge(col, occ_class(rule, D.hits[z * layer + i], D.passes[z * layer + i]));
     out[i] = col;
   }
+}
+
+// ---- the static map
+__global__ void __launch_bounds__(OCC_T) occ_mark(LmCtx L, OccDev D, OccStatic S, alego_static_rule rule, int slot, int kinds) {
+  __shared__ float s_m[12];
+  __shared__ unsigned s_stat[ALEGO_STATIC_VERDICTS];
+  const int tid = threadIdx.x;
+  const int2 it = S.items[blockIdx.x];
+  const KfArcFrame A = kf_arc_frame(L, slot, it.x);
+  const int n = kf_sel_count(A, kinds);
+  if (tid == 0) {
+    float m[3][4];
+    keypose_matrix(A.pose, m);
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) s_m[r * 4 + c] = m[r][c];
+  }
+  if (tid < ALEGO_STATIC_VERDICTS) s_stat[tid] = 0;
+  __syncthreads();
+  const int i = it.y * OCC_T + tid;
+  const long long pos = (long long)S.frame_off[it.x] + i;
+  int v = -1;
+  if (i < n && pos >= 0 && pos < S.n_pts) {   // (pos < n_pts always, by map_offsets: the test keeps a fault in it from becoming a write outside the arrays)
+    float m[3][4];
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) m[r][c] = s_m[r * 4 + c];
+    const float4 raw = A.pts[kf_arc_index(A.nc, A.ns, kinds, i)];
+    const float4 p = kf_transform(m, raw);
+    const float e[3] = {p.x, p.y, p.z};
+    v = occ_static_verdict(D.G, rule, D.hits, D.passes, e, raw.z);
+    S.verdict[pos] = (uint8_t)v;
+    S.pts[pos] = p;
+  }
+#pragma unroll
+  for (int k = 0; k < ALEGO_STATIC_VERDICTS; ++k) {
+    const unsigned long long b = __ballot(v == k);
+    if ((tid & 63) == 0 && b) atomicAdd(&s_stat[k], (unsigned)__popcll(b));
+  }
+  __syncthreads();
+  if (tid < ALEGO_STATIC_VERDICTS && s_stat[tid]) atomicAdd(S.stats + tid, (unsigned long long)s_stat[tid]);
+  if (tid == 0) {
+    unsigned kept = 0;
+    for (int k = 0; k < ALEGO_STATIC_VERDICTS; ++k) if (k != ALEGO_STATIC_REMOVED) kept += s_stat[k];
+    S.kept[blockIdx.x] = (int)kept;
+  }
+}
+
+// one workgroup: off[i] = kept points of the items [0, i), off[n_items] = *n = the total
+__global__ void __launch_bounds__(OCC_SCAN_T) occ_offsets(const int* kept, int n_items, int* off, int* n) {
+  __shared__ int s_w[OCC_SCAN_T / 64];
+  int carry = 0;
+  for (int i0 = 0; i0 < n_items; i0 += OCC_SCAN_T) {
+    const int i = i0 + threadIdx.x;
+    const int v = i < n_items ? kept[i] : 0;
+    int tot;
+    const int ex = block_excl_scan<OCC_SCAN_T / 64>(v, s_w, &tot);
+    if (i < n_items) off[i] = carry + ex;
+    carry += tot;
+  }
+  if (threadIdx.x == 0) { off[n_items] = carry; *n = carry; }
+}
+
+__global__ void __launch_bounds__(OCC_T) occ_emit(OccStatic S, int kinds, float4* out, int out_cap) {
+  __shared__ int s_w[OCC_T / 64];
+  const int2 it = S.items[blockIdx.x];
+  const int f0 = S.frame_off[it.x], n = S.frame_off[it.x + 1] - f0;   // the frame's selected points, as occ_mark counted them
+  const int i = it.y * OCC_T + threadIdx.x;
+  const long long pos = (long long)f0 + i;
+  const bool keep = i < n && pos >= 0 && pos < S.n_pts && S.verdict[pos] != ALEGO_STATIC_REMOVED;
+  int tot;
+  const int rank = block_excl_scan<OCC_T / 64>(keep ? 1 : 0, s_w, &tot);
+  const long long o = (long long)S.off[blockIdx.x] + rank;
+  if (keep && o >= 0 && o < out_cap) {
+    float4 p = S.pts[pos];
+    if (kinds & 8) p.w = (float)it.x;
+    out[o] = p;
+  }
+}
+
+void launch_occ_mark(const LmCtx& L, const OccDev& D, const OccStatic& S, const alego_static_rule& rule, int slot, int kinds, hipStream_t st) {
+  (void)hipMemsetAsync(S.stats, 0, ALEGO_STATIC_VERDICTS * sizeof(unsigned long long), st);
+  if (S.n_items > 0) ALEGO_LAUNCH(occ_mark, dim3(S.n_items), dim3(OCC_T), 0, st, L, D, S, rule, slot, kinds);
+}
+void launch_occ_emit(const OccStatic& S, int kinds, float4* out, int out_cap, int* n_dev, hipStream_t st) {
+  ALEGO_LAUNCH(occ_offsets, dim3(1), dim3(OCC_SCAN_T), 0, st, S.kept, S.n_items, S.off, n_dev);
+  if (S.n_items > 0) ALEGO_LAUNCH(occ_emit, dim3(S.n_items), dim3(OCC_T), 0, st, S, kinds, out, out_cap);
 }
 
 void launch_occ_cast(const LmCtx& L, const OccDev& D, int slot, int kinds, const int2* items, int n_items, int piece, hipStream_t st) {

@@ -62,6 +62,9 @@ int lm_host_occ_integrate(LmHost* lm, int slot, int first, int n, int kinds, int
 int lm_host_occ_get(LmHost* lm, uint32_t* hits, uint32_t* passes, std::string* err);
 int lm_host_occ_classify(LmHost* lm, const alego_occ_rule& rule, int collapse_z, int8_t* out, std::string* err);
 int lm_host_occ_set_piece(LmHost* lm, int piece);   // alego_debug_occ_piece
+// the static map: verdicts of every selected point of `slot` (returns their number), and the assembly without the removed points
+int lm_host_occ_mark(LmHost* lm, int slot, int kinds, const alego_static_rule& rule, uint8_t* verdict, int cap, int64_t* stats, std::string* err);
+int lm_host_map_assemble_static(LmHost* lm, int slot, int kinds, float leaf, const alego_static_rule& rule, alego_point* out, int cap, int64_t* stats, std::string* err);
 int lm_host_get_local_map(LmHost* lm, int slot, alego_point* corner, int corner_cap, alego_point* surf, int surf_cap, int* n_out, std::string* err);
 int lm_host_voxel_grid(LmHost* lm, hipStream_t st, const alego_point* pts, int n, float leaf, alego_point* out, int cap, std::string* err);
 int lm_host_set_gv_small_max(LmHost* lm, int v);

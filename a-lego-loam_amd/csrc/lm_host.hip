@@ -76,6 +76,11 @@ struct LmHost {
   int occ_piece = OCC_PIECE_DEFAULT;
   DevBuf<int2> occ_items;
   DevBuf<int8_t> occ_cls;
+  // alego_occ_mark / alego_map_assemble_static: the verdicts in assembly order, the kept count per work item, their scan and the six verdict
+  // counts of a call; allocated by the first call and kept
+  DevBuf<uint8_t> st_verdict;
+  DevBuf<int> st_kept, st_off;
+  DevBuf<unsigned long long> st_stats;
 };
 
 namespace {
@@ -1347,6 +1352,17 @@ static int copy_out(const float4* src, int n, alego_point* out, int cap, const c
   if (n > 0 && hipMemcpy(out, src, (size_t)n * 16, hipMemcpyDeviceToHost) != hipSuccess) { *err = std::string(what) + ": copy failed"; return ALEGO_ERR_HIP; }
   return n;
 }
+// the cloud the launches on `s` leave in gv.in, its size in gv.cnt[0], to the caller: as it is (leaf <= 0) or through the device-wide VoxelGrid
+static int assembled_out(LmHost* lm, hipStream_t s, float leaf, alego_point* out, int cap, const char* what, std::string* err) {
+  GvCtx& G = lm->gv;
+  int n = 0;
+  if (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(&n, G.cnt, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { *err = std::string(what) + ": assembly failed"; return ALEGO_ERR_HIP; }
+  if (leaf <= 0.f) return copy_out(G.in, n, out, cap, what, err);
+  if (int r = gv_filter(&G, n, leaf, s, err)) return r == -3 ? ALEGO_ERR_CAPACITY : ALEGO_ERR_HIP;
+  int m = 0;
+  if (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(&m, G.cnt + 1, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { *err = std::string(what) + ": VoxelGrid failed"; return ALEGO_ERR_HIP; }
+  return copy_out(G.out, m, out, cap, what, err);
+}
 int lm_host_map_assemble(LmHost* lm, int slot, int kinds, float leaf, alego_point* out, int cap, std::string* err) {
   int st[AS_W];
   if (int r = map_stat(lm, slot, st, err)) return r;
@@ -1355,13 +1371,7 @@ int lm_host_map_assemble(LmHost* lm, int slot, int kinds, float leaf, alego_poin
   GvCtx& G = lm->gv;
   if (int r = gv_reserve(&G, lm->L.arc_points_cap, err)) return r == -3 ? ALEGO_ERR_CAPACITY : ALEGO_ERR_HIP;
   launch_map_assemble(lm->L, slot, st[AS_FRAMES], kinds, G.in, lm->arc_off, G.cnt, s);
-  int n = 0;
-  if (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(&n, G.cnt, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { *err = "map_assemble: assembly failed"; return ALEGO_ERR_HIP; }
-  if (leaf <= 0.f) return copy_out(G.in, n, out, cap, "map_assemble", err);
-  if (int r = gv_filter(&G, n, leaf, s, err)) return r == -3 ? ALEGO_ERR_CAPACITY : ALEGO_ERR_HIP;
-  int m = 0;
-  if (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(&m, G.cnt + 1, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { *err = "map_assemble: VoxelGrid failed"; return ALEGO_ERR_HIP; }
-  return copy_out(G.out, m, out, cap, "map_assemble", err);
+  return assembled_out(lm, s, leaf, out, cap, "map_assemble", err);
 }
 int lm_host_map_keyposes(LmHost* lm, int slot, alego_point* out, int cap, std::string* err) {
   int st[AS_W];
@@ -1394,6 +1404,22 @@ int lm_host_occ_clear(LmHost* lm, std::string* err) {
   if (hipStreamSynchronize(lm->st[0]) != hipSuccess) { *err = "occ_clear: clearing failed"; return ALEGO_ERR_HIP; }
   return 0;
 }
+// the work list of frames [first, first + n) of `slot` (n > 0) in lm->occ_items: (frame, chunk of OCC_T selected points), frames ascending; returns the
+// items (0: no point is selected) or an error
+static int occ_work_items(LmHost* lm, int slot, int first, int n, int kinds, const char* what, std::string* err) {
+  const LmCtx& L = lm->L;
+  std::vector<int> tab((size_t)n * AT_W);
+  if (hipMemcpy(tab.data(), arc_tab_of(L, slot, first), tab.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { *err = std::string(what) + ": device read failed"; return ALEGO_ERR_HIP; }
+  std::vector<int2> items;
+  for (int f = 0; f < n; ++f) {
+    const int sel = kf_sel_count(kf_arc_frame(L, slot, first + f, tab.data() + (size_t)f * AT_W), kinds);
+    for (int c = 0; c * OCC_T < sel; ++c) items.push_back(make_int2(first + f, c));
+  }
+  if (items.empty()) return 0;
+  if (lm->occ_items.reserve(items.size()) != hipSuccess) { *err = std::string(what) + ": allocation failed"; return ALEGO_ERR_HIP; }
+  if (hipMemcpy(lm->occ_items.p, items.data(), items.size() * sizeof(int2), hipMemcpyHostToDevice) != hipSuccess) { *err = std::string(what) + ": upload failed"; return ALEGO_ERR_HIP; }
+  return (int)items.size();
+}
 int lm_host_occ_integrate(LmHost* lm, int slot, int first, int n, int kinds, int64_t* stats, std::string* err) {
   int st[AS_W];
   if (int r = map_stat(lm, slot, st, err)) return r;   // (behind the slot's own stream: archive appends happen there)
@@ -1405,19 +1431,11 @@ int lm_host_occ_integrate(LmHost* lm, int slot, int first, int n, int kinds, int
   if (stats) for (int k = 0; k < ALEGO_OCC_STATS; ++k) stats[k] = 0;
   if (n == 0) return 0;
   const LmCtx& L = lm->L;
-  std::vector<int> tab((size_t)n * AT_W);
-  if (hipMemcpy(tab.data(), arc_tab_of(L, slot, first), tab.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { *err = "occ_integrate: device read failed"; return ALEGO_ERR_HIP; }
-  std::vector<int2> items;
-  for (int f = 0; f < n; ++f) {
-    const int sel = kf_sel_count(kf_arc_frame(L, slot, first + f, tab.data() + (size_t)f * AT_W), kinds);
-    for (int c = 0; c * OCC_T < sel; ++c) items.push_back(make_int2(first + f, c));
-  }
-  if (items.empty()) return 0;
+  const int n_items = occ_work_items(lm, slot, first, n, kinds, "occ_integrate", err);
+  if (n_items <= 0) return n_items;
   hipStream_t s = stream_of_slot(lm, slot);
-  if (lm->occ_items.reserve(items.size()) != hipSuccess) { *err = "occ_integrate: allocation failed"; return ALEGO_ERR_HIP; }
-  if (hipMemcpy(lm->occ_items.p, items.data(), items.size() * sizeof(int2), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemsetAsync(lm->occ.stats, 0, ALEGO_OCC_STATS * sizeof(unsigned long long), s) != hipSuccess) { *err = "occ_integrate: upload failed"; return ALEGO_ERR_HIP; }
-  launch_occ_cast(L, lm->occ, slot, kinds, lm->occ_items.p, (int)items.size(), lm->occ_piece, s);
+  if (hipMemsetAsync(lm->occ.stats, 0, ALEGO_OCC_STATS * sizeof(unsigned long long), s) != hipSuccess) { *err = "occ_integrate: upload failed"; return ALEGO_ERR_HIP; }
+  launch_occ_cast(L, lm->occ, slot, kinds, lm->occ_items.p, n_items, lm->occ_piece, s);
   unsigned long long got[ALEGO_OCC_STATS];
   if (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(got, lm->occ.stats, sizeof(got), hipMemcpyDeviceToHost) != hipSuccess) { *err = "occ_integrate: ray casting failed"; return ALEGO_ERR_HIP; }
   if (stats) for (int k = 0; k < ALEGO_OCC_STATS; ++k) stats[k] = (int64_t)got[k];
@@ -1436,6 +1454,62 @@ int lm_host_occ_classify(LmHost* lm, const alego_occ_rule& rule, int collapse_z,
   launch_occ_classify(lm->occ, rule, collapse_z, lm->occ_cls.p, lm->st[0]);
   if (hipStreamSynchronize(lm->st[0]) != hipSuccess || hipMemcpy(out, lm->occ_cls.p, n_out, hipMemcpyDeviceToHost) != hipSuccess) { *err = "occ_classify: classification failed"; return ALEGO_ERR_HIP; }
   return 0;
+}
+// ---- the static map (alego_occ_mark / alego_map_assemble_static; kernels_occ.hip) ----
+// Enqueues map_offsets and occ_mark over every frame of `slot` on its stream: verdicts in lm->st_verdict, transformed points in gv.out, both in
+// assembly order.  *n_sel = the selected points; `limit` >= 0 refuses (ALEGO_ERR_CAPACITY, before any launch) more selected points than that.
+static int static_mark(LmHost* lm, int slot, int kinds, const alego_static_rule& rule, int limit, const char* what, OccStatic* S, int* n_sel, std::string* err) {
+  int st[AS_W];
+  if (int r = map_stat(lm, slot, st, err)) return r;
+  const LmCtx& L = lm->L;
+  const int nf = st[AS_FRAMES];
+  GvCtx& G = lm->gv;
+  if (int r = gv_reserve(&G, L.arc_points_cap, err)) return r == -3 ? ALEGO_ERR_CAPACITY : ALEGO_ERR_HIP;
+  const int n_items = nf > 0 ? occ_work_items(lm, slot, 0, nf, kinds & KF_SEL_ALL, what, err) : 0;
+  if (n_items < 0) return n_items;
+  hipStream_t s = stream_of_slot(lm, slot);
+  launch_map_offsets(L, slot, nf, kinds & KF_SEL_ALL, lm->arc_off, G.cnt, s);
+  int n = 0;
+  if (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(&n, G.cnt, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { *err = std::string(what) + ": offsets failed"; return ALEGO_ERR_HIP; }
+  if (n < 0 || n > G.cap) { *err = std::string(what) + ": the archive holds more points than its capacity"; return ALEGO_ERR_HIP; }
+  if (limit >= 0 && n > limit) { *err = std::string(what) + ": output capacity"; return ALEGO_ERR_CAPACITY; }
+  if (lm->st_verdict.reserve(std::max(n, 1)) != hipSuccess || lm->st_kept.reserve(std::max(n_items, 1)) != hipSuccess ||
+      lm->st_off.reserve((size_t)n_items + 1) != hipSuccess || lm->st_stats.reserve(ALEGO_STATIC_VERDICTS) != hipSuccess) { *err = std::string(what) + ": allocation failed"; return ALEGO_ERR_HIP; }
+  *S = OccStatic{lm->occ_items.p, n_items, lm->arc_off, n, lm->st_verdict.p, G.out, lm->st_kept.p, lm->st_off.p, lm->st_stats.p};
+  launch_occ_mark(L, lm->occ, *S, rule, slot, kinds & KF_SEL_ALL, s);
+  *n_sel = n;
+  return 0;
+}
+static int static_stats(LmHost* lm, int64_t* stats, const char* what, std::string* err) {
+  unsigned long long got[ALEGO_STATIC_VERDICTS];
+  if (hipMemcpy(got, lm->st_stats.p, sizeof(got), hipMemcpyDeviceToHost) != hipSuccess) { *err = std::string(what) + ": device read failed"; return ALEGO_ERR_HIP; }
+  if (stats) for (int k = 0; k < ALEGO_STATIC_VERDICTS; ++k) stats[k] = (int64_t)got[k];
+  return 0;
+}
+int lm_host_occ_mark(LmHost* lm, int slot, int kinds, const alego_static_rule& rule, uint8_t* verdict, int cap, int64_t* stats, std::string* err) {
+  if ((kinds & ~15) || !(kinds & KF_SEL_ALL)) { *err = "occ_mark: kinds must select surf / corner / outlier (optionally | FRAME_ID)"; return ALEGO_ERR_ARG; }
+  if (cap < 0 || (cap > 0 && !verdict)) { *err = "occ_mark: a capacity without a buffer, or a negative one"; return ALEGO_ERR_ARG; }
+  const bool count_only = !verdict && cap == 0;
+  OccStatic S;
+  int n = 0;
+  if (int r = static_mark(lm, slot, kinds, rule, count_only ? -1 : cap, "occ_mark", &S, &n, err)) return r;
+  if (hipStreamSynchronize(stream_of_slot(lm, slot)) != hipSuccess) { *err = "occ_mark: marking failed"; return ALEGO_ERR_HIP; }
+  if (int r = static_stats(lm, stats, "occ_mark", err)) return r;
+  if (!count_only && n > 0 && hipMemcpy(verdict, S.verdict, (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) { *err = "occ_mark: copy failed"; return ALEGO_ERR_HIP; }
+  return n;
+}
+int lm_host_map_assemble_static(LmHost* lm, int slot, int kinds, float leaf, const alego_static_rule& rule, alego_point* out, int cap, int64_t* stats, std::string* err) {
+  if ((kinds & ~15) || !(kinds & KF_SEL_ALL)) { *err = "map_assemble_static: kinds must select surf / corner / outlier (optionally | FRAME_ID)"; return ALEGO_ERR_ARG; }
+  if (cap < 0) { *err = "map_assemble_static: negative capacity"; return ALEGO_ERR_ARG; }
+  OccStatic S;
+  int n = 0;
+  if (int r = static_mark(lm, slot, kinds, rule, -1, "map_assemble_static", &S, &n, err)) return r;
+  hipStream_t s = stream_of_slot(lm, slot);
+  GvCtx& G = lm->gv;
+  launch_occ_emit(S, kinds, G.in, G.cap, G.cnt, s);   // the kept points end where gv_filter reads its input
+  if (hipStreamSynchronize(s) != hipSuccess) { *err = "map_assemble_static: compaction failed"; return ALEGO_ERR_HIP; }
+  if (int r = static_stats(lm, stats, "map_assemble_static", err)) return r;
+  return assembled_out(lm, s, leaf, out, cap, "map_assemble_static", err);
 }
 int lm_host_get_local_map(LmHost* lm, int slot, alego_point* corner, int corner_cap, alego_point* surf, int surf_cap, int* n_out, std::string* err) {
   const LmCtx& L = lm->L;

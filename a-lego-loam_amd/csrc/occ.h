@@ -24,4 +24,19 @@ void launch_occ_cast(const LmCtx& L, const OccDev& D, int slot, int kinds, const
 // out[cells], or out[n0 n1] with collapse_z
 void launch_occ_classify(const OccDev& D, alego_occ_rule rule, int collapse_z, int8_t* out, hipStream_t st);
 void launch_occ_clear(const OccDev& D, hipStream_t st);
+
+// the static map over the same work items, all frames of `slot`
+struct OccStatic {
+  const int2* items; int n_items;
+  const int* frame_off;             // map_offsets' offsets of the frames in assembly order
+  int n_pts;                        // selected points = capacity of verdict / pts
+  uint8_t* verdict;                 // [n_pts] in assembly order
+  float4* pts;                      // [n_pts] the transformed points in assembly order (the assembly scratch)
+  int* kept;                        // [n_items] kept points per item
+  int* off;                         // [n_items + 1] their exclusive scan
+  unsigned long long* stats;        // [ALEGO_STATIC_VERDICTS], zeroed by the launch
+};
+void launch_occ_mark(const LmCtx& L, const OccDev& D, const OccStatic& S, const alego_static_rule& rule, int slot, int kinds, hipStream_t st);
+// the kept points of S.pts, stably, to out[0, out_cap); their number to *n_dev; kinds & ALEGO_MAP_FRAME_ID: w = frame index
+void launch_occ_emit(const OccStatic& S, int kinds, float4* out, int out_cap, int* n_dev, hipStream_t st);
 #endif

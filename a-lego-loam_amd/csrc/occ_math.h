@@ -1,5 +1,5 @@
 // occ_math.h — the rule of the occupancy grid (alego_occ_*), shared by the kernels (kernels_occ.hip) and the host twins
-// (alego_occ_ray_host, alego_occ_integrate_host, alego_occ_classify_host): one definition, so the two cannot drift apart.  Plain C++ that a
+// (alego_occ_ray_host, alego_occ_integrate_host, alego_occ_classify_host; alego_occ_mark_host of the static map, section 25): one definition, so the two cannot drift apart.  Plain C++ that a
 // host compiler reads without the HIP runtime; no contraction (-ffp-contract=off).  The rule is the project's own.
 //
 // GRID: origin[3] is the world position of the corner of cell (0, 0, 0), cell[3] > 0 the edge lengths, n[3] >= 1 the cells per axis
@@ -187,6 +187,58 @@ OCC_FN int8_t occ_class(const alego_occ_rule& r, uint32_t hits, uint32_t passes)
 }
 // a column's class from its layers': 100 if any is 100, else 0 if any is 0, else -1
 OCC_FN int8_t occ_class_merge(int8_t column, int8_t layer) { return column == 100 || layer == 100 ? 100 : (column == 0 || layer == 0 ? 0 : -1); }
+
+// ---- the static map (alego_occ_mark, alego_map_assemble_static, alego_occ_mark_host) ----
+// A point of the archive is judged by its own cell: e = the f32 world position map_gather writes, widened to f64, c_k = floor(occ_coord(G, k, e_k)),
+// the expression that gives c1 in occ_ray_setup.  The tests in order: OUTSIDE (a non-finite coordinate, |q_k| > 2^30, a cell outside the grid),
+// BELOW (use_keep_below and sensor_z < keep_below), OCCUPIED (class 100), UNKNOWN (class -1), NEIGHBOUR (class 0, protect_radius r > 0 and a cell
+// of the grid within Chebyshev distance r of class 100), REMOVED (class 0 otherwise).  Only REMOVED points leave the map.
+inline const char* occ_static_rule_fault(const alego_static_rule* r) {
+  if (const char* why = occ_rule_fault(&r->occ)) return why;
+  if (r->protect_radius < 0 || r->protect_radius > 2) return "protect_radius must lie in [0, 2]";
+  if (r->use_keep_below && !occ_finite((double)r->keep_below)) return "keep_below is not finite";
+  return nullptr;
+}
+inline alego_static_rule occ_static_rule_default() { return alego_static_rule{{1, 2, 1, 0}, 0, 0, 0.f, 0}; }
+// hits / passes: the grid's counts (read only at cells inside the grid)
+OCC_FN uint8_t occ_static_verdict(const OccGrid& G, const alego_static_rule& r, const uint32_t* hits, const uint32_t* passes, const float* ef, float sensor_z) {
+  int32_t c[3];
+  for (int k = 0; k < 3; ++k) {
+    const double x = (double)ef[k];
+    if (!occ_finite(x)) return ALEGO_STATIC_OUTSIDE;
+    const double q = occ_coord(G, k, x);
+    if (!(fabs(q) <= OCC_COORD_MAX)) return ALEGO_STATIC_OUTSIDE;
+    c[k] = (int32_t)floor(q);
+  }
+  if (!occ_inside(G, c)) return ALEGO_STATIC_OUTSIDE;
+  if (r.use_keep_below && sensor_z < r.keep_below) return ALEGO_STATIC_BELOW;
+  const size_t i = occ_index(G, c);
+  const int8_t cls = occ_class(r.occ, hits[i], passes[i]);
+  if (cls == 100) return ALEGO_STATIC_OCCUPIED;
+  if (cls < 0) return ALEGO_STATIC_UNKNOWN;
+  const int32_t rad = r.protect_radius < 2 ? r.protect_radius : 2;   // (the host refuses more: a bound the loops can rely on)
+  if (rad > 0) {
+    int32_t lo[3], hi[3];
+    for (int k = 0; k < 3; ++k) { lo[k] = c[k] - rad < 0 ? 0 : c[k] - rad; hi[k] = c[k] + rad > G.n[k] - 1 ? G.n[k] - 1 : c[k] + rad; }
+    int32_t d[3];
+    for (d[2] = lo[2]; d[2] <= hi[2]; ++d[2])
+      for (d[1] = lo[1]; d[1] <= hi[1]; ++d[1])
+        for (d[0] = lo[0]; d[0] <= hi[0]; ++d[0]) {
+          const size_t j = occ_index(G, d);
+          if (occ_class(r.occ, hits[j], passes[j]) == 100) return ALEGO_STATIC_NEIGHBOUR;
+        }
+  }
+  return ALEGO_STATIC_REMOVED;
+}
+inline void occ_mark_host(const OccGrid& G, const alego_static_rule& r, const uint32_t* hits, const uint32_t* passes, const alego_point* pts, const float* sensor_z,
+                          int32_t n, uint8_t* verdict, int64_t* stats /* [ALEGO_STATIC_VERDICTS] */) {
+  for (int32_t i = 0; i < n; ++i) {
+    const float e[3] = {pts[i].x, pts[i].y, pts[i].z};
+    const uint8_t v = occ_static_verdict(G, r, hits, passes, e, sensor_z ? sensor_z[i] : 0.f);
+    verdict[i] = v;
+    stats[v] += 1;
+  }
+}
 
 // ---- the host twins ----
 // The visited cells of one ray in order, the first `cap` of them to cells3[3 i + k]; *hit = 1 when the last cell takes a hit.  Returns the cells visited or a skip code.

@@ -77,6 +77,13 @@
 //       highest, so that ground returns leave the layer from below and count as free space only.  Writes DIR/occupancy.pgm (P5; 254 free,
 //       0 occupied, 205 unknown; the top row is the largest y, as map_server reads it) and DIR/occupancy.yaml, and prints one line
 //       "occupancy: origin X Y Z cell CX CY CZ n NX NY NZ max_range R rays N short S truncated T culled C bad B updates U".
+//   --save-map DIR + --static CELL [--occ-range R] [--static-keep-below Z] [--static-protect RADIUS]
+//       the static map (alego_map_assemble_static): after --merge / --thin and the files above, a 3-D grid of cubes of CELL
+//       metres over the key poses' bounding box plus R (default 30 m) in x and y and from 3 m below the lowest key pose to 3 m above the highest in
+//       z takes every archived point as a ray (max_range = R); DIR/static.pcd is global.pcd (all kinds, --map-leaf applied) without the points
+//       that lie in cells seen free: what moved while the map was made.  Z keeps every point whose sensor-frame z is below Z (ground returns),
+//       RADIUS keeps points next to an occupied cell.  Prints one line
+//       "static: kept_occupied A unknown B outside C below D neighbour E removed F of N".  Not together with --occupancy (one grid per handle).
 // Every scan goes through ImageProjection -> LaserOdometry -> LaserMapping with one alego_scan_process call, as a single nodelet
 // manager would run them (launch/test.launch:6-10); every new key frame is pulled across the boundary the way the reference's
 // pose-graph thread reads cloud_keyposes_6d_ (laserMapping.cpp:586-596); one JSON line with the final poses is printed.
@@ -98,7 +105,8 @@ extern "C" int alego_synth_scan(const alego_params* P, int stream, long scan_ind
 
 int main(int argc, char** argv) {
   std::string bag_path, topic = "/lslidar_point_cloud", map_dir, occ_dir;
-  double occ_cell = 0.0, occ_range = 30.0;
+  double occ_cell = 0.0, occ_range = 30.0, static_cell = 0.0;
+  alego_static_rule static_rule = {{1, 2, 1, 0}, 0, 0, 0.f, 0};
   float map_leaf = 0.f;
   int map_frames = 4096, map_points = 1 << 24, loop_every = 0, close_every = 0, max_loops = 16;
   bool list_only = false, standalone = false, localize = false, relocalize = false, appearance = false, merge = false, on_device = false, regcov = false, regcov_graph = false, remap = false;
@@ -135,6 +143,9 @@ int main(int argc, char** argv) {
     else if (a == "--thin") thin_dist = std::atof(val());
     else if (a == "--occupancy") { occ_cell = std::atof(val()); occ_dir = val(); }
     else if (a == "--occ-range") occ_range = std::atof(val());
+    else if (a == "--static") static_cell = std::atof(val());
+    else if (a == "--static-keep-below") { static_rule.use_keep_below = 1; static_rule.keep_below = (float)std::atof(val()); }
+    else if (a == "--static-protect") static_rule.protect_radius = std::atoi(val());
     else if (a == "--recent-keyframes") recent_keyframes = std::atoi(val());
     else if (a == "--localize") localize = true;
     else if (a == "--on-device") on_device = true;
@@ -189,6 +200,9 @@ int main(int argc, char** argv) {
     return 1;
   }
   if (!occ_dir.empty() && !(occ_cell > 0.0 && occ_range > 0.0)) { std::fprintf(stderr, "--occupancy needs a positive CELL (and --occ-range a positive R)\n"); alego_destroy(h); return 2; }
+  if (static_cell != 0.0 && (map_dir.empty() || !occ_dir.empty() || !(static_cell > 0.0 && occ_range > 0.0))) {
+    std::fprintf(stderr, "--static needs --save-map DIR and a positive CELL, and goes without --occupancy\n"); alego_destroy(h); return 2;
+  }
   if ((!map_dir.empty() || !occ_dir.empty() || loop_every > 0 || close_every > 0 || localize || align_start >= 0 || thin_dist >= 0.0 || regcov_graph) && alego_map_enable(h, map_frames, map_points) != ALEGO_OK) {
     std::fprintf(stderr, "map_enable: %s\n", alego_last_error(h)); alego_destroy(h); return 1;
   }
@@ -438,6 +452,40 @@ int main(int argc, char** argv) {
     int32_t st[4];
     if (!rc && alego_map_status(h, 0, st) == ALEGO_OK && st[1] > 0) std::fprintf(stderr, "map: %d key frames did not fit the archive (--map-frames / --map-points)\n", st[1]);
     if (rc) std::fprintf(stderr, "save map to %s: %s\n", map_dir.c_str(), alego_last_error(h));
+  }
+  if (static_cell > 0.0 && !rc) {   // the static map of slot 0's archive at the key poses that hold now
+    std::vector<alego_point> kp;
+    int n = alego_map_keyposes(h, 0, nullptr, 0);
+    if (n > 0) { kp.resize(n); n = alego_map_keyposes(h, 0, kp.data(), n); }
+    if (n <= 0) { std::fprintf(stderr, "static: no key frame archived\n"); alego_destroy(h); return 1; }
+    double lo[3] = {kp[0].x, kp[0].y, kp[0].z}, hi[3] = {kp[0].x, kp[0].y, kp[0].z};
+    for (int i = 1; i < n; ++i) {
+      const double v[3] = {kp[i].x, kp[i].y, kp[i].z};
+      for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], v[a]); hi[a] = std::max(hi[a], v[a]); }
+    }
+    alego_occ_opts oo{};
+    for (int a = 0; a < 3; ++a) {
+      const double margin = a < 2 ? occ_range : 3.0;
+      oo.cell[a] = static_cell;
+      oo.origin[a] = std::floor((lo[a] - margin) / static_cell) * static_cell;
+      oo.n[a] = (int32_t)std::ceil((hi[a] + margin - oo.origin[a]) / static_cell);
+    }
+    oo.min_range = 0.0; oo.max_range = occ_range;
+    const int all = ALEGO_MAP_SURF | ALEGO_MAP_CORNER | ALEGO_MAP_OUTLIER;
+    int64_t st[ALEGO_STATIC_VERDICTS];
+    std::vector<alego_point> cloud(1);
+    int m = -1;
+    if (alego_occ_enable(h, &oo) == ALEGO_OK && alego_occ_integrate(h, 0, 0, -1, all, nullptr) == ALEGO_OK) {
+      m = alego_map_assemble_static(h, 0, all, map_leaf, &static_rule, nullptr, 0, nullptr);
+      if (m >= 0) { cloud.resize(m > 0 ? m : 1); m = alego_map_assemble_static(h, 0, all, map_leaf, &static_rule, cloud.data(), m, st); }
+    }
+    if (m < 0) { std::fprintf(stderr, "static: %s\n", alego_last_error(h)); alego_destroy(h); return 1; }
+    if (alego_write_pcd((map_dir + "/static.pcd").c_str(), cloud.data(), m) != ALEGO_OK) { std::fprintf(stderr, "static: cannot write to %s\n", map_dir.c_str()); rc = 1; }
+    long long total = 0;
+    for (int k = 0; k < ALEGO_STATIC_VERDICTS; ++k) total += st[k];
+    std::printf("static: kept_occupied %lld unknown %lld outside %lld below %lld neighbour %lld removed %lld of %lld\n", (long long)st[ALEGO_STATIC_OCCUPIED],
+                (long long)st[ALEGO_STATIC_UNKNOWN], (long long)st[ALEGO_STATIC_OUTSIDE], (long long)st[ALEGO_STATIC_BELOW], (long long)st[ALEGO_STATIC_NEIGHBOUR],
+                (long long)st[ALEGO_STATIC_REMOVED], total);
   }
   if (!occ_dir.empty() && !rc) {   // the occupancy grid of slot 0's archive at the key poses that hold now
     std::vector<alego_point> kp;

@@ -1029,6 +1029,49 @@ int alego_occ_classify_host(const alego_occ_opts* opts, const alego_occ_rule* ru
  * walks a whole ray, the baseline tools/occ_timing.py measures next to the default).  The counts do not depend on it. */
 int alego_debug_occ_piece(alego_handle* h, int32_t piece);
 
+/* ---- static map: the archive's points that the occupancy grid saw through are dropped (csrc/kernels_occ.hip, csrc/occ_math.h; DESIGN.md
+ * section 25).  Not part of the reference.  A car that stood somewhere for one key frame stays in the assembled map as a trail of points;
+ * the grid holds the evidence against them: their cells were hit once and passed through many times.  Every point of the archive is
+ * judged by its OWN cell, against the counts as they stand (the caller integrates first: typically alego_occ_clear, then
+ * alego_occ_integrate of all frames with the final poses).  Nothing is allocated or launched without these calls; the archive is not changed.
+ *
+ * CELL     the point as alego_map_assemble gives it (f32), widened to f64; c_k = floor((x_k - origin_k) / cell_k), the expression that
+ *          gives a ray's end cell: after an integration without ranges a point's cell is the cell its own ray hit.
+ * VERDICTS one uint8_t per point; the tests are made in this order:
+ *   2 OUTSIDE    a coordinate is non-finite, |(x_k - origin_k) / cell_k| > 2^30, or the cell lies outside the grid                kept
+ *   3 BELOW      use_keep_below and the point's sensor-frame z (the archived z, f32, z up) < keep_below: ground returns, whose cells
+ *                grazing rays pass many times per hit                                                                                kept
+ *   0 OCCUPIED   the cell's class under rule.occ is 100                                                                             kept
+ *   1 UNKNOWN    the class is -1                                                                                                    kept
+ *   4 NEIGHBOUR  the class is 0, protect_radius = r > 0 and a cell of the grid within Chebyshev distance r is of class 100: a wall's
+ *                points that fell into the cell next to the wall's own                                                               kept
+ *   5 REMOVED    the class is 0 otherwise                                                                                           removed
+ * rule = NULL: {{1, 2, 1, 0}, 0, 0, 0, 0}.  ALEGO_ERR_ARG: a negative weight or min_hits, protect_radius outside [0, 2], a non-finite
+ * keep_below with use_keep_below set.  Integer and exact f64 arithmetic: device and host agree exactly.
+ *
+ * alego_occ_mark             returns the number of selected points; verdict[i] belongs to point i of alego_map_assemble(h, slot, kinds & 7,
+ *                            leaf 0).  verdict = NULL with cap = 0 only counts (stats is still filled); cap below the count:
+ *                            ALEGO_ERR_CAPACITY, nothing written.  stats (may be NULL) gets the number of points per verdict.
+ * alego_map_assemble_static  alego_map_assemble's contract (kinds with ALEGO_MAP_FRAME_ID, leaf, count-only, ALEGO_ERR_CAPACITY, return
+ *                            value) over the kept points: leaf <= 0 gives the kept points of the raw assembly, in their order and bit for
+ *                            bit; leaf > 0 what alego_voxel_grid gives for that cloud.
+ * Both are synchronous, behind the slot's own stream, and need a mapping handle with the archive on and the grid enabled.
+ * alego_occ_mark_host        the host twin (no device, no handle): pts are world points, sensor_z[i] the sensor-frame z of point i (may be
+ *                            NULL when use_keep_below is 0, else ALEGO_ERR_ARG); verdict[n] and stats (may be NULL; set, not added to). */
+typedef struct alego_static_rule {
+  alego_occ_rule occ;
+  int32_t protect_radius;   /* 0..2 */
+  int32_t use_keep_below;
+  float keep_below;
+  int32_t pad;
+} alego_static_rule;
+enum { ALEGO_STATIC_OCCUPIED = 0, ALEGO_STATIC_UNKNOWN, ALEGO_STATIC_OUTSIDE, ALEGO_STATIC_BELOW, ALEGO_STATIC_NEIGHBOUR, ALEGO_STATIC_REMOVED, ALEGO_STATIC_VERDICTS };
+int alego_occ_mark(alego_handle* h, int slot, int kinds, const alego_static_rule* rule, uint8_t* verdict, int32_t cap, int64_t stats[ALEGO_STATIC_VERDICTS]);
+int alego_map_assemble_static(alego_handle* h, int slot, int kinds, float leaf, const alego_static_rule* rule, alego_point* out, int32_t cap,
+                              int64_t stats[ALEGO_STATIC_VERDICTS]);
+int alego_occ_mark_host(const alego_occ_opts* opts, const alego_static_rule* rule, const uint32_t* hits, const uint32_t* passes, const alego_point* pts,
+                        const float* sensor_z, int32_t n, uint8_t* verdict, int64_t stats[ALEGO_STATIC_VERDICTS]);
+
 /* ---- one scan-to-map registration sharded over the GPUs of a node (BASELINE.json config 5) ----------------
  * One process per GPU; every rank feeds its handle the SAME scans and so keeps a bit-identical replica of the stream's state
  * (ImageProjection, feature extraction, LaserOdometry and the local map are cheap and are computed redundantly).  What is split
