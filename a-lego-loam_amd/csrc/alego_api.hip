@@ -313,6 +313,7 @@ int alego_create(const alego_params* params, int device, int n_slots, int ring_l
   d.opt_fo_spin = env_int("ALEGO_FE_SPIN", 0);
   d.opt_fo_pad8 = env_int("ALEGO_FE_PAD8", 0) != 0;
   d.opt_map_merge = env_int("ALEGO_MAP_MERGE", 1) != 0;
+  d.opt_lm_total_merge = env_int("ALEGO_LM_TOTAL_MERGE", 1) != 0;
   d.opt_solve_full_eval = env_int("ALEGO_SOLVE_FULL_EVAL", 0) != 0;
   d.fcap[F_SHARP] = d.cap_sharp * d.NS; d.fcap[F_LSHARP] = d.cap_lsharp * d.NS; d.fcap[F_FLAT] = d.cap_flat * d.NS; d.fcap[F_LFLAT] = d.N;
   d.lo_qcap_surf = d.fcap[F_FLAT]; d.lo_qcap_corner = d.fcap[F_SHARP];
@@ -1073,6 +1074,7 @@ int alego_debug_set_option(alego_handle* h, const char* name, int value) {
     else HIP_TRY(h, hipMemset2D(scal_of(d, 0) + SC_FE_ERR, scal_n() * sizeof(int), 0, 4, d.n_slots));
   }
   else if (s == "ALEGO_MAP_MERGE") { if (int r = lm_host_set_map_merge(h->lm, value != 0, &h->err)) return r; d.opt_map_merge = value != 0; }
+  else if (s == "ALEGO_LM_TOTAL_MERGE") d.opt_lm_total_merge = value != 0;   // (both sequences leave the same clouds and counts; lm_total_merge's list counters are its own, vox_plan never writes them)
   else if (s == "ALEGO_IP_FAST") d.ip_fast = h->ip_fast_capable & value;
   else if (s == "ALEGO_POKE_GUARD") { HIP_TRY(h, hipMemset(scal_of(d, d.n_slots) + value, 0xFF, 4)); }   // tests of the guard pages: a write `value` ints past the end of an array
   else if (s == "ALEGO_GV_SMALL_MAX") { WAIT_ALL(h); return lm_host_set_gv_small_max(h->lm, value); }   // tools/gmap_timing.py: largest cloud alego_voxel_grid gives to one workgroup

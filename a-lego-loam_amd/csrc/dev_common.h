@@ -47,6 +47,7 @@ struct DevCtx {
   int opt_lo_box_lds;   // ALEGO_LO_BOX_LDS boxes staged in LDS by lo_assoc (0: straight from HBM)
   int opt_map_merge;    // ALEGO_MAP_MERGE  1: local map from the pre-sorted key frames; 0: concat + radix VoxelGrid
   int opt_ip_screen;    // ALEGO_IP_SCREEN  1: ip_fused_h / ip_fused_w / ipb_band decide ground and edge tests in f32 where f32 can (ip_pred.h), in fp64 where it cannot; 0: every site in fp64
+  int opt_lm_total_merge;    // ALEGO_LM_TOTAL_MERGE  1: lm_total_merge (small /outlier clouds filtered and laser_surf_total_ds_ merged by one light kernel); 0: lm_total + the second VoxelGrid round
   int opt_solve_full_eval;   // ALEGO_SOLVE_FULL_EVAL  0: lo_solve_t / lm_solve evaluate a candidate for its cost and the normal equations only where a step is computed from them; 1: every point in full
   // ---- input ring ----
   float4* in_pts;  // [slot][ring][Pcap]

@@ -4,7 +4,8 @@
 //   lm_prepare     laserOdomHandler + mainLoop gate + transformAssociateToMap; stages the inputs
 //   lm_concat      a19: concatenation of the <= K most recent key frames (already in the map frame)
 //   (voxel.h)      a19/a20: VoxelGrid of the map (only when the key-frame set changed) and of the scan
-//   lm_total       laser_surf_total_ = laser_surf_ds_ + laser_outlier_ds_ (:337-340)
+//   lm_total       laser_surf_total_ = laser_surf_ds_ + laser_outlier_ds_ (:337-340); ALEGO_LM_TOTAL_MERGE=0 only
+//   lm_total_merge laser_outlier_ds_ of a small /outlier cloud and laser_surf_total_ds_ by merging (:333-342; vox_merge.h)
 //   lm_grid_*      uniform grid (cell >= 1 m) over the down-sampled maps: exact 5-NN for every
 //                  accepted query because acceptance needs d5^2 < 1.0 (:376,:426) — replaces KdTreeFLANN
 //   lm_assoc       a21/a22: 5-NN, 3x3 scatter eigen-decomposition (line) / 5x3 Householder LS (plane)
@@ -23,6 +24,7 @@
 #include "kf_store.h"
 #include "gmap.h"
 #include "vgrid.h"
+#include "vox_merge.h"
 
 #define LM_BLOCK 256
 
@@ -178,6 +180,207 @@ __global__ void __launch_bounds__(LM_BLOCK) lm_total(DevCtx d, LmCtx L) {
   for (int i = blockIdx.x * LM_BLOCK + threadIdx.x; i < ns; i += gridDim.x * LM_BLOCK) t[i] = s[i];
   for (int i = blockIdx.x * LM_BLOCK + threadIdx.x; i < no; i += gridDim.x * LM_BLOCK) t[ns + i] = o[i];
   if (blockIdx.x == 0 && threadIdx.x == 0) li[LI_NTOTAL] = ns + no;
+}
+
+// ---- lm_total_merge (ALEGO_LM_TOTAL_MERGE, the default): one light workgroup per slot in the place of lm_total, the second VoxelGrid round and, for
+// a small /outlier cloud, the first round's outlier job.  The rules are vox_merge.h's.
+//   a  /outlier of at most LT_OCAP points: laser_outlier_ds_ = VoxelGrid(lm_leaf_outlier) by rank-by-counting (vox_plan leaves that job out)
+//   b  laser_surf_total_ds_ by merging laser_surf_ds_, which round 1 left in voxel-key order, with laser_outlier_ds_
+// A slot that vm_refuse turns down gets lm_total's concatenation and puts its round-2 job on the work lists of the group's second VoxelGrid
+// context, which vox_plan would have written: one vox_small launch with a small grid stays behind for them.  No __threadfence() here: with one
+// workgroup per slot an agent-scope fence each costs the other stream groups' kernels more than the second round did.
+#define LT_T 256
+#define LT_B 8   // S points a thread has in flight
+DEV_INLINE void lt_box_reduce(float mn[3], float mx[3], float (*s_red)[LT_T / 64]) {   // every thread gets the workgroup's box
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();   // the previous readers of s_red are done
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    bfly_minmax_f32(mn[a], mx[a]);
+    if (lane == 0) { s_red[a][wave] = mn[a]; s_red[3 + a][wave] = mx[a]; }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    mn[a] = s_red[a][0]; mx[a] = s_red[3 + a][0];
+#pragma unroll
+    for (int w = 1; w < LT_T / 64; ++w) { mn[a] = fminf(mn[a], s_red[a][w]); mx[a] = fmaxf(mx[a], s_red[3 + a][w]); }
+  }
+}
+// s_key[0, n) -> s_skey (the keys in stable order) and s_idx (their input positions); n <= LT_OCAP
+DEV_INLINE void lt_order(const vm_u64* s_key, vm_u64* s_skey, unsigned short* s_idx, int n) {
+  __syncthreads();
+  for (int i = threadIdx.x; i < n; i += LT_T) { const int r = vm_rank(s_key, n, i); s_skey[r] = s_key[i]; s_idx[r] = (unsigned short)i; }
+  __syncthreads();
+}
+
+// grid (slots)
+__global__ void __launch_bounds__(LT_T) lm_total_merge(DevCtx d, LmCtx L, LtLists W) {
+  const int slot = blockIdx.x + d.slot0, tid = threadIdx.x;
+  int* li = lip(L, slot);
+  __shared__ vm_u64 s_key[LT_OCAP], s_skey[LT_OCAP];
+  __shared__ unsigned short s_idx[LT_OCAP];
+  __shared__ int s_osb[LT_OCAP];       // part b: an O element between two S keys: owner thread << 16 | S heads of the owner's chunk before it; -1: its key is one of S's
+  __shared__ int s_oop[LT_OCAP + 1];   // part b: voxels of O elements alone among the sorted ranks below j
+  __shared__ int s_base[LT_T];         // part b: S heads before a thread's chunk
+  __shared__ float s_red[6][LT_T / 64];
+  __shared__ int s_w[LT_T / 64];
+  int state = 0;   // 0: nothing left to do for the slot; 1 / 2: its round-2 job goes on the small / big list
+  if (li[LI_RUN]) {
+    const float FMAX = 3.402823466e+38f;
+    int no = li[LI_NCUR_O];
+    // ---- a: the outlier filter (bit for bit what vox_small_job writes)
+    const int nin = min(li[LI_NIN_O], L.in_cap_o);
+    if (nin <= LT_OCAP) {
+      const float4* in = L.in_outl + (size_t)slot * L.in_cap_o;
+      float4* out = L.cur_outl_ds + (size_t)slot * L.kf_cap_o;
+      const int cap = L.kf_cap_o;
+      const float inv = 1.0f / d.P.lm_leaf_outlier;
+      int nvox = 0, full = nin;   // full: what the filter produces before the capacity cuts it
+      if (nin > 0) {
+        float mn[3] = {FMAX, FMAX, FMAX}, mx[3] = {-FMAX, -FMAX, -FMAX};
+        for (int i = tid; i < nin; i += LT_T) vgr_box_add(mn, mx, in[i]);
+        lt_box_reduce(mn, mx, s_red);
+        if (vgr_leaf_too_small(mn, mx, inv)) {   // output = input
+          for (int i = tid; i < min(nin, cap); i += LT_T) out[i] = in[i];
+        } else {
+          const VgrGeom g = vgr_geom(mn, mx, inv);
+          for (int i = tid; i < nin; i += LT_T) s_key[i] = vgr_id(g, in[i], inv);   // (u32 ids, wrap included, in the order of their bits)
+          lt_order(s_key, s_skey, s_idx, nin);
+          for (int t0 = 0; t0 < nin; t0 += LT_T) {
+            const int m = t0 + tid;
+            const bool head = m < nin && (m == 0 || s_skey[m] != s_skey[m - 1]);
+            int tot;
+            const int r = nvox + block_excl_scan<LT_T / 64>(head ? 1 : 0, s_w, &tot);
+            if (head && r < cap) {
+              int b = m + 1;
+              while (b < nin && s_skey[b] == s_skey[m]) ++b;
+              out[r] = vm_centroid([&](int j) { return in[s_idx[j]]; }, m, b);
+            }
+            nvox += tot;
+          }
+          full = nvox;
+        }
+      }
+      no = min(full, cap);
+      if (tid == 0) { li[LI_NCUR_O] = no; if (full > cap) li[LI_OVERFLOW] = 1; }
+      __syncthreads();   // laser_outlier_ds_ is complete for part b; s_key / s_skey / s_idx are free again
+    }
+    // ---- b: laser_surf_total_ = laser_surf_ds_ ++ laser_outlier_ds_ (lm_total's truncation), filtered by merging.  The merged cloud itself is never
+    // written: nothing reads laser_surf_total_ but the filter.  S's stable-merge position is i + #{O keys < its key} and O's j + #{S keys <= its key}
+    // (vox_merge.h), so a voxel's run is an S run followed by the O elements of that key, and its output rank the S heads and the O-only voxels before
+    // it.  Every thread owns a contiguous chunk of S and keeps LT_B loads in flight: the kernel is a chain of memory round trips, and the wavefront
+    // slots it holds while it waits are what it costs the kernels of the other stream groups.
+    const int ns = li[LI_NCUR_S];
+    if (ns + no > L.total_cap) { no = L.total_cap - ns; if (tid == 0) li[LI_OVERFLOW] = 1; }
+    const int n = ns + no, cap = L.total_cap;
+    const float4* S = L.cur_surf_ds + (size_t)slot * L.kf_cap_s;
+    const float4* O = L.cur_outl_ds + (size_t)slot * L.kf_cap_o;
+    float4* out = L.cur_total_ds + (size_t)slot * L.total_cap;
+    const float inv = 1.0f / d.P.lm_leaf_surf;
+    const int c = (ns + LT_T - 1) / LT_T, c0 = min(ns, tid * c), c1 = min(ns, c0 + c);   // this thread's S elements
+    bool refuse = no > LT_OCAP;
+    int heads = 0;   // S elements of the chunk that start a voxel
+    if (!refuse && n > 0) {
+      float mn[3] = {FMAX, FMAX, FMAX}, mx[3] = {-FMAX, -FMAX, -FMAX};
+      int good = 1;   // finite, and S in key order
+      for (int j = tid; j < no; j += LT_T) { const float4 p = O[j]; vgr_box_add(mn, mx, p); good &= vm_finite(p); s_key[j] = vkey_of(p, inv); s_osb[j] = -1; }
+      lt_order(s_key, s_skey, s_idx, no);
+      // S, first pass: box, order, voxel heads, and the O elements that fall strictly between two S keys (s_osb: thread << 16 | its heads before them)
+      vm_u64 kprev = 0;
+      int ole_prev = 0;   // #{O keys <= the previous S key}
+      if (c0 > 0 && c0 < c1) { kprev = vkey_of(S[c0 - 1], inv); ole_prev = vm_count_le(s_skey, no, kprev); }
+      for (int b0 = c0; b0 < c1; b0 += LT_B) {
+        float4 p[LT_B];
+#pragma unroll
+        for (int k = 0; k < LT_B; ++k) p[k] = S[min(b0 + k, c1 - 1)];
+#pragma unroll
+        for (int k = 0; k < LT_B; ++k) {
+          const int i = b0 + k;
+          if (i < c1) {
+            vgr_box_add(mn, mx, p[k]);
+            const vm_u64 key = vkey_of(p[k], inv);
+            good &= vm_finite(p[k]) && (i == 0 || kprev <= key);
+            const int ol = vm_count_less(s_skey, no, key);
+            for (int j = ole_prev; j < ol; ++j) s_osb[j] = tid << 16 | heads;
+            heads += (i == 0 || kprev != key) ? 1 : 0;
+            kprev = key; ole_prev = vm_count_le(s_skey, no, key);
+          }
+        }
+      }
+      if ((c0 < c1 && c1 == ns) || (ns == 0 && tid == 0)) for (int j = ole_prev; j < no; ++j) s_osb[j] = tid << 16 | heads;   // behind the last S key
+      lt_box_reduce(mn, mx, s_red);
+      good = __syncthreads_and(good);
+      refuse = vm_refuse(good != 0, no, mn, mx, inv);
+    }
+    if (!refuse) {
+      int nsh;
+      const int base = block_excl_scan<LT_T / 64>(heads, s_w, &nsh);   // S heads before the chunk
+      s_base[tid] = base;
+      int noo = 0;   // voxels that hold O elements only
+      for (int t0 = 0; t0 < no; t0 += LT_T) {
+        const int j = t0 + tid;
+        const bool oh = j < no && s_osb[j] >= 0 && (j == 0 || s_skey[j - 1] != s_skey[j]);
+        int tot;
+        const int e = noo + block_excl_scan<LT_T / 64>(oh ? 1 : 0, s_w, &tot);
+        if (j < no) s_oop[j] = e;
+        noo += tot;
+      }
+      if (tid == 0) s_oop[no] = noo;
+      __syncthreads();
+      // S, second pass: a head adds its S run (one element, unless a centroid left its voxel into an occupied one), then the O elements of its key
+      vm_u64 kprev = c0 > 0 && c0 < c1 ? vkey_of(S[c0 - 1], inv) : 0;
+      int hl = 0;
+      for (int b0 = c0; b0 < c1; b0 += LT_B) {
+        float4 p[LT_B + 1];
+#pragma unroll
+        for (int k = 0; k <= LT_B; ++k) p[k] = S[min(b0 + k, ns - 1)];   // (one past the chunk: the key behind its last element)
+#pragma unroll
+        for (int k = 0; k < LT_B; ++k) {
+          const int i = b0 + k;
+          if (i < c1) {
+            const vm_u64 key = vkey_of(p[k], inv);
+            if (i == 0 || kprev != key) {
+              const int ol = vm_count_less(s_skey, no, key), ole = vm_count_le(s_skey, no, key);
+              const int r = base + hl + s_oop[ol];
+              ++hl;
+              if (r < cap) {
+                int nsr = 1;
+                if (i + 1 < ns && vkey_of(p[k + 1], inv) == key) while (i + nsr < ns && vkey_of(S[i + nsr], inv) == key) ++nsr;
+                out[r] = vm_centroid([&](int q) { return q == 0 ? p[k] : (q < nsr ? S[i + q] : O[s_idx[ol + q - nsr]]); }, 0, nsr + ole - ol);
+              }
+            }
+            kprev = key;
+          }
+        }
+      }
+      for (int j = tid; j < no; j += LT_T) {   // the voxels of O elements alone
+        if (s_osb[j] >= 0 && (j == 0 || s_skey[j - 1] != s_skey[j])) {
+          const int r = s_base[s_osb[j] >> 16] + (s_osb[j] & 0xFFFF) + s_oop[j];
+          if (r < cap) {
+            int e = j + 1;
+            while (e < no && s_skey[e] == s_skey[j]) ++e;
+            out[r] = vm_centroid([&](int q) { return O[s_idx[q]]; }, j, e);
+          }
+        }
+      }
+      const int nvox = nsh + noo;
+      if (tid == 0) { li[LI_NTOTAL] = n; li[LI_NTOTAL_DS] = min(nvox, cap); if (nvox > cap) li[LI_OVERFLOW] = 1; li[LI_TM_FAST] += 1; }
+    } else {
+      float4* t = L.cur_total + (size_t)slot * L.total_cap;
+      for (int i = tid; i < ns; i += LT_T) t[i] = S[i];
+      for (int i = tid; i < no; i += LT_T) t[ns + i] = O[i];
+      if (tid == 0) { li[LI_NTOTAL] = n; li[LI_TM_LIST] += 1; }
+      state = n > W.small_max ? 2 : 1;
+    }
+  }
+  // ---- the work lists of the round-2 context (vox_plan's part): a refused slot appends its job.  No fence and no last workgroup: the counters of this
+  // launch were zeroed by the launch before it (two sets, alternating), and the end of the kernel publishes lists and counters to vox_small.
+  if (tid == 0) {
+    if (state == 1) W.list_small[atomicAdd(&W.cnt[0], 1)] = slot - L.vox_slot0;   // (the context has one job per slot of the stream group)
+    else if (state == 2) W.list_big[atomicAdd(&W.cnt[1], 1)] = slot - L.vox_slot0;
+    if (blockIdx.x == 0) { W.cnt_next[0] = 0; W.cnt_next[1] = 0; }
+  }
 }
 
 // the cell of a point in the grid g of nn_rules.h's exact lattice (nn_lm_coord): its coordinates relative to the grid's origin cell and its clamped index
@@ -1278,6 +1481,9 @@ void launch_lm_concat(const DevCtx& d, const LmCtx& L, hipStream_t st) {
 }
 void launch_lm_total(const DevCtx& d, const LmCtx& L, hipStream_t st) {
   ALEGO_LAUNCH(lm_total, dim3(8, d.n_launch), dim3(LM_BLOCK), 0, st, d, L);
+}
+void launch_lm_total_merge(const DevCtx& d, const LmCtx& L, const LtLists& W, hipStream_t st) {
+  ALEGO_LAUNCH(lm_total_merge, dim3(d.n_launch), dim3(LT_T), 0, st, d, L, W);
 }
 void launch_lm_grid(const DevCtx& d, const LmCtx& L, hipStream_t st) {
   ALEGO_LAUNCH(lm_grid_build, dim3(2, d.n_launch), dim3(LM_BLOCK), 0, st, d, L);

@@ -28,10 +28,6 @@ typedef unsigned long long u64;
 
 __device__ __forceinline__ bool vx_enabled(const VoxJob& J) { return J.enable == nullptr || *J.enable != 0; }
 
-#ifndef VX_SMALL_MAX
-#define VX_SMALL_MAX 8192      // jobs up to this many points are done by vox_small
-#endif
-
 // ---------------------------------------------------------------------------------------------------------
 // vox_big: one 1024-thread workgroup per job.
 //   1 getMinMax3D, grid geometry (identical arithmetic to vox_small / PCL)
@@ -493,6 +489,7 @@ __global__ void __launch_bounds__(256) vox_plan(VoxCtx V) {
     const VoxJob J = V.jobs[j];
     if (!vx_enabled(J)) continue;
     const int n = min(*J.n_in, J.cap);
+    if (V.skip_on && J.skip_le > 0 && n <= J.skip_le) continue;   // (an empty cloud included: the owner writes its count)
     if (n == 0) { *J.n_out = 0; if (J.mode == 1 && J.n_sel_out) J.n_sel_out[(size_t)(J.out_sel ? *J.out_sel : 0) * J.n_sel_stride] = 0; continue; }
     if (n <= VX_SMALL_MAX) V.list_small[atomicAdd(&s_n[0], 1)] = j;
     else V.list_big[atomicAdd(&s_n[1], 1)] = j;
@@ -519,7 +516,7 @@ int vox_create(VoxCtx* V, const VoxJob* jobs, int njobs, std::string* err) {
   auto A = [&](auto** p, size_t count) { if (e == hipSuccess) e = mem.get(p, count, true); };
   A(&V->jobs, (size_t)njobs); A(&V->bbox, (size_t)njobs * 8);
   A(&V->keys, total); A(&V->pairs_a, total); A(&V->pairs_b, total);
-  A(&V->list_small, (size_t)njobs); A(&V->list_big, (size_t)njobs); A(&V->cnt, 2);
+  A(&V->list_small, (size_t)njobs); A(&V->list_big, (size_t)njobs); A(&V->cnt, 6);
   V->grid_small = V->grid_big = njobs;
   if (e == hipSuccess) e = hipMemcpy(V->jobs, h.data(), sizeof(VoxJob) * njobs, hipMemcpyHostToDevice);
   if (e != hipSuccess) { std::memset(V, 0, sizeof(*V)); *err = std::string("vox_create: ") + hipGetErrorString(e); return -2; }
@@ -538,6 +535,13 @@ int vox_run(const VoxCtx& V, hipStream_t st, std::string* err) {
   if (V.njobs == 0) return 0;
   ALEGO_LAUNCH(vox_plan, dim3(1), dim3(256), 0, st, V);
   static_assert(VG_T == VX_SB && VG_LDS_BYTES <= VX_SMALL_LDS, "large jobs run in vox_small's workgroups and LDS");
+  ALEGO_LAUNCH(vox_small, dim3(std::max(V.grid_small, V.grid_big)), dim3(VX_SB), (size_t)VX_SMALL_LDS, st, V);
+  return 0;
+}
+
+int vox_run_listed(const VoxCtx& V, hipStream_t st, std::string* err) {
+  (void)err;
+  if (V.njobs == 0) return 0;
   ALEGO_LAUNCH(vox_small, dim3(std::max(V.grid_small, V.grid_big)), dim3(VX_SB), (size_t)VX_SMALL_LDS, st, V);
   return 0;
 }

@@ -33,6 +33,8 @@ enum {
                    // bit 2 + m: map m was refused because its window does not fit the voxel key (LI_OVERFLOW 8, no list and no map)
   LI_SORT_N,       // (2 entries) point counts written by the key-frame sort jobs
   LI_SORT_N1,
+  LI_TM_FAST,      // mapping frames whose laser_surf_total_ds_ lm_total_merge built by merging (kernels_lm.hip) ...
+  LI_TM_LIST,      // ... and frames it refused, whose round-2 job went on the VoxelGrid work list (tests: which path a scene took)
   LI_COUNT = 48
 };
 enum {
@@ -55,6 +57,7 @@ struct MapWork {     // work list of map_accum, written by map_update (kernels_m
   int* count;      // [2]: items, ticket
   int cap;
 };
+struct LtLists { int *list_small, *list_big, *cnt, *cnt_next; int small_max; };   // work lists of the round-2 VoxelGrid context (voxel.h): cnt this launch's two list sizes (zero on entry), cnt_next the set it zeroes for the next launch
 struct GridGeom { int ox, oy, oz; float inv; int gx, gy, gz, ncell; };   // cell of x: floorf(x * inv) - ox (lm_grid_build)
 
 
@@ -216,6 +219,7 @@ void launch_lm_prepare(const DevCtx& d, const LmCtx& L, int stage, int run_hint,
 void launch_lm_stage(const DevCtx& d, const LmCtx& L, int run_hint, int par, hipStream_t st);
 void launch_lm_concat(const DevCtx& d, const LmCtx& L, hipStream_t st);
 void launch_lm_total(const DevCtx& d, const LmCtx& L, hipStream_t st);
+void launch_lm_total_merge(const DevCtx& d, const LmCtx& L, const LtLists& W, hipStream_t st);
 void launch_lm_grid(const DevCtx& d, const LmCtx& L, hipStream_t st);
 void launch_lm_solve(const DevCtx& d, const LmCtx& L, bool remap, hipStream_t st);   // the solver kernel alone (launch_lm_register's, and alego_debug_remap_solve's on a one-slot view)
 int launch_lm_register(const DevCtx& d, const LmCtx& L, hipStream_t st, int (*allreduce)(void*, double*, size_t, hipStream_t), void* ar_ctx);

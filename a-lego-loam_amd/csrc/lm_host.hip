@@ -14,6 +14,7 @@
 
 #include "kf_store.h"
 #include "voxel.h"
+#include "vox_merge.h"
 #include "gmap.h"
 #include "loc_math.h"
 #include "pgraph.h"
@@ -37,6 +38,7 @@ struct LmHost {
   std::vector<VoxCtx> vm, v2;
   std::vector<VoxCtx> vk;      // per group: the two key-frame sort jobs of every slot alone (set_keypose / add_keyframe, outside the regular sequence)
   std::vector<MapWork> work;   // per group: work list of map_accum
+  std::vector<int> tm_grid1, tm_grid, tm_par;   // per stream group under ALEGO_LM_TOTAL_MERGE: workgroups of round 1's and of round 2's vox_small launch; which set of list counters the next lm_total_merge uses
   bool fallback_ok = true;     // buffers of the concat + radix VoxelGrid path (ALEGO_MAP_MERGE=0) are allocated
   ncclComm_t comm = nullptr;   // alego_dist_init: the registration of every slot is sharded over the ranks of this communicator
   std::string dist_err;
@@ -199,6 +201,7 @@ LmHost* lm_host_create(const alego_params& P, const DevCtx& d, int n_slots, int 
     j1.push_back(VoxJob{L.in_corner + b * L.in_cap_c, li + LI_NIN_C, L.cur_corner_ds + b * L.kf_cap_c, li + LI_NCUR_C, li + LI_RUN, P.lm_leaf_corner, L.in_cap_c, L.kf_cap_c, li + LI_OVERFLOW, 0});
     j1.push_back(VoxJob{L.in_surf + b * L.in_cap_s, li + LI_NIN_S, L.cur_surf_ds + b * L.kf_cap_s, li + LI_NCUR_S, li + LI_RUN, P.lm_leaf_surf, L.in_cap_s, L.kf_cap_s, li + LI_OVERFLOW, 0});
     j1.push_back(VoxJob{L.in_outl + b * L.in_cap_o, li + LI_NIN_O, L.cur_outl_ds + b * L.kf_cap_o, li + LI_NCUR_O, li + LI_RUN, P.lm_leaf_outlier, L.in_cap_o, L.kf_cap_o, li + LI_OVERFLOW, 0});
+    j1.back().skip_le = LT_OCAP;   // lm_total_merge filters a small /outlier cloud itself (a round with VoxCtx::skip_on)
     j2.push_back(VoxJob{L.cur_total + b * L.total_cap, li + LI_NTOTAL, L.cur_total_ds + b * L.total_cap, li + LI_NTOTAL_DS, li + LI_RUN, P.lm_leaf_surf, L.total_cap, L.total_cap, li + LI_OVERFLOW, 0});
     kf_sort_jobs(L, P, (int)b, &jk);
   }
@@ -214,10 +217,19 @@ LmHost* lm_host_create(const alego_params& P, const DevCtx& d, int n_slots, int 
   //  mapping frames are expected per round, instead of a handful for the rare one — 64x2048: 1.85 -> see profiles/r02_geo_64x2048*)
   const bool big_scans = d.N > 8 * 8192;
   lm->vm[g].grid_small = 3 * ns + std::max(2, ns / 2);
-  if (const char* e = getenv("ALEGO_VOX_GRID_DIV")) { const int dv = std::max(1, atoi(e)); lm->vm[g].grid_small = std::max(2, lm->vm[g].grid_small / dv); lm->v2[g].grid_small = std::max(1, lm->v2[g].grid_small / dv); }
+  // under ALEGO_LM_TOTAL_MERGE the /outlier jobs of small clouds are lm_total_merge's: a third of the scan's jobs less to keep workgroups for (a
+  // group whose /outlier clouds exceed LT_OCAP keeps those jobs and loops over them: correct, the workgroups are persistent, and not measured)
+  int tm_grid1 = 2 * ns + std::max(2, ns / 2);
+  if (const char* e = getenv("ALEGO_VOX_GRID_DIV")) {
+    const int dv = std::max(1, atoi(e));
+    lm->vm[g].grid_small = std::max(2, lm->vm[g].grid_small / dv); lm->v2[g].grid_small = std::max(1, lm->v2[g].grid_small / dv);
+    tm_grid1 = std::max(2, tm_grid1 / dv);
+  }
   lm->vm[g].grid_big = (!d.opt_map_merge || big_scans) ? std::max(2, ns / 2) : std::min(8, std::max(2, ns / 2));
   lm->v2[g].grid_big = big_scans ? std::max(2, ns / 2) : std::max(1, ns / 16);
   lm->vk[g].grid_small = 2; lm->vk[g].grid_big = 2;
+  lm->tm_grid1.push_back(tm_grid1); lm->tm_par.push_back(0);
+  lm->tm_grid.push_back(std::max(1, ns / 16));   // workgroups of the vox_small launch behind lm_total_merge: only the slots it refused have work there
   MapWork& W = lm->work[g];
   W.cap = std::max(4096, 64 * ns);
   if (!A(lm, &W.items, (size_t)W.cap, err) || !A(lm, &W.count, 2, err)) { lm_host_destroy(lm); return nullptr; }
@@ -257,7 +269,9 @@ static int map_sequence(LmHost* lm, const DevCtx& d, const LmCtx& L, int g, hipS
     launch_lm_concat(d, L, st);
     if (!dbg_sync(st, "lm_concat", err)) return ALEGO_ERR_HIP;
   }
-  if (int r = vox_run(lm->vm[g], st, err)) return r;
+  VoxCtx V1 = lm->vm[g];
+  if (d.opt_lm_total_merge) { V1.skip_on = 1; V1.grid_small = lm->tm_grid1[g]; }   // (the /outlier jobs of small clouds are lm_total_merge's)
+  if (int r = vox_run(V1, st, err)) return r;
   if (!dbg_sync(st, "vox round 1", err)) return ALEGO_ERR_HIP;
   launch_map_update(d, L, lm->work[g], st);   // (also closes the key-frame sort's bookkeeping when the maps come from the radix path)
   if (!dbg_sync(st, "map_update", err)) return ALEGO_ERR_HIP;
@@ -313,8 +327,24 @@ static int lm_sequence(LmHost* lm, const DevCtx& d, int stage, const std::vector
     if (!dbg_sync(st, "loc_select", err)) return ALEGO_ERR_HIP;
   }
   if (int r = map_sequence(lm, d, L, g, st, err)) return r;   // (includes the VoxelGrid filters of the scan's three clouds)
-  launch_lm_total(d, L, st);
-  if (int r = vox_run(lm->v2[g], st, err)) return r;
+  if (d.opt_lm_total_merge) {
+    // laser_outlier_ds_ of a small /outlier cloud and laser_surf_total_ds_ by one light workgroup per slot; the slots it refuses are on the
+    // round-2 context's work lists behind it, for a vox_small launch of a few persistent workgroups (lm_total_merge_grid)
+    VoxCtx V2 = lm->v2[g];
+    int* const cnt = V2.cnt;
+    const int par = lm->tm_par[g];
+    lm->tm_par[g] ^= 1;
+    // this launch's list sizes: one of two sets that only lm_total_merge writes (vox_plan's own pair is cnt[0..1], so rounds with the option off
+    // in between leave them alone), zeroed by the lm_total_merge launch before it, which used the other set
+    V2.cnt = cnt + 2 + 2 * par;
+    launch_lm_total_merge(d, L, LtLists{V2.list_small, V2.list_big, V2.cnt, cnt + 2 + 2 * (par ^ 1), VX_SMALL_MAX}, st);
+    if (!dbg_sync(st, "lm_total_merge", err)) return ALEGO_ERR_HIP;
+    V2.grid_small = V2.grid_big = lm->tm_grid[g];
+    if (int r = vox_run_listed(V2, st, err)) return r;
+  } else {
+    launch_lm_total(d, L, st);
+    if (int r = vox_run(lm->v2[g], st, err)) return r;
+  }
   if (!dbg_sync(st, "vox total", err)) return ALEGO_ERR_HIP;
   if (int r = launch_lm_register(d, L, st, lm->comm ? &lm_allreduce : nullptr, lm)) { *err = "sharded registration: " + lm->dist_err; return r; }
   if (!dbg_sync(st, "lm_register", err)) return ALEGO_ERR_HIP;

@@ -10,6 +10,10 @@
 
 #include <string>
 
+#ifndef VX_SMALL_MAX
+#define VX_SMALL_MAX 8192      // jobs up to this many points are done by vox_small
+#endif
+
 struct VoxJob {
   const float4* in;     // input cloud
   const int* n_in;      // device count
@@ -31,6 +35,8 @@ struct VoxJob {
   float* box_out;       // mode 1 (may be nullptr): min xyz / max xyz of the cloud as 8 floats at box_out + *out_sel * 8
   int* n_sel_out;       // mode 1 (may be nullptr): n is also stored at n_sel_out[*out_sel * n_sel_stride]
   int n_sel_stride;
+  int skip_le;          // with VoxCtx::skip_on: a cloud of 1 .. skip_le points is not planned, its owner filters it elsewhere (0: never; LaserMapping's
+                        // /outlier job, lm_total_merge)
 };
 
 struct VoxCtx {
@@ -39,9 +45,11 @@ struct VoxCtx {
   unsigned* bbox;       // [job][8] bounding box of the input cloud (vgrid.h format)
   unsigned* keys;       // voxel id per input point; later the list of voxel run starts
   unsigned long long *pairs_a, *pairs_b;  // (voxel id << 32 | position) ping-pong buffers of the radix passes
-  int *list_small, *list_big, *cnt;       // work lists of a round (vox_plan): enabled jobs of <= 8192 / more points; cnt[2]
+  int *list_small, *list_big, *cnt;       // work lists of a round (vox_plan): enabled jobs of <= 8192 / more points; cnt: the two list sizes
+                                          // (vox_plan's pair, then two more pairs, zeroed at create: a caller whose own kernel writes the lists alternates between cnt + 2 and cnt + 4)
   int grid_small, grid_big;               // workgroups launched for each list (default njobs; persistent loop over the list)
   unsigned total;       // total scratch elements
+  int skip_on;          // VoxJob::skip_le applies to this round (set per launch by the caller)
 };
 
 // host: allocate scratch for `jobs` (host copy of the job table), upload the table
@@ -49,5 +57,7 @@ int vox_create(VoxCtx* V, const VoxJob* jobs, int njobs, std::string* err);
 void vox_destroy(VoxCtx* V);
 // enqueue one round over all jobs of V
 int vox_run(const VoxCtx& V, hipStream_t st, std::string* err);
+// the same without vox_plan: the caller's own kernel has written list_small / list_big / cnt on this stream
+int vox_run_listed(const VoxCtx& V, hipStream_t st, std::string* err);
 
 #endif

@@ -249,7 +249,7 @@ int alego_debug_transform_to_start(alego_handle* h, const double* params6, const
  * them in `report` */
 int alego_debug_check_guards(char* report, int cap);
 /* Run-time switches of kernel variants (parity tests run both variants of a kernel inside one process).  Read once from
- * the environment at alego_create (ALEGO_CC_FUSED, ALEGO_FE_PICK1, ALEGO_LO_BOX_LDS, ALEGO_MAP_MERGE, ALEGO_IP_FAST); this
+ * the environment at alego_create (ALEGO_CC_FUSED, ALEGO_FE_PICK1, ALEGO_LO_BOX_LDS, ALEGO_MAP_MERGE, ALEGO_LM_TOTAL_MERGE, ALEGO_IP_FAST); this
  * call overrides one of them by its environment name.  Not a hot-path call. */
 int alego_debug_set_option(alego_handle* h, const char* name, int value);
 
