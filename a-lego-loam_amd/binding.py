@@ -45,6 +45,7 @@ EXPORTS = [
     "alego_remap_enable", "alego_remap_get", "alego_remap_host", "alego_remap_step_host", "alego_debug_remap_solve",
     "alego_occ_enable", "alego_occ_clear", "alego_occ_integrate", "alego_occ_get", "alego_occ_classify", "alego_occ_ray_host", "alego_occ_integrate_host",
     "alego_occ_classify_host", "alego_debug_occ_piece", "alego_occ_mark", "alego_map_assemble_static", "alego_occ_mark_host",
+    "alego_occ_set", "alego_occ_distance", "alego_occ_costmap", "alego_occ_distance_host", "alego_occ_cost_table_host", "alego_occ_costmap_host",
 ]
 
 REPLAY_PINGPONG = 0x100
@@ -54,6 +55,8 @@ ERR_CAPACITY, ERR_ARG = -3, -4
 OCC_RAYS, OCC_SHORT, OCC_TRUNCATED, OCC_CULLED, OCC_BAD, OCC_UPDATES, OCC_STATS = 0, 1, 2, 3, 4, 5, 6   # ALEGO_OCC_*
 OCC_SKIP_SHORT, OCC_SKIP_CULLED, OCC_SKIP_BAD = -10, -11, -12
 STATIC_OCCUPIED, STATIC_UNKNOWN, STATIC_OUTSIDE, STATIC_BELOW, STATIC_NEIGHBOUR, STATIC_REMOVED, STATIC_VERDICTS = 0, 1, 2, 3, 4, 5, 6   # ALEGO_STATIC_*
+OCC_FAR = 0xFFFFFFFF                                                    # ALEGO_OCC_FAR
+EDT_SOURCES, EDT_FAR_CELLS, EDT_MAX_D2, EDT_STATS = 0, 1, 2, 3          # ALEGO_EDT_*
 RELOC_MAX_CAND = 8
 RELOC_SECTORS, RELOC_RINGS = 60, 20
 ALIGN_MAX_QUERIES = 32
@@ -197,6 +200,14 @@ class OccRule(C.Structure):
 
 class StaticRule(C.Structure):
     _fields_ = [("occ", OccRule), ("protect_radius", C.c_int32), ("use_keep_below", C.c_int32), ("keep_below", C.c_float), ("pad", C.c_int32)]
+
+
+class OccDistOpts(C.Structure):
+    _fields_ = [("collapse_z", C.c_int32), ("unknown_is_obstacle", C.c_int32), ("max_cells", C.c_int32), ("pad", C.c_int32)]
+
+
+class OccInflation(C.Structure):
+    _fields_ = [("inscribed_radius", C.c_double), ("inflation_radius", C.c_double), ("cost_scaling", C.c_double), ("inflate_unknown", C.c_int32), ("pad", C.c_int32)]
 
 
 class GraphEdge(C.Structure):
@@ -593,6 +604,12 @@ def lib():
         L.alego_occ_ray_host.argtypes = [C.POINTER(OccOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
         L.alego_occ_integrate_host.argtypes = [C.POINTER(OccOpts), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.alego_occ_classify_host.argtypes = [C.POINTER(OccOpts), C.POINTER(OccRule), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.alego_occ_set.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.alego_occ_distance.argtypes = [C.c_void_p, C.POINTER(OccRule), C.POINTER(OccDistOpts), C.c_void_p, C.c_void_p]
+        L.alego_occ_costmap.argtypes = [C.c_void_p, C.POINTER(OccRule), C.c_int, C.c_int, C.POINTER(OccInflation), C.c_void_p]
+        L.alego_occ_distance_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int32, C.c_void_p, C.c_void_p]
+        L.alego_occ_cost_table_host.argtypes = [C.c_double, C.POINTER(OccInflation), C.c_void_p, C.c_int32]
+        L.alego_occ_costmap_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int32, C.c_int, C.c_void_p]
         L.alego_occ_mark.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(StaticRule), C.c_void_p, C.c_int32, C.c_void_p]
         L.alego_map_assemble_static.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.POINTER(StaticRule), C.c_void_p, C.c_int32, C.c_void_p]
         L.alego_occ_mark_host.argtypes = [C.POINTER(OccOpts), C.POINTER(StaticRule), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
@@ -881,6 +898,42 @@ def occ_mark_host(opts, hits, passes, pts, rule=None, sensor_z=None):
     if rc < 0:
         raise AlegoError(f"alego_occ_mark_host failed ({rc})")
     return verdict[:q.shape[0]], stats
+
+
+def occ_inflation(inscribed_radius, inflation_radius, cost_scaling=10.0, inflate_unknown=False):
+    """alego_occ_inflation: costmap_2d's inflation parameters, in metres"""
+    return OccInflation(float(inscribed_radius), float(inflation_radius), float(cost_scaling), int(bool(inflate_unknown)), 0)
+
+
+def occ_distance_host(cls, unknown_is_obstacle=False, max_cells=0):
+    """alego_occ_distance_host: (d2 uint32 of cls's shape, stats (EDT_STATS,) int64) of a class array (n2, n1, n0), (n1, n0) or (n0,) as occ_classify gives it"""
+    c = np.ascontiguousarray(cls, np.int8)
+    n = (C.c_int32 * 3)(*([1] * (3 - c.ndim) + list(c.shape))[::-1])
+    d2, stats = np.zeros(c.shape, np.uint32), np.zeros(EDT_STATS, np.int64)
+    rc = lib().alego_occ_distance_host(c.ctypes.data, n, int(bool(unknown_is_obstacle)), int(max_cells), d2.ctypes.data, stats.ctypes.data)
+    if rc < 0:
+        raise AlegoError(f"alego_occ_distance_host failed ({rc})")
+    return d2, stats
+
+
+def occ_cost_table_host(s, inflation):
+    """alego_occ_cost_table_host: the cost table (r r + 1,) uint8 over d2 for cells of edge s"""
+    table = np.empty(4095 * 4095 + 1, np.uint8)   # the largest table there is; the library returns how much of it the parameters use (r r + 1)
+    rc = lib().alego_occ_cost_table_host(float(s), C.byref(inflation), table.ctypes.data, table.size)
+    if rc < 0:
+        raise AlegoError(f"alego_occ_cost_table_host failed ({rc})")
+    return table[:rc].copy()
+
+
+def occ_costmap_host(cls, d2, table, unknown_is_obstacle=False, inflate_unknown=False):
+    """alego_occ_costmap_host: the costs uint8 of cls's shape from the classes, their d2 and the cost table"""
+    c, d, t = np.ascontiguousarray(cls, np.int8), np.ascontiguousarray(d2, np.uint32), np.ascontiguousarray(table, np.uint8)
+    assert c.shape == d.shape
+    out = np.zeros(c.shape, np.uint8)
+    rc = lib().alego_occ_costmap_host(c.ctypes.data, d.ctypes.data, c.size, int(bool(unknown_is_obstacle)), t.ctypes.data, t.size, int(bool(inflate_unknown)), out.ctypes.data)
+    if rc < 0:
+        raise AlegoError(f"alego_occ_costmap_host failed ({rc})")
+    return out
 
 
 def _reloc_result(r):
@@ -1473,6 +1526,29 @@ class Handle:
         """alego_occ_classify: int8 classes (n2, n1, n0), or (n1, n0) with collapse_z; rule = (min_hits, hit_weight, pass_weight) or None for the defaults"""
         out = np.zeros(_occ_shape(self._occ_opts, collapse_z), np.int8)
         self._check(lib().alego_occ_classify(self._h, _occ_rule(rule), int(bool(collapse_z)), out.ctypes.data), "alego_occ_classify")
+        return out
+
+    def occ_set(self, hits=None, passes=None):
+        """alego_occ_set: copies counts (n2, n1, n0) uint32 to the grid; None keeps that array's counts"""
+        shape = _occ_shape(self._occ_opts)
+        h = None if hits is None else np.ascontiguousarray(hits, np.uint32)
+        p = None if passes is None else np.ascontiguousarray(passes, np.uint32)
+        assert all(a is None or a.shape == shape for a in (h, p))
+        self._check(lib().alego_occ_set(self._h, None if h is None else h.ctypes.data, None if p is None else p.ctypes.data), "alego_occ_set")
+
+    def occ_distance(self, rule=None, collapse_z=False, unknown_is_obstacle=False, max_cells=0, want_d2=True):
+        """alego_occ_distance: (d2 uint32 (n2, n1, n0), or (n1, n0) with collapse_z, or None without want_d2; stats (EDT_STATS,) int64)"""
+        o = OccDistOpts(int(bool(collapse_z)), int(bool(unknown_is_obstacle)), int(max_cells), 0)
+        d2 = np.zeros(_occ_shape(self._occ_opts, collapse_z), np.uint32) if want_d2 else None
+        stats = np.zeros(EDT_STATS, np.int64)
+        self._check(lib().alego_occ_distance(self._h, _occ_rule(rule), C.byref(o), None if d2 is None else d2.ctypes.data, stats.ctypes.data), "alego_occ_distance")
+        return d2, stats
+
+    def occ_costmap(self, inflation, rule=None, collapse_z=False, unknown_is_obstacle=False):
+        """alego_occ_costmap: uint8 costs (n2, n1, n0), or (n1, n0) with collapse_z; inflation from occ_inflation()"""
+        out = np.zeros(_occ_shape(self._occ_opts, collapse_z), np.uint8)
+        self._check(lib().alego_occ_costmap(self._h, _occ_rule(rule), int(bool(collapse_z)), int(bool(unknown_is_obstacle)), C.byref(inflation), out.ctypes.data),
+                    "alego_occ_costmap")
         return out
 
     def occ_mark(self, kinds=7, rule=None, slot=0):

@@ -22,6 +22,7 @@
 #include "merge_math.h"
 #include "nn_rules.h"
 #include "thin_math.h"
+#include "edt_math.h"
 #include "occ_math.h"
 #include "loop_ctx.h"
 #include "pgraph.h"
@@ -1747,6 +1748,52 @@ int alego_occ_classify_host(const alego_occ_opts* opts, const alego_occ_rule* ru
   const alego_occ_rule& R = rule ? *rule : dflt;
   if (occ_rule_fault(&R)) return ALEGO_ERR_ARG;
   occ_classify_host(occ_grid(opts), R, hits, passes, collapse_z, out);
+  return 0;
+}
+
+// ---- the clearance field and the cost map (kernels_edt.hip, edt_math.h) ----
+int alego_occ_set(alego_handle* h, const uint32_t* hits, const uint32_t* passes) {
+  ALEGO_GATE(h);
+  if (int r = occ_need(h, "alego_occ_set")) return r;
+  return lm_host_occ_set(h->lm, hits, passes, &h->err);
+}
+int alego_occ_distance(alego_handle* h, const alego_occ_rule* rule, const alego_occ_dist_opts* opts, uint32_t* d2, int64_t stats[ALEGO_EDT_STATS]) {
+  ALEGO_GATE(h);
+  if (int r = occ_need(h, "alego_occ_distance")) return r;
+  const alego_occ_rule dflt = {1, 2, 1, 0};
+  const alego_occ_rule& R = rule ? *rule : dflt;
+  if (const char* why = occ_rule_fault(&R)) { h->err = std::string("alego_occ_distance: ") + why; return ALEGO_ERR_ARG; }
+  const alego_occ_dist_opts O = opts ? *opts : alego_occ_dist_opts{0, 0, 0, 0};
+  return lm_host_occ_distance(h->lm, R, O, d2, stats, &h->err);
+}
+int alego_occ_costmap(alego_handle* h, const alego_occ_rule* rule, int collapse_z, int unknown_is_obstacle, const alego_occ_inflation* infl, uint8_t* out) {
+  ALEGO_GATE(h);
+  if (!infl || !out) return ALEGO_ERR_ARG;
+  if (int r = occ_need(h, "alego_occ_costmap")) return r;
+  const alego_occ_rule dflt = {1, 2, 1, 0};
+  const alego_occ_rule& R = rule ? *rule : dflt;
+  if (const char* why = occ_rule_fault(&R)) { h->err = std::string("alego_occ_costmap: ") + why; return ALEGO_ERR_ARG; }
+  return lm_host_occ_costmap(h->lm, R, collapse_z, unknown_is_obstacle, *infl, out, &h->err);
+}
+int alego_occ_distance_host(const int8_t* cls, const int32_t n[3], int unknown_is_obstacle, int32_t max_cells, uint32_t* d2, int64_t stats[ALEGO_EDT_STATS]) {
+  if (!cls || !n || (!d2 && !stats) || edt_dims_fault(n, max_cells)) return ALEGO_ERR_ARG;
+  const size_t cells = (size_t)n[0] * n[1] * n[2];
+  std::vector<uint32_t> work(cells), own(d2 ? 0 : cells);
+  std::vector<EdtTop> stack((size_t)std::max(n[0], std::max(n[1], n[2])));
+  edt_distance_host(cls, n, unknown_is_obstacle, max_cells, d2 ? d2 : own.data(), work.data(), stack.data(), stats);
+  return 0;
+}
+int alego_occ_cost_table_host(double s, const alego_occ_inflation* infl, uint8_t* table, int32_t cap) {
+  int32_t r = 0;
+  if (!infl || cap < 0 || (cap > 0 && !table) || edt_inflation_fault(s, infl, &r)) return ALEGO_ERR_ARG;
+  if (cap < r * r + 1) return ALEGO_ERR_CAPACITY;
+  edt_cost_table(s, infl, r, table);
+  return r * r + 1;
+}
+int alego_occ_costmap_host(const int8_t* cls, const uint32_t* d2, int64_t cells, int unknown_is_obstacle, const uint8_t* table, int32_t n_table, int inflate_unknown,
+                           uint8_t* out) {
+  if (cells < 0 || n_table < 1 || !table || (cells > 0 && (!cls || !d2 || !out))) return ALEGO_ERR_ARG;
+  for (int64_t i = 0; i < cells; ++i) out[i] = edt_cost(cls[i], d2[i], unknown_is_obstacle, table, n_table, inflate_unknown);
   return 0;
 }
 

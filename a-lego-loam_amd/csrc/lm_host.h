@@ -62,6 +62,10 @@ int lm_host_occ_integrate(LmHost* lm, int slot, int first, int n, int kinds, int
 int lm_host_occ_get(LmHost* lm, uint32_t* hits, uint32_t* passes, std::string* err);
 int lm_host_occ_classify(LmHost* lm, const alego_occ_rule& rule, int collapse_z, int8_t* out, std::string* err);
 int lm_host_occ_set_piece(LmHost* lm, int piece);   // alego_debug_occ_piece
+// the clearance field and the cost map (alego_occ_distance / alego_occ_costmap; kernels_edt.hip); d2 / stats may be null
+int lm_host_occ_set(LmHost* lm, const uint32_t* hits, const uint32_t* passes, std::string* err);
+int lm_host_occ_distance(LmHost* lm, const alego_occ_rule& rule, const alego_occ_dist_opts& o, uint32_t* d2, int64_t* stats, std::string* err);
+int lm_host_occ_costmap(LmHost* lm, const alego_occ_rule& rule, int collapse_z, int unknown_is_obstacle, const alego_occ_inflation& infl, uint8_t* out, std::string* err);
 // the static map: verdicts of every selected point of `slot` (returns their number), and the assembly without the removed points
 int lm_host_occ_mark(LmHost* lm, int slot, int kinds, const alego_static_rule& rule, uint8_t* verdict, int cap, int64_t* stats, std::string* err);
 int lm_host_map_assemble_static(LmHost* lm, int slot, int kinds, float leaf, const alego_static_rule& rule, alego_point* out, int cap, int64_t* stats, std::string* err);

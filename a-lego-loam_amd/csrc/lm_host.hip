@@ -22,6 +22,7 @@
 #include "merge_math.h"
 #include "thin.h"
 #include "thin_math.h"
+#include "edt_math.h"
 #include "occ.h"
 #include "loc_store.h"
 #include "remap_math.h"
@@ -83,6 +84,12 @@ struct LmHost {
   DevBuf<uint8_t> st_verdict;
   DevBuf<int> st_kept, st_off;
   DevBuf<unsigned long long> st_stats;
+  // alego_occ_distance / alego_occ_costmap: the two d2 arrays the passes go between, the envelopes' stacks, the statistics, the cost table and
+  // the costs of a call; allocated by the first call and kept
+  DevBuf<uint32_t> edt_a, edt_b;
+  DevBuf<int2> edt_env;
+  DevBuf<unsigned long long> edt_stats;
+  DevBuf<uint8_t> edt_table, edt_cost;
 };
 
 namespace {
@@ -1483,6 +1490,61 @@ int lm_host_occ_classify(LmHost* lm, const alego_occ_rule& rule, int collapse_z,
   if (lm->occ_cls.reserve(n_out) != hipSuccess) { *err = "occ_classify: allocation failed"; return ALEGO_ERR_HIP; }
   launch_occ_classify(lm->occ, rule, collapse_z, lm->occ_cls.p, lm->st[0]);
   if (hipStreamSynchronize(lm->st[0]) != hipSuccess || hipMemcpy(out, lm->occ_cls.p, n_out, hipMemcpyDeviceToHost) != hipSuccess) { *err = "occ_classify: classification failed"; return ALEGO_ERR_HIP; }
+  return 0;
+}
+int lm_host_occ_set(LmHost* lm, const uint32_t* hits, const uint32_t* passes, std::string* err) {
+  const size_t bytes = occ_cells(lm->occ.G) * sizeof(uint32_t);
+  if ((hits && hipMemcpy(lm->occ.hits, hits, bytes, hipMemcpyHostToDevice) != hipSuccess) ||
+      (passes && hipMemcpy(lm->occ.passes, passes, bytes, hipMemcpyHostToDevice) != hipSuccess)) { *err = "occ_set: copy failed"; return ALEGO_ERR_HIP; }
+  return 0;
+}
+// ---- the clearance field and the cost map (alego_occ_distance / alego_occ_costmap; kernels_edt.hip) ----
+// Classifies and enqueues the transform on st[0]; *d2 is the device array that will hold the result, dom the domain.  Nothing is awaited.
+static int edt_enqueue(LmHost* lm, const alego_occ_rule& rule, int collapse_z, int unknown_is_obstacle, int32_t max_cells, const char* what, int32_t* dom, double* s,
+                       uint32_t** d2, std::string* err) {
+  const OccGrid& G = lm->occ.G;
+  const char* why = edt_domain(G.n, G.cell, collapse_z, dom, s);
+  if (!why) why = edt_dims_fault(dom, max_cells);
+  if (why) { *err = std::string(what) + ": " + why; return ALEGO_ERR_ARG; }
+  const size_t cells = (size_t)dom[0] * dom[1] * dom[2];
+  const bool env = dom[1] > 1 || dom[2] > 1;
+  if (lm->occ_cls.reserve(cells) != hipSuccess || lm->edt_a.reserve(cells) != hipSuccess || lm->edt_stats.reserve(ALEGO_EDT_STATS) != hipSuccess ||
+      (env && (lm->edt_b.reserve(cells) != hipSuccess || lm->edt_env.reserve(cells) != hipSuccess))) { *err = std::string(what) + ": allocation failed"; return ALEGO_ERR_HIP; }
+  launch_occ_classify(lm->occ, rule, collapse_z, lm->occ_cls.p, lm->st[0]);
+  EdtWork W = {lm->occ_cls.p, {dom[0], dom[1], dom[2]}, unknown_is_obstacle ? 1 : 0, (uint32_t)max_cells * (uint32_t)max_cells, lm->edt_a.p, lm->edt_b.p, lm->edt_env.p,
+               env ? cells : 0, lm->edt_stats.p};
+  *d2 = launch_edt(W, lm->st[0]);
+  return 0;
+}
+static int edt_stats_out(LmHost* lm, int64_t* stats, const char* what, std::string* err) {
+  unsigned long long got[ALEGO_EDT_STATS];
+  if (hipMemcpy(got, lm->edt_stats.p, sizeof(got), hipMemcpyDeviceToHost) != hipSuccess) { *err = std::string(what) + ": copy failed"; return ALEGO_ERR_HIP; }
+  if (stats) { stats[ALEGO_EDT_SOURCES] = (int64_t)got[ALEGO_EDT_SOURCES]; stats[ALEGO_EDT_FAR_CELLS] = (int64_t)got[ALEGO_EDT_FAR_CELLS]; stats[ALEGO_EDT_MAX_D2] = (int64_t)got[ALEGO_EDT_MAX_D2] - 1; }
+  return 0;
+}
+int lm_host_occ_distance(LmHost* lm, const alego_occ_rule& rule, const alego_occ_dist_opts& o, uint32_t* d2, int64_t* stats, std::string* err) {
+  int32_t dom[3]; double s; uint32_t* dev = nullptr;
+  if (int r = edt_enqueue(lm, rule, o.collapse_z, o.unknown_is_obstacle, o.max_cells, "occ_distance", dom, &s, &dev, err)) return r;
+  if (hipStreamSynchronize(lm->st[0]) != hipSuccess) { *err = "occ_distance: the transform failed"; return ALEGO_ERR_HIP; }
+  if (d2 && hipMemcpy(d2, dev, (size_t)dom[0] * dom[1] * dom[2] * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) { *err = "occ_distance: copy failed"; return ALEGO_ERR_HIP; }
+  return stats ? edt_stats_out(lm, stats, "occ_distance", err) : 0;
+}
+int lm_host_occ_costmap(LmHost* lm, const alego_occ_rule& rule, int collapse_z, int unknown_is_obstacle, const alego_occ_inflation& infl, uint8_t* out, std::string* err) {
+  const OccGrid& G = lm->occ.G;
+  int32_t dom[3], r = 0; double s;
+  const char* why = edt_domain(G.n, G.cell, collapse_z, dom, &s);
+  if (!why) why = edt_inflation_fault(s, &infl, &r);
+  if (!why) why = edt_dims_fault(dom, r);   // (before anything is allocated; edt_enqueue asks again)
+  if (why) { *err = std::string("occ_costmap: ") + why; return ALEGO_ERR_ARG; }
+  std::vector<uint8_t> table((size_t)r * r + 1);
+  edt_cost_table(s, &infl, r, table.data());
+  const size_t cells = (size_t)dom[0] * dom[1] * dom[2];
+  if (lm->edt_table.reserve(table.size()) != hipSuccess || lm->edt_cost.reserve(cells) != hipSuccess) { *err = "occ_costmap: allocation failed"; return ALEGO_ERR_HIP; }
+  if (hipMemcpy(lm->edt_table.p, table.data(), table.size(), hipMemcpyHostToDevice) != hipSuccess) { *err = "occ_costmap: upload failed"; return ALEGO_ERR_HIP; }
+  uint32_t* dev = nullptr;
+  if (int rc = edt_enqueue(lm, rule, collapse_z, unknown_is_obstacle, r, "occ_costmap", dom, &s, &dev, err)) return rc;
+  launch_edt_cost(lm->occ_cls.p, dev, cells, unknown_is_obstacle ? 1 : 0, lm->edt_table.p, (int)table.size(), infl.inflate_unknown ? 1 : 0, lm->edt_cost.p, lm->st[0]);
+  if (hipStreamSynchronize(lm->st[0]) != hipSuccess || hipMemcpy(out, lm->edt_cost.p, cells, hipMemcpyDeviceToHost) != hipSuccess) { *err = "occ_costmap: the cost map failed"; return ALEGO_ERR_HIP; }
   return 0;
 }
 // ---- the static map (alego_occ_mark / alego_map_assemble_static; kernels_occ.hip) ----

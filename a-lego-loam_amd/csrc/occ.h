@@ -39,4 +39,19 @@ struct OccStatic {
 void launch_occ_mark(const LmCtx& L, const OccDev& D, const OccStatic& S, const alego_static_rule& rule, int slot, int kinds, hipStream_t st);
 // the kept points of S.pts, stably, to out[0, out_cap); their number to *n_dev; kinds & ALEGO_MAP_FRAME_ID: w = frame index
 void launch_occ_emit(const OccStatic& S, int kinds, float4* out, int out_cap, int* n_dev, hipStream_t st);
+
+// the clearance field (kernels_edt.hip, edt_math.h) of a class array whose domain passed edt_dims_fault
+struct EdtWork {
+  const int8_t* cls;                // [cells] of the domain n[0] n[1] n[2]
+  int32_t n[3];
+  int32_t unknown_is_obstacle;
+  uint32_t r2;                      // the cap's square; 0: no limit
+  uint32_t *a, *b;                  // [cells] each: the passes go back and forth between them
+  int2* env; size_t env_cap;        // the envelopes' stacks, [cells] (unused when n[1] = n[2] = 1)
+  unsigned long long* stats;        // [ALEGO_EDT_STATS]: sources, FAR cells, the largest finite d2 + 1 (0: none); zeroed by the launch
+};
+// pass X, passes Y and Z where the axis has more than one cell, the cap and the statistics; returns the one of a / b that holds d2
+uint32_t* launch_edt(const EdtWork& W, hipStream_t st);
+void launch_edt_cost(const int8_t* cls, const uint32_t* d2, size_t cells, int unknown_is_obstacle, const uint8_t* table, int n_table, int inflate_unknown, uint8_t* out,
+                     hipStream_t st);
 #endif

@@ -77,6 +77,12 @@
 //       highest, so that ground returns leave the layer from below and count as free space only.  Writes DIR/occupancy.pgm (P5; 254 free,
 //       0 occupied, 205 unknown; the top row is the largest y, as map_server reads it) and DIR/occupancy.yaml, and prints one line
 //       "occupancy: origin X Y Z cell CX CY CZ n NX NY NZ max_range R rays N short S truncated T culled C bad B updates U".
+//   --occupancy CELL DIR + --inflate INSCRIBED RADIUS [SCALING]
+//       the inflated cost map of that grid (alego_occ_costmap): costmap_2d's inflation layer with the robot's inscribed
+//       radius, the inflation radius (metres) and the cost scaling factor (default 10) over the collapsed grid.  Writes DIR/costmap.pgm (P5,
+//       maxval 255, the raw costs: 254 lethal, 253 inscribed, 255 unknown; rows as occupancy.pgm orders them) and prints one line
+//       "costmap: r R sources A far B max_d2 C lethal D inscribed E unknown F" (R the radius in cells; sources, cells beyond it and the
+//       largest squared distance within it, in cells).  Without --occupancy it is a usage error (exit status 2).
 //   --save-map DIR + --static CELL [--occ-range R] [--static-keep-below Z] [--static-protect RADIUS]
 //       the static map (alego_map_assemble_static): after --merge / --thin and the files above, a 3-D grid of cubes of CELL
 //       metres over the key poses' bounding box plus R (default 30 m) in x and y and from 3 m below the lowest key pose to 3 m above the highest in
@@ -106,6 +112,8 @@ extern "C" int alego_synth_scan(const alego_params* P, int stream, long scan_ind
 int main(int argc, char** argv) {
   std::string bag_path, topic = "/lslidar_point_cloud", map_dir, occ_dir;
   double occ_cell = 0.0, occ_range = 30.0, static_cell = 0.0;
+  bool inflate = false;
+  alego_occ_inflation inflation = {0.0, 0.0, 10.0, 0, 0};
   alego_static_rule static_rule = {{1, 2, 1, 0}, 0, 0, 0.f, 0};
   float map_leaf = 0.f;
   int map_frames = 4096, map_points = 1 << 24, loop_every = 0, close_every = 0, max_loops = 16;
@@ -143,6 +151,10 @@ int main(int argc, char** argv) {
     else if (a == "--thin") thin_dist = std::atof(val());
     else if (a == "--occupancy") { occ_cell = std::atof(val()); occ_dir = val(); }
     else if (a == "--occ-range") occ_range = std::atof(val());
+    else if (a == "--inflate") {
+      inflate = true; inflation.inscribed_radius = std::atof(val()); inflation.inflation_radius = std::atof(val());
+      if (i + 1 < argc && (std::isdigit((unsigned char)argv[i + 1][0]) || argv[i + 1][0] == '.')) inflation.cost_scaling = std::atof(argv[++i]);
+    }
     else if (a == "--static") static_cell = std::atof(val());
     else if (a == "--static-keep-below") { static_rule.use_keep_below = 1; static_rule.keep_below = (float)std::atof(val()); }
     else if (a == "--static-protect") static_rule.protect_radius = std::atoi(val());
@@ -158,6 +170,7 @@ int main(int argc, char** argv) {
     else if (a == "--remap") { remap = true; if (i + 1 < argc && (std::isdigit((unsigned char)argv[i + 1][0]) || argv[i + 1][0] == '.')) remap_eig_min = std::atof(argv[++i]); }
     else pos.push_back(argv[i]);
   }
+  if (inflate && occ_dir.empty()) { std::fprintf(stderr, "--inflate needs --occupancy CELL DIR\n"); return 2; }
   alego_bag* bag = nullptr;
   long n_scans = pos.size() > 0 ? std::atol(pos[0]) : 40;
   if (!bag_path.empty()) {
@@ -529,6 +542,28 @@ int main(int argc, char** argv) {
       ok = false;
     }
     if (!ok) { std::fprintf(stderr, "occupancy: cannot write to %s\n", occ_dir.c_str()); rc = 1; }
+    if (inflate && ok) {   // the inflated cost map of the collapsed grid
+      std::vector<uint8_t> cost(cls.size());
+      std::vector<uint8_t> table((size_t)4095 * 4095 + 1);   // the largest table there is: the library says how much of it the parameters use
+      const int n_table = alego_occ_cost_table_host(occ_cell, &inflation, table.data(), (int32_t)table.size());
+      if (n_table < 1) { std::fprintf(stderr, "--inflate: INSCRIBED <= RADIUS, both and SCALING not negative, RADIUS at most 4095 cells\n"); alego_destroy(h); return 2; }
+      const int r = (int)std::lround(std::sqrt((double)(n_table - 1)));   // n_table = r r + 1
+      const alego_occ_dist_opts dopt = {1, 0, r, 0};
+      int64_t ds[ALEGO_EDT_STATS];
+      if (alego_occ_costmap(h, nullptr, 1, 0, &inflation, cost.data()) != ALEGO_OK || alego_occ_distance(h, nullptr, &dopt, nullptr, ds) != ALEGO_OK) {
+        std::fprintf(stderr, "costmap: %s\n", alego_last_error(h)); alego_destroy(h); return 1;
+      }
+      long long lethal = 0, inscribed = 0, unknown = 0;
+      for (uint8_t c : cost) { lethal += c == 254; inscribed += c == 253; unknown += c == 255; }
+      std::printf("costmap: r %d sources %lld far %lld max_d2 %lld lethal %lld inscribed %lld unknown %lld\n", r, (long long)ds[ALEGO_EDT_SOURCES],
+                  (long long)ds[ALEGO_EDT_FAR_CELLS], (long long)ds[ALEGO_EDT_MAX_D2], lethal, inscribed, unknown);
+      for (int y = 0; y < oo.n[1]; ++y)
+        for (int x = 0; x < oo.n[0]; ++x) img[(size_t)y * oo.n[0] + x] = cost[(size_t)(oo.n[1] - 1 - y) * oo.n[0] + x];
+      f = std::fopen((occ_dir + "/costmap.pgm").c_str(), "wb");
+      ok = f != nullptr;
+      if (ok) { ok = std::fprintf(f, "P5\n%d %d\n255\n", oo.n[0], oo.n[1]) > 0 && std::fwrite(img.data(), 1, img.size(), f) == img.size(); ok = std::fclose(f) == 0 && ok; }
+      if (!ok) { std::fprintf(stderr, "costmap: cannot write to %s\n", occ_dir.c_str()); rc = 1; }
+    }
   }
   alego_destroy(h);
   if (bag) alego_bag_close(bag);

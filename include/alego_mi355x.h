@@ -1029,6 +1029,45 @@ int alego_occ_classify_host(const alego_occ_opts* opts, const alego_occ_rule* ru
  * walks a whole ray, the baseline tools/occ_timing.py measures next to the default).  The counts do not depend on it. */
 int alego_debug_occ_piece(alego_handle* h, int32_t piece);
 
+/* ---- clearance field and inflated cost map of the occupancy grid (csrc/kernels_edt.hip, csrc/edt_math.h) ---------
+ * Not part of the reference.  What a planner reads off the grid is how far every cell is from the nearest obstacle: the clearance of a
+ * path, costmap_2d's inflation layer, an ESDF.  The exact squared Euclidean distance transform of the classified grid, in integers: device
+ * and host agree exactly.  Nothing is allocated or launched without these calls; the counts are not changed.
+ *
+ * DOMAIN   the class array alego_occ_classify gives: n[0] n[1] n[2] cells, or n[0] n[1] with collapse_z.  An axis with one cell contributes
+ *          no displacement; every axis with more than one cell must have the same edge length s (compared as doubles; no such axis:
+ *          s = cell[0]), and the sum of (n_k - 1)^2 over the axes must not exceed 2^32 - 2, so that no finite value reaches FAR.
+ * SOURCES  the cells of class 100; with unknown_is_obstacle those of class -1 as well.
+ * D2       u32 per cell: the minimum over the sources of dx^2 + dy^2 + dz^2 in cells; ALEGO_OCC_FAR where there is no source.
+ *          max_cells = r > 0 turns every d2 > r^2 into FAR; 0: no limit; r < 0 or r > 65535 is refused.  The distance is s sqrt(d2).
+ * TABLE    costmap_2d's computeCost over d2: r = ceil(inflation_radius / s); table[0] = 254; for 1 <= d2 <= r^2 with
+ *          dist = sqrt((double) d2) s: 253 if dist <= inscribed_radius, else (uint8_t)(252.0 exp(-cost_scaling (dist - inscribed_radius))).
+ *          Refused: a non-finite or negative radius or scaling, inflation_radius < inscribed_radius, r > 4095.
+ * COST     254 on a source; else t = table[d2] (0 beyond the table or where d2 is FAR): a free cell gets t, an unknown one t if
+ *          t >= (inflate_unknown ? 1 : 253), else 255 (NO_INFORMATION).
+ *
+ * alego_occ_set       the counterpart of alego_occ_get: copies counts to the grid (either pointer may be NULL: that array keeps its counts).
+ * alego_occ_distance  classifies on the device under `rule` (NULL: the defaults), transforms, and copies d2 (may be NULL: stats only) and
+ *                     stats (may be NULL) out; opts = NULL: {0, 0, 0, 0}.  stats: sources, FAR cells, the largest finite d2 (-1: none).
+ * alego_occ_costmap   the same with max_cells = r, then the cost of every cell to out.
+ * Both are synchronous and need a mapping handle with the archive on and the grid enabled.  Every refusal is ALEGO_ERR_ARG with
+ * alego_last_error set.
+ * Host twins (no device, no handle): alego_occ_distance_host takes what alego_occ_classify / alego_occ_classify_host gave (for a collapsed
+ * grid pass n[2] = 1); d2 or stats may be NULL.  alego_occ_cost_table_host writes table[0, r r] and returns r r + 1 (cap below that:
+ * ALEGO_ERR_CAPACITY).  alego_occ_costmap_host is the cost rule over `cells` cells. */
+#define ALEGO_OCC_FAR 0xFFFFFFFFu
+typedef struct alego_occ_dist_opts { int32_t collapse_z, unknown_is_obstacle, max_cells, pad; } alego_occ_dist_opts;
+typedef struct alego_occ_inflation { double inscribed_radius, inflation_radius, cost_scaling; int32_t inflate_unknown, pad; } alego_occ_inflation;
+/* int64 each: sources, FAR cells, the largest finite d2 (-1: none) */
+enum { ALEGO_EDT_SOURCES = 0, ALEGO_EDT_FAR_CELLS, ALEGO_EDT_MAX_D2, ALEGO_EDT_STATS };
+int alego_occ_set(alego_handle* h, const uint32_t* hits, const uint32_t* passes);
+int alego_occ_distance(alego_handle* h, const alego_occ_rule* rule, const alego_occ_dist_opts* opts, uint32_t* d2, int64_t stats[ALEGO_EDT_STATS]);
+int alego_occ_costmap(alego_handle* h, const alego_occ_rule* rule, int collapse_z, int unknown_is_obstacle, const alego_occ_inflation* infl, uint8_t* out);
+int alego_occ_distance_host(const int8_t* cls, const int32_t n[3], int unknown_is_obstacle, int32_t max_cells, uint32_t* d2, int64_t stats[ALEGO_EDT_STATS]);
+int alego_occ_cost_table_host(double s, const alego_occ_inflation* infl, uint8_t* table, int32_t cap);
+int alego_occ_costmap_host(const int8_t* cls, const uint32_t* d2, int64_t cells, int unknown_is_obstacle, const uint8_t* table, int32_t n_table, int inflate_unknown,
+                           uint8_t* out);
+
 /* ---- static map: the archive's points that the occupancy grid saw through are dropped (csrc/kernels_occ.hip, csrc/occ_math.h; DESIGN.md
  * section 25).  Not part of the reference.  A car that stood somewhere for one key frame stays in the assembled map as a trail of points;
  * the grid holds the evidence against them: their cells were hit once and passed through many times.  Every point of the archive is
