@@ -15,6 +15,7 @@
 #include "../../include/alego_mi355x.h"
 #include "api_gate.h"
 #include "dev_common.h"
+#include "dev_copy.h"
 #include "dev_mem.h"
 #include "front_end.h"
 #include "lm_ctx.h"
@@ -108,12 +109,12 @@ DevCtx view(const alego_handle* h, int slot0, int n) {
 }
 
 hipStream_t stream_of(const alego_handle* h, int slot) { return h->streams[slot / h->gsize]; }
-hipError_t sync_all(const alego_handle* h) {
-  hipError_t r = hipSuccess;
-  for (hipStream_t s : h->streams) { hipError_t e = hipStreamSynchronize(s); if (e != hipSuccess) r = e; }
-  for (hipStream_t s : h->back) { hipError_t e = hipStreamSynchronize(s); if (e != hipSuccess) r = e; }
-  for (hipStream_t s : {h->s_lo, h->s_lm}) if (s) { hipError_t e = hipStreamSynchronize(s); if (e != hipSuccess) r = e; }
-  return r;
+// every stream of the handle, in the order a wait for all of them visits: front, back, look-ahead
+std::vector<hipStream_t> all_streams(const alego_handle* h) {
+  std::vector<hipStream_t> v(h->streams);
+  v.insert(v.end(), h->back.begin(), h->back.end());
+  for (hipStream_t s : {h->s_lo, h->s_lm}) if (s) v.push_back(s);
+  return v;
 }
 
 int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
@@ -123,8 +124,8 @@ int env_int(const char* name, int dflt) { const char* e = getenv(name); return e
 // calls (alego_lo_process, alego_lm_process, alego_dist_*) for all of them; alego_stream_run runs LaserMapping on the back stream itself and
 // orders its streams behind it with events.  A handle without back streams (stream_plan.h) has nothing to wait for.
 void drain_back(alego_handle* h, int slot = -1) {
-  if (slot >= 0 && !h->back.empty()) { (void)hipStreamSynchronize(h->back[std::min<size_t>((size_t)(slot / h->gsize), h->back.size() - 1)]); return; }
-  for (hipStream_t s : h->back) (void)hipStreamSynchronize(s);
+  if (slot >= 0 && !h->back.empty()) { (void)dev_wait(h->back[std::min<size_t>((size_t)(slot / h->gsize), h->back.size() - 1)]); return; }
+  (void)dev_wait(h->back);
 }
 // the per-slot wait: the slot exists and, unless the caller keeps the back stream running (it says why), its group's back stream is drained
 enum BackStream { BACK_DRAINED, BACK_KEPT_RUNNING };
@@ -134,7 +135,7 @@ int check_slot(alego_handle* h, int slot, BackStream back = BACK_DRAINED) {
   return 0;
 }
 // behind everything already queued on every stream group: the host waits for all the handle's streams, front, back and look-ahead
-#define WAIT_ALL(h) HIP_TRY(h, sync_all(h))
+#define WAIT_ALL(h) do { if (int r_ = DevTry(__func__, &(h)->err).wait(all_streams(h))) return r_; } while (0)
 
 // ---- the gate (api_gate.h has the order of checks and the list rules) --------------------------------------------------------------
 // Opened on the first line of every entry point that takes a handle: a null handle is refused; otherwise the handle's device is current and
@@ -352,8 +353,7 @@ int alego_create(const alego_params* params, int device, int n_slots, int ring_l
     }
     double2 *rtd = nullptr, *ctd = nullptr;
     rc |= dalloc(h, &rtd, NS + 6); rc |= dalloc(h, &ctd, (size_t)d.ip_ncb);
-    if (!rc && (hipMemcpy(rtd, rt.data(), rt.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(ctd, ct.data(), ct.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)) { h->err = "upload of the projection tables failed"; rc = ALEGO_ERR_HIP; }
+    if (!rc) rc = DevTry("alego_create", &h->err, "upload of the projection tables").up(reinterpret_cast<double*>(rtd), rt).up(reinterpret_cast<double*>(ctd), ct);
     d.ip_rowtab = rtd; d.ip_coltab = ctd;
     {  // col / 10000.0 of every column (the fraction of the intensity row + col / 10000.0, imageProjection.cpp:101): one IEEE fp64 division each, done here once
        // instead of ~35 instructions per emitted cell on the device; the sum with the row and the rounding to f32 stay where they were
@@ -361,7 +361,7 @@ int alego_create(const alego_params* params, int device, int n_slots, int ring_l
       for (int c = 0; c < d.H; ++c) cf[c] = c / 10000.0;
       double* cfd = nullptr;
       rc |= dalloc(h, &cfd, (size_t)d.H);
-      if (!rc && hipMemcpy(cfd, cf.data(), cf.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) { h->err = "upload of the column table failed"; rc = ALEGO_ERR_HIP; }
+      if (!rc) rc = DevTry("alego_create", &h->err, "upload of the column table").up(cfd, cf);
       d.ip_colfrac = cfd;
     }
     d.ip_fast = 0;
@@ -388,13 +388,8 @@ int alego_create(const alego_params* params, int device, int n_slots, int ring_l
     imu_ptr_of(hd, b)[IMP_LAST] = -1;   // imu_ptr_last_ = -1, imu_ptr_front_ = imu_ptr_last_iter_ = 0 (laserOdometry.cpp:17-19)
   }
   d.seg_lo = h->P.deskew_mode ? d.seg_dsk : d.seg_pts;
-  if (hipMemcpy(d.imu_ptr, ip0.data(), ip0.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) { std::fprintf(stderr, "alego_create: initial state upload failed\n"); alego_destroy(h); return ALEGO_ERR_HIP; }
   h->imu_last_stamp.assign(B, -1e300);
-  if (hipMemcpy(d.scal, sc0.data(), sc0.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(d.lo_state, st.data(), st.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(d.poses, po.data(), po.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-    std::fprintf(stderr, "alego_create: initial state upload failed\n"); alego_destroy(h); return ALEGO_ERR_HIP;
-  }
+  if (DevTry("alego_create", &h->err, "initial state upload").up(d.imu_ptr, ip0).up(d.scal, sc0).up(d.lo_state, st).up(d.poses, po)) { std::fprintf(stderr, "%s\n", h->err.c_str()); alego_destroy(h); return ALEGO_ERR_HIP; }
   if (ip_configure(d) != 0 || lo_configure() != 0 || lm_configure() != 0) { h->err = "hipFuncSetAttribute failed"; std::fprintf(stderr, "alego_create: %s\n", h->err.c_str()); alego_destroy(h); return ALEGO_ERR_HIP; }
   h->lm = lm_host_create(h->P, d, n_slots, h->gsize, h->streams, &h->err);
   if (!h->lm) { std::fprintf(stderr, "alego_create: %s\n", h->err.c_str()); alego_destroy(h); return ALEGO_ERR_HIP; }
@@ -405,7 +400,7 @@ int alego_create(const alego_params* params, int device, int n_slots, int ring_l
 void alego_destroy(alego_handle* h) {
   if (!h) return;
   hipSetDevice(h->device);
-  (void)sync_all(h);
+  (void)dev_wait(all_streams(h));
   if (h->lm) lm_host_destroy(h->lm);
   loop_ctx_destroy(h->lc);
   reloc_ctx_destroy(h->rl);
@@ -433,10 +428,8 @@ int alego_batch_load(alego_handle* h, int slot, int ring_pos, const alego_point*
   if (ring_pos < 0 || ring_pos >= h->d.ring_len || n < 0 || (n > 0 && !pts)) { h->err = "ring_pos / n out of range or null points"; return ALEGO_ERR_ARG; }
   if (n > h->d.Pcap) { h->err = "scan larger than n_scan*horizon_scan"; return ALEGO_ERR_CAPACITY; }
   float4* dst = h->d.in_pts + ((size_t)slot * h->d.ring_len + ring_pos) * h->d.Pcap;
-  if (n > 0) HIP_TRY(h, hipMemcpyAsync(dst, pts, (size_t)n * sizeof(alego_point), hipMemcpyHostToDevice, stream_of(h, slot)));
-  HIP_TRY(h, hipMemcpyAsync(h->d.in_n + slot * h->d.ring_len + ring_pos, &n, sizeof(int), hipMemcpyHostToDevice, stream_of(h, slot)));
-  HIP_TRY(h, hipStreamSynchronize(stream_of(h, slot)));
-  return 0;
+  const hipStream_t S = stream_of(h, slot);
+  return DevTry(__func__, &h->err).up(dst, pts, (size_t)n, S).up(h->d.in_n + slot * h->d.ring_len + ring_pos, &n, 1, S).wait(S);
 }
 
 int alego_replay_create(alego_handle* h, int n_bags, int bag_len) {
@@ -453,15 +446,13 @@ int alego_replay_load(alego_handle* h, int bag, int scan, const alego_point* pts
   if (!h->d.bag_pts || bag < 0 || bag >= h->d.n_bags || scan < 0 || scan >= h->d.bag_len || n < 0 || (n > 0 && !pts)) return ALEGO_ERR_ARG;
   if (n > h->d.Pcap) { h->err = "scan larger than n_scan*horizon_scan"; return ALEGO_ERR_CAPACITY; }
   const size_t idx = (size_t)bag * h->d.bag_len + scan;
-  HIP_TRY(h, hipMemcpy(const_cast<float4*>(h->d.bag_pts) + idx * h->d.Pcap, pts, (size_t)n * sizeof(alego_point), hipMemcpyHostToDevice));
-  HIP_TRY(h, hipMemcpy(const_cast<int*>(h->d.bag_n) + idx, &n, sizeof(int), hipMemcpyHostToDevice));
-  return 0;
+  return DevTry(__func__, &h->err).up(const_cast<float4*>(h->d.bag_pts) + idx * h->d.Pcap, pts, (size_t)n).up(const_cast<int*>(h->d.bag_n) + idx, &n, 1);
 }
 int alego_replay_assign(alego_handle* h, int slot, int bag, int start_scan) {
   ALEGO_GATE_SLOT(h, slot);
   if (!h->d.bag_pts || bag < 0 || bag >= h->d.n_bags || start_scan < 0) return ALEGO_ERR_ARG;
   const int2 v = make_int2(bag, start_scan % h->d.bag_len);
-  HIP_TRY(h, hipMemcpy(const_cast<int2*>(h->d.bag_src) + slot, &v, sizeof(v), hipMemcpyHostToDevice));
+  if (int r = DevTry(__func__, &h->err).up(const_cast<int2*>(h->d.bag_src) + slot, &v, 1)) return r;
   h->replay_assigned = true;
   return 0;
 }
@@ -623,10 +614,8 @@ static int fetch_pose(alego_handle* h, int slot, alego_pose* odom, alego_pose* m
   int sc[SC_COUNT];
   const int pslot = (h->stream_mode && slot == 0) ? h->pose_slot : slot;   // alego_stream_run: the last scan's poses live in its lane
   if (h->stream_mode) WAIT_ALL(h);
-  HIP_TRY(h, hipMemcpyAsync(po, poses_of(h->d, pslot), sizeof(po), hipMemcpyDeviceToHost, stream_of(h, slot)));
-  HIP_TRY(h, hipMemcpyAsync(st, lo_state_of(h->d, slot), sizeof(st), hipMemcpyDeviceToHost, stream_of(h, slot)));
-  HIP_TRY(h, hipMemcpyAsync(sc, scal_of(h->d, slot), sizeof(sc), hipMemcpyDeviceToHost, stream_of(h, slot)));
-  HIP_TRY(h, hipStreamSynchronize(stream_of(h, slot)));
+  const hipStream_t S = stream_of(h, slot);
+  if (int r = DevTry(__func__, &h->err).down(po, poses_of(h->d, pslot), S).down(st, lo_state_of(h->d, slot), S).down(sc, scal_of(h->d, slot), S).wait(S)) return r;
   if (odom) {
     for (int i = 0; i < 3; ++i) odom->t[i] = po[PO_ODOM_T + i];
     for (int i = 0; i < 4; ++i) odom->q[i] = po[PO_ODOM_Q + i];
@@ -667,14 +656,11 @@ int alego_trajectory_get(alego_handle* h, int slot, int32_t first, int32_t n, do
   if (!h->d.traj || first < 0 || n < 0 || (n > 0 && !out14)) return ALEGO_ERR_ARG;
   hipStream_t S = stream_of(h, slot);
   int logged = 0;
-  HIP_TRY(h, hipMemcpyAsync(&logged, traj_n_of(h->d, slot), sizeof(int), hipMemcpyDeviceToHost, S));
-  HIP_TRY(h, hipStreamSynchronize(S));
+  DevTry c(__func__, &h->err);
+  if (c.down(&logged, traj_n_of(h->d, slot), 1, S).wait(S)) return c;
   const int have = std::min(logged, h->d.traj_cap);
   if (first > have || n > have - first) { h->err = "alego_trajectory_get: range beyond the scans logged"; return ALEGO_ERR_ARG; }   // (not first + n: it overflows for large arguments)
-  if (n > 0) {
-    HIP_TRY(h, hipMemcpyAsync(out14, traj_of(h->d, slot, first), (size_t)n * PO_LOG_W * sizeof(double), hipMemcpyDeviceToHost, S));
-    HIP_TRY(h, hipStreamSynchronize(S));
-  }
+  if (n > 0 && c.down(out14, traj_of(h->d, slot, first), (size_t)n * PO_LOG_W, S).wait(S)) return c;   // (the guard is the wait's)
   return logged;
 }
 
@@ -684,11 +670,11 @@ int alego_batch_get_counts(alego_handle* h, int slot, int32_t* out, int cap) {
   const bool lane = h->stream_mode && slot == 0;   // alego_stream_run: the per-scan counters of the last scan live in its lane (buffer 0)
   const int cslot = lane ? h->pose_slot : slot;
   if (lane) WAIT_ALL(h);
-  HIP_TRY(h, hipMemcpyAsync(sc, scal_of(h->d, cslot), sizeof(sc), hipMemcpyDeviceToHost, stream_of(h, slot)));
-  HIP_TRY(h, hipMemcpyAsync(sl, scal_of(h->d, slot), sizeof(sl), hipMemcpyDeviceToHost, stream_of(h, slot)));
-  HIP_TRY(h, hipStreamSynchronize(stream_of(h, slot)));
+  const hipStream_t S = stream_of(h, slot);
+  DevTry c(__func__, &h->err);
+  if (c.down(sc, scal_of(h->d, cslot), S).down(sl, scal_of(h->d, slot), S).wait(S)) return c;
   const int cur = lane ? 0 : sc[SC_CUR];  // buffer written by the last processed scan
-  HIP_TRY(h, hipMemcpy(fc, feat_cnt_of(h->d, fbuf(cslot, cur)), sizeof(fc), hipMemcpyDeviceToHost));
+  if (c.down(fc, feat_cnt_of(h->d, fbuf(cslot, cur)))) return c;
   sc[SC_LO_NSURF] = sl[SC_LO_NSURF]; sc[SC_LO_NCORNER] = sl[SC_LO_NCORNER];   // LaserOdometry's counters belong to the stream's own slot
   int v[16] = {sc[SC_PVALID_OUT], sc[SC_M], sc[SC_NOUT], fc[F_SHARP], fc[F_LSHARP], fc[F_FLAT], fc[F_LFLAT],
                sc[SC_LO_NSURF], sc[SC_LO_NCORNER], 0, 0, 0, 0, 0, 0, 0};  // v[15] = map rebuilds so far
@@ -700,40 +686,40 @@ int alego_batch_get_counts(alego_handle* h, int slot, int32_t* out, int cap) {
 static int download_seg(alego_handle* h, int slot, alego_seg_out* out) {
   const DevCtx& d = h->d;
   int sc[SC_COUNT];
-  HIP_TRY(h, hipMemcpyAsync(sc, scal_of(d, slot), sizeof(sc), hipMemcpyDeviceToHost, stream_of(h, slot)));
-  HIP_TRY(h, hipStreamSynchronize(stream_of(h, slot)));
+  const hipStream_t S = stream_of(h, slot);
+  DevTry c(__func__, &h->err);
+  if (c.down(sc, scal_of(d, slot), S).wait(S)) return c;
   const int M = sc[SC_M], NO = sc[SC_NOUT];
   out->m = M; out->n_outlier = NO;
   if (M > out->seg_cap || NO > out->outlier_cap) { h->err = "seg/outlier capacity too small"; return ALEGO_ERR_CAPACITY; }
   const size_t base = (size_t)slot * d.N;
-  if (out->seg) HIP_TRY(h, hipMemcpyAsync(out->seg, d.seg_pts + base, (size_t)M * 16, hipMemcpyDeviceToHost, stream_of(h, slot)));
-  if (out->ground) HIP_TRY(h, hipMemcpyAsync(out->ground, d.seg_ground + base, (size_t)M, hipMemcpyDeviceToHost, stream_of(h, slot)));
-  if (out->col) HIP_TRY(h, hipMemcpyAsync(out->col, d.seg_col + base, (size_t)M * 4, hipMemcpyDeviceToHost, stream_of(h, slot)));
-  if (out->range) HIP_TRY(h, hipMemcpyAsync(out->range, d.seg_range + base, (size_t)M * 4, hipMemcpyDeviceToHost, stream_of(h, slot)));
-  if (out->ring_start) HIP_TRY(h, hipMemcpyAsync(out->ring_start, ring_start_of(d, slot, 0), d.NS * 4, hipMemcpyDeviceToHost, stream_of(h, slot)));
-  if (out->ring_end) HIP_TRY(h, hipMemcpyAsync(out->ring_end, ring_end_of(d, slot, 0), d.NS * 4, hipMemcpyDeviceToHost, stream_of(h, slot)));
-  HIP_TRY(h, hipMemcpyAsync(out->orientation, ori_of(d, slot), ORI_N * 4, hipMemcpyDeviceToHost, stream_of(h, slot)));
-  if (out->outlier) HIP_TRY(h, hipMemcpyAsync(out->outlier, d.outlier + base, (size_t)NO * 16, hipMemcpyDeviceToHost, stream_of(h, slot)));
-  if (out->label_image) HIP_TRY(h, hipMemcpyAsync(out->label_image, d.label_img + base, (size_t)d.N * 4, hipMemcpyDeviceToHost, stream_of(h, slot)));
-  HIP_TRY(h, hipStreamSynchronize(stream_of(h, slot)));
-  return 0;
+  static_assert(sizeof(out->orientation) == ORI_N * sizeof(float), "alego_seg_out::orientation is an ori row without its padding");
+  if (out->seg) c.down(out->seg, d.seg_pts + base, (size_t)M, S);
+  if (out->ground) c.down(out->ground, d.seg_ground + base, (size_t)M, S);
+  if (out->col) c.down(out->col, d.seg_col + base, (size_t)M, S);
+  if (out->range) c.down(out->range, d.seg_range + base, (size_t)M, S);
+  if (out->ring_start) c.down(out->ring_start, ring_start_of(d, slot, 0), (size_t)d.NS, S);
+  if (out->ring_end) c.down(out->ring_end, ring_end_of(d, slot, 0), (size_t)d.NS, S);
+  c.down(out->orientation, ori_of(d, slot), S);
+  if (out->outlier) c.down(out->outlier, d.outlier + base, (size_t)NO, S);
+  if (out->label_image) c.down(out->label_image, d.label_img + base, (size_t)d.N, S);
+  return c.wait(S);
 }
 
 static int download_feat(alego_handle* h, int slot, alego_feat_out* f) {
   const DevCtx& d = h->d;
   int fc[F_KINDS], M, cur;
-  HIP_TRY(h, hipMemcpy(&cur, scal_of(d, slot) + SC_CUR, 4, hipMemcpyDeviceToHost));
-  HIP_TRY(h, hipMemcpyAsync(fc, feat_cnt_of(d, fbuf(slot, cur)), sizeof(fc), hipMemcpyDeviceToHost, stream_of(h, slot)));
-  HIP_TRY(h, hipMemcpyAsync(&M, scal_of(d, slot) + SC_M, 4, hipMemcpyDeviceToHost, stream_of(h, slot)));
-  HIP_TRY(h, hipStreamSynchronize(stream_of(h, slot)));
+  const hipStream_t S = stream_of(h, slot);
+  DevTry c(__func__, &h->err);
+  if (c.down(&cur, scal_of(d, slot) + SC_CUR, 1)) return c;
+  if (c.down(fc, feat_cnt_of(d, fbuf(slot, cur)), S).down(&M, scal_of(d, slot) + SC_M, 1, S).wait(S)) return c;
   f->n_sharp = fc[F_SHARP]; f->n_less_sharp = fc[F_LSHARP]; f->n_flat = fc[F_FLAT]; f->n_less_flat = fc[F_LFLAT];
   if (fc[F_SHARP] > f->sharp_cap || fc[F_LSHARP] > f->less_sharp_cap || fc[F_FLAT] > f->flat_cap || fc[F_LFLAT] > f->less_flat_cap) { h->err = "feature capacity too small"; return ALEGO_ERR_CAPACITY; }
   alego_point* dst[F_KINDS] = {f->sharp, f->less_sharp, f->flat, f->less_flat};
   for (int k = 0; k < F_KINDS; ++k)
-    if (dst[k]) HIP_TRY(h, hipMemcpyAsync(dst[k], feat_of(d, k, fbuf(slot, cur)), (size_t)fc[k] * 16, hipMemcpyDeviceToHost, stream_of(h, slot)));
-  if (f->point_label) HIP_TRY(h, hipMemcpyAsync(f->point_label, d.plabel + (size_t)slot * d.N, (size_t)M * 4, hipMemcpyDeviceToHost, stream_of(h, slot)));
-  HIP_TRY(h, hipStreamSynchronize(stream_of(h, slot)));
-  return 0;
+    if (dst[k]) c.down(dst[k], feat_of(d, k, fbuf(slot, cur)), (size_t)fc[k], S);
+  if (f->point_label) c.down(f->point_label, d.plabel + (size_t)slot * d.N, (size_t)M, S);
+  return c.wait(S);
 }
 
 int alego_ip_process(alego_handle* h, const alego_scan_in* in, alego_seg_out* out) {
@@ -756,17 +742,14 @@ int alego_lo_process(alego_handle* h, const alego_seg_out* in, alego_feat_out* f
   if (in->m < 0 || in->m > d.N) { h->err = "segmented cloud larger than n_scan*horizon_scan"; return ALEGO_ERR_CAPACITY; }
   if (!in->ring_start || !in->ring_end || (in->m > 0 && (!in->seg || !in->ground || !in->col || !in->range))) { h->err = "alego_lo_process: null input array"; return ALEGO_ERR_ARG; }
   const size_t M = in->m;
-  HIP_TRY(h, hipMemcpyAsync(d.seg_pts, in->seg, M * 16, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(d.seg_ground, in->ground, M, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(d.seg_col, in->col, M * 4, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(d.seg_range, in->range, M * 4, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(ring_start_of(d, slot, 0), in->ring_start, d.NS * 4, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(ring_end_of(d, slot, 0), in->ring_end, d.NS * 4, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(scal_of(d, slot) + SC_M, &in->m, 4, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(ori_of(d, slot), in->orientation, ORI_N * 4, hipMemcpyHostToDevice, h->stream));       // seg_info's start / end orientation: adjustDistortion reads them
-  HIP_TRY(h, hipMemcpyAsync(d.scan_stamp + slot, &in->stamp, 8, hipMemcpyHostToDevice, h->stream));
-  if (h->map_on && lm_host_map_mark_stamped(h->lm, 0, h->stream)) { h->err = "alego_lo_process: upload failed"; return ALEGO_ERR_HIP; }
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  const hipStream_t S = h->stream;
+  DevTry c(__func__, &h->err);
+  c.up(d.seg_pts, in->seg, M, S).up(d.seg_ground, in->ground, M, S).up(d.seg_col, in->col, M, S).up(d.seg_range, in->range, M, S);
+  c.up(ring_start_of(d, slot, 0), in->ring_start, (size_t)d.NS, S).up(ring_end_of(d, slot, 0), in->ring_end, (size_t)d.NS, S).up(scal_of(d, slot) + SC_M, &in->m, 1, S);
+  c.up(ori_of(d, slot), in->orientation, S);       // seg_info's start / end orientation: adjustDistortion reads them
+  if (c.up(d.scan_stamp + slot, &in->stamp, 1, S)) return c;
+  if (h->map_on && lm_host_map_mark_stamped(h->lm, 0, S)) { h->err = "alego_lo_process: upload failed"; return ALEGO_ERR_HIP; }
+  if (c.wait(S)) return c;
   if (int r = enqueue_scan(h, 0, 1, 0, 2, false)) return r;
   if (feat) { if (int r = download_feat(h, 0, feat)) return r; }
   const int r = fetch_pose(h, 0, odom, nullptr);
@@ -786,9 +769,11 @@ int alego_scan_process(alego_handle* h, int slot, const alego_scan_in* in, int s
   ALEGO_GATE_SLOT(h, slot);
   if (!in) return ALEGO_ERR_ARG;
   if (int r = alego_batch_load(h, slot, 0, in->pts, in->n)) return r;
-  HIP_TRY(h, hipMemcpyAsync(h->d.scan_stamp + slot, &in->stamp, 8, hipMemcpyHostToDevice, stream_of(h, slot)));
-  if (h->map_on && lm_host_map_mark_stamped(h->lm, slot, stream_of(h, slot))) { h->err = "alego_scan_process: upload failed"; return ALEGO_ERR_HIP; }
-  HIP_TRY(h, hipStreamSynchronize(stream_of(h, slot)));   // (`in` is the caller's)
+  const hipStream_t S = stream_of(h, slot);
+  DevTry c(__func__, &h->err);
+  if (c.up(h->d.scan_stamp + slot, &in->stamp, 1, S)) return c;
+  if (h->map_on && lm_host_map_mark_stamped(h->lm, slot, S)) { h->err = "alego_scan_process: upload failed"; return ALEGO_ERR_HIP; }
+  if (c.wait(S)) return c;   // (`in` is the caller's)
   if (int r = enqueue_scan(h, slot, 1, 0, stages, seg && seg->label_image)) return r;
   if (seg) { if (int r = download_seg(h, slot, seg)) return r; seg->stamp = in->stamp; }
   if (feat && (stages & 2)) { if (int r = download_feat(h, slot, feat)) return r; }
@@ -797,9 +782,8 @@ int alego_scan_process(alego_handle* h, int slot, const alego_scan_in* in, int s
 
 int alego_set_lo_params(alego_handle* h, int slot, const double* p6) {
   ALEGO_GATE_SLOT(h, slot);
-  HIP_TRY(h, hipMemcpyAsync(lo_state_of(h->d, slot) + LS_PARAMS, p6, 48, hipMemcpyHostToDevice, stream_of(h, slot)));
-  HIP_TRY(h, hipStreamSynchronize(stream_of(h, slot)));
-  return 0;
+  const hipStream_t S = stream_of(h, slot);
+  return DevTry(__func__, &h->err).up(lo_state_of(h->d, slot) + LS_PARAMS, p6, 6, S).wait(S);
 }
 int alego_set_lm_params(alego_handle* h, int slot, const double* p6) {
   ALEGO_GATE_SLOT(h, slot);
@@ -812,10 +796,11 @@ int alego_lo_get_undistorted(alego_handle* h, int slot, alego_point* out, int32_
   if (!h->P.deskew_mode) { h->err = "alego_lo_get_undistorted: deskew_mode is 0 (adjustDistortion is not run: laserOdometry.cpp:115)"; return ALEGO_ERR_ARG; }
   if (cap < 0 || (cap > 0 && !out)) return ALEGO_ERR_ARG;
   int M = 0;
-  HIP_TRY(h, hipMemcpyAsync(&M, scal_of(h->d, slot) + SC_M_DSK, 4, hipMemcpyDeviceToHost, stream_of(h, slot)));   // lo_deskew's own count, not SC_M
-  HIP_TRY(h, hipStreamSynchronize(stream_of(h, slot)));
+  const hipStream_t S = stream_of(h, slot);
+  DevTry c(__func__, &h->err);
+  if (c.down(&M, scal_of(h->d, slot) + SC_M_DSK, 1, S).wait(S)) return c;   // lo_deskew's own count, not SC_M
   if (M > cap) return ALEGO_ERR_CAPACITY;
-  if (M > 0) HIP_TRY(h, hipMemcpy(out, h->d.seg_dsk + (size_t)slot * h->d.N, (size_t)M * sizeof(alego_point), hipMemcpyDeviceToHost));
+  if (M > 0 && c.down(out, h->d.seg_dsk + (size_t)slot * h->d.N, (size_t)M)) return c;   // (M < 0 cannot be a count)
   return M;
 }
 
@@ -908,9 +893,10 @@ int alego_lo_push_imu(alego_handle* h, int slot, const alego_imu* smp, int32_t n
   double* dp;
   HIP_TRY(h, T.get(&dp, pre.size(), false));
   hipStream_t S = stream_of(h, slot);
-  HIP_TRY(h, hipMemcpyAsync(dp, pre.data(), pre.size() * 8, hipMemcpyHostToDevice, S));
+  DevTry c(__func__, &h->err);
+  if (c.up(dp, pre, S)) return c;
   launch_lo_imu_push(h->d, slot, dp, n, S);
-  HIP_TRY(h, hipStreamSynchronize(S));
+  if (c.wait(S)) return c;
   h->imu_last_stamp[slot] = prev;
   return 0;
 }
@@ -951,19 +937,18 @@ int alego_debug_voxel(alego_handle* h, const alego_point* pts, int n, float leaf
   const int c = n > 0 ? n : 1;
   HIP_TRY(h, T.get(&din, (size_t)c, false)); HIP_TRY(h, T.get(&dout, (size_t)c, false)); HIP_TRY(h, T.get(&cnt, 2, false));
   const int hc[2] = {n, 0};
-  HIP_TRY(h, hipMemcpy(cnt, hc, 8, hipMemcpyHostToDevice));
-  if (n) HIP_TRY(h, hipMemcpy(din, pts, (size_t)n * 16, hipMemcpyHostToDevice));
+  DevTry t(__func__, &h->err);
+  if (t.up(cnt, hc).up(din, pts, (size_t)n)) return t;
   VoxJob job{din, cnt, dout, cnt + 1, nullptr, leaf, c, c, nullptr, 0};
   VoxCtx V;
   if (vox_create(&V, &job, 1, &h->err)) return ALEGO_ERR_HIP;
   int rc = vox_run(V, h->stream, &h->err);
-  hipError_t e = hipStreamSynchronize(h->stream);
   int nout = 0;
-  if (e == hipSuccess) e = hipMemcpy(&nout, cnt + 1, 4, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && rc == 0 && nout > cap) { h->err = "debug_voxel: output capacity"; rc = ALEGO_ERR_CAPACITY; }
-  if (e == hipSuccess && rc == 0 && nout) e = hipMemcpy(out, dout, (size_t)nout * 16, hipMemcpyDeviceToHost);
+  t.wait(h->stream).down(&nout, cnt + 1, 1);
+  if (t.ok() && rc == 0 && nout > cap) { h->err = "debug_voxel: output capacity"; rc = ALEGO_ERR_CAPACITY; }
+  if (rc == 0) t.down(out, dout, (size_t)nout);
   vox_destroy(&V);
-  if (e != hipSuccess) { h->err = std::string("debug_voxel: ") + hipGetErrorString(e); return ALEGO_ERR_HIP; }
+  if (t) return t;
   return rc ? rc : nout;
 }
 
@@ -974,13 +959,13 @@ int alego_debug_math(alego_handle* h, int mode, const float* a, const float* b, 
   DevPool T;   // temporaries of this call
   float *da, *db, *dout;
   HIP_TRY(h, T.get(&da, (size_t)n, false)); HIP_TRY(h, T.get(&db, (size_t)n, false)); HIP_TRY(h, T.get(&dout, (size_t)n, false));
-  HIP_TRY(h, hipMemcpy(da, a, (size_t)n * 4, hipMemcpyHostToDevice));
-  if (b) HIP_TRY(h, hipMemcpy(db, b, (size_t)n * 4, hipMemcpyHostToDevice));
+  DevTry c(__func__, &h->err);
+  c.up(da, a, (size_t)n);
+  if (b) c.up(db, b, (size_t)n);
+  if (c) return c;
   // the probe kernel takes (y, x): atan2f(y, x), hypotf(x, y), sinf(y), cosf(y)
   launch_atan2f_probe(da, db, dout, n, mode, h->stream);
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  HIP_TRY(h, hipMemcpy(out, dout, (size_t)n * 4, hipMemcpyDeviceToHost));
-  return 0;
+  return c.wait(h->stream).down(out, dout, (size_t)n);
 }
 int alego_debug_atan2f(alego_handle* h, const float* y, const float* x, float* out, int n) { ALEGO_GATE(h); return alego_debug_math(h, 0, y, x, out, n); }
 
@@ -992,11 +977,11 @@ int alego_debug_std_sort(alego_handle* h, const uint32_t* keys, int n, int depth
   uint32_t* dk;
   int* dp;
   HIP_TRY(h, T.get(&dk, (size_t)n, false)); HIP_TRY(h, T.get(&dp, (size_t)n, false));
-  HIP_TRY(h, hipMemcpy(dk, keys, (size_t)n * 4, hipMemcpyHostToDevice));
+  DevTry c(__func__, &h->err);
+  if (c.up(dk, keys, (size_t)n)) return c;
   if (launch_stdsort_probe(dk, n, depth_limit, dp, h->stream)) return ALEGO_ERR_ARG;
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
   std::vector<int> pos(n), arr(n);
-  HIP_TRY(h, hipMemcpy(pos.data(), dp, (size_t)n * 4, hipMemcpyDeviceToHost));
+  if (c.wait(h->stream).down(pos, dp)) return c;
   // the device returns where the partition phase left every element; __final_insertion_sort is a stable sort of that arrangement
   for (int i = 0; i < n; ++i) { if (pos[i] < 0 || pos[i] >= n) { h->err = "alego_debug_std_sort: arrangement out of range"; return ALEGO_ERR_HIP; } arr[pos[i]] = i; }
   std::stable_sort(arr.begin(), arr.end(), [&](int a, int b) { return keys[a] < keys[b]; });
@@ -1011,13 +996,10 @@ int alego_debug_eval_blocks(alego_handle* h, int type, int n, const double* geom
   DevPool T;   // temporaries of this call
   double *dg, *dp, *dr, *dj;
   HIP_TRY(h, T.get(&dg, (size_t)n * 13, false)); HIP_TRY(h, T.get(&dp, 6, false)); HIP_TRY(h, T.get(&dr, (size_t)n, false)); HIP_TRY(h, T.get(&dj, (size_t)n * 6, false));
-  HIP_TRY(h, hipMemcpy(dg, geom13, (size_t)n * 13 * 8, hipMemcpyHostToDevice));
-  HIP_TRY(h, hipMemcpy(dp, params6, 48, hipMemcpyHostToDevice));
+  DevTry c(__func__, &h->err);
+  if (c.up(dg, geom13, (size_t)n * 13).up(dp, params6, 6)) return c;
   launch_dbg_eval_blocks(type, n, dg, dp, dr, dj, h->stream);
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  HIP_TRY(h, hipMemcpy(res, dr, (size_t)n * 8, hipMemcpyDeviceToHost));
-  HIP_TRY(h, hipMemcpy(jac6, dj, (size_t)n * 48, hipMemcpyDeviceToHost));
-  return 0;
+  return c.wait(h->stream).down(res, dr, (size_t)n).down(jac6, dj, (size_t)n * 6);
 }
 
 int alego_debug_transform_to_start(alego_handle* h, const double* params6, const alego_point* pts, int n, alego_point* out) {
@@ -1028,12 +1010,10 @@ int alego_debug_transform_to_start(alego_handle* h, const double* params6, const
   double* dp;
   float4 *di, *dout;
   HIP_TRY(h, T.get(&dp, 6, false)); HIP_TRY(h, T.get(&di, (size_t)n, false)); HIP_TRY(h, T.get(&dout, (size_t)n, false));
-  HIP_TRY(h, hipMemcpy(dp, params6, 48, hipMemcpyHostToDevice));
-  HIP_TRY(h, hipMemcpy(di, pts, (size_t)n * 16, hipMemcpyHostToDevice));
+  DevTry c(__func__, &h->err);
+  if (c.up(dp, params6, 6).up(di, pts, (size_t)n)) return c;
   launch_dbg_transform_to_start(dp, di, n, dout, h->stream);
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  HIP_TRY(h, hipMemcpy(out, dout, (size_t)n * 16, hipMemcpyDeviceToHost));
-  return 0;
+  return c.wait(h->stream).down(out, dout, (size_t)n);
 }
 
 int alego_debug_check_guards(char* report, int cap) {
@@ -1205,19 +1185,19 @@ int alego_graph_status(alego_handle* h, int slot, int32_t out[4]) {
   ALEGO_GATE_SLOT(h, slot);
   if (!out) return ALEGO_ERR_ARG;
   if (int r = gate_need(h, "alego_graph_status", GRAPH)) return r;
-  HIP_TRY(h, hipStreamSynchronize(stream_of(h, slot)));
+  if (int r = DevTry(__func__, &h->err).wait(stream_of(h, slot))) return r;
   return graph_status(*lm_host_ctx(h->lm), slot, out, &h->err);
 }
 int alego_graph_get_edges(alego_handle* h, int slot, int kind, int32_t first, int32_t n, alego_graph_edge* out) {
   ALEGO_GATE_SLOT(h, slot);
   if (int r = gate_need(h, "alego_graph_get_edges", GRAPH)) return r;
-  HIP_TRY(h, hipStreamSynchronize(stream_of(h, slot)));
+  if (int r = DevTry(__func__, &h->err).wait(stream_of(h, slot))) return r;
   return graph_get_edges(*lm_host_ctx(h->lm), slot, kind, first, n, out, &h->err);
 }
 int alego_graph_set_edges(alego_handle* h, int slot, int32_t first, int32_t n, const alego_graph_edge* chain) {
   ALEGO_GATE_SLOT(h, slot);
   if (int r = gate_need(h, "alego_graph_set_edges", GRAPH)) return r;
-  HIP_TRY(h, hipStreamSynchronize(stream_of(h, slot)));
+  if (int r = DevTry(__func__, &h->err).wait(stream_of(h, slot))) return r;
   return graph_set_edges(*lm_host_ctx(h->lm), slot, first, n, chain, &h->err);
 }
 int alego_graph_add_loops(alego_handle* h, const int32_t* slots, int32_t n, const alego_loop_result* r) {
@@ -1385,15 +1365,10 @@ int alego_debug_regcov(alego_handle* h, const double params6[6], const double* e
   alego_regcov* drec;
   HIP_TRY(h, T.get(&db, blocks.size(), false)); HIP_TRY(h, T.get(&dp, 6, false)); HIP_TRY(h, T.get(&dopt, (size_t)RC_OPT_W, false));
   HIP_TRY(h, T.get(&dqc, qc.size() / 4, false)); HIP_TRY(h, T.get(&dqs, qs.size() / 4, false)); HIP_TRY(h, T.get(&drec, 1, true));
-  HIP_TRY(h, hipMemcpy(db, blocks.data(), blocks.size() * 8, hipMemcpyHostToDevice));
-  HIP_TRY(h, hipMemcpy(dp, params6, 48, hipMemcpyHostToDevice));
-  HIP_TRY(h, hipMemcpy(dopt, opt, sizeof(opt), hipMemcpyHostToDevice));
-  HIP_TRY(h, hipMemcpy(dqc, qc.data(), qc.size() * 4, hipMemcpyHostToDevice));
-  HIP_TRY(h, hipMemcpy(dqs, qs.data(), qs.size() * 4, hipMemcpyHostToDevice));
+  DevTry c(__func__, &h->err);
+  if (c.up(db, blocks).up(dp, params6, 6).up(dopt, opt).up(reinterpret_cast<float*>(dqc), qc).up(reinterpret_cast<float*>(dqs), qs)) return c;   // (the queries are staged as floats, four to a point)
   launch_lm_regcov_debug(db, dqc, n_edge, dqs, n_plane, dp, h->d.P.huber_delta, dopt, drec, h->stream);
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  HIP_TRY(h, hipMemcpy(out, drec, sizeof(*out), hipMemcpyDeviceToHost));
-  return 0;
+  return c.wait(h->stream).down(out, drec, 1);
 }
 
 // ---- solution remapping of the scan-to-map registration ----------------------------------------
@@ -1448,22 +1423,17 @@ int alego_debug_remap_solve(alego_handle* h, const double start6[6], const doubl
   HIP_TRY(h, T.get(&L.li, li.size(), false)); HIP_TRY(h, T.get(&L.ld, ld.size(), false)); HIP_TRY(h, T.get(&L.blocks, blocks.size(), false));
   HIP_TRY(h, T.get(&L.crows, nr * LMS_W, true)); HIP_TRY(h, T.get(&L.cur_corner_ds, qc.size() / 4, false)); HIP_TRY(h, T.get(&L.cur_total_ds, qs.size() / 4, false));
   HIP_TRY(h, T.get(&L.rm_rec, 1, true));
-  HIP_TRY(h, hipMemcpy(L.li, li.data(), li.size() * sizeof(int), hipMemcpyHostToDevice));
-  HIP_TRY(h, hipMemcpy(L.ld, ld.data(), ld.size() * 8, hipMemcpyHostToDevice));
-  HIP_TRY(h, hipMemcpy(L.blocks, blocks.data(), blocks.size() * 8, hipMemcpyHostToDevice));
-  HIP_TRY(h, hipMemcpy(L.cur_corner_ds, qc.data(), qc.size() * 4, hipMemcpyHostToDevice));
-  HIP_TRY(h, hipMemcpy(L.cur_total_ds, qs.data(), qs.size() * 4, hipMemcpyHostToDevice));
+  DevTry c(__func__, &h->err);
+  if (c.up(L.li, li).up(L.ld, ld).up(L.blocks, blocks).up(reinterpret_cast<float*>(L.cur_corner_ds), qc).up(reinterpret_cast<float*>(L.cur_total_ds), qs)) return c;
   DevCtx d = h->d;
   d.slot0 = 0; d.n_launch = 1;
   launch_lm_solve(d, L, remap != 0, h->stream);
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  HIP_TRY(h, hipMemcpy(li.data(), L.li, li.size() * sizeof(int), hipMemcpyDeviceToHost));
-  HIP_TRY(h, hipMemcpy(ld.data(), L.ld, ld.size() * 8, hipMemcpyDeviceToHost));
+  if (c.wait(h->stream).down(li, L.li).down(ld, L.ld)) return c;
   for (int k = 0; k < 12; ++k) params_it[k] = ld[LD_PARAMS_IT + k];
   for (int k = 0; k < 4; ++k) costs[k] = ld[LD_COSTS + k];
   summary[0] = li[LI_SUM0]; summary[1] = li[LI_SUM1];
-  if (rec) HIP_TRY(h, hipMemcpy(rec, L.rm_rec, sizeof(*rec), hipMemcpyDeviceToHost));
-  return 0;
+  if (rec) c.down(rec, L.rm_rec, 1);
+  return c;
 }
 
 // ---- one registration sharded over the GPUs of a node ---------------------------------------------------------------
@@ -1507,7 +1477,7 @@ int alego_loc_enable_from_map(alego_handle* h, alego_handle* map, int slot, doub
   ALEGO_GATE(h);
   if (int r = gate_need(h, "alego_loc_enable_from_map", NOT_STREAM_MODE | UNUSED_HANDLE)) return r;
   if (int r = handover_source(h, map, slot, "alego_loc_enable_from_map")) return r;
-  HIP_TRY(h, sync_all(map));   // a key frame still queued by alego_batch_run(.., sync = 0) is part of the hand-over
+  if (int r = DevTry(__func__, &h->err).wait(all_streams(map))) return r;   // a key frame still queued by alego_batch_run(.., sync = 0) is part of the hand-over
   WAIT_ALL(h);
   return lm_host_loc_enable_from_map(h->lm, h->d, map->lm, slot, radius, capacity, &h->err);
 }
@@ -1515,7 +1485,7 @@ int alego_loc_update_from_map(alego_handle* h, alego_handle* map, int slot) {
   ALEGO_GATE(h);
   if (int r = gate_need(h, "alego_loc_update_from_map", LOCALISING)) return r;
   if (int r = handover_source(h, map, slot, "alego_loc_update_from_map")) return r;
-  HIP_TRY(h, sync_all(map));
+  if (int r = DevTry(__func__, &h->err).wait(all_streams(map))) return r;
   WAIT_ALL(h);   // behind the work queued on every stream group, front and back
   bool rewritten = false;
   const int rc = lm_host_loc_update_from_map(h->lm, map->lm, slot, &rewritten, &h->err);
@@ -1921,15 +1891,15 @@ int alego_debug_get(alego_handle* h, int slot, const char* name, void* out, int 
   ALEGO_GATE_SLOT(h, slot);
   const DevCtx& d = h->d;
   int sc[SC_COUNT];
-  HIP_TRY(h, hipMemcpyAsync(sc, scal_of(d, slot), sizeof(sc), hipMemcpyDeviceToHost, stream_of(h, slot)));
-  HIP_TRY(h, hipStreamSynchronize(stream_of(h, slot)));
+  DevTry c(__func__, &h->err);
+  if (c.down(sc, scal_of(d, slot), stream_of(h, slot)).wait(stream_of(h, slot))) return c;
   const std::string s(name);
   if (s.rfind("la_", 0) == 0) {   // the appearance search: the descriptors / ring keys of the slot's archived frames described so far, as bytes
     const void* rsrc = nullptr;
     size_t bytes = 0;
     if (loop_app_debug_get(h->rl, slot, name, &rsrc, &bytes)) { h->err = std::string("debug_get: ") + name + " needs alego_loop_appearance_enable"; return ALEGO_ERR_ARG; }
     if ((size_t)cap_bytes < bytes) { h->err = "debug_get: buffer too small"; return ALEGO_ERR_CAPACITY; }
-    if (bytes) HIP_TRY(h, hipMemcpy(out, rsrc, bytes, hipMemcpyDeviceToHost));
+    if (c.took(dev_down_bytes(out, rsrc, bytes), "device read")) return c;
     *count = (int)bytes; *dtype = 3;
     return 0;
   }
@@ -1944,7 +1914,7 @@ int alego_debug_get(alego_handle* h, int slot, const char* name, void* out, int 
     size_t bytes = 0;
     if (reloc_debug_get(h->rl, slot, name, &rsrc, &bytes)) { h->err = std::string("debug_get: ") + name + " needs alego_reloc_enable"; return ALEGO_ERR_ARG; }
     if ((size_t)cap_bytes < bytes) { h->err = "debug_get: buffer too small"; return ALEGO_ERR_CAPACITY; }
-    if (bytes) HIP_TRY(h, hipMemcpy(out, rsrc, bytes, hipMemcpyDeviceToHost));
+    if (c.took(dev_down_bytes(out, rsrc, bytes), "device read")) return c;
     *count = (int)bytes; *dtype = 3;
     return 0;
   }
@@ -1968,7 +1938,7 @@ int alego_debug_get(alego_handle* h, int slot, const char* name, void* out, int 
   const size_t base = (size_t)slot * d.N, M = sc[SC_M];
   const size_t fb = fbuf(slot, sc[SC_CUR]);  // buffer written by the last processed scan
   int fc[F_KINDS];
-  HIP_TRY(h, hipMemcpy(fc, feat_cnt_of(d, fb), sizeof(fc), hipMemcpyDeviceToHost));
+  if (c.down(fc, feat_cnt_of(d, fb))) return c;
   static const char* const cloud[F_KINDS] = {"sharp", "less_sharp", "flat", "less_flat"};
   struct Row { std::string name; const void* row; size_t n; int dtype; };   // dtype 0: f32, 1: f64, 2: i32, 3: u8
   std::vector<Row> tab = {
@@ -1994,7 +1964,7 @@ int alego_debug_get(alego_handle* h, int slot, const char* name, void* out, int 
   const size_t n = hit->n, esz = hit->dtype == 1 ? 8 : hit->dtype == 3 ? 1 : 4;
   const int dt = hit->dtype;
   if ((size_t)cap_bytes < n * esz) { h->err = "debug_get: buffer too small"; return ALEGO_ERR_CAPACITY; }
-  if (n) HIP_TRY(h, hipMemcpy(out, src, n * esz, hipMemcpyDeviceToHost));
+  if (c.took(dev_down_bytes(out, src, n * esz), "device read")) return c;
   *count = (int)n; *dtype = dt;
   return 0;
 }

@@ -22,6 +22,7 @@
 #include <cstring>
 
 #include "../../include/alego_mi355x.h"
+#include "dev_copy.h"
 #include "gmap.h"
 #include "kf_store.h"
 #include "pg_math.h"
@@ -360,8 +361,9 @@ int gv_filter(GvCtx* G, int n, float leaf, hipStream_t st, std::string* err) {
   if (n > G->cap) { *err = "voxel grid: scratch too small"; return -3; }
   if (n <= G->small_cap && n <= G->small_max) {
     // (the job table lives on the device: only its leaf changes between calls)
-    if (hipMemcpyAsync(reinterpret_cast<char*>(G->small.jobs) + offsetof(VoxJob, leaf), &leaf, sizeof(float), hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess) { *err = "voxel grid: job upload failed"; return -2; }
+    static_assert(std::is_same<decltype(VoxJob::leaf), float>::value && ALEGO_ERR_HIP == -2, "the leaf of a job is one float; a failed copy returns this file's -2");
+    float* leaf_dev = reinterpret_cast<float*>(reinterpret_cast<char*>(G->small.jobs) + offsetof(VoxJob, leaf));
+    if (int r = DevTry("voxel grid", err, "job upload").up(leaf_dev, &leaf, 1, st).wait(st)) return r;
     return vox_run(G->small, st, err);
   }
   const int nb = (int)std::min<size_t>(((size_t)n + GV_T * 8 - 1) / (GV_T * 8), 2048);

@@ -28,6 +28,7 @@
 
 #include "../../include/alego_mi355x.h"
 #include "dev_cost.h"
+#include "dev_copy.h"
 #include "dev_mem.h"
 #include "kf_store.h"
 #include "pg_math.h"
@@ -376,9 +377,7 @@ void graph_ctx_set_budget(PgCtx** pc, long long bytes) {
 namespace {
 // the counters of one slot: arc4 = LmCtx::arc_stat, pg4 = LmCtx::pg_stat
 int pg_read_slot(const LmCtx& L, int slot, int* arc4, int* pg4, std::string* err) {
-  if (hipMemcpy(arc4, arc_stat_of(L, slot), AS_W * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
-      hipMemcpy(pg4, pg_stat_of(L, slot), PS_W * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return pg_fail(err, "graph: device read failed", ALEGO_ERR_HIP);
-  return 0;
+  return DevTry("graph", err).down(arc4, arc_stat_of(L, slot), AS_W).down(pg4, pg_stat_of(L, slot), PS_W);
 }
 }  // namespace
 
@@ -396,8 +395,7 @@ int graph_get_edges(const LmCtx& L, int slot, int kind, int first, int n, alego_
   if ((kind != 0 && kind != 1) || first < 0 || n < 0 || first > have || n > have - first || (n > 0 && !out)) return pg_fail(err, "graph_get_edges: range beyond the stored edges", ALEGO_ERR_ARG);
   if (n == 0) return 0;
   const alego_graph_edge* src = kind == 0 ? L.pg_chain + arc_row(L, slot, first) : L.pg_loops + (size_t)slot * L.pg_loops_cap + first;
-  if (hipMemcpy(out, src, (size_t)n * sizeof(alego_graph_edge), hipMemcpyDeviceToHost) != hipSuccess) return pg_fail(err, "graph_get_edges: copy failed", ALEGO_ERR_HIP);
-  return 0;
+  return DevTry("graph_get_edges", err, "copy").down(out, src, (size_t)n);
 }
 
 int graph_set_edges(const LmCtx& L, int slot, int first, int n, const alego_graph_edge* chain, std::string* err) {
@@ -410,9 +408,7 @@ int graph_set_edges(const LmCtx& L, int slot, int first, int n, const alego_grap
     if (!pg_edge_finite(chain[i].between, chain[i].variance)) return pg_fail(err, "graph_set_edges: measurement not finite or variance not positive and finite", ALEGO_ERR_ARG);
   }
   if (n == 0) return 0;
-  if (hipMemcpy(L.pg_chain + arc_row(L, slot, first), chain, (size_t)n * sizeof(alego_graph_edge), hipMemcpyHostToDevice) != hipSuccess)
-    return pg_fail(err, "graph_set_edges: copy failed", ALEGO_ERR_HIP);
-  return 0;
+  return DevTry("graph_set_edges", err, "copy").up(L.pg_chain + arc_row(L, slot, first), chain, (size_t)n);
 }
 
 // appends every entry (validated as a whole first: nothing is written on an error)
@@ -436,14 +432,10 @@ int graph_append(PgCtx** pc, const LmCtx& L, int n_slots, const std::vector<PgAp
     last[a[i].slot] = (int)i;
   }
   for (int s = 0; s < n_slots; ++s) if (last[s] >= 0) a[last[s]].last = 1;
-  if (C->stage.reserve(a.size()) != hipSuccess) return pg_fail(err, "graph: staging allocation failed", ALEGO_ERR_HIP);
-  hipError_t e = hipMemcpy(C->stage.p, a.data(), a.size() * sizeof(PgAppend), hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    ALEGO_LAUNCH(pg_append, dim3(((int)a.size() + 63) / 64), dim3(64), 0, st, L, (const PgAppend*)C->stage.p, (int)a.size());
-    e = hipStreamSynchronize(st);
-  }
-  if (e != hipSuccess) return pg_fail(err, "graph: append failed", ALEGO_ERR_HIP);
-  return 0;
+  DevTry c("graph", err);
+  if (c.took(C->stage.reserve(a.size()), "staging allocation").at("append").up(C->stage.p, a)) return c;
+  ALEGO_LAUNCH(pg_append, dim3(((int)a.size() + 63) / 64), dim3(64), 0, st, L, (const PgAppend*)C->stage.p, (int)a.size());
+  return c.wait(st);
 }
 
 int graph_get_estimate(const LmCtx& L, int slot, int first, int n, double* poses12, std::string* err) {
@@ -451,9 +443,7 @@ int graph_get_estimate(const LmCtx& L, int slot, int first, int n, double* poses
   if (int r = pg_read_slot(L, slot, arc, pg, err)) return r;
   const int have = pg[PS_EST];
   if (first < 0 || n < 0 || first > have || n > have - first || (n > 0 && !poses12)) return pg_fail(err, "graph_get_estimate: range beyond the poses of the last optimise", ALEGO_ERR_ARG);
-  if (n && hipMemcpy(poses12, L.pg_est + arc_row(L, slot, first) * 12, (size_t)n * 12 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-    return pg_fail(err, "graph_get_estimate: copy failed", ALEGO_ERR_HIP);
-  return 0;
+  return DevTry("graph_get_estimate", err, "copy").down(poses12, L.pg_est + arc_row(L, slot, first) * 12, (size_t)n * 12);
 }
 
 // Gauss-Newton for the listed slots, chunk by chunk under the budget; out[i] belongs to slots[i].  apply_out[slot] = 1 for the slots whose
@@ -488,16 +478,16 @@ int graph_optimize(PgCtx** pc, const LmCtx& L, int n_slots, const int* slots, in
     pg_layout(&W, C->buf.p, S, P.Nmax, P.Lmax);
     ctl.assign((size_t)S * PC_COUNT, 0);
     for (int q = 0; q < S; ++q) pg_ctl_entry(&ctl, q, out[todo[c0 + q]].n_poses, out[todo[c0 + q]].n_loops, slots[todo[c0 + q]]);
-    if (pg_ctl_upload(W, ctl, st) != hipSuccess || hipMemsetAsync(W.dctl, 0, (size_t)S * PD_COUNT * sizeof(double), st) != hipSuccess)
-      return pg_fail(err, "graph_optimize: upload failed", ALEGO_ERR_HIP);
+    DevTry c("graph_optimize", err, "upload");
+    if (c.up(W.ctl, ctl, st) || c.took(hipMemsetAsync(W.dctl, 0, (size_t)S * PD_COUNT * sizeof(double), st))) return c;
+    c.at("a kernel");
     pg_launch_init(L, W, st);
     for (int it = 0; it < opt.max_iters; ++it) {
       pg_launch_linearize(L, W, st, 0, it == 0 ? (int)PD_COST0 : -1);
       pg_launch_solve(L, W, st);
       ALEGO_LAUNCH(pg_update, dim3(S), dim3(PG_T), 0, st, W, opt.max_iters, opt.step_tol);
       // one read per iteration for the whole chunk: stop launching once every slot of it has finished
-      if (hipMemcpyAsync(ctl.data(), W.ctl, ctl.size() * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-        return pg_fail(err, "graph_optimize: a kernel failed", ALEGO_ERR_HIP);
+      if (c.down(ctl, W.ctl, st).wait(st)) return c;
       bool all = true;
       for (int q = 0; q < S; ++q) all = all && ctl[q * PC_COUNT + PC_DONE];
       if (all) break;
@@ -505,9 +495,7 @@ int graph_optimize(PgCtx** pc, const LmCtx& L, int n_slots, const int* slots, in
     pg_launch_linearize(L, W, st, 1, (int)PD_COST);
     ALEGO_LAUNCH(pg_store, dim3((P.Nmax * 12 + PG_T - 1) / PG_T, S), dim3(PG_T), 0, st, L, W);
     dctl.assign((size_t)S * PD_COUNT, 0.0);
-    if (hipMemcpyAsync(ctl.data(), W.ctl, ctl.size() * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipMemcpyAsync(dctl.data(), W.dctl, dctl.size() * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-      return pg_fail(err, "graph_optimize: a kernel failed", ALEGO_ERR_HIP);
+    if (c.down(ctl, W.ctl, st).down(dctl, W.dctl, st).wait(st)) return c;
     for (int q = 0; q < S; ++q) {
       alego_graph_result& r = out[todo[c0 + q]];
       const int s = slots[todo[c0 + q]];
@@ -521,9 +509,7 @@ int graph_optimize(PgCtx** pc, const LmCtx& L, int n_slots, const int* slots, in
 
 // the applied slots' flags on the device (kept with the context)
 int graph_upload_apply(PgCtx* C, const std::vector<int>& apply, const int** dev, hipStream_t st, std::string* err) {
-  if (C->apply.reserve(apply.size()) != hipSuccess) return pg_fail(err, "graph_optimize: allocation failed", ALEGO_ERR_HIP);
-  if (hipMemcpyAsync(C->apply.p, apply.data(), apply.size() * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-    return pg_fail(err, "graph_optimize: upload failed", ALEGO_ERR_HIP);
+  if (int r = DevTry("graph_optimize", err).took(C->apply.reserve(apply.size())).at("upload").up(C->apply.p, apply, st).wait(st)) return r;
   *dev = C->apply.p;
   return 0;
 }

@@ -139,6 +139,7 @@ __global__ void icp_init(IcpState* S, int n_src, const int* n_tgt) {
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------
+#include "dev_copy.h"
 #include "dev_mem.h"
 #include "loop_ctx.h"
 
@@ -163,15 +164,12 @@ int icp_run(const alego_params& P, const alego_kf_in* latest, const alego_kf_in*
   DevPool T;   // temporaries of this call
   IcpFrame* dF; float4 *draw, *dsrc, *dcur, *dtraw, *dtgt; int* dcnt; IcpState* dS; double* dpart;
   const int nwg = std::max(1, (n_src + ICP_T - 1) / ICP_T);
-  hipError_t e = hipSuccess;
-  auto get = [&](auto** p, size_t count) { if (e == hipSuccess) e = T.get(p, count, false); };
+  DevTry c("loop closure", err);
+  auto get = [&](auto** p, size_t count) { if (c.ok()) c.took(T.get(p, count, false)); };
   get(&dF, (size_t)nf); get(&draw, raw.size()); get(&dsrc, (size_t)std::max(n_src, 1)); get(&dcur, (size_t)std::max(n_src, 1));
   get(&dtraw, (size_t)std::max(n_traw, 1)); get(&dtgt, (size_t)std::max(n_traw, 1)); get(&dcnt, 2); get(&dS, 1); get(&dpart, (size_t)nwg * 18);
-  if (e == hipSuccess) e = hipMemcpyAsync(dF, F.data(), sizeof(IcpFrame) * nf, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess && !raw.empty()) e = hipMemcpyAsync(draw, raw.data(), raw.size() * 16, hipMemcpyHostToDevice, st);
   const int hc[2] = {n_traw, 0};
-  if (e == hipSuccess) e = hipMemcpyAsync(dcnt, hc, 8, hipMemcpyHostToDevice, st);
-  if (e != hipSuccess) { *err = std::string("loop closure: ") + hipGetErrorString(e); return ALEGO_ERR_HIP; }
+  if (c.up(dF, F, st).up(draw, raw, st).up(dcnt, hc, st)) return c;
   hipLaunchKernelGGL(icp_build, dim3(8, nf), dim3(ICP_T), 0, st, dF, nf, draw, dsrc, dtraw);
   VoxJob job{dtraw, dcnt, dtgt, dcnt + 1, nullptr, P.lc_leaf, std::max(n_traw, 1), std::max(n_traw, 1), nullptr, 0};
   VoxCtx V;
@@ -187,11 +185,11 @@ int icp_run(const alego_params& P, const alego_kf_in* latest, const alego_kf_in*
   if (n_src > 0) hipLaunchKernelGGL(icp_fitness, dim3(nwg), dim3(ICP_T), 0, st, dS, dsrc, dtgt, dpart);   // (its idle lanes read src[n_src - 1]; without a source the fitness stays icp_init's)
   if (n_src > 0) hipLaunchKernelGGL(icp_fitness_final, dim3(1), dim3(64), 0, st, dS, dpart, nwg);
   IcpState S;
-  e = hipMemcpyAsync(&S, dS, sizeof(S), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e == hipSuccess && target_out && S.n_tgt > 0) e = hipMemcpy(target_out, dtgt, (size_t)std::min(S.n_tgt, target_cap) * 16, hipMemcpyDeviceToHost);
+  c.down(&S, dS, 1, st).wait(st);
+  if (c.ok() && target_out && S.n_tgt > 0) c.down(target_out, dtgt, (size_t)std::min(S.n_tgt, target_cap));
   vox_destroy(&V);
-  if (e != hipSuccess || rc) { *err = std::string("loop closure: ") + (rc ? "VoxelGrid failed" : hipGetErrorString(e)); return ALEGO_ERR_HIP; }
+  if (rc) { *err = "loop closure: VoxelGrid failed"; return ALEGO_ERR_HIP; }
+  if (c) return c;
   out->converged = S.converged; out->iterations = S.iter; out->fitness = S.n_src && S.n_tgt ? S.fitness : 1.7976931348623157e308;
   for (int k = 0; k < 16; ++k) out->correction[k] = S.Tf[k];
   out->n_source = S.n_src; out->n_target = S.n_tgt;

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/alego_mi355x.h"
+#include "dev_copy.h"
 #include "dev_mem.h"
 #include "icp_math.h"
 #include "kf_store.h"
@@ -425,11 +426,12 @@ static int lc_attempts(LcCtx* C, const alego_params& P, const int* slots, const 
     }
     if (!cur.empty()) chunks.push_back(cur);
   }
+  DevTry t("loop search", err);
   if (!chunks.empty()) {
     if (int rc = lc_reserve(C, C->list_cap, std::max(C->budget, need), err)) return rc;
     for (const auto& ch : chunks) {
       const int J = (int)ch.size();
-      if (hipMemcpyAsync(C->jobs, ch.data(), (size_t)J * sizeof(LcJob), hipMemcpyHostToDevice, st) != hipSuccess) { *err = "loop search: upload failed"; return ALEGO_ERR_HIP; }
+      if (t.up(C->jobs, ch, st)) return t;
       gather(C->jobs, C->det, J, nfr, C->src, C->raw, st);
       vjobs.emplace_back((size_t)J);
       std::vector<VoxJob>& vj = vjobs.back();
@@ -440,7 +442,7 @@ static int lc_attempts(LcCtx* C, const alego_params& P, const int* slots, const 
         vj[j].in = C->raw + b.raw_off; vj[j].n_in = &C->det[b.li].n_raw; vj[j].out = C->tgt + b.raw_off; vj[j].n_out = C->ntgt + j;
         vj[j].leaf = P.lc_leaf; vj[j].cap = nr; vj[j].out_cap = nr; vj[j].off = b.raw_off;
       }
-      if (hipMemcpyAsync(C->V.jobs, vj.data(), (size_t)J * sizeof(VoxJob), hipMemcpyHostToDevice, st) != hipSuccess) { *err = "loop search: upload failed"; return ALEGO_ERR_HIP; }
+      if (t.up(C->V.jobs, vj, st)) return t;
       VoxCtx V = C->V;
       V.njobs = J; V.grid_small = J; V.grid_big = J;
       if (int rc = vox_run(V, st, err)) return rc;
@@ -449,20 +451,16 @@ static int lc_attempts(LcCtx* C, const alego_params& P, const int* slots, const 
       // the next chunk reuses jobs / scratch: the copies and kernels above are ordered on `st`
     }
   }
-  if (hipMemcpyAsync(o, C->out, (size_t)n * sizeof(LcOut), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-    *err = "loop search: kernels failed"; return ALEGO_ERR_HIP;
-  }
-  return 0;
+  return t.at("kernels").down(o, C->out, (size_t)n, st).wait(st);
 }
 
 // one piece of the list (at most list_cap entries): detection, then the attempted slots in chunks
 static int lc_piece(LcCtx* C, const LmCtx& L, const alego_params& P, const int* slots, int n, alego_loop_result* res, hipStream_t st, std::string* err) {
-  if (hipMemcpyAsync(C->list, slots, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess) { *err = "loop search: upload failed"; return ALEGO_ERR_HIP; }
+  DevTry t("loop search", err);
+  if (t.up(C->list, slots, (size_t)n, st)) return t;
   ALEGO_LAUNCH(lc_detect, dim3(n), dim3(LC_DT), 0, st, L, C->list, P, C->det);
   std::vector<LcDet> det((size_t)n);
-  if (hipMemcpyAsync(det.data(), C->det, (size_t)n * sizeof(LcDet), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-    *err = "loop search: detection failed"; return ALEGO_ERR_HIP;
-  }
+  if (t.at("detection").down(det, C->det, st).wait(st)) return t;
   std::vector<LcOut> o((size_t)n);
   if (int rc = lc_attempts(C, P, slots, det.data(), n, loop_archive_gather(L), o.data(), st, err)) return rc;
   for (int i = 0; i < n; ++i) {
@@ -510,7 +508,7 @@ int loop_attempts(LcCtx** pc, const alego_params& P, int n_slots, const int* slo
   // entries may repeat a slot
   for (int i0 = 0; i0 < n; i0 += C->list_cap) {
     const int c = std::min(C->list_cap, n - i0);
-    if (hipMemcpyAsync(C->det, det + i0, (size_t)c * sizeof(LcDet), hipMemcpyHostToDevice, st) != hipSuccess) { *err = "loop attempts: upload failed"; return ALEGO_ERR_HIP; }
+    if (int rc = DevTry("loop attempts", err).up(C->det, det + i0, (size_t)c, st)) return rc;
     if (int rc = lc_attempts(C, P, slots + i0, det + i0, c, gather, out + i0, st, err)) return rc;
   }
   return 0;
@@ -545,14 +543,9 @@ int loop_debug_nn1(const alego_point* tgt, int n_tgt, const alego_point* q, int 
   if (!get(&dt, (size_t)n_tgt) || !get(&dq, (size_t)nq) || !get(&sp, (size_t)n_tgt) || !get(&cb, (size_t)cell_cap * 2) ||
       !get(&cs, (size_t)cell_cap + 1) || !get(&cc, (size_t)cell_cap + 1) || !get(&di, (size_t)nq) || !get(&dd, (size_t)nq) ||
       !get(&g, 1)) { *err = "debug_nn1: allocation failed"; return ALEGO_ERR_HIP; }
-  hipError_t e = n_tgt ? hipMemcpyAsync(dt, tgt, (size_t)n_tgt * 16, hipMemcpyHostToDevice, st) : hipSuccess;
-  if (e == hipSuccess && nq) e = hipMemcpyAsync(dq, q, (size_t)nq * 16, hipMemcpyHostToDevice, st);
-  if (e != hipSuccess) { *err = "debug_nn1: upload failed"; return ALEGO_ERR_HIP; }
+  DevTry c("debug_nn1", err);
+  if (c.up(dt, tgt, (size_t)n_tgt, st).up(dq, q, (size_t)nq, st)) return c;
   ALEGO_LAUNCH(lc_grid_one, dim3(1), dim3(LC_DT), 0, st, dt, n_tgt, cell_cap, g, cs, cc, cb, sp);
   if (nq) ALEGO_LAUNCH(lc_nn_many, dim3((nq + LC_DT - 1) / LC_DT), dim3(LC_DT), 0, st, g, cs, cb, sp, dq, nq, di, dd);
-  if (nq) e = hipMemcpyAsync(idx, di, (size_t)nq * 4, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess && nq) e = hipMemcpyAsync(d2, dd, (size_t)nq * 4, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) { *err = std::string("debug_nn1: ") + hipGetErrorString(e); return ALEGO_ERR_HIP; }
-  return 0;
+  return c.down(idx, di, (size_t)nq, st).down(d2, dd, (size_t)nq, st).wait(st);
 }

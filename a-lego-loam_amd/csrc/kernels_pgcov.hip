@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/alego_mi355x.h"
+#include "dev_copy.h"
 #include "dev_mem.h"
 #include "kf_store.h"
 #include "pg_cov_math.h"
@@ -238,10 +239,8 @@ int pgc_run(PgCtx** pc, const LmCtx& L, const std::vector<PgcEntry>& ent, bool m
       std::copy(e.nodes.begin(), e.nodes.end(), nodes.begin() + (size_t)q * Umax);
       std::copy(e.cand.begin(), e.cand.end(), cand.begin() + (size_t)q * Kmax);
     }
-    hipError_t he = pg_ctl_upload(W, ctl, st);
-    if (he == hipSuccess && Kmax > 0) he = hipMemcpyAsync(V.nodes, nodes.data(), (size_t)S * Umax * sizeof(int), hipMemcpyHostToDevice, st);
-    if (he == hipSuccess && Kmax > 0) he = hipMemcpyAsync(V.cand, cand.data(), (size_t)S * Kmax * sizeof(PgcCand), hipMemcpyHostToDevice, st);
-    if (he != hipSuccess) return pg_fail(err, "graph covariance: upload failed", ALEGO_ERR_HIP);
+    // (nodes and cand keep one spare element when there are no candidates: Kmax == 0 means Umax == 0, and nothing is copied)
+    if (int r = DevTry("graph covariance", err).up(W.ctl, ctl, st).up(V.nodes, nodes.data(), (size_t)S * Umax, st).up(V.cand, cand.data(), (size_t)S * Kmax, st)) return r;
     launch_pg_linear_pass(L, W, st);
     if (marg) {
       ALEGO_LAUNCH(pgc_blocks, dim3((Nmax + PG_T - 1) / PG_T, S), dim3(PG_T), 0, st, W, V);
@@ -278,9 +277,7 @@ int graph_marginals(PgCtx** pc, const LmCtx& L, int n_slots, const int* slots, i
   std::vector<double> host;
   return pgc_run(pc, L, ent, true, st, err, [&](const PgWork& W, const PgCov& V, size_t c0, int S) {
     ctl.resize((size_t)S * PC_COUNT); host.resize((size_t)S * W.Nmax * 36);
-    if (hipMemcpyAsync(ctl.data(), W.ctl, ctl.size() * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipMemcpyAsync(host.data(), V.Sd, host.size() * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-      return pg_fail(err, "graph_marginals: a kernel failed", ALEGO_ERR_HIP);
+    if (int r = DevTry("graph_marginals", err, "a kernel").down(ctl, W.ctl, st).down(host, V.Sd, st).wait(st)) return r;
     for (int q = 0; q < S; ++q) {
       const int i = which[c0 + q];
       out[i].status = ctl[(size_t)q * PC_COUNT + PC_STATUS] == -2 ? -2 : 1;
@@ -328,8 +325,7 @@ int graph_check(PgCtx** pc, const LmCtx& L, int n_slots, const int* slots, int n
   std::vector<alego_graph_check> host;
   return pgc_run(pc, L, run, false, st, err, [&](const PgWork&, const PgCov& V, size_t c0, int S) {
     host.resize((size_t)S * V.Kmax);
-    if (hipMemcpyAsync(host.data(), V.out, host.size() * sizeof(alego_graph_check), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-      return pg_fail(err, "graph check: a kernel failed", ALEGO_ERR_HIP);
+    if (int r = DevTry("graph check", err, "a kernel").down(host, V.out, st).wait(st)) return r;
     for (int q = 0; q < S; ++q) {
       const PgcEntry& x = run[c0 + q];
       for (size_t k = 0; k < x.where.size(); ++k) out[x.where[k]] = host[(size_t)q * V.Kmax + k];

@@ -67,6 +67,7 @@
 #include "merge_math.h"
 #include "dev_common.h"
 #include "dev_cost.h"
+#include "dev_copy.h"
 #include "dev_mem.h"
 #include "kf_store.h"
 #include "loop_ctx.h"
@@ -462,23 +463,18 @@ void reloc_ctx_set(RlCtx** pr, int what, long long v) {   // what 0: pairs per c
 bool reloc_enabled(const RlCtx* R) { return R && R->n_slots > 0; }
 
 // descriptors and ring keys of the store's L.loc_n frames (queued on st, finished on return), and the host copy of their counts and poses
-static hipError_t rl_describe_map(RlCtx* R, const LmCtx& L, hipStream_t st) {
+static void rl_describe_map(RlCtx* R, const LmCtx& L, hipStream_t st, DevTry* c) {
   const int N = L.loc_n;
-  hipError_t e = hipSuccess;
   if (N > 0) ALEGO_LAUNCH(rl_desc, dim3(N), dim3(RL_T), 0, st, L, 0, (const int*)nullptr, R->w, R->zoff, R->mdesc, R->mkey, (RlSlot*)nullptr, (uint16_t*)nullptr);
   std::vector<int> cnt((size_t)N * KF_CNT_W);
   std::vector<float> pose((size_t)N * KF_POSE_W);
-  if (e == hipSuccess && N > 0) e = hipMemcpyAsync(cnt.data(), kf_cnt_of(L, kf_row_at(L, 0, 0)), cnt.size() * sizeof(int), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess && N > 0) e = hipMemcpyAsync(pose.data(), kf_pose_of(L, kf_row_at(L, 0, 0)), pose.size() * sizeof(float), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return e;
+  if (c->down(cnt, kf_cnt_of(L, kf_row_at(L, 0, 0)), st).down(pose, kf_pose_of(L, kf_row_at(L, 0, 0)), st).wait(st)) return;
   R->cnt.resize(N); R->pose.resize((size_t)N * 6);
   for (int i = 0; i < N; ++i) {
     R->cnt[i] = kf_clouds_points(kf_clouds_row_at(L, 0, i, cnt.data() + (size_t)i * KF_CNT_W));   // as rl_gather counts them
     for (int k = 0; k < 6; ++k) R->pose[(size_t)i * 6 + k] = pose[(size_t)i * KF_POSE_W + k];
   }
   R->N = N;
-  return hipSuccess;
 }
 
 int reloc_enable(RlCtx** pr, const LmCtx& L, int n_slots, double max_range, double z_offset, hipStream_t st, std::string* err) {
@@ -490,21 +486,21 @@ int reloc_enable(RlCtx** pr, const LmCtx& L, int n_slots, double max_range, doub
   const DevGet get{R->store, RL_ERR, err};
   if (!get(&R->mdesc, F * RL_WORDS) || !get(&R->mkey, F * RL_NR) || !get(&R->qdesc, (size_t)n_slots * RL_WORDS) || !get(&R->qkey, (size_t)n_slots * RL_NR) ||
       !get(&R->list, (size_t)n_slots) || !get(&R->apply, (size_t)n_slots) || !get(&R->state, (size_t)n_slots) || !get(&R->klist, (size_t)n_slots * RL_NR)) return undo(ALEGO_ERR_HIP);
-  hipError_t e = hipMemsetAsync(R->qdesc, 0, std::max<size_t>(16, (size_t)n_slots * RL_BYTES), st);
-  if (e == hipSuccess) e = hipMemsetAsync(R->qkey, 0, std::max<size_t>(16, (size_t)n_slots * RL_NR * 2), st);
-  if (e == hipSuccess) e = rl_describe_map(R, L, st);
-  if (e != hipSuccess) { *err = std::string("alego_reloc_enable: ") + hipGetErrorString(e); return undo(ALEGO_ERR_HIP); }
+  DevTry c("alego_reloc_enable", err);
+  c.took(hipMemsetAsync(R->qdesc, 0, std::max<size_t>(16, (size_t)n_slots * RL_BYTES), st), "clearing");
+  if (c.ok()) c.took(hipMemsetAsync(R->qkey, 0, std::max<size_t>(16, (size_t)n_slots * RL_NR * 2), st), "clearing");
+  if (c.ok()) rl_describe_map(R, L, st, &c);
+  if (c) return undo(c);
   R->n_slots = n_slots;
   return 0;
 }
 // the store changed (alego_loc_update_from_map): the descriptors and ring keys of its frames are built again; a failure leaves none (no frame is a candidate)
 int reloc_refresh(RlCtx* R, const LmCtx& L, hipStream_t st, std::string* err) {
   if (!reloc_enabled(R)) return 0;
-  const hipError_t e = rl_describe_map(R, L, st);
-  if (e == hipSuccess) return 0;
-  R->N = 0; R->cnt.clear(); R->pose.clear();
-  *err = std::string("alego_loc_update_from_map: describing the map failed: ") + hipGetErrorString(e);
-  return ALEGO_ERR_HIP;
+  DevTry c("alego_loc_update_from_map", err, "describing the map");
+  rl_describe_map(R, L, st, &c);
+  if (c) { R->N = 0; R->cnt.clear(); R->pose.clear(); }
+  return c;
 }
 
 // The exact search of nq queries (qr[q]; off is filled in here): cand[q][r] = the candidate word, RL_CAND_NONE where fewer frames are eligible.
@@ -519,6 +515,7 @@ static int rl_search_run(RlCtx* R, const uint32_t* qdesc, const uint16_t* qkey, 
   for (int q = 0; q < nq; ++q) { all += qr[q].n; if (nelig) nelig[q] = 0; }
   R->stats[0] = 0; R->stats[1] = (int)std::min<long long>(all, 0x7fffffff);
   if (nq == 0 || all == 0) return 0;
+  DevTry t("descriptor search", err);
   // chunks [first, first + count): consecutive queries; pairs and queries of the largest chunk size the scratch
   const long long budget = std::min<long long>(R->budget, 1LL << 30);
   std::vector<std::pair<int, int>> chunks;
@@ -534,7 +531,7 @@ static int rl_search_run(RlCtx* R, const uint32_t* qdesc, const uint16_t* qkey, 
   }
   if (R->pairs_cap < pc || R->q_cap < qc) {
     pc = std::max(R->pairs_cap, pc); qc = std::max(R->q_cap, qc);
-    if (hipStreamSynchronize(st) != hipSuccess) { *err = "descriptor search: a stream failed"; return ALEGO_ERR_HIP; }
+    if (t.wait(st)) return t;
     R->scratch.clear(); R->pairs_cap = R->q_cap = 0;
     const DevGet get{R->scratch, RL_ERR, err};
     if (!get(&R->bound, pc) || !get(&R->res2, pc) || !get(&R->list2, pc) || !get(&R->resA, qc * ALEGO_RELOC_MAX_CAND) || !get(&R->listA, qc * ALEGO_RELOC_MAX_CAND) || !get(&R->cntA, qc) ||
@@ -548,10 +545,10 @@ static int rl_search_run(RlCtx* R, const uint32_t* qdesc, const uint16_t* qkey, 
     for (int q = q0; q < q0 + c; ++q) nmax = std::max(nmax, qr[q].n);
     const int nblk = std::max(1, std::min(RL_SEARCH_BLOCKS, (nmax + RL_WAVES - 1) / RL_WAVES));
     const dim3 gb(std::max(1, (nmax + RL_T - 1) / RL_T), c);
-    if (hipMemcpyAsync(R->qr, qr + q0, (size_t)c * sizeof(RlQuery), hipMemcpyHostToDevice, st) != hipSuccess) { *err = "descriptor search: upload failed"; return ALEGO_ERR_HIP; }
+    if (t.at("upload").up(R->qr, qr + q0, (size_t)c, st)) return t;
     ALEGO_LAUNCH(rl_bound, gb, dim3(RL_T), 0, st, (const RlQuery*)R->qr, qkey, mkey, R->bound);
     if (mask) {
-      if (hipMemsetAsync(R->nelig, 0, (size_t)c * sizeof(int), st) != hipSuccess) { *err = "descriptor search: the search failed"; return ALEGO_ERR_HIP; }
+      if (t.took(hipMemsetAsync(R->nelig, 0, (size_t)c * sizeof(int), st), "the search")) return t;
       mask(R->qr, c, nmax, R->bound, R->nelig, st);
     }
     ALEGO_LAUNCH(rl_pick, dim3(c), dim3(RL_T), 0, st, (const RlQuery*)R->qr, R->bound, n_cand, R->listA, R->cntA);
@@ -561,10 +558,9 @@ static int rl_search_run(RlCtx* R, const uint32_t* qdesc, const uint16_t* qkey, 
     ALEGO_LAUNCH(rl_topk, dim3(c), dim3(RL_T), 0, st, (const RlQuery*)R->qr, R->list2, R->cnt2, R->res2, n_cand, R->cand);
     // (the next chunk reuses the scratch: copies and kernels are ordered on `st`; cand is pageable, so the copy below has left the device when it returns)
     cnt2.resize((size_t)c);
-    if (hipMemcpyAsync(cand + (size_t)q0 * ALEGO_RELOC_MAX_CAND, R->cand, (size_t)c * ALEGO_RELOC_MAX_CAND * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipMemcpyAsync(cnt2.data(), R->cnt2, (size_t)c * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
-        (mask && nelig && hipMemcpyAsync(nelig + q0, R->nelig, (size_t)c * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess) ||
-        hipStreamSynchronize(st) != hipSuccess) { *err = "descriptor search: the search failed"; return ALEGO_ERR_HIP; }
+    t.at("the search").down(cand + (size_t)q0 * ALEGO_RELOC_MAX_CAND, R->cand, (size_t)c * ALEGO_RELOC_MAX_CAND, st).down(cnt2, R->cnt2, st);
+    if (mask && nelig) t.down(nelig + q0, R->nelig, (size_t)c, st);
+    if (t.wait(st)) return t;
     for (int v : cnt2) R->stats[0] = (int)std::min<long long>((long long)R->stats[0] + v, 0x7fffffff);
   }
   return 0;
@@ -587,9 +583,8 @@ int reloc_debug_search(RlCtx** pr, const uint8_t* map_desc, int n_map, const uin
   uint16_t *mk = nullptr, *qk = nullptr;
   const DevGet get{tmp, RL_ERR, err};
   if (!get(&md, (size_t)n_map * RL_WORDS) || !get(&qd, (size_t)n_q * RL_WORDS) || !get(&mk, (size_t)n_map * RL_NR) || !get(&qk, (size_t)n_q * RL_NR)) return ALEGO_ERR_HIP;
-  hipError_t e = n_map ? hipMemcpyAsync(md, map_desc, (size_t)n_map * RL_BYTES, hipMemcpyHostToDevice, st) : hipSuccess;
-  if (e == hipSuccess && n_q) e = hipMemcpyAsync(qd, q_desc, (size_t)n_q * RL_BYTES, hipMemcpyHostToDevice, st);
-  if (e != hipSuccess) { *err = "debug_reloc_search: upload failed"; return ALEGO_ERR_HIP; }
+  DevTry c("debug_reloc_search", err);   // (a descriptor: RL_BYTES bytes on the host, RL_WORDS words on the device)
+  if (c.up(reinterpret_cast<uint8_t*>(md), map_desc, (size_t)n_map * RL_BYTES, st).up(reinterpret_cast<uint8_t*>(qd), q_desc, (size_t)n_q * RL_BYTES, st)) return c;
   if (n_map) ALEGO_LAUNCH(rl_keys, dim3(n_map), dim3(64), 0, st, md, mk);
   if (n_q) ALEGO_LAUNCH(rl_keys, dim3(n_q), dim3(64), 0, st, qd, qk);
   std::vector<int> sel((size_t)n_q);
@@ -597,7 +592,8 @@ int reloc_debug_search(RlCtx** pr, const uint8_t* map_desc, int n_map, const uin
   std::vector<unsigned long long> cand((size_t)n_q * ALEGO_RELOC_MAX_CAND);
   std::vector<RlQuery> qr = rl_whole_map(sel.data(), n_q, n_map);
   int rc = rl_search_run(R, qd, qk, qr.data(), n_q, md, mk, n_cand, cand.data(), RlMask(), nullptr, st, err);
-  if (hipStreamSynchronize(st) != hipSuccess && !rc) { *err = "debug_reloc_search: kernels failed"; rc = ALEGO_ERR_HIP; }
+  const hipError_t we = dev_wait(st);
+  if (!rc) rc = c.took(we, "kernels");
   if (rc) return rc;
   for (int q = 0; q < n_q; ++q)
     for (int r = 0; r < n_cand; ++r) {
@@ -643,12 +639,10 @@ int reloc_run(RlCtx* R, LcCtx** lc, const LmCtx& L, const alego_params& P, const
   // the listed slots' descriptors, and of their state what the host needs (the caller has drained every stream): O(n), whatever the handle's size
   std::vector<RlSlot> state((size_t)n);
   std::vector<uint16_t> qkey((size_t)n * RL_NR);
-  if (hipMemcpyAsync(R->list, slots, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess) { *err = "alego_loc_relocalize: upload failed"; return ALEGO_ERR_HIP; }
+  DevTry c("alego_loc_relocalize", err);
+  if (c.up(R->list, slots, (size_t)n, st)) return c;
   ALEGO_LAUNCH(rl_desc, dim3(n), dim3(RL_T), 0, st, L, 1, (const int*)R->list, R->w, R->zoff, R->qdesc, R->qkey, R->state, R->klist);
-  hipError_t e = hipMemcpyAsync(state.data(), R->state, state.size() * sizeof(RlSlot), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(qkey.data(), R->klist, qkey.size() * sizeof(uint16_t), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) { *err = std::string("alego_loc_relocalize: descriptors failed: ") + hipGetErrorString(e); return ALEGO_ERR_HIP; }
+  if (c.at("descriptors").down(state, R->state, st).down(qkey, R->klist, st).wait(st)) return c;
   // searchable: a mapping frame has run and a point lies in range (every code is >= 1, so an all-zero key is an empty descriptor)
   std::vector<int> qi, sel;
   for (int i = 0; i < n; ++i) {
@@ -701,9 +695,9 @@ int reloc_run(RlCtx* R, LcCtx** lc, const LmCtx& L, const alego_params& P, const
         out[i].applied = 1;
       }
     if (!ap.empty()) {
-      if (hipMemcpyAsync(R->apply, ap.data(), ap.size() * sizeof(RlApply), hipMemcpyHostToDevice, st) != hipSuccess) { *err = "alego_loc_relocalize: upload failed"; return ALEGO_ERR_HIP; }
+      if (c.at("upload").up(R->apply, ap, st)) return c;
       ALEGO_LAUNCH(rl_apply, dim3(((int)ap.size() + 63) / 64), dim3(64), 0, st, L, (const RlApply*)R->apply, (int)ap.size());
-      if (hipStreamSynchronize(st) != hipSuccess) { *err = "alego_loc_relocalize: apply failed"; return ALEGO_ERR_HIP; }
+      if (c.at("apply").wait(st)) return c;
     }
   }
   return 0;
@@ -764,8 +758,7 @@ static void la_world_correction(const float* t_correct, const float* latest6, fl
 // queues the descriptors of the pending (slot, frame) pairs on `st` and counts them as described
 static int la_describe(RlCtx* R, const LmCtx& L, const std::vector<int>& pend, const char* who, hipStream_t st, std::string* err) {
   if (pend.empty()) return 0;
-  if (R->la_pend.reserve(pend.size()) != hipSuccess) { *err = std::string(who) + ": out of device memory"; return ALEGO_ERR_HIP; }
-  if (hipMemcpyAsync(R->la_pend.p, pend.data(), pend.size() * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess) { *err = std::string(who) + ": upload failed"; return ALEGO_ERR_HIP; }
+  if (int r = DevTry(who, err).took(R->la_pend.reserve(pend.size())).up(R->la_pend.p, pend, st)) return r;
   ALEGO_LAUNCH(rl_desc, dim3((unsigned)(pend.size() / 2)), dim3(RL_T), 0, st, L, 2, (const int*)R->la_pend.p, R->la_w, R->la_zoff, R->la_desc, R->la_key, (RlSlot*)nullptr, (uint16_t*)nullptr);
   // (pend is pageable: the copy has left the host buffer when the call returns; the kernel is ordered behind it on `st`)
   for (size_t k = 0; k < pend.size(); k += 2) R->la_described[pend[k]] = std::max(R->la_described[pend[k]], pend[k + 1] + 1);   // only now: the rows are queued
@@ -782,9 +775,8 @@ int loop_app_run(RlCtx* R, LcCtx** lc, const LmCtx& L, const alego_params& P, co
   if (n == 0) return 0;
   // frames stored / dropped of every slot (the caller has drained every stream), then the descriptors of the listed slots' frames [described, nf)
   std::vector<int> stat((size_t)R->la_slots * AS_W);
-  if (hipMemcpyAsync(stat.data(), arc_stat_of(L, 0), stat.size() * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-    *err = "alego_loop_search_appearance: reading the archive failed"; return ALEGO_ERR_HIP;
-  }
+  DevTry t("alego_loop_search_appearance", err, "reading the archive");
+  if (t.down(stat, arc_stat_of(L, 0), st).wait(st)) return t;
   std::vector<int> pend;
   std::vector<RlQuery> qr;
   std::vector<int> qi;
@@ -809,7 +801,7 @@ int loop_app_run(RlCtx* R, LcCtx** lc, const LmCtx& L, const alego_params& P, co
                              [&](const RlQuery* dq, int c, int nmax, uint32_t* bound, int* ne, hipStream_t s2) {
                                ALEGO_LAUNCH(la_elig, dim3(std::max(1, (nmax + RL_T - 1) / RL_T), c), dim3(RL_T), 0, s2, L, dq, (const uint16_t*)R->la_key, gap, jump2, bound, ne);
                              }, nelig.data(), st, err)) return rc;
-  if (hipStreamSynchronize(st) != hipSuccess) { *err = "alego_loop_search_appearance: descriptors failed"; return ALEGO_ERR_HIP; }   // (no query: the descriptors alone)
+  if (t.at("descriptors").wait(st)) return t;   // (no query: the descriptors alone)
   std::vector<unsigned long long> ecand((size_t)n * ALEGO_RELOC_MAX_CAND, RL_CAND_NONE);   // per listed entry, after the max_dist cut
   std::vector<int> ncand((size_t)n, 0);
   bool any = false;
@@ -831,13 +823,9 @@ int loop_app_run(RlCtx* R, LcCtx** lc, const LmCtx& L, const alego_params& P, co
   // the attempts on every candidate, planned on the device from the archive's tables
   std::vector<LcDet> plan((size_t)n * ALEGO_RELOC_MAX_CAND);
   std::vector<float> latest((size_t)n * 6);
-  if (hipMemcpyAsync(R->la_list, slots, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess ||
-      hipMemcpyAsync(R->la_cand, ecand.data(), ecand.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st) != hipSuccess) { *err = "alego_loop_search_appearance: upload failed"; return ALEGO_ERR_HIP; }
+  if (t.at("upload").up(R->la_list, slots, (size_t)n, st).up(R->la_cand, ecand, st)) return t;
   ALEGO_LAUNCH(la_plan, dim3((n * ALEGO_RELOC_MAX_CAND + 63) / 64), dim3(64), 0, st, L, (const int*)R->la_list, (const unsigned long long*)R->la_cand, n, P.lc_search_num, R->la_det, R->la_latest);
-  if (hipMemcpyAsync(plan.data(), R->la_det, plan.size() * sizeof(LcDet), hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipMemcpyAsync(latest.data(), R->la_latest, latest.size() * sizeof(float), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-    *err = "alego_loop_search_appearance: planning failed"; return ALEGO_ERR_HIP;
-  }
+  if (t.at("planning").down(plan, R->la_det, st).down(latest, R->la_latest, st).wait(st)) return t;
   const double fitness_max = o.fitness_max > 0.0 ? o.fitness_max : P.lc_fitness_max;
   return loop_rounds(lc, P, R->la_slots, slots, n, o.verify, loop_archive_gather(L), [&](int i, int v, LcDet* D) {
     if (ncand[i] <= v) return false;
@@ -867,9 +855,8 @@ int map_align_run(RlCtx* R, LcCtx** lc, const LmCtx& L, const alego_params& P, c
   auto finish = [&]() { if (hyp_out && n > 0) std::memcpy(hyp_out, hyp.data(), hyp.size() * sizeof(alego_map_align_hyp)); return 0; };
   if (n == 0) return 0;
   std::vector<int> stat((size_t)R->la_slots * AS_W);
-  if (hipMemcpyAsync(stat.data(), arc_stat_of(L, 0), stat.size() * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-    *err = std::string(who) + ": reading the archive failed"; return ALEGO_ERR_HIP;
-  }
+  DevTry t(who, err, "reading the archive");
+  if (t.down(stat, arc_stat_of(L, 0), st).wait(st)) return t;
   // the entries: one per (pair, query), in pair order
   std::vector<MaEntry> ent;
   std::vector<RlQuery> qr;
@@ -905,7 +892,7 @@ int map_align_run(RlCtx* R, LcCtx** lc, const LmCtx& L, const alego_params& P, c
                              [&](const RlQuery* dq, int c, int nmax, uint32_t* bound, int*, hipStream_t s2) {
                                ALEGO_LAUNCH(ma_mask, dim3(std::max(1, (nmax + RL_T - 1) / RL_T), c), dim3(RL_T), 0, s2, dq, (const uint16_t*)R->la_key, bound);
                              }, nullptr, st, err)) return rc;
-  if (hipStreamSynchronize(st) != hipSuccess) { *err = std::string(who) + ": descriptors failed"; return ALEGO_ERR_HIP; }
+  if (t.at("descriptors").wait(st)) return t;
   auto hyp_of = [&](int e) -> alego_map_align_hyp& { return hyp[(size_t)ent[e].pair * MA_MAX_QUERIES + (e - first[ent[e].pair])]; };
   std::vector<unsigned long long> ecand((size_t)ne * ALEGO_RELOC_MAX_CAND + 1, RL_CAND_NONE);   // per entry, after the max_dist cut
   std::vector<int> ncand((size_t)ne + 1, 0);
@@ -934,13 +921,9 @@ int map_align_run(RlCtx* R, LcCtx** lc, const LmCtx& L, const alego_params& P, c
   }
   std::vector<LcDet> plan(na);
   std::vector<float> spose((size_t)ne * 6);
-  if (hipMemcpyAsync(R->ma_ent.p, ent.data(), (size_t)ne * sizeof(MaEntry), hipMemcpyHostToDevice, st) != hipSuccess ||
-      hipMemcpyAsync(R->ma_cand.p, ecand.data(), na * sizeof(unsigned long long), hipMemcpyHostToDevice, st) != hipSuccess) { *err = std::string(who) + ": upload failed"; return ALEGO_ERR_HIP; }
+  if (t.at("upload").up(R->ma_ent.p, ent, st).up(R->ma_cand.p, ecand.data(), na, st)) return t;   // (ecand has a spare word past na)
   ALEGO_LAUNCH(ma_plan, dim3(((int)na + 63) / 64), dim3(64), 0, st, L, (const MaEntry*)R->ma_ent.p, (const unsigned long long*)R->ma_cand.p, ne, P.lc_search_num, R->ma_det.p, R->ma_spose.p);
-  if (hipMemcpyAsync(plan.data(), R->ma_det.p, na * sizeof(LcDet), hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipMemcpyAsync(spose.data(), R->ma_spose.p, spose.size() * sizeof(float), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-    *err = std::string(who) + ": planning failed"; return ALEGO_ERR_HIP;
-  }
+  if (t.at("planning").down(plan, R->ma_det.p, st).down(spose, R->ma_spose.p, st).wait(st)) return t;
   std::vector<int> eslot((size_t)ne);
   for (int e = 0; e < ne; ++e) eslot[e] = ent[e].dst;
   const double fitness_max = o.fitness_max > 0.0 ? o.fitness_max : P.lc_fitness_max;
@@ -976,12 +959,9 @@ int map_align_run(RlCtx* R, LcCtx** lc, const LmCtx& L, const alego_params& P, c
     M.accepted = H.accepted; M.fitness = H.fitness;
   }
   const double tol_trans = o.tol_trans > 0.0 ? o.tol_trans : ALEGO_ALIGN_TOL_TRANS, tol_rot = o.tol_rot > 0.0 ? o.tol_rot : ALEGO_ALIGN_TOL_ROT;
-  if (hipMemcpyAsync(R->ma_hyp.p, mh.data(), mh.size() * sizeof(MaHyp), hipMemcpyHostToDevice, st) != hipSuccess ||
-      hipMemcpyAsync(R->ma_nq.p, nq.data(), nq.size() * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess) { *err = std::string(who) + ": upload failed"; return ALEGO_ERR_HIP; }
+  if (t.at("upload").up(R->ma_hyp.p, mh, st).up(R->ma_nq.p, nq, st)) return t;
   ALEGO_LAUNCH(ma_consensus, dim3(n), dim3(64), 0, st, (const MaHyp*)R->ma_hyp.p, (const int*)R->ma_nq.p, tol_trans, tol_rot, R->ma_cons.p);
-  if (hipMemcpyAsync(cons.data(), R->ma_cons.p, cons.size() * sizeof(MaCons), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-    *err = std::string(who) + ": the consensus failed"; return ALEGO_ERR_HIP;
-  }
+  if (t.at("the consensus").down(cons, R->ma_cons.p, st).wait(st)) return t;
   const int min_support = o.min_support > 0 ? o.min_support : 2;
   for (int i = 0; i < n; ++i) {
     alego_map_align_result& r = out[i];

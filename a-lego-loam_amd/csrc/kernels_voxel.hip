@@ -21,6 +21,7 @@
 #include "voxel.h"
 #include "wave.h"
 #include "vgrid.h"
+#include "dev_copy.h"
 #include "dev_mem.h"
 #include "prof.h"
 
@@ -511,15 +512,15 @@ int vox_create(VoxCtx* V, const VoxJob* jobs, int njobs, std::string* err) {
   }
   if (total > 0x7fffffffull) { *err = "vox_create: scratch exceeds 2^31 elements"; return -3; }
   V->njobs = njobs; V->total = (unsigned)total;
-  hipError_t e = hipSuccess;
+  static_assert(ALEGO_ERR_HIP == -2, "a failed copy returns this file's -2");
+  DevTry c("vox_create", err);
   DevPool mem;   // owns the blocks until everything has succeeded; then V does (a POD: it is a kernel argument), until vox_destroy
-  auto A = [&](auto** p, size_t count) { if (e == hipSuccess) e = mem.get(p, count, true); };
+  auto A = [&](auto** p, size_t count) { if (c.ok()) c.took(mem.get(p, count, true)); };
   A(&V->jobs, (size_t)njobs); A(&V->bbox, (size_t)njobs * 8);
   A(&V->keys, total); A(&V->pairs_a, total); A(&V->pairs_b, total);
   A(&V->list_small, (size_t)njobs); A(&V->list_big, (size_t)njobs); A(&V->cnt, 6);
   V->grid_small = V->grid_big = njobs;
-  if (e == hipSuccess) e = hipMemcpy(V->jobs, h.data(), sizeof(VoxJob) * njobs, hipMemcpyHostToDevice);
-  if (e != hipSuccess) { std::memset(V, 0, sizeof(*V)); *err = std::string("vox_create: ") + hipGetErrorString(e); return -2; }
+  if (c.up(V->jobs, h)) { std::memset(V, 0, sizeof(*V)); return c; }
   mem.detach();
   return 0;
 }

@@ -1,6 +1,7 @@
 // lm_host.hip — LaserMapping: HBM allocation and kernel sequencing (no numerics here).
 #include "lm_host.h"
 #include "api_gate.h"
+#include "dev_copy.h"
 #include "dev_mem.h"
 
 #include <cstddef>
@@ -192,10 +193,11 @@ LmHost* lm_host_create(const alego_params& P, const DevCtx& d, int n_slots, int 
   // identity quaternions (laserMapping.cpp:56-61)
   std::vector<double> ld(B * LD_COUNT, 0.0);
   for (size_t b = 0; b < B; ++b) { ld[b * LD_COUNT + LD_Q_M2O] = 1.0; ld[b * LD_COUNT + LD_Q_O2L] = 1.0; ld[b * LD_COUNT + LD_Q_M2L] = 1.0; }
-  if (hipMemcpy(L.ld, ld.data(), ld.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) { *err = "lm_host_create: upload failed"; lm_host_destroy(lm); return nullptr; }
+  DevTry c("lm_host_create", err);
+  if (c.up(L.ld, ld)) { lm_host_destroy(lm); return nullptr; }
   std::vector<int> li0(B * LI_COUNT, 0);
   for (size_t b = 0; b < B; ++b) li0[b * LI_COUNT + LI_LATEST] = -1;   // laserMapping.cpp:50
-  if (hipMemcpy(L.li, li0.data(), li0.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) { *err = "lm_host_create: upload failed"; lm_host_destroy(lm); return nullptr; }
+  if (c.up(L.li, li0)) { lm_host_destroy(lm); return nullptr; }
   // VoxelGrid job tables (laserMapping.cpp:37-39,316-319,329-342)
   for (size_t g = 0; g < st.size(); ++g) {
   std::vector<VoxJob> jm, j1, j2, jk;
@@ -391,31 +393,22 @@ int lm_host_process_host(LmHost* lm, const DevCtx& dfull, const alego_point* cor
   d.slot0 = 0; d.n_launch = 1;
   hipStream_t st = lm->st[0];
   if ((n_corner > 0 && !corner_last) || (n_surf > 0 && !surf_last) || (n_outlier > 0 && !outlier) || n_corner < 0 || n_surf < 0 || n_outlier < 0) { *err = "alego_lm_process: null cloud / negative count"; return ALEGO_ERR_ARG; }
-  hipError_t e = hipSuccess;
-  auto up = [&](void* dst, const void* src, size_t bytes) { if (e == hipSuccess && bytes) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st); };
-  up(L.in_corner, corner_last, (size_t)n_corner * 16);
-  up(L.in_surf, surf_last, (size_t)n_surf * 16);
-  up(L.in_outl, outlier, (size_t)n_outlier * 16);
+  DevTry c("alego_lm_process", err, "upload");
+  c.up(L.in_corner, corner_last, (size_t)n_corner, st).up(L.in_surf, surf_last, (size_t)n_surf, st).up(L.in_outl, outlier, (size_t)n_outlier, st);
   const int nin[3] = {n_corner, n_surf, n_outlier};
-  up(L.li + LI_NIN_C, nin, sizeof(nin));
+  c.up(L.li + LI_NIN_C, nin, st);
   double po[7] = {odom->t[0], odom->t[1], odom->t[2], odom->q[0], odom->q[1], odom->q[2], odom->q[3]};
-  up(poses_of(d, 0) + PO_ODOM_T, po, sizeof(po));   // (the single-scan entry points work on slot 0)
+  c.up(poses_of(d, 0) + PO_ODOM_T, po, st);   // (the single-scan entry points work on slot 0)
   const int one = 1;
-  up(scal_of(d, 0) + SC_ODOM_VALID, &one, sizeof(int));
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) { *err = std::string("alego_lm_process: upload failed: ") + hipGetErrorString(e); return ALEGO_ERR_HIP; }
+  if (c.up(scal_of(d, 0) + SC_ODOM_VALID, &one, 1, st).wait(st)) return c;
   clear_run_flags_outside(lm, d);
   if (int r = lm_sequence(lm, d, 0, std::vector<char>(1, 1), err)) return r;
   double out[PO_W], ld[LD_COUNT];
   int li[LI_COUNT];
-  e = hipMemcpyAsync(out, poses_of(d, 0), sizeof(out), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(ld, L.ld, sizeof(ld), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(li, L.li, sizeof(li), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) { *err = std::string("alego_lm_process: kernels failed: ") + hipGetErrorString(e); return ALEGO_ERR_HIP; }
+  if (c.at("kernels").down(out, poses_of(d, 0), st).down(ld, L.ld, st).down(li, L.li, st).wait(st)) return c;
   if (li[LI_OVERFLOW]) {   // reported by the call that caused it, then cleared
     const int zero = 0;
-    (void)hipMemcpy(L.li + LI_OVERFLOW, &zero, sizeof(int), hipMemcpyHostToDevice);
+    (void)dev_up(L.li + LI_OVERFLOW, &zero, 1);
     *err = li[LI_OVERFLOW] == 2 ? "alego_lm_process: launch logic out of sync"
          : li[LI_OVERFLOW] == 8 ? "alego_lm_process: the key-frame window has a point outside the voxel-key range of -2^20 .. 2^20 - 1 leaves per axis (no local map was built)"
                                 : "alego_lm_process: device capacity exceeded (cloud truncated)";
@@ -432,26 +425,25 @@ int lm_host_process_host(LmHost* lm, const DevCtx& dfull, const alego_point* cor
 
 const double* lm_host_stage_odom(LmHost* lm) { return lm->L.stage_odom; }
 void lm_host_get_params(LmHost* lm, int slot, double* p6) {
-  (void)hipMemcpy(p6, lm->L.ld + (size_t)slot * LD_COUNT + LD_PARAMS, 48, hipMemcpyDeviceToHost);
+  (void)dev_down(p6, lm->L.ld + (size_t)slot * LD_COUNT + LD_PARAMS, 6);
 }
 int lm_host_set_params(LmHost* lm, int slot, const double* p6, std::string* err) {
-  if (hipMemcpy(lm->L.ld + (size_t)slot * LD_COUNT + LD_PARAMS, p6, 48, hipMemcpyHostToDevice) != hipSuccess) { *err = "set_lm_params failed"; return ALEGO_ERR_HIP; }
-  return 0;
+  return DevTry("set_lm_params", err).up(lm->L.ld + (size_t)slot * LD_COUNT + LD_PARAMS, p6, 6);
 }
 // LI_OVERFLOW stays set until it has been reported to the host once (the batch path only looks at the end of a run)
 int lm_host_get_flags(LmHost* lm, int slot) {
   int li[LI_COUNT];
-  if (hipMemcpy(li, lm->L.li + (size_t)slot * LI_COUNT, sizeof(li), hipMemcpyDeviceToHost) != hipSuccess) return ALEGO_ERR_HIP;
+  if (dev_down(li, lm->L.li + (size_t)slot * LI_COUNT) != hipSuccess) return ALEGO_ERR_HIP;
   if (li[LI_OVERFLOW]) {
     const int zero = 0;
-    (void)hipMemcpy(lm->L.li + (size_t)slot * LI_COUNT + LI_OVERFLOW, &zero, sizeof(int), hipMemcpyHostToDevice);
+    (void)dev_up(lm->L.li + (size_t)slot * LI_COUNT + LI_OVERFLOW, &zero, 1);
     return ALEGO_ERR_CAPACITY;
   }
   return li[LI_FLAGS];
 }
 void lm_host_get_counts(LmHost* lm, int slot, int* o) {  // o[7]
   int li[LI_COUNT];
-  (void)hipMemcpy(li, lm->L.li + (size_t)slot * LI_COUNT, sizeof(li), hipMemcpyDeviceToHost);
+  (void)dev_down(li, lm->L.li + (size_t)slot * LI_COUNT);
   o[0] = li[LI_KRAW_C]; o[1] = li[LI_KRAW_S]; o[2] = li[LI_KDS_C]; o[3] = li[LI_KDS_S]; o[4] = li[LI_NCUR_C]; o[5] = li[LI_NTOTAL_DS]; o[6] = li[LI_NREBUILD];
 }
 
@@ -459,24 +451,22 @@ void lm_host_get_counts(LmHost* lm, int slot, int* o) {  // o[7]
 static hipStream_t stream_of_slot(LmHost* lm, int slot) { return lm->st[slot / lm->gsize]; }
 int lm_host_keyframe_count(LmHost* lm, int slot) {
   int n = 0;
-  if (hipStreamSynchronize(stream_of_slot(lm, slot)) != hipSuccess) return ALEGO_ERR_HIP;
-  if (hipMemcpy(&n, lm->L.li + (size_t)slot * LI_COUNT + LI_NKF, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return ALEGO_ERR_HIP;
+  if (dev_wait(stream_of_slot(lm, slot)) != hipSuccess || dev_down(&n, lm->L.li + (size_t)slot * LI_COUNT + LI_NKF, 1) != hipSuccess) return ALEGO_ERR_HIP;
   return n;
 }
 // One frame to the host: id, pose and counts always, each cloud the caller gave a buffer for (ALEGO_ERR_CAPACITY when one is too small); n / src: points and device cloud per kind
 static int frame_to_host(const char* what, int id, const float* pose_dev, const int* n, const float4* const* src, alego_keyframe* out, std::string* err) {
   float kp[KF_POSE_W];
-  if (hipMemcpy(kp, pose_dev, sizeof(kp), hipMemcpyDeviceToHost) != hipSuccess) { *err = std::string(what) + ": copy failed"; return ALEGO_ERR_HIP; }
+  DevTry c(what, err, "copy");
+  if (c.down(kp, pose_dev)) return c;
   out->id = id;
   for (int k = 0; k < 6; ++k) out->pose[k] = kp[k];
   out->n_corner = n[KF_CORNER]; out->n_surf = n[KF_SURF]; out->n_outlier = n[KF_OUTL];
   alego_point* const dst[KF_KINDS] = {out->corner, out->surf, out->outlier};   // (KF_CORNER, KF_SURF, KF_OUTL)
   const int cap[KF_KINDS] = {out->corner_cap, out->surf_cap, out->outlier_cap};
   for (int k = 0; k < KF_KINDS; ++k) if (dst[k] && n[k] > cap[k]) { *err = std::string(what) + ": buffer too small"; return ALEGO_ERR_CAPACITY; }
-  hipError_t e = hipSuccess;
-  for (int k = 0; k < KF_KINDS; ++k) if (e == hipSuccess && dst[k] && n[k]) e = hipMemcpy(dst[k], src[k], (size_t)n[k] * 16, hipMemcpyDeviceToHost);
-  if (e != hipSuccess) { *err = std::string(what) + ": " + hipGetErrorString(e); return ALEGO_ERR_HIP; }
-  return 0;
+  for (int k = 0; k < KF_KINDS; ++k) if (dst[k]) c.down(dst[k], src[k], (size_t)n[k]);
+  return c;
 }
 int lm_host_get_keyframe(LmHost* lm, int slot, int kf_id, alego_keyframe* out, std::string* err) {
   const LmCtx& L = lm->L;
@@ -486,19 +476,17 @@ int lm_host_get_keyframe(LmHost* lm, int slot, int kf_id, alego_keyframe* out, s
   if (kf_id < 0 || kf_id >= nkf || kf_id < nkf - L.K) { *err = "get_keyframe: key frame not resident (only the recent_keyframe_num newest are)"; return ALEGO_ERR_ARG; }
   const KfRingRow R = kf_ring_row_at(L, slot, kf_entry(L, kf_id), KF_CORNER);
   int cnt[KF_CNT_W];
-  if (hipMemcpy(cnt, R.cnt, sizeof(cnt), hipMemcpyDeviceToHost) != hipSuccess) { *err = "get_keyframe: copy failed"; return ALEGO_ERR_HIP; }
+  if (int r = DevTry("get_keyframe", err, "copy").down(cnt, R.cnt)) return r;
   const float4* const src[KF_KINDS] = {R.raw, kf_raw_of(L, R.row, KF_SURF), kf_raw_of(L, R.row, KF_OUTL)};
   return frame_to_host("get_keyframe", kf_id, R.pose, cnt, src, out, err);
 }
 // a frame of the host into ring row R: key pose, counts, the three clouds
-static hipError_t frame_to_row(const LmCtx& L, const KfRingRow& R, const alego_kf_in& f) {
+static void frame_to_row(const LmCtx& L, const KfRingRow& R, const alego_kf_in& f, DevTry* c) {
   const float kp[KF_POSE_W] = {f.pose[0], f.pose[1], f.pose[2], f.pose[3], f.pose[4], f.pose[5], 0.f, 0.f};
   const int cnt[KF_CNT_W] = {f.n_corner, f.n_surf, f.n_outlier, 0};   // (KF_CORNER, KF_SURF, KF_OUTL)
   const alego_point* const src[KF_KINDS] = {f.corner, f.surf, f.outlier};
-  hipError_t e = hipMemcpy(R.pose, kp, sizeof(kp), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(R.cnt, cnt, sizeof(cnt), hipMemcpyHostToDevice);
-  for (int k = 0; k < KF_KINDS; ++k) if (e == hipSuccess && cnt[k]) e = hipMemcpy(kf_raw_of(L, R.row, k), src[k], (size_t)cnt[k] * 16, hipMemcpyHostToDevice);
-  return e;
+  c->up(R.pose, kp).up(R.cnt, cnt);
+  for (int k = 0; k < KF_KINDS; ++k) c->up(kf_raw_of(L, R.row, k), src[k], (size_t)cnt[k]);
 }
 static int retransform(LmHost* lm, const DevCtx& dfull, int slot, int ring, std::string* err) {
   DevCtx d = dfull;
@@ -509,45 +497,45 @@ static int retransform(LmHost* lm, const DevCtx& dfull, int slot, int ring, std:
   int* li = lm->L.li + (size_t)slot * LI_COUNT;
   // a key frame saved by the last mapping frame may still wait in kf_tmp_* for its sort: flush it before the buffer is reused
   if (int r = vox_run(lm->vk[g], st, err)) return r;
-  (void)hipMemcpyAsync(li + LI_KF_PENDING, &zero, sizeof(int), hipMemcpyHostToDevice, st);
+  (void)dev_up(li + LI_KF_PENDING, &zero, 1, st);
   launch_lm_retransform(d, lm->L, ring, st);
   // the row's clouds were (re)written outside the regular sequence: sort it into the ring now, and the next map update rebuilds its voxel lists
   std::string e;
   (void)vox_run(lm->vk[g], st, &e);
-  (void)hipMemcpyAsync(li + LI_KF_PENDING, &zero, sizeof(int), hipMemcpyHostToDevice, st);
-  (void)hipMemcpyAsync(li + LI_UVALID, &zero, sizeof(int), hipMemcpyHostToDevice, st);
-  if (hipStreamSynchronize(st) != hipSuccess) { *err = "key-frame transform failed"; return ALEGO_ERR_HIP; }
-  return 0;
+  (void)dev_up(li + LI_KF_PENDING, &zero, 1, st);
+  (void)dev_up(li + LI_UVALID, &zero, 1, st);
+  return DevTry("retransform", err, "key-frame transform").wait(st);
 }
 int lm_host_set_keypose(LmHost* lm, const DevCtx& dfull, int slot, int kf_id, const float* pose6, std::string* err) {
   const LmCtx& L = lm->L;
   const int nkf = lm_host_keyframe_count(lm, slot);
   if (nkf < 0) return nkf;
   if (kf_id < 0 || kf_id >= nkf || kf_id < nkf - L.K) { *err = "set_keypose: key frame not resident"; return ALEGO_ERR_ARG; }
-  if (hipMemcpy(kf_pose_of(L, kf_row(L, slot, kf_id)), pose6, 6 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { *err = "set_keypose: copy failed"; return ALEGO_ERR_HIP; }
+  DevTry c("set_keypose", err, "copy");
+  if (c.up(kf_pose_of(L, kf_row(L, slot, kf_id)), pose6, 6)) return c;
   if (L.arc_frames_cap > 0) {   // the archived copy of the frame (alego_map_enable) follows
     int stat[AS_W];
-    if (hipMemcpy(stat, arc_stat_of(L, slot), sizeof(stat), hipMemcpyDeviceToHost) != hipSuccess) { *err = "set_keypose: copy failed"; return ALEGO_ERR_HIP; }
-    if (kf_id < stat[AS_FRAMES] && hipMemcpy(arc_pose_of(L, slot, kf_id), pose6, 6 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { *err = "set_keypose: copy failed"; return ALEGO_ERR_HIP; }
+    if (c.down(stat, arc_stat_of(L, slot))) return c;
+    if (kf_id < stat[AS_FRAMES] && c.up(arc_pose_of(L, slot, kf_id), pose6, 6)) return c;
   }
   return retransform(lm, dfull, slot, kf_entry(L, kf_id), err);
 }
 int lm_host_reset_window(LmHost* lm, int slot, std::string* err) {
   int* li = lm->L.li + (size_t)slot * LI_COUNT;
-  bool ok = hipStreamSynchronize(stream_of_slot(lm, slot)) == hipSuccess;
-  kf_reset_window([&](int w, int v) { ok = ok && hipMemcpy(li + w, &v, sizeof(int), hipMemcpyHostToDevice) == hipSuccess; });
-  if (!ok) { *err = "reset_window failed"; return ALEGO_ERR_HIP; }
-  return 0;
+  DevTry c("reset_window", err);
+  c.wait(stream_of_slot(lm, slot));
+  kf_reset_window([&](int w, int v) { c.up(li + w, &v, 1); });
+  return c;
 }
 int lm_host_apply_correction(LmHost* lm, const DevCtx& dfull, int slot, const double* rc12, std::string* err) {
   DevPool tmp;
   double* dev = nullptr;
   hipStream_t st = stream_of_slot(lm, slot);
   if (tmp.get(&dev, 12, false) != hipSuccess) { *err = "apply_correction: allocation failed"; return ALEGO_ERR_HIP; }
-  hipError_t e = hipMemcpy(dev, rc12, 12 * sizeof(double), hipMemcpyHostToDevice);
-  if (e == hipSuccess) { launch_lm_apply_correction(dfull, lm->L, slot, dev, st); e = hipStreamSynchronize(st); }
-  if (e != hipSuccess) { *err = std::string("apply_correction: ") + hipGetErrorString(e); return ALEGO_ERR_HIP; }
-  return 0;
+  DevTry c("apply_correction", err);
+  if (c.up(dev, rc12, 12)) return c;
+  launch_lm_apply_correction(dfull, lm->L, slot, dev, st);
+  return c.wait(st);
 }
 int lm_host_add_keyframe(LmHost* lm, const DevCtx& dfull, int slot, const float* pose6, const alego_point* corner, int nc, const alego_point* surf, int ns,
                          const alego_point* outlier, int no, std::string* err) {
@@ -558,16 +546,17 @@ int lm_host_add_keyframe(LmHost* lm, const DevCtx& dfull, int slot, const float*
   const int nkf = lm_host_keyframe_count(lm, slot);
   if (nkf < 0) return nkf;
   int* li = L.li + (size_t)slot * LI_COUNT;
+  DevTry c("add_keyframe", err);
   {
     // A full window advances by ONE frame per mapping frame (pop the oldest, push the newest, laserMapping.cpp:224-237): it keeps its
     // K - 1 other frames however many frames were added in between, and falls behind the newest frames by one for every extra frame.
     // The device holds the K + 1 newest frames, so the window may lag by one: the frame inserted here (id nkf) is refused when the
     // oldest frame the next window still needs, rec[1], would no longer be among the K + 1 newest, i.e. rec[1] < nkf - K.
     int rec_cnt = 0;
-    if (hipMemcpy(&rec_cnt, li + LI_REC_CNT, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { *err = "add_keyframe: device read failed"; return ALEGO_ERR_HIP; }
+    if (c.down(&rec_cnt, li + LI_REC_CNT, 1)) return c;
     if (rec_cnt >= L.K && L.K >= 2) {
       int rec1 = 0;
-      if (hipMemcpy(&rec1, L.rec + (size_t)slot * L.K + 1, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { *err = "add_keyframe: device read failed"; return ALEGO_ERR_HIP; }
+      if (c.down(&rec1, L.rec + (size_t)slot * L.K + 1, 1)) return c;
       if (rec1 < nkf - L.K) {
         *err = "add_keyframe: the full local-map window already lags one frame behind the newest key frames (it advances by one frame per mapping frame); "
                "insert at most one extra key frame per window length, or call alego_lm_reset_window first (the window is then rebuilt from the newest frames)";
@@ -576,18 +565,16 @@ int lm_host_add_keyframe(LmHost* lm, const DevCtx& dfull, int slot, const float*
     }
   }
   const int nkf1 = nkf + 1, one = 1;
-  hipError_t e = frame_to_row(L, kf_ring_row_at(L, slot, kf_entry(L, nkf), KF_CORNER), f);
-  if (e == hipSuccess) e = hipMemcpy(li + LI_NKF, &nkf1, sizeof(int), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(li + LI_DIRTY, &one, sizeof(int), hipMemcpyHostToDevice);
-  if (e != hipSuccess) { *err = std::string("add_keyframe: ") + hipGetErrorString(e); return ALEGO_ERR_HIP; }
+  frame_to_row(L, kf_ring_row_at(L, slot, kf_entry(L, nkf), KF_CORNER), f, &c);
+  if (c.up(li + LI_NKF, &nkf1, 1).up(li + LI_DIRTY, &one, 1)) return c;
   if (int r = retransform(lm, dfull, slot, kf_entry(L, nkf), err)) return r;
   if (L.arc_frames_cap > 0) {   // the archive (alego_map_enable) takes the inserted frame like a saved one
     DevCtx d = dfull;
     d.slot0 = slot; d.n_launch = 1;
     launch_map_archive(d, L, 1, stream_of_slot(lm, slot));
-    if (hipStreamSynchronize(stream_of_slot(lm, slot)) != hipSuccess) { *err = "add_keyframe: archive append failed"; return ALEGO_ERR_HIP; }
+    c.at("archive append").wait(stream_of_slot(lm, slot));
   }
-  return 0;
+  return c;
 }
 
 // ---- one registration sharded over the ranks of a communicator (alego_dist_*) ----
@@ -628,18 +615,18 @@ int lm_host_dist_probe(LmHost* lm, int iters, double* usec, std::string* err) {
   (void)hipEventRecord(e0, st);
   for (int i = 0; i < iters && !rc; ++i) rc = lm_allreduce(lm, buf, 32, st);
   (void)hipEventRecord(e1, st);
-  const hipError_t se = hipStreamSynchronize(st);
+  const hipError_t se = dev_wait(st);
   float ms = 0.f;
   if (!rc && se == hipSuccess) (void)hipEventElapsedTime(&ms, e0, e1);
   (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); tmp.clear();
   if (rc) { *err = lm->dist_err; return rc; }
-  if (se != hipSuccess) { *err = std::string("alego_dist_allreduce_probe: ") + hipGetErrorString(se); return ALEGO_ERR_HIP; }
+  if (int r = DevTry("alego_dist_allreduce_probe", err).took(se, "a stream")) return r;
   *usec = 1e3 * (double)ms / iters;
   return 0;
 }
 int lm_host_dist_shutdown(LmHost* lm) {
   if (!lm->comm) return 0;
-  for (hipStream_t s : lm->st) (void)hipStreamSynchronize(s);
+  (void)dev_wait(lm->st);
   (void)ncclCommDestroy(lm->comm);
   lm->comm = nullptr; lm->L.shard_rank = 0; lm->L.shard_world = 0;
   return 0;
@@ -657,17 +644,17 @@ int lm_host_debug_slice(LmHost* lm, int rank, int world, std::string* err) {
 int lm_host_set_map_merge(LmHost* lm, int on, std::string* err) {
   if (!on && !lm->fallback_ok) { *err = "ALEGO_MAP_MERGE=0 needs the handle to be created with it (more than 64 slots)"; return ALEGO_ERR_ARG; }
   if (!on && lm->L.loc_on) { *err = "ALEGO_MAP_MERGE=0: a localising handle builds its local maps from the map store's sorted runs only"; return ALEGO_ERR_ARG; }
-  for (hipStream_t s : lm->st) (void)hipStreamSynchronize(s);
+  (void)dev_wait(lm->st);
   const int zero = 0;
-  for (int b = 0; b < lm->n_slots; ++b)
-    if (hipMemcpy(lm->L.li + (size_t)b * LI_COUNT + LI_UVALID, &zero, sizeof(int), hipMemcpyHostToDevice) != hipSuccess) { *err = "set_map_merge: copy failed"; return ALEGO_ERR_HIP; }
-  return 0;
+  DevTry c("set_map_merge", err, "copy");
+  for (int b = 0; b < lm->n_slots; ++b) c.up(lm->L.li + (size_t)b * LI_COUNT + LI_UVALID, &zero, 1);
+  return c;
 }
 
 int lm_host_debug_get(LmHost* lm, int slot, const char* name, void* out, int cap_bytes, int* count, int* dtype, std::string* err) {
   const LmCtx& L = lm->L;
   int li[LI_COUNT];
-  (void)hipMemcpy(li, L.li + (size_t)slot * LI_COUNT, sizeof(li), hipMemcpyDeviceToHost);
+  (void)dev_down(li, L.li + (size_t)slot * LI_COUNT);
   const std::string s(name);
   const void* src = nullptr;
   size_t n = 0;
@@ -693,7 +680,7 @@ int lm_host_debug_get(LmHost* lm, int slot, const char* name, void* out, int cap
     if (nkf <= 0) { *count = 0; *dtype = 0; return 0; }
     const int m = s == "lm_kf_corner_map" ? 0 : 1;
     int n = 0;
-    (void)hipMemcpy(&n, L.kfs_n + kf_run_at(L, slot, m, kf_entry(L, nkf - 1)), sizeof(int), hipMemcpyDeviceToHost);
+    (void)dev_down(&n, L.kfs_n + kf_run_at(L, slot, m, kf_entry(L, nkf - 1)), 1);
     if (m == 0) set(L.kfs_c + kf_row(L, slot, nkf - 1) * L.kf_cap_c, (size_t)n * 4, 0);
     else set(L.kfs_s + kf_row(L, slot, nkf - 1) * L.total_cap, (size_t)n * 4, 0);
   }
@@ -706,8 +693,8 @@ int lm_host_debug_get(LmHost* lm, int slot, const char* name, void* out, int cap
     const int f = atoi(s.c_str() + s.find(':') + 1);
     if (!L.loc_on || f < 0 || f >= L.loc_n) { *err = std::string("debug_get: ") + name + ": no such frame in a map store"; return ALEGO_ERR_ARG; }
     int cnt[KF_CNT_W], run[2];
-    for (int m = 0; m < 2; ++m) (void)hipMemcpy(run + m, L.kfs_n + kf_run_at(L, 0, m, f), sizeof(int), hipMemcpyDeviceToHost);
-    (void)hipMemcpy(cnt, kf_cnt_of(L, kf_row_at(L, 0, f)), sizeof(cnt), hipMemcpyDeviceToHost);
+    for (int m = 0; m < 2; ++m) (void)dev_down(run + m, L.kfs_n + kf_run_at(L, 0, m, f), 1);
+    (void)dev_down(cnt, kf_cnt_of(L, kf_row_at(L, 0, f)));
     const KfClouds C = kf_clouds_row_at(L, 0, f, cnt);
     if (w == "ls_corner") set(L.kfs_c + kf_row_at(L, 0, f) * L.kf_cap_c, (size_t)std::min(std::max(run[0], 0), L.kf_cap_c) * 4, 0);
     else if (w == "ls_surf") set(L.kfs_s + kf_row_at(L, 0, f) * L.total_cap, (size_t)std::min(std::max(run[1], 0), L.total_cap) * 4, 0);
@@ -725,7 +712,7 @@ int lm_host_debug_get(LmHost* lm, int slot, const char* name, void* out, int cap
   }
   else { *err = std::string("debug_get: unknown name ") + name; return ALEGO_ERR_ARG; }
   if ((size_t)cap_bytes < n * esz) { *err = "debug_get: buffer too small"; return ALEGO_ERR_CAPACITY; }
-  if (n && hipMemcpy(out, src, n * esz, hipMemcpyDeviceToHost) != hipSuccess) { *err = "debug_get: copy failed"; return ALEGO_ERR_HIP; }
+  if (int r = DevTry("debug_get", err).took(dev_down_bytes(out, src, n * esz), "copy")) return r;
   *count = (int)n; *dtype = dt;
   return 0;
 }
@@ -733,7 +720,7 @@ int lm_host_debug_get(LmHost* lm, int slot, const char* name, void* out, int cap
 // 0 while no slot has saved a key frame (scans too: or run a mapping frame), else ALEGO_ERR_ARG: what is enabled on a handle has to exist before the first one
 static int rings_empty(LmHost* lm, const char* what, bool scans_too, std::string* err) {
   std::vector<int> li((size_t)lm->n_slots * LI_COUNT);
-  if (hipMemcpy(li.data(), lm->L.li, li.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { *err = std::string(what) + ": device read failed"; return ALEGO_ERR_HIP; }
+  if (int r = DevTry(what, err).down(li, lm->L.li)) return r;
   for (int s = 0; s < lm->n_slots; ++s)
     if (li[(size_t)s * LI_COUNT + LI_NKF] != 0 || (scans_too && li[(size_t)s * LI_COUNT + LI_FRAME] != 0)) {
       *err = std::string(what) + (scans_too ? ": call it before the first scan / key frame of any slot" : ": call it before the first key frame is saved");
@@ -761,10 +748,7 @@ int lm_host_map_enable(LmHost* lm, int max_frames, int max_points, std::string* 
 }
 static int map_stat(LmHost* lm, int slot, int* st4 /* [AS_W] */, std::string* err) {
   if (lm->L.arc_frames_cap <= 0) { *err = "the key-frame archive is off (alego_map_enable)"; return ALEGO_ERR_ARG; }
-  if (hipStreamSynchronize(stream_of_slot(lm, slot)) != hipSuccess || hipMemcpy(st4, arc_stat_of(lm->L, slot), AS_W * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) {
-    *err = "map: device read failed"; return ALEGO_ERR_HIP;
-  }
-  return 0;
+  return DevTry("map", err, "device read").wait(stream_of_slot(lm, slot)).down(st4, arc_stat_of(lm->L, slot), AS_W);
 }
 int lm_host_map_status(LmHost* lm, int slot, int* out4, std::string* err) {
   int st[AS_W];
@@ -788,13 +772,13 @@ int lm_host_map_stamps(LmHost* lm, int slot, int first, int n, double* stamps, i
   if (first < 0 || n < 0 || first > st[AS_FRAMES] || n > st[AS_FRAMES] - first || (n > 0 && !stamps)) { *err = "map_stamps: range beyond the archived frames"; return ALEGO_ERR_ARG; }
   if (n == 0) return 0;
   double* dev = lm->L.arc_stamp + arc_row(lm->L, slot, first);
-  if (hipMemcpy(write ? (void*)dev : (void*)stamps, write ? (const void*)stamps : (const void*)dev, (size_t)n * sizeof(double),
-                write ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost) != hipSuccess) { *err = "map_stamps: copy failed"; return ALEGO_ERR_HIP; }
-  return 0;
+  DevTry c("map_stamps", err, "copy");
+  if (write) c.up(dev, stamps, (size_t)n); else c.down(stamps, dev, (size_t)n);
+  return c;
 }
 int lm_host_map_mark_stamped(LmHost* lm, int slot, hipStream_t st) {
   static const int one = 1;
-  return lm->L.arc_frames_cap > 0 && hipMemcpyAsync(lm->L.arc_stamped + slot, &one, sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess ? ALEGO_ERR_HIP : 0;
+  return lm->L.arc_frames_cap > 0 && dev_up(lm->L.arc_stamped + slot, &one, 1, st) != hipSuccess ? ALEGO_ERR_HIP : 0;
 }
 const LmCtx* lm_host_ctx(LmHost* lm) { return &lm->L; }
 
@@ -811,7 +795,7 @@ int loc_handle_ready(LmHost* lm, const DevCtx& dfull, const std::string& what, s
   if (lm->comm) { *err = what + ": not available on a handle with a sharded registration (alego_dist_init)"; return ALEGO_ERR_ARG; }
   if (!dfull.opt_map_merge) { *err = what + ": ALEGO_MAP_MERGE=0 (concat + radix VoxelGrid) is a mapping-only path"; return ALEGO_ERR_ARG; }
   for (long f : lm->frames) if (f != 0) { *err = what + ": call it before the first scan of any slot"; return ALEGO_ERR_ARG; }
-  for (hipStream_t s : lm->st) if (hipStreamSynchronize(s) != hipSuccess) { *err = what + ": a stream failed"; return ALEGO_ERR_HIP; }
+  if (int r = DevTry(what, err).wait(lm->st)) return r;
   return rings_empty(lm, what.c_str(), true, err);
 }
 // a frame of nc / ns / no points against the key-frame capacities of the handle
@@ -836,7 +820,7 @@ int loc_store_view(LmHost* lm, LmCtx* T, int rows, int n, double radius, const s
   return 0;
 }
 int loc_store_undo(LmHost* lm, LmCtx& T, int rc) {
-  (void)hipStreamSynchronize(lm->st[0]);
+  (void)dev_wait(lm->st[0]);
   ring_release(lm, T);
   return rc;
 }
@@ -866,7 +850,7 @@ int lm_host_loc_enable(LmHost* lm, const DevCtx& dfull, const alego_kf_in* frame
   if (int r = loc_store_view(lm, &T, n, n, radius, what, err)) return r;
   int* li0 = T.li;
   auto undo = [&](int rc) {
-    (void)hipStreamSynchronize(lm->st[0]);
+    (void)dev_wait(lm->st[0]);
     (void)hipMemset(li0 + LI_KF_PENDING, 0, 8 * sizeof(int));
     (void)hipMemset(li0 + LI_OVERFLOW, 0, sizeof(int));
     if (lm->vloc_made) { vox_destroy(&lm->vloc); lm->vloc_made = false; }
@@ -882,20 +866,18 @@ int lm_host_loc_enable(LmHost* lm, const DevCtx& dfull, const alego_kf_in* frame
   hipStream_t st = lm->st[0];
   DevCtx d = dfull;
   d.slot0 = 0; d.n_launch = 1;
-  hipError_t e = hipSuccess;
-  for (int i = 0; i < n && e == hipSuccess; ++i) {
-    e = frame_to_row(T, kf_ring_row_at(T, 0, kf_entry(T, i), KF_CORNER), frames[i]);
-    if (e != hipSuccess) break;
+  DevTry c(what, err, "building the map store");
+  for (int i = 0; i < n; ++i) {
+    frame_to_row(T, kf_ring_row_at(T, 0, kf_entry(T, i), KF_CORNER), frames[i], &c);
+    if (!c.ok()) break;
     launch_lm_retransform(d, T, kf_entry(T, i), st);   // row i of the store -> kf_tmp_* of slot 0
     if (int r = vox_run(lm->vloc, st, err)) return undo(r);
   }
   // slot 0 lent its key-frame staging words (LI_KF_PENDING .. LI_SORT_N1) to the build: it leaves as fresh as every other slot
   static_assert(LI_SORT_N1 - LI_KF_PENDING == 7 && LI_REBUILD_FB > LI_KF_PENDING && LI_MAP_PASS < LI_SORT_N1, "the words in between are zero on a fresh slot too");
-  if (e == hipSuccess) e = hipMemsetAsync(li0 + LI_KF_PENDING, 0, 8 * sizeof(int), st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) { *err = std::string("alego_loc_enable: building the map store failed: ") + hipGetErrorString(e); return undo(ALEGO_ERR_HIP); }
+  if (c.ok()) c.took(hipMemsetAsync(li0 + LI_KF_PENDING, 0, 8 * sizeof(int), st), "clearing");
   int ovf = 0;
-  if (hipMemcpy(&ovf, li0 + LI_OVERFLOW, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { *err = "alego_loc_enable: device read failed"; return undo(ALEGO_ERR_HIP); }
+  if (c.wait(st).at("device read").down(&ovf, li0 + LI_OVERFLOW, 1)) return undo(c);
   if (ovf) { *err = "alego_loc_enable: a frame was truncated while it was sorted"; return undo(ALEGO_ERR_CAPACITY); }
   loc_store_commit(lm, T);
   return 0;
@@ -916,10 +898,11 @@ int loc_chunk_frames(const LmHost* lm, int n) {
 // the archive of `slot` of the source as it is now (its streams have been synchronised): frames stored, their arc_tab rows on the host
 int loc_src_read(LmHost* src, int slot, const std::string& what, std::vector<int>* tab, std::string* err) {
   int st[AS_W];
-  if (hipMemcpy(st, arc_stat_of(src->L, slot), sizeof(st), hipMemcpyDeviceToHost) != hipSuccess) { *err = what + ": device read failed"; return ALEGO_ERR_HIP; }
+  DevTry c(what, err);
+  if (c.down(st, arc_stat_of(src->L, slot))) return c;
   const int n = std::max(0, std::min(st[AS_FRAMES], src->L.arc_frames_cap));   // (a source that dropped frames: the stored prefix is handed over)
   tab->assign((size_t)n * AT_W, 0);
-  if (n > 0 && hipMemcpy(tab->data(), arc_tab_of(src->L, slot, 0), tab->size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { *err = what + ": device read failed"; return ALEGO_ERR_HIP; }
+  if (c.down(*tab, arc_tab_of(src->L, slot, 0))) return c;
   return n;
 }
 int loc_src_ok(LmHost* lm, LmHost* src, int slot, const std::string& what, std::string* err) {
@@ -931,7 +914,7 @@ int loc_src_ok(LmHost* lm, LmHost* src, int slot, const std::string& what, std::
 // Frames 0 .. n - 1 of S into rows 0 .. n - 1 of the store T names, in chunks: loc_fill, then one VoxelGrid round of the chunk's 2 C sort jobs, one workgroup
 // per job.  Everything is queued on st and finished when this returns; tab: the host copy of the frames' arc_tab rows.
 int loc_store_fill(LmHost* lm, const LmCtx& T, const KfArcSrc& S, const std::vector<int>& tab, int n, hipStream_t st, const std::string& what, std::string* err) {
-  if (n == 0) return hipStreamSynchronize(st) == hipSuccess ? 0 : ALEGO_ERR_HIP;
+  if (n == 0) return dev_wait(st) == hipSuccess ? 0 : ALEGO_ERR_HIP;
   const int C = loc_chunk_frames(lm, n);
   DevPool tmp;
   float4 *stage_c = nullptr, *stage_s = nullptr;
@@ -955,9 +938,8 @@ int loc_store_fill(LmHost* lm, const LmCtx& T, const KfArcSrc& S, const std::vec
     rc = vox_run(V, st, err);
   }
   int o = 0;
-  const hipError_t e = hipStreamSynchronize(st);
-  if (!rc && e != hipSuccess) { *err = what + ": building the map store failed: " + hipGetErrorString(e); rc = ALEGO_ERR_HIP; }
-  if (!rc && hipMemcpy(&o, ovf, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { *err = what + ": device read failed"; rc = ALEGO_ERR_HIP; }
+  const hipError_t e = dev_wait(st);
+  if (!rc) rc = DevTry(what, err).took(e, "building the map store").down(&o, ovf, 1);
   if (!rc && o) { *err = what + ": a frame was truncated while it was sorted"; rc = ALEGO_ERR_CAPACITY; }
   vox_destroy(&V);
   tmp.clear();
@@ -994,7 +976,7 @@ int lm_host_loc_update_from_map(LmHost* lm, LmHost* src, int slot, bool* rewritt
   LmCtx& L = lm->L;
   if (!L.loc_on) { *err = what + ": the handle does not localise (alego_loc_enable / alego_loc_enable_from_map)"; return ALEGO_ERR_ARG; }
   if (int r = loc_src_ok(lm, src, slot, what, err)) return r;
-  for (hipStream_t s : lm->st) if (hipStreamSynchronize(s) != hipSuccess) { *err = what + ": a stream failed"; return ALEGO_ERR_HIP; }
+  if (int r = DevTry(what, err).wait(lm->st)) return r;
   std::vector<int> tab;
   const int n = loc_src_read(src, slot, what, &tab, err);
   if (n < 0) return n;
@@ -1014,7 +996,8 @@ int lm_host_loc_update_from_map(LmHost* lm, LmHost* src, int slot, bool* rewritt
   if (!rc) rc = loc_store_fill(lm, L, kf_arc_src(src->L, slot), tab, n, st, what, err);
   L.loc_n = rc ? 0 : n;   // a failure in the middle leaves the store empty: every slot is off the map and dead-reckons
   launch_loc_reset_windows(L, lm->n_slots, st);
-  if (hipStreamSynchronize(st) != hipSuccess && !rc) { *err = what + ": the window reset failed"; L.loc_n = 0; rc = ALEGO_ERR_HIP; }
+  const hipError_t we = dev_wait(st);
+  if (!rc && (rc = DevTry(what, err).took(we, "the window reset"))) L.loc_n = 0;
   return rc;
 }
 int lm_host_set_loc_chunk(LmHost* lm, int frames) { lm->loc_chunk = std::max(1, frames); return 0; }
@@ -1022,7 +1005,7 @@ int lm_host_loc_status(LmHost* lm, int slot, int* out4, std::string* err) {
   const LmCtx& L = lm->L;
   if (!L.loc_on) { *err = "alego_loc_status: the handle does not localise (alego_loc_enable)"; return ALEGO_ERR_ARG; }
   int li[LI_COUNT];
-  if (hipStreamSynchronize(stream_of_slot(lm, slot)) != hipSuccess || hipMemcpy(li, L.li + (size_t)slot * LI_COUNT, sizeof(li), hipMemcpyDeviceToHost) != hipSuccess) { *err = "alego_loc_status: device read failed"; return ALEGO_ERR_HIP; }
+  if (int r = DevTry("alego_loc_status", err, "device read").wait(stream_of_slot(lm, slot)).down(li, L.li + (size_t)slot * LI_COUNT)) return r;
   out4[0] = L.loc_n; out4[1] = li[LI_REC_CNT]; out4[2] = li[LI_NREBUILD]; out4[3] = li[LI_OPTIMIZED];
   return 0;
 }
@@ -1063,9 +1046,8 @@ template <class Rec> static int lm_records_get(LmHost* lm, const char* what, con
   if (int r = gate_slot_list(what, slots, n, lm->n_slots, true, err)) return r;
   if (n == 0) return 0;
   const int lo = *std::min_element(slots, slots + n), hi = *std::max_element(slots, slots + n);
-  for (hipStream_t s : lm->st) if (hipStreamSynchronize(s) != hipSuccess) { *err = std::string(what) + ": a stream failed"; return ALEGO_ERR_HIP; }
   std::vector<Rec> tmp((size_t)(hi - lo + 1));
-  if (hipMemcpy(tmp.data(), dev_records + lo, tmp.size() * sizeof(Rec), hipMemcpyDeviceToHost) != hipSuccess) { *err = std::string(what) + ": device read failed"; return ALEGO_ERR_HIP; }
+  if (int r = DevTry(what, err).wait(lm->st).down(tmp, dev_records + lo)) return r;
   for (int i = 0; i < n; ++i) out[i] = tmp[(size_t)(slots[i] - lo)];
   return 0;
 }
@@ -1087,7 +1069,7 @@ int lm_host_regcov_enable(LmHost* lm, const alego_regcov_opts* opts, std::string
   LmCtx T = L;
   double* dopt = nullptr;
   if (!A(lm, &T.rc_rec, (size_t)lm->n_slots, err) || !A(lm, &dopt, (size_t)RC_OPT_W, err)) return ALEGO_ERR_HIP;
-  if (hipMemcpy(dopt, opt, sizeof(opt), hipMemcpyHostToDevice) != hipSuccess) { *err = "alego_regcov_enable: copy failed"; return ALEGO_ERR_HIP; }
+  if (int r = DevTry("alego_regcov_enable", err, "copy").up(dopt, opt)) return r;
   T.rc_opt = dopt; T.rc_graph = graph ? 1 : 0;
   L = T;
   std::memcpy(lm->rc_opt, opt, sizeof(opt));
@@ -1136,15 +1118,15 @@ template <class F> static int resort_rounds(LmHost* lm, const std::vector<int>& 
       launch_pg_sorted(L, mask_dev, s0, n, 0, st);
     }
   }
-  for (hipStream_t s : lm->st) if (hipStreamSynchronize(s) != hipSuccess) { *err = std::string(what) + ": key-frame transform failed"; return ALEGO_ERR_HIP; }
-  return 0;
+  return DevTry(what, err, "key-frame transform").wait(lm->st);
 }
 
 int lm_host_graph_apply(LmHost* lm, const std::vector<int>& apply, const int* apply_dev, int n_poses_max, std::string* err) {
   const LmCtx& L = lm->L;
-  for (hipStream_t s : lm->st) if (hipStreamSynchronize(s) != hipSuccess) { *err = "graph apply: a stream failed"; return ALEGO_ERR_HIP; }
+  DevTry c("graph apply", err);
+  if (c.wait(lm->st)) return c;
   launch_pg_apply(L, apply_dev, lm->n_slots, lm->st[0]);
-  if (hipStreamSynchronize(lm->st[0]) != hipSuccess) { *err = "graph apply: pose write failed"; return ALEGO_ERR_HIP; }
+  if (c.at("pose write").wait(lm->st[0])) return c;
   // every resident frame of every applied slot
   return resort_rounds(lm, apply, apply_dev, std::min(L.K, n_poses_max), 1,
                        [&](int s0, int n, int j, hipStream_t st) { launch_pg_retransform(L, apply_dev, s0, n, j, st); }, "graph apply", err);
@@ -1155,20 +1137,19 @@ namespace {
 // the per-slot words `tail` (frames to re-sort, newest last) on the device, then the rounds
 int merge_rounds(LmHost* lm, const std::vector<int>& tail, const char* what, std::string* err) {
   const LmCtx& L = lm->L;
-  if (lm->mg_tail.reserve(tail.size()) != hipSuccess || hipMemcpy(lm->mg_tail.p, tail.data(), tail.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
-    *err = std::string(what) + ": upload failed"; return ALEGO_ERR_HIP;
-  }
+  if (int r = DevTry(what, err, "upload").took(lm->mg_tail.reserve(tail.size())).up(lm->mg_tail.p, tail)) return r;
   const int* dev = lm->mg_tail.p;
   return resort_rounds(lm, tail, dev, *std::max_element(tail.begin(), tail.end()), 0,
                        [&](int s0, int n, int j, hipStream_t st) { launch_mg_retransform(L, dev, s0, n, j, st); }, what, err);
 }
 int read_stats(LmHost* lm, std::vector<int>* arc, std::vector<int>* pg, const char* what, std::string* err) {
   const LmCtx& L = lm->L;
-  for (hipStream_t s : lm->st) if (hipStreamSynchronize(s) != hipSuccess) { *err = std::string(what) + ": a stream failed"; return ALEGO_ERR_HIP; }
+  DevTry c(what, err);
+  if (c.wait(lm->st)) return c;
   arc->assign((size_t)lm->n_slots * AS_W, 0); pg->assign((size_t)lm->n_slots * PS_W, 0);
-  if (hipMemcpy(arc->data(), L.arc_stat, arc->size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
-      (L.pg_loops_cap > 0 && hipMemcpy(pg->data(), L.pg_stat, pg->size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)) { *err = std::string(what) + ": device read failed"; return ALEGO_ERR_HIP; }
-  return 0;
+  c.down(*arc, L.arc_stat);
+  if (L.pg_loops_cap > 0) c.down(*pg, L.pg_stat);
+  return c;
 }
 }  // namespace
 
@@ -1188,9 +1169,10 @@ int lm_host_map_move(LmHost* lm, const int* slots, int n, const double* T12, int
     tail[slots[i]] = std::min(L.K, st[AS_FRAMES]);   // the resident frames, as alego_lm_set_keypose accepts them
   }
   if (mv.empty()) return 0;
-  if (lm->mg_moves.reserve(mv.size()) != hipSuccess || hipMemcpy(lm->mg_moves.p, mv.data(), mv.size() * sizeof(MgMove), hipMemcpyHostToDevice) != hipSuccess) { *err = "map_move: upload failed"; return ALEGO_ERR_HIP; }
+  DevTry c("map_move", err, "upload");
+  if (c.took(lm->mg_moves.reserve(mv.size())).up(lm->mg_moves.p, mv)) return c;
   launch_mg_move(L, lm->mg_moves.p, (int)mv.size(), lm->st[0]);
-  if (hipStreamSynchronize(lm->st[0]) != hipSuccess) { *err = "map_move: pose write failed"; return ALEGO_ERR_HIP; }
+  if (c.at("pose write").wait(lm->st[0])) return c;
   return merge_rounds(lm, tail, "map_move", err);
 }
 
@@ -1220,8 +1202,7 @@ int lm_host_map_merge(LmHost* lm, PgCtx** pc, const int* src, const int* dst, in
     if (graph && ls + nx > 0) {
       std::vector<alego_graph_edge> sl((size_t)ls);
       std::vector<float> kp((size_t)(nx ? nd : 0) * KF_POSE_W);
-      if ((ls && hipMemcpy(sl.data(), L.pg_loops + (size_t)src[i] * L.pg_loops_cap, sl.size() * sizeof(alego_graph_edge), hipMemcpyDeviceToHost) != hipSuccess) ||
-          (!kp.empty() && hipMemcpy(kp.data(), arc_pose_of(L, dst[i], 0), kp.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)) { *err = "map_merge: device read failed"; return ALEGO_ERR_HIP; }
+      if (int r = DevTry("map_merge", err).down(sl, L.pg_loops + (size_t)src[i] * L.pg_loops_cap).down(kp, arc_pose_of(L, dst[i], 0))) return r;
       PgAppend a;
       std::memset(&a, 0, sizeof(a));
       a.slot = dst[i];
@@ -1254,13 +1235,13 @@ int lm_host_map_merge(LmHost* lm, PgCtx** pc, const int* src, const int* dst, in
   if (pairs.empty()) return 0;
   // ---- points, rows and edges, ring rows: three launches for all pairs
   hipStream_t st = lm->st[0];
-  if (lm->mg_pairs.reserve(pairs.size()) != hipSuccess || lm->mg_items.reserve(std::max<size_t>(items.size(), 1)) != hipSuccess ||
-      hipMemcpy(lm->mg_pairs.p, pairs.data(), pairs.size() * sizeof(MgPair), hipMemcpyHostToDevice) != hipSuccess ||
-      (!items.empty() && hipMemcpy(lm->mg_items.p, items.data(), items.size() * sizeof(int2), hipMemcpyHostToDevice) != hipSuccess)) { *err = "map_merge: upload failed"; return ALEGO_ERR_HIP; }
+  DevTry c("map_merge", err, "upload");
+  c.took(lm->mg_pairs.reserve(pairs.size())).took(lm->mg_items.reserve(std::max<size_t>(items.size(), 1)));
+  if (c.up(lm->mg_pairs.p, pairs).up(lm->mg_items.p, items)) return c;
   launch_mg_copy(L, lm->mg_pairs.p, lm->mg_items.p, (int)items.size(), st);
   launch_mg_frames(L, lm->mg_pairs.p, (int)pairs.size(), ns_max, st);
   launch_mg_ring(L, lm->mg_pairs.p, (int)pairs.size(), tail_max, st);
-  if (hipStreamSynchronize(st) != hipSuccess) { *err = "map_merge: append failed"; return ALEGO_ERR_HIP; }
+  if (c.at("append").wait(st)) return c;
   // ---- every ring row that now holds a source frame is transformed and sorted, oldest first
   if (int r = merge_rounds(lm, tail, "map_merge", err)) return r;
   return graph ? graph_append(pc, L, lm->n_slots, edges, st, err) : 0;
@@ -1284,10 +1265,10 @@ int thin_select(LmHost* lm, std::vector<ThJob>& jobs, std::vector<int>* cnt, con
   }
   hipStream_t st = lm->st[0];
   cnt->assign(4 * nj, 0);
-  if (hipMemcpy(lm->th_jobs.p, jobs.data(), nj * sizeof(ThJob), hipMemcpyHostToDevice) != hipSuccess) { *err = std::string(what) + ": upload failed"; return ALEGO_ERR_HIP; }
+  DevTry c(what, err);
+  if (c.up(lm->th_jobs.p, jobs)) return c;
   launch_th_select(lm->L, lm->th_jobs.p, (int)nj, st);
-  if (hipStreamSynchronize(st) != hipSuccess || hipMemcpy(cnt->data(), lm->th_ints.p, 4 * nj * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { *err = std::string(what) + ": the selection failed"; return ALEGO_ERR_HIP; }
-  return 0;
+  return c.at("the selection").wait(st).down(*cnt, lm->th_ints.p);
 }
 }  // namespace
 
@@ -1344,31 +1325,31 @@ int lm_host_map_thin(LmHost* lm, const int* slots, int n, double min_dist, alego
   hipStream_t st = lm->st[0];
   if (lm->th_items.reserve(std::max<size_t>(items.size(), 1)) != hipSuccess || lm->th_pts.reserve(std::max(stage_pt, 1)) != hipSuccess ||
       lm->th_rows.reserve(std::max(stage_row, 1)) != hipSuccess || lm->mg_pairs.reserve(ring.size()) != hipSuccess) { *err = "map_thin: allocation failed"; return ALEGO_ERR_HIP; }
-  if (hipMemcpy(lm->th_jobs.p, go.data(), go.size() * sizeof(ThJob), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(lm->mg_pairs.p, ring.data(), ring.size() * sizeof(MgPair), hipMemcpyHostToDevice) != hipSuccess ||
-      (!items.empty() && hipMemcpy(lm->th_items.p, items.data(), items.size() * sizeof(int2), hipMemcpyHostToDevice) != hipSuccess)) { *err = "map_thin: upload failed"; return ALEGO_ERR_HIP; }
+  DevTry c("map_thin", err);
+  if (c.up(lm->th_jobs.p, go).up(lm->mg_pairs.p, ring).up(lm->th_items.p, items)) return c;
   // ---- points and rows through the staging buffers (each read launch ends before its write launch starts), then the ring rows
   launch_th_gather(L, lm->th_jobs.p, lm->th_items.p, (int)items.size(), lm->th_pts.p, st);
   launch_th_rows_read(L, lm->th_jobs.p, (int)go.size(), rows_max, lm->th_rows.p, st);
   launch_th_scatter(L, lm->th_jobs.p, lm->th_items.p, (int)items.size(), lm->th_pts.p, st);
   launch_th_rows_write(L, lm->th_jobs.p, (int)go.size(), lanes_max, lm->th_rows.p, st);
   launch_mg_ring(L, lm->mg_pairs.p, (int)ring.size(), tail_max, st);
-  if (hipStreamSynchronize(st) != hipSuccess) { *err = "map_thin: compaction failed"; return ALEGO_ERR_HIP; }
+  if (c.at("compaction").wait(st)) return c;
   return merge_rounds(lm, tail, "map_thin", err);
 }
 
 int lm_host_debug_thin_select(LmHost* lm, const float* keyposes6, const uint8_t* protect, int n, double min_dist, uint8_t* keep, std::string* err) {
   if (n == 0) return 0;
-  if (lm->th_pose.reserve((size_t)n * 6) != hipSuccess || hipMemcpy(lm->th_pose.p, keyposes6, (size_t)n * 6 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { *err = "debug_thin_select: upload failed"; return ALEGO_ERR_HIP; }
+  DevTry c("debug_thin_select", err, "upload");
+  if (c.took(lm->th_pose.reserve((size_t)n * 6)).up(lm->th_pose.p, keyposes6, (size_t)n * 6)) return c;
   std::vector<ThJob> jobs(1);
   std::memset(&jobs[0], 0, sizeof(ThJob));
   jobs[0].pose = lm->th_pose.p; jobs[0].pose_stride = 6; jobs[0].n = n; jobs[0].slot = -1; jobs[0].r2 = th_r2(min_dist);
   // (the tables are laid out first, so that the caller's protect mask can go to its place before the launch)
-  if (lm->th_prot.reserve((size_t)n) != hipSuccess || hipMemcpy(lm->th_prot.p, protect, (size_t)n, hipMemcpyHostToDevice) != hipSuccess) { *err = "debug_thin_select: upload failed"; return ALEGO_ERR_HIP; }
+  if (c.took(lm->th_prot.reserve((size_t)n)).up(lm->th_prot.p, protect, (size_t)n)) return c;
   std::vector<int> cnt;
   if (int r = thin_select(lm, jobs, &cnt, "debug_thin_select", err)) return r;
   std::vector<int> id((size_t)n);
-  if (hipMemcpy(id.data(), jobs[0].new_id, (size_t)n * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { *err = "debug_thin_select: device read failed"; return ALEGO_ERR_HIP; }
+  if (c.at("device read").down(id, jobs[0].new_id)) return c;
   for (int i = 0; i < n; ++i) keep[i] = id[i] >= 0 ? 1 : 0;
   return cnt[0];
 }
@@ -1377,7 +1358,7 @@ int lm_host_map_get_keyframe(LmHost* lm, int slot, int id, alego_keyframe* out, 
   if (int r = map_stat(lm, slot, st, err)) return r;
   if (id < 0 || id >= st[AS_FRAMES]) { *err = "map_get_keyframe: frame not archived"; return ALEGO_ERR_ARG; }
   int tab[AT_W];
-  if (hipMemcpy(tab, arc_tab_of(lm->L, slot, id), sizeof(tab), hipMemcpyDeviceToHost) != hipSuccess) { *err = "map_get_keyframe: copy failed"; return ALEGO_ERR_HIP; }
+  if (int r = DevTry("map_get_keyframe", err, "copy").down(tab, arc_tab_of(lm->L, slot, id))) return r;
   const KfArcFrame A = kf_arc_frame(lm->L, slot, id, tab);
   const float4* const src[KF_KINDS] = {A.pts, A.pts + A.nc, A.pts + A.nc + A.ns};
   return frame_to_host("map_get_keyframe", id, A.pose, tab + AT_N, src, out, err);
@@ -1386,18 +1367,19 @@ int lm_host_map_get_keyframe(LmHost* lm, int slot, int id, alego_keyframe* out, 
 static int copy_out(const float4* src, int n, alego_point* out, int cap, const char* what, std::string* err) {
   if (!out && cap == 0) return n;
   if (cap < n || (n > 0 && !out)) { *err = std::string(what) + ": output capacity"; return ALEGO_ERR_CAPACITY; }
-  if (n > 0 && hipMemcpy(out, src, (size_t)n * 16, hipMemcpyDeviceToHost) != hipSuccess) { *err = std::string(what) + ": copy failed"; return ALEGO_ERR_HIP; }
+  if (int r = DevTry(what, err, "copy").down(out, src, (size_t)std::max(n, 0))) return r;
   return n;
 }
 // the cloud the launches on `s` leave in gv.in, its size in gv.cnt[0], to the caller: as it is (leaf <= 0) or through the device-wide VoxelGrid
 static int assembled_out(LmHost* lm, hipStream_t s, float leaf, alego_point* out, int cap, const char* what, std::string* err) {
   GvCtx& G = lm->gv;
   int n = 0;
-  if (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(&n, G.cnt, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { *err = std::string(what) + ": assembly failed"; return ALEGO_ERR_HIP; }
+  DevTry c(what, err, "assembly");
+  if (c.wait(s).down(&n, G.cnt, 1)) return c;
   if (leaf <= 0.f) return copy_out(G.in, n, out, cap, what, err);
   if (int r = gv_filter(&G, n, leaf, s, err)) return r == -3 ? ALEGO_ERR_CAPACITY : ALEGO_ERR_HIP;
   int m = 0;
-  if (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(&m, G.cnt + 1, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { *err = std::string(what) + ": VoxelGrid failed"; return ALEGO_ERR_HIP; }
+  if (c.at("VoxelGrid").wait(s).down(&m, G.cnt + 1, 1)) return c;
   return copy_out(G.out, m, out, cap, what, err);
 }
 int lm_host_map_assemble(LmHost* lm, int slot, int kinds, float leaf, alego_point* out, int cap, std::string* err) {
@@ -1417,7 +1399,7 @@ int lm_host_map_keyposes(LmHost* lm, int slot, alego_point* out, int cap, std::s
   if (!out && cap == 0) return nf;
   if (cap < nf || (nf > 0 && !out)) { *err = "map_keyposes: output capacity"; return ALEGO_ERR_CAPACITY; }
   std::vector<float> kp((size_t)nf * KF_POSE_W);
-  if (nf > 0 && hipMemcpy(kp.data(), arc_pose_of(lm->L, slot, 0), kp.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) { *err = "map_keyposes: copy failed"; return ALEGO_ERR_HIP; }
+  if (int r = DevTry("map_keyposes", err, "copy").down(kp, arc_pose_of(lm->L, slot, 0))) return r;
   for (int i = 0; i < nf; ++i) out[i] = alego_point{kp[(size_t)i * KF_POSE_W + 0], kp[(size_t)i * KF_POSE_W + 1], kp[(size_t)i * KF_POSE_W + 2], (float)i};   // saveMapCB :833-838
   return nf;
 }
@@ -1438,23 +1420,21 @@ int lm_host_occ_enable(LmHost* lm, const alego_occ_opts* opts, std::string* err)
 int lm_host_occ_set_piece(LmHost* lm, int piece) { lm->occ_piece = piece; return 0; }
 int lm_host_occ_clear(LmHost* lm, std::string* err) {
   launch_occ_clear(lm->occ, lm->st[0]);
-  if (hipStreamSynchronize(lm->st[0]) != hipSuccess) { *err = "occ_clear: clearing failed"; return ALEGO_ERR_HIP; }
-  return 0;
+  return DevTry("occ_clear", err, "clearing").wait(lm->st[0]);
 }
 // the work list of frames [first, first + n) of `slot` (n > 0) in lm->occ_items: (frame, chunk of OCC_T selected points), frames ascending; returns the
 // items (0: no point is selected) or an error
 static int occ_work_items(LmHost* lm, int slot, int first, int n, int kinds, const char* what, std::string* err) {
   const LmCtx& L = lm->L;
   std::vector<int> tab((size_t)n * AT_W);
-  if (hipMemcpy(tab.data(), arc_tab_of(L, slot, first), tab.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { *err = std::string(what) + ": device read failed"; return ALEGO_ERR_HIP; }
+  DevTry c(what, err);
+  if (c.down(tab, arc_tab_of(L, slot, first))) return c;
   std::vector<int2> items;
   for (int f = 0; f < n; ++f) {
     const int sel = kf_sel_count(kf_arc_frame(L, slot, first + f, tab.data() + (size_t)f * AT_W), kinds);
     for (int c = 0; c * OCC_T < sel; ++c) items.push_back(make_int2(first + f, c));
   }
-  if (items.empty()) return 0;
-  if (lm->occ_items.reserve(items.size()) != hipSuccess) { *err = std::string(what) + ": allocation failed"; return ALEGO_ERR_HIP; }
-  if (hipMemcpy(lm->occ_items.p, items.data(), items.size() * sizeof(int2), hipMemcpyHostToDevice) != hipSuccess) { *err = std::string(what) + ": upload failed"; return ALEGO_ERR_HIP; }
+  if (c.took(lm->occ_items.reserve(items.size())).up(lm->occ_items.p, items)) return c;
   return (int)items.size();
 }
 int lm_host_occ_integrate(LmHost* lm, int slot, int first, int n, int kinds, int64_t* stats, std::string* err) {
@@ -1474,29 +1454,30 @@ int lm_host_occ_integrate(LmHost* lm, int slot, int first, int n, int kinds, int
   if (hipMemsetAsync(lm->occ.stats, 0, ALEGO_OCC_STATS * sizeof(unsigned long long), s) != hipSuccess) { *err = "occ_integrate: upload failed"; return ALEGO_ERR_HIP; }
   launch_occ_cast(L, lm->occ, slot, kinds, lm->occ_items.p, n_items, lm->occ_piece, s);
   unsigned long long got[ALEGO_OCC_STATS];
-  if (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(got, lm->occ.stats, sizeof(got), hipMemcpyDeviceToHost) != hipSuccess) { *err = "occ_integrate: ray casting failed"; return ALEGO_ERR_HIP; }
+  if (int r = DevTry("occ_integrate", err, "ray casting").wait(s).down(got, lm->occ.stats)) return r;
   if (stats) for (int k = 0; k < ALEGO_OCC_STATS; ++k) stats[k] = (int64_t)got[k];
   return 0;
 }
 int lm_host_occ_get(LmHost* lm, uint32_t* hits, uint32_t* passes, std::string* err) {
-  const size_t bytes = occ_cells(lm->occ.G) * sizeof(uint32_t);
-  if ((hits && hipMemcpy(hits, lm->occ.hits, bytes, hipMemcpyDeviceToHost) != hipSuccess) ||
-      (passes && hipMemcpy(passes, lm->occ.passes, bytes, hipMemcpyDeviceToHost) != hipSuccess)) { *err = "occ_get: copy failed"; return ALEGO_ERR_HIP; }
-  return 0;
+  const size_t cells = occ_cells(lm->occ.G);
+  DevTry c("occ_get", err, "copy");
+  if (hits) c.down(hits, lm->occ.hits, cells);
+  if (passes) c.down(passes, lm->occ.passes, cells);
+  return c;
 }
 int lm_host_occ_classify(LmHost* lm, const alego_occ_rule& rule, int collapse_z, int8_t* out, std::string* err) {
   const OccGrid& G = lm->occ.G;
   const size_t n_out = collapse_z ? (size_t)G.n[0] * G.n[1] : occ_cells(G);
   if (lm->occ_cls.reserve(n_out) != hipSuccess) { *err = "occ_classify: allocation failed"; return ALEGO_ERR_HIP; }
   launch_occ_classify(lm->occ, rule, collapse_z, lm->occ_cls.p, lm->st[0]);
-  if (hipStreamSynchronize(lm->st[0]) != hipSuccess || hipMemcpy(out, lm->occ_cls.p, n_out, hipMemcpyDeviceToHost) != hipSuccess) { *err = "occ_classify: classification failed"; return ALEGO_ERR_HIP; }
-  return 0;
+  return DevTry("occ_classify", err, "classification").wait(lm->st[0]).down(out, lm->occ_cls.p, n_out);
 }
 int lm_host_occ_set(LmHost* lm, const uint32_t* hits, const uint32_t* passes, std::string* err) {
-  const size_t bytes = occ_cells(lm->occ.G) * sizeof(uint32_t);
-  if ((hits && hipMemcpy(lm->occ.hits, hits, bytes, hipMemcpyHostToDevice) != hipSuccess) ||
-      (passes && hipMemcpy(lm->occ.passes, passes, bytes, hipMemcpyHostToDevice) != hipSuccess)) { *err = "occ_set: copy failed"; return ALEGO_ERR_HIP; }
-  return 0;
+  const size_t cells = occ_cells(lm->occ.G);
+  DevTry c("occ_set", err, "copy");
+  if (hits) c.up(lm->occ.hits, hits, cells);
+  if (passes) c.up(lm->occ.passes, passes, cells);
+  return c;
 }
 // ---- the clearance field and the cost map (alego_occ_distance / alego_occ_costmap; kernels_edt.hip) ----
 // Classifies and enqueues the transform on st[0]; *d2 is the device array that will hold the result, dom the domain.  Nothing is awaited.
@@ -1518,15 +1499,16 @@ static int edt_enqueue(LmHost* lm, const alego_occ_rule& rule, int collapse_z, i
 }
 static int edt_stats_out(LmHost* lm, int64_t* stats, const char* what, std::string* err) {
   unsigned long long got[ALEGO_EDT_STATS];
-  if (hipMemcpy(got, lm->edt_stats.p, sizeof(got), hipMemcpyDeviceToHost) != hipSuccess) { *err = std::string(what) + ": copy failed"; return ALEGO_ERR_HIP; }
+  if (int r = DevTry(what, err, "copy").down(got, lm->edt_stats.p)) return r;
   if (stats) { stats[ALEGO_EDT_SOURCES] = (int64_t)got[ALEGO_EDT_SOURCES]; stats[ALEGO_EDT_FAR_CELLS] = (int64_t)got[ALEGO_EDT_FAR_CELLS]; stats[ALEGO_EDT_MAX_D2] = (int64_t)got[ALEGO_EDT_MAX_D2] - 1; }
   return 0;
 }
 int lm_host_occ_distance(LmHost* lm, const alego_occ_rule& rule, const alego_occ_dist_opts& o, uint32_t* d2, int64_t* stats, std::string* err) {
   int32_t dom[3]; double s; uint32_t* dev = nullptr;
   if (int r = edt_enqueue(lm, rule, o.collapse_z, o.unknown_is_obstacle, o.max_cells, "occ_distance", dom, &s, &dev, err)) return r;
-  if (hipStreamSynchronize(lm->st[0]) != hipSuccess) { *err = "occ_distance: the transform failed"; return ALEGO_ERR_HIP; }
-  if (d2 && hipMemcpy(d2, dev, (size_t)dom[0] * dom[1] * dom[2] * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) { *err = "occ_distance: copy failed"; return ALEGO_ERR_HIP; }
+  DevTry c("occ_distance", err, "the transform");
+  if (c.wait(lm->st[0])) return c;
+  if (d2 && c.at("copy").down(d2, dev, (size_t)dom[0] * dom[1] * dom[2])) return c;
   return stats ? edt_stats_out(lm, stats, "occ_distance", err) : 0;
 }
 int lm_host_occ_costmap(LmHost* lm, const alego_occ_rule& rule, int collapse_z, int unknown_is_obstacle, const alego_occ_inflation& infl, uint8_t* out, std::string* err) {
@@ -1540,12 +1522,12 @@ int lm_host_occ_costmap(LmHost* lm, const alego_occ_rule& rule, int collapse_z, 
   edt_cost_table(s, &infl, r, table.data());
   const size_t cells = (size_t)dom[0] * dom[1] * dom[2];
   if (lm->edt_table.reserve(table.size()) != hipSuccess || lm->edt_cost.reserve(cells) != hipSuccess) { *err = "occ_costmap: allocation failed"; return ALEGO_ERR_HIP; }
-  if (hipMemcpy(lm->edt_table.p, table.data(), table.size(), hipMemcpyHostToDevice) != hipSuccess) { *err = "occ_costmap: upload failed"; return ALEGO_ERR_HIP; }
+  DevTry c("occ_costmap", err);
+  if (c.up(lm->edt_table.p, table)) return c;
   uint32_t* dev = nullptr;
   if (int rc = edt_enqueue(lm, rule, collapse_z, unknown_is_obstacle, r, "occ_costmap", dom, &s, &dev, err)) return rc;
   launch_edt_cost(lm->occ_cls.p, dev, cells, unknown_is_obstacle ? 1 : 0, lm->edt_table.p, (int)table.size(), infl.inflate_unknown ? 1 : 0, lm->edt_cost.p, lm->st[0]);
-  if (hipStreamSynchronize(lm->st[0]) != hipSuccess || hipMemcpy(out, lm->edt_cost.p, cells, hipMemcpyDeviceToHost) != hipSuccess) { *err = "occ_costmap: the cost map failed"; return ALEGO_ERR_HIP; }
-  return 0;
+  return c.at("the cost map").wait(lm->st[0]).down(out, lm->edt_cost.p, cells);
 }
 // ---- the static map (alego_occ_mark / alego_map_assemble_static; kernels_occ.hip) ----
 // Enqueues map_offsets and occ_mark over every frame of `slot` on its stream: verdicts in lm->st_verdict, transformed points in gv.out, both in
@@ -1562,7 +1544,7 @@ static int static_mark(LmHost* lm, int slot, int kinds, const alego_static_rule&
   hipStream_t s = stream_of_slot(lm, slot);
   launch_map_offsets(L, slot, nf, kinds & KF_SEL_ALL, lm->arc_off, G.cnt, s);
   int n = 0;
-  if (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(&n, G.cnt, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { *err = std::string(what) + ": offsets failed"; return ALEGO_ERR_HIP; }
+  if (int r = DevTry(what, err, "offsets").wait(s).down(&n, G.cnt, 1)) return r;
   if (n < 0 || n > G.cap) { *err = std::string(what) + ": the archive holds more points than its capacity"; return ALEGO_ERR_HIP; }
   if (limit >= 0 && n > limit) { *err = std::string(what) + ": output capacity"; return ALEGO_ERR_CAPACITY; }
   if (lm->st_verdict.reserve(std::max(n, 1)) != hipSuccess || lm->st_kept.reserve(std::max(n_items, 1)) != hipSuccess ||
@@ -1574,7 +1556,7 @@ static int static_mark(LmHost* lm, int slot, int kinds, const alego_static_rule&
 }
 static int static_stats(LmHost* lm, int64_t* stats, const char* what, std::string* err) {
   unsigned long long got[ALEGO_STATIC_VERDICTS];
-  if (hipMemcpy(got, lm->st_stats.p, sizeof(got), hipMemcpyDeviceToHost) != hipSuccess) { *err = std::string(what) + ": device read failed"; return ALEGO_ERR_HIP; }
+  if (int r = DevTry(what, err).down(got, lm->st_stats.p)) return r;
   if (stats) for (int k = 0; k < ALEGO_STATIC_VERDICTS; ++k) stats[k] = (int64_t)got[k];
   return 0;
 }
@@ -1585,9 +1567,10 @@ int lm_host_occ_mark(LmHost* lm, int slot, int kinds, const alego_static_rule& r
   OccStatic S;
   int n = 0;
   if (int r = static_mark(lm, slot, kinds, rule, count_only ? -1 : cap, "occ_mark", &S, &n, err)) return r;
-  if (hipStreamSynchronize(stream_of_slot(lm, slot)) != hipSuccess) { *err = "occ_mark: marking failed"; return ALEGO_ERR_HIP; }
+  DevTry c("occ_mark", err, "marking");
+  if (c.wait(stream_of_slot(lm, slot))) return c;
   if (int r = static_stats(lm, stats, "occ_mark", err)) return r;
-  if (!count_only && n > 0 && hipMemcpy(verdict, S.verdict, (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) { *err = "occ_mark: copy failed"; return ALEGO_ERR_HIP; }
+  if (!count_only && c.at("copy").down(verdict, S.verdict, (size_t)n)) return c;
   return n;
 }
 int lm_host_map_assemble_static(LmHost* lm, int slot, int kinds, float leaf, const alego_static_rule& rule, alego_point* out, int cap, int64_t* stats, std::string* err) {
@@ -1599,32 +1582,31 @@ int lm_host_map_assemble_static(LmHost* lm, int slot, int kinds, float leaf, con
   hipStream_t s = stream_of_slot(lm, slot);
   GvCtx& G = lm->gv;
   launch_occ_emit(S, kinds, G.in, G.cap, G.cnt, s);   // the kept points end where gv_filter reads its input
-  if (hipStreamSynchronize(s) != hipSuccess) { *err = "map_assemble_static: compaction failed"; return ALEGO_ERR_HIP; }
+  if (int r = DevTry("map_assemble_static", err, "compaction").wait(s)) return r;
   if (int r = static_stats(lm, stats, "map_assemble_static", err)) return r;
   return assembled_out(lm, s, leaf, out, cap, "map_assemble_static", err);
 }
 int lm_host_get_local_map(LmHost* lm, int slot, alego_point* corner, int corner_cap, alego_point* surf, int surf_cap, int* n_out, std::string* err) {
   const LmCtx& L = lm->L;
   int li[LI_COUNT];
-  if (hipStreamSynchronize(stream_of_slot(lm, slot)) != hipSuccess || hipMemcpy(li, L.li + (size_t)slot * LI_COUNT, sizeof(li), hipMemcpyDeviceToHost) != hipSuccess) { *err = "get_local_map: device read failed"; return ALEGO_ERR_HIP; }
+  DevTry c("get_local_map", err, "device read");
+  if (c.wait(stream_of_slot(lm, slot)).down(li, L.li + (size_t)slot * LI_COUNT)) return c;
   const int nc = li[LI_KDS_C], ns = li[LI_KDS_S];
   n_out[0] = nc; n_out[1] = ns;
   if ((corner && nc > corner_cap) || (surf && ns > surf_cap)) { *err = "get_local_map: buffer too small"; return ALEGO_ERR_CAPACITY; }
-  hipError_t e = hipSuccess;
-  if (corner && nc) e = hipMemcpy(corner, L.map_corner_ds + (size_t)slot * L.map_cap_c, (size_t)nc * 16, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && surf && ns) e = hipMemcpy(surf, L.map_surf_ds + (size_t)slot * L.map_cap_s, (size_t)ns * 16, hipMemcpyDeviceToHost);
-  if (e != hipSuccess) { *err = std::string("get_local_map: ") + hipGetErrorString(e); return ALEGO_ERR_HIP; }
-  return 0;
+  if (corner) c.down(corner, L.map_corner_ds + (size_t)slot * L.map_cap_c, (size_t)nc);
+  if (surf) c.down(surf, L.map_surf_ds + (size_t)slot * L.map_cap_s, (size_t)ns);
+  return c;
 }
 int lm_host_voxel_grid(LmHost* lm, hipStream_t s, const alego_point* pts, int n, float leaf, alego_point* out, int cap, std::string* err) {
   GvCtx& G = lm->gv;
   if (n == 0) return copy_out(G.out, 0, out, cap, "voxel_grid", err);
   if (int r = gv_reserve(&G, n, err)) return r == -3 ? ALEGO_ERR_CAPACITY : ALEGO_ERR_HIP;
-  if (hipMemcpyAsync(G.in, pts, (size_t)n * 16, hipMemcpyHostToDevice, s) != hipSuccess || hipMemcpyAsync(G.cnt, &n, sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess ||
-      hipStreamSynchronize(s) != hipSuccess) { *err = "voxel_grid: upload failed"; return ALEGO_ERR_HIP; }
+  DevTry c("voxel_grid", err, "upload");
+  if (c.up(G.in, pts, (size_t)n, s).up(G.cnt, &n, 1, s).wait(s)) return c;
   if (int r = gv_filter(&G, n, leaf, s, err)) return r == -3 ? ALEGO_ERR_CAPACITY : ALEGO_ERR_HIP;
   int m = 0;
-  if (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(&m, G.cnt + 1, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) { *err = "voxel_grid: filter failed"; return ALEGO_ERR_HIP; }
+  if (c.at("filter").wait(s).down(&m, G.cnt + 1, 1)) return c;
   return copy_out(G.out, m, out, cap, "voxel_grid", err);
 }
 int lm_host_set_gv_small_max(LmHost* lm, int v) {

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/alego_mi355x.h"
+#include "dev_copy.h"
 #include "dev_mem.h"
 #include "kf_store.h"
 #include "pg_chain.h"
@@ -77,21 +78,16 @@ struct PgPlan {
     return C->buf.reserve(layout(nullptr, chunk));
   }
 };
-// the control words of a chunk on the host ([S][PC_COUNT], zero before): entry q's graph and candidates; then their way to the device
+// the control words of a chunk on the host ([S][PC_COUNT], zero before): entry q's graph and candidates (the whole vector then goes to PgWork::ctl)
 inline void pg_ctl_entry(std::vector<int>* ctl, int q, int N, int NL, int slot, int NC = 0, int NU = 0) {
   int* w = ctl->data() + (size_t)q * PC_COUNT;
   w[PC_N] = N; w[PC_NL] = NL; w[PC_SLOT] = slot; w[PC_NC] = NC; w[PC_NU] = NU;
-}
-inline hipError_t pg_ctl_upload(const PgWork& W, const std::vector<int>& ctl, hipStream_t st) {
-  return hipMemcpyAsync(W.ctl, ctl.data(), ctl.size() * sizeof(int), hipMemcpyHostToDevice, st);
 }
 inline int pg_fail(std::string* err, const char* msg, int rc) { *err = msg; return rc; }
 // the counters of every slot: arc = LmCtx::arc_stat, pg = LmCtx::pg_stat
 inline int pg_read_stats(const LmCtx& L, int n_slots, std::vector<int>* arc, std::vector<int>* pg, std::string* err) {
   arc->resize((size_t)n_slots * AS_W); pg->resize((size_t)n_slots * PS_W);
-  if (hipMemcpy(arc->data(), L.arc_stat, arc->size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
-      hipMemcpy(pg->data(), L.pg_stat, pg->size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return pg_fail(err, "graph: device read failed", ALEGO_ERR_HIP);
-  return 0;
+  return DevTry("graph", err).down(*arc, L.arc_stat).down(*pg, L.pg_stat);
 }
 
 // pg_init -> pg_linearize -> pg_assemble -> pg_factor_chain -> pg_solve once for the S entries of W (kernels_graph.hip): leaves the factor of
